@@ -26,6 +26,22 @@ Launching:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N            # as the ranks of an external launcher: always the torch form
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, ms_per_step, the workload's
+counts).  --full adds everything else the benchmark measures or checks, each outside the timed region: the stage
+breakdown and roofline of the dominant kernel, single-shot contexts, the ABI fetch, the end-to-end command-line run, the
+one-GPU run of a sharded job, the CPU baseline with its parity gate and calibration, and --check.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's view), float64 .npy files:
+  summary.npy   [n_pass1, n_pass2, n_tokens, n_groups, n_patterns, then sums over ALL records: read index, low_lexi,
+                 token, repeat length, n_ss, ss positions; sums over all tokens / patterns: lengths, bytes, pattern group]
+  records.npy   [k, 7] a fixed seeded sample of the pass-1 + pass-2 records (pass-1 first, as a caller receives them):
+                 record index, read index, low_lexi, token, repeat length, n_ss, pass (1 / 2)
+  records_ss.npy [k, S] those records' spacer / repeat positions, -1 past n_ss
+  tokens.npy    [t, 2 + Lmax] token index, length, bytes (0 past the length); every token, or a seeded sample
+  groups.npy    [g, 2] (group index, token) for every member of every group, or a seeded sample
+  patterns.npy  [p, 3 + Lmax] pattern index, pattern group, length, bytes; every pattern, or a seeded sample
+The samples shrink until the files hold at most 64 MB together.
 """
 import argparse
 import hashlib
@@ -66,14 +82,18 @@ def parse():
     ap.add_argument("--read-len", type=int, default=0)
     ap.add_argument("--n-dr", type=int, default=0)
     ap.add_argument("--gc-classes", type=int, default=-1)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure (roofline, "
+                    "single shots, ABI fetch, end to end, one-GPU base of a sharded job, CPU baseline + parity gate); off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's results to DIR/<name>.npy (float64, "
+                    "at most 64 MB; a fixed seeded sample of larger outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: reads timed on the CPU baseline (0 = skip)")
     ap.add_argument("--no-strong-base", action="store_true",
-                    help="N>1 strong scaling: skip the untimed one-GPU run of the whole job on rank 0 (speedup_vs_1gpu)")
+                    help="--full, N>1 strong scaling: skip the untimed one-GPU run of the whole job on rank 0 (speedup_vs_1gpu)")
     ap.add_argument("--alternate", action="store_true", help="alternate between two resident batches (speculation bounds "
                     "are then learnt from a different batch than the one being processed)")
-    ap.add_argument("--single-shots", type=int, default=3, help="N=1: fresh contexts timed for single_shot_ms (0 = skip)")
-    ap.add_argument("--check", action="store_true", help="also verify the GPU result against the oracle on the CPU sample")
-    ap.add_argument("--e2e-reads", type=int, default=-1, help="N=1: reads of the end-to-end command-line run reported as e2e_reads_per_s "
+    ap.add_argument("--single-shots", type=int, default=-1, help="--full, N=1: fresh contexts timed for single_shot_ms (default 3; 0 = skip)")
+    ap.add_argument("--check", action="store_true", help="--full: also verify the GPU result against the oracle on the CPU sample")
+    ap.add_argument("--e2e-reads", type=int, default=-1, help="--full, N=1: reads of the end-to-end command-line run reported as e2e_reads_per_s "
                                                               "(FASTA in tmpfs -> crass-hip -> output files; default for 150 bp configs: 50 M where the host has the memory, else 5 M; 0 = skip)")
     ap.add_argument("--launcher", default="group", choices=["group", "torch"],
                     help="N>1 from a plain interpreter: group = one process drives N contexts through crass_hip_group_* (C++ RCCL); "
@@ -84,7 +104,14 @@ def parse():
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
     ap.add_argument("--params", default="", help="crass options other than the defaults, as on crass's command line: d=20,D=40 / w=7 / s=20,S=60 / n=3 / k=5 "
                                                   "(what a user of -d/-D/-s/-S/-w/-n gets: the fast filter and the position hints are built for the defaults)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.check or args.cpu_sample > 0 or args.single_shots > 0 or args.e2e_reads > 0):
+        ap.error("--check, --cpu-sample, --single-shots and --e2e-reads measure beyond the headline figure: add --full")
+    if args.single_shots < 0:
+        args.single_shots = 3
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -182,7 +209,7 @@ def main():
     #      and no pinned buffers of its own: what a user of `crass-hip` gets.  (Run behind the timed steps, beside this process's
     #      resident engine, the same child took 2.0 s instead of 1.6-1.7: profiles/NOTES_r06.md.) ----
     e2e_early = None
-    if world == 1 and not group_mode and rank == 0 and torch.cuda.device_count() > 0:      # (counting devices does not initialise one)
+    if args.full and world == 1 and not group_mode and rank == 0 and torch.cuda.device_count() > 0:      # (counting devices does not initialise one)
         e2e_n = args.e2e_reads if args.e2e_reads >= 0 else (_e2e_default_reads(L) if L <= 300 and not custom else 0)
         if e2e_n > 0:
             e2e_early = _e2e_cli(ca, spec, L, min(e2e_n, total))
@@ -280,33 +307,36 @@ def main():
     first_call_ms = (time.perf_counter() - t0) * 1e3
     for _ in range(max(0, args.warmup - 1)):
         step()
-    # untimed scouting steps with every stage timed (level 2): the stage breakdown, and which of the three large
-    # kernels is the dominant one
-    eng.set_stage_timing(2)
-    scout_keys = ("ms_filter", "ms_survivor", "ms_recruit", "ms_compact", "ms_pass1_total", "ms_merge_device", "ms_recruit_finish",
-                  "ms_pass2_total")
-    scout = {k: [] for k in scout_keys}
-    for _ in range(3):
-        step()
-        cs = eng.counters()
-        for k in scout:
-            scout[k].append(cs[k])
-    scout = {k: float(np.mean(v)) for k, v in scout.items()}
-    stages = {k: round(scout[k], 4) for k in ("ms_compact", "ms_pass1_total", "ms_merge_device", "ms_recruit_finish", "ms_pass2_total")}
-    names = {"seed_scan_filter": ("ms_filter", 1), "survivor": ("ms_survivor", 2), "recruit_scan": ("ms_recruit", 4)}
-    dom = max(names, key=lambda k: scout[names[k][0]])
-    # timed region: HIP events around the dominant kernel only (level 1 with a focus: every event record costs ~6 us
-    # of stream time, and the other two kernels' durations are reported from the scouting steps)
-    eng.set_stage_timing(1)
-    eng.set_timing_focus(names[dom][1])
+    kern = {}
+    if args.full:
+        # untimed scouting steps with every stage timed (level 2): the stage breakdown, and which of the three large
+        # kernels is the dominant one
+        eng.set_stage_timing(2)
+        scout_keys = ("ms_filter", "ms_survivor", "ms_recruit", "ms_compact", "ms_pass1_total", "ms_merge_device", "ms_recruit_finish",
+                      "ms_pass2_total")
+        scout = {k: [] for k in scout_keys}
+        for _ in range(3):
+            step()
+            cs = eng.counters()
+            for k in scout:
+                scout[k].append(cs[k])
+        scout = {k: float(np.mean(v)) for k, v in scout.items()}
+        stages = {k: round(scout[k], 4) for k in ("ms_compact", "ms_pass1_total", "ms_merge_device", "ms_recruit_finish", "ms_pass2_total")}
+        names = {"seed_scan_filter": ("ms_filter", 1), "survivor": ("ms_survivor", 2), "recruit_scan": ("ms_recruit", 4)}
+        dom = max(names, key=lambda k: scout[names[k][0]])
+        # timed region: HIP events around the dominant kernel only (level 1 with a focus: every event record costs ~6 us
+        # of stream time, and the other two kernels' durations are reported from the scouting steps)
+        eng.set_stage_timing(1)
+        eng.set_timing_focus(names[dom][1])
+        if args.alternate:
+            eng_b.set_stage_timing(1)
+            eng_b.set_timing_focus(names[dom][1])
+        kern = {names[dom][0]: [], "ms_merge_host": [], "ms_sink_host": []}
     if args.alternate:
-        eng_b.set_stage_timing(1)
-        eng_b.set_timing_focus(names[dom][1])
         for _ in range(2):
             step(eng_b)
     for _ in range(2):                                   # (settle into the timed configuration)
         step()
-    kern = {names[dom][0]: [], "ms_merge_host": [], "ms_sink_host": []}
     import gc
     gc.collect()
     gc.disable()                                         # (no collector pauses inside the timed region)
@@ -317,15 +347,20 @@ def main():
     for it in range(args.steps):
         e = eng_b if (args.alternate and it & 1) else eng
         step(e)
-        c = e.counters()
-        for k in kern:
-            kern[k].append(c[k])
+        if kern:
+            c = e.counters()
+            for k in kern:
+                kern[k].append(c[k])
         step_marks[it + 1] = time.perf_counter()
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
     per_step = np.diff(np.asarray(step_marks)) * 1e3
-    eng.set_timing_focus(7)
+    dumped = None
+    if args.dump_outputs and rank == 0:                  # (before anything else steps the engines)
+        dumped = _dump_outputs(ca, e, args.dump_outputs)
+    if args.full:
+        eng.set_timing_focus(7)
     tot_p1, tot_p2 = None, None
     c = eng.counters()
     rccl_ranks = None
@@ -345,57 +380,59 @@ def main():
     ms_per_step = dt * 1e3 / args.steps
     value = total * args.steps / dt if not args.reads else world * n * args.steps / dt
 
-    # ---- roofline of the dominant kernel (HIP events on the engine's stream, see engine.cpp) ----
-    avg = {k: float(np.mean(v)) for k, v in kern.items()}
-    bytes_per_read_per_pass = (L + 3) // 4               # ceil(L/4) B per read per pass
-    dom_ms = avg[names[dom][0]]                          # HIP events over the timed region
     n_surv = c["n_filter_survivors"]
-    if dom == "survivor":
-        alg_bytes = n_surv * bytes_per_read_per_pass
-    else:
-        alg_bytes = n * bytes_per_read_per_pass
-    achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    # per-kernel view (the two streaming kernels touch every read; the survivor kernel only the reads that
-    # survive the filter, so for short reads its algorithmic bytes are tiny and it is issue bound by nature)
-    per_kernel = {}
-    for name, units in (("seed_scan_filter", n), ("survivor", n_surv), ("recruit_scan", n)):
-        ms = dom_ms if name == dom else scout[names[name][0]]
-        b = units * bytes_per_read_per_pass
-        gbs = b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-        per_kernel[name] = {"avg_launch_ms": round(ms, 4), "algorithmic_bytes": int(b), "achieved_GBps": round(gbs, 1),
-                            "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 5),
-                            "measured_in": "timed steps" if name == dom else "scouting steps (untimed)"}
-    # HBM bytes per launch of the dominant kernel from the rocprofv3 PMC passes committed under profiles/ — only when
-    # they were taken on THIS kernel source (hash recorded by profiles/summarize_pmc.py) and this workload
-    traffic, traffic_src, valu_issue = None, None, None
-    try:
-        pm = _pmc_file(n, L)
-        # (the seed-scan stage is k_filter_fast_impl for short uniform reads, k_hint_positions for long ones, else k_filter_general)
-        keys = {"seed_scan_filter": ("k_filter_fast", "k_hint_positions", "k_filter_general"), "survivor": ("k_survivor",),
-                "recruit_scan": ("k_anchor_filter",)}[dom]
-        if pm and pm.get("source_hash") == source_hash() and pm.get("reads") == n and pm.get("read_len") == L:
-            for k, v in sorted(pm["per_launch"].items(), key=lambda kv: -kv[1].get("hbm_bytes", 0)):
-                if traffic is None and k.startswith(keys):
-                    traffic, traffic_src = v["hbm_bytes"], "profiles/%s (committed PMC passes, same kernel source hash)" % pm["_file"]
-                    if "sq" in v and v["sq"].get("SQ_INSTS_VALU"):
-                        # what actually bounds this kernel: a wave64 VALU instruction occupies its SIMD for 4 cycles, the chip
-                        # has 256 CUs x 4 SIMDs and holds at most 2.4 GHz (MI355X_MICROARCH.md)
-                        insts = v["sq"]["SQ_INSTS_VALU"]
-                        bound_ms = insts * 4.0 / (256 * 4) / 2.4e9 * 1e3
-                        valu_issue = {"insts_valu_per_launch": int(insts), "cycles_per_wave64_inst": 4, "simds": 1024, "clock_ghz": 2.4,
-                                      "bound_ms": round(bound_ms, 4), "frac": round(bound_ms / dom_ms, 4) if dom_ms > 0 else None,
-                                      "note": "the kernel is VALU-issue bound, not HBM bound: frac = VALU issue time at peak clock / measured launch time"}
-    except (OSError, KeyError, ValueError, TypeError):
-        pass
-    path_bytes = 2 * bytes_per_read_per_pass             # both passes read every base once at 2 bits
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "valu_issue": valu_issue,
-                "path_frac": round(value / n_gpus * path_bytes / (HBM_PEAK_GBS * 1e9), 5),
-                "path_frac_note": "whole path per GPU: reads/s/GPU x %d B / 8 TB/s (SURVEY 8d)" % path_bytes,
-                "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(dom_ms, 4),
-                "per_kernel": per_kernel, "host_ms": {"merge": round(avg["ms_merge_host"], 3), "sink": round(avg["ms_sink_host"], 3)},
-                "merge_device_ms": stages["ms_merge_device"], "device_merge": int(c.get("used_device_merge", 0)),
-                "stages_ms_scouting_steps": stages}
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel (HIP events on the engine's stream, see engine.cpp) ----
+        avg = {k: float(np.mean(v)) for k, v in kern.items()}
+        bytes_per_read_per_pass = (L + 3) // 4               # ceil(L/4) B per read per pass
+        dom_ms = avg[names[dom][0]]                          # HIP events over the timed region
+        if dom == "survivor":
+            alg_bytes = n_surv * bytes_per_read_per_pass
+        else:
+            alg_bytes = n * bytes_per_read_per_pass
+        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        # per-kernel view (the two streaming kernels touch every read; the survivor kernel only the reads that
+        # survive the filter, so for short reads its algorithmic bytes are tiny and it is issue bound by nature)
+        per_kernel = {}
+        for name, units in (("seed_scan_filter", n), ("survivor", n_surv), ("recruit_scan", n)):
+            ms = dom_ms if name == dom else scout[names[name][0]]
+            b = units * bytes_per_read_per_pass
+            gbs = b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            per_kernel[name] = {"avg_launch_ms": round(ms, 4), "algorithmic_bytes": int(b), "achieved_GBps": round(gbs, 1),
+                                "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 5),
+                                "measured_in": "timed steps" if name == dom else "scouting steps (untimed)"}
+        # HBM bytes per launch of the dominant kernel from the rocprofv3 PMC passes committed under profiles/ — only when
+        # they were taken on THIS kernel source (hash recorded by profiles/summarize_pmc.py) and this workload
+        traffic, traffic_src, valu_issue = None, None, None
+        try:
+            pm = _pmc_file(n, L)
+            # (the seed-scan stage is k_filter_fast_impl for short uniform reads, k_hint_positions for long ones, else k_filter_general)
+            keys = {"seed_scan_filter": ("k_filter_fast", "k_hint_positions", "k_filter_general"), "survivor": ("k_survivor",),
+                    "recruit_scan": ("k_anchor_filter",)}[dom]
+            if pm and pm.get("source_hash") == source_hash() and pm.get("reads") == n and pm.get("read_len") == L:
+                for k, v in sorted(pm["per_launch"].items(), key=lambda kv: -kv[1].get("hbm_bytes", 0)):
+                    if traffic is None and k.startswith(keys):
+                        traffic, traffic_src = v["hbm_bytes"], "profiles/%s (committed PMC passes, same kernel source hash)" % pm["_file"]
+                        if "sq" in v and v["sq"].get("SQ_INSTS_VALU"):
+                            # what actually bounds this kernel: a wave64 VALU instruction occupies its SIMD for 4 cycles, the chip
+                            # has 256 CUs x 4 SIMDs and holds at most 2.4 GHz (MI355X)
+                            insts = v["sq"]["SQ_INSTS_VALU"]
+                            bound_ms = insts * 4.0 / (256 * 4) / 2.4e9 * 1e3
+                            valu_issue = {"insts_valu_per_launch": int(insts), "cycles_per_wave64_inst": 4, "simds": 1024, "clock_ghz": 2.4,
+                                          "bound_ms": round(bound_ms, 4), "frac": round(bound_ms / dom_ms, 4) if dom_ms > 0 else None,
+                                          "note": "the kernel is VALU-issue bound, not HBM bound: frac = VALU issue time at peak clock / measured launch time"}
+        except (OSError, KeyError, ValueError, TypeError):
+            pass
+        path_bytes = 2 * bytes_per_read_per_pass             # both passes read every base once at 2 bits
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "valu_issue": valu_issue,
+                    "path_frac": round(value / n_gpus * path_bytes / (HBM_PEAK_GBS * 1e9), 5),
+                    "path_frac_note": "whole path per GPU: reads/s/GPU x %d B / 8 TB/s (SURVEY 8d)" % path_bytes,
+                    "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(dom_ms, 4),
+                    "per_kernel": per_kernel, "host_ms": {"merge": round(avg["ms_merge_host"], 3), "sink": round(avg["ms_sink_host"], 3)},
+                    "merge_device_ms": stages["ms_merge_device"], "device_merge": int(c.get("used_device_merge", 0)),
+                    "stages_ms_scouting_steps": stages}
 
     workload = "%d synthetic %d bp reads%s, %d seeded DRs%s (%s%s); pass1 + merge + pass2" % (
         total, L, "" if n_gpus == 1 else " sharded over %d GPUs" % n_gpus, n_dr,
@@ -425,8 +462,11 @@ def main():
         "timed_batches": "two resident batches, alternating" if args.alternate else
                          "one resident batch repeated (speculation bounds learnt from the previous, identical step; "
                          "first_call_ms = the same step on a fresh context; --alternate switches batches)",
-        "roofline": roofline,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if rccl_ranks is not None:
         out["rccl_ranks"] = rccl_ranks
     if os.environ.get("CRASS_BENCH_FALLBACK"):
@@ -435,7 +475,7 @@ def main():
     # ---- the single-shot truth: a crass run scans each read set ONCE.  A FRESH context (no learnt bounds; its pools are
     #      sized from the read count when the reads are loaded), reads resident, ONE step, wall clock.  Outside the timed
     #      region. ----
-    if world == 1 and not group_mode and args.single_shots > 0 and not args.alternate:
+    if args.full and world == 1 and not group_mode and args.single_shots > 0 and not args.alternate:
         shots = []
         for _ in range(args.single_shots):
             e1 = ca.SearchEngine(prm, local_rank)
@@ -479,7 +519,7 @@ def main():
 
     # ---- what the adapter pays on top of a step: the ABI's wide arrays (crass_candidates / crass_merge_view / crass_recruits)
     #      are widened from the compact blobs ON REQUEST, outside the timed region ----
-    if world == 1 and not group_mode:
+    if args.full and world == 1 and not group_mode:
         fetch = []
         for _ in range(3):
             step()
@@ -497,7 +537,7 @@ def main():
                 out["e2e_reads_per_s"] = out["e2e"]["reads_per_s"]
 
     # ---- strong scaling: the same job on ONE GPU (rank 0, untimed part of the run; the other ranks wait) ----
-    if (world > 1 or group_mode) and scaling == "strong" and not args.no_strong_base and args.dist_backend == "nccl":
+    if args.full and (world > 1 or group_mode) and scaling == "strong" and not args.no_strong_base and args.dist_backend == "nccl":
         base = None
         if rank == 0:
             try:
@@ -530,7 +570,7 @@ def main():
     # ---- CPU baseline: the oracle (single core, same algorithm class as the reference) on a
     #      bounded prefix of the SAME stream; rank 0 at N=1 only ----
     cpu_sample = cfg["cpu_sample"] if args.cpu_sample < 0 else args.cpu_sample
-    if rank == 0 and world == 1 and not group_mode and cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not group_mode and cpu_sample > 0:
         from tests import orc
         m = min(cpu_sample, n)
         asc = ca.unpack_ascii(words, W, L, m)
@@ -643,6 +683,96 @@ class _GroupRunner:
 
     def close(self):
         self.g.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20250923
+
+
+def _dump_outputs(ca, e, out_dir):
+    """--dump-outputs: the last timed step's hand-off, read through the getters a caller of the path uses (outside the timed
+    region), written as DIR/<name>.npy; returns what the result line says about it"""
+    import numpy as np
+    src = e.g if isinstance(e, _GroupRunner) else e
+    cand, rec, mg = src.candidates(), src.recruits(), src.merge_view()
+    arrays = output_arrays(ca.engine.PipelineResult(cand, mg, rec, cand.max_read_len))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "shapes": {name: list(a.shape) for name, a in arrays.items()}}
+
+
+def output_arrays(res, limit=DUMP_LIMIT_BYTES):
+    """{name: float64 array} of a pipeline result (crass_amd.engine.PipelineResult or tests/orc.PipelineResult: the fields the
+    parity check compares), laid out as the module docstring says.  Tables larger than the sample size are cut to a sorted,
+    seeded sample of their rows; the sample size halves until the arrays hold at most `limit` bytes."""
+    import numpy as np
+    import zlib
+    n1, n2 = int(res.n_pass1), int(res.n_pass2)
+    n = n1 + n2
+    cols = [np.asarray(x[:n], np.int64) for x in (res.rec_read, res.rec_lowlexi, res.rec_token, res.rec_replen, res.rec_nss)]
+    nss, ss_off = cols[4], np.asarray(res.rec_ss_off[:n], np.int64)
+    pool = np.asarray(res.ss_pool, np.int64)
+    # every record's positions in record order (the pool itself may hold unused slots between records)
+    run = np.repeat(ss_off - (np.cumsum(nss) - nss), nss) + np.arange(int(nss.sum()), dtype=np.int64)
+    ss_all = pool[run] if len(run) else np.zeros(0, np.int64)
+    tokens, patterns = list(res.tokens), list(res.patterns)
+    pat_group = np.asarray(res.pat_group, np.int64)
+    grp_size = np.array([len(g) for g in res.groups], np.int64)
+    grp_pairs = np.stack([np.repeat(np.arange(len(grp_size), dtype=np.int64), grp_size),
+                          np.asarray([t for g in res.groups for t in g], np.int64)], axis=1) if grp_size.sum() else np.zeros((0, 2), np.int64)
+
+    def crc(a):
+        return float(zlib.crc32(np.ascontiguousarray(a, np.int64).tobytes()))
+
+    def strings_crc(strs):
+        return float(zlib.crc32(b"".join(strs), zlib.crc32(np.array([len(s) for s in strs], np.int64).tobytes())))
+
+    tok_len = np.array([len(t) for t in tokens], np.int64)
+    pat_len = np.array([len(p) for p in patterns], np.int64)
+    summary = [n1, n2, int(res.n_tokens), int(res.n_groups), int(res.n_patterns)]
+    summary += [float(c.sum()) for c in cols] + [float(ss_all.sum())]
+    summary += [float(tok_len.sum()), float(sum(sum(t) for t in tokens)), float(pat_len.sum()), float(sum(sum(p) for p in patterns)),
+                float(pat_group.sum()), float(grp_size.sum())]
+    # order-sensitive digests (CRC-32 of the int64 column / of lengths + bytes), exact in float64
+    summary += [crc(c) for c in cols] + [crc(ss_all), strings_crc(tokens), crc(grp_pairs), strings_crc(patterns), crc(pat_group)]
+
+    def sample(count, k, salt):
+        if count <= k:
+            return np.arange(count)
+        return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(count, k, replace=False))
+
+    def str_table(strs, idx, extra):
+        width = max((len(strs[i]) for i in idx), default=0)
+        t = np.zeros((len(idx), len(extra) + 1 + width))
+        for j, x in enumerate(extra):
+            t[:, j] = x
+        for r, i in enumerate(idx):
+            s = strs[i]
+            t[r, len(extra)] = len(s)
+            t[r, len(extra) + 1:len(extra) + 1 + len(s)] = np.frombuffer(s, np.uint8)
+        return t
+
+    k = 1 << 16
+    while True:
+        ri = sample(n, k, 1)
+        width = int(nss[ri].max()) if len(ri) else 0
+        at = ss_off[ri][:, None] + np.arange(width, dtype=np.int64)[None, :]
+        inside = np.arange(width)[None, :] < nss[ri][:, None]
+        rec_ss = np.where(inside, pool[np.minimum(at, max(len(pool) - 1, 0))] if len(pool) else 0, -1)
+        ti, gi, pi = sample(len(tokens), k, 2), sample(len(grp_pairs), k, 3), sample(len(patterns), k, 4)
+        arrays = {
+            "summary": np.array(summary, np.float64),
+            "records": np.stack([ri] + [c[ri] for c in cols] + [np.where(ri < n1, 1, 2)], axis=1).astype(np.float64),
+            "records_ss": rec_ss.astype(np.float64),
+            "tokens": str_table(tokens, ti, [ti]),
+            "groups": grp_pairs[gi].astype(np.float64),
+            "patterns": str_table(patterns, pi, [pi, pat_group[pi]]),
+        }
+        if sum(a.nbytes for a in arrays.values()) <= limit or k == 1:
+            return arrays
+        k //= 2
 
 
 def _e2e_dir(need_bytes):

@@ -226,7 +226,7 @@ def test_bench_group_launcher_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--local-copies", "--total-reads", "2000000", "--steps", "5",
-                        "--warmup", "2", "--cpu-sample", "0"], capture_output=True, timeout=600)
+                        "--warmup", "2", "--cpu-sample", "0", "--full"], capture_output=True, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["launcher"].startswith("group")

@@ -359,7 +359,7 @@ def test_bench_spawns_its_own_ranks_strong_scaling():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["total_reads"] == 1000000
     assert d["config"]["reads_per_gpu"] == 500000 and d["value"] > 0
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--total-reads", "1000000", "--steps", "2",
-                          "--warmup", "1", "--cpu-sample", "100000"], capture_output=True, timeout=900)
+                          "--warmup", "1", "--cpu-sample", "100000", "--full"], capture_output=True, timeout=900)
     d1 = _bench_line(one)
     assert d1["scaling"] == "strong" and "roofline" in d1 and "cpu_baseline" in d1
     assert 0 < d1["roofline"]["path_frac"] < 1 and d1["roofline"]["frac"] > 0
@@ -394,7 +394,7 @@ def test_bench_rccl_strong_scaling_one_rank_per_gpu():
     ng = torch.cuda.device_count()
     if ng >= 2:
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total-reads", "2000000", "--steps", "3",
-                            "--warmup", "2"], capture_output=True, timeout=900)
+                            "--warmup", "2", "--full"], capture_output=True, timeout=900)
         d = _bench_line(r)
         assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["rccl_ranks"] == 2
         assert d["one_gpu_same_job"]["pass1_found"] == d["config"]["pass1_found"]
@@ -408,7 +408,7 @@ def test_bench_other_configs_small(cfg, extra):
     """--config 3 (10 kbp reads, arrays of 20-60 repeats) and --config 4 (500 DRs, 4 GC classes) at reduced size, with
     the oracle check on a prefix"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(cfg), "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "2000" if cfg == 3 else "100000", "--check"] + extra, capture_output=True, timeout=900)
+                        "--cpu-sample", "2000" if cfg == 3 else "100000", "--check", "--full"] + extra, capture_output=True, timeout=900)
     d = _bench_line(r)
     assert d["config"]["baseline_config"] == cfg and d["config"]["pass1_found"] > 0 and d["value"] > 0
     assert "roofline" in d and "cpu_baseline" in d

@@ -1,6 +1,7 @@
 """The oracle of the stage behind the hot path (findConsensusDRs — true-DR consensus, group
 splitting, start/stop repair):
-* its ksw_align restatement against the COMPILED reference ksw.c (oracle/_ref), with the scoring the Aligner uses;
+* its ksw_align restatement against the COMPILED reference ksw.c (oracle/_ref), with the scoring the Aligner uses (the
+  reference's answers recorded in tests/golden, tests/refvec.py; checked against the live library where it is built);
 * the whole stage against the known answers SURVEY §8c recorded from the compiled reference: true DR strings, group ids
   and per-group read counts on the reference's own regression inputs."""
 import os
@@ -9,16 +10,14 @@ import random
 import numpy as np
 import pytest
 
-from tests import orc, fastx
+from tests import orc, fastx, refvec
 
 DATA = os.path.join(os.path.dirname(__file__), "golden", "data")
 
 
-def test_ksw_align_matches_the_compiled_reference():
-    if orc.ref() is None or not hasattr(orc.ref(), "ref_ksw_align"):
-        pytest.skip("oracle/_ref not available")
+def ksw_cases():
     rng = random.Random(11)
-    n = 0
+    cases = []
     for case in range(6000):
         tl = rng.randint(1, 60)
         t = [rng.randrange(4) for _ in range(tl)]
@@ -42,8 +41,22 @@ def test_ksw_align_matches_the_compiled_reference():
         else:                                # low-complexity: ties everywhere
             q = [rng.choice([0, 0, 0, 1]) for _ in range(rng.randint(1, 40))]
             t = [rng.choice([0, 0, 0, 1]) for _ in range(tl)]
-        got, want = orc.ksw_align(q, t, "oracle"), orc.ksw_align(q, t, "ref")
-        assert got == want, (q, t, got, want)
+        cases.append((q, t))
+    return cases
+
+
+def ksw_live(cases):
+    if not hasattr(orc.ref(), "ref_ksw_align"):
+        return None
+    return [orc.ksw_align(q, t, "ref") for q, t in cases]
+
+
+def test_ksw_align_matches_the_compiled_reference():
+    cases = ksw_cases()
+    n = 0
+    for (q, t), want in zip(cases, refvec.answers("ksw_align", cases, ksw_live)):
+        got = orc.ksw_align(q, t, "oracle")
+        assert list(got) == want, (q, t, got, want)
         n += want[0] >= 5
     assert n > 2000
 
@@ -127,3 +140,7 @@ def test_a_gid_without_a_group_is_skipped():
     assert a.error == 0 and b.error == 0
     assert b.gids == [g + 1 for g in a.gids] and b.true_drs == a.true_drs and b.groups == a.groups
     assert b.next_free_gid == a.next_free_gid + 1
+
+
+# what tests/golden/make_ref_vectors.py records: name -> (inputs, live reference)
+RECORDS = {"ksw_align": (ksw_cases, ksw_live)}

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/len_sweep}; mkdir -p $out
 for L in ${LENS:-100 150 250 256 300 400 500 700 1000 2000 2100}; do
   n=$((1500000000 / L))
-  python bench.py --read-len $L --total-reads $n --steps 5 --warmup 2 --cpu-sample 0 --single-shots 0 --e2e-reads 0 > $out/L$L.json 2> $out/L$L.err
+  python bench.py --full --read-len $L --total-reads $n --steps 5 --warmup 2 --cpu-sample 0 --single-shots 0 --e2e-reads 0 > $out/L$L.json 2> $out/L$L.err
   python - $out/L$L.json $L $n <<'P'
 import json, sys
 try:

@@ -24,13 +24,13 @@ python3 $GRAFT_REPO_ROOT/tools/timeline.py $out/rp 0 > $out/timeline.txt; rm -rf
 cd $GRAFT_REPO_ROOT
 bash tools/pmc_round.sh $tag/pmc > $out/pmc_summary.txt 2>&1
 cp $out/pmc/pmc_traffic.json profiles/r02_pmc_traffic.json 2>/dev/null      # (on the box only: so that the bench lines below quote it)
-timeout 300 python bench.py --cpu-sample 0 --steps 100 > /dev/null 2>&1      # (throw-away: the first run after the counter passes shows many slow steps, step_ms.p90 0.80 instead of 0.71)
-timeout 500 python bench.py > $out/bench_default.json 2> $out/bench_default.err
-timeout 300 python bench.py --alternate --cpu-sample 0 > $out/bench_alt.json 2> $out/bench_alt.err
-timeout 600 python bench.py --gpus 1 --config 2 --cpu-sample 0 > $out/bench_c2.json 2> $out/bench_c2.err
-timeout 600 python bench.py --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
-timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c4.json 2> $out/bench_c4.err
-timeout 600 python bench.py --gpus 2 --share-gpu --dist-backend gloo --total-reads 20000000 --cpu-sample 0 > $out/bench_2rank_shared.json 2> $out/bench_2rank_shared.err
+timeout 300 python bench.py --full --cpu-sample 0 --steps 100 > /dev/null 2>&1      # (throw-away: the first run after the counter passes shows many slow steps, step_ms.p90 0.80 instead of 0.71)
+timeout 500 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+timeout 300 python bench.py --full --alternate --cpu-sample 0 > $out/bench_alt.json 2> $out/bench_alt.err
+timeout 600 python bench.py --full --gpus 1 --config 2 --cpu-sample 0 > $out/bench_c2.json 2> $out/bench_c2.err
+timeout 600 python bench.py --full --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
+timeout 600 python bench.py --full --config 4 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c4.json 2> $out/bench_c4.err
+timeout 600 python bench.py --full --gpus 2 --share-gpu --dist-backend gloo --total-reads 20000000 --cpu-sample 0 > $out/bench_2rank_shared.json 2> $out/bench_2rank_shared.err
 timeout 600 python tools/consensus_timing.py 10000000 > $out/consensus_timing.json 2> $out/consensus_timing.err
 for f in $out/bench_default.json $out/bench_alt.json $out/bench_c2.json $out/bench_c3.json $out/bench_c4.json $out/bench_2rank_shared.json; do echo $f; python - $f <<'PY'
 import json,sys

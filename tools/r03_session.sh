@@ -21,7 +21,7 @@ PY
 if has smoke; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1 || { tail -20 $out/smoke.txt; echo SMOKE FAILED; exit 1; }
   tail -1 $out/smoke.txt
-  timeout 300 python bench.py --config 1 --steps 20 --warmup 3 --cpu-sample 0 > $out/bench_c1_quick.json 2> $out/bench_c1_quick.err || { tail -5 $out/bench_c1_quick.err; echo QUICK BENCH FAILED; exit 1; }
+  timeout 300 python bench.py --full --config 1 --steps 20 --warmup 3 --cpu-sample 0 > $out/bench_c1_quick.json 2> $out/bench_c1_quick.err || { tail -5 $out/bench_c1_quick.err; echo QUICK BENCH FAILED; exit 1; }
   summ $out/bench_c1_quick.json
 fi
 if has ubench; then
@@ -32,11 +32,11 @@ if has tests; then
   grep -q " failed" $out/pytest.txt && { echo TESTS FAILED; exit 1; }
 fi
 if has bench; then
-  timeout 600 python bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err || tail -5 $out/bench_default.err
-  CRASS_NO_PRESIZE=1 timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 > $out/bench_nopresize.json 2> $out/bench_nopresize.err
-  timeout 400 python bench.py --config 1 --cpu-sample 0 > $out/bench_c1.json 2> $out/bench_c1.err
-  CRASS_NO_PRESIZE=1 timeout 400 python bench.py --config 1 --cpu-sample 0 > $out/bench_c1_nopresize.json 2> $out/bench_c1_nopresize.err
-  timeout 400 python bench.py --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err || tail -5 $out/bench_default.err
+  CRASS_NO_PRESIZE=1 timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 > $out/bench_nopresize.json 2> $out/bench_nopresize.err
+  timeout 400 python bench.py --full --config 1 --cpu-sample 0 > $out/bench_c1.json 2> $out/bench_c1.err
+  CRASS_NO_PRESIZE=1 timeout 400 python bench.py --full --config 1 --cpu-sample 0 > $out/bench_c1_nopresize.json 2> $out/bench_c1_nopresize.err
+  timeout 400 python bench.py --full --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
   summ $out/bench_default.json $out/bench_nopresize.json $out/bench_c1.json $out/bench_c1_nopresize.json $out/bench_group2_shared.json
 fi
 cd /tmp; export TMPDIR=/tmp
@@ -63,9 +63,9 @@ if has hygiene; then
 fi
 if has other; then
   cd $GRAFT_REPO_ROOT
-  timeout 400 python bench.py --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
-  timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c4.json 2> $out/bench_c4.err
-  CRASS_DV_ONE=1 timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --single-shots 0 > $out/bench_c2_dv_one.json 2> $out/bench_c2_dv_one.err
+  timeout 400 python bench.py --full --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
+  timeout 600 python bench.py --full --config 4 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c4.json 2> $out/bench_c4.err
+  CRASS_DV_ONE=1 timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --single-shots 0 > $out/bench_c2_dv_one.json 2> $out/bench_c2_dv_one.err
   summ $out/bench_c3.json $out/bench_c4.json $out/bench_c2_dv_one.json
 fi
 if has scale; then

@@ -27,11 +27,11 @@ if has tests; then
   grep -q " failed" $out/pytest.txt && { echo TESTS FAILED; exit 1; }
 fi
 if has bench; then
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_c2_driver_style.json 2> $out/bench_c2_driver_style.err || tail -5 $out/bench_c2_driver_style.err
-  timeout 400 python bench.py --config 1 --cpu-sample 0 --e2e-reads 0 > $out/bench_c1.json 2> $out/bench_c1.err
-  timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --alternate > $out/bench_c2_alternate.json 2> $out/bench_c2_alternate.err
-  timeout 400 python bench.py --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
-  CRASS_DEVICE_VIEW=1 timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --single-shots 0 > $out/bench_c2_device_view.json 2> $out/bench_c2_device_view.err
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_c2_driver_style.json 2> $out/bench_c2_driver_style.err || tail -5 $out/bench_c2_driver_style.err
+  timeout 400 python bench.py --full --config 1 --cpu-sample 0 --e2e-reads 0 > $out/bench_c1.json 2> $out/bench_c1.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --alternate > $out/bench_c2_alternate.json 2> $out/bench_c2_alternate.err
+  timeout 400 python bench.py --full --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
+  CRASS_DEVICE_VIEW=1 timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --single-shots 0 > $out/bench_c2_device_view.json 2> $out/bench_c2_device_view.err
   summ $out/bench_c2_driver_style.json $out/bench_c1.json $out/bench_c2_alternate.json $out/bench_group2_shared.json $out/bench_c2_device_view.json
 fi
 if has prof; then
@@ -57,8 +57,8 @@ if has hygiene; then
   POISON=1 bash tools/mem_hygiene.sh $tag/hygiene > $out/hygiene.txt 2>&1; cat $out/hygiene.txt
 fi
 if has other; then
-  timeout 400 python bench.py --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
-  timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --cpu-sample 0 --e2e-reads 0 > $out/bench_c4.json 2> $out/bench_c4.err
+  timeout 400 python bench.py --full --config 3 --steps 10 --warmup 2 --cpu-sample 0 > $out/bench_c3.json 2> $out/bench_c3.err
+  timeout 600 python bench.py --full --config 4 --steps 10 --warmup 2 --cpu-sample 0 --e2e-reads 0 > $out/bench_c4.json 2> $out/bench_c4.err
   summ $out/bench_c3.json $out/bench_c4.json
   for d in 0 1 2 3; do CRASS_SURV_DEBUG=$d python tools/longread_ab.py 2>&1 | tail -1; done > $out/longread_breakdown.txt; cat $out/longread_breakdown.txt
 fi

@@ -22,9 +22,9 @@ fi
 B="--steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --single-shots 0"
 if has ab; then
   for rep in 1 2; do
-    timeout 300 python bench.py $B > $out/ab_new_$rep.json 2> $out/ab.err
+    timeout 300 python bench.py --full $B > $out/ab_new_$rep.json 2> $out/ab.err
     for sw in ${SWITCHES:-CRASS_DV_PAIR CRASS_DD_FULL_TABLE}; do
-      env $sw=1 timeout 300 python bench.py $B > $out/ab_${sw}_$rep.json 2>> $out/ab.err
+      env $sw=1 timeout 300 python bench.py --full $B > $out/ab_${sw}_$rep.json 2>> $out/ab.err
     done
   done
   line $out/ab_*.json

@@ -31,21 +31,21 @@ if has tests; then
   [ $rc -ne 0 ] && { echo "TESTS FAILED (pytest exit $rc)"; exit 1; }
 fi
 if has bench; then
-  timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_c2_driver_style.json 2> $out/bench_c2_driver_style.err; rc=$?
+  timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_c2_driver_style.json 2> $out/bench_c2_driver_style.err; rc=$?
   [ $rc -ne 0 ] && { tail -5 $out/bench_c2_driver_style.err; echo "DRIVER-STYLE BENCH FAILED (exit $rc)"; exit 1; }
-  timeout 400 python bench.py --config 1 --e2e-reads 0 > $out/bench_c1.json 2> $out/bench_c1.err
-  timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --alternate > $out/bench_c2_alternate.json 2> $out/bench_c2_alternate.err
-  timeout 400 python bench.py --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
+  timeout 400 python bench.py --full --config 1 --e2e-reads 0 > $out/bench_c1.json 2> $out/bench_c1.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e-reads 0 --alternate > $out/bench_c2_alternate.json 2> $out/bench_c2_alternate.err
+  timeout 400 python bench.py --full --gpus 2 --local-copies --cpu-sample 0 --steps 20 > $out/bench_group2_shared.json 2> $out/bench_group2_shared.err
   summ $out/bench_c2_driver_style.json $out/bench_c1.json $out/bench_c2_alternate.json $out/bench_group2_shared.json
 fi
 if has params; then
   # what a user of non-default options gets: 10 M x 150 bp, the kernel that ran is in config.fast_filter
   for p in "w=7" "d=20,D=40" "s=20,S=60" "n=3"; do
     f=$out/bench_c1_params_$(echo $p | tr '=,' '__').json
-    timeout 400 python bench.py --config 1 --params "$p" --steps 20 --warmup 3 --cpu-sample 200000 --e2e-reads 0 --single-shots 0 > $f 2> ${f%.json}.err
+    timeout 400 python bench.py --full --config 1 --params "$p" --steps 20 --warmup 3 --cpu-sample 200000 --e2e-reads 0 --single-shots 0 > $f 2> ${f%.json}.err
     summ $f
   done
-  timeout 400 python bench.py --config 3 --params "d=20,D=40" --steps 5 --warmup 2 --cpu-sample 0 --e2e-reads 0 --single-shots 0 > $out/bench_c3_params_d_20_D_40.json 2> $out/bench_c3_params.err
+  timeout 400 python bench.py --full --config 3 --params "d=20,D=40" --steps 5 --warmup 2 --cpu-sample 0 --e2e-reads 0 --single-shots 0 > $out/bench_c3_params_d_20_D_40.json 2> $out/bench_c3_params.err
   summ $out/bench_c3_params_d_20_D_40.json
 fi
 if has prof; then
@@ -83,8 +83,8 @@ if has hygiene; then
   POISON=1 bash tools/mem_hygiene.sh $tag/hygiene > $out/hygiene.txt 2>&1; cat $out/hygiene.txt
 fi
 if has other; then
-  timeout 400 python bench.py --config 3 --steps 20 --warmup 5 > $out/bench_c3.json 2> $out/bench_c3.err
-  timeout 600 python bench.py --config 4 --steps 10 --warmup 2 --cpu-sample 200000 --e2e-reads 0 > $out/bench_c4.json 2> $out/bench_c4.err
+  timeout 400 python bench.py --full --config 3 --steps 20 --warmup 5 > $out/bench_c3.json 2> $out/bench_c3.err
+  timeout 600 python bench.py --full --config 4 --steps 10 --warmup 2 --cpu-sample 200000 --e2e-reads 0 > $out/bench_c4.json 2> $out/bench_c4.err
   summ $out/bench_c3.json $out/bench_c4.json
 fi
 if has scale; then
@@ -98,7 +98,7 @@ if has lens; then
   # ... the same lengths under another window / seed lattice (the hint bits' every-position form), with and without it
   : > $out/len_sweep_params.txt
   for L in 300 1000; do n=$((1500000000 / L)); for p in w=7 d=20,D=40; do for e in CRASS_X=1 CRASS_NO_HINT_FILTER=1; do
-    env $e python bench.py --read-len $L --total-reads $n --params $p --steps 5 --warmup 2 --cpu-sample 20000 --single-shots 0 --e2e-reads 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('L=$L $p $e', 'ms/step', d['ms_per_step'], {k:v['avg_launch_ms'] for k,v in d['roofline']['per_kernel'].items()}, 'fast_filter', d['config'].get('fast_filter'), 'parity', (d.get('parity_checked') or {}).get('equal'))" >> $out/len_sweep_params.txt
+    env $e python bench.py --full --read-len $L --total-reads $n --params $p --steps 5 --warmup 2 --cpu-sample 20000 --single-shots 0 --e2e-reads 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('L=$L $p $e', 'ms/step', d['ms_per_step'], {k:v['avg_launch_ms'] for k,v in d['roofline']['per_kernel'].items()}, 'fast_filter', d['config'].get('fast_filter'), 'parity', (d.get('parity_checked') or {}).get('equal'))" >> $out/len_sweep_params.txt
   done; done; done
   cat $out/len_sweep_params.txt
 fi
