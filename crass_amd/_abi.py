@@ -186,6 +186,10 @@ SYMBOLS = {
     "crass_hip_consensus": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(ConsInput), C.POINTER(C.c_void_p)]),
     "crass_hip_consensus_view": (C.c_int, [C.c_void_p, C.POINTER(ConsView)]),
     "crass_hip_consensus_free": (None, [C.c_void_p]),
+    "crass_hip_ksw_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_uint32, C.c_void_p]),
+    "crass_hip_smith_waterman_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_uint64, C.c_double] +
+                                       [C.c_void_p] * 7),
     "crass_fastx_find": (C.c_uint64, [C.POINTER(Fastx), C.c_char_p, C.c_uint64]),
     "crass_index_fastx": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "crass_index_fastx_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -29,6 +29,7 @@
 #include <vector>
 
 using namespace crass;
+static_assert(CRASS_HIP_KSW_MAX_QLEN == kKswMaxQlen, "the header's ksw query cap is k_cons_ksw's");
 
 namespace {
 
@@ -692,6 +693,78 @@ void combine_groups(crass_cons *s)
     }
 }
 
+// smithWaterman's similarity test (SmithWaterman.cpp:281-296): a_ret and b_ret are kept when 1 - LD / |a_ret| >= similarity
+inline bool sw_similar(int32_t lev, int a_len, double similarity) { return 1.0 - (lev / (double)a_len) >= similarity; }
+
+// the traceback scratch one k_cons_sw launch may use (long reads: (search length + 1) x (DR + 1) bytes per task);
+// CRASS_CONS_SW_BUDGET (bytes) lowers it for tests, so that small inputs take the chunked path
+uint64_t sw_scratch_budget()
+{
+    if (const char *e = getenv("CRASS_CONS_SW_BUDGET")) return (uint64_t)std::max(1ll, atoll(e));
+    return 1ull << 30;
+}
+
+// The device part of smithWaterman for a task list whose dir_off the caller laid out (cons_sw_scratch_bytes, in task
+// order): the DR strings go up (d_drchars, and behind the records in d_seq at seq_bytes for the Levenshtein batch),
+// k_cons_sw runs in chunks bounded by sw_scratch_budget(), then the Levenshtein filter of SmithWaterman.cpp:283 over
+// (a_ret, b_ret).  rec_off(k): record k's offset in d_seq.  bad: a task the reference would have thrown on.
+template <typename RecOff>
+int sw_device_batch(crass_cons *s, const std::vector<ConsSwTask> &tasks, const std::vector<char> &drc, const std::vector<uint32_t> &dr_off,
+                    const std::vector<uint32_t> &dr_len, uint64_t seq_bytes, RecOff rec_off, std::vector<ConsSwOut> &out, std::vector<int32_t> &lev,
+                    bool &bad, uint32_t *n_launches)
+{
+    out.assign(tasks.size(), ConsSwOut{});
+    lev.assign(tasks.size(), 0);
+    bad = false;
+    if (n_launches) *n_launches = 0;
+    if (tasks.empty()) return CRASS_OK;
+    const size_t n_dr = dr_off.size();
+    HCHK(s, s->d_drchars.ensure(drc.size() + 1)); HCHK(s, s->d_droff.ensure(n_dr)); HCHK(s, s->d_drlen.ensure(n_dr));
+    HCHK(s, hipMemcpyAsync(s->d_drchars.p, drc.data(), drc.size(), hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_seq.p + seq_bytes, drc.data(), drc.size(), hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_droff.p, dr_off.data(), n_dr * 4, hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_drlen.p, dr_len.data(), n_dr * 4, hipMemcpyHostToDevice, s->st));
+    const uint64_t budget = sw_scratch_budget();
+    size_t at = 0;
+    while (at < tasks.size()) {
+        size_t end = at; const uint64_t base = tasks[at].dir_off;
+        while (end < tasks.size() && (end == at || tasks[end].dir_off + cons_sw_scratch_bytes((uint32_t)tasks[end].len, dr_len[tasks[end].dr]) - base <= budget)) end++;
+        const size_t n = end - at;
+        // (straight from / into pageable memory: pinned staging buffers would be allocated per call — measured slower, 7.0 vs 5.8 ms)
+        const bool whole = at == 0 && end == tasks.size();           // one chunk (the usual case): its offsets are already relative
+        std::vector<ConsSwTask> part;
+        if (!whole) { part.assign(tasks.begin() + (long)at, tasks.begin() + (long)end); for (auto &t : part) t.dir_off -= base; }
+        const ConsSwTask *chunk = whole ? tasks.data() : part.data();
+        const uint64_t bytes = chunk[n - 1].dir_off + cons_sw_scratch_bytes((uint32_t)chunk[n - 1].len, dr_len[chunk[n - 1].dr]);
+        HCHK(s, s->d_dirs.ensure(bytes + 64)); HCHK(s, s->d_tasks.ensure(n)); HCHK(s, s->d_swout.ensure(n));
+        HCHK(s, hipMemcpyAsync(s->d_tasks.p, chunk, n * sizeof(ConsSwTask), hipMemcpyHostToDevice, s->st));
+        HCHK(s, launch_cons_sw(s->d_seq.p, s->d_roff.p, s->d_rlen.p, s->d_tasks.p, (uint32_t)n, s->d_drchars.p, s->d_droff.p, s->d_drlen.p, s->d_dirs.p,
+                               s->d_swout.p, s->st));
+        HCHK(s, hipMemcpyAsync(out.data() + at, s->d_swout.p, n * sizeof(ConsSwOut), hipMemcpyDeviceToHost, s->st));
+        HCHK(s, hipStreamSynchronize(s->st));
+        if (n_launches) ++*n_launches;
+        at = end;
+    }
+    std::vector<uint64_t> a_off(tasks.size()), b_off(tasks.size()); std::vector<uint32_t> a_len(tasks.size()), b_len(tasks.size());
+    uint32_t max_len = 1;
+    for (size_t q = 0; q < tasks.size(); q++) {
+        if (out[q].err) { bad = true; return CRASS_OK; }
+        a_off[q] = rec_off(tasks[q].rec) + (uint64_t)out[q].a_off; a_len[q] = (uint32_t)out[q].a_len;
+        b_off[q] = seq_bytes + dr_off[tasks[q].dr] + (uint64_t)out[q].b_off; b_len[q] = (uint32_t)out[q].b_len;
+        max_len = std::max(max_len, std::max(a_len[q], b_len[q]));
+    }
+    const size_t n = tasks.size();
+    HCHK(s, s->d_a_off.ensure(n)); HCHK(s, s->d_b_off.ensure(n)); HCHK(s, s->d_a_len.ensure(n)); HCHK(s, s->d_b_len.ensure(n)); HCHK(s, s->d_lev.ensure(n));
+    HCHK(s, hipMemcpyAsync(s->d_a_off.p, a_off.data(), n * 8, hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_b_off.p, b_off.data(), n * 8, hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_a_len.p, a_len.data(), n * 4, hipMemcpyHostToDevice, s->st));
+    HCHK(s, hipMemcpyAsync(s->d_b_len.p, b_len.data(), n * 4, hipMemcpyHostToDevice, s->st));
+    HCHK(s, launch_levenshtein_batch(s->d_seq.p, s->d_a_off.p, s->d_a_len.p, s->d_b_off.p, s->d_b_len.p, n, s->d_lev.p, nullptr, max_len, s->st));
+    HCHK(s, hipMemcpyAsync(lev.data(), s->d_lev.p, n * 4, hipMemcpyDeviceToHost, s->st));
+    HCHK(s, hipStreamSynchronize(s->st));
+    return CRASS_OK;
+}
+
 // ReadHolder::updateStartStops for every read that reached a leaf (ReadHolder.cpp:382-511): the pair arithmetic on the
 // host, the partial-repeat searches (smithWaterman + Levenshtein) as one device batch
 int update_all_start_stops(crass_cons *s)
@@ -753,58 +826,15 @@ int update_all_start_stops(crass_cons *s)
     }
     s->cnt.n_sw_tasks = tasks.size();
     sub("pair arithmetic, task list");
-    std::vector<ConsSwOut> out(tasks.size());
-    std::vector<int32_t> lev(tasks.size(), 0);
-    if (!tasks.empty()) {
-        // the DR strings follow the records in the device buffer (one character array for the Levenshtein batch)
-        const uint64_t seq_bytes = s->hseq.size();
-        HCHK(s, s->d_drchars.ensure(drc.size() + 1)); HCHK(s, s->d_droff.ensure(n_dr + 1)); HCHK(s, s->d_drlen.ensure(n_dr + 1));
-        HCHK(s, hipMemcpyAsync(s->d_drchars.p, drc.data(), drc.size(), hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_seq.p + seq_bytes, drc.data(), drc.size(), hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_droff.p, dr_off.data(), (n_dr + 1) * 4, hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_drlen.p, dr_len.data(), (n_dr + 1) * 4, hipMemcpyHostToDevice, s->st));
-        // chunks bounded by the traceback scratch (long reads: (search length + 1) x (DR + 1) bytes per task)
-        const uint64_t budget = 1ull << 30;
-        size_t at = 0;
-        while (at < tasks.size()) {
-            size_t end = at; const uint64_t base = tasks[at].dir_off;
-            while (end < tasks.size() && (end == at || tasks[end].dir_off + cons_sw_scratch_bytes((uint32_t)tasks[end].len, dr_len[tasks[end].dr]) - base <= budget)) end++;
-            const size_t n = end - at;
-            // (straight from / into pageable memory: pinned staging buffers would be allocated per call — measured slower, 7.0 vs 5.8 ms)
-            const bool whole = at == 0 && end == tasks.size();           // one chunk (the usual case): its offsets are already relative
-            std::vector<ConsSwTask> part;
-            if (!whole) { part.assign(tasks.begin() + (long)at, tasks.begin() + (long)end); for (auto &t : part) t.dir_off -= base; }
-            const ConsSwTask *chunk = whole ? tasks.data() : part.data();
-            const uint64_t bytes = chunk[n - 1].dir_off + cons_sw_scratch_bytes((uint32_t)chunk[n - 1].len, dr_len[chunk[n - 1].dr]);
-            HCHK(s, s->d_dirs.ensure(bytes + 64)); HCHK(s, s->d_tasks.ensure(n)); HCHK(s, s->d_swout.ensure(n));
-            HCHK(s, hipMemcpyAsync(s->d_tasks.p, chunk, n * sizeof(ConsSwTask), hipMemcpyHostToDevice, s->st));
-            HCHK(s, launch_cons_sw(s->d_seq.p, s->d_roff.p, s->d_rlen.p, s->d_tasks.p, (uint32_t)n, s->d_drchars.p, s->d_droff.p, s->d_drlen.p, s->d_dirs.p,
-                                   s->d_swout.p, s->st));
-            HCHK(s, hipMemcpyAsync(out.data() + at, s->d_swout.p, n * sizeof(ConsSwOut), hipMemcpyDeviceToHost, s->st));
-            HCHK(s, hipStreamSynchronize(s->st));
-            at = end;
-        }
-        sub("smithWaterman batch");
-        // the Levenshtein filter of SmithWaterman.cpp:283 over (a_ret, b_ret), as one batch of the engine's kernel
-        std::vector<uint64_t> a_off(tasks.size()), b_off(tasks.size()); std::vector<uint32_t> a_len(tasks.size()), b_len(tasks.size());
-        uint32_t max_len = 1;
-        for (size_t q = 0; q < tasks.size(); q++) {
-            if (out[q].err) { s->error = 3; return CRASS_OK; }
-            a_off[q] = s->rec[tasks[q].rec].roff + (uint64_t)out[q].a_off; a_len[q] = (uint32_t)out[q].a_len;
-            b_off[q] = seq_bytes + dr_off[tasks[q].dr] + (uint64_t)out[q].b_off; b_len[q] = (uint32_t)out[q].b_len;
-            max_len = std::max(max_len, std::max(a_len[q], b_len[q]));
-        }
-        const size_t n = tasks.size();
-        HCHK(s, s->d_a_off.ensure(n)); HCHK(s, s->d_b_off.ensure(n)); HCHK(s, s->d_a_len.ensure(n)); HCHK(s, s->d_b_len.ensure(n)); HCHK(s, s->d_lev.ensure(n));
-        HCHK(s, hipMemcpyAsync(s->d_a_off.p, a_off.data(), n * 8, hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_b_off.p, b_off.data(), n * 8, hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_a_len.p, a_len.data(), n * 4, hipMemcpyHostToDevice, s->st));
-        HCHK(s, hipMemcpyAsync(s->d_b_len.p, b_len.data(), n * 4, hipMemcpyHostToDevice, s->st));
-        HCHK(s, launch_levenshtein_batch(s->d_seq.p, s->d_a_off.p, s->d_a_len.p, s->d_b_off.p, s->d_b_len.p, n, s->d_lev.p, nullptr, max_len, s->st));
-        HCHK(s, hipMemcpyAsync(lev.data(), s->d_lev.p, n * 4, hipMemcpyDeviceToHost, s->st));
-        HCHK(s, hipStreamSynchronize(s->st));
+    std::vector<ConsSwOut> out;
+    std::vector<int32_t> lev;
+    {
+        bool bad = false;
+        const int rc = sw_device_batch(s, tasks, drc, dr_off, dr_len, s->hseq.size(), [s](uint32_t k) { return s->rec[k].roff; }, out, lev, bad, nullptr);
+        if (rc) return rc;
+        if (bad) { s->error = 3; return CRASS_OK; }
     }
-    sub("Levenshtein batch");
+    sub("smithWaterman + Levenshtein batches");
     // the decisions of updateStartStops on the alignments, front task before back task of a read (tasks are in that order);
     // ranges of tasks on the host pool, cut between records (a record's two tasks stay with one worker)
     std::vector<size_t> cuts(1, 0);
@@ -821,8 +851,7 @@ int update_all_start_stops(crass_cons *s)
         const char *DR = drc.data() + dr_off[tasks[q].dr];
         const size_t DR_size = dr_len[tasks[q].dr];
         int part_s = o.a_start, part_e = o.a_end, a_len = o.a_len, b_len = o.b_len;
-        const double similarity_ld = 1.0 - (lev[q] / (double)a_len);
-        if (!(similarity_ld >= kPartialSim)) { part_s = 0; part_e = 0; a_len = 0; b_len = 0; }
+        if (!sw_similar(lev[q], a_len, kPartialSim)) { part_s = 0; part_e = 0; a_len = 0; b_len = 0; }
         if (0 == part_e || part_e - part_s < kMinPartialLen) continue;
         // b_ret = DR.substr(b_off, b_len) (clamped to the string's end).  "DR.rfind(b_ret) + b_ret.size() == DR.size()": the LAST
         // occurrence ends where DR ends <=> DR ends with b_ret; "0 == DR.find(b_ret)" <=> DR starts with it (no strings built:
@@ -925,6 +954,34 @@ void give_stream(int device, hipStream_t st)
     auto &v = g_stream_pool[device];
     if (v.size() < 8) v.push_back(st); else (void)hipStreamDestroy(st);
 }
+
+// Aligner ctor (Aligner.h:112-136): gapo 5, gape 2, minsc 5, match 1, mismatch -3, ambiguous 0
+void aligner_ksw_params(ConsKswParams &P)
+{
+    P.gapo = 5; P.gape = 2; P.minsc = 5;
+    int k = 0;
+    for (int i = 0; i < 4; ++i) { for (int j = 0; j < 4; ++j) P.mat[k++] = i == j ? 1 : -3; P.mat[k++] = 0; }
+    for (int j = 0; j < 5; ++j) P.mat[k++] = 0;
+}
+
+// a bare stage object for the batch entry points: device, stream and the Aligner's scoring, no records
+int batch_state(int device, std::unique_ptr<crass_cons> &sp)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return CRASS_ERR_NO_DEVICE;
+    sp.reset(new (std::nothrow) crass_cons());
+    if (!sp) return CRASS_ERR_OOM;
+    sp->device = device;
+    if (hipSetDevice(device) != hipSuccess) return CRASS_ERR_NO_DEVICE;
+    sp->st = take_stream(device);
+    if (!sp->st) return CRASS_ERR_HIP;
+    aligner_ksw_params(sp->ksw);
+    return CRASS_OK;
+}
+void batch_release(crass_cons *s)
+{
+    if (s->st) { (void)hipStreamSynchronize(s->st); give_stream(s->device, s->st); s->st = nullptr; }
+}
 } // namespace
 
 extern "C" {
@@ -947,9 +1004,7 @@ int crass_hip_consensus(const crass_params *p, int device, const crass_cons_inpu
     s->st = take_stream(device);
     if (!s->st) return CRASS_ERR_HIP;
     build_comp_table(s->comp);
-    // Aligner ctor (Aligner.h:112-136): gapo 5, gape 2, minsc 5, match 1, mismatch -3, ambiguous 0
-    s->ksw.gapo = 5; s->ksw.gape = 2; s->ksw.minsc = 5;
-    { int k = 0; for (int i = 0; i < 4; ++i) { for (int j = 0; j < 4; ++j) s->ksw.mat[k++] = i == j ? 1 : -3; s->ksw.mat[k++] = 0; } for (int j = 0; j < 5; ++j) s->ksw.mat[k++] = 0; }
+    aligner_ksw_params(s->ksw);
     int rc = CRASS_OK;
     const bool timing = getenv("CRASS_TIMING") != nullptr;
     auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1066,6 +1121,92 @@ int crass_hip_consensus_view(const crass_cons *s, crass_cons_view *v)
     v->rec_nss = s->o_nss.data(); v->rec_ss_off = s->o_ss_off.data(); v->ss_pool = s->o_ss.data();
     v->tokread_off = s->o_tokread_off.data(); v->tokread_idx = s->o_tokread_idx.data(); v->tok_has_list = s->o_has.data();
     v->counters = s->cnt;
+    return CRASS_OK;
+}
+
+int crass_hip_ksw_batch(int device, const uint8_t *q_codes, const uint32_t *q_off, const uint32_t *q_len, const uint32_t *q_tgt, uint32_t n,
+                        const uint8_t *t_codes, const uint32_t *t_off, const uint32_t *t_len, uint32_t n_targets, int32_t *out)
+{
+    if (n && (!q_codes || !q_off || !q_len || !q_tgt || !t_codes || !t_off || !t_len || !out)) return CRASS_ERR_INVALID_ARG;
+    if (n == 0) return CRASS_OK;
+    // the codes go back to characters: ksw_batch takes the strings the consensus aligns and codes them itself (nt4)
+    static const char kCodeChar[5] = {'A', 'C', 'G', 'T', 'N'};
+    auto str = [&](const uint8_t *c, uint32_t off, uint32_t len, std::string &o) {
+        o.resize(len);
+        for (uint32_t i = 0; i < len; i++) { if (c[(size_t)off + i] > 4) return false; o[i] = kCodeChar[c[(size_t)off + i]]; }
+        return true;
+    };
+    std::vector<std::string> strs(n), masters(n_targets);
+    std::vector<uint32_t> tgt(q_tgt, q_tgt + n);
+    for (uint32_t v = 0; v < n; v++) {
+        if (q_len[v] < 1 || q_tgt[v] >= n_targets) return CRASS_ERR_INVALID_ARG;
+        if (q_len[v] > kKswMaxQlen) return CRASS_ERR_UNSUPPORTED;                     // k_cons_ksw's LDS cap: not launched
+        if (!str(q_codes, q_off[v], q_len[v], strs[v])) return CRASS_ERR_INVALID_ARG;
+    }
+    for (uint32_t t = 0; t < n_targets; t++) {
+        if (t_len[t] < 1) return CRASS_ERR_INVALID_ARG;
+        if (!str(t_codes, t_off[t], t_len[t], masters[t])) return CRASS_ERR_INVALID_ARG;
+    }
+    std::unique_ptr<crass_cons> sp;
+    int rc = batch_state(device, sp);
+    if (rc) return rc;
+    std::vector<std::array<int, 6>> res;
+    rc = ksw_batch(sp.get(), strs, tgt, masters, res);
+    batch_release(sp.get());
+    if (rc) return rc;
+    for (uint32_t v = 0; v < n; v++) for (int q = 0; q < 6; q++) out[(size_t)v * 6 + q] = res[v][q];
+    return CRASS_OK;
+}
+
+int crass_hip_smith_waterman_batch(int device, const char *chars, uint64_t n_chars, const uint64_t *read_off, const uint32_t *read_len,
+                                   const uint64_t *dr_off, const uint32_t *dr_len, const int32_t *start, const int32_t *len, uint64_t n,
+                                   double similarity, int32_t *a_start, int32_t *a_end, int32_t *a_off, int32_t *a_len, int32_t *b_off,
+                                   int32_t *b_len, uint32_t *n_launches)
+{
+    if (n_launches) *n_launches = 0;
+    if (n && (!chars || !read_off || !read_len || !dr_off || !dr_len || !start || !len || !a_start || !a_end || !a_off || !a_len || !b_off || !b_len))
+        return CRASS_ERR_INVALID_ARG;
+    if (n == 0) return CRASS_OK;
+    if (n > UINT32_MAX || n_chars >= (1ull << 31)) return CRASS_ERR_UNSUPPORTED;
+    // the reference's domain (ReadHolder.cpp:438,481 only call it with a non-empty window inside the read); outside it the
+    // reference reads out of bounds or crashes, and nothing is launched here
+    for (uint64_t k = 0; k < n; k++) {
+        if (read_off[k] + read_len[k] > n_chars || dr_off[k] + dr_len[k] > n_chars || dr_len[k] < 1) return CRASS_ERR_INVALID_ARG;
+        if (start[k] < 0 || len[k] < 1 || (uint64_t)start[k] + (uint64_t)len[k] > read_len[k]) return CRASS_ERR_INVALID_ARG;
+    }
+    std::unique_ptr<crass_cons> sp;
+    int rc = batch_state(device, sp);
+    if (rc) return rc;
+    crass_cons *s = sp.get();
+    // record k = the read of task k, DR k = its DR: the characters once in d_seq as the records, once behind them as the DR table
+    std::vector<ConsSwTask> tasks((size_t)n);
+    std::vector<uint32_t> d_off((size_t)n), d_len((size_t)n), rlen((size_t)n);
+    uint64_t dir_total = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        ConsSwTask &t = tasks[(size_t)k];
+        t.rec = (uint32_t)k; t.dr = (uint32_t)k; t.start = start[k]; t.len = len[k]; t.dir_off = dir_total;
+        dir_total += cons_sw_scratch_bytes((uint32_t)t.len, dr_len[k]);
+        d_off[(size_t)k] = (uint32_t)dr_off[k]; d_len[(size_t)k] = dr_len[k]; rlen[(size_t)k] = read_len[k];
+    }
+    const std::vector<char> drc(chars, chars + n_chars);
+    std::vector<ConsSwOut> out; std::vector<int32_t> lev;
+    bool bad = false;
+    auto body = [&]() -> int {
+        HCHK(s, s->d_seq.ensure(2 * n_chars + 64)); HCHK(s, s->d_roff.ensure((size_t)n)); HCHK(s, s->d_rlen.ensure((size_t)n));
+        HCHK(s, hipMemcpyAsync(s->d_seq.p, chars, n_chars, hipMemcpyHostToDevice, s->st));
+        HCHK(s, hipMemcpyAsync(s->d_roff.p, read_off, n * 8, hipMemcpyHostToDevice, s->st));
+        HCHK(s, hipMemcpyAsync(s->d_rlen.p, rlen.data(), n * 4, hipMemcpyHostToDevice, s->st));
+        return sw_device_batch(s, tasks, drc, d_off, d_len, n_chars, [&](uint32_t k) { return read_off[k]; }, out, lev, bad, n_launches);
+    };
+    rc = body();
+    batch_release(s);
+    if (rc) return rc;
+    if (bad) return CRASS_ERR_INVALID_ARG;
+    for (uint64_t k = 0; k < n; k++) {
+        const ConsSwOut &o = out[(size_t)k];
+        a_start[k] = o.a_start; a_end[k] = o.a_end; a_off[k] = o.a_off; a_len[k] = o.a_len; b_off[k] = o.b_off; b_len[k] = o.b_len;
+        if (0 != similarity && !sw_similar(lev[(size_t)k], o.a_len, similarity)) { a_start[k] = 0; a_end[k] = 0; a_len[k] = 0; b_len[k] = 0; }
+    }
     return CRASS_OK;
 }
 

@@ -345,9 +345,9 @@ hipError_t launch_cons_ksw(const uint8_t *q_codes, const uint32_t *q_off, const 
                            const uint8_t *t_codes, const uint32_t *t_off, const uint32_t *t_len, const ConsKswParams &P, int32_t *out, hipStream_t st)
 {
     if (!n_str) return hipSuccess;
+    if (max_qlen > kKswMaxQlen) return hipErrorInvalidValue;
     const int nvec_max = (int)((max_qlen + 7) / 8) * 8;
     const size_t lds = (size_t)4 * nvec_max * 64 * sizeof(int16_t);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cons_ksw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     CRASS_LAUNCH(k_cons_ksw, dim3((2 * n_str + 63) / 64), dim3(64), lds, st, q_codes, q_off, q_len, q_tgt, n_str, t_codes, t_off, t_len, P, nvec_max, out);

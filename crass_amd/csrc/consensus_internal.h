@@ -14,6 +14,8 @@ hipError_t launch_cons_cover(const uint8_t *seq, const uint64_t *roff, const uin
                              uint32_t n_plc, int *cov, int length, hipStream_t st);
 // strings as codes 0..4 (seq_nt4_table, Aligner.cpp:40-58), string v against target q_tgt[v] (its group's master DR);
 // out[2 v + o][3] = score, tb, qb of string v (o = 1: its reverse complement)
+// k_cons_ksw keeps four int16 vectors of ceil8(qlen) entries per thread in LDS, 64 threads a block: 160 KB at qlen 320
+static constexpr uint32_t kKswMaxQlen = 320;
 hipError_t launch_cons_ksw(const uint8_t *q_codes, const uint32_t *q_off, const uint32_t *q_len, const uint32_t *q_tgt, uint32_t n_str, uint32_t max_qlen,
                            const uint8_t *t_codes, const uint32_t *t_off, const uint32_t *t_len, const ConsKswParams &P, int32_t *out, hipStream_t st);
 // A task whose direction matrix and read window fit the kernel's per-wave LDS keeps them there (k_cons_sw) and needs no scratch

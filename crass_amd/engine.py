@@ -904,6 +904,47 @@ def consensus(seqs, res, params=None, device=0):
         lib.crass_hip_consensus_free(h)
 
 
+def ksw_batch(cases, device=0):
+    """crass_hip_ksw_batch: cases = [(query codes, target codes)] (codes 0..4) -> int32 [n, 2, 3]: (score, tb, qb) of each query
+    and of its reverse complement against its target, with the Aligner's scoring"""
+    q_off, q_len, t_off, t_len, items, pos = [], [], [], [], [], 0
+    for q, _ in cases:
+        q_off.append(pos); q_len.append(len(q)); items.append(bytes(q)); pos += len(q)
+    qc = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
+    items, pos = [], 0
+    for _, t in cases:
+        t_off.append(pos); t_len.append(len(t)); items.append(bytes(t)); pos += len(t)
+    tc = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
+    q_off, q_len, t_off, t_len = (np.array(x, np.uint32) for x in (q_off, q_len, t_off, t_len))
+    tgt = np.arange(len(cases), dtype=np.uint32)
+    out = np.zeros((len(cases), 2, 3), np.int32)
+    _chk(_abi.load().crass_hip_ksw_batch(int(device), qc.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, tgt.ctypes.data, len(cases),
+                                         tc.ctypes.data, t_off.ctypes.data, t_len.ctypes.data, len(cases), out.ctypes.data),
+         "crass_hip_ksw_batch")
+    return out
+
+
+def smith_waterman_batch(tasks, similarity=0.85, device=0):
+    """crass_hip_smith_waterman_batch: tasks = [(read bytes, DR bytes, start, len)] -> (int32 [n, 6] of aStart, aEnd, a_off, a_len,
+    b_off, b_len, number of k_cons_sw launches).  a_ret = read[a_off:a_off + a_len], b_ret = DR[b_off:b_off + b_len]"""
+    r_off, r_len, d_off, d_len, st, ln, items, pos = [], [], [], [], [], [], [], 0
+    for a, b, s, n in tasks:
+        r_off.append(pos); r_len.append(len(a)); items.append(bytes(a)); pos += len(a)
+        d_off.append(pos); d_len.append(len(b)); items.append(bytes(b)); pos += len(b)
+        st.append(s); ln.append(n)
+    chars = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
+    r_off, d_off = np.array(r_off, np.uint64), np.array(d_off, np.uint64)
+    r_len, d_len = np.array(r_len, np.uint32), np.array(d_len, np.uint32)
+    st, ln = np.array(st, np.int32), np.array(ln, np.int32)
+    out = np.zeros((6, len(tasks)), np.int32)
+    launches = C.c_uint32(0)
+    _chk(_abi.load().crass_hip_smith_waterman_batch(int(device), chars.ctypes.data, pos, r_off.ctypes.data, r_len.ctypes.data, d_off.ctypes.data,
+                                                    d_len.ctypes.data, st.ctypes.data, ln.ctypes.data, len(tasks), float(similarity),
+                                                    *[out[k].ctypes.data for k in range(6)], C.byref(launches)),
+         "crass_hip_smith_waterman_batch")
+    return out.T.copy(), launches.value
+
+
 def build_outputs(groups, out_dir="./", timestamp="", command_line="", cwd="", log_to_screen=True, cov_cutoff=0, write_to=None):
     """crass_build_outputs (WorkHorse::buildGraph ... outputResults): groups = [(gid, true_dr bytes, [(header, comment or None, seq,
     start_stops), ...])] in ascending GID, the reads in buildGraph's order.  Returns (files {name: bytes}, kept gids, stdout text);

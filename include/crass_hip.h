@@ -413,6 +413,28 @@ int  crass_hip_consensus(const crass_params *p, int device, const crass_cons_inp
 int  crass_hip_consensus_view(const crass_cons *c, crass_cons_view *v);
 void crass_hip_consensus_free(crass_cons *c);
 
+/* ---- the consensus stage's two alignment kernels on their own (tests: against the compiled reference's answers) ----
+ * crass_hip_ksw_batch: ksw_align (ksw.c:330-360) with the Aligner's scoring (Aligner.h:112-136) of query v (codes 0..4,
+ * q_codes[q_off[v] .. + q_len[v])) against target q_tgt[v] (t_codes[t_off[t] .. + t_len[t])), and of its reverse
+ * complement, through the consensus stage's own batch code.  out[2 v + o][3] = score, tb, qb (o = 1: the reverse
+ * complement; tb = qb = -1 below minsc).  CRASS_ERR_UNSUPPORTED (nothing launched): a query longer than
+ * CRASS_HIP_KSW_MAX_QLEN; CRASS_ERR_INVALID_ARG: an empty string, a code above 4, a target index out of range.          */
+#define CRASS_HIP_KSW_MAX_QLEN 320
+int crass_hip_ksw_batch(int device, const uint8_t *q_codes, const uint32_t *q_off, const uint32_t *q_len, const uint32_t *q_tgt,
+                        uint32_t n, const uint8_t *t_codes, const uint32_t *t_off, const uint32_t *t_len, uint32_t n_targets,
+                        int32_t *out);
+/* crass_hip_smith_waterman_batch: smithWaterman(read, dr, &aStart, &aEnd, start[k], len[k], similarity)
+ * (SmithWaterman.cpp:151-308) of task k, read = chars[read_off[k] .. + read_len[k]), dr = chars[dr_off[k] .. + dr_len[k]),
+ * through the consensus stage's own updateStartStops code (scratch layout, k_cons_sw launches in scratch-bounded chunks,
+ * Levenshtein batch, similarity decision).  a_ret = read[a_off .. + a_len), b_ret = dr[b_off .. + b_len); a rejected
+ * alignment (similarity != 0) has aStart = aEnd = a_len = b_len = 0.  n_launches (may be NULL): k_cons_sw launches used.
+ * CRASS_ERR_INVALID_ARG (nothing launched): len < 1, start < 0, start + len > read_len, an empty DR, chars out of range.
+ * CRASS_CONS_SW_BUDGET (environment, bytes, read per call): the traceback scratch budget per launch (default 1 GB).        */
+int crass_hip_smith_waterman_batch(int device, const char *chars, uint64_t n_chars, const uint64_t *read_off, const uint32_t *read_len,
+                                   const uint64_t *dr_off, const uint32_t *dr_len, const int32_t *start, const int32_t *len, uint64_t n,
+                                   double similarity, int32_t *a_start, int32_t *a_end, int32_t *a_off, int32_t *a_len, int32_t *b_off,
+                                   int32_t *b_len, uint32_t *n_launches);
+
 /* ---- the stages behind findConsensusDRs: spacer graph + crass's output files ----
  * replaces, for a caller that wants crass's outputs from the hand-off: WorkHorse::buildGraph / cleanGraph / makeSpacerGraphs /
  * cleanSpacerGraphs / splitIntoContigs / generateFlankers / removeLowConfidenceNodeManagers (WorkHorse.cpp:196-277 ->

@@ -20,11 +20,11 @@
  *   smithWaterman / findMax                src/crass/SmithWaterman.cpp:68-129,151-308
  *   drHasHighlyAbundantKmers               src/crass/libcrispr.cpp:1077-1117
  *
- * Pinning: ksw_align against the COMPILED ksw.c (oracle/_ref; tests/test_oracle_consensus.py); Levenshtein and
- * reverseComplement as in crass_oracle.c; everything above them by the known answers SURVEY §8c recorded from the
- * compiled reference (true DR strings, group ids and per-group read counts on the reference's regression inputs).
- * Aligner.cpp / SmithWaterman.cpp / ReadHolder.cpp / WorkHorse.cpp themselves include the autoconf config.h and are
- * not buildable here; no record-level vectors of theirs exist: "parity pinned at group level".
+ * Pinning: ksw_align against the COMPILED ksw.c and smithWaterman against the COMPILED SmithWaterman.cpp (oracle/_ref,
+ * built against an empty config.h; tests/test_oracle_consensus.py); Levenshtein and reverseComplement as in
+ * crass_oracle.c; everything above them by the known answers SURVEY §8c recorded from the compiled reference (true DR
+ * strings, group ids and per-group read counts on the reference's regression inputs).  Aligner.cpp / ReadHolder.cpp /
+ * WorkHorse.cpp are not built (libcrispr.cpp's PACKAGE_NAME, Xerces-C): "parity pinned at group level" above the leaves.
  */
 #include "crass_oracle.h"
 

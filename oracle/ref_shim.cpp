@@ -2,12 +2,13 @@
  * ref_shim.cpp — extern "C" harness over the *unmodified, compiled reference sources*.
  *
  * TEST INFRASTRUCTURE ONLY.  oracle/Makefile compiles this file together with
- *   /root/reference/src/crass/{PatternMatcher,StringCheck,kseq}.cpp, ksw.c (klib's SSE2 Smith-Waterman, includes only ksw.h)
- *   /root/reference/src/aho-corasick/{acism,acism_create,acism_file,msutil}.c
- * straight from where they lie into oracle/_ref/libcrass_ref.so (git-ignored).
- * Those are the hot-path reference files that compile without generated code
- * (autoconf config.h) or Xerces-C; libcrispr.cpp / ReadHolder.cpp / WorkHorse.cpp
- * need both and are therefore NOT built (see DESIGN.md "Oracle").
+ *   src/crass/{PatternMatcher,StringCheck,kseq}.cpp, ksw.c (klib's SSE2 Smith-Waterman, includes only ksw.h)
+ *   src/crass/{SmithWaterman,LoggerSimp}.cpp (include autoconf's config.h but use nothing from it: compiled
+ *                                            against an empty one the Makefile writes into _ref/inc/)
+ *   src/aho-corasick/{acism,acism_create,acism_file,msutil}.c
+ * of the reference tree, straight from where they lie into oracle/_ref/libcrass_ref.so (git-ignored).
+ * libcrispr.cpp / WorkHorse.cpp need more (PACKAGE_NAME from config.h, Xerces-C) and are NOT built
+ * (see DESIGN.md "Oracle").
  *
  * The functions here only marshal arguments; the algorithms are the reference's.
  */
@@ -28,6 +29,9 @@ extern "C" {
 #include "acism.h"
 }
 #include "ksw.h"
+#include "SmithWaterman.h"
+#include "LoggerSimp.h"
+#include "Exception.h"
 
 extern "C" {
 
@@ -163,6 +167,31 @@ void ref_ksw_align(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, c
     kswr_t r = ksw_align(qlen, query, tlen, target, m, mat, gapo, gape, xtra, &qp);
     free(qp);
     *score = r.score; *te = r.te; *qe = r.qe; *tb = r.tb; *qb = r.qb;
+}
+
+/* smithWaterman (SmithWaterman.cpp:151-308) as ReadHolder::updateStartStops calls it (ReadHolder.cpp:438,481).  a_ret and
+ * b_ret come back as (offset, length) into seqA / seqB: a_ret starts at *aStartAlign when it is not empty, b_ret at the
+ * FIRST place seqB holds it (the same string; the reference hands back only the strings).  Returns 1 with the strings, 0
+ * when the similarity test rejected them ("", "" and zeros), -1 when the reference threw. */
+int ref_smith_waterman(const char *a, int la, const char *b, int lb, int start, int len, double similarity, int *aStart, int *aEnd,
+                       int *a_off, int *a_len, int *b_off, int *b_len)
+{
+    static bool logger_ready = false;
+    if (!logger_ready) { intialiseGlobalLogger("", 0); logger_ready = true; }
+    std::string A(a, (size_t)la), B(b, (size_t)lb);
+    int s = 0, e = 0;
+    stringPair p;
+    try {
+        p = smithWaterman(A, B, &s, &e, start, len, similarity);
+    } catch (crispr::exception &) {
+        return -1;
+    }
+    *aStart = s; *aEnd = e;
+    *a_len = (int)p.first.size(); *b_len = (int)p.second.size();
+    *a_off = p.first.empty() ? 0 : s;
+    const size_t bo = B.find(p.second);
+    *b_off = p.second.empty() || bo == std::string::npos ? 0 : (int)bo;
+    return (similarity != 0 && p.first.empty()) ? 0 : 1;
 }
 
 /* ---- calibration loops (see oracle/crass_oracle.c orc_calib_*): the reference's two hot

@@ -156,6 +156,10 @@ def ref():
                                     C.POINTER(C.c_int)]
         R.ref_kseq_dump.restype = C.c_long
         R.ref_free.argtypes = [C.c_void_p]
+        if hasattr(R, "ref_smith_waterman"):
+            R.ref_smith_waterman.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double] + \
+                [C.POINTER(C.c_int)] * 6
+            R.ref_smith_waterman.restype = C.c_int
         if hasattr(R, "ref_ksw_align"):
             R.ref_ksw_align.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + \
                 [C.POINTER(C.c_int)] * 5
@@ -354,10 +358,15 @@ def ksw_align(query, target, impl="oracle", mat=ALIGNER_MAT, gapo=5, gape=2, xtr
     return tuple(o.value for o in out)
 
 
-def smith_waterman(a, b, start, length, similarity=0.85):
+def smith_waterman(a, b, start, length, similarity=0.85, impl="oracle"):
+    """smithWaterman(a, b, &aStart, &aEnd, start, length, similarity) -> (ret, aStart, aEnd, a_ret, b_ret); ret 1: the strings,
+    0: rejected by the similarity test, -1: the reference throws (impl "ref": the compiled SmithWaterman.cpp)"""
     o = [C.c_int() for _ in range(6)]
-    r = lib().orc_smith_waterman(a, len(a), b, len(b), C.byref(o[0]), C.byref(o[1]), start, length, similarity,
-                                 C.byref(o[2]), C.byref(o[3]), C.byref(o[4]), C.byref(o[5]))
+    if impl == "oracle":
+        r = lib().orc_smith_waterman(a, len(a), b, len(b), C.byref(o[0]), C.byref(o[1]), start, length, similarity,
+                                     C.byref(o[2]), C.byref(o[3]), C.byref(o[4]), C.byref(o[5]))
+    else:
+        r = ref().ref_smith_waterman(a, len(a), b, len(b), start, length, similarity, *[C.byref(x) for x in o])
     return r, o[0].value, o[1].value, a[o[2].value:o[2].value + o[3].value], b[o[4].value:o[4].value + o[5].value]
 
 

@@ -142,6 +142,28 @@ def test_group_argument_validation_needs_no_gpu(ca):
         assert lib.crass_hip_group_create(C.byref(p), devs, 2, 1, C.byref(h)) == 3
 
 
+def test_alignment_batch_argument_validation_needs_no_gpu(ca):
+    """crass_hip_ksw_batch / crass_hip_smith_waterman_batch refuse what the kernels do not handle before they touch a device:
+    a query over k_cons_ksw's LDS cap (320 codes), codes above 4, smithWaterman windows outside the reference's domain"""
+    for cases, status in [([([0, 1] * 160 + [2], [0, 1, 2])], 2), ([([0, 5], [0, 1])], 1), ([([], [0, 1])], 1), ([([0, 1], [])], 1)]:
+        with pytest.raises(ca.CrassError) as e:
+            ca.ksw_batch(cases)
+        assert e.value.status == status, cases
+    read, dr = b"ACGTACGTAC", b"ACGT"
+    for task in [(read, dr, 0, 0), (read, dr, 5, 6), (read, dr, -1, 3), (read, b"", 0, 4)]:
+        with pytest.raises(ca.CrassError) as e:
+            ca.smith_waterman_batch([(read, dr, 0, 4), task])
+        assert e.value.status == 1, task
+    import torch
+    if not torch.cuda.is_available():                   # valid arguments, no device
+        with pytest.raises(ca.CrassError) as e:
+            ca.ksw_batch([([0, 1] * 160, [0, 1, 2])])
+        assert e.value.status == 3
+        with pytest.raises(ca.CrassError) as e:
+            ca.smith_waterman_batch([(read, dr, 0, 10)])
+        assert e.value.status == 3
+
+
 def test_missing_rccl_is_an_error_code_not_a_crash(tmp_path):
     """a group whose RCCL library cannot be loaded must come back with CRASS_ERR_RCCL and a text, before any device is
     touched (the loader used to read dlerror() twice: the second read is NULL).  In a child process: the binding is per process."""

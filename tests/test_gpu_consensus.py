@@ -130,3 +130,51 @@ def test_a_gid_without_a_group_is_skipped_and_bad_tokens_are_refused(ca):
     with pytest.raises(ca.CrassError) as e:
         ca.consensus(seqs, bad)
     assert e.value.status == 1
+
+
+def to_orc_params(p):
+    return orc.Params(p.lowDRsize, p.highDRsize, p.lowSpacerSize, p.highSpacerSize, p.searchWindowLength, p.minNumRepeats,
+                      p.kmer_clust_size)
+
+
+@pytest.mark.parametrize("L", [400, 500])
+def test_long_drs(ca, L):
+    """true DRs of 65..100 bases: updateStartStops' searches take k_cons_sw's serial form (DR longer than one wave)"""
+    from tests.parity import assert_same_pipeline
+    p = ca.default_params(lowDRsize=60, highDRsize=110)
+    seqs = synth_reads(ca, 20000, read_len=L, n_dr=6, dr_len_min=65, dr_len_max=100, spacer_len_min=30, spacer_len_max=45,
+                       crispr_per_million=200000)
+    search = ca.search_pipeline(seqs, params=p)
+    ref_search = orc.pipeline(seqs, params=to_orc_params(p))
+    assert_same_pipeline(search, ref_search)
+    gpu = ca.consensus(seqs, search, params=p)
+    ref = orc.consensus(seqs, ref_search, params=to_orc_params(p))
+    assert_same_consensus(gpu, ref)
+    assert max(len(d) for d in gpu.true_drs) > 64
+    assert gpu.counters["n_sw_tasks"] > 0
+
+
+@pytest.mark.parametrize("L,n", [(1500, 2000), (10000, 300)])
+def test_long_reads(ca, L, n):
+    """CRISPR arrays inside long reads: windows past k_cons_sw's LDS (the direction matrix in global scratch) and a coverage
+    array over 64 KB (kConsArrayMul x read length x 16 B: k_cons_cover with global atomics)"""
+    seqs = synth_reads(ca, n, read_len=L, n_dr=6, crispr_per_million=200000, array_min_repeats=5, array_max_repeats=30)
+    assert 4 * L * 16 > 64 * 1024
+    search = ca.search_pipeline(seqs)
+    gpu = ca.consensus(seqs, search)
+    ref = orc.consensus(seqs, orc.pipeline(seqs))
+    assert_same_consensus(gpu, ref)
+    assert len(gpu.gids) >= 4 and gpu.counters["n_sw_tasks"] > 0
+
+
+@pytest.mark.parametrize("L,n,kw", [(150, 60000, {}), (250, 60000, dict(n_dr=30, crispr_per_million=40000)),
+                                    (1500, 2000, dict(n_dr=6, crispr_per_million=200000, array_min_repeats=5, array_max_repeats=30))])
+def test_small_sw_scratch_budget_keeps_the_result(ca, monkeypatch, L, n, kw):
+    """CRASS_CONS_SW_BUDGET (read per call) cuts the smithWaterman batch into many launches where its tasks need scratch (the
+    250- and 1 500-base reads; the 150-base tasks all keep their direction matrix in LDS): the same result"""
+    kw = dict(dict(crispr_per_million=20000), **kw)
+    seqs = synth_reads(ca, n, read_len=L, **kw)
+    search = ca.search_pipeline(seqs)
+    ref = orc.consensus(seqs, orc.pipeline(seqs))
+    monkeypatch.setenv("CRASS_CONS_SW_BUDGET", "65536")
+    assert_same_consensus(ca.consensus(seqs, search), ref)
