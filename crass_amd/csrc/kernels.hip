@@ -221,6 +221,23 @@ static __device__ __forceinline__ uint32_t pk_nonzero_u16(uint32_t a)
 }
 typedef uint32_t ff_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t ff_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+// The W packed words of read r (r < n_reads).
+template <int W, int N>
+static __device__ __forceinline__ void ff_load_words(const DevReads &R, uint64_t r, uint32_t (&w)[N])
+{
+    const uint32_t *g = R.packed + r * (uint64_t)W;
+    // a row is dword-aligned only; global_load_dwordx4 takes that on gfx950, so W words are W/4 wide loads and a tail
+#pragma unroll
+    for (int i = 0; i + 4 <= W; i += 4) {
+        const ff_u32x4 v = *reinterpret_cast<const ff_u32x4 *>(g + i);
+        w[i] = v.x; w[i + 1] = v.y; w[i + 2] = v.z; w[i + 3] = v.w;
+    }
+    if ((W & 3) >= 2) {
+        const ff_u32x2 v = *reinterpret_cast<const ff_u32x2 *>(g + (W & ~3));
+        w[W & ~3] = v.x; w[(W & ~3) + 1] = v.y;
+    }
+    if (W & 1) w[W - 1] = g[W - 1];
+}
 // One read's row (W words, zero when r is past the end) and its exception flag.
 template <int W>
 static __device__ __forceinline__ void ff_load_row(const DevReads &R, const DevParams &P, uint64_t r, uint32_t (&w)[W], uint64_t &exc_word)
@@ -235,20 +252,46 @@ static __device__ __forceinline__ void ff_load_row(const DevReads &R, const DevP
         const uint32_t *e = R.exc_mask + 2 * wave_word;
         exc_word = (uint64_t)e[0] | ((uint64_t)e[1] << 32);
     }
-    if (r < R.n_reads) {
-        const uint32_t *g = R.packed + r * (uint64_t)W;
-        // a row is dword-aligned only; global_load_dwordx4 takes that on gfx950, so W words are W/4 wide loads and a tail
+    if (r < R.n_reads) ff_load_words<W>(R, r, w);
+}
+
+// The scan of one row: acc[k] halfword h becomes 0 iff the 8-mer at seed 8 (2k + h) re-occurs at some shift D0 .. D1.
+template <int D0, int D1, int LCT, int WX, int SW>
+static __device__ __forceinline__ void ff_exact_scan(const uint32_t (&w)[WX], uint32_t (&acc)[SW])
+{
 #pragma unroll
-        for (int i = 0; i + 4 <= W; i += 4) {
-            const ff_u32x4 v = *reinterpret_cast<const ff_u32x4 *>(g + i);
-            w[i] = v.x; w[i + 1] = v.y; w[i + 2] = v.z; w[i + 3] = v.w;
+    for (int i = 0; i < SW; i++) acc[i] = 0xFFFFFFFFu;
+#pragma unroll
+    for (int d = D0; d <= D1; d++) {
+        const int q = d >> 4;
+        const int sh = (d & 15) * 2;
+#pragma unroll
+        for (int k = 0; k < SW; k++) {
+            if (LCT > 0 && d > LCT - 9 - 16 * k) continue;               // window past the read end for both seeds of word k
+            uint32_t lo = w[k + q], hi = w[k + q + 1];
+            uint32_t s = sh ? ((lo >> sh) | (hi << (32 - sh))) : lo;      // v_alignbit_b32
+            uint32_t x = s ^ w[k];
+            // per-halfword running minimum: a halfword of acc becomes 0 iff some x halfword was 0
+            acc[k] = pk_min_u16(acc[k], x);
         }
-        if ((W & 3) >= 2) {
-            const ff_u32x2 v = *reinterpret_cast<const ff_u32x2 *>(g + (W & ~3));
-            w[W & ~3] = v.x; w[(W & ~3) + 1] = v.y;
-        }
-        if (W & 1) w[W - 1] = g[W - 1];
     }
+}
+// ... and its hint: bit h set iff lattice seed j = 8h may have a hit (superset); halfwords 0 .. n_seed-1 hold lattice seeds.
+template <int LCT, int SW>
+static __device__ __forceinline__ uint32_t ff_exact_hint(const uint32_t (&acc)[SW], int n_seed)
+{
+    // min(halfword, 1) is 0 exactly for a hit; the words are folded two bits apart (low halfwords -> bits 2k, high -> bits
+    // 2k + 16) and the halves interleaved at the end
+    uint32_t t0 = 0, t1 = 0;                        // words 0..7 and 8..15 (a fold holds 16 seeds)
+#pragma unroll
+    for (int k = 0; k < SW; k++) {
+        if (LCT > 0 && 2 * k >= n_seed) continue;
+        const uint32_t f = pk_nonzero_u16(acc[k]);
+        if (k < 8) t0 |= f << (2 * k); else t1 |= f << (2 * (k - 8));
+    }
+    uint32_t miss = (t0 | (t0 >> 15)) & 0xFFFFu;
+    if (SW > 8) miss |= (t1 | (t1 >> 15)) << 16;
+    return ~miss & (n_seed >= 32 ? 0xFFFFFFFFu : ((1u << n_seed) - 1u));
 }
 
 // RPL: reads per lane.  A lane's reads are 256 apart (a wave still covers 64 consecutive reads, one mask word); the row of the
@@ -278,44 +321,122 @@ __global__ __launch_bounds__(256) void k_filter_fast_impl(DevReads R, DevParams 
     // seeds live in halfwords 0 .. searchEnd/8 with searchEnd = L-58 <= 16W-58: only words < SW hold one
     constexpr int SW = ((16 * W - 58) / 8 + 2) / 2;
     uint32_t acc[SW];
-#pragma unroll
-    for (int i = 0; i < SW; i++) acc[i] = 0xFFFFFFFFu;
-#pragma unroll
-    for (int d = D0; d <= D1; d++) {
-        const int q = d >> 4;
-        const int sh = (d & 15) * 2;
-#pragma unroll
-        for (int k = 0; k < SW; k++) {
-            if (LCT > 0 && d > LCT - 9 - 16 * k) continue;               // window past the read end for both seeds of word k
-            uint32_t lo = w[k + q], hi = w[k + q + 1];
-            uint32_t s = sh ? ((lo >> sh) | (hi << (32 - sh))) : lo;      // v_alignbit_b32
-            uint32_t x = s ^ w[k];
-            // per-halfword running minimum: a halfword of acc becomes 0 iff some x halfword was 0
-            acc[k] = pk_min_u16(acc[k], x);
-        }
-    }
+    ff_exact_scan<D0, D1, LCT>(w, acc);
     bool hit = false;
     // a uniform-length instantiation knows the seed count at compile time (D0 = lowDR + lowSp, checked by the launcher)
     const int searchEnd = LCT > 0 ? (LCT - D0 - 8 - 1) : (int)(L - P.lowDR - P.lowSp - 8 - 1);
     if (active && !exc && searchEnd >= 0) {
-        const int n_seed = searchEnd / 8 + 1;           // halfwords 0 .. n_seed-1 hold lattice seeds
-        // bit h of the hint: lattice seed j = 8h may have a hit (superset).  min(halfword, 1) is 0 exactly for a hit; the words
-        // are folded two bits apart (low halfwords -> bits 2k, high -> bits 2k + 16) and the halves interleaved at the end
-        uint32_t t0 = 0, t1 = 0;                        // words 0..7 and 8..15 (a fold holds 16 seeds)
-#pragma unroll
-        for (int k = 0; k < SW; k++) {
-            if (LCT > 0 && 2 * k >= n_seed) continue;
-            const uint32_t f = pk_nonzero_u16(acc[k]);
-            if (k < 8) t0 |= f << (2 * k); else t1 |= f << (2 * (k - 8));
-        }
-        uint32_t miss = (t0 | (t0 >> 15)) & 0xFFFFu;
-        if (SW > 8) miss |= (t1 | (t1 >> 15)) << 16;
-        const uint32_t hint = ~miss & (n_seed >= 32 ? 0xFFFFFFFFu : ((1u << n_seed) - 1u));
+        const uint32_t hint = ff_exact_hint<LCT>(acc, searchEnd / 8 + 1);
         hit = hint != 0;
         if (hit) seed_hint[r] = hint;                   // sparse: ~2 % of the lanes
     }
     uint64_t m = __ballot(hit);
     if ((threadIdx.x & 63) == 0 && active) hitmask[r >> 6] = m;
+    }
+}
+
+// The same filter with two shifts folded per minimum (gfx950: v_bitop3_b32, v_pk_minimum3_f16), for uniform lengths and RPL rows.
+// LOOSE scan: x = (s ^ w[k]) & 0x3FFF3FFF is one v_bitop3_b32; a halfword of it read as f16 has sign 0 and an exponent below
+// all-ones (no NaN, no Inf; denormals are kept: profiles/ubench/valu_rate_asm_bitop3_mi355x.txt checks every triple), so
+// v_pk_minimum3_f16 is the UNSIGNED minimum of three such words: acc = minimum3(acc, x_d, x_d+1), three instructions per two
+// (word, shift) pairs instead of four.  The mask drops the seed's eighth base from the comparison: a zero halfword now means "the
+// 7-mer re-occurs", which every exact hit is and ~3 % of random reads are.  EXACT recheck: loose-positive lanes queue their read
+// in LDS; when the block's rows are done its waves take 64 queued reads at a time, reload their rows (L2-hot) and run
+// k_filter_fast_impl's own scan, which decides the read's mask bit and hint.  hitmask and seed_hint are bit for bit
+// k_filter_fast_impl's.  A wave's mask word gets its bits from rechecked reads of other lanes, so the block's 4 RPL words are
+// built in LDS and stored once each at the end.
+static __device__ __forceinline__ uint32_t pk_minimum3_f16(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+template <int W, int D0, int D1, int LCT, int RPL>
+__global__ __launch_bounds__(256) void k_filter_fast_pairs(DevReads R, DevParams P, uint64_t *hitmask, uint32_t *seed_hint, uint8_t *clear_found)
+{
+    static_assert(LCT > 0 && LCT - D0 - 9 >= 0 && RPL * 256 <= 65536, "uniform length with at least one seed");
+    __shared__ uint32_t q_n;
+    __shared__ uint16_t q[256 * RPL];                   // reads to recheck, as offsets into the block (every lane and row at most once)
+    __shared__ uint32_t tile_mask[2 * 4 * RPL];         // the block's mask words, as 32-bit halves
+    const uint64_t r_block = blockIdx.x * (uint64_t)(256 * RPL);
+    const uint64_t r_first = r_block + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (clear_found && r_first == 0) clear_found[R.n_reads] = 0;
+    constexpr int WX = W + (D1 >> 4) + 2;
+    constexpr int SW = ((16 * W - 58) / 8 + 2) / 2;
+    constexpr int n_seed = (LCT - D0 - 9) / 8 + 1;
+    constexpr uint32_t M14 = 0x3FFF3FFFu;
+    uint32_t nxt[W];
+    uint64_t nxt_exc;
+    ff_load_row<W>(R, P, r_first, nxt, nxt_exc);
+    if (threadIdx.x < 2 * 4 * RPL) tile_mask[threadIdx.x] = 0;
+    if (threadIdx.x == 0) q_n = 0;
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < RPL; it++) {
+        const uint64_t r = r_first + (uint64_t)it * 256u;
+        const bool active = r < R.n_reads;
+        if (clear_found && active) clear_found[r] = 0;
+        uint32_t w[WX];
+#pragma unroll
+        for (int i = 0; i < WX; i++) w[i] = i < W ? nxt[i] : 0u;
+        const bool exc = (nxt_exc >> (r & 63)) & 1u;
+        if (it + 1 < RPL) ff_load_row<W>(R, P, r + 256u, nxt, nxt_exc);
+        uint32_t acc[SW];
+#pragma unroll
+        for (int i = 0; i < SW; i++) acc[i] = 0x3C003C00u;
+#pragma unroll
+        for (int d = D0; d <= D1; d += 2) {
+#pragma unroll
+            for (int k = 0; k < SW; k++) {
+                if (d > LCT - 9 - 16 * k) continue;
+                const int q0 = d >> 4, sh0 = (d & 15) * 2;
+                const uint32_t s0 = sh0 ? __builtin_amdgcn_alignbit(w[k + q0 + 1], w[k + q0], sh0) : w[k + q0];
+                const uint32_t a = (s0 ^ w[k]) & M14;                                   // v_bitop3_b32
+                uint32_t b = a;                                                         // (an odd shift left over)
+                if (d + 1 <= D1 && d + 1 <= LCT - 9 - 16 * k) {
+                    const int q1 = (d + 1) >> 4, sh1 = ((d + 1) & 15) * 2;
+                    const uint32_t s1 = sh1 ? __builtin_amdgcn_alignbit(w[k + q1 + 1], w[k + q1], sh1) : w[k + q1];
+                    b = (s1 ^ w[k]) & M14;
+                }
+                acc[k] = pk_minimum3_f16(acc[k], a, b);
+            }
+        }
+        // loose-positive: some seed halfword is zero (a seedless high half of the last word may count: the recheck decides)
+        uint32_t m = 0x3C003C00u;
+#pragma unroll
+        for (int k = 0; 2 * k < n_seed; k += 2) m = pk_minimum3_f16(m, acc[k], 2 * (k + 1) < n_seed ? acc[k + 1] : acc[k]);
+        const bool pos = active && !exc && pk_nonzero_u16(m) != 0x00010001u;
+        const uint64_t pm = __ballot(pos);
+        if (pm) {                                                                       // (wave-uniform)
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&q_n, (uint32_t)__popcll(pm));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+            if (pos) q[base + before] = (uint16_t)(it * 256 + threadIdx.x);
+        }
+    }
+    __syncthreads();
+    const uint32_t qn = q_n;
+    for (uint32_t b0 = threadIdx.x & ~63u; b0 < qn; b0 += 256u) {                        // (wave-uniform)
+        const bool have = b0 + lane < qn;
+        const uint32_t loc = have ? q[b0 + lane] : 0u;
+        uint32_t w[WX];
+#pragma unroll
+        for (int i = 0; i < WX; i++) w[i] = 0u;
+        if (have) ff_load_words<W>(R, r_block + loc, w);
+        uint32_t acc[SW];
+        ff_exact_scan<D0, D1, LCT>(w, acc);
+        const uint32_t hint = ff_exact_hint<LCT>(acc, n_seed);
+        if (have && hint != 0) {
+            seed_hint[r_block + loc] = hint;
+            atomicOr(&tile_mask[loc >> 5], 1u << (loc & 31u));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 * RPL) {
+        const uint64_t r0 = r_block + threadIdx.x * 64u;
+        if (r0 < R.n_reads) hitmask[r0 >> 6] = (uint64_t)tile_mask[2 * threadIdx.x] | ((uint64_t)tile_mask[2 * threadIdx.x + 1] << 32);
     }
 }
 
@@ -503,9 +624,12 @@ hipError_t launch_filter_fast(const DevReads &R, const DevParams &P, uint64_t *h
     static const int rpl_env = getenv("CRASS_FF_RPL") ? atoi(getenv("CRASS_FF_RPL")) : 0;
     const int rpl = rpl_env ? rpl_env : (R.n_reads >= (1u << 22) ? 4 : 1);
     dim3 g((unsigned)blocks), b(256), g4((unsigned)((blocks + 3) / 4));
-    if (cleared && clear_found) *cleared = true;            // (every path below is k_filter_fast_impl)
+    // (CRASS_FF_EXACT = 1 keeps k_filter_fast_impl where k_filter_fast_pairs would run: the A/B and the parity tests of the two)
+    static const bool ff_exact = getenv("CRASS_FF_EXACT") && atoi(getenv("CRASS_FF_EXACT")) != 0;
+    if (cleared && clear_found) *cleared = true;            // (every path below clears the found flags)
 #define FF_LEN(LL, WW) if (R.uniform_len == LL && R.stride_words == WW) { \
-        if (rpl >= 4) CRASS_LAUNCH((k_filter_fast_impl<WW, 49, 97, LL, 4>), g4, b, 0, st, R, P, hitmask, seed_hint, clear_found); \
+        if (rpl >= 4 && !ff_exact) CRASS_LAUNCH((k_filter_fast_pairs<WW, 49, 97, LL, 4>), g4, b, 0, st, R, P, hitmask, seed_hint, clear_found); \
+        else if (rpl >= 4) CRASS_LAUNCH((k_filter_fast_impl<WW, 49, 97, LL, 4>), g4, b, 0, st, R, P, hitmask, seed_hint, clear_found); \
         else CRASS_LAUNCH((k_filter_fast_impl<WW, 49, 97, LL, 1>), g, b, 0, st, R, P, hitmask, seed_hint, clear_found); \
         return hipGetLastError(); }
     FF_LEN(100, 7) FF_LEN(101, 7) FF_LEN(125, 8) FF_LEN(126, 8) FF_LEN(150, 10) FF_LEN(151, 10) FF_LEN(250, 16) FF_LEN(251, 16)
