@@ -99,6 +99,8 @@ def lib():
         L.orc_search_core.argtypes = [C.c_char_p, C.c_int, C.POINTER(Params), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32)]
         L.orc_has_lattice_hit.argtypes = [C.c_char_p, C.c_int, C.POINTER(Params)]
+        L.orc_stats_get.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
+        L.orc_stats_get.restype = None
         L.orc_dr_low_lexi.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_char_p,
                                       C.POINTER(C.c_int)]
         L.orc_ac_create.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.c_uint32]
