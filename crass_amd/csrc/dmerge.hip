@@ -194,6 +194,11 @@ static __device__ __forceinline__ uint32_t rset_hash(uint32_t g, uint32_t w, uin
 {
     return ((w * 0x9E3779B1u) ^ (g * 0x85EBCA6Bu)) >> (32u - log_size);
 }
+// a needle's key and a haystack window's key are cut to the same min(16, min_len) bases (kAnchor in merge.cpp): a member of 15
+// bases has no sixteenth base, the window that holds it has one
+static __device__ __forceinline__ uint32_t rset_mask(const DevMerge &M) { return M.min_len >= 16u ? 0xFFFFFFFFu : (1u << (2u * M.min_len)) - 1u; }
+// the anchor keys' mask: akey_bases bases (16, or 12 = a 24-bit key; see kDevMinDR)
+static __device__ __forceinline__ uint32_t akey_mask(const DevMerge &M) { return M.akey_bases >= 16u ? 0xFFFFFFFFu : (1u << (2u * M.akey_bases)) - 1u; }
 __global__ __launch_bounds__(1024) void k_dm_greedy(DevMerge M)
 {
     if (dm_abandoned(M)) return;
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(1024) void k_dm_greedy(DevMerge M)
             __hip_atomic_store(&M.root_of[t], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (M.ablate & 4u) continue;
             // 4a. needle key of this member
-            const uint32_t g = root + 1, w = (uint32_t)M.packed[(uint64_t)t * 4];
+            const uint32_t g = root + 1, w = (uint32_t)M.packed[(uint64_t)t * 4] & rset_mask(M);
             const unsigned long long want = ((unsigned long long)g << 32) | w;            // g >= 1: never 0
             const uint32_t mask = (1u << M.rset_log) - 1u;
             uint32_t h = rset_hash(g, w, M.rset_log);
@@ -261,11 +266,11 @@ __global__ __launch_bounds__(1024) void k_dm_greedy(DevMerge M)
 // ---- 4. removeRedundantRepeats: a member is dropped iff a strictly shorter member of its group, or
 // that member's reverse complement, occurs in it (equal-length members are distinct strings; the
 // relation is transitive, so "blanked earlier" never matters).  t or rc(t) in s <=> t in s or in rc(s).
-// The needles are indexed by (group root, first 16 bases): every member claims its key in an open-addressing
+// The needles are indexed by (group root, first min(16, min_len) bases): every member claims its key in an open-addressing
 // set (4a, above) and the members of one key are laid out contiguously ({len | token << 32, bits lo, bits hi, N mask}):
 // 4b allocates the keys' ranges, 4c fills them.  A member j then probes the index with every window of its own string
 // and of its reverse complement in which a member (>= 23 bases) could still start, and compares only the few
-// candidates that share the window's first 16 bases — instead of trying every shorter member at every shift.
+// candidates that share the window's first 16 (or min_len) bases — instead of trying every shorter member at every shift.
 __global__ __launch_bounds__(256) void k_dm_rd_bases(DevMerge M)
 {
     if (dm_abandoned(M)) return;
@@ -325,7 +330,7 @@ __global__ __launch_bounds__(256) void k_dm_redundant(DevMerge M)
             const uint64_t wm = (o ? mrj : mfj) >> (act ? p : 0u);           // 'N' positions of the window
             uint32_t cnt = 0, base = 0;
             if (act && !(M.ablate & 32u)) {
-                const uint32_t w = (uint32_t)w0;
+                const uint32_t w = (uint32_t)w0 & rset_mask(M);
                 const unsigned long long want = ((unsigned long long)g << 32) | w;
                 uint32_t h = rset_hash(g, w, M.rset_log);
                 for (;;) {
@@ -373,7 +378,8 @@ __global__ __launch_bounds__(256) void k_dm_redundant(DevMerge M)
     if (threadIdx.x == 0) { const uint32_t tot = surv_w[0] + surv_w[1] + surv_w[2] + surv_w[3]; if (tot) atomicAdd(&M.hot[dm_hot(kHotSurvivors, blockIdx.x)], tot); }
 }
 
-// ---- 6a. anchor keys: every 16-mer at offset 0..7 of a pattern (see kernels.hip, pass-2 fast path).  A member that
+// ---- 6a. anchor keys: every 16-mer at offset 0..7 of a pattern — or, patterns of fewer than 23 / 19 bases, the 16-mers / 12-mers at
+// offsets 0..3 (kDevMinDR, engine_internal.h) — (see kernels.hip, pass-2 fast path).  A member that
 // survived is a pattern (pid 2t) and so is its reverse complement (pid 2t + 1, WorkHorse.cpp:690-697); entry
 // e = pid * 8 + r = 16 t + 8 o + r.  Distinct keys are claimed in an open-addressing set and counted (thread per entry:
 // a wave-per-member form inside k_dm_redundant ran the claims at a quarter of the lanes behind that kernel's probe
@@ -386,9 +392,11 @@ __global__ __launch_bounds__(256) void k_dm_keys(DevMerge M)
     const uint32_t t = e >> 4, o = (e >> 3) & 1u, r = e & 7u;
     uint32_t slot = 0xFFFFFFFFu, my_key = 0xFFFFFFFFu, won = 0u;
     const bool in_range = t < dm_ntok(M);               // (no early return: the block meets at the end)
-    // (anchor windows every 4 bases — patterns of 19 .. 22 bases — : offsets 0 .. 3 only; the entry numbering stays 16 per token)
+    // (anchor windows every 4 bases — patterns of 15 .. 22 bases — : offsets 0 .. 3 only; the entry numbering stays 16 per token)
+    // A 12-base key is a 24-bit value: it is never 0xFFFFFFFF, so the free-slot sentinel of the table and the all-T flag need no
+    // second form — all_t stays 0, k_dm_fill_finish fills the free slots with a member key, and a masked window never equals a free slot.
     if (in_range && !M.blank[t] && r < (1u << M.akey_shift) && !(M.ablate & 512u)) {
-        const uint32_t key = (uint32_t)shr128_lo(M.packed[(uint64_t)t * 4 + 2 * o], M.packed[(uint64_t)t * 4 + 2 * o + 1], 2 * r);
+        const uint32_t key = (uint32_t)shr128_lo(M.packed[(uint64_t)t * 4 + 2 * o], M.packed[(uint64_t)t * 4 + 2 * o + 1], 2 * r) & akey_mask(M);
         const uint32_t kmask = (1u << M.kset_log) - 1u;
         const unsigned long long want = (unsigned long long)key | (1ull << 32);
         uint32_t h = kset_hash(key, M.kset_log);
@@ -1279,24 +1287,26 @@ __global__ __launch_bounds__(256) void k_dm_verify(DevReads R, DevMerge M, const
             return i < nw ? g[i] : 0u;
         };
         uint32_t best_end = 0xFFFFFFFFu, best_len = 0, best_pid = 0;      // wave-uniform
-        if (L >= 16) {
-            const uint32_t ash = M.akey_shift;                              // windows every 8 (or, patterns of 19 .. 22 bases, 4) bases
-            const uint32_t h_max = (L - 16) >> ash;
+        // (KL: bases per key.  An occurrence found through window a ends at >= a + KL, hence the two early exits below)
+        const uint32_t KL = M.akey_bases, vmask = akey_mask(M);
+        if (L >= KL) {
+            const uint32_t ash = M.akey_shift;                              // windows every 8 (or, patterns of 15 .. 22 bases, 4) bases
+            const uint32_t h_max = (L - KL) >> ash;
             for (uint32_t hb = 0; hb <= h_max; hb += 64) {
-                if (best_end <= (hb << ash) + 15) break;
+                if (best_end <= (hb << ash) + KL - 1u) break;
                 const uint32_t h = hb + lane;
                 uint32_t cnt = 0, base = 0;
                 if (h <= h_max) {
                     const uint32_t pos = h << ash, wi = pos >> 4;
                     const uint32_t lo = word(wi), hi = word(wi + 1);
-                    dv_probe(M, __builtin_amdgcn_alignbit(hi, lo, (pos & 15u) * 2u), kmask, cnt, base);
+                    dv_probe(M, __builtin_amdgcn_alignbit(hi, lo, (pos & 15u) * 2u) & vmask, kmask, cnt, base);
                 }
                 uint64_t hits = __ballot(cnt > 0);
                 while (hits) {
                     const int src = __ffsll((unsigned long long)hits) - 1;
                     hits &= hits - 1;
                     const uint32_t a = (hb + (uint32_t)src) << ash;
-                    if (best_end <= a + 15) { hits = 0; break; }              // later windows cannot end earlier
+                    if (best_end <= a + KL - 1u) { hits = 0; break; }         // later windows cannot end earlier
                     const uint32_t cnt_s = (uint32_t)__shfl((int)cnt, src), base_s = (uint32_t)__shfl((int)base, src);
                     dv_candidates(M, word, raw, L, a, cnt_s, base_s, lane, best_end, best_len, best_pid);
                 }
@@ -1324,7 +1334,7 @@ hipError_t launch_dm_verify(const DevReads &R, const DevMerge &M, const uint64_t
     if (n_max == 0) return hipSuccess;
     static const bool dv_one = getenv("CRASS_DV_ONE") != nullptr;      // A/B switch, read once per process
     // every read at most 183 bases (uniform length): three reads per wave and round
-    const bool shortr = M.akey_shift == 3 && R.uniform_len >= 16 && ((R.uniform_len - 16) >> 3) < DV_GL && ((R.uniform_len + 15) >> 4) <= DV_MAXW && !dv_one;
+    const bool shortr = M.akey_shift == 3 && M.akey_bases == 16 && R.uniform_len >= 16 && ((R.uniform_len - 16) >> 3) < DV_GL && ((R.uniform_len + 15) >> 4) <= DV_MAXW && !dv_one;
     uint64_t nb = shortr ? (n_max + 4 * DV_G - 1) / (4 * DV_G) : (n_max + 3) / 4;
     if (nb > 8192) nb = 8192;
     static const bool dv_pair = getenv("CRASS_DV_SINGLE") == nullptr;  // two candidates per lane and step (CRASS_DV_SINGLE: the A/B switch, one)

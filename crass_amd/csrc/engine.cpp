@@ -665,6 +665,17 @@ extern "C" {
 
 int crass_hip_abi_version(void) { return CRASS_HIP_ABI_VERSION; }
 
+// Test seam, not part of include/crass_hip.h: the anchor keys' shape the device path selects for a lowDRsize (dm_anchor_shape,
+// engine_internal.h) — bases per key and the windows' alignment in bases; 0 when the device path does not take that lowDRsize.
+int crassi_anchor_shape(uint32_t low_dr, uint32_t *key_bases, uint32_t *align_bases)
+{
+    uint32_t kb = 0, ash = 0;
+    const bool ok = dm_anchor_shape(low_dr, kb, ash);
+    if (key_bases) *key_bases = ok ? kb : 0u;
+    if (align_bases) *align_bases = ok ? 1u << ash : 0u;
+    return ok ? 1 : 0;
+}
+
 void crass_default_params(crass_params *p)
 {
     p->lowDRsize = 23; p->highDRsize = 47; p->lowSpacerSize = 26; p->highSpacerSize = 50;
@@ -2253,7 +2264,8 @@ static int device_merge_prepare(crass_hip_ctx *c, const char *dx_chars, const ui
     DevMerge M{};
     M.dx_chars = dx_chars; M.dx_len = dx_len; M.stride = stride; M.n_tok = n; M.d_ntok = d_ntok;
     M.thr = (uint32_t)std::max(c->prm.kmer_clust_size, 2); M.kmax = stride - 10;
-    M.min_len = (uint32_t)c->prm.lowDRsize; M.akey_shift = M.min_len >= 23u ? 3u : 2u;
+    M.min_len = (uint32_t)c->prm.lowDRsize;
+    if (!dm_anchor_shape(M.min_len, M.akey_bases, M.akey_shift)) return CRASS_ERR_STATE;      // (every caller checked lowDRsize >= kDevMinDR)
     { const char *ab = getenv("CRASS_DM_ABLATE"); M.ablate = ab ? (uint32_t)strtoul(ab, nullptr, 0) : 0u; }      // (profiling aid, read per merge)
     M.kset_log = 10; while ((1ull << M.kset_log) < 32ull * n) M.kset_log++;
     M.tab_log_alloc = 16; while (M.tab_log_alloc < 24 && (1ull << M.tab_log_alloc) < 48ull * n) M.tab_log_alloc++;
@@ -3289,6 +3301,10 @@ int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_
         {
             c->hit_cap_hint = hit_bound(c->h_count.p[0]);
         }
+        // (the probe's selectivity — 12-base keys flag some per cent of the reads, 16-base keys 0.4 % —: CRASS_MERGE_PROFILE=1)
+        if (c->env.merge_profile)
+            fprintf(stderr, "[crass_dm] recruit: anchor probe flagged %u of %llu reads (%u keys of %u bases, windows every %u)\n", c->h_count.p[0],
+                    (unsigned long long)n, c->dm.h_st.p->n_keys, c->dm.M.akey_bases, 1u << c->dm.M.akey_shift);
         if (const int bs = c->wait_bulk()) return bs;   // the step ends with the pass-1 hand-off records in host memory too
         c->q_n = *reinterpret_cast<const uint64_t *>(c->h_qblob.p);
         c->q_blob_active = true;

@@ -158,17 +158,34 @@ static constexpr uint32_t kDmxTiles = 1024;         // tiles of 1024 tokens: n_t
 // (The reference's pattern ORDER — per group, survivors then reverse complements, WorkHorse.cpp:690-697 — only exists in
 // the host view; pass 2 depends on the set alone, SURVEY a-14.)
 // The device merge and pass 2's anchor probe take DR strings of kDevMinDR .. 64 bases.  The anchor argument: a pattern P that
-// occurs at offset o of a read contains the read's aligned 16-base window at a = ceil_A(o) iff |P| >= 16 + A - 1 — every 8 bases
-// for |P| >= 23 (crass's default lowDRsize), every 4 bases for |P| >= 19 (-d 19 .. 22: four keys per pattern instead of eight,
-// twice the windows per read).  Shorter patterns (-d 8 .. 18) take the host merge and the byte-wise automaton kernels.
-static constexpr uint32_t kDevMinDR = 19;
+// occurs at offset o of a read contains the read's aligned KL-base window at a = ceil_A(o) iff |P| >= KL + A - 1 (a <= o + A - 1,
+// so a + KL <= o + KL + A - 1).  A (KL, A) pair is therefore admissible for a job iff
+//     KL + A - 1 <= lowDRsize                                                            (dm_anchor_shape below)
+// with KL in {16, 12} (a 32-bit or a 24-bit key) and A in {8, 4} (halfword or byte positions of the packed words):
+//     lowDRsize >= 23 (crass's default)   KL = 16, A = 8   eight keys per pattern and orientation
+//     lowDRsize 19 .. 22                  KL = 16, A = 4   four keys, twice the windows per read
+//     lowDRsize 15 .. 18                  KL = 12, A = 4   four 24-bit keys: 12 + 4 - 1 = 15
+// The 12-base key is far less selective (a random read of 150 bases is flagged with probability ~35 K / 4^12 for K keys, some
+// per cent at thousands of patterns; measured: 1.6 % at 6 000 keys): k_dm_verify sees that share of the reads instead of 0.44 % — still an exact check of a
+// small share of the reads and not an automaton over all of them (profiles/NOTES_r08.md).
+// lowDRsize 11 .. 14 (only under -w 6 / -w 7; crass takes -d >= 8) stay on the host merge and the byte-wise automaton kernels:
+// the rule leaves them KL <= 11 at A = 4 (KL <= 7 at A = 8), and a key of 10 bases — 4^10 = 1 M values — flags about
+// 35 K / 4^10 of the reads, i.e. every third read at 10 000 keys: the "filter" would hand most of the set to the verification.
+static constexpr uint32_t kDevMinDR = 15;
+// the anchor keys' shape for a job: key length in bases and log2 of the windows' alignment; false: no admissible pair
+__host__ __device__ inline bool dm_anchor_shape(uint32_t low_dr, uint32_t &key_bases, uint32_t &akey_shift)
+{
+    key_bases = low_dr >= 19u ? 16u : 12u;
+    akey_shift = low_dr >= 23u ? 3u : 2u;
+    return low_dr >= kDevMinDR && key_bases + (1u << akey_shift) - 1u <= low_dr;
+}
 struct DevMerge {
     // input: distinct candidate DR strings in first-occurrence (= token) order
     const char *dx_chars; const uint16_t *dx_len;
     uint32_t stride, n_tok;
     const uint32_t *d_ntok;       // nullptr, or the device-side token count (n_tok is then the bound the launch is sized for)
     uint32_t min_len;             // lowDRsize: no token is shorter (kDevMinDR <= min_len)
-    uint32_t akey_shift;          // log2 of the anchor windows' alignment: 3 (every 8 bases: min_len >= 23) or 2 (every 4: min_len >= 19)
+    uint32_t akey_shift;          // log2 of the anchor windows' alignment: 3 (every 8 bases: min_len >= 23) or 2 (every 4: min_len >= 15)
     uint32_t thr;                 // max(kmer_clust_size, 2): sightings of a group that decide membership
     uint32_t kmax;                // k-mer slots per token (stride - 10)
     // per token
@@ -179,7 +196,7 @@ struct DevMerge {
     unsigned long long *bk_key;   // [kDmBadSlots] identity of the 11-mers with an 'N': laurenized 33-bit key | 1 << 40; 0 = empty
     uint32_t *root_of;            // [n_tok] first token of the token's group
     uint8_t  *blank;              // [n_tok] removed by removeRedundantRepeats
-    // needle index of removeRedundantRepeats: key = ((root + 1) << 32) | first 16 bases
+    // needle index of removeRedundantRepeats: key = ((root + 1) << 32) | first min(16, min_len) bases
     unsigned long long *rset_key; // [1 << rset_log]
     uint32_t *rset_cnt, *rset_base, *rset_fill;   // [1 << rset_log]
     uint32_t rset_log;
@@ -228,6 +245,8 @@ struct DevMerge {
     uint32_t group_cap;           // a needle key with more candidates than this sets fail bit 32: removeRedundantRepeats here
                                   // compares a window with every shorter member that shares its first 16 bases, which is
                                   // quadratic in a group of near-identical variants; the host merge handles such inputs
+    uint32_t akey_bases;          // bases per anchor key: 16, or 12 (a 24-bit key) for min_len 15 .. 18 — see kDevMinDR.  (Last on
+                                  // purpose: it takes the struct's tail padding, so no other kernel argument moves.)
 };
 
 // the words a merge polls, counts into or probes, cleared by k_dm_init — or, when the launch is sized before pass 1 has

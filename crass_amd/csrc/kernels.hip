@@ -4412,13 +4412,20 @@ static __device__ __forceinline__ bool anchor_probe_fp(const uint16_t *tab, uint
 }
 
 // ASH: log2 of the windows' alignment — 3: every 8 bases (halfword positions; patterns of >= 23 bases), 2: every 4 bases (byte
-// positions; patterns of 19 .. 22 bases, `-d 19` .. `-d 22`: twice the windows per read, see kDevMinDR)
-template <int W, int THREADS, int MODE, int ASH = 3>     // W = uniform stride in words (0: ragged / any stride)
+// positions; patterns of 15 .. 22 bases, `-d 15` .. `-d 22`: twice the windows per read, see kDevMinDR)
+// KL: bases per key — 16, or 12 (patterns of 15 .. 18 bases): the window's value is cut to 24 bits before it is hashed and
+// compared (one v_and_b32, the one ak_hash needs anyway: its top-byte term is then zero), and a window only needs KL bases
+// inside the read, so a read has one more of them at its end
+template <int W, int THREADS, int MODE, int ASH = 3, int KL = 16>     // W = uniform stride in words (0: ragged / any stride)
 static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, const DevAnchors &K, const uint32_t *ak_lds,
                                                           const uint8_t *found_flag, uint64_t *hitmask)
 {
     constexpr uint32_t PW = 16u >> ASH;              // windows per packed word (2 or 4)
     constexpr uint32_t WB = 32u / PW;                // bits between two windows (16 or 8)
+    constexpr uint32_t KMASK = KL >= 16 ? 0xFFFFFFFFu : (1u << (2 * KL)) - 1u;
+    constexpr int NWIN = W > 0 ? (16 * W - KL) / (1 << ASH) + 1 : 0;      // windows of a row of W words
+    static_assert(KL == 16 || (KL == 12 && ASH == 2), "anchor key shapes: engine_internal.h, kDevMinDR");
+    auto cut = [](uint32_t V) { return KL >= 16 ? V : (V & KMASK); };
     const uint32_t mask = 32u - K.log_size;          // right shift that keeps the top log_size bits
     const uint64_t n_tiles = (R.n_reads + 63) / 64;
     const int lane = threadIdx.x & 63;
@@ -4440,9 +4447,9 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                 if (r >= R.n_reads) break;
                 if (!(K.with_exc || !rd_is_exc(R, r)) || found_flag[rd_header_id(R, r)]) continue;
                 const uint32_t L = rd_len(R, r);
-                if (L < 16) continue;
+                if (L < (uint32_t)KL) continue;
                 const uint32_t *g = R.packed + rd_word_off(R, r);
-                const uint32_t nw = (L + 15) >> 4, h_max = (L - 16) >> ASH;
+                const uint32_t nw = (L + 15) >> 4, h_max = (L - (uint32_t)KL) >> ASH;
                 // a lane takes FOUR consecutive windows (halfword positions 4q .. 4q+3 = words 2q, 2q+1 and the low half of
                 // 2q+2): three loads serve four probes, one ballot decides 256 windows, and the words of the next round are
                 // requested before this round is probed (one window per lane and round was 20 dependent round trips per
@@ -4464,7 +4471,7 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
 #pragma unroll
                     for (uint32_t i = 0; i < PL; i++) {
                         const uint32_t V = i < PW ? __builtin_amdgcn_alignbit(b, a, (i * WB) & 31u) : __builtin_amdgcn_alignbit(c3, b, ((i - PW) * WB) & 31u);
-                        if (h + i <= h_max) f = f | probe(V);
+                        if (h + i <= h_max) f = f | probe(cut(V));
                     }
                     if (__ballot(f)) { bits |= 1ull << k; break; }              // one window is enough to flag the read
                 }
@@ -4502,8 +4509,8 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
         if (r < R.n_reads && (K.with_exc || !rd_is_exc(R, r)) && !found_flag[rd_header_id(R, r)]) {
             const uint32_t L = rd_len(R, r);
             const uint32_t *g = R.packed + rd_word_off(R, r);
-            if (L >= 16) {
-                const uint32_t h_max = (L - 16) >> ASH;          // last window position (halfword, or byte) whose 16-mer is inside the read
+            if (L >= (uint32_t)KL) {
+                const uint32_t h_max = (L - (uint32_t)KL) >> ASH;          // last window position (halfword, or byte) whose 16-mer is inside the read
                 if (W > 0) {
                     uint32_t w[W + 1];
 #pragma unroll
@@ -4518,8 +4525,8 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                         typedef typename std::conditional<ASH == 3, uint32_t, uint64_t>::type pm_t;      // (up to 61 windows every 4 bases)
                         pm_t pm = 0;
 #pragma unroll
-                        for (int h = 0; h < (int)PW * (W - 1) + 1; h++) {
-                            const uint32_t V = __builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB);
+                        for (int h = 0; h < NWIN; h++) {
+                            const uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
                             // (blocked Bloom: ONE hash, one LDS word, both bits from it; a shift by a register takes the register's low
                             // five bits, so the two positions cost a shift each and the window's flag joins pm with one v_lshl_or)
                             const uint32_t h1 = ak_hash(V, K.m1);
@@ -4534,7 +4541,7 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                             uint32_t lo = 0, hi = 0;
 #pragma unroll
                             for (int i = 0; i < W; i++) { lo = kk == (uint32_t)i ? w[i] : lo; hi = kk == (uint32_t)i ? w[i + 1] : hi; }
-                            const uint32_t V = __builtin_amdgcn_alignbit(hi, lo, (h % PW) * WB);
+                            const uint32_t V = cut(__builtin_amdgcn_alignbit(hi, lo, (h % PW) * WB));
                             const uint32_t h1 = ak_hash(V, K.m1), h2 = ak_hash(V, K.m2);
                             if ((K.table[h1 >> mask] == V) | (K.table[h2 >> mask] == V)) { flag = true; pm = 0; }
                         }
@@ -4542,8 +4549,8 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                     // (uniform read length: the last window is a scalar, and "window inside the read" costs no vector compare)
                     auto scan = [&](const uint32_t hm) {
 #pragma unroll
-                        for (int h = 0; h < (int)PW * (W - 1) + 1; h++) {
-                            uint32_t V = __builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB);
+                        for (int h = 0; h < NWIN; h++) {
+                            uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
                             bool hit = MODE == 3 ? anchor_probe_fp(reinterpret_cast<const uint16_t *>(ak_lds), V, K)
                                                  : anchor_probe<(MODE == 3 || MODE == 4) ? 0 : MODE>(ak_lds, V, K, mask);
                             flag = flag | (hit & ((uint32_t)h <= hm));
@@ -4552,7 +4559,7 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                             if ((h & 7) == 7) __builtin_amdgcn_sched_barrier(0);
                         }
                     };
-                    if (R.uniform_len) scan((R.uniform_len - 16u) >> ASH);
+                    if (R.uniform_len) scan((R.uniform_len - (uint32_t)KL) >> ASH);
                     else scan(h_max);
                     }
                 } else {
@@ -4574,7 +4581,7 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
                         for (uint32_t q = 0; q < 4; q++) {
 #pragma unroll
                             for (uint32_t i = 0; i < PW; i++)
-                                if (h + PW * q + i <= h_max && probe(__builtin_amdgcn_alignbit(x[q], lo, i * WB))) flag = true;
+                                if (h + PW * q + i <= h_max && probe(cut(__builtin_amdgcn_alignbit(x[q], lo, i * WB)))) flag = true;
                             lo = x[q];
                         }
                     }
@@ -4607,7 +4614,7 @@ __global__ __launch_bounds__(THREADS) void k_anchor_filter(DevReads R, DevAnchor
 // the same filter when the key table was built on the device (dmerge.hip): its size is only known there
 // (ASH is a template parameter of the KERNEL: with both forms in one kernel the default one was allocated the other's registers —
 // 99 instead of 56 — and no other kernel's waves fitted beside its four per SIMD any more)
-template <int W, int THREADS, int ASH>
+template <int W, int THREADS, int ASH, int KL>
 __global__ __launch_bounds__(THREADS) void k_anchor_filter_dev(DevReads R, DevMerge M, const uint8_t *found_flag, uint64_t *hitmask)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t ak_lds_buf[];
@@ -4624,34 +4631,35 @@ __global__ __launch_bounds__(THREADS) void k_anchor_filter_dev(DevReads R, DevMe
         const uint32_t tsize = 1u << K.log_size;
         for (uint32_t i = threadIdx.x; i < tsize; i += THREADS) ak_lds_buf[i] = K.table[i];
         __syncthreads();
-        anchor_filter_body<W, THREADS, 0, ASH>(R, K, ak_lds_buf, found_flag, hitmask);
+        anchor_filter_body<W, THREADS, 0, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
     } else if (M.st->tab_mode == 3) {
         for (uint32_t i = threadIdx.x; i < (1u << 15); i += THREADS) ak_lds_buf[i] = M.anchor_fp[i];
         __syncthreads();
-        anchor_filter_body<W, THREADS, 3, ASH>(R, K, ak_lds_buf, found_flag, hitmask);
+        anchor_filter_body<W, THREADS, 3, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
     } else {
         for (uint32_t i = threadIdx.x; i < (1u << 15); i += THREADS) ak_lds_buf[i] = M.anchor_fp[i];
         __syncthreads();
-        anchor_filter_body<W, THREADS, 4, ASH>(R, K, ak_lds_buf, found_flag, hitmask);
+        anchor_filter_body<W, THREADS, 4, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
     }
 }
 
 hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st)
 {
     if (R.n_reads == 0) return hipSuccess;
+    if (!((M.akey_bases == 16u && (M.akey_shift == 3u || M.akey_shift == 2u)) || (M.akey_bases == 12u && M.akey_shift == 2u))) return hipErrorInvalidValue;
     const size_t lds = 128 * 1024;
     const uint64_t n_tiles = (R.n_reads + 63) / 64;
     constexpr int T = 1024;
     uint64_t blocks = (n_tiles + (T / 64) - 1) / (T / 64);
     if (blocks > 256) blocks = 256;
     hipError_t e;
-#define AKD_LAUNCH1(WW, AA)                                                                                             \
+#define AKD_LAUNCH1(WW, AA, KK)                                                                                           \
     {                                                                                                                   \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_anchor_filter_dev<WW, T, AA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_anchor_filter_dev<WW, T, AA, KK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return e;                                                                                  \
-        CRASS_LAUNCH((k_anchor_filter_dev<WW, T, AA>), dim3((unsigned)blocks), dim3(T), lds, st, R, M, found_flag, hitmask); \
+        CRASS_LAUNCH((k_anchor_filter_dev<WW, T, AA, KK>), dim3((unsigned)blocks), dim3(T), lds, st, R, M, found_flag, hitmask); \
     }
-#define AKD_LAUNCH(WW) { if (M.akey_shift == 2u) AKD_LAUNCH1(WW, 2) else AKD_LAUNCH1(WW, 3) }
+#define AKD_LAUNCH(WW) { if (M.akey_shift == 2u && M.akey_bases == 12u) AKD_LAUNCH1(WW, 2, 12) else if (M.akey_shift == 2u) AKD_LAUNCH1(WW, 2, 16) else AKD_LAUNCH1(WW, 3, 16) }
     switch (R.stride_words) {
         case 4: AKD_LAUNCH(4) break;  case 5: AKD_LAUNCH(5) break;  case 6: AKD_LAUNCH(6) break;  case 7: AKD_LAUNCH(7) break;
         case 8: AKD_LAUNCH(8) break;  case 9: AKD_LAUNCH(9) break;  case 10: AKD_LAUNCH(10) break; case 11: AKD_LAUNCH(11) break;

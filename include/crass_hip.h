@@ -296,7 +296,8 @@ typedef struct {
     float ms_recruit, ms_recruit_finish, ms_pass2_total;
     float ms_merge_host, ms_sink_host;
     uint64_t bytes_reads_device;    /* packed read bytes resident in HBM                          */
-    uint32_t anchor_keys;           /* distinct 16-mer anchor keys of the pattern set (pass 2)    */
+    uint32_t anchor_keys;           /* distinct anchor keys of the pattern set (pass 2): 16-mers;
+                                       12-mers when lowDRsize is 15 .. 18 (device-built sets)     */
     uint32_t anchor_table_kind;     /* 0 exact keys in LDS, 1 fingerprint buckets in LDS,
                                        2 exact keys probed in L2 (key set beyond LDS)             */
     uint32_t used_device_merge;     /* 1: clustering / non-redundant set / pass-2 index built on the
