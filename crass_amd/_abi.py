@@ -154,6 +154,12 @@ SYMBOLS = {
     "crass_hip_last_hip_error": (C.c_int, [C.c_void_p]),
     "crass_hip_load_reads": (C.c_int, [C.c_void_p, C.POINTER(Reads)]),
     "crass_hip_attach_device_reads": (C.c_int, [C.c_void_p, C.POINTER(Reads)]),
+    "crass_hip_load_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]),
+    "crass_hip_attach_device_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]),
+    "crass_hip_last_pack_ms": (C.c_float, [C.c_void_p]),
+    "crass_hip_get_packed": (C.c_int, [C.c_void_p, C.POINTER(Packed)]),
+    "crass_pack_layout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, u32p, u32p]),
+    "crass_pack_code4": (C.c_uint32, [C.c_uint32, u32p]),
     "crass_hip_seed_scan": (C.c_int, [C.c_void_p]),
     "crass_hip_get_candidates": (C.c_int, [C.c_void_p, C.POINTER(Candidates)]),
     "crass_hip_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64]),

@@ -641,6 +641,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     uint64_t n = 0;
     double t1 = t0;
     crass_reads r;
+    const char *dp_env = getenv("CRASS_DEVICE_PACK");
+    const bool device_pack = dp_env && *dp_env && *dp_env != '0' && !indexed && !streamed && devs.size() == 1;
+    const uint8_t *text_seq = nullptr; const uint64_t *text_off = nullptr; const uint64_t *text_hid = nullptr;
     if (indexed) {
         uint32_t ml = 0; int lr = 0;
         chk(crass_fastx_index_reads(IX.ix, &r, &ml, &lr), "crass_fastx_index_reads");
@@ -733,9 +736,14 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         }
         seq = J.seq.data(); off = J.seq_off.data(); hid = any ? J.header_id.data() : nullptr;
     }
+    // CRASS_DEVICE_PACK=1 (one context): the reader's text goes to the device as it is and is packed there (crass_hip_load_text);
+    // off by default.  The indexed and the streamed reader pack while they parse: not their switch.
+    if (device_pack) { text_seq = seq; text_off = off; text_hid = hid; memset(&r, 0, sizeof(r)); }
+    else {
     chk(crass_pack_reads(seq, off, n, 2, &J.pk), "crass_pack_reads");
     r = J.pk.reads;
     r.header_id = hid;
+    }
     }
     const double t2 = now();
     auto rss_mb = [] {
@@ -770,7 +778,10 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             chk(crass_hip_group_get_merge(made.g, &v), "crass_hip_group_get_merge");
             chk(crass_hip_group_get_recruits(made.g, &q), "crass_hip_group_get_recruits");
         } else {
-            chk(crass_hip_load_reads(made.c, &r), "crass_hip_load_reads");
+            if (device_pack) {
+                chk(crass_hip_load_text(made.c, text_seq, text_off, n, 2, text_hid, 0), "crass_hip_load_text");
+                if (timing) fprintf(stderr, "[crass_timing] %llu reads packed on the device (crass_hip_load_text)\n", (unsigned long long)n);
+            } else chk(crass_hip_load_reads(made.c, &r), "crass_hip_load_reads");
             drop_host_reads();
             chk(crass_hip_seed_scan(made.c), "crass_hip_seed_scan");
             chk(crass_hip_merge(made.c, nullptr, nullptr, 0, 0), "crass_hip_merge");

@@ -8,6 +8,7 @@
 #include "../../include/crass_hip.h"
 #include "engine_internal.h"
 #include "merge.h"
+#include "pack_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -181,6 +182,7 @@ struct EnvSwitches {
     bool no_hint_filter = false;                     // A/B switch: k_filter_general where the hint bits would be the filter
     uint32_t wave_walk_min = 800;                    // pass 2 walks a read per wave when the longest read is beyond this (CRASS_WAVE_WALK_MIN)
     uint32_t long_min = 2048;                        // read sets whose longest read is beyond this take the long-read path (CRASS_LONG_MIN: the A/B switch)
+    uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
     void read()
     {
         auto on = [](const char *n) { return getenv(n) != nullptr; };
@@ -201,6 +203,7 @@ struct EnvSwitches {
         long_min = 2048; if (const char *e = getenv("CRASS_LONG_MIN")) long_min = (uint32_t)std::max(0, atoi(e));
         no_warm_launch = getenv("CRASS_NO_WARM_LAUNCH") != nullptr;
         no_dense_light = getenv("CRASS_NO_DENSE_LIGHT") != nullptr;
+        text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
         pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
     }
 };
@@ -249,6 +252,11 @@ struct crass_hip_ctx {
     DevBuf<uint32_t> r_packed; DevBuf<uint64_t> r_word_off; DevBuf<uint32_t> r_lengths; DevBuf<uint64_t> r_header_id;
     DevBuf<uint32_t> r_exc_mask; DevBuf<uint64_t> r_exc_read; DevBuf<uint64_t> r_exc_off; DevBuf<uint8_t> r_exc_bytes;
     std::vector<uint64_t> h_exc_read;        // host copy of the exception read indices (local)
+    // crass_hip_load_text / crass_hip_attach_device_text: the text's offsets on the device (lengths that differ), the two
+    // staged chunks of a host text (pinned source of the copy, device destination) and their events
+    DevBuf<uint64_t> t_off; DevBuf<uint8_t> t_dev[2]; PinBuf<uint8_t> t_pin[2];
+    hipEvent_t ev_t_copy[2] = {nullptr, nullptr}, ev_t_pack[2] = {nullptr, nullptr}, ev_t_time[2] = {nullptr, nullptr};
+    float last_pack_ms = 0;                  // HIP-event time of the last call's pack kernels (stage timing >= 1, else 0)
 
     // scratch
     DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;
@@ -846,6 +854,13 @@ void crass_hip_destroy(crass_hip_ctx *c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     c->r_packed.release(); c->r_word_off.release(); c->r_lengths.release(); c->r_header_id.release();
     c->r_exc_mask.release(); c->r_exc_read.release(); c->r_exc_off.release(); c->r_exc_bytes.release();
+    c->t_off.release();
+    for (int k = 0; k < 2; k++) {
+        c->t_dev[k].release(); c->t_pin[k].release();
+        if (c->ev_t_copy[k]) (void)hipEventDestroy(c->ev_t_copy[k]);
+        if (c->ev_t_pack[k]) (void)hipEventDestroy(c->ev_t_pack[k]);
+        if (c->ev_t_time[k]) (void)hipEventDestroy(c->ev_t_time[k]);
+    }
     c->d_mask.release(); c->d_word_prefix.release(); c->d_block_sums.release(); c->d_idx.release(); c->d_count.release();
     c->d_found.release(); c->d_hit_info.release(); c->d_surv.release(); c->d_dr.release(); c->d_ss_pool.release();
     c->d_ss_used.release(); c->d_rec.release(); c->d_exc_hit.release(); c->d_extra.release();
@@ -972,6 +987,28 @@ static void reset_results(crass_hip_ctx *c)
     memset(&c->cnt, 0, sizeof(c->cnt));
 }
 
+// what every call that makes a read set resident ends with, once the set's arrays are on their way to the device: the
+// scratch sized by the read count, the long reads' position hints, the first call's speculation bounds and pools, counters.
+// lengths: host array, nullptr for a uniform length.
+static int finish_load(crass_hip_ctx *c, const DevReads &R, uint64_t read_index_base, uint32_t max_len, const uint32_t *lengths, uint64_t total_words)
+{
+    c->R = R;
+    c->read_base = read_index_base;
+    c->max_len = max_len;
+    c->uniform = R.uniform_len != 0;
+    c->have_reads = true;
+    int s = alloc_scratch(c);
+    if (s) return s;
+    s = setup_pos_hints(c, R.uniform_len ? nullptr : lengths, R.uniform_len, R.n_reads);
+    if (s) return s;
+    s = first_call_bounds(c);
+    if (s) return s;
+    presize_hostloop(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cnt.n_reads = R.n_reads; c->cnt.n_exceptions = R.n_exc; c->cnt.bytes_reads_device = total_words * 4;
+    return CRASS_OK;
+}
+
 int crass_hip_load_reads(crass_hip_ctx *c, const crass_reads *h)
 {
     if (!c) return CRASS_ERR_INVALID_ARG;
@@ -1033,21 +1070,7 @@ int crass_hip_load_reads(crass_hip_ctx *c, const crass_reads *h)
         R.exc_read = c->r_exc_read.p; R.exc_off = c->r_exc_off.p; R.exc_bytes = c->r_exc_bytes.p;
         HIPCHK(c, launch_build_exc_mask(R.exc_read, ne, c->r_exc_mask.p, c->stream));
     }
-    c->R = R;
-    c->read_base = h->read_index_base;
-    c->max_len = max_len;
-    c->uniform = h->uniform_len != 0;
-    c->have_reads = true;
-    int s = alloc_scratch(c);
-    if (s) return s;
-    s = setup_pos_hints(c, h->uniform_len ? nullptr : h->lengths, h->uniform_len, n);
-    if (s) return s;
-    s = first_call_bounds(c);
-    if (s) return s;
-    presize_hostloop(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->cnt.n_reads = n; c->cnt.n_exceptions = h->n_exceptions; c->cnt.bytes_reads_device = total_words * 4;
-    return CRASS_OK;
+    return finish_load(c, R, h->read_index_base, max_len, h->uniform_len ? nullptr : h->lengths, total_words);
 }
 
 int crass_hip_attach_device_reads(crass_hip_ctx *c, const crass_reads *d)
@@ -1083,6 +1106,235 @@ int crass_hip_attach_device_reads(crass_hip_ctx *c, const crass_reads *d)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cnt.n_reads = d->n_reads; c->cnt.n_exceptions = 0;
     c->cnt.bytes_reads_device = d->n_reads * (uint64_t)d->stride_words * 4;
+    return CRASS_OK;
+}
+
+// ---- sequence text in, packed on the device (pack.hip) ----
+// h_seqs (host text) or d_seqs (device text); off[n + 1] is a host array either way.  The resident set, the host mirrors and
+// the counters end up as after crass_pack_reads + crass_hip_load_reads on the same bytes.
+static int load_text_impl(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t *d_seqs, const uint64_t *off, uint64_t n,
+                            int pad_uniform, const uint64_t *header_id, uint64_t read_index_base)
+{
+    if (!c || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
+    if (n && ((!h_seqs && !d_seqs) || !off)) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    reset_results(c);
+    c->have_reads = false;                              // (a failure below must not leave the previous reads half replaced)
+    PackLayout lay;
+    if (const int ls = pack_layout(off, n, pad_uniform, &lay)) return ls;      // (nothing launched)
+    const uint64_t total_words = lay.total_words, out_words = (total_words + 4 + 3) & ~3ull;      // (the last vector store ends inside the buffer)
+    HIPCHK(c, c->r_packed.ensure(out_words));
+    DevReads R{};
+    R.packed = c->r_packed.p; R.n_reads = n; R.stride_words = lay.stride_words; R.uniform_len = lay.uniform_len;
+    std::vector<uint64_t> word_off;
+    std::vector<uint32_t> lengths;
+    if (!lay.stride_words && n) {
+        word_off.resize(n + 1);
+        uint64_t w = 0;
+        for (uint64_t i = 0; i < n; i++) { word_off[i] = w; w += (off[i + 1] - off[i] + 15) / 16; }
+        word_off[n] = w;
+        HIPCHK(c, c->r_word_off.ensure(n + 1));
+        HIPCHK(c, hipMemcpyAsync(c->r_word_off.p, word_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        R.word_off = c->r_word_off.p;
+    }
+    if (!lay.uniform_len && n) {
+        lengths.resize(n);
+        for (uint64_t i = 0; i < n; i++) lengths[i] = (uint32_t)(off[i + 1] - off[i]);
+        HIPCHK(c, c->r_lengths.ensure(n));
+        HIPCHK(c, hipMemcpyAsync(c->r_lengths.p, lengths.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        R.lengths = c->r_lengths.p;
+        HIPCHK(c, c->t_off.ensure(n + 1));              // (a uniform length needs no per-read array: off[i] = off[0] + i L)
+        HIPCHK(c, hipMemcpyAsync(c->t_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (header_id && n) {
+        HIPCHK(c, c->r_header_id.ensure(n));
+        HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, header_id, n * 8, hipMemcpyHostToDevice, c->stream));
+        R.header_id = c->r_header_id.p;
+    }
+    const uint64_t mask_words = (n + 31) / 32 + 1;
+    HIPCHK(c, c->r_exc_mask.ensure(mask_words));
+    HIPCHK(c, hipMemsetAsync(c->r_exc_mask.p, 0, mask_words * 4, c->stream));
+    R.exc_mask = c->r_exc_mask.p;
+    c->h_exc_read.clear();
+
+    PackJob J{};
+    J.off = lay.uniform_len ? nullptr : c->t_off.p;
+    J.uni_base = n ? off[0] : 0; J.uni_len = lay.uniform_len;
+    J.stride_words = lay.stride_words; J.word_off = R.word_off;
+    J.out = c->r_packed.p; J.exc_mask = c->r_exc_mask.p;
+    auto word_start = [&](uint64_t r) { return lay.stride_words ? r * (uint64_t)lay.stride_words : word_off[r]; };
+    // stage timing (crass_hip_set_stage_timing >= 1): the pack kernels between two events, crass_hip_last_pack_ms
+    c->last_pack_ms = 0;
+    const bool timed = c->timing_level >= 1 && n != 0;
+    if (timed) {
+        for (auto &e : c->ev_t_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_t_time[0], c->stream));
+    }
+    if (n == 0) {
+        HIPCHK(c, hipMemsetAsync(c->r_packed.p, 0, out_words * 4, c->stream));
+    } else if (d_seqs) {
+        J.text = d_seqs; J.bias = 0; J.r_begin = 0; J.r_end = n; J.w_begin = 0; J.w_end = out_words;
+        HIPCHK(c, launch_pack_text(J, c->stream));
+    } else {
+        // chunks of whole reads through two staged buffers: the copy of chunk k + 1 (copy stream) runs beside the pack kernel of
+        // chunk k (main stream).  Pageable text goes through the pinned buffers; text that is already pinned is copied from where it is.
+        const uint64_t text_bytes = off[n] - off[0];
+        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, lay.max_len), std::max<uint64_t>(text_bytes, 1));
+        hipPointerAttribute_t pa{};
+        const bool src_pinned = hipPointerGetAttributes(&pa, h_seqs) == hipSuccess && pa.type == hipMemoryTypeHost;
+        (void)hipGetLastError();                        // (pageable memory is reported as an invalid value: not an error of ours)
+        for (int k = 0; k < 2; k++) {
+            if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
+            if (!c->ev_t_pack[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_pack[k], hipEventDisableTiming));
+        }
+        uint64_t ra = 0;
+        for (uint64_t k = 0; ra < n; k++) {
+            const int b = (int)(k & 1);
+            uint64_t rb;                                // the chunk: reads [ra, rb), at least one
+            if (lay.uniform_len) rb = std::min<uint64_t>(n, ra + std::max<uint64_t>(1, cap / lay.uniform_len));
+            else rb = std::max<uint64_t>(ra + 1, (uint64_t)(std::upper_bound(off + ra, off + n + 1, off[ra] + cap) - off) - 1);
+            const uint64_t bytes = off[rb] - off[ra];
+            const bool last = rb == n;
+            if (bytes) {
+                HIPCHK(c, c->t_dev[b].ensure(cap + 16));
+                const uint8_t *from = h_seqs + off[ra];
+                if (!src_pinned) {
+                    HIPCHK(c, c->t_pin[b].ensure(cap));
+                    if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
+                    memcpy(c->t_pin[b].p, from, bytes);
+                    from = c->t_pin[b].p;
+                }
+                if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_t_pack[b], 0));      // (the kernel that last read this device buffer)
+                HIPCHK(c, hipMemcpyAsync(c->t_dev[b].p, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
+                HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
+                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));
+            }
+            J.text = c->t_dev[b].p; J.bias = off[ra]; J.r_begin = ra; J.r_end = rb;
+            J.w_begin = word_start(ra); J.w_end = last ? out_words : word_start(rb);
+            HIPCHK(c, launch_pack_text(J, c->stream));
+            if (bytes) HIPCHK(c, hipEventRecord(c->ev_t_pack[b], c->stream));
+            ra = rb;
+        }
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_t_time[1], c->stream));
+    // the exception list: ascending read indices from the mask (ordered look-back compaction), their bytes from the text
+    c->R = R;
+    if (n) {
+        int s = alloc_scratch(c);
+        if (s) return s;
+        const uint64_t n_words = (n + 63) / 64;
+        Lookback lbs;
+        const Lookback *lb = c->next_lookback(n_words, &lbs);
+        HIPCHK(c, launch_compact(reinterpret_cast<const uint64_t *>(c->r_exc_mask.p), n_words, n, c->d_word_prefix.p, c->d_block_sums.p, c->d_idx.p, n,
+                                 c->d_count.p, c->stream, nullptr, 0, nullptr, 0, lb));
+        HIPCHK(c, hipMemcpyAsync(c->h_count.p, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((s = c->lookback_ok())) return s;
+        const uint64_t ne = c->h_count.p[0];
+        if (ne) {
+            c->h_exc_read.resize(ne);
+            HIPCHK(c, c->r_exc_read.ensure(ne));
+            HIPCHK(c, hipMemcpyAsync(c->r_exc_read.p, c->d_idx.p, ne * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpy(c->h_exc_read.data(), c->d_idx.p, ne * 8, hipMemcpyDeviceToHost));
+            std::vector<uint64_t> exc_off(ne + 1);
+            exc_off[0] = 0;
+            for (uint64_t e = 0; e < ne; e++) { const uint64_t r = c->h_exc_read[e]; exc_off[e + 1] = exc_off[e] + (off[r + 1] - off[r]); }
+            HIPCHK(c, c->r_exc_off.ensure(ne + 1));
+            HIPCHK(c, c->r_exc_bytes.ensure(exc_off[ne] + 16));
+            HIPCHK(c, hipMemcpyAsync(c->r_exc_off.p, exc_off.data(), (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            if (d_seqs) {
+                HIPCHK(c, launch_gather_exc_text(d_seqs, 0, J.off, J.uni_base, J.uni_len, c->r_exc_read.p, c->r_exc_off.p, ne, c->r_exc_bytes.p, c->stream));
+            } else {
+                std::vector<uint8_t> bytes(exc_off[ne] + 1);
+                for (uint64_t e = 0; e < ne; e++) { const uint64_t r = c->h_exc_read[e]; memcpy(bytes.data() + exc_off[e], h_seqs + off[r], off[r + 1] - off[r]); }
+                HIPCHK(c, hipMemcpyAsync(c->r_exc_bytes.p, bytes.data(), exc_off[ne], hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));      // (bytes goes out of scope)
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));          // (exc_off goes out of scope; the caller's text may be freed on return)
+            R.exc_read = c->r_exc_read.p; R.exc_off = c->r_exc_off.p; R.exc_bytes = c->r_exc_bytes.p; R.n_exc = ne;
+        }
+    }
+    const int s = finish_load(c, R, read_index_base, lay.max_len, lay.uniform_len ? nullptr : lengths.data(), total_words);
+    if (!s && timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t_time[0], c->ev_t_time[1]));
+        c->last_pack_ms = ms;
+    }
+    return s;
+}
+
+static int load_text_common(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t *d_seqs, const uint64_t *off, uint64_t n,
+                            int pad_uniform, const uint64_t *header_id, uint64_t read_index_base)
+{
+    const int s = load_text_impl(c, h_seqs, d_seqs, off, n, pad_uniform, header_id, read_index_base);
+    if (c) {
+        // what only this call needed goes back, on every way out: the text's offsets (8 bytes per read) and the two staged chunks
+        // (pinned and device memory of up to CRASS_TEXT_CHUNK_BYTES each) — a context loads a read set once
+        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
+        c->t_off.release();
+        for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    }
+    return s;
+}
+
+int crass_hip_load_text(crass_hip_ctx *c, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads, int pad_uniform,
+                        const uint64_t *header_id, uint64_t read_index_base)
+{
+    return load_text_common(c, seqs, nullptr, off, n_reads, pad_uniform, header_id, read_index_base);
+}
+
+int crass_hip_attach_device_text(crass_hip_ctx *c, const uint8_t *d_seqs, const uint64_t *off, uint64_t n_reads, int pad_uniform,
+                                 const uint64_t *header_id, uint64_t read_index_base)
+{
+    return load_text_common(c, nullptr, d_seqs, off, n_reads, pad_uniform, header_id, read_index_base);
+}
+
+float crass_hip_last_pack_ms(const crass_hip_ctx *c) { return c ? c->last_pack_ms : 0.0f; }
+
+int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)
+{
+    if (!c || !out) return CRASS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    if (!c->have_reads) return CRASS_ERR_STATE;
+    (void)hipSetDevice(c->device);
+    const DevReads &R = c->R;
+    const uint64_t n = R.n_reads, ne = R.n_exc;
+    auto get = [&](void *dst, const void *src, uint64_t bytes) {
+        if (!bytes) return CRASS_OK;
+        const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { c->last_hip = (int)e; return CRASS_ERR_HIP; }
+        return CRASS_OK;
+    };
+    // the word count: n strides, or the last read's first word and its own words
+    uint64_t total_words = n * (uint64_t)R.stride_words;
+    if (!R.stride_words && n) {
+        uint64_t w_last = 0; uint32_t l_last = R.uniform_len;
+        int s = get(&w_last, R.word_off + (n - 1), 8);
+        if (!s && !R.uniform_len) s = get(&l_last, R.lengths + (n - 1), 4);
+        if (s) return s;
+        total_words = w_last + (l_last + 15) / 16;
+    }
+    uint64_t exc_total = 0;
+    if (ne) { const int s = get(&exc_total, R.exc_off + ne, 8); if (s) return s; }
+    crass_packed pk;
+    PackedArrays a{};
+    int s = packed_alloc(total_words + 4, R.stride_words ? 0 : n + 1, R.uniform_len ? 0 : n, ne, ne + 1, exc_total, R.header_id ? n : 0, &pk, &a);
+    if (s) return s;
+    s = get(a.packed, R.packed, total_words * 4);
+    if (!s) memset(a.packed + total_words, 0, 16);
+    if (!s && a.word_off) { s = get(a.word_off, R.word_off, n * 8); a.word_off[n] = total_words; }
+    if (!s && a.lengths) s = get(a.lengths, R.lengths, n * 4);
+    if (!s && ne) s = get(a.exc_read, R.exc_read, ne * 8);
+    if (!s && ne) s = get(a.exc_off, R.exc_off, (ne + 1) * 8);
+    if (!ne) a.exc_off[0] = 0;
+    if (!s && exc_total) s = get(a.exc_bytes, R.exc_bytes, exc_total);
+    if (!s && a.header_id) s = get(a.header_id, R.header_id, n * 8);
+    if (s) { crass_free_packed(&pk); return s; }
+    crass_reads &r = pk.reads;
+    r.n_reads = n; r.packed = a.packed; r.stride_words = R.stride_words; r.word_off = a.word_off; r.uniform_len = R.uniform_len; r.lengths = a.lengths;
+    r.n_exceptions = ne; r.exc_read = a.exc_read; r.exc_off = a.exc_off; r.exc_bytes = a.exc_bytes; r.header_id = a.header_id;
+    r.read_index_base = c->read_base;
+    *out = pk;
     return CRASS_OK;
 }
 

@@ -2,6 +2,7 @@
 // FASTA/FASTQ(.gz) reader with kseq_read record semantics, and the deterministic synthetic
 // metagenome generator used by bench.py and the parity tests.  Host-only C++17 (+ zlib).
 #include "../../include/crass_hip.h"
+#include "pack_text.h"
 
 #include <algorithm>
 #include <atomic>
@@ -14,6 +15,7 @@
 #include <deque>
 #include <mutex>
 #include <memory>
+#include <new>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -40,6 +42,7 @@ struct PackedOwner {
     std::vector<uint32_t> lengths;
     std::vector<uint64_t> exc_read, exc_off;
     std::vector<uint8_t> exc_bytes;
+    std::vector<uint64_t> header_id;                   // (crass_hip_get_packed only)
 };
 
 }
@@ -197,32 +200,83 @@ template <typename T> struct GrowBuf {
 
 } // namespace
 
-extern "C" {
-
-int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int pad_uniform, crass_packed *out)
+// the layout of a packed set: crass_pack_reads and the device packer (crass_hip_load_text, crass_hip_attach_device_text) decide here
+int crass::pack_layout(const uint64_t *off, uint64_t n, int pad_uniform, crass::PackLayout *out)
 {
-    if (!out || (n && (!seqs || !off))) return CRASS_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    PackedOwner *o = new PackedOwner();
+    *out = crass::PackLayout();
     uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
     for (uint64_t i = 0; i < n; i++) {
+        if (off[i + 1] < off[i]) return CRASS_ERR_INVALID_ARG;
         uint64_t l = off[i + 1] - off[i];
-        if (l > CRASS_HIP_MAX_READ_LEN) { delete o; return CRASS_ERR_UNSUPPORTED; }
+        if (l > CRASS_HIP_MAX_READ_LEN) return CRASS_ERR_UNSUPPORTED;
         max_len = std::max<uint32_t>(max_len, (uint32_t)l);
         min_len = std::min<uint32_t>(min_len, (uint32_t)l);
     }
     if (n == 0) min_len = 0;
     const bool uniform_len = (n > 0 && max_len == min_len && max_len > 0);       // (uniform_len == 0 says "lengths differ": a set of empty reads keeps its lengths array)
     uint32_t stride = 0;
+    uint64_t tight = 0;
+    for (uint64_t i = 0; i < n; i++) tight += (off[i + 1] - off[i] + 15) / 16;
     if (pad_uniform == 2) {
         // auto: short reads of differing lengths (trimmed Illumina data) are padded to one stride when that costs at
         // most twice the words — the bit-parallel filter and the lane-per-read kernels need a uniform stride
-        uint64_t tight = 0;
-        for (uint64_t i = 0; i < n; i++) tight += (off[i + 1] - off[i] + 15) / 16;
         const uint64_t padded = n * (uint64_t)((max_len + 15) / 16);
         pad_uniform = (max_len <= 256 && max_len >= 64 && padded <= 2 * tight) ? 1 : 0;
     }
     if (pad_uniform || uniform_len) stride = std::max<uint32_t>(1, (max_len + 15) / 16);
+    out->max_len = max_len; out->stride_words = stride; out->uniform_len = uniform_len ? max_len : 0;
+    out->total_words = stride ? n * (uint64_t)stride : tight;
+    return CRASS_OK;
+}
+
+int crass::packed_alloc(uint64_t n_words, uint64_t n_word_off, uint64_t n_lengths, uint64_t n_exc_read, uint64_t n_exc_off, uint64_t n_exc_bytes,
+                        uint64_t n_header_id, crass_packed *out, crass::PackedArrays *a)
+{
+    memset(out, 0, sizeof(*out));
+    PackedOwner *o = new (std::nothrow) PackedOwner();
+    if (!o) return CRASS_ERR_OOM;
+    try {
+        o->packed.resize(n_words); o->word_off.resize(n_word_off); o->lengths.resize(n_lengths); o->exc_read.resize(n_exc_read);
+        o->exc_off.resize(n_exc_off); o->exc_bytes.resize(n_exc_bytes); o->header_id.resize(n_header_id);
+    } catch (const std::bad_alloc &) { delete o; return CRASS_ERR_OOM; }
+    a->packed = n_words ? o->packed.data() : nullptr; a->word_off = n_word_off ? o->word_off.data() : nullptr;
+    a->lengths = n_lengths ? o->lengths.data() : nullptr; a->exc_read = n_exc_read ? o->exc_read.data() : nullptr;
+    a->exc_off = n_exc_off ? o->exc_off.data() : nullptr; a->exc_bytes = n_exc_bytes ? o->exc_bytes.data() : nullptr;
+    a->header_id = n_header_id ? o->header_id.data() : nullptr;
+    out->owner = o;
+    return CRASS_OK;
+}
+
+extern "C" {
+
+uint32_t crass_pack_code4(uint32_t four_bytes, uint32_t *bad)
+{
+    uint32_t b = 0;
+    const uint32_t c = crass::pack_code4(four_bytes, &b);
+    if (bad) *bad = b;
+    return c;
+}
+
+int crass_pack_layout(const uint64_t *off, uint64_t n_reads, int pad_uniform, uint32_t *stride_words, uint32_t *uniform_len)
+{
+    if (n_reads && !off) return CRASS_ERR_INVALID_ARG;
+    crass::PackLayout lay;
+    const int s = crass::pack_layout(off, n_reads, pad_uniform, &lay);
+    if (stride_words) *stride_words = lay.stride_words;
+    if (uniform_len) *uniform_len = lay.uniform_len;
+    return s;
+}
+
+int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int pad_uniform, crass_packed *out)
+{
+    if (!out || (n && (!seqs || !off))) return CRASS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    crass::PackLayout lay;
+    // (offsets that decrease have always been reported here as a read beyond the length limit)
+    if (const int ls = crass::pack_layout(off, n, pad_uniform, &lay)) return ls == CRASS_ERR_INVALID_ARG ? CRASS_ERR_UNSUPPORTED : ls;
+    PackedOwner *o = new PackedOwner();
+    const uint32_t max_len = lay.max_len, stride = lay.stride_words;
+    const bool uniform_len = lay.uniform_len != 0;
     if (!stride) {
         o->word_off.resize(n + 1);
         uint64_t w = 0;

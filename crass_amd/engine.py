@@ -98,6 +98,68 @@ class PackedReads:
             pass
 
 
+def packed_arrays(r):
+    """Every array of a crass_reads with HOST pointers (_abi.Reads) as numpy copies, by field name; arrays the set does not
+    have are None.  `packed` includes padding and the four tail words."""
+    n, ne = int(r.n_reads), int(r.n_exceptions)
+    stride, ulen = int(r.stride_words), int(r.uniform_len)
+    d = {"n_reads": n, "stride_words": stride, "uniform_len": ulen, "n_exceptions": ne, "read_index_base": int(r.read_index_base)}
+    d["word_off"] = None if stride else _npv(r.word_off, n + 1, np.uint64)
+    d["lengths"] = None if ulen else _npv(r.lengths, n, np.uint32)
+    total = n * stride if stride else (int(d["word_off"][n]) if n else 0)
+    d["packed"] = _npv(r.packed, total + 4, np.uint32)
+    d["exc_read"] = _npv(r.exc_read, ne, np.uint64)
+    d["exc_off"] = _npv(r.exc_off, ne + 1, np.uint64)
+    d["exc_bytes"] = _npv(r.exc_bytes, int(d["exc_off"][ne]) if ne else 0, np.uint8)
+    d["header_id"] = _npv(r.header_id, n, np.uint64) if r.header_id else None
+    return d
+
+
+class ResidentReads:
+    """A context's resident read set copied back to the host (crass_hip_get_packed); usable wherever a PackedReads is."""
+
+    def __init__(self, engine):
+        self.p = _abi.Packed()
+        _chk(engine.lib.crass_hip_get_packed(engine.h, C.byref(self.p)), "crass_hip_get_packed")
+        self.header_id = None
+
+    @property
+    def reads(self):
+        return self.p.reads
+
+    @property
+    def n_reads(self):
+        return int(self.p.reads.n_reads)
+
+    def arrays(self):
+        return packed_arrays(self.p.reads)
+
+    def close(self):
+        if self.p.owner:
+            _abi.load().crass_free_packed(C.byref(self.p))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_layout(offsets, pad_uniform):
+    """(stride_words, uniform_len) the packers give reads with these byte offsets (crass_pack_layout; no GPU needed)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    st, ul = C.c_uint32(), C.c_uint32()
+    _chk(_abi.load().crass_pack_layout(off.ctypes.data, len(off) - 1, int(pad_uniform), C.byref(st), C.byref(ul)), "crass_pack_layout")
+    return int(st.value), int(ul.value)
+
+
+def pack_code4(four_bytes):
+    """(codes, bad bits) of four sequence bytes given as a little-endian uint32 (crass_pack_code4; no GPU needed)."""
+    bad = C.c_uint32()
+    code = _abi.load().crass_pack_code4(int(four_bytes) & 0xFFFFFFFF, C.byref(bad))
+    return int(code), int(bad.value)
+
+
 class FastxFile:
     """FASTA/FASTQ(.gz) records with kseq_read semantics (C++ reader, crass_read_fastx)."""
 
@@ -451,6 +513,48 @@ class SearchEngine:
         r.read_index_base = int(read_index_base)
         _chk(self.lib.crass_hip_attach_device_reads(self.h, C.byref(r)), "crass_hip_attach_device_reads")
         self._keep = tensor
+
+    @staticmethod
+    def _text_args(seqs):
+        # a (buffer, offsets) pair: two elements, the second an array of offsets (not a read); anything else: a list of reads
+        if isinstance(seqs, tuple) and len(seqs) == 2 and not isinstance(seqs[1], (bytes, bytearray)):
+            buf, off = seqs
+            if isinstance(buf, (bytes, bytearray)):
+                buf = np.frombuffer(bytes(buf), dtype=np.uint8)
+            return buf, np.ascontiguousarray(off, dtype=np.uint64)
+        return concat(list(seqs))
+
+    def load_text(self, seqs, pad_uniform=2, header_id=None, read_index_base=0):
+        """Sequence text (a list of bytes, or a (uint8 buffer, offsets[n + 1]) pair) in host memory; packed on the
+        device (crass_hip_load_text).  The state afterwards is that of load_reads(PackedReads(seqs, pad_uniform))."""
+        buf, off = self._text_args(seqs)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        hid = None if header_id is None else np.ascontiguousarray(header_id, dtype=np.uint64)
+        _chk(self.lib.crass_hip_load_text(self.h, buf.ctypes.data, off.ctypes.data, len(off) - 1, int(pad_uniform),
+                                          None if hid is None else hid.ctypes.data, int(read_index_base)), "crass_hip_load_text")
+        self._keep = None
+
+    def attach_device_text(self, tensor, offsets, pad_uniform=2, header_id=None, read_index_base=0):
+        """Sequence text in a torch uint8 DEVICE tensor (offsets[n + 1]: host array of byte offsets into it); packed on
+        the device (crass_hip_attach_device_text).  The context keeps nothing of the tensor."""
+        if str(tensor.dtype) != "torch.uint8" or not tensor.is_cuda or not tensor.is_contiguous():
+            raise ValueError("attach_device_text needs a contiguous uint8 device tensor")
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(off) > 1 and int(off[-1]) > tensor.numel():
+            raise ValueError("offsets reach beyond the tensor")
+        hid = None if header_id is None else np.ascontiguousarray(header_id, dtype=np.uint64)
+        _chk(self.lib.crass_hip_attach_device_text(self.h, int(tensor.data_ptr()), off.ctypes.data, len(off) - 1, int(pad_uniform),
+                                                   None if hid is None else hid.ctypes.data, int(read_index_base)),
+             "crass_hip_attach_device_text")
+        self._keep = None
+
+    def last_pack_ms(self):
+        """HIP-event milliseconds of the last load_text / attach_device_text call's pack kernels (stage timing >= 1, else 0)."""
+        return float(self.lib.crass_hip_last_pack_ms(self.h))
+
+    def packed(self):
+        """The resident read set copied back (crass_hip_get_packed): a ResidentReads with PackedReads' fields."""
+        return ResidentReads(self)
 
     # ---- passes ----
     def seed_scan(self, fetch=True):

@@ -122,6 +122,22 @@ int crass_hip_load_reads(crass_hip_ctx *ctx, const crass_reads *host_reads);
 /* same, but every pointer in `dev_reads` is a DEVICE pointer the caller owns (e.g. torch
  * tensors) and keeps alive until the context is destroyed or new reads are set. */
 int crass_hip_attach_device_reads(crass_hip_ctx *ctx, const crass_reads *dev_reads);
+/* replaces: crass_pack_reads + crass_hip_load_reads for a caller that holds sequence TEXT (one byte per base, read i =
+ * seqs[off[i] .. off[i+1]), off[n_reads+1] a host array): the 2-bit packing runs on the device (pack.hip) with
+ * crass_pack_reads' byte semantics and layout rules (pad_uniform 0 | 1 | 2 as there), and the resident set, the exception
+ * list and the counters end up exactly as after the host route.  The text goes up in chunks of whole reads through two
+ * pinned staging buffers, the copy of one chunk beside the pack kernel of the one before (CRASS_TEXT_CHUNK_BYTES, read at
+ * crass_hip_create: bytes per chunk, default 64 MB); text in pinned memory is copied from where it is.
+ * CRASS_ERR_INVALID_ARG: a NULL pointer with n_reads > 0, offsets that decrease; CRASS_ERR_UNSUPPORTED (nothing launched,
+ * no reads resident): a read beyond CRASS_HIP_MAX_READ_LEN. */
+int crass_hip_load_text(crass_hip_ctx *ctx, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads,
+                        int pad_uniform, const uint64_t *header_id, uint64_t read_index_base);
+/* same, but d_seqs is a DEVICE pointer (a torch uint8 tensor, the output of another GPU stage, a decompressor); off stays
+ * a host array.  The text is only read during the call: the packed set belongs to the context, the caller may free the
+ * text on return.  Any lengths and any bytes: the way to attach device-resident input that is ragged or holds an 'N'
+ * (crass_hip_attach_device_reads takes packed words of one stride without exception reads). */
+int crass_hip_attach_device_text(crass_hip_ctx *ctx, const uint8_t *d_seqs, const uint64_t *off, uint64_t n_reads,
+                                 int pad_uniform, const uint64_t *header_id, uint64_t read_index_base);
 
 /* ---- pass 1 : searchFile / searchCore (libcrispr.cpp:68-166, 265-395) ---- *
  * Runs the seed-scan filter, ordered compaction, and the survivor kernel (scanRight,
@@ -494,6 +510,22 @@ typedef struct {
 int  crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n_reads,
                       int pad_uniform, crass_packed *out);
 void crass_free_packed(crass_packed *p);
+/* HIP-event time, in milliseconds on the context's stream, of the pack kernels of the last crass_hip_load_text /
+ * crass_hip_attach_device_text call; measured when the stage timing level is >= 1 (crass_hip_set_stage_timing), else 0.
+ * Device text: the kernel alone.  Host text: first kernel to last, the waits for the chunks' copies included.
+ * (No reference counterpart: crass has no timers.) */
+float crass_hip_last_pack_ms(const crass_hip_ctx *ctx);
+/* the context's resident read set copied back to the host as a crass_packed (malloc'd, free with crass_free_packed; arrays
+ * the set does not have are NULL, as from crass_pack_reads; header_id and read_index_base as loaded): lets a caller cache
+ * the packed form of text it loaded with crass_hip_load_text / crass_hip_attach_device_text.  CRASS_ERR_STATE: no reads.
+ * (No reference counterpart: crass reads its input files again for every pass.) */
+int  crass_hip_get_packed(const crass_hip_ctx *ctx, crass_packed *out);
+/* the two decisions of the packers on their own, for callers and tests without a GPU: the layout crass_pack_reads and
+ * crass_hip_load_text give a set (stride_words / uniform_len as in crass_reads), and the byte -> code function both use —
+ * four sequence bytes (byte 0 first) -> their 2-bit codes in bits [2i, 2i+2), *bad bit i set when byte i is not A C G T
+ * (its code is then 0). */
+int  crass_pack_layout(const uint64_t *off, uint64_t n_reads, int pad_uniform, uint32_t *stride_words, uint32_t *uniform_len);
+uint32_t crass_pack_code4(uint32_t four_bytes, uint32_t *bad);
 
 /* FASTA/FASTQ(.gz) reader with kseq_read record semantics (kseq.cpp:171-226).  Buffers are
  * malloc'd, free with crass_free_fastx.                                                    */
