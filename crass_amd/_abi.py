@@ -81,6 +81,10 @@ class Packed(C.Structure):
     _fields_ = [("reads", Reads), ("owner", C.c_void_p)]
 
 
+class Text(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("chars", u8p), ("off", u64p)]
+
+
 class Fastx(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("seq", u8p), ("seq_off", u64p), ("name", u8p), ("name_off", u64p),
                 ("comment", u8p), ("comment_off", u64p), ("has_comment", u8p), ("qual", u8p), ("qual_off", u64p),
@@ -158,6 +162,10 @@ SYMBOLS = {
     "crass_hip_attach_device_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]),
     "crass_hip_last_pack_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_get_packed": (C.c_int, [C.c_void_p, C.POINTER(Packed)]),
+    "crass_hip_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
+    "crass_hip_fetch_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fetch_record_text": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Text)]),
+    "crass_hip_last_fetch_ms": (C.c_float, [C.c_void_p]),
     "crass_pack_layout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, u32p, u32p]),
     "crass_pack_code4": (C.c_uint32, [C.c_uint32, u32p]),
     "crass_hip_seed_scan": (C.c_int, [C.c_void_p]),
@@ -228,6 +236,7 @@ SYMBOLS = {
     "crass_hip_group_get_candidates": (C.c_int, [C.c_void_p, C.POINTER(Candidates)]),
     "crass_hip_group_get_merge": (C.c_int, [C.c_void_p, C.POINTER(MergeView)]),
     "crass_hip_group_get_recruits": (C.c_int, [C.c_void_p, C.POINTER(Recruits)]),
+    "crass_hip_group_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
     "crass_build_outputs": (C.c_int, [C.POINTER(GraphInput), C.POINTER(OutputOpts), C.POINTER(C.c_void_p)]),
     "crass_outputs_get": (C.c_int, [C.c_void_p, C.POINTER(OutputsView)]),
     "crass_outputs_write": (C.c_int, [C.c_void_p, C.c_char_p]),

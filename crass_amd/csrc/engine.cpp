@@ -257,6 +257,16 @@ struct crass_hip_ctx {
     DevBuf<uint64_t> t_off; DevBuf<uint8_t> t_dev[2]; PinBuf<uint8_t> t_pin[2];
     hipEvent_t ev_t_copy[2] = {nullptr, nullptr}, ev_t_pack[2] = {nullptr, nullptr}, ev_t_time[2] = {nullptr, nullptr};
     float last_pack_ms = 0;                  // HIP-event time of the last call's pack kernels (stage timing >= 1, else 0)
+    // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
+    // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
+    // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
+    // what crass_text points at), the events of crass_hip_last_fetch_ms, the flags of crass_hip_fetch_record_text
+    std::vector<uint32_t> h_lengths;
+    DevBuf<uint64_t> f_idx, f_off; DevBuf<uint8_t> f_rc, f_chars;
+    PinBuf<uint64_t> f_h_idx, f_h_off; PinBuf<uint8_t> f_h_rc, f_h_chars;
+    hipEvent_t ev_f_time[2] = {nullptr, nullptr};
+    float last_fetch_ms = 0;
+    std::vector<uint8_t> f_flags;
 
     // scratch
     DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;
@@ -776,7 +786,7 @@ int crass_hip_create(const crass_params *p, int device, crass_hip_ctx **out)
     (void)warm_dmerge_module();                         // (code-object load: here, not inside the first merge)
     unsigned char tab[128];
     build_comp_table(tab);
-    if (upload_comp_table(tab) != hipSuccess) { delete c; return CRASS_ERR_HIP; }
+    if (upload_comp_table(tab) != hipSuccess || upload_fetch_comp_table(tab) != hipSuccess) { delete c; return CRASS_ERR_HIP; }
     *out = c;
     return CRASS_OK;
 }
@@ -855,6 +865,9 @@ void crass_hip_destroy(crass_hip_ctx *c)
     c->r_packed.release(); c->r_word_off.release(); c->r_lengths.release(); c->r_header_id.release();
     c->r_exc_mask.release(); c->r_exc_read.release(); c->r_exc_off.release(); c->r_exc_bytes.release();
     c->t_off.release();
+    c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
+    c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
+    for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++) {
         c->t_dev[k].release(); c->t_pin[k].release();
         if (c->ev_t_copy[k]) (void)hipEventDestroy(c->ev_t_copy[k]);
@@ -1042,7 +1055,8 @@ int crass_hip_load_reads(crass_hip_ctx *c, const crass_reads *h)
         HIPCHK(c, c->r_lengths.ensure(n));
         HIPCHK(c, hipMemcpyAsync(c->r_lengths.p, h->lengths, n * 4, hipMemcpyHostToDevice, c->stream));
         R.lengths = c->r_lengths.p;
-    }
+        c->h_lengths.assign(h->lengths, h->lengths + n);
+    } else c->h_lengths.clear();
     if (h->header_id) {
         HIPCHK(c, c->r_header_id.ensure(n));
         HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, h->header_id, n * 8, hipMemcpyHostToDevice, c->stream));
@@ -1091,6 +1105,7 @@ int crass_hip_attach_device_reads(crass_hip_ctx *c, const crass_reads *d)
     HIPCHK(c, hipMemsetAsync(c->r_exc_mask.p, 0, mask_words * 4, c->stream));
     R.exc_mask = c->r_exc_mask.p;
     c->h_exc_read.clear();
+    c->h_lengths.clear();
     c->R = R;
     c->read_base = d->read_index_base;
     c->max_len = d->uniform_len;
@@ -1255,6 +1270,7 @@ static int load_text_impl(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t
         }
     }
     const int s = finish_load(c, R, read_index_base, lay.max_len, lay.uniform_len ? nullptr : lengths.data(), total_words);
+    c->h_lengths.swap(lengths);                         // (empty for a uniform length)
     if (!s && timed) {
         float ms = 0;
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t_time[0], c->ev_t_time[1]));
@@ -1337,6 +1353,102 @@ int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)
     *out = pk;
     return CRASS_OK;
 }
+
+// ---- text of selected reads out of the resident set (k_fetch_text, pack.hip) ----
+// d_user == nullptr: the host route (the text comes back into pinned memory, *out points at it); else the caller's device
+// buffer of cap bytes, the offsets into off_user.  Every check comes before the first launch; the resident set is only read.
+static int fetch_text_impl(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, uint8_t *d_user, uint64_t cap,
+                           uint64_t *off_user, crass_text *out)
+{
+    if (n && !read_idx) return CRASS_ERR_INVALID_ARG;
+    if (!c->have_reads) return CRASS_ERR_STATE;
+    const DevReads &R = c->R;
+    for (uint64_t k = 0; k < n; k++) if (read_idx[k] < c->read_base || read_idx[k] - c->read_base >= R.n_reads) return CRASS_ERR_INVALID_ARG;
+    if (!R.uniform_len && c->h_lengths.size() != R.n_reads) return CRASS_ERR_STATE;      // (never expected: every load keeps them)
+    c->last_fetch_ms = 0;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, c->f_h_off.ensure(n + 1));
+    uint64_t *off = c->f_h_off.p;
+    off[0] = 0;
+    if (n) {
+        HIPCHK(c, c->f_h_idx.ensure(n));
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t r = read_idx[k] - c->read_base;
+            c->f_h_idx.p[k] = r;
+            off[k + 1] = off[k] + (R.uniform_len ? R.uniform_len : c->h_lengths[r]);
+        }
+    }
+    const uint64_t total = off[n];
+    if (off_user) memcpy(off_user, off, (n + 1) * 8);
+    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
+    if (!d_user) HIPCHK(c, c->f_h_chars.ensure(total));
+    if (out) { out->n = n; out->chars = c->f_h_chars.p; out->off = off; }
+    if (!total) return CRASS_OK;                        // (no record, or empty reads only: nothing to launch or wait for)
+    HIPCHK(c, c->f_idx.ensure(n));
+    HIPCHK(c, c->f_off.ensure(n + 1));
+    HIPCHK(c, hipMemcpyAsync(c->f_idx.p, c->f_h_idx.p, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->f_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (revcomp) {
+        HIPCHK(c, c->f_h_rc.ensure(n));
+        HIPCHK(c, c->f_rc.ensure(n));
+        memcpy(c->f_h_rc.p, revcomp, n);
+        HIPCHK(c, hipMemcpyAsync(c->f_rc.p, c->f_h_rc.p, n, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!d_user) HIPCHK(c, c->f_chars.ensure(total));
+    FetchJob J{};
+    J.R = R; J.idx = c->f_idx.p; J.rc = revcomp ? c->f_rc.p : nullptr; J.out_off = c->f_off.p; J.n = n; J.total = total;
+    J.out = d_user ? d_user : c->f_chars.p;
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_f_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_f_time[0], c->stream));
+    }
+    HIPCHK(c, launch_fetch_text(J, c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_f_time[1], c->stream));
+    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->f_h_chars.p, c->f_chars.p, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // the call's one wait (device route: the staged indices are free again, the text is written)
+    if (timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_f_time[0], c->ev_f_time[1]));
+        c->last_fetch_ms = ms;
+    }
+    return CRASS_OK;
+}
+
+int crass_hip_fetch_text(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *out)
+{
+    if (!c || !out) return CRASS_ERR_INVALID_ARG;
+    return fetch_text_impl(c, read_idx, revcomp, n, nullptr, 0, nullptr, out);
+}
+
+int crass_hip_fetch_text_device(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, uint8_t *d_chars,
+                                uint64_t cap_bytes, uint64_t *off_out)
+{
+    if (!c || !off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
+    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone: the device route, which then overflows or writes nothing)
+    return fetch_text_impl(c, read_idx, revcomp, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr);
+}
+
+int crass_hip_fetch_record_text(crass_hip_ctx *c, int pass, crass_text *out)
+{
+    if (!c || !out || (pass != 1 && pass != 2)) return CRASS_ERR_INVALID_ARG;
+    const uint64_t *idx = nullptr; const uint8_t *low = nullptr; uint64_t n = 0;
+    if (pass == 1) {
+        crass_candidates v;
+        if (const int s = crass_hip_get_candidates(c, &v)) return s;
+        idx = v.read_idx; low = v.low_lexi; n = v.n;
+    } else {
+        crass_recruits v;
+        if (const int s = crass_hip_get_recruits(c, &v)) return s;
+        idx = v.read_idx; low = v.low_lexi; n = v.n;
+    }
+    // RH_Seq = low_lexi ? seq : revcomp(seq): the adapter's fill_holder, ReadHolder.cpp:513-591
+    c->f_flags.resize(n);
+    for (uint64_t k = 0; k < n; k++) c->f_flags[k] = low[k] ? 0 : 1;
+    return fetch_text_impl(c, idx, c->f_flags.data(), n, nullptr, 0, nullptr, out);
+}
+
+float crass_hip_last_fetch_ms(const crass_hip_ctx *c) { return c ? c->last_fetch_ms : 0.0f; }
 
 static void ensure_distinct(crass_hip_ctx *c);
 

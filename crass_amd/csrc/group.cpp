@@ -59,7 +59,26 @@ struct Rccl {
             lib = dlopen(forced, RTLD_NOW | RTLD_LOCAL);
             if (!lib) { const char *e = dlerror(); why = e ? e : "dlopen failed"; }      // (dlerror() clears the state: read it ONCE)
         } else {
+            // First the RCCL that lies beside the HIP runtime THIS library calls, by its full path.  A bare "librccl.so.1" is
+            // answered with any loaded library of that soname — a torch wheel imported after this library brings its own RCCL
+            // AND its own HIP runtime ($ORIGIN), and an ncclAllGather of that pair on a stream of ours (another runtime's
+            // handle) aborts the process.  Where torch came first this library runs on torch's runtime, no RCCL lies beside
+            // it under these names, and the soname below finds torch's: the matching pair again.
+            Dl_info di{};
+            if (dladdr((const void *)&hipGetDeviceCount, &di) && di.dli_fname) {
+                std::string dir(di.dli_fname);
+                const size_t cut = dir.rfind('/');
+                if (cut != std::string::npos) {
+                    dir.resize(cut + 1);
+                    for (const char *n : {"librccl.so.1", "librccl.so"}) {
+                        lib = dlopen((dir + n).c_str(), RTLD_NOW | RTLD_LOCAL);
+                        if (lib) break;
+                        (void)dlerror();
+                    }
+                }
+            }
             for (const char *n : names) {
+                if (lib) break;
                 lib = dlopen(n, RTLD_NOW | RTLD_LOCAL);
                 if (lib) break;
                 const char *e = dlerror();
@@ -161,6 +180,7 @@ struct crass_hip_group {
         std::vector<char> dr; uint32_t stride = 0, max_len = 0; bool ready = false;
     } C;
     struct { std::vector<uint32_t> cand_token; bool ready = false; } M;
+    struct { std::vector<uint8_t> chars; std::vector<uint64_t> off; } T;      // crass_hip_group_fetch_text's result
     struct {
         std::vector<uint64_t> read; std::vector<uint8_t> low; std::vector<uint32_t> start, end, token; std::vector<uint16_t> dr_len;
         std::vector<char> dr; uint32_t stride = 0; bool ready = false;
@@ -605,6 +625,43 @@ int crass_hip_group_get_candidates(crass_hip_group *g, crass_candidates *o)
     o->n = C.read.size(); o->read_idx = C.read.data(); o->low_lexi = C.low.data(); o->repeat_len = C.replen.data();
     o->n_ss = C.nss.data(); o->ss_off = C.ss_off.data(); o->ss_pool = C.ss.data(); o->dr_stride = C.stride;
     o->dr_len = C.dr_len.data(); o->dr_chars = C.dr.data(); o->max_read_len = C.max_len;
+    return CRASS_OK;
+}
+
+// the text of reads of the whole job: every index goes to the rank whose shard holds it (a shard's read_index_base is the
+// job's plus its first read, so the global indices pass through as they are), one crass_hip_fetch_text per rank that has any,
+// and the records are put back in the caller's order
+int crass_hip_group_fetch_text(crass_hip_group *g, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *o)
+{
+    if (!g || !o || (n && !read_idx)) return CRASS_ERR_INVALID_ARG;
+    if (!g->loaded) return CRASS_ERR_STATE;
+    for (uint64_t k = 0; k < n; k++) if (read_idx[k] < g->base || read_idx[k] - g->base >= g->n_reads) return CRASS_ERR_INVALID_ARG;
+    try {
+        std::vector<std::vector<uint64_t>> idx(g->n), at(g->n);
+        std::vector<std::vector<uint8_t>> rc(g->n);
+        for (uint64_t k = 0; k < n; k++) {
+            const int r = (int)(std::upper_bound(g->first.begin(), g->first.end(), read_idx[k] - g->base) - g->first.begin()) - 1;
+            idx[r].push_back(read_idx[k]); at[r].push_back(k);
+            if (revcomp) rc[r].push_back(revcomp[k]);
+        }
+        // (a rank's result lives in its own context until that context's next fetch: all of them are there at once)
+        std::vector<crass_text> part(g->n, crass_text{0, nullptr, nullptr});
+        for (int r = 0; r < g->n; r++) {
+            if (idx[r].empty()) continue;
+            const int s = crass_hip_fetch_text(g->ctx[r], idx[r].data(), revcomp ? rc[r].data() : nullptr, idx[r].size(), &part[r]);
+            if (s) return s;
+        }
+        auto &T = g->T;
+        T.off.assign(n + 1, 0);
+        for (int r = 0; r < g->n; r++) for (uint64_t q = 0; q < part[r].n; q++) T.off[at[r][q] + 1] = part[r].off[q + 1] - part[r].off[q];
+        for (uint64_t k = 0; k < n; k++) T.off[k + 1] += T.off[k];
+        T.chars.resize(T.off[n] + 1);
+        for (int r = 0; r < g->n; r++) for (uint64_t q = 0; q < part[r].n; q++) {
+            const uint64_t len = part[r].off[q + 1] - part[r].off[q];
+            if (len) memcpy(T.chars.data() + T.off[at[r][q]], part[r].chars + part[r].off[q], len);
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    o->n = n; o->chars = g->T.chars.data(); o->off = g->T.off.data();
     return CRASS_OK;
 }
 

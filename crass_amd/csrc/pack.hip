@@ -1,5 +1,6 @@
 // pack.hip — the 2-bit packer on the device: concatenated sequence text (one byte per base, reads at arbitrary byte
-// offsets) -> the packed read set of include/crass_hip.h, with crass_pack_reads' byte semantics (ingest.cpp).
+// offsets) -> the packed read set of include/crass_hip.h, with crass_pack_reads' byte semantics (ingest.cpp); and the way
+// back, k_fetch_text (below the packer): selected reads of the resident set as text again, forward or reverse-complemented.
 //
 // A pure stream: 1 byte in, 0.25 byte out per base.  A block owns a tile of kPackTileWords consecutive OUTPUT words (so
 // every lane stores one aligned 16-byte vector, whatever the reads' lengths); the text those words come from is one
@@ -152,6 +153,132 @@ __global__ __launch_bounds__(256) void k_gather_exc_text(const uint8_t *text, ui
         const uint64_t at = exc_off[e], L = exc_off[e + 1] - at;
         for (uint64_t i = lane; i < L; i += 64) exc_bytes[at + i] = s[i];
     }
+}
+
+// ---- k_fetch_text: the way back.  A stream driven by the OUTPUT: 0.25 byte read, 1 byte written per base ----
+// A block owns kFetchTileBytes consecutive output bytes that start on a 16-byte ADDRESS boundary (the output buffer itself may
+// start anywhere), a lane one aligned 16-byte vector of them.  The records that meet the tile are found by bisection in
+// out_off (two lanes, for the tile's first and last byte), a lane's own first record by bisection between those; a vector
+// inside one long read takes one turn of the loop below, a vector over many short or empty records one turn per record that
+// has a byte in it (empty records are stepped over by the bisection).
+// A turn builds the WHOLE vector as if the record went on for ever on both sides — vector byte t is the record's byte j0 + t —
+// and keeps the bytes the record really has:
+//   forward:             the 16 codes from base j0 on: a funnel shift over (at most) two packed words; four codes -> four
+//                        letters by one byte permute against "ACGT" (the selector = the codes spread to a byte each);
+//   reverse complement:  vector byte t is the complement of base L - 1 - j0 - t: the 16 codes from base L - 16 - j0 on, the
+//                        permute against "TGCA" (code c -> the complement's letter) with the selector's bytes reversed and the
+//                        four dwords in reverse order;
+//   exception read:      its raw bytes (exc_bytes; the slot by bisection in exc_read), through c_fcomp under the flag.
+// Words are only loaded where the read has one (a caller's attached buffer ends with its last read's last word).
+// Every lane stores its vector once: 16 aligned bytes, or — the first and the last vector of the output — its bytes one by one.
+static constexpr int kFetchThreads = 256;
+static constexpr uint32_t kFetchTileBytes = 16 * kFetchThreads;
+
+__constant__ unsigned char c_fcomp[128];      // reverseComplement table (merge.cpp build_comp_table; kernels.hip keeps its own copy)
+
+// the 16 codes of a read from base j on (j < 0 or beyond the read: codes of no meaning); W: the read's nw words
+static __device__ __forceinline__ uint32_t ft_window(const uint32_t *W, int32_t j, int32_t nw)
+{
+    const int32_t w = j >> 4;                           // (floor: j may be -15 .. -1)
+    const uint32_t s = 2u * (uint32_t)(j & 15);
+    const uint32_t lo = (w >= 0 && w < nw) ? W[w] : 0u;
+    const uint32_t hi = (s && w + 1 >= 0 && w + 1 < nw) ? W[w + 1] : 0u;
+    return __funnelshift_r(lo, hi, s);
+}
+// four codes (8 bits) -> one per byte: a v_perm_b32 selector
+static __device__ __forceinline__ uint32_t ft_sel(uint32_t c)
+{
+    c &= 0xFFu;
+    return (c | (c << 6) | (c << 12) | (c << 18)) & 0x03030303u;
+}
+static __device__ __forceinline__ uint32_t ft_low_bytes(int32_t k)      // the k lowest bytes of a dword, k clamped to 0 .. 4
+{
+    return k <= 0 ? 0u : (k >= 4 ? 0xFFFFFFFFu : (1u << (8 * k)) - 1u);
+}
+
+__global__ __launch_bounds__(kFetchThreads) void k_fetch_text(const FetchJob J)
+{
+    __shared__ uint64_t s_rec[2];                       // the records of the tile's first and last byte
+    const DevReads &R = J.R;
+    const uint32_t tid = threadIdx.x;
+    // positions count from the aligned address at or below out: the output is [lead, end)
+    const uint64_t lead = (uint64_t)((uintptr_t)J.out & 15u), end = lead + J.total;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kFetchTileBytes;
+    if (tid < 2) {
+        const uint64_t tile_end = tile0 + kFetchTileBytes < end ? tile0 + kFetchTileBytes : end;
+        const uint64_t p = tid ? tile_end - 1 : (tile0 > lead ? tile0 : lead);      // (the tile holds a byte of the output: the grid ends with it)
+        s_rec[tid] = pk_find(J.out_off, 0, J.n - 1, p - lead);
+    }
+    __syncthreads();
+    const uint64_t v0 = tile0 + 16u * tid;
+    const uint64_t a = v0 > lead ? v0 : lead, b = v0 + 16 < end ? v0 + 16 : end;      // this lane's bytes: [a, b)
+    if (a >= b) return;
+    uint32_t acc[4] = {0u, 0u, 0u, 0u};
+    const int64_t vrel = (int64_t)v0 - (int64_t)lead;   // output offset of vector byte 0 (negative in the first vector of an unaligned output)
+    const uint64_t stop = b - lead;
+    uint64_t pos = a - lead;
+    uint64_t k = pk_find(J.out_off, s_rec[0], s_rec[1], pos);
+    for (;;) {
+        const uint64_t o0 = J.out_off[k], o1 = J.out_off[k + 1];      // o0 <= pos < o1
+        const int32_t L = (int32_t)(o1 - o0);
+        const int32_t j0 = (int32_t)(vrel - (int64_t)o0);
+        const int32_t t0 = j0 < 0 ? -j0 : 0, t1 = L - j0 < 16 ? L - j0 : 16;      // the record's bytes of the vector: [t0, t1)
+        const uint64_t r = J.idx[k];
+        const bool rc = J.rc && J.rc[k];
+        uint32_t x[4] = {0u, 0u, 0u, 0u};
+        if (!((R.exc_mask[r >> 5] >> (uint32_t)(r & 31u)) & 1u)) {
+            const uint32_t *W = R.packed + (R.stride_words ? r * (uint64_t)R.stride_words : R.word_off[r]);
+            const int32_t nw = (L + 15) >> 4;
+            if (!rc) {
+                const uint32_t c = ft_window(W, j0, nw);
+#pragma unroll
+                for (int q = 0; q < 4; q++) x[q] = __builtin_amdgcn_perm(0x54474341u, 0x54474341u, ft_sel(c >> (8 * q)));      // "ACGT"
+            } else {
+                const uint32_t c = ft_window(W, L - 16 - j0, nw);
+#pragma unroll
+                for (int q = 0; q < 4; q++) x[q] = __builtin_amdgcn_perm(0x41434754u, 0x41434754u, __builtin_bswap32(ft_sel(c >> (8 * (3 - q)))));      // "TGCA"
+            }
+        } else {
+            uint64_t lo = 0, hi = R.n_exc - 1;          // the read's slot: exc_read is ascending and holds r
+            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (R.exc_read[mid] < r) lo = mid + 1; else hi = mid; }
+            const uint8_t *src = R.exc_bytes + R.exc_off[lo];
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                if (t < t0 || t >= t1) continue;
+                const uint32_t by = rc ? (uint32_t)c_fcomp[src[L - 1 - j0 - t] & 127] : (uint32_t)src[j0 + t];
+                x[t >> 2] |= by << (8 * (t & 3));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] |= x[q] & ft_low_bytes(t1 - 4 * q) & ~ft_low_bytes(t0 - 4 * q);
+        pos = o1;
+        if (pos >= stop) break;
+        k = pk_find(J.out_off, k + 1, s_rec[1], pos);
+    }
+    uint8_t *dst = J.out + vrel;                        // 16-byte aligned (up to 15 bytes below out in the first vector: those are not stored)
+    if (a == v0 && b == v0 + 16) {
+        uint4 o4; o4.x = acc[0]; o4.y = acc[1]; o4.z = acc[2]; o4.w = acc[3];
+        *reinterpret_cast<uint4 *>(dst) = o4;
+    } else {                                            // (the output's first or last vector)
+        const uint32_t ta = (uint32_t)(a - v0), tb = (uint32_t)(b - v0);
+#pragma unroll
+        for (uint32_t t = 0; t < 16; t++) if (t >= ta && t < tb) dst[t] = (uint8_t)(acc[t >> 2] >> (8 * (t & 3)));
+    }
+}
+
+hipError_t launch_fetch_text(const FetchJob &J, hipStream_t st)
+{
+    if (!J.n || !J.total) return hipSuccess;
+    const uint64_t span = (uint64_t)((uintptr_t)J.out & 15u) + J.total;
+    const uint64_t tiles = (span + kFetchTileBytes - 1) / kFetchTileBytes;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_fetch_text, dim3((unsigned)tiles), dim3(kFetchThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t upload_fetch_comp_table(const unsigned char *tab128)
+{
+    return hipMemcpyToSymbol(HIP_SYMBOL(c_fcomp), tab128, 128);
 }
 
 hipError_t launch_pack_text(const PackJob &J, hipStream_t st)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pack_text.h"
+#include "engine_internal.h"
 
 namespace crass {
 
@@ -27,5 +28,21 @@ hipError_t launch_pack_text(const PackJob &J, hipStream_t st);
 // exc_bytes[exc_off[e] .. exc_off[e + 1]) = the text of read exc_read[e]; off / uni_*: as in PackJob
 hipError_t launch_gather_exc_text(const uint8_t *text, uint64_t bias, const uint64_t *off, uint64_t uni_base, uint32_t uni_len,
                                   const uint64_t *exc_read, const uint64_t *exc_off, uint64_t n_exc, uint8_t *exc_bytes, hipStream_t st);
+
+// ---- the way back (pack.hip): records of the resident set as text ----
+// Record k is the read idx[k] (LOCAL index) of R, reverse-complemented when rc && rc[k]; its text goes to
+// out[out_off[k] .. out_off[k + 1]).  out_off is the exclusive prefix sum of the records' lengths (the caller computes it: it
+// sizes the output from it), total = out_off[n].  out may have any alignment; no byte outside out[0 .. total) is written.
+struct FetchJob {
+    DevReads R;
+    const uint64_t *idx;            // device, [n]
+    const uint8_t *rc;              // device, [n], or nullptr: every record forward
+    const uint64_t *out_off;        // device, [n + 1]
+    uint64_t n, total;
+    uint8_t *out;
+};
+hipError_t launch_fetch_text(const FetchJob &J, hipStream_t st);
+// the reverse-complement table of merge.cpp (build_comp_table) for k_fetch_text's exception reads, on the current device
+hipError_t upload_fetch_comp_table(const unsigned char *tab128);
 
 } // namespace crass

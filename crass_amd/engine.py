@@ -145,6 +145,38 @@ class ResidentReads:
             pass
 
 
+class Text:
+    """Records of sequence text (crass_text): `chars` (uint8) and `off` (uint64, n + 1) are numpy VIEWS of the memory the
+    library owns — valid until the owner's next fetch, load or close; t[k] copies record k out as bytes."""
+
+    def __init__(self, v):
+        self.n = int(v.n)
+        self.off = np.ctypeslib.as_array(v.off, shape=(self.n + 1,))
+        total = int(self.off[self.n])
+        self.chars = np.ctypeslib.as_array(v.chars, shape=(total,)) if total else np.zeros(0, np.uint8)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, k):
+        k = int(k)
+        if k < 0:
+            k += self.n
+        if not 0 <= k < self.n:
+            raise IndexError(k)
+        return self.chars[int(self.off[k]):int(self.off[k + 1])].tobytes()
+
+
+def _fetch_args(idx, revcomp):
+    a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+    rc = None
+    if revcomp is not None:
+        rc = np.ascontiguousarray(np.asarray(revcomp).reshape(-1) != 0, dtype=np.uint8)
+        if len(rc) != len(a):
+            raise ValueError("one reverse-complement flag per index")
+    return a, rc
+
+
 def pack_layout(offsets, pad_uniform):
     """(stride_words, uniform_len) the packers give reads with these byte offsets (crass_pack_layout; no GPU needed)."""
     off = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -552,6 +584,39 @@ class SearchEngine:
         """HIP-event milliseconds of the last load_text / attach_device_text call's pack kernels (stage timing >= 1, else 0)."""
         return float(self.lib.crass_hip_last_pack_ms(self.h))
 
+    def fetch_text(self, idx, revcomp=None, out=None):
+        """The text of the reads idx (GLOBAL indices: candidates' / recruits' read_idx as they are), reverse-complemented
+        where revcomp[k] is set, unpacked on the device (crass_hip_fetch_text).  Returns a Text.  out: a contiguous torch
+        uint8 DEVICE tensor — the text is written there instead (crass_hip_fetch_text_device) and the offsets (uint64,
+        n + 1) are returned; a tensor too small raises CrassError with status 8 and the offsets in its `offsets`."""
+        a, rc = _fetch_args(idx, revcomp)
+        if out is None:
+            v = _abi.Text()
+            _chk(self.lib.crass_hip_fetch_text(self.h, a.ctypes.data if len(a) else None, None if rc is None else rc.ctypes.data, len(a),
+                                               C.byref(v)), "crass_hip_fetch_text")
+            return Text(v)
+        if str(out.dtype) != "torch.uint8" or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("fetch_text(out=...) needs a contiguous uint8 device tensor")
+        off = np.zeros(len(a) + 1, np.uint64)
+        st = self.lib.crass_hip_fetch_text_device(self.h, a.ctypes.data if len(a) else None, None if rc is None else rc.ctypes.data, len(a),
+                                                  int(out.data_ptr()) if out.numel() else None, int(out.numel()), off.ctypes.data)
+        if st != 0:
+            e = CrassError(st, "crass_hip_fetch_text_device")
+            e.offsets = off
+            raise e
+        return off
+
+    def fetch_record_text(self, pass_):
+        """RH_Seq of every record of the last pass 1 (pass_ = 1: the candidates' order) or pass 2 (2: the recruits'): the
+        read's text, reverse-complemented where low_lexi is 0 (crass_hip_fetch_record_text).  Returns a Text."""
+        v = _abi.Text()
+        _chk(self.lib.crass_hip_fetch_record_text(self.h, int(pass_), C.byref(v)), "crass_hip_fetch_record_text")
+        return Text(v)
+
+    def last_fetch_ms(self):
+        """HIP-event milliseconds of the last fetch's kernel (stage timing >= 1, else 0)."""
+        return float(self.lib.crass_hip_last_fetch_ms(self.h))
+
     def packed(self):
         """The resident read set copied back (crass_hip_get_packed): a ResidentReads with PackedReads' fields."""
         return ResidentReads(self)
@@ -822,6 +887,15 @@ class SearchGroup:
         v = _abi.Recruits()
         self._chk(self.lib.crass_hip_group_get_recruits(self.h, C.byref(v)), "crass_hip_group_get_recruits")
         return RecruitSet(v)
+
+    def fetch_text(self, idx, revcomp=None):
+        """SearchEngine.fetch_text over the whole job: every global index goes to the rank whose shard holds it, the records
+        come back in idx's order (crass_hip_group_fetch_text).  Returns a Text owned by the group."""
+        a, rc = _fetch_args(idx, revcomp)
+        v = _abi.Text()
+        self._chk(self.lib.crass_hip_group_fetch_text(self.h, a.ctypes.data if len(a) else None, None if rc is None else rc.ctypes.data,
+                                                      len(a), C.byref(v)), "crass_hip_group_fetch_text")
+        return Text(v)
 
     def rank_counters(self, rank):
         c = _abi.Counters()

@@ -520,6 +520,45 @@ float crass_hip_last_pack_ms(const crass_hip_ctx *ctx);
  * the packed form of text it loaded with crass_hip_load_text / crass_hip_attach_device_text.  CRASS_ERR_STATE: no reads.
  * (No reference counterpart: crass reads its input files again for every pass.) */
 int  crass_hip_get_packed(const crass_hip_ctx *ctx, crass_packed *out);
+/* ---- the text of selected reads, out of the resident set ----
+ * n records back to back: record k is chars[off[k] .. off[k+1]), off[n+1] the exclusive prefix sum of the records' lengths.
+ * The gather and the unpacking run on the device (k_fetch_text, pack.hip), where the words are: only the selected reads'
+ * bytes move.  Reads without an exception come back as A C G T from their codes; exception reads as the raw bytes they were
+ * loaded with ('N', lower case, 0x00, 0xFF).  revcomp[k] != 0 (revcomp may be NULL: none) gives the reverse complement by
+ * reverseComplement's table (SeqUtils.cpp:50-59): byte i = table[byte[len - 1 - i] & 127].  Works on every resident set,
+ * however it was loaded or attached; a read may be listed more than once.
+ * Errors (nothing is launched, the resident set is untouched): CRASS_ERR_INVALID_ARG — a NULL context or result pointer, a
+ * NULL index array with n > 0, an index outside [read_index_base, read_index_base + n_reads), a pass other than 1 or 2;
+ * CRASS_ERR_STATE — no reads resident, no results of that pass. */
+typedef struct {
+    uint64_t        n;
+    const uint8_t  *chars;         /* off[n] bytes                                                   */
+    const uint64_t *off;           /* [n+1]                                                          */
+} crass_text;
+/* replaces: the second reading of the input files in findSingletons (the getFileHandle / kseq_read loop of libcrispr.cpp:471-487)
+ * and any host copy of the text a caller kept only to look up the reads the search returned.  read_idx: GLOBAL indices
+ * (read_index_base + local) — crass_candidates.read_idx and crass_recruits.read_idx as they are.  The result lives in the
+ * context's pinned memory, valid until the next fetch, load or destroy.  One copy up per array, an exact-size copy back, one
+ * host wait; n == 0 (or empty reads only): an empty result, nothing launched, no wait. */
+int crass_hip_fetch_text(crass_hip_ctx *ctx, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *out);
+/* replaces: the same loop (libcrispr.cpp:471-487) for a caller whose next stage is on the device: the text goes into the caller's
+ * DEVICE buffer d_chars (cap_bytes bytes, any alignment; a torch uint8 tensor), the offsets into the host array off_out[n+1].
+ * cap_bytes < off_out[n]: CRASS_ERR_OVERFLOW with off_out filled and nothing written to d_chars — size the buffer from off_out[n]
+ * and call again (d_chars may be NULL when cap_bytes is 0).  No byte at or beyond d_chars + off_out[n] is written. */
+int crass_hip_fetch_text_device(crass_hip_ctx *ctx, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n,
+                                uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out);
+/* replaces: ReadHolder's RH_Seq (ReadHolder.h; filled from the kseq record at libcrispr.cpp:471-487 and reversed by DRLowLexi,
+ * ReadHolder.cpp:513-591) for every record of the last pass 1 (pass == 1: the candidates, in crass_hip_get_candidates' order) or
+ * pass 2 (pass == 2: the recruits, in crass_hip_get_recruits' order): record k = low_lexi[k] ? seq : revcomp(seq) of the read
+ * read_idx[k] — what crass_graph_input.seq_chars takes. */
+int crass_hip_fetch_record_text(crass_hip_ctx *ctx, int pass, crass_text *out);
+/* HIP-event time, in milliseconds on the context's stream, of the fetch kernel of the last crass_hip_fetch_* call; measured
+ * when the stage timing level is >= 1 (crass_hip_set_stage_timing), else 0.  (No reference counterpart: crass has no timers.) */
+float crass_hip_last_fetch_ms(const crass_hip_ctx *ctx);
+/* replaces: the second reading of the input files (libcrispr.cpp:471-487) for a group (crass_hip_group_*): crass_hip_fetch_text
+ * over the whole job.  Every global index is routed to the rank whose shard holds it; the records come back in the caller's
+ * order in one crass_text owned by the group, valid until the next group fetch, load or destroy. */
+int crass_hip_group_fetch_text(crass_hip_group *g, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *out);
 /* the two decisions of the packers on their own, for callers and tests without a GPU: the layout crass_pack_reads and
  * crass_hip_load_text give a set (stride_words / uniform_len as in crass_reads), and the byte -> code function both use —
  * four sequence bytes (byte 0 first) -> their 2-bit codes in bits [2i, 2i+2), *bad bit i set when byte i is not A C G T
