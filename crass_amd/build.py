@@ -10,8 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrass_hip.so")
-SOURCES = ["kernels.hip", "dmerge.hip", "consensus.hip", "pack.hip", "engine.cpp", "merge.cpp", "ingest.cpp", "consensus.cpp", "group.cpp", "graph.cpp", "sdma.cpp", "pgzip.cpp"]
-DEPS = SOURCES + ["engine_internal.h", "devmem.h", "pack_text.h", "pack_launch.h", "consensus_internal.h", "merge.h", os.path.join("..", "..", "include", "crass_hip.h")]
+SOURCES = ["kernels.hip", "pass2.hip", "sinks.hip", "dmerge.hip", "consensus.hip", "pack.hip", "engine.cpp", "merge.cpp", "ingest.cpp", "consensus.cpp", "group.cpp", "graph.cpp", "sdma.cpp", "pgzip.cpp"]
+# a newer header rebuilds every source: no per-source include lists to keep true
+HEADERS = ["engine_internal.h", "dev_common.h", "comp_table.h", "devmem.h", "pack_text.h", "pack_launch.h", "consensus_internal.h", "merge.h", os.path.join("..", "..", "include", "crass_hip.h")]
 
 
 def _hipcc():
@@ -22,7 +23,6 @@ def _hipcc():
 
 
 OBJ = os.path.join(CSRC, "_obj")
-HEADERS = ["engine_internal.h", "devmem.h", "pack_text.h", "pack_launch.h", "consensus_internal.h", "merge.h", os.path.join("..", "..", "include", "crass_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function"]
 LIBS = ["-lz", "-lpthread", "-ldl"]
 
@@ -35,7 +35,7 @@ def _stale(target, deps):
 
 
 def needs_build():
-    return _stale(LIB, [os.path.join(CSRC, d) for d in DEPS])
+    return _stale(LIB, [os.path.join(CSRC, d) for d in SOURCES + HEADERS])
 
 
 def build(force=False, verbose=False):

@@ -16,6 +16,7 @@
 #include "consensus_internal.h"
 #include "engine_internal.h"
 #include "merge.h"
+#include "comp_table.h"
 
 #include <algorithm>
 #include <array>
@@ -1003,7 +1004,7 @@ int crass_hip_consensus(const crass_params *p, int device, const crass_cons_inpu
     if (hipSetDevice(device) != hipSuccess) return CRASS_ERR_NO_DEVICE;
     s->st = take_stream(device);
     if (!s->st) return CRASS_ERR_HIP;
-    build_comp_table(s->comp);
+    memcpy(s->comp, kCompTable.v, sizeof s->comp);
     aligner_ksw_params(s->ksw);
     int rc = CRASS_OK;
     const bool timing = getenv("CRASS_TIMING") != nullptr;

@@ -46,7 +46,7 @@ static __device__ __forceinline__ uint32_t kset_hash(uint32_t key, uint32_t log_
 }
 static __device__ __forceinline__ uint32_t ak_h(uint32_t v, uint32_t m, uint32_t rsh)
 {
-    return ak_hash(v, m) >> rsh;                              // same hash as anchor_probe (kernels.hip)
+    return ak_hash(v, m) >> rsh;                              // same hash as anchor_probe_any (pass2.hip)
 }
 
 // number of tokens: M.n_tok, or — when the merge is launched before the host knows the count (crass_hip_seed_scan
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void k_dm_redundant(DevMerge M)
 }
 
 // ---- 6a. anchor keys: every 16-mer at offset 0..7 of a pattern — or, patterns of fewer than 23 / 19 bases, the 16-mers / 12-mers at
-// offsets 0..3 (kDevMinDR, engine_internal.h) — (see kernels.hip, pass-2 fast path).  A member that
+// offsets 0..3 (kDevMinDR, engine_internal.h) — (see pass2.hip, pass-2 fast path).  A member that
 // survived is a pattern (pid 2t) and so is its reverse complement (pid 2t + 1, WorkHorse.cpp:690-697); entry
 // e = pid * 8 + r = 16 t + 8 o + r.  Distinct keys are claimed in an open-addressing set and counted (thread per entry:
 // a wave-per-member form inside k_dm_redundant ran the claims at a quarter of the lanes behind that kernel's probe
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(256) void k_dm_fill_finish(DevMerge M)
         uint32_t v = M.anchor_tab[2 * w + q];
         if (fill && v == 0xFFFFFFFFu) v = k0;           // (the slot's own thread stores the same value)
         const uint32_t p1 = ak_hash(v, M.m1) >> 16, p2 = ak_hash(v, M.m2) >> 16, slot = 2 * w + q;
-        out |= (slot == p1 ? p2 : p1) << (16 * q);       // the key's other slot (anchor_probe_fp, kernels.hip)
+        out |= (slot == p1 ? p2 : p1) << (16 * q);       // the key's other slot (anchor_probe_any, MODE 3, pass2.hip)
     }
     M.anchor_fp[w] = out;
 }

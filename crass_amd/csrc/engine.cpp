@@ -3,7 +3,7 @@
 // the ordered hand-off (candidates, tokens, groups, patterns, recruits).
 //
 // There is no CPU fallback anywhere in this file: every search decision is made by the HIP
-// kernels in kernels.hip; the host only orders, tokenises and clusters their output
+// kernels in kernels.hip, pass2.hip and sinks.hip; the host only orders, tokenises and clusters their output
 // ("stays on host").
 #include "../../include/crass_hip.h"
 #include "engine_internal.h"
@@ -784,9 +784,6 @@ int crass_hip_create(const crass_params *p, int device, crass_hip_ctx **out)
         c->dx_via_dma = c->dma_dx[0] && c->dma_dx[1] && c->dma_dx[2];
     }
     (void)warm_dmerge_module();                         // (code-object load: here, not inside the first merge)
-    unsigned char tab[128];
-    build_comp_table(tab);
-    if (upload_comp_table(tab) != hipSuccess || upload_fetch_comp_table(tab) != hipSuccess) { delete c; return CRASS_ERR_HIP; }
     *out = c;
     return CRASS_OK;
 }

@@ -1,4 +1,4 @@
-// engine_internal.h — types shared by the HIP kernels (kernels.hip) and the host engine
+// engine_internal.h — types shared by the HIP kernels (kernels.hip, pass2.hip, sinks.hip) and the host engine
 // (engine.cpp).  Not part of the public ABI (include/crass_hip.h is).
 #pragma once
 #include <stdint.h>
@@ -325,7 +325,7 @@ struct SurvLds {
     uint32_t ss_slot;             // entries per survivor slot of the start/stop pool in slot mode: the FULL layout's ss_cap in every launch of a set
 };
 
-// ---- launch wrappers implemented in kernels.hip (all asynchronous on `st`) ----
+// ---- launch wrappers implemented in kernels.hip, pass2.hip and sinks.hip (all asynchronous on `st`) ----
 hipError_t launch_filter_general(const DevReads &R, const DevParams &P, uint64_t *hitmask,
                                  uint32_t max_len, hipStream_t st);
 // per-position seed hints for long / ragged packed reads (default window and DR/spacer bounds only):
@@ -527,6 +527,5 @@ hipError_t launch_dr_dedupe(const char *dr, const uint16_t *dr_len, uint32_t str
 // with err == 6 and are redone with the uncapped layout)
 SurvLds survivor_lds_layout(uint32_t max_len, const DevParams &P, uint32_t row_len_cap = 0xFFFFFFFFu,
                             uint32_t seq_window_bytes = 0, uint32_t ss_entries_cap = 0);   // the two caps of the long-read layout (0: none)
-hipError_t upload_comp_table(const unsigned char *tab128);
 
 } // namespace crass

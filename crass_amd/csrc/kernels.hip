@@ -1,118 +1,26 @@
-// kernels.hip — hand-written HIP kernels for gfx950 (MI355X, CDNA4, wave64).
+// kernels.hip — hand-written HIP kernels for gfx950 (MI355X, CDNA4, wave64): pass 1's search.
 //
 // The hot path of crass's WorkHorse search (reference citations are relative to the
 // crass v1.0.1 tree):
 //   pass 1  searchCore / scanRight / extendPreRepeat / qcFoundRepeats / DRLowLexi
 //           (src/crass/libcrispr.cpp:170-395,520-1069, ReadHolder.cpp:513-609,
-//            PatternMatcher.cpp:26-204)
+//            PatternMatcher.cpp:26-204)                                     this file
 //   pass 2  findSingletons / on_match over an Aho-Corasick automaton
-//           (src/crass/libcrispr.cpp:399-518, src/aho-corasick/acism.c:25-106)
+//           (src/crass/libcrispr.cpp:399-518, src/aho-corasick/acism.c:25-106)     pass2.hip
+//   ordered compaction, de-duplication and the hand-off blobs of both passes         sinks.hip
 //
 // Integer/byte work, HBM- and issue-bound: no MFMA.  Reads are 2-bit packed and streamed
 // once per pass; wave64 ballot/ffs gives Boyer-Moore's "leftmost occurrence" for free;
 // the pass-2 automaton is staged in LDS when it fits.  Compile with -ffp-contract=off:
 // qcFoundRepeats' float evaluation order is part of the parity contract.
-#include "engine_internal.h"
+#include "dev_common.h"
+#include "comp_table.h"
 #include <type_traits>
 #include <algorithm>
 
 namespace crass {
 
-#define WAVE 64
-
-__constant__ unsigned char c_comp[128];     // reverseComplement table, SeqUtils.cpp:50-59
-
-static __device__ __forceinline__ void wave_sync()
-{
-    // LDS traffic of one wave is executed in order; this only stops the compiler from
-    // moving LDS accesses across the point where lanes exchange data through LDS.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A value that is the same in every lane but was read from LDS (or computed from such a read) lives in a VGPR as far as the
-// compiler knows, and everything derived from it — loop counters, branch conditions — becomes vector arithmetic under exec
-// masks.  The wave-per-read kernel's control flow is wave-uniform throughout: naming the value once puts it, and what follows
-// from it, on the scalar unit.
-static __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-static __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-static __device__ __forceinline__ uint64_t uni64(uint64_t x) { return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | (uint64_t)uni((uint32_t)x); }
-
-static __device__ __forceinline__ uint64_t rd_word_off(const DevReads &R, uint64_t r)
-{
-    return R.stride_words ? r * (uint64_t)R.stride_words : R.word_off[r];
-}
-static __device__ __forceinline__ uint32_t rd_len(const DevReads &R, uint64_t r)
-{
-    return R.uniform_len ? R.uniform_len : R.lengths[r];
-}
-static __device__ __forceinline__ bool rd_is_exc(const DevReads &R, uint64_t r)
-{
-    return (R.exc_mask[r >> 5] >> (r & 31)) & 1u;
-}
-// first word of read r's position hints: reads of one length need no table look-up (a dependent global load per read in the
-// wave kernel's prefetch otherwise)
-static __device__ __forceinline__ uint64_t rd_hint_off(const DevReads &R, uint64_t r)
-{
-    return R.uniform_len ? r * (uint64_t)((R.uniform_len + 63u) >> 6) : R.pos_hint_off[r];
-}
-static __device__ __forceinline__ uint64_t rd_header_id(const DevReads &R, uint64_t r)
-{
-    return R.header_id ? R.header_id[r] : r;
-}
-
-// ------------------------------------------------------------------------------------
-// exception bit mask
-// ------------------------------------------------------------------------------------
-__global__ void k_build_exc_mask(const uint64_t *exc_read, uint64_t n_exc, uint32_t *exc_mask)
-{
-    uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i < n_exc) {
-        uint64_t r = exc_read[i];
-        atomicOr(&exc_mask[r >> 5], 1u << (r & 31));
-    }
-}
-
-__global__ void k_mark_found(const uint64_t *idx, uint64_t n, const uint64_t *header_id, uint8_t *found_flag)
-{
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i < n) { const uint64_t r = idx[i]; found_flag[header_id ? header_id[r] : r] = 1; }
-}
-hipError_t launch_mark_found(const uint64_t *idx, uint64_t n, const uint64_t *header_id, uint8_t *found_flag, hipStream_t st)
-{
-    if (!n) return hipSuccess;
-    CRASS_LAUNCH(k_mark_found, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, idx, n, header_id, found_flag);
-    return hipGetLastError();
-}
-
-// Device -> pinned host copy by a handful of workgroups (the link is the bound: ~55 GB/s needs a few hundred stores in
-// flight, not a chip): the fall-back of the DMA-engine copy (sdma.cpp).  Like the runtime's blit kernel it costs the kernels
-// of the other stream its own duration — PCIe stores from shader waves do, however few waves issue them and on however
-// many XCDs (profiles/NOTES_r03.md §9) — so the engine orders it behind the merge kernels.
-__global__ __launch_bounds__(256) void k_copy_to_host(const uint4 *src, uint4 *dst, uint64_t n16, const uint8_t *src_tail, uint8_t *dst_tail, uint32_t n_tail)
-{
-    const uint64_t nth = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n16; i += nth) dst[i] = src[i];
-    if (blockIdx.x == 0 && threadIdx.x < n_tail) dst_tail[threadIdx.x] = src_tail[threadIdx.x];
-}
-hipError_t launch_copy_to_host(const void *d_src, void *h_dst, uint64_t bytes, hipStream_t st)
-{
-    if (!bytes) return hipSuccess;
-    if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(h_dst)) & 15u) return hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st);
-    const uint64_t n16 = bytes / 16;
-    const unsigned blocks = (unsigned)std::min<uint64_t>(32, (n16 + 255) / 256 + 1);
-    CRASS_LAUNCH(k_copy_to_host, dim3(blocks), dim3(256), 0, st, static_cast<const uint4 *>(d_src), static_cast<uint4 *>(h_dst), n16,
-                 static_cast<const uint8_t *>(d_src) + n16 * 16, static_cast<uint8_t *>(h_dst) + n16 * 16, (uint32_t)(bytes & 15u));
-    return hipGetLastError();
-}
-
-hipError_t launch_build_exc_mask(const uint64_t *exc_read, uint64_t n_exc, uint32_t *exc_mask, hipStream_t st)
-{
-    if (!n_exc) return hipSuccess;
-    CRASS_LAUNCH(k_build_exc_mask, dim3((unsigned)((n_exc + 255) / 256)), dim3(256), 0, st, exc_read, n_exc, exc_mask);
-    return hipGetLastError();
-}
+static __constant__ CompTable c_comp = make_comp_table();     // reverseComplement table, SeqUtils.cpp:50-59
 
 // ------------------------------------------------------------------------------------
 // pass 1, step 1: seed-scan filter (general parameters, any read length)
@@ -200,12 +108,6 @@ hipError_t launch_filter_general(const DevReads &R, const DevParams &P, uint64_t
 // The window's right clamp (libcrispr.cpp:301-304) and bases in the padding are ignored:
 // that can only ADD survivors (superset contract), never lose one.
 // ------------------------------------------------------------------------------------
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    u16x2 r = __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b));   // v_pk_min_u16
-    return __builtin_bit_cast(uint32_t, r);
-}
 
 // Fully unrolled implementation: D0..D1 are compile-time so every register index is static.
 // LCT: compile-time read length (0 = unknown).  With it, shifts that would put the window past the
@@ -811,252 +713,106 @@ hipError_t launch_hint_positions(const DevReads &R, const DevParams &P, const ui
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------
-// ordered compaction: bit mask -> ascending list of set-bit indices
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_mask_count(const uint64_t *mask, uint64_t n_words, uint64_t n_bits,
-                                                     uint32_t *word_prefix, uint32_t *block_sums)
+// The every-position form of the scan for one hint word: bit p is set iff the wn-mer at position p has a copy D0 .. D1 further on
+// (k_filter_fast_any's test, any window and lattice).  Used by the filter below and by the light walk k_long_light_any.
+static __device__ __forceinline__ uint64_t hint_bits_every(const uint32_t (&w)[13], int wn, int D0, int D1)
 {
-    __shared__ uint32_t sh[256];
-    uint64_t wi = blockIdx.x * 256ull + threadIdx.x;
-    uint32_t c = 0;
-    if (wi < n_words) {
-        uint64_t m = mask[wi];
-        uint64_t rem = n_bits - wi * 64;
-        if (rem < 64) m &= (1ull << rem) - 1ull;
-        c = (uint32_t)__popcll(m);
-    }
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        uint32_t v = (threadIdx.x >= (unsigned)off) ? sh[threadIdx.x - off] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if (wi < n_words) word_prefix[wi] = sh[threadIdx.x] - c;
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = sh[255];
-}
-
-__global__ __launch_bounds__(1024) void k_block_scan(uint32_t *block_sums, uint32_t n_blocks, uint32_t *d_count, uint32_t *zero_a, uint32_t n_a, uint32_t *zero_b, uint32_t n_b)
-{
-    // counters the NEXT stage accumulates into are cleared here instead of by their own fill launches
-    if (threadIdx.x < n_a) zero_a[threadIdx.x] = 0u;
-    if (threadIdx.x < n_b) zero_b[threadIdx.x] = 0u;
-
-    __shared__ uint32_t sh[1024];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_blocks; base += 1024) {
-        uint32_t i = base + threadIdx.x;
-        uint32_t c = (i < n_blocks) ? block_sums[i] : 0;
-        sh[threadIdx.x] = c;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            uint32_t v = (threadIdx.x >= (unsigned)off) ? sh[threadIdx.x - off] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += v;
-            __syncthreads();
-        }
-        uint32_t excl = sh[threadIdx.x] - c + carry;
-        if (i < n_blocks) block_sums[i] = excl;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *d_count = carry;
-}
-
-__global__ __launch_bounds__(256) void k_mask_scatter(const uint64_t *mask, uint64_t n_words, uint64_t n_bits,
-                                                       const uint32_t *word_prefix, const uint32_t *block_sums,
-                                                       uint64_t *out_idx, uint64_t out_cap)
-{
-    uint64_t wi = blockIdx.x * 256ull + threadIdx.x;
-    if (wi >= n_words) return;
-    uint64_t m = mask[wi];
-    uint64_t rem = n_bits - wi * 64;
-    if (rem < 64) m &= (1ull << rem) - 1ull;
-    uint64_t o = (uint64_t)block_sums[blockIdx.x] + word_prefix[wi];
-    while (m) {
-        int b = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        if (o < out_cap) out_idx[o] = wi * 64 + b;
-        o++;
-    }
-}
-
-// ---- single-pass form: decoupled look-back over tiles of 1024 mask words ----
-static __device__ __forceinline__ unsigned long long lb_pack(uint32_t epoch, uint32_t flag, uint32_t value)
-{
-    return ((unsigned long long)epoch << 34) | ((unsigned long long)flag << 32) | value;
-}
-// Exclusive prefix of this tile's total over the tiles before it.  Called by every thread of the block
-// (one __syncthreads inside); wave 0 does the look-back, 64 predecessor tiles per step.
-static __device__ uint32_t lb_exclusive_prefix(const Lookback &lb, uint32_t tile, uint32_t total)
-{
-    __shared__ uint32_t excl_sh;
-    if (threadIdx.x < 64) {
-        const int lane = (int)threadIdx.x;
-        if (lane == 0)
-            __hip_atomic_store(&lb.status[tile], lb_pack(lb.epoch, tile == 0 ? 2u : 1u, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t excl = 0;
-        int t = (int)tile - 1;                           // wave-uniform: this step looks at tiles t, t-1, ..., t-63
-        while (t >= 0) {
-            const int idx = t - lane;
-            uint32_t flag = 2u, val = 0u;                // tiles before tile 0: an empty prefix
-            if (idx >= 0) {
-                flag = 0u;
-                for (uint32_t spins = 0; spins < (1u << 24); spins++) {
-                    const unsigned long long w = __hip_atomic_load(&lb.status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((uint32_t)(w >> 34) == lb.epoch && ((w >> 32) & 3ull) != 0ull) { flag = (uint32_t)(w >> 32) & 3u; val = (uint32_t)w; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                if (flag == 0u) { *lb.fail = 1u; flag = 2u; }               // gave up (pinned host word): terminate, the host reports it
+    const int s1 = min(1, wn - 1), s2 = min(2, wn - 1 - s1), s3 = min(4, wn - 1 - s1 - s2), s4 = wn - 1 - s1 - s2 - s3;
+    uint32_t nz[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        if (16 * q + 15 < D0 || 16 * q > D1) continue;
+        const int sb_lo = max(0, D0 - 16 * q), sb_hi = min(15, D1 - 16 * q);
+        for (int sb = sb_lo; sb <= sb_hi; sb++) {
+            const uint32_t sh = (uint32_t)(2 * sb);
+            uint32_t z[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const uint32_t x = __builtin_amdgcn_alignbit(w[k + q + 1], w[k + q], sh) ^ w[k];
+                z[k] = x | (x >> 1);
             }
-            const unsigned long long pm = __ballot(flag == 2u);
-            const int stop = pm ? __ffsll(pm) - 1 : 64;  // nearest tile whose inclusive prefix is known
-            uint32_t v = lane <= stop ? val : 0u;
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
-            excl += v;
-            if (pm) break;
-            t -= 64;
+            for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s1));
+            if (s2 > 0) {
+                z[4] |= z[4] >> (2 * s1);
+#pragma unroll
+                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s2));
+            }
+            if (s3 > 0) {
+                z[4] |= z[4] >> (2 * s2);
+#pragma unroll
+                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s3));
+            }
+            if (s4 > 0) {
+                z[4] |= z[4] >> (2 * s3);
+#pragma unroll
+                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s4));
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) nz[k] &= z[k];
         }
-        if (lane == 0) {
-            if (tile != 0) __hip_atomic_store(&lb.status[tile], lb_pack(lb.epoch, 2u, excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            excl_sh = excl;
-        }
     }
-    __syncthreads();
-    return excl_sh;
-}
-// A tile id per block, in start order.  n_act blocks of the launch call this (every block computes the same n_act; the
-// others have returned before): the block that draws the last ticket puts the counter back to zero for the next launch — by
-// then every other ticket of this launch has been drawn.  (The counter is ONE word for all launches of a context's stream.
-// Returning atomics on one address retire every 20-30 ns on this part however many CUs issue them — the whole cost of a
-// look-back kernel over a few thousand tiles, rocprofv3 round 4: 1 526 tiles of the read mask 32 us, 4 950 mostly EMPTY
-// tiles of the candidate list 50 us — so tiles are fat, and tiles past a device-side count draw no ticket at all.)
-static __device__ uint32_t lb_tile_id(const Lookback &lb, uint32_t n_act)
-{
-    __shared__ uint32_t tile_sh;
-    if (threadIdx.x == 0) {
-        const uint32_t t = atomicAdd(lb.ticket, 1u);
-        if (t + 1u >= n_act) __hip_atomic_store(lb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tile_sh = t;
-    }
-    __syncthreads();
-    return tile_sh;
-}
-// exclusive prefix of v over the T threads of the block; *total = block sum
-template <int T>
-static __device__ uint32_t block_scan_t(uint32_t v, uint32_t *total)
-{
-    __shared__ uint32_t wsum[T / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, off);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < T / 64; k++) { const uint32_t s = wsum[k]; if (k < wv) base += s; all += s; }
-    *total = all;
-    return base + incl - v;
+    // bit 2p of ~nz[k] = a copy exists for position 16 k + p: the even bits of the four words, packed
+    auto even16 = [](uint32_t x) {
+        x &= 0x55555555u;
+        x = (x | (x >> 1)) & 0x33333333u;
+        x = (x | (x >> 2)) & 0x0F0F0F0Fu;
+        x = (x | (x >> 4)) & 0x00FF00FFu;
+        x = (x | (x >> 8)) & 0x0000FFFFu;
+        return x;
+    };
+    const uint32_t lo = even16(~nz[0]) | (even16(~nz[1]) << 16), hi = even16(~nz[2]) | (even16(~nz[3]) << 16);
+    return ((uint64_t)hi << 32) | (uint64_t)lo;
 }
 
-// T threads x W consecutive mask words per tile: 1024 x 4 for the masks over all reads (few, fat tiles: the ticket is the
-// kernel's cost), 256 x 1 for the short dense masks of the later stages (more blocks for the per-word scatter loops)
-template <int T, int W>
-__global__ __launch_bounds__(T) void k_mask_compact_lb(const uint64_t *mask, uint64_t n_words, uint64_t n_bits, uint32_t *word_prefix,
-                                                        uint32_t *block_sums, uint64_t *out_idx, uint64_t out_cap, uint32_t *d_count,
-                                                        uint32_t *zero_a, uint32_t n_a, uint32_t *zero_b, uint32_t n_b, Lookback lb,
-                                                        uint32_t n_tiles)
+// The seed-scan FILTER of reads of 257 .. 2 048 bases (and of sets whose strides differ) under another window or seed lattice
+// (-w, -d): no position hints are kept for those (the walks' hint forms know the default lattice), so a tile's bits are computed,
+// cut to the lattice positions j = i * skips <= searchEnd, and only the read's bit in the (cleared) filter mask is set.  A superset
+// like every filter here; 11 instructions per word and shift for every position — four times the lattice-class kernel, a fifth of
+// k_filter_general, which these sets took until now.
+__global__ __launch_bounds__(256) void k_hint_filter_any(DevReads R, DevParams P, const uint64_t *hint_off, const uint32_t *blk_read, uint64_t n_words,
+                                                         uint64_t *hitmask, uint64_t *hint_bits)
 {
-    const uint32_t tile = lb_tile_id(lb, n_tiles);
-    if (tile == 0) {                                    // counters the NEXT stage accumulates into
-        if (threadIdx.x < n_a) zero_a[threadIdx.x] = 0u;
-        if (threadIdx.x < n_b) zero_b[threadIdx.x] = 0u;
-    }
-    const uint64_t w0 = ((uint64_t)tile * T + threadIdx.x) * W;
-    uint64_t m[W];
-    uint32_t cnt = 0;
+    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (t >= n_words) return;
+    uint64_t r;
+    uint32_t tile;
+    hint_tile_read(R, hint_off, blk_read, t, n_words, r, tile);
+    const uint32_t L = rd_len(R, r);
+    const int D0 = (int)(P.lowDR + P.lowSp), D1 = (int)(P.highDR + P.highSp);
+    const int last = (int)L - D0 - (int)P.window - 1 - (int)(tile * 64u);        // searchEnd, counted from this tile's first position
+    if (last < 0) { hint_bits[t] = 0ull; return; }
+    const uint32_t nw = (L + 15) >> 4;
+    const uint32_t *g = R.packed + rd_word_off(R, r) + tile * 4u;
+    const uint32_t rem = nw - tile * 4u;
+    uint32_t w[13];
 #pragma unroll
-    for (int q = 0; q < W; q++) {
-        const uint64_t wi = w0 + q;
-        m[q] = 0;
-        if (wi < n_words) {
-            m[q] = mask[wi];
-            const uint64_t rem = n_bits - wi * 64;
-            if (rem < 64) m[q] &= (1ull << rem) - 1ull;
-        }
-        cnt += (uint32_t)__popcll(m[q]);
+    for (int i = 0; i < 13; i++) w[i] = (uint32_t)i < rem ? g[i] : 0u;
+    uint64_t bits = hint_bits_every(w, (int)P.window, D0, D1);
+    if (last < 63) bits &= (2ull << last) - 1ull;
+    // every position's bit is kept: the survivors' walks step over the positions whose bit is clear, on the lattice and — behind a
+    // rejected candidate — off it (DevReads.hint_all)
+    hint_bits[t] = bits;
+    // the lattice: positions that are multiples of skips
+    const uint32_t skips = P.skips;
+    if (skips > 1) {
+        const uint64_t p0 = (uint64_t)tile * 64u;
+        uint32_t b = (uint32_t)((skips - (uint32_t)(p0 % skips)) % skips);
+        uint64_t m = 0;
+        for (; b < 64u; b += skips) m |= 1ull << b;
+        bits &= m;
     }
-    uint32_t total;
-    const uint32_t in_tile = block_scan_t<T>(cnt, &total);
-    const uint32_t excl = lb_exclusive_prefix(lb, tile, total);
-    if (tile == n_tiles - 1 && threadIdx.x == 0) *d_count = excl + total;
-    uint64_t o = (uint64_t)excl + in_tile;
-#pragma unroll
-    for (int q = 0; q < W; q++) {
-        const uint64_t wi = w0 + q;
-        if (wi >= n_words) break;
-        if (word_prefix) {                              // same meaning as the three-kernel form: block_sums[w >> 8] + word_prefix[w]
-            word_prefix[wi] = (uint32_t)o;
-            if ((wi & 255u) == 0) block_sums[wi >> 8] = 0u;
-        }
-        uint64_t mm = m[q];
-        while (mm) {
-            const int b = __ffsll((unsigned long long)mm) - 1;
-            mm &= mm - 1;
-            if (o < out_cap) out_idx[o] = wi * 64 + b;
-            o++;
-        }
-    }
+    if (bits && (P.exc_survive || !rd_is_exc(R, r))) atomicOr(reinterpret_cast<unsigned long long *>(hitmask) + (r >> 6), 1ull << (r & 63u));
 }
 
-// element-wise form: tiles of 4096 elements, 1024 threads x 4 consecutive elements (few, fat tiles keep the look-back
-// to one or two steps).  cnt = flagged elements of this thread; returns the rank of the thread's first flagged element
-// among all flagged elements before it; *upto = flagged elements up to and including this tile.
-static constexpr uint32_t kLbElemsPerTile = 4096;
-static __device__ uint32_t lb_rank4(const Lookback &lb, uint32_t tile, uint32_t cnt, uint32_t *upto)
+hipError_t launch_hint_filter_any(const DevReads &R, const DevParams &P, const uint64_t *hint_off, const uint32_t *blk_read, uint64_t n_words,
+                                  uint64_t *hitmask, uint64_t *hint_bits, hipStream_t st)
 {
-    uint32_t all;
-    const uint32_t in_tile = block_scan_t<1024>(cnt, &all);
-    const uint32_t excl = lb_exclusive_prefix(lb, tile, all);
-    *upto = excl + all;
-    return excl + in_tile;
-}
-
-hipError_t launch_compact(const uint64_t *mask, uint64_t n_words, uint64_t n_bits, uint32_t *word_prefix,
-                          uint32_t *block_sums, uint64_t *out_idx, uint64_t out_cap, uint32_t *d_count, hipStream_t st,
-                          uint32_t *zero_a, uint32_t n_a, uint32_t *zero_b, uint32_t n_b, const Lookback *lb)
-{
-    if (lb && n_words) {
-        // (the caller reserved ceil(n_words / lookback_tile_words(n_words)) tickets)
-        const uint32_t tw = lookback_tile_words(n_words);
-        const uint32_t n_tiles = (uint32_t)((n_words + tw - 1) / tw);
-        if (tw == 256)
-            CRASS_LAUNCH((k_mask_compact_lb<256, 1>), dim3(n_tiles), dim3(256), 0, st, mask, n_words, n_bits, word_prefix, block_sums, out_idx, out_cap,
-                               d_count, zero_a, n_a, zero_b, n_b, *lb, n_tiles);
-        else
-            CRASS_LAUNCH((k_mask_compact_lb<1024, 4>), dim3(n_tiles), dim3(1024), 0, st, mask, n_words, n_bits, word_prefix, block_sums, out_idx, out_cap,
-                               d_count, zero_a, n_a, zero_b, n_b, *lb, n_tiles);
-        return hipGetLastError();
-    }
-    if (n_words == 0) {
-        if (n_a) (void)hipMemsetAsync(zero_a, 0, 4 * (size_t)n_a, st);
-        if (n_b) (void)hipMemsetAsync(zero_b, 0, 4 * (size_t)n_b, st);
-        return hipMemsetAsync(d_count, 0, 4, st);
-    }
-    unsigned nb = (unsigned)((n_words + 255) / 256);
-    CRASS_LAUNCH(k_mask_count, dim3(nb), dim3(256), 0, st, mask, n_words, n_bits, word_prefix, block_sums);
-    CRASS_LAUNCH(k_block_scan, dim3(1), dim3(1024), 0, st, block_sums, nb, d_count, zero_a, n_a, zero_b, n_b);
-    CRASS_LAUNCH(k_mask_scatter, dim3(nb), dim3(256), 0, st, mask, n_words, n_bits, word_prefix, block_sums, out_idx, out_cap);
+    if (P.window < 6 || P.window > 9 || P.skips < 1 || P.lowDR + P.lowSp < 17 || P.highDR + P.highSp > 127 || P.highDR + P.highSp < P.lowDR + P.lowSp) return hipErrorNotSupported;
+    if (!n_words) return hipSuccess;
+    const uint64_t nb = (n_words + 255) / 256;
+    if (nb > 0x7FFFFFFFull) return hipErrorNotSupported;
+    CRASS_LAUNCH(k_hint_filter_any, dim3((unsigned)nb), dim3(256), 0, st, R, P, hint_off, blk_read, n_words, hitmask, hint_bits);
     return hipGetLastError();
 }
 
@@ -2036,7 +1792,7 @@ static __device__ int dr_low_lexi(RH &h, char *dr_out, int dr_stride, int &was_l
     for (int i0 = 0; i0 < (int)dlen; i0 += WAVE) {
         int i = i0 + lane;
         uint8_t a = 0, b = 0;
-        if (i < (int)dlen) { a = dr[i]; b = c_comp[dr[dlen - 1 - i] & 127]; }
+        if (i < (int)dlen) { a = dr[i]; b = c_comp.v[dr[dlen - 1 - i] & 127]; }
         uint64_t m = __ballot(a != b);
         if (m) {
             int f = __ffsll((unsigned long long)m) - 1;
@@ -2049,7 +1805,7 @@ static __device__ int dr_low_lexi(RH &h, char *dr_out, int dr_stride, int &was_l
         for (int i = lane; i < dr_stride; i += WAVE) dr_out[i] = (i < (int)dlen) ? (char)dr[i] : (char)0;   // zero padding: slots are bit-reproducible
         was_low_lexi = 1;
     } else {
-        for (int i = lane; i < dr_stride; i += WAVE) dr_out[i] = (i < (int)dlen) ? (char)c_comp[dr[dlen - 1 - i] & 127] : (char)0;
+        for (int i = lane; i < dr_stride; i += WAVE) dr_out[i] = (i < (int)dlen) ? (char)c_comp.v[dr[dlen - 1 - i] & 127] : (char)0;
         // reverseStartStops: new[k] = L-1 - ss[nss-1-k]
         wave_sync();
         for (int k0 = 0; k0 < h.nss; k0 += WAVE) {       // read everything of a chunk pair-wise before writing
@@ -2567,107 +2323,6 @@ __global__ __launch_bounds__(WAVE) void k_long_light(DevReads R, DevParams P, co
 // when it gets there (lane = hint word: 4 packed words + halo, 11 instructions per word and shift), finds the next set bit at or
 // behind j and takes it if it lies on the lattice that starts at j.  No hint kernel, no hint array.  Everything else is
 // k_long_light.  (1 M x 10 kbp with -d 20 -D 40: 512 ms on the un-hinted wave kernel.)
-static __device__ __forceinline__ uint64_t hint_bits_every(const uint32_t (&w)[13], int wn, int D0, int D1)
-{
-    const int s1 = min(1, wn - 1), s2 = min(2, wn - 1 - s1), s3 = min(4, wn - 1 - s1 - s2), s4 = wn - 1 - s1 - s2 - s3;
-    uint32_t nz[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (16 * q + 15 < D0 || 16 * q > D1) continue;
-        const int sb_lo = max(0, D0 - 16 * q), sb_hi = min(15, D1 - 16 * q);
-        for (int sb = sb_lo; sb <= sb_hi; sb++) {
-            const uint32_t sh = (uint32_t)(2 * sb);
-            uint32_t z[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                const uint32_t x = __builtin_amdgcn_alignbit(w[k + q + 1], w[k + q], sh) ^ w[k];
-                z[k] = x | (x >> 1);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s1));
-            if (s2 > 0) {
-                z[4] |= z[4] >> (2 * s1);
-#pragma unroll
-                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s2));
-            }
-            if (s3 > 0) {
-                z[4] |= z[4] >> (2 * s2);
-#pragma unroll
-                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s3));
-            }
-            if (s4 > 0) {
-                z[4] |= z[4] >> (2 * s3);
-#pragma unroll
-                for (int k = 0; k < 4; k++) z[k] |= __builtin_amdgcn_alignbit(z[k + 1], z[k], (uint32_t)(2 * s4));
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) nz[k] &= z[k];
-        }
-    }
-    // bit 2p of ~nz[k] = a copy exists for position 16 k + p: the even bits of the four words, packed
-    auto even16 = [](uint32_t x) {
-        x &= 0x55555555u;
-        x = (x | (x >> 1)) & 0x33333333u;
-        x = (x | (x >> 2)) & 0x0F0F0F0Fu;
-        x = (x | (x >> 4)) & 0x00FF00FFu;
-        x = (x | (x >> 8)) & 0x0000FFFFu;
-        return x;
-    };
-    const uint32_t lo = even16(~nz[0]) | (even16(~nz[1]) << 16), hi = even16(~nz[2]) | (even16(~nz[3]) << 16);
-    return ((uint64_t)hi << 32) | (uint64_t)lo;
-}
-
-// The seed-scan FILTER of reads of 257 .. 2 048 bases (and of sets whose strides differ) under another window or seed lattice
-// (-w, -d): no position hints are kept for those (the walks' hint forms know the default lattice), so a tile's bits are computed,
-// cut to the lattice positions j = i * skips <= searchEnd, and only the read's bit in the (cleared) filter mask is set.  A superset
-// like every filter here; 11 instructions per word and shift for every position — four times the lattice-class kernel, a fifth of
-// k_filter_general, which these sets took until now.
-__global__ __launch_bounds__(256) void k_hint_filter_any(DevReads R, DevParams P, const uint64_t *hint_off, const uint32_t *blk_read, uint64_t n_words,
-                                                         uint64_t *hitmask, uint64_t *hint_bits)
-{
-    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (t >= n_words) return;
-    uint64_t r;
-    uint32_t tile;
-    hint_tile_read(R, hint_off, blk_read, t, n_words, r, tile);
-    const uint32_t L = rd_len(R, r);
-    const int D0 = (int)(P.lowDR + P.lowSp), D1 = (int)(P.highDR + P.highSp);
-    const int last = (int)L - D0 - (int)P.window - 1 - (int)(tile * 64u);        // searchEnd, counted from this tile's first position
-    if (last < 0) { hint_bits[t] = 0ull; return; }
-    const uint32_t nw = (L + 15) >> 4;
-    const uint32_t *g = R.packed + rd_word_off(R, r) + tile * 4u;
-    const uint32_t rem = nw - tile * 4u;
-    uint32_t w[13];
-#pragma unroll
-    for (int i = 0; i < 13; i++) w[i] = (uint32_t)i < rem ? g[i] : 0u;
-    uint64_t bits = hint_bits_every(w, (int)P.window, D0, D1);
-    if (last < 63) bits &= (2ull << last) - 1ull;
-    // every position's bit is kept: the survivors' walks step over the positions whose bit is clear, on the lattice and — behind a
-    // rejected candidate — off it (DevReads.hint_all)
-    hint_bits[t] = bits;
-    // the lattice: positions that are multiples of skips
-    const uint32_t skips = P.skips;
-    if (skips > 1) {
-        const uint64_t p0 = (uint64_t)tile * 64u;
-        uint32_t b = (uint32_t)((skips - (uint32_t)(p0 % skips)) % skips);
-        uint64_t m = 0;
-        for (; b < 64u; b += skips) m |= 1ull << b;
-        bits &= m;
-    }
-    if (bits && (P.exc_survive || !rd_is_exc(R, r))) atomicOr(reinterpret_cast<unsigned long long *>(hitmask) + (r >> 6), 1ull << (r & 63u));
-}
-
-hipError_t launch_hint_filter_any(const DevReads &R, const DevParams &P, const uint64_t *hint_off, const uint32_t *blk_read, uint64_t n_words,
-                                  uint64_t *hitmask, uint64_t *hint_bits, hipStream_t st)
-{
-    if (P.window < 6 || P.window > 9 || P.skips < 1 || P.lowDR + P.lowSp < 17 || P.highDR + P.highSp > 127 || P.highDR + P.highSp < P.lowDR + P.lowSp) return hipErrorNotSupported;
-    if (!n_words) return hipSuccess;
-    const uint64_t nb = (n_words + 255) / 256;
-    if (nb > 0x7FFFFFFFull) return hipErrorNotSupported;
-    CRASS_LAUNCH(k_hint_filter_any, dim3((unsigned)nb), dim3(256), 0, st, R, P, hint_off, blk_read, n_words, hitmask, hint_bits);
-    return hipGetLastError();
-}
-
 __global__ __launch_bounds__(WAVE) void k_long_light_any(DevReads R, DevParams P, const uint32_t *d_n, uint64_t n_max, SurvOut *out, uint64_t slot_base,
                                                          uint32_t *punt_list, uint32_t *d_punt_n, const uint64_t *surv_idx)
 {
@@ -3706,493 +3361,6 @@ hipError_t launch_survivor_lanes(const DevReads &R, const DevParams &P, const ui
     return hipGetLastError();
 }
 
-// ---- device-side gather of the found records (fast path: short reads, slot-mode pool) ----
-// mask of slots with found != 0; the worst error code is max-reduced into *d_err
-__global__ __launch_bounds__(256) void k_found_mask(const SurvOut *out, const uint32_t *d_n, uint64_t n, uint64_t *mask, uint32_t *d_err,
-                                                     unsigned long long *dd_keys, uint32_t *dd_first, uint32_t dd_size)
-{
-    const uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    // the de-duplication table of the next stage is cleared on the way (saves its own launch)
-    for (uint64_t i = s; i < dd_size; i += (uint64_t)gridDim.x * blockDim.x) { dd_keys[i] = 0ull; dd_first[i] = 0xFFFFFFFFu; }
-    bool f = false;
-    if (s < n && s < (uint64_t)*d_n) {                  // slots past the device-side count were never written
-        const SurvOut o = out[s];
-        f = o.found != 0;
-        if (o.err) atomicMax(d_err, (uint32_t)o.err);
-    }
-    const uint64_t m = __ballot(f);
-    if ((threadIdx.x & 63) == 0 && s < n) mask[s >> 6] = m;
-}
-
-// ---- device-side de-duplication of the candidates' DR strings (single-GPU merge fast path) ----
-// Same 64-bit hash as TokenTable::hash (merge.cpp) so the host can reuse it.  Every distinct
-// string gets one table slot; `first` keeps the smallest candidate index (= first occurrence in
-// read order).  The host re-checks every (candidate, representative) pair with memcmp, so a hash
-// collision between different strings is detected and only costs the fast path.
-static __device__ uint64_t dr_hash64(const char *p, uint32_t n)
-{
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)n * 0xD6E8FEB86659FD93ull);
-    while (n >= 8) {
-        uint64_t v = 0;
-        for (int i = 0; i < 8; i++) v |= (uint64_t)(uint8_t)p[i] << (8 * i);
-        h = (h ^ v) * 0xFF51AFD7ED558CCDull; h ^= h >> 32; p += 8; n -= 8;
-    }
-    if (n) {
-        uint64_t v = 0;
-        for (uint32_t i = 0; i < n; i++) v |= (uint64_t)(uint8_t)p[i] << (8 * i);
-        h = (h ^ v) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 29;
-    }
-    return h ^ (h >> 31);
-}
-
-// found records -> compact hand-off blob + dense DR strings on the device + de-duplication insert
-// (one thread per found record; see launch_gather_found in engine_internal.h)
-// The insert goes through LDS first: most records carry one of a few popular strings, every resident thread meets the table
-// while it is still empty, and returning atomics on one address retire one every 20-30 ns — 5.6 k compare-and-swaps on each
-// popular slot were ~100 of this kernel's 125 us at 100 M reads.  A block of 1 024 records claims its strings in an LDS table
-// (hash, smallest record index), then ONE thread per distinct string of the block goes to the global table.
-#define GF_BLOCK 1024
-#define GF_SLOTS 2048
-__global__ __launch_bounds__(GF_BLOCK) void k_gather_found(const uint64_t *fidx, const uint32_t *d_nf, uint64_t n_max,
-                                                            const SurvOut *out, const uint64_t *surv_idx, uint64_t read_base,
-                                                            const char *dr_chars, uint32_t dr_stride, const uint32_t *ss_pool,
-                                                            uint32_t ss_cap, uint32_t ss_elem, uint8_t *blob, uint16_t *g_dr_len, char *g_dr,
-                                                            unsigned long long *dd_keys, uint32_t *dd_first, uint32_t dd_mask,
-                                                            uint64_t *dd_hash, uint32_t *dd_slot, uint32_t *d_mismatch)
-{
-    __shared__ unsigned long long lkey[GF_SLOTS];
-    __shared__ uint32_t lmin[GF_SLOTS], lslot[GF_SLOTS];
-    const uint64_t k = blockIdx.x * (uint64_t)GF_BLOCK + threadIdx.x;
-    uint64_t n = *d_nf;
-    if (n > n_max) n = n_max;
-    if (blockIdx.x * (uint64_t)GF_BLOCK >= n) return;    // (the launch is sized for the survivor bound)
-    if (dd_keys) {
-        for (uint32_t i = threadIdx.x; i < GF_SLOTS; i += GF_BLOCK) { lkey[i] = 0ull; lmin[i] = 0xFFFFFFFFu; }
-        __syncthreads();
-    }
-    uint32_t ls = 0;
-    if (k < n) {
-        const P1Blob b = p1_blob_layout(n, ss_cap, ss_elem);
-        const uint64_t s = fidx[k];
-        const SurvOut o = out[s];
-        reinterpret_cast<uint64_t *>(blob + b.read)[k] = read_base + surv_idx[s];
-        reinterpret_cast<uint16_t *>(blob + b.replen)[k] = (uint16_t)o.repeat_len;
-        (blob + b.nss)[k] = (uint8_t)o.n_ss;
-        (blob + b.low)[k] = o.low_lexi;
-        const uint32_t *ps = ss_pool + o.ss_off;
-        if (ss_elem == 1 && (o.ss_off & 3u) == 0u) {         // ss_cap is a multiple of 4: whole words, and 16-byte loads (slot-mode pool)
-            uint32_t *pd = reinterpret_cast<uint32_t *>(blob + b.ss + k * (uint64_t)ss_cap);
-            const uint4 *p4 = reinterpret_cast<const uint4 *>(ps);
-            for (uint32_t i = 0; i < ss_cap; i += 4) {
-                const uint4 x = p4[i >> 2];
-                const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-                uint32_t v = 0;
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) v |= ((i + q < o.n_ss) ? (xs[q] & 0xFFu) : 0u) << (8 * q);
-                pd[i >> 2] = v;
-            }
-        } else if (ss_elem == 1) {
-            uint32_t *pd = reinterpret_cast<uint32_t *>(blob + b.ss + k * (uint64_t)ss_cap);
-            for (uint32_t i = 0; i < ss_cap; i += 4) {
-                uint32_t v = 0;
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) v |= ((i + q < o.n_ss) ? (ps[i + q] & 0xFFu) : 0u) << (8 * q);
-                pd[i >> 2] = v;
-            }
-        } else {
-            uint32_t *pd = reinterpret_cast<uint32_t *>(blob + b.ss + k * (uint64_t)ss_cap * 2);
-            for (uint32_t i = 0; i < ss_cap; i += 2) {
-                const uint32_t lo = (i < o.n_ss) ? (ps[i] & 0xFFFFu) : 0u, hi = (i + 1 < o.n_ss) ? (ps[i + 1] & 0xFFFFu) : 0u;
-                pd[i >> 1] = lo | (hi << 16);
-            }
-        }
-        g_dr_len[k] = o.dr_len;
-        // the string is copied 16 bytes at a time and hashed from the same registers (dr_hash64 over a zero-padded slot: a
-        // partial last word IS the value its byte loop assembles; 36 byte loads per record were a third of this kernel)
-        const uint4 *src = reinterpret_cast<const uint4 *>(dr_chars + s * (uint64_t)dr_stride);
-        uint4 *dst = reinterpret_cast<uint4 *>(g_dr + k * (uint64_t)dr_stride);
-        uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)o.dr_len * 0xD6E8FEB86659FD93ull);
-        uint32_t rem = o.dr_len;
-        for (uint32_t i = 0; i < dr_stride / 16; i++) {
-            const uint4 v4 = src[i];
-            dst[i] = v4;
-            const uint64_t w2[2] = {(uint64_t)v4.x | ((uint64_t)v4.y << 32), (uint64_t)v4.z | ((uint64_t)v4.w << 32)};
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (rem >= 8) { h = (h ^ w2[q]) * 0xFF51AFD7ED558CCDull; h ^= h >> 32; rem -= 8; }
-                else if (rem) { h = (h ^ w2[q]) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 29; rem = 0; }
-            }
-        }
-        h ^= h >> 31;
-        if (dd_keys) {
-            // (the same 64-bit hash as TokenTable::hash, merge.cpp); 0 marks an empty slot
-            dd_hash[k] = h;
-            const unsigned long long key = h | 1ull;
-            ls = (uint32_t)(h >> 40) & (GF_SLOTS - 1u);
-            for (;;) {                                       // (at most 1 024 distinct keys in 2 048 slots: always ends)
-                const unsigned long long old = atomicCAS(&lkey[ls], 0ull, key);
-                if (old == 0ull || old == key) break;
-                ls = (ls + 1u) & (GF_SLOTS - 1u);
-            }
-            atomicMin(&lmin[ls], (uint32_t)k);
-        }
-    }
-    if (!dd_keys) return;
-    __syncthreads();
-    // The global table was cleared by the found-flag compaction.  It is sized for the DISTINCT strings the caller expects
-    // (a learnt bound), not for the records: a probe sequence that outlasts kDdMaxProbes means the bound was too small.
-    // Bit 2 of the mismatch word tells the host (which then de-duplicates itself and sizes the next call's table for the
-    // records); the string keeps the occupied slot it stopped at, so that everything downstream stays in range.
-    // Looking at a slot before the CAS / atomicMin pays at 100 M reads but costs two more round trips at 10 M: done for
-    // launches sized for more than 2^20 records (the headline workload).
-    const bool look = n_max > (1ull << 20);
-    for (uint32_t i = threadIdx.x; i < GF_SLOTS; i += GF_BLOCK) {
-        const unsigned long long key = lkey[i];
-        if (key == 0ull) continue;
-        uint32_t slot = (uint32_t)(key >> 17) & dd_mask;
-        for (uint32_t probes = 0;; probes++) {
-            unsigned long long old = look ? __hip_atomic_load(&dd_keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-            if (old == 0ull) old = atomicCAS(&dd_keys[slot], 0ull, key);
-            if (old == 0ull || old == key) break;
-            if (probes >= kDdMaxProbes) { atomicOr(d_mismatch, 2u); break; }
-            slot = (slot + 1) & dd_mask;
-        }
-        const uint32_t kmin = lmin[i];
-        if (!look || __hip_atomic_load(&dd_first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > kmin) atomicMin(&dd_first[slot], kmin);
-        lslot[i] = slot;
-    }
-    __syncthreads();
-    if (k < n) dd_slot[k] = lslot[ls];
-}
-
-// k_found_mask + compaction in one pass (decoupled look-back): survivor slot s -> rank among the found records ->
-// fidx[rank] = s.  Also clears the de-duplication table of the next stage.  (The gather itself stays a dense kernel:
-// with one found record in six slots a fused body would run at a sixth of the lanes.)  Tiles of 16 384 slots (16 per
-// thread); the launch is sized for the survivor BOUND, tiles past the device-side count leave at once.
-static constexpr uint32_t kFcPerThread = 16, kFcTile = 1024u * kFcPerThread;
-// Wave w of the block takes slots [w * 1024, (w + 1) * 1024) of the tile, 64 consecutive slots per step (one per lane: the
-// loads of a step cover one contiguous 1 280-byte run); a step's found flags are one ballot.
-__global__ __launch_bounds__(1024) void k_found_compact(const SurvOut *out, const uint32_t *d_n, uint64_t n_max, uint32_t *d_err,
-                                                         unsigned long long *dd_keys, uint32_t *dd_first, uint32_t dd_size,
-                                                         uint64_t *fidx, uint32_t *d_nf, Lookback lb)
-{
-    uint64_t n = *d_n;                                   // slots past the device-side count were never written
-    if (n > n_max) n = n_max;
-    const uint32_t n_act = n ? (uint32_t)((n + kFcTile - 1) / kFcTile) : 1u;
-    if (blockIdx.x >= n_act) return;
-    const uint32_t tile = lb_tile_id(lb, n_act);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t s0 = (uint64_t)tile * kFcTile + (uint64_t)wv * 1024u;
-    for (uint64_t i = (uint64_t)tile * 1024u + threadIdx.x; i < dd_size; i += (uint64_t)n_act * 1024u) { dd_keys[i] = 0ull; dd_first[i] = 0xFFFFFFFFu; }
-    uint32_t err = 0, cnt = 0;
-    uint64_t fm[kFcPerThread];
-#pragma unroll
-    for (uint32_t e = 0; e < kFcPerThread; e++) {
-        const uint64_t sl = s0 + e * 64u + (uint32_t)lane;
-        bool f = false;
-        if (sl < n) { f = out[sl].found != 0; err = max(err, (uint32_t)out[sl].err); }
-        fm[e] = __ballot(f);
-        cnt += (uint32_t)__popcll(fm[e]);                // (wave-uniform)
-    }
-    if (err) atomicMax(d_err, err);
-    // ranks: the wave's base from a scan over the 16 wave totals, then step by step
-    __shared__ uint32_t wtot[16];
-    if (lane == 0) wtot[wv] = cnt;
-    __syncthreads();
-    uint32_t wbase = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) { const uint32_t t = wtot[q]; if (q < wv) wbase += t; all += t; }
-    const uint32_t excl = lb_exclusive_prefix(lb, tile, all);
-    if (tile == n_act - 1 && threadIdx.x == 0) *d_nf = excl + all;
-    uint64_t k = (uint64_t)excl + wbase;
-    const uint64_t lt = (1ull << lane) - 1ull;
-#pragma unroll
-    for (uint32_t e = 0; e < kFcPerThread; e++) {
-        if ((fm[e] >> lane) & 1ull) fidx[k + (uint32_t)__popcll(fm[e] & lt)] = s0 + e * 64u + (uint32_t)lane;
-        k += (uint32_t)__popcll(fm[e]);
-    }
-}
-hipError_t launch_found_compact(const SurvOut *out, const uint32_t *d_n, uint64_t n_max, uint32_t *d_err, unsigned long long *dd_keys,
-                                uint32_t *dd_first, uint32_t dd_size, uint64_t *fidx, uint32_t *d_nf, const Lookback &lb, hipStream_t st)
-{
-    if (n_max == 0) return hipSuccess;
-    const uint32_t n_tiles = (uint32_t)((n_max + kFcTile - 1) / kFcTile);
-    CRASS_LAUNCH(k_found_compact, dim3(n_tiles), dim3(1024), 0, st, out, d_n, n_max, d_err, dd_keys, dd_first, dd_keys ? dd_size : 0u,
-                       fidx, d_nf, lb);
-    return hipGetLastError();
-}
-
-// ---- host-loop sink: select + gather of the found records (engine_internal.h) ----
-__global__ __launch_bounds__(256) void k_select_found(const SurvOut *out, uint64_t n, uint64_t *mask, uint32_t *d_err)
-{
-    const uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    bool f = false;
-    if (s < n) {
-        const SurvOut o = out[s];
-        f = o.found != 0 && o.err == 0;
-        if (o.err && o.err != 5) atomicMax(d_err, o.err == 1 ? 2u : 1u);
-    }
-    const uint64_t m = __ballot(f);
-    if ((threadIdx.x & 63) == 0 && s < n) mask[s >> 6] = m;
-}
-__global__ __launch_bounds__(256) void k_gather_sparse(const uint64_t *fidx, const uint32_t *d_nf, uint64_t n_max, const SurvOut *out, const char *dr_chars,
-                                                        uint32_t dr_stride, const uint32_t *ss_pool, SurvOut *g_out, uint64_t *g_slot, char *g_dr,
-                                                        uint32_t *g_ss, uint32_t g_ss_cap, uint32_t *d_ss_total, uint16_t *g_dr_len, int ss16)
-{
-    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t n = *d_nf;
-    if (n > n_max) n = n_max;
-    SurvOut o; o.found = 0; o.n_ss = 0; o.repeat_len = 0; o.ss_off = 0; o.dr_len = 0; o.low_lexi = 0; o.err = 0;
-    uint64_t s = 0;
-    if (k < n) { s = fidx[k]; o = out[s]; }
-    const uint32_t off = block_reserve<256>(k < n ? o.n_ss : 0u, d_ss_total);      // (every thread of the block)
-    if (k >= n) return;
-    // (ss16: every position of the set fits 16 bits — the packed pool then travels in half the bytes: 50 k records with 80
-    // start/stops each are 16 MB of a long-read step's 20 MB of copies)
-    if ((uint64_t)off + o.n_ss <= g_ss_cap) {
-        if (ss16) { uint16_t *g16 = reinterpret_cast<uint16_t *>(g_ss); for (uint32_t i = 0; i < o.n_ss; i++) g16[off + i] = (uint16_t)ss_pool[o.ss_off + i]; }
-        else for (uint32_t i = 0; i < o.n_ss; i++) g_ss[off + i] = ss_pool[o.ss_off + i];
-    }
-    o.ss_off = off;
-    g_out[k] = o;
-    g_slot[k] = s;
-    if (g_dr_len) g_dr_len[k] = o.dr_len;               // (dense lengths: the de-duplication that may follow on the device)
-    const char *src = dr_chars + s * (uint64_t)dr_stride;
-    char *dst = g_dr + k * (uint64_t)dr_stride;
-    for (uint32_t i = 0; i < dr_stride; i++) dst[i] = src[i];
-}
-hipError_t launch_select_found(const SurvOut *out, uint64_t n, uint64_t *mask, uint32_t *d_err, hipStream_t st)
-{
-    if (n == 0) return hipSuccess;
-    CRASS_LAUNCH(k_select_found, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, n, mask, d_err);
-    return hipGetLastError();
-}
-hipError_t launch_gather_sparse(const uint64_t *fidx, const uint32_t *d_nf, uint64_t n_max, const SurvOut *out, const char *dr_chars, uint32_t dr_stride,
-                                const uint32_t *ss_pool, SurvOut *g_out, uint64_t *g_slot, char *g_dr, uint32_t *g_ss, uint32_t g_ss_cap,
-                                uint32_t *d_ss_total, hipStream_t st, uint16_t *g_dr_len, int ss16)
-{
-    if (n_max == 0) return hipSuccess;
-    CRASS_LAUNCH(k_gather_sparse, dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, st, fidx, d_nf, n_max, out, dr_chars, dr_stride, ss_pool,
-                       g_out, g_slot, g_dr, g_ss, g_ss_cap, d_ss_total, g_dr_len, ss16);
-    return hipGetLastError();
-}
-
-hipError_t launch_found_mask(const SurvOut *out, const uint32_t *d_n, uint64_t n, uint64_t *mask, uint32_t *d_err, hipStream_t st,
-                             unsigned long long *dd_keys, uint32_t *dd_first, uint32_t dd_size)
-{
-    if (n == 0) return hipSuccess;
-    CRASS_LAUNCH(k_found_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, d_n, n, mask, d_err, dd_keys, dd_first, dd_keys ? dd_size : 0u);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather_found(const uint64_t *fidx, const uint32_t *d_nf, uint64_t n_max, const SurvOut *out,
-                               const uint64_t *surv_idx, uint64_t read_base, const char *dr_chars, uint32_t dr_stride,
-                               const uint32_t *ss_pool, uint32_t ss_cap, uint32_t ss_elem, uint8_t *h_blob,
-                               uint16_t *g_dr_len, char *g_dr, hipStream_t st,
-                               unsigned long long *dd_keys, uint32_t *dd_first, uint32_t dd_size, uint64_t *dd_hash, uint32_t *dd_slot,
-                               uint32_t *d_mismatch)
-{
-    if (n_max == 0) return hipSuccess;
-    if ((ss_cap & 3u) || (ss_elem != 1 && ss_elem != 2)) return hipErrorInvalidValue;
-    CRASS_LAUNCH(k_gather_found, dim3((unsigned)((n_max + GF_BLOCK - 1) / GF_BLOCK)), dim3(GF_BLOCK), 0, st, fidx, d_nf, n_max, out, surv_idx,
-                       read_base, dr_chars, dr_stride, ss_pool, ss_cap, ss_elem, h_blob, g_dr_len, g_dr,
-                       dd_keys, dd_first, dd_keys ? dd_size - 1 : 0u, dd_hash, dd_slot, d_mismatch);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void k_dr_dedupe_clear(unsigned long long *keys, uint32_t *first, uint32_t table_size)
-{
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < table_size; i += gridDim.x * blockDim.x) { keys[i] = 0ull; first[i] = 0xFFFFFFFFu; }
-}
-
-__global__ __launch_bounds__(256) void k_dr_dedupe_insert(const char *dr, const uint16_t *dr_len, uint32_t stride, const uint32_t *d_n,
-                                                           uint32_t n_max, unsigned long long *keys, uint32_t *first, uint32_t mask,
-                                                           uint64_t *hash_out, uint32_t *slot_out)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = min(*d_n, n_max);
-    if (k >= n) return;
-    const uint64_t h = dr_hash64(dr + (uint64_t)k * stride, dr_len[k]);
-    hash_out[k] = h;
-    const unsigned long long key = h | 1ull;                 // 0 marks an empty slot
-    uint32_t slot = (uint32_t)(h >> 17) & mask;
-    for (;;) {
-        const unsigned long long old = atomicCAS(&keys[slot], 0ull, key);
-        if (old == 0ull || old == key) break;
-        slot = (slot + 1) & mask;
-    }
-    atomicMin(&first[slot], k);
-    slot_out[k] = slot;
-}
-
-// the candidate count lives on the device (*d_n, at most n_max): no host round trip before this launch
-hipError_t launch_dr_dedupe(const char *dr, const uint16_t *dr_len, uint32_t stride, const uint32_t *d_n, uint32_t n, unsigned long long *keys,
-                            uint32_t *first, uint32_t table_size, uint64_t *hash_out, uint32_t *slot_tmp, uint32_t *rep, hipStream_t st,
-                            bool table_cleared)
-{
-    if (n == 0) return hipSuccess;
-    if (!table_cleared) CRASS_LAUNCH(k_dr_dedupe_clear, dim3((unsigned)std::min<uint32_t>((table_size + 255) / 256, 2048u)), dim3(256), 0, st, keys, first, table_size);
-    const unsigned nb = (n + 255) / 256;
-    CRASS_LAUNCH(k_dr_dedupe_insert, dim3(nb), dim3(256), 0, st, dr, dr_len, stride, d_n, n, keys, first, table_size - 1, hash_out, slot_tmp);
-    (void)rep;                                  // rep[] = first occurrence of every candidate: written by k_dx_flag
-    return hipGetLastError();
-}
-
-// ---- device-side token ranks: distinct strings in first-occurrence order ----
-// bit k of `mask` = candidate k is the first occurrence of its string; every other candidate is compared
-// byte for byte with its representative, so a 64-bit hash collision between different strings is
-// DETECTED (flag) and the host then takes its plain path.
-__global__ __launch_bounds__(256) void k_dx_flag(const char *dr, const uint16_t *dr_len, uint32_t stride, const uint32_t *d_n, uint32_t n_max,
-                                                  const uint32_t *slot_of, const uint32_t *first, uint32_t *rep, uint64_t *mask, uint32_t *d_mismatch)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = min(*d_n, n_max);
-    bool is_rep = false;
-    if (k < n) {
-        const uint32_t f = first[slot_of[k]];               // (was k_dr_dedupe_rep: one launch less)
-        rep[k] = f;
-        is_rep = (f == k);
-        if (!is_rep) {
-            bool same = f < k && dr_len[f] == dr_len[k];
-            if (same) {
-                const uint4 *a = reinterpret_cast<const uint4 *>(dr + (uint64_t)k * stride);
-                const uint4 *b = reinterpret_cast<const uint4 *>(dr + (uint64_t)f * stride);
-                for (uint32_t i = 0; i < stride / 16; i++) {          // slots are zero padded: whole-slot compare
-                    const uint4 x = a[i], y = b[i];
-                    same = same && x.x == y.x && x.y == y.y && x.z == y.z && x.w == y.w;
-                }
-            }
-            if (!same) atomicOr(d_mismatch, 1u);
-        }
-    }
-    const uint64_t m = __ballot(is_rep);
-    if ((threadIdx.x & 63) == 0 && k < n_max) mask[k >> 6] = m;       // words past the count are zero
-}
-
-// dmap[k] = rank of k's representative among the first occurrences (token = rank + 2 on one GPU)
-__global__ __launch_bounds__(256) void k_dx_assign(const uint32_t *rep, const uint32_t *d_n, uint32_t n_max, const uint64_t *mask,
-                                                    const uint32_t *word_prefix, const uint32_t *block_sums, uint32_t *dmap)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= min(*d_n, n_max)) return;
-    const uint32_t f = rep[k], w = f >> 6;
-    dmap[k] = block_sums[w >> 8] + word_prefix[w] + (uint32_t)__popcll(mask[w] & ((1ull << (f & 63)) - 1ull));
-}
-
-__global__ __launch_bounds__(256) void k_dx_gather(const uint64_t *dx_idx, const uint32_t *d_nd, uint32_t n_max, const char *dr,
-                                                    const uint16_t *dr_len, const uint64_t *hash, uint32_t stride, char *out_chars,
-                                                    uint16_t *out_len, uint64_t *out_hash, char *dev_chars, uint16_t *dev_len,
-                                                    const uint32_t *cnt_src, uint32_t *cnt_dst, uint32_t n_cnt)
-{
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_cnt) cnt_dst[j] = cnt_src[j];             // the stage's counters, straight into pinned host memory
-    uint32_t nd = *d_nd;
-    if (nd > n_max) nd = n_max;
-    if (j >= nd) return;
-    const uint64_t k = dx_idx[j];
-    const uint4 *src = reinterpret_cast<const uint4 *>(dr + k * stride);
-    uint4 *dst = reinterpret_cast<uint4 *>(out_chars + (uint64_t)j * stride);
-    uint4 *dst2 = reinterpret_cast<uint4 *>(dev_chars + (uint64_t)j * stride);      // device copy for the device merge
-    // (out_*: pinned host memory, or nullptr when nobody on the host reads the list — the device merge exports its own view)
-    for (uint32_t i = 0; i < stride / 16; i++) { const uint4 v = src[i]; if (out_chars) dst[i] = v; if (dev_chars) dst2[i] = v; }
-    const uint16_t l = dr_len[k];
-    if (out_len) out_len[j] = l;
-    if (dev_len) dev_len[j] = l;
-    if (out_hash) out_hash[j] = hash[k];
-}
-
-// k_dx_flag + compaction in one pass (decoupled look-back over tiles of 1024 candidates, one per thread: the body is a
-// chain of dependent loads, so it wants many blocks rather than fat ones): candidate k is a first occurrence iff
-// first[slot_of[k]] == k; dx_idx[rank] = k, and the representative's rank is left in slot_of[k] (every thread only
-// ever reads its OWN slot_of entry here, so overwriting it is safe) for the assign kernel that follows.
-__global__ __launch_bounds__(1024) void k_dx_flag_compact(const char *dr, const uint16_t *dr_len, uint32_t stride, const uint32_t *d_n, uint32_t n_max,
-                                                           uint32_t *slot_of, const uint32_t *first, uint32_t *rep, uint64_t *dx_idx, uint32_t *d_nd,
-                                                           uint32_t *d_mismatch, Lookback lb)
-{
-    const uint32_t n = min(*d_n, n_max);
-    const uint32_t n_tiles = n ? (n + 1023u) / 1024u : 1u;          // (the launch is sized for a bound: the tiles past the count leave at once)
-    if (blockIdx.x >= n_tiles) return;
-    const uint32_t tile = lb_tile_id(lb, n_tiles);
-    const uint32_t k = tile * 1024u + threadIdx.x;
-    bool is_rep = false;
-    if (k < n) {
-        const uint32_t f = first[slot_of[k]];
-        rep[k] = f;
-        is_rep = (f == k);
-        if (!is_rep) {
-            bool same = f < k && dr_len[f] == dr_len[k];
-            if (same) {
-                const uint4 *a = reinterpret_cast<const uint4 *>(dr + (uint64_t)k * stride);
-                const uint4 *b = reinterpret_cast<const uint4 *>(dr + (uint64_t)f * stride);
-                for (uint32_t i = 0; i < stride / 16; i++) {          // slots are zero padded: whole-slot compare
-                    const uint4 x = a[i], y = b[i];
-                    same = same && x.x == y.x && x.y == y.y && x.z == y.z && x.w == y.w;
-                }
-            }
-            if (!same) atomicOr(d_mismatch, 1u);
-        }
-    }
-    uint32_t all;
-    const uint32_t in_tile = block_scan_t<1024>(is_rep ? 1u : 0u, &all);
-    const uint32_t excl = lb_exclusive_prefix(lb, tile, all);
-    if (tile == n_tiles - 1 && threadIdx.x == 0) *d_nd = excl + all;
-    if (is_rep) { const uint32_t q = excl + in_tile; dx_idx[q] = k; slot_of[k] = q; }
-}
-
-// dense: every candidate's rank (dmap = rank of its representative) and, for the first nd threads, the distinct string's slot
-__global__ __launch_bounds__(256) void k_dx_assign_gather(const uint32_t *rep, const uint32_t *d_n, uint32_t n_max, const uint32_t *rank_of,
-                                                           uint32_t *dmap, const uint64_t *dx_idx, const uint32_t *d_nd, const char *dr,
-                                                           const uint16_t *dr_len, const uint64_t *hash, uint32_t stride, char *out_chars,
-                                                           uint16_t *out_len, uint64_t *out_hash, char *dev_chars, uint16_t *dev_len,
-                                                           const uint32_t *cnt_src, uint32_t *cnt_dst, uint32_t n_cnt)
-{
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_cnt) cnt_dst[j] = cnt_src[j];             // the stage's counters, straight into pinned host memory
-    if (j < min(*d_n, n_max)) dmap[j] = rank_of[rep[j]];
-    uint32_t nd = *d_nd;
-    if (nd > n_max) nd = n_max;
-    if (j >= nd) return;
-    const uint64_t k = dx_idx[j];
-    const uint4 *src = reinterpret_cast<const uint4 *>(dr + k * stride);
-    uint4 *dst = reinterpret_cast<uint4 *>(out_chars + (uint64_t)j * stride);
-    uint4 *dst2 = reinterpret_cast<uint4 *>(dev_chars + (uint64_t)j * stride);      // device copy for the device merge
-    // (out_*: pinned host memory, or nullptr when nobody on the host reads the list — the device merge exports its own view)
-    for (uint32_t i = 0; i < stride / 16; i++) { const uint4 v = src[i]; if (out_chars) dst[i] = v; if (dev_chars) dst2[i] = v; }
-    const uint16_t l = dr_len[k];
-    if (out_len) out_len[j] = l;
-    if (dev_len) dev_len[j] = l;
-    if (out_hash) out_hash[j] = hash[k];
-}
-
-// needs stride % 16 == 0; mask / word_prefix / block_sums / dx_idx are scratch of >= n bits / words.  The candidate
-// count is *d_n (<= n).  dmap / out_* may be pinned host memory: the kernels then write the merge's inputs
-// straight into it (a few hundred KB; no copy calls on the critical path).
-hipError_t launch_dx_tokens(const char *dr, const uint16_t *dr_len, const uint64_t *hash, uint32_t stride, const uint32_t *d_n, uint32_t n, uint32_t *rep,
-                            uint32_t *slot_of, const uint32_t *first,
-                            uint64_t *mask, uint32_t *word_prefix, uint32_t *block_sums, uint64_t *dx_idx, uint32_t *d_nd,
-                            uint32_t *d_mismatch, uint32_t *dmap, char *out_chars, uint16_t *out_len, uint64_t *out_hash,
-                            char *dev_chars, uint16_t *dev_len, hipStream_t st, const uint32_t *cnt_src, uint32_t *cnt_dst, uint32_t n_cnt,
-                            const Lookback *lb)
-{
-    if (n == 0) return hipSuccess;
-    const unsigned nb = (n + 255) / 256;
-    if (lb) {           // two launches: flags + single-pass compaction (element-wise look-back), dense assign + gather
-        const uint32_t n_tiles = (n + 1023u) / 1024u;                               // (the caller reserved that many tickets)
-        CRASS_LAUNCH(k_dx_flag_compact, dim3(n_tiles), dim3(1024), 0, st, dr, dr_len, stride, d_n, n, slot_of, first, rep, dx_idx, d_nd, d_mismatch,
-                           *lb);
-        CRASS_LAUNCH(k_dx_assign_gather, dim3(nb), dim3(256), 0, st, rep, d_n, n, (const uint32_t *)slot_of, dmap, dx_idx, d_nd, dr, dr_len,
-                           hash, stride, out_chars, out_len, out_hash, dev_chars, dev_len, cnt_src, cnt_dst, cnt_dst ? n_cnt : 0u);
-        return hipGetLastError();
-    }
-    CRASS_LAUNCH(k_dx_flag, dim3(nb), dim3(256), 0, st, dr, dr_len, stride, d_n, n, slot_of, first, rep, mask, d_mismatch);
-    hipError_t e = launch_compact(mask, (n + 63) / 64, n, word_prefix, block_sums, dx_idx, n, d_nd, st);
-    if (e != hipSuccess) return e;
-    CRASS_LAUNCH(k_dx_assign, dim3(nb), dim3(256), 0, st, rep, d_n, n, mask, word_prefix, block_sums, dmap);
-    CRASS_LAUNCH(k_dx_gather, dim3(nb), dim3(256), 0, st, dx_idx, d_nd, n, dr, dr_len, hash, stride, out_chars, out_len, out_hash, dev_chars, dev_len,
-                       cnt_src, cnt_dst, cnt_dst ? n_cnt : 0u);
-    return hipGetLastError();
-}
-
 SurvLds survivor_lds_layout(uint32_t max_len, const DevParams &P, uint32_t row_len_cap, uint32_t seq_window_bytes, uint32_t ss_entries_cap)
 {
     SurvLds l;
@@ -4236,806 +3404,6 @@ hipError_t launch_survivor(const DevReads &R, const DevParams &P, bool exception
         CRASS_LAUNCH(k_survivor<false>, dim3(grid), dim3(WAVE), lds_bytes, st, R, P, surv_idx, d_n_surv, n_surv_max,
                            out, dr_chars, dr_stride, ss_pool, ss_pool_cap, d_ss_used, found_flag, seed_hint, lds, punt_only, slot_base, slot_total, punt_list, d_punt_n, redo_list);
     }
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// pass 2: first-match multi-pattern scan (findSingletons/on_match semantics: the first ACISM
-// callback = occurrence with the smallest end position, ties -> longest pattern;
-// libcrispr.cpp:441, acism.c:73-102).  Lane per read, 64 consecutive reads per wave so the
-// ballot is the mask word.  hit_info[r] = (end_exclusive << 8) | pattern_length.
-// ------------------------------------------------------------------------------------
-template <bool LDS_TABLE, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_recruit(DevReads R, DevAutomaton A, const uint8_t *found_flag,
-                                                 uint64_t *hitmask, uint32_t *hit_info)
-{
-    extern __shared__ __attribute__((aligned(16))) uint16_t rc_lds[];
-    const uint16_t *go4 = A.go4;
-    const uint16_t *outl = A.out_len;
-    if (LDS_TABLE) {
-        // stage [n_states][4] transitions + out_len in LDS
-        uint16_t *l_go = rc_lds;
-        uint16_t *l_out = rc_lds + (size_t)A.n_states * 4;
-        for (uint32_t i = threadIdx.x; i < A.n_states * 4; i += blockDim.x) l_go[i] = A.go4[i];
-        for (uint32_t i = threadIdx.x; i < A.n_states; i += blockDim.x) l_out[i] = A.out_len[i];
-        __syncthreads();
-        go4 = l_go; outl = l_out;
-    }
-    const uint64_t n_tiles = (R.n_reads + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave_global = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t wave_total = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
-        const uint64_t r = tile * 64 + lane;
-        bool hit = false;
-        if (r < R.n_reads && !rd_is_exc(R, r) && !found_flag[rd_header_id(R, r)]) {
-            const uint32_t L = rd_len(R, r);
-            const uint32_t *g = R.packed + rd_word_off(R, r);
-            uint32_t state = 0;
-            uint32_t word = 0;
-            for (uint32_t i = 0; i < L; i++) {
-                if ((i & 15u) == 0) word = g[i >> 4];
-                uint32_t c = word & 3u;
-                word >>= 2;
-                state = go4[state * 4 + c];
-                uint32_t ol = outl[state];
-                if (ol) { hit_info[r] = ((i + 1) << 8) | ol; hit = true; break; }
-            }
-        }
-        uint64_t m = __ballot(hit);
-        if (lane == 0) hitmask[tile] = m;
-    }
-}
-
-// generic transition tables (any symbol count / state count), global memory
-__global__ __launch_bounds__(256) void k_recruit_wide(DevReads R, DevAutomaton A, const uint8_t *found_flag,
-                                                       uint64_t *hitmask, uint32_t *hit_info)
-{
-    const uint64_t n_tiles = (R.n_reads + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave_global = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t wave_total = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const uint32_t symA = A.sym['A'], symC = A.sym['C'], symG = A.sym['G'], symT = A.sym['T'];
-    for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
-        const uint64_t r = tile * 64 + lane;
-        bool hit = false;
-        if (r < R.n_reads && !rd_is_exc(R, r) && !found_flag[rd_header_id(R, r)]) {
-            const uint32_t L = rd_len(R, r);
-            const uint32_t *g = R.packed + rd_word_off(R, r);
-            uint32_t state = 0, word = 0;
-            for (uint32_t i = 0; i < L; i++) {
-                if ((i & 15u) == 0) word = g[i >> 4];
-                uint32_t c = word & 3u;
-                word >>= 2;
-                uint32_t sy = c == 0 ? symA : c == 1 ? symC : c == 2 ? symG : symT;
-                state = A.go16 ? (uint32_t)A.go16[(size_t)state * A.n_sym1 + sy] : A.go32[(size_t)state * A.n_sym1 + sy];
-                uint32_t ol = A.out_len[state];
-                if (ol) { hit_info[r] = ((i + 1) << 8) | ol; hit = true; break; }
-            }
-        }
-        uint64_t m = __ballot(hit);
-        if (lane == 0) hitmask[tile] = m;
-    }
-}
-
-hipError_t launch_recruit_general(const DevReads &R, const DevAutomaton &A, const uint8_t *found_flag,
-                                  uint64_t *hitmask, uint32_t *hit_info, hipStream_t st)
-{
-    if (R.n_reads == 0) return hipSuccess;
-    uint64_t n_tiles = (R.n_reads + 63) / 64;
-    uint64_t blocks = (n_tiles + 3) / 4;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (A.acgt_ok && A.go4)
-        CRASS_LAUNCH((k_recruit<false, 256>), dim3((unsigned)blocks), dim3(256), 0, st, R, A, found_flag, hitmask, hit_info);
-    else
-        CRASS_LAUNCH(k_recruit_wide, dim3((unsigned)blocks), dim3(256), 0, st, R, A, found_flag, hitmask, hit_info);
-    return hipGetLastError();
-}
-
-hipError_t launch_recruit_lds(const DevReads &R, const DevAutomaton &A, const uint8_t *found_flag,
-                              uint64_t *hitmask, uint32_t *hit_info, hipStream_t st)
-{
-    if (R.n_reads == 0) return hipSuccess;
-    if (!A.acgt_ok || !A.go4) return hipErrorNotSupported;
-    size_t lds = (size_t)A.n_states * 10;       // 4 x u16 transitions + u16 out_len
-    if (lds > 160 * 1024) return hipErrorNotSupported;
-    uint64_t n_tiles = (R.n_reads + 63) / 64;
-    // one workgroup per CU-slot; the LDS footprint decides how many fit, so size the block to fill the CU
-    const int threads = lds > 80 * 1024 ? 1024 : (lds > 40 * 1024 ? 512 : 256);
-    uint64_t waves_per_block = threads / 64;
-    uint64_t blocks = (n_tiles + waves_per_block - 1) / waves_per_block;
-    uint64_t cap = lds > 80 * 1024 ? 256 : (lds > 40 * 1024 ? 512 : (lds > 20 * 1024 ? 1024 : 2048));
-    if (blocks > cap) blocks = cap;
-    hipError_t e;
-#define RC_LAUNCH(T)                                                                                                   \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_recruit<true, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) return e;                                                                                     \
-    CRASS_LAUNCH((k_recruit<true, T>), dim3((unsigned)blocks), dim3(T), lds, st, R, A, found_flag, hitmask, hit_info);
-    if (threads == 1024) { RC_LAUNCH(1024) }
-    else if (threads == 512) { RC_LAUNCH(512) }
-    else { RC_LAUNCH(256) }
-#undef RC_LAUNCH
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// pass 2 fast path: anchor filter + exact verification of the flagged reads.
-//
-// Every pattern has length >= 23.  If pattern P occurs at offset o of a read, let a be the
-// smallest multiple of 8 with a >= o (a <= o+7): bases [a, a+16) lie inside the occurrence
-// (a+16 <= o+23 <= o+|P|) and equal P[a-o .. a-o+16).  So the halfword-aligned 32-bit window
-// of the read at base a is one of the keys {P[r..r+16) : r = 0..7}.  The filter probes every
-// aligned window (ceil(L/8)-1 per read, all independent) in an exact LDS hash set of the keys:
-// no false negatives by construction; the rare false positives (a key occurring by chance,
-// ~n_keys * L/8 / 4^16) are removed by the exact automaton scan of the flagged reads
-// (k_recruit_list), which also yields ACISM's first-callback (end, length).
-// ------------------------------------------------------------------------------------
-// MODE 0: exact keys in LDS, 1: buckets of two 16-bit fingerprints in LDS, 2: exact keys in global memory
-template <int MODE>
-static __device__ __forceinline__ bool anchor_probe(const uint32_t *tab, uint32_t V, const DevAnchors &K, uint32_t rshift)
-{
-    const uint32_t h1 = ak_hash(V, K.m1);
-    const uint32_t h2 = ak_hash(V, K.m2);
-    const uint32_t a = tab[h1 >> rshift], b = tab[h2 >> rshift];   // both probes always issued: independent reads, no branches
-    if (MODE == 1) {
-        // fingerprint = HIGH halfword of h1 ^ h2 (the bits that depend on every base of the key; the low halfword only
-        // sees the first eight, see anchor_probe_fp), replicated into both halves
-        const uint32_t hx = h1 ^ h2;
-        const uint32_t ff = __builtin_amdgcn_perm(hx, hx, 0x03020302u);
-        // a halfword of (slot ^ ff) is zero <=> that fingerprint matches; min(x, 1) per halfword keeps 1 unless zero
-        const uint32_t t = pk_min_u16(a ^ ff, 0x00010001u) & pk_min_u16(b ^ ff, 0x00010001u);
-        return t != 0x00010001u;
-    }
-    return (a == V) | (b == V);
-}
-// MODE 4 (device-built tables beyond the LDS tiers): 2^20-bit Bloom filter in LDS, exact keys in global memory
-static __device__ __forceinline__ bool anchor_probe_bloom(const uint32_t *bloom, const uint32_t *gtab, uint32_t V, const DevAnchors &K, uint32_t rshift)
-{
-    const uint32_t h1 = ak_hash(V, K.m1);
-    const uint32_t wd = bloom[ak_bloom_word(h1)];
-    bool hit = false;
-    if (((wd >> ((h1 >> 12) & 31u)) & (wd >> ((h1 >> 7) & 31u)) & 1u) != 0u)          // ~7 % of the probes at 150 k keys
-        hit = (gtab[h1 >> rshift] == V) | (gtab[ak_hash(V, K.m2) >> rshift] == V);
-    return hit;
-}
-// MODE 3 (device-built tables): 2^16 slots, 16 bits per slot in LDS — the OTHER slot index of the key that sits there
-// (partial-key cuckoo: slot h1(K) stores h2(K) and the other way round), so a window matches when one of its two slots
-// names the other.  Sixteen bits that depend on every base of the key through an independent hash; the low halfword of
-// h1 ^ h2 — the first form — only depends on the key's first eight bases, which the hundreds of variants of one repeat
-// share: every read carrying a near-copy of a repeat then met that value in ~30 slots instead of one (k_dm_verify
-// 364 -> 464 us at 100 M reads, profiles/NOTES_r03.md).
-static __device__ __forceinline__ bool anchor_probe_fp(const uint16_t *tab, uint32_t V, const DevAnchors &K)
-{
-    const uint32_t i1 = ak_hash(V, K.m1) >> 16, i2 = ak_hash(V, K.m2) >> 16;
-    const uint32_t a = tab[i1], b = tab[i2];
-    return (a == i2) | (b == i1);
-}
-
-// ASH: log2 of the windows' alignment — 3: every 8 bases (halfword positions; patterns of >= 23 bases), 2: every 4 bases (byte
-// positions; patterns of 15 .. 22 bases, `-d 15` .. `-d 22`: twice the windows per read, see kDevMinDR)
-// KL: bases per key — 16, or 12 (patterns of 15 .. 18 bases): the window's value is cut to 24 bits before it is hashed and
-// compared (one v_and_b32, the one ak_hash needs anyway: its top-byte term is then zero), and a window only needs KL bases
-// inside the read, so a read has one more of them at its end
-template <int W, int THREADS, int MODE, int ASH = 3, int KL = 16>     // W = uniform stride in words (0: ragged / any stride)
-static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, const DevAnchors &K, const uint32_t *ak_lds,
-                                                          const uint8_t *found_flag, uint64_t *hitmask)
-{
-    constexpr uint32_t PW = 16u >> ASH;              // windows per packed word (2 or 4)
-    constexpr uint32_t WB = 32u / PW;                // bits between two windows (16 or 8)
-    constexpr uint32_t KMASK = KL >= 16 ? 0xFFFFFFFFu : (1u << (2 * KL)) - 1u;
-    constexpr int NWIN = W > 0 ? (16 * W - KL) / (1 << ASH) + 1 : 0;      // windows of a row of W words
-    static_assert(KL == 16 || (KL == 12 && ASH == 2), "anchor key shapes: engine_internal.h, kDevMinDR");
-    auto cut = [](uint32_t V) { return KL >= 16 ? V : (V & KMASK); };
-    const uint32_t mask = 32u - K.log_size;          // right shift that keeps the top log_size bits
-    const uint64_t n_tiles = (R.n_reads + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave_global = (blockIdx.x * (uint64_t)THREADS + threadIdx.x) >> 6;
-    const uint64_t wave_total = ((uint64_t)gridDim.x * THREADS) >> 6;
-    if (W == 0 && R.wave_walk) {
-        // long reads: a lane walking its own 10 kbp read
-        // touches one word per 2.5 KB row, 258 GB/s; here the WAVE walks one read, lane = window, so the loads are
-        // consecutive words, and a tile's 64 reads are taken one after the other (bit k of the mask word = read k)
-        auto probe = [&](uint32_t V) {
-            return MODE == 4 ? anchor_probe_bloom(ak_lds, K.table, V, K, mask)
-                             : MODE == 3 ? anchor_probe_fp(reinterpret_cast<const uint16_t *>(ak_lds), V, K)
-                                         : anchor_probe<(MODE == 3 || MODE == 4) ? 0 : MODE>(ak_lds, V, K, mask);
-        };
-        for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
-            uint64_t bits = 0;
-            for (int k = 0; k < 64; k++) {
-                const uint64_t r = tile * 64 + (uint64_t)k;                     // wave-uniform
-                if (r >= R.n_reads) break;
-                if (!(K.with_exc || !rd_is_exc(R, r)) || found_flag[rd_header_id(R, r)]) continue;
-                const uint32_t L = rd_len(R, r);
-                if (L < (uint32_t)KL) continue;
-                const uint32_t *g = R.packed + rd_word_off(R, r);
-                const uint32_t nw = (L + 15) >> 4, h_max = (L - (uint32_t)KL) >> ASH;
-                // a lane takes FOUR consecutive windows (halfword positions 4q .. 4q+3 = words 2q, 2q+1 and the low half of
-                // 2q+2): three loads serve four probes, one ballot decides 256 windows, and the words of the next round are
-                // requested before this round is probed (one window per lane and round was 20 dependent round trips per
-                // 10 kbp read: 3.3 ms for 1 M reads)
-                auto fetch3 = [&](uint32_t q, uint32_t &a, uint32_t &b, uint32_t &c3) {
-                    const uint32_t w0 = 2u * q;
-                    a = w0 < nw ? g[w0] : 0u; b = w0 + 1u < nw ? g[w0 + 1u] : 0u; c3 = w0 + 2u < nw ? g[w0 + 2u] : 0u;
-                };
-                uint32_t na, nb, nc;
-                fetch3((uint32_t)lane, na, nb, nc);
-                // (windows every 4 bases: the same three words serve EIGHT probes per lane)
-                constexpr uint32_t PL = 2u * PW;                                // windows per lane and round
-                for (uint32_t h0 = 0; h0 <= h_max; h0 += 64u * PL) {
-                    const uint32_t q = (h0 / PL) + (uint32_t)lane;
-                    const uint32_t a = na, b = nb, c3 = nc;
-                    if (h0 + 64u * PL <= h_max) fetch3(q + 64u, na, nb, nc);
-                    const uint32_t h = PL * q;
-                    bool f = false;
-#pragma unroll
-                    for (uint32_t i = 0; i < PL; i++) {
-                        const uint32_t V = i < PW ? __builtin_amdgcn_alignbit(b, a, (i * WB) & 31u) : __builtin_amdgcn_alignbit(c3, b, ((i - PW) * WB) & 31u);
-                        if (h + i <= h_max) f = f | probe(cut(V));
-                    }
-                    if (__ballot(f)) { bits |= 1ull << k; break; }              // one window is enough to flag the read
-                }
-            }
-            if (lane == 0) hitmask[tile] = bits;
-        }
-        return;
-    }
-    // uniform stride: the words of the wave's NEXT tile are requested before the current one is hashed and probed, so a
-    // wave never sits idle for the ~1-2 us of its own loads (4 waves per SIMD — the table takes 128 KB of LDS — were
-    // not enough to cover them: the kernel ran at 62 % of its VALU issue time)
-    uint32_t pre[W > 0 ? W : 1];
-    auto prefetch = [&](uint64_t tile) {
-        if (W > 0) {
-            const uint64_t rr = tile * 64 + lane;
-            if (tile < n_tiles && rr < R.n_reads) {
-                const uint32_t *gp = R.packed + rr * (uint64_t)W;
-#pragma unroll
-                for (int i = 0; i < (W > 0 ? W : 1); i++) pre[i] = gp[i];
-            }
-        }
-    };
-    prefetch(wave_global);
-    for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
-        const uint64_t r = tile * 64 + lane;
-        bool flag = false;
-        uint32_t cur[W > 0 ? W : 1];
-        if (W > 0) {
-#pragma unroll
-            for (int i = 0; i < (W > 0 ? W : 1); i++) cur[i] = pre[i];
-            prefetch(tile + wave_total);
-        }
-        // with_exc: every pattern is pure ACGT, so an occurrence in an exception read lies in a stretch whose packed
-        // codes are the real bases — the probe stays a superset filter; the verification checks the bytes
-        if (r < R.n_reads && (K.with_exc || !rd_is_exc(R, r)) && !found_flag[rd_header_id(R, r)]) {
-            const uint32_t L = rd_len(R, r);
-            const uint32_t *g = R.packed + rd_word_off(R, r);
-            if (L >= (uint32_t)KL) {
-                const uint32_t h_max = (L - (uint32_t)KL) >> ASH;          // last window position (halfword, or byte) whose 16-mer is inside the read
-                if (W > 0) {
-                    uint32_t w[W + 1];
-#pragma unroll
-                    for (int i = 0; i < W; i++) w[i] = cur[i];
-                    w[W] = 0;
-                    if (MODE == 4) {
-                        // Bloom filter in LDS, exact keys in global memory.  ~7 % of the windows pass the Bloom filter, i.e.
-                        // in nearly every one of the 2W-1 unrolled windows SOME lane of the wave does, and a conditional
-                        // pair of global loads per window made the wave wait for 19 round trips.  So: all Bloom tests
-                        // first (LDS only, a bit per window), then every lane resolves ITS positives one per round —
-                        // the wave needs as many rounds as its busiest lane has positives (4-5).
-                        typedef typename std::conditional<ASH == 3, uint32_t, uint64_t>::type pm_t;      // (up to 61 windows every 4 bases)
-                        pm_t pm = 0;
-#pragma unroll
-                        for (int h = 0; h < NWIN; h++) {
-                            const uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
-                            // (blocked Bloom: ONE hash, one LDS word, both bits from it; a shift by a register takes the register's low
-                            // five bits, so the two positions cost a shift each and the window's flag joins pm with one v_lshl_or)
-                            const uint32_t h1 = ak_hash(V, K.m1);
-                            const uint32_t wd = ak_lds[ak_bloom_word(h1)];
-                            const uint32_t bit = (wd >> ((h1 >> 12) & 31u)) & (wd >> ((h1 >> 7) & 31u)) & 1u;
-                            if ((uint32_t)h <= h_max) pm |= (pm_t)bit << h;
-                        }
-                        while (pm) {                                   // (divergent: lanes with fewer positives idle)
-                            const uint32_t h = (uint32_t)(ASH == 3 ? __ffs((int)(uint32_t)pm) : __ffsll((unsigned long long)pm)) - 1u;
-                            pm &= pm - 1u;
-                            const uint32_t kk = h / PW;
-                            uint32_t lo = 0, hi = 0;
-#pragma unroll
-                            for (int i = 0; i < W; i++) { lo = kk == (uint32_t)i ? w[i] : lo; hi = kk == (uint32_t)i ? w[i + 1] : hi; }
-                            const uint32_t V = cut(__builtin_amdgcn_alignbit(hi, lo, (h % PW) * WB));
-                            const uint32_t h1 = ak_hash(V, K.m1), h2 = ak_hash(V, K.m2);
-                            if ((K.table[h1 >> mask] == V) | (K.table[h2 >> mask] == V)) { flag = true; pm = 0; }
-                        }
-                    } else {
-                    // (uniform read length: the last window is a scalar, and "window inside the read" costs no vector compare)
-                    auto scan = [&](const uint32_t hm) {
-#pragma unroll
-                        for (int h = 0; h < NWIN; h++) {
-                            uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
-                            bool hit = MODE == 3 ? anchor_probe_fp(reinterpret_cast<const uint16_t *>(ak_lds), V, K)
-                                                 : anchor_probe<(MODE == 3 || MODE == 4) ? 0 : MODE>(ak_lds, V, K, mask);
-                            flag = flag | (hit & ((uint32_t)h <= hm));
-                            // (16 LDS reads in flight are plenty; left alone the scheduler hoists all 4W-2 of them and, from
-                            // W = 12, spills)
-                            if ((h & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-                        }
-                    };
-                    if (R.uniform_len) scan((R.uniform_len - (uint32_t)KL) >> ASH);
-                    else scan(h_max);
-                    }
-                } else {
-                    // (four words per round, requested together: one word per round was one dependent round trip per 16 bases — reads of
-                    // 300 .. 800 bases, lane per read, took twice the time of the register form per base)
-                    const uint32_t nw = (L + 15) >> 4;
-                    auto probe = [&](uint32_t V) {
-                        return MODE == 4 ? anchor_probe_bloom(ak_lds, K.table, V, K, mask)
-                                         : MODE == 3 ? anchor_probe_fp(reinterpret_cast<const uint16_t *>(ak_lds), V, K)
-                                                     : anchor_probe<(MODE == 3 || MODE == 4) ? 0 : MODE>(ak_lds, V, K, mask);
-                    };
-                    uint32_t lo = g[0];
-                    for (uint32_t h = 0; h <= h_max && !flag; h += 4u * PW) {
-                        const uint32_t wi = (h / PW) + 1;
-                        uint32_t x[4];
-#pragma unroll
-                        for (uint32_t q = 0; q < 4; q++) x[q] = wi + q < nw ? g[wi + q] : 0u;
-#pragma unroll
-                        for (uint32_t q = 0; q < 4; q++) {
-#pragma unroll
-                            for (uint32_t i = 0; i < PW; i++)
-                                if (h + PW * q + i <= h_max && probe(cut(__builtin_amdgcn_alignbit(x[q], lo, i * WB)))) flag = true;
-                            lo = x[q];
-                        }
-                    }
-                }
-            }
-        }
-        uint64_t m = __ballot(flag);
-        if (lane == 0) hitmask[tile] = m;
-    }
-}
-
-template <int W, int THREADS, int MODE>
-__global__ __launch_bounds__(THREADS) void k_anchor_filter(DevReads R, DevAnchors K, const uint8_t *found_flag, uint64_t *hitmask)
-{
-    // (1 024 threads per block and, with its table in LDS, one block per CU.  Until round 4 a CRASS_VGPR_FLOOR(120) kept every
-    // instantiation off a multiple of 8 registers: 4 waves x 128 allocated registers = a SIMD's whole file, so no wave of any
-    // other kernel could share the CU — the view export beside it then cost the probe 144 -> 216 us.  The build's guard is exact
-    // now, crass_amd/vgpr_guard.py, and these kernels hold no 64-bit shift by their last register.)
-    extern __shared__ __attribute__((aligned(16))) uint32_t ak_lds_buf[];
-    const uint32_t tsize = 1u << K.log_size;
-    const uint32_t *ak_lds = K.table;                   // key sets too large for LDS are probed in global memory (L2)
-    if (MODE != 2) {
-        for (uint32_t i = threadIdx.x; i < tsize; i += THREADS) ak_lds_buf[i] = K.table[i];
-        __syncthreads();
-        ak_lds = ak_lds_buf;
-    }
-    anchor_filter_body<W, THREADS, MODE>(R, K, ak_lds, found_flag, hitmask);
-}
-
-// the same filter when the key table was built on the device (dmerge.hip): its size is only known there
-// (ASH is a template parameter of the KERNEL: with both forms in one kernel the default one was allocated the other's registers —
-// 99 instead of 56 — and no other kernel's waves fitted beside its four per SIMD any more)
-template <int W, int THREADS, int ASH, int KL>
-__global__ __launch_bounds__(THREADS) void k_anchor_filter_dev(DevReads R, DevMerge M, const uint8_t *found_flag, uint64_t *hitmask)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t ak_lds_buf[];
-    if (M.flag_post && blockIdx.x == 0 && threadIdx.x == 0) stage_flag_store(M.flag_post, M.flag_post_val);      // (the merge's kernels are complete)
-    DevAnchors K;
-    K.table = M.anchor_tab; K.log_size = M.st->log_size; K.mode = 0; K.m1 = M.m1; K.m2 = M.m2; K.n_keys = 0;
-    K.with_exc = 1;
-    if (M.st->fail != 0 || K.log_size == 0) {            // the host redoes the merge; flag nothing
-        const uint64_t n_tiles = (R.n_reads + 63) / 64;
-        for (uint64_t t = blockIdx.x * (uint64_t)THREADS + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * THREADS) hitmask[t] = 0ull;
-        return;
-    }
-    if (K.log_size <= 15) {
-        const uint32_t tsize = 1u << K.log_size;
-        for (uint32_t i = threadIdx.x; i < tsize; i += THREADS) ak_lds_buf[i] = K.table[i];
-        __syncthreads();
-        anchor_filter_body<W, THREADS, 0, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
-    } else if (M.st->tab_mode == 3) {
-        for (uint32_t i = threadIdx.x; i < (1u << 15); i += THREADS) ak_lds_buf[i] = M.anchor_fp[i];
-        __syncthreads();
-        anchor_filter_body<W, THREADS, 3, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
-    } else {
-        for (uint32_t i = threadIdx.x; i < (1u << 15); i += THREADS) ak_lds_buf[i] = M.anchor_fp[i];
-        __syncthreads();
-        anchor_filter_body<W, THREADS, 4, ASH, KL>(R, K, ak_lds_buf, found_flag, hitmask);
-    }
-}
-
-hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st)
-{
-    if (R.n_reads == 0) return hipSuccess;
-    if (!((M.akey_bases == 16u && (M.akey_shift == 3u || M.akey_shift == 2u)) || (M.akey_bases == 12u && M.akey_shift == 2u))) return hipErrorInvalidValue;
-    const size_t lds = 128 * 1024;
-    const uint64_t n_tiles = (R.n_reads + 63) / 64;
-    constexpr int T = 1024;
-    uint64_t blocks = (n_tiles + (T / 64) - 1) / (T / 64);
-    if (blocks > 256) blocks = 256;
-    hipError_t e;
-#define AKD_LAUNCH1(WW, AA, KK)                                                                                           \
-    {                                                                                                                   \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_anchor_filter_dev<WW, T, AA, KK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return e;                                                                                  \
-        CRASS_LAUNCH((k_anchor_filter_dev<WW, T, AA, KK>), dim3((unsigned)blocks), dim3(T), lds, st, R, M, found_flag, hitmask); \
-    }
-#define AKD_LAUNCH(WW) { if (M.akey_shift == 2u && M.akey_bases == 12u) AKD_LAUNCH1(WW, 2, 12) else if (M.akey_shift == 2u) AKD_LAUNCH1(WW, 2, 16) else AKD_LAUNCH1(WW, 3, 16) }
-    switch (R.stride_words) {
-        case 4: AKD_LAUNCH(4) break;  case 5: AKD_LAUNCH(5) break;  case 6: AKD_LAUNCH(6) break;  case 7: AKD_LAUNCH(7) break;
-        case 8: AKD_LAUNCH(8) break;  case 9: AKD_LAUNCH(9) break;  case 10: AKD_LAUNCH(10) break; case 11: AKD_LAUNCH(11) break;
-        case 12: AKD_LAUNCH(12) break; case 13: AKD_LAUNCH(13) break; case 14: AKD_LAUNCH(14) break; case 15: AKD_LAUNCH(15) break;
-        case 16: AKD_LAUNCH(16) break;
-        default: AKD_LAUNCH(0) break;
-    }
-#undef AKD_LAUNCH
-#undef AKD_LAUNCH1
-    return hipGetLastError();
-}
-
-hipError_t launch_anchor_filter(const DevReads &R, const DevAnchors &K, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st)
-{
-    if (R.n_reads == 0) return hipSuccess;
-    const size_t tbytes = (size_t)4 << K.log_size;
-    const bool in_lds = tbytes <= 128 * 1024;
-    if (K.mode == 1 && !in_lds) return hipErrorInvalidValue;
-    const size_t lds = in_lds ? tbytes : 0;
-    const uint64_t n_tiles = (R.n_reads + 63) / 64;
-    constexpr int T = 1024;
-    uint64_t blocks = (n_tiles + (T / 64) - 1) / (T / 64);
-    const uint64_t cap = lds > 80 * 1024 ? 256 : (lds > 40 * 1024 ? 512 : 1024);
-    if (blocks > cap) blocks = cap;
-    hipError_t e;
-#define AK_LAUNCH_M(WW, MM)                                                                                             \
-    {                                                                                                                   \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_anchor_filter<WW, T, MM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return e;                                                                                  \
-        CRASS_LAUNCH((k_anchor_filter<WW, T, MM>), dim3((unsigned)blocks), dim3(T), lds, st, R, K, found_flag, hitmask); \
-    }
-#define AK_LAUNCH(WW)                                                                                                   \
-    if (!in_lds) AK_LAUNCH_M(WW, 2) else if (K.mode == 1) AK_LAUNCH_M(WW, 1) else AK_LAUNCH_M(WW, 0)
-    switch (R.stride_words) {
-        case 4: AK_LAUNCH(4) break;  case 5: AK_LAUNCH(5) break;  case 6: AK_LAUNCH(6) break;  case 7: AK_LAUNCH(7) break;
-        case 8: AK_LAUNCH(8) break;  case 9: AK_LAUNCH(9) break;  case 10: AK_LAUNCH(10) break; case 11: AK_LAUNCH(11) break;
-        case 12: AK_LAUNCH(12) break; case 13: AK_LAUNCH(13) break; case 14: AK_LAUNCH(14) break; case 15: AK_LAUNCH(15) break;
-        case 16: AK_LAUNCH(16) break;
-        default: AK_LAUNCH(0) break;
-    }
-#undef AK_LAUNCH
-#undef AK_LAUNCH_M
-    return hipGetLastError();
-}
-
-// exact first-match scan of the flagged reads (lane per flagged read), transition table in global
-// memory (L2-resident).  info_by_slot[k] = (end_exclusive << 8) | length, 0 = no pattern occurs.
-__global__ __launch_bounds__(256) void k_recruit_list(DevReads R, DevAutomaton A, const uint64_t *idx, const uint32_t *d_n,
-                                                       uint64_t n_max, uint32_t *info_by_slot, uint32_t *pid_by_slot)
-{
-    uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t n = *d_n;
-    if (n > n_max) n = n_max;
-    if (k >= n) return;
-    const uint64_t r = idx[k];
-    const uint32_t L = rd_len(R, r);
-    const uint32_t *g = R.packed + rd_word_off(R, r);
-    const uint32_t symA = A.sym['A'], symC = A.sym['C'], symG = A.sym['G'], symT = A.sym['T'];
-    uint32_t state = 0, word = 0, info = 0, pid = 0;
-    for (uint32_t i = 0; i < L; i++) {
-        if ((i & 15u) == 0) word = g[i >> 4];
-        uint32_t c = word & 3u;
-        word >>= 2;
-        if (A.go4) state = A.go4[state * 4 + c];
-        else if (A.go4w) state = A.go4w[(size_t)state * 4 + c];
-        else {
-            uint32_t sy = c == 0 ? symA : c == 1 ? symC : c == 2 ? symG : symT;
-            state = A.go16 ? (uint32_t)A.go16[(size_t)state * A.n_sym1 + sy] : A.go32[(size_t)state * A.n_sym1 + sy];
-        }
-        uint32_t ol = A.out_len[state];
-        if (ol) { info = ((i + 1) << 8) | ol; pid = A.out_pid[state]; break; }
-    }
-    info_by_slot[k] = info;
-    pid_by_slot[k] = pid;
-}
-
-// The same for long reads: one WAVE per flagged read.  The automaton's state at a position only depends on the last
-// max_pat_len bases (the depth of the trie), so lane l scans its own slice [l * seg, (l + 1) * seg) after a warm-up of
-// max_pat_len bases from the start state and is in the exact state for every position it reports; the first callback
-// of the whole read is the smallest reported position over the lanes (a lane per 10 kbp read walked 10 000 dependent
-// table look-ups: 2.8 ms for a few hundred reads).
-__global__ __launch_bounds__(256) void k_recruit_list_wave(DevReads R, DevAutomaton A, const uint64_t *idx, const uint32_t *d_n,
-                                                            uint64_t n_max, uint32_t *info_by_slot, uint32_t *pid_by_slot)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t k = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    uint64_t n = *d_n;
-    if (n > n_max) n = n_max;
-    if (k >= n) return;
-    const uint64_t r = idx[k];
-    const uint32_t L = rd_len(R, r);
-    const uint32_t *g = R.packed + rd_word_off(R, r);
-    const uint32_t symA = A.sym['A'], symC = A.sym['C'], symG = A.sym['G'], symT = A.sym['T'];
-    const uint32_t seg = (L + 63u) / 64u;
-    const uint32_t s0 = (uint32_t)lane * seg, e0 = min(L, s0 + seg);
-    uint32_t first = 0xFFFFFFFFu, ol_found = 0, pid = 0;
-    if (s0 < L) {
-        const uint32_t p0 = s0 >= A.max_pat_len ? s0 - A.max_pat_len : 0u;        // warm-up (exact from the read start anyway)
-        uint32_t state = 0, word = 0;
-        for (uint32_t i = p0; i < e0; i++) {
-            if ((i & 15u) == 0 || i == p0) word = g[i >> 4] >> ((i & 15u) * 2u);
-            const uint32_t c = word & 3u;
-            word >>= 2;
-            if (A.go4) state = A.go4[state * 4 + c];
-            else if (A.go4w) state = A.go4w[(size_t)state * 4 + c];
-            else {
-                const uint32_t sy = c == 0 ? symA : c == 1 ? symC : c == 2 ? symG : symT;
-                state = A.go16 ? (uint32_t)A.go16[(size_t)state * A.n_sym1 + sy] : A.go32[(size_t)state * A.n_sym1 + sy];
-            }
-            if (i >= s0) {
-                const uint32_t ol = A.out_len[state];
-                if (ol) { first = i; ol_found = ol; pid = A.out_pid[state]; break; }
-            }
-        }
-    }
-    uint32_t best = first;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, off));
-    if (best == 0xFFFFFFFFu) { if (lane == 0) { info_by_slot[k] = 0; pid_by_slot[k] = 0; } return; }
-    if (first == best) {                                  // exactly one lane owns that position
-        info_by_slot[k] = ((best + 1) << 8) | ol_found;
-        pid_by_slot[k] = pid;
-    }
-}
-
-hipError_t launch_recruit_list(const DevReads &R, const DevAutomaton &A, const uint64_t *idx, const uint32_t *d_n,
-                               uint64_t n_max, uint32_t *info_by_slot, uint32_t *pid_by_slot, hipStream_t st)
-{
-    if (n_max == 0) return hipSuccess;
-    if (R.wave_walk && A.max_pat_len)                      // long reads
-        CRASS_LAUNCH(k_recruit_list_wave, dim3((unsigned)((n_max + 3) / 4)), dim3(256), 0, st, R, A, idx, d_n, n_max, info_by_slot, pid_by_slot);
-    else
-        CRASS_LAUNCH(k_recruit_list, dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, st, R, A, idx, d_n, n_max, info_by_slot, pid_by_slot);
-    return hipGetLastError();
-}
-
-// exception reads: raw bytes through the byte-symbol automaton, lane per exception read
-__global__ __launch_bounds__(256) void k_recruit_exc(DevReads R, DevAutomaton A, const uint8_t *found_flag, uint32_t *exc_hit_info)
-{
-    uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (s >= R.n_exc) return;
-    uint64_t r = R.exc_read[s];
-    uint32_t info = 0;
-    if (!found_flag[rd_header_id(R, r)]) {
-        uint64_t o0 = R.exc_off[s];
-        uint32_t L = (uint32_t)(R.exc_off[s + 1] - o0);
-        uint32_t state = 0;
-        for (uint32_t i = 0; i < L; i++) {
-            uint32_t sy = A.sym[R.exc_bytes[o0 + i]];
-            state = A.go16 ? (uint32_t)A.go16[(size_t)state * A.n_sym1 + sy] : A.go32[(size_t)state * A.n_sym1 + sy];
-            uint32_t ol = A.out_len[state];
-            if (ol) { info = ((i + 1) << 8) | ol; break; }
-        }
-    }
-    exc_hit_info[s] = info;
-}
-
-hipError_t launch_recruit_exceptions(const DevReads &R, const DevAutomaton &A, const uint8_t *found_flag,
-                                     uint32_t *exc_hit_info, hipStream_t st)
-{
-    if (R.n_exc == 0) return hipSuccess;
-    CRASS_LAUNCH(k_recruit_exc, dim3((unsigned)((R.n_exc + 255) / 256)), dim3(256), 0, st, R, A, found_flag, exc_hit_info);
-    return hipGetLastError();
-}
-
-// on_match + addReadHolder's DRLowLexi for the single recruited repeat
-// (libcrispr.cpp:408-442, ReadHolder.cpp:524-528,573-590).  Thread per hit.
-template <bool EXC>
-__global__ __launch_bounds__(256) void k_recruit_finish(DevReads R, const uint64_t *hit_idx, const uint32_t *d_n_hits,
-                                                        uint64_t n_max, const uint32_t *hit_info, int info_by_slot,
-                                                        const uint32_t *pid_by_slot, const uint32_t *pat_token,
-                                                        RecruitOut *out, char *dr_chars, uint32_t dr_stride, const uint64_t *pat_mask)
-{
-    if constexpr (!EXC) CRASS_VGPR_FLOOR(24);      // 24 VGPRs with the 128-bit shift amount in v23: the kernel that exposed the erratum
-    uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t n = EXC ? R.n_exc : (uint64_t)(*d_n_hits);
-    if (n > n_max) n = n_max;
-    if (k >= n) return;
-    RecruitOut o; o.start = 0; o.end = 0; o.token = 0; o.dr_len = 0; o.low_lexi = 0; o.pad = 0;
-    uint32_t info;
-    uint32_t L;
-    uint64_t r = 0, o0 = 0;
-    const uint32_t *g = nullptr;
-    if (EXC) {
-        info = hit_info[k];
-        o0 = R.exc_off[k];
-        L = (uint32_t)(R.exc_off[k + 1] - o0);
-    } else {
-        r = hit_idx[k];
-        info = info_by_slot ? hit_info[k] : hit_info[r];
-        L = rd_len(R, r);
-        g = R.packed + rd_word_off(R, r);
-    }
-    if (info == 0) { out[k] = o; return; }              // no match (exception read / anchor false positive)
-    uint32_t textpos = info >> 8, len = info & 0xFFu;
-    uint32_t DR_end = textpos - 1;
-    if (DR_end >= L) DR_end = L - 1;
-    uint32_t start = DR_end - (len - 1);
-    // a pattern with an 'N' (device merge, dmerge.hip) matched an exception read: the packed words hold 'A' there,
-    // so the repeat is read from the read's bytes
-    const uint8_t *raw = nullptr;
-    if (!EXC && pat_mask && pid_by_slot && pat_mask[pid_by_slot[k]] != 0ull && R.n_exc) {
-        uint64_t lo = 0, hi = R.n_exc - 1;
-        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (R.exc_read[mid] < r) lo = mid + 1; else hi = mid; }
-        raw = R.exc_bytes + R.exc_off[lo];
-    }
-    if (!EXC && len <= 64 && !raw) {
-        // packed reads: the repeat as a 128-bit value (base i in bits 2i..2i+1), its reverse complement by bit
-        // reversal, and DRLowLexi's string comparison as "first differing base from the low end"
-        const uint32_t nw = (L + 15) >> 4, w0 = start >> 4, sh = (start & 15u) * 2u;
-        uint32_t x[5];
-#pragma unroll
-        for (int q = 0; q < 5; q++) x[q] = (w0 + q < nw) ? g[w0 + q] : 0u;
-        uint32_t y[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) y[q] = sh ? ((x[q] >> sh) | (x[q + 1] << (32 - sh))) : x[q];
-        uint64_t v0 = (uint64_t)y[0] | ((uint64_t)y[1] << 32), v1 = (uint64_t)y[2] | ((uint64_t)y[3] << 32);
-        const uint64_t m0 = len >= 32 ? ~0ull : ((1ull << (2 * len)) - 1ull);
-        const uint64_t m1 = len >= 64 ? ~0ull : (len > 32 ? ((1ull << (2 * (len - 32))) - 1ull) : 0ull);
-        v0 &= m0; v1 &= m1;
-        auto rev2 = [](uint64_t t) -> uint64_t {          // reverse the order of the 32 two-bit groups
-            t = __brevll(t);
-            return ((t >> 1) & 0x5555555555555555ull) | ((t & 0x5555555555555555ull) << 1);
-        };
-        // complement, reverse all 64 groups of the 128-bit value, then shift the len groups down to bit 0
-        const uint64_t c0 = rev2(~v1), c1 = rev2(~v0);     // (c1:c0) = reversed 128 bits
-        const uint32_t drop = 128u - 2u * len;             // unused high groups became low groups
-        uint64_t r0, r1;
-        if (drop == 0) { r0 = c0; r1 = c1; }
-        else if (drop < 64) { r0 = (c0 >> drop) | (c1 << (64 - drop)); r1 = c1 >> drop; }
-        else { r0 = c1 >> (drop - 64); r1 = 0; }
-        r0 &= m0; r1 &= m1;
-        int less = 0;
-        const uint64_t d0 = v0 ^ r0, d1 = v1 ^ r1;
-        if (d0 | d1) {
-            const uint64_t dv = d0 ? d0 : d1, av = d0 ? v0 : v1, bv = d0 ? r0 : r1;
-            const int p = (__ffsll((unsigned long long)dv) - 1) & ~1;
-            less = ((av >> p) & 3ull) < ((bv >> p) & 3ull);
-        }
-        const uint64_t s0 = less ? v0 : r0, s1 = less ? v1 : r1;
-        if (dr_chars) {
-            char *dr = dr_chars + k * (uint64_t)dr_stride;
-            for (uint32_t i = 0; i < dr_stride; i++) {
-                const uint32_t c = (uint32_t)(((i < 32 ? s0 : s1) >> (2 * (i & 31))) & 3ull);
-                dr[i] = i < len ? "ACGT"[c] : (char)0;
-            }
-        }
-        if (less) { o.start = start; o.end = DR_end; o.low_lexi = 1; }
-        else { o.start = L - 1 - DR_end; o.end = L - 1 - start; o.low_lexi = 0; }
-        o.dr_len = (uint16_t)len;
-        if (pid_by_slot && pat_token) o.token = pat_token[pid_by_slot[k]];
-        out[k] = o;
-        return;
-    }
-    auto base_at = [&](uint32_t i) -> uint8_t {
-        if (EXC) return R.exc_bytes[o0 + i];
-        if (raw) return raw[i];
-        uint32_t c = (g[i >> 4] >> ((i & 15u) * 2u)) & 3u;
-        return (uint8_t)("ACGT"[c]);
-    };
-    int less = 0;
-    for (uint32_t i = 0; i < len; i++) {
-        uint8_t a = base_at(start + i);
-        uint8_t b = c_comp[base_at(start + len - 1 - i) & 127];
-        if (a != b) { less = a < b; break; }
-    }
-    char *dr = dr_chars ? dr_chars + k * (uint64_t)dr_stride : nullptr;
-    if (less) {
-        if (dr) for (uint32_t i = 0; i < len; i++) dr[i] = (char)base_at(start + i);
-        o.start = start; o.end = DR_end; o.low_lexi = 1;
-    } else {
-        if (dr) for (uint32_t i = 0; i < len; i++) dr[i] = (char)c_comp[base_at(start + len - 1 - i) & 127];
-        o.start = L - 1 - DR_end; o.end = L - 1 - start; o.low_lexi = 0;
-    }
-    if (dr) for (uint32_t i = len; i < dr_stride; i++) dr[i] = 0;
-    o.dr_len = (uint16_t)len;
-    // the matched pattern's low-lexi form is a stored DR variant: its token was resolved once per
-    // pattern on the host (addReadHolder's lookup, libcrispr.cpp:1137)
-    if (pid_by_slot && pat_token) o.token = pat_token[pid_by_slot[k]];
-    out[k] = o;
-}
-
-hipError_t launch_recruit_finish(const DevReads &R, const uint64_t *hit_idx, const uint32_t *d_n_hits, uint64_t n_hits_max,
-                                 const uint32_t *hit_info, bool info_by_slot, bool exceptions,
-                                 const uint32_t *pid_by_slot, const uint32_t *pat_token, RecruitOut *out,
-                                 char *dr_chars, uint32_t dr_stride, hipStream_t st, const uint64_t *pat_mask)
-{
-    if (n_hits_max == 0) return hipSuccess;
-    unsigned nb = (unsigned)((n_hits_max + 255) / 256);
-    if (exceptions)
-        CRASS_LAUNCH(k_recruit_finish<true>, dim3(nb), dim3(256), 0, st, R, hit_idx, d_n_hits, n_hits_max, hit_info, 1, pid_by_slot, pat_token, out, dr_chars, dr_stride, (const uint64_t *)nullptr);
-    else
-        CRASS_LAUNCH(k_recruit_finish<false>, dim3(nb), dim3(256), 0, st, R, hit_idx, d_n_hits, n_hits_max, hit_info, info_by_slot ? 1 : 0, pid_by_slot, pat_token, out, dr_chars, dr_stride, pat_mask);
-    return hipGetLastError();
-}
-
-// ---- pass-2 sink on the device: drop the slots without a match, pack the rest (read order) ----
-__global__ __launch_bounds__(256) void k_recruit_valid_mask(const RecruitOut *rec, const uint32_t *d_n, uint64_t n_max, uint64_t *mask)
-{
-    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t n = *d_n;
-    if (n > n_max) n = n_max;
-    const bool v = k < n && rec[k].dr_len != 0;
-    const uint64_t m = __ballot(v);
-    if ((threadIdx.x & 63) == 0 && k < n_max) mask[k >> 6] = m;
-}
-__global__ __launch_bounds__(256) void k_pack_p2_blob(const RecruitOut *rec, const uint64_t *hit_idx, uint64_t read_base, const uint64_t *vidx,
-                                                       const uint32_t *d_nv, uint64_t cap, uint8_t *blob, const uint32_t *d_n_hits, uint32_t *h_n_hits,
-                                                       uint32_t narrow)
-{
-    const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t nv = *d_nv;
-    if (nv > cap) nv = cap;
-    if (q == 0) {
-        reinterpret_cast<uint64_t *>(blob)[0] = nv; reinterpret_cast<uint64_t *>(blob)[1] = cap;
-        if (h_n_hits) *h_n_hits = *d_n_hits;            // the flagged-read count the host checks its bound against
-    }
-    if (q >= nv) return;
-    const P2Blob b = p2_blob_layout(cap, narrow);
-    const uint64_t k = vidx[q];
-    const RecruitOut o = rec[k];
-    if (narrow == 2) {
-        reinterpret_cast<uint32_t *>(blob + b.token)[q] = o.token | ((uint32_t)(o.low_lexi != 0) << 31);
-        reinterpret_cast<uint32_t *>(blob + b.read)[q] = (uint32_t)hit_idx[k];
-        (blob + b.start)[q] = (uint8_t)o.start;
-        return;
-    }
-    reinterpret_cast<uint32_t *>(blob + b.token)[q] = o.token;
-    if (narrow) {
-        reinterpret_cast<uint32_t *>(blob + b.read)[q] = (uint32_t)hit_idx[k];          // (local index: the host adds the base)
-        (blob + b.start)[q] = (uint8_t)o.start;
-        (blob + b.end)[q] = (uint8_t)o.end;
-    } else {
-        reinterpret_cast<uint64_t *>(blob + b.read)[q] = read_base + hit_idx[k];
-        reinterpret_cast<uint16_t *>(blob + b.start)[q] = (uint16_t)o.start;
-        reinterpret_cast<uint16_t *>(blob + b.end)[q] = (uint16_t)o.end;
-    }
-    (blob + b.dr_len)[q] = (uint8_t)o.dr_len;
-    (blob + b.low)[q] = o.low_lexi;
-}
-// k_recruit_valid_mask + compaction in one pass (decoupled look-back): vidx[rank] = slot of the rank-th valid hit
-__global__ __launch_bounds__(1024) void k_valid_compact(const RecruitOut *rec, const uint32_t *d_n_hits, uint64_t cap, uint64_t *vidx, uint32_t *d_nv,
-                                                         Lookback lb)
-{
-    uint64_t n = *d_n_hits;
-    if (n > cap) n = cap;
-    const uint32_t n_tiles = n ? (uint32_t)((n + kLbElemsPerTile - 1) / kLbElemsPerTile) : 1u;      // (sized for a bound: the tiles past the count leave at once)
-    if (blockIdx.x >= n_tiles) return;
-    const uint32_t tile = lb_tile_id(lb, n_tiles);
-    const uint64_t k0 = (uint64_t)tile * kLbElemsPerTile + 4u * threadIdx.x;
-    uint32_t fm = 0;
-#pragma unroll
-    for (int e = 0; e < 4; e++) if (k0 + e < n && rec[k0 + e].dr_len != 0) fm |= 1u << e;
-    uint32_t upto;
-    uint64_t q = lb_rank4(lb, tile, (uint32_t)__popc(fm), &upto);
-    if (tile == n_tiles - 1 && threadIdx.x == 0) *d_nv = upto;
-#pragma unroll
-    for (int e = 0; e < 4; e++) if (fm & (1u << e)) vidx[q++] = k0 + e;
-}
-
-hipError_t launch_pack_p2_blob(const RecruitOut *rec, const uint64_t *hit_idx, uint64_t read_base,
-                               const uint32_t *d_n_hits, uint64_t n_hits_max, uint64_t *mask, uint32_t *word_prefix, uint32_t *block_sums,
-                               uint64_t *vidx, uint32_t *d_nv, uint8_t *blob, hipStream_t st, uint32_t *h_n_hits, const Lookback *lb, uint32_t narrow)
-{
-    if (n_hits_max == 0) return hipSuccess;
-    const unsigned nb = (unsigned)((n_hits_max + 255) / 256);
-    if (lb) {           // (the caller reserved nb tiles)
-        const unsigned nt = (unsigned)((n_hits_max + kLbElemsPerTile - 1) / kLbElemsPerTile);
-        CRASS_LAUNCH(k_valid_compact, dim3(nt), dim3(1024), 0, st, rec, d_n_hits, n_hits_max, vidx, d_nv, *lb);
-        CRASS_LAUNCH(k_pack_p2_blob, dim3(nb), dim3(256), 0, st, rec, hit_idx, read_base, vidx, d_nv, n_hits_max, blob, d_n_hits, h_n_hits, narrow);
-        return hipGetLastError();
-    }
-    CRASS_LAUNCH(k_recruit_valid_mask, dim3(nb), dim3(256), 0, st, rec, d_n_hits, n_hits_max, mask);
-    hipError_t e = launch_compact(mask, (n_hits_max + 63) / 64, n_hits_max, word_prefix, block_sums, vidx, n_hits_max, d_nv, st);
-    if (e != hipSuccess) return e;
-    CRASS_LAUNCH(k_pack_p2_blob, dim3(nb), dim3(256), 0, st, rec, hit_idx, read_base, vidx, d_nv, n_hits_max, blob, d_n_hits, h_n_hits, narrow);
     return hipGetLastError();
 }
 
@@ -5098,11 +3466,6 @@ hipError_t launch_levenshtein_batch(const uint8_t *chars, const uint64_t *a_off,
     uint64_t grid = n_pairs < 4096 ? n_pairs : 4096;
     CRASS_LAUNCH(k_lev_batch, dim3((unsigned)grid), dim3(WAVE), lds, st, chars, a_off, a_len, b_off, b_len, n_pairs, dist, sim, row_elems, str_bytes);
     return hipGetLastError();
-}
-
-hipError_t upload_comp_table(const unsigned char *tab128)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(c_comp), tab128, 128);
 }
 
 } // namespace crass

@@ -1,6 +1,7 @@
 // merge.cpp — the serial "merge" step between the two device passes (stays on the host:
 // a few thousand DR variants, negligible next to the scans).
 #include "merge.h"
+#include "comp_table.h"
 #include "../../include/crass_hip.h"
 
 #include <algorithm>
@@ -18,34 +19,9 @@
 
 namespace crass {
 
-void build_comp_table(unsigned char tab[128])
-{
-    // IUPAC complement pairs, U->A, everything else maps to itself; entry 96 ('`') holds 64,
-    // exactly like the reference table (SeqUtils.cpp:50-59).
-    for (int i = 0; i < 128; i++) tab[i] = (unsigned char)i;
-    const char *a = "ACBDKRSWN", *b = "TGVHMYSWN";
-    for (int i = 0; a[i]; i++) {
-        tab[(int)a[i]] = (unsigned char)b[i];
-        tab[(int)b[i]] = (unsigned char)a[i];
-        tab[(int)a[i] + 32] = (unsigned char)(b[i] + 32);
-        tab[(int)b[i] + 32] = (unsigned char)(a[i] + 32);
-    }
-    tab['U'] = 'A';
-    tab['u'] = 'a';
-    tab[96] = 64;
-}
-
-static const unsigned char *comp_table()
-{
-    static unsigned char tab[128];
-    static bool ready = false;
-    if (!ready) { build_comp_table(tab); ready = true; }
-    return tab;
-}
-
 std::string reverse_complement(const std::string &s)
 {
-    const unsigned char *tab = comp_table();
+    const unsigned char *tab = kCompTable.v;
     std::string r(s.size(), '\0');
     for (size_t i = 0; i < s.size(); i++) r[i] = (char)tab[(unsigned char)s[s.size() - 1 - i] & 127];
     return r;
@@ -751,7 +727,7 @@ static bool assign_tokens_from_rep(MergeResult &m, const char *dr_chars, const u
 // every group contributes its survivors, then their reverse complements (WorkHorse.cpp:690-705)
 static void emit_patterns(MergeResult &m, const std::vector<std::vector<Member>> &survivors)
 {
-    const unsigned char *ctab = comp_table();
+    const unsigned char *ctab = kCompTable.v;
     size_t n_pat = 0, n_pat_chars = 0;
     for (const auto &g : survivors) { n_pat += 2 * g.size(); for (const Member &x : g) n_pat_chars += 2 * (size_t)x.len; }
     m.patterns.chars.reserve(n_pat_chars); m.patterns.off.reserve(n_pat + 1);
@@ -922,7 +898,7 @@ bool merge_from_device_finish(MergeResult &m, const uint32_t *gid_of, const uint
     m.patterns.off[0] = 0;
     m.pat_group.resize(n_pat);
     m.pat_token.resize(n_pat);
-    const unsigned char *ctab = comp_table();
+    const unsigned char *ctab = kCompTable.v;
     std::atomic<int> need_lookup{0};
     parallel_tasks(n_tasks, host_threads, [&](size_t c) {
         for (size_t g = c * gchunk; g < std::min<size_t>(n_groups, (c + 1) * gchunk); g++) {
@@ -1294,7 +1270,7 @@ void build_anchors(HostAnchors &k, const StringArena &patterns)
                 if (!ok) break;
             }
             if (!ok) continue;
-            // fingerprint = high 16 bits of (h1 ^ h2) (kernels.hip, anchor_probe); empty slots keep 0 (any value
+            // fingerprint = high 16 bits of (h1 ^ h2) (pass2.hip, anchor_probe_any); empty slots keep 0 (any value
             // there is just one more false-positive source of the same 2^-16 weight)
             std::vector<uint32_t> tab(nb, 0);
             for (uint32_t bk = 0; bk < nb; bk++) {

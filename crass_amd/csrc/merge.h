@@ -8,7 +8,7 @@
 #include <vector>
 #include <unordered_map>
 
-// Hash of the pass-2 anchor tables (host-built: merge.cpp; device-built: dmerge.hip; probed by kernels.hip): the low 24 bits
+// Hash of the pass-2 anchor tables (host-built: merge.cpp; device-built: dmerge.hip; probed by pass2.hip): the low 24 bits
 // of the 16-mer times a 24-bit multiplier, plus the 16-mer's top byte left where it is (bits 24..31: inside the slot index
 // of every table size).  On the device that is one v_and_b32 shared by both hashes of a window and one v_mad_u32_u24 each.
 // The earlier form, mul24(V ^ (V >> s_i), m_i), took three instructions per hash (the probe kernel is VALU-bound) and folds
@@ -29,7 +29,6 @@ CRASS_HD static inline uint32_t ak_hash(uint32_t v, uint32_t m)
 
 namespace crass {
 
-void build_comp_table(unsigned char tab[128]);                 // SeqUtils.cpp:50-59
 std::string reverse_complement(const std::string &s);          // SeqUtils.cpp:61-87
 
 // StringCheck (StringCheck.h:52-71, StringCheck.cpp:46-81): first token is 2, discovery order.
@@ -135,11 +134,11 @@ struct HostAutomaton {
 void build_automaton(HostAutomaton &a, const StringArena &patterns);
 
 // pass-2 anchor keys: every 16-mer starting at offset 0..7 of an ACGT-only pattern, packed like
-// the reads (base i in bits 2i..2i+1), in a two-choice cuckoo table (see kernels.hip).
+// the reads (base i in bits 2i..2i+1), in a two-choice cuckoo table (see pass2.hip).
 struct HostAnchors {
     bool ok = false;                    // false: some pattern is shorter than 23 or the table would not fit
     uint32_t log_size = 0, m1 = 0, m2 = 0, n_keys = 0;
-    uint32_t mode = 0;                  // 0: exact 32-bit keys; 1: buckets of two 16-bit fingerprints (see kernels.hip)
+    uint32_t mode = 0;                  // 0: exact 32-bit keys; 1: buckets of two 16-bit fingerprints (see pass2.hip)
     std::vector<uint32_t> table;
 };
 void build_anchors(HostAnchors &k, const StringArena &patterns);

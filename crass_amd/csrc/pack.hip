@@ -18,6 +18,7 @@
 //      without exception reads never enter that loop.
 #include "pack_launch.h"
 #include "devmem.h"
+#include "comp_table.h"
 #include <algorithm>
 
 namespace crass {
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void k_gather_exc_text(const uint8_t *text, ui
 static constexpr int kFetchThreads = 256;
 static constexpr uint32_t kFetchTileBytes = 16 * kFetchThreads;
 
-__constant__ unsigned char c_fcomp[128];      // reverseComplement table (merge.cpp build_comp_table; kernels.hip keeps its own copy)
+static __constant__ CompTable c_fcomp = make_comp_table();      // reverseComplement table (comp_table.h)
 
 // the 16 codes of a read from base j on (j < 0 or beyond the read: codes of no meaning); W: the read's nw words
 static __device__ __forceinline__ uint32_t ft_window(const uint32_t *W, int32_t j, int32_t nw)
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(kFetchThreads) void k_fetch_text(const FetchJob J)
 #pragma unroll
             for (int t = 0; t < 16; t++) {
                 if (t < t0 || t >= t1) continue;
-                const uint32_t by = rc ? (uint32_t)c_fcomp[src[L - 1 - j0 - t] & 127] : (uint32_t)src[j0 + t];
+                const uint32_t by = rc ? (uint32_t)c_fcomp.v[src[L - 1 - j0 - t] & 127] : (uint32_t)src[j0 + t];
                 x[t >> 2] |= by << (8 * (t & 3));
             }
         }
@@ -274,11 +275,6 @@ hipError_t launch_fetch_text(const FetchJob &J, hipStream_t st)
     if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_fetch_text, dim3((unsigned)tiles), dim3(kFetchThreads), 0, st, J);
     return hipGetLastError();
-}
-
-hipError_t upload_fetch_comp_table(const unsigned char *tab128)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(c_fcomp), tab128, 128);
 }
 
 hipError_t launch_pack_text(const PackJob &J, hipStream_t st)

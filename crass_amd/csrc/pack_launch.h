@@ -42,7 +42,5 @@ struct FetchJob {
     uint8_t *out;
 };
 hipError_t launch_fetch_text(const FetchJob &J, hipStream_t st);
-// the reverse-complement table of merge.cpp (build_comp_table) for k_fetch_text's exception reads, on the current device
-hipError_t upload_fetch_comp_table(const unsigned char *tab128);
 
 } // namespace crass
