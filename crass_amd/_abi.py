@@ -85,6 +85,11 @@ class Text(C.Structure):
     _fields_ = [("n", C.c_uint64), ("chars", u8p), ("off", u64p)]
 
 
+class FastxLayoutC(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("format", C.c_int32), ("decline_reason", C.c_int32), ("decline_pos", C.c_uint64),
+                ("max_len", C.c_uint32), ("rec_pos", u64p), ("seq_off", u64p)]
+
+
 class Fastx(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("seq", u8p), ("seq_off", u64p), ("name", u8p), ("name_off", u64p),
                 ("comment", u8p), ("comment_off", u64p), ("has_comment", u8p), ("qual", u8p), ("qual_off", u64p),
@@ -162,6 +167,14 @@ SYMBOLS = {
     "crass_hip_attach_device_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]),
     "crass_hip_last_pack_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_get_packed": (C.c_int, [C.c_void_p, C.POINTER(Packed)]),
+    "crass_fastx_scan_host": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(FastxLayoutC)]),
+    "crass_fastx_layout_free": (None, [C.POINTER(FastxLayoutC)]),
+    "crass_hip_load_fastx_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(FastxLayoutC)]),
+    "crass_hip_attach_device_fastx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(FastxLayoutC)]),
+    "crass_hip_set_header_ids": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "crass_fastx_header_ids": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fastx_tile_bytes": (C.c_uint32, []),
+    "crass_hip_last_scan_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
     "crass_hip_fetch_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fetch_record_text": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Text)]),

@@ -9,6 +9,7 @@
 #include "engine_internal.h"
 #include "merge.h"
 #include "pack_launch.h"
+#include "fastx_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -257,6 +258,13 @@ struct crass_hip_ctx {
     DevBuf<uint64_t> t_off; DevBuf<uint8_t> t_dev[2]; PinBuf<uint8_t> t_pin[2];
     hipEvent_t ev_t_copy[2] = {nullptr, nullptr}, ev_t_pack[2] = {nullptr, nullptr}, ev_t_time[2] = {nullptr, nullptr};
     float last_pack_ms = 0;                  // HIP-event time of the last call's pack kernels (stage timing >= 1, else 0)
+    // crass_hip_load_fastx_bytes / crass_hip_attach_device_fastx (fastx_scan.hip): the raw bytes of a host file, the tile arrays,
+    // the totals ([0..4), then the verdict word), the reads' text and the two per-record arrays — all given back before the call
+    // returns; the pinned copies crass_fastx_layout points at stay until the next such call or destroy
+    DevBuf<uint8_t> x_raw, x_text; DevBuf<FxTile> x_tiles; DevBuf<FxBase> x_base; DevBuf<uint64_t> x_tot, x_rec_pos, x_seq_off;
+    PinBuf<uint64_t> x_h_tot, x_h_rec_pos, x_h_seq_off;
+    hipEvent_t ev_x_time[2] = {nullptr, nullptr};
+    float last_scan_ms = 0;                  // HIP-event time of the last call's scan kernels (stage timing >= 1, else 0)
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
     // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
     // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
@@ -862,6 +870,9 @@ void crass_hip_destroy(crass_hip_ctx *c)
     c->r_packed.release(); c->r_word_off.release(); c->r_lengths.release(); c->r_header_id.release();
     c->r_exc_mask.release(); c->r_exc_read.release(); c->r_exc_off.release(); c->r_exc_bytes.release();
     c->t_off.release();
+    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release(); c->x_rec_pos.release(); c->x_seq_off.release();
+    c->x_h_tot.release(); c->x_h_rec_pos.release(); c->x_h_seq_off.release();
+    for (auto &e : c->ev_x_time) if (e) (void)hipEventDestroy(e);
     c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
     c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
     for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
@@ -1303,6 +1314,158 @@ int crass_hip_attach_device_text(crass_hip_ctx *c, const uint8_t *d_seqs, const 
 }
 
 float crass_hip_last_pack_ms(const crass_hip_ctx *c) { return c ? c->last_pack_ms : 0.0f; }
+
+// ---- the raw bytes of a FASTA / FASTQ file in, parsed on the device (fastx_scan.hip) ----
+// h_bytes (host) or d_bytes (device).  Accepted: the state is that of crass_hip_load_text on the reads' text; declined: no reads.
+static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8_t *d_bytes, uint64_t n, int pad_uniform,
+                           uint64_t read_index_base, crass_fastx_layout *out)
+{
+    if (out) memset(out, 0, sizeof(*out));
+    if (!c || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
+    if (n && !h_bytes && !d_bytes) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    reset_results(c);
+    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    c->last_scan_ms = 0; c->last_pack_ms = 0;
+    auto decline = [&](int32_t format, uint64_t pos, int32_t reason) {
+        if (out) { out->format = format; out->decline_pos = pos; out->decline_reason = reason; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    if (n == 0) return decline(0, 0, FX_EMPTY);
+    uint8_t b0 = 0;
+    if (h_bytes) b0 = h_bytes[0];
+    else HIPCHK(c, hipMemcpy(&b0, d_bytes, 1, hipMemcpyDeviceToHost));
+    if (!fx_is_hdr_char(b0)) return decline(0, 0, FX_FIRST_BYTE);
+    if (h_bytes) {
+        // up through the two pinned staging buffers of crass_hip_load_text, into one device buffer; bytes that are already pinned
+        // are copied from where they are
+        HIPCHK(c, c->x_raw.ensure(n + 16));
+        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, 1), n);
+        hipPointerAttribute_t pa{};
+        const bool src_pinned = hipPointerGetAttributes(&pa, h_bytes) == hipSuccess && pa.type == hipMemoryTypeHost;
+        (void)hipGetLastError();                        // (pageable memory is reported as an invalid value: not an error of ours)
+        for (int k = 0; k < 2; k++) if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
+        int b = 0;
+        uint64_t k = 0;
+        for (uint64_t at = 0; at < n; at += cap, k++) {
+            b = (int)(k & 1);
+            const uint64_t bytes = std::min<uint64_t>(cap, n - at);
+            const uint8_t *from = h_bytes + at;
+            if (!src_pinned) {
+                HIPCHK(c, c->t_pin[b].ensure(cap));
+                if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
+                memcpy(c->t_pin[b].p, from, bytes);
+                from = c->t_pin[b].p;
+            }
+            HIPCHK(c, hipMemcpyAsync(c->x_raw.p + at, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
+            HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
+        }
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));      // (the last copy: the copy stream runs them in order)
+        d_bytes = c->x_raw.p;
+    }
+    FxJob J{};
+    J.bytes = d_bytes; J.n = n; J.lead = (uint32_t)((uintptr_t)d_bytes & 15u); J.format = b0;
+    J.n_tiles = fastx_n_tiles(d_bytes, n);
+    if (J.n_tiles > 0x7FFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (beyond 8 TB)
+    HIPCHK(c, c->x_tiles.ensure(J.n_tiles)); HIPCHK(c, c->x_base.ensure(J.n_tiles));
+    HIPCHK(c, c->x_tot.ensure(8)); HIPCHK(c, c->x_h_tot.ensure(8));
+    J.tiles = c->x_tiles.p; J.base = c->x_base.p; J.tot = c->x_tot.p;
+    J.verdict = reinterpret_cast<unsigned long long *>(c->x_tot.p + 4);
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_x_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_x_time[0], c->stream));
+    }
+    HIPCHK(c, launch_fx_summary(J, c->stream));
+    HIPCHK(c, launch_fx_tile_scan(J, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p, c->x_tot.p, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the record count sizes the next kernel's arrays)
+    J.n_lines = c->x_h_tot.p[0]; J.n_reads = c->x_h_tot.p[1];
+    const uint64_t nr = J.n_reads, total_seq = c->x_h_tot.p[2];
+    J.text_cap = total_seq;
+    HIPCHK(c, c->x_text.ensure(total_seq + 32));
+    HIPCHK(c, c->x_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_seq_off.ensure(nr + 1));
+    HIPCHK(c, c->x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_h_seq_off.ensure(nr + 1));
+    J.text = c->x_text.p; J.rec_pos = c->x_rec_pos.p; J.seq_off = c->x_seq_off.p;
+    HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
+    HIPCHK(c, launch_fx_emit(J, c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_x_time[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p + 4, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
+    if (nr) {
+        HIPCHK(c, hipMemcpyAsync(c->x_h_rec_pos.p, c->x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->x_h_seq_off.p, c->x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x_time[0], c->ev_x_time[1]));
+        c->last_scan_ms = ms;
+    }
+    const uint64_t verdict = c->x_h_tot.p[4];
+    if (verdict != kFxNoOffence) return decline(b0, verdict >> 8, (int32_t)(verdict & 0xFF));
+    if (nr == 0 || c->x_h_tot.p[3] != (b0 == 0x40 ? total_seq : 0)) return CRASS_ERR_STATE;      // (never expected: an accepted input has a record and as many quality as sequence bytes)
+    uint64_t *rec_pos = c->x_h_rec_pos.p, *seq_off = c->x_h_seq_off.p;
+    rec_pos[nr] = n; seq_off[nr] = total_seq;
+    uint64_t max_len = 0;
+    for (uint64_t r = 0; r < nr; r++) {
+        const uint64_t l = seq_off[r + 1] - seq_off[r];
+        if (l > CRASS_HIP_MAX_READ_LEN) return decline(b0, rec_pos[r], FX_READ_TOO_LONG);
+        max_len = std::max(max_len, l);
+    }
+    const int s = load_text_impl(c, nullptr, c->x_text.p, seq_off, nr, pad_uniform, nullptr, read_index_base);
+    if (s) return s;
+    if (out) { out->n_reads = nr; out->format = b0; out->max_len = (uint32_t)max_len; out->rec_pos = rec_pos; out->seq_off = seq_off; }
+    return CRASS_OK;
+}
+
+static int load_fastx_common(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8_t *d_bytes, uint64_t n, int pad_uniform,
+                             uint64_t read_index_base, crass_fastx_layout *out)
+{
+    const int s = load_fastx_impl(c, h_bytes, d_bytes, n, pad_uniform, read_index_base, out);
+    if (c) {
+        // the scratch goes back on every way out: the raw copy, the reads' text, the tile and per-record arrays, and what
+        // crass_hip_load_text's own part needed (load_text_common)
+        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
+        c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
+        c->x_rec_pos.release(); c->x_seq_off.release();
+        c->t_off.release();
+        for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    }
+    return s;
+}
+
+int crass_hip_load_fastx_bytes(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                               crass_fastx_layout *out)
+{
+    return load_fastx_common(c, bytes, nullptr, n_bytes, pad_uniform, read_index_base, out);
+}
+
+int crass_hip_attach_device_fastx(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                                  crass_fastx_layout *out)
+{
+    return load_fastx_common(c, nullptr, d_bytes, n_bytes, pad_uniform, read_index_base, out);
+}
+
+uint32_t crass_hip_fastx_tile_bytes(void) { return fastx_tile_bytes(); }
+float crass_hip_last_scan_ms(const crass_hip_ctx *c) { return c ? c->last_scan_ms : 0.0f; }
+
+int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    if (!c->have_reads) return CRASS_ERR_STATE;
+    (void)hipSetDevice(c->device);
+    const uint64_t n_reads = c->cnt.n_reads, n_exc = c->cnt.n_exceptions, bytes_dev = c->cnt.bytes_reads_device;
+    reset_results(c);                                   // (pass 1's found flags are keyed by header id: earlier results are void)
+    c->cnt.n_reads = n_reads; c->cnt.n_exceptions = n_exc; c->cnt.bytes_reads_device = bytes_dev;
+    const uint64_t n = c->R.n_reads;
+    if (header_id && n) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (nothing may still read the array this replaces)
+        HIPCHK(c, c->r_header_id.ensure(n));
+        HIPCHK(c, hipMemcpy(c->r_header_id.p, header_id, n * 8, hipMemcpyHostToDevice));
+        c->R.header_id = c->r_header_id.p;
+    } else c->R.header_id = nullptr;
+    return CRASS_OK;
+}
 
 int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)
 {

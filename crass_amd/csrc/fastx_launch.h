@@ -1,0 +1,51 @@
+// fastx_launch.h — the device record scan's job description and launch wrappers (fastx_scan.hip), for the engine.  Not part
+// of the public ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "fastx_scan.h"
+
+namespace crass {
+
+// Positions are counted twice: FILE positions 0 .. n (64-bit), and positions in "aligned space", which starts at the 16-byte
+// aligned address at or below the bytes: aligned position = lead + file position, lead = address of byte 0 modulo 16.  A tile is
+// kFxTileBytes of aligned space, so every lane's vector is an aligned 16-byte load whatever the bytes' own alignment.
+
+// what a tile knows about itself without its neighbours (k_fx_summary)
+struct FxTile {
+    uint32_t n_ls;          // line starts in the tile
+    uint32_t lls;           // the last of them: ((offset in the tile + 1) << 1) | (its first byte is '>'); 0: the tile starts no line
+    uint32_t lead_g;        // bytes 33..126 in front of the tile's first line start (the tail of a line of an earlier tile)
+    uint32_t n_hdr;         // FASTA: line starts whose byte is '>'
+    uint32_t c01, c23;      // bytes 33..126 in the lines that start in the tile; FASTA: c0 = those of sequence lines;
+                            // FASTQ: c_r = those of the lines whose index AMONG THE TILE'S OWN is r modulo 4 (16 bits each)
+};
+// what the scan over the tiles adds (k_fx_tile_scan): everything in front of the tile
+struct FxBase {
+    uint64_t ls_before;     // line starts = index of the first line that starts in the tile
+    uint64_t carry_ls;      // file position of the last of them (the line the tile's first bytes belong to)
+    uint64_t rec_before, seq_before, qual_before;      // records, sequence bytes, quality bytes (FASTQ)
+    uint32_t carry_kind;    // FxKind of that line
+    uint32_t pad;
+};
+
+struct FxJob {
+    const uint8_t *bytes;   // device pointer, any alignment
+    uint64_t n;             // > 0
+    uint32_t lead;          // address of bytes modulo 16
+    int32_t format;         // '>' | '@' (byte 0)
+    uint64_t n_tiles;
+    FxTile *tiles; FxBase *base;
+    uint64_t *tot;          // [4] lines, records, sequence bytes, quality bytes (k_fx_tile_scan)
+    // k_fx_emit
+    uint64_t n_lines, n_reads, text_cap;
+    uint8_t *text;          // [text_cap] the reads' bytes back to back (16-byte aligned)
+    uint64_t *rec_pos, *seq_off;      // [n_reads]
+    unsigned long long *verdict;      // the smallest fx_offence, kFxNoOffence before the launch
+};
+uint32_t fastx_tile_bytes();
+uint64_t fastx_n_tiles(const uint8_t *bytes, uint64_t n);
+hipError_t launch_fx_summary(const FxJob &J, hipStream_t st);
+hipError_t launch_fx_tile_scan(const FxJob &J, hipStream_t st);
+hipError_t launch_fx_emit(const FxJob &J, hipStream_t st);
+
+} // namespace crass

@@ -1,0 +1,115 @@
+// fastx_scan.cpp — the record scan of fastx_scan.h on the host, one byte after the other: the restatement the device scan
+// (fastx_scan.hip) is tested against, and the header ids of a scanned file.  Host-only C++17 that any compiler builds
+// (tools/sanitize).
+#include "../../include/crass_hip.h"
+#include "fastx_scan.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string_view>
+#include <unordered_map>
+#include <vector>
+
+namespace crass {
+
+int fastx_scan_serial(const uint8_t *bytes, uint64_t n, FxHostScan *out)
+{
+    *out = FxHostScan();
+    auto decline = [&](uint64_t pos, int32_t reason) { out->reason = reason; out->decline_pos = pos; out->n_reads = 0; out->max_len = 0; return CRASS_ERR_UNSUPPORTED; };
+    if (n == 0) return decline(0, FX_EMPTY);
+    if (!fx_is_hdr_char(bytes[0])) return decline(0, FX_FIRST_BYTE);
+    out->format = bytes[0];
+    const bool fastq = bytes[0] == 0x40;
+    uint64_t n_lines = 0;
+    if (fastq) {
+        for (uint64_t i = 0; i < n; i++) n_lines += fx_is_nl(bytes[i]) ? 1 : 0;
+        if (!fx_is_nl(bytes[n - 1])) n_lines++;
+    }
+    const uint64_t first_partial = n_lines & ~3ull;      // FASTQ: index of the first line of an incomplete record
+    std::vector<uint64_t> rec_pos, seq_off;
+    try {
+        uint64_t seq = 0, qual = 0, idx = 0, max_len = 0;
+        uint32_t kind = FX_QUAL;                          // (FASTQ: the kind of the line before line 0)
+        for (uint64_t p = 0; p < n; idx++) {
+            uint64_t e = p;
+            while (e < n && !fx_is_nl(bytes[e])) e++;     // the line: [p, e), its '\n' (if any) at e
+            uint64_t off = kFxNoOffence;
+            auto offend = [&](uint32_t reason) { const uint64_t o = fx_offence(p, reason); if (o < off) off = o; };
+            kind = fastq ? (kind + 1) & 3u : (bytes[p] == 0x3E ? FX_HEADER : FX_SEQ);
+            uint64_t graph = 0;
+            bool forbidden = false, del = false;
+            for (uint64_t i = p; i < e; i++) { graph += fx_is_seq_byte(bytes[i]) ? 1 : 0; forbidden |= fx_is_forbidden(bytes[i]); del |= fx_is_del(bytes[i]); }
+            if (kind == FX_HEADER) {
+                if (fastq && (n_lines & 3) && idx == first_partial) offend(FX_LINE_COUNT);
+                if (fastq && bytes[p] != 0x40) offend(FX_FQ_HEADER);
+                if (!fastq && p == n - 1) offend(FX_LONE_HEADER);
+                if (!rec_pos.empty()) max_len = std::max<uint64_t>(max_len, seq - seq_off.back());
+                rec_pos.push_back(p); seq_off.push_back(seq);
+            } else if (kind == FX_SEQ) {
+                if (forbidden) offend(FX_SEQ_CHAR);
+                seq += graph;
+            } else if (kind == FX_PLUS) {
+                if (bytes[p] != 0x2B) offend(FX_FQ_PLUS);
+            } else {
+                if (del) offend(FX_QUAL_DEL);
+                qual += graph;
+                if (seq > qual) offend(FX_QUAL_SHORT);
+                if (seq < qual) offend(FX_QUAL_LONG);
+            }
+            if (off != kFxNoOffence) return decline(off >> 8, (int32_t)(off & 0xFF));
+            p = e + 1;
+        }
+        max_len = std::max<uint64_t>(max_len, seq - seq_off.back());      // (byte 0 starts a header line: there is a record)
+        rec_pos.push_back(n); seq_off.push_back(seq);
+        out->n_reads = rec_pos.size() - 1;
+        out->max_len = (uint32_t)std::min<uint64_t>(max_len, 0xFFFFFFFFull);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    const size_t bytes_arr = rec_pos.size() * sizeof(uint64_t);
+    out->rec_pos = (uint64_t *)malloc(bytes_arr); out->seq_off = (uint64_t *)malloc(bytes_arr);
+    if (!out->rec_pos || !out->seq_off) { free(out->rec_pos); free(out->seq_off); *out = FxHostScan(); return CRASS_ERR_OOM; }
+    memcpy(out->rec_pos, rec_pos.data(), bytes_arr); memcpy(out->seq_off, seq_off.data(), bytes_arr);
+    return CRASS_OK;
+}
+
+} // namespace crass
+
+extern "C" {
+
+int crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_layout *out)
+{
+    if (!out || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    crass::FxHostScan h;
+    const int s = crass::fastx_scan_serial(bytes, n_bytes, &h);
+    out->n_reads = h.n_reads; out->format = h.format; out->decline_reason = h.reason; out->decline_pos = h.decline_pos; out->max_len = h.max_len;
+    out->rec_pos = h.rec_pos; out->seq_off = h.seq_off;
+    return s;
+}
+
+void crass_fastx_layout_free(crass_fastx_layout *l)
+{
+    if (!l) return;
+    free((void *)l->rec_pos); free((void *)l->seq_off);
+    l->rec_pos = nullptr; l->seq_off = nullptr;
+}
+
+int crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, uint64_t *header_id_out)
+{
+    if (n_reads && (!bytes || !rec_pos || !header_id_out)) return CRASS_ERR_INVALID_ARG;
+    auto is_space = [](uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+    try {
+        std::unordered_map<std::string_view, uint64_t> first;
+        first.reserve(n_reads * 2);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            if (rec_pos[r] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+            uint64_t a = rec_pos[r] + 1, b = a;
+            while (b < n_bytes && !is_space(bytes[b])) b++;      // the name: up to the first isspace() byte, as kseq cuts it
+            header_id_out[r] = first.emplace(std::string_view((const char *)bytes + a, b - a), r).first->second;
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+} // extern "C"

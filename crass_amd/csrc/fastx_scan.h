@@ -1,0 +1,84 @@
+// fastx_scan.h — what the host restatement (fastx_scan.cpp), the device scan (fastx_scan.hip) and the engine (engine.cpp)
+// share about finding the records of a FASTA / FASTQ file by LINES: the byte classes, the line kinds, the decline reasons and
+// the order in which offences are reported.  Plain C++ with CRASS_HD (pack_text.h), so the rule exists once for host and
+// device.  Not part of the public ABI (the reasons' VALUES are: include/crass_hip.h names them).
+//
+// kseq (kseq.cpp:171-226) is a byte-stream parser: '>', '@' or '+' ANYWHERE in a sequence ends it.  A scan by lines agrees with
+// it on the regular class only, and declines everything else:
+//   regular FASTA   byte 0 is '>'; a line whose first byte is '>' is a header line; every other line is a sequence line and
+//                   holds none of '>' '@' '+'; the file does not end with a '>' that is the first byte of its line.
+//   regular FASTQ   byte 0 is '@'; the number of lines is a multiple of 4; line 4k starts with '@', line 4k+1 holds none of
+//                   '>' '@' '+', line 4k+2 starts with '+', line 4k+3 holds no byte 127 and as many bytes in 33..126 as line 4k+1.
+// Lines are the pieces between '\n' bytes (the last may lack its '\n'; an empty piece after a final '\n' is no line).  A read is
+// the bytes 33..126 of its record's sequence lines.
+//
+// The verdict of a declined input is the SMALLEST (position of the line, reason) pair over all offences of all lines: both
+// scans evaluate every offence of a line, so the first offending line and, within it, the smallest reason value win.
+#pragma once
+#include <stdint.h>
+#include "pack_text.h"
+
+namespace crass {
+
+// decline reasons (crass_fastx_layout.decline_reason); 0: accepted
+enum FxReason : int32_t {
+    FX_OK = 0,
+    FX_EMPTY = 1,            // n_bytes == 0: no format to report
+    FX_FIRST_BYTE = 2,       // byte 0 is neither '>' nor '@' (junk in front)
+    FX_LINE_COUNT = 3,       // FASTQ: the lines are no multiple of 4; position: the first line of the incomplete record
+    FX_FQ_HEADER = 4,        // FASTQ: line 4k does not start with '@' (a '>' record, a trailing blank line, multi-line records)
+    FX_SEQ_CHAR = 5,         // '>' '@' or '+' in a sequence line (FASTA: a line that does not start with '>'; FASTQ: line 4k+1)
+    FX_FQ_PLUS = 6,          // FASTQ: line 4k+2 does not start with '+'
+    FX_QUAL_DEL = 7,         // FASTQ: byte 127 in a quality line (kseq counts it as a quality byte)
+    FX_QUAL_SHORT = 8,       // FASTQ: the quality line holds fewer bytes in 33..126 than the sequence line
+    FX_QUAL_LONG = 9,        // FASTQ: ... more
+    FX_LONE_HEADER = 10,     // FASTA: the last byte is a '>' that starts its line (kseq finds no record there)
+    FX_READ_TOO_LONG = 11    // accepted by the scan, refused by the layout: a read beyond CRASS_HIP_MAX_READ_LEN (the load calls only)
+};
+
+// the kind of a line.  FASTA: header or sequence; FASTQ: the line's index modulo 4 — so 0 is a header and 1 a sequence line in both
+enum FxKind : uint32_t { FX_HEADER = 0, FX_SEQ = 1, FX_PLUS = 2, FX_QUAL = 3 };
+
+// ---- byte classes ----
+CRASS_HD inline bool fx_is_nl(uint8_t b) { return b == 0x0A; }
+CRASS_HD inline bool fx_is_hdr_char(uint8_t b) { return b == 0x3E || b == 0x40; }                  // '>' '@'
+CRASS_HD inline bool fx_is_forbidden(uint8_t b) { return b == 0x3E || b == 0x40 || b == 0x2B; }      // '>' '@' '+': ends kseq's sequence
+CRASS_HD inline bool fx_is_seq_byte(uint8_t b) { return b >= 33 && b <= 126; }                       // isgraph(): what kseq keeps
+CRASS_HD inline bool fx_is_del(uint8_t b) { return b == 127; }
+
+// the same classes for four bytes at once (byte 0 = bits 0..7): bit i of a result says byte i is in the class
+struct FxClass4 { uint32_t nl, gt, at, plus, del, graph; };
+CRASS_HD inline uint32_t fx_gather4(uint32_t high_bits)      // bits 7, 15, 23, 31 -> bits 0 .. 3
+{
+    return ((high_bits >> 7) * 0x10204080u) >> 28;           // (the partial products meet in no bit: pack_code4)
+}
+CRASS_HD inline uint32_t fx_eq4(uint32_t v, uint32_t c)     // bytes equal to c, exact for all 256 values
+{
+    const uint32_t z = v ^ (c * 0x01010101u);
+    const uint32_t nz = (((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z) & 0x80808080u;
+    return fx_gather4(nz ^ 0x80808080u);
+}
+CRASS_HD inline FxClass4 fx_class4(uint32_t v)
+{
+    FxClass4 c;
+    c.nl = fx_eq4(v, 0x0Au); c.gt = fx_eq4(v, 0x3Eu); c.at = fx_eq4(v, 0x40u); c.plus = fx_eq4(v, 0x2Bu); c.del = fx_eq4(v, 0x7Fu);
+    const uint32_t low = v & 0x7F7F7F7Fu;
+    const uint32_t ge33 = (low + 0x5F5F5F5Fu) & 0x80808080u;               // low 7 bits >= 33 (at most 127 + 95: no carry into the next byte)
+    const uint32_t is127 = (low + 0x01010101u) & 0x80808080u;              // low 7 bits == 127
+    c.graph = fx_gather4(ge33 & ~is127 & ~(v & 0x80808080u));
+    return c;
+}
+
+// one offence as a sortable word: the smallest over all offences is the verdict
+CRASS_HD inline uint64_t fx_offence(uint64_t line_pos, uint32_t reason) { return (line_pos << 8) | reason; }
+static const uint64_t kFxNoOffence = ~0ull;
+
+// ---- the serial host restatement of the whole scan (fastx_scan.cpp) ----
+// rec_pos / seq_off: malloc'd arrays of n_reads + 1 entries (free()), nullptr when the input is declined
+struct FxHostScan {
+    uint64_t n_reads = 0; int32_t format = 0, reason = 0; uint64_t decline_pos = 0; uint32_t max_len = 0;
+    uint64_t *rec_pos = nullptr, *seq_off = nullptr;
+};
+int fastx_scan_serial(const uint8_t *bytes, uint64_t n_bytes, FxHostScan *out);      // CRASS_OK, CRASS_ERR_UNSUPPORTED (declined), CRASS_ERR_OOM
+
+} // namespace crass

@@ -1,0 +1,337 @@
+// fastx_scan.hip — the record scan of fastx_scan.h on the device: the raw bytes of a FASTA / FASTQ file -> the reads' bytes back
+// to back (the text pack.hip packs), the position of every record's header character, the reads' offsets in the text, and one
+// verdict word.  Raw bytes -> per-tile summaries -> one scan over the tiles -> emit: TWO passes over the raw bytes.
+//
+// What a byte means depends on the line it is in (header, sequence, '+', quality), and what a line is depends on everything in
+// front of it: FASTA — whether its first byte is '>'; FASTQ — its index modulo 4.  Both are carried as "the last line start in
+// front of here" (a tile's function on that is a constant, the tile's own last line start, or the identity, a tile that starts no
+// line) and "line starts so far" (a sum), so they scan associatively over tiles:
+//   k_fx_summary    one block per tile of kFxTileBytes, a lane one aligned 16-byte vector: line starts, the last one, and the
+//                   bytes 33..126 of the tile sorted by what they could turn out to be (FxTile).  24 bytes per tile.
+//   k_fx_tile_scan  one block walks the tiles, 1 024 per step: line index, carried line, records / sequence / quality bytes in
+//                   front of every tile (FxBase, 48 bytes per tile) and the four totals.  64-bit sums (files beyond 4 GB), which
+//                   is why this is not the 32-bit look-back of sinks.hip.
+//   k_fx_emit       the tile again, now with its base: sequence bytes go through LDS to the text in aligned 16-byte stores,
+//                   every header line start writes rec_pos / seq_off, every offence of fastx_scan.h is min-ed into the verdict.
+// Temporary HBM per input byte: 72 / 4096 for the tile arrays, at most 1 for the text, 16 per record for the two arrays.
+// No byte beyond the input is read: the first and the last vector are loaded byte by byte where they are not whole.
+#include "fastx_launch.h"
+#include "devmem.h"
+
+namespace crass {
+
+static constexpr int kFxThreads = 256;
+static constexpr uint32_t kFxTileBytes = 16 * kFxThreads;
+static constexpr int kFxScanThreads = 1024;
+
+// a lane's vector: the bytes and, 16 bits each, what they are (bit j: byte j; invalid bytes are in no class)
+struct FxVec { uint32_t w[4]; uint32_t valid, nl, ls, gt, at, pl, del, gr; };
+
+static __device__ __forceinline__ void fx_load(const FxJob &J, uint64_t q0, FxVec &V)
+{
+    const uint64_t lead = J.lead, end = lead + J.n;      // the input in aligned space: [lead, end)
+    uint32_t valid = 0;
+    if (q0 + 16 > lead && q0 < end) {
+        const uint32_t lo = q0 < lead ? (uint32_t)(lead - q0) : 0u;
+        const uint32_t hi = end - q0 < 16 ? (uint32_t)(end - q0) : 16u;
+        valid = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+    }
+    const uint8_t *a = reinterpret_cast<const uint8_t *>((uintptr_t)J.bytes - (uintptr_t)lead + (uintptr_t)q0);      // 16-byte aligned
+    V.w[0] = V.w[1] = V.w[2] = V.w[3] = 0u;
+    if (valid == 0xFFFFu) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(a);
+        V.w[0] = v.x; V.w[1] = v.y; V.w[2] = v.z; V.w[3] = v.w;
+    } else if (valid) {                                  // (the input's first and last vector)
+#pragma unroll
+        for (int j = 0; j < 16; j++) if ((valid >> j) & 1u) V.w[j >> 2] |= (uint32_t)a[j] << (8 * (j & 3));
+    }
+    const FxClass4 c0 = fx_class4(V.w[0]), c1 = fx_class4(V.w[1]), c2 = fx_class4(V.w[2]), c3 = fx_class4(V.w[3]);
+    V.valid = valid;
+    V.nl = (c0.nl | (c1.nl << 4) | (c2.nl << 8) | (c3.nl << 12)) & valid;
+    V.gt = (c0.gt | (c1.gt << 4) | (c2.gt << 8) | (c3.gt << 12)) & valid;
+    V.at = (c0.at | (c1.at << 4) | (c2.at << 8) | (c3.at << 12)) & valid;
+    V.pl = (c0.plus | (c1.plus << 4) | (c2.plus << 8) | (c3.plus << 12)) & valid;
+    V.del = (c0.del | (c1.del << 4) | (c2.del << 8) | (c3.del << 12)) & valid;
+    V.gr = (c0.graph | (c1.graph << 4) | (c2.graph << 8) | (c3.graph << 12)) & valid;
+    // line starts: file position 0, and every valid byte behind a '\n' (the byte in front of the vector: the lane before, or —
+    // a wave's first lane — one byte load; it is inside the input)
+    uint32_t prev = (uint32_t)__shfl_up((int)(V.nl >> 15), 1);
+    if ((threadIdx.x & 63u) == 0) prev = (q0 > lead && q0 - 1 < end) ? (uint32_t)fx_is_nl(a[-1]) : 0u;
+    V.ls = (((V.nl << 1) | (prev & 1u)) & 0xFFFFu) & valid;
+    if (lead >= q0 && lead < q0 + 16) V.ls |= (1u << (uint32_t)(lead - q0)) & valid;
+}
+
+// exclusive prefix sum of v over the block's NW waves; *total: the block's sum.  s_w: NW words of LDS, free again on return
+template <int NW> static __device__ __forceinline__ uint32_t fx_scan_add(uint32_t v, uint32_t *s_w, uint32_t *total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, off); if (lane >= off) incl += y; }
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    uint32_t base = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < NW; k++) { const uint32_t s = s_w[k]; if (k < wv) base += s; all += s; }
+    __syncthreads();
+    *total = all;
+    return base + incl - v;
+}
+// the same with max: the largest v of the threads BEFORE this one (0: none); *total: the block's largest
+template <int NW> static __device__ __forceinline__ uint32_t fx_scan_max(uint32_t v, uint32_t *s_w, uint32_t *total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, off); if (lane >= off && y > incl) incl = y; }
+    if (lane == 63) s_w[wv] = incl;
+    uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
+    if (lane == 0) excl = 0u;
+    __syncthreads();
+    uint32_t all = 0;
+#pragma unroll
+    for (int k = 0; k < NW; k++) { const uint32_t s = s_w[k]; if (k < wv && s > excl) excl = s; if (s > all) all = s; }
+    __syncthreads();
+    *total = all;
+    return excl;
+}
+static __device__ __forceinline__ uint32_t fx_wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
+    return v;
+}
+
+// The lines of a vector in order: f(seg, started, j, kind) for the bytes `seg` of one line — the one that reaches in from the
+// left (started false, kind in_kind), then every line that starts in the vector (at bit j).  FASTQ: a line's kind is the one
+// before it plus one; FASTA: whether its first byte is '>'.
+template <class F> static __device__ __forceinline__ void fx_walk(const FxVec &V, bool fastq, uint32_t in_kind, F f)
+{
+    uint32_t rem = V.ls;
+    const uint32_t first = rem ? (uint32_t)__builtin_ctz(rem) : 16u;
+    const uint32_t seg0 = V.valid & ((1u << first) - 1u);
+    if (seg0) f(seg0, false, 0u, in_kind);
+    uint32_t kind = in_kind;
+    while (rem) {
+        const uint32_t j = (uint32_t)__builtin_ctz(rem);
+        rem &= rem - 1u;
+        const uint32_t nxt = rem ? (uint32_t)__builtin_ctz(rem) : 16u;
+        const uint32_t seg = V.valid & ((1u << nxt) - 1u) & ~((1u << j) - 1u);
+        kind = fastq ? (kind + 1u) & 3u : (((V.gt >> j) & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ);
+        f(seg, true, j, kind);
+    }
+}
+// a lane's last line start as a sortable code (FxTile::lls with the offset in the TILE); 0: none
+static __device__ __forceinline__ uint32_t fx_last_ls_code(const FxVec &V)
+{
+    if (!V.ls) return 0u;
+    const uint32_t j = 31u - (uint32_t)__builtin_clz(V.ls);
+    return ((16u * threadIdx.x + j + 1u) << 1) | ((V.gt >> j) & 1u);
+}
+
+__global__ __launch_bounds__(kFxThreads) void k_fx_summary(const FxJob J)
+{
+    __shared__ uint32_t s_w[kFxThreads / 64];
+    __shared__ uint32_t s_acc[6];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t q0 = (uint64_t)blockIdx.x * kFxTileBytes + 16u * tid;
+    const bool fastq = J.format == 0x40;
+    if (tid < 6) s_acc[tid] = 0u;                       // (the scans below synchronise before anybody adds)
+    FxVec V;
+    fx_load(J, q0, V);
+    uint32_t tot_ls, tot_code;
+    const uint32_t excl = fx_scan_add<kFxThreads / 64>((uint32_t)__builtin_popcount(V.ls), s_w, &tot_ls);
+    const uint32_t prev = fx_scan_max<kFxThreads / 64>(fx_last_ls_code(V), s_w, &tot_code);
+    // FASTQ: kinds are the lines' indices among the tile's own, modulo 4
+    const uint32_t in_kind = fastq ? (excl - 1u) & 3u : ((prev & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ);
+    uint32_t cp = 0, lead_g = 0, n_hdr = 0;             // cp: four 8-bit counts (a lane has 16 bytes)
+    {                                                   // (fx_walk's order, written out: its captures cost this kernel 12 bytes of scratch)
+        uint32_t rem = V.ls, kind = in_kind;
+        const uint32_t first = rem ? (uint32_t)__builtin_ctz(rem) : 16u;
+        const uint32_t g0 = (uint32_t)__builtin_popcount(V.gr & ((1u << first) - 1u));
+        if (prev == 0u) lead_g = g0;
+        else if (fastq) cp = g0 << (8u * kind);
+        else if (kind == FX_SEQ) cp = g0;
+        while (rem) {
+            const uint32_t j = (uint32_t)__builtin_ctz(rem);
+            rem &= rem - 1u;
+            const uint32_t nxt = rem ? (uint32_t)__builtin_ctz(rem) : 16u;
+            const uint32_t g = (uint32_t)__builtin_popcount(V.gr & ((1u << nxt) - 1u) & ~((1u << j) - 1u));
+            kind = fastq ? (kind + 1u) & 3u : (((V.gt >> j) & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ);
+            if (fastq) cp += g << (8u * kind);
+            else if (kind == FX_SEQ) cp += g;
+            else n_hdr++;
+        }
+    }
+    const uint32_t lo = fx_wave_sum(cp & 0x00FF00FFu), hi = fx_wave_sum((cp >> 8) & 0x00FF00FFu);      // (64 x 16 fits 16 bits)
+    lead_g = fx_wave_sum(lead_g); n_hdr = fx_wave_sum(n_hdr);
+    if ((tid & 63u) == 0) {
+        atomicAdd(&s_acc[0], lo & 0xFFFFu); atomicAdd(&s_acc[1], hi & 0xFFFFu); atomicAdd(&s_acc[2], lo >> 16); atomicAdd(&s_acc[3], hi >> 16);
+        atomicAdd(&s_acc[4], lead_g); atomicAdd(&s_acc[5], n_hdr);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        FxTile T;
+        T.n_ls = tot_ls; T.lls = tot_code; T.lead_g = s_acc[4]; T.n_hdr = s_acc[5];
+        T.c01 = s_acc[0] | (s_acc[1] << 16); T.c23 = s_acc[2] | (s_acc[3] << 16);      // (at most 4 096 each)
+        J.tiles[blockIdx.x] = T;
+    }
+}
+
+__global__ __launch_bounds__(kFxScanThreads) void k_fx_tile_scan(const FxJob J)
+{
+    __shared__ uint32_t s_w[kFxScanThreads / 64];
+    __shared__ uint64_t s_pos[kFxScanThreads];
+    __shared__ uint32_t s_lls[kFxScanThreads];
+    const uint32_t tid = threadIdx.x;
+    const bool fastq = J.format == 0x40;
+    uint64_t r_ls = 0, r_pos = 0, r_rec = 0, r_seq = 0, r_qual = 0;      // everything in front of this step's tiles (the same in every thread)
+    uint32_t r_kind = FX_HEADER;
+    for (uint64_t t0 = 0; t0 < J.n_tiles; t0 += kFxScanThreads) {
+        const uint64_t t = t0 + tid;
+        const bool have = t < J.n_tiles;
+        FxTile S{};
+        if (have) S = J.tiles[t];
+        s_pos[tid] = t * kFxTileBytes - J.lead + (S.lls >> 1) - 1u;      // file position of the tile's last line start
+        s_lls[tid] = S.lls;
+        uint32_t tot_ls, tot_code, tot_seq, tot_qual, tot_hdr;
+        const uint64_t ls_before = r_ls + fx_scan_add<kFxScanThreads / 64>(S.n_ls, s_w, &tot_ls);
+        const uint32_t prev = fx_scan_max<kFxScanThreads / 64>(S.lls ? tid + 1u : 0u, s_w, &tot_code);
+        const uint64_t carry_ls = prev ? s_pos[prev - 1] : r_pos;
+        const uint32_t fa_kind = prev ? ((s_lls[prev - 1] & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ) : r_kind;
+        const uint32_t carry_kind = fastq ? (uint32_t)(ls_before - 1u) & 3u : fa_kind;
+        const uint32_t c[4] = {S.c01 & 0xFFFFu, S.c01 >> 16, S.c23 & 0xFFFFu, S.c23 >> 16};
+        auto pick = [&](uint32_t r) { return r == 0 ? c[0] : r == 1 ? c[1] : r == 2 ? c[2] : c[3]; };
+        uint32_t seq, qual = 0, hdr;
+        if (fastq) {                                    // the tile's own line j is line ls_before + j of the file
+            seq = (carry_kind == FX_SEQ ? S.lead_g : 0u) + pick((uint32_t)(1u - ls_before) & 3u);
+            qual = (carry_kind == FX_QUAL ? S.lead_g : 0u) + pick((uint32_t)(3u - ls_before) & 3u);
+            const uint32_t j0 = (uint32_t)(0u - ls_before) & 3u;
+            hdr = S.n_ls > j0 ? (S.n_ls - j0 + 3u) / 4u : 0u;
+        } else {
+            seq = (carry_kind == FX_SEQ ? S.lead_g : 0u) + c[0];
+            hdr = S.n_hdr;
+        }
+        FxBase B;
+        B.ls_before = ls_before; B.carry_ls = carry_ls; B.carry_kind = carry_kind; B.pad = 0;
+        B.seq_before = r_seq + fx_scan_add<kFxScanThreads / 64>(seq, s_w, &tot_seq);
+        B.qual_before = r_qual + fx_scan_add<kFxScanThreads / 64>(qual, s_w, &tot_qual);
+        B.rec_before = r_rec + fx_scan_add<kFxScanThreads / 64>(hdr, s_w, &tot_hdr);
+        if (have) J.base[t] = B;
+        if (tot_code) { r_pos = s_pos[tot_code - 1]; r_kind = (s_lls[tot_code - 1] & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ; }
+        r_ls += tot_ls; r_seq += tot_seq; r_qual += tot_qual; r_rec += tot_hdr;
+        __syncthreads();                                // (s_pos / s_lls are written again)
+    }
+    if (tid == 0) { J.tot[0] = r_ls; J.tot[1] = r_rec; J.tot[2] = r_seq; J.tot[3] = r_qual; }
+}
+
+__global__ __launch_bounds__(kFxThreads) void k_fx_emit(const FxJob J)
+{
+    __shared__ uint32_t s_w[kFxThreads / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[kFxTileBytes + 32];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t q0 = (uint64_t)blockIdx.x * kFxTileBytes + 16u * tid;
+    const uint64_t p0 = q0 - J.lead;                    // file position of the vector's byte 0 (wraps in front of the input: those bytes are not valid)
+    const bool fastq = J.format == 0x40;
+    const FxBase B = J.base[blockIdx.x];
+    FxVec V;
+    fx_load(J, q0, V);
+    uint32_t tot_ls, tot_code, tot_sq, tot_h;
+    const uint32_t excl = fx_scan_add<kFxThreads / 64>((uint32_t)__builtin_popcount(V.ls), s_w, &tot_ls);
+    const uint32_t prev = fx_scan_max<kFxThreads / 64>(fx_last_ls_code(V), s_w, &tot_code);
+    // the line that reaches into this vector: one of the tile (prev) or the tile's carried one
+    const uint64_t in_pos = prev ? (uint64_t)blockIdx.x * kFxTileBytes - J.lead + (prev >> 1) - 1u : B.carry_ls;
+    const uint64_t in_idx = B.ls_before + excl - 1u;    // its index (wraps to -1 in front of line 0: no valid byte is there)
+    const uint32_t in_kind = fastq ? (uint32_t)in_idx & 3u : (prev ? ((prev & 1u) ? (uint32_t)FX_HEADER : (uint32_t)FX_SEQ) : B.carry_kind);
+    // 1. how many sequence bytes, quality bytes and records this lane has
+    uint32_t s_cnt = 0, q_cnt = 0, h_cnt = 0, seqmask = 0;
+    fx_walk(V, fastq, in_kind, [&](uint32_t seg, bool started, uint32_t, uint32_t kind) {
+        const uint32_t g = V.gr & seg;
+        if (kind == FX_SEQ) { s_cnt += (uint32_t)__builtin_popcount(g); seqmask |= g; }
+        else if (kind == FX_QUAL) q_cnt += (uint32_t)__builtin_popcount(g);
+        if (started && kind == FX_HEADER) h_cnt++;
+    });
+    const uint32_t sq = fx_scan_add<kFxThreads / 64>(s_cnt | (q_cnt << 16), s_w, &tot_sq);      // (a tile has at most 4 096 of either)
+    const uint32_t h_excl = fx_scan_add<kFxThreads / 64>(h_cnt, s_w, &tot_h);
+    // 2. records and offences
+    uint32_t s_run = sq & 0xFFFFu, q_run = sq >> 16, h_run = h_excl;
+    uint64_t gidx = in_idx;
+    uint64_t off = kFxNoOffence;
+    const uint64_t last_q = (uint64_t)J.lead + J.n - 1u;       // the input's last byte in aligned space
+    const uint32_t last_bit = (last_q >= q0 && last_q < q0 + 16) ? 1u << (uint32_t)(last_q - q0) : 0u;
+    uint64_t ls_pos = in_pos;
+    fx_walk(V, fastq, in_kind, [&](uint32_t seg, bool started, uint32_t j, uint32_t kind) {
+        auto offend = [&](uint32_t reason) { const uint64_t o = fx_offence(ls_pos, reason); if (o < off) off = o; };
+        if (started) {
+            ls_pos = p0 + j; gidx++;
+            if (kind == FX_HEADER) {
+                const uint64_t r = B.rec_before + h_run++;
+                if (r < J.n_reads) { J.rec_pos[r] = ls_pos; J.seq_off[r] = B.seq_before + s_run; }
+                if (fastq) {
+                    if ((J.n_lines & 3u) && gidx == (J.n_lines & ~3ull)) offend(FX_LINE_COUNT);
+                    if (!((V.at >> j) & 1u)) offend(FX_FQ_HEADER);
+                } else if (ls_pos == J.n - 1u) offend(FX_LONE_HEADER);
+            } else if (kind == FX_PLUS && !((V.pl >> j) & 1u)) offend(FX_FQ_PLUS);
+        }
+        if (kind == FX_SEQ) {
+            if ((V.gt | V.at | V.pl) & seg) offend(FX_SEQ_CHAR);
+            s_run += (uint32_t)__builtin_popcount(V.gr & seg);
+        } else if (kind == FX_QUAL) {
+            if (V.del & seg) offend(FX_QUAL_DEL);
+            q_run += (uint32_t)__builtin_popcount(V.gr & seg);
+            if ((V.nl | last_bit) & seg) {              // the line ends here: sequence and quality bytes so far must be as many
+                const uint64_t S = B.seq_before + s_run, Q = B.qual_before + q_run;
+                if (S > Q) offend(FX_QUAL_SHORT);
+                if (S < Q) offend(FX_QUAL_LONG);
+            }
+        }
+    });
+    if (off != kFxNoOffence) atomicMin(J.verdict, (unsigned long long)off);
+    // 3. the tile's sequence bytes: into LDS where they will lie relative to the text's 16-byte vectors, then out
+    const uint32_t shift = (uint32_t)(B.seq_before & 15u);
+    {
+        uint32_t o = shift + (sq & 0xFFFFu);
+#pragma unroll
+        for (int j = 0; j < 16; j++) if ((seqmask >> j) & 1u) { if (o < kFxTileBytes + 32u) s_out[o] = (uint8_t)(V.w[j >> 2] >> (8 * (j & 3))); o++; }
+    }
+    __syncthreads();
+    const uint32_t n_out = shift + (tot_sq & 0xFFFFu);  // LDS bytes [shift, n_out) are the tile's
+    const uint64_t g0 = B.seq_before - shift;           // text offset of LDS byte 0 (a multiple of 16)
+    for (uint32_t v = tid; 16u * v < n_out; v += kFxThreads) {
+        const uint32_t a = 16u * v, b = a + 16u;
+        if (a >= shift && b <= n_out && g0 + b <= J.text_cap) {
+            *reinterpret_cast<uint4 *>(J.text + g0 + a) = *reinterpret_cast<const uint4 *>(s_out + a);
+        } else {                                        // (the vector the tile shares with the one before or behind it)
+            for (uint32_t i = a > shift ? a : shift; i < b && i < n_out; i++) if (g0 + i < J.text_cap) J.text[g0 + i] = s_out[i];
+        }
+    }
+}
+
+uint32_t fastx_tile_bytes() { return kFxTileBytes; }
+
+uint64_t fastx_n_tiles(const uint8_t *bytes, uint64_t n)
+{
+    return (((uint64_t)((uintptr_t)bytes & 15u)) + n + kFxTileBytes - 1) / kFxTileBytes;
+}
+
+hipError_t launch_fx_summary(const FxJob &J, hipStream_t st)
+{
+    if (!J.n_tiles || J.n_tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_fx_summary, dim3((unsigned)J.n_tiles), dim3(kFxThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_fx_tile_scan(const FxJob &J, hipStream_t st)
+{
+    CRASS_LAUNCH(k_fx_tile_scan, dim3(1), dim3(kFxScanThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_fx_emit(const FxJob &J, hipStream_t st)
+{
+    if (!J.n_tiles || J.n_tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_fx_emit, dim3((unsigned)J.n_tiles), dim3(kFxThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+} // namespace crass

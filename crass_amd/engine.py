@@ -192,6 +192,63 @@ def pack_code4(four_bytes):
     return int(code), int(bad.value)
 
 
+class FastxLayout:
+    """What the record scan found in the raw bytes of a FASTA / FASTQ file (crass_fastx_layout), as numpy copies: n_reads, format
+    (b">" or b"@"; b"" when unknown), max_len, rec_pos / seq_off (uint64, n_reads + 1); a declined input has accepted False,
+    decline_reason / decline_pos and empty arrays."""
+
+    def __init__(self, v):
+        self.n_reads = int(v.n_reads)
+        self.format = bytes([v.format]) if v.format else b""
+        self.decline_reason, self.decline_pos = int(v.decline_reason), int(v.decline_pos)
+        self.accepted = self.decline_reason == 0
+        self.max_len = int(v.max_len)
+        have = bool(v.rec_pos) and bool(v.seq_off)
+        self.rec_pos = _np(v.rec_pos, self.n_reads + 1, np.uint64) if have else np.zeros(0, np.uint64)
+        self.seq_off = _np(v.seq_off, self.n_reads + 1, np.uint64) if have else np.zeros(0, np.uint64)
+
+
+class FastxDeclined(CrassError):
+    """The record scan declined the input (status 2): `layout` says why and where; the caller takes the host readers."""
+
+    def __init__(self, status, where, layout):
+        super().__init__(status, where)
+        self.layout = layout
+
+
+def _bytes_arg(buf):
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(buf), dtype=np.uint8)
+    return np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+
+
+def fastx_scan_host(buf):
+    """The record scan of the raw bytes of a FASTA / FASTQ file on the host (crass_fastx_scan_host; no GPU needed): a
+    FastxLayout, accepted or declined."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    v = _abi.FastxLayoutC()
+    st = lib.crass_fastx_scan_host(a.ctypes.data if len(a) else None, len(a), C.byref(v))
+    try:
+        if st not in (0, 2):
+            raise CrassError(st, "crass_fastx_scan_host")
+        return FastxLayout(v)
+    finally:
+        lib.crass_fastx_layout_free(C.byref(v))
+
+
+def fastx_header_ids(buf, rec_pos):
+    """header_id[r] = index of the first read with the same name, from the file's bytes and the records' positions
+    (crass_fastx_header_ids; host, names compared exactly).  rec_pos: n_reads + 1 entries as in a FastxLayout."""
+    a = _bytes_arg(buf)
+    rp = np.ascontiguousarray(rec_pos, dtype=np.uint64)
+    n = max(len(rp) - 1, 0)
+    out = np.zeros(n, np.uint64)
+    _chk(_abi.load().crass_fastx_header_ids(a.ctypes.data if len(a) else None, len(a), rp.ctypes.data, n, out.ctypes.data),
+         "crass_fastx_header_ids")
+    return out
+
+
 class FastxFile:
     """FASTA/FASTQ(.gz) records with kseq_read semantics (C++ reader, crass_read_fastx)."""
 
@@ -583,6 +640,44 @@ class SearchEngine:
     def last_pack_ms(self):
         """HIP-event milliseconds of the last load_text / attach_device_text call's pack kernels (stage timing >= 1, else 0)."""
         return float(self.lib.crass_hip_last_pack_ms(self.h))
+
+    def _fastx_result(self, st, v, where):
+        lay = FastxLayout(v)
+        if st == 2 and lay.decline_reason:
+            raise FastxDeclined(st, where, lay)
+        _chk(st, where)
+        self._keep = None
+        return lay
+
+    def load_fastx_bytes(self, buf, pad_uniform=2, read_index_base=0):
+        """The raw bytes of a FASTA / FASTQ file in host memory (bytes or a uint8 array); records found and reads packed on the
+        device (crass_hip_load_fastx_bytes).  Returns a FastxLayout; raises FastxDeclined (status 2, nothing resident) for an
+        input outside the regular class.  Header ids: set_header_ids(fastx_header_ids(buf, layout.rec_pos))."""
+        a = _bytes_arg(buf)
+        v = _abi.FastxLayoutC()
+        st = self.lib.crass_hip_load_fastx_bytes(self.h, a.ctypes.data if len(a) else None, len(a), int(pad_uniform), int(read_index_base),
+                                                 C.byref(v))
+        return self._fastx_result(st, v, "crass_hip_load_fastx_bytes")
+
+    def attach_device_fastx(self, tensor, pad_uniform=2, read_index_base=0):
+        """The same for file bytes in a torch uint8 DEVICE tensor of any alignment (crass_hip_attach_device_fastx).  The context
+        keeps nothing of the tensor."""
+        if str(tensor.dtype) != "torch.uint8" or not tensor.is_cuda or not tensor.is_contiguous():
+            raise ValueError("attach_device_fastx needs a contiguous uint8 device tensor")
+        v = _abi.FastxLayoutC()
+        st = self.lib.crass_hip_attach_device_fastx(self.h, int(tensor.data_ptr()) if tensor.numel() else None, int(tensor.numel()),
+                                                    int(pad_uniform), int(read_index_base), C.byref(v))
+        return self._fastx_result(st, v, "crass_hip_attach_device_fastx")
+
+    def set_header_ids(self, arr):
+        """header_id of the resident set (None: all headers unique), whichever call loaded it; drops earlier results as a load
+        does (crass_hip_set_header_ids)."""
+        hid = None if arr is None else np.ascontiguousarray(arr, dtype=np.uint64)
+        _chk(self.lib.crass_hip_set_header_ids(self.h, None if hid is None else hid.ctypes.data), "crass_hip_set_header_ids")
+
+    def last_scan_ms(self):
+        """HIP-event milliseconds of the last load_fastx_bytes / attach_device_fastx call's scan kernels (stage timing >= 1, else 0)."""
+        return float(self.lib.crass_hip_last_scan_ms(self.h))
 
     def fetch_text(self, idx, revcomp=None, out=None):
         """The text of the reads idx (GLOBAL indices: candidates' / recruits' read_idx as they are), reverse-complemented

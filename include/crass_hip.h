@@ -520,6 +520,62 @@ float crass_hip_last_pack_ms(const crass_hip_ctx *ctx);
  * the packed form of text it loaded with crass_hip_load_text / crass_hip_attach_device_text.  CRASS_ERR_STATE: no reads.
  * (No reference counterpart: crass reads its input files again for every pass.) */
 int  crass_hip_get_packed(const crass_hip_ctx *ctx, crass_packed *out);
+/* ---- the raw bytes of a FASTA / FASTQ file in, parsed on the device (fastx_scan.hip) ----
+ * replaces: crass_read_fastx + crass_pack_reads + crass_hip_load_reads (the kseq_read loop of libcrispr.cpp:96-131 and the
+ * packer) for a caller that holds the FILE's bytes — in host memory, or in HBM as the output of another GPU stage: no host code
+ * touches a sequence byte.  kseq is a byte-stream parser ('>' '@' '+' anywhere in a sequence end it); the device scans by LINES,
+ * which agrees with kseq on the regular class below and on nothing else, so every input is either
+ *   accepted (CRASS_OK): the resident set, the exception list, the counters and seq_off equal, bit for bit, what crass_read_fastx
+ *     on the same bytes + crass_pack_reads (same pad_uniform) + crass_hip_load_reads give; or
+ *   declined (CRASS_ERR_UNSUPPORTED): no reads are resident (as after a failed crass_hip_load_text), decline_reason / decline_pos
+ *     say why, and the caller takes the host readers.  A different answer is never an outcome.
+ * Lines are the pieces between '\n' bytes (the last may lack its '\n'; an empty piece after a final '\n' is no line).
+ *   regular FASTA: byte 0 is '>'; every line whose first byte is '>' is a header line; every other line is a sequence line and
+ *     holds none of '>' '@' '+' (empty lines, '\r', blanks, NUL, bytes >= 128 are fine); the file does not end with a '>' that is
+ *     the first byte of its line.  A record may have no sequence line: an empty read.
+ *   regular four-line FASTQ: byte 0 is '@'; the lines are a multiple of 4; line 4k starts with '@'; line 4k+1 holds none of
+ *     '>' '@' '+'; line 4k+2 starts with '+'; line 4k+3 holds no byte 127 and as many bytes in 33..126 as line 4k+1.
+ * A read is the bytes 33..126 of its record's sequence lines.  Reads beyond CRASS_HIP_MAX_READ_LEN: CRASS_ERR_UNSUPPORTED as from
+ * crass_hip_load_text (decline_reason 11).  Other errors: CRASS_ERR_INVALID_ARG — a NULL pointer with n_bytes > 0, pad_uniform
+ * outside 0..2; CRASS_ERR_UNSUPPORTED — n_bytes == 0 (an empty file has no format to report).
+ * decline_reason: 1 empty input, 2 byte 0 is neither '>' nor '@', 3 FASTQ lines no multiple of 4 (position: the first line of the
+ * incomplete record), 4 FASTQ line 4k does not start with '@', 5 '>' '@' '+' in a sequence line, 6 FASTQ line 4k+2 does not start
+ * with '+', 7 byte 127 in a quality line, 8 / 9 quality line shorter / longer than its sequence line, 10 FASTA ends with a lone
+ * '>', 11 a read beyond the length limit.  The verdict is the first offending line and, within it, the smallest reason. */
+typedef struct {
+    uint64_t n_reads; int32_t format;      /* '>' | '@' */
+    int32_t decline_reason;                /* 0 when accepted */
+    uint64_t decline_pos;                  /* byte position of the first offending line, when declined */
+    uint32_t max_len;
+    const uint64_t *rec_pos;               /* [n_reads+1] position of each record's header character; rec_pos[n] = n_bytes */
+    const uint64_t *seq_off;               /* [n_reads+1] offsets in the concatenated sequence text */
+} crass_fastx_layout;
+/* the scan on the host, one byte after the other (no GPU needed): what the device scan is tested against.  rec_pos / seq_off are
+ * malloc'd (crass_fastx_layout_free), NULL when the input is declined. */
+int  crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_layout *out);
+void crass_fastx_layout_free(crass_fastx_layout *l);
+/* bytes in host memory: they go up through the two staged buffers of crass_hip_load_text (CRASS_TEXT_CHUNK_BYTES each) into one
+ * device buffer of n_bytes, then the device route runs.  out may be NULL; its arrays are context-owned pinned memory, valid until
+ * the next load, attach or destroy (NULL when declined).  header_id is left NULL (crass_hip_set_header_ids). */
+int  crass_hip_load_fastx_bytes(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                                crass_fastx_layout *out);
+/* same, but d_bytes is a DEVICE pointer of any alignment (a torch uint8 tensor, a decompressor's output).  The bytes are read
+ * only during the call: the caller may free them on return. */
+int  crass_hip_attach_device_fastx(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                                   crass_fastx_layout *out);
+/* replaces: the header_id argument of the load calls, for ANY resident set: header_id[n_reads] (host; NULL: all headers unique)
+ * is copied to the device and the results of earlier passes are dropped, as by a load.  CRASS_ERR_STATE: no reads resident. */
+int  crass_hip_set_header_ids(crass_hip_ctx *ctx, const uint64_t *header_id);
+/* replaces: crass_fastx.header_id for a scanned file, on the host: header_id_out[r] = index of the first read with the same NAME,
+ * the bytes behind the header character up to the first isspace() byte, compared exactly (readsFound's key, libcrispr.cpp:138,411). */
+int  crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, uint64_t *header_id_out);
+/* bytes one workgroup of the device scan handles per tile; tiles start at multiples of it counted from the 16-byte aligned
+ * address at or below the bytes (tests place line and record edges on tile edges) */
+uint32_t crass_hip_fastx_tile_bytes(void);
+/* HIP-event time, in milliseconds on the context's stream, of the scan kernels (first to last, the host's look at the totals
+ * between them included) of the last crass_hip_load_fastx_bytes / crass_hip_attach_device_fastx call; measured when the stage timing
+ * level is >= 1, else 0; crass_hip_last_pack_ms then holds the pack kernel's.  (No reference counterpart: crass has no timers.) */
+float crass_hip_last_scan_ms(const crass_hip_ctx *ctx);
 /* ---- the text of selected reads, out of the resident set ----
  * n records back to back: record k is chars[off[k] .. off[k+1]), off[n+1] the exclusive prefix sum of the records' lengths.
  * The gather and the unpacking run on the device (k_fetch_text, pack.hip), where the words are: only the selected reads'
