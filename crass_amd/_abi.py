@@ -173,6 +173,10 @@ SYMBOLS = {
     "crass_hip_attach_device_fastx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(FastxLayoutC)]),
     "crass_hip_set_header_ids": (C.c_int, [C.c_void_p, C.c_void_p]),
     "crass_fastx_header_ids": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fastx_header_ids_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "crass_hip_last_header_ids_ms": (C.c_float, [C.c_void_p, C.c_int]),
+    "crass_hip_fetch_header_lines_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
+    "crass_hip_fetch_header_lines_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "crass_hip_fastx_tile_bytes": (C.c_uint32, []),
     "crass_hip_last_scan_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),

@@ -10,6 +10,7 @@
 #include "merge.h"
 #include "pack_launch.h"
 #include "fastx_launch.h"
+#include "fastx_names_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -184,6 +185,7 @@ struct EnvSwitches {
     uint32_t wave_walk_min = 800;                    // pass 2 walks a read per wave when the longest read is beyond this (CRASS_WAVE_WALK_MIN)
     uint32_t long_min = 2048;                        // read sets whose longest read is beyond this take the long-read path (CRASS_LONG_MIN: the A/B switch)
     uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
+    uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
     void read()
     {
         auto on = [](const char *n) { return getenv(n) != nullptr; };
@@ -205,6 +207,7 @@ struct EnvSwitches {
         no_warm_launch = getenv("CRASS_NO_WARM_LAUNCH") != nullptr;
         no_dense_light = getenv("CRASS_NO_DENSE_LIGHT") != nullptr;
         text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
+        hid_hash_bits = 64; if (const char *e = getenv("CRASS_HID_TEST_HASH_BITS")) hid_hash_bits = (uint32_t)std::min(64, std::max(0, atoi(e)));
         pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
     }
 };
@@ -275,6 +278,17 @@ struct crass_hip_ctx {
     hipEvent_t ev_f_time[2] = {nullptr, nullptr};
     float last_fetch_ms = 0;
     std::vector<uint8_t> f_flags;
+    // crass_hip_fastx_header_ids_device (fastx_names.hip): the name table, the uploaded record positions, the ids, the list of
+    // long names and the control words ([0..4) 32-bit: long names, bad position; then the 64-bit count of repeats) — all given
+    // back before the call returns; the events and times of crass_hip_last_header_ids_ms
+    DevBuf<unsigned long long> n_table; DevBuf<uint64_t> n_rec_pos, n_ids, n_ctl; DevBuf<uint32_t> n_long;
+    PinBuf<uint64_t> n_h_ctl;
+    hipEvent_t ev_n_time[3] = {nullptr, nullptr, nullptr};
+    float last_hid_ms[3] = {0, 0, 0};        // whole call's kernels, the insert launches, the lookup launch
+    // crass_hip_fetch_header_lines_device: the records' first bytes, lengths (line, then name), offsets and the lines on the
+    // device (given back before the call returns) and their pinned host sides (hl_h_off and hl_h_chars are what crass_text points at)
+    DevBuf<uint64_t> hl_src, hl_off; DevBuf<uint32_t> hl_len; DevBuf<uint8_t> hl_chars;
+    PinBuf<uint64_t> hl_h_src, hl_h_off; PinBuf<uint32_t> hl_h_len; PinBuf<uint8_t> hl_h_chars;
 
     // scratch
     DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;
@@ -876,6 +890,10 @@ void crass_hip_destroy(crass_hip_ctx *c)
     c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
     c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
     for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
+    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_ctl.release(); c->n_long.release(); c->n_h_ctl.release();
+    for (auto &e : c->ev_n_time) if (e) (void)hipEventDestroy(e);
+    c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
+    c->hl_h_src.release(); c->hl_h_off.release(); c->hl_h_len.release(); c->hl_h_chars.release();
     for (int k = 0; k < 2; k++) {
         c->t_dev[k].release(); c->t_pin[k].release();
         if (c->ev_t_copy[k]) (void)hipEventDestroy(c->ev_t_copy[k]);
@@ -1465,6 +1483,154 @@ int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
         c->R.header_id = c->r_header_id.p;
     } else c->R.header_id = nullptr;
     return CRASS_OK;
+}
+
+// ---- header ids from a file's raw bytes on the device (fastx_names.hip) ----
+// Every check that needs no byte of the file comes first; a record position outside the input is seen by the insert launch and
+// reported before the lookup launch and before anything is installed.
+static int header_ids_device_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
+                                  uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
+{
+    (void)hipSetDevice(c->device);
+    for (auto &m : c->last_hid_ms) m = 0;
+    uint64_t slots = 2;
+    while (slots < 2 * n) slots <<= 1;
+    HIPCHK(c, c->n_rec_pos.ensure(n)); HIPCHK(c, c->n_ids.ensure(n)); HIPCHK(c, c->n_long.ensure(n));
+    HIPCHK(c, c->n_ctl.ensure(4)); HIPCHK(c, c->n_h_ctl.ensure(4)); HIPCHK(c, c->n_table.ensure(slots));
+    HidJob J{};
+    J.bytes = d_bytes; J.n_bytes = n_bytes; J.rec_pos = c->n_rec_pos.p; J.n_reads = n;
+    J.table = c->n_table.p; J.mask = slots - 1; J.hash_bits = c->env.hid_hash_bits;
+    J.ids = c->n_ids.p; J.long_list = c->n_long.p;
+    J.ctl = reinterpret_cast<uint32_t *>(c->n_ctl.p); J.n_repeated = reinterpret_cast<unsigned long long *>(c->n_ctl.p + 2);
+    HIPCHK(c, hipMemcpyAsync(c->n_rec_pos.p, rec_pos, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->n_table.p, 0xFF, slots * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->n_ctl.p, 0, 32, c->stream));
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_n_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_n_time[0], c->stream));
+    }
+    HIPCHK(c, launch_hid_insert(J, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->n_h_ctl.p, c->n_ctl.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (how many long names there are sizes the wave kernel's launch)
+    const uint32_t *h_ctl = reinterpret_cast<const uint32_t *>(c->n_h_ctl.p);
+    if (h_ctl[1]) return CRASS_ERR_INVALID_ARG;         // a rec_pos[r] >= n_bytes
+    if (h_ctl[0]) HIPCHK(c, launch_hid_insert_long(J, h_ctl[0], c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[1], c->stream));
+    HIPCHK(c, launch_hid_lookup(J, c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[2], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->n_h_ctl.p + 2, c->n_ctl.p + 2, 8, hipMemcpyDeviceToHost, c->stream));
+    if (header_id_out) HIPCHK(c, hipMemcpyAsync(header_id_out, c->n_ids.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[0], c->ev_n_time[0], c->ev_n_time[2]));
+        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[1], c->ev_n_time[0], c->ev_n_time[1]));
+        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[2], c->ev_n_time[1], c->ev_n_time[2]));
+    }
+    if (n_repeated_out) *n_repeated_out = c->n_h_ctl.p[2];
+    if (install) {                                      // crass_hip_set_header_ids, the array from where it is
+        const uint64_t n_reads = c->cnt.n_reads, n_exc = c->cnt.n_exceptions, bytes_dev = c->cnt.bytes_reads_device;
+        reset_results(c);
+        c->cnt.n_reads = n_reads; c->cnt.n_exceptions = n_exc; c->cnt.bytes_reads_device = bytes_dev;
+        HIPCHK(c, c->r_header_id.ensure(n));
+        HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, c->n_ids.p, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->R.header_id = c->r_header_id.p;
+    }
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_header_ids_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                      uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
+{
+    if (!c || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
+    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (a slot holds a 32-bit index, all-ones is the free slot's)
+    if (install) {
+        if (!c->have_reads) return CRASS_ERR_STATE;
+        if (n_reads != c->R.n_reads) return CRASS_ERR_INVALID_ARG;
+    }
+    if (n_repeated_out) *n_repeated_out = 0;
+    if (n_reads == 0) return install ? crass_hip_set_header_ids(c, nullptr) : CRASS_OK;
+    (void)hipSetDevice(c->device);
+    if (install) HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing may still read the array this replaces)
+    const int s = header_ids_device_impl(c, d_bytes, n_bytes, rec_pos, n_reads, header_id_out, install, n_repeated_out);
+    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out
+    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
+    return s;
+}
+
+float crass_hip_last_header_ids_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 3 ? c->last_hid_ms[part] : 0.0f; }
+
+// ---- header lines of selected records from a file's raw bytes on the device (fastx_names.hip) ----
+// d_user == nullptr: the host route (the lines come back into pinned memory, *out points at it); else the caller's device buffer
+// of cap bytes, the offsets into off_user.  Every check comes before the first launch; the resident set is not involved.
+static int header_lines_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                             const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
+                             uint32_t *name_len_out)
+{
+    for (uint64_t k = 0; k < n; k++) if (idx[k] >= n_reads || rec_pos[idx[k]] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, c->hl_h_off.ensure(n + 1));
+    uint64_t *off = c->hl_h_off.p;
+    off[0] = 0;
+    if (n) {
+        HIPCHK(c, c->hl_h_src.ensure(n)); HIPCHK(c, c->hl_h_len.ensure(2 * n));
+        HIPCHK(c, c->hl_src.ensure(n)); HIPCHK(c, c->hl_len.ensure(2 * n));
+        for (uint64_t k = 0; k < n; k++) c->hl_h_src.p[k] = rec_pos[idx[k]] + 1;
+    }
+    HlJob J{};
+    J.bytes = d_bytes; J.n_bytes = n_bytes; J.src = c->hl_src.p; J.n = n;
+    J.line_len = c->hl_len.p; J.name_len = c->hl_len.p + n;
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(c->hl_src.p, c->hl_h_src.p, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_hl_measure(J, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->hl_h_len.p, c->hl_len.p, 2 * n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the lengths size the result)
+        for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + c->hl_h_len.p[k];
+        if (name_len_out) memcpy(name_len_out, c->hl_h_len.p + n, n * 4);
+    }
+    const uint64_t total = off[n];
+    if (off_user) memcpy(off_user, off, (n + 1) * 8);
+    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
+    if (!d_user) HIPCHK(c, c->hl_h_chars.ensure(total));
+    if (out) { out->n = n; out->chars = c->hl_h_chars.p; out->off = off; }
+    if (!total) return CRASS_OK;
+    HIPCHK(c, c->hl_off.ensure(n + 1));
+    if (!d_user) HIPCHK(c, c->hl_chars.ensure(total));
+    HIPCHK(c, hipMemcpyAsync(c->hl_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    J.off = c->hl_off.p; J.total = total; J.out = d_user ? d_user : c->hl_chars.p;
+    HIPCHK(c, launch_hl_copy(J, c->stream));
+    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->hl_h_chars.p, c->hl_chars.p, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CRASS_OK;
+}
+
+static int header_lines_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                               const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
+                               uint32_t *name_len_out)
+{
+    if (!c || (n && !idx) || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
+    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    const int s = header_lines_impl(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_user, cap, off_user, out, name_len_out);
+    (void)hipStreamSynchronize(c->stream);              // the device scratch goes back on every way out; the pinned result stays
+    c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
+    return s;
+}
+
+int crass_hip_fetch_header_lines_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                        const uint64_t *idx, uint64_t n, crass_text *out, uint32_t *name_len_out)
+{
+    if (!out) return CRASS_ERR_INVALID_ARG;
+    return header_lines_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, nullptr, 0, nullptr, out, name_len_out);
+}
+
+int crass_hip_fetch_header_lines_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                           const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
+                                           uint32_t *name_len_out)
+{
+    if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
+    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
+    return header_lines_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, name_len_out);
 }
 
 int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)

@@ -1,0 +1,347 @@
+// fastx_names.hip — what the header lines of a FASTA / FASTQ file's raw bytes hold, on the device, for a caller whose bytes
+// exist only in HBM: header_id (the index of the first read with the same NAME: readsFound's key, libcrispr.cpp:138,411) and the
+// header lines of selected records (RH_Header / RH_Comment).  The restatement both are tested against is the host's
+// crass_fastx_header_ids (fastx_scan.cpp) and kseq's name cut.
+//
+// A NAME is the bytes behind the record's header character up to the first isspace() byte (' ', '\t' .. '\r') or the input's end.
+// Names lie at any byte offset: they are read as ALIGNED dwords, funnel-shifted into name-relative dwords (v_alignbyte_b32), so a
+// name's hash and the comparison of two names do not depend on where they lie.  No byte below bytes or at / beyond bytes + n_bytes
+// is read: the one dword that holds the input's first byte and the one that holds its last are loaded byte by byte (nm_ld4).
+//
+// header ids — an open-addressing table of 2^k >= 2 n_reads slots of 64 bits, {hash tag : 32 | read index : 32}, all-ones = free:
+//   k_hid_insert       a lane per record: hash the name, probe linearly.  Free slot: claim it by CAS.  Other tag: next slot.  Same
+//                      tag: compare the names byte for byte, lengths included — equal: atomicMin on the slot (same tag, so the
+//                      smaller index), different: next slot.  A slot's owner only ever changes to a read with the IDENTICAL name,
+//                      so the comparison's outcome does not depend on when the slot was read; no lane waits for another.  The
+//                      record's slot goes to ids[r].  Names beyond kHidLaneMax bytes are only listed ...
+//   k_hid_insert_long  ... and inserted by a wave per record (a 12 KB name must not be one lane's tail): the wave finds the name's
+//                      end 256 bytes a step, hashes and compares a dword per lane.  The two kernels hash differently, which is
+//                      fine: equal names have equal lengths, so both are hashed by the same kernel.
+//   k_hid_lookup       a launch of its own, so the table is final: ids[r] = the index in the record's slot — the smallest index
+//                      with that name, whatever the scheduling.  (The slot was kept at insert, so no name is read twice.)
+// No answer rests on a hash: hash_bits (CRASS_HID_TEST_HASH_BITS) cuts the hash to its low bits, down to none, for the tests.
+// Slot accesses are agent-scope atomics; the name bytes and rec_pos are read-only input.
+//
+// header lines — k_hl_measure: a lane per selected record walks its header line: bytes up to the '\n' (or the input's end) and the
+// name's length.  The host sums the lengths.  k_hl_copy: driven by the OUTPUT, a lane per byte finds its record in the offsets;
+// nothing outside [out, out + total) is stored.  Neither is hot: about one read in a hundred is handed on.
+#include "fastx_names_launch.h"
+#include "devmem.h"
+
+namespace crass {
+
+static constexpr int kNmThreads = 256;
+static constexpr uint32_t kHidLaneMax = 256;             // names beyond this many bytes go to the wave kernel
+
+// the aligned dword at address q of the input [lo, hi); bytes outside the input read as 0 and are not touched
+static __device__ __forceinline__ uint32_t nm_ld4(uintptr_t lo, uintptr_t hi, uintptr_t q)
+{
+    if (q >= lo && q + 4 <= hi) return *reinterpret_cast<const uint32_t *>(q);
+    uint32_t w = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) { const uintptr_t a = q + j; if (a >= lo && a < hi) w |= (uint32_t)*reinterpret_cast<const uint8_t *>(a) << (8 * j); }
+    return w;
+}
+
+// the input's bytes from a position on, four at a time (byte 0 lowest); one aligned load per step
+struct NmCur {
+    uintptr_t lo, hi, q;
+    uint32_t w0, sh;
+    uint64_t left;                   // bytes from here to the input's end
+    __device__ __forceinline__ void init(uintptr_t lo_, uintptr_t hi_, uint64_t pos)      // pos <= hi - lo
+    {
+        lo = lo_; hi = hi_;
+        const uintptr_t a = lo + pos;
+        sh = (uint32_t)(a & 3u); q = a - sh; left = hi - a;
+        w0 = left ? nm_ld4(lo, hi, q) : 0u;
+    }
+    __device__ __forceinline__ uint32_t next(uint32_t *avail)      // *avail: how many of the four bytes are inside the input
+    {
+        const uint32_t w1 = left > 4u - sh ? nm_ld4(lo, hi, q + 4) : 0u;
+        const uint32_t w = __builtin_amdgcn_alignbyte(w1, w0, sh);
+        *avail = left < 4 ? (uint32_t)left : 4u;
+        w0 = w1; q += 4; left -= *avail;
+        return w;
+    }
+};
+// the four bytes at a position, without a cursor (the wave kernel: a dword per lane)
+static __device__ __forceinline__ uint32_t nm_dword_at(uintptr_t lo, uintptr_t hi, uint64_t pos, uint32_t *avail)
+{
+    if (pos >= hi - lo) { *avail = 0; return 0u; }
+    NmCur c;
+    c.init(lo, hi, pos);
+    return c.next(avail);
+}
+
+static __device__ __forceinline__ uint32_t nm_is_space(uint32_t c) { return (uint32_t)(c - 9u < 5u) | (uint32_t)(c == 32u); }
+// how many of the first `avail` bytes of w come before the first isspace() byte / the first '\n'
+static __device__ __forceinline__ uint32_t nm_name_bytes(uint32_t w, uint32_t avail)
+{
+    uint32_t stop = 1u << avail;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) stop |= nm_is_space((w >> (8 * j)) & 0xFFu) << j;
+    return (uint32_t)__builtin_ctz(stop);
+}
+static __device__ __forceinline__ uint32_t nm_line_bytes(uint32_t w, uint32_t avail)
+{
+    uint32_t stop = 1u << avail;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) stop |= (uint32_t)(((w >> (8 * j)) & 0xFFu) == 10u) << j;
+    return (uint32_t)__builtin_ctz(stop);
+}
+static __device__ __forceinline__ uint32_t nm_low_bytes(uint32_t cnt) { return cnt >= 4 ? 0xFFFFFFFFu : (1u << (8 * cnt)) - 1u; }
+
+static __device__ __forceinline__ uint64_t nm_fmix(uint64_t h)      // (the 64-bit finaliser of MurmurHash3)
+{
+    h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
+    return h;
+}
+static __device__ __forceinline__ uint64_t nm_cut(uint64_t h, uint32_t bits) { return bits >= 64 ? h : bits == 0 ? 0ull : h & ((1ull << bits) - 1ull); }
+
+static __device__ __forceinline__ unsigned long long hid_load(unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// claims a free slot; true: it is ours, else *seen is what the slot holds
+static __device__ __forceinline__ bool hid_claim(unsigned long long *p, unsigned long long mine, unsigned long long *seen)
+{
+    unsigned long long expected = kHidEmpty;
+    const bool won = __hip_atomic_compare_exchange_strong(p, &expected, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *seen = expected;
+    return won;
+}
+static __device__ __forceinline__ void hid_min(unsigned long long *p, unsigned long long mine) { (void)__hip_atomic_fetch_min(p, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// one lane: is the name at a the name at b?  (Both end at their first isspace() byte or the input's end; the walk ends with the
+// shorter of the two.)
+static __device__ __forceinline__ bool hid_same_name_lane(uintptr_t lo, uintptr_t hi, uint64_t a, uint64_t b)
+{
+    NmCur ca, cb;
+    ca.init(lo, hi, a); cb.init(lo, hi, b);
+    for (;;) {
+        uint32_t ava, avb;
+        const uint32_t wa = ca.next(&ava), wb = cb.next(&avb);
+        const uint32_t na = nm_name_bytes(wa, ava), nb = nm_name_bytes(wb, avb);
+        if (na != nb || ((wa ^ wb) & nm_low_bytes(na))) return false;
+        if (na < 4) return true;
+    }
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_insert(const HidJob J)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (r >= J.n_reads) return;
+    const uint64_t pos = J.rec_pos[r];
+    if (pos >= J.n_bytes) { J.ctl[1] = 1u; J.ids[r] = kHidEmpty; return; }
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    NmCur c;
+    c.init(lo, hi, pos + 1);
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    uint32_t len = 0;
+    for (;;) {
+        uint32_t avail;
+        const uint32_t w = c.next(&avail);
+        const uint32_t cnt = nm_name_bytes(w, avail);
+        if (cnt) { h = (h ^ (w & nm_low_bytes(cnt))) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
+        len += cnt;
+        if (cnt < 4) break;
+        if (len > kHidLaneMax) {                        // the wave kernel's
+            J.long_list[atomicAdd(&J.ctl[0], 1u)] = (uint32_t)r;
+            return;
+        }
+    }
+    h = nm_cut(nm_fmix(h ^ len), J.hash_bits);
+    const unsigned long long tag = h >> 32, mine = (tag << 32) | r;
+    uint64_t s = h & J.mask;
+    for (;;) {                                          // (ends: the table has more slots than there are records)
+        unsigned long long cur = hid_load(&J.table[s]);
+        if (cur == kHidEmpty && hid_claim(&J.table[s], mine, &cur)) break;
+        if ((cur >> 32) == tag) {
+            const uint64_t owner = cur & 0xFFFFFFFFull;
+            if (owner == r || hid_same_name_lane(lo, hi, pos + 1, J.rec_pos[owner] + 1)) {
+                if (owner > r) hid_min(&J.table[s], mine);
+                break;
+            }
+        }
+        s = (s + 1) & J.mask;
+    }
+    J.ids[r] = s;
+}
+
+static __device__ __forceinline__ uint64_t nm_bcast64(uint64_t v, int src)
+{
+    const uint32_t a = (uint32_t)__shfl((int)(uint32_t)v, src), b = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+    return ((uint64_t)b << 32) | a;
+}
+static __device__ __forceinline__ uint64_t nm_wave_sum64(uint64_t v)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t a = (uint32_t)__shfl_xor((int)(uint32_t)v, s), b = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), s);
+        v += ((uint64_t)b << 32) | a;
+    }
+    return v;
+}
+
+// the wave: is the name of len bytes at a the name at b?  (The len bytes are equal and b's name ends behind them.)
+static __device__ __forceinline__ bool hid_same_name_wave(uintptr_t lo, uintptr_t hi, uint64_t a, uint64_t len, uint64_t b, uint32_t lane)
+{
+    const uint64_t n = hi - lo;
+    if (b > n || n - b < len) return false;
+    if (b + len < n && !nm_is_space(*reinterpret_cast<const uint8_t *>(lo + b + len))) return false;
+    for (uint64_t k0 = 0; 4 * k0 < len; k0 += 64) {
+        const uint64_t k = k0 + lane;
+        uint32_t diff = 0;
+        if (4 * k < len) {
+            uint32_t ava, avb;
+            const uint32_t wa = nm_dword_at(lo, hi, a + 4 * k, &ava), wb = nm_dword_at(lo, hi, b + 4 * k, &avb);
+            const uint64_t rest = len - 4 * k;
+            diff = (wa ^ wb) & nm_low_bytes(rest < 4 ? (uint32_t)rest : 4u);
+        }
+        if (__any(diff != 0)) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_insert_long(const HidJob J, const uint32_t n_long)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t li = (uint64_t)blockIdx.x * (kNmThreads / 64) + (threadIdx.x >> 6);
+    if (li >= n_long) return;                           // (the whole wave)
+    const uint64_t r = J.long_list[li];
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    const uint64_t a = J.rec_pos[r] + 1;
+    // the name's end, 64 dwords a step; every dword of the name is mixed with its index, the sum is the hash
+    uint64_t acc = 0, len = 0;
+    for (uint64_t k0 = 0;; k0 += 64) {
+        const uint64_t k = k0 + lane;
+        uint32_t avail;
+        const uint32_t w = nm_dword_at(lo, hi, a + 4 * k, &avail);
+        const uint32_t cnt = nm_name_bytes(w, avail);
+        const unsigned long long ended = __ballot(cnt < 4);
+        const uint32_t first = ended ? (uint32_t)__builtin_ctzll(ended) : 64u;
+        if (lane <= first && cnt) acc += nm_fmix(((k + 1) << 32) | (w & nm_low_bytes(cnt)));
+        if (ended) { len = 4 * (k0 + first) + (uint32_t)__shfl((int)cnt, (int)first); break; }
+    }
+    const uint64_t h = nm_cut(nm_fmix(nm_wave_sum64(acc) ^ len), J.hash_bits);
+    const unsigned long long tag = h >> 32, mine = (tag << 32) | r;
+    uint64_t s = h & J.mask;
+    for (;;) {                                          // (every lane takes the same way: lane 0's view of the slot decides)
+        unsigned long long cur = 0;
+        uint32_t won = 0;
+        if (lane == 0) {
+            cur = hid_load(&J.table[s]);
+            if (cur == kHidEmpty) won = hid_claim(&J.table[s], mine, &cur) ? 1u : 0u;
+        }
+        if (__shfl((int)won, 0)) break;
+        cur = nm_bcast64(cur, 0);
+        if ((cur >> 32) == tag) {
+            const uint64_t owner = cur & 0xFFFFFFFFull;
+            if (owner == r || hid_same_name_wave(lo, hi, a, len, J.rec_pos[owner] + 1, lane)) {
+                if (lane == 0 && owner > r) hid_min(&J.table[s], mine);
+                break;
+            }
+        }
+        s = (s + 1) & J.mask;
+    }
+    if (lane == 0) J.ids[r] = s;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_lookup(const HidJob J)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    uint32_t rep = 0;
+    if (r < J.n_reads) {
+        const uint64_t s = J.ids[r];
+        if (s <= J.mask) {                              // (not so behind a rec_pos beyond the input: the call fails, nothing is read)
+            const uint64_t id = hid_load(&J.table[s]) & 0xFFFFFFFFull;
+            J.ids[r] = id;
+            rep = id != r ? 1u : 0u;
+        }
+    }
+    const unsigned long long m = __ballot(rep);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(J.n_repeated, (unsigned long long)__builtin_popcountll(m));
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hl_measure(const HlJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uintptr_t lo = (uintptr_t)J.bytes;
+    NmCur c;
+    c.init(lo, lo + J.n_bytes, J.src[k]);
+    uint64_t line = 0, name = 0;
+    bool named = false;
+    for (;;) {
+        uint32_t avail;
+        const uint32_t w = c.next(&avail);
+        const uint32_t lb = nm_line_bytes(w, avail);
+        if (!named) { const uint32_t nb = nm_name_bytes(w, avail); name += nb; named = nb < 4; }      // ('\n' is a space: nb <= lb)
+        line += lb;
+        if (lb < 4) break;
+    }
+    J.line_len[k] = line > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)line;
+    J.name_len[k] = name > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)name;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hl_copy(const HlJob J)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (i >= J.total) return;
+    uint64_t a = 0, b = J.n - 1;                        // the last record whose offset is <= i (empty records in front of it share the offset)
+    while (a < b) {
+        const uint64_t mid = (a + b + 1) >> 1;
+        if (J.off[mid] <= i) a = mid; else b = mid - 1;
+    }
+    const uint64_t p = J.src[a] + (i - J.off[a]);
+    if (p < J.n_bytes) J.out[i] = J.bytes[p];
+}
+
+uint32_t hid_lane_max() { return kHidLaneMax; }
+
+static bool nm_grid(uint64_t items, uint64_t per_block, unsigned *blocks)
+{
+    const uint64_t g = (items + per_block - 1) / per_block;
+    if (!g || g > 0x7FFFFFFFull) return false;
+    *blocks = (unsigned)g;
+    return true;
+}
+
+hipError_t launch_hid_insert(const HidJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n_reads, kNmThreads, &g) || J.n_reads >= 0xFFFFFFFFull || J.mask + 1 < 2 * J.n_reads || (J.mask & (J.mask + 1))) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_insert, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_insert_long(const HidJob &J, uint32_t n_long, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(n_long, kNmThreads / 64, &g) || n_long > J.n_reads) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_insert_long, dim3(g), dim3(kNmThreads), 0, st, J, n_long);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_lookup(const HidJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n_reads, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_lookup, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_hl_measure(const HlJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hl_measure, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_hl_copy(const HlJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!J.n || !nm_grid(J.total, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hl_copy, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+} // namespace crass

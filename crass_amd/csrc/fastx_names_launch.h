@@ -1,0 +1,43 @@
+// fastx_names_launch.h — the job descriptions and launch wrappers of fastx_names.hip (header ids and header lines from the raw
+// bytes of a FASTA / FASTQ file on the device), for the engine.  Not part of the public ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace crass {
+
+static constexpr unsigned long long kHidEmpty = ~0ull;      // a free slot of the name table
+
+// k_hid_insert / k_hid_insert_long / k_hid_lookup
+struct HidJob {
+    const uint8_t *bytes;            // device pointer, any alignment; [bytes, bytes + n_bytes) is all that is ever read
+    uint64_t n_bytes;
+    const uint64_t *rec_pos;         // [n_reads] position of every record's header character
+    uint64_t n_reads;                // < 2^32 - 1
+    unsigned long long *table;       // [mask + 1] {hash tag : 32 | read index : 32}, kHidEmpty before the insert launch
+    uint64_t mask;                   // slots - 1, slots a power of two >= 2 n_reads
+    uint32_t hash_bits;              // 64, or fewer: only that many low bits of the hash are kept (tests)
+    uint64_t *ids;                   // [n_reads] insert: the record's slot; lookup: its header id
+    uint32_t *long_list;             // [n_reads] the records whose name is beyond kHidLaneMax bytes (k_hid_insert -> k_hid_insert_long)
+    uint32_t *ctl;                   // [4] 0: entries of long_list, 1: a rec_pos at or beyond n_bytes was seen
+    unsigned long long *n_repeated;  // reads with ids[r] != r (k_hid_lookup)
+};
+uint32_t hid_lane_max();
+hipError_t launch_hid_insert(const HidJob &J, hipStream_t st);
+hipError_t launch_hid_insert_long(const HidJob &J, uint32_t n_long, hipStream_t st);
+hipError_t launch_hid_lookup(const HidJob &J, hipStream_t st);
+
+// k_hl_measure / k_hl_copy
+struct HlJob {
+    const uint8_t *bytes; uint64_t n_bytes;
+    const uint64_t *src;             // [n] position of the first byte behind the record's header character (<= n_bytes)
+    uint64_t n;
+    uint32_t *line_len, *name_len;   // [n] k_hl_measure
+    const uint64_t *off;             // [n + 1] k_hl_copy: where the records lie in out
+    uint64_t total;                  // off[n]
+    uint8_t *out;                    // [total], any alignment
+};
+hipError_t launch_hl_measure(const HlJob &J, hipStream_t st);
+hipError_t launch_hl_copy(const HlJob &J, hipStream_t st);
+
+} // namespace crass

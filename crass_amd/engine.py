@@ -675,6 +675,63 @@ class SearchEngine:
         hid = None if arr is None else np.ascontiguousarray(arr, dtype=np.uint64)
         _chk(self.lib.crass_hip_set_header_ids(self.h, None if hid is None else hid.ctypes.data), "crass_hip_set_header_ids")
 
+    @staticmethod
+    def _device_bytes(src, layout):
+        """(address, n_bytes, rec_pos, n_reads) of file bytes on the device: src is a contiguous torch uint8 device tensor, or a
+        raw device address (then the layout's rec_pos[n_reads] is the byte count); layout: a FastxLayout or its rec_pos"""
+        rp = np.ascontiguousarray(getattr(layout, "rec_pos", layout), dtype=np.uint64)
+        n = max(len(rp) - 1, 0)
+        if isinstance(src, int):
+            return (src or None), (int(rp[n]) if len(rp) else 0), rp, n
+        if str(src.dtype) != "torch.uint8" or not src.is_cuda or not src.is_contiguous():
+            raise ValueError("file bytes on the device: a contiguous uint8 device tensor or an address")
+        return (int(src.data_ptr()) if src.numel() else None), int(src.numel()), rp, n
+
+    def device_header_ids(self, src, layout, install=True):
+        """header_id[r] = index of the first read with the same name, from file bytes that live on the DEVICE (a torch uint8
+        tensor or an address) and the records' positions (a FastxLayout or its rec_pos): what fastx_header_ids gives on the
+        same bytes, computed on the device (crass_hip_fastx_header_ids_device).  install: also make them the resident set's,
+        as set_header_ids does, without a host round trip.  Returns (ids, n_repeated)."""
+        ptr, nb, rp, n = self._device_bytes(src, layout)
+        out = np.zeros(n, np.uint64)
+        rep = C.c_uint64()
+        _chk(self.lib.crass_hip_fastx_header_ids_device(self.h, ptr, nb, rp.ctypes.data if n else None, n, out.ctypes.data if n else None,
+                                                        1 if install else 0, C.byref(rep)), "crass_hip_fastx_header_ids_device")
+        return out, int(rep.value)
+
+    def last_header_ids_ms(self):
+        """HIP-event milliseconds of the last device_header_ids call: (all kernels, insert launches, lookup launch); stage
+        timing >= 1, else zeros."""
+        return tuple(float(self.lib.crass_hip_last_header_ids_ms(self.h, k)) for k in range(3))
+
+    def fetch_header_lines(self, src, layout, idx, out=None):
+        """The header lines (without the header character and the line end) of the records idx (LOCAL record numbers, any order,
+        repeats allowed) of file bytes on the DEVICE (crass_hip_fetch_header_lines_device).  Returns (chars, off, name_len):
+        numpy copies of the lines back to back (uint8), their offsets (uint64, n + 1) and the length of the name at each line's
+        start (uint32).  out: a contiguous torch uint8 DEVICE tensor — the lines are written there instead
+        (crass_hip_fetch_header_lines_device_to) and chars is None; a tensor too small raises CrassError with status 8 and the
+        offsets in its `offsets`."""
+        ptr, nb, rp, n = self._device_bytes(src, layout)
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        name_len = np.zeros(len(a), np.uint32)
+        args = (self.h, ptr, nb, rp.ctypes.data if n else None, n, a.ctypes.data if len(a) else None, len(a))
+        if out is None:
+            v = _abi.Text()
+            _chk(self.lib.crass_hip_fetch_header_lines_device(*args, C.byref(v), name_len.ctypes.data if len(a) else None),
+                 "crass_hip_fetch_header_lines_device")
+            t = Text(v)
+            return t.chars.copy(), t.off.copy(), name_len
+        if str(out.dtype) != "torch.uint8" or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("fetch_header_lines(out=...) needs a contiguous uint8 device tensor")
+        off = np.zeros(len(a) + 1, np.uint64)
+        st = self.lib.crass_hip_fetch_header_lines_device_to(*args, int(out.data_ptr()) if out.numel() else None, int(out.numel()), off.ctypes.data,
+                                                             name_len.ctypes.data if len(a) else None)
+        if st != 0:
+            e = CrassError(st, "crass_hip_fetch_header_lines_device_to")
+            e.offsets = off
+            raise e
+        return None, off, name_len
+
     def last_scan_ms(self):
         """HIP-event milliseconds of the last load_fastx_bytes / attach_device_fastx call's scan kernels (stage timing >= 1, else 0)."""
         return float(self.lib.crass_hip_last_scan_ms(self.h))

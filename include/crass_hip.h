@@ -556,7 +556,8 @@ int  crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_l
 void crass_fastx_layout_free(crass_fastx_layout *l);
 /* bytes in host memory: they go up through the two staged buffers of crass_hip_load_text (CRASS_TEXT_CHUNK_BYTES each) into one
  * device buffer of n_bytes, then the device route runs.  out may be NULL; its arrays are context-owned pinned memory, valid until
- * the next load, attach or destroy (NULL when declined).  header_id is left NULL (crass_hip_set_header_ids). */
+ * the next load, attach or destroy (NULL when declined).  header_id is left NULL (crass_hip_set_header_ids,
+ * crass_hip_fastx_header_ids_device). */
 int  crass_hip_load_fastx_bytes(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
                                 crass_fastx_layout *out);
 /* same, but d_bytes is a DEVICE pointer of any alignment (a torch uint8 tensor, a decompressor's output).  The bytes are read
@@ -569,6 +570,25 @@ int  crass_hip_set_header_ids(crass_hip_ctx *ctx, const uint64_t *header_id);
 /* replaces: crass_fastx.header_id for a scanned file, on the host: header_id_out[r] = index of the first read with the same NAME,
  * the bytes behind the header character up to the first isspace() byte, compared exactly (readsFound's key, libcrispr.cpp:138,411). */
 int  crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, uint64_t *header_id_out);
+/* replaces: the same (crass_fastx.header_id, readsFound's key) for a caller whose file bytes exist only on the DEVICE, which would
+ * otherwise copy the file back to feed crass_fastx_header_ids: header_id_out[r] (host, [n_reads], may be NULL) is exactly that
+ * function's result on the same bytes.  Names are hashed into a device table and compared byte for byte (fastx_names.hip): no
+ * answer rests on a hash.  d_bytes: a device pointer of any alignment, read only during the call; rec_pos: the HOST array of a
+ * layout (the context's own pinned one is fine), uploaded into scratch that is given back with the table (8 bytes per slot,
+ * the smallest power of two >= 2 n_reads slots) before the call returns.  install != 0: as crass_hip_set_header_ids(ctx, those
+ * ids) — earlier results are dropped, the array (always one, never NULL) goes device to device; needs n_reads == the resident
+ * set's (else CRASS_ERR_INVALID_ARG) and reads (CRASS_ERR_STATE).  *n_repeated_out (may be NULL): reads with header_id[r] != r.
+ * Errors (the resident set is untouched): CRASS_ERR_INVALID_ARG — a NULL context, NULL d_bytes or rec_pos with n_reads > 0
+ * (nothing launched), a rec_pos[r] >= n_bytes (seen on the device, reported before anything is installed or written to
+ * header_id_out); CRASS_ERR_UNSUPPORTED — n_reads >= 2^32 - 1.  n_reads == 0: CRASS_OK.
+ * CRASS_HID_TEST_HASH_BITS=b (read when the context is created): only the low b bits of a name's hash are kept, so that a few
+ * names make long probe chains and equal tags (tests). */
+int  crass_hip_fastx_header_ids_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                       uint64_t *header_id_out, int install, uint64_t *n_repeated_out);
+/* HIP-event time, in milliseconds on the context's stream, of the last crass_hip_fastx_header_ids_device call's kernels: part 0
+ * first to last, 1 the insert launches (the host's look at the count of long names included), 2 the lookup launch; measured when
+ * the stage timing level is >= 1, else 0.  (No reference counterpart: crass has no timers.) */
+float crass_hip_last_header_ids_ms(const crass_hip_ctx *ctx, int part);
 /* bytes one workgroup of the device scan handles per tile; tiles start at multiples of it counted from the 16-byte aligned
  * address at or below the bytes (tests place line and record edges on tile edges) */
 uint32_t crass_hip_fastx_tile_bytes(void);
@@ -611,6 +631,23 @@ int crass_hip_fetch_record_text(crass_hip_ctx *ctx, int pass, crass_text *out);
 /* HIP-event time, in milliseconds on the context's stream, of the fetch kernel of the last crass_hip_fetch_* call; measured
  * when the stage timing level is >= 1 (crass_hip_set_stage_timing), else 0.  (No reference counterpart: crass has no timers.) */
 float crass_hip_last_fetch_ms(const crass_hip_ctx *ctx);
+/* replaces: ReadHolder's RH_Header / RH_Comment (filled from the kseq record at libcrispr.cpp:471-487) for a caller whose file
+ * bytes exist only on the device: the header LINES of the records idx[0..n) (LOCAL record numbers in [0, n_reads), any order,
+ * repeats allowed) back to back — record k is the bytes from rec_pos[idx[k]] + 1 up to, not including, the '\n' that ends the
+ * line, or up to n_bytes (a '\r' in front of the '\n' stays).  name_len_out[k] (host [n], may be NULL): the length of the NAME at
+ * the line's start (the bytes up to the first isspace() byte, as above): the caller cuts header and comment there.  The result
+ * follows crass_hip_fetch_text: a crass_text in the context's pinned memory (its own, not that of the text fetches), valid until
+ * the next call of this function, or destroy.  Errors (nothing launched): CRASS_ERR_INVALID_ARG — a NULL context or result
+ * pointer, NULL d_bytes or rec_pos with n_reads > 0, a NULL idx with n > 0, an idx[k] >= n_reads, a rec_pos[idx[k]] >= n_bytes;
+ * CRASS_ERR_UNSUPPORTED — n_reads >= 2^32 - 1.  Needs no resident reads. */
+int  crass_hip_fetch_header_lines_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                         const uint64_t *idx, uint64_t n, crass_text *out, uint32_t *name_len_out);
+/* the same into the caller's DEVICE buffer d_chars (cap_bytes bytes, any alignment), the offsets into the host array off_out[n+1],
+ * by the rules of crass_hip_fetch_text_device: cap_bytes < off_out[n] is CRASS_ERR_OVERFLOW with off_out and name_len_out filled
+ * and nothing written; no byte at or beyond d_chars + off_out[n] is written. */
+int  crass_hip_fetch_header_lines_device_to(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                            const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
+                                            uint32_t *name_len_out);
 /* replaces: the second reading of the input files (libcrispr.cpp:471-487) for a group (crass_hip_group_*): crass_hip_fetch_text
  * over the whole job.  Every global index is routed to the rank whose shard holds it; the records come back in the caller's
  * order in one crass_text owned by the group, valid until the next group fetch, load or destroy. */
