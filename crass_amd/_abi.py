@@ -90,6 +90,14 @@ class FastxLayoutC(C.Structure):
                 ("max_len", C.c_uint32), ("rec_pos", u64p), ("seq_off", u64p)]
 
 
+class BgzfVerdict(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("member", C.c_uint64), ("in_pos", C.c_uint64)]
+
+
+class BgzfIndexC(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("in_off", u64p), ("out_off", u64p), ("data_off", u64p), ("decline", BgzfVerdict)]
+
+
 class Fastx(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("seq", u8p), ("seq_off", u64p), ("name", u8p), ("name_off", u64p),
                 ("comment", u8p), ("comment_off", u64p), ("has_comment", u8p), ("qual", u8p), ("qual_off", u64p),
@@ -179,6 +187,13 @@ SYMBOLS = {
     "crass_hip_fetch_header_lines_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "crass_hip_fastx_tile_bytes": (C.c_uint32, []),
     "crass_hip_last_scan_ms": (C.c_float, [C.c_void_p]),
+    "crass_bgzf_index_host": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(BgzfIndexC)]),
+    "crass_bgzf_index_free": (None, [C.POINTER(BgzfIndexC)]),
+    "crass_bgzf_inflate_host": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(BgzfIndexC), C.c_void_p, C.c_uint64, C.POINTER(BgzfVerdict)]),
+    "crass_hip_inflate_bgzf_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfIndexC), C.c_void_p, C.c_uint64, C.POINTER(BgzfVerdict)]),
+    "crass_hip_load_fastx_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(FastxLayoutC),
+                                            C.POINTER(BgzfVerdict)]),
+    "crass_hip_last_inflate_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
     "crass_hip_fetch_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fetch_record_text": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Text)]),

@@ -11,6 +11,7 @@
 #include "pack_launch.h"
 #include "fastx_launch.h"
 #include "fastx_names_launch.h"
+#include "inflate_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -185,6 +186,7 @@ struct EnvSwitches {
     uint32_t wave_walk_min = 800;                    // pass 2 walks a read per wave when the longest read is beyond this (CRASS_WAVE_WALK_MIN)
     uint32_t long_min = 2048;                        // read sets whose longest read is beyond this take the long-read path (CRASS_LONG_MIN: the A/B switch)
     uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
+    bool inflate_hbm_window = true;                  // CRASS_INFLATE_WINDOW=lds: k_bgzf_inflate decodes in the wave's LDS window, not in the output's own range (A/B switch, inflate.hip)
     uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
     void read()
     {
@@ -207,6 +209,7 @@ struct EnvSwitches {
         no_warm_launch = getenv("CRASS_NO_WARM_LAUNCH") != nullptr;
         no_dense_light = getenv("CRASS_NO_DENSE_LIGHT") != nullptr;
         text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
+        inflate_hbm_window = true; if (const char *e = getenv("CRASS_INFLATE_WINDOW")) inflate_hbm_window = strcmp(e, "lds") != 0;
         hid_hash_bits = 64; if (const char *e = getenv("CRASS_HID_TEST_HASH_BITS")) hid_hash_bits = (uint32_t)std::min(64, std::max(0, atoi(e)));
         pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
     }
@@ -268,6 +271,13 @@ struct crass_hip_ctx {
     PinBuf<uint64_t> x_h_tot, x_h_rec_pos, x_h_seq_off;
     hipEvent_t ev_x_time[2] = {nullptr, nullptr};
     float last_scan_ms = 0;                  // HIP-event time of the last call's scan kernels (stage timing >= 1, else 0)
+    // crass_hip_inflate_bgzf_device / crass_hip_load_fastx_bgzf (inflate.hip): the index's three arrays back to back, every
+    // member's reason, the verdict word, the compressed bytes of a host file and the text that is not the caller's — all given
+    // back before the call returns
+    DevBuf<uint64_t> z_idx; DevBuf<uint32_t> z_reason; DevBuf<unsigned long long> z_verdict; DevBuf<uint8_t> z_raw, z_text;
+    PinBuf<unsigned long long> z_h_verdict;
+    hipEvent_t ev_z_time[2] = {nullptr, nullptr};
+    float last_inflate_ms = 0;               // HIP-event time of the last call's inflate kernel (stage timing >= 1, else 0)
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
     // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
     // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
@@ -887,6 +897,8 @@ void crass_hip_destroy(crass_hip_ctx *c)
     c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release(); c->x_rec_pos.release(); c->x_seq_off.release();
     c->x_h_tot.release(); c->x_h_rec_pos.release(); c->x_h_seq_off.release();
     for (auto &e : c->ev_x_time) if (e) (void)hipEventDestroy(e);
+    c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release(); c->z_h_verdict.release();
+    for (auto &e : c->ev_z_time) if (e) (void)hipEventDestroy(e);
     c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
     c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
     for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
@@ -1333,6 +1345,35 @@ int crass_hip_attach_device_text(crass_hip_ctx *c, const uint8_t *d_seqs, const 
 
 float crass_hip_last_pack_ms(const crass_hip_ctx *c) { return c ? c->last_pack_ms : 0.0f; }
 
+// n host bytes up into dst (device) through the two pinned staging buffers of crass_hip_load_text; bytes that are already pinned are
+// copied from where they are.  The context's stream waits for the last copy.
+static int upload_staged(crass_hip_ctx *c, const uint8_t *h_bytes, uint64_t n, uint8_t *dst)
+{
+    if (n == 0) return CRASS_OK;
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, 1), n);
+    hipPointerAttribute_t pa{};
+    const bool src_pinned = hipPointerGetAttributes(&pa, h_bytes) == hipSuccess && pa.type == hipMemoryTypeHost;
+    (void)hipGetLastError();                            // (pageable memory is reported as an invalid value: not an error of ours)
+    for (int k = 0; k < 2; k++) if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
+    int b = 0;
+    uint64_t k = 0;
+    for (uint64_t at = 0; at < n; at += cap, k++) {
+        b = (int)(k & 1);
+        const uint64_t bytes = std::min<uint64_t>(cap, n - at);
+        const uint8_t *from = h_bytes + at;
+        if (!src_pinned) {
+            HIPCHK(c, c->t_pin[b].ensure(cap));
+            if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
+            memcpy(c->t_pin[b].p, from, bytes);
+            from = c->t_pin[b].p;
+        }
+        HIPCHK(c, hipMemcpyAsync(dst + at, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));      // (the last copy: the copy stream runs them in order)
+    return CRASS_OK;
+}
+
 // ---- the raw bytes of a FASTA / FASTQ file in, parsed on the device (fastx_scan.hip) ----
 // h_bytes (host) or d_bytes (device).  Accepted: the state is that of crass_hip_load_text on the reads' text; declined: no reads.
 static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8_t *d_bytes, uint64_t n, int pad_uniform,
@@ -1355,30 +1396,9 @@ static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8
     else HIPCHK(c, hipMemcpy(&b0, d_bytes, 1, hipMemcpyDeviceToHost));
     if (!fx_is_hdr_char(b0)) return decline(0, 0, FX_FIRST_BYTE);
     if (h_bytes) {
-        // up through the two pinned staging buffers of crass_hip_load_text, into one device buffer; bytes that are already pinned
-        // are copied from where they are
         HIPCHK(c, c->x_raw.ensure(n + 16));
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, 1), n);
-        hipPointerAttribute_t pa{};
-        const bool src_pinned = hipPointerGetAttributes(&pa, h_bytes) == hipSuccess && pa.type == hipMemoryTypeHost;
-        (void)hipGetLastError();                        // (pageable memory is reported as an invalid value: not an error of ours)
-        for (int k = 0; k < 2; k++) if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
-        int b = 0;
-        uint64_t k = 0;
-        for (uint64_t at = 0; at < n; at += cap, k++) {
-            b = (int)(k & 1);
-            const uint64_t bytes = std::min<uint64_t>(cap, n - at);
-            const uint8_t *from = h_bytes + at;
-            if (!src_pinned) {
-                HIPCHK(c, c->t_pin[b].ensure(cap));
-                if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
-                memcpy(c->t_pin[b].p, from, bytes);
-                from = c->t_pin[b].p;
-            }
-            HIPCHK(c, hipMemcpyAsync(c->x_raw.p + at, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
-            HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
-        }
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));      // (the last copy: the copy stream runs them in order)
+        const int up = upload_staged(c, h_bytes, n, c->x_raw.p);
+        if (up) return up;
         d_bytes = c->x_raw.p;
     }
     FxJob J{};
@@ -1466,6 +1486,104 @@ int crass_hip_attach_device_fastx(crass_hip_ctx *c, const uint8_t *d_bytes, uint
 
 uint32_t crass_hip_fastx_tile_bytes(void) { return fastx_tile_bytes(); }
 float crass_hip_last_scan_ms(const crass_hip_ctx *c) { return c ? c->last_scan_ms : 0.0f; }
+
+// ---- BGZF members inflated on the device (inflate.hip) ----
+// the index is checked, d_in / d_out are device pointers: upload the offsets, launch, read the verdict
+static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_bgzf_index *ix, uint8_t *d_out, crass_bgzf_verdict *v)
+{
+    const uint64_t n = ix->n_members;
+    c->last_inflate_ms = 0;
+    if (n == 0) return CRASS_OK;
+    HIPCHK(c, c->z_idx.ensure(3 * n + 2)); HIPCHK(c, c->z_reason.ensure(n)); HIPCHK(c, c->z_verdict.ensure(1)); HIPCHK(c, c->z_h_verdict.ensure(1));
+    BzJob J{};
+    J.in = d_in; J.out = d_out; J.n_members = n;
+    J.in_off = c->z_idx.p; J.out_off = c->z_idx.p + (n + 1); J.data_off = c->z_idx.p + 2 * (n + 1);
+    J.reason = c->z_reason.p; J.verdict = c->z_verdict.p; J.hbm_window = c->env.inflate_hbm_window ? 1 : 0;
+    HIPCHK(c, hipMemcpyAsync(c->z_idx.p, ix->in_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->z_idx.p + (n + 1), ix->out_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->z_idx.p + 2 * (n + 1), ix->data_off, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_z_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_z_time[0], c->stream));
+    }
+    HIPCHK(c, launch_bgzf_inflate(J, c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_z_time[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the index's host arrays are the caller's: nothing reads them after this)
+    if (timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_z_time[0], c->ev_z_time[1]));
+        c->last_inflate_ms = ms;
+    }
+    const uint64_t w = c->z_h_verdict.p[0];
+    if (w == kBzNoOffence) return CRASS_OK;
+    if (v) { v->reason = (int32_t)(w & 0xFF); v->member = w >> 8; v->in_pos = ix->in_off[w >> 8]; }
+    return CRASS_ERR_UNSUPPORTED;
+}
+
+static void inflate_bgzf_release(crass_hip_ctx *c)
+{
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
+    c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release();
+}
+
+int crass_hip_inflate_bgzf_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, const crass_bgzf_index *ix, uint8_t *d_out, uint64_t out_cap,
+                                  crass_bgzf_verdict *v)
+{
+    if (v) memset(v, 0, sizeof(*v));
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    const int chk = bgzf_index_check(ix, n_in, out_cap);
+    if (chk) return chk;
+    if (ix->n_members && (!d_in || (ix->out_off[ix->n_members] && !d_out))) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const int s = inflate_bgzf_impl(c, d_in, ix, d_out, v);
+    inflate_bgzf_release(c);
+    return s;
+}
+
+static int load_fastx_bgzf_impl(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const crass_bgzf_index *ix, int pad_uniform,
+                                uint64_t read_index_base, uint8_t *d_text, crass_fastx_layout *out, crass_bgzf_verdict *v)
+{
+    const uint64_t n_text = ix->out_off[ix->n_members];
+    HIPCHK(c, c->z_raw.ensure(n_bytes + 16));
+    const int up = upload_staged(c, bytes, n_bytes, c->z_raw.p);
+    if (up) return up;
+    if (!d_text) { HIPCHK(c, c->z_text.ensure(n_text + 16)); d_text = c->z_text.p; }
+    const int s = inflate_bgzf_impl(c, c->z_raw.p, ix, d_text, v);
+    if (s) return s;
+    c->z_raw.release();                                 // (the compressed bytes are done with: the scan's arrays may have their room)
+    return load_fastx_impl(c, nullptr, d_text, n_text, pad_uniform, read_index_base, out);
+}
+
+int crass_hip_load_fastx_bgzf(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
+                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
+{
+    if (out) memset(out, 0, sizeof(*out));
+    if (v) memset(v, 0, sizeof(*v));
+    if (!c || pad_uniform < 0 || pad_uniform > 2 || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
+    crass_bgzf_index ix;
+    int s = crass_bgzf_index_host(bytes, n_bytes, &ix);
+    if (s == CRASS_OK && d_text && d_text_cap < ix.out_off[ix.n_members]) s = CRASS_ERR_INVALID_ARG;
+    if (s == CRASS_ERR_INVALID_ARG || s == CRASS_ERR_OOM) { crass_bgzf_index_free(&ix); return s; }
+    (void)hipSetDevice(c->device);
+    reset_results(c);
+    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
+    if (s == CRASS_ERR_UNSUPPORTED) { if (v) *v = ix.decline; return s; }
+    s = load_fastx_bgzf_impl(c, bytes, n_bytes, &ix, pad_uniform, read_index_base, d_text, out, v);
+    // the scratch goes back on every way out, as in load_fastx_common
+    inflate_bgzf_release(c);
+    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
+    c->x_rec_pos.release(); c->x_seq_off.release();
+    c->t_off.release();
+    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    crass_bgzf_index_free(&ix);
+    return s;
+}
+
+float crass_hip_last_inflate_ms(const crass_hip_ctx *c) { return c ? c->last_inflate_ms : 0.0f; }
 
 int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
 {

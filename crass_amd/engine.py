@@ -237,6 +237,71 @@ def fastx_scan_host(buf):
         lib.crass_fastx_layout_free(C.byref(v))
 
 
+class BgzfDeclined(CrassError):
+    """The BGZF index or a member's inflate declined the input (status 2): `reason` (inflate_core.h: 1 .. 9 a member's deflate data,
+    10 not BGZF), `member` and `in_pos` (the file position of that member's first byte); the caller takes the host readers."""
+
+    def __init__(self, status, where, verdict):
+        super().__init__(status, where)
+        self.reason, self.member, self.in_pos = int(verdict.reason), int(verdict.member), int(verdict.in_pos)
+        self.verdict = (self.reason, self.member, self.in_pos)
+
+
+class BgzfIndex:
+    """Where the members of a BGZF file are (crass_bgzf_index): n_members, in_off / out_off (uint64, n_members + 1), data_off
+    (uint64, n_members: where each member's deflate data starts), n_text = out_off[-1]."""
+
+    def __init__(self, in_off, out_off, data_off):
+        self.in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        self.out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        self.data_off = np.ascontiguousarray(data_off, dtype=np.uint64)
+        self.n_members = len(self.data_off)
+        if len(self.in_off) != self.n_members + 1 or len(self.out_off) != self.n_members + 1:
+            raise ValueError("a BGZF index has n + 1 input and output offsets for n members")
+        self.n_text = int(self.out_off[-1])
+
+    def _c(self):
+        v = _abi.BgzfIndexC()
+        v.n_members = self.n_members
+        v.in_off = self.in_off.ctypes.data_as(_abi.u64p)
+        v.out_off = self.out_off.ctypes.data_as(_abi.u64p)
+        v.data_off = self.data_off.ctypes.data_as(_abi.u64p) if self.n_members else None
+        return v
+
+
+def bgzf_index(buf):
+    """The walk over the members' headers and trailers of a BGZF file's bytes (crass_bgzf_index_host; no GPU needed): a BgzfIndex;
+    raises BgzfDeclined (reason 10) for anything else, a plain .gz among it."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    v = _abi.BgzfIndexC()
+    st = lib.crass_bgzf_index_host(a.ctypes.data if len(a) else None, len(a), C.byref(v))
+    try:
+        if st == 2:
+            raise BgzfDeclined(st, "crass_bgzf_index_host", v.decline)
+        _chk(st, "crass_bgzf_index_host")
+        n = int(v.n_members)
+        return BgzfIndex(_np(v.in_off, n + 1, np.uint64).copy(), _np(v.out_off, n + 1, np.uint64).copy(), _np(v.data_off, n, np.uint64).copy())
+    finally:
+        lib.crass_bgzf_index_free(C.byref(v))
+
+
+def bgzf_inflate_host(buf, index=None):
+    """The text of a BGZF file's bytes, member after member through the decoder the kernel runs (crass_bgzf_inflate_host; no GPU
+    needed): a uint8 array; raises BgzfDeclined with the verdict.  index: a BgzfIndex of the same bytes (default: bgzf_index(buf))."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    ix = bgzf_index(a) if index is None else index
+    out = np.zeros(ix.n_text, np.uint8)
+    ver = _abi.BgzfVerdict()
+    ixc = ix._c()
+    st = lib.crass_bgzf_inflate_host(a.ctypes.data if len(a) else None, len(a), C.byref(ixc), out.ctypes.data if len(out) else None, len(out), C.byref(ver))
+    if st == 2:
+        raise BgzfDeclined(st, "crass_bgzf_inflate_host", ver)
+    _chk(st, "crass_bgzf_inflate_host")
+    return out
+
+
 def fastx_header_ids(buf, rec_pos):
     """header_id[r] = index of the first read with the same name, from the file's bytes and the records' positions
     (crass_fastx_header_ids; host, names compared exactly).  rec_pos: n_reads + 1 entries as in a FastxLayout."""
@@ -668,6 +733,43 @@ class SearchEngine:
         st = self.lib.crass_hip_attach_device_fastx(self.h, int(tensor.data_ptr()) if tensor.numel() else None, int(tensor.numel()),
                                                     int(pad_uniform), int(read_index_base), C.byref(v))
         return self._fastx_result(st, v, "crass_hip_attach_device_fastx")
+
+    def inflate_bgzf_device(self, tensor_in, index, tensor_out):
+        """The members of a BGZF file whose bytes are in a torch uint8 DEVICE tensor (any alignment), inflated on the device into
+        tensor_out (the same; at least index.n_text bytes): crass_hip_inflate_bgzf_device.  index: the BgzfIndex of the same bytes.
+        Returns the bytes of text; raises BgzfDeclined with the host function's verdict.  The resident set is untouched."""
+        for t in (tensor_in, tensor_out):
+            if str(t.dtype) != "torch.uint8" or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("inflate_bgzf_device needs contiguous uint8 device tensors")
+        ver = _abi.BgzfVerdict()
+        ixc = index._c()
+        st = self.lib.crass_hip_inflate_bgzf_device(self.h, int(tensor_in.data_ptr()) if tensor_in.numel() else None, int(tensor_in.numel()), C.byref(ixc),
+                                                    int(tensor_out.data_ptr()) if tensor_out.numel() else None, int(tensor_out.numel()), C.byref(ver))
+        if st == 2:
+            raise BgzfDeclined(st, "crass_hip_inflate_bgzf_device", ver)
+        _chk(st, "crass_hip_inflate_bgzf_device")
+        return index.n_text
+
+    def load_fastx_bgzf(self, buf, pad_uniform=2, read_index_base=0, keep=None):
+        """The bytes of a BGZF-compressed FASTA / FASTQ file in host memory: indexed on the host, inflated, scanned and packed on
+        the device (crass_hip_load_fastx_bgzf).  Returns a FastxLayout, as attach_device_fastx on the inflated bytes would; raises
+        BgzfDeclined (the compression) or FastxDeclined (the text), nothing resident either way.  keep: a contiguous torch uint8
+        DEVICE tensor of at least the text's size — the text stays in its first layout.rec_pos[-1] bytes, for device_header_ids
+        and fetch_header_lines."""
+        a = _bytes_arg(buf)
+        if keep is not None and (str(keep.dtype) != "torch.uint8" or not keep.is_cuda or not keep.is_contiguous()):
+            raise ValueError("load_fastx_bgzf(keep=...) needs a contiguous uint8 device tensor")
+        v, ver = _abi.FastxLayoutC(), _abi.BgzfVerdict()
+        st = self.lib.crass_hip_load_fastx_bgzf(self.h, a.ctypes.data if len(a) else None, len(a), int(pad_uniform), int(read_index_base),
+                                                int(keep.data_ptr()) if keep is not None and keep.numel() else None,
+                                                int(keep.numel()) if keep is not None else 0, C.byref(v), C.byref(ver))
+        if st == 2 and ver.reason:
+            raise BgzfDeclined(st, "crass_hip_load_fastx_bgzf", ver)
+        return self._fastx_result(st, v, "crass_hip_load_fastx_bgzf")
+
+    def last_inflate_ms(self):
+        """HIP-event milliseconds of the last inflate_bgzf_device / load_fastx_bgzf call's inflate kernel (stage timing >= 1, else 0)."""
+        return float(self.lib.crass_hip_last_inflate_ms(self.h))
 
     def set_header_ids(self, arr):
         """header_id of the resident set (None: all headers unique), whichever call loaded it; drops earlier results as a load

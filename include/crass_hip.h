@@ -596,6 +596,61 @@ uint32_t crass_hip_fastx_tile_bytes(void);
  * between them included) of the last crass_hip_load_fastx_bytes / crass_hip_attach_device_fastx call; measured when the stage timing
  * level is >= 1, else 0; crass_hip_last_pack_ms then holds the pack kernel's.  (No reference counterpart: crass has no timers.) */
 float crass_hip_last_scan_ms(const crass_hip_ctx *ctx);
+/* ---- BGZF-compressed input, inflated on the device (inflate.hip) ----
+ * replaces: getFileHandle / gzopen (SeqUtils.cpp:100-126) for a .gz input written as BGZF (bgzip; Illumina's converters): a
+ * series of gzip members of at most 64 KB of text, each naming its compressed size in a 'BC' extra subfield and its text size in
+ * its trailer, so that the members' places in the input and in the output are known before anything is inflated and the members
+ * inflate side by side.  A file is either inflated exactly (the bytes zlib gives) or declined with a verdict; plain single-member
+ * gzip is declined (reason 10) and stays with the host readers.
+ * reason: 0 accepted, 1 block type 3, 2 stored block LEN != ~NLEN, 3 code lengths (over-subscribed or incomplete code — but a
+ * single distance code of one bit —, repeat code 16 first, a repeat past HLIT + HDIST, no end-of-block code, HLIT > 286, HDIST > 30),
+ * 4 a bit pattern that is no code, length symbol 286 / 287, distance symbol 30 / 31, 5 a distance beyond the member's own text,
+ * 6 the deflate data ends before the final block does, 7 / 8 more / less text than ISIZE, 9 CRC-32, 10 not BGZF.
+ * A member's verdict is the first reason its decoder meets; the file's is that of the first offending member; in_pos is the file
+ * position of that member's first byte.  Bits between a member's final block and its trailer are ignored. */
+typedef struct {
+    int32_t reason; uint64_t member; uint64_t in_pos;
+} crass_bgzf_verdict;
+typedef struct {
+    uint64_t n_members;
+    uint64_t *in_off;                      /* [n_members+1] member m is bytes[in_off[m] .. in_off[m+1]) */
+    uint64_t *out_off;                     /* [n_members+1] ... and inflates to text[out_off[m] .. out_off[m+1]) */
+    uint64_t *data_off;                    /* [n_members] where member m's deflate data starts; it ends 8 bytes before in_off[m+1] */
+    crass_bgzf_verdict decline;            /* reason 10 and the member that does not parse, when declined */
+} crass_bgzf_index;
+/* replaces: the same (gzopen's view of the file as one stream) — the walk over the members' headers and trailers, on the host: accepts
+ * what the host readers' side-by-side inflate accepts (the 28-byte end-of-file member, empty members anywhere, further extra
+ * subfields around 'BC'), with one difference: data_off honours FNAME / FCOMMENT / FHCRC, which that walk never looks at, so a
+ * member in which those fields run into the trailer is declined here; everything else: CRASS_ERR_UNSUPPORTED, out->decline filled, arrays NULL.  The arrays are malloc'd:
+ * crass_bgzf_index_free. */
+int  crass_bgzf_index_host(const uint8_t *bytes, uint64_t n_bytes, crass_bgzf_index *out);
+void crass_bgzf_index_free(crass_bgzf_index *ix);
+/* replaces: gzread (SeqUtils.cpp:100-126) — member after member through the decoder the kernel runs (inflate_core.h), on the host, no
+ * GPU needed: what the device is tested against.  CRASS_OK: out[0 .. out_off[n]) is the text.  CRASS_ERR_UNSUPPORTED: declined, *v
+ * (may be NULL) says why; out's contents are unspecified, nothing outside [out, out + out_cap) is written.  CRASS_ERR_INVALID_ARG:
+ * NULL pointers with work to do, out_cap < out_off[n], an index that is not ascending or reaches beyond n_bytes. */
+int  crass_bgzf_inflate_host(const uint8_t *bytes, uint64_t n_bytes, const crass_bgzf_index *index, uint8_t *out, uint64_t out_cap,
+                             crass_bgzf_verdict *v);
+/* replaces: gzread (SeqUtils.cpp:100-126) for compressed bytes that are in HBM: d_in and d_out are caller-owned DEVICE pointers of any
+ * alignment, index is the HOST index of the same bytes; its offsets go up into scratch that is given back before the call returns.
+ * One wave inflates one member (k_bgzf_inflate).  CRASS_OK: d_out[0 .. out_off[n]) equals zlib's text.  CRASS_ERR_UNSUPPORTED:
+ * declined, *v (may be NULL) equals crass_bgzf_inflate_host's verdict, d_out's contents are unspecified.  CRASS_ERR_INVALID_ARG (checked
+ * on the host, nothing is launched): as crass_bgzf_inflate_host.  The resident set is untouched either way. */
+int  crass_hip_inflate_bgzf_device(crass_hip_ctx *ctx, const uint8_t *d_in, uint64_t n_in, const crass_bgzf_index *index, uint8_t *d_out,
+                                   uint64_t out_cap, crass_bgzf_verdict *v);
+/* replaces: getFileHandle / gzopen + the kseq_read loop (SeqUtils.cpp:100-126, libcrispr.cpp:96-131) for a BGZF file's bytes in HOST
+ * memory: index on the host, the compressed bytes up through the staged buffers of crass_hip_load_text, inflate, then the device scan
+ * and pack of crass_hip_attach_device_fastx on the text — accepted means exactly what that call gives on the inflated bytes.
+ * d_text == NULL: the text lives in context scratch that is given back before the call returns.  d_text (DEVICE, d_text_cap >= the
+ * text's size, else CRASS_ERR_INVALID_ARG): the text stays there for crass_hip_fastx_header_ids_device /
+ * crass_hip_fetch_header_lines_device; its size is out->rec_pos[n_reads].  CRASS_ERR_UNSUPPORTED: a compression decline fills *v
+ * (may be NULL), a FASTA / FASTQ decline fills out->decline_reason (v->reason stays 0); no reads are resident either way. */
+int  crass_hip_load_fastx_bgzf(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                               uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v);
+/* HIP-event time, in milliseconds on the context's stream, of the inflate kernel of the last crass_hip_inflate_bgzf_device /
+ * crass_hip_load_fastx_bgzf call; measured when the stage timing level is >= 1, else 0.  (No reference counterpart: crass has no
+ * timers.) */
+float crass_hip_last_inflate_ms(const crass_hip_ctx *ctx);
 /* ---- the text of selected reads, out of the resident set ----
  * n records back to back: record k is chars[off[k] .. off[k+1]), off[n+1] the exclusive prefix sum of the records' lengths.
  * The gather and the unpacking run on the device (k_fetch_text, pack.hip), where the words are: only the selected reads'
