@@ -94,6 +94,12 @@ class BgzfVerdict(C.Structure):
     _fields_ = [("reason", C.c_int32), ("member", C.c_uint64), ("in_pos", C.c_uint64)]
 
 
+class FastxFilesLayoutC(C.Structure):
+    _fields_ = [("n_files", C.c_uint32), ("decline_file", C.c_int32), ("decline_reason", C.c_int32), ("max_len", C.c_uint32),
+                ("decline_pos", C.c_uint64), ("bgzf", BgzfVerdict), ("n_reads", C.c_uint64), ("file_read_base", u64p),
+                ("file_byte_base", u64p), ("format", C.POINTER(C.c_int32)), ("rec_pos", u64p), ("seq_off", u64p)]
+
+
 class BgzfIndexC(C.Structure):
     _fields_ = [("n_members", C.c_uint64), ("in_off", u64p), ("out_off", u64p), ("data_off", u64p), ("decline", BgzfVerdict)]
 
@@ -194,6 +200,12 @@ SYMBOLS = {
     "crass_hip_load_fastx_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(FastxLayoutC),
                                             C.POINTER(BgzfVerdict)]),
     "crass_hip_last_inflate_ms": (C.c_float, [C.c_void_p]),
+    "crass_fastx_files_scan_host": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.POINTER(FastxFilesLayoutC)]),
+    "crass_fastx_files_layout_free": (None, [C.POINTER(FastxFilesLayoutC)]),
+    "crass_hip_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.POINTER(FastxFilesLayoutC)]),
+    "crass_hip_resident_fastx": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),
+    "crass_hip_fetch_quality_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
+    "crass_hip_fetch_quality_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "crass_hip_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
     "crass_hip_fetch_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fetch_record_text": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Text)]),

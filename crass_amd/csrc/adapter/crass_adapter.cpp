@@ -16,6 +16,9 @@
 #include <unordered_map>
 #include <vector>
 #include <unistd.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
 
 namespace crass_hip {
 
@@ -581,6 +584,50 @@ bool want_streamed_ingest(const Vecstr &files)
     return text * 36 / 10 > avail / 4;
 }
 
+// CRASS_INGEST=device: the inputs mapped read-only, as they are on disk (an empty file: a NULL range of no bytes)
+struct MappedFiles {
+    std::vector<const uint8_t *> ptr; std::vector<uint64_t> len;
+    bool map(const std::string &path)
+    {
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return false; }
+        void *p = nullptr;
+        if (st.st_size > 0) {
+            p = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (p == MAP_FAILED) { close(fd); return false; }
+        }
+        close(fd);
+        ptr.push_back((const uint8_t *)p); len.push_back((uint64_t)st.st_size);
+        return true;
+    }
+    ~MappedFiles() { for (size_t k = 0; k < ptr.size(); k++) if (ptr[k]) munmap((void *)ptr[k], (size_t)len[k]); }
+};
+
+// the one line a declined input of the device reader gets: the file, the reason, the position
+std::string decline_message(const Vecstr &files, const crass_fastx_files_layout &lay)
+{
+    static const char *const fx[] = {"", "the file is empty", "byte 0 is neither '>' nor '@'", "the FASTQ lines are no multiple of 4", "a FASTQ record does not start with '@'",
+                                     "'>', '@' or '+' in a sequence line", "the third line of a FASTQ record does not start with '+'", "byte 127 in a quality line",
+                                     "a quality line is shorter than its sequence line", "a quality line is longer than its sequence line", "the file ends with a lone '>'",
+                                     "a read is longer than the device path takes"};
+    static const char *const bz[] = {"", "a deflate block of type 3", "a stored block whose length check fails", "bad code lengths", "a bit pattern that is no code",
+                                     "a distance beyond the member's text", "the deflate data ends early", "more text than the member's trailer says",
+                                     "less text than the member's trailer says", "a member's CRC-32 does not match", "gzip, but not BGZF (plain gzip stays with the host readers)"};
+    const std::string name = lay.decline_file >= 0 && (size_t)lay.decline_file < files.size() ? files[(size_t)lay.decline_file] : std::string("?");
+    std::string m = "crass [ERROR]: CRASS_INGEST=device cannot take " + name + ": ";
+    if (lay.bgzf.reason) {
+        const int r = lay.bgzf.reason;
+        m += std::string(r >= 1 && r <= 10 ? bz[r] : "compression") + " (BGZF reason " + std::to_string(r) + ", member " + std::to_string(lay.bgzf.member) +
+             ") at byte " + std::to_string(lay.bgzf.in_pos);
+    } else {
+        const int r = lay.decline_reason;
+        m += std::string(r >= 1 && r <= 11 ? fx[r] : "not a regular FASTA / FASTQ file") + " (reason " + std::to_string(r) + ") at byte " + std::to_string(lay.decline_pos);
+    }
+    return m;
+}
+
 // a hand-off record whose text (header, comment, sequence, quality) is still to come from its input file
 struct Fill { uint64_t idx; ReadHolder *h; bool low; };
 } // namespace
@@ -599,6 +646,11 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     std::vector<int> devs = g_devices;
     if (devs.empty()) devs.push_back(device());
     const bool local = g_local_copies;
+    // CRASS_INGEST=device: the inputs are mapped and go to the device as they are — parsed, inflated (BGZF) and packed there
+    // (crass_hip_load_fastx_files), the handed-on records' text fetched back from the device.  One device only.
+    const bool device_ingest = [] { const char *e = getenv("CRASS_INGEST"); return e && !strcmp(e, "device"); }();
+    if (device_ingest && devs.size() > 1)
+        throw input_error("crass [ERROR]: CRASS_INGEST=device needs one device, " + std::to_string(devs.size()) + " were asked for (--gpus / --devices)");
     // contexts (HIP start-up, code objects, RCCL communicators) come up on their own thread while this one reads the files
     struct Made { int rc = 0; crass_hip_ctx *c = nullptr; crass_hip_group *g = nullptr; };
     struct Pending {
@@ -634,7 +686,8 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             else if (rc != CRASS_ERR_UNSUPPORTED || force) chk(rc, "crass_index_fastx_files");
         }
     }
-    const bool streamed = !indexed && want_streamed_ingest(seqFiles);
+    const bool streamed = !indexed && !device_ingest && want_streamed_ingest(seqFiles);
+    MappedFiles M;
     JobFiles J;
     StreamedJob S;
     int max_len = 0;
@@ -644,7 +697,11 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     const char *dp_env = getenv("CRASS_DEVICE_PACK");
     const bool device_pack = dp_env && *dp_env && *dp_env != '0' && !indexed && !streamed && devs.size() == 1;
     const uint8_t *text_seq = nullptr; const uint64_t *text_off = nullptr; const uint64_t *text_hid = nullptr;
-    if (indexed) {
+    if (device_ingest) {
+        for (const std::string &f : seqFiles) if (!M.map(f)) CRASS_THROW(std::string("Could not open FASTQ ") + f + " for reading.");
+        memset(&r, 0, sizeof(r));
+        t1 = now();
+    } else if (indexed) {
         uint32_t ml = 0; int lr = 0;
         chk(crass_fastx_index_reads(IX.ix, &r, &ml, &lr), "crass_fastx_index_reads");
         n = r.n_reads; max_len = (int)ml;
@@ -761,6 +818,16 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     if (made.rc == CRASS_ERR_RCCL) CRASS_THROW(std::string("crass_hip_group_create: ") + crass_hip_group_last_error());
     chk(made.rc, made.g ? "crass_hip_group_create" : "crass_hip_create");
     crass_candidates c; crass_merge_view v; crass_recruits q;
+    crass_fastx_files_layout lay;
+    memset(&lay, 0, sizeof(lay));
+    if (device_ingest) {
+        // as soon as the context is up; a declined input is an error, as with a forced CRASS_INGEST=index
+        const int s = crass_hip_load_fastx_files(made.c, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, &lay);
+        if (s == CRASS_ERR_UNSUPPORTED && lay.decline_file >= 0) throw input_error(decline_message(seqFiles, lay));
+        chk(s, "crass_hip_load_fastx_files");
+        n = lay.n_reads; max_len = (int)lay.max_len;
+        if (timing) fprintf(stderr, "[crass_timing] %llu reads of %zu file(s) parsed and packed on the device (crass_hip_load_fastx_files)\n", (unsigned long long)n, seqFiles.size());
+    }
     // (the reads are resident on the device(s) once loaded: the host copy of a streamed job goes at once)
     auto drop_host_reads = [&] {
         if (!streamed) return;
@@ -778,7 +845,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             chk(crass_hip_group_get_merge(made.g, &v), "crass_hip_group_get_merge");
             chk(crass_hip_group_get_recruits(made.g, &q), "crass_hip_group_get_recruits");
         } else {
-            if (device_pack) {
+            if (device_ingest) {
+                // (loaded above)
+            } else if (device_pack) {
                 chk(crass_hip_load_text(made.c, text_seq, text_off, n, 2, text_hid, 0), "crass_hip_load_text");
                 if (timing) fprintf(stderr, "[crass_timing] %llu reads packed on the device (crass_hip_load_text)\n", (unsigned long long)n);
             } else chk(crass_hip_load_reads(made.c, &r), "crass_hip_load_reads");
@@ -816,7 +885,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     std::vector<ReadHolder *> cand_holders(c.n);
     for (uint64_t k = 0; k < c.n; k++) {
         ReadHolder *h = new ReadHolder();
-        if (streamed || indexed) fills.push_back(Fill{c.read_idx[k], h, c.low_lexi[k] != 0});
+        if (streamed || indexed || device_ingest) fills.push_back(Fill{c.read_idx[k], h, c.low_lexi[k] != 0});
         else {
             size_t f; uint64_t i;
             J.locate(c.read_idx[k], f, i);
@@ -869,7 +938,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     hlap();      // 2: groups, patterns
     for (uint64_t k = 0; k < q.n; k++) {
         ReadHolder *h = new ReadHolder();
-        if (streamed || indexed) fills.push_back(Fill{q.read_idx[k], h, q.low_lexi[k] != 0});
+        if (streamed || indexed || device_ingest) fills.push_back(Fill{q.read_idx[k], h, q.low_lexi[k] != 0});
         else {
             size_t f; uint64_t i;
             J.locate(q.read_idx[k], f, i);
@@ -888,6 +957,42 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     }
     hlap();      // 3: recruit holders
     double t_fill = 0;
+    if (device_ingest && !fills.empty()) {
+        // the handed-on records' text from the device: RH_Seq out of the resident packed set (oriented there), header lines and
+        // quality strings out of the files' text in the arena.  fills = pass 1's records, then pass 2's, in the getters' order.
+        const double tf0 = now();
+        const size_t nf = fills.size();
+        for (int pass = 1; pass <= 2; pass++) {
+            const size_t first = pass == 1 ? 0 : (size_t)c.n, cnt = pass == 1 ? (size_t)c.n : (size_t)q.n;
+            if (!cnt) continue;
+            crass_text t;
+            chk(crass_hip_fetch_record_text(made.c, pass, &t), "crass_hip_fetch_record_text");
+            if (t.n != cnt) CRASS_THROW("record text / record count mismatch");
+            for (size_t k = 0; k < cnt; k++) {          // (copied out before the next fetch takes the buffer)
+                ReadHolder &h = *fills[first + k].h;
+                h.RH_Seq.assign((const char *)t.chars + t.off[k], (size_t)(t.off[k + 1] - t.off[k]));
+                h.RH_WasLowLexi = fills[first + k].low;
+            }
+        }
+        const uint8_t *arena = nullptr; uint64_t arena_bytes = 0;
+        chk(crass_hip_resident_fastx(made.c, &arena, &arena_bytes), "crass_hip_resident_fastx");
+        std::vector<uint64_t> want(nf);
+        for (size_t k = 0; k < nf; k++) want[k] = fills[k].idx;
+        std::vector<uint32_t> name_len(nf);
+        std::vector<uint8_t> has_qual(nf);
+        crass_text hl, ql;
+        chk(crass_hip_fetch_header_lines_device(made.c, arena, arena_bytes, lay.rec_pos, lay.n_reads, want.data(), nf, &hl, name_len.data()), "crass_hip_fetch_header_lines_device");
+        chk(crass_hip_fetch_quality_device(made.c, arena, arena_bytes, lay.rec_pos, lay.n_reads, want.data(), nf, &ql, has_qual.data()), "crass_hip_fetch_quality_device");
+        for (size_t k = 0; k < nf; k++) {
+            ReadHolder &h = *fills[k].h;
+            const char *line = (const char *)hl.chars + hl.off[k];
+            const size_t len = (size_t)(hl.off[k + 1] - hl.off[k]), nl = std::min<size_t>(name_len[k], len);
+            h.RH_Header.assign(line, nl);                // kseq: the name ends at the first isspace() byte, the comment is the rest of the line behind it
+            if (nl < len) h.RH_Comment.assign(line + nl + 1, len - nl - 1);
+            if (has_qual[k]) { h.RH_Qual.assign((const char *)ql.chars + ql.off[k], (size_t)(ql.off[k + 1] - ql.off[k])); h.RH_IsFasta = false; }
+        }
+        t_fill = now() - tf0;
+    }
     if (indexed && !fills.empty()) {
         // the text of the records that are handed on, parsed from the mapping (crass_fastx_index_fetch: every core), then the
         // holders filled — also over the cores: a holder is its own object
@@ -959,9 +1064,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     std::cout << "\r[crass_singletonFinder]: Processed " << g_read_counter_p2 << " ..." << difftime(tnow, time_start) << " sec" << std::endl;
     if (timing)
         fprintf(stderr, "[crass_timing] searchAndRecruit: %llu reads on %zu device(s)%s; read+parse%s %.3f s, pack %.3f s, device (H2D + pass 1 + merge + pass 2) %.3f s, hand-off %.3f s%s\n",
-                (unsigned long long)n, devs.size(), streamed ? ", streamed ingest" : indexed ? ", indexed ingest" : "", (streamed || indexed) ? "+pack" : "", t1 - t0, t2 - t1, t3 - t2, now() - t3,
+                (unsigned long long)n, devs.size(), streamed ? ", streamed ingest" : indexed ? ", indexed ingest" : device_ingest ? ", device ingest" : "", (streamed || indexed) ? "+pack" : "", t1 - t0, t2 - t1, t3 - t2, now() - t3,
                 streamed ? (" (of which the second pass over the inputs " + std::to_string(t_fill) + " s)").c_str()
-                         : indexed ? (" (of which the handed-on records' text " + std::to_string(t_fill) + " s)").c_str() : "");
+                         : (indexed || device_ingest) ? (" (of which the handed-on records' text " + std::to_string(t_fill) + " s)").c_str() : "");
     if (timing)
         fprintf(stderr, "[crass_timing] searchAndRecruit: resident set after ingest %.0f MB, with the device context(s) up %.0f MB, at the end %.0f MB\n",
                 rss_ingested, rss_ctx, rss_mb());

@@ -34,6 +34,12 @@ public:
         : std::runtime_error(std::string("[ERROR]: ") + message + "\n" + file + " : " + std::to_string(line) + " : " + function) {}
 };
 
+// an input or an option the chosen reader does not take: what() is the one line to print (it starts with "crass [ERROR]: ")
+class input_error : public std::runtime_error {
+public:
+    explicit input_error(const std::string &line) : std::runtime_error(line) {}
+};
+
 // the hot-path subset of `options` (crassDefines.h:140-170) with the reference's field names
 struct options {
     int logLevel = 1;

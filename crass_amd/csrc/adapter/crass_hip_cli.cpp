@@ -40,7 +40,12 @@ static void usage()
                  "  --gpus N       shard the reads over GPUs 0..N-1 (one RCCL all-gather of the candidate DR strings per job)\n"
                  "  --devices L    the same with an explicit device list\n"
                  "  --seam         drive the engine through crass's three calls (searchFile / createNonRedundantSet /\n"
-                 "                 findSingletons: the DR merge then runs on the host) instead of the one-call device path\n";
+                 "                 findSingletons: the DR merge then runs on the host) instead of the one-call device path\n"
+                 "environment:\n"
+                 "  CRASS_INGEST=index|whole|stream|device   the reader of the inputs (default: index, and for what it does not take\n"
+                 "                 stream / whole).  device: the files are mapped and parsed, inflated (BGZF) and packed on the GPU,\n"
+                 "                 several files as one read set; one device only; an input it declines (plain gzip, irregular\n"
+                 "                 FASTA / FASTQ) is an error\n";
 }
 
 // CRASS_SMAPS_AT_EXIT=1: the mappings with the largest resident sets, at the end of every stage (what the kernel takes back at _exit)

@@ -299,6 +299,14 @@ struct crass_hip_ctx {
     // device (given back before the call returns) and their pinned host sides (hl_h_off and hl_h_chars are what crass_text points at)
     DevBuf<uint64_t> hl_src, hl_off; DevBuf<uint32_t> hl_len; DevBuf<uint8_t> hl_chars;
     PinBuf<uint64_t> hl_h_src, hl_h_off; PinBuf<uint32_t> hl_h_len; PinBuf<uint8_t> hl_h_chars;
+    // crass_hip_load_fastx_files: the arena (every file's text, a '\n' behind each) stays until the next load, attach or destroy
+    // (drop_arena); the pinned per-file arrays crass_fastx_files_layout points at (read bases, byte bases, formats)
+    DevBuf<uint8_t> fa_arena; uint64_t fa_bytes = 0; bool have_arena = false;
+    PinBuf<uint64_t> fa_h_base; PinBuf<int32_t> fa_h_format;
+    // crass_hip_fetch_quality_device: the records' positions and ends, the quality lines' starts, lengths and flags, offsets and
+    // the strings on the device (given back before the call returns) and their pinned host sides (ql_h_off, ql_h_chars: crass_text)
+    DevBuf<uint64_t> ql_src, ql_start, ql_off; DevBuf<uint32_t> ql_len; DevBuf<uint8_t> ql_chars;
+    PinBuf<uint64_t> ql_h_src, ql_h_off; PinBuf<uint32_t> ql_h_len; PinBuf<uint8_t> ql_h_chars;
 
     // scratch
     DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;
@@ -906,6 +914,9 @@ void crass_hip_destroy(crass_hip_ctx *c)
     for (auto &e : c->ev_n_time) if (e) (void)hipEventDestroy(e);
     c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
     c->hl_h_src.release(); c->hl_h_off.release(); c->hl_h_len.release(); c->hl_h_chars.release();
+    c->fa_arena.release(); c->fa_h_base.release(); c->fa_h_format.release();
+    c->ql_src.release(); c->ql_start.release(); c->ql_off.release(); c->ql_len.release(); c->ql_chars.release();
+    c->ql_h_src.release(); c->ql_h_off.release(); c->ql_h_len.release(); c->ql_h_chars.release();
     for (int k = 0; k < 2; k++) {
         c->t_dev[k].release(); c->t_pin[k].release();
         if (c->ev_t_copy[k]) (void)hipEventDestroy(c->ev_t_copy[k]);
@@ -1027,6 +1038,14 @@ static int setup_pos_hints(crass_hip_ctx *c, const uint32_t *lengths, uint32_t u
 static int first_call_bounds(crass_hip_ctx *c);
 static void presize_hostloop(crass_hip_ctx *c);
 
+// the file arena of crass_hip_load_fastx_files goes with the read set it belongs to: every public load and attach calls this
+// (load_text_impl, the pack step those calls share with crass_hip_load_fastx_files itself, does not)
+static void drop_arena(crass_hip_ctx *c)
+{
+    if (c->fa_arena.p) { (void)hipStreamSynchronize(c->stream); c->fa_arena.release(); }
+    c->have_arena = false; c->fa_bytes = 0;
+}
+
 static void reset_results(crass_hip_ctx *c)
 {
     quiesce_worker(c);
@@ -1068,6 +1087,7 @@ int crass_hip_load_reads(crass_hip_ctx *c, const crass_reads *h)
     (void)hipSetDevice(c->device);
     reset_results(c);
     c->have_reads = false;                              // (a failure below must not leave the previous reads half replaced)
+    drop_arena(c);
     const uint64_t n = h->n_reads;
     // host-side scan for the total word count / max length
     uint64_t total_words = 0;
@@ -1135,6 +1155,7 @@ int crass_hip_attach_device_reads(crass_hip_ctx *c, const crass_reads *d)
     (void)hipSetDevice(c->device);
     reset_results(c);
     c->have_reads = false;
+    drop_arena(c);
     DevReads R{};
     R.packed = d->packed; R.n_reads = d->n_reads; R.stride_words = d->stride_words; R.uniform_len = d->uniform_len;
     R.header_id = d->header_id;
@@ -1320,6 +1341,8 @@ static int load_text_impl(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t
 static int load_text_common(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t *d_seqs, const uint64_t *off, uint64_t n,
                             int pad_uniform, const uint64_t *header_id, uint64_t read_index_base)
 {
+    // (with arguments load_text_impl refuses, the resident set and its arena stay)
+    if (c && pad_uniform >= 0 && pad_uniform <= 2 && !(n && ((!h_seqs && !d_seqs) || !off))) { (void)hipSetDevice(c->device); drop_arena(c); }
     const int s = load_text_impl(c, h_seqs, d_seqs, off, n, pad_uniform, header_id, read_index_base);
     if (c) {
         // what only this call needed goes back, on every way out: the text's offsets (8 bytes per read) and the two staged chunks
@@ -1385,6 +1408,7 @@ static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8
     (void)hipSetDevice(c->device);
     reset_results(c);
     c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    drop_arena(c);
     c->last_scan_ms = 0; c->last_pack_ms = 0;
     auto decline = [&](int32_t format, uint64_t pos, int32_t reason) {
         if (out) { out->format = format; out->decline_pos = pos; out->decline_reason = reason; }
@@ -1570,6 +1594,7 @@ int crass_hip_load_fastx_bgzf(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n
     (void)hipSetDevice(c->device);
     reset_results(c);
     c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    drop_arena(c);
     c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
     if (s == CRASS_ERR_UNSUPPORTED) { if (v) *v = ix.decline; return s; }
     s = load_fastx_bgzf_impl(c, bytes, n_bytes, &ix, pad_uniform, read_index_base, d_text, out, v);
@@ -1749,6 +1774,258 @@ int crass_hip_fetch_header_lines_device_to(crass_hip_ctx *c, const uint8_t *d_by
     if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
     static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
     return header_lines_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, name_len_out);
+}
+
+// ---- several files into one resident set (fastx_scan.hip, inflate.hip, fastx_names.hip) ----
+namespace {
+struct FilesPlan {
+    struct File { bool bgzf = false; crass_bgzf_index ix{}; uint64_t n_text = 0; int32_t format = 0; };
+    std::vector<File> f;
+    ~FilesPlan() { for (auto &x : f) if (x.bgzf) crass_bgzf_index_free(&x.ix); }
+};
+}
+
+static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
+                                 crass_fastx_files_layout *out)
+{
+    // a decline found before the scan (format, compression) waits here: a file in front of it may still offend in the scan
+    int32_t pend_file = -1, pend_reason = 0; uint64_t pend_pos = 0; crass_bgzf_verdict pend_v{};
+    auto decline = [&](uint32_t file, int32_t reason, uint64_t pos, const crass_bgzf_verdict *v) {
+        if (out) { out->decline_file = (int32_t)file; out->decline_reason = reason; out->decline_pos = pos; if (v) out->bgzf = *v; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    // 1. what every file is, and how much text it holds (host: first bytes, BGZF index)
+    FilesPlan P;
+    P.f.resize(n_files);
+    uint32_t nf = n_files;
+    for (uint32_t f = 0; f < nf; f++) {
+        FilesPlan::File &F = P.f[f];
+        const uint8_t *b = bytes[f];
+        const uint64_t n = n_bytes[f];
+        if (n >= 2 && b[0] == 0x1F && b[1] == 0x8B) {
+            const int s = crass_bgzf_index_host(b, n, &F.ix);
+            if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = F.ix.decline; nf = f; break; }
+            if (s) return s;
+            F.bgzf = true; F.n_text = F.ix.out_off[F.ix.n_members];
+            if (F.n_text == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
+        } else {
+            if (n == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
+            if (!fx_is_hdr_char(b[0])) { pend_file = (int32_t)f; pend_reason = FX_FIRST_BYTE; nf = f; break; }
+            F.n_text = n; F.format = b[0];
+        }
+    }
+    auto pending = [&]() { return decline((uint32_t)pend_file, pend_reason, pend_pos, pend_v.reason ? &pend_v : nullptr); };
+    if (nf == 0) return pending();
+    // 2. the arena; every file's bytes up, a BGZF file inflated into its place; the first two scan kernels of file f are queued
+    //    before file f + 1 is staged
+    std::vector<uint64_t> base(nf + 1, 0), tile0(nf + 1, 0);
+    for (uint32_t f = 0; f < nf; f++) base[f + 1] = base[f] + P.f[f].n_text + 1;
+    HIPCHK(c, c->fa_arena.ensure(base[nf] + 16));
+    uint8_t *arena = c->fa_arena.p;
+    for (uint32_t f = 0; f < nf; f++) {
+        tile0[f + 1] = tile0[f] + fastx_n_tiles(arena + base[f], P.f[f].n_text);
+    }
+    if (tile0[nf] > 0x7FFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    HIPCHK(c, c->x_tiles.ensure(tile0[nf])); HIPCHK(c, c->x_base.ensure(tile0[nf]));
+    HIPCHK(c, c->x_tot.ensure(5 * (uint64_t)nf)); HIPCHK(c, c->x_h_tot.ensure(5 * (uint64_t)nf));      // [4 f ..): the totals; [4 nf + f]: the verdict
+    std::vector<FxJob> jobs(nf);
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_x_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_x_time[0], c->stream));
+    }
+    for (uint32_t f = 0; f < nf; f++) {
+        FilesPlan::File &F = P.f[f];
+        if (f) HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // (the staged buffers are the file before's until its last copy is done)
+        if (F.bgzf) {
+            HIPCHK(c, c->z_raw.ensure(n_bytes[f] + 16));
+            const int up = upload_staged(c, bytes[f], n_bytes[f], c->z_raw.p);
+            if (up) return up;
+            crass_bgzf_verdict v{};
+            const int s = inflate_bgzf_impl(c, c->z_raw.p, &F.ix, arena + base[f], &v);      // (waits for the stream: z_raw may be used again)
+            if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_reason = 0; pend_v = v; nf = f; break; }
+            if (s) return s;
+            HIPCHK(c, hipMemcpy(&F.format, arena + base[f], 1, hipMemcpyDeviceToHost));
+            F.format &= 0xFF;
+            if (!fx_is_hdr_char((uint8_t)F.format)) { pend_file = (int32_t)f; pend_reason = FX_FIRST_BYTE; pend_v = crass_bgzf_verdict{}; nf = f; break; }
+        } else {
+            const int up = upload_staged(c, bytes[f], n_bytes[f], arena + base[f]);
+            if (up) return up;
+        }
+        FxJob &J = jobs[f];
+        J = FxJob{};
+        J.bytes = arena + base[f]; J.n = F.n_text; J.lead = (uint32_t)((uintptr_t)J.bytes & 15u); J.format = F.format;
+        J.n_tiles = tile0[f + 1] - tile0[f];
+        J.tiles = c->x_tiles.p + tile0[f]; J.base = c->x_base.p + tile0[f]; J.tot = c->x_tot.p + 4 * (uint64_t)f;
+        HIPCHK(c, launch_fx_summary(J, c->stream));
+        HIPCHK(c, launch_fx_tile_scan(J, c->stream));
+    }
+    if (nf == 0) return pending();
+    for (uint32_t f = 0; f < nf; f++) HIPCHK(c, hipMemsetAsync(arena + base[f + 1] - 1, 0x0A, 1, c->stream));      // the '\n' behind every file
+    const uint32_t nf_alloc = (uint32_t)jobs.size();          // (the verdict words lie behind the totals of every planned file)
+    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p, c->x_tot.p, 4 * (uint64_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the record counts size the next kernels' arrays)
+    // 3. every file emits into one text and one pair of per-record arrays
+    std::vector<uint64_t> rbase(nf + 1, 0), tbase(nf + 1, 0);
+    for (uint32_t f = 0; f < nf; f++) { rbase[f + 1] = rbase[f] + c->x_h_tot.p[4 * f + 1]; tbase[f + 1] = tbase[f] + c->x_h_tot.p[4 * f + 2]; }
+    const uint64_t nr = rbase[nf], total_seq = tbase[nf];
+    if (nr >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (the name table holds 32-bit indices)
+    HIPCHK(c, c->x_text.ensure(total_seq + 32));
+    HIPCHK(c, c->x_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_seq_off.ensure(nr + 1));
+    HIPCHK(c, c->x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_h_seq_off.ensure(nr + 1));
+    unsigned long long *d_verdict = reinterpret_cast<unsigned long long *>(c->x_tot.p + 4 * (uint64_t)nf_alloc);
+    HIPCHK(c, hipMemsetAsync(d_verdict, 0xFF, 8 * (uint64_t)nf, c->stream));
+    for (uint32_t f = 0; f < nf; f++) {
+        FxJob &J = jobs[f];
+        J.n_lines = c->x_h_tot.p[4 * f]; J.n_reads = rbase[f + 1] - rbase[f];
+        J.text = c->x_text.p; J.text_base = tbase[f]; J.text_cap = tbase[f + 1];
+        J.rec_pos = c->x_rec_pos.p; J.seq_off = c->x_seq_off.p; J.read_base = rbase[f]; J.arena_base = base[f];
+        J.verdict = d_verdict + f;
+        HIPCHK(c, launch_fx_emit(J, c->stream));
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_x_time[1], c->stream));
+    uint64_t *h_verdict = c->x_h_tot.p + 4 * (uint64_t)nf_alloc;
+    HIPCHK(c, hipMemcpyAsync(h_verdict, d_verdict, 8 * (uint64_t)nf, hipMemcpyDeviceToHost, c->stream));
+    if (nr) {
+        HIPCHK(c, hipMemcpyAsync(c->x_h_rec_pos.p, c->x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->x_h_seq_off.p, c->x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x_time[0], c->ev_x_time[1]));
+        c->last_scan_ms = ms;
+    }
+    // 4. the verdict: the first file in order that offends
+    uint64_t *rec_pos = c->x_h_rec_pos.p, *seq_off = c->x_h_seq_off.p;
+    rec_pos[nr] = base[nf] - 1; seq_off[nr] = total_seq;
+    uint64_t max_len = 0;
+    for (uint32_t f = 0; f < nf; f++) {
+        const uint64_t verdict = h_verdict[f];
+        if (verdict != kFxNoOffence) return decline(f, (int32_t)(verdict & 0xFF), verdict >> 8, nullptr);
+        const uint64_t seq_f = tbase[f + 1] - tbase[f];
+        if (rbase[f + 1] == rbase[f] || c->x_h_tot.p[4 * f + 3] != (P.f[f].format == 0x40 ? seq_f : 0)) return CRASS_ERR_STATE;      // (never expected, as in load_fastx_impl)
+        for (uint64_t r = rbase[f]; r < rbase[f + 1]; r++) {
+            const uint64_t l = (r + 1 < rbase[f + 1] ? seq_off[r + 1] : tbase[f + 1]) - seq_off[r];
+            if (l > CRASS_HIP_MAX_READ_LEN) return decline(f, FX_READ_TOO_LONG, rec_pos[r] - base[f], nullptr);
+            max_len = std::max(max_len, l);
+        }
+    }
+    if (pend_file >= 0) return pending();
+    // 5. one pack launch over the joined text, then the header ids on the arena, installed from where they are
+    const int s = load_text_impl(c, nullptr, c->x_text.p, seq_off, nr, pad_uniform, nullptr, 0);
+    if (s) return s;
+    uint64_t n_rep = 0;
+    const int hs = header_ids_device_impl(c, arena, base[nf], rec_pos, nr, nullptr, 1, &n_rep);
+    if (hs) { c->have_reads = false; return hs; }
+    if (n_rep == 0) c->R.header_id = nullptr;           // (all names unique: as a load without header ids)
+    HIPCHK(c, c->fa_h_base.ensure(2 * ((uint64_t)nf + 1))); HIPCHK(c, c->fa_h_format.ensure(nf));
+    for (uint32_t f = 0; f <= nf; f++) { c->fa_h_base.p[f] = rbase[f]; c->fa_h_base.p[nf + 1 + f] = base[f]; }
+    for (uint32_t f = 0; f < nf; f++) c->fa_h_format.p[f] = P.f[f].format;
+    c->fa_bytes = base[nf]; c->have_arena = true;
+    if (out) {
+        out->n_reads = nr; out->max_len = (uint32_t)max_len; out->rec_pos = rec_pos; out->seq_off = seq_off;
+        out->file_read_base = c->fa_h_base.p; out->file_byte_base = c->fa_h_base.p + nf + 1; out->format = c->fa_h_format.p;
+    }
+    return CRASS_OK;
+}
+
+int crass_hip_load_fastx_files(crass_hip_ctx *c, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
+                               crass_fastx_files_layout *out)
+{
+    if (out) { memset(out, 0, sizeof(*out)); out->decline_file = -1; out->n_files = n_files; }
+    if (!c || !n_files || !bytes || !n_bytes || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
+    for (uint32_t f = 0; f < n_files; f++) if (n_bytes[f] && !bytes[f]) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    reset_results(c);
+    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    drop_arena(c);
+    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
+    const int s = load_fastx_files_impl(c, bytes, n_bytes, n_files, pad_uniform, out);
+    // the scratch goes back on every way out, as in load_fastx_common; the arena stays only with an accepted set
+    inflate_bgzf_release(c);
+    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
+    c->x_rec_pos.release(); c->x_seq_off.release();
+    c->t_off.release();
+    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
+    if (s) { c->have_reads = false; drop_arena(c); }
+    return s;
+}
+
+int crass_hip_resident_fastx(const crass_hip_ctx *c, const uint8_t **d_bytes, uint64_t *n_bytes)
+{
+    if (!c || !d_bytes || !n_bytes) return CRASS_ERR_INVALID_ARG;
+    *d_bytes = nullptr; *n_bytes = 0;
+    if (!c->have_arena || !c->have_reads) return CRASS_ERR_STATE;
+    *d_bytes = c->fa_arena.p; *n_bytes = c->fa_bytes;
+    return CRASS_OK;
+}
+
+// ---- quality strings of selected records from raw bytes on the device (fastx_names.hip) ----
+// the shape of header_lines_impl: every check comes before the first launch; the resident set is not involved
+static int quality_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                        const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out, uint8_t *has_qual_out)
+{
+    for (uint64_t k = 0; k < n; k++) if (idx[k] >= n_reads || rec_pos[idx[k]] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, c->ql_h_off.ensure(n + 1));
+    uint64_t *off = c->ql_h_off.p;
+    off[0] = 0;
+    QlJob J{};
+    J.bytes = d_bytes; J.n_bytes = n_bytes; J.n = n;
+    if (n) {
+        HIPCHK(c, c->ql_h_src.ensure(2 * n)); HIPCHK(c, c->ql_h_len.ensure(2 * n));
+        HIPCHK(c, c->ql_src.ensure(2 * n)); HIPCHK(c, c->ql_start.ensure(n)); HIPCHK(c, c->ql_len.ensure(2 * n));
+        for (uint64_t k = 0; k < n; k++) { c->ql_h_src.p[k] = rec_pos[idx[k]]; c->ql_h_src.p[n + k] = std::min(rec_pos[idx[k] + 1], n_bytes); }
+        J.src = c->ql_src.p; J.lim = c->ql_src.p + n; J.start = c->ql_start.p; J.len = c->ql_len.p; J.flags = c->ql_len.p + n;
+        HIPCHK(c, hipMemcpyAsync(c->ql_src.p, c->ql_h_src.p, 2 * n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_ql_measure(J, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ql_h_len.p, c->ql_len.p, 2 * n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the lengths size the result)
+        for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + c->ql_h_len.p[k];
+        if (has_qual_out) for (uint64_t k = 0; k < n; k++) has_qual_out[k] = (uint8_t)(c->ql_h_len.p[n + k] & 1u);
+    }
+    const uint64_t total = off[n];
+    if (off_user) memcpy(off_user, off, (n + 1) * 8);
+    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
+    if (!d_user) HIPCHK(c, c->ql_h_chars.ensure(total));
+    if (out) { out->n = n; out->chars = c->ql_h_chars.p; out->off = off; }
+    if (!total) return CRASS_OK;
+    HIPCHK(c, c->ql_off.ensure(n + 1));
+    if (!d_user) HIPCHK(c, c->ql_chars.ensure(total));
+    HIPCHK(c, hipMemcpyAsync(c->ql_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    J.off = c->ql_off.p; J.total = total; J.out = d_user ? d_user : c->ql_chars.p;
+    HIPCHK(c, launch_ql_copy(J, c->stream));
+    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->ql_h_chars.p, c->ql_chars.p, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CRASS_OK;
+}
+
+static int quality_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                          const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out, uint8_t *has_qual_out)
+{
+    if (!c || (n && !idx) || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
+    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    const int s = quality_impl(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_user, cap, off_user, out, has_qual_out);
+    (void)hipStreamSynchronize(c->stream);              // the device scratch goes back on every way out; the pinned result stays
+    c->ql_src.release(); c->ql_start.release(); c->ql_off.release(); c->ql_len.release(); c->ql_chars.release();
+    return s;
+}
+
+int crass_hip_fetch_quality_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                   const uint64_t *idx, uint64_t n, crass_text *out, uint8_t *has_qual_out)
+{
+    if (!out) return CRASS_ERR_INVALID_ARG;
+    return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, nullptr, 0, nullptr, out, has_qual_out);
+}
+
+int crass_hip_fetch_quality_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                      const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out, uint8_t *has_qual_out)
+{
+    if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
+    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
+    return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, has_qual_out);
 }
 
 int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)

@@ -41,6 +41,10 @@ struct FxJob {
     uint8_t *text;          // [text_cap] the reads' bytes back to back (16-byte aligned)
     uint64_t *rec_pos, *seq_off;      // [n_reads]
     unsigned long long *verdict;      // the smallest fx_offence, kFxNoOffence before the launch
+    // several files into one set (crass_hip_load_fastx_files; all 0 for a file on its own): this file's record r is entry
+    // read_base + r of rec_pos / seq_off, its sequence bytes start at text[text_base] (text_cap: where they end), and rec_pos holds
+    // arena_base + the file position.  Offences stay in file positions.
+    uint64_t text_base, read_base, arena_base;
 };
 uint32_t fastx_tile_bytes();
 uint64_t fastx_n_tiles(const uint8_t *bytes, uint64_t n);

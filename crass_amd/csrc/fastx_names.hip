@@ -25,6 +25,13 @@
 // header lines — k_hl_measure: a lane per selected record walks its header line: bytes up to the '\n' (or the input's end) and the
 // name's length.  The host sums the lengths.  k_hl_copy: driven by the OUTPUT, a lane per byte finds its record in the offsets;
 // nothing outside [out, out + total) is stored.  Neither is hot: about one read in a hundred is handed on.
+//
+// quality strings (RH_Qual) — the same shape.  k_ql_measure: a lane per selected record; a record whose header character is '@'
+// has its quality on its fourth line, found by three line ends from the header character and bounded by the next record's header
+// character: the string is the bytes 33..126 of that line, as kseq keeps them (a '\r' in front of the '\n' is none).  A '>'
+// record has none.  k_ql_copy: a lane per output byte; where the line's first bytes are the string (every line but one with
+// blanks inside) the byte is at start + k, else the lane walks the line to its k-th such byte.  No byte outside
+// [src, min(lim, n_bytes)) of a record is read.
 #include "fastx_names_launch.h"
 #include "devmem.h"
 
@@ -294,6 +301,53 @@ __global__ __launch_bounds__(kNmThreads) void k_hl_copy(const HlJob J)
     if (p < J.n_bytes) J.out[i] = J.bytes[p];
 }
 
+static __device__ __forceinline__ bool ql_is_graph(uint8_t b) { return b >= 33 && b <= 126; }
+
+__global__ __launch_bounds__(kNmThreads) void k_ql_measure(const QlJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uint64_t p0 = J.src[k];
+    const uint64_t end = J.lim[k] < J.n_bytes ? J.lim[k] : J.n_bytes;
+    uint64_t start = p0;
+    uint32_t len = 0, flags = 0;
+    if (p0 < end && J.bytes[p0] == 0x40) {
+        flags = 1u;
+        uint64_t p = p0;
+        for (uint32_t lines = 0; lines < 3 && p < end; p++) lines += J.bytes[p] == 0x0A ? 1u : 0u;      // behind the third line end
+        start = p;
+        bool gap = false, dense = true;
+        for (; p < end; p++) {
+            const uint8_t b = J.bytes[p];
+            if (b == 0x0A) break;
+            if (ql_is_graph(b)) { if (gap) dense = false; if (len != 0xFFFFFFFFu) len++; }
+            else gap = true;
+        }
+        if (dense) flags |= 2u;
+    }
+    J.start[k] = start; J.len[k] = len; J.flags[k] = flags;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_ql_copy(const QlJob J)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (i >= J.total) return;
+    uint64_t a = 0, b = J.n - 1;                        // the last record whose offset is <= i, as in k_hl_copy
+    while (a < b) {
+        const uint64_t mid = (a + b + 1) >> 1;
+        if (J.off[mid] <= i) a = mid; else b = mid - 1;
+    }
+    const uint64_t k = i - J.off[a];
+    const uint64_t end = J.lim[a] < J.n_bytes ? J.lim[a] : J.n_bytes;
+    uint64_t p = J.start[a];
+    if (J.flags[a] & 2u) p += k;
+    else {                                              // the line's k-th byte in 33..126
+        uint64_t seen = 0;
+        for (; p < end; p++) if (ql_is_graph(J.bytes[p]) && seen++ == k) break;
+    }
+    if (p < end) J.out[i] = J.bytes[p];
+}
+
 uint32_t hid_lane_max() { return kHidLaneMax; }
 
 static bool nm_grid(uint64_t items, uint64_t per_block, unsigned *blocks)
@@ -341,6 +395,22 @@ hipError_t launch_hl_copy(const HlJob &J, hipStream_t st)
     unsigned g;
     if (!J.n || !nm_grid(J.total, kNmThreads, &g)) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_hl_copy, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_ql_measure(const QlJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_ql_measure, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_ql_copy(const QlJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!J.n || !nm_grid(J.total, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_ql_copy, dim3(g), dim3(kNmThreads), 0, st, J);
     return hipGetLastError();
 }
 

@@ -40,4 +40,19 @@ struct HlJob {
 hipError_t launch_hl_measure(const HlJob &J, hipStream_t st);
 hipError_t launch_hl_copy(const HlJob &J, hipStream_t st);
 
+// k_ql_measure / k_ql_copy: the quality strings of selected records
+struct QlJob {
+    const uint8_t *bytes; uint64_t n_bytes;
+    const uint64_t *src;             // [n] position of the record's header character (< n_bytes)
+    const uint64_t *lim;             // [n] where the record ends: the next record's header character, or the end of the last file
+    uint64_t n;
+    uint64_t *start;                 // [n] k_ql_measure: position of the first byte of the record's fourth line
+    uint32_t *len, *flags;           // [n] its bytes 33..126; bit 0: a FASTQ record, bit 1: those bytes lie back to back at start
+    const uint64_t *off;             // [n + 1] k_ql_copy: where the records lie in out
+    uint64_t total;                  // off[n]
+    uint8_t *out;                    // [total], any alignment
+};
+hipError_t launch_ql_measure(const QlJob &J, hipStream_t st);
+hipError_t launch_ql_copy(const QlJob &J, hipStream_t st);
+
 } // namespace crass

@@ -95,6 +95,74 @@ void crass_fastx_layout_free(crass_fastx_layout *l)
     l->rec_pos = nullptr; l->seq_off = nullptr;
 }
 
+// several files as one set (crass_hip_load_fastx_files' restatement): file after file, the first that is declined ends the walk
+int crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, crass_fastx_files_layout *out)
+{
+    if (!out) return CRASS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->decline_file = -1;
+    if (!n_files || !bytes || !n_bytes) return CRASS_ERR_INVALID_ARG;
+    for (uint32_t f = 0; f < n_files; f++) if (n_bytes[f] && !bytes[f]) return CRASS_ERR_INVALID_ARG;
+    out->n_files = n_files;
+    std::vector<uint64_t> read_base(1, 0), byte_base(1, 0), rec_pos, seq_off;
+    std::vector<int32_t> format;
+    uint32_t max_len = 0;
+    int status = CRASS_OK;
+    try {
+        std::vector<uint8_t> text;
+        for (uint32_t f = 0; f < n_files && status == CRASS_OK; f++) {
+            const uint8_t *b = bytes[f];
+            uint64_t n = n_bytes[f];
+            if (n >= 2 && b[0] == 0x1F && b[1] == 0x8B) {      // compressed: BGZF or nothing
+                crass_bgzf_index ix;
+                status = crass_bgzf_index_host(b, n, &ix);
+                if (status == CRASS_ERR_UNSUPPORTED) { out->decline_file = (int32_t)f; out->bgzf = ix.decline; }
+                if (status == CRASS_OK) {
+                    text.resize(ix.out_off[ix.n_members] + 1);
+                    crass_bgzf_verdict v;
+                    memset(&v, 0, sizeof(v));
+                    status = crass_bgzf_inflate_host(b, n, &ix, text.data(), text.size(), &v);
+                    if (status == CRASS_ERR_UNSUPPORTED) { out->decline_file = (int32_t)f; out->bgzf = v; }
+                    n = ix.out_off[ix.n_members]; b = text.data();
+                }
+                crass_bgzf_index_free(&ix);
+                if (status != CRASS_OK) break;
+            }
+            crass::FxHostScan h;
+            status = crass::fastx_scan_serial(b, n, &h);
+            if (status == CRASS_ERR_UNSUPPORTED) { out->decline_file = (int32_t)f; out->decline_reason = h.reason; out->decline_pos = h.decline_pos; }
+            if (status == CRASS_OK) {
+                const uint64_t t0 = seq_off.empty() ? 0 : seq_off.back();
+                if (!seq_off.empty()) { rec_pos.pop_back(); seq_off.pop_back(); }      // (the entry behind the file before)
+                for (uint64_t r = 0; r <= h.n_reads; r++) { rec_pos.push_back(byte_base.back() + h.rec_pos[r]); seq_off.push_back(t0 + h.seq_off[r]); }
+                read_base.push_back(read_base.back() + h.n_reads);
+                byte_base.push_back(byte_base.back() + n + 1);      // (the '\n' behind the file)
+                format.push_back(h.format);
+                max_len = std::max(max_len, h.max_len);
+            }
+            free(h.rec_pos); free(h.seq_off);
+        }
+        if (status != CRASS_OK) return status;
+        const uint64_t nr = read_base.back();
+        uint64_t *a = (uint64_t *)malloc((n_files + 1) * 8), *bb = (uint64_t *)malloc((n_files + 1) * 8);
+        uint64_t *rp = (uint64_t *)malloc((nr + 1) * 8), *so = (uint64_t *)malloc((nr + 1) * 8);
+        int32_t *fm = (int32_t *)malloc(n_files * 4);
+        if (!a || !bb || !rp || !so || !fm) { free(a); free(bb); free(rp); free(so); free(fm); return CRASS_ERR_OOM; }
+        memcpy(a, read_base.data(), (n_files + 1) * 8); memcpy(bb, byte_base.data(), (n_files + 1) * 8);
+        memcpy(rp, rec_pos.data(), (nr + 1) * 8); memcpy(so, seq_off.data(), (nr + 1) * 8); memcpy(fm, format.data(), n_files * 4);
+        out->file_read_base = a; out->file_byte_base = bb; out->rec_pos = rp; out->seq_off = so; out->format = fm;
+        out->n_reads = nr; out->max_len = max_len;
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+void crass_fastx_files_layout_free(crass_fastx_files_layout *l)
+{
+    if (!l) return;
+    free((void *)l->file_read_base); free((void *)l->file_byte_base); free((void *)l->format); free((void *)l->rec_pos); free((void *)l->seq_off);
+    l->file_read_base = l->file_byte_base = l->rec_pos = l->seq_off = nullptr; l->format = nullptr;
+}
+
 int crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, uint64_t *header_id_out)
 {
     if (n_reads && (!bytes || !rec_pos || !header_id_out)) return CRASS_ERR_INVALID_ARG;

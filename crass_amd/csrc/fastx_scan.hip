@@ -13,6 +13,8 @@
 //                   is why this is not the 32-bit look-back of sinks.hip.
 //   k_fx_emit       the tile again, now with its base: sequence bytes go through LDS to the text in aligned 16-byte stores,
 //                   every header line start writes rec_pos / seq_off, every offence of fastx_scan.h is min-ed into the verdict.
+//                   Several files as one set (crass_hip_load_fastx_files): a launch per file with the file's text base, read
+//                   base and arena base, so that all files fill one text, one seq_off and one rec_pos (arena positions).
 // Temporary HBM per input byte: 72 / 4096 for the tile arrays, at most 1 for the text, 16 per record for the two arrays.
 // No byte beyond the input is read: the first and the last vector are loaded byte by byte where they are not whole.
 #include "fastx_launch.h"
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_emit(const FxJob J)
             ls_pos = p0 + j; gidx++;
             if (kind == FX_HEADER) {
                 const uint64_t r = B.rec_before + h_run++;
-                if (r < J.n_reads) { J.rec_pos[r] = ls_pos; J.seq_off[r] = B.seq_before + s_run; }
+                if (r < J.n_reads) { J.rec_pos[J.read_base + r] = J.arena_base + ls_pos; J.seq_off[J.read_base + r] = J.text_base + B.seq_before + s_run; }
                 if (fastq) {
                     if ((J.n_lines & 3u) && gidx == (J.n_lines & ~3ull)) offend(FX_LINE_COUNT);
                     if (!((V.at >> j) & 1u)) offend(FX_FQ_HEADER);
@@ -288,7 +290,8 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_emit(const FxJob J)
     });
     if (off != kFxNoOffence) atomicMin(J.verdict, (unsigned long long)off);
     // 3. the tile's sequence bytes: into LDS where they will lie relative to the text's 16-byte vectors, then out
-    const uint32_t shift = (uint32_t)(B.seq_before & 15u);
+    const uint64_t t0 = J.text_base + B.seq_before;    // where the tile's first sequence byte goes in the text
+    const uint32_t shift = (uint32_t)(t0 & 15u);
     {
         uint32_t o = shift + (sq & 0xFFFFu);
 #pragma unroll
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_emit(const FxJob J)
     }
     __syncthreads();
     const uint32_t n_out = shift + (tot_sq & 0xFFFFu);  // LDS bytes [shift, n_out) are the tile's
-    const uint64_t g0 = B.seq_before - shift;           // text offset of LDS byte 0 (a multiple of 16)
+    const uint64_t g0 = t0 - shift;           // text offset of LDS byte 0 (a multiple of 16)
     for (uint32_t v = tid; 16u * v < n_out; v += kFxThreads) {
         const uint32_t a = 16u * v, b = a + 16u;
         if (a >= shift && b <= n_out && g0 + b <= J.text_cap) {

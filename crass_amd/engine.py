@@ -302,6 +302,62 @@ def bgzf_inflate_host(buf, index=None):
     return out
 
 
+class FastxFilesLayout:
+    """Several files as one read set (crass_fastx_files_layout), as numpy copies: n_files, n_reads, max_len, file_read_base /
+    file_byte_base (uint64, n_files + 1; byte bases and rec_pos are ARENA positions: every file's text with a "\\n" behind it),
+    formats (a list of b">" / b"@"), rec_pos / seq_off (uint64, n_reads + 1).  A declined set has accepted False, decline_file,
+    and either decline_reason / decline_pos (a FASTA / FASTQ decline, the position inside that file) or bgzf = (reason, member,
+    in_pos) (a compression decline), and empty arrays."""
+
+    def __init__(self, v):
+        self.n_files, self.n_reads, self.max_len = int(v.n_files), int(v.n_reads), int(v.max_len)
+        self.decline_file, self.decline_reason, self.decline_pos = int(v.decline_file), int(v.decline_reason), int(v.decline_pos)
+        self.bgzf = (int(v.bgzf.reason), int(v.bgzf.member), int(v.bgzf.in_pos))
+        self.accepted = self.decline_file < 0
+        have = bool(v.rec_pos) and bool(v.seq_off) and bool(v.file_read_base) and bool(v.file_byte_base) and bool(v.format)
+        z = np.zeros(0, np.uint64)
+        self.file_read_base = _np(v.file_read_base, self.n_files + 1, np.uint64).copy() if have else z
+        self.file_byte_base = _np(v.file_byte_base, self.n_files + 1, np.uint64).copy() if have else z
+        self.formats = [bytes([int(v.format[f]) & 0xFF]) for f in range(self.n_files)] if have else []
+        self.rec_pos = _np(v.rec_pos, self.n_reads + 1, np.uint64).copy() if have else z
+        self.seq_off = _np(v.seq_off, self.n_reads + 1, np.uint64).copy() if have else z
+
+    @property
+    def verdict(self):
+        """what a declined set is compared by: (file, FASTA / FASTQ reason, position, BGZF verdict)"""
+        return (self.decline_file, self.decline_reason, self.decline_pos, self.bgzf)
+
+
+class FastxFilesDeclined(CrassError):
+    """crass_hip_load_fastx_files declined a file (status 2, nothing resident): `layout` says which and why."""
+
+    def __init__(self, status, where, layout):
+        super().__init__(status, where)
+        self.layout = layout
+
+
+def _files_args(bufs):
+    arrs = [_bytes_arg(b) for b in bufs]
+    ptrs = (C.c_void_p * max(len(arrs), 1))(*[(a.ctypes.data if len(a) else None) for a in arrs])
+    lens = np.array([len(a) for a in arrs], dtype=np.uint64)
+    return arrs, ptrs, lens
+
+
+def fastx_files_scan_host(bufs):
+    """Several files' bytes as one read set on the host (crass_fastx_files_scan_host; no GPU needed): a FastxFilesLayout,
+    accepted or declined — what SearchEngine.load_fastx_files is tested against."""
+    lib = _abi.load()
+    arrs, ptrs, lens = _files_args(bufs)
+    v = _abi.FastxFilesLayoutC()
+    st = lib.crass_fastx_files_scan_host(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), C.byref(v))
+    try:
+        if st not in (0, 2):
+            raise CrassError(st, "crass_fastx_files_scan_host")
+        return FastxFilesLayout(v)
+    finally:
+        lib.crass_fastx_files_layout_free(C.byref(v))
+
+
 def fastx_header_ids(buf, rec_pos):
     """header_id[r] = index of the first read with the same name, from the file's bytes and the records' positions
     (crass_fastx_header_ids; host, names compared exactly).  rec_pos: n_reads + 1 entries as in a FastxLayout."""
@@ -766,6 +822,59 @@ class SearchEngine:
         if st == 2 and ver.reason:
             raise BgzfDeclined(st, "crass_hip_load_fastx_bgzf", ver)
         return self._fastx_result(st, v, "crass_hip_load_fastx_bgzf")
+
+    def load_fastx_files(self, bufs, pad_uniform=2):
+        """Several input files' bytes (plain FASTA / FASTQ or BGZF, each on its own terms) as ONE resident set in (file, read)
+        order, parsed on the device, header ids across the files installed (crass_hip_load_fastx_files).  Returns a
+        FastxFilesLayout; raises FastxFilesDeclined (status 2, nothing resident) when a file is declined.  The files' text stays
+        on the device: resident_fastx()."""
+        arrs, ptrs, lens = _files_args(bufs)
+        v = _abi.FastxFilesLayoutC()
+        st = self.lib.crass_hip_load_fastx_files(self.h, ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(pad_uniform), C.byref(v))
+        lay = FastxFilesLayout(v)
+        if st == 2 and not lay.accepted:
+            raise FastxFilesDeclined(st, "crass_hip_load_fastx_files", lay)
+        _chk(st, "crass_hip_load_fastx_files")
+        self._keep = None
+        return lay
+
+    def resident_fastx(self):
+        """(device address, n_bytes) of the arena of the last load_fastx_files (crass_hip_resident_fastx); CrassError with
+        status CRASS_ERR_STATE when the last load was not one.  The address goes where fetch_quality takes `src`; for
+        device_header_ids and fetch_header_lines (which take the byte count from rec_pos[-1] when src is an address) pass
+        np.append(layout.rec_pos[:-1], n_bytes) as the layout."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _chk(self.lib.crass_hip_resident_fastx(self.h, C.byref(p), C.byref(n)), "crass_hip_resident_fastx")
+        return int(p.value or 0), int(n.value)
+
+    def fetch_quality(self, src, n_bytes, rec_pos, idx, out=None):
+        """The quality strings of the records idx (LOCAL record numbers, any order, repeats allowed) of file bytes on the DEVICE
+        (src: an address or a contiguous torch uint8 device tensor; n_bytes: how many; rec_pos: n_reads + 1 positions):
+        crass_hip_fetch_quality_device.  Returns (chars, off, has_qual): numpy copies of the strings back to back (uint8), their
+        offsets (uint64, n + 1) and whether the record is a FASTQ one (uint8).  out: a contiguous torch uint8 DEVICE tensor — the
+        strings are written there instead (crass_hip_fetch_quality_device_to) and chars is None; a tensor too small raises
+        CrassError with status 8 and the offsets in its `offsets`."""
+        ptr = src if isinstance(src, int) else (int(src.data_ptr()) if src.numel() else 0)
+        rp = np.ascontiguousarray(rec_pos, dtype=np.uint64)
+        n = max(len(rp) - 1, 0)
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        has = np.zeros(len(a), np.uint8)
+        args = (self.h, ptr or None, int(n_bytes), rp.ctypes.data if n else None, n, a.ctypes.data if len(a) else None, len(a))
+        if out is None:
+            v = _abi.Text()
+            _chk(self.lib.crass_hip_fetch_quality_device(*args, C.byref(v), has.ctypes.data if len(a) else None), "crass_hip_fetch_quality_device")
+            t = Text(v)
+            return t.chars.copy(), t.off.copy(), has
+        if str(out.dtype) != "torch.uint8" or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("fetch_quality(out=...) needs a contiguous uint8 device tensor")
+        off = np.zeros(len(a) + 1, np.uint64)
+        st = self.lib.crass_hip_fetch_quality_device_to(*args, int(out.data_ptr()) if out.numel() else None, int(out.numel()), off.ctypes.data,
+                                                        has.ctypes.data if len(a) else None)
+        if st != 0:
+            e = CrassError(st, "crass_hip_fetch_quality_device_to")
+            e.offsets = off
+            raise e
+        return None, off, has
 
     def last_inflate_ms(self):
         """HIP-event milliseconds of the last inflate_bgzf_device / load_fastx_bgzf call's inflate kernel (stage timing >= 1, else 0)."""

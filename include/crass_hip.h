@@ -703,6 +703,77 @@ int  crass_hip_fetch_header_lines_device(crass_hip_ctx *ctx, const uint8_t *d_by
 int  crass_hip_fetch_header_lines_device_to(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
                                             const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
                                             uint32_t *name_len_out);
+/* ---- several input files (paired-end files, lanes) as ONE resident set, parsed on the device ----
+ * replaces: crass_index_fastx_files + crass_fastx_index_reads + crass_hip_load_reads, i.e. the kseq_read loop of libcrispr.cpp:96-131
+ * over every file of parseSeqFiles (WorkHorse.cpp:336-393), for a caller that holds the files' bytes in HOST memory: the job's reads in
+ * (file, read) order in one packed set, header ids across the files.  Each file is taken on its own terms: byte 0 '>' or '@' — plain
+ * text (FASTA and FASTQ may be mixed in one call); bytes 1f 8b and a valid BGZF index — inflated on the device (k_bgzf_inflate);
+ * anything else, plain single-member gzip included — declined.
+ * The ARENA: every file's text (inflated where compressed) lies in one device buffer in file order, file f at
+ * [file_byte_base[f], file_byte_base[f+1] - 1); the byte behind each file's last byte is a '\n' that belongs to no file, so nothing
+ * that walks a line or a name runs into the next file.  The context keeps the arena until the next load, attach or destroy
+ * (crass_hip_resident_fastx); rec_pos holds ARENA positions.
+ * accepted (CRASS_OK): the resident packed words, stride / uniform length, exception list, counters and seq_off are bit for bit what
+ *   the three calls above give on the same files (same pad_uniform; a set whose files differ in read length is ragged exactly as the
+ *   host packer makes it) — with one exception: in the words of an EXCEPTION read, a byte that is not A C G T has crass_pack_reads'
+ *   code 0 here (as after crass_hip_load_text), where the indexed reader's own packer leaves another code; the search reads such reads
+ *   from the exception list, never from those words.  header_id is theirs: the index of the first read, over all files, with the same name (k_hid_insert /
+ *   k_hid_lookup on the arena, installed device to device; none installed when no name repeats).
+ * declined (CRASS_ERR_UNSUPPORTED): no reads are resident and no arena is kept; decline_file says which file, and either
+ *   decline_reason / decline_pos (a FASTA / FASTQ decline: the reasons 1..11 of crass_fastx_layout, the position inside THAT file) or
+ *   bgzf (a compression decline: bgzf.reason != 0, decline_reason 0).  When several files offend, the first file in order wins.
+ *   A different answer is never an outcome.
+ * Other errors: CRASS_ERR_INVALID_ARG — a NULL context, n_files == 0, NULL arrays, a NULL bytes[f] with n_bytes[f] > 0, pad_uniform
+ * outside 0..2; CRASS_ERR_UNSUPPORTED without a verdict — 2^32 - 1 reads or more. */
+typedef struct {
+    uint32_t n_files;
+    int32_t  decline_file;                 /* -1 when accepted */
+    int32_t  decline_reason;               /* FASTA / FASTQ decline of that file, else 0 */
+    uint32_t max_len;
+    uint64_t decline_pos;                  /* position inside that file */
+    crass_bgzf_verdict bgzf;               /* compression decline of that file (reason 0: none) */
+    uint64_t n_reads;
+    const uint64_t *file_read_base;        /* [n_files+1] first read of every file; [n_files] = n_reads */
+    const uint64_t *file_byte_base;        /* [n_files+1] arena position of every file's byte 0; [n_files] = the arena's size */
+    const int32_t  *format;                /* [n_files] '>' | '@' */
+    const uint64_t *rec_pos;               /* [n_reads+1] arena position of each record's header character; [n_reads] = the end of the
+                                              last file's text = the arena's size - 1 */
+    const uint64_t *seq_off;               /* [n_reads+1] offsets in the concatenated sequence text */
+} crass_fastx_files_layout;
+/* the same layout on the host (no GPU needed): crass_fastx_scan_host per file, crass_bgzf_index_host + crass_bgzf_inflate_host for a
+ * BGZF file — what the device call is tested against.  The arrays are malloc'd (crass_fastx_files_layout_free), NULL when declined
+ * (n_files and the decline fields are always filled).  With one plain file: crass_fastx_scan_host's answer with bases 0. */
+int  crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, crass_fastx_files_layout *out);
+void crass_fastx_files_layout_free(crass_fastx_files_layout *l);
+/* the device call.  Uploads go through the two staged buffers of crass_hip_load_text, file after file (a BGZF file's compressed bytes
+ * into scratch, inflated from there into the arena); file f's two scan kernels are queued before file f+1 is staged, so they run
+ * beside its upload.  Each file is scanned by k_fx_summary / k_fx_tile_scan / k_fx_emit with its own format and tile grid, all files
+ * emit into one text and one seq_off, ONE k_pack_text launch packs the set.  out may be NULL; its arrays are context-owned pinned
+ * memory, valid until the next load, attach or destroy (NULL when declined). */
+int  crass_hip_load_fastx_files(crass_hip_ctx *ctx, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
+                                crass_fastx_files_layout *out);
+/* the arena of the last crass_hip_load_fastx_files: a DEVICE pointer and its size (= file_byte_base[n_files]), for
+ * crass_hip_fastx_header_ids_device, crass_hip_fetch_header_lines_device(_to) and crass_hip_fetch_quality_device(_to), which work on
+ * it unchanged.  CRASS_ERR_STATE: the last load was not a files load (or was declined). */
+int  crass_hip_resident_fastx(const crass_hip_ctx *ctx, const uint8_t **d_bytes, uint64_t *n_bytes);
+/* replaces: ReadHolder's RH_Qual / RH_IsFasta (filled from the kseq record at libcrispr.cpp:471-487) for a caller whose file bytes
+ * exist only on the device: the QUALITY strings of the records idx[0..n) (LOCAL record numbers in [0, n_reads), any order, repeats
+ * allowed) back to back.  A record whose header character is '@' has its quality on its fourth line, found from rec_pos[idx[k]] by
+ * three line ends and bounded by rec_pos[idx[k] + 1] (rec_pos has n_reads + 1 entries; entries beyond n_bytes count as n_bytes): the
+ * string is that line's bytes 33..126 — for a regular four-line FASTQ record exactly crass_fastx_index_fetch's qual —, has_qual_out[k]
+ * (host [n], may be NULL) is 1.  A '>' record gives an empty string and has_qual 0.  The result follows
+ * crass_hip_fetch_header_lines_device: a crass_text in the context's pinned memory (its own), valid until the next call of this
+ * function, or destroy.  Errors (nothing launched, nothing outside the bytes read): CRASS_ERR_INVALID_ARG — a NULL context or result
+ * pointer, NULL d_bytes or rec_pos with n_reads > 0, a NULL idx with n > 0, an idx[k] >= n_reads, a rec_pos[idx[k]] >= n_bytes;
+ * CRASS_ERR_UNSUPPORTED — n_reads >= 2^32 - 1.  n == 0: CRASS_OK, an empty result.  Needs no resident reads. */
+int  crass_hip_fetch_quality_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                    const uint64_t *idx, uint64_t n, crass_text *out, uint8_t *has_qual_out);
+/* the same into the caller's DEVICE buffer d_chars (cap_bytes bytes, any alignment), the offsets into the host array off_out[n+1], by
+ * the rules of crass_hip_fetch_text_device: cap_bytes < off_out[n] is CRASS_ERR_OVERFLOW with off_out and has_qual_out filled and
+ * nothing written; no byte outside [d_chars, d_chars + off_out[n]) is written. */
+int  crass_hip_fetch_quality_device_to(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                       const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
+                                       uint8_t *has_qual_out);
 /* replaces: the second reading of the input files (libcrispr.cpp:471-487) for a group (crass_hip_group_*): crass_hip_fetch_text
  * over the whole job.  Every global index is routed to the rank whose shard holds it; the records come back in the caller's
  * order in one crass_text owned by the group, valid until the next group fetch, load or destroy. */

@@ -1,8 +1,10 @@
 // AddressSanitizer / UBSan harness for the record scan's host code (csrc/fastx_scan.cpp + csrc/fastx_scan.h), next to ingest_main.cpp:
 // every file given — the sets of tests/fastx_sets.py, dumped by tools/sanitize/fastx_scan_dump.py — goes through crass_fastx_scan_host
 // and, where it is accepted, crass_fastx_header_ids; the four-bytes-at-once byte classes of fastx_scan.h are compared with the
-// byte predicates for every byte value in every position.  CPU only.  Prints one line per file; any sanitizer report fails the run.
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp \
+// byte predicates for every byte value in every position.  Then all files given go through crass_fastx_files_scan_host as ONE set,
+// and every file with its successor as a set of two (plain files; a BGZF file among them is inflated by the host decoder): the
+// joined arrays are checked against the single-file scans.  CPU only.  Prints one line per file; any sanitizer report fails the run.
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp \
 //       tools/sanitize/fastx_scan_main.cpp -o fastx_scan_asan && python3 tools/sanitize/fastx_scan_dump.py DIR && ./fastx_scan_asan DIR/*
 #include "../../include/crass_hip.h"
 #include "../../crass_amd/csrc/fastx_scan.h"
@@ -32,9 +34,39 @@ static int check_classes()
     printf("%s byte classes: 1024 cases\n", bad ? "DIFF" : "ok  ");
     return bad;
 }
+// files [a, b) as one set against their single-file scans (plain files: a BGZF one only has to come back accepted or declined)
+static int check_set(const std::vector<uint8_t *> &ptr, const std::vector<uint64_t> &len, size_t a, size_t b)
+{
+    crass_fastx_files_layout lay;
+    const int rc = crass_fastx_files_scan_host(ptr.data() + a, len.data() + a, (uint32_t)(b - a), &lay);
+    bool ok = rc == CRASS_OK || rc == CRASS_ERR_UNSUPPORTED;
+    uint64_t reads = 0, at = 0;
+    for (size_t f = a; ok && f < b; f++) {
+        crass_fastx_layout one;
+        const int r1 = crass_fastx_scan_host(ptr[f], len[f], &one);
+        const bool plain = !(len[f] >= 2 && ptr[f][0] == 0x1F && ptr[f][1] == 0x8B);
+        if (rc == CRASS_ERR_UNSUPPORTED && (size_t)lay.decline_file == f - a) {
+            ok = !lay.rec_pos && !lay.seq_off && !lay.file_read_base && (!plain || (r1 == CRASS_ERR_UNSUPPORTED && one.decline_reason == lay.decline_reason && one.decline_pos == lay.decline_pos));
+            crass_fastx_layout_free(&one);
+            break;
+        }
+        if (rc == CRASS_OK && plain) {
+            ok = r1 == CRASS_OK && lay.file_read_base[f - a] == reads && lay.file_byte_base[f - a] == at && lay.format[f - a] == one.format;
+            for (uint64_t r = 0; ok && r < one.n_reads; r++) ok = lay.rec_pos[reads + r] == at + one.rec_pos[r] && lay.seq_off[reads + r + 1] - lay.seq_off[reads + r] == one.seq_off[r + 1] - one.seq_off[r];
+            reads += one.n_reads; at += len[f] + 1;
+        } else if (rc == CRASS_OK) { reads = lay.file_read_base[f - a + 1]; at = lay.file_byte_base[f - a + 1]; }
+        else if (plain) ok = r1 == CRASS_OK;             // (a file in front of the declined one)
+        crass_fastx_layout_free(&one);
+    }
+    if (rc == CRASS_OK) ok = ok && lay.n_reads == reads && lay.file_byte_base[b - a] == at && lay.rec_pos[reads] == at - 1;
+    printf("%s set of files %zu..%zu: rc %d, %llu records, declined file %d\n", ok ? "ok  " : "DIFF", a, b - 1, rc, (unsigned long long)lay.n_reads, lay.decline_file);
+    crass_fastx_files_layout_free(&lay);
+    return ok ? 0 : 1;
+}
 int main(int argc, char **argv)
 {
     int bad = check_classes();
+    std::vector<uint8_t *> all_ptr; std::vector<uint64_t> all_len;
     for (int a = 1; a < argc; a++) {
         FILE *f = fopen(argv[a], "rb");
         if (!f) { printf("DIFF %s: cannot open\n", argv[a]); bad++; continue; }
@@ -60,7 +92,20 @@ int main(int argc, char **argv)
                (unsigned long long)lay.decline_pos);
         bad += ok ? 0 : 1;
         crass_fastx_layout_free(&lay);
-        free(exact);
+        all_ptr.push_back(exact); all_len.push_back(data.size());
     }
+    if (!all_ptr.empty()) {
+        for (size_t f = 0; f + 1 < all_ptr.size(); f++) bad += check_set(all_ptr, all_len, f, f + 2);
+        bad += check_set(all_ptr, all_len, 0, all_ptr.size());
+        // the accepted files alone as one set: the joins of all of them
+        std::vector<uint8_t *> ok_ptr; std::vector<uint64_t> ok_len;
+        for (size_t f = 0; f < all_ptr.size(); f++) {
+            crass_fastx_layout one;
+            if (crass_fastx_scan_host(all_ptr[f], all_len[f], &one) == CRASS_OK) { ok_ptr.push_back(all_ptr[f]); ok_len.push_back(all_len[f]); }
+            crass_fastx_layout_free(&one);
+        }
+        if (!ok_ptr.empty()) bad += check_set(ok_ptr, ok_len, 0, ok_ptr.size());
+    }
+    for (uint8_t *p : all_ptr) free(p);
     return bad ? 1 : 0;
 }
