@@ -614,12 +614,14 @@ std::string decline_message(const Vecstr &files, const crass_fastx_files_layout 
                                      "a read is longer than the device path takes"};
     static const char *const bz[] = {"", "a deflate block of type 3", "a stored block whose length check fails", "bad code lengths", "a bit pattern that is no code",
                                      "a distance beyond the member's text", "the deflate data ends early", "more text than the member's trailer says",
-                                     "less text than the member's trailer says", "a member's CRC-32 does not match", "gzip, but not BGZF (plain gzip stays with the host readers)"};
+                                     "less text than the member's trailer says", "a member's CRC-32 does not match", "gzip, but not BGZF (plain gzip stays with the host readers)",
+                                     "not a gzip header, or a header that runs into the trailer", "no deflate block start within the span of a chunk",
+                                     "the gzip member ends before the file does (further members, trailing bytes)", "a distance that reaches in front of the text"};
     const std::string name = lay.decline_file >= 0 && (size_t)lay.decline_file < files.size() ? files[(size_t)lay.decline_file] : std::string("?");
     std::string m = "crass [ERROR]: CRASS_INGEST=device cannot take " + name + ": ";
     if (lay.bgzf.reason) {
         const int r = lay.bgzf.reason;
-        m += std::string(r >= 1 && r <= 10 ? bz[r] : "compression") + " (BGZF reason " + std::to_string(r) + ", member " + std::to_string(lay.bgzf.member) +
+        m += std::string(r >= 1 && r <= 14 ? bz[r] : "compression") + " (BGZF reason " + std::to_string(r) + ", member " + std::to_string(lay.bgzf.member) +
              ") at byte " + std::to_string(lay.bgzf.in_pos);
     } else {
         const int r = lay.decline_reason;
@@ -822,6 +824,8 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     memset(&lay, 0, sizeof(lay));
     if (device_ingest) {
         // as soon as the context is up; a declined input is an error, as with a forced CRASS_INGEST=index
+        // CRASS_DEVICE_GZIP=1: a plain gzip input is inflated on the device too (gunzip.hip); without it such an input is declined
+        if (const char *e = getenv("CRASS_DEVICE_GZIP")) chk(crass_hip_set_gzip_on_device(made.c, atoi(e) != 0), "crass_hip_set_gzip_on_device");
         const int s = crass_hip_load_fastx_files(made.c, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, &lay);
         if (s == CRASS_ERR_UNSUPPORTED && lay.decline_file >= 0) throw input_error(decline_message(seqFiles, lay));
         chk(s, "crass_hip_load_fastx_files");

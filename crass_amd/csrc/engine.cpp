@@ -12,6 +12,7 @@
 #include "fastx_launch.h"
 #include "fastx_names_launch.h"
 #include "inflate_launch.h"
+#include "gunzip_launch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -278,6 +279,13 @@ struct crass_hip_ctx {
     PinBuf<unsigned long long> z_h_verdict;
     hipEvent_t ev_z_time[2] = {nullptr, nullptr};
     float last_inflate_ms = 0;               // HIP-event time of the last call's inflate kernel (stage timing >= 1, else 0)
+    // crass_hip_inflate_gzip_device / crass_hip_load_fastx_gzip (gunzip.hip): per chunk start / text_len / end_bit and link / reason
+    // (count step); per chain element start / end_bit of all chunks + the elements' offsets and chain / CRC parts, the text as
+    // 16-bit symbols and the 32 KB windows (decode step) — all given back before the call returns
+    DevBuf<uint64_t> gz_a64, gz_b64; DevBuf<uint32_t> gz_a32, gz_b32; DevBuf<uint16_t> gz_sym; DevBuf<uint8_t> gz_win;
+    hipEvent_t ev_gz_time[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float last_gzip_ms[5] = {0, 0, 0, 0, 0};  // find, count, decode, windows, narrow of the last gzip inflate (stage timing >= 1, else 0)
+    bool gzip_on_device = false;             // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
     // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
     // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
@@ -907,6 +915,8 @@ void crass_hip_destroy(crass_hip_ctx *c)
     for (auto &e : c->ev_x_time) if (e) (void)hipEventDestroy(e);
     c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release(); c->z_h_verdict.release();
     for (auto &e : c->ev_z_time) if (e) (void)hipEventDestroy(e);
+    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release();
+    for (auto &e : c->ev_gz_time) if (e) (void)hipEventDestroy(e);
     c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
     c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
     for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
@@ -1608,6 +1618,215 @@ int crass_hip_load_fastx_bgzf(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n
     return s;
 }
 
+// ---- one plain gzip member inflated on the device chunk by chunk (gunzip.hip, gunzip_core.h) ----
+namespace {
+// what the count step and the chain walk decided about one file: all the decode step needs beside the bytes
+struct GzState {
+    GzMember M{};
+    std::vector<uint64_t> start, text_len, end_bit;
+    std::vector<uint32_t> link, chain;
+    std::vector<int32_t> reason;
+    uint64_t n_chain = 0, n_text = 0;
+};
+}
+
+static void gzip_release(crass_hip_ctx *c)
+{
+    (void)hipStreamSynchronize(c->stream);
+    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release();
+}
+
+// header and trailer (host), find and count (device), the chain (host): CRASS_OK with S.n_text known, or the decline
+static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, GzState &S, crass_gzip_plan *plan,
+                           crass_bgzf_verdict *v)
+{
+    c->last_inflate_ms = 0;
+    for (auto &m : c->last_gzip_ms) m = 0;
+    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
+        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    try {
+        // the header's bytes come down in a piece that grows until the header ends inside it
+        std::vector<uint8_t> head;
+        uint8_t trailer[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n_in >= 18) HIPCHK(c, hipMemcpy(trailer, d_in + n_in - 8, 8, hipMemcpyDeviceToHost));
+        int32_t why = BZ_NOT_GZIP;
+        for (uint64_t h = std::min<uint64_t>(n_in, 65536);; h = std::min<uint64_t>(n_in, h * 4)) {
+            head.resize(h ? h : 1);
+            if (h) HIPCHK(c, hipMemcpy(head.data(), d_in, h, hipMemcpyDeviceToHost));
+            why = gz_parse_member(head.data(), h, trailer, n_in, chunk_bytes, &S.M);
+            if (why != -1 || h == n_in) break;
+        }
+        if (why != BZ_OK) return decline(BZ_NOT_GZIP, 0, 0);
+        const GzGeom &G = S.M.G;
+        const uint64_t nc = G.nc;
+        HIPCHK(c, c->gz_a64.ensure(3 * nc)); HIPCHK(c, c->gz_a32.ensure(2 * nc));
+        GzJob J{};
+        J.d = d_in + G.d_off; J.G = G;
+        J.start = c->gz_a64.p; J.text_len = c->gz_a64.p + nc; J.end_bit = c->gz_a64.p + 2 * nc;
+        J.link = c->gz_a32.p; J.reason = reinterpret_cast<int32_t *>(c->gz_a32.p + nc);
+        const bool timed = c->timing_level >= 1;
+        if (timed) {
+            for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, hipEventRecord(c->ev_gz_time[0], c->stream));
+        }
+        HIPCHK(c, launch_gz_find(J, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[1], c->stream));
+        HIPCHK(c, launch_gz_count(J, c->stream));         // (a launch of its own: every start is final before a chunk counts)
+        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
+        S.start.resize(nc); S.text_len.resize(nc); S.end_bit.resize(nc); S.link.resize(nc); S.reason.resize(nc); S.chain.assign(nc, 0);
+        HIPCHK(c, hipMemcpyAsync(S.start.data(), J.start, nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.text_len.data(), J.text_len, nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.end_bit.data(), J.end_bit, nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.link.data(), J.link, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.reason.data(), J.reason, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (timed) {
+            HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[0], c->ev_gz_time[0], c->ev_gz_time[1]));
+            HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[1], c->ev_gz_time[1], c->ev_gz_time[2]));
+            c->last_inflate_ms = c->last_gzip_ms[0] + c->last_gzip_ms[1];
+        }
+        GzVerdict gv{};
+        const int32_t bad = gz_chain(S.M, S.start.data(), S.link.data(), S.text_len.data(), S.end_bit.data(), S.reason.data(), S.chain.data(),
+                                     &S.n_chain, &S.n_text, &gv);
+        const int ps = gz_plan_fill(plan, nc, S.start.data(), S.link.data(), S.text_len.data(), S.n_chain);
+        if (ps) return ps;
+        if (bad != BZ_OK) return decline(gv.reason, gv.member, gv.in_pos);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+// decode, windows, narrow: the text of an accepted count into d_out[0, S.n_text)
+static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState &S, uint8_t *d_out, crass_bgzf_verdict *v)
+{
+    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
+        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    const GzGeom &G = S.M.G;
+    const uint64_t nc = G.nc, n = S.n_chain;
+    try {
+        std::vector<uint64_t> off(n + 1, 0);
+        for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + S.text_len[S.chain[i]];
+        std::vector<uint32_t> crc_part(n, 0);
+        HIPCHK(c, c->gz_b64.ensure(2 * nc + n + 1)); HIPCHK(c, c->gz_b32.ensure(2 * n));
+        HIPCHK(c, c->gz_sym.ensure(S.n_text)); HIPCHK(c, c->gz_win.ensure(n * (uint64_t)kGzWindow));
+        HIPCHK(c, c->z_verdict.ensure(1)); HIPCHK(c, c->z_h_verdict.ensure(1));
+        GzJob J{};
+        J.d = d_in + G.d_off; J.G = G;
+        J.start = c->gz_b64.p; J.end_bit = c->gz_b64.p + nc;
+        J.n_chain = n; J.off = c->gz_b64.p + 2 * nc; J.chain = c->gz_b32.p; J.crc_part = c->gz_b32.p + n;
+        J.sym = c->gz_sym.p; J.win = c->gz_win.p; J.out = d_out; J.verdict = c->z_verdict.p;
+        HIPCHK(c, hipMemcpyAsync(J.start, S.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(J.end_bit, S.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->gz_b64.p + 2 * nc, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->gz_b32.p, S.chain.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
+        const bool timed = c->timing_level >= 1;
+        if (timed) {
+            for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
+        }
+        HIPCHK(c, launch_gz_decode(J, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[3], c->stream));
+        HIPCHK(c, launch_gz_windows(J, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[4], c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[5], c->stream));
+        HIPCHK(c, hipMemcpyAsync(crc_part.data(), J.crc_part, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (timed) {
+            for (int k = 2; k < 5; k++) {
+                HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[k], c->ev_gz_time[k], c->ev_gz_time[k + 1]));
+                c->last_inflate_ms += c->last_gzip_ms[k];
+            }
+        }
+        const uint64_t w = c->z_h_verdict.p[0];
+        if (w != kBzNoOffence) {
+            const uint64_t k = S.chain[w];
+            return decline(BZ_MARKER, k, G.d_off + (S.start[k] >> 3));
+        }
+        uint32_t crc = 0;
+        for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
+        if (crc != S.M.crc) return decline(BZ_CRC, 0, 0);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+int crass_hip_inflate_gzip_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
+                                  uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    if (v) memset(v, 0, sizeof(*v));
+    if (plan) memset(plan, 0, sizeof(*plan));
+    if (n_text) *n_text = 0;
+    if (!c || !n_text || (n_in && !d_in) || (out_cap && !d_out)) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    GzState S;
+    int s = gzip_count_impl(c, d_in, n_in, chunk_bytes, S, plan, v);
+    if (s == CRASS_OK) {
+        *n_text = S.n_text;
+        if (out_cap < S.n_text) s = CRASS_ERR_OVERFLOW;       // (known before anything is stored)
+        else s = gzip_decode_impl(c, d_in, S, d_out, v);
+    }
+    gzip_release(c);
+    c->z_verdict.release();
+    return s;
+}
+
+int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
+                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
+{
+    if (out) memset(out, 0, sizeof(*out));
+    if (v) memset(v, 0, sizeof(*v));
+    if (!c || pad_uniform < 0 || pad_uniform > 2 || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    reset_results(c);
+    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
+    drop_arena(c);
+    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
+    auto run = [&]() -> int {
+        HIPCHK(c, c->z_raw.ensure(n_bytes + 16));
+        const int up = upload_staged(c, bytes, n_bytes, c->z_raw.p);
+        if (up) return up;
+        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+        GzState S;
+        int s = gzip_count_impl(c, c->z_raw.p, n_bytes, 0, S, nullptr, v);
+        if (s) return s;
+        if (d_text && d_text_cap < S.n_text) return CRASS_ERR_INVALID_ARG;
+        if (!d_text) { HIPCHK(c, c->z_text.ensure(S.n_text + 16)); d_text = c->z_text.p; }
+        s = gzip_decode_impl(c, c->z_raw.p, S, d_text, v);
+        if (s) return s;
+        gzip_release(c);
+        c->z_raw.release();                             // (the compressed bytes are done with: the scan's arrays may have their room)
+        return load_fastx_impl(c, nullptr, d_text, S.n_text, pad_uniform, read_index_base, out);
+    };
+    const int s = run();
+    // the scratch goes back on every way out, as in load_fastx_common
+    gzip_release(c);
+    inflate_bgzf_release(c);
+    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
+    c->x_rec_pos.release(); c->x_seq_off.release();
+    c->t_off.release();
+    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    return s;
+}
+
+int crass_hip_set_gzip_on_device(crass_hip_ctx *c, int on)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    c->gzip_on_device = on != 0;
+    return CRASS_OK;
+}
+
+int crass_hip_last_gzip_ms(const crass_hip_ctx *c, float *ms)
+{
+    if (!c || !ms) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 5; k++) ms[k] = c->last_gzip_ms[k];
+    return CRASS_OK;
+}
+
 float crass_hip_last_inflate_ms(const crass_hip_ctx *c) { return c ? c->last_inflate_ms : 0.0f; }
 
 int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
@@ -1779,7 +1998,7 @@ int crass_hip_fetch_header_lines_device_to(crass_hip_ctx *c, const uint8_t *d_by
 // ---- several files into one resident set (fastx_scan.hip, inflate.hip, fastx_names.hip) ----
 namespace {
 struct FilesPlan {
-    struct File { bool bgzf = false; crass_bgzf_index ix{}; uint64_t n_text = 0; int32_t format = 0; };
+    struct File { bool bgzf = false, gz = false; crass_bgzf_index ix{}; GzState gzs; uint64_t n_text = 0; int32_t format = 0; };
     std::vector<File> f;
     ~FilesPlan() { for (auto &x : f) if (x.bgzf) crass_bgzf_index_free(&x.ix); }
 };
@@ -1804,6 +2023,20 @@ static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, 
         const uint64_t n = n_bytes[f];
         if (n >= 2 && b[0] == 0x1F && b[1] == 0x8B) {
             const int s = crass_bgzf_index_host(b, n, &F.ix);
+            if (s == CRASS_ERR_UNSUPPORTED && c->gzip_on_device) {
+                // plain gzip (crass_hip_set_gzip_on_device): its bytes go up once for the count step, which sizes its share of the arena
+                HIPCHK(c, c->z_raw.ensure(n + 16));
+                const int up = upload_staged(c, b, n, c->z_raw.p);
+                if (up) return up;
+                HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+                crass_bgzf_verdict v{};
+                const int gs = gzip_count_impl(c, c->z_raw.p, n, 0, F.gzs, nullptr, &v);
+                if (gs == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = v; nf = f; break; }
+                if (gs) return gs;
+                F.gz = true; F.n_text = F.gzs.n_text;
+                if (F.n_text == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
+                continue;
+            }
             if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = F.ix.decline; nf = f; break; }
             if (s) return s;
             F.bgzf = true; F.n_text = F.ix.out_off[F.ix.n_members];
@@ -1837,12 +2070,13 @@ static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, 
     for (uint32_t f = 0; f < nf; f++) {
         FilesPlan::File &F = P.f[f];
         if (f) HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // (the staged buffers are the file before's until its last copy is done)
-        if (F.bgzf) {
+        if (F.bgzf || F.gz) {
             HIPCHK(c, c->z_raw.ensure(n_bytes[f] + 16));
             const int up = upload_staged(c, bytes[f], n_bytes[f], c->z_raw.p);
             if (up) return up;
             crass_bgzf_verdict v{};
-            const int s = inflate_bgzf_impl(c, c->z_raw.p, &F.ix, arena + base[f], &v);      // (waits for the stream: z_raw may be used again)
+            // (both wait for the stream: z_raw may be used again)
+            const int s = F.gz ? gzip_decode_impl(c, c->z_raw.p, F.gzs, arena + base[f], &v) : inflate_bgzf_impl(c, c->z_raw.p, &F.ix, arena + base[f], &v);
             if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_reason = 0; pend_v = v; nf = f; break; }
             if (s) return s;
             HIPCHK(c, hipMemcpy(&F.format, arena + base[f], 1, hipMemcpyDeviceToHost));
@@ -1943,6 +2177,7 @@ int crass_hip_load_fastx_files(crass_hip_ctx *c, const uint8_t *const *bytes, co
     c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
     const int s = load_fastx_files_impl(c, bytes, n_bytes, n_files, pad_uniform, out);
     // the scratch goes back on every way out, as in load_fastx_common; the arena stays only with an accepted set
+    gzip_release(c);
     inflate_bgzf_release(c);
     c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
     c->x_rec_pos.release(); c->x_seq_off.release();

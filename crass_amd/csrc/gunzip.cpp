@@ -1,0 +1,136 @@
+// gunzip.cpp — plain gzip on the host: a serial run of gunzip_core.h's rule (find, count, chain, decode, windows, narrow), one
+// chunk after the other.  It needs no GPU; it is what the kernels (gunzip.hip) are tested against, itself tested against zlib.
+// Host-only C++17 that any compiler builds (tools/sanitize).  Scratch: 2 bytes per text byte and 32 KB per chain element.
+#include "../../include/crass_hip.h"
+#include "gunzip_core.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace crass {
+
+// the host's way through the core: one executor, one index after the other
+struct GzHostIO {
+    const uint8_t *d; uint64_t dn; const uint8_t *src; uint32_t n_in; uint16_t *sym; uint64_t cap;
+    void at(uint64_t b0, uint32_t n) { src = d + b0; n_in = n; }
+    uint32_t in(uint32_t i) const { return i < n_in ? src[i] : 0u; }
+    void put(uint64_t p, uint32_t s) { if (p < cap) sym[p] = (uint16_t)s; }
+    uint32_t get(uint64_t p) const { return p < cap ? sym[p] : 0u; }
+    template <class F> void par(uint32_t n, F f) { for (uint32_t i = 0; i < n; i++) f(i); }
+    bool lead() const { return true; }
+    void sync() {}
+    uint64_t survivors(uint64_t base, uint64_t hi, uint64_t limit) const
+    {
+        uint64_t m = 0;
+        for (uint32_t l = 0; l < 64; l++) m |= (uint64_t)gz_survives(d, dn, base + l, hi, limit) << l;
+        return m;
+    }
+};
+
+// what the rule decided, for the caller (malloc'd: crass_gzip_plan_free)
+int gz_plan_fill(crass_gzip_plan *plan, uint64_t nc, const uint64_t *start, const uint32_t *link, const uint64_t *text_len, uint64_t n_chain)
+{
+    if (!plan) return CRASS_OK;
+    crass_gzip_plan_free(plan);
+    plan->start_bit = (uint64_t *)malloc(nc * 8); plan->link = (uint32_t *)malloc(nc * 4); plan->text_len = (uint64_t *)malloc(nc * 8);
+    if (!plan->start_bit || !plan->link || !plan->text_len) { crass_gzip_plan_free(plan); return CRASS_ERR_OOM; }
+    memcpy(plan->start_bit, start, nc * 8); memcpy(plan->link, link, nc * 4); memcpy(plan->text_len, text_len, nc * 8);
+    plan->n_chunks = nc; plan->n_chain = n_chain;
+    return CRASS_OK;
+}
+
+} // namespace crass
+
+using namespace crass;
+
+extern "C" {
+
+void crass_gzip_plan_free(crass_gzip_plan *p)
+{
+    if (!p) return;
+    free(p->start_bit); free(p->link); free(p->text_len);
+    p->start_bit = nullptr; p->link = nullptr; p->text_len = nullptr; p->n_chunks = 0; p->n_chain = 0;
+}
+
+int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                            crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    if (v) memset(v, 0, sizeof(*v));
+    if (plan) memset(plan, 0, sizeof(*plan));
+    if (n_text) *n_text = 0;
+    if (!n_text || (n_bytes && !bytes) || (out_cap && !out)) return CRASS_ERR_INVALID_ARG;
+    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
+        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    GzMember M{};
+    if (gz_parse_member(bytes, n_bytes, n_bytes >= 8 ? bytes + n_bytes - 8 : nullptr, n_bytes, chunk_bytes, &M) != BZ_OK) return decline(BZ_NOT_GZIP, 0, 0);
+    const GzGeom &G = M.G;
+    const uint64_t nc = G.nc;
+    BzTables *T = new (std::nothrow) BzTables;
+    if (!T) return CRASS_ERR_OOM;
+    int status = CRASS_OK;
+    try {
+        std::vector<uint64_t> start(nc, kGzNoStart), text_len(nc, 0), end_bit(nc, 0), off(nc, 0);
+        std::vector<uint32_t> link(nc, GZ_LINK_NONE), chain(nc, 0);
+        std::vector<int32_t> reason(nc, 0);
+        GzHostIO io{bytes + G.d_off, G.dn, nullptr, 0, nullptr, 0};
+        bz_prepare(io, *T);
+        // find
+        start[0] = 0;
+        for (uint64_t k = 1; k < nc; k++) start[k] = gz_find(io, *T, G, k);
+        // count
+        for (uint64_t k = 0; k < nc; k++) {
+            if (start[k] == kGzNoStart) continue;
+            const GzRun R = gz_run<GZ_COUNT>(io, *T, G, k, start[k], start.data(), 0);
+            link[k] = R.link; text_len[k] = R.text; end_bit[k] = R.end_bit; reason[k] = R.reason;
+        }
+        // chain
+        uint64_t n_chain = 0, total = 0;
+        GzVerdict gv{};
+        const int32_t why = gz_chain(M, start.data(), link.data(), text_len.data(), end_bit.data(), reason.data(), chain.data(), &n_chain, &total, &gv);
+        status = gz_plan_fill(plan, nc, start.data(), link.data(), text_len.data(), n_chain);
+        if (status) { delete T; return status; }
+        if (why != BZ_OK) { delete T; return decline(gv.reason, gv.member, gv.in_pos); }
+        *n_text = total;
+        if (out_cap < total) { delete T; return CRASS_ERR_OVERFLOW; }
+        // decode
+        std::vector<uint16_t> sym(total ? total : 1);
+        std::vector<uint8_t> win(n_chain * (uint64_t)kGzWindow);
+        uint64_t t = 0;
+        for (uint64_t i = 0; i < n_chain; i++) { off[chain[i]] = t; t += text_len[chain[i]]; }
+        for (uint64_t i = 0; i < n_chain; i++) {
+            const uint64_t k = chain[i];
+            io.sym = sym.data() + off[k]; io.cap = text_len[k];
+            (void)gz_run<GZ_DECODE>(io, *T, G, k, start[k], nullptr, end_bit[k]);
+        }
+        // windows, in chain order
+        for (uint64_t i = 1; i < n_chain; i++) {
+            const uint64_t kp = chain[i - 1];
+            const uint8_t *wp = i > 1 ? win.data() + (i - 1) * (uint64_t)kGzWindow : nullptr;
+            uint8_t *w = win.data() + i * (uint64_t)kGzWindow;
+            for (uint32_t e = 0; e < kGzWindow; e++) w[e] = gz_window_entry(sym.data() + off[kp], text_len[kp], wp, e);
+        }
+        // narrow, the CRC-32 element by element
+        uint32_t crc = 0;
+        for (uint64_t i = 0; i < n_chain && status == CRASS_OK; i++) {
+            const uint64_t k = chain[i];
+            const uint8_t *w = i ? win.data() + i * (uint64_t)kGzWindow : nullptr;
+            uint32_t c = 0xFFFFFFFFu;
+            for (uint64_t p = 0; p < text_len[k]; p++) {
+                const uint32_t b = gz_narrow(sym[off[k] + p], w, off[k]);
+                if (b > 0xFFu) { status = decline(BZ_MARKER, k, G.d_off + (start[k] >> 3)); break; }
+                out[off[k] + p] = (uint8_t)b;
+                c = T->crc_tab[(c ^ b) & 0xFFu] ^ (c >> 8);
+            }
+            crc = gz_crc_join(crc, text_len[k] ? ~c : 0u, text_len[k]);
+        }
+        if (status == CRASS_OK && crc != M.crc) status = decline(BZ_CRC, 0, 0);
+    } catch (const std::bad_alloc &) { status = CRASS_ERR_OOM; }
+    delete T;
+    return status;
+}
+
+} // extern "C"

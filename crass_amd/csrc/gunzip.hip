@@ -1,0 +1,218 @@
+// gunzip.hip — one plain gzip member inflated on the device chunk by chunk: the rule is gunzip_core.h's, statement for statement
+// what the host runs (gunzip.cpp); this file only says how waves go through it.  Five launches, none waits for another's waves:
+//   k_gz_find     a wave per chunk, grid-stride.  The 64 lanes test 64 consecutive bit positions at a time in registers
+//                 (gz_survives: BFINAL / BTYPE, HLIT, HDIST, the code-length code's Kraft sum); a ballot gives the survivors,
+//                 which the whole wave takes in ascending position through the header parse and the two trial block decodes
+//   k_gz_count    a wave per chunk: the blocks from its start to the next chunk's start it runs into, storing nothing
+//   k_gz_decode   a wave per chain element: the same bits again, as 16-bit symbols at the element's exact place in HBM
+//   k_gz_windows  ONE workgroup walks the chain in order, 32 768 entries per element
+//   k_gz_narrow   a workgroup per chain element: symbols to bytes through the element's window, aligned 16-byte stores with byte
+//                 stores only in the first and last partial vector (as k_fetch_text), then the element's CRC-32 in 256 slices
+// As in inflate.hip: symbol decoding is serial, all 64 lanes run it with the same values; tables (BzTables, 7 KB per wave) are in
+// LDS, the text in HBM; what a lane wrote is read by lanes of the SAME wave only, so io.sync() is a wavefront-scope fence plus a
+// wave barrier (see inflate.hip for the memory model's wording); no workgroup barrier inside the serial decode.
+// Scratch is the engine's: 2 bytes per text byte (sym) plus 32 KB per chain element (win), taken from dev_alloc and given back
+// before the call returns.
+// Bounds: input is read inside d[0, dn) only (in() and gz_survives check the index); a decode wave writes sym[off[i], off[i+1])
+// only (put() checks); k_gz_windows writes win[32768 i, 32768 (i + 1)); k_gz_narrow writes out[off[i], off[i+1]).
+#include "gunzip_launch.h"
+#include "engine_internal.h"
+#include "devmem.h"
+
+namespace crass {
+
+static constexpr int kGzWaves = 4;                        // waves per workgroup in find / count / decode
+static constexpr int kGzNarrowThreads = 256, kGzWindowThreads = 1024;
+
+struct GzWaveIO {
+    const uint8_t *d; uint64_t dn; const uint8_t *src; uint32_t n_in; uint16_t *sym; uint64_t cap; uint32_t lane;
+    __device__ __forceinline__ void at(uint64_t b0, uint32_t n) { src = d + b0; n_in = n; }
+    __device__ __forceinline__ uint32_t in(uint32_t i) const { return i < n_in ? (uint32_t)src[i] : 0u; }
+    __device__ __forceinline__ void put(uint64_t p, uint32_t s) { if (p < cap) sym[p] = (uint16_t)s; }
+    __device__ __forceinline__ uint32_t get(uint64_t p) const { return p < cap ? (uint32_t)sym[p] : 0u; }
+    template <class F> __device__ __forceinline__ void par(uint32_t n, F f) { for (uint32_t i = lane; i < n; i += 64u) f(i); }
+    __device__ __forceinline__ bool lead() const { return lane == 0; }
+    __device__ __forceinline__ void sync()
+    {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // lane l answers for position base + l
+    __device__ __forceinline__ uint64_t survivors(uint64_t base, uint64_t hi, uint64_t limit) const
+    {
+        return (uint64_t)__ballot(gz_survives(d, dn, base + lane, hi, limit) ? 1 : 0);
+    }
+};
+
+__global__ __launch_bounds__(64 * kGzWaves) void k_gz_find(GzJob J)
+{
+    __shared__ BzTables tabs[kGzWaves];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    BzTables &T = tabs[wv];
+    GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    bz_prepare(io, T);
+    const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
+    for (uint64_t k = (uint64_t)blockIdx.x * kGzWaves + wv; k < J.G.nc; k += n_waves) {
+        const uint64_t s = k ? gz_find(io, T, J.G, k) : 0;
+        if (lane == 0) J.start[k] = s;
+        io.sync();
+    }
+}
+
+__global__ __launch_bounds__(64 * kGzWaves) void k_gz_count(GzJob J)
+{
+    __shared__ BzTables tabs[kGzWaves];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    BzTables &T = tabs[wv];
+    GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    bz_prepare(io, T);
+    const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
+    for (uint64_t k = (uint64_t)blockIdx.x * kGzWaves + wv; k < J.G.nc; k += n_waves) {
+        const uint64_t s = J.start[k];
+        GzRun R{BZ_OK, GZ_LINK_NONE, 0, 0};
+        if (s != kGzNoStart) R = gz_run<GZ_COUNT>(io, T, J.G, k, s, J.start, 0);
+        if (lane == 0) { J.link[k] = R.link; J.text_len[k] = R.text; J.end_bit[k] = R.end_bit; J.reason[k] = R.reason; }
+        io.sync();
+    }
+}
+
+__global__ __launch_bounds__(64 * kGzWaves) void k_gz_decode(GzJob J)
+{
+    __shared__ BzTables tabs[kGzWaves];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    BzTables &T = tabs[wv];
+    GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    bz_prepare(io, T);
+    const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
+    for (uint64_t i = (uint64_t)blockIdx.x * kGzWaves + wv; i < J.n_chain; i += n_waves) {
+        const uint64_t k = J.chain[i];
+        io.sym = J.sym + J.off[i]; io.cap = J.off[i + 1] - J.off[i];
+        (void)gz_run<GZ_DECODE>(io, T, J.G, k, J.start[k], nullptr, J.end_bit[k]);
+        io.sync();
+    }
+}
+
+// element i's window needs element i - 1's: one workgroup, a barrier between elements
+__global__ __launch_bounds__(kGzWindowThreads) void k_gz_windows(GzJob J)
+{
+    for (uint64_t i = 1; i < J.n_chain; i++) {
+        const uint16_t *sp = J.sym + J.off[i - 1];
+        const uint64_t L = J.off[i] - J.off[i - 1];
+        const uint8_t *wp = i > 1 ? J.win + (i - 1) * (uint64_t)kGzWindow : nullptr;
+        uint8_t *w = J.win + i * (uint64_t)kGzWindow;
+        for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_entry(sp, L, wp, e);
+        __syncthreads();                                  // (workgroup scope: the next element reads what all threads wrote)
+    }
+}
+
+__global__ __launch_bounds__(kGzNarrowThreads) void k_gz_narrow(GzJob J)
+{
+    __shared__ uint32_t crc_tab[256];
+    __shared__ uint32_t crc_acc, bad_acc;
+    crc_tab[threadIdx.x & 255u] = bz_crc_entry(threadIdx.x & 255u);
+    for (uint64_t i = blockIdx.x; i < J.n_chain; i += gridDim.x) {
+        if (threadIdx.x == 0) { crc_acc = 0; bad_acc = 0; }
+        __syncthreads();
+        const uint64_t o0 = J.off[i], L = J.off[i + 1] - o0;
+        const uint16_t *sp = J.sym + o0;
+        const uint8_t *win = i ? J.win + i * (uint64_t)kGzWindow : nullptr;
+        // vector by vector of the OUTPUT's aligned space: [lead, lead + L) of it is the element's
+        const uint32_t lead = (uint32_t)(((uintptr_t)J.out + o0) & 15u);
+        uint8_t *const a_out = J.out + o0 - lead;          // 16-byte aligned (only [lead, lead + L) of it is touched)
+        const uint64_t end = lead + L, n_vec = (end + 15u) / 16u;
+        uint32_t bad = 0;
+        for (uint64_t v = threadIdx.x; v < n_vec; v += kGzNarrowThreads) {
+            const uint64_t lo = v * 16u;
+            if (lo >= lead && lo + 16u <= end) {
+                uint32_t w[4] = {0, 0, 0, 0};
+                for (uint32_t q = 0; q < 16u; q++) {
+                    const uint32_t b = gz_narrow(sp[lo - lead + q], win, o0);
+                    bad |= b >> 8;
+                    w[q >> 2] |= (b & 0xFFu) << (8u * (q & 3u));
+                }
+                *reinterpret_cast<uint4 *>(a_out + lo) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+                for (uint64_t q = lo < lead ? lead : lo; q < lo + 16u && q < end; q++) {
+                    const uint32_t b = gz_narrow(sp[q - lead], win, o0);
+                    bad |= b >> 8;
+                    a_out[q] = (uint8_t)b;
+                }
+            }
+        }
+        if (bad) atomicOr(&bad_acc, 1u);
+        __syncthreads();                                  // (workgroup scope: the slices below read what all threads stored)
+        // the element's CRC-32: 256 slices, each one's CRC moved to its place by x^(8 bytes behind it), summed
+        const uint64_t per = (L + kGzNarrowThreads - 1) / kGzNarrowThreads;
+        const uint64_t a = threadIdx.x * per < L ? threadIdx.x * per : L, b = a + per < L ? a + per : L;
+        if (b > a) {
+            const uint8_t *t = J.out + o0;
+            uint32_t c = 0xFFFFFFFFu;
+            for (uint64_t p = a; p < b; p++) c = crc_tab[(c ^ t[p]) & 0xFFu] ^ (c >> 8);
+            atomicXor(&crc_acc, gz_crc_join(~c, 0u, L - b));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            J.crc_part[i] = crc_acc;
+            if (bad_acc) atomicMin(J.verdict, (unsigned long long)i);
+        }
+        __syncthreads();
+    }
+}
+
+static hipError_t gz_grid(uint64_t n_items, int per_group, int groups_per_cu, unsigned *grid)
+{
+    int dev = 0, n_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    const uint64_t want = (n_items + per_group - 1) / per_group;
+    *grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)groups_per_cu * (uint64_t)std::max(n_cu, 1)));
+    return hipSuccess;
+}
+
+hipError_t launch_gz_find(const GzJob &J, hipStream_t st)
+{
+    unsigned grid = 1;
+    hipError_t e = gz_grid(J.G.nc, kGzWaves, 4, &grid);
+    if (e != hipSuccess) return e;
+    CRASS_LAUNCH(k_gz_find, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_count(const GzJob &J, hipStream_t st)
+{
+    unsigned grid = 1;
+    hipError_t e = gz_grid(J.G.nc, kGzWaves, 4, &grid);
+    if (e != hipSuccess) return e;
+    CRASS_LAUNCH(k_gz_count, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_decode(const GzJob &J, hipStream_t st)
+{
+    if (J.n_chain == 0) return hipSuccess;
+    unsigned grid = 1;
+    hipError_t e = gz_grid(J.n_chain, kGzWaves, 4, &grid);
+    if (e != hipSuccess) return e;
+    CRASS_LAUNCH(k_gz_decode, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_windows(const GzJob &J, hipStream_t st)
+{
+    if (J.n_chain < 2) return hipSuccess;
+    CRASS_LAUNCH(k_gz_windows, dim3(1), dim3(kGzWindowThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_narrow(const GzJob &J, hipStream_t st)
+{
+    if (J.n_chain == 0) return hipSuccess;
+    unsigned grid = 1;
+    hipError_t e = gz_grid(J.n_chain, 1, 8, &grid);
+    if (e != hipSuccess) return e;
+    CRASS_LAUNCH(k_gz_narrow, dim3(grid), dim3(kGzNarrowThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+} // namespace crass

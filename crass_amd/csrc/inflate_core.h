@@ -41,7 +41,12 @@ enum BzReason : int32_t {
     BZ_OUTPUT_LONG = 7,      // more text than ISIZE
     BZ_OUTPUT_SHORT = 8,     // the final block ends before ISIZE bytes
     BZ_CRC = 9,              // the text's CRC-32 is not the trailer's
-    BZ_NOT_BGZF = 10         // the index: a member that does not parse as BGZF (a plain .gz); position: that member's first byte
+    BZ_NOT_BGZF = 10,        // the index: a member that does not parse as BGZF (a plain .gz); position: that member's first byte
+    // plain gzip, one member inflated chunk by chunk (gunzip_core.h); `member` is the chunk there
+    BZ_NOT_GZIP = 11,        // not a gzip header (magic, method, reserved flags, header CRC), or a header that runs into the trailer
+    BZ_NO_START = 12,        // a chunk on the chain met no block start of a later chunk within kGzMaxSpan chunks
+    BZ_TRAILING = 13,        // the final block ends before the deflate data does (further members, trailing bytes)
+    BZ_MARKER = 14           // a distance that reaches in front of the text's first byte
 };
 
 static const uint32_t kBzMaxText = 65536;        // ISIZE of a member (bgzf_walk's limit)
@@ -178,6 +183,67 @@ template <class IO> CRASS_HD inline void bz_prepare(IO &io, BzTables &T)
     io.sync();
 }
 
+// the literal / length and distance codes of a block of type 1 (fixed) or 2 (dynamic: its header comes off the reader): BZ_OK or
+// the reason
+template <class IO> CRASS_HD inline int32_t bz_block_tables(IO &io, BzTables &T, BzBits<IO> &B, uint32_t type)
+{
+    if (type == 1) {
+        io.par(288, [&](uint32_t s) { T.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8); });
+        io.par(32, [&](uint32_t s) { T.lens[288 + s] = 5; });
+        (void)bz_build(io, T.lit, T.lens, 288);
+        (void)bz_build(io, T.dist, T.lens + 288, 32);
+    } else {
+        B.refill();
+        const uint32_t hlit = B.take(5) + 257, hdist = B.take(5) + 1, hclen = B.take(4) + 4;
+        if (B.over()) return BZ_INPUT_END;
+        if (hlit > 286 || hdist > 30) return BZ_CODE_LENGTHS;
+        const uint64_t order_lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 |
+                                  5ull << 45 | 11ull << 50 | 4ull << 55;
+        const uint64_t order_hi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
+        io.par(19, [&](uint32_t s) { T.lens[s] = 0; });
+        io.sync();
+        for (uint32_t k = 0; k < hclen; k++) {
+            B.refill();
+            const uint32_t v = B.take(3);
+            if (B.over()) return BZ_INPUT_END;
+            const uint32_t s = (uint32_t)((k < 12 ? order_lo >> (5 * k) : order_hi >> (5 * (k - 12))) & 31u);
+            if (io.lead()) T.lens[s] = (uint8_t)v;
+        }
+        BzCode &CL = T.cl;
+        if (bz_build(io, CL, T.lens, 19) != BZ_COMPLETE) return BZ_CODE_LENGTHS;
+        const uint32_t total = hlit + hdist;
+        for (uint32_t i = 0; i < total;) {            // a code-length symbol: at least one bit
+            B.refill();
+            int32_t why = 0;
+            const int32_t s = bz_symbol(B, CL, &why);
+            if (s < 0) return why;
+            if (s < 16) {
+                if (io.lead()) T.lens[i] = (uint8_t)s;
+                i++;
+                io.sync();
+                continue;
+            }
+            uint32_t rep, val = 0;
+            if (s == 16) { rep = 3 + B.take(2); }
+            else if (s == 17) rep = 3 + B.take(3);
+            else rep = 11 + B.take(7);
+            if (B.over()) return BZ_INPUT_END;
+            if (s == 16) {
+                if (i == 0) return BZ_CODE_LENGTHS;
+                val = T.lens[i - 1];
+            }
+            if (rep > total - i) return BZ_CODE_LENGTHS;
+            io.par(rep, [&](uint32_t k) { T.lens[i + k] = (uint8_t)val; });
+            io.sync();
+            i += rep;
+        }
+        if (T.lens[256] == 0) return BZ_CODE_LENGTHS;
+        if (bz_build(io, T.lit, T.lens, hlit) != BZ_COMPLETE) return BZ_CODE_LENGTHS;
+        if (bz_build(io, T.dist, T.lens + hlit, hdist) == BZ_REFUSED) return BZ_CODE_LENGTHS;
+    }
+    return BZ_OK;
+}
+
 // the deflate data of one member -> its text.  BZ_OK: exactly isize bytes were put
 template <class IO> CRASS_HD inline int32_t bz_inflate_member(IO &io, BzTables &T, uint32_t n_in, uint32_t isize)
 {
@@ -204,60 +270,7 @@ template <class IO> CRASS_HD inline int32_t bz_inflate_member(IO &io, BzTables &
             pos += len;
             B.ip = from + len; B.hold = 0; B.nb = 0;
         } else {
-            if (type == 1) {
-                io.par(288, [&](uint32_t s) { T.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8); });
-                io.par(32, [&](uint32_t s) { T.lens[288 + s] = 5; });
-                (void)bz_build(io, T.lit, T.lens, 288);
-                (void)bz_build(io, T.dist, T.lens + 288, 32);
-            } else {
-                B.refill();
-                const uint32_t hlit = B.take(5) + 257, hdist = B.take(5) + 1, hclen = B.take(4) + 4;
-                if (B.over()) return BZ_INPUT_END;
-                if (hlit > 286 || hdist > 30) return BZ_CODE_LENGTHS;
-                const uint64_t order_lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 |
-                                          5ull << 45 | 11ull << 50 | 4ull << 55;
-                const uint64_t order_hi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
-                io.par(19, [&](uint32_t s) { T.lens[s] = 0; });
-                io.sync();
-                for (uint32_t k = 0; k < hclen; k++) {
-                    B.refill();
-                    const uint32_t v = B.take(3);
-                    if (B.over()) return BZ_INPUT_END;
-                    const uint32_t s = (uint32_t)((k < 12 ? order_lo >> (5 * k) : order_hi >> (5 * (k - 12))) & 31u);
-                    if (io.lead()) T.lens[s] = (uint8_t)v;
-                }
-                BzCode &CL = T.cl;
-                if (bz_build(io, CL, T.lens, 19) != BZ_COMPLETE) return BZ_CODE_LENGTHS;
-                const uint32_t total = hlit + hdist;
-                for (uint32_t i = 0; i < total;) {            // a code-length symbol: at least one bit
-                    B.refill();
-                    int32_t why = 0;
-                    const int32_t s = bz_symbol(B, CL, &why);
-                    if (s < 0) return why;
-                    if (s < 16) {
-                        if (io.lead()) T.lens[i] = (uint8_t)s;
-                        i++;
-                        io.sync();
-                        continue;
-                    }
-                    uint32_t rep, val = 0;
-                    if (s == 16) { rep = 3 + B.take(2); }
-                    else if (s == 17) rep = 3 + B.take(3);
-                    else rep = 11 + B.take(7);
-                    if (B.over()) return BZ_INPUT_END;
-                    if (s == 16) {
-                        if (i == 0) return BZ_CODE_LENGTHS;
-                        val = T.lens[i - 1];
-                    }
-                    if (rep > total - i) return BZ_CODE_LENGTHS;
-                    io.par(rep, [&](uint32_t k) { T.lens[i + k] = (uint8_t)val; });
-                    io.sync();
-                    i += rep;
-                }
-                if (T.lens[256] == 0) return BZ_CODE_LENGTHS;
-                if (bz_build(io, T.lit, T.lens, hlit) != BZ_COMPLETE) return BZ_CODE_LENGTHS;
-                if (bz_build(io, T.dist, T.lens + hlit, hdist) == BZ_REFUSED) return BZ_CODE_LENGTHS;
-            }
+            { const int32_t why = bz_block_tables(io, T, B, type); if (why != BZ_OK) return why; }
             for (;;) {                                        // a literal / length symbol: at least one bit
                 B.refill();
                 int32_t why = 0;

@@ -302,6 +302,55 @@ def bgzf_inflate_host(buf, index=None):
     return out
 
 
+class GzipPlan:
+    """What the gzip rule decided (crass_gzip_plan), as numpy copies: n_chunks, n_chain, start_bit (uint64, ~0: none), link (uint32:
+    a chunk, or LINK_END / LINK_UNFINISHED / LINK_BAD / LINK_NONE) and text_len (uint64), one entry per chunk."""
+    LINK_END, LINK_UNFINISHED, LINK_BAD, LINK_NONE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+
+    def __init__(self, v):
+        n = int(v.n_chunks)
+        self.n_chunks, self.n_chain = n, int(v.n_chain)
+        self.start_bit = _np(v.start_bit, n, np.uint64).copy() if n else np.zeros(0, np.uint64)
+        self.link = _np(v.link, n, np.uint32).copy() if n else np.zeros(0, np.uint32)
+        self.text_len = _np(v.text_len, n, np.uint64).copy() if n else np.zeros(0, np.uint64)
+
+
+def gzip_inflate_host(buf, chunk_bytes=0, out_cap=None, with_plan=False):
+    """The text of a plain (single-member) gzip file's bytes, chunk by chunk through the rule the kernels run
+    (crass_gzip_inflate_host; no GPU needed): a uint8 array, with with_plan (text, GzipPlan).  chunk_bytes: 0 is the default.
+    Raises BgzfDeclined with the verdict (its `plan` holds the GzipPlan when the header parsed); out_cap smaller than the text
+    raises CrassError with status 8 and the text's size in its `n_text`."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    ptr = a.ctypes.data if len(a) else None
+    n_text, ver, pc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC()
+    try:
+        st = lib.crass_gzip_inflate_host(ptr, len(a), int(chunk_bytes), None, 0, C.byref(n_text), C.byref(pc), C.byref(ver))
+        plan = GzipPlan(pc)
+    finally:
+        lib.crass_gzip_plan_free(C.byref(pc))
+    if st == 2:
+        e = BgzfDeclined(st, "crass_gzip_inflate_host", ver)
+        e.plan = plan
+        raise e
+    if st not in (0, 8):
+        _chk(st, "crass_gzip_inflate_host")
+    cap = int(n_text.value) if out_cap is None else int(out_cap)
+    out = np.zeros(cap, np.uint8)
+    st = lib.crass_gzip_inflate_host(ptr, len(a), int(chunk_bytes), out.ctypes.data if cap else None, cap, C.byref(n_text), None, C.byref(ver))
+    if st == 2:
+        e = BgzfDeclined(st, "crass_gzip_inflate_host", ver)
+        e.plan = plan
+        raise e
+    if st == 8:
+        e = CrassError(st, "crass_gzip_inflate_host")
+        e.n_text, e.out = int(n_text.value), out
+        raise e
+    _chk(st, "crass_gzip_inflate_host")
+    out = out[:int(n_text.value)]
+    return (out, plan) if with_plan else out
+
+
 class FastxFilesLayout:
     """Several files as one read set (crass_fastx_files_layout), as numpy copies: n_files, n_reads, max_len, file_read_base /
     file_byte_base (uint64, n_files + 1; byte bases and rec_pos are ARENA positions: every file's text with a "\\n" behind it),
@@ -822,6 +871,58 @@ class SearchEngine:
         if st == 2 and ver.reason:
             raise BgzfDeclined(st, "crass_hip_load_fastx_bgzf", ver)
         return self._fastx_result(st, v, "crass_hip_load_fastx_bgzf")
+
+    def inflate_gzip_device(self, tensor_in, tensor_out, chunk_bytes=0, with_plan=False):
+        """A plain (single-member) gzip file whose bytes are in a torch uint8 DEVICE tensor (any alignment), inflated on the device
+        chunk by chunk into tensor_out (the same): crass_hip_inflate_gzip_device.  Returns the bytes of text, with with_plan
+        (n_text, GzipPlan); raises BgzfDeclined with the host function's verdict (`plan`: the GzipPlan when the header parsed);
+        a tensor_out too small raises CrassError with status 8 and the text's size in its `n_text`, nothing written.  The
+        resident set is untouched."""
+        for t in (tensor_in, tensor_out):
+            if str(t.dtype) != "torch.uint8" or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("inflate_gzip_device needs contiguous uint8 device tensors")
+        n_text, ver, pc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC()
+        try:
+            st = self.lib.crass_hip_inflate_gzip_device(self.h, int(tensor_in.data_ptr()) if tensor_in.numel() else None, int(tensor_in.numel()),
+                                                        int(chunk_bytes), int(tensor_out.data_ptr()) if tensor_out.numel() else None,
+                                                        int(tensor_out.numel()), C.byref(n_text), C.byref(pc), C.byref(ver))
+            plan = GzipPlan(pc)
+        finally:
+            self.lib.crass_gzip_plan_free(C.byref(pc))
+        if st == 2:
+            e = BgzfDeclined(st, "crass_hip_inflate_gzip_device", ver)
+            e.plan = plan
+            raise e
+        if st == 8:
+            e = CrassError(st, "crass_hip_inflate_gzip_device")
+            e.n_text, e.plan = int(n_text.value), plan
+            raise e
+        _chk(st, "crass_hip_inflate_gzip_device")
+        return (int(n_text.value), plan) if with_plan else int(n_text.value)
+
+    def load_fastx_gzip(self, buf, pad_uniform=2, read_index_base=0, keep=None):
+        """The bytes of a plain gzip FASTA / FASTQ file in host memory: inflated chunk by chunk, scanned and packed on the device
+        (crass_hip_load_fastx_gzip), the mirror of load_fastx_bgzf."""
+        a = _bytes_arg(buf)
+        if keep is not None and (str(keep.dtype) != "torch.uint8" or not keep.is_cuda or not keep.is_contiguous()):
+            raise ValueError("load_fastx_gzip(keep=...) needs a contiguous uint8 device tensor")
+        v, ver = _abi.FastxLayoutC(), _abi.BgzfVerdict()
+        st = self.lib.crass_hip_load_fastx_gzip(self.h, a.ctypes.data if len(a) else None, len(a), int(pad_uniform), int(read_index_base),
+                                                int(keep.data_ptr()) if keep is not None and keep.numel() else None,
+                                                int(keep.numel()) if keep is not None else 0, C.byref(v), C.byref(ver))
+        if st == 2 and ver.reason:
+            raise BgzfDeclined(st, "crass_hip_load_fastx_gzip", ver)
+        return self._fastx_result(st, v, "crass_hip_load_fastx_gzip")
+
+    def set_gzip_on_device(self, on=True):
+        """load_fastx_files takes a plain gzip file on a BGZF file's terms (crass_hip_set_gzip_on_device); default off."""
+        _chk(self.lib.crass_hip_set_gzip_on_device(self.h, 1 if on else 0), "crass_hip_set_gzip_on_device")
+
+    def last_gzip_ms(self):
+        """HIP-event milliseconds of the last gzip inflate's steps: dict find, count, decode, windows, narrow (stage timing >= 1, else 0)."""
+        ms = (C.c_float * 5)()
+        _chk(self.lib.crass_hip_last_gzip_ms(self.h, ms), "crass_hip_last_gzip_ms")
+        return dict(zip(("find", "count", "decode", "windows", "narrow"), (float(x) for x in ms)))
 
     def load_fastx_files(self, bufs, pad_uniform=2):
         """Several input files' bytes (plain FASTA / FASTQ or BGZF, each on its own terms) as ONE resident set in (file, read)

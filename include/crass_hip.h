@@ -605,7 +605,8 @@ float crass_hip_last_scan_ms(const crass_hip_ctx *ctx);
  * reason: 0 accepted, 1 block type 3, 2 stored block LEN != ~NLEN, 3 code lengths (over-subscribed or incomplete code — but a
  * single distance code of one bit —, repeat code 16 first, a repeat past HLIT + HDIST, no end-of-block code, HLIT > 286, HDIST > 30),
  * 4 a bit pattern that is no code, length symbol 286 / 287, distance symbol 30 / 31, 5 a distance beyond the member's own text,
- * 6 the deflate data ends before the final block does, 7 / 8 more / less text than ISIZE, 9 CRC-32, 10 not BGZF.
+ * 6 the deflate data ends before the final block does, 7 / 8 more / less text than ISIZE, 9 CRC-32, 10 not BGZF (11 .. 14: plain
+ * gzip on the device, below).
  * A member's verdict is the first reason its decoder meets; the file's is that of the first offending member; in_pos is the file
  * position of that member's first byte.  Bits between a member's final block and its trailer are ignored. */
 typedef struct {
@@ -651,6 +652,53 @@ int  crass_hip_load_fastx_bgzf(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_
  * crass_hip_load_fastx_bgzf call; measured when the stage timing level is >= 1, else 0.  (No reference counterpart: crass has no
  * timers.) */
 float crass_hip_last_inflate_ms(const crass_hip_ctx *ctx);
+/* ---- plain gzip input, inflated on the device chunk by chunk (gunzip.hip) ----
+ * replaces: getFileHandle / gzopen + gzread (SeqUtils.cpp:100-126) for a .gz input as gzip / pigz write it: ONE member, one deflate
+ * stream.  The stream is cut into chunks of about chunk_bytes (0: the default, 256 KB; at least 4096, at most 4 MB); a chunk is entered at the
+ * first dynamic block start found inside it, bytes copied from the unknown 32 KB in front of a chunk are carried as 16-bit
+ * markers and resolved afterwards, and the result is accepted only with the trailer's length and CRC-32 (gunzip_core.h).  A file
+ * is either inflated exactly (the bytes zlib gives) or declined with a crass_bgzf_verdict whose `member` is the offending CHUNK
+ * (the first in text order) and whose in_pos is the file byte that holds that chunk's start bit (0 for header and trailer reasons).
+ * reason: 1 .. 6 as above, 7 / 8 more / less text than ISIZE, 9 CRC-32, 11 not a gzip header (magic, method, reserved flags,
+ * header CRC) or a header that runs into the trailer, 12 a chunk met no later chunk's block start within 32 chunks (stored or
+ * fixed blocks throughout, blocks much longer than a chunk: take a larger chunk_bytes), 13 the member ends before the input does
+ * (further members, trailing bytes), 14 a distance that reaches in front of the text's first byte. */
+#define CRASS_GZIP_LINK_END        0xFFFFFFFFu   /* the chunk ran to the final block's end */
+#define CRASS_GZIP_LINK_UNFINISHED 0xFFFFFFFEu   /* ... gave up at the span's end */
+#define CRASS_GZIP_LINK_BAD        0xFFFFFFFDu   /* ... met a fault */
+#define CRASS_GZIP_LINK_NONE       0xFFFFFFFCu   /* no start was found in the chunk */
+typedef struct {
+    uint64_t n_chunks, n_chain;            /* chunks of the deflate data; how many of them the text is made of */
+    uint64_t *start_bit;                   /* [n_chunks] the bit of the deflate data where chunk k is entered, ~0: nowhere */
+    uint32_t *link;                        /* [n_chunks] the chunk whose start this one ran into, or CRASS_GZIP_LINK_* */
+    uint64_t *text_len;                    /* [n_chunks] the text between the chunk's start and its link */
+} crass_gzip_plan;
+void crass_gzip_plan_free(crass_gzip_plan *plan);
+/* replaces: gzread (SeqUtils.cpp:100-126) — the rule above as a serial run on the host, no GPU needed: what the kernels are tested
+ * against.  CRASS_OK: out[0 .. *n_text) is the text.  CRASS_ERR_OVERFLOW: out_cap < *n_text, *n_text is filled and nothing is
+ * written (out NULL with out_cap 0 asks for the size).  CRASS_ERR_UNSUPPORTED: declined, *v (may be NULL) says why; out's contents
+ * are unspecified.  plan (may be NULL) reports what the rule decided, whenever the header parsed; its arrays are malloc'd:
+ * crass_gzip_plan_free.  CRASS_ERR_INVALID_ARG: NULL n_text, NULL bytes / out with a size. */
+int  crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                             crass_gzip_plan *plan, crass_bgzf_verdict *v);
+/* replaces: gzread (SeqUtils.cpp:100-126) for compressed bytes that are in HBM: d_in and d_out are caller-owned DEVICE pointers of any
+ * alignment.  k_gz_find (a lane per bit position), k_gz_count and k_gz_decode (a wave per chunk), k_gz_windows, k_gz_narrow.
+ * Scratch: 2 bytes per text byte plus 32 KB per chain element, given back before the call returns.  Results as
+ * crass_gzip_inflate_host, the verdict and the plan field for field; CRASS_ERR_OVERFLOW is known before anything is stored.  The
+ * resident set is untouched. */
+int  crass_hip_inflate_gzip_device(crass_hip_ctx *ctx, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
+                                   uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v);
+/* replaces: getFileHandle / gzopen + the kseq_read loop (SeqUtils.cpp:100-126, libcrispr.cpp:96-131) for a plain gzip file's bytes in
+ * HOST memory: the mirror of crass_hip_load_fastx_bgzf (default chunk size).  d_text_cap smaller than the text: CRASS_ERR_INVALID_ARG,
+ * found after the count step, nothing resident. */
+int  crass_hip_load_fastx_gzip(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                               uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v);
+/* on != 0: crass_hip_load_fastx_files takes a plain gzip file on the terms of a BGZF one (inflated on the device into the arena).
+ * Default off: such a file is declined with reason 10.  (No reference counterpart.) */
+int  crass_hip_set_gzip_on_device(crass_hip_ctx *ctx, int on);
+/* HIP-event milliseconds of the last gzip inflate's five steps, ms[0 .. 5): find, count, decode, windows, narrow; measured when the
+ * stage timing level is >= 1, else 0.  crass_hip_last_inflate_ms holds their sum.  (No reference counterpart.) */
+int  crass_hip_last_gzip_ms(const crass_hip_ctx *ctx, float *ms);
 /* ---- the text of selected reads, out of the resident set ----
  * n records back to back: record k is chars[off[k] .. off[k+1]), off[n+1] the exclusive prefix sum of the records' lengths.
  * The gather and the unpacking run on the device (k_fetch_text, pack.hip), where the words are: only the selected reads'
