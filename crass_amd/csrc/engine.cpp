@@ -189,6 +189,7 @@ struct EnvSwitches {
     uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
     bool inflate_hbm_window = true;                  // CRASS_INFLATE_WINDOW=lds: k_bgzf_inflate decodes in the wave's LDS window, not in the output's own range (A/B switch, inflate.hip)
     uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
+    uint32_t probe_blocks = 0;                       // tests: CRASS_PROBE_BLOCKS caps the grid of pass 2's anchor probe, so that a few thousand reads are several tiles per wave (0: off)
     void read()
     {
         auto on = [](const char *n) { return getenv(n) != nullptr; };
@@ -212,6 +213,7 @@ struct EnvSwitches {
         text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
         inflate_hbm_window = true; if (const char *e = getenv("CRASS_INFLATE_WINDOW")) inflate_hbm_window = strcmp(e, "lds") != 0;
         hid_hash_bits = 64; if (const char *e = getenv("CRASS_HID_TEST_HASH_BITS")) hid_hash_bits = (uint32_t)std::min(64, std::max(0, atoi(e)));
+        probe_blocks = 0; if (const char *e = getenv("CRASS_PROBE_BLOCKS")) probe_blocks = (uint32_t)std::max(0, atoi(e));
         pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
     }
 };
@@ -4520,10 +4522,10 @@ int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_
     // otherwise the byte-wise automaton scans them separately
     const uint64_t n_exc = dmp ? 0 : c->R.n_exc;
     if (dmp) {
-        HIPCHK(c, launch_anchor_filter_dev(c->R, c->dm.M, c->d_found.p, c->d_mask.p, c->stream));
+        HIPCHK(c, launch_anchor_filter_dev(c->R, c->dm.M, c->d_found.p, c->d_mask.p, c->stream, c->env.probe_blocks));
         anchors = true;
     } else if (c->have_anchors) {
-        hipError_t ae = launch_anchor_filter(c->R, c->K, c->d_found.p, c->d_mask.p, c->stream);
+        hipError_t ae = launch_anchor_filter(c->R, c->K, c->d_found.p, c->d_mask.p, c->stream, c->env.probe_blocks);
         if (ae == hipSuccess) anchors = true;
         else if (ae != hipErrorNotSupported) { c->last_hip = (int)ae; return CRASS_ERR_HIP; }
     }

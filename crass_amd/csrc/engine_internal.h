@@ -307,7 +307,8 @@ hipError_t launch_device_merge(const DevMerge &M, hipStream_t st, bool init_done
                                hipEvent_t ev_fork = nullptr, hipEvent_t ev_view = nullptr,
                                hipEvent_t ev_apply = nullptr);     // ev_apply: behind k_dmx_apply (the blob's token half is complete)
 // pass-2 anchor filter with table parameters read from the device (M.st); flags nothing when M.st->fail
-hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st);
+// (max_blocks: 0, or a cap on the grid — CRASS_PROBE_BLOCKS, tests)
+hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st, uint32_t max_blocks = 0);
 hipError_t launch_dm_verify(const DevReads &R, const DevMerge &M, const uint64_t *idx, const uint32_t *d_n, uint64_t n_max,
                             uint32_t *info_by_slot, uint32_t *pid_by_slot, hipStream_t st);
 hipError_t warm_dmerge_module();      // loads dmerge.hip's code object on the current device (crass_hip_create)
@@ -422,7 +423,7 @@ hipError_t launch_recruit_general(const DevReads &R, const DevAutomaton &A, cons
 hipError_t launch_recruit_lds(const DevReads &R, const DevAutomaton &A, const uint8_t *found_flag,
                               uint64_t *hitmask, uint32_t *hit_info, hipStream_t st);
 hipError_t launch_anchor_filter(const DevReads &R, const DevAnchors &K, const uint8_t *found_flag,
-                                uint64_t *hitmask, hipStream_t st);
+                                uint64_t *hitmask, hipStream_t st, uint32_t max_blocks = 0);
 hipError_t launch_recruit_list(const DevReads &R, const DevAutomaton &A, const uint64_t *idx, const uint32_t *d_n,
                                uint64_t n_max, uint32_t *info_by_slot, uint32_t *pid_by_slot, hipStream_t st);
 hipError_t launch_recruit_exceptions(const DevReads &R, const DevAutomaton &A, const uint8_t *found_flag,

@@ -157,14 +157,35 @@ static __device__ __forceinline__ void ff_load_row(const DevReads &R, const DevP
     if (r < R.n_reads) ff_load_words<W>(R, r, w);
 }
 
+// The same request for the kernels that keep the NEXT row in flight while they scan one: every load is unconditional, from a
+// read index clamped to the last read (r_last = n_reads - 1), and the exception word's is only under wave-uniform conditions.
+// A load under a lane predicate is a divergent branch, and behind its join the compiler's wait for the OLDER row came out as
+// vmcnt(0) — it waited for the row just requested too (profiles/NOTES_r17.md).  A clamped lane's row is never used: the callers
+// test r < n_reads where a result leaves the lane.
+template <int W>
+static __device__ __forceinline__ void ff_request_row(const DevReads &R, const DevParams &P, uint64_t r, uint64_t r_last, uint32_t (&w)[W], uint64_t &exc_word)
+{
+    uint64_t wave_word = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(r >> 38)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)(r >> 6));
+    if (wave_word > (r_last >> 6)) wave_word = r_last >> 6;
+    // (loaded whether it is used or not — exc_survive: eight bytes per wave and row: behind the join of even a wave-uniform
+    // branch the wait for the row before must assume the path WITHOUT the load, and comes out one short)
+    const uint32_t *e = R.exc_mask + 2 * wave_word;
+    const uint64_t ew = (uint64_t)e[0] | ((uint64_t)e[1] << 32);
+    exc_word = P.exc_survive ? 0ull : ew;
+    ff_load_words<W>(R, r < r_last ? r : r_last, w);
+}
+
 // The scan of one row: acc[k] halfword h becomes 0 iff the 8-mer at seed 8 (2k + h) re-occurs at some shift D0 .. D1.
-template <int D0, int D1, int LCT, int WX, int SW>
-static __device__ __forceinline__ void ff_exact_scan(const uint32_t (&w)[WX], uint32_t (&acc)[SW])
+// (early(): called once behind the first shift, i.e. behind the wait for the row — where a streaming caller puts a store)
+struct ff_nothing { __device__ __forceinline__ void operator()() const {} };
+template <int D0, int D1, int LCT, int WX, int SW, typename F = ff_nothing>
+static __device__ __forceinline__ void ff_exact_scan(const uint32_t (&w)[WX], uint32_t (&acc)[SW], F &&early = F())
 {
 #pragma unroll
     for (int i = 0; i < SW; i++) acc[i] = 0xFFFFFFFFu;
 #pragma unroll
     for (int d = D0; d <= D1; d++) {
+        if (d == D0 + 1) early();
         const int q = d >> 4;
         const int sh = (d & 15) * 2;
 #pragma unroll
@@ -197,7 +218,10 @@ static __device__ __forceinline__ uint32_t ff_exact_hint(const uint32_t (&acc)[S
 }
 
 // RPL: reads per lane.  A lane's reads are 256 apart (a wave still covers 64 consecutive reads, one mask word); the row of the
-// next read is loaded before the current one is scanned, so a wave's only exposed memory latency is its first load.
+// next read is requested before the current one is scanned and the wait for the current one is COUNTED (vmcnt(4): the next
+// row's three loads and its exception word stay outstanding), so a wave's only exposed memory latency is its first load.
+// (Until round 17 the loads sat under the lane's r < n_reads and the waits came out as vmcnt(0): the rows were in effect
+// awaited in pairs, two exposed round trips per four rows.  ff_request_row, profiles/NOTES_r17.md.)
 template <int W, int D0, int D1, int LCT, int RPL>
 __global__ __launch_bounds__(256) void k_filter_fast_impl(DevReads R, DevParams P, uint64_t *hitmask, uint32_t *seed_hint, uint8_t *clear_found)
 {
@@ -206,24 +230,33 @@ __global__ __launch_bounds__(256) void k_filter_fast_impl(DevReads R, DevParams 
     // beside 2.5 KB of loads, instead of a 12-100 MB fill kernel in front of every seed scan (6-30 us of the step)
     if (clear_found && r_first == 0) clear_found[R.n_reads] = 0;
     constexpr int WX = W + (D1 >> 4) + 2;
+    const uint64_t r_last = R.n_reads - 1;
     uint32_t nxt[W];
     uint64_t nxt_exc;
-    ff_load_row<W>(R, P, r_first, nxt, nxt_exc);
+    if constexpr (RPL > 1) ff_request_row<W>(R, P, r_first, r_last, nxt, nxt_exc);
+    else ff_load_row<W>(R, P, r_first, nxt, nxt_exc);   // (one row per lane: nothing to keep in flight, the form of round 7)
 #pragma unroll
     for (int it = 0; it < RPL; it++) {
     const uint64_t r = r_first + (uint64_t)it * 256u;
     const bool active = r < R.n_reads;
-    if (clear_found && active) clear_found[r] = 0;
+    if constexpr (RPL == 1) { if (clear_found && active) clear_found[r] = 0; }
     uint32_t w[WX];
 #pragma unroll
     for (int i = 0; i < WX; i++) w[i] = i < W ? nxt[i] : 0u;
     const bool exc = (nxt_exc >> (r & 63)) & 1u;        // (exception reads are left to their own pass, see k_filter_general)
-    if (it + 1 < RPL) ff_load_row<W>(R, P, r + 256u, nxt, nxt_exc);
+    if (it + 1 < RPL) {
+        ff_request_row<W>(R, P, r + 256u, r_last, nxt, nxt_exc);
+        __builtin_amdgcn_sched_barrier(0);              // (the requests stay IN FRONT of the scan: left alone the scheduler sinks them four fifths into it)
+    }
     const uint32_t L = active ? rd_len(R, r) : 0u;
     // seeds live in halfwords 0 .. searchEnd/8 with searchEnd = L-58 <= 16W-58: only words < SW hold one
     constexpr int SW = ((16 * W - 58) / 8 + 2) / 2;
     uint32_t acc[SW];
-    ff_exact_scan<D0, D1, LCT>(w, acc);
+    // (the flag's store counts on vmcnt like the loads.  Issued just behind the wait for this row — a whole scan before the next
+    // wait — and by every lane, a lane past the end clearing the spare byte once more, it is long complete when the next row is
+    // waited for and no divergent branch holds it; in front of this row's wait it would be one more operation of unknown
+    // presence between the two rows, behind the scan the next wait would sit out most of its round trip.)
+    ff_exact_scan<D0, D1, LCT>(w, acc, [&]() { if constexpr (RPL > 1) { if (clear_found) clear_found[active ? r : R.n_reads] = 0; } });
     bool hit = false;
     // a uniform-length instantiation knows the seed count at compile time (D0 = lowDR + lowSp, checked by the launcher)
     const int searchEnd = LCT > 0 ? (LCT - D0 - 8 - 1) : (int)(L - P.lowDR - P.lowSp - 8 - 1);
@@ -268,9 +301,10 @@ __global__ __launch_bounds__(256) void k_filter_fast_pairs(DevReads R, DevParams
     constexpr int SW = ((16 * W - 58) / 8 + 2) / 2;
     constexpr int n_seed = (LCT - D0 - 9) / 8 + 1;
     constexpr uint32_t M14 = 0x3FFF3FFFu;
+    const uint64_t r_last = R.n_reads - 1;
     uint32_t nxt[W];
     uint64_t nxt_exc;
-    ff_load_row<W>(R, P, r_first, nxt, nxt_exc);
+    ff_request_row<W>(R, P, r_first, r_last, nxt, nxt_exc);
     if (threadIdx.x < 2 * 4 * RPL) tile_mask[threadIdx.x] = 0;
     if (threadIdx.x == 0) q_n = 0;
     __syncthreads();
@@ -278,17 +312,21 @@ __global__ __launch_bounds__(256) void k_filter_fast_pairs(DevReads R, DevParams
     for (int it = 0; it < RPL; it++) {
         const uint64_t r = r_first + (uint64_t)it * 256u;
         const bool active = r < R.n_reads;
-        if (clear_found && active) clear_found[r] = 0;
         uint32_t w[WX];
 #pragma unroll
         for (int i = 0; i < WX; i++) w[i] = i < W ? nxt[i] : 0u;
         const bool exc = (nxt_exc >> (r & 63)) & 1u;
-        if (it + 1 < RPL) ff_load_row<W>(R, P, r + 256u, nxt, nxt_exc);
+        if (it + 1 < RPL) {
+            ff_request_row<W>(R, P, r + 256u, r_last, nxt, nxt_exc);
+            __builtin_amdgcn_sched_barrier(0);          // (the requests stay IN FRONT of the scan: left alone the scheduler sinks them four fifths into it)
+        }
         uint32_t acc[SW];
 #pragma unroll
         for (int i = 0; i < SW; i++) acc[i] = 0x3C003C00u;
 #pragma unroll
         for (int d = D0; d <= D1; d += 2) {
+            // (the found flag's store, just behind the wait for this row and by every lane: see k_filter_fast_impl)
+            if (d == D0 + 2 && clear_found) clear_found[active ? r : R.n_reads] = 0;
 #pragma unroll
             for (int k = 0; k < SW; k++) {
                 if (d > LCT - 9 - 16 * k) continue;

@@ -246,104 +246,146 @@ static __device__ __forceinline__ void anchor_filter_body(const DevReads &R, con
         }
         return;
     }
-    // uniform stride: the words of the wave's NEXT tile are requested before the current one is hashed and probed, so a
-    // wave never sits idle for the ~1-2 us of its own loads (4 waves per SIMD — the table takes 128 KB of LDS — were
-    // not enough to cover them: the kernel ran at 62 % of its VALU issue time)
-    uint32_t pre[W > 0 ? W : 1];
-    auto prefetch = [&](uint64_t tile) {
-        if (W > 0) {
-            const uint64_t rr = tile * 64 + lane;
-            if (tile < n_tiles && rr < R.n_reads) {
-                const uint32_t *gp = R.packed + rr * (uint64_t)W;
+    if constexpr (W > 0) {
+        // Uniform stride, a software pipeline one tile deep: EVERYTHING a tile's turn reads from global memory — the rows, the
+        // found flag, the read's length (padded ragged sets) and its exception word (host-built tables) — is requested one
+        // turn earlier, in one place, and carried in registers; where header ids exist a tile's ids are requested TWO turns
+        // earlier, so that the flag's address is in a register when the flag is requested.  A turn then waits once, at its
+        // top, for what the turn before it asked for, and asks for nothing it needs itself: between the requests and the next
+        // top lie the tile's 2W-1 hashes and LDS probes.  (Until round 17 only the rows were requested ahead and the flag
+        // was loaded — behind a wait that, vmcnt retiring in order, also covered the rows just requested — in front of the
+        // probes: two serial HBM round trips per wave and tile, two thirds of the wave's time parked, NOTES r17.)
+        // The loads are unconditional, from an index clamped to the last read, not loads under a lane predicate: behind the
+        // join of a divergent branch the compiler's wait for an OLDER load comes out as vmcnt(0).  A clamped lane's values are
+        // never used (r < n_reads is tested where they would be).  found_flag is read a tile early: nothing writes it while
+        // the probe runs — the scan that cleared it and the kernels that set it are complete before the probe is launched,
+        // and pass 2's own recruits are marked by a later kernel.  The mask word of a tile is stored in the NEXT turn, behind
+        // that turn's requests: stored at the end of its own turn (or in front of the requests) the store is the newest
+        // vector-memory operation when the wait comes, and the wave sits out the store's round trip instead.
+        // (MODE 2 and 4 probe keys in global memory inside the turn; those loads wait where they are used, as before.)
+        const uint64_t wave0 = uni64(wave_global), wave_step = uni64(wave_total);
+        const uint64_t r_last = R.n_reads - 1;
+        const bool ids = R.header_id != nullptr;         // (wave-uniform like uniform_len and with_exc: scalar branches)
+        uint32_t pre[W], pre_len = 0, pre_exc = 0;
+        uint32_t pre_found = 0;
+        uint64_t pre_id = 0;                             // header ids of the tile BEHIND the one in pre[]
+        auto clamped = [&](uint64_t tile) { const uint64_t rr = tile * 64 + lane; return rr < r_last ? rr : r_last; };
+        auto request_ids = [&](uint64_t tile) { if (ids) pre_id = R.header_id[clamped(tile)]; };
+        auto request = [&](uint64_t tile, uint64_t id) {
+            const uint64_t rc = clamped(tile);
+            const uint32_t *gp = R.packed + rc * (uint64_t)W;
 #pragma unroll
-                for (int i = 0; i < (W > 0 ? W : 1); i++) pre[i] = gp[i];
-            }
-        }
-    };
-    prefetch(wave_global);
-    for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
-        const uint64_t r = tile * 64 + lane;
-        bool flag = false;
-        uint32_t cur[W > 0 ? W : 1];
-        if (W > 0) {
+            for (int i = 0; i < W; i++) pre[i] = gp[i];
+            pre_found = found_flag[ids ? id : rc];
+            if (!R.uniform_len) pre_len = R.lengths[rc];
+            if (!K.with_exc) pre_exc = R.exc_mask[rc >> 5];
+        };
+        request_ids(wave0);
+        const uint64_t id0 = pre_id;
+        request_ids(wave0 + wave_step);
+        request(wave0, id0);                             // (with header ids the one dependent round trip of a wave's life)
+        uint64_t m_done = 0, tile_done = 0;
+        bool have_done = false;
+        for (uint64_t tile = wave0; tile < n_tiles; tile += wave_step) {
+            const uint64_t r = tile * 64 + lane;
+            uint32_t w[W + 1];
 #pragma unroll
-            for (int i = 0; i < (W > 0 ? W : 1); i++) cur[i] = pre[i];
-            prefetch(tile + wave_total);
-        }
-        // with_exc: every pattern is pure ACGT, so an occurrence in an exception read lies in a stretch whose packed
-        // codes are the real bases — the probe stays a superset filter; the verification checks the bytes
-        if (r < R.n_reads && (K.with_exc || !rd_is_exc(R, r)) && !found_flag[rd_header_id(R, r)]) {
-            const uint32_t L = rd_len(R, r);
-            const uint32_t *g = R.packed + rd_word_off(R, r);
-            if (L >= (uint32_t)KL) {
+            for (int i = 0; i < W; i++) w[i] = pre[i];
+            w[W] = 0;
+            const uint32_t found = pre_found, L = R.uniform_len ? R.uniform_len : pre_len, excw = pre_exc;
+            const uint64_t id_next = pre_id;
+            request(tile + wave_step, id_next);
+            request_ids(tile + 2 * wave_step);
+            if (have_done && lane == 0) hitmask[tile_done] = m_done;
+            bool flag = false;
+            // with_exc: every pattern is pure ACGT, so an occurrence in an exception read lies in a stretch whose packed
+            // codes are the real bases — the probe stays a superset filter; the verification checks the bytes
+            if (r < R.n_reads && (K.with_exc || !((excw >> (r & 31)) & 1u)) && !found && L >= (uint32_t)KL) {
                 const uint32_t h_max = (L - (uint32_t)KL) >> ASH;          // last window position (halfword, or byte) whose 16-mer is inside the read
-                if (W > 0) {
-                    uint32_t w[W + 1];
+                if (MODE == 4) {
+                    // Bloom filter in LDS, exact keys in global memory.  ~7 % of the windows pass the Bloom filter, i.e.
+                    // in nearly every one of the 2W-1 unrolled windows SOME lane of the wave does, and a conditional
+                    // pair of global loads per window made the wave wait for 19 round trips.  So: all Bloom tests
+                    // first (LDS only, a bit per window), then every lane resolves ITS positives one per round —
+                    // the wave needs as many rounds as its busiest lane has positives (4-5).
+                    typedef typename std::conditional<ASH == 3, uint32_t, uint64_t>::type pm_t;      // (up to 61 windows every 4 bases)
+                    pm_t pm = 0;
 #pragma unroll
-                    for (int i = 0; i < W; i++) w[i] = cur[i];
-                    w[W] = 0;
-                    if (MODE == 4) {
-                        // Bloom filter in LDS, exact keys in global memory.  ~7 % of the windows pass the Bloom filter, i.e.
-                        // in nearly every one of the 2W-1 unrolled windows SOME lane of the wave does, and a conditional
-                        // pair of global loads per window made the wave wait for 19 round trips.  So: all Bloom tests
-                        // first (LDS only, a bit per window), then every lane resolves ITS positives one per round —
-                        // the wave needs as many rounds as its busiest lane has positives (4-5).
-                        typedef typename std::conditional<ASH == 3, uint32_t, uint64_t>::type pm_t;      // (up to 61 windows every 4 bases)
-                        pm_t pm = 0;
+                    for (int h = 0; h < NWIN; h++) {
+                        const uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
+                        // (blocked Bloom: ONE hash, one LDS word, both bits from it; a shift by a register takes the register's low
+                        // five bits, so the two positions cost a shift each and the window's flag joins pm with one v_lshl_or)
+                        const uint32_t h1 = ak_hash(V, K.m1);
+                        const uint32_t wd = ak_lds[ak_bloom_word(h1)];
+                        const uint32_t bit = (wd >> ((h1 >> 12) & 31u)) & (wd >> ((h1 >> 7) & 31u)) & 1u;
+                        if ((uint32_t)h <= h_max) pm |= (pm_t)bit << h;
+                    }
+                    while (pm) {                                   // (divergent: lanes with fewer positives idle)
+                        const uint32_t h = (uint32_t)(ASH == 3 ? __ffs((int)(uint32_t)pm) : __ffsll((unsigned long long)pm)) - 1u;
+                        pm &= pm - 1u;
+                        const uint32_t kk = h / PW;
+                        uint32_t lo = 0, hi = 0;
+#pragma unroll
+                        for (int i = 0; i < W; i++) { lo = kk == (uint32_t)i ? w[i] : lo; hi = kk == (uint32_t)i ? w[i + 1] : hi; }
+                        const uint32_t V = cut(__builtin_amdgcn_alignbit(hi, lo, (h % PW) * WB));
+                        const uint32_t h1 = ak_hash(V, K.m1), h2 = ak_hash(V, K.m2);
+                        if ((K.table[h1 >> mask] == V) | (K.table[h2 >> mask] == V)) { flag = true; pm = 0; }
+                    }
+                } else {
+                    // Uniform read length: the last window hm is a scalar.  A read that needs all W words of its row has more
+                    // than 16 (W-1) bases, so windows up to HS lie inside it whatever its length and "inside the read" is a
+                    // scalar condition on the result, no vector compare; the few windows behind HS (two of 19 at 150 bases and
+                    // W = 10) are hashed and probed only where hm reaches them — a scalar branch each.  (A uniform length
+                    // shorter than that — a padded stride — masks the early windows and skips the late ones: still exact.)
+                    // Per-read lengths keep the vector mask.
+                    auto scan = [&](const uint32_t hm, auto uniform_c) {
+                        constexpr int HS = decltype(uniform_c)::value ? (int)((16u * (uint32_t)(W - 1) + 1u - (uint32_t)KL) >> ASH) : NWIN - 1;
 #pragma unroll
                         for (int h = 0; h < NWIN; h++) {
-                            const uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
-                            // (blocked Bloom: ONE hash, one LDS word, both bits from it; a shift by a register takes the register's low
-                            // five bits, so the two positions cost a shift each and the window's flag joins pm with one v_lshl_or)
-                            const uint32_t h1 = ak_hash(V, K.m1);
-                            const uint32_t wd = ak_lds[ak_bloom_word(h1)];
-                            const uint32_t bit = (wd >> ((h1 >> 12) & 31u)) & (wd >> ((h1 >> 7) & 31u)) & 1u;
-                            if ((uint32_t)h <= h_max) pm |= (pm_t)bit << h;
-                        }
-                        while (pm) {                                   // (divergent: lanes with fewer positives idle)
-                            const uint32_t h = (uint32_t)(ASH == 3 ? __ffs((int)(uint32_t)pm) : __ffsll((unsigned long long)pm)) - 1u;
-                            pm &= pm - 1u;
-                            const uint32_t kk = h / PW;
-                            uint32_t lo = 0, hi = 0;
-#pragma unroll
-                            for (int i = 0; i < W; i++) { lo = kk == (uint32_t)i ? w[i] : lo; hi = kk == (uint32_t)i ? w[i + 1] : hi; }
-                            const uint32_t V = cut(__builtin_amdgcn_alignbit(hi, lo, (h % PW) * WB));
-                            const uint32_t h1 = ak_hash(V, K.m1), h2 = ak_hash(V, K.m2);
-                            if ((K.table[h1 >> mask] == V) | (K.table[h2 >> mask] == V)) { flag = true; pm = 0; }
-                        }
-                    } else {
-                    // (uniform read length: the last window is a scalar, and "window inside the read" costs no vector compare)
-                    auto scan = [&](const uint32_t hm) {
-#pragma unroll
-                        for (int h = 0; h < NWIN; h++) {
-                            uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
-                            bool hit = anchor_probe_any<MODE>(ak_lds, V, K, mask);
-                            flag = flag | (hit & ((uint32_t)h <= hm));
+                            auto probe = [&]() {
+                                const uint32_t V = cut(__builtin_amdgcn_alignbit(w[h / (int)PW + 1], w[h / (int)PW], ((uint32_t)h % PW) * WB));
+                                return anchor_probe_any<MODE>(ak_lds, V, K, mask);
+                            };
+                            if (h > HS) { if ((uint32_t)h <= hm) flag = flag | probe(); }
+                            else flag = flag | (probe() & ((uint32_t)h <= hm));
                             // (16 LDS reads in flight are plenty; left alone the scheduler hoists all 4W-2 of them and, from
                             // W = 12, spills)
                             if ((h & 7) == 7) __builtin_amdgcn_sched_barrier(0);
                         }
                     };
-                    if (R.uniform_len) scan((R.uniform_len - (uint32_t)KL) >> ASH);
-                    else scan(h_max);
-                    }
-                } else {
-                    // (four words per round, requested together: one word per round was one dependent round trip per 16 bases — reads of
-                    // 300 .. 800 bases, lane per read, took twice the time of the register form per base)
-                    const uint32_t nw = (L + 15) >> 4;
-                    uint32_t lo = g[0];
-                    for (uint32_t h = 0; h <= h_max && !flag; h += 4u * PW) {
-                        const uint32_t wi = (h / PW) + 1;
-                        uint32_t x[4];
+                    if (R.uniform_len) scan((R.uniform_len - (uint32_t)KL) >> ASH, std::true_type{});
+                    else scan(h_max, std::false_type{});
+                }
+            }
+            m_done = __ballot(flag); tile_done = tile; have_done = true;
+        }
+        if (have_done && lane == 0) hitmask[tile_done] = m_done;
+        return;
+    }
+    // any stride, lane per read
+    for (uint64_t tile = wave_global; tile < n_tiles; tile += wave_total) {
+        const uint64_t r = tile * 64 + lane;
+        bool flag = false;
+        if (r < R.n_reads && (K.with_exc || !rd_is_exc(R, r)) && !found_flag[rd_header_id(R, r)]) {
+            const uint32_t L = rd_len(R, r);
+            const uint32_t *g = R.packed + rd_word_off(R, r);
+            if (L >= (uint32_t)KL) {
+                const uint32_t h_max = (L - (uint32_t)KL) >> ASH;          // last window position (halfword, or byte) whose 16-mer is inside the read
+                // (four words per round, requested together: one word per round was one dependent round trip per 16 bases — reads of
+                // 300 .. 800 bases, lane per read, took twice the time of the register form per base)
+                const uint32_t nw = (L + 15) >> 4;
+                uint32_t lo = g[0];
+                for (uint32_t h = 0; h <= h_max && !flag; h += 4u * PW) {
+                    const uint32_t wi = (h / PW) + 1;
+                    uint32_t x[4];
 #pragma unroll
-                        for (uint32_t q = 0; q < 4; q++) x[q] = wi + q < nw ? g[wi + q] : 0u;
+                    for (uint32_t q = 0; q < 4; q++) x[q] = wi + q < nw ? g[wi + q] : 0u;
 #pragma unroll
-                        for (uint32_t q = 0; q < 4; q++) {
+                    for (uint32_t q = 0; q < 4; q++) {
 #pragma unroll
-                            for (uint32_t i = 0; i < PW; i++)
-                                if (h + PW * q + i <= h_max && anchor_probe_any<MODE>(ak_lds, cut(__builtin_amdgcn_alignbit(x[q], lo, i * WB)), K, mask)) flag = true;
-                            lo = x[q];
-                        }
+                        for (uint32_t i = 0; i < PW; i++)
+                            if (h + PW * q + i <= h_max && anchor_probe_any<MODE>(ak_lds, cut(__builtin_amdgcn_alignbit(x[q], lo, i * WB)), K, mask)) flag = true;
+                        lo = x[q];
                     }
                 }
             }
@@ -418,7 +460,8 @@ static hipError_t with_row_words(uint32_t stride_words, F &&f)
     }
 }
 
-hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st)
+// max_blocks: 0, or a cap on the grid (CRASS_PROBE_BLOCKS: the tests make every wave walk several tiles of a small read set)
+hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st, uint32_t max_blocks)
 {
     if (R.n_reads == 0) return hipSuccess;
     if (!((M.akey_bases == 16u && (M.akey_shift == 3u || M.akey_shift == 2u)) || (M.akey_bases == 12u && M.akey_shift == 2u))) return hipErrorInvalidValue;
@@ -427,6 +470,7 @@ hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const 
     constexpr int T = 1024;
     uint64_t blocks = (n_tiles + (T / 64) - 1) / (T / 64);
     if (blocks > 256) blocks = 256;
+    if (max_blocks && blocks > max_blocks) blocks = max_blocks;
     return with_row_words(R.stride_words, [&](auto w) -> hipError_t {
         constexpr int W = decltype(w)::value;
 #define AKD_LAUNCH(AA, KK)                                                                                                \
@@ -441,7 +485,7 @@ hipError_t launch_anchor_filter_dev(const DevReads &R, const DevMerge &M, const 
     });
 }
 
-hipError_t launch_anchor_filter(const DevReads &R, const DevAnchors &K, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st)
+hipError_t launch_anchor_filter(const DevReads &R, const DevAnchors &K, const uint8_t *found_flag, uint64_t *hitmask, hipStream_t st, uint32_t max_blocks)
 {
     if (R.n_reads == 0) return hipSuccess;
     const size_t tbytes = (size_t)4 << K.log_size;
@@ -453,6 +497,7 @@ hipError_t launch_anchor_filter(const DevReads &R, const DevAnchors &K, const ui
     uint64_t blocks = (n_tiles + (T / 64) - 1) / (T / 64);
     const uint64_t cap = lds > 80 * 1024 ? 256 : (lds > 40 * 1024 ? 512 : 1024);
     if (blocks > cap) blocks = cap;
+    if (max_blocks && blocks > max_blocks) blocks = max_blocks;
     return with_row_words(R.stride_words, [&](auto w) -> hipError_t {
         constexpr int W = decltype(w)::value;
 #define AK_LAUNCH(MM)                                                                                                     \
