@@ -189,6 +189,7 @@ struct EnvSwitches {
     uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
     bool inflate_hbm_window = true;                  // CRASS_INFLATE_WINDOW=lds: k_bgzf_inflate decodes in the wave's LDS window, not in the output's own range (A/B switch, inflate.hip)
     uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
+    bool lane_find_serial = false;                   // CRASS_LANE_FIND_SERIAL=1: the A/B switch of the lane kernel's packed seed find (lane_find.h)
     uint32_t probe_blocks = 0;                       // tests: CRASS_PROBE_BLOCKS caps the grid of pass 2's anchor probe, so that a few thousand reads are several tiles per wave (0: off)
     void read()
     {
@@ -213,6 +214,7 @@ struct EnvSwitches {
         text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
         inflate_hbm_window = true; if (const char *e = getenv("CRASS_INFLATE_WINDOW")) inflate_hbm_window = strcmp(e, "lds") != 0;
         hid_hash_bits = 64; if (const char *e = getenv("CRASS_HID_TEST_HASH_BITS")) hid_hash_bits = (uint32_t)std::min(64, std::max(0, atoi(e)));
+        lane_find_serial = false; if (const char *e = getenv("CRASS_LANE_FIND_SERIAL")) lane_find_serial = atoi(e) != 0;
         probe_blocks = 0; if (const char *e = getenv("CRASS_PROBE_BLOCKS")) probe_blocks = (uint32_t)std::max(0, atoi(e));
         pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
     }
@@ -799,6 +801,7 @@ int crass_hip_create(const crass_params *p, int device, crass_hip_ctx **out)
     c->env.read();
     g_dev_cap.store(c->env.pool_cap_bytes, std::memory_order_relaxed);
     c->dp.debug_stop = c->env.surv_debug;
+    c->dp.find_serial = c->env.lane_find_serial ? 1u : 0u;
     if (c->env.stage_timing >= 0) c->timing_level = c->env.stage_timing;
     if (c->env.no_lookback) c->lb_on = false;                    // A/B switch: three-kernel compaction
     c->dr_stride = (p->highDRsize + 15u) & ~15u;
@@ -852,6 +855,7 @@ int crass_hip_reload_env(crass_hip_ctx *c)
     c->env.read();
     g_dev_cap.store(c->env.pool_cap_bytes, std::memory_order_relaxed);
     c->dp.debug_stop = c->env.surv_debug;
+    c->dp.find_serial = c->env.lane_find_serial ? 1u : 0u;
     if (c->env.stage_timing >= 0) c->timing_level = c->env.stage_timing;
     c->lb_on = !c->env.no_lookback;
     return CRASS_OK;

@@ -42,6 +42,8 @@ struct DevParams {
     uint32_t debug_stop;          // diagnostics only (env CRASS_SURV_DEBUG): 0 = normal; 1..3 cut the survivor kernel short
     uint32_t exc_survive;         // 1: the filter passes every exception read on (they join the survivor list and are
                                   // evaluated byte-wise in place, so the dense pass-1 path also holds with N reads)
+    uint32_t find_serial;         // A/B switch (env CRASS_LANE_FIND_SERIAL=1): the lane kernel's seed find one candidate at a time
+                                  // (ln_find_serial) instead of the packed form of lane_find.h
     unsigned long long *prof;     // diagnostics only (env CRASS_SURV_PROF): 192 counters of the wave kernel's phases, else nullptr
 };
 

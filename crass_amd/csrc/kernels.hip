@@ -15,6 +15,7 @@
 // qcFoundRepeats' float evaluation order is part of the parity contract.
 #include "dev_common.h"
 #include "comp_table.h"
+#include "lane_find.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -2586,11 +2587,14 @@ static __device__ __forceinline__ void ln_planes(uint64_t lo, uint64_t hi, int n
     p0 &= m; p1 &= m;
 }
 
-// bmpSearch semantics (PatternMatcher.cpp:26-59) for the w-mer at `pat` in [begin, end).  The text is pulled through a
-// 64-bit register, 32 bases per refill: no LDS access inside the compare loop (a per-base ln_base() there was one LDS
-// round trip per iteration).
-static __device__ int ln_find(const LaneRead &h, int begin, int end, int pat, int plen)
+// bmpSearch semantics (PatternMatcher.cpp:26-59) for the w-mer at `pat` in [begin, end), one candidate per iteration.  The
+// text is pulled through a 64-bit register, 32 bases per refill: no LDS access inside the compare loop (a per-base ln_base()
+// there was one LDS round trip per iteration).  The route of -w 9 (18 bits: no two codes per register) and of
+// CRASS_LANE_FIND_SERIAL=1, the A/B switch of the packed form below.
+static __device__ __noinline__ int ln_find_serial(const uint32_t *w, uint32_t cmask, int begin, int end, int pat, int plen)
 {
+    LaneRead h;
+    h.w = w; h.cmask = cmask;
     if (end - begin <= 0 || plen <= 0 || plen > end - begin) return -1;
     const uint32_t sj = ln_code(h, pat);
     uint32_t code = ln_code(h, begin);
@@ -2612,6 +2616,33 @@ static __device__ int ln_find(const LaneRead &h, int begin, int end, int pat, in
     }
 }
 
+// The same rule on packed registers (lane_find.h).  The text from `begin` on is brought into four words once
+// (ln_load128).  Every pair of candidates t, t + 8 is then one funnel shift at a STATIC amount, one xor-and-mask
+// against the duplicated code and two packed 16-bit operations that keep the first match: four instructions per two
+// candidates.  The loop above spends 26 per candidate, half of them exec-mask bookkeeping, and a wave runs it for
+// as long as its slowest lane, in practice the whole window.
+// The candidates are begin .. end - plen: the last one at p + plen <= end, the reference's off-by-one at a clipped
+// endSearch = L - 1 included.  A window beyond 64 - plen + 1 candidates (-s / -S / -D) takes several chunks under a
+// wave-uniform loop.  serial and plen are the same in every lane.
+static __device__ __forceinline__ int ln_find(const LaneRead &h, int begin, int end, int pat, int plen, uint32_t serial)
+{
+    if (serial || plen > 8) return ln_find_serial(h.w, h.cmask, begin, end, pat, plen);
+    int left = (end - begin <= 0 || plen <= 0 || plen > end - begin) ? 0 : end - plen - begin + 1;      // candidates not looked at yet
+    const uint32_t sj = ln_code(h, pat);
+    const int chunk = 64 - plen + 1;
+    int found = -1;
+    while (__any((int)(left > 0))) {
+        uint64_t lo, hi;
+        ln_load128(h, begin, lo, hi);
+        const int n = left < chunk ? left : chunk;
+        const int t = find_packed_steps(lo, hi, sj, plen, n, __any((int)(n > kLaneFindShortNpos)) != 0);
+        if (t >= 0) { found = begin + t; left = 0; }
+        else if (left > chunk) { left -= chunk; begin += chunk; }
+        else left = 0;
+    }
+    return found;
+}
+
 static __device__ void ln_add(LaneRead &h, uint32_t i, uint32_t j)          // startStopsAdd, ReadHolder.cpp:263-297
 {
     if (h.nss + 2 > h.cap) { h.punt = 1; return; }
@@ -2620,7 +2651,7 @@ static __device__ void ln_add(LaneRead &h, uint32_t i, uint32_t j)          // s
     h.nss += 2;
 }
 
-static __device__ void ln_scan_right(LaneRead &h, int pat, uint32_t pattern_length, uint32_t minSpacerLength, uint32_t scanRange)
+static __device__ void ln_scan_right(LaneRead &h, int pat, uint32_t pattern_length, uint32_t minSpacerLength, uint32_t scanRange, uint32_t find_serial)
 {   // scanRight, libcrispr.cpp:170-263
     uint32_t last_repeat_index = ln_ss(h, h.nss - 2);
     uint32_t second_last_repeat_index = ln_ss(h, h.nss - 4);
@@ -2635,7 +2666,7 @@ static __device__ void ln_scan_right(LaneRead &h, int pat, uint32_t pattern_leng
         if (begin_search > read_length - 1) return;
         if (end_search > read_length) end_search = read_length;
         if (begin_search >= end_search) return;
-        int position = ln_find(h, (int)begin_search, (int)end_search, pat, (int)pattern_length);
+        int position = ln_find(h, (int)begin_search, (int)end_search, pat, (int)pattern_length, find_serial);
         if (position < 0) return;
         ln_add(h, (uint32_t)position, (uint32_t)position + pattern_length - 1);
         if (h.punt) return;
@@ -2855,32 +2886,18 @@ static __device__ int ln_distance(LaneRead &h, int s0, int n, int t0, int m, int
     return (n <= 32) ? ln_lev_core<uint32_t>(h, s0, n, t0, m) : ln_lev_core<uint64_t>(h, s0, n, t0, m);
 }
 
-// getStringSimilarity (PatternMatcher.cpp:197-204); sets h.punt when the pair needs the wavefront DP
-static __device__ float ln_similarity(LaneRead &h, int s0, int n, int t0, int m)
+// qcFoundRepeats, libcrispr.cpp:869-1029, in the lane.  Its similarity tests — getStringSimilarity (PatternMatcher.cpp:197-204)
+// as a value or as "(double)similarity > 0.82" — are ONE site in one loop (ln_distance's three loops exist once here, not once
+// per test of the source): which pair comes next, and what becomes of the result, is chosen around it.
+//   two repeats      one threshold test: repeat vs spacer
+//   three repeats    two threshold tests: spacer vs spacer, repeat vs spacer.  ONE comparison, so every average is the single
+//                    value itself (x / 1.0f == x) and the tests are plain threshold tests
+//   four and more    per spacer but the last: repeat vs spacer and spacer vs next spacer as values, averaged
+// A threshold test may stop early: the similarity falls monotonically with the distance, so the smallest distance d_no whose
+// similarity is NOT above the cut is found first (with the reference's own float expression) and the DP stops as soon as the
+// distance is known to reach it (ln_lev_regs).  A pair that needs the wavefront DP sets h.punt, and every path then returns 0.
+static __device__ __forceinline__ int ln_qc(LaneRead &h, int minSpacerLength, int maxSpacerLength, uint32_t dbg)
 {
-    float max_length = (float)(n > m ? n : m);
-    if (n < 3 || m < 3) return 0.0f;
-    const int d = ln_distance(h, s0, n, t0, m, -1);
-    float edit_distance = (float)d;
-    return (float)(1.0 - (double)(edit_distance / max_length));
-}
-
-// "(double)getStringSimilarity(a, b) > cut" without the full distance when the answer is no: the similarity falls
-// monotonically with the distance, so the smallest distance d_no whose similarity is NOT above the cut is found first
-// (with the reference's own float expression) and the DP stops as soon as the distance is known to reach it
-static __device__ bool ln_similarity_above(LaneRead &h, int s0, int n, int t0, int m, double cut)
-{
-    if (n < 3 || m < 3) return 0.0 > cut;
-    const float max_length = (float)(n > m ? n : m);
-    int d_no = 0;
-    while (d_no <= (n > m ? n : m) && (double)(float)(1.0 - (double)((float)d_no / max_length)) > cut) d_no++;
-    const int d = ln_distance(h, s0, n, t0, m, d_no);
-    if (h.punt) return false;
-    return (double)(float)(1.0 - (double)((float)d / max_length)) > cut;
-}
-
-static __device__ int ln_qc(LaneRead &h, int minSpacerLength, int maxSpacerLength, uint32_t dbg = 0)
-{   // qcFoundRepeats, libcrispr.cpp:869-1029
     if (dbg == 6) return 1;                             // (CRASS_SURV_DEBUG, timing breakdown only)
     const int num_repeats = h.nss / 2;
     if (num_repeats < 2) return -1;
@@ -2900,75 +2917,90 @@ static __device__ int ln_qc(LaneRead &h, int minSpacerLength, int maxSpacerLengt
         if (c0 > cut_off || c3 > cut_off || c2 > cut_off || c1 > cut_off) return 0;
     }
     if (dbg == 5) return 1;
-    bool is_short = (2 > (num_repeats - 1));
-    if (!is_short) {
-        float ave_spacer_to_spacer_len_difference = 0.0f, ave_repeat_to_spacer_len_difference = 0.0f;
-        float ave_spacer_to_spacer_difference = 0.0f, ave_repeat_to_spacer_difference = 0.0f;
-        int min_spacer_length = 10000000, max_spacer_length = 0, num_compared = 0;
-        const int nsp = num_repeats - 1;
-        uint32_t cur_start = ln_ss(h, 1) + 1, cur_len;
+    const int nsp = num_repeats - 1;
+    const int mode = nsp < 2 ? 0 : (nsp == 2 ? 1 : 2);       // two repeats / three / four and more
+    float ave_spacer_to_spacer_len_difference = 0.0f, ave_repeat_to_spacer_len_difference = 0.0f;
+    float ave_spacer_to_spacer_difference = 0.0f, ave_repeat_to_spacer_difference = 0.0f;
+    int min_spacer_length = 10000000, max_spacer_length = 0, num_compared = 0;
+    uint32_t cur_start = ln_ss(h, 1) + 1, cur_len = 0, nxt_start = 0, nxt_len = 0;
+    if (mode == 0) {
+        const uint32_t e = ln_ss(h, 2) - 1;
+        if (!substr_len(h.L, cur_start, e - cur_start, cur_len)) return -1;
+        if ((int)cur_len < minSpacerLength) return 0;
+        if ((int)cur_len > maxSpacerLength) return 0;
+    } else {
         if (!substr_len(h.L, cur_start, ln_ss(h, 2) - cur_start, cur_len)) return -1;
-        if (nsp == 2) {
-            // three repeats, ONE comparison: every average is the single value itself (x / 1.0f == x), so the two similarity
-            // tests are plain threshold tests and may stop early (ln_similarity_above); the outcome is a boolean either way
-            uint32_t nxt_start = ln_ss(h, 3) + 1, nxt_len;
+        if (mode == 1) {
+            nxt_start = ln_ss(h, 3) + 1;
             if (!substr_len(h.L, nxt_start, ln_ss(h, 4) - nxt_start, nxt_len)) return -1;
             const int mn = (int)(cur_len < nxt_len ? cur_len : nxt_len), mx = (int)(cur_len > nxt_len ? cur_len : nxt_len);
             if (mn < minSpacerLength || mx > maxSpacerLength) return 0;
-            const bool a = ln_similarity_above(h, (int)cur_start, (int)cur_len, (int)nxt_start, (int)nxt_len, 0.82);
-            if (h.punt) return 0;
-            if (a) return 0;
-            const bool b = ln_similarity_above(h, (int)rep_start, (int)rep_len, (int)cur_start, (int)cur_len, 0.82);
-            if (h.punt) return 0;
-            if (b) return 0;
-            if ((int)fabsf(((float)cur_len - (float)nxt_len) / 1.0f) > 12) return 0;
-            if ((int)fabsf(((float)rep_len - (float)cur_len) / 1.0f) > 30) return 0;
-            return 1;
         }
-        for (int i = 0; i < nsp; i++) {
-            if ((int)cur_len < min_spacer_length) min_spacer_length = (int)cur_len;
-            if ((int)cur_len > max_spacer_length) max_spacer_length = (int)cur_len;
-            if (i + 1 < nsp) {
-                uint32_t nxt_start = ln_ss(h, 2 * i + 3) + 1, nxt_len;
-                if (!substr_len(h.L, nxt_start, ln_ss(h, 2 * i + 4) - nxt_start, nxt_len)) return -1;
-                num_compared++;
-                ave_repeat_to_spacer_difference += ln_similarity(h, (int)rep_start, (int)rep_len, (int)cur_start, (int)cur_len);
-                float ss_diff = 0;
-                ss_diff += ln_similarity(h, (int)cur_start, (int)cur_len, (int)nxt_start, (int)nxt_len);
-                ave_spacer_to_spacer_difference += ss_diff;
-                ave_spacer_to_spacer_len_difference += ((float)cur_len - (float)nxt_len);
-                ave_repeat_to_spacer_len_difference += ((float)rep_len - (float)cur_len);
-                cur_start = nxt_start; cur_len = nxt_len;
-                if (h.punt) return 0;
-            }
-        }
-        ave_spacer_to_spacer_difference /= (float)num_compared;
-        ave_repeat_to_spacer_difference /= (float)num_compared;
-        ave_spacer_to_spacer_len_difference /= (float)num_compared;
-        ave_spacer_to_spacer_len_difference = fabsf(ave_spacer_to_spacer_len_difference);
-        ave_repeat_to_spacer_len_difference /= (float)num_compared;
-        ave_repeat_to_spacer_len_difference = fabsf(ave_repeat_to_spacer_len_difference);
-        if (min_spacer_length < minSpacerLength) return 0;
-        if (max_spacer_length > maxSpacerLength) return 0;
-        if ((double)ave_spacer_to_spacer_difference > 0.82) return 0;
-        if ((double)ave_repeat_to_spacer_difference > 0.82) return 0;
-        if ((int)ave_spacer_to_spacer_len_difference > 12) return 0;
-        if ((int)ave_repeat_to_spacer_len_difference > 30) return 0;
     }
-    if (is_short) {
-        uint32_t s = ln_ss(h, 1) + 1;
-        uint32_t e = ln_ss(h, 2) - 1;
-        uint32_t sp_len;
-        if (!substr_len(h.L, s, e - s, sp_len)) return -1;
-        if ((int)sp_len < minSpacerLength) return 0;
-        if ((int)sp_len > maxSpacerLength) return 0;
-        const bool too_similar = ln_similarity_above(h, (int)rep_start, (int)rep_len, (int)s, (int)sp_len, 0.82);
-        if (h.punt) return 0;
-        if (too_similar) return 0;
-        int dlen = (int)sp_len - (int)rep_len;
+    const int n_tests = mode == 0 ? 1 : (mode == 1 ? 2 : 2 * (nsp - 1));
+    for (int k = 0; k < n_tests; k++) {
+        bool rep_vs_cur;                                 // this test's pair: repeat vs current spacer, else current vs next spacer
+        if (mode == 2) {
+            rep_vs_cur = !(k & 1);
+            if (rep_vs_cur) {                            // spacer k / 2 of the loop at :935-975
+                if ((int)cur_len < min_spacer_length) min_spacer_length = (int)cur_len;
+                if ((int)cur_len > max_spacer_length) max_spacer_length = (int)cur_len;
+                nxt_start = ln_ss(h, k + 3) + 1;
+                if (!substr_len(h.L, nxt_start, ln_ss(h, k + 4) - nxt_start, nxt_len)) return -1;
+                num_compared++;
+            }
+        } else rep_vs_cur = mode == 0 || k == 1;
+        const int s0 = rep_vs_cur ? (int)rep_start : (int)cur_start, n = rep_vs_cur ? (int)rep_len : (int)cur_len;
+        const int t0 = rep_vs_cur ? (int)cur_start : (int)nxt_start, m = rep_vs_cur ? (int)cur_len : (int)nxt_len;
+        float sim = 0.0f;                                // a string below three bases: similarity 0
+        if (!(n < 3 || m < 3)) {
+            const float max_length = (float)(n > m ? n : m);
+            int stop_at = -1;
+            if (mode != 2) {
+                stop_at = 0;
+                while (stop_at <= (n > m ? n : m) && (double)(float)(1.0 - (double)((float)stop_at / max_length)) > 0.82) stop_at++;
+            }
+            const int d = ln_distance(h, s0, n, t0, m, stop_at);
+            if (h.punt) return 0;
+            sim = (float)(1.0 - (double)((float)d / max_length));
+        }
+        if (mode != 2) {
+            if ((double)sim > 0.82) return 0;
+        } else if (rep_vs_cur) ave_repeat_to_spacer_difference += sim;
+        else {
+            float ss_diff = 0;
+            ss_diff += sim;
+            ave_spacer_to_spacer_difference += ss_diff;
+            ave_spacer_to_spacer_len_difference += ((float)cur_len - (float)nxt_len);
+            ave_repeat_to_spacer_len_difference += ((float)rep_len - (float)cur_len);
+            cur_start = nxt_start; cur_len = nxt_len;
+        }
+    }
+    if (mode == 0) {
+        int dlen = (int)cur_len - (int)rep_len;
         if (dlen < 0) dlen = -dlen;
         if (dlen > 30) return 0;
+        return 1;
     }
+    if (mode == 1) {
+        if ((int)fabsf(((float)cur_len - (float)nxt_len) / 1.0f) > 12) return 0;
+        if ((int)fabsf(((float)rep_len - (float)cur_len) / 1.0f) > 30) return 0;
+        return 1;
+    }
+    if ((int)cur_len < min_spacer_length) min_spacer_length = (int)cur_len;       // the last spacer
+    if ((int)cur_len > max_spacer_length) max_spacer_length = (int)cur_len;
+    ave_spacer_to_spacer_difference /= (float)num_compared;
+    ave_repeat_to_spacer_difference /= (float)num_compared;
+    ave_spacer_to_spacer_len_difference /= (float)num_compared;
+    ave_spacer_to_spacer_len_difference = fabsf(ave_spacer_to_spacer_len_difference);
+    ave_repeat_to_spacer_len_difference /= (float)num_compared;
+    ave_repeat_to_spacer_len_difference = fabsf(ave_repeat_to_spacer_len_difference);
+    if (min_spacer_length < minSpacerLength) return 0;
+    if (max_spacer_length > maxSpacerLength) return 0;
+    if ((double)ave_spacer_to_spacer_difference > 0.82) return 0;
+    if ((double)ave_repeat_to_spacer_difference > 0.82) return 0;
+    if ((int)ave_spacer_to_spacer_len_difference > 12) return 0;
+    if ((int)ave_repeat_to_spacer_len_difference > 30) return 0;
     return 1;
 }
 
@@ -3029,17 +3061,17 @@ static __device__ __forceinline__ void qc_run_task(const QcPool &q, uint32_t slo
 }
 
 // qcFoundRepeats (libcrispr.cpp:869-1029) up to its similarity tests: -1 / 0 / 1 = decided here (ln_qc's values); 2 = the
-// candidate's tests are queued (pd says which), qc_pool_end decides.  Candidates of four repeats or more, and strings beyond
-// 64 bases, take ln_qc as before (rare at these read lengths).
-static __device__ int qc_pool_begin(LaneRead &h, int minSpacerLength, int maxSpacerLength, uint32_t dbg, const QcPool &q, QcPending &pd)
+// candidate's tests are queued (pd says which), qc_pool_end decides; 3 = candidates of four repeats or more, and strings beyond
+// 64 bases: ln_qc as before (rare at these read lengths), from qc_pool_begin's ONE call of it.
+static __device__ __forceinline__ int qc_pool_begin_queued(LaneRead &h, int minSpacerLength, int maxSpacerLength, uint32_t dbg, const QcPool &q, QcPending &pd)
 {
     pd.kind = 0;
     const int num_repeats = h.nss / 2;
-    if (dbg == 5 || dbg == 6 || num_repeats < 2 || num_repeats > 3) return ln_qc(h, minSpacerLength, maxSpacerLength, dbg);
+    if (dbg == 5 || dbg == 6 || num_repeats < 2 || num_repeats > 3) return 3;
     uint32_t rep_len;
     const uint32_t rep_start = ln_ss(h, 0);
     if (!substr_len(h.L, rep_start, ln_ss(h, 1) - rep_start + 1, rep_len)) return -1;
-    if (rep_len > 64) return ln_qc(h, minSpacerLength, maxSpacerLength, dbg);
+    if (rep_len > 64) return 3;
     {   // isRepeatLowComplexity (:1031-1069); packed reads hold A/C/G/T only
         uint64_t lo, hi, p0, p1;
         ln_load128(h, (int)rep_start, lo, hi);
@@ -3055,7 +3087,7 @@ static __device__ int qc_pool_begin(LaneRead &h, int minSpacerLength, int maxSpa
         if (!substr_len(h.L, nxt_start, ln_ss(h, 4) - nxt_start, nxt_len)) return -1;
         const int mn = (int)(cur_len < nxt_len ? cur_len : nxt_len), mx = (int)(cur_len > nxt_len ? cur_len : nxt_len);
         if (mn < minSpacerLength || mx > maxSpacerLength) return 0;
-        if (cur_len > 64 || nxt_len > 64) return ln_qc(h, minSpacerLength, maxSpacerLength, dbg);
+        if (cur_len > 64 || nxt_len > 64) return 3;
         bool a_now, b_now;
         pd.slot_a = qc_enqueue_above(q, (int)cur_start, (int)cur_len, (int)nxt_start, (int)nxt_len, &a_now);
         if (pd.slot_a == 0xFFFFFFFFu && a_now) return 0;
@@ -3071,13 +3103,19 @@ static __device__ int qc_pool_begin(LaneRead &h, int minSpacerLength, int maxSpa
     if (!substr_len(h.L, s, e - s, sp_len)) return -1;
     if ((int)sp_len < minSpacerLength) return 0;
     if ((int)sp_len > maxSpacerLength) return 0;
-    if (sp_len > 64) return ln_qc(h, minSpacerLength, maxSpacerLength, dbg);
+    if (sp_len > 64) return 3;
     bool now;
     pd.slot_a = qc_enqueue_above(q, (int)rep_start, (int)rep_len, (int)s, (int)sp_len, &now);
     if (pd.slot_a == 0xFFFFFFFFu && now) return 0;
     pd.slot_b = 0xFFFFFFFFu;
     pd.kind = 2; pd.sp_len = sp_len; pd.rep_len = rep_len;
     return 2;
+}
+static __device__ __forceinline__ int qc_pool_begin(LaneRead &h, int minSpacerLength, int maxSpacerLength, uint32_t dbg, const QcPool &q, QcPending &pd)
+{
+    const int r = qc_pool_begin_queued(h, minSpacerLength, maxSpacerLength, dbg, q, pd);
+    if (__builtin_expect(r == 3, 0)) return ln_qc(h, minSpacerLength, maxSpacerLength, dbg);
+    return r;
 }
 // ... and from the tests' results on (same values as ln_qc)
 static __device__ int qc_pool_end(const QcPool &q, const QcPending &pd)
@@ -3131,12 +3169,12 @@ static __device__ int ln_search_core(LaneRead &h, const DevParams &o, uint64_t s
             if (endSearch >= seq_length) endSearch = seq_length - 1;
             if (endSearch < beginSearch) endSearch = beginSearch;
             if (beginSearch > seq_length) { error = true; continue; }
-            int pos = ln_find(h, (int)beginSearch, (int)endSearch, (int)j, (int)o.window);
+            int pos = ln_find(h, (int)beginSearch, (int)endSearch, (int)j, (int)o.window, o.find_serial);
             if (o.debug_stop == 2) pos = -1;                // (CRASS_SURV_DEBUG, timing breakdown only: seed finds alone)
             if (pos >= 0) {
                 ln_add(h, j, j + o.window - 1);
                 ln_add(h, (uint32_t)pos, (uint32_t)pos + o.window - 1);
-                if (!h.punt) ln_scan_right(h, (int)j, o.window, o.lowSp, 24);
+                if (!h.punt) ln_scan_right(h, (int)j, o.window, o.lowSp, 24, o.find_serial);
                 if (h.punt) { finished = true; result = 0; continue; }
             }
             if ((uint32_t)(h.nss / 2) >= o.minRepeats) {
