@@ -108,6 +108,10 @@ class GzipPlanC(C.Structure):
     _fields_ = [("n_chunks", C.c_uint64), ("n_chain", C.c_uint64), ("start_bit", u64p), ("link", C.POINTER(C.c_uint32)), ("text_len", u64p)]
 
 
+class GzipMembersC(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("in_off", u64p), ("text_off", u64p)]
+
+
 class Fastx(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("seq", u8p), ("seq_off", u64p), ("name", u8p), ("name_off", u64p),
                 ("comment", u8p), ("comment_off", u64p), ("has_comment", u8p), ("qual", u8p), ("qual_off", u64p),
@@ -211,6 +215,13 @@ SYMBOLS = {
                                                 C.POINTER(GzipPlanC), C.POINTER(BgzfVerdict)]),
     "crass_hip_load_fastx_gzip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(FastxLayoutC),
                                             C.POINTER(BgzfVerdict)]),
+    "crass_gzip_members_free": (None, [C.POINTER(GzipMembersC)]),
+    "crass_gzip_inflate_members_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(GzipPlanC), C.POINTER(GzipMembersC), C.POINTER(BgzfVerdict)]),
+    "crass_hip_inflate_gzip_members_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                        C.POINTER(GzipPlanC), C.POINTER(GzipMembersC), C.POINTER(BgzfVerdict)]),
+    "crass_hip_load_fastx_gzip_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                    C.POINTER(FastxLayoutC), C.POINTER(GzipMembersC), C.POINTER(BgzfVerdict)]),
     "crass_hip_set_gzip_on_device": (C.c_int, [C.c_void_p, C.c_int]),
     "crass_hip_last_gzip_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "crass_fastx_files_scan_host": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.POINTER(FastxFilesLayoutC)]),

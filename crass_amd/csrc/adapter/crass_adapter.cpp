@@ -616,7 +616,7 @@ std::string decline_message(const Vecstr &files, const crass_fastx_files_layout 
                                      "a distance beyond the member's text", "the deflate data ends early", "more text than the member's trailer says",
                                      "less text than the member's trailer says", "a member's CRC-32 does not match", "gzip, but not BGZF (plain gzip stays with the host readers)",
                                      "not a gzip header, or a header that runs into the trailer", "no deflate block start within the span of a chunk",
-                                     "the gzip member ends before the file does (further members, trailing bytes)", "a distance that reaches in front of the text"};
+                                     "the gzip member ends before the file does (further members, trailing bytes)", "a distance that reaches in front of the text or of its member"};
     const std::string name = lay.decline_file >= 0 && (size_t)lay.decline_file < files.size() ? files[(size_t)lay.decline_file] : std::string("?");
     std::string m = "crass [ERROR]: CRASS_INGEST=device cannot take " + name + ": ";
     if (lay.bgzf.reason) {
@@ -824,8 +824,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     memset(&lay, 0, sizeof(lay));
     if (device_ingest) {
         // as soon as the context is up; a declined input is an error, as with a forced CRASS_INGEST=index
-        // CRASS_DEVICE_GZIP=1: a plain gzip input is inflated on the device too (gunzip.hip); without it such an input is declined
-        if (const char *e = getenv("CRASS_DEVICE_GZIP")) chk(crass_hip_set_gzip_on_device(made.c, atoi(e) != 0), "crass_hip_set_gzip_on_device");
+        // CRASS_DEVICE_GZIP=1: a plain gzip input is inflated on the device too (gunzip.hip); without it such an input is declined.
+        // The value goes through as it is: 2 takes plain gzip of any number of members (CRASS_GZIP_ON_DEVICE_MEMBERS)
+        if (const char *e = getenv("CRASS_DEVICE_GZIP")) chk(crass_hip_set_gzip_on_device(made.c, atoi(e)), "crass_hip_set_gzip_on_device");
         const int s = crass_hip_load_fastx_files(made.c, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, &lay);
         if (s == CRASS_ERR_UNSUPPORTED && lay.decline_file >= 0) throw input_error(decline_message(seqFiles, lay));
         chk(s, "crass_hip_load_fastx_files");

@@ -287,9 +287,10 @@ struct crass_hip_ctx {
     // (count step); per chain element start / end_bit of all chunks + the elements' offsets and chain / CRC parts, the text as
     // 16-bit symbols and the 32 KB windows (decode step) — all given back before the call returns
     DevBuf<uint64_t> gz_a64, gz_b64; DevBuf<uint32_t> gz_a32, gz_b32; DevBuf<uint16_t> gz_sym; DevBuf<uint8_t> gz_win;
+    DevBuf<uint64_t> gz_ends;                // members mode: the GzEnd records (3 words each)
     hipEvent_t ev_gz_time[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float last_gzip_ms[5] = {0, 0, 0, 0, 0};  // find, count, decode, windows, narrow of the last gzip inflate (stage timing >= 1, else 0)
-    bool gzip_on_device = false;             // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip
+    int gzip_on_device = 0;                  // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip (CRASS_GZIP_ON_DEVICE_*)
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
     // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
     // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
@@ -921,7 +922,7 @@ void crass_hip_destroy(crass_hip_ctx *c)
     for (auto &e : c->ev_x_time) if (e) (void)hipEventDestroy(e);
     c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release(); c->z_h_verdict.release();
     for (auto &e : c->ev_z_time) if (e) (void)hipEventDestroy(e);
-    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release();
+    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release(); c->gz_ends.release();
     for (auto &e : c->ev_gz_time) if (e) (void)hipEventDestroy(e);
     c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
     c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
@@ -1633,19 +1634,26 @@ struct GzState {
     std::vector<uint32_t> link, chain;
     std::vector<int32_t> reason;
     uint64_t n_chain = 0, n_text = 0;
+    // members mode (gunzip_core.h): what count reported about member ends, and after the decode step the member table
+    bool members = false;
+    uint64_t n_file = 0;
+    std::vector<uint32_t> n_ends;
+    std::vector<uint64_t> last_end, in_off, text_off;
 };
 }
 
 static void gzip_release(crass_hip_ctx *c)
 {
     (void)hipStreamSynchronize(c->stream);
-    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release();
+    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release(); c->gz_ends.release();
 }
 
 // header and trailer (host), find and count (device), the chain (host): CRASS_OK with S.n_text known, or the decline
+// (members: the rule's members mode, kept in S for the decode step)
 static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, GzState &S, crass_gzip_plan *plan,
-                           crass_bgzf_verdict *v)
+                           crass_bgzf_verdict *v, bool members = false)
 {
+    S.members = members; S.n_file = n_in;
     c->last_inflate_ms = 0;
     for (auto &m : c->last_gzip_ms) m = 0;
     auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
@@ -1667,19 +1675,20 @@ static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in,
         if (why != BZ_OK) return decline(BZ_NOT_GZIP, 0, 0);
         const GzGeom &G = S.M.G;
         const uint64_t nc = G.nc;
-        HIPCHK(c, c->gz_a64.ensure(3 * nc)); HIPCHK(c, c->gz_a32.ensure(2 * nc));
+        HIPCHK(c, c->gz_a64.ensure((members ? 4 : 3) * nc)); HIPCHK(c, c->gz_a32.ensure((members ? 3 : 2) * nc));
         GzJob J{};
         J.d = d_in + G.d_off; J.G = G;
         J.start = c->gz_a64.p; J.text_len = c->gz_a64.p + nc; J.end_bit = c->gz_a64.p + 2 * nc;
         J.link = c->gz_a32.p; J.reason = reinterpret_cast<int32_t *>(c->gz_a32.p + nc);
+        if (members) { J.last_end = c->gz_a64.p + 3 * nc; J.n_ends = c->gz_a32.p + 2 * nc; }
         const bool timed = c->timing_level >= 1;
         if (timed) {
             for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
             HIPCHK(c, hipEventRecord(c->ev_gz_time[0], c->stream));
         }
-        HIPCHK(c, launch_gz_find(J, c->stream));
+        HIPCHK(c, launch_gz_find(J, c->stream, members));
         if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[1], c->stream));
-        HIPCHK(c, launch_gz_count(J, c->stream));         // (a launch of its own: every start is final before a chunk counts)
+        HIPCHK(c, launch_gz_count(J, c->stream, members));      // (a launch of its own: every start is final before a chunk counts)
         if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
         S.start.resize(nc); S.text_len.resize(nc); S.end_bit.resize(nc); S.link.resize(nc); S.reason.resize(nc); S.chain.assign(nc, 0);
         HIPCHK(c, hipMemcpyAsync(S.start.data(), J.start, nc * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1687,6 +1696,11 @@ static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in,
         HIPCHK(c, hipMemcpyAsync(S.end_bit.data(), J.end_bit, nc * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(S.link.data(), J.link, nc * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(S.reason.data(), J.reason, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        if (members) {
+            S.n_ends.resize(nc); S.last_end.resize(nc);
+            HIPCHK(c, hipMemcpyAsync(S.n_ends.data(), J.n_ends, nc * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(S.last_end.data(), J.last_end, nc * 8, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (timed) {
             HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[0], c->ev_gz_time[0], c->ev_gz_time[1]));
@@ -1695,7 +1709,7 @@ static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in,
         }
         GzVerdict gv{};
         const int32_t bad = gz_chain(S.M, S.start.data(), S.link.data(), S.text_len.data(), S.end_bit.data(), S.reason.data(), S.chain.data(),
-                                     &S.n_chain, &S.n_text, &gv);
+                                     &S.n_chain, &S.n_text, &gv, members);
         const int ps = gz_plan_fill(plan, nc, S.start.data(), S.link.data(), S.text_len.data(), S.n_chain);
         if (ps) return ps;
         if (bad != BZ_OK) return decline(gv.reason, gv.member, gv.in_pos);
@@ -1704,8 +1718,10 @@ static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in,
 }
 
 // decode, windows, narrow: the text of an accepted count into d_out[0, S.n_text)
-static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState &S, uint8_t *d_out, crass_bgzf_verdict *v)
+// (members mode: every member's ISIZE and CRC-32 are checked here, behind the kernels; S gets the member table)
+static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, GzState &S, uint8_t *d_out, crass_bgzf_verdict *v)
 {
+    const bool members = S.members;
     auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
         if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
         return CRASS_ERR_UNSUPPORTED;
@@ -1716,7 +1732,16 @@ static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState
         std::vector<uint64_t> off(n + 1, 0);
         for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + S.text_len[S.chain[i]];
         std::vector<uint32_t> crc_part(n, 0);
-        HIPCHK(c, c->gz_b64.ensure(2 * nc + n + 1)); HIPCHK(c, c->gz_b32.ensure(2 * n));
+        // members mode: [slot (n + 1) | m0 (n)] go up behind off; the pieces' bounds follow once the member table is known
+        std::vector<uint64_t> places(2 * n + 1, 0);
+        if (members) {
+            std::vector<uint64_t> off2(n + 1, 0);
+            gz_places(S.chain.data(), n, S.text_len.data(), S.n_ends.data(), S.last_end.data(), off2.data(), places.data(), places.data() + n + 1);
+        }
+        const uint64_t nm = members ? places[n] : 0;
+        const uint64_t max_pieces = members ? nm + S.n_text / kGzCrcPiece + 1 : 0;
+        HIPCHK(c, c->gz_b64.ensure(2 * nc + n + 1 + (members ? 2 * n + 1 + max_pieces + 1 : 0))); HIPCHK(c, c->gz_b32.ensure(2 * n + max_pieces));
+        if (members) HIPCHK(c, c->gz_ends.ensure(3 * (nm ? nm : 1)));
         HIPCHK(c, c->gz_sym.ensure(S.n_text)); HIPCHK(c, c->gz_win.ensure(n * (uint64_t)kGzWindow));
         HIPCHK(c, c->z_verdict.ensure(1)); HIPCHK(c, c->z_h_verdict.ensure(1));
         GzJob J{};
@@ -1724,6 +1749,13 @@ static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState
         J.start = c->gz_b64.p; J.end_bit = c->gz_b64.p + nc;
         J.n_chain = n; J.off = c->gz_b64.p + 2 * nc; J.chain = c->gz_b32.p; J.crc_part = c->gz_b32.p + n;
         J.sym = c->gz_sym.p; J.win = c->gz_win.p; J.out = d_out; J.verdict = c->z_verdict.p;
+        if (members) {
+            static_assert(sizeof(GzEnd) == 24 && alignof(GzEnd) == 8, "GzEnd is three words");
+            uint64_t *pl = c->gz_b64.p + 2 * nc + n + 1;
+            J.slot = pl; J.m0 = pl + n + 1; J.piece = pl + 2 * n + 1; J.crc_piece = c->gz_b32.p + 2 * n;
+            J.ends = reinterpret_cast<GzEnd *>(c->gz_ends.p);
+            HIPCHK(c, hipMemcpyAsync(pl, places.data(), (2 * n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        }
         HIPCHK(c, hipMemcpyAsync(J.start, S.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(J.end_bit, S.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->gz_b64.p + 2 * nc, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -1734,13 +1766,35 @@ static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState
             for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
             HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
         }
-        HIPCHK(c, launch_gz_decode(J, c->stream));
+        HIPCHK(c, launch_gz_decode(J, c->stream, members));
         if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[3], c->stream));
         HIPCHK(c, launch_gz_windows(J, c->stream));
         if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[4], c->stream));
-        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream, members));
+        std::vector<uint64_t> piece;
+        std::vector<uint32_t> mcrc, misz;
+        if (members) {
+            // the records come down (the stream is waited for: decode is done, narrow may still run), the member table and the
+            // pieces are made, the pieces' bounds go up for k_gz_member_crc; narrow's time then includes that round trip
+            std::vector<GzEnd> ends(nm ? nm : 1);
+            HIPCHK(c, hipMemcpyAsync(ends.data(), J.ends, nm * sizeof(GzEnd), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            S.in_off.assign(nm + 1, 0); S.text_off.assign(nm + 1, 0); mcrc.assign(nm, 0); misz.assign(nm, 0);
+            gz_member_table(S.M, S.n_file, off.data(), places.data(), n, ends.data(), S.in_off.data(), S.text_off.data(), mcrc.data(), misz.data());
+            for (uint64_t m = 0; m < nm; m++) {
+                if (S.text_off[m + 1] < S.text_off[m] || S.text_off[m + 1] > S.n_text) return CRASS_ERR_STATE;      // (a record nobody wrote)
+                for (uint64_t p = S.text_off[m]; p < S.text_off[m + 1]; p += kGzCrcPiece) piece.push_back(p);
+            }
+            piece.push_back(S.n_text);
+            if (piece.size() - 1 > max_pieces) return CRASS_ERR_STATE;
+            J.n_pieces = piece.size() - 1;
+            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(J.piece), piece.data(), piece.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, launch_gz_member_crc(J, c->stream));
+        }
         if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[5], c->stream));
-        HIPCHK(c, hipMemcpyAsync(crc_part.data(), J.crc_part, n * 4, hipMemcpyDeviceToHost, c->stream));
+        std::vector<uint32_t> crc_piece(members ? piece.size() : 1, 0);
+        if (members && J.n_pieces) HIPCHK(c, hipMemcpyAsync(crc_piece.data(), J.crc_piece, J.n_pieces * 4, hipMemcpyDeviceToHost, c->stream));
+        if (!members) HIPCHK(c, hipMemcpyAsync(crc_part.data(), J.crc_part, n * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (timed) {
@@ -1754,6 +1808,17 @@ static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState
             const uint64_t k = S.chain[w];
             return decline(BZ_MARKER, k, G.d_off + (S.start[k] >> 3));
         }
+        if (members) {
+            // a member's pieces joined in text order (an empty member has none: CRC 0)
+            std::vector<uint32_t> got(nm, 0);
+            uint64_t q = 0;
+            for (uint64_t m = 0; m < nm; m++)
+                for (; q + 1 < piece.size() && piece[q] < S.text_off[m + 1]; q++) got[m] = gz_crc_join(got[m], crc_piece[q], piece[q + 1] - piece[q]);
+            GzVerdict mv{};
+            if (gz_member_verdict(nm, S.in_off.data(), S.text_off.data(), mcrc.data(), misz.data(), got.data(), &mv) != BZ_OK)
+                return decline(mv.reason, mv.member, mv.in_pos);
+            return CRASS_OK;
+        }
         uint32_t crc = 0;
         for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
         if (crc != S.M.crc) return decline(BZ_CRC, 0, 0);
@@ -1761,31 +1826,46 @@ static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, const GzState
     return CRASS_OK;
 }
 
-int crass_hip_inflate_gzip_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
-                                  uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+static int inflate_gzip_device_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
+                                    uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, bool mode, crass_bgzf_verdict *v)
 {
     if (v) memset(v, 0, sizeof(*v));
     if (plan) memset(plan, 0, sizeof(*plan));
+    if (members) memset(members, 0, sizeof(*members));
     if (n_text) *n_text = 0;
     if (!c || !n_text || (n_in && !d_in) || (out_cap && !d_out)) return CRASS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     GzState S;
-    int s = gzip_count_impl(c, d_in, n_in, chunk_bytes, S, plan, v);
+    int s = gzip_count_impl(c, d_in, n_in, chunk_bytes, S, plan, v, mode);
     if (s == CRASS_OK) {
         *n_text = S.n_text;
         if (out_cap < S.n_text) s = CRASS_ERR_OVERFLOW;       // (known before anything is stored)
         else s = gzip_decode_impl(c, d_in, S, d_out, v);
+        if (s == CRASS_OK && mode) s = gz_members_fill(members, S.in_off.size() - 1, S.in_off.data(), S.text_off.data());
     }
     gzip_release(c);
     c->z_verdict.release();
     return s;
 }
 
-int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
-                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
+int crass_hip_inflate_gzip_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
+                                  uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    return inflate_gzip_device_impl(c, d_in, n_in, chunk_bytes, d_out, out_cap, n_text, plan, nullptr, false, v);
+}
+
+int crass_hip_inflate_gzip_members_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
+                                          uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
+{
+    return inflate_gzip_device_impl(c, d_in, n_in, chunk_bytes, d_out, out_cap, n_text, plan, members, true, v);
+}
+
+static int load_fastx_gzip_impl(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
+                                uint64_t d_text_cap, crass_fastx_layout *out, crass_gzip_members *members, bool mode, crass_bgzf_verdict *v)
 {
     if (out) memset(out, 0, sizeof(*out));
     if (v) memset(v, 0, sizeof(*v));
+    if (members) memset(members, 0, sizeof(*members));
     if (!c || pad_uniform < 0 || pad_uniform > 2 || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     reset_results(c);
@@ -1798,12 +1878,13 @@ int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n
         if (up) return up;
         HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->copy_stream));
         GzState S;
-        int s = gzip_count_impl(c, c->z_raw.p, n_bytes, 0, S, nullptr, v);
+        int s = gzip_count_impl(c, c->z_raw.p, n_bytes, 0, S, nullptr, v, mode);
         if (s) return s;
         if (d_text && d_text_cap < S.n_text) return CRASS_ERR_INVALID_ARG;
         if (!d_text) { HIPCHK(c, c->z_text.ensure(S.n_text + 16)); d_text = c->z_text.p; }
         s = gzip_decode_impl(c, c->z_raw.p, S, d_text, v);
         if (s) return s;
+        if (mode) { s = gz_members_fill(members, S.in_off.size() - 1, S.in_off.data(), S.text_off.data()); if (s) return s; }
         gzip_release(c);
         c->z_raw.release();                             // (the compressed bytes are done with: the scan's arrays may have their room)
         return load_fastx_impl(c, nullptr, d_text, S.n_text, pad_uniform, read_index_base, out);
@@ -1816,13 +1897,27 @@ int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n
     c->x_rec_pos.release(); c->x_seq_off.release();
     c->t_off.release();
     for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
+    if (s && members) crass_gzip_members_free(members);      // (a scan decline behind an accepted inflate: no table without reads)
     return s;
+}
+
+int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
+                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
+{
+    return load_fastx_gzip_impl(c, bytes, n_bytes, pad_uniform, read_index_base, d_text, d_text_cap, out, nullptr, false, v);
+}
+
+int crass_hip_load_fastx_gzip_members(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                                      uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_gzip_members *members,
+                                      crass_bgzf_verdict *v)
+{
+    return load_fastx_gzip_impl(c, bytes, n_bytes, pad_uniform, read_index_base, d_text, d_text_cap, out, members, true, v);
 }
 
 int crass_hip_set_gzip_on_device(crass_hip_ctx *c, int on)
 {
     if (!c) return CRASS_ERR_INVALID_ARG;
-    c->gzip_on_device = on != 0;
+    c->gzip_on_device = on == CRASS_GZIP_ON_DEVICE_MEMBERS ? CRASS_GZIP_ON_DEVICE_MEMBERS : on != 0 ? CRASS_GZIP_ON_DEVICE_ONE_MEMBER : CRASS_GZIP_ON_DEVICE_OFF;
     return CRASS_OK;
 }
 
@@ -2030,13 +2125,13 @@ static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, 
         if (n >= 2 && b[0] == 0x1F && b[1] == 0x8B) {
             const int s = crass_bgzf_index_host(b, n, &F.ix);
             if (s == CRASS_ERR_UNSUPPORTED && c->gzip_on_device) {
-                // plain gzip (crass_hip_set_gzip_on_device): its bytes go up once for the count step, which sizes its share of the arena
+                // plain gzip (crass_hip_set_gzip_on_device; of any number of members with CRASS_GZIP_ON_DEVICE_MEMBERS): its bytes go up once for the count step, which sizes its share of the arena
                 HIPCHK(c, c->z_raw.ensure(n + 16));
                 const int up = upload_staged(c, b, n, c->z_raw.p);
                 if (up) return up;
                 HIPCHK(c, hipStreamSynchronize(c->copy_stream));
                 crass_bgzf_verdict v{};
-                const int gs = gzip_count_impl(c, c->z_raw.p, n, 0, F.gzs, nullptr, &v);
+                const int gs = gzip_count_impl(c, c->z_raw.p, n, 0, F.gzs, nullptr, &v, c->gzip_on_device == CRASS_GZIP_ON_DEVICE_MEMBERS);
                 if (gs == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = v; nf = f; break; }
                 if (gs) return gs;
                 F.gz = true; F.n_text = F.gzs.n_text;

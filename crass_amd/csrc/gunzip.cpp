@@ -1,5 +1,6 @@
 // gunzip.cpp — plain gzip on the host: a serial run of gunzip_core.h's rule (find, count, chain, decode, windows, narrow), one
 // chunk after the other.  It needs no GPU; it is what the kernels (gunzip.hip) are tested against, itself tested against zlib.
+// crass_gzip_inflate_members_host is the same run in members mode (a file of several members).
 // Host-only C++17 that any compiler builds (tools/sanitize).  Scratch: 2 bytes per text byte and 32 KB per chain element.
 #include "../../include/crass_hip.h"
 #include "gunzip_core.h"
@@ -14,6 +15,7 @@ namespace crass {
 // the host's way through the core: one executor, one index after the other
 struct GzHostIO {
     const uint8_t *d; uint64_t dn; const uint8_t *src; uint32_t n_in; uint16_t *sym; uint64_t cap;
+    GzEnd *ends = nullptr; uint32_t ends_cap = 0;         // (members mode)
     void at(uint64_t b0, uint32_t n) { src = d + b0; n_in = n; }
     uint32_t in(uint32_t i) const { return i < n_in ? src[i] : 0u; }
     void put(uint64_t p, uint32_t s) { if (p < cap) sym[p] = (uint16_t)s; }
@@ -27,6 +29,14 @@ struct GzHostIO {
         for (uint32_t l = 0; l < 64; l++) m |= (uint64_t)gz_survives(d, dn, base + l, hi, limit) << l;
         return m;
     }
+    uint64_t header_survivors(uint64_t base, uint64_t hi, uint64_t limit) const
+    {
+        uint64_t m = 0;
+        for (uint32_t l = 0; l < 64; l += 8) m |= (uint64_t)gz_survives_header(d, dn, base + l, hi, limit) << l;      // (base is a multiple of 8)
+        return m;
+    }
+    uint32_t tail(uint32_t i) const { return i < 8 ? d[dn + i] : 0u; }
+    void end(uint32_t e, const GzEnd &r) { if (e < ends_cap) ends[e] = r; }
 };
 
 // what the rule decided, for the caller (malloc'd: crass_gzip_plan_free)
@@ -41,24 +51,29 @@ int gz_plan_fill(crass_gzip_plan *plan, uint64_t nc, const uint64_t *start, cons
     return CRASS_OK;
 }
 
+int gz_members_fill(crass_gzip_members *m, uint64_t nm, const uint64_t *in_off, const uint64_t *text_off)
+{
+    if (!m) return CRASS_OK;
+    crass_gzip_members_free(m);
+    m->in_off = (uint64_t *)malloc((nm + 1) * 8); m->text_off = (uint64_t *)malloc((nm + 1) * 8);
+    if (!m->in_off || !m->text_off) { crass_gzip_members_free(m); return CRASS_ERR_OOM; }
+    memcpy(m->in_off, in_off, (nm + 1) * 8); memcpy(m->text_off, text_off, (nm + 1) * 8);
+    m->n_members = nm;
+    return CRASS_OK;
+}
+
 } // namespace crass
 
 using namespace crass;
 
-extern "C" {
-
-void crass_gzip_plan_free(crass_gzip_plan *p)
-{
-    if (!p) return;
-    free(p->start_bit); free(p->link); free(p->text_len);
-    p->start_bit = nullptr; p->link = nullptr; p->text_len = nullptr; p->n_chunks = 0; p->n_chain = 0;
-}
-
-int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
-                            crass_gzip_plan *plan, crass_bgzf_verdict *v)
+// the serial run; MEM: members mode (gunzip_core.h), `members` (may be NULL) gets the member table
+template <bool MEM>
+static int gz_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                           crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
 {
     if (v) memset(v, 0, sizeof(*v));
     if (plan) memset(plan, 0, sizeof(*plan));
+    if (members) memset(members, 0, sizeof(*members));
     if (n_text) *n_text = 0;
     if (!n_text || (n_bytes && !bytes) || (out_cap && !out)) return CRASS_ERR_INVALID_ARG;
     auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
@@ -76,21 +91,23 @@ int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chu
         std::vector<uint64_t> start(nc, kGzNoStart), text_len(nc, 0), end_bit(nc, 0), off(nc, 0);
         std::vector<uint32_t> link(nc, GZ_LINK_NONE), chain(nc, 0);
         std::vector<int32_t> reason(nc, 0);
+        std::vector<uint32_t> n_ends(nc, 0);
+        std::vector<uint64_t> last_end(nc, 0);
         GzHostIO io{bytes + G.d_off, G.dn, nullptr, 0, nullptr, 0};
         bz_prepare(io, *T);
         // find
         start[0] = 0;
-        for (uint64_t k = 1; k < nc; k++) start[k] = gz_find(io, *T, G, k);
+        for (uint64_t k = 1; k < nc; k++) start[k] = gz_find<MEM>(io, *T, G, k);
         // count
         for (uint64_t k = 0; k < nc; k++) {
             if (start[k] == kGzNoStart) continue;
-            const GzRun R = gz_run<GZ_COUNT>(io, *T, G, k, start[k], start.data(), 0);
-            link[k] = R.link; text_len[k] = R.text; end_bit[k] = R.end_bit; reason[k] = R.reason;
+            const GzRun R = gz_run<GZ_COUNT, MEM>(io, *T, G, k, start[k], start.data(), 0);
+            link[k] = R.link; text_len[k] = R.text; end_bit[k] = R.end_bit; reason[k] = R.reason; n_ends[k] = R.n_ends; last_end[k] = R.last_end;
         }
         // chain
         uint64_t n_chain = 0, total = 0;
         GzVerdict gv{};
-        const int32_t why = gz_chain(M, start.data(), link.data(), text_len.data(), end_bit.data(), reason.data(), chain.data(), &n_chain, &total, &gv);
+        const int32_t why = gz_chain(M, start.data(), link.data(), text_len.data(), end_bit.data(), reason.data(), chain.data(), &n_chain, &total, &gv, MEM);
         status = gz_plan_fill(plan, nc, start.data(), link.data(), text_len.data(), n_chain);
         if (status) { delete T; return status; }
         if (why != BZ_OK) { delete T; return decline(gv.reason, gv.member, gv.in_pos); }
@@ -101,10 +118,15 @@ int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chu
         std::vector<uint8_t> win(n_chain * (uint64_t)kGzWindow);
         uint64_t t = 0;
         for (uint64_t i = 0; i < n_chain; i++) { off[chain[i]] = t; t += text_len[chain[i]]; }
+        // (members mode: the chain's places by element, every element's GzEnd slots)
+        std::vector<uint64_t> eoff(n_chain + 1, 0), slot(n_chain + 1, 0), m0(n_chain, 0);
+        if (MEM) gz_places(chain.data(), n_chain, text_len.data(), n_ends.data(), last_end.data(), eoff.data(), slot.data(), m0.data());
+        std::vector<GzEnd> ends(slot[n_chain] ? slot[n_chain] : 1);
         for (uint64_t i = 0; i < n_chain; i++) {
             const uint64_t k = chain[i];
             io.sym = sym.data() + off[k]; io.cap = text_len[k];
-            (void)gz_run<GZ_DECODE>(io, *T, G, k, start[k], nullptr, end_bit[k]);
+            io.ends = ends.data() + slot[i]; io.ends_cap = (uint32_t)(slot[i + 1] - slot[i]);
+            (void)gz_run<GZ_DECODE, MEM>(io, *T, G, k, start[k], nullptr, end_bit[k]);
         }
         // windows, in chain order
         for (uint64_t i = 1; i < n_chain; i++) {
@@ -120,17 +142,61 @@ int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chu
             const uint8_t *w = i ? win.data() + i * (uint64_t)kGzWindow : nullptr;
             uint32_t c = 0xFFFFFFFFu;
             for (uint64_t p = 0; p < text_len[k]; p++) {
-                const uint32_t b = gz_narrow(sym[off[k] + p], w, off[k]);
+                const uint32_t b = gz_narrow(sym[off[k] + p], w, off[k], m0[i]);
                 if (b > 0xFFu) { status = decline(BZ_MARKER, k, G.d_off + (start[k] >> 3)); break; }
                 out[off[k] + p] = (uint8_t)b;
                 c = T->crc_tab[(c ^ b) & 0xFFu] ^ (c >> 8);
             }
             crc = gz_crc_join(crc, text_len[k] ? ~c : 0u, text_len[k]);
         }
-        if (status == CRASS_OK && crc != M.crc) status = decline(BZ_CRC, 0, 0);
+        if (!MEM && status == CRASS_OK && crc != M.crc) status = decline(BZ_CRC, 0, 0);
+        if (MEM && status == CRASS_OK) {
+            // every member's place, ISIZE and CRC-32: behind the decode step, from the records the runs left
+            const uint64_t nm = slot[n_chain];
+            std::vector<uint64_t> in_off(nm + 1, 0), text_off(nm + 1, 0);
+            std::vector<uint32_t> mcrc(nm, 0), misz(nm, 0), got(nm, 0);
+            gz_member_table(M, n_bytes, eoff.data(), slot.data(), n_chain, ends.data(), in_off.data(), text_off.data(), mcrc.data(), misz.data());
+            for (uint64_t m = 0; m < nm; m++) {
+                uint32_t c = 0xFFFFFFFFu;
+                for (uint64_t p = text_off[m]; p < text_off[m + 1]; p++) c = T->crc_tab[(c ^ out[p]) & 0xFFu] ^ (c >> 8);
+                got[m] = text_off[m + 1] > text_off[m] ? ~c : 0u;
+            }
+            GzVerdict mv{};
+            if (gz_member_verdict(nm, in_off.data(), text_off.data(), mcrc.data(), misz.data(), got.data(), &mv) != BZ_OK)
+                status = decline(mv.reason, mv.member, mv.in_pos);
+            else status = gz_members_fill(members, nm, in_off.data(), text_off.data());
+        }
     } catch (const std::bad_alloc &) { status = CRASS_ERR_OOM; }
     delete T;
     return status;
+}
+
+extern "C" {
+
+void crass_gzip_plan_free(crass_gzip_plan *p)
+{
+    if (!p) return;
+    free(p->start_bit); free(p->link); free(p->text_len);
+    p->start_bit = nullptr; p->link = nullptr; p->text_len = nullptr; p->n_chunks = 0; p->n_chain = 0;
+}
+
+int crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                            crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    return gz_inflate_host<false>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, nullptr, v);
+}
+
+void crass_gzip_members_free(crass_gzip_members *m)
+{
+    if (!m) return;
+    free(m->in_off); free(m->text_off);
+    m->in_off = nullptr; m->text_off = nullptr; m->n_members = 0;
+}
+
+int crass_gzip_inflate_members_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                                    crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
+{
+    return gz_inflate_host<true>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, members, v);
 }
 
 } // extern "C"

@@ -27,8 +27,41 @@
 // also bounds what one wave decodes (nothing runs away on a pathological input) and keeps a run's bit offsets inside 32 bits:
 // 32 chunks of less than 2 kGzMaxChunk bytes are less than 2^31 bits.
 //
-// Bounds: a run reads d[b0, b0 + n_in) only (in() answers 0 beyond, every taker checks over()); every loop iteration takes at
-// least one input bit or ends; a decode run writes symbols [0, counted length) of its chunk only (put() checks).
+// Members mode (the MEM template parameter; off, every statement above is what it was): a file of SEVERAL plain members (cat of
+// .gz files, gzip's >>, a compressor that starts a member every N records), which zlib's gzread reads as one stream.  The region
+// d[0, dn) is still what lies between the FIRST header and the file's LAST 8 bytes (the last member's trailer); inner trailers and
+// inner headers are bytes of the region, chunks and nominal[] are cut over all of it.
+//   a run    goes on past a final block: to the byte edge; at the region's end it ends with GZ_LINK_END; otherwise 8 trailer
+//            bytes, then at byte H a gzip header (the fields gz_parse_member checks), then the next member's first block.  Bytes at
+//            H without the magic, or fewer than 18 bytes up to the file's end: reason 13; the magic but a header the rule does not
+//            take, or one that runs into the file's last 8 bytes: 11; a header (or inner trailer) the run cannot read inside its
+//            input bound n_in (kGzSlack behind the span) surfaces as the span reason, 12 — accepted: such a run would have given
+//            up a few bytes further on anyway, and a larger chunk takes the file.  n_ends counts the final blocks a run passed,
+//            last_end is the text position of the last of them
+//   window   a match that stands p text bytes behind the last member boundary the run passed, with a distance > p, is a fault
+//            (14) in TRIAL, COUNT and DECODE alike; before a run's first boundary references in front of the run stay markers
+//   find     position p also passes when it is byte-aligned, the bytes there are a gzip header the rule takes, the member's first
+//            block (of any type) decodes and a second one too if there is one, and, where the first block is final, the ISIZE
+//            behind it equals the text produced (so a file of many members of one final block each has starts).  Such a start
+//            is the bit of the header's FIRST byte.  A byte-aligned 1F reads as BFINAL 1 / BTYPE 3, so the two kinds of start
+//            cannot be confused: a run that begins on the magic parses the header first, knows that its member begins there and
+//            emits no markers (14 instead).  gz_survives_header is the cheap part, as gz_survives
+//   links    COUNT's link test and DECODE's end test run at H as at a block boundary (start[j] == 8 H and text produced), behind
+//            the check of the magic at H.  A link goes only to a start of the kind the run arrives as: at H to a member's start,
+//            at a block boundary never to one (there the byte-aligned magic is BTYPE 3, as for zlib)
+//   narrow   gz_narrow gets m0, the text offset of the start of the member that holds the element's first byte (the host derives
+//            it from the chain's n_ends / last_end): a marker w with t0 - m0 + w < kGzWindow points in front of the member (14)
+//   ends     DECODE writes a GzEnd per final block it passes into the element's slots (base: the prefix sum of n_ends over the
+//            chain); from them the host gets every member's place in file and text and checks every member's ISIZE (7 / 8) and,
+//            from k_gz_member_crc's pieces joined with gz_crc_join, its CRC-32 (9).  Unlike the single-member rule, which knows
+//            the one ISIZE before it decodes, this happens AFTER the decode step: inner trailers are only met by the runs
+// Three deliberate differences from gzread: bytes behind the last member that are no gzip header (zero padding included) are
+// declined (13) where zlib ignores them; stored-only or fixed-only data needs a start every kGzMaxSpan chunks (12) where zlib
+// takes any size; an inner header beyond a run's input bound is declined (12).
+//
+// Bounds: a run reads d[b0, b0 + n_in) only, and in members mode the 8 bytes behind the region through io.tail() (in() answers 0
+// beyond, every taker checks over()); every loop iteration takes at least one input bit or ends; a decode run writes symbols
+// [0, counted length) of its chunk only (put() checks) and its own GzEnd slots only (end() checks).
 #pragma once
 #include "inflate_core.h"
 
@@ -142,22 +175,79 @@ CRASS_HD inline bool gz_survives(const uint8_t *d, uint64_t dn, uint64_t p, uint
     return gz_prefilter(lo, c >> sh);
 }
 
+// members mode: position p may be a member's start: byte-aligned, the magic, method 8, no reserved flag
+CRASS_HD inline bool gz_survives_header(const uint8_t *d, uint64_t dn, uint64_t p, uint64_t hi, uint64_t limit)
+{
+    if (p >= hi || p + 64 >= limit || (p & 7u)) return false;
+    const uint64_t b = p >> 3;                            // (b + 8 < dn)
+    return b + 3 < dn && d[b] == 0x1Fu && d[b + 1] == 0x8Bu && d[b + 2] == 8u && !(d[b + 3] & 0xE0u);
+}
+
 // ---- a run: blocks decoded from a bit position, in one of three ways ----
 // The IO of inflate_core.h, with 16-bit symbols as text and a movable input:
 //   void     at(uint64_t b0, uint32_t n) in(i) is byte b0 + i of the deflate data for i < n, else 0
 //   void     put(uint64_t p, uint32_t s) symbol p of the chunk (p below the counted length, else nothing)
 //   uint32_t get(uint64_t p)             ... read back
 //   uint64_t survivors(d.., base, hi, limit) bit l: gz_survives(base + l)
+// and in members mode:
+//   uint64_t header_survivors(base, hi, limit) bit l: gz_survives_header(base + l)
+//   uint32_t tail(uint32_t i)            byte i < 8 behind the region: the file's last trailer
+//   void     end(uint32_t e, GzEnd r)    the record of the e-th final block this run passed (e below the counted n_ends, else nothing)
 enum GzMode : int { GZ_TRIAL = 0, GZ_COUNT = 1, GZ_DECODE = 2 };
-struct GzRun { int32_t reason; uint32_t link; uint64_t text, end_bit; };
+struct GzRun { int32_t reason; uint32_t link; uint64_t text, end_bit; uint32_t n_ends; uint64_t last_end; };
+// a member's end as DECODE met it: the text position in the element, the file byte of the next member's header (the file's size
+// behind the last member), the trailer's CRC-32 and ISIZE (0 for the last member: the host holds that trailer)
+struct GzEnd { uint64_t pos, next; uint32_t crc, isize; };
+
+// members mode: the gzip header at byte h <= n_in of the run's input, of which `room` bytes lie in front of the region's end: its
+// length, or minus the reason — 13 without the magic, 11 for a header the rule does not take or that runs into the file's last 8
+// bytes, 6 for one the run may not read to its end (gz_run turns that into 12 where the run does not see the region's end)
+template <class IO> CRASS_HD inline int32_t gz_header_at(IO &io, const BzTables &T, uint32_t h, uint32_t n_in, uint64_t room)
+{
+    const uint64_t avail = n_in - h;
+    if (avail < 2) return -BZ_INPUT_END;
+    if (io.in(h) != 0x1Fu || io.in(h + 1) != 0x8Bu) return -BZ_TRAILING;
+    if (avail < 10) return -BZ_INPUT_END;
+    if (io.in(h + 2) != 8u || (io.in(h + 3) & 0xE0u)) return -BZ_NOT_GZIP;
+    const uint32_t flg = io.in(h + 3);
+    uint64_t d = 10;
+    if (flg & 4u) {
+        if (d + 2 > room) return -BZ_NOT_GZIP;
+        if (d + 2 > avail) return -BZ_INPUT_END;
+        d += 2 + (uint64_t)(io.in(h + 10) | io.in(h + 11) << 8);
+        if (d > room) return -BZ_NOT_GZIP;
+        if (d > avail) return -BZ_INPUT_END;
+    }
+    for (uint32_t bit = 3; bit <= 4; bit++)
+        if (flg & (1u << bit)) {
+            for (;; d++) {                                // (ends: d reaches room or avail)
+                if (d >= room) return -BZ_NOT_GZIP;
+                if (d >= avail) return -BZ_INPUT_END;
+                if (!io.in(h + (uint32_t)d)) break;
+            }
+            d++;
+        }
+    if (flg & 2u) {
+        if (d + 2 > room) return -BZ_NOT_GZIP;
+        if (d + 2 > avail) return -BZ_INPUT_END;
+        uint32_t c = 0xFFFFFFFFu;
+        for (uint32_t i = 0; i < (uint32_t)d; i++) c = T.crc_tab[(c ^ io.in(h + i)) & 0xFFu] ^ (c >> 8);
+        c = ~c;
+        if ((c & 0xFFFFu) != (io.in(h + (uint32_t)d) | io.in(h + (uint32_t)d + 1) << 8)) return -BZ_NOT_GZIP;
+        d += 2;
+    }
+    return (int32_t)d;                                    // (<= n_in < 2^29)
+}
 
 template <class IO> CRASS_HD inline uint64_t gz_at(const BzBits<IO> &B, uint64_t b0) { return b0 * 8 + (uint64_t)(8u * B.ip - B.nb); }
 
 // TRIAL   two blocks from start_bit, the first one BFINAL 0 / BTYPE 2: reason BZ_OK when both decode
 // COUNT   until a link (start[] are all chunks' starts), the final block's end, the span's end or a fault
 // DECODE  the blocks COUNT went through (it ended at bit end_bit), as symbols
-template <int MODE, class IO>
-CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, uint64_t start_bit, const uint64_t *start, uint64_t end_bit)
+// MEM: members mode; header_trial: the TRIAL is that of a member's start (COUNT and DECODE see what their start is by its bytes)
+template <int MODE, bool MEM = false, class IO>
+CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, uint64_t start_bit, const uint64_t *start, uint64_t end_bit,
+                             bool header_trial = false)
 {
     const uint64_t b0 = start_bit >> 3, limit = G.dn * 8;
     const uint64_t stop_bit = gz_nominal(G, k + kGzMaxSpan);
@@ -168,11 +258,18 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
     const bool sees_end = b0 + n_in == G.dn;
     io.at(b0, n_in);
     BzBits<IO> B(io, n_in);
-    B.refill();
-    B.drop((uint32_t)(start_bit & 7u));
     uint64_t pos = 0;
     uint32_t blocks = 0;
-    GzRun R{BZ_OK, GZ_LINK_BAD, 0, 0};
+    GzRun R{BZ_OK, GZ_LINK_BAD, 0, 0, 0, 0};
+    // members mode: the text position of the last member boundary passed, once there is one
+    bool bounded = false;
+    uint64_t mb = 0;
+    const bool at_header = MEM && k > 0 && !(start_bit & 7u) && (MODE != GZ_TRIAL || header_trial) && io.in(0) == 0x1Fu && io.in(1) == 0x8Bu;
+    if (MEM && MODE == GZ_TRIAL && header_trial && !at_header) { R.reason = BZ_NOT_GZIP; return R; }
+    if (!at_header) {
+        B.refill();
+        B.drop((uint32_t)(start_bit & 7u));
+    }
 #define GZ_STOP(why_)                                                                                                     \
     {                                                                                                                     \
         int32_t w_ = (why_);                                                                                              \
@@ -180,11 +277,25 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
         R.reason = w_; R.link = w_ == BZ_NO_START ? GZ_LINK_UNFINISHED : GZ_LINK_BAD; R.text = pos; R.end_bit = gz_at(B, b0); \
         return R;                                                                                                         \
     }
+    if (at_header) {
+        const int32_t hl = gz_header_at(io, T, 0, n_in, G.dn - b0);
+        if (hl < 0) GZ_STOP(-hl);
+        B.ip = (uint32_t)hl;
+        bounded = true;
+    }
     for (;;) {                                            // a block: at least its 3 header bits
         const uint64_t here = gz_at(B, b0);
         if (MODE == GZ_COUNT && pos > 0 && here < limit) {
             const uint64_t j = gz_chunk_of(G, here);
-            if (j > k && start[j] == here) { R.link = (uint32_t)j; break; }
+            // (members mode: a byte-aligned start on the magic is a MEMBER's start; a run that arrives at it at a block boundary
+            // stands in the middle of a member, where 1F is BFINAL 1 / BTYPE 3: no link, the block header below faults.  Where the
+            // two bytes lie beyond the run's input the kind is unknown: no link either, the run ends at its bound)
+            bool member_start = false;
+            if (MEM && !(here & 7u)) {
+                const uint64_t r = (here >> 3) - b0;
+                member_start = r + 2 > n_in || (io.in((uint32_t)r) == 0x1Fu && io.in((uint32_t)r + 1) == 0x8Bu);
+            }
+            if (j > k && start[j] == here && !member_start) { R.link = (uint32_t)j; break; }
         }
         if (MODE == GZ_DECODE && here == end_bit) break;
         if (MODE == GZ_TRIAL && blocks == 2) break;
@@ -193,7 +304,7 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
         const uint32_t hdr = B.take(3);
         if (B.over()) GZ_STOP(BZ_INPUT_END);
         const uint32_t final_block = hdr & 1u, type = hdr >> 1;
-        if (MODE == GZ_TRIAL && blocks == 0 && hdr != 4u) GZ_STOP(BZ_BLOCK_TYPE);
+        if (MODE == GZ_TRIAL && blocks == 0 && !at_header && hdr != 4u) GZ_STOP(BZ_BLOCK_TYPE);
         if (type == 3) GZ_STOP(BZ_BLOCK_TYPE);
         if (type == 0) {
             B.drop(B.nb & 7u);                            // to the byte edge
@@ -239,6 +350,7 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
                 else { const uint32_t e = ((uint32_t)d >> 1) - 1; dist = 1 + ((2 + ((uint32_t)d & 1u)) << e) + B.take(e); }
                 if (B.over()) GZ_STOP(BZ_INPUT_END);
                 // (dist <= 32768: it reaches the chunk's own symbols or the window in front of it, nothing else)
+                if (MEM && bounded && dist > pos - mb) GZ_STOP(BZ_MARKER);      // ... or, behind a boundary, the member's own text
                 if (MODE == GZ_DECODE) {
                     // symbol i comes from pos - dist + (i mod dist): all of them were there before this match, or lie in the window
                     io.sync();
@@ -252,7 +364,56 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
             }
         }
         blocks++;
-        if (final_block) { R.link = GZ_LINK_END; break; }
+        if (!MEM) {
+            if (final_block) { R.link = GZ_LINK_END; break; }
+            continue;
+        }
+        if (MODE == GZ_TRIAL && blocks == 2) break;
+        if (!final_block) continue;
+        // a member's end: the byte edge, the trailer, and unless the region ends here the next member's header
+        B.drop(B.nb & 7u);
+        const uint32_t from = B.ip - B.nb / 8;            // (<= n_in: not over)
+        const uint64_t edge = b0 + from;
+        if (MODE == GZ_TRIAL) {                           // (a member's start whose first block is final: its ISIZE)
+            uint32_t isz = 0;
+            if (edge == G.dn) { for (uint32_t i = 0; i < 4; i++) isz |= io.tail(4 + i) << (8 * i); }
+            else {
+                if ((uint64_t)from + 8 > n_in) GZ_STOP(BZ_INPUT_END);
+                for (uint32_t i = 0; i < 4; i++) isz |= io.in(from + 4 + i) << (8 * i);
+            }
+            if (isz != (uint32_t)pos) GZ_STOP(BZ_OUTPUT_SHORT);
+            break;
+        }
+        R.n_ends++; R.last_end = pos;
+        if (edge == G.dn) {
+            if (MODE == GZ_DECODE && io.lead()) io.end(R.n_ends - 1, GzEnd{pos, G.d_off + G.dn + 8, 0, 0});
+            R.link = GZ_LINK_END;
+            break;
+        }
+        B.ip = from; B.hold = 0; B.nb = 0;
+        if (edge + 8 + 18 > G.dn + 8) GZ_STOP(BZ_TRAILING);
+        if ((uint64_t)from + 8 > n_in) GZ_STOP(BZ_INPUT_END);
+        if (MODE == GZ_DECODE && io.lead()) {
+            uint32_t crc = 0, isz = 0;
+            for (uint32_t i = 0; i < 4; i++) { crc |= io.in(from + i) << (8 * i); isz |= io.in(from + 4 + i) << (8 * i); }
+            io.end(R.n_ends - 1, GzEnd{pos, G.d_off + edge + 8, crc, isz});
+        }
+        B.ip = from + 8;
+        const uint64_t hbit = (edge + 8) * 8;             // (< limit: 18 bytes follow)
+        // the magic before the link and end tests: a link at H goes to a member's start only, never to a block start that
+        // happens to stand where a header should (a byte-aligned start on the magic is a member's start: 1F is no BFINAL 0)
+        if ((uint64_t)from + 10 > n_in) GZ_STOP(BZ_INPUT_END);
+        if (io.in(from + 8) != 0x1Fu || io.in(from + 9) != 0x8Bu) GZ_STOP(BZ_TRAILING);
+        if (MODE == GZ_COUNT && pos > 0) {
+            const uint64_t j = gz_chunk_of(G, hbit);
+            if (j > k && start[j] == hbit) { R.link = (uint32_t)j; break; }
+        }
+        if (MODE == GZ_DECODE && hbit == end_bit) break;
+        if (!to_end && hbit >= stop_bit) GZ_STOP(BZ_NO_START);
+        const int32_t hl = gz_header_at(io, T, from + 8, n_in, G.dn - (edge + 8));
+        if (hl < 0) GZ_STOP(-hl);
+        B.ip = from + 8 + (uint32_t)hl;
+        bounded = true; mb = pos;
     }
 #undef GZ_STOP
     R.text = pos; R.end_bit = gz_at(B, b0);
@@ -260,15 +421,18 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
 }
 
 // start[k] for k >= 1: positions in ascending order, 64 at a time through gz_survives, the survivors through the trial
-template <class IO> CRASS_HD inline uint64_t gz_find(IO &io, BzTables &T, const GzGeom &G, uint64_t k)
+// (members mode: block starts and member starts alike, whichever comes first)
+template <bool MEM = false, class IO> CRASS_HD inline uint64_t gz_find(IO &io, BzTables &T, const GzGeom &G, uint64_t k)
 {
     const uint64_t lo = gz_nominal(G, k), hi = gz_nominal(G, k + 1), limit = G.dn * 8;
     for (uint64_t base = lo; base < hi && base + 64 < limit; base += 64) {
-        uint64_t mask = io.survivors(base, hi, limit);
+        uint64_t heads = 0;
+        if (MEM) heads = io.header_survivors(base, hi, limit);
+        uint64_t mask = io.survivors(base, hi, limit) | heads;
         while (mask) {
             const uint32_t l = (uint32_t)__builtin_ctzll(mask);
             mask &= mask - 1;
-            const GzRun R = gz_run<GZ_TRIAL>(io, T, G, k, base + l, nullptr, 0);
+            const GzRun R = gz_run<GZ_TRIAL, MEM>(io, T, G, k, base + l, nullptr, 0, MEM && ((heads >> l) & 1u));
             if (R.reason == BZ_OK) return base + l;
         }
     }
@@ -288,21 +452,22 @@ CRASS_HD inline uint8_t gz_window_entry(const uint16_t *sp, uint64_t L, const ui
     return wp ? wp[w + L] : (uint8_t)0;
 }
 // a symbol of the element whose text starts at byte t0, through its window: the byte, or 0x100 for a marker that points in front
-// of the text
-CRASS_HD inline uint32_t gz_narrow(uint32_t s, const uint8_t *win, uint64_t t0)
+// of the text — in members mode in front of the member that holds the element's first byte, whose text starts at m0 <= t0
+CRASS_HD inline uint32_t gz_narrow(uint32_t s, const uint8_t *win, uint64_t t0, uint64_t m0 = 0)
 {
     if (s < 0x8000u) return s & 0xFFu;
     const uint32_t w = s & 0x7FFFu;
-    if (!win || t0 + w < kGzWindow) return 0x100u;
+    if (!win || t0 - m0 + w < kGzWindow) return 0x100u;
     return win[w];
 }
 
 // ---- the chain (host: a few hundred entries) ----
 struct GzVerdict { int32_t reason; uint64_t member, in_pos; };
 // from chunk 0 along link: chain[] gets the chunks in order (at most nc), *n_chain their number, *n_text the text's length.
-// BZ_OK or the decline (reasons 1 .. 6, 12, 13, 7 / 8)
+// BZ_OK or the decline (reasons 1 .. 6, 12, 13, 7 / 8; members: 1 .. 6, 11 .. 14 as the runs met them — every member's ISIZE is
+// checked behind the decode step, gz_member_verdict)
 inline int32_t gz_chain(const GzMember &M, const uint64_t *start, const uint32_t *link, const uint64_t *text_len, const uint64_t *end_bit,
-                        const int32_t *reason, uint32_t *chain, uint64_t *n_chain, uint64_t *n_text, GzVerdict *v)
+                        const int32_t *reason, uint32_t *chain, uint64_t *n_chain, uint64_t *n_text, GzVerdict *v, bool members = false)
 {
     const GzGeom &G = M.G;
     uint64_t n = 0, total = 0, k = 0;
@@ -319,7 +484,50 @@ inline int32_t gz_chain(const GzMember &M, const uint64_t *start, const uint32_t
     }
     *n_chain = n; *n_text = total;
     if ((end_bit[k] + 7) / 8 != G.dn) { v->reason = BZ_TRAILING; v->member = k; v->in_pos = G.d_off + (start[k] >> 3); return v->reason; }
+    if (members) return BZ_OK;
     if ((uint32_t)total != M.isize) { v->reason = (uint32_t)total > M.isize ? BZ_OUTPUT_LONG : BZ_OUTPUT_SHORT; v->member = 0; v->in_pos = 0; return v->reason; }
+    return BZ_OK;
+}
+
+// ---- members mode: places and the member table (host) ----
+static const uint64_t kGzCrcPiece = 65536;                // k_gz_member_crc: a member's text is cut into pieces of at most this
+// the chain's places from what COUNT reported per chunk: off[i] (text), slot[i] (GzEnd records), both [n + 1], and m0[i] [n]: the
+// text offset of the start of the member that holds element i's first byte
+inline void gz_places(const uint32_t *chain, uint64_t n, const uint64_t *text_len, const uint32_t *n_ends, const uint64_t *last_end, uint64_t *off,
+                      uint64_t *slot, uint64_t *m0)
+{
+    uint64_t m = 0;
+    off[0] = 0; slot[0] = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t k = chain[i];
+        m0[i] = m;
+        off[i + 1] = off[i] + text_len[k]; slot[i + 1] = slot[i] + n_ends[k];
+        if (n_ends[k]) m = off[i] + last_end[k];
+    }
+}
+// the member table from DECODE's records, slot[n] = nm >= 1 of them: in_off / text_off [nm + 1], crc / isize [nm] (the last
+// member's from the file's last 8 bytes)
+inline void gz_member_table(const GzMember &M, uint64_t n_file, const uint64_t *off, const uint64_t *slot, uint64_t n, const GzEnd *ends,
+                            uint64_t *in_off, uint64_t *text_off, uint32_t *crc, uint32_t *isize)
+{
+    in_off[0] = 0; text_off[0] = 0;
+    for (uint64_t i = 0; i < n; i++)
+        for (uint64_t e = slot[i]; e < slot[i + 1]; e++) {
+            text_off[e + 1] = off[i] + ends[e].pos; in_off[e + 1] = ends[e].next;
+            crc[e] = ends[e].crc; isize[e] = ends[e].isize;
+        }
+    const uint64_t nm = slot[n];
+    in_off[nm] = n_file; crc[nm - 1] = M.crc; isize[nm - 1] = M.isize;
+}
+// the first offending member, ISIZE (7 / 8) before CRC-32 (9) within a member; crc_got[m]: the CRC-32 of member m's text
+inline int32_t gz_member_verdict(uint64_t nm, const uint64_t *in_off, const uint64_t *text_off, const uint32_t *crc, const uint32_t *isize,
+                                 const uint32_t *crc_got, GzVerdict *v)
+{
+    for (uint64_t m = 0; m < nm; m++) {
+        const uint32_t len = (uint32_t)(text_off[m + 1] - text_off[m]);
+        const int32_t why = len > isize[m] ? BZ_OUTPUT_LONG : len < isize[m] ? BZ_OUTPUT_SHORT : crc_got[m] != crc[m] ? BZ_CRC : BZ_OK;
+        if (why != BZ_OK) { v->reason = why; v->member = m; v->in_pos = in_off[m]; return why; }
+    }
     return BZ_OK;
 }
 

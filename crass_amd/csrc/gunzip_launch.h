@@ -21,13 +21,24 @@ struct GzJob {
     uint8_t *out;           // the text, device pointer, any alignment
     uint32_t *crc_part;     // [n_chain] every element's own CRC-32
     unsigned long long *verdict;      // the first chain element that holds an unresolved marker, kBzNoOffence before the launch
+    // members mode (NULL / 0 otherwise)
+    uint32_t *n_ends; uint64_t *last_end;      // per chunk [G.nc], from count
+    const uint64_t *slot;   // [n_chain + 1] where an element's GzEnd records start
+    const uint64_t *m0;     // [n_chain] the text offset of the start of the member that holds the element's first byte
+    GzEnd *ends;            // [slot[n_chain]]
+    uint64_t n_pieces;
+    const uint64_t *piece;  // [n_pieces + 1] the text cut at member boundaries and every kGzCrcPiece bytes inside a member
+    uint32_t *crc_piece;    // [n_pieces]
 };
-hipError_t launch_gz_find(const GzJob &J, hipStream_t st);
-hipError_t launch_gz_count(const GzJob &J, hipStream_t st);
-hipError_t launch_gz_decode(const GzJob &J, hipStream_t st);
+// members: the kernels of members mode (k_gz_*_members)
+hipError_t launch_gz_find(const GzJob &J, hipStream_t st, bool members = false);
+hipError_t launch_gz_count(const GzJob &J, hipStream_t st, bool members = false);
+hipError_t launch_gz_decode(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_windows(const GzJob &J, hipStream_t st);
-hipError_t launch_gz_narrow(const GzJob &J, hipStream_t st);
+hipError_t launch_gz_narrow(const GzJob &J, hipStream_t st, bool members = false);
+hipError_t launch_gz_member_crc(const GzJob &J, hipStream_t st);
 // gunzip.cpp: what the rule decided, for the caller
 int gz_plan_fill(crass_gzip_plan *plan, uint64_t nc, const uint64_t *start, const uint32_t *link, const uint64_t *text_len, uint64_t n_chain);
+int gz_members_fill(crass_gzip_members *m, uint64_t nm, const uint64_t *in_off, const uint64_t *text_off);
 
 } // namespace crass

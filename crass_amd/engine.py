@@ -351,6 +351,58 @@ def gzip_inflate_host(buf, chunk_bytes=0, out_cap=None, with_plan=False):
     return (out, plan) if with_plan else out
 
 
+class GzipMembers:
+    """The members of a plain gzip file (crass_gzip_members), as numpy copies: n_members, in_off (uint64 [n + 1]: the file byte of
+    each member's header, in_off[n] the file's size) and text_off (uint64 [n + 1]: member m is text[text_off[m] : text_off[m + 1]])."""
+
+    def __init__(self, v):
+        n = int(v.n_members)
+        self.n_members = n
+        self.in_off = _np(v.in_off, n + 1, np.uint64).copy() if v.in_off else np.zeros(0, np.uint64)
+        self.text_off = _np(v.text_off, n + 1, np.uint64).copy() if v.text_off else np.zeros(0, np.uint64)
+
+
+def gzip_inflate_members_host(buf, chunk_bytes=0, out_cap=None, with_plan=False):
+    """gzip_inflate_host for a plain gzip file of any number of members (crass_gzip_inflate_members_host): a uint8 array, with
+    with_plan (text, GzipPlan, GzipMembers).  Raises as gzip_inflate_host does; for reasons 7 / 8 / 9 the verdict's `member` is the
+    gzip member and `in_pos` the file byte of its header."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    ptr = a.ctypes.data if len(a) else None
+    fn = "crass_gzip_inflate_members_host"
+    n_text, ver, pc, mc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC(), _abi.GzipMembersC()
+    try:
+        st = lib.crass_gzip_inflate_members_host(ptr, len(a), int(chunk_bytes), None, 0, C.byref(n_text), C.byref(pc), None, C.byref(ver))
+        plan = GzipPlan(pc)
+    finally:
+        lib.crass_gzip_plan_free(C.byref(pc))
+    if st == 2:
+        e = BgzfDeclined(st, fn, ver)
+        e.plan = plan
+        raise e
+    if st not in (0, 8):
+        _chk(st, fn)
+    cap = int(n_text.value) if out_cap is None else int(out_cap)
+    out = np.zeros(cap, np.uint8)
+    try:
+        st = lib.crass_gzip_inflate_members_host(ptr, len(a), int(chunk_bytes), out.ctypes.data if cap else None, cap, C.byref(n_text), None,
+                                                 C.byref(mc), C.byref(ver))
+        members = GzipMembers(mc)
+    finally:
+        lib.crass_gzip_members_free(C.byref(mc))
+    if st == 2:
+        e = BgzfDeclined(st, fn, ver)
+        e.plan = plan
+        raise e
+    if st == 8:
+        e = CrassError(st, fn)
+        e.n_text, e.out = int(n_text.value), out
+        raise e
+    _chk(st, fn)
+    out = out[:int(n_text.value)]
+    return (out, plan, members) if with_plan else out
+
+
 class FastxFilesLayout:
     """Several files as one read set (crass_fastx_files_layout), as numpy copies: n_files, n_reads, max_len, file_read_base /
     file_byte_base (uint64, n_files + 1; byte bases and rec_pos are ARENA positions: every file's text with a "\\n" behind it),
@@ -900,6 +952,54 @@ class SearchEngine:
         _chk(st, "crass_hip_inflate_gzip_device")
         return (int(n_text.value), plan) if with_plan else int(n_text.value)
 
+    def inflate_gzip_members_device(self, tensor_in, tensor_out, chunk_bytes=0, with_plan=False):
+        """inflate_gzip_device for a plain gzip file of any number of members (crass_hip_inflate_gzip_members_device).  Returns the
+        bytes of text, with with_plan (n_text, GzipPlan, GzipMembers); raises as inflate_gzip_device does, with the verdict of
+        gzip_inflate_members_host."""
+        for t in (tensor_in, tensor_out):
+            if str(t.dtype) != "torch.uint8" or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("inflate_gzip_members_device needs contiguous uint8 device tensors")
+        fn = "crass_hip_inflate_gzip_members_device"
+        n_text, ver, pc, mc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC(), _abi.GzipMembersC()
+        try:
+            st = self.lib.crass_hip_inflate_gzip_members_device(self.h, int(tensor_in.data_ptr()) if tensor_in.numel() else None,
+                                                                int(tensor_in.numel()), int(chunk_bytes),
+                                                                int(tensor_out.data_ptr()) if tensor_out.numel() else None,
+                                                                int(tensor_out.numel()), C.byref(n_text), C.byref(pc), C.byref(mc), C.byref(ver))
+            plan, members = GzipPlan(pc), GzipMembers(mc)
+        finally:
+            self.lib.crass_gzip_plan_free(C.byref(pc))
+            self.lib.crass_gzip_members_free(C.byref(mc))
+        if st == 2:
+            e = BgzfDeclined(st, fn, ver)
+            e.plan = plan
+            raise e
+        if st == 8:
+            e = CrassError(st, fn)
+            e.n_text, e.plan = int(n_text.value), plan
+            raise e
+        _chk(st, fn)
+        return (int(n_text.value), plan, members) if with_plan else int(n_text.value)
+
+    def load_fastx_gzip_members(self, buf, pad_uniform=2, read_index_base=0, keep=None, with_members=False):
+        """load_fastx_gzip for a plain gzip file of any number of members (crass_hip_load_fastx_gzip_members); with with_members
+        (layout, GzipMembers)."""
+        a = _bytes_arg(buf)
+        if keep is not None and (str(keep.dtype) != "torch.uint8" or not keep.is_cuda or not keep.is_contiguous()):
+            raise ValueError("load_fastx_gzip_members(keep=...) needs a contiguous uint8 device tensor")
+        v, ver, mc = _abi.FastxLayoutC(), _abi.BgzfVerdict(), _abi.GzipMembersC()
+        try:
+            st = self.lib.crass_hip_load_fastx_gzip_members(self.h, a.ctypes.data if len(a) else None, len(a), int(pad_uniform), int(read_index_base),
+                                                            int(keep.data_ptr()) if keep is not None and keep.numel() else None,
+                                                            int(keep.numel()) if keep is not None else 0, C.byref(v), C.byref(mc), C.byref(ver))
+            members = GzipMembers(mc)
+        finally:
+            self.lib.crass_gzip_members_free(C.byref(mc))
+        if st == 2 and ver.reason:
+            raise BgzfDeclined(st, "crass_hip_load_fastx_gzip_members", ver)
+        lay = self._fastx_result(st, v, "crass_hip_load_fastx_gzip_members")
+        return (lay, members) if with_members else lay
+
     def load_fastx_gzip(self, buf, pad_uniform=2, read_index_base=0, keep=None):
         """The bytes of a plain gzip FASTA / FASTQ file in host memory: inflated chunk by chunk, scanned and packed on the device
         (crass_hip_load_fastx_gzip), the mirror of load_fastx_bgzf."""
@@ -914,9 +1014,10 @@ class SearchEngine:
             raise BgzfDeclined(st, "crass_hip_load_fastx_gzip", ver)
         return self._fastx_result(st, v, "crass_hip_load_fastx_gzip")
 
-    def set_gzip_on_device(self, on=True):
-        """load_fastx_files takes a plain gzip file on a BGZF file's terms (crass_hip_set_gzip_on_device); default off."""
-        _chk(self.lib.crass_hip_set_gzip_on_device(self.h, 1 if on else 0), "crass_hip_set_gzip_on_device")
+    def set_gzip_on_device(self, on=True, members=False):
+        """load_fastx_files takes a plain gzip file on a BGZF file's terms (crass_hip_set_gzip_on_device); default off.  members:
+        plain gzip of any number of members (CRASS_GZIP_ON_DEVICE_MEMBERS), else single-member files only."""
+        _chk(self.lib.crass_hip_set_gzip_on_device(self.h, (2 if members else 1) if on else 0), "crass_hip_set_gzip_on_device")
 
     def last_gzip_ms(self):
         """HIP-event milliseconds of the last gzip inflate's steps: dict find, count, decode, windows, narrow (stage timing >= 1, else 0)."""

@@ -693,8 +693,47 @@ int  crass_hip_inflate_gzip_device(crass_hip_ctx *ctx, const uint8_t *d_in, uint
  * found after the count step, nothing resident. */
 int  crass_hip_load_fastx_gzip(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
                                uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v);
-/* on != 0: crass_hip_load_fastx_files takes a plain gzip file on the terms of a BGZF one (inflated on the device into the arena).
- * Default off: such a file is declined with reason 10.  (No reference counterpart.) */
+/* ---- plain gzip of SEVERAL members (cat of .gz files, gzip's >>, a compressor that starts a member every N records) ----
+ * replaces: gzread (SeqUtils.cpp:100-126), which reads such a file as one stream.  The rule above in members mode (gunzip_core.h):
+ * chunks are cut over everything between the first header and the file's last 8 bytes, a run goes on past a final block through
+ * the inner trailer and the next member's header, member starts are chunk starts too, no match reaches over a member boundary, and
+ * every member is accepted only with its own ISIZE and CRC-32 (k_gz_member_crc) — checked behind the decode step, since inner
+ * trailers are only met by the runs.  A single-member file gives the plan of the single-member calls; those calls are unchanged and
+ * go on declining further members with reason 13.
+ * Verdicts: reasons 1 .. 6 and 11 .. 14 met by a run or by narrowing name the CHUNK (the first in text order) and the file byte that
+ * holds its start, as above; 7 / 8 / 9 name the gzip MEMBER (the first offending one, 7 / 8 before 9 within a member) and the file
+ * byte of its header; 11 for the file's first header: member 0, in_pos 0.  At an inner header: 13 without the magic or with fewer
+ * than 18 bytes up to the file's end; 11 for the magic with a header the rule does not take or that runs into the file's last 8
+ * bytes; 14 for a distance that reaches in front of its own member.
+ * Three deliberate differences from gzread: bytes behind the last member that are no gzip header (zero padding included) are
+ * declined (13) where zlib ignores them; stored-only or fixed-only data needs a chunk start every 32 chunks (12: take a larger
+ * chunk_bytes) where zlib takes any size; an inner header beyond the input a chunk's run may read is declined (12). */
+typedef struct {
+    uint64_t n_members;
+    uint64_t *in_off;                      /* [n_members+1] file byte of each member's header, in_off[n_members] = n_bytes */
+    uint64_t *text_off;                    /* [n_members+1] member m inflates to text[text_off[m] .. text_off[m+1]) */
+} crass_gzip_members;
+void crass_gzip_members_free(crass_gzip_members *m);
+/* crass_gzip_inflate_host in members mode: the same overflow and argument protocol; members (may be NULL) is filled when the file is
+ * accepted, its arrays are malloc'd: crass_gzip_members_free. */
+int  crass_gzip_inflate_members_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap,
+                                     uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v);
+/* crass_hip_inflate_gzip_device in members mode: results as crass_gzip_inflate_members_host, text, plan, members and verdict field
+ * for field.  Further scratch: 24 bytes per member and 4 per 64 KB piece of text. */
+int  crass_hip_inflate_gzip_members_device(crass_hip_ctx *ctx, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out,
+                                           uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members,
+                                           crass_bgzf_verdict *v);
+/* the mirror of crass_hip_load_fastx_gzip for a file of any number of members; members (may be NULL) as above.  Members may end
+ * anywhere in the text (in the middle of a record): the text as a whole is what is scanned. */
+int  crass_hip_load_fastx_gzip_members(crass_hip_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
+                                       uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_gzip_members *members,
+                                       crass_bgzf_verdict *v);
+/* crass_hip_load_fastx_files takes a plain gzip file on the terms of a BGZF one (inflated on the device into the arena): OFF (the
+ * default) such a file is declined with reason 10; ONE_MEMBER takes a single-member file and declines further members (13); MEMBERS
+ * takes plain gzip of any number of members.  Any other non-zero value is ONE_MEMBER.  (No reference counterpart.) */
+#define CRASS_GZIP_ON_DEVICE_OFF        0
+#define CRASS_GZIP_ON_DEVICE_ONE_MEMBER 1
+#define CRASS_GZIP_ON_DEVICE_MEMBERS    2
 int  crass_hip_set_gzip_on_device(crass_hip_ctx *ctx, int on);
 /* HIP-event milliseconds of the last gzip inflate's five steps, ms[0 .. 5): find, count, decode, windows, narrow; measured when the
  * stage timing level is >= 1, else 0.  crass_hip_last_inflate_ms holds their sum.  (No reference counterpart.) */

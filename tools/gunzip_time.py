@@ -10,6 +10,9 @@ One input held in memory (and written once to a scratch file for the reader that
   (b) SearchEngine.load_fastx_gzip (default chunk size): wall seconds from host bytes to resident packed reads, and its parts
   (c) crass_index_fastx on the same .gz: the host's several-thread inflate + parse + pack (CRASS_TIMING=1 prints its stage times
       to stderr), then crass_hip_load_reads
+  (d) SearchEngine.inflate_gzip_members_device (members mode, default chunk size) on the same text as ONE member and as 16 members
+      of equal text size: wall seconds, the five event times (narrow's includes k_gz_member_crc and the round trip in front of
+      it), the chain's shape and the number of members
 Output: stdout and profiles/gunzip_mi355x.txt (--out)."""
 import argparse
 import os
@@ -72,6 +75,29 @@ def main():
                 best = (kb, med(wall))
         say("    fastest: %d KB" % best[0])
         assert bytes(d_out[:1 << 20].cpu().numpy()) == text[:1 << 20] and bytes(d_out[-(1 << 20):].cpu().numpy()) == text[-(1 << 20):]
+        # (d) members mode: the file above as it is, and the same text cut into 16 members
+        per = (len(text) + 15) // 16
+        def member(t):
+            co = zlib.compressobj(6, zlib.DEFLATED, 31)
+            return co.compress(t) + co.flush()
+        sixteen = b"".join(member(text[at:at + per]) for at in range(0, len(text), per))
+        for label, blob in (("1 member", None), ("16 members", sixteen)):
+            d_m = d_in if blob is None else torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to("cuda")
+            n, plan, members = e.inflate_gzip_members_device(d_m, d_out, 0, with_plan=True)      # warm
+            assert n == len(text)
+            wall, parts = [], {k: [] for k in STEPS}
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.inflate_gzip_members_device(d_m, d_out, 0)
+                wall.append(time.perf_counter() - t0)
+                for k, v in e.last_gzip_ms().items():
+                    parts[k].append(v / 1e3)
+            say("(d) members mode, %s: %d chunks, %d on the chain, %d members; wall %.3f s (%.2f GB of text per second); kernels %s" %
+                (label, plan.n_chunks, plan.n_chain, members.n_members, med(wall), len(text) / 1e9 / med(wall),
+                 " + ".join("%s %.3f" % (k, med(parts[k])) for k in STEPS)))
+            assert bytes(d_out[:1 << 20].cpu().numpy()) == text[:1 << 20] and bytes(d_out[-(1 << 20):].cpu().numpy()) == text[-(1 << 20):]
+            del d_m
         del d_in, d_out
         torch.cuda.empty_cache()
         e.load_fastx_gzip(arr)

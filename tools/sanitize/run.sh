@@ -52,3 +52,8 @@ grep -c "^ok  " $out/report.txt; grep "^DIFF" $out/report.txt | head; grep -c "E
 g++ -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Iinclude crass_amd/csrc/ingest.cpp crass_amd/csrc/pgzip.cpp tools/sanitize/ingest_main.cpp -o $out/ingest_tsan -lz -ldl -lpthread
 $out/ingest_tsan $out/s00*.txt $out/s01*.gz $out/s03*.txt $out/big.gz $out/big.bgzf.gz > $out/report_tsan.txt 2> $out/tsan.txt || true
 echo "tsan: $(grep -c '^ok  ' $out/report_tsan.txt) files ok, $(grep -c 'WARNING: ThreadSanitizer' $out/tsan.txt || true) warnings"
+# the plain-gzip host rule in members mode (gunzip.cpp, gunzip_core.h) over the sets of tests/gzip_member_sets.py, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/gunzip.cpp tools/sanitize/gzip_members_main.cpp -o $out/gzip_members_asan
+python3 tools/sanitize/gzip_members_dump.py $out/members > /dev/null
+$out/gzip_members_asan $out/members/* > $out/report_members.txt 2> $out/sanitizer_members.txt || true
+echo "gzip members: $(tail -1 $out/report_members.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_members.txt || true) sanitizer reports"
