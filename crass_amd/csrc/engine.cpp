@@ -3588,7 +3588,11 @@ static int install_patterns(crass_hip_ctx *c, const StringArena &pats)
     c->dm.active = false;                               // the installed set is the host-built one from here on
     c->cnt.n_patterns = (uint32_t)pats.size();
     if (pats.empty()) { c->cnt.ac_states = 0; return CRASS_OK; }
-    for (size_t i = 0; i < pats.size(); i++) if (pats.len(i) == 0 || pats.len(i) > 255) return CRASS_ERR_UNSUPPORTED;
+    // a recruit's DR string lives in a slot of dr_stride bytes (d_dr, h_dr, q_dr: ensure_recruit_buffers, k_recruit_finish, the
+    // host sink), so a longer pattern is declined here, before anything is uploaded; have_patterns stays false and a recruit
+    // that follows returns CRASS_ERR_STATE
+    for (size_t i = 0; i < pats.size(); i++)
+        if (pats.len(i) == 0 || pats.len(i) > 255 || pats.len(i) > c->dr_stride) return CRASS_ERR_UNSUPPORTED;
     HostAutomaton &H = c->H;
     HostAnchors HK;
     const bool prof = c->env.merge_profile;

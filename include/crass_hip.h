@@ -270,7 +270,13 @@ void crass_merge_destroy(crass_merge_handle *h);
 
 /* ---- pass 2 : findSingletons / on_match (libcrispr.cpp:399-518) ---- */
 /* replaces: refsplit + acism_create (libcrispr.cpp:452-469).  Optional: merge() already
- * installed the non-redundant set; use this to recruit with an explicit pattern list.     */
+ * installed the non-redundant set; use this to recruit with an explicit pattern list.
+ * A pattern is 1 .. min(255, dr_stride) bytes long, dr_stride = highDRsize rounded up to a
+ * multiple of 16 (crass_recruits.dr_stride: the slot a recruit's DR string is returned in;
+ * 48 with the default parameters).  A set holding an empty or a longer pattern is declined
+ * as a whole with CRASS_ERR_UNSUPPORTED before anything is installed: the context then has
+ * no pattern set, and crass_hip_recruit returns CRASS_ERR_STATE until a valid one is given.
+ * An empty list (n = 0) is valid: crass_hip_recruit then recruits nothing.                   */
 int crass_hip_set_patterns(crass_hip_ctx *ctx, const char *const *patterns,
                            const uint32_t *lengths, uint32_t n);
 /* replaces: the acism_scan loop.  Reads whose header was found in pass 1 (readsFound,

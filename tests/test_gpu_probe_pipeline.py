@@ -108,6 +108,90 @@ def test_last_windows_of_a_uniform_read(ca, L):
     assert all(i in got for i in want) and not any(i in got for i in cut)
 
 
+def designed_copies(ca, L, n_base, offsets, kw=None, synth_kw=None):
+    """The construction of test_last_windows_of_a_uniform_read for any read length and option set, the probe at its default grid:
+    a synthetic base set, then designed reads — random but for one copy of a repeat pass 1 found in the base set, at every
+    offset offsets(L, len(repeat)) gives (recruited), and one with the copy's last base cut off at the read's end (not
+    recruited).  The whole pipeline against the oracle, and the preconditions of the existing test: `want` all recruited by the
+    oracle, `cut` none, the table built on the device."""
+    kw = kw or {}
+    low = kw.get("lowDRsize", 23)
+    rng = random.Random(L * 131 + low)
+    synth_kw = synth_kw or dict(dr_len_min=23, dr_len_max=27)
+    base = synth_reads(ca, n_base, read_len=L, crispr_per_million=150000, **synth_kw)
+    p = ca.default_params(**kw)
+    op = to_orc_params(p)
+    ref0 = orc.pipeline(base, params=op, do_pass2=False)
+    pats = [bytes(x) for x in ref0.patterns]
+    toks = sorted({bytes(t) for t in ref0.tokens if bytes(t) in pats}, key=lambda t: (len(t), t))
+    assert toks and len(toks[0]) <= low + 1, "the set must hold short repeats: only they can sit in the last window"
+    picked = toks[:6] + toks[-2:]
+    seqs, want, cut = list(base), [], []
+    for t in picked:
+        for o in offsets(L, len(t)):
+            assert 0 <= o and o + len(t) <= L
+            s = _filler(rng, o) + t + _filler(rng, L - o - len(t))
+            want.append(len(seqs)); seqs.append(s)
+        s = _filler(rng, L - len(t) + 1) + t[:-1]
+        if not any(q in s for q in pats):
+            cut.append(len(seqs)); seqs.append(s)
+    assert want and cut
+    ref = orc.pipeline(seqs, params=op)
+    recruited = set(int(r) for r in ref.rec_read[ref.n_pass1:ref.n_pass1 + ref.n_pass2])
+    assert all(i in recruited for i in want) and not any(i in recruited for i in cut)
+    gpu = ca.search_pipeline(seqs, params=p)
+    assert_same_pipeline(gpu, ref)
+    got = set(int(r) for r in gpu.rec_read[gpu.n_pass1:gpu.n_pass1 + gpu.n_pass2])
+    assert all(i in got for i in want) and not any(i in got for i in cut)
+    assert gpu.counters["used_device_merge"] == 1
+    return gpu
+
+
+def _ends(L, n):
+    return [L - n - back for back in range(0, 9)]      # the copy ends 0 .. 8 bases before the read's end
+
+
+@pytest.mark.parametrize("L", [64, 256, 257])
+def test_device_built_table_first_and_last_register_forms(ca, L):
+    """Rows of 4 and 16 words (the register form's first and last instantiations) and of 17 (the lane-per-read body, W = 0),
+    the table built on the device.  Copies at offsets 0 .. 8 and at the read's end.  Two repeats of 23 bases and a spacer of
+    26 do not fit into 64 bases, so pass 1 can find nothing in such reads under the default options: that case runs with
+    lowSpacerSize = 10 and spacers of 10 .. 14 bases."""
+    kw, skw = {}, None
+    if L == 64:
+        kw, skw = dict(lowSpacerSize=10), dict(dr_len_min=23, dr_len_max=25, spacer_len_min=10, spacer_len_max=14)
+    designed_copies(ca, L, 3000, lambda L, n: list(range(0, 9)) + _ends(L, n), kw, skw)
+
+
+def _round_edge(L, n, first, step):
+    """copies whose window is the last of the wave walk's first round and the first of its second, where they fit, and copies at
+    the read's end (windows h_max and h_max - 1)"""
+    return [o for o in range(first, first + 2 * step) if o + n <= L] + _ends(L, n)
+
+
+@pytest.mark.parametrize("L", [2056, 2063, 2064])
+def test_device_built_table_wave_walk(ca, L):
+    """Reads over 800 bases: a wave walks a read, 256 windows a round.  h_max = (L - 16) >> 3 is 255, 255, 256: the read's
+    last window is the first round's last, or a second round's only one.  Copies at 2 033 .. 2 048 (windows 255 and 256)
+    and at the read's end."""
+    designed_copies(ca, L, 1500, lambda L, n: _round_edge(L, n, 2033, 8))
+
+
+@pytest.mark.parametrize("kw,skw", [(dict(lowDRsize=20, highDRsize=40), dict(dr_len_min=20, dr_len_max=26)),
+                                    (dict(lowDRsize=15, searchWindowLength=8), dict(dr_len_min=15, dr_len_max=21))],
+                         ids=["ASH=2", "KL=12"])
+def test_device_built_table_wave_walk_windows_every_four_bases(ca, kw, skw):
+    """Windows every 4 bases: a round is 512 windows = 2 048 bases.  L = 2 080: h_max = (L - KL) >> 2 is 516 (keys of 16 bases)
+    and 517 (keys of 12: one more window at the read's end).  Copies at 2 041 .. 2 048 (windows 511 and 512, either side of
+    the round's end) and ending 0 .. 8 bases before the read's end (windows h_max - 3 .. h_max)."""
+    L = 2080
+    KL = 12 if kw["lowDRsize"] < 19 else 16
+    assert (L - KL) >> 2 == (517 if KL == 12 else 516)
+    skw = dict(skw, n_dr=40, spacer_len_min=26, spacer_len_max=34)
+    gpu = designed_copies(ca, L, 1500, lambda L, n: _round_edge(L, n, 2041, 4), kw, skw)
+    assert gpu.n_pass2 > 0
+
+
 def test_per_read_lengths_exception_reads_and_duplicate_headers(ca):
     """The construction of test_gpu_parity's ragged test at 3 000 reads, padded to one stride: per-read lengths (requested a tile
     ahead), header ids (two tiles ahead) whose found flag belongs to a read of another tile, exception reads."""
