@@ -71,6 +71,7 @@ class DistinctDev(C.Structure):
 
 
 ERR_OVERFLOW = 8          # CRASS_ERR_OVERFLOW (include/crass_hip.h)
+NAME_NOT_FOUND = 2 ** 64 - 1     # CRASS_NAME_NOT_FOUND
 
 
 class Exchange(C.Structure):
@@ -197,6 +198,11 @@ SYMBOLS = {
     "crass_fastx_header_ids": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fastx_header_ids_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "crass_hip_last_header_ids_ms": (C.c_float, [C.c_void_p, C.c_int]),
+    "crass_fastx_find_names": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fastx_names_build_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "crass_hip_fastx_names_find": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fastx_names_drop": (C.c_int, [C.c_void_p]),
+    "crass_hip_last_names_ms": (C.c_float, [C.c_void_p, C.c_int]),
     "crass_hip_fetch_header_lines_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_hip_fetch_header_lines_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "crass_hip_fastx_tile_bytes": (C.c_uint32, []),

@@ -308,6 +308,16 @@ struct crass_hip_ctx {
     PinBuf<uint64_t> n_h_ctl;
     hipEvent_t ev_n_time[3] = {nullptr, nullptr, nullptr};
     float last_hid_ms[3] = {0, 0, 0};        // whole call's kernels, the insert launches, the lookup launch
+    // crass_hip_fastx_names_build_device: the same table and record positions, KEPT until crass_hip_fastx_names_drop, the next
+    // build or destroy (built on the arena: also until the next load or attach, drop_arena); the bytes are the caller's or the
+    // arena's.  crass_hip_fastx_names_find: the queries, their offsets, the list of long ones and the answers on the device — given
+    // back before the call returns; the events and times of crass_hip_last_names_ms
+    DevBuf<unsigned long long> nt_table; DevBuf<uint64_t> nt_rec_pos;
+    bool have_names = false, nt_on_arena = false;
+    const uint8_t *nt_bytes = nullptr; uint64_t nt_n_bytes = 0, nt_n_reads = 0, nt_mask = 0;
+    DevBuf<uint8_t> nq_names; DevBuf<uint64_t> nq_off, nq_out; DevBuf<uint32_t> nq_long;
+    hipEvent_t ev_nq_time[2] = {nullptr, nullptr};
+    float last_names_ms[2] = {0, 0};         // the last build's insert launches, the last find's kernels
     // crass_hip_fetch_header_lines_device: the records' first bytes, lengths (line, then name), offsets and the lines on the
     // device (given back before the call returns) and their pinned host sides (hl_h_off and hl_h_chars are what crass_text points at)
     DevBuf<uint64_t> hl_src, hl_off; DevBuf<uint32_t> hl_len; DevBuf<uint8_t> hl_chars;
@@ -929,6 +939,8 @@ void crass_hip_destroy(crass_hip_ctx *c)
     for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
     c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_ctl.release(); c->n_long.release(); c->n_h_ctl.release();
     for (auto &e : c->ev_n_time) if (e) (void)hipEventDestroy(e);
+    c->nt_table.release(); c->nt_rec_pos.release(); c->nq_names.release(); c->nq_off.release(); c->nq_out.release(); c->nq_long.release();
+    for (auto &e : c->ev_nq_time) if (e) (void)hipEventDestroy(e);
     c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
     c->hl_h_src.release(); c->hl_h_off.release(); c->hl_h_len.release(); c->hl_h_chars.release();
     c->fa_arena.release(); c->fa_h_base.release(); c->fa_h_format.release();
@@ -1057,8 +1069,15 @@ static void presize_hostloop(crass_hip_ctx *c);
 
 // the file arena of crass_hip_load_fastx_files goes with the read set it belongs to: every public load and attach calls this
 // (load_text_impl, the pack step those calls share with crass_hip_load_fastx_files itself, does not)
+static void names_drop(crass_hip_ctx *c)
+{
+    if (c->nt_table.p || c->nt_rec_pos.p) { (void)hipStreamSynchronize(c->stream); c->nt_table.release(); c->nt_rec_pos.release(); }
+    c->have_names = false; c->nt_on_arena = false; c->nt_bytes = nullptr; c->nt_n_bytes = c->nt_n_reads = c->nt_mask = 0;
+}
+
 static void drop_arena(crass_hip_ctx *c)
 {
+    if (c->have_names && c->nt_on_arena) names_drop(c);      // (a name table built on the arena refers to its bytes)
     if (c->fa_arena.p) { (void)hipStreamSynchronize(c->stream); c->fa_arena.release(); }
     c->have_arena = false; c->fa_bytes = 0;
 }
@@ -1951,22 +1970,23 @@ int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
 // ---- header ids from a file's raw bytes on the device (fastx_names.hip) ----
 // Every check that needs no byte of the file comes first; a record position outside the input is seen by the insert launch and
 // reported before the lookup launch and before anything is installed.
-static int header_ids_device_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
-                                  uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
+// the insert step, shared by the header ids (the table is scratch) and crass_hip_fastx_names_build_device (the table is kept):
+// table and d_rec_pos are the two arrays that make a table, the slots per record, the list of long names and the control words
+// are the context's scratch.  Queued on return: both insert launches; ev_n_time[0] / [1] lie around them when timed.
+static int names_insert_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
+                             DevBuf<unsigned long long> &table, DevBuf<uint64_t> &d_rec_pos, HidJob &J)
 {
-    (void)hipSetDevice(c->device);
-    for (auto &m : c->last_hid_ms) m = 0;
     uint64_t slots = 2;
     while (slots < 2 * n) slots <<= 1;
-    HIPCHK(c, c->n_rec_pos.ensure(n)); HIPCHK(c, c->n_ids.ensure(n)); HIPCHK(c, c->n_long.ensure(n));
-    HIPCHK(c, c->n_ctl.ensure(4)); HIPCHK(c, c->n_h_ctl.ensure(4)); HIPCHK(c, c->n_table.ensure(slots));
-    HidJob J{};
-    J.bytes = d_bytes; J.n_bytes = n_bytes; J.rec_pos = c->n_rec_pos.p; J.n_reads = n;
-    J.table = c->n_table.p; J.mask = slots - 1; J.hash_bits = c->env.hid_hash_bits;
+    HIPCHK(c, d_rec_pos.ensure(n)); HIPCHK(c, c->n_ids.ensure(n)); HIPCHK(c, c->n_long.ensure(n));
+    HIPCHK(c, c->n_ctl.ensure(4)); HIPCHK(c, c->n_h_ctl.ensure(4)); HIPCHK(c, table.ensure(slots));
+    J = HidJob{};
+    J.bytes = d_bytes; J.n_bytes = n_bytes; J.rec_pos = d_rec_pos.p; J.n_reads = n;
+    J.table = table.p; J.mask = slots - 1; J.hash_bits = c->env.hid_hash_bits;
     J.ids = c->n_ids.p; J.long_list = c->n_long.p;
     J.ctl = reinterpret_cast<uint32_t *>(c->n_ctl.p); J.n_repeated = reinterpret_cast<unsigned long long *>(c->n_ctl.p + 2);
-    HIPCHK(c, hipMemcpyAsync(c->n_rec_pos.p, rec_pos, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->n_table.p, 0xFF, slots * 8, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_rec_pos.p, rec_pos, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(table.p, 0xFF, slots * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->n_ctl.p, 0, 32, c->stream));
     const bool timed = c->timing_level >= 1;
     if (timed) {
@@ -1980,6 +2000,18 @@ static int header_ids_device_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint
     if (h_ctl[1]) return CRASS_ERR_INVALID_ARG;         // a rec_pos[r] >= n_bytes
     if (h_ctl[0]) HIPCHK(c, launch_hid_insert_long(J, h_ctl[0], c->stream));
     if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[1], c->stream));
+    return CRASS_OK;
+}
+
+static int header_ids_device_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
+                                  uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
+{
+    (void)hipSetDevice(c->device);
+    for (auto &m : c->last_hid_ms) m = 0;
+    HidJob J{};
+    const int ins = names_insert_impl(c, d_bytes, n_bytes, rec_pos, n, c->n_table, c->n_rec_pos, J);
+    if (ins) return ins;
+    const bool timed = c->timing_level >= 1;
     HIPCHK(c, launch_hid_lookup(J, c->stream));
     if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[2], c->stream));
     HIPCHK(c, hipMemcpyAsync(c->n_h_ctl.p + 2, c->n_ctl.p + 2, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2023,6 +2055,105 @@ int crass_hip_fastx_header_ids_device(crass_hip_ctx *c, const uint8_t *d_bytes, 
 }
 
 float crass_hip_last_header_ids_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 3 ? c->last_hid_ms[part] : 0.0f; }
+
+// ---- the name table kept on the device: names in, first read index out (fastx_names.hip) ----
+// The table is built aside and replaces the one before only when the insert step accepted every record position: a build that
+// fails leaves the context as it was.
+static int names_build_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
+                            DevBuf<unsigned long long> &table, DevBuf<uint64_t> &d_rec_pos, uint64_t *mask_out)
+{
+    HidJob J{};
+    const int ins = names_insert_impl(c, d_bytes, n_bytes, rec_pos, n, table, d_rec_pos, J);
+    if (ins) return ins;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->timing_level >= 1) HIPCHK(c, hipEventElapsedTime(&c->last_names_ms[0], c->ev_n_time[0], c->ev_n_time[1]));
+    *mask_out = J.mask;
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_names_build_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    const bool on_arena = !d_bytes && !rec_pos;
+    if (on_arena) {                                     // the arena and layout of the last crass_hip_load_fastx_files
+        if (!c->have_arena || !c->have_reads) return CRASS_ERR_STATE;
+        d_bytes = c->fa_arena.p; n_bytes = c->fa_bytes; rec_pos = c->x_h_rec_pos.p; n_reads = c->R.n_reads;
+    }
+    if (n_reads && (!d_bytes || !rec_pos)) return CRASS_ERR_INVALID_ARG;
+    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (a slot holds a 32-bit index, all-ones is the free slot's)
+    (void)hipSetDevice(c->device);
+    c->last_names_ms[0] = 0;
+    DevBuf<unsigned long long> table; DevBuf<uint64_t> d_rec_pos;
+    uint64_t mask = 0;
+    const int s = n_reads ? names_build_impl(c, d_bytes, n_bytes, rec_pos, n_reads, table, d_rec_pos, &mask) : CRASS_OK;
+    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out
+    c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
+    if (s) { table.release(); d_rec_pos.release(); return s; }
+    names_drop(c);
+    c->nt_table = table; c->nt_rec_pos = d_rec_pos;     // (DevBuf owns nothing by itself: the context's release gives them back)
+    c->have_names = true; c->nt_on_arena = on_arena;
+    c->nt_bytes = d_bytes; c->nt_n_bytes = n_bytes; c->nt_n_reads = n_reads; c->nt_mask = mask;
+    return CRASS_OK;
+}
+
+static int names_find_impl(crass_hip_ctx *c, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, const std::vector<uint32_t> &longs,
+                           uint64_t *first_out)
+{
+    const uint64_t total = name_off[n_names];
+    HIPCHK(c, c->nq_names.ensure(total)); HIPCHK(c, c->nq_off.ensure(n_names + 1)); HIPCHK(c, c->nq_out.ensure(n_names));
+    HIPCHK(c, c->nq_long.ensure(longs.size()));
+    HidFindJob J{};
+    J.bytes = c->nt_bytes; J.n_bytes = c->nt_n_bytes; J.rec_pos = c->nt_rec_pos.p;
+    J.table = c->nt_table.p; J.mask = c->nt_mask; J.hash_bits = c->env.hid_hash_bits;
+    J.names = c->nq_names.p; J.name_off = c->nq_off.p; J.n_names = n_names; J.long_list = c->nq_long.p; J.first_out = c->nq_out.p;
+    if (total) HIPCHK(c, hipMemcpyAsync(c->nq_names.p, names, total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->nq_off.p, name_off, (n_names + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (!longs.empty()) HIPCHK(c, hipMemcpyAsync(c->nq_long.p, longs.data(), longs.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const bool timed = c->timing_level >= 1;
+    if (timed) {
+        for (auto &e : c->ev_nq_time) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->ev_nq_time[0], c->stream));
+    }
+    HIPCHK(c, launch_hid_find(J, c->stream));
+    if (!longs.empty()) HIPCHK(c, launch_hid_find_long(J, (uint32_t)longs.size(), c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_nq_time[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(first_out, c->nq_out.p, n_names * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (timed) HIPCHK(c, hipEventElapsedTime(&c->last_names_ms[1], c->ev_nq_time[0], c->ev_nq_time[1]));
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_names_find(crass_hip_ctx *c, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out)
+{
+    if (!c || (n_names && (!name_off || !first_out))) return CRASS_ERR_INVALID_ARG;
+    for (uint64_t k = 0; k < n_names; k++) if (name_off[k + 1] < name_off[k]) return CRASS_ERR_INVALID_ARG;
+    if (n_names && name_off[n_names] && !names) return CRASS_ERR_INVALID_ARG;
+    if (n_names >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (the list of long queries holds 32-bit indices)
+    if (!c->have_names) return CRASS_ERR_STATE;
+    c->last_names_ms[1] = 0;
+    if (n_names == 0) return CRASS_OK;
+    if (c->nt_n_reads == 0) { for (uint64_t k = 0; k < n_names; k++) first_out[k] = CRASS_NAME_NOT_FOUND; return CRASS_OK; }
+    std::vector<uint32_t> longs;
+    try {
+        const uint64_t lane_end = hid_lane_end();
+        for (uint64_t k = 0; k < n_names; k++) if (name_off[k + 1] - name_off[k] >= lane_end) longs.push_back((uint32_t)k);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    (void)hipSetDevice(c->device);
+    const int s = names_find_impl(c, names, name_off, n_names, longs, first_out);
+    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out; the table stays
+    c->nq_names.release(); c->nq_off.release(); c->nq_out.release(); c->nq_long.release();
+    return s;
+}
+
+int crass_hip_fastx_names_drop(crass_hip_ctx *c)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    names_drop(c);
+    return CRASS_OK;
+}
+
+float crass_hip_last_names_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 2 ? c->last_names_ms[part] : 0.0f; }
 
 // ---- header lines of selected records from a file's raw bytes on the device (fastx_names.hip) ----
 // d_user == nullptr: the host route (the lines come back into pinned memory, *out points at it); else the caller's device buffer

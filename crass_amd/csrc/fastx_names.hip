@@ -19,6 +19,12 @@
 //                      fine: equal names have equal lengths, so both are hashed by the same kernel.
 //   k_hid_lookup       a launch of its own, so the table is final: ids[r] = the index in the record's slot — the smallest index
 //                      with that name, whatever the scheduling.  (The slot was kept at insert, so no name is read twice.)
+//   k_hid_find        names in, first index out, on a table that is kept (crass_hip_fastx_names_build_device): a lane per query.  The
+//                      query is a name that ends with its own bytes: it is hashed by the function k_hid_insert hashes with
+//                      (hid_hash_lane), then probed for linearly from the hash's slot — free slot: not found; other tag: next slot;
+//                      same tag: the query against the slot owner's name, lengths included; equal: the slot's index.  The table is
+//                      final and only read: no atomics, no waiting, and a probe that has seen every slot ends with not found.
+//   k_hid_find_long    a wave per query of kHidLaneEnd bytes or more, hashed as k_hid_insert_long hashes (hid_hash_wave).
 // No answer rests on a hash: hash_bits (CRASS_HID_TEST_HASH_BITS) cuts the hash to its low bits, down to none, for the tests.
 // Slot accesses are agent-scope atomics; the name bytes and rec_pos are read-only input.
 //
@@ -39,6 +45,7 @@ namespace crass {
 
 static constexpr int kNmThreads = 256;
 static constexpr uint32_t kHidLaneMax = 256;             // names beyond this many bytes go to the wave kernel
+static constexpr uint32_t kHidLaneEnd = kHidLaneMax + 4; // ... seen a dword at a time: names of this many bytes or more are the wave kernels'
 
 // the aligned dword at address q of the input [lo, hi); bytes outside the input read as 0 and are not touched
 static __device__ __forceinline__ uint32_t nm_ld4(uintptr_t lo, uintptr_t hi, uintptr_t q)
@@ -116,12 +123,12 @@ static __device__ __forceinline__ bool hid_claim(unsigned long long *p, unsigned
 }
 static __device__ __forceinline__ void hid_min(unsigned long long *p, unsigned long long mine) { (void)__hip_atomic_fetch_min(p, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// one lane: is the name at a the name at b?  (Both end at their first isspace() byte or the input's end; the walk ends with the
-// shorter of the two.)
-static __device__ __forceinline__ bool hid_same_name_lane(uintptr_t lo, uintptr_t hi, uint64_t a, uint64_t b)
+// one lane: is the name at a of the input [loa, hia) the name at b of [lob, hib)?  (Both end at their first isspace() byte or their
+// input's end; the walk ends with the shorter of the two.)
+static __device__ __forceinline__ bool hid_same_name_lane(uintptr_t loa, uintptr_t hia, uint64_t a, uintptr_t lob, uintptr_t hib, uint64_t b)
 {
     NmCur ca, cb;
-    ca.init(lo, hi, a); cb.init(lo, hi, b);
+    ca.init(loa, hia, a); cb.init(lob, hib, b);
     for (;;) {
         uint32_t ava, avb;
         const uint32_t wa = ca.next(&ava), wb = cb.next(&avb);
@@ -131,15 +138,12 @@ static __device__ __forceinline__ bool hid_same_name_lane(uintptr_t lo, uintptr_
     }
 }
 
-__global__ __launch_bounds__(kNmThreads) void k_hid_insert(const HidJob J)
+// one lane hashes the name at pos of the input [lo, hi): its length and its hash before the cut to hash_bits.  False: the name is
+// of kHidLaneEnd bytes or more, the wave kernels'.  (k_hid_insert and k_hid_find: the one function, so the two cannot drift.)
+static __device__ __forceinline__ bool hid_hash_lane(uintptr_t lo, uintptr_t hi, uint64_t pos, uint64_t *h_out, uint32_t *len_out)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
-    if (r >= J.n_reads) return;
-    const uint64_t pos = J.rec_pos[r];
-    if (pos >= J.n_bytes) { J.ctl[1] = 1u; J.ids[r] = kHidEmpty; return; }
-    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
     NmCur c;
-    c.init(lo, hi, pos + 1);
+    c.init(lo, hi, pos);
     uint64_t h = 0x9E3779B97F4A7C15ull;
     uint32_t len = 0;
     for (;;) {
@@ -149,12 +153,26 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_insert(const HidJob J)
         if (cnt) { h = (h ^ (w & nm_low_bytes(cnt))) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
         len += cnt;
         if (cnt < 4) break;
-        if (len > kHidLaneMax) {                        // the wave kernel's
-            J.long_list[atomicAdd(&J.ctl[0], 1u)] = (uint32_t)r;
-            return;
-        }
+        if (len > kHidLaneMax) return false;
     }
-    h = nm_cut(nm_fmix(h ^ len), J.hash_bits);
+    *h_out = nm_fmix(h ^ len); *len_out = len;
+    return true;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_insert(const HidJob J)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (r >= J.n_reads) return;
+    const uint64_t pos = J.rec_pos[r];
+    if (pos >= J.n_bytes) { J.ctl[1] = 1u; J.ids[r] = kHidEmpty; return; }
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    uint64_t h;
+    uint32_t len;
+    if (!hid_hash_lane(lo, hi, pos + 1, &h, &len)) {    // the wave kernel's
+        J.long_list[atomicAdd(&J.ctl[0], 1u)] = (uint32_t)r;
+        return;
+    }
+    h = nm_cut(h, J.hash_bits);
     const unsigned long long tag = h >> 32, mine = (tag << 32) | r;
     uint64_t s = h & J.mask;
     for (;;) {                                          // (ends: the table has more slots than there are records)
@@ -162,7 +180,7 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_insert(const HidJob J)
         if (cur == kHidEmpty && hid_claim(&J.table[s], mine, &cur)) break;
         if ((cur >> 32) == tag) {
             const uint64_t owner = cur & 0xFFFFFFFFull;
-            if (owner == r || hid_same_name_lane(lo, hi, pos + 1, J.rec_pos[owner] + 1)) {
+            if (owner == r || hid_same_name_lane(lo, hi, pos + 1, lo, hi, J.rec_pos[owner] + 1)) {
                 if (owner > r) hid_min(&J.table[s], mine);
                 break;
             }
@@ -187,18 +205,20 @@ static __device__ __forceinline__ uint64_t nm_wave_sum64(uint64_t v)
     return v;
 }
 
-// the wave: is the name of len bytes at a the name at b?  (The len bytes are equal and b's name ends behind them.)
-static __device__ __forceinline__ bool hid_same_name_wave(uintptr_t lo, uintptr_t hi, uint64_t a, uint64_t len, uint64_t b, uint32_t lane)
+// the wave: is the name of len bytes at a of the input [loa, hia) the name at b of [lob, hib)?  (The len bytes are equal and b's
+// name ends behind them.)
+static __device__ __forceinline__ bool hid_same_name_wave(uintptr_t loa, uintptr_t hia, uint64_t a, uint64_t len, uintptr_t lob, uintptr_t hib, uint64_t b,
+                                                          uint32_t lane)
 {
-    const uint64_t n = hi - lo;
+    const uint64_t n = hib - lob;
     if (b > n || n - b < len) return false;
-    if (b + len < n && !nm_is_space(*reinterpret_cast<const uint8_t *>(lo + b + len))) return false;
+    if (b + len < n && !nm_is_space(*reinterpret_cast<const uint8_t *>(lob + b + len))) return false;
     for (uint64_t k0 = 0; 4 * k0 < len; k0 += 64) {
         const uint64_t k = k0 + lane;
         uint32_t diff = 0;
         if (4 * k < len) {
             uint32_t ava, avb;
-            const uint32_t wa = nm_dword_at(lo, hi, a + 4 * k, &ava), wb = nm_dword_at(lo, hi, b + 4 * k, &avb);
+            const uint32_t wa = nm_dword_at(loa, hia, a + 4 * k, &ava), wb = nm_dword_at(lob, hib, b + 4 * k, &avb);
             const uint64_t rest = len - 4 * k;
             diff = (wa ^ wb) & nm_low_bytes(rest < 4 ? (uint32_t)rest : 4u);
         }
@@ -207,14 +227,10 @@ static __device__ __forceinline__ bool hid_same_name_wave(uintptr_t lo, uintptr_
     return true;
 }
 
-__global__ __launch_bounds__(kNmThreads) void k_hid_insert_long(const HidJob J, const uint32_t n_long)
+// the wave hashes the name at a of the input [lo, hi): its length and its hash before the cut to hash_bits, the same in every lane.
+// (k_hid_insert_long and k_hid_find_long: the one function.)
+static __device__ __forceinline__ uint64_t hid_hash_wave(uintptr_t lo, uintptr_t hi, uint64_t a, uint32_t lane, uint64_t *len_out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t li = (uint64_t)blockIdx.x * (kNmThreads / 64) + (threadIdx.x >> 6);
-    if (li >= n_long) return;                           // (the whole wave)
-    const uint64_t r = J.long_list[li];
-    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
-    const uint64_t a = J.rec_pos[r] + 1;
     // the name's end, 64 dwords a step; every dword of the name is mixed with its index, the sum is the hash
     uint64_t acc = 0, len = 0;
     for (uint64_t k0 = 0;; k0 += 64) {
@@ -227,7 +243,20 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_insert_long(const HidJob J, 
         if (lane <= first && cnt) acc += nm_fmix(((k + 1) << 32) | (w & nm_low_bytes(cnt)));
         if (ended) { len = 4 * (k0 + first) + (uint32_t)__shfl((int)cnt, (int)first); break; }
     }
-    const uint64_t h = nm_cut(nm_fmix(nm_wave_sum64(acc) ^ len), J.hash_bits);
+    *len_out = len;
+    return nm_fmix(nm_wave_sum64(acc) ^ len);
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_insert_long(const HidJob J, const uint32_t n_long)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t li = (uint64_t)blockIdx.x * (kNmThreads / 64) + (threadIdx.x >> 6);
+    if (li >= n_long) return;                           // (the whole wave)
+    const uint64_t r = J.long_list[li];
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    const uint64_t a = J.rec_pos[r] + 1;
+    uint64_t len;
+    const uint64_t h = nm_cut(hid_hash_wave(lo, hi, a, lane, &len), J.hash_bits);
     const unsigned long long tag = h >> 32, mine = (tag << 32) | r;
     uint64_t s = h & J.mask;
     for (;;) {                                          // (every lane takes the same way: lane 0's view of the slot decides)
@@ -241,7 +270,7 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_insert_long(const HidJob J, 
         cur = nm_bcast64(cur, 0);
         if ((cur >> 32) == tag) {
             const uint64_t owner = cur & 0xFFFFFFFFull;
-            if (owner == r || hid_same_name_wave(lo, hi, a, len, J.rec_pos[owner] + 1, lane)) {
+            if (owner == r || hid_same_name_wave(lo, hi, a, len, lo, hi, J.rec_pos[owner] + 1, lane)) {
                 if (lane == 0 && owner > r) hid_min(&J.table[s], mine);
                 break;
             }
@@ -265,6 +294,69 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_lookup(const HidJob J)
     }
     const unsigned long long m = __ballot(rep);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(J.n_repeated, (unsigned long long)__builtin_popcountll(m));
+}
+
+// ---- names in, first index out: the table of crass_hip_fastx_names_build_device is final here and only read ----
+// a query is an input of its own, [names + name_off[k], names + name_off[k + 1]): the name that starts with it ends with it, or
+// before that at an isspace() byte — then no record's name equals the query
+
+// the probe of one lane for a query of hash h (cut already): every step ends the loop or moves on a slot, mask + 1 steps at most
+static __device__ __forceinline__ uint64_t hid_probe_lane(const HidFindJob &J, uintptr_t qlo, uintptr_t qhi, uint64_t h)
+{
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    const unsigned long long tag = h >> 32;
+    uint64_t s = h & J.mask;
+    for (uint64_t step = 0; step <= J.mask; step++) {
+        const unsigned long long cur = J.table[s];
+        if (cur == kHidEmpty) break;
+        if ((cur >> 32) == tag) {
+            const uint64_t owner = cur & 0xFFFFFFFFull;
+            if (hid_same_name_lane(qlo, qhi, 0, lo, hi, J.rec_pos[owner] + 1)) return owner;
+        }
+        s = (s + 1) & J.mask;
+    }
+    return kHidNotFound;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_find(const HidFindJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n_names) return;
+    const uint64_t qa = J.name_off[k], qlen = J.name_off[k + 1] - qa;
+    if (qlen >= kHidLaneEnd) return;                    // the wave kernel's (the host listed it)
+    const uintptr_t qlo = (uintptr_t)J.names + qa, qhi = qlo + qlen;
+    uint64_t h, found = kHidNotFound;
+    uint32_t len;
+    if (hid_hash_lane(qlo, qhi, 0, &h, &len) && len == qlen)      // (a shorter name: an isspace() byte inside the query)
+        found = hid_probe_lane(J, qlo, qhi, nm_cut(h, J.hash_bits));
+    J.first_out[k] = found;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_hid_find_long(const HidFindJob J, const uint32_t n_long)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t li = (uint64_t)blockIdx.x * (kNmThreads / 64) + (threadIdx.x >> 6);
+    if (li >= n_long) return;                           // (the whole wave)
+    const uint64_t k = J.long_list[li];
+    const uint64_t qa = J.name_off[k], qlen = J.name_off[k + 1] - qa;
+    const uintptr_t qlo = (uintptr_t)J.names + qa, qhi = qlo + qlen;
+    const uintptr_t lo = (uintptr_t)J.bytes, hi = lo + J.n_bytes;
+    uint64_t len, found = kHidNotFound;
+    const uint64_t h = nm_cut(hid_hash_wave(qlo, qhi, 0, lane, &len), J.hash_bits);
+    if (len == qlen) {                                  // (every lane takes the same way: the slot is the same word for all of them)
+        const unsigned long long tag = h >> 32;
+        uint64_t s = h & J.mask;
+        for (uint64_t step = 0; step <= J.mask; step++) {
+            const unsigned long long cur = J.table[s];
+            if (cur == kHidEmpty) break;
+            if ((cur >> 32) == tag) {
+                const uint64_t owner = cur & 0xFFFFFFFFull;
+                if (hid_same_name_wave(qlo, qhi, 0, len, lo, hi, J.rec_pos[owner] + 1, lane)) { found = owner; break; }
+            }
+            s = (s + 1) & J.mask;
+        }
+    }
+    if (lane == 0) J.first_out[k] = found;
 }
 
 __global__ __launch_bounds__(kNmThreads) void k_hl_measure(const HlJob J)
@@ -349,6 +441,7 @@ __global__ __launch_bounds__(kNmThreads) void k_ql_copy(const QlJob J)
 }
 
 uint32_t hid_lane_max() { return kHidLaneMax; }
+uint32_t hid_lane_end() { return kHidLaneEnd; }
 
 static bool nm_grid(uint64_t items, uint64_t per_block, unsigned *blocks)
 {
@@ -379,6 +472,22 @@ hipError_t launch_hid_lookup(const HidJob &J, hipStream_t st)
     unsigned g;
     if (!nm_grid(J.n_reads, kNmThreads, &g)) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_hid_lookup, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_find(const HidFindJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n_names, kNmThreads, &g) || (J.mask & (J.mask + 1))) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_find, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_find_long(const HidFindJob &J, uint32_t n_long, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(n_long, kNmThreads / 64, &g) || n_long > J.n_names || (J.mask & (J.mask + 1))) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_find_long, dim3(g), dim3(kNmThreads), 0, st, J, n_long);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// fastx_names_launch.h — the job descriptions and launch wrappers of fastx_names.hip (header ids and header lines from the raw
+// fastx_names_launch.h — the job descriptions and launch wrappers of fastx_names.hip (header ids, name lookups and header lines from the raw
 // bytes of a FASTA / FASTQ file on the device), for the engine.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 namespace crass {
 
 static constexpr unsigned long long kHidEmpty = ~0ull;      // a free slot of the name table
+static constexpr uint64_t kHidNotFound = ~0ull;             // CRASS_NAME_NOT_FOUND
 
 // k_hid_insert / k_hid_insert_long / k_hid_lookup
 struct HidJob {
@@ -26,6 +27,21 @@ uint32_t hid_lane_max();
 hipError_t launch_hid_insert(const HidJob &J, hipStream_t st);
 hipError_t launch_hid_insert_long(const HidJob &J, uint32_t n_long, hipStream_t st);
 hipError_t launch_hid_lookup(const HidJob &J, hipStream_t st);
+
+// k_hid_find / k_hid_find_long: queries against a table k_hid_insert(_long) filled; everything is read but first_out
+struct HidFindJob {
+    const uint8_t *bytes; uint64_t n_bytes;      // the file the table was built on
+    const uint64_t *rec_pos;                     // [n_reads] as at the insert: every entry < n_bytes
+    const unsigned long long *table; uint64_t mask; uint32_t hash_bits;
+    const uint8_t *names;                        // device copy of the queries, any alignment; query k is [name_off[k], name_off[k + 1])
+    const uint64_t *name_off;                    // [n_names + 1], not decreasing
+    uint64_t n_names;
+    const uint32_t *long_list;                   // the queries of hid_lane_end() bytes or more, listed by the host
+    uint64_t *first_out;                         // [n_names] the smallest record index with that name, or kHidNotFound
+};
+uint32_t hid_lane_end();                         // names of this many bytes or more are hashed and compared by the wave kernels
+hipError_t launch_hid_find(const HidFindJob &J, hipStream_t st);
+hipError_t launch_hid_find_long(const HidFindJob &J, uint32_t n_long, hipStream_t st);
 
 // k_hl_measure / k_hl_copy
 struct HlJob {

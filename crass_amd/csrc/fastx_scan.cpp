@@ -180,4 +180,30 @@ int crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_
     return CRASS_OK;
 }
 
+int crass_fastx_find_names(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint8_t *names,
+                           const uint64_t *name_off, uint64_t n_names, uint64_t *first_out)
+{
+    if ((n_reads && (!bytes || !rec_pos)) || (n_names && (!name_off || !first_out))) return CRASS_ERR_INVALID_ARG;
+    for (uint64_t k = 0; k < n_names; k++) if (name_off[k + 1] < name_off[k]) return CRASS_ERR_INVALID_ARG;
+    if (n_names && name_off[n_names] && !names) return CRASS_ERR_INVALID_ARG;
+    auto is_space = [](uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+    try {
+        std::unordered_map<std::string_view, uint64_t> first;
+        first.reserve(n_reads * 2);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            if (rec_pos[r] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+            uint64_t a = rec_pos[r] + 1, b = a;
+            while (b < n_bytes && !is_space(bytes[b])) b++;      // the name, as crass_fastx_header_ids cuts it
+            first.emplace(std::string_view((const char *)bytes + a, b - a), r);
+        }
+        // (a query with an isspace() byte is looked up like any other: no name holds one, so it is not found)
+        for (uint64_t k = 0; k < n_names; k++) {
+            const uint64_t len = name_off[k + 1] - name_off[k];
+            const auto it = first.find(std::string_view(len ? (const char *)names + name_off[k] : "", len));
+            first_out[k] = it == first.end() ? CRASS_NAME_NOT_FOUND : it->second;
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
 } // extern "C"

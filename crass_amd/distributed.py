@@ -6,6 +6,11 @@ the pass-1 candidates' representative DR strings between the seed pass and the m
 (SURVEY §8e).  Rank order == global read order, so every rank replays the same
 addReadHolder token order and builds the identical pattern list locally — no broadcast of
 tables.  Payload: <= a few 10^4 candidates x (stride + 2) bytes, i.e. latency-bound.
+
+A job whose shards share header NAMES (paired files, one per rank) asks for a second exchange,
+FoundNameExchange, between the merge and pass 2: the names of every rank's pass-1 reads, so
+that a read whose name was found elsewhere is not recruited (readsFound, libcrispr.cpp:411).
+A caller that does not ask for it pays no collective for it.
 """
 import numpy as np
 
@@ -168,3 +173,87 @@ class GatheredExchange:
             cap *= 2
         self._setup(cap)
         return False
+
+
+def allgather_bytes(chars, off, dist, device=None):
+    """chars: uint8 [off[-1]], off: uint64 [n + 1] (n byte strings back to back)  ->  a list, per rank, of (chars, off).  The
+    pattern of allgather_candidates: counts first, then padded buffers of equal shape (lengths, then bytes)."""
+    import torch
+    world = dist.get_world_size()
+    dev = device if device is not None else torch.device("cpu")
+    chars = np.ascontiguousarray(chars, dtype=np.uint8).reshape(-1)
+    lens = np.diff(np.ascontiguousarray(off, dtype=np.uint64).astype(np.int64))
+    meta = torch.tensor([len(lens), len(chars)], dtype=torch.int64, device=dev)
+    metas = [torch.zeros_like(meta) for _ in range(world)]
+    dist.all_gather(metas, meta)
+    counts = [(int(m[0].item()), int(m[1].item())) for m in metas]
+    cap_n, cap_b = max(c[0] for c in counts), max(c[1] for c in counts)
+    if cap_n == 0:
+        return [(np.zeros(0, np.uint8), np.zeros(1, np.uint64)) for _ in range(world)]
+    buf = np.zeros(8 * cap_n + cap_b, dtype=np.uint8)      # [cap_n] int64 lengths, then the bytes
+    buf[:8 * len(lens)] = lens.astype("<i8").view(np.uint8)
+    buf[8 * cap_n:8 * cap_n + len(chars)] = chars
+    send = torch.from_numpy(buf).to(dev)
+    recv = [torch.empty_like(send) for _ in range(world)]
+    dist.all_gather(recv, send)
+    out = []
+    for r in range(world):
+        a = recv[r].cpu().numpy()
+        n, nb = counts[r]
+        o = np.zeros(n + 1, np.uint64)
+        o[1:] = np.cumsum(np.ascontiguousarray(a[:8 * n]).view("<i8"))
+        assert int(o[-1]) == nb, "a rank's name lengths do not add up to its byte count"
+        out.append((a[8 * cap_n:8 * cap_n + nb].copy(), o))
+    return out
+
+
+class FoundNameExchange:
+    """The found-header exchange of the one-process-per-GPU launcher ("with duplicate headers across shards the
+    found-header set must also be exchanged").  Every rank holds its shard's file bytes on the device and has installed its local
+    header ids; the name table of those bytes is built here, or by the caller (eng.names_build).  Between the merge and
+    eng.recruit every rank calls extra_found with the LOCAL record numbers of its pass-1 reads (ranks that found nothing
+    too: the call is collective, two all-gathers):
+
+        xf = FoundNameExchange(eng, dist)
+        cand = eng.seed_scan(); ...exchange, merge...
+        rec = eng.recruit(extra_found=xf.extra_found(cand.read_idx - base, src, layout))
+
+    Works with gloo (host tensors) and nccl (pass the rank's device)."""
+
+    def __init__(self, eng, dist, device=None, read_index_base=0):
+        self.eng, self.dist, self.device = eng, dist, device
+        self.read_index_base = int(read_index_base)
+
+    def extra_found(self, found_local_idx, src, layout, job_level=False, build=True):
+        """found_local_idx: LOCAL record numbers of this rank's pass-1 reads; src, layout: what fetch_header_lines takes.
+        Returns the sorted unique LOCAL record numbers (uint64) of the first record of every name that some OTHER rank found in
+        pass 1 — the array eng.recruit(extra_found=...) takes, which marks their header ids found.  job_level: the same with
+        read_index_base added (the job's read numbering, e.g. for SearchGroup.recruit).  build=False: the caller has built the
+        name table on these bytes (eng.names_build(src, layout)) and nothing has dropped it since; else it is built here, which
+        costs well under a millisecond per million reads."""
+        eng = self.eng
+        if build:
+            eng.names_build(src, layout)
+        idx = np.unique(np.asarray(found_local_idx, dtype=np.uint64).reshape(-1))
+        chars, off, name_len = eng.fetch_header_lines(src, layout, idx)
+        # the lines cut at name_len, back to back
+        n_off = np.zeros(len(idx) + 1, np.uint64)
+        n_off[1:] = np.cumsum(name_len.astype(np.uint64))
+        n_chars = np.zeros(int(n_off[-1]), np.uint8)
+        for k in range(len(idx)):
+            a = int(off[k])
+            n_chars[int(n_off[k]):int(n_off[k + 1])] = chars[a:a + int(name_len[k])]
+        parts = allgather_bytes(n_chars, n_off, self.dist, self.device)
+        rank = self.dist.get_rank()
+        others = set()
+        for r, (c, o) in enumerate(parts):
+            if r == rank:
+                continue
+            b = c.tobytes()
+            others.update(b[int(o[k]):int(o[k + 1])] for k in range(len(o) - 1))
+        if not others:
+            return np.zeros(0, np.uint64)
+        from . import _abi
+        first = eng.names_find(sorted(others))
+        first = np.unique(first[first != np.uint64(_abi.NAME_NOT_FOUND)])
+        return first + np.uint64(self.read_index_base) if job_level else first

@@ -471,6 +471,30 @@ def fastx_header_ids(buf, rec_pos):
     return out
 
 
+def _names_arg(names):
+    """a list of names (bytes), or (uint8 array, uint64 offsets[n + 1]) -> (chars, offsets), contiguous"""
+    if isinstance(names, tuple):
+        chars, off = names
+        return np.ascontiguousarray(chars, dtype=np.uint8).reshape(-1), np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+    return concat([bytes(x) for x in names])
+
+
+def find_names(buf, rec_pos, names):
+    """first[k] = the smallest record index whose NAME equals names[k] byte for byte, _abi.NAME_NOT_FOUND where there is none,
+    from the file's bytes and the records' positions (crass_fastx_find_names; host).  rec_pos: n_reads + 1 entries as in a
+    FastxLayout; names: a list of bytes, or (uint8 chars, uint64 offsets[n + 1]).  Returns uint64 [n]."""
+    a = _bytes_arg(buf)
+    rp = np.ascontiguousarray(rec_pos, dtype=np.uint64)
+    n = max(len(rp) - 1, 0)
+    chars, off = _names_arg(names)
+    m = max(len(off) - 1, 0)
+    out = np.zeros(m, np.uint64)
+    _chk(_abi.load().crass_fastx_find_names(a.ctypes.data if len(a) else None, len(a), rp.ctypes.data if len(rp) else None, n,
+                                            chars.ctypes.data if len(chars) else None, off.ctypes.data if len(off) else None, m,
+                                            out.ctypes.data if m else None), "crass_fastx_find_names")
+    return out
+
+
 class FastxFile:
     """FASTA/FASTQ(.gz) records with kseq_read semantics (C++ reader, crass_read_fastx)."""
 
@@ -1116,6 +1140,40 @@ class SearchEngine:
         """HIP-event milliseconds of the last device_header_ids call: (all kernels, insert launches, lookup launch); stage
         timing >= 1, else zeros."""
         return tuple(float(self.lib.crass_hip_last_header_ids_ms(self.h, k)) for k in range(3))
+
+    def names_build(self, src, layout):
+        """Builds and KEEPS the name table of file bytes on the DEVICE (src, layout: as fetch_header_lines takes them) for
+        names_find (crass_hip_fastx_names_build_device).  The table refers to the bytes: keep the tensor alive and unchanged
+        until names_drop, the next names_build, or close.  names_build(None, None): the arena and layout of the last
+        load_fastx_files; any load or attach then drops the table."""
+        if src is None and layout is None:
+            _chk(self.lib.crass_hip_fastx_names_build_device(self.h, None, 0, None, 0), "crass_hip_fastx_names_build_device")
+            self._names_keep = None
+            return
+        ptr, nb, rp, n = self._device_bytes(src, layout)
+        _chk(self.lib.crass_hip_fastx_names_build_device(self.h, ptr, nb, rp.ctypes.data, n), "crass_hip_fastx_names_build_device")
+        self._names_keep = src
+
+    def names_find(self, names):
+        """first[k] = the smallest LOCAL record index whose name equals names[k] (a list of bytes, or (uint8 chars, uint64
+        offsets)), _abi.NAME_NOT_FOUND where no record has it: find_names' answer, from the table names_build left on the device
+        (crass_hip_fastx_names_find).  Returns uint64 [n]."""
+        chars, off = _names_arg(names)
+        m = max(len(off) - 1, 0)
+        out = np.zeros(m, np.uint64)
+        _chk(self.lib.crass_hip_fastx_names_find(self.h, chars.ctypes.data if len(chars) else None, off.ctypes.data if len(off) else None, m,
+                                                 out.ctypes.data if m else None), "crass_hip_fastx_names_find")
+        return out
+
+    def names_drop(self):
+        """Gives the table of names_build back (crass_hip_fastx_names_drop); fine without one."""
+        _chk(self.lib.crass_hip_fastx_names_drop(self.h), "crass_hip_fastx_names_drop")
+        self._names_keep = None
+
+    def last_names_ms(self):
+        """HIP-event milliseconds of (the last names_build's insert launches, the last names_find's kernels); stage timing >= 1,
+        else zeros."""
+        return tuple(float(self.lib.crass_hip_last_names_ms(self.h, k)) for k in range(2))
 
     def fetch_header_lines(self, src, layout, idx, out=None):
         """The header lines (without the header character and the line end) of the records idx (LOCAL record numbers, any order,

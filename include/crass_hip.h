@@ -576,6 +576,17 @@ int  crass_hip_set_header_ids(crass_hip_ctx *ctx, const uint64_t *header_id);
 /* replaces: crass_fastx.header_id for a scanned file, on the host: header_id_out[r] = index of the first read with the same NAME,
  * the bytes behind the header character up to the first isspace() byte, compared exactly (readsFound's key, libcrispr.cpp:138,411). */
 int  crass_fastx_header_ids(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, uint64_t *header_id_out);
+/* replaces: the other direction of the same key, names in and first read index out — what findSingletons asks of readsFound
+ * (libcrispr.cpp:411: a read whose NAME was found in pass 1 is not recruited) when the names come from somewhere else: a mate
+ * file, another lane, another rank.  first_out[k] = the smallest r whose NAME (as crass_fastx_header_ids cuts it: the bytes behind
+ * the header character at rec_pos[r] up to the first isspace() byte or the end of the bytes) equals the query
+ * names[name_off[k] .. name_off[k+1]) byte for byte, CRASS_NAME_NOT_FOUND when no record has that name.  A query is raw bytes: an
+ * empty one matches exactly the records with an empty name, one that holds an isspace() byte matches nothing.  On the host, no
+ * GPU needed: what crass_hip_fastx_names_find is tested against.  CRASS_ERR_INVALID_ARG: NULL arrays with counts > 0, a
+ * decreasing name_off, a rec_pos[r] >= n_bytes.  n_names == 0: CRASS_OK; n_reads == 0: every query is not found. */
+#define CRASS_NAME_NOT_FOUND (~0ull)
+int  crass_fastx_find_names(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                            const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out);
 /* replaces: the same (crass_fastx.header_id, readsFound's key) for a caller whose file bytes exist only on the DEVICE, which would
  * otherwise copy the file back to feed crass_fastx_header_ids: header_id_out[r] (host, [n_reads], may be NULL) is exactly that
  * function's result on the same bytes.  Names are hashed into a device table and compared byte for byte (fastx_names.hip): no
@@ -595,6 +606,31 @@ int  crass_hip_fastx_header_ids_device(crass_hip_ctx *ctx, const uint8_t *d_byte
  * first to last, 1 the insert launches (the host's look at the count of long names included), 2 the lookup launch; measured when
  * the stage timing level is >= 1, else 0.  (No reference counterpart: crass has no timers.) */
 float crass_hip_last_header_ids_ms(const crass_hip_ctx *ctx, int part);
+/* replaces: crass_fastx_find_names (readsFound's lookup by NAME, libcrispr.cpp:411) for a caller whose file bytes exist only on
+ * the DEVICE and whose names come from elsewhere (crass_amd/distributed.py: the found headers of other ranks), which would
+ * otherwise copy the file back.  build: the insert step of crass_hip_fastx_header_ids_device (the same kernels, slots, table size
+ * and CRASS_HID_TEST_HASH_BITS), but the table and the device copy of rec_pos (HOST array, [n_reads]) are KEPT by the context: 8
+ * bytes per slot + 8 per record until crass_hip_fastx_names_drop, the next build, or destroy.  The table refers to d_bytes (names
+ * are compared byte for byte): the caller keeps those bytes alive and unchanged for as long.  d_bytes == NULL && rec_pos == NULL:
+ * the arena and layout of the last crass_hip_load_fastx_files (n_bytes and n_reads are ignored; CRASS_ERR_STATE if there is none);
+ * any load or attach on the context drops a table built on the arena.
+ * find: first_out[k] (host, [n_names]) is exactly crass_fastx_find_names' answer on the bytes and rec_pos of the build; names and
+ * name_off ([n_names + 1]) are HOST arrays, uploaded into scratch that is given back before the call returns.  Nothing outside
+ * [names, names + name_off[n_names]) and [d_bytes, d_bytes + n_bytes) is read; no answer rests on a hash, and none depends on
+ * scheduling (the table is final: k_hid_find / k_hid_find_long only read).  Any number of find calls may follow one build.
+ * Errors (the table before and the resident set are untouched): CRASS_ERR_INVALID_ARG — a NULL context, NULL arrays with counts
+ * > 0, a decreasing name_off, a rec_pos[r] >= n_bytes (seen on the device, reported as crass_hip_fastx_header_ids_device reports
+ * it; the build then keeps no table of its own); CRASS_ERR_STATE — find without a table; CRASS_ERR_UNSUPPORTED — n_reads or
+ * n_names >= 2^32 - 1.  n_names == 0 (with a table): CRASS_OK.  n_reads == 0 (with a non-NULL pointer): build is CRASS_OK and every query is
+ * CRASS_NAME_NOT_FOUND.  drop without a table: CRASS_OK.
+ * Not here: queries that are already in device memory — a _device twin of find can follow. */
+int  crass_hip_fastx_names_build_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads);
+int  crass_hip_fastx_names_find(crass_hip_ctx *ctx, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out);
+int  crass_hip_fastx_names_drop(crass_hip_ctx *ctx);
+/* HIP-event time, in milliseconds on the context's stream: part 0 the insert launches of the last crass_hip_fastx_names_build_device
+ * (the host's look at the count of long names included), 1 the kernels of the last crass_hip_fastx_names_find; measured when the
+ * stage timing level is >= 1, else 0.  (No reference counterpart: crass has no timers.) */
+float crass_hip_last_names_ms(const crass_hip_ctx *ctx, int part);
 /* bytes one workgroup of the device scan handles per tile; tiles start at multiples of it counted from the 16-byte aligned
  * address at or below the bytes (tests place line and record edges on tile edges) */
 uint32_t crass_hip_fastx_tile_bytes(void);
