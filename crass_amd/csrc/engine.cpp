@@ -2,685 +2,16 @@
 // kernel sequencing on one HIP stream, and the host-side sink that turns device records into
 // the ordered hand-off (candidates, tokens, groups, patterns, recruits).
 //
+// The device ingest (load / attach, scan, inflate, names, fetch text) is engine_ingest.cpp; the context itself is engine_ctx.h.
+//
 // There is no CPU fallback anywhere in this file: every search decision is made by the HIP
 // kernels in kernels.hip, pass2.hip and sinks.hip; the host only orders, tokenises and clusters their output
 // ("stays on host").
-#include "../../include/crass_hip.h"
-#include "engine_internal.h"
-#include "merge.h"
-#include "pack_launch.h"
-#include "fastx_launch.h"
-#include "fastx_names_launch.h"
-#include "inflate_launch.h"
-#include "gunzip_launch.h"
+#include "engine_ctx.h"
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 #include <string>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
-#include <memory>
-#include <utility>
-#include <vector>
-
-using namespace crass;
-
-namespace {
-
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// One helper thread per context: rebuilds the host view of a device-side merge while the calling thread keeps
-// the device fed (pass 2).  submit() hands over one job; wait() returns when it has finished.
-class HostWorker {
-public:
-    ~HostWorker() { stop(); }
-    void submit(std::function<void()> job)
-    {
-        wait();
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            if (!started_) { th_ = std::thread([this] { loop(); }); started_ = true; }
-            job_ = std::move(job); busy_ = true;
-        }
-        cv_.notify_all();
-    }
-    void wait()
-    {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [this] { return !busy_; });
-    }
-    // The caller is about to wait for the job: if the helper has not even picked it up yet (its wake-up is normally
-    // ~50 us, but on a busy or CPU-limited host it was seen to take 4-14 ms — every slow step of tools/step_spikes.py was
-    // this wait), the caller runs the job itself instead.  Returns false when the helper has it (then: wait()).
-    bool run_here_if_not_started()
-    {
-        std::function<void()> job;
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            if (!(busy_ && job_)) return false;
-            job = std::move(job_); job_ = nullptr;          // the helper's wait predicate (busy_ && job_) stays false: it sleeps on
-        }
-        try { job(); } catch (...) { failed_.store(true, std::memory_order_relaxed); }      // (the job records its own status; this only keeps busy_ honest)
-        { std::lock_guard<std::mutex> lk(m_); busy_ = false; }
-        cv_.notify_all();
-        return true;
-    }
-    bool take_failed() { return failed_.exchange(false, std::memory_order_relaxed); }
-    void stop()
-    {
-        if (!started_) return;
-        wait();
-        { std::lock_guard<std::mutex> lk(m_); quit_ = true; }
-        cv_.notify_all();
-        th_.join();
-        started_ = false;
-    }
-private:
-    void loop()
-    {
-        for (;;) {
-            std::function<void()> job;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [this] { return quit_ || (busy_ && job_); });
-                if (quit_) return;
-                job = std::move(job_); job_ = nullptr;
-            }
-            try { job(); } catch (...) { failed_.store(true, std::memory_order_relaxed); }
-            { std::lock_guard<std::mutex> lk(m_); busy_ = false; }
-            cv_.notify_all();
-        }
-    }
-    std::atomic<bool> failed_{false};
-    std::thread th_;
-    std::mutex m_;
-    std::condition_variable cv_;
-    std::function<void()> job_;
-    bool busy_ = false, quit_ = false, started_ = false;
-};
-
-// std::allocator whose resize() leaves trivially constructible elements uninitialised
-template <typename T> struct NoInitAlloc : std::allocator<T> {
-    template <typename U> struct rebind { typedef NoInitAlloc<U> other; };
-    NoInitAlloc() = default;
-    template <typename U> NoInitAlloc(const NoInitAlloc<U> &) {}
-    template <typename U, typename... A> void construct(U *p, A &&...a)
-    {
-        if constexpr (sizeof...(A) == 0) ::new ((void *)p) U;
-        else ::new ((void *)p) U(std::forward<A>(a)...);
-    }
-};
-
-// device allocations of this library, and an optional cap on them (tests: CRASS_POOL_CAP_MB makes an allocation beyond the
-// cap fail with hipErrorOutOfMemory, so the error paths can be exercised without exhausting a 288 GB device)
-std::atomic<uint64_t> g_dev_bytes{0};
-std::atomic<uint64_t> g_dev_cap{0};
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t want)
-    {
-        if (want <= n && p) return hipSuccess;
-        release();
-        if (want == 0) want = 1;
-        const uint64_t cap = g_dev_cap.load(std::memory_order_relaxed);
-        if (cap && g_dev_bytes.load(std::memory_order_relaxed) + want * sizeof(T) > cap) return hipErrorOutOfMemory;
-        hipError_t e = crass::dev_alloc((void **)&p, want * sizeof(T));
-        if (e == hipSuccess) { n = want; g_dev_bytes.fetch_add(want * sizeof(T), std::memory_order_relaxed); }
-        else p = nullptr;
-        return e;
-    }
-    void release()
-    {
-        if (p) { crass::dev_free(p); g_dev_bytes.fetch_sub(n * sizeof(T), std::memory_order_relaxed); }
-        p = nullptr; n = 0;
-    }
-};
-
-template <typename T> struct PinBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t want)
-    {
-        if (want <= n && p) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-        if (want == 0) want = 1;
-        hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
-};
-
-} // namespace
-
-// A/B and test switches from the environment, read ONCE per context (crass_hip_create; crass_hip_reload_env re-reads
-// them for a live context) — never on the per-call path
-struct EnvSwitches {
-    bool no_lookback = false, no_pos_hints = false, merge_profile = false, no_lane_kernel = false;
-    bool host_merge = false, no_speculation = false, exc_separate = false, dm_inject_fail = false, dm_init_late = false;
-    bool no_presize = false;                         // A/B switch: no first-call bounds / pool sizing at crass_hip_load_reads
-    bool dd_full_table = false;                      // A/B switch: pass 1's de-duplication table sized for the survivor slots (the round-3 size)
-    bool no_device_view = false;                     // A/B switch: the host rebuilds crass_merge_view from root_of / blank (the round-3 path)
-    bool force_device_view = false;                  // CRASS_DEVICE_VIEW=1: the device assembles it for a single context too (default: multi-rank only)
-    bool no_dense_light = false;                     // CRASS_NO_DENSE_LIGHT: the A/B switch of the light walk over the dense path's survivors
-    bool no_warm_launch = false;                     // CRASS_NO_WARM_LAUNCH: the A/B switch of first_call_bounds' empty launch
-    uint32_t view_group_cap = 32768;                 // groups beyond this many members are ranked by the host (CRASS_VIEW_GROUP_CAP)
-    uint32_t view_sort_max = 2048;                   // groups of 65 .. this many members are ranked by a sort in LDS (k_dmx_sort; CRASS_VIEW_SORT_MAX: tests)
-    uint64_t test_bounds[4] = {0, 0, 0, 0};          // tests: CRASS_TEST_BOUNDS="survivors,distinct,flagged,gathered" replaces the
-                                                     // first-call bounds (0 = computed), so that every overflow path can be forced
-    uint32_t row_cap = 256, dm_group_cap = 16384, surv_debug = 0;     // row_cap: Levenshtein fallback rows of the long-read layout (strings beyond it: second launch, full rows)
-    int stage_timing = -1;
-    uint64_t pool_cap_bytes = 0;                     // tests: device allocations beyond this total fail with hipErrorOutOfMemory
-    bool no_hint_filter = false;                     // A/B switch: k_filter_general where the hint bits would be the filter
-    uint32_t wave_walk_min = 800;                    // pass 2 walks a read per wave when the longest read is beyond this (CRASS_WAVE_WALK_MIN)
-    uint32_t long_min = 2048;                        // read sets whose longest read is beyond this take the long-read path (CRASS_LONG_MIN: the A/B switch)
-    uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
-    bool inflate_hbm_window = true;                  // CRASS_INFLATE_WINDOW=lds: k_bgzf_inflate decodes in the wave's LDS window, not in the output's own range (A/B switch, inflate.hip)
-    uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
-    bool lane_find_serial = false;                   // CRASS_LANE_FIND_SERIAL=1: the A/B switch of the lane kernel's packed seed find (lane_find.h)
-    uint32_t probe_blocks = 0;                       // tests: CRASS_PROBE_BLOCKS caps the grid of pass 2's anchor probe, so that a few thousand reads are several tiles per wave (0: off)
-    void read()
-    {
-        auto on = [](const char *n) { return getenv(n) != nullptr; };
-        no_lookback = on("CRASS_NO_LOOKBACK"); no_pos_hints = on("CRASS_NO_POS_HINTS");
-        merge_profile = on("CRASS_MERGE_PROFILE"); no_lane_kernel = on("CRASS_NO_LANE_KERNEL"); host_merge = on("CRASS_HOST_MERGE");
-        no_speculation = on("CRASS_NO_SPECULATION"); exc_separate = on("CRASS_EXC_SEPARATE"); dm_init_late = on("CRASS_DM_INIT_LATE");
-        dm_inject_fail = on("CRASS_DM_INJECT_FAIL"); no_presize = on("CRASS_NO_PRESIZE"); no_device_view = on("CRASS_NO_DEVICE_VIEW"); dd_full_table = on("CRASS_DD_FULL_TABLE"); force_device_view = on("CRASS_DEVICE_VIEW");
-        view_group_cap = 32768; if (const char *e = getenv("CRASS_VIEW_GROUP_CAP")) view_group_cap = (uint32_t)std::max(1, atoi(e));
-        view_sort_max = 2048; if (const char *e = getenv("CRASS_VIEW_SORT_MAX")) view_sort_max = (uint32_t)std::min(2048, std::max(64, atoi(e)));
-        row_cap = 256; if (const char *e = getenv("CRASS_ROW_CAP")) row_cap = (uint32_t)std::max(1, atoi(e));
-        dm_group_cap = 16384; if (const char *e = getenv("CRASS_DM_GROUP_CAP")) dm_group_cap = (uint32_t)std::max(1, atoi(e));
-        surv_debug = 0; if (const char *e = getenv("CRASS_SURV_DEBUG")) surv_debug = (uint32_t)atoi(e);
-        stage_timing = -1; if (const char *e = getenv("CRASS_STAGE_TIMING")) stage_timing = std::min(2, std::max(0, atoi(e)));
-        for (auto &b : test_bounds) b = 0;
-        if (const char *e = getenv("CRASS_TEST_BOUNDS")) { int k = 0; for (const char *q = e; *q && k < 4; k++) { test_bounds[k] = (uint64_t)atoll(q); while (*q && *q != ',') q++; if (*q == ',') q++; } }
-        no_hint_filter = on("CRASS_NO_HINT_FILTER");
-        wave_walk_min = 800; if (const char *e = getenv("CRASS_WAVE_WALK_MIN")) wave_walk_min = (uint32_t)std::max(0, atoi(e));
-        long_min = 2048; if (const char *e = getenv("CRASS_LONG_MIN")) long_min = (uint32_t)std::max(0, atoi(e));
-        no_warm_launch = getenv("CRASS_NO_WARM_LAUNCH") != nullptr;
-        no_dense_light = getenv("CRASS_NO_DENSE_LIGHT") != nullptr;
-        text_chunk_bytes = 64ull << 20; if (const char *e = getenv("CRASS_TEXT_CHUNK_BYTES")) text_chunk_bytes = (uint64_t)std::max(1ll, atoll(e));
-        inflate_hbm_window = true; if (const char *e = getenv("CRASS_INFLATE_WINDOW")) inflate_hbm_window = strcmp(e, "lds") != 0;
-        hid_hash_bits = 64; if (const char *e = getenv("CRASS_HID_TEST_HASH_BITS")) hid_hash_bits = (uint32_t)std::min(64, std::max(0, atoi(e)));
-        lane_find_serial = false; if (const char *e = getenv("CRASS_LANE_FIND_SERIAL")) lane_find_serial = atoi(e) != 0;
-        probe_blocks = 0; if (const char *e = getenv("CRASS_PROBE_BLOCKS")) probe_blocks = (uint32_t)std::max(0, atoi(e));
-        pool_cap_bytes = 0; if (const char *e = getenv("CRASS_POOL_CAP_MB")) pool_cap_bytes = (uint64_t)std::max(1ll, atoll(e)) << 20;
-    }
-};
-
-// ---- the context's state, in one place -----------------------------------------------------------------------------
-// Results:      have_reads -> have_pass1 -> have_merge -> have_pass2 (each API call clears everything to its right and
-//               refuses with CRASS_ERR_STATE if what it needs on its left is missing).  dense.active / q_blob_active say
-//               which representation holds pass 1's / pass 2's records (compact pinned blob vs host vectors).
-// Speculation:  five bounds learnt from the PREVIOUS call of the same stage, each 1.5 x the count seen then, each used to
-//               size and queue the next stage before the host has seen the current count.  Every one of them has the same
-//               three-step protocol: (1) the kernels read the real count on the device and never touch a slot beyond the
-//               bound, (2) the real count reaches the host with the stage's final synchronisation, (3) count > bound =>
-//               nothing of the speculative launch is used, the bound is dropped (set to 0) and the stage is repeated with
-//               the exact count.  None is ever trusted for a result.
-//                 surv_cap_hint     survivors of the seed scan        -> survivor kernels queued behind the compaction
-//                 dx_cap_hint       distinct DR strings (one GPU)     -> the device merge queued behind pass 1 (premerge)
-//                 xchg.gx_cap_hint  distinct DR strings (all ranks)   -> the same behind the exchange's de-duplication
-//                 hit_cap_hint      reads flagged by the anchor probe -> verify / finish / pack queued behind it
-//                 (recruit_exact    one-shot: the next recruit call must not speculate, it repeats an overflowed one)
-// Queued merge: premerge 0 none / 2 queued by the seed scan and valid (count within the bound), premerge_inflight: its
-//               kernels may still be running when the seed scan returns; dm_prepared_n / dm_prepared_src: the survivor
-//               kernel already cleared the merge tables for that many tokens of that buffer.  crass_hip_merge ADOPTS a
-//               queued merge iff no strings were passed in and premerge == 2, otherwise launches its own.  dm_prev_local: the previous merge ran on the device for this
-//               context alone (only then is the next one queued ahead of time).  dm.active: the installed pattern set is
-//               the device-built one (dm.M), not the host-built automaton / anchors; dm.host_built, dm.build_pending: the
-//               host view (c->merge) of a device merge is being / has been rebuilt by the helper thread.
-// Copies:       bulk_pending: exact-size copies of pass 1's hand-off records are in flight on copy_stream; wait_bulk()
-//               before any getter reads them (a failed copy is reported there, bulk_status).
-// Failure:      a device merge that gives up sets dm.h_st->fail; whoever sees it calls host_merge_fallback (counted in
-//               n_merge_fallbacks) and repeats pass 2.  An allocation failure anywhere returns CRASS_ERR_OOM with the
-//               context still usable (tests/test_gpu_device_merge.py::test_out_of_memory_is_reported_and_the_context_survives).
-struct crass_hip_ctx {
-    crass_params prm{};
-    EnvSwitches env;
-    DevParams dp{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    mutable int last_hip = 0;
-
-    // resident reads
-    DevReads R{};
-    bool have_reads = false;
-    uint64_t read_base = 0;
-    uint32_t max_len = 0;
-    bool uniform = false;
-    DevBuf<uint32_t> r_packed; DevBuf<uint64_t> r_word_off; DevBuf<uint32_t> r_lengths; DevBuf<uint64_t> r_header_id;
-    DevBuf<uint32_t> r_exc_mask; DevBuf<uint64_t> r_exc_read; DevBuf<uint64_t> r_exc_off; DevBuf<uint8_t> r_exc_bytes;
-    std::vector<uint64_t> h_exc_read;        // host copy of the exception read indices (local)
-    // crass_hip_load_text / crass_hip_attach_device_text: the text's offsets on the device (lengths that differ), the two
-    // staged chunks of a host text (pinned source of the copy, device destination) and their events
-    DevBuf<uint64_t> t_off; DevBuf<uint8_t> t_dev[2]; PinBuf<uint8_t> t_pin[2];
-    hipEvent_t ev_t_copy[2] = {nullptr, nullptr}, ev_t_pack[2] = {nullptr, nullptr}, ev_t_time[2] = {nullptr, nullptr};
-    float last_pack_ms = 0;                  // HIP-event time of the last call's pack kernels (stage timing >= 1, else 0)
-    // crass_hip_load_fastx_bytes / crass_hip_attach_device_fastx (fastx_scan.hip): the raw bytes of a host file, the tile arrays,
-    // the totals ([0..4), then the verdict word), the reads' text and the two per-record arrays — all given back before the call
-    // returns; the pinned copies crass_fastx_layout points at stay until the next such call or destroy
-    DevBuf<uint8_t> x_raw, x_text; DevBuf<FxTile> x_tiles; DevBuf<FxBase> x_base; DevBuf<uint64_t> x_tot, x_rec_pos, x_seq_off;
-    PinBuf<uint64_t> x_h_tot, x_h_rec_pos, x_h_seq_off;
-    hipEvent_t ev_x_time[2] = {nullptr, nullptr};
-    float last_scan_ms = 0;                  // HIP-event time of the last call's scan kernels (stage timing >= 1, else 0)
-    // crass_hip_inflate_bgzf_device / crass_hip_load_fastx_bgzf (inflate.hip): the index's three arrays back to back, every
-    // member's reason, the verdict word, the compressed bytes of a host file and the text that is not the caller's — all given
-    // back before the call returns
-    DevBuf<uint64_t> z_idx; DevBuf<uint32_t> z_reason; DevBuf<unsigned long long> z_verdict; DevBuf<uint8_t> z_raw, z_text;
-    PinBuf<unsigned long long> z_h_verdict;
-    hipEvent_t ev_z_time[2] = {nullptr, nullptr};
-    float last_inflate_ms = 0;               // HIP-event time of the last call's inflate kernel (stage timing >= 1, else 0)
-    // crass_hip_inflate_gzip_device / crass_hip_load_fastx_gzip (gunzip.hip): per chunk start / text_len / end_bit and link / reason
-    // (count step); per chain element start / end_bit of all chunks + the elements' offsets and chain / CRC parts, the text as
-    // 16-bit symbols and the 32 KB windows (decode step) — all given back before the call returns
-    DevBuf<uint64_t> gz_a64, gz_b64; DevBuf<uint32_t> gz_a32, gz_b32; DevBuf<uint16_t> gz_sym; DevBuf<uint8_t> gz_win;
-    DevBuf<uint64_t> gz_ends;                // members mode: the GzEnd records (3 words each)
-    hipEvent_t ev_gz_time[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float last_gzip_ms[5] = {0, 0, 0, 0, 0};  // find, count, decode, windows, narrow of the last gzip inflate (stage timing >= 1, else 0)
-    int gzip_on_device = 0;                  // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip (CRASS_GZIP_ON_DEVICE_*)
-    // crass_hip_fetch_text (k_fetch_text, pack.hip): the lengths of a set whose reads differ in length, kept on the host (the
-    // offsets of a fetch's records are summed here, so the output is sized and the copy back is exact without a second wait);
-    // the records' indices / flags / offsets and the text on the device, their pinned host sides (f_h_off and f_h_chars are
-    // what crass_text points at), the events of crass_hip_last_fetch_ms, the flags of crass_hip_fetch_record_text
-    std::vector<uint32_t> h_lengths;
-    DevBuf<uint64_t> f_idx, f_off; DevBuf<uint8_t> f_rc, f_chars;
-    PinBuf<uint64_t> f_h_idx, f_h_off; PinBuf<uint8_t> f_h_rc, f_h_chars;
-    hipEvent_t ev_f_time[2] = {nullptr, nullptr};
-    float last_fetch_ms = 0;
-    std::vector<uint8_t> f_flags;
-    // crass_hip_fastx_header_ids_device (fastx_names.hip): the name table, the uploaded record positions, the ids, the list of
-    // long names and the control words ([0..4) 32-bit: long names, bad position; then the 64-bit count of repeats) — all given
-    // back before the call returns; the events and times of crass_hip_last_header_ids_ms
-    DevBuf<unsigned long long> n_table; DevBuf<uint64_t> n_rec_pos, n_ids, n_ctl; DevBuf<uint32_t> n_long;
-    PinBuf<uint64_t> n_h_ctl;
-    hipEvent_t ev_n_time[3] = {nullptr, nullptr, nullptr};
-    float last_hid_ms[3] = {0, 0, 0};        // whole call's kernels, the insert launches, the lookup launch
-    // crass_hip_fastx_names_build_device: the same table and record positions, KEPT until crass_hip_fastx_names_drop, the next
-    // build or destroy (built on the arena: also until the next load or attach, drop_arena); the bytes are the caller's or the
-    // arena's.  crass_hip_fastx_names_find: the queries, their offsets, the list of long ones and the answers on the device — given
-    // back before the call returns; the events and times of crass_hip_last_names_ms
-    DevBuf<unsigned long long> nt_table; DevBuf<uint64_t> nt_rec_pos;
-    bool have_names = false, nt_on_arena = false;
-    const uint8_t *nt_bytes = nullptr; uint64_t nt_n_bytes = 0, nt_n_reads = 0, nt_mask = 0;
-    DevBuf<uint8_t> nq_names; DevBuf<uint64_t> nq_off, nq_out; DevBuf<uint32_t> nq_long;
-    hipEvent_t ev_nq_time[2] = {nullptr, nullptr};
-    float last_names_ms[2] = {0, 0};         // the last build's insert launches, the last find's kernels
-    // crass_hip_fetch_header_lines_device: the records' first bytes, lengths (line, then name), offsets and the lines on the
-    // device (given back before the call returns) and their pinned host sides (hl_h_off and hl_h_chars are what crass_text points at)
-    DevBuf<uint64_t> hl_src, hl_off; DevBuf<uint32_t> hl_len; DevBuf<uint8_t> hl_chars;
-    PinBuf<uint64_t> hl_h_src, hl_h_off; PinBuf<uint32_t> hl_h_len; PinBuf<uint8_t> hl_h_chars;
-    // crass_hip_load_fastx_files: the arena (every file's text, a '\n' behind each) stays until the next load, attach or destroy
-    // (drop_arena); the pinned per-file arrays crass_fastx_files_layout points at (read bases, byte bases, formats)
-    DevBuf<uint8_t> fa_arena; uint64_t fa_bytes = 0; bool have_arena = false;
-    PinBuf<uint64_t> fa_h_base; PinBuf<int32_t> fa_h_format;
-    // crass_hip_fetch_quality_device: the records' positions and ends, the quality lines' starts, lengths and flags, offsets and
-    // the strings on the device (given back before the call returns) and their pinned host sides (ql_h_off, ql_h_chars: crass_text)
-    DevBuf<uint64_t> ql_src, ql_start, ql_off; DevBuf<uint32_t> ql_len; DevBuf<uint8_t> ql_chars;
-    PinBuf<uint64_t> ql_h_src, ql_h_off; PinBuf<uint32_t> ql_h_len; PinBuf<uint8_t> ql_h_chars;
-
-    // scratch
-    DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;
-    DevBuf<uint64_t> d_idx; DevBuf<uint32_t> d_count; DevBuf<uint8_t> d_found; DevBuf<uint32_t> d_hit_info;
-    bool hints_valid = false;       // d_hit_info doubles as the pass-1 seed-hint array (pass 2 reuses it afterwards)
-    DevBuf<SurvOut> d_surv; DevBuf<char> d_dr; DevBuf<uint32_t> d_ss_pool; DevBuf<uint32_t> d_ss_used;
-    DevBuf<RecruitOut> d_rec; DevBuf<uint32_t> d_exc_hit; DevBuf<uint64_t> d_extra;
-    PinBuf<uint32_t> h_count; PinBuf<SurvOut> h_surv; PinBuf<char> h_dr; PinBuf<uint32_t> h_ss; PinBuf<uint64_t> h_idx;
-    DevBuf<SurvOut> g_surv; DevBuf<char> g_dr; DevBuf<uint32_t> g_ss;       // host-loop sink: the found records, dense
-    PinBuf<RecruitOut> h_rec;
-    // automaton
-    DevBuf<uint16_t> a_go16; DevBuf<uint32_t> a_go32; DevBuf<uint16_t> a_out; DevBuf<uint16_t> a_go4;
-    DevAutomaton A{};
-    HostAutomaton H;
-    bool full_automaton_uploaded = false;
-    DevBuf<uint32_t> a_go4w;
-    DevBuf<uint32_t> a_anchor; DevBuf<uint32_t> d_slot_info; DevBuf<uint32_t> d_slot_pid; DevBuf<uint32_t> a_out_pid; DevBuf<uint32_t> a_pat_token;
-    bool have_pat_token = false;
-    DevAnchors K{};
-    bool have_anchors = false;
-    bool have_patterns = false;
-    uint32_t n_installed_patterns = 0;
-
-    // pass-1 results (host), final hand-off layout
-    bool have_pass1 = false;
-    struct P1List {
-        std::vector<uint64_t> read; std::vector<uint8_t> low; std::vector<uint32_t> replen, nss;
-        // (the two large arrays are filled by the host pool right after resize(): no value-initialisation pass over them)
-        std::vector<uint64_t> ss_off; std::vector<uint32_t, NoInitAlloc<uint32_t>> ss; std::vector<uint16_t> dr_len; std::vector<char, NoInitAlloc<char>> dr;
-        void clear() { read.clear(); low.clear(); replen.clear(); nss.clear(); ss_off.clear(); ss.clear(); dr_len.clear(); dr.clear(); }
-        void reserve(size_t n, uint32_t stride) { read.reserve(n); low.reserve(n); replen.reserve(n); nss.reserve(n); ss_off.reserve(n); ss.reserve(n * 6); dr_len.reserve(n); dr.reserve(n * stride); }
-        size_t size() const { return read.size(); }
-    } cand;
-    // fast path: the found records are gathered on the device into dense arrays and land in pinned
-    // host memory already in the hand-off layout (no per-record host work)
-    mutable struct P1Dense {
-        DevBuf<uint16_t> d_dr_len; DevBuf<char> d_dr;       // dense DR strings of the found records (input of the de-duplication)
-        uint64_t n = 0;
-        bool active = false;
-        // everything else of the found records: the compact hand-off blob (p1_blob_layout), assembled by the gather kernel
-        // in device memory; its used bytes are copied by the runtime on the copy stream once the host knows the record
-        // count (beside the merge kernels; bulk_pending until wait_bulk())
-        PinBuf<uint8_t> h_blob; DevBuf<uint8_t> d_blob;
-        P1Blob lay{};
-        uint32_t pack_ss_cap = 0;
-        // the ABI's wide per-candidate arrays (crass_candidates), widened from the compact blob on first request
-        bool wide_ready = false;
-        // (the two large ones are filled by the host pool right after resize(): no value-initialisation pass over 85 MB)
-        std::vector<uint32_t> w_replen, w_nss; std::vector<uint32_t, NoInitAlloc<uint32_t>> w_ss; std::vector<uint64_t> w_ss_off; std::vector<uint16_t> w_dr_len;
-        std::vector<char, NoInitAlloc<char>> w_dr;
-        PinBuf<char> h_dr_fb; PinBuf<uint16_t> h_dr_len_fb; bool dr_fallback = false;    // candidates' own strings (no distinct list)
-        void release()
-        {
-            h_blob.release(); d_blob.release(); h_dr_fb.release(); h_dr_len_fb.release(); d_dr_len.release(); d_dr.release();
-        }
-    } dense;
-    DevBuf<uint64_t> d_fidx;
-    DevBuf<uint64_t> g_fidx;                        // host-loop sink: the found records' slots, gathered (a source of the sink's copies)
-    DevBuf<uint64_t> d_pos_hint, d_pos_hint_off; uint64_t n_pos_hint_words = 0;     // long reads: per-position seed hints
-    DevBuf<uint32_t> d_punt;                                                          // long reads: [0] count, [1 ..] slots the light walk handed over
-    DevBuf<uint32_t> d_redo;                                                          // ... [0] count, [1 ..] slots the full kernel hands on to its full-layout launch
-    SdmaCopy *dma_sink[4] = {nullptr, nullptr, nullptr, nullptr};                     // the long-read sink's four copies on DMA engines (created with the first long-read set)
-    DevBuf<uint32_t> d_pos_hint_blk; bool pos_hint_blk = false;                       // ragged lengths: read of every 256th hint word
-    // device-side DR de-duplication (single-GPU merge fast path)
-    DevBuf<unsigned long long> dd_keys; DevBuf<uint32_t> dd_first, dd_slot, dd_rep; DevBuf<uint64_t> dd_hash;
-    PinBuf<uint32_t> h_rep; PinBuf<uint64_t> h_hash;
-    bool have_rep = false;
-    // device-side token ranks: distinct strings (first-occurrence order) + every candidate's distinct index.
-    // With these the host merge never touches the per-candidate strings.
-    DevBuf<uint32_t> dd_map; DevBuf<char> dd_dx_chars; DevBuf<uint16_t> dd_dx_len; DevBuf<uint64_t> dd_dx_hash;
-    PinBuf<uint32_t> h_dmap; PinBuf<char> h_dx_chars; PinBuf<uint16_t> h_dx_len; PinBuf<uint64_t> h_dx_hash;
-    uint64_t n_dx = 0;
-    bool have_dev_tokens = false;
-    uint32_t n_cu = 0;
-    bool host_view_light = false;              // crass_hip_set_host_view: a device merge's host view = the own candidates' tokens only
-    HostWorker worker;
-    uint64_t surv_cap_hint = 0;
-    uint64_t hit_cap_hint = 0;                // speculative bound for pass 2's flagged reads (0: none yet)
-    bool recruit_exact = false;               // the next recruit call must not speculate (it repeats an overflowed one)               // speculative survivor bound for the next seed scan (0: none yet)
-    hipStream_t copy_stream = nullptr;
-    // Long reads: k_hint_positions runs in kHintParts slices of the reads, the first on the main stream and the others on
-    // hint_stream BESIDE the walking kernel, which is launched slice by slice behind the slice's hints (run_survivors): the
-    // hint kernel is VALU-issue bound, the walk LDS-latency bound at two waves per SIMD.
-    static constexpr int kHintParts = 4;     // (at most; the default is two — see setup_pos_hints)
-    hipStream_t hint_stream = nullptr;
-    hipEvent_t ev_hint[kHintParts] = {nullptr, nullptr, nullptr, nullptr}, ev_hint_go = nullptr;
-    int hint_parts = 1;                         // slices of this read set (1: one launch on the main stream)
-    bool hint_filter = false;                   // the hint bits are this set's seed-scan filter (no lane-per-read filter for its layout)
-    bool hint_filter_any = false;               // ... in their every-position form (another window or seed lattice): computed for the filter, not kept
-    uint64_t hint_read_split[kHintParts + 1] = {0, 0, 0, 0, 0}, hint_word_split[kHintParts + 1] = {0, 0, 0, 0, 0};
-    DevBuf<uint16_t> g_dr_len; DevBuf<uint64_t> hl_dx_idx;      // host-loop sink: dense DR lengths, scratch of the device de-duplication
-    bool hint_pending = false;                  // slices are in flight on hint_stream: the main stream has not waited for them yet
-    hipEvent_t ev_gathered = nullptr;
-    hipEvent_t ev_premerge = nullptr;           // recorded behind a merge queued in the seed scan: the hand-off copy waits for it
-    mutable bool bulk_pending = false;          // rare paths only: D2H copies of the candidates' own strings in flight on copy_stream
-    // CRASS_OK, or CRASS_ERR_HIP with last_hip set: a failed copy must not be mistaken for delivered records
-    int wait_bulk() const
-    {
-        if (!bulk_pending) return bulk_status;
-        const hipError_t e = hipStreamSynchronize(copy_stream);
-        int de = sdma_wait(dma);
-        for (SdmaCopy *s : dma_sink) de |= sdma_wait(s);
-        bulk_pending = false;
-        if (e != hipSuccess) { last_hip = (int)e; bulk_status = CRASS_ERR_HIP; }
-        else if (de) { last_hip = (int)hipErrorUnknown; bulk_status = CRASS_ERR_HIP; }
-        return bulk_status;
-    }
-    SdmaCopy *dma = nullptr;                    // the hand-off records travel on a DMA engine when the HSA runtime offers one (sdma.cpp)
-    // The distinct list of pass 1 (every candidate's index in it, the strings, their lengths) reaches the host the same way:
-    // the de-duplication kernel used to write it straight into pinned memory — 5 MB of PCIe stores at 100 M reads, 90 us of
-    // the pass-1 tail — while its first reader (the helper thread's view build, get_candidates, the host-merge fall-backs) is
-    // a millisecond away.  dx_via_dma: three engine copies started when the counts are known; wait_dx() before any read.
-    SdmaCopy *dma_dx[3] = {nullptr, nullptr, nullptr};
-    bool dx_via_dma = false;
-    mutable std::mutex dx_mu;
-    mutable bool dx_pending = false, dx_stream_copy = false;
-    mutable int dx_status = CRASS_OK;
-    mutable bool dx_hash_valid = true;          // h_dx_hash holds the strings' TokenTable hashes (else: computed on first use)
-    int wait_dx() const
-    {
-        std::lock_guard<std::mutex> lk(dx_mu);
-        if (!dx_pending) return dx_status;
-        int bad = 0;
-        for (SdmaCopy *s : dma_dx) bad |= sdma_wait(s);
-        if (dx_stream_copy) { const hipError_t e = hipStreamSynchronize(copy_stream); if (e != hipSuccess) { last_hip = (int)e; bad = 1; } }
-        dx_pending = false; dx_stream_copy = false;
-        if (bad) { if (!last_hip) last_hip = (int)hipErrorUnknown; dx_status = CRASS_ERR_HIP; }
-        return dx_status;
-    }
-    mutable int bulk_status = CRASS_OK;         // sticky until the next seed scan issues new copies
-    // device-side merge (dmerge.hip): clustering, non-redundant set, anchor keys and the pass-2 verification
-    // index are built on the device; the host view (c->merge) is rebuilt from its per-token results while
-    // pass 2 runs.  dm.active: the installed pattern set lives in dm.M, not in the automaton/anchors above.
-    struct DM {
-        DevBuf<uint64_t> packed, tmask; DevBuf<uint32_t> codes, owner, root_of, pat_token;
-        DevBuf<uint32_t> kset_u32, ent_slot, anchor_tab, anchor_fp; DevBuf<uint8_t> blank; DevBuf<uint64_t> ents, rents; DevBuf<uint32_t> rset_u32, rd_slot;
-        DevBuf<unsigned long long> rset_key, bk_key;
-        DevBuf<unsigned long long> kset_key; DevBuf<DevMergeState> st; DevBuf<uint32_t> hot;
-        PinBuf<DevMergeState> h_st; PinBuf<uint32_t> h_root; PinBuf<uint8_t> h_blank;
-        std::vector<uint32_t> gid_tmp;
-        DevMerge M{};
-        bool active = false, host_built = false;
-        int build_status = 0;                       // result of the host-view build that runs on `worker`
-        bool build_pending = false;
-        // what the build found out, written by whichever thread runs it and copied into the context's own fields
-        // (n_installed_patterns, cnt.*, last_hip) by the CALLING thread once the build is known to be over (apply_build_result):
-        // the helper thread never writes a field the caller may read without waiting for it
-        struct BuildResult { bool valid = false; uint32_t n_patterns = 0, n_keys = 0; float ms_device = 0; int hip = 0; } br;
-        uint64_t n_cand = 0;
-        // what the host view is rebuilt from: the distinct list (pinned host copy) and every own candidate's index in it
-        const char *hx_chars = nullptr; const uint16_t *hx_len = nullptr; uint64_t n_tok = 0;
-        // multi-rank: the merge runs over the de-duplicated concatenation of every rank's list
-        bool global = false; uint64_t my_off = 0, n_global = 0;
-        DevBuf<char> g_chars, gx_chars; DevBuf<uint16_t> g_len, gx_len; DevBuf<unsigned long long> g_keys;
-        DevBuf<uint32_t> g_first, g_slot, g_rep, g_prefix, g_bsum; DevBuf<uint64_t> g_hash, g_mask, g_idx;
-        PinBuf<uint32_t> h_gmap; PinBuf<char> h_gx_chars; PinBuf<uint16_t> h_gx_len; PinBuf<uint64_t> h_gx_hash;
-        std::vector<uint32_t> cand_map;
-        hipEvent_t ev_done = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-        uint32_t want_post = 0;                     // the stage flag value pass 2's probe stores for this merge (h_flags[2])
-        // crass_merge_view assembled on the device (k_dmx_*, dmerge.hip): scratch, the dense blob, its totals; the blob
-        // reaches h_view on a DMA engine (dma_view) started by the helper thread once ev_view has fired
-        DevBuf<uint32_t> x_u32, x_members, x_tile; DevBuf<uint8_t> x_blob; DevBuf<DevViewTotals> x_tot;
-        PinBuf<DevViewTotals> x_htot; PinBuf<uint8_t> h_view;
-        hipStream_t view_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_view = nullptr, ev_apply = nullptr;
-        SdmaCopy *dma_view = nullptr, *dma_view2 = nullptr, *dma_view3 = nullptr;
-        uint32_t want_blank = 0;                    // the stage flag value k_dm_keys stores for this merge (h_flags[3]): blank[] is final      // (the blob travels in two pieces: the token half behind k_dmx_apply, the rest behind the last kernel)
-        bool hx_on_host = true;                     // the gathered distinct list has a pinned host copy (else: on the device only)
-        bool view_launched = false;                 // export kernels may be running on view_stream (ev_view orders after them)
-        bool apply_recorded = false;                // ev_apply was recorded behind this merge's k_dmx_apply
-        bool view_ready = false;                    // h_view holds the view of the current merge (crass_hip_get_merge reads it)
-        DevViewTotals view_tot{};
-        void release()
-        {
-            x_u32.release(); x_members.release(); x_tile.release(); x_blob.release(); x_tot.release(); x_htot.release(); h_view.release();
-            packed.release(); tmask.release(); bk_key.release(); codes.release(); owner.release(); root_of.release();
-            pat_token.release(); kset_u32.release(); ent_slot.release(); anchor_tab.release(); anchor_fp.release();
-            blank.release(); ents.release(); rents.release(); rset_u32.release(); rd_slot.release(); rset_key.release(); kset_key.release(); st.release(); hot.release(); h_st.release(); h_root.release(); h_blank.release();
-            g_chars.release(); gx_chars.release(); g_len.release(); gx_len.release(); g_keys.release(); g_first.release(); g_slot.release();
-            g_rep.release(); g_prefix.release(); g_bsum.release(); g_hash.release(); g_mask.release(); g_idx.release();
-            h_gmap.release(); h_gx_chars.release(); h_gx_len.release(); h_gx_hash.release();
-            if (ev_done) (void)hipEventDestroy(ev_done);
-            if (ev_t0) (void)hipEventDestroy(ev_t0);
-            if (ev_t1) (void)hipEventDestroy(ev_t1);
-            ev_done = ev_t0 = ev_t1 = nullptr;
-            if (view_stream) (void)hipStreamSynchronize(view_stream);
-            sdma_destroy(dma_view); dma_view = nullptr;
-            sdma_destroy(dma_view2); dma_view2 = nullptr;
-            sdma_destroy(dma_view3); dma_view3 = nullptr;
-            if (ev_apply) (void)hipEventDestroy(ev_apply);
-            ev_apply = nullptr;
-            if (ev_fork) (void)hipEventDestroy(ev_fork);
-            if (ev_view) (void)hipEventDestroy(ev_view);
-            if (view_stream) (void)hipStreamDestroy(view_stream);
-            ev_fork = ev_view = nullptr; view_stream = nullptr;
-            view_launched = view_ready = false;
-        }
-    } dm;
-    // one-collective exchange (crass_hip_exchange_setup): this rank's distinct list in a fixed-size device buffer
-    struct Xchg {
-        bool active = false;
-        uint32_t world = 1, rank = 0, slot = 0;
-        uint64_t cap = 0, needed = 0;
-        uint32_t gx_cap_hint = 0;                   // bound for the merge queued ahead of the counters (previous global count x 1.5)
-        hipEvent_t ev_counts = nullptr;
-        DevBuf<uint8_t> send; DevBuf<uint32_t> xinfo; PinBuf<uint32_t> h_xinfo;
-        uint64_t send_bytes() const { return (cap + 1) * (uint64_t)slot; }
-    } xchg;
-    // distinct candidate strings (multi-GPU exchange)
-    std::vector<char> dx_chars; std::vector<uint16_t> dx_len; std::vector<uint32_t> dx_map; bool have_distinct = false;
-    // host-loop sink, one chunk without exception reads: the found records reach pinned host memory on the copy stream (bulk_pending)
-    // while the merge and pass 2 are queued; the ABI's per-candidate arrays (`cand`) are filled from them when somebody asks
-    mutable std::function<void()> cand_fill;
-    hipEvent_t ev_sink_copies = nullptr;        // behind those copies on the copy stream: pass 2 re-uses one of their source buffers (d_fidx)
-    mutable uint64_t cand_pending_n = 0;
-    void materialize_cand() const { if (cand_fill) { std::function<void()> f; f.swap(cand_fill); f(); } }
-    uint64_t n_cand() const { return dense.active ? dense.n : (cand_fill ? cand_pending_n : cand.size()); }
-    // the distinct DR strings (token order) and every candidate's index among them came from the DEVICE: the dense sink, or the
-    // host-loop sink of a long-read set (hl_tokens: its gathered records were de-duplicated on the device beside the copies)
-    bool hl_tokens = false;
-    bool dev_tokens() const { return have_dev_tokens && (dense.active || hl_tokens); }
-    void widen_p1() const;
-    const char *cand_dr() const { if (dense.active) { widen_p1(); return dense.w_dr.data(); } materialize_cand(); return cand.dr.data(); }
-    const uint16_t *cand_dr_len() const { if (dense.active) { widen_p1(); return dense.w_dr_len.data(); } materialize_cand(); return cand.dr_len.data(); }
-    uint32_t dr_stride = 48;
-    // merge
-    MergeResult merge;
-    bool have_merge = false;
-    // pass-2 results
-    bool have_pass2 = false;
-    std::vector<uint64_t> q_read; std::vector<uint8_t> q_low; std::vector<uint32_t> q_start, q_end, q_token;
-    std::vector<uint16_t> q_dr_len; std::vector<char, NoInitAlloc<char>> q_dr;      // (q_dr: whoever grows it fills the new bytes)
-    // ... or, when the sink ran on the device, one pinned blob (p2_blob_layout)
-    PinBuf<uint8_t> h_qblob; P2Blob q_lay{}; uint64_t q_n = 0; bool q_blob_active = false, q_wide_ready = false;
-
-    crass_counters cnt{};
-    uint32_t n_merge_fallbacks = 0, last_fallback_bits = 0;
-    std::atomic<uint32_t> n_view_fallbacks{0};      // device merges whose host view was built by the host after all (a group beyond the export's cap)
-    uint32_t n_bound_overflows[4] = {0, 0, 0, 0};   // speculation bounds that turned out too small (stage repeated): survivors, distinct, flagged, gathered
-    hipEvent_t ev[12]{};
-    // stage timing (crass_hip_set_stage_timing): an event record costs ~6 us of stream time, 14 of them 8 % of a 1 ms step.
-    // 0 none (the default: a crass run reads no stage times), 1 the three large kernels only (seed scan, survivors, pass-2 scan), 2 every stage
-    int timing_level = 0;
-    // single-pass compaction (k_mask_compact_lb): status words + ticket counter shared by every launch of the context
-    DevBuf<unsigned long long> lb_status; DevBuf<uint32_t> lb_ticket; PinBuf<uint32_t> h_lb_fail;
-    uint32_t lb_epoch = 0;
-    bool lb_on = true;
-    // nullptr: use the three-kernel form (switched off, or allocation failed)
-    const Lookback *next_lookback(uint64_t n_words, Lookback *out)
-    {
-        const uint32_t tw = lookback_tile_words(n_words);
-        return next_lookback_tiles((n_words + tw - 1) / tw, out);
-    }
-    // element-wise kernels (k_found_compact, k_dx_flag_rank, k_valid_compact): tiles of 4096 elements
-    const Lookback *next_lookback_elems(uint64_t n, Lookback *out) { return next_lookback_tiles((n + 4095) / 4096, out); }
-    const Lookback *next_lookback_tiles(uint64_t n_tiles, Lookback *out)
-    {
-        if (!lb_on || n_tiles == 0) return nullptr;
-        if (n_tiles > (1u << 24)) return nullptr;
-        if (!lb_status.p || lb_status.n < n_tiles) {
-            if (lb_status.ensure(std::max<uint64_t>(n_tiles * 2, 4096)) != hipSuccess) return nullptr;
-            if (hipMemsetAsync(lb_status.p, 0, lb_status.n * 8, stream) != hipSuccess) return nullptr;
-        }
-        if (!lb_ticket.p) {
-            if (lb_ticket.ensure(4) != hipSuccess || h_lb_fail.ensure(4) != hipSuccess) return nullptr;
-            if (hipMemsetAsync(lb_ticket.p, 0, 16, stream) != hipSuccess) return nullptr;
-            h_lb_fail.p[0] = 0;
-        }
-        lb_epoch = (lb_epoch + 1) & 0x3FFFFFFFu;
-        if (lb_epoch == 0) lb_epoch = 1;
-        out->status = lb_status.p; out->ticket = lb_ticket.p; out->epoch = lb_epoch; out->fail = h_lb_fail.p;
-        return out;
-    }
-    // allocation only (crass_hip_load_reads): hands out no tickets — a launch that never runs must not move the ticket base
-    void prealloc_lookback(uint64_t n_tiles)
-    {
-        if (!lb_on || n_tiles == 0 || n_tiles > (1u << 24)) return;
-        if (!lb_status.p || lb_status.n < n_tiles) {
-            if (lb_status.ensure(std::max<uint64_t>(n_tiles * 2, 4096)) != hipSuccess) return;
-            if (hipMemsetAsync(lb_status.p, 0, lb_status.n * 8, stream) != hipSuccess) return;
-            // (a re-allocated status array starts a new life: epochs of the old one mean nothing in it)
-        }
-        if (!lb_ticket.p) {
-            if (lb_ticket.ensure(4) != hipSuccess || h_lb_fail.ensure(4) != hipSuccess) return;
-            if (hipMemsetAsync(lb_ticket.p, 0, 16, stream) != hipSuccess) return;
-            h_lb_fail.p[0] = 0;
-        }
-    }
-    // after a synchronisation: a look-back spin that gave up invalidates the stage (never expected)
-    int lookback_ok()
-    {
-        if (!h_lb_fail.p || !h_lb_fail.p[0]) return CRASS_OK;
-        h_lb_fail.p[0] = 0; lb_on = false;
-        last_hip = (int)hipErrorLaunchTimeOut;
-        return CRASS_ERR_HIP;
-    }
-    // the device merge queued by the seed scan itself, right behind pass 1 (no host round trip in between): sized by a
-    // bound learnt from the previous merge, adopted by crass_hip_merge when the counts turn out to fit
-    bool dd_full_table = false;                         // a de-duplication table sized for the distinct strings overflowed once
-    uint32_t dx_cap_hint = 0; bool dm_prev_local = false; int premerge = 0;      // premerge: 0 none, 2 queued and valid
-    // a merge sized ahead of pass 1's survivor stage, whose kernel cleared the merge's tables (device_merge_prepare)
-    uint64_t dm_prepared_n = 0; const char *dm_prepared_src = nullptr;
-    bool premerge_inflight = false;                 // merge kernels may still be running when the seed scan returns
-    double t_p1_sync = 0;                           // CRASS_MERGE_PROFILE: host time line between pass 1 and the merge
-    bool spans_p1 = false, spans_p2 = false, span_survivors = false;     // spans to evaluate at the next counters fetch
-    // Deferred pass-1 tail (crass_hip_exchange_set_deferred; a rank of a multi-rank job): crass_hip_seed_scan queues pass 1 up to the
-    // kernel that fills the exchange's send buffer and RETURNS — the caller queues the collective and crass_hip_merge_gathered its
-    // kernels behind it on the same stream, and only then does the host wait for pass 1's counters (p1_finish).  The ~60 us the
-    // device idled between pass 1's last kernel and the exchange (host wake-up, the collective's and the unpack's launches) are
-    // gone.  The counters of the deferred stage land in h_count[16..24) (the exchange's kernels rewrite h_count[0..8) meanwhile).
-    // A launch that turns out unusable (bound too small, no device-resident distinct list) was marked by k_xg_fill in the send
-    // buffer's header from the same counters: every rank then sees an exchange that "did not fit" and the step is repeated, this
-    // context's next seed scan running synchronously (force_sync).
-    // Stage flags (DevMerge::flag_pre, engine_internal.h): pinned words stored by the first kernel of a stage; the host polls them
-    // where it used to wait for an event recorded between two kernels.  [0] pass 1 complete (k_xg_fill, deferred pass 1),
-    // [1] everything in front of the merge complete (k_dm_pack_codes), [2] the merge complete (pass 2's probe).  A poll that runs
-    // out of its budget falls back to a stream synchronisation (CRASS_NO_POLL: the events of round 5, the A/B switch).
-    PinBuf<uint32_t> h_flags; uint32_t flag_seq = 0, want_p1 = 0, want_pre = 0, want_post = 0; bool poll_on = false;
-    mutable std::atomic<uint32_t> n_poll_timeouts{0};
-    bool poll_flag(int k, uint32_t want, double budget_ms) const
-    {
-        const volatile uint32_t *f = h_flags.p + k;
-        const double t0 = now_ms();
-        for (uint32_t it = 0;; it++) {
-            if ((int32_t)(*f - want) >= 0) { std::atomic_thread_fence(std::memory_order_acquire); return true; }
-            __builtin_ia32_pause();
-            if ((it & 255u) == 255u && now_ms() - t0 > budget_ms) { n_poll_timeouts++; return false; }
-        }
-    }
-    struct P1Deferred {
-        bool enabled = false, active = false, finishing = false, force_sync = false;
-        uint64_t n_bound = 0; uint32_t ss_cap = 0, ss_elem = 1;
-        bool fast = false, hint_filtered = false;
-    } p1d;
-    const uint32_t *p1_counts() const { return p1d.finishing ? h_count.p + 16 : h_count.p; }
-    // level 1 only: which of the three large kernels are bracketed (bit 0 seed scan, 1 survivors, 2 pass-2 scan)
-    unsigned timing_focus = 7;
-    bool timed(int i, int level) const
-    {
-        if (timing_level < level) return false;
-        if (timing_level >= 2 || level != 1) return true;
-        const unsigned bit = (i <= 1) ? 1u : (i == 8 || i == 9) ? 2u : 4u;
-        return (timing_focus & bit) != 0;
-    }
-    hipError_t stamp(int i, int level) { return timed(i, level) ? hipEventRecord(ev[i], stream) : hipSuccess; }
-    float span(int a, int b, int level) const
-    {
-        float ms = 0;
-        if (!timed(a, level) || !timed(b, level) || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) ms = 0;
-        return ms;
-    }
-};
 
 // crass_candidates' arrays from the compact hand-off blob (and the distinct-string list for the DR strings)
 void crass_hip_ctx::widen_p1() const
@@ -736,11 +67,6 @@ static bool getenv_once_copy_early()                 // A/B switch: CRASS_COPY_E
     return on;
 }
 
-#define HIPCHK(ctx, call)                                                       \
-    do {                                                                        \
-        hipError_t e__ = (call);                                                \
-        if (e__ != hipSuccess) { (ctx)->last_hip = (int)e__; return e__ == hipErrorOutOfMemory ? CRASS_ERR_OOM : CRASS_ERR_HIP; } \
-    } while (0)
 
 extern "C" {
 
@@ -756,6 +82,10 @@ int crassi_anchor_shape(uint32_t low_dr, uint32_t *key_bases, uint32_t *align_ba
     if (align_bases) *align_bases = ok ? 1u << ash : 0u;
     return ok ? 1 : 0;
 }
+
+// Test seam, not part of include/crass_hip.h: the device bytes this library holds right now, over every context of the
+// process (DevBuf's counter) — what tests/test_gpu_ingest_scratch.py compares before and after a call.
+uint64_t crassi_dev_bytes_live(void) { return g_dev_bytes.load(std::memory_order_relaxed); }
 
 void crass_default_params(crass_params *p)
 {
@@ -908,6 +238,7 @@ void crass_hip_destroy(crass_hip_ctx *c)
     if (c->hint_stream) (void)hipStreamSynchronize(c->hint_stream);
     (void)sdma_wait(c->dma);                            // (before any buffer goes)
     (void)c->wait_dx();
+    ingest_free_all(c);                                 // (while the streams its release functions wait for are alive)
     if (getenv("CRASS_POLL_REPORT")) fprintf(stderr, "[crass_hip] stage-flag polls that ran out of their budget: %u (of %u flags)\n", c->n_poll_timeouts.load(), c->flag_seq);
     c->lb_status.release(); c->lb_ticket.release(); c->h_lb_fail.release(); c->h_flags.release();
     if (c->xchg.ev_counts) (void)hipEventDestroy(c->xchg.ev_counts);
@@ -926,32 +257,6 @@ void crass_hip_destroy(crass_hip_ctx *c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     c->r_packed.release(); c->r_word_off.release(); c->r_lengths.release(); c->r_header_id.release();
     c->r_exc_mask.release(); c->r_exc_read.release(); c->r_exc_off.release(); c->r_exc_bytes.release();
-    c->t_off.release();
-    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release(); c->x_rec_pos.release(); c->x_seq_off.release();
-    c->x_h_tot.release(); c->x_h_rec_pos.release(); c->x_h_seq_off.release();
-    for (auto &e : c->ev_x_time) if (e) (void)hipEventDestroy(e);
-    c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release(); c->z_h_verdict.release();
-    for (auto &e : c->ev_z_time) if (e) (void)hipEventDestroy(e);
-    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release(); c->gz_ends.release();
-    for (auto &e : c->ev_gz_time) if (e) (void)hipEventDestroy(e);
-    c->f_idx.release(); c->f_off.release(); c->f_rc.release(); c->f_chars.release();
-    c->f_h_idx.release(); c->f_h_off.release(); c->f_h_rc.release(); c->f_h_chars.release();
-    for (auto &e : c->ev_f_time) if (e) (void)hipEventDestroy(e);
-    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_ctl.release(); c->n_long.release(); c->n_h_ctl.release();
-    for (auto &e : c->ev_n_time) if (e) (void)hipEventDestroy(e);
-    c->nt_table.release(); c->nt_rec_pos.release(); c->nq_names.release(); c->nq_off.release(); c->nq_out.release(); c->nq_long.release();
-    for (auto &e : c->ev_nq_time) if (e) (void)hipEventDestroy(e);
-    c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
-    c->hl_h_src.release(); c->hl_h_off.release(); c->hl_h_len.release(); c->hl_h_chars.release();
-    c->fa_arena.release(); c->fa_h_base.release(); c->fa_h_format.release();
-    c->ql_src.release(); c->ql_start.release(); c->ql_off.release(); c->ql_len.release(); c->ql_chars.release();
-    c->ql_h_src.release(); c->ql_h_off.release(); c->ql_h_len.release(); c->ql_h_chars.release();
-    for (int k = 0; k < 2; k++) {
-        c->t_dev[k].release(); c->t_pin[k].release();
-        if (c->ev_t_copy[k]) (void)hipEventDestroy(c->ev_t_copy[k]);
-        if (c->ev_t_pack[k]) (void)hipEventDestroy(c->ev_t_pack[k]);
-        if (c->ev_t_time[k]) (void)hipEventDestroy(c->ev_t_time[k]);
-    }
     c->d_mask.release(); c->d_word_prefix.release(); c->d_block_sums.release(); c->d_idx.release(); c->d_count.release();
     c->d_found.release(); c->d_hit_info.release(); c->d_surv.release(); c->d_dr.release(); c->d_ss_pool.release();
     c->d_ss_used.release(); c->d_rec.release(); c->d_exc_hit.release(); c->d_extra.release();
@@ -962,7 +267,7 @@ void crass_hip_destroy(crass_hip_ctx *c)
     delete c;
 }
 
-static int validate_reads(const crass_reads *r)
+int validate_reads(const crass_reads *r)
 {
     if (!r) return CRASS_ERR_INVALID_ARG;
     if (r->n_reads && !r->packed) return CRASS_ERR_INVALID_ARG;
@@ -973,7 +278,7 @@ static int validate_reads(const crass_reads *r)
     return CRASS_OK;
 }
 
-static int alloc_scratch(crass_hip_ctx *c)
+int alloc_scratch(crass_hip_ctx *c)
 {
     const uint64_t n = c->R.n_reads;
     // (the mask / prefix scratch also serves compactions over survivor and hit SLOTS, whose launches are sized by bounds of
@@ -1064,25 +369,7 @@ static int setup_pos_hints(crass_hip_ctx *c, const uint32_t *lengths, uint32_t u
     return CRASS_OK;
 }
 
-static int first_call_bounds(crass_hip_ctx *c);
-static void presize_hostloop(crass_hip_ctx *c);
-
-// the file arena of crass_hip_load_fastx_files goes with the read set it belongs to: every public load and attach calls this
-// (load_text_impl, the pack step those calls share with crass_hip_load_fastx_files itself, does not)
-static void names_drop(crass_hip_ctx *c)
-{
-    if (c->nt_table.p || c->nt_rec_pos.p) { (void)hipStreamSynchronize(c->stream); c->nt_table.release(); c->nt_rec_pos.release(); }
-    c->have_names = false; c->nt_on_arena = false; c->nt_bytes = nullptr; c->nt_n_bytes = c->nt_n_reads = c->nt_mask = 0;
-}
-
-static void drop_arena(crass_hip_ctx *c)
-{
-    if (c->have_names && c->nt_on_arena) names_drop(c);      // (a name table built on the arena refers to its bytes)
-    if (c->fa_arena.p) { (void)hipStreamSynchronize(c->stream); c->fa_arena.release(); }
-    c->have_arena = false; c->fa_bytes = 0;
-}
-
-static void reset_results(crass_hip_ctx *c)
+void reset_results(crass_hip_ctx *c)
 {
     quiesce_worker(c);
     if (c->p1d.active) { (void)hipStreamSynchronize(c->stream); c->p1d.active = false; }      // (a deferred pass 1 nobody finished)
@@ -1093,10 +380,13 @@ static void reset_results(crass_hip_ctx *c)
     memset(&c->cnt, 0, sizeof(c->cnt));
 }
 
+static int first_call_bounds(crass_hip_ctx *c);
+static void presize_hostloop(crass_hip_ctx *c);
+
 // what every call that makes a read set resident ends with, once the set's arrays are on their way to the device: the
 // scratch sized by the read count, the long reads' position hints, the first call's speculation bounds and pools, counters.
 // lengths: host array, nullptr for a uniform length.
-static int finish_load(crass_hip_ctx *c, const DevReads &R, uint64_t read_index_base, uint32_t max_len, const uint32_t *lengths, uint64_t total_words)
+int finish_load(crass_hip_ctx *c, const DevReads &R, uint64_t read_index_base, uint32_t max_len, const uint32_t *lengths, uint64_t total_words)
 {
     c->R = R;
     c->read_base = read_index_base;
@@ -1115,1528 +405,6 @@ static int finish_load(crass_hip_ctx *c, const DevReads &R, uint64_t read_index_
     return CRASS_OK;
 }
 
-int crass_hip_load_reads(crass_hip_ctx *c, const crass_reads *h)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    int v = validate_reads(h);
-    if (v) return v;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (a failure below must not leave the previous reads half replaced)
-    drop_arena(c);
-    const uint64_t n = h->n_reads;
-    // host-side scan for the total word count / max length
-    uint64_t total_words = 0;
-    uint32_t max_len = h->uniform_len;
-    if (!h->uniform_len) for (uint64_t i = 0; i < n; i++) max_len = std::max(max_len, h->lengths[i]);
-    if (max_len > CRASS_HIP_MAX_READ_LEN) return CRASS_ERR_UNSUPPORTED;
-    if (h->stride_words) total_words = n * (uint64_t)h->stride_words;
-    else if (n) {
-        uint32_t lastL = h->uniform_len ? h->uniform_len : h->lengths[n - 1];
-        total_words = h->word_off[n - 1] + (lastL + 15) / 16;
-    }
-    HIPCHK(c, c->r_packed.ensure(total_words + 4));
-    HIPCHK(c, hipMemcpyAsync(c->r_packed.p, h->packed, total_words * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->r_packed.p + total_words, 0, 16, c->stream));
-    DevReads R{};
-    R.packed = c->r_packed.p; R.n_reads = n; R.stride_words = h->stride_words; R.uniform_len = h->uniform_len;
-    if (!h->stride_words) {
-        HIPCHK(c, c->r_word_off.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_word_off.p, h->word_off, n * 8, hipMemcpyHostToDevice, c->stream));
-        R.word_off = c->r_word_off.p;
-    }
-    if (!h->uniform_len) {
-        HIPCHK(c, c->r_lengths.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_lengths.p, h->lengths, n * 4, hipMemcpyHostToDevice, c->stream));
-        R.lengths = c->r_lengths.p;
-        c->h_lengths.assign(h->lengths, h->lengths + n);
-    } else c->h_lengths.clear();
-    if (h->header_id) {
-        HIPCHK(c, c->r_header_id.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, h->header_id, n * 8, hipMemcpyHostToDevice, c->stream));
-        R.header_id = c->r_header_id.p;
-    }
-    const uint64_t mask_words = (n + 31) / 32 + 1;
-    HIPCHK(c, c->r_exc_mask.ensure(mask_words));
-    HIPCHK(c, hipMemsetAsync(c->r_exc_mask.p, 0, mask_words * 4, c->stream));
-    R.exc_mask = c->r_exc_mask.p;
-    R.n_exc = h->n_exceptions;
-    c->h_exc_read.assign(h->exc_read, h->exc_read + h->n_exceptions);
-    if (h->n_exceptions) {
-        const uint64_t ne = h->n_exceptions;
-        for (uint64_t i = 0; i < ne; i++) {
-            uint64_t l = h->exc_off[i + 1] - h->exc_off[i];
-            if (l > CRASS_HIP_MAX_READ_LEN) return CRASS_ERR_UNSUPPORTED;
-            max_len = std::max<uint32_t>(max_len, (uint32_t)l);
-        }
-        HIPCHK(c, c->r_exc_read.ensure(ne));
-        HIPCHK(c, c->r_exc_off.ensure(ne + 1));
-        HIPCHK(c, c->r_exc_bytes.ensure(h->exc_off[ne] + 16));
-        HIPCHK(c, hipMemcpyAsync(c->r_exc_read.p, h->exc_read, ne * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->r_exc_off.p, h->exc_off, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->r_exc_bytes.p, h->exc_bytes, h->exc_off[ne], hipMemcpyHostToDevice, c->stream));
-        R.exc_read = c->r_exc_read.p; R.exc_off = c->r_exc_off.p; R.exc_bytes = c->r_exc_bytes.p;
-        HIPCHK(c, launch_build_exc_mask(R.exc_read, ne, c->r_exc_mask.p, c->stream));
-    }
-    return finish_load(c, R, h->read_index_base, max_len, h->uniform_len ? nullptr : h->lengths, total_words);
-}
-
-int crass_hip_attach_device_reads(crass_hip_ctx *c, const crass_reads *d)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    int v = validate_reads(d);
-    if (v) return v;
-    if (!d->uniform_len || !d->stride_words) return CRASS_ERR_UNSUPPORTED;   // attach mode: uniform shards only
-    if (d->n_exceptions) return CRASS_ERR_UNSUPPORTED;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;
-    drop_arena(c);
-    DevReads R{};
-    R.packed = d->packed; R.n_reads = d->n_reads; R.stride_words = d->stride_words; R.uniform_len = d->uniform_len;
-    R.header_id = d->header_id;
-    const uint64_t mask_words = (d->n_reads + 31) / 32 + 1;
-    HIPCHK(c, c->r_exc_mask.ensure(mask_words));
-    HIPCHK(c, hipMemsetAsync(c->r_exc_mask.p, 0, mask_words * 4, c->stream));
-    R.exc_mask = c->r_exc_mask.p;
-    c->h_exc_read.clear();
-    c->h_lengths.clear();
-    c->R = R;
-    c->read_base = d->read_index_base;
-    c->max_len = d->uniform_len;
-    c->uniform = true;
-    c->have_reads = true;
-    int s = alloc_scratch(c);
-    if (s) return s;
-    s = setup_pos_hints(c, nullptr, d->uniform_len, d->n_reads);
-    if (s) return s;
-    s = first_call_bounds(c);
-    if (s) return s;
-    presize_hostloop(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->cnt.n_reads = d->n_reads; c->cnt.n_exceptions = 0;
-    c->cnt.bytes_reads_device = d->n_reads * (uint64_t)d->stride_words * 4;
-    return CRASS_OK;
-}
-
-// ---- sequence text in, packed on the device (pack.hip) ----
-// h_seqs (host text) or d_seqs (device text); off[n + 1] is a host array either way.  The resident set, the host mirrors and
-// the counters end up as after crass_pack_reads + crass_hip_load_reads on the same bytes.
-static int load_text_impl(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t *d_seqs, const uint64_t *off, uint64_t n,
-                            int pad_uniform, const uint64_t *header_id, uint64_t read_index_base)
-{
-    if (!c || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
-    if (n && ((!h_seqs && !d_seqs) || !off)) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (a failure below must not leave the previous reads half replaced)
-    PackLayout lay;
-    if (const int ls = pack_layout(off, n, pad_uniform, &lay)) return ls;      // (nothing launched)
-    const uint64_t total_words = lay.total_words, out_words = (total_words + 4 + 3) & ~3ull;      // (the last vector store ends inside the buffer)
-    HIPCHK(c, c->r_packed.ensure(out_words));
-    DevReads R{};
-    R.packed = c->r_packed.p; R.n_reads = n; R.stride_words = lay.stride_words; R.uniform_len = lay.uniform_len;
-    std::vector<uint64_t> word_off;
-    std::vector<uint32_t> lengths;
-    if (!lay.stride_words && n) {
-        word_off.resize(n + 1);
-        uint64_t w = 0;
-        for (uint64_t i = 0; i < n; i++) { word_off[i] = w; w += (off[i + 1] - off[i] + 15) / 16; }
-        word_off[n] = w;
-        HIPCHK(c, c->r_word_off.ensure(n + 1));
-        HIPCHK(c, hipMemcpyAsync(c->r_word_off.p, word_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        R.word_off = c->r_word_off.p;
-    }
-    if (!lay.uniform_len && n) {
-        lengths.resize(n);
-        for (uint64_t i = 0; i < n; i++) lengths[i] = (uint32_t)(off[i + 1] - off[i]);
-        HIPCHK(c, c->r_lengths.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_lengths.p, lengths.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        R.lengths = c->r_lengths.p;
-        HIPCHK(c, c->t_off.ensure(n + 1));              // (a uniform length needs no per-read array: off[i] = off[0] + i L)
-        HIPCHK(c, hipMemcpyAsync(c->t_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    if (header_id && n) {
-        HIPCHK(c, c->r_header_id.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, header_id, n * 8, hipMemcpyHostToDevice, c->stream));
-        R.header_id = c->r_header_id.p;
-    }
-    const uint64_t mask_words = (n + 31) / 32 + 1;
-    HIPCHK(c, c->r_exc_mask.ensure(mask_words));
-    HIPCHK(c, hipMemsetAsync(c->r_exc_mask.p, 0, mask_words * 4, c->stream));
-    R.exc_mask = c->r_exc_mask.p;
-    c->h_exc_read.clear();
-
-    PackJob J{};
-    J.off = lay.uniform_len ? nullptr : c->t_off.p;
-    J.uni_base = n ? off[0] : 0; J.uni_len = lay.uniform_len;
-    J.stride_words = lay.stride_words; J.word_off = R.word_off;
-    J.out = c->r_packed.p; J.exc_mask = c->r_exc_mask.p;
-    auto word_start = [&](uint64_t r) { return lay.stride_words ? r * (uint64_t)lay.stride_words : word_off[r]; };
-    // stage timing (crass_hip_set_stage_timing >= 1): the pack kernels between two events, crass_hip_last_pack_ms
-    c->last_pack_ms = 0;
-    const bool timed = c->timing_level >= 1 && n != 0;
-    if (timed) {
-        for (auto &e : c->ev_t_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_t_time[0], c->stream));
-    }
-    if (n == 0) {
-        HIPCHK(c, hipMemsetAsync(c->r_packed.p, 0, out_words * 4, c->stream));
-    } else if (d_seqs) {
-        J.text = d_seqs; J.bias = 0; J.r_begin = 0; J.r_end = n; J.w_begin = 0; J.w_end = out_words;
-        HIPCHK(c, launch_pack_text(J, c->stream));
-    } else {
-        // chunks of whole reads through two staged buffers: the copy of chunk k + 1 (copy stream) runs beside the pack kernel of
-        // chunk k (main stream).  Pageable text goes through the pinned buffers; text that is already pinned is copied from where it is.
-        const uint64_t text_bytes = off[n] - off[0];
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, lay.max_len), std::max<uint64_t>(text_bytes, 1));
-        hipPointerAttribute_t pa{};
-        const bool src_pinned = hipPointerGetAttributes(&pa, h_seqs) == hipSuccess && pa.type == hipMemoryTypeHost;
-        (void)hipGetLastError();                        // (pageable memory is reported as an invalid value: not an error of ours)
-        for (int k = 0; k < 2; k++) {
-            if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
-            if (!c->ev_t_pack[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_pack[k], hipEventDisableTiming));
-        }
-        uint64_t ra = 0;
-        for (uint64_t k = 0; ra < n; k++) {
-            const int b = (int)(k & 1);
-            uint64_t rb;                                // the chunk: reads [ra, rb), at least one
-            if (lay.uniform_len) rb = std::min<uint64_t>(n, ra + std::max<uint64_t>(1, cap / lay.uniform_len));
-            else rb = std::max<uint64_t>(ra + 1, (uint64_t)(std::upper_bound(off + ra, off + n + 1, off[ra] + cap) - off) - 1);
-            const uint64_t bytes = off[rb] - off[ra];
-            const bool last = rb == n;
-            if (bytes) {
-                HIPCHK(c, c->t_dev[b].ensure(cap + 16));
-                const uint8_t *from = h_seqs + off[ra];
-                if (!src_pinned) {
-                    HIPCHK(c, c->t_pin[b].ensure(cap));
-                    if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
-                    memcpy(c->t_pin[b].p, from, bytes);
-                    from = c->t_pin[b].p;
-                }
-                if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_t_pack[b], 0));      // (the kernel that last read this device buffer)
-                HIPCHK(c, hipMemcpyAsync(c->t_dev[b].p, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
-                HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));
-            }
-            J.text = c->t_dev[b].p; J.bias = off[ra]; J.r_begin = ra; J.r_end = rb;
-            J.w_begin = word_start(ra); J.w_end = last ? out_words : word_start(rb);
-            HIPCHK(c, launch_pack_text(J, c->stream));
-            if (bytes) HIPCHK(c, hipEventRecord(c->ev_t_pack[b], c->stream));
-            ra = rb;
-        }
-    }
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_t_time[1], c->stream));
-    // the exception list: ascending read indices from the mask (ordered look-back compaction), their bytes from the text
-    c->R = R;
-    if (n) {
-        int s = alloc_scratch(c);
-        if (s) return s;
-        const uint64_t n_words = (n + 63) / 64;
-        Lookback lbs;
-        const Lookback *lb = c->next_lookback(n_words, &lbs);
-        HIPCHK(c, launch_compact(reinterpret_cast<const uint64_t *>(c->r_exc_mask.p), n_words, n, c->d_word_prefix.p, c->d_block_sums.p, c->d_idx.p, n,
-                                 c->d_count.p, c->stream, nullptr, 0, nullptr, 0, lb));
-        HIPCHK(c, hipMemcpyAsync(c->h_count.p, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((s = c->lookback_ok())) return s;
-        const uint64_t ne = c->h_count.p[0];
-        if (ne) {
-            c->h_exc_read.resize(ne);
-            HIPCHK(c, c->r_exc_read.ensure(ne));
-            HIPCHK(c, hipMemcpyAsync(c->r_exc_read.p, c->d_idx.p, ne * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpy(c->h_exc_read.data(), c->d_idx.p, ne * 8, hipMemcpyDeviceToHost));
-            std::vector<uint64_t> exc_off(ne + 1);
-            exc_off[0] = 0;
-            for (uint64_t e = 0; e < ne; e++) { const uint64_t r = c->h_exc_read[e]; exc_off[e + 1] = exc_off[e] + (off[r + 1] - off[r]); }
-            HIPCHK(c, c->r_exc_off.ensure(ne + 1));
-            HIPCHK(c, c->r_exc_bytes.ensure(exc_off[ne] + 16));
-            HIPCHK(c, hipMemcpyAsync(c->r_exc_off.p, exc_off.data(), (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            if (d_seqs) {
-                HIPCHK(c, launch_gather_exc_text(d_seqs, 0, J.off, J.uni_base, J.uni_len, c->r_exc_read.p, c->r_exc_off.p, ne, c->r_exc_bytes.p, c->stream));
-            } else {
-                std::vector<uint8_t> bytes(exc_off[ne] + 1);
-                for (uint64_t e = 0; e < ne; e++) { const uint64_t r = c->h_exc_read[e]; memcpy(bytes.data() + exc_off[e], h_seqs + off[r], off[r + 1] - off[r]); }
-                HIPCHK(c, hipMemcpyAsync(c->r_exc_bytes.p, bytes.data(), exc_off[ne], hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));      // (bytes goes out of scope)
-            }
-            HIPCHK(c, hipStreamSynchronize(c->stream));          // (exc_off goes out of scope; the caller's text may be freed on return)
-            R.exc_read = c->r_exc_read.p; R.exc_off = c->r_exc_off.p; R.exc_bytes = c->r_exc_bytes.p; R.n_exc = ne;
-        }
-    }
-    const int s = finish_load(c, R, read_index_base, lay.max_len, lay.uniform_len ? nullptr : lengths.data(), total_words);
-    c->h_lengths.swap(lengths);                         // (empty for a uniform length)
-    if (!s && timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t_time[0], c->ev_t_time[1]));
-        c->last_pack_ms = ms;
-    }
-    return s;
-}
-
-static int load_text_common(crass_hip_ctx *c, const uint8_t *h_seqs, const uint8_t *d_seqs, const uint64_t *off, uint64_t n,
-                            int pad_uniform, const uint64_t *header_id, uint64_t read_index_base)
-{
-    // (with arguments load_text_impl refuses, the resident set and its arena stay)
-    if (c && pad_uniform >= 0 && pad_uniform <= 2 && !(n && ((!h_seqs && !d_seqs) || !off))) { (void)hipSetDevice(c->device); drop_arena(c); }
-    const int s = load_text_impl(c, h_seqs, d_seqs, off, n, pad_uniform, header_id, read_index_base);
-    if (c) {
-        // what only this call needed goes back, on every way out: the text's offsets (8 bytes per read) and the two staged chunks
-        // (pinned and device memory of up to CRASS_TEXT_CHUNK_BYTES each) — a context loads a read set once
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
-        c->t_off.release();
-        for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
-    }
-    return s;
-}
-
-int crass_hip_load_text(crass_hip_ctx *c, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads, int pad_uniform,
-                        const uint64_t *header_id, uint64_t read_index_base)
-{
-    return load_text_common(c, seqs, nullptr, off, n_reads, pad_uniform, header_id, read_index_base);
-}
-
-int crass_hip_attach_device_text(crass_hip_ctx *c, const uint8_t *d_seqs, const uint64_t *off, uint64_t n_reads, int pad_uniform,
-                                 const uint64_t *header_id, uint64_t read_index_base)
-{
-    return load_text_common(c, nullptr, d_seqs, off, n_reads, pad_uniform, header_id, read_index_base);
-}
-
-float crass_hip_last_pack_ms(const crass_hip_ctx *c) { return c ? c->last_pack_ms : 0.0f; }
-
-// n host bytes up into dst (device) through the two pinned staging buffers of crass_hip_load_text; bytes that are already pinned are
-// copied from where they are.  The context's stream waits for the last copy.
-static int upload_staged(crass_hip_ctx *c, const uint8_t *h_bytes, uint64_t n, uint8_t *dst)
-{
-    if (n == 0) return CRASS_OK;
-    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->env.text_chunk_bytes, 1), n);
-    hipPointerAttribute_t pa{};
-    const bool src_pinned = hipPointerGetAttributes(&pa, h_bytes) == hipSuccess && pa.type == hipMemoryTypeHost;
-    (void)hipGetLastError();                            // (pageable memory is reported as an invalid value: not an error of ours)
-    for (int k = 0; k < 2; k++) if (!c->ev_t_copy[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_t_copy[k], hipEventDisableTiming));
-    int b = 0;
-    uint64_t k = 0;
-    for (uint64_t at = 0; at < n; at += cap, k++) {
-        b = (int)(k & 1);
-        const uint64_t bytes = std::min<uint64_t>(cap, n - at);
-        const uint8_t *from = h_bytes + at;
-        if (!src_pinned) {
-            HIPCHK(c, c->t_pin[b].ensure(cap));
-            if (k >= 2) HIPCHK(c, hipEventSynchronize(c->ev_t_copy[b]));      // (the copy that last read this pinned buffer)
-            memcpy(c->t_pin[b].p, from, bytes);
-            from = c->t_pin[b].p;
-        }
-        HIPCHK(c, hipMemcpyAsync(dst + at, from, bytes, hipMemcpyHostToDevice, c->copy_stream));
-        HIPCHK(c, hipEventRecord(c->ev_t_copy[b], c->copy_stream));
-    }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_t_copy[b], 0));      // (the last copy: the copy stream runs them in order)
-    return CRASS_OK;
-}
-
-// ---- the raw bytes of a FASTA / FASTQ file in, parsed on the device (fastx_scan.hip) ----
-// h_bytes (host) or d_bytes (device).  Accepted: the state is that of crass_hip_load_text on the reads' text; declined: no reads.
-static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8_t *d_bytes, uint64_t n, int pad_uniform,
-                           uint64_t read_index_base, crass_fastx_layout *out)
-{
-    if (out) memset(out, 0, sizeof(*out));
-    if (!c || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
-    if (n && !h_bytes && !d_bytes) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
-    drop_arena(c);
-    c->last_scan_ms = 0; c->last_pack_ms = 0;
-    auto decline = [&](int32_t format, uint64_t pos, int32_t reason) {
-        if (out) { out->format = format; out->decline_pos = pos; out->decline_reason = reason; }
-        return CRASS_ERR_UNSUPPORTED;
-    };
-    if (n == 0) return decline(0, 0, FX_EMPTY);
-    uint8_t b0 = 0;
-    if (h_bytes) b0 = h_bytes[0];
-    else HIPCHK(c, hipMemcpy(&b0, d_bytes, 1, hipMemcpyDeviceToHost));
-    if (!fx_is_hdr_char(b0)) return decline(0, 0, FX_FIRST_BYTE);
-    if (h_bytes) {
-        HIPCHK(c, c->x_raw.ensure(n + 16));
-        const int up = upload_staged(c, h_bytes, n, c->x_raw.p);
-        if (up) return up;
-        d_bytes = c->x_raw.p;
-    }
-    FxJob J{};
-    J.bytes = d_bytes; J.n = n; J.lead = (uint32_t)((uintptr_t)d_bytes & 15u); J.format = b0;
-    J.n_tiles = fastx_n_tiles(d_bytes, n);
-    if (J.n_tiles > 0x7FFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (beyond 8 TB)
-    HIPCHK(c, c->x_tiles.ensure(J.n_tiles)); HIPCHK(c, c->x_base.ensure(J.n_tiles));
-    HIPCHK(c, c->x_tot.ensure(8)); HIPCHK(c, c->x_h_tot.ensure(8));
-    J.tiles = c->x_tiles.p; J.base = c->x_base.p; J.tot = c->x_tot.p;
-    J.verdict = reinterpret_cast<unsigned long long *>(c->x_tot.p + 4);
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_x_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_x_time[0], c->stream));
-    }
-    HIPCHK(c, launch_fx_summary(J, c->stream));
-    HIPCHK(c, launch_fx_tile_scan(J, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p, c->x_tot.p, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the record count sizes the next kernel's arrays)
-    J.n_lines = c->x_h_tot.p[0]; J.n_reads = c->x_h_tot.p[1];
-    const uint64_t nr = J.n_reads, total_seq = c->x_h_tot.p[2];
-    J.text_cap = total_seq;
-    HIPCHK(c, c->x_text.ensure(total_seq + 32));
-    HIPCHK(c, c->x_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_seq_off.ensure(nr + 1));
-    HIPCHK(c, c->x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_h_seq_off.ensure(nr + 1));
-    J.text = c->x_text.p; J.rec_pos = c->x_rec_pos.p; J.seq_off = c->x_seq_off.p;
-    HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
-    HIPCHK(c, launch_fx_emit(J, c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_x_time[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p + 4, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
-    if (nr) {
-        HIPCHK(c, hipMemcpyAsync(c->x_h_rec_pos.p, c->x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->x_h_seq_off.p, c->x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x_time[0], c->ev_x_time[1]));
-        c->last_scan_ms = ms;
-    }
-    const uint64_t verdict = c->x_h_tot.p[4];
-    if (verdict != kFxNoOffence) return decline(b0, verdict >> 8, (int32_t)(verdict & 0xFF));
-    if (nr == 0 || c->x_h_tot.p[3] != (b0 == 0x40 ? total_seq : 0)) return CRASS_ERR_STATE;      // (never expected: an accepted input has a record and as many quality as sequence bytes)
-    uint64_t *rec_pos = c->x_h_rec_pos.p, *seq_off = c->x_h_seq_off.p;
-    rec_pos[nr] = n; seq_off[nr] = total_seq;
-    uint64_t max_len = 0;
-    for (uint64_t r = 0; r < nr; r++) {
-        const uint64_t l = seq_off[r + 1] - seq_off[r];
-        if (l > CRASS_HIP_MAX_READ_LEN) return decline(b0, rec_pos[r], FX_READ_TOO_LONG);
-        max_len = std::max(max_len, l);
-    }
-    const int s = load_text_impl(c, nullptr, c->x_text.p, seq_off, nr, pad_uniform, nullptr, read_index_base);
-    if (s) return s;
-    if (out) { out->n_reads = nr; out->format = b0; out->max_len = (uint32_t)max_len; out->rec_pos = rec_pos; out->seq_off = seq_off; }
-    return CRASS_OK;
-}
-
-static int load_fastx_common(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8_t *d_bytes, uint64_t n, int pad_uniform,
-                             uint64_t read_index_base, crass_fastx_layout *out)
-{
-    const int s = load_fastx_impl(c, h_bytes, d_bytes, n, pad_uniform, read_index_base, out);
-    if (c) {
-        // the scratch goes back on every way out: the raw copy, the reads' text, the tile and per-record arrays, and what
-        // crass_hip_load_text's own part needed (load_text_common)
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
-        c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
-        c->x_rec_pos.release(); c->x_seq_off.release();
-        c->t_off.release();
-        for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
-    }
-    return s;
-}
-
-int crass_hip_load_fastx_bytes(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
-                               crass_fastx_layout *out)
-{
-    return load_fastx_common(c, bytes, nullptr, n_bytes, pad_uniform, read_index_base, out);
-}
-
-int crass_hip_attach_device_fastx(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
-                                  crass_fastx_layout *out)
-{
-    return load_fastx_common(c, nullptr, d_bytes, n_bytes, pad_uniform, read_index_base, out);
-}
-
-uint32_t crass_hip_fastx_tile_bytes(void) { return fastx_tile_bytes(); }
-float crass_hip_last_scan_ms(const crass_hip_ctx *c) { return c ? c->last_scan_ms : 0.0f; }
-
-// ---- BGZF members inflated on the device (inflate.hip) ----
-// the index is checked, d_in / d_out are device pointers: upload the offsets, launch, read the verdict
-static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_bgzf_index *ix, uint8_t *d_out, crass_bgzf_verdict *v)
-{
-    const uint64_t n = ix->n_members;
-    c->last_inflate_ms = 0;
-    if (n == 0) return CRASS_OK;
-    HIPCHK(c, c->z_idx.ensure(3 * n + 2)); HIPCHK(c, c->z_reason.ensure(n)); HIPCHK(c, c->z_verdict.ensure(1)); HIPCHK(c, c->z_h_verdict.ensure(1));
-    BzJob J{};
-    J.in = d_in; J.out = d_out; J.n_members = n;
-    J.in_off = c->z_idx.p; J.out_off = c->z_idx.p + (n + 1); J.data_off = c->z_idx.p + 2 * (n + 1);
-    J.reason = c->z_reason.p; J.verdict = c->z_verdict.p; J.hbm_window = c->env.inflate_hbm_window ? 1 : 0;
-    HIPCHK(c, hipMemcpyAsync(c->z_idx.p, ix->in_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->z_idx.p + (n + 1), ix->out_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->z_idx.p + 2 * (n + 1), ix->data_off, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_z_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_z_time[0], c->stream));
-    }
-    HIPCHK(c, launch_bgzf_inflate(J, c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_z_time[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the index's host arrays are the caller's: nothing reads them after this)
-    if (timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_z_time[0], c->ev_z_time[1]));
-        c->last_inflate_ms = ms;
-    }
-    const uint64_t w = c->z_h_verdict.p[0];
-    if (w == kBzNoOffence) return CRASS_OK;
-    if (v) { v->reason = (int32_t)(w & 0xFF); v->member = w >> 8; v->in_pos = ix->in_off[w >> 8]; }
-    return CRASS_ERR_UNSUPPORTED;
-}
-
-static void inflate_bgzf_release(crass_hip_ctx *c)
-{
-    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->copy_stream);
-    c->z_idx.release(); c->z_reason.release(); c->z_verdict.release(); c->z_raw.release(); c->z_text.release();
-}
-
-int crass_hip_inflate_bgzf_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, const crass_bgzf_index *ix, uint8_t *d_out, uint64_t out_cap,
-                                  crass_bgzf_verdict *v)
-{
-    if (v) memset(v, 0, sizeof(*v));
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    const int chk = bgzf_index_check(ix, n_in, out_cap);
-    if (chk) return chk;
-    if (ix->n_members && (!d_in || (ix->out_off[ix->n_members] && !d_out))) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    const int s = inflate_bgzf_impl(c, d_in, ix, d_out, v);
-    inflate_bgzf_release(c);
-    return s;
-}
-
-static int load_fastx_bgzf_impl(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const crass_bgzf_index *ix, int pad_uniform,
-                                uint64_t read_index_base, uint8_t *d_text, crass_fastx_layout *out, crass_bgzf_verdict *v)
-{
-    const uint64_t n_text = ix->out_off[ix->n_members];
-    HIPCHK(c, c->z_raw.ensure(n_bytes + 16));
-    const int up = upload_staged(c, bytes, n_bytes, c->z_raw.p);
-    if (up) return up;
-    if (!d_text) { HIPCHK(c, c->z_text.ensure(n_text + 16)); d_text = c->z_text.p; }
-    const int s = inflate_bgzf_impl(c, c->z_raw.p, ix, d_text, v);
-    if (s) return s;
-    c->z_raw.release();                                 // (the compressed bytes are done with: the scan's arrays may have their room)
-    return load_fastx_impl(c, nullptr, d_text, n_text, pad_uniform, read_index_base, out);
-}
-
-int crass_hip_load_fastx_bgzf(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
-                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
-{
-    if (out) memset(out, 0, sizeof(*out));
-    if (v) memset(v, 0, sizeof(*v));
-    if (!c || pad_uniform < 0 || pad_uniform > 2 || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
-    crass_bgzf_index ix;
-    int s = crass_bgzf_index_host(bytes, n_bytes, &ix);
-    if (s == CRASS_OK && d_text && d_text_cap < ix.out_off[ix.n_members]) s = CRASS_ERR_INVALID_ARG;
-    if (s == CRASS_ERR_INVALID_ARG || s == CRASS_ERR_OOM) { crass_bgzf_index_free(&ix); return s; }
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
-    drop_arena(c);
-    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
-    if (s == CRASS_ERR_UNSUPPORTED) { if (v) *v = ix.decline; return s; }
-    s = load_fastx_bgzf_impl(c, bytes, n_bytes, &ix, pad_uniform, read_index_base, d_text, out, v);
-    // the scratch goes back on every way out, as in load_fastx_common
-    inflate_bgzf_release(c);
-    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
-    c->x_rec_pos.release(); c->x_seq_off.release();
-    c->t_off.release();
-    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
-    crass_bgzf_index_free(&ix);
-    return s;
-}
-
-// ---- one plain gzip member inflated on the device chunk by chunk (gunzip.hip, gunzip_core.h) ----
-namespace {
-// what the count step and the chain walk decided about one file: all the decode step needs beside the bytes
-struct GzState {
-    GzMember M{};
-    std::vector<uint64_t> start, text_len, end_bit;
-    std::vector<uint32_t> link, chain;
-    std::vector<int32_t> reason;
-    uint64_t n_chain = 0, n_text = 0;
-    // members mode (gunzip_core.h): what count reported about member ends, and after the decode step the member table
-    bool members = false;
-    uint64_t n_file = 0;
-    std::vector<uint32_t> n_ends;
-    std::vector<uint64_t> last_end, in_off, text_off;
-};
-}
-
-static void gzip_release(crass_hip_ctx *c)
-{
-    (void)hipStreamSynchronize(c->stream);
-    c->gz_a64.release(); c->gz_b64.release(); c->gz_a32.release(); c->gz_b32.release(); c->gz_sym.release(); c->gz_win.release(); c->gz_ends.release();
-}
-
-// header and trailer (host), find and count (device), the chain (host): CRASS_OK with S.n_text known, or the decline
-// (members: the rule's members mode, kept in S for the decode step)
-static int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, GzState &S, crass_gzip_plan *plan,
-                           crass_bgzf_verdict *v, bool members = false)
-{
-    S.members = members; S.n_file = n_in;
-    c->last_inflate_ms = 0;
-    for (auto &m : c->last_gzip_ms) m = 0;
-    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
-        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
-        return CRASS_ERR_UNSUPPORTED;
-    };
-    try {
-        // the header's bytes come down in a piece that grows until the header ends inside it
-        std::vector<uint8_t> head;
-        uint8_t trailer[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (n_in >= 18) HIPCHK(c, hipMemcpy(trailer, d_in + n_in - 8, 8, hipMemcpyDeviceToHost));
-        int32_t why = BZ_NOT_GZIP;
-        for (uint64_t h = std::min<uint64_t>(n_in, 65536);; h = std::min<uint64_t>(n_in, h * 4)) {
-            head.resize(h ? h : 1);
-            if (h) HIPCHK(c, hipMemcpy(head.data(), d_in, h, hipMemcpyDeviceToHost));
-            why = gz_parse_member(head.data(), h, trailer, n_in, chunk_bytes, &S.M);
-            if (why != -1 || h == n_in) break;
-        }
-        if (why != BZ_OK) return decline(BZ_NOT_GZIP, 0, 0);
-        const GzGeom &G = S.M.G;
-        const uint64_t nc = G.nc;
-        HIPCHK(c, c->gz_a64.ensure((members ? 4 : 3) * nc)); HIPCHK(c, c->gz_a32.ensure((members ? 3 : 2) * nc));
-        GzJob J{};
-        J.d = d_in + G.d_off; J.G = G;
-        J.start = c->gz_a64.p; J.text_len = c->gz_a64.p + nc; J.end_bit = c->gz_a64.p + 2 * nc;
-        J.link = c->gz_a32.p; J.reason = reinterpret_cast<int32_t *>(c->gz_a32.p + nc);
-        if (members) { J.last_end = c->gz_a64.p + 3 * nc; J.n_ends = c->gz_a32.p + 2 * nc; }
-        const bool timed = c->timing_level >= 1;
-        if (timed) {
-            for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-            HIPCHK(c, hipEventRecord(c->ev_gz_time[0], c->stream));
-        }
-        HIPCHK(c, launch_gz_find(J, c->stream, members));
-        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[1], c->stream));
-        HIPCHK(c, launch_gz_count(J, c->stream, members));      // (a launch of its own: every start is final before a chunk counts)
-        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
-        S.start.resize(nc); S.text_len.resize(nc); S.end_bit.resize(nc); S.link.resize(nc); S.reason.resize(nc); S.chain.assign(nc, 0);
-        HIPCHK(c, hipMemcpyAsync(S.start.data(), J.start, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(S.text_len.data(), J.text_len, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(S.end_bit.data(), J.end_bit, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(S.link.data(), J.link, nc * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(S.reason.data(), J.reason, nc * 4, hipMemcpyDeviceToHost, c->stream));
-        if (members) {
-            S.n_ends.resize(nc); S.last_end.resize(nc);
-            HIPCHK(c, hipMemcpyAsync(S.n_ends.data(), J.n_ends, nc * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(S.last_end.data(), J.last_end, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (timed) {
-            HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[0], c->ev_gz_time[0], c->ev_gz_time[1]));
-            HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[1], c->ev_gz_time[1], c->ev_gz_time[2]));
-            c->last_inflate_ms = c->last_gzip_ms[0] + c->last_gzip_ms[1];
-        }
-        GzVerdict gv{};
-        const int32_t bad = gz_chain(S.M, S.start.data(), S.link.data(), S.text_len.data(), S.end_bit.data(), S.reason.data(), S.chain.data(),
-                                     &S.n_chain, &S.n_text, &gv, members);
-        const int ps = gz_plan_fill(plan, nc, S.start.data(), S.link.data(), S.text_len.data(), S.n_chain);
-        if (ps) return ps;
-        if (bad != BZ_OK) return decline(gv.reason, gv.member, gv.in_pos);
-    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
-    return CRASS_OK;
-}
-
-// decode, windows, narrow: the text of an accepted count into d_out[0, S.n_text)
-// (members mode: every member's ISIZE and CRC-32 are checked here, behind the kernels; S gets the member table)
-static int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, GzState &S, uint8_t *d_out, crass_bgzf_verdict *v)
-{
-    const bool members = S.members;
-    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
-        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
-        return CRASS_ERR_UNSUPPORTED;
-    };
-    const GzGeom &G = S.M.G;
-    const uint64_t nc = G.nc, n = S.n_chain;
-    try {
-        std::vector<uint64_t> off(n + 1, 0);
-        for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + S.text_len[S.chain[i]];
-        std::vector<uint32_t> crc_part(n, 0);
-        // members mode: [slot (n + 1) | m0 (n)] go up behind off; the pieces' bounds follow once the member table is known
-        std::vector<uint64_t> places(2 * n + 1, 0);
-        if (members) {
-            std::vector<uint64_t> off2(n + 1, 0);
-            gz_places(S.chain.data(), n, S.text_len.data(), S.n_ends.data(), S.last_end.data(), off2.data(), places.data(), places.data() + n + 1);
-        }
-        const uint64_t nm = members ? places[n] : 0;
-        const uint64_t max_pieces = members ? nm + S.n_text / kGzCrcPiece + 1 : 0;
-        HIPCHK(c, c->gz_b64.ensure(2 * nc + n + 1 + (members ? 2 * n + 1 + max_pieces + 1 : 0))); HIPCHK(c, c->gz_b32.ensure(2 * n + max_pieces));
-        if (members) HIPCHK(c, c->gz_ends.ensure(3 * (nm ? nm : 1)));
-        HIPCHK(c, c->gz_sym.ensure(S.n_text)); HIPCHK(c, c->gz_win.ensure(n * (uint64_t)kGzWindow));
-        HIPCHK(c, c->z_verdict.ensure(1)); HIPCHK(c, c->z_h_verdict.ensure(1));
-        GzJob J{};
-        J.d = d_in + G.d_off; J.G = G;
-        J.start = c->gz_b64.p; J.end_bit = c->gz_b64.p + nc;
-        J.n_chain = n; J.off = c->gz_b64.p + 2 * nc; J.chain = c->gz_b32.p; J.crc_part = c->gz_b32.p + n;
-        J.sym = c->gz_sym.p; J.win = c->gz_win.p; J.out = d_out; J.verdict = c->z_verdict.p;
-        if (members) {
-            static_assert(sizeof(GzEnd) == 24 && alignof(GzEnd) == 8, "GzEnd is three words");
-            uint64_t *pl = c->gz_b64.p + 2 * nc + n + 1;
-            J.slot = pl; J.m0 = pl + n + 1; J.piece = pl + 2 * n + 1; J.crc_piece = c->gz_b32.p + 2 * n;
-            J.ends = reinterpret_cast<GzEnd *>(c->gz_ends.p);
-            HIPCHK(c, hipMemcpyAsync(pl, places.data(), (2 * n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(c, hipMemcpyAsync(J.start, S.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(J.end_bit, S.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->gz_b64.p + 2 * nc, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->gz_b32.p, S.chain.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
-        const bool timed = c->timing_level >= 1;
-        if (timed) {
-            for (auto &e : c->ev_gz_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-            HIPCHK(c, hipEventRecord(c->ev_gz_time[2], c->stream));
-        }
-        HIPCHK(c, launch_gz_decode(J, c->stream, members));
-        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[3], c->stream));
-        HIPCHK(c, launch_gz_windows(J, c->stream));
-        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[4], c->stream));
-        HIPCHK(c, launch_gz_narrow(J, c->stream, members));
-        std::vector<uint64_t> piece;
-        std::vector<uint32_t> mcrc, misz;
-        if (members) {
-            // the records come down (the stream is waited for: decode is done, narrow may still run), the member table and the
-            // pieces are made, the pieces' bounds go up for k_gz_member_crc; narrow's time then includes that round trip
-            std::vector<GzEnd> ends(nm ? nm : 1);
-            HIPCHK(c, hipMemcpyAsync(ends.data(), J.ends, nm * sizeof(GzEnd), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            S.in_off.assign(nm + 1, 0); S.text_off.assign(nm + 1, 0); mcrc.assign(nm, 0); misz.assign(nm, 0);
-            gz_member_table(S.M, S.n_file, off.data(), places.data(), n, ends.data(), S.in_off.data(), S.text_off.data(), mcrc.data(), misz.data());
-            for (uint64_t m = 0; m < nm; m++) {
-                if (S.text_off[m + 1] < S.text_off[m] || S.text_off[m + 1] > S.n_text) return CRASS_ERR_STATE;      // (a record nobody wrote)
-                for (uint64_t p = S.text_off[m]; p < S.text_off[m + 1]; p += kGzCrcPiece) piece.push_back(p);
-            }
-            piece.push_back(S.n_text);
-            if (piece.size() - 1 > max_pieces) return CRASS_ERR_STATE;
-            J.n_pieces = piece.size() - 1;
-            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(J.piece), piece.data(), piece.size() * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, launch_gz_member_crc(J, c->stream));
-        }
-        if (timed) HIPCHK(c, hipEventRecord(c->ev_gz_time[5], c->stream));
-        std::vector<uint32_t> crc_piece(members ? piece.size() : 1, 0);
-        if (members && J.n_pieces) HIPCHK(c, hipMemcpyAsync(crc_piece.data(), J.crc_piece, J.n_pieces * 4, hipMemcpyDeviceToHost, c->stream));
-        if (!members) HIPCHK(c, hipMemcpyAsync(crc_part.data(), J.crc_part, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (timed) {
-            for (int k = 2; k < 5; k++) {
-                HIPCHK(c, hipEventElapsedTime(&c->last_gzip_ms[k], c->ev_gz_time[k], c->ev_gz_time[k + 1]));
-                c->last_inflate_ms += c->last_gzip_ms[k];
-            }
-        }
-        const uint64_t w = c->z_h_verdict.p[0];
-        if (w != kBzNoOffence) {
-            const uint64_t k = S.chain[w];
-            return decline(BZ_MARKER, k, G.d_off + (S.start[k] >> 3));
-        }
-        if (members) {
-            // a member's pieces joined in text order (an empty member has none: CRC 0)
-            std::vector<uint32_t> got(nm, 0);
-            uint64_t q = 0;
-            for (uint64_t m = 0; m < nm; m++)
-                for (; q + 1 < piece.size() && piece[q] < S.text_off[m + 1]; q++) got[m] = gz_crc_join(got[m], crc_piece[q], piece[q + 1] - piece[q]);
-            GzVerdict mv{};
-            if (gz_member_verdict(nm, S.in_off.data(), S.text_off.data(), mcrc.data(), misz.data(), got.data(), &mv) != BZ_OK)
-                return decline(mv.reason, mv.member, mv.in_pos);
-            return CRASS_OK;
-        }
-        uint32_t crc = 0;
-        for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
-        if (crc != S.M.crc) return decline(BZ_CRC, 0, 0);
-    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
-    return CRASS_OK;
-}
-
-static int inflate_gzip_device_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
-                                    uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, bool mode, crass_bgzf_verdict *v)
-{
-    if (v) memset(v, 0, sizeof(*v));
-    if (plan) memset(plan, 0, sizeof(*plan));
-    if (members) memset(members, 0, sizeof(*members));
-    if (n_text) *n_text = 0;
-    if (!c || !n_text || (n_in && !d_in) || (out_cap && !d_out)) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    GzState S;
-    int s = gzip_count_impl(c, d_in, n_in, chunk_bytes, S, plan, v, mode);
-    if (s == CRASS_OK) {
-        *n_text = S.n_text;
-        if (out_cap < S.n_text) s = CRASS_ERR_OVERFLOW;       // (known before anything is stored)
-        else s = gzip_decode_impl(c, d_in, S, d_out, v);
-        if (s == CRASS_OK && mode) s = gz_members_fill(members, S.in_off.size() - 1, S.in_off.data(), S.text_off.data());
-    }
-    gzip_release(c);
-    c->z_verdict.release();
-    return s;
-}
-
-int crass_hip_inflate_gzip_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
-                                  uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
-{
-    return inflate_gzip_device_impl(c, d_in, n_in, chunk_bytes, d_out, out_cap, n_text, plan, nullptr, false, v);
-}
-
-int crass_hip_inflate_gzip_members_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out, uint64_t out_cap,
-                                          uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
-{
-    return inflate_gzip_device_impl(c, d_in, n_in, chunk_bytes, d_out, out_cap, n_text, plan, members, true, v);
-}
-
-static int load_fastx_gzip_impl(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
-                                uint64_t d_text_cap, crass_fastx_layout *out, crass_gzip_members *members, bool mode, crass_bgzf_verdict *v)
-{
-    if (out) memset(out, 0, sizeof(*out));
-    if (v) memset(v, 0, sizeof(*v));
-    if (members) memset(members, 0, sizeof(*members));
-    if (!c || pad_uniform < 0 || pad_uniform > 2 || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
-    drop_arena(c);
-    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
-    auto run = [&]() -> int {
-        HIPCHK(c, c->z_raw.ensure(n_bytes + 16));
-        const int up = upload_staged(c, bytes, n_bytes, c->z_raw.p);
-        if (up) return up;
-        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        GzState S;
-        int s = gzip_count_impl(c, c->z_raw.p, n_bytes, 0, S, nullptr, v, mode);
-        if (s) return s;
-        if (d_text && d_text_cap < S.n_text) return CRASS_ERR_INVALID_ARG;
-        if (!d_text) { HIPCHK(c, c->z_text.ensure(S.n_text + 16)); d_text = c->z_text.p; }
-        s = gzip_decode_impl(c, c->z_raw.p, S, d_text, v);
-        if (s) return s;
-        if (mode) { s = gz_members_fill(members, S.in_off.size() - 1, S.in_off.data(), S.text_off.data()); if (s) return s; }
-        gzip_release(c);
-        c->z_raw.release();                             // (the compressed bytes are done with: the scan's arrays may have their room)
-        return load_fastx_impl(c, nullptr, d_text, S.n_text, pad_uniform, read_index_base, out);
-    };
-    const int s = run();
-    // the scratch goes back on every way out, as in load_fastx_common
-    gzip_release(c);
-    inflate_bgzf_release(c);
-    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
-    c->x_rec_pos.release(); c->x_seq_off.release();
-    c->t_off.release();
-    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
-    if (s && members) crass_gzip_members_free(members);      // (a scan decline behind an accepted inflate: no table without reads)
-    return s;
-}
-
-int crass_hip_load_fastx_gzip(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base, uint8_t *d_text,
-                              uint64_t d_text_cap, crass_fastx_layout *out, crass_bgzf_verdict *v)
-{
-    return load_fastx_gzip_impl(c, bytes, n_bytes, pad_uniform, read_index_base, d_text, d_text_cap, out, nullptr, false, v);
-}
-
-int crass_hip_load_fastx_gzip_members(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
-                                      uint8_t *d_text, uint64_t d_text_cap, crass_fastx_layout *out, crass_gzip_members *members,
-                                      crass_bgzf_verdict *v)
-{
-    return load_fastx_gzip_impl(c, bytes, n_bytes, pad_uniform, read_index_base, d_text, d_text_cap, out, members, true, v);
-}
-
-int crass_hip_set_gzip_on_device(crass_hip_ctx *c, int on)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    c->gzip_on_device = on == CRASS_GZIP_ON_DEVICE_MEMBERS ? CRASS_GZIP_ON_DEVICE_MEMBERS : on != 0 ? CRASS_GZIP_ON_DEVICE_ONE_MEMBER : CRASS_GZIP_ON_DEVICE_OFF;
-    return CRASS_OK;
-}
-
-int crass_hip_last_gzip_ms(const crass_hip_ctx *c, float *ms)
-{
-    if (!c || !ms) return CRASS_ERR_INVALID_ARG;
-    for (int k = 0; k < 5; k++) ms[k] = c->last_gzip_ms[k];
-    return CRASS_OK;
-}
-
-float crass_hip_last_inflate_ms(const crass_hip_ctx *c) { return c ? c->last_inflate_ms : 0.0f; }
-
-int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    if (!c->have_reads) return CRASS_ERR_STATE;
-    (void)hipSetDevice(c->device);
-    const uint64_t n_reads = c->cnt.n_reads, n_exc = c->cnt.n_exceptions, bytes_dev = c->cnt.bytes_reads_device;
-    reset_results(c);                                   // (pass 1's found flags are keyed by header id: earlier results are void)
-    c->cnt.n_reads = n_reads; c->cnt.n_exceptions = n_exc; c->cnt.bytes_reads_device = bytes_dev;
-    const uint64_t n = c->R.n_reads;
-    if (header_id && n) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));     // (nothing may still read the array this replaces)
-        HIPCHK(c, c->r_header_id.ensure(n));
-        HIPCHK(c, hipMemcpy(c->r_header_id.p, header_id, n * 8, hipMemcpyHostToDevice));
-        c->R.header_id = c->r_header_id.p;
-    } else c->R.header_id = nullptr;
-    return CRASS_OK;
-}
-
-// ---- header ids from a file's raw bytes on the device (fastx_names.hip) ----
-// Every check that needs no byte of the file comes first; a record position outside the input is seen by the insert launch and
-// reported before the lookup launch and before anything is installed.
-// the insert step, shared by the header ids (the table is scratch) and crass_hip_fastx_names_build_device (the table is kept):
-// table and d_rec_pos are the two arrays that make a table, the slots per record, the list of long names and the control words
-// are the context's scratch.  Queued on return: both insert launches; ev_n_time[0] / [1] lie around them when timed.
-static int names_insert_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
-                             DevBuf<unsigned long long> &table, DevBuf<uint64_t> &d_rec_pos, HidJob &J)
-{
-    uint64_t slots = 2;
-    while (slots < 2 * n) slots <<= 1;
-    HIPCHK(c, d_rec_pos.ensure(n)); HIPCHK(c, c->n_ids.ensure(n)); HIPCHK(c, c->n_long.ensure(n));
-    HIPCHK(c, c->n_ctl.ensure(4)); HIPCHK(c, c->n_h_ctl.ensure(4)); HIPCHK(c, table.ensure(slots));
-    J = HidJob{};
-    J.bytes = d_bytes; J.n_bytes = n_bytes; J.rec_pos = d_rec_pos.p; J.n_reads = n;
-    J.table = table.p; J.mask = slots - 1; J.hash_bits = c->env.hid_hash_bits;
-    J.ids = c->n_ids.p; J.long_list = c->n_long.p;
-    J.ctl = reinterpret_cast<uint32_t *>(c->n_ctl.p); J.n_repeated = reinterpret_cast<unsigned long long *>(c->n_ctl.p + 2);
-    HIPCHK(c, hipMemcpyAsync(d_rec_pos.p, rec_pos, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(table.p, 0xFF, slots * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->n_ctl.p, 0, 32, c->stream));
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_n_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_n_time[0], c->stream));
-    }
-    HIPCHK(c, launch_hid_insert(J, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->n_h_ctl.p, c->n_ctl.p, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));         // (how many long names there are sizes the wave kernel's launch)
-    const uint32_t *h_ctl = reinterpret_cast<const uint32_t *>(c->n_h_ctl.p);
-    if (h_ctl[1]) return CRASS_ERR_INVALID_ARG;         // a rec_pos[r] >= n_bytes
-    if (h_ctl[0]) HIPCHK(c, launch_hid_insert_long(J, h_ctl[0], c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[1], c->stream));
-    return CRASS_OK;
-}
-
-static int header_ids_device_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
-                                  uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
-{
-    (void)hipSetDevice(c->device);
-    for (auto &m : c->last_hid_ms) m = 0;
-    HidJob J{};
-    const int ins = names_insert_impl(c, d_bytes, n_bytes, rec_pos, n, c->n_table, c->n_rec_pos, J);
-    if (ins) return ins;
-    const bool timed = c->timing_level >= 1;
-    HIPCHK(c, launch_hid_lookup(J, c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_n_time[2], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->n_h_ctl.p + 2, c->n_ctl.p + 2, 8, hipMemcpyDeviceToHost, c->stream));
-    if (header_id_out) HIPCHK(c, hipMemcpyAsync(header_id_out, c->n_ids.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (timed) {
-        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[0], c->ev_n_time[0], c->ev_n_time[2]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[1], c->ev_n_time[0], c->ev_n_time[1]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_hid_ms[2], c->ev_n_time[1], c->ev_n_time[2]));
-    }
-    if (n_repeated_out) *n_repeated_out = c->n_h_ctl.p[2];
-    if (install) {                                      // crass_hip_set_header_ids, the array from where it is
-        const uint64_t n_reads = c->cnt.n_reads, n_exc = c->cnt.n_exceptions, bytes_dev = c->cnt.bytes_reads_device;
-        reset_results(c);
-        c->cnt.n_reads = n_reads; c->cnt.n_exceptions = n_exc; c->cnt.bytes_reads_device = bytes_dev;
-        HIPCHK(c, c->r_header_id.ensure(n));
-        HIPCHK(c, hipMemcpyAsync(c->r_header_id.p, c->n_ids.p, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->R.header_id = c->r_header_id.p;
-    }
-    return CRASS_OK;
-}
-
-int crass_hip_fastx_header_ids_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                                      uint64_t *header_id_out, int install, uint64_t *n_repeated_out)
-{
-    if (!c || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
-    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (a slot holds a 32-bit index, all-ones is the free slot's)
-    if (install) {
-        if (!c->have_reads) return CRASS_ERR_STATE;
-        if (n_reads != c->R.n_reads) return CRASS_ERR_INVALID_ARG;
-    }
-    if (n_repeated_out) *n_repeated_out = 0;
-    if (n_reads == 0) return install ? crass_hip_set_header_ids(c, nullptr) : CRASS_OK;
-    (void)hipSetDevice(c->device);
-    if (install) HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing may still read the array this replaces)
-    const int s = header_ids_device_impl(c, d_bytes, n_bytes, rec_pos, n_reads, header_id_out, install, n_repeated_out);
-    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out
-    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
-    return s;
-}
-
-float crass_hip_last_header_ids_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 3 ? c->last_hid_ms[part] : 0.0f; }
-
-// ---- the name table kept on the device: names in, first read index out (fastx_names.hip) ----
-// The table is built aside and replaces the one before only when the insert step accepted every record position: a build that
-// fails leaves the context as it was.
-static int names_build_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
-                            DevBuf<unsigned long long> &table, DevBuf<uint64_t> &d_rec_pos, uint64_t *mask_out)
-{
-    HidJob J{};
-    const int ins = names_insert_impl(c, d_bytes, n_bytes, rec_pos, n, table, d_rec_pos, J);
-    if (ins) return ins;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->timing_level >= 1) HIPCHK(c, hipEventElapsedTime(&c->last_names_ms[0], c->ev_n_time[0], c->ev_n_time[1]));
-    *mask_out = J.mask;
-    return CRASS_OK;
-}
-
-int crass_hip_fastx_names_build_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    const bool on_arena = !d_bytes && !rec_pos;
-    if (on_arena) {                                     // the arena and layout of the last crass_hip_load_fastx_files
-        if (!c->have_arena || !c->have_reads) return CRASS_ERR_STATE;
-        d_bytes = c->fa_arena.p; n_bytes = c->fa_bytes; rec_pos = c->x_h_rec_pos.p; n_reads = c->R.n_reads;
-    }
-    if (n_reads && (!d_bytes || !rec_pos)) return CRASS_ERR_INVALID_ARG;
-    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (a slot holds a 32-bit index, all-ones is the free slot's)
-    (void)hipSetDevice(c->device);
-    c->last_names_ms[0] = 0;
-    DevBuf<unsigned long long> table; DevBuf<uint64_t> d_rec_pos;
-    uint64_t mask = 0;
-    const int s = n_reads ? names_build_impl(c, d_bytes, n_bytes, rec_pos, n_reads, table, d_rec_pos, &mask) : CRASS_OK;
-    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out
-    c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
-    if (s) { table.release(); d_rec_pos.release(); return s; }
-    names_drop(c);
-    c->nt_table = table; c->nt_rec_pos = d_rec_pos;     // (DevBuf owns nothing by itself: the context's release gives them back)
-    c->have_names = true; c->nt_on_arena = on_arena;
-    c->nt_bytes = d_bytes; c->nt_n_bytes = n_bytes; c->nt_n_reads = n_reads; c->nt_mask = mask;
-    return CRASS_OK;
-}
-
-static int names_find_impl(crass_hip_ctx *c, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, const std::vector<uint32_t> &longs,
-                           uint64_t *first_out)
-{
-    const uint64_t total = name_off[n_names];
-    HIPCHK(c, c->nq_names.ensure(total)); HIPCHK(c, c->nq_off.ensure(n_names + 1)); HIPCHK(c, c->nq_out.ensure(n_names));
-    HIPCHK(c, c->nq_long.ensure(longs.size()));
-    HidFindJob J{};
-    J.bytes = c->nt_bytes; J.n_bytes = c->nt_n_bytes; J.rec_pos = c->nt_rec_pos.p;
-    J.table = c->nt_table.p; J.mask = c->nt_mask; J.hash_bits = c->env.hid_hash_bits;
-    J.names = c->nq_names.p; J.name_off = c->nq_off.p; J.n_names = n_names; J.long_list = c->nq_long.p; J.first_out = c->nq_out.p;
-    if (total) HIPCHK(c, hipMemcpyAsync(c->nq_names.p, names, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->nq_off.p, name_off, (n_names + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (!longs.empty()) HIPCHK(c, hipMemcpyAsync(c->nq_long.p, longs.data(), longs.size() * 4, hipMemcpyHostToDevice, c->stream));
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_nq_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_nq_time[0], c->stream));
-    }
-    HIPCHK(c, launch_hid_find(J, c->stream));
-    if (!longs.empty()) HIPCHK(c, launch_hid_find_long(J, (uint32_t)longs.size(), c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_nq_time[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(first_out, c->nq_out.p, n_names * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (timed) HIPCHK(c, hipEventElapsedTime(&c->last_names_ms[1], c->ev_nq_time[0], c->ev_nq_time[1]));
-    return CRASS_OK;
-}
-
-int crass_hip_fastx_names_find(crass_hip_ctx *c, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out)
-{
-    if (!c || (n_names && (!name_off || !first_out))) return CRASS_ERR_INVALID_ARG;
-    for (uint64_t k = 0; k < n_names; k++) if (name_off[k + 1] < name_off[k]) return CRASS_ERR_INVALID_ARG;
-    if (n_names && name_off[n_names] && !names) return CRASS_ERR_INVALID_ARG;
-    if (n_names >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (the list of long queries holds 32-bit indices)
-    if (!c->have_names) return CRASS_ERR_STATE;
-    c->last_names_ms[1] = 0;
-    if (n_names == 0) return CRASS_OK;
-    if (c->nt_n_reads == 0) { for (uint64_t k = 0; k < n_names; k++) first_out[k] = CRASS_NAME_NOT_FOUND; return CRASS_OK; }
-    std::vector<uint32_t> longs;
-    try {
-        const uint64_t lane_end = hid_lane_end();
-        for (uint64_t k = 0; k < n_names; k++) if (name_off[k + 1] - name_off[k] >= lane_end) longs.push_back((uint32_t)k);
-    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
-    (void)hipSetDevice(c->device);
-    const int s = names_find_impl(c, names, name_off, n_names, longs, first_out);
-    (void)hipStreamSynchronize(c->stream);              // the scratch goes back on every way out; the table stays
-    c->nq_names.release(); c->nq_off.release(); c->nq_out.release(); c->nq_long.release();
-    return s;
-}
-
-int crass_hip_fastx_names_drop(crass_hip_ctx *c)
-{
-    if (!c) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    names_drop(c);
-    return CRASS_OK;
-}
-
-float crass_hip_last_names_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 2 ? c->last_names_ms[part] : 0.0f; }
-
-// ---- header lines of selected records from a file's raw bytes on the device (fastx_names.hip) ----
-// d_user == nullptr: the host route (the lines come back into pinned memory, *out points at it); else the caller's device buffer
-// of cap bytes, the offsets into off_user.  Every check comes before the first launch; the resident set is not involved.
-static int header_lines_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                             const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
-                             uint32_t *name_len_out)
-{
-    for (uint64_t k = 0; k < n; k++) if (idx[k] >= n_reads || rec_pos[idx[k]] >= n_bytes) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, c->hl_h_off.ensure(n + 1));
-    uint64_t *off = c->hl_h_off.p;
-    off[0] = 0;
-    if (n) {
-        HIPCHK(c, c->hl_h_src.ensure(n)); HIPCHK(c, c->hl_h_len.ensure(2 * n));
-        HIPCHK(c, c->hl_src.ensure(n)); HIPCHK(c, c->hl_len.ensure(2 * n));
-        for (uint64_t k = 0; k < n; k++) c->hl_h_src.p[k] = rec_pos[idx[k]] + 1;
-    }
-    HlJob J{};
-    J.bytes = d_bytes; J.n_bytes = n_bytes; J.src = c->hl_src.p; J.n = n;
-    J.line_len = c->hl_len.p; J.name_len = c->hl_len.p + n;
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->hl_src.p, c->hl_h_src.p, n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, launch_hl_measure(J, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->hl_h_len.p, c->hl_len.p, 2 * n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the lengths size the result)
-        for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + c->hl_h_len.p[k];
-        if (name_len_out) memcpy(name_len_out, c->hl_h_len.p + n, n * 4);
-    }
-    const uint64_t total = off[n];
-    if (off_user) memcpy(off_user, off, (n + 1) * 8);
-    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
-    if (!d_user) HIPCHK(c, c->hl_h_chars.ensure(total));
-    if (out) { out->n = n; out->chars = c->hl_h_chars.p; out->off = off; }
-    if (!total) return CRASS_OK;
-    HIPCHK(c, c->hl_off.ensure(n + 1));
-    if (!d_user) HIPCHK(c, c->hl_chars.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(c->hl_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    J.off = c->hl_off.p; J.total = total; J.out = d_user ? d_user : c->hl_chars.p;
-    HIPCHK(c, launch_hl_copy(J, c->stream));
-    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->hl_h_chars.p, c->hl_chars.p, total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CRASS_OK;
-}
-
-static int header_lines_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                               const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
-                               uint32_t *name_len_out)
-{
-    if (!c || (n && !idx) || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
-    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
-    const int s = header_lines_impl(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_user, cap, off_user, out, name_len_out);
-    (void)hipStreamSynchronize(c->stream);              // the device scratch goes back on every way out; the pinned result stays
-    c->hl_src.release(); c->hl_off.release(); c->hl_len.release(); c->hl_chars.release();
-    return s;
-}
-
-int crass_hip_fetch_header_lines_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                                        const uint64_t *idx, uint64_t n, crass_text *out, uint32_t *name_len_out)
-{
-    if (!out) return CRASS_ERR_INVALID_ARG;
-    return header_lines_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, nullptr, 0, nullptr, out, name_len_out);
-}
-
-int crass_hip_fetch_header_lines_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                                           const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
-                                           uint32_t *name_len_out)
-{
-    if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
-    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
-    return header_lines_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, name_len_out);
-}
-
-// ---- several files into one resident set (fastx_scan.hip, inflate.hip, fastx_names.hip) ----
-namespace {
-struct FilesPlan {
-    struct File { bool bgzf = false, gz = false; crass_bgzf_index ix{}; GzState gzs; uint64_t n_text = 0; int32_t format = 0; };
-    std::vector<File> f;
-    ~FilesPlan() { for (auto &x : f) if (x.bgzf) crass_bgzf_index_free(&x.ix); }
-};
-}
-
-static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
-                                 crass_fastx_files_layout *out)
-{
-    // a decline found before the scan (format, compression) waits here: a file in front of it may still offend in the scan
-    int32_t pend_file = -1, pend_reason = 0; uint64_t pend_pos = 0; crass_bgzf_verdict pend_v{};
-    auto decline = [&](uint32_t file, int32_t reason, uint64_t pos, const crass_bgzf_verdict *v) {
-        if (out) { out->decline_file = (int32_t)file; out->decline_reason = reason; out->decline_pos = pos; if (v) out->bgzf = *v; }
-        return CRASS_ERR_UNSUPPORTED;
-    };
-    // 1. what every file is, and how much text it holds (host: first bytes, BGZF index)
-    FilesPlan P;
-    P.f.resize(n_files);
-    uint32_t nf = n_files;
-    for (uint32_t f = 0; f < nf; f++) {
-        FilesPlan::File &F = P.f[f];
-        const uint8_t *b = bytes[f];
-        const uint64_t n = n_bytes[f];
-        if (n >= 2 && b[0] == 0x1F && b[1] == 0x8B) {
-            const int s = crass_bgzf_index_host(b, n, &F.ix);
-            if (s == CRASS_ERR_UNSUPPORTED && c->gzip_on_device) {
-                // plain gzip (crass_hip_set_gzip_on_device; of any number of members with CRASS_GZIP_ON_DEVICE_MEMBERS): its bytes go up once for the count step, which sizes its share of the arena
-                HIPCHK(c, c->z_raw.ensure(n + 16));
-                const int up = upload_staged(c, b, n, c->z_raw.p);
-                if (up) return up;
-                HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-                crass_bgzf_verdict v{};
-                const int gs = gzip_count_impl(c, c->z_raw.p, n, 0, F.gzs, nullptr, &v, c->gzip_on_device == CRASS_GZIP_ON_DEVICE_MEMBERS);
-                if (gs == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = v; nf = f; break; }
-                if (gs) return gs;
-                F.gz = true; F.n_text = F.gzs.n_text;
-                if (F.n_text == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
-                continue;
-            }
-            if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_v = F.ix.decline; nf = f; break; }
-            if (s) return s;
-            F.bgzf = true; F.n_text = F.ix.out_off[F.ix.n_members];
-            if (F.n_text == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
-        } else {
-            if (n == 0) { pend_file = (int32_t)f; pend_reason = FX_EMPTY; nf = f; break; }
-            if (!fx_is_hdr_char(b[0])) { pend_file = (int32_t)f; pend_reason = FX_FIRST_BYTE; nf = f; break; }
-            F.n_text = n; F.format = b[0];
-        }
-    }
-    auto pending = [&]() { return decline((uint32_t)pend_file, pend_reason, pend_pos, pend_v.reason ? &pend_v : nullptr); };
-    if (nf == 0) return pending();
-    // 2. the arena; every file's bytes up, a BGZF file inflated into its place; the first two scan kernels of file f are queued
-    //    before file f + 1 is staged
-    std::vector<uint64_t> base(nf + 1, 0), tile0(nf + 1, 0);
-    for (uint32_t f = 0; f < nf; f++) base[f + 1] = base[f] + P.f[f].n_text + 1;
-    HIPCHK(c, c->fa_arena.ensure(base[nf] + 16));
-    uint8_t *arena = c->fa_arena.p;
-    for (uint32_t f = 0; f < nf; f++) {
-        tile0[f + 1] = tile0[f] + fastx_n_tiles(arena + base[f], P.f[f].n_text);
-    }
-    if (tile0[nf] > 0x7FFFFFFFull) return CRASS_ERR_UNSUPPORTED;
-    HIPCHK(c, c->x_tiles.ensure(tile0[nf])); HIPCHK(c, c->x_base.ensure(tile0[nf]));
-    HIPCHK(c, c->x_tot.ensure(5 * (uint64_t)nf)); HIPCHK(c, c->x_h_tot.ensure(5 * (uint64_t)nf));      // [4 f ..): the totals; [4 nf + f]: the verdict
-    std::vector<FxJob> jobs(nf);
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_x_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_x_time[0], c->stream));
-    }
-    for (uint32_t f = 0; f < nf; f++) {
-        FilesPlan::File &F = P.f[f];
-        if (f) HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // (the staged buffers are the file before's until its last copy is done)
-        if (F.bgzf || F.gz) {
-            HIPCHK(c, c->z_raw.ensure(n_bytes[f] + 16));
-            const int up = upload_staged(c, bytes[f], n_bytes[f], c->z_raw.p);
-            if (up) return up;
-            crass_bgzf_verdict v{};
-            // (both wait for the stream: z_raw may be used again)
-            const int s = F.gz ? gzip_decode_impl(c, c->z_raw.p, F.gzs, arena + base[f], &v) : inflate_bgzf_impl(c, c->z_raw.p, &F.ix, arena + base[f], &v);
-            if (s == CRASS_ERR_UNSUPPORTED) { pend_file = (int32_t)f; pend_reason = 0; pend_v = v; nf = f; break; }
-            if (s) return s;
-            HIPCHK(c, hipMemcpy(&F.format, arena + base[f], 1, hipMemcpyDeviceToHost));
-            F.format &= 0xFF;
-            if (!fx_is_hdr_char((uint8_t)F.format)) { pend_file = (int32_t)f; pend_reason = FX_FIRST_BYTE; pend_v = crass_bgzf_verdict{}; nf = f; break; }
-        } else {
-            const int up = upload_staged(c, bytes[f], n_bytes[f], arena + base[f]);
-            if (up) return up;
-        }
-        FxJob &J = jobs[f];
-        J = FxJob{};
-        J.bytes = arena + base[f]; J.n = F.n_text; J.lead = (uint32_t)((uintptr_t)J.bytes & 15u); J.format = F.format;
-        J.n_tiles = tile0[f + 1] - tile0[f];
-        J.tiles = c->x_tiles.p + tile0[f]; J.base = c->x_base.p + tile0[f]; J.tot = c->x_tot.p + 4 * (uint64_t)f;
-        HIPCHK(c, launch_fx_summary(J, c->stream));
-        HIPCHK(c, launch_fx_tile_scan(J, c->stream));
-    }
-    if (nf == 0) return pending();
-    for (uint32_t f = 0; f < nf; f++) HIPCHK(c, hipMemsetAsync(arena + base[f + 1] - 1, 0x0A, 1, c->stream));      // the '\n' behind every file
-    const uint32_t nf_alloc = (uint32_t)jobs.size();          // (the verdict words lie behind the totals of every planned file)
-    HIPCHK(c, hipMemcpyAsync(c->x_h_tot.p, c->x_tot.p, 4 * (uint64_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the record counts size the next kernels' arrays)
-    // 3. every file emits into one text and one pair of per-record arrays
-    std::vector<uint64_t> rbase(nf + 1, 0), tbase(nf + 1, 0);
-    for (uint32_t f = 0; f < nf; f++) { rbase[f + 1] = rbase[f] + c->x_h_tot.p[4 * f + 1]; tbase[f + 1] = tbase[f] + c->x_h_tot.p[4 * f + 2]; }
-    const uint64_t nr = rbase[nf], total_seq = tbase[nf];
-    if (nr >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (the name table holds 32-bit indices)
-    HIPCHK(c, c->x_text.ensure(total_seq + 32));
-    HIPCHK(c, c->x_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_seq_off.ensure(nr + 1));
-    HIPCHK(c, c->x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, c->x_h_seq_off.ensure(nr + 1));
-    unsigned long long *d_verdict = reinterpret_cast<unsigned long long *>(c->x_tot.p + 4 * (uint64_t)nf_alloc);
-    HIPCHK(c, hipMemsetAsync(d_verdict, 0xFF, 8 * (uint64_t)nf, c->stream));
-    for (uint32_t f = 0; f < nf; f++) {
-        FxJob &J = jobs[f];
-        J.n_lines = c->x_h_tot.p[4 * f]; J.n_reads = rbase[f + 1] - rbase[f];
-        J.text = c->x_text.p; J.text_base = tbase[f]; J.text_cap = tbase[f + 1];
-        J.rec_pos = c->x_rec_pos.p; J.seq_off = c->x_seq_off.p; J.read_base = rbase[f]; J.arena_base = base[f];
-        J.verdict = d_verdict + f;
-        HIPCHK(c, launch_fx_emit(J, c->stream));
-    }
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_x_time[1], c->stream));
-    uint64_t *h_verdict = c->x_h_tot.p + 4 * (uint64_t)nf_alloc;
-    HIPCHK(c, hipMemcpyAsync(h_verdict, d_verdict, 8 * (uint64_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (nr) {
-        HIPCHK(c, hipMemcpyAsync(c->x_h_rec_pos.p, c->x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->x_h_seq_off.p, c->x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x_time[0], c->ev_x_time[1]));
-        c->last_scan_ms = ms;
-    }
-    // 4. the verdict: the first file in order that offends
-    uint64_t *rec_pos = c->x_h_rec_pos.p, *seq_off = c->x_h_seq_off.p;
-    rec_pos[nr] = base[nf] - 1; seq_off[nr] = total_seq;
-    uint64_t max_len = 0;
-    for (uint32_t f = 0; f < nf; f++) {
-        const uint64_t verdict = h_verdict[f];
-        if (verdict != kFxNoOffence) return decline(f, (int32_t)(verdict & 0xFF), verdict >> 8, nullptr);
-        const uint64_t seq_f = tbase[f + 1] - tbase[f];
-        if (rbase[f + 1] == rbase[f] || c->x_h_tot.p[4 * f + 3] != (P.f[f].format == 0x40 ? seq_f : 0)) return CRASS_ERR_STATE;      // (never expected, as in load_fastx_impl)
-        for (uint64_t r = rbase[f]; r < rbase[f + 1]; r++) {
-            const uint64_t l = (r + 1 < rbase[f + 1] ? seq_off[r + 1] : tbase[f + 1]) - seq_off[r];
-            if (l > CRASS_HIP_MAX_READ_LEN) return decline(f, FX_READ_TOO_LONG, rec_pos[r] - base[f], nullptr);
-            max_len = std::max(max_len, l);
-        }
-    }
-    if (pend_file >= 0) return pending();
-    // 5. one pack launch over the joined text, then the header ids on the arena, installed from where they are
-    const int s = load_text_impl(c, nullptr, c->x_text.p, seq_off, nr, pad_uniform, nullptr, 0);
-    if (s) return s;
-    uint64_t n_rep = 0;
-    const int hs = header_ids_device_impl(c, arena, base[nf], rec_pos, nr, nullptr, 1, &n_rep);
-    if (hs) { c->have_reads = false; return hs; }
-    if (n_rep == 0) c->R.header_id = nullptr;           // (all names unique: as a load without header ids)
-    HIPCHK(c, c->fa_h_base.ensure(2 * ((uint64_t)nf + 1))); HIPCHK(c, c->fa_h_format.ensure(nf));
-    for (uint32_t f = 0; f <= nf; f++) { c->fa_h_base.p[f] = rbase[f]; c->fa_h_base.p[nf + 1 + f] = base[f]; }
-    for (uint32_t f = 0; f < nf; f++) c->fa_h_format.p[f] = P.f[f].format;
-    c->fa_bytes = base[nf]; c->have_arena = true;
-    if (out) {
-        out->n_reads = nr; out->max_len = (uint32_t)max_len; out->rec_pos = rec_pos; out->seq_off = seq_off;
-        out->file_read_base = c->fa_h_base.p; out->file_byte_base = c->fa_h_base.p + nf + 1; out->format = c->fa_h_format.p;
-    }
-    return CRASS_OK;
-}
-
-int crass_hip_load_fastx_files(crass_hip_ctx *c, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
-                               crass_fastx_files_layout *out)
-{
-    if (out) { memset(out, 0, sizeof(*out)); out->decline_file = -1; out->n_files = n_files; }
-    if (!c || !n_files || !bytes || !n_bytes || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
-    for (uint32_t f = 0; f < n_files; f++) if (n_bytes[f] && !bytes[f]) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    reset_results(c);
-    c->have_reads = false;                              // (declined or failed: no reads, as after a failed crass_hip_load_text)
-    drop_arena(c);
-    c->last_scan_ms = 0; c->last_pack_ms = 0; c->last_inflate_ms = 0;
-    const int s = load_fastx_files_impl(c, bytes, n_bytes, n_files, pad_uniform, out);
-    // the scratch goes back on every way out, as in load_fastx_common; the arena stays only with an accepted set
-    gzip_release(c);
-    inflate_bgzf_release(c);
-    c->x_raw.release(); c->x_text.release(); c->x_tiles.release(); c->x_base.release(); c->x_tot.release();
-    c->x_rec_pos.release(); c->x_seq_off.release();
-    c->t_off.release();
-    for (int k = 0; k < 2; k++) { c->t_dev[k].release(); c->t_pin[k].release(); }
-    c->n_table.release(); c->n_rec_pos.release(); c->n_ids.release(); c->n_long.release(); c->n_ctl.release();
-    if (s) { c->have_reads = false; drop_arena(c); }
-    return s;
-}
-
-int crass_hip_resident_fastx(const crass_hip_ctx *c, const uint8_t **d_bytes, uint64_t *n_bytes)
-{
-    if (!c || !d_bytes || !n_bytes) return CRASS_ERR_INVALID_ARG;
-    *d_bytes = nullptr; *n_bytes = 0;
-    if (!c->have_arena || !c->have_reads) return CRASS_ERR_STATE;
-    *d_bytes = c->fa_arena.p; *n_bytes = c->fa_bytes;
-    return CRASS_OK;
-}
-
-// ---- quality strings of selected records from raw bytes on the device (fastx_names.hip) ----
-// the shape of header_lines_impl: every check comes before the first launch; the resident set is not involved
-static int quality_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                        const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out, uint8_t *has_qual_out)
-{
-    for (uint64_t k = 0; k < n; k++) if (idx[k] >= n_reads || rec_pos[idx[k]] >= n_bytes) return CRASS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, c->ql_h_off.ensure(n + 1));
-    uint64_t *off = c->ql_h_off.p;
-    off[0] = 0;
-    QlJob J{};
-    J.bytes = d_bytes; J.n_bytes = n_bytes; J.n = n;
-    if (n) {
-        HIPCHK(c, c->ql_h_src.ensure(2 * n)); HIPCHK(c, c->ql_h_len.ensure(2 * n));
-        HIPCHK(c, c->ql_src.ensure(2 * n)); HIPCHK(c, c->ql_start.ensure(n)); HIPCHK(c, c->ql_len.ensure(2 * n));
-        for (uint64_t k = 0; k < n; k++) { c->ql_h_src.p[k] = rec_pos[idx[k]]; c->ql_h_src.p[n + k] = std::min(rec_pos[idx[k] + 1], n_bytes); }
-        J.src = c->ql_src.p; J.lim = c->ql_src.p + n; J.start = c->ql_start.p; J.len = c->ql_len.p; J.flags = c->ql_len.p + n;
-        HIPCHK(c, hipMemcpyAsync(c->ql_src.p, c->ql_h_src.p, 2 * n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, launch_ql_measure(J, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->ql_h_len.p, c->ql_len.p, 2 * n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the lengths size the result)
-        for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + c->ql_h_len.p[k];
-        if (has_qual_out) for (uint64_t k = 0; k < n; k++) has_qual_out[k] = (uint8_t)(c->ql_h_len.p[n + k] & 1u);
-    }
-    const uint64_t total = off[n];
-    if (off_user) memcpy(off_user, off, (n + 1) * 8);
-    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
-    if (!d_user) HIPCHK(c, c->ql_h_chars.ensure(total));
-    if (out) { out->n = n; out->chars = c->ql_h_chars.p; out->off = off; }
-    if (!total) return CRASS_OK;
-    HIPCHK(c, c->ql_off.ensure(n + 1));
-    if (!d_user) HIPCHK(c, c->ql_chars.ensure(total));
-    HIPCHK(c, hipMemcpyAsync(c->ql_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    J.off = c->ql_off.p; J.total = total; J.out = d_user ? d_user : c->ql_chars.p;
-    HIPCHK(c, launch_ql_copy(J, c->stream));
-    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->ql_h_chars.p, c->ql_chars.p, total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CRASS_OK;
-}
-
-static int quality_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                          const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out, uint8_t *has_qual_out)
-{
-    if (!c || (n && !idx) || (n_reads && (!d_bytes || !rec_pos))) return CRASS_ERR_INVALID_ARG;
-    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
-    const int s = quality_impl(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_user, cap, off_user, out, has_qual_out);
-    (void)hipStreamSynchronize(c->stream);              // the device scratch goes back on every way out; the pinned result stays
-    c->ql_src.release(); c->ql_start.release(); c->ql_off.release(); c->ql_len.release(); c->ql_chars.release();
-    return s;
-}
-
-int crass_hip_fetch_quality_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                                   const uint64_t *idx, uint64_t n, crass_text *out, uint8_t *has_qual_out)
-{
-    if (!out) return CRASS_ERR_INVALID_ARG;
-    return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, nullptr, 0, nullptr, out, has_qual_out);
-}
-
-int crass_hip_fetch_quality_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
-                                      const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out, uint8_t *has_qual_out)
-{
-    if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
-    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
-    return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, has_qual_out);
-}
-
-int crass_hip_get_packed(const crass_hip_ctx *c, crass_packed *out)
-{
-    if (!c || !out) return CRASS_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    if (!c->have_reads) return CRASS_ERR_STATE;
-    (void)hipSetDevice(c->device);
-    const DevReads &R = c->R;
-    const uint64_t n = R.n_reads, ne = R.n_exc;
-    auto get = [&](void *dst, const void *src, uint64_t bytes) {
-        if (!bytes) return CRASS_OK;
-        const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->last_hip = (int)e; return CRASS_ERR_HIP; }
-        return CRASS_OK;
-    };
-    // the word count: n strides, or the last read's first word and its own words
-    uint64_t total_words = n * (uint64_t)R.stride_words;
-    if (!R.stride_words && n) {
-        uint64_t w_last = 0; uint32_t l_last = R.uniform_len;
-        int s = get(&w_last, R.word_off + (n - 1), 8);
-        if (!s && !R.uniform_len) s = get(&l_last, R.lengths + (n - 1), 4);
-        if (s) return s;
-        total_words = w_last + (l_last + 15) / 16;
-    }
-    uint64_t exc_total = 0;
-    if (ne) { const int s = get(&exc_total, R.exc_off + ne, 8); if (s) return s; }
-    crass_packed pk;
-    PackedArrays a{};
-    int s = packed_alloc(total_words + 4, R.stride_words ? 0 : n + 1, R.uniform_len ? 0 : n, ne, ne + 1, exc_total, R.header_id ? n : 0, &pk, &a);
-    if (s) return s;
-    s = get(a.packed, R.packed, total_words * 4);
-    if (!s) memset(a.packed + total_words, 0, 16);
-    if (!s && a.word_off) { s = get(a.word_off, R.word_off, n * 8); a.word_off[n] = total_words; }
-    if (!s && a.lengths) s = get(a.lengths, R.lengths, n * 4);
-    if (!s && ne) s = get(a.exc_read, R.exc_read, ne * 8);
-    if (!s && ne) s = get(a.exc_off, R.exc_off, (ne + 1) * 8);
-    if (!ne) a.exc_off[0] = 0;
-    if (!s && exc_total) s = get(a.exc_bytes, R.exc_bytes, exc_total);
-    if (!s && a.header_id) s = get(a.header_id, R.header_id, n * 8);
-    if (s) { crass_free_packed(&pk); return s; }
-    crass_reads &r = pk.reads;
-    r.n_reads = n; r.packed = a.packed; r.stride_words = R.stride_words; r.word_off = a.word_off; r.uniform_len = R.uniform_len; r.lengths = a.lengths;
-    r.n_exceptions = ne; r.exc_read = a.exc_read; r.exc_off = a.exc_off; r.exc_bytes = a.exc_bytes; r.header_id = a.header_id;
-    r.read_index_base = c->read_base;
-    *out = pk;
-    return CRASS_OK;
-}
-
-// ---- text of selected reads out of the resident set (k_fetch_text, pack.hip) ----
-// d_user == nullptr: the host route (the text comes back into pinned memory, *out points at it); else the caller's device
-// buffer of cap bytes, the offsets into off_user.  Every check comes before the first launch; the resident set is only read.
-static int fetch_text_impl(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, uint8_t *d_user, uint64_t cap,
-                           uint64_t *off_user, crass_text *out)
-{
-    if (n && !read_idx) return CRASS_ERR_INVALID_ARG;
-    if (!c->have_reads) return CRASS_ERR_STATE;
-    const DevReads &R = c->R;
-    for (uint64_t k = 0; k < n; k++) if (read_idx[k] < c->read_base || read_idx[k] - c->read_base >= R.n_reads) return CRASS_ERR_INVALID_ARG;
-    if (!R.uniform_len && c->h_lengths.size() != R.n_reads) return CRASS_ERR_STATE;      // (never expected: every load keeps them)
-    c->last_fetch_ms = 0;
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, c->f_h_off.ensure(n + 1));
-    uint64_t *off = c->f_h_off.p;
-    off[0] = 0;
-    if (n) {
-        HIPCHK(c, c->f_h_idx.ensure(n));
-        for (uint64_t k = 0; k < n; k++) {
-            const uint64_t r = read_idx[k] - c->read_base;
-            c->f_h_idx.p[k] = r;
-            off[k + 1] = off[k] + (R.uniform_len ? R.uniform_len : c->h_lengths[r]);
-        }
-    }
-    const uint64_t total = off[n];
-    if (off_user) memcpy(off_user, off, (n + 1) * 8);
-    if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
-    if (!d_user) HIPCHK(c, c->f_h_chars.ensure(total));
-    if (out) { out->n = n; out->chars = c->f_h_chars.p; out->off = off; }
-    if (!total) return CRASS_OK;                        // (no record, or empty reads only: nothing to launch or wait for)
-    HIPCHK(c, c->f_idx.ensure(n));
-    HIPCHK(c, c->f_off.ensure(n + 1));
-    HIPCHK(c, hipMemcpyAsync(c->f_idx.p, c->f_h_idx.p, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->f_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (revcomp) {
-        HIPCHK(c, c->f_h_rc.ensure(n));
-        HIPCHK(c, c->f_rc.ensure(n));
-        memcpy(c->f_h_rc.p, revcomp, n);
-        HIPCHK(c, hipMemcpyAsync(c->f_rc.p, c->f_h_rc.p, n, hipMemcpyHostToDevice, c->stream));
-    }
-    if (!d_user) HIPCHK(c, c->f_chars.ensure(total));
-    FetchJob J{};
-    J.R = R; J.idx = c->f_idx.p; J.rc = revcomp ? c->f_rc.p : nullptr; J.out_off = c->f_off.p; J.n = n; J.total = total;
-    J.out = d_user ? d_user : c->f_chars.p;
-    const bool timed = c->timing_level >= 1;
-    if (timed) {
-        for (auto &e : c->ev_f_time) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->ev_f_time[0], c->stream));
-    }
-    HIPCHK(c, launch_fetch_text(J, c->stream));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_f_time[1], c->stream));
-    if (!d_user) HIPCHK(c, hipMemcpyAsync(c->f_h_chars.p, c->f_chars.p, total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));         // the call's one wait (device route: the staged indices are free again, the text is written)
-    if (timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_f_time[0], c->ev_f_time[1]));
-        c->last_fetch_ms = ms;
-    }
-    return CRASS_OK;
-}
-
-int crass_hip_fetch_text(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *out)
-{
-    if (!c || !out) return CRASS_ERR_INVALID_ARG;
-    return fetch_text_impl(c, read_idx, revcomp, n, nullptr, 0, nullptr, out);
-}
-
-int crass_hip_fetch_text_device(crass_hip_ctx *c, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, uint8_t *d_chars,
-                                uint64_t cap_bytes, uint64_t *off_out)
-{
-    if (!c || !off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
-    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone: the device route, which then overflows or writes nothing)
-    return fetch_text_impl(c, read_idx, revcomp, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr);
-}
-
-int crass_hip_fetch_record_text(crass_hip_ctx *c, int pass, crass_text *out)
-{
-    if (!c || !out || (pass != 1 && pass != 2)) return CRASS_ERR_INVALID_ARG;
-    const uint64_t *idx = nullptr; const uint8_t *low = nullptr; uint64_t n = 0;
-    if (pass == 1) {
-        crass_candidates v;
-        if (const int s = crass_hip_get_candidates(c, &v)) return s;
-        idx = v.read_idx; low = v.low_lexi; n = v.n;
-    } else {
-        crass_recruits v;
-        if (const int s = crass_hip_get_recruits(c, &v)) return s;
-        idx = v.read_idx; low = v.low_lexi; n = v.n;
-    }
-    // RH_Seq = low_lexi ? seq : revcomp(seq): the adapter's fill_holder, ReadHolder.cpp:513-591
-    c->f_flags.resize(n);
-    for (uint64_t k = 0; k < n; k++) c->f_flags[k] = low[k] ? 0 : 1;
-    return fetch_text_impl(c, idx, c->f_flags.data(), n, nullptr, 0, nullptr, out);
-}
-
-float crass_hip_last_fetch_ms(const crass_hip_ctx *c) { return c ? c->last_fetch_ms : 0.0f; }
 
 static void ensure_distinct(crass_hip_ctx *c);
 
