@@ -1,6 +1,8 @@
 // engine_ctx.h — the context behind include/crass_hip.h and what its members are made of, shared by the host files that
-// implement the ABI: engine.cpp (create / destroy, pass 1, merge, pass 2, Levenshtein, counters) and engine_ingest.cpp (the
-// device ingest: load / attach, FASTA / FASTQ scan, BGZF and gzip inflate, header ids, names, header lines, quality, fetch text).
+// implement the ABI: engine.cpp (create / destroy, what every load ends with, pattern install, Levenshtein, counters),
+// engine_pass1.cpp (the seed scan and its sinks), engine_merge.cpp (the merge on the device and on the host, the exchange),
+// engine_pass2.cpp (set_patterns, recruit) and engine_ingest.cpp (the device ingest: load / attach, FASTA / FASTQ scan, BGZF
+// and gzip inflate, header ids, names, header lines, quality, fetch text).  What crosses these files is declared at the end.
 // Host only: no .hip file includes this.
 #pragma once
 #include "../../include/crass_hip.h"
@@ -714,14 +716,56 @@ struct crass_hip_ctx {
         if (e__ != hipSuccess) { (ctx)->last_hip = (int)e__; return e__ == hipErrorOutOfMemory ? CRASS_ERR_OOM : CRASS_ERR_HIP; } \
     } while (0)
 
-// ---- engine.cpp's helpers the ingest calls end with or start from --------------------------------------------------------------
+// ---- the bounds a stage is sized with before the host knows its count: 1.5 x the count of the previous call, rounded up ---------
+inline uint64_t hit_bound(uint64_t n_hits)              // pass 2's flagged reads
+{
+    return std::max<uint64_t>(4096, (n_hits + n_hits / 2 + 4095) & ~4095ull);
+}
+inline uint64_t survivor_bound(uint64_t n_surv)         // the seed filter's survivors
+{
+    return std::min<uint64_t>(std::max<uint64_t>(65536, (n_surv + n_surv / 2 + 65535) & ~65535ull), 1ull << 26);
+}
+inline uint64_t distinct_bound(uint64_t n_tok)          // distinct DR strings: a context's own, or the gathered list's
+{
+    return (n_tok * 3 / 2 + 4095) & ~4095ull;
+}
+// slots of the de-duplication table for up to n strings: a power of two, at most half full
+inline uint32_t dedupe_table_size(uint64_t n)
+{
+    uint32_t tsize = 1024;
+    while (tsize < n * 2) tsize <<= 1;
+    return tsize;
+}
+
+// p1_finish: the speculative launch of a deferred pass 1 cannot be used — k_xg_fill marked the send buffer from the same counters,
+// so every rank of the job sees an exchange that did not fit and repeats the step; this context's next seed scan runs synchronously
+constexpr int kP1Redo = 1000;
+
+// ---- what crosses the engine's files, each declared once ------------------------------------------------------------------------
 // (C linkage like the ABI functions they are defined among; hidden: not part of the library's dynamic symbols)
 #pragma GCC visibility push(hidden)
 extern "C" {
+// engine.cpp
 int validate_reads(const crass_reads *r);
 void reset_results(crass_hip_ctx *c);
 int alloc_scratch(crass_hip_ctx *c);
 int finish_load(crass_hip_ctx *c, const DevReads &R, uint64_t read_index_base, uint32_t max_len, const uint32_t *lengths, uint64_t total_words);
+void quiesce_worker(crass_hip_ctx *c);
+int install_patterns(crass_hip_ctx *c, const StringArena &pats);
+int ensure_full_automaton(crass_hip_ctx *c);
+// engine_pass1.cpp
+int first_call_bounds(crass_hip_ctx *c);
+void presize_hostloop(crass_hip_ctx *c);
+int ensure_recruit_buffers(crass_hip_ctx *c, uint64_t h_alloc, uint64_t n_exc, bool dev_sink, bool anchors);
+int read_count(crass_hip_ctx *c);
+int p1_finish(crass_hip_ctx *c);
+int settle_p1(crass_hip_ctx *c);
+// engine_merge.cpp
+int device_merge_prepare(crass_hip_ctx *c, const char *dx_chars, const uint16_t *dx_len, uint64_t n_tok, const uint32_t *d_ntok);
+int device_merge_enqueue(crass_hip_ctx *c, const char *dx_chars, const uint16_t *dx_len, uint64_t n_tok, const uint32_t *d_ntok, bool prepared);
+void ensure_distinct(crass_hip_ctx *c);
+int ensure_host_merge(crass_hip_ctx *c);
+int host_merge_fallback(crass_hip_ctx *c);
 // engine_ingest.cpp: every device and pinned buffer and every event of c->in goes; crass_hip_destroy calls it with the
 // context's streams still alive and waited for
 void ingest_free_all(crass_hip_ctx *c);

@@ -1,5 +1,5 @@
 // engine_internal.h — types shared by the HIP kernels (kernels.hip, pass2.hip, sinks.hip) and the host engine
-// (engine.cpp).  Not part of the public ABI (include/crass_hip.h is).
+// (engine.cpp, engine_pass1.cpp, engine_merge.cpp, engine_pass2.cpp, engine_ingest.cpp).  Not part of the public ABI (include/crass_hip.h is).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -234,7 +234,7 @@ struct DevMerge {
     DevViewTotals *x_htot;
     uint32_t x_on;                // 0: no export (the host rebuilds the view from h_root / h_blank)
     uint32_t x_group_cap;         // a group with more members than this is not ranked here (quadratic): the host builds the view
-    // stage flags (engine.cpp: crass_hip_ctx::h_flags): pinned host words that the FIRST kernel of a stage stores at system scope
+    // stage flags (engine_ctx.h: crass_hip_ctx::h_flags): pinned host words that the FIRST kernel of a stage stores at system scope
     // — everything queued in front of that kernel is then complete — for the host to poll instead of an event recorded
     // between two kernels (~6 us of stream time each).  flag_pre: k_dm_pack_codes; flag_post: pass 2's probe
     uint32_t *flag_pre; uint32_t flag_pre_val;
@@ -290,7 +290,7 @@ static __device__ __forceinline__ void stage_flag_store(uint32_t *flag, uint32_t
     __hip_atomic_store(flag, val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // one-collective exchange (see crass_hip_exchange_setup): fill this rank's send buffer / unpack the gathered buffers
-// p1_counts / surv_bound (a deferred pass 1, engine.cpp p1d): the stage's device counters — [0] survivors, [2] found records,
+// p1_counts / surv_bound (a deferred pass 1, engine_pass1.cpp p1d): the stage's device counters — [0] survivors, [2] found records,
 // [3] worst error, [5] de-duplication flags — are checked HERE, by the kernel that fills the send buffer: a launch the host will
 // find unusable (more survivors than the bound, none, an error, no exact distinct list) sets bit 63 of the header's count, which
 // every rank's k_xg_unpack reports as an exchange that did not fit

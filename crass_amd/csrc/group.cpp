@@ -1,6 +1,6 @@
 // group.cpp — several GPUs from ONE process: crass_hip_group_* of include/crass_hip.h.
 //
-// A group is N contexts (engine.cpp), one per device, driven by N host threads (the caller is rank 0's thread).  The
+// A group is N contexts (engine.cpp and its engine_*.cpp stage files), one per device, driven by N host threads (the caller is rank 0's thread).  The
 // path shards by contiguous read ranges; the only exchange is ONE all-gather per step of every rank's distinct
 // candidate DR strings between pass 1 and the merge, issued by rank 0's thread for all ranks inside
 // ncclGroupStart / ncclGroupEnd on the contexts' own streams — the canonical single-process form of RCCL

@@ -1,4 +1,4 @@
-// gunzip_core.h — what the host function (gunzip.cpp), the kernels (gunzip.hip) and the engine (engine.cpp) share about inflating
+// gunzip_core.h — what the host function (gunzip.cpp), the kernels (gunzip.hip) and the engine (engine_ingest.cpp) share about inflating
 // ONE plain gzip member (RFC 1952) chunk by chunk: pgzip.cpp's technique (one deflate stream entered at block starts found in
 // its middle, bytes copied from the unknown 32 KB in front of a chunk carried as 16-bit markers and resolved afterwards, the
 // result accepted only with the trailer's length and CRC-32), made wait-free: no chunk ever waits for another, every step is a

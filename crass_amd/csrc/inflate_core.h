@@ -1,4 +1,4 @@
-// inflate_core.h — what the host function (bgzf.cpp), the kernel (inflate.hip) and the engine (engine.cpp) share about inflating
+// inflate_core.h — what the host function (bgzf.cpp), the kernel (inflate.hip) and the engine (engine_ingest.cpp) share about inflating
 // ONE member of a BGZF file (SAM spec 4.1: a gzip member of at most 64 KB of text that names its own size): the DEFLATE decoder
 // (RFC 1951: stored, fixed and dynamic blocks, any number per member), the CRC-32 of RFC 1952, the decline reasons and the order
 // in which they are reported.  Plain C++ with CRASS_HD (pack_text.h), so the rule exists once for host and device, like

@@ -1,4 +1,4 @@
-// pack_text.h — what the host packer (ingest.cpp), the device packer (pack.hip) and the engine (engine.cpp) share about
+// pack_text.h — what the host packer (ingest.cpp), the device packer (pack.hip) and the engine (engine_ingest.cpp) share about
 // turning sequence text into the 2-bit layout of include/crass_hip.h: the byte -> code function and the layout decision
 // (stride / uniform length).  Plain C++: ingest.cpp stays host-only code that any compiler builds (tools/sanitize); under
 // hipcc the code function is a __host__ __device__ one.  The kernel's job description and launch wrappers: pack_launch.h.
