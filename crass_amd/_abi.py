@@ -101,6 +101,13 @@ class FastxFilesLayoutC(C.Structure):
                 ("file_byte_base", u64p), ("format", C.POINTER(C.c_int32)), ("rec_pos", u64p), ("seq_off", u64p)]
 
 
+class FastxShardsC(C.Structure):
+    _fields_ = [("n_ranks", C.c_uint32), ("n_files", C.c_uint32), ("decline_file", C.c_int32), ("decline_reason", C.c_int32),
+                ("decline_pos", C.c_uint64), ("bgzf", BgzfVerdict), ("n_reads", C.c_uint64), ("max_len", C.c_uint32),
+                ("rank_read_base", u64p), ("cut_file", C.POINTER(C.c_uint32)), ("cut_pos", u64p), ("file_read_base", u64p),
+                ("format", C.POINTER(C.c_int32))]
+
+
 class BgzfIndexC(C.Structure):
     _fields_ = [("n_members", C.c_uint64), ("in_off", u64p), ("out_off", u64p), ("data_off", u64p), ("decline", BgzfVerdict)]
 
@@ -311,6 +318,15 @@ SYMBOLS = {
     "crass_hip_group_get_merge": (C.c_int, [C.c_void_p, C.POINTER(MergeView)]),
     "crass_hip_group_get_recruits": (C.c_int, [C.c_void_p, C.POINTER(Recruits)]),
     "crass_hip_group_fetch_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text)]),
+    "crass_fastx_files_shards_host": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(FastxShardsC)]),
+    "crass_fastx_shards_free": (None, [C.POINTER(FastxShardsC)]),
+    "crass_fastx_cut_probe_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "crass_hip_fastx_cut_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "crass_hip_last_cut_probe_ms": (C.c_float, [C.c_void_p]),
+    "crass_hip_group_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.c_void_p,
+                                                   C.POINTER(FastxShardsC)]),
+    "crass_hip_group_fetch_header_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
+    "crass_hip_group_fetch_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_build_outputs": (C.c_int, [C.POINTER(GraphInput), C.POINTER(OutputOpts), C.POINTER(C.c_void_p)]),
     "crass_outputs_get": (C.c_int, [C.c_void_p, C.POINTER(OutputsView)]),
     "crass_outputs_write": (C.c_int, [C.c_void_p, C.c_char_p]),

@@ -606,7 +606,7 @@ struct MappedFiles {
 };
 
 // the one line a declined input of the device reader gets: the file, the reason, the position
-std::string decline_message(const Vecstr &files, const crass_fastx_files_layout &lay)
+std::string decline_message(const Vecstr &files, const crass_fastx_files_layout &lay, const char *mode = "device")
 {
     static const char *const fx[] = {"", "the file is empty", "byte 0 is neither '>' nor '@'", "the FASTQ lines are no multiple of 4", "a FASTQ record does not start with '@'",
                                      "'>', '@' or '+' in a sequence line", "the third line of a FASTQ record does not start with '+'", "byte 127 in a quality line",
@@ -618,7 +618,7 @@ std::string decline_message(const Vecstr &files, const crass_fastx_files_layout 
                                      "not a gzip header, or a header that runs into the trailer", "no deflate block start within the span of a chunk",
                                      "the gzip member ends before the file does (further members, trailing bytes)", "a distance that reaches in front of the text or of its member"};
     const std::string name = lay.decline_file >= 0 && (size_t)lay.decline_file < files.size() ? files[(size_t)lay.decline_file] : std::string("?");
-    std::string m = "crass [ERROR]: CRASS_INGEST=device cannot take " + name + ": ";
+    std::string m = std::string("crass [ERROR]: CRASS_INGEST=") + mode + " cannot take " + name + ": ";
     if (lay.bgzf.reason) {
         const int r = lay.bgzf.reason;
         m += std::string(r >= 1 && r <= 14 ? bz[r] : "compression") + " (BGZF reason " + std::to_string(r) + ", member " + std::to_string(lay.bgzf.member) +
@@ -653,6 +653,10 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     const bool device_ingest = [] { const char *e = getenv("CRASS_INGEST"); return e && !strcmp(e, "device"); }();
     if (device_ingest && devs.size() > 1)
         throw input_error("crass [ERROR]: CRASS_INGEST=device needs one device, " + std::to_string(devs.size()) + " were asked for (--gpus / --devices)");
+    // CRASS_INGEST=devices: the same for any number of devices — the mapped inputs are cut into record-aligned shards, one per
+    // device, each parsed on its own device beside the others (crass_hip_group_load_fastx_files); one device: a group of one
+    const bool devices_ingest = [] { const char *e = getenv("CRASS_INGEST"); return e && !strcmp(e, "devices"); }();
+    const bool from_device = device_ingest || devices_ingest;      // the handed-on records' text comes back from the device(s)
     // contexts (HIP start-up, code objects, RCCL communicators) come up on their own thread while this one reads the files
     struct Made { int rc = 0; crass_hip_ctx *c = nullptr; crass_hip_group *g = nullptr; };
     struct Pending {
@@ -660,9 +664,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         Made &get() { if (!got) { m = fut.get(); got = true; } return m; }
         ~Pending() { if (fut.valid() || got) { Made &r = get(); if (r.g) crass_hip_group_destroy(r.g); if (r.c) crass_hip_destroy(r.c); } }
     } dev;
-    dev.fut = std::async(std::launch::async, [p, devs, local]() {
+    dev.fut = std::async(std::launch::async, [p, devs, local, devices_ingest]() {
         Made m;
-        if (devs.size() > 1) m.rc = crass_hip_group_create(&p, devs.data(), (int)devs.size(), local ? CRASS_GROUP_LOCAL_COPIES : 0u, &m.g);
+        if (devs.size() > 1 || devices_ingest) m.rc = crass_hip_group_create(&p, devs.data(), (int)devs.size(), local ? CRASS_GROUP_LOCAL_COPIES : 0u, &m.g);
         else m.rc = crass_hip_create(&p, devs[0], &m.c);
         return m;
     });
@@ -688,7 +692,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             else if (rc != CRASS_ERR_UNSUPPORTED || force) chk(rc, "crass_index_fastx_files");
         }
     }
-    const bool streamed = !indexed && !device_ingest && want_streamed_ingest(seqFiles);
+    const bool streamed = !indexed && !from_device && want_streamed_ingest(seqFiles);
     MappedFiles M;
     JobFiles J;
     StreamedJob S;
@@ -699,7 +703,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     const char *dp_env = getenv("CRASS_DEVICE_PACK");
     const bool device_pack = dp_env && *dp_env && *dp_env != '0' && !indexed && !streamed && devs.size() == 1;
     const uint8_t *text_seq = nullptr; const uint64_t *text_off = nullptr; const uint64_t *text_hid = nullptr;
-    if (device_ingest) {
+    if (from_device) {
         for (const std::string &f : seqFiles) if (!M.map(f)) CRASS_THROW(std::string("Could not open FASTQ ") + f + " for reading.");
         memset(&r, 0, sizeof(r));
         t1 = now();
@@ -833,6 +837,18 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         n = lay.n_reads; max_len = (int)lay.max_len;
         if (timing) fprintf(stderr, "[crass_timing] %llu reads of %zu file(s) parsed and packed on the device (crass_hip_load_fastx_files)\n", (unsigned long long)n, seqFiles.size());
     }
+    if (devices_ingest) {
+        crass_fastx_shards sh;
+        const int s = crass_hip_group_load_fastx_files(made.g, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, nullptr, &sh);
+        if (s == CRASS_ERR_UNSUPPORTED && sh.decline_file >= 0) {
+            lay.decline_file = sh.decline_file; lay.decline_reason = sh.decline_reason; lay.decline_pos = sh.decline_pos; lay.bgzf = sh.bgzf;
+            throw input_error(decline_message(seqFiles, lay, "devices"));
+        }
+        if (s == CRASS_ERR_RCCL) CRASS_THROW(std::string("crass_hip_group_load_fastx_files: ") + crass_hip_group_last_error());
+        chk(s, "crass_hip_group_load_fastx_files");
+        n = sh.n_reads; max_len = (int)sh.max_len;
+        if (timing) fprintf(stderr, "[crass_timing] %llu reads of %zu file(s) parsed and packed on %zu device(s) (crass_hip_group_load_fastx_files)\n", (unsigned long long)n, seqFiles.size(), devs.size());
+    }
     // (the reads are resident on the device(s) once loaded: the host copy of a streamed job goes at once)
     auto drop_host_reads = [&] {
         if (!streamed) return;
@@ -841,7 +857,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     };
     try {
         if (made.g) {
-            chk(crass_hip_group_load_reads(made.g, &r), "crass_hip_group_load_reads");
+            if (!devices_ingest) chk(crass_hip_group_load_reads(made.g, &r), "crass_hip_group_load_reads");
             drop_host_reads();
             const int s = crass_hip_group_step(made.g);
             if (s == CRASS_ERR_RCCL) CRASS_THROW(std::string("crass_hip_group_step: ") + crass_hip_group_last_error());
@@ -890,7 +906,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     std::vector<ReadHolder *> cand_holders(c.n);
     for (uint64_t k = 0; k < c.n; k++) {
         ReadHolder *h = new ReadHolder();
-        if (streamed || indexed || device_ingest) fills.push_back(Fill{c.read_idx[k], h, c.low_lexi[k] != 0});
+        if (streamed || indexed || from_device) fills.push_back(Fill{c.read_idx[k], h, c.low_lexi[k] != 0});
         else {
             size_t f; uint64_t i;
             J.locate(c.read_idx[k], f, i);
@@ -943,7 +959,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     hlap();      // 2: groups, patterns
     for (uint64_t k = 0; k < q.n; k++) {
         ReadHolder *h = new ReadHolder();
-        if (streamed || indexed || device_ingest) fills.push_back(Fill{q.read_idx[k], h, q.low_lexi[k] != 0});
+        if (streamed || indexed || from_device) fills.push_back(Fill{q.read_idx[k], h, q.low_lexi[k] != 0});
         else {
             size_t f; uint64_t i;
             J.locate(q.read_idx[k], f, i);
@@ -993,6 +1009,31 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             const char *line = (const char *)hl.chars + hl.off[k];
             const size_t len = (size_t)(hl.off[k + 1] - hl.off[k]), nl = std::min<size_t>(name_len[k], len);
             h.RH_Header.assign(line, nl);                // kseq: the name ends at the first isspace() byte, the comment is the rest of the line behind it
+            if (nl < len) h.RH_Comment.assign(line + nl + 1, len - nl - 1);
+            if (has_qual[k]) { h.RH_Qual.assign((const char *)ql.chars + ql.off[k], (size_t)(ql.off[k + 1] - ql.off[k])); h.RH_IsFasta = false; }
+        }
+        t_fill = now() - tf0;
+    }
+    if (devices_ingest && !fills.empty()) {
+        // the same from the ranks of the group: every record is routed to the rank that holds its read (crass_hip_group_fetch_*);
+        // RH_Seq is the read's text, reverse-complemented on the device where the record is not in its low-lexi orientation
+        const double tf0 = now();
+        const size_t nf = fills.size();
+        std::vector<uint64_t> want(nf);
+        std::vector<uint8_t> rc(nf), has_qual(nf);
+        std::vector<uint32_t> name_len(nf);
+        for (size_t k = 0; k < nf; k++) { want[k] = fills[k].idx; rc[k] = fills[k].low ? 0 : 1; }
+        crass_text t, hl, ql;
+        chk(crass_hip_group_fetch_text(made.g, want.data(), rc.data(), nf, &t), "crass_hip_group_fetch_text");
+        chk(crass_hip_group_fetch_header_lines(made.g, want.data(), nf, &hl, name_len.data()), "crass_hip_group_fetch_header_lines");
+        chk(crass_hip_group_fetch_quality(made.g, want.data(), nf, &ql, has_qual.data()), "crass_hip_group_fetch_quality");
+        for (size_t k = 0; k < nf; k++) {
+            ReadHolder &h = *fills[k].h;
+            h.RH_Seq.assign((const char *)t.chars + t.off[k], (size_t)(t.off[k + 1] - t.off[k]));
+            h.RH_WasLowLexi = fills[k].low;
+            const char *line = (const char *)hl.chars + hl.off[k];
+            const size_t len = (size_t)(hl.off[k + 1] - hl.off[k]), nl = std::min<size_t>(name_len[k], len);
+            h.RH_Header.assign(line, nl);
             if (nl < len) h.RH_Comment.assign(line + nl + 1, len - nl - 1);
             if (has_qual[k]) { h.RH_Qual.assign((const char *)ql.chars + ql.off[k], (size_t)(ql.off[k + 1] - ql.off[k])); h.RH_IsFasta = false; }
         }
@@ -1069,9 +1110,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
     std::cout << "\r[crass_singletonFinder]: Processed " << g_read_counter_p2 << " ..." << difftime(tnow, time_start) << " sec" << std::endl;
     if (timing)
         fprintf(stderr, "[crass_timing] searchAndRecruit: %llu reads on %zu device(s)%s; read+parse%s %.3f s, pack %.3f s, device (H2D + pass 1 + merge + pass 2) %.3f s, hand-off %.3f s%s\n",
-                (unsigned long long)n, devs.size(), streamed ? ", streamed ingest" : indexed ? ", indexed ingest" : device_ingest ? ", device ingest" : "", (streamed || indexed) ? "+pack" : "", t1 - t0, t2 - t1, t3 - t2, now() - t3,
+                (unsigned long long)n, devs.size(), streamed ? ", streamed ingest" : indexed ? ", indexed ingest" : device_ingest ? ", device ingest" : devices_ingest ? ", devices ingest" : "", (streamed || indexed) ? "+pack" : "", t1 - t0, t2 - t1, t3 - t2, now() - t3,
                 streamed ? (" (of which the second pass over the inputs " + std::to_string(t_fill) + " s)").c_str()
-                         : (indexed || device_ingest) ? (" (of which the handed-on records' text " + std::to_string(t_fill) + " s)").c_str() : "");
+                         : (indexed || from_device) ? (" (of which the handed-on records' text " + std::to_string(t_fill) + " s)").c_str() : "");
     if (timing)
         fprintf(stderr, "[crass_timing] searchAndRecruit: resident set after ingest %.0f MB, with the device context(s) up %.0f MB, at the end %.0f MB\n",
                 rss_ingested, rss_ctx, rss_mb());

@@ -250,6 +250,16 @@ struct Ingest {
     // (drop_arena); the pinned per-file arrays crass_fastx_files_layout points at (read bases, byte bases, formats)
     DevBuf<uint8_t> fa_arena; uint64_t fa_bytes = 0; bool have_arena = false;
     PinBuf<uint64_t> fa_h_base; PinBuf<int32_t> fa_h_format;
+    // a shard of a group's files load (fastx_shards.h): the staged text of the nominal range and where each file's part lies in
+    // it, a BGZF tail, the probe's per-block parts — all given back by shard_pack / shard_abort; what shard_scan found for
+    // shard_pack (the slices' arena bases, the records); the marks around the last k_fx_cut_probe launch
+    struct ShardStaged { uint32_t file; uint64_t a, b, off; };      // the text range [a, b) of the file lies at sh_stage + off
+    DevBuf<uint8_t> sh_stage, sh_tail; DevBuf<FxProbe> sh_part; PinBuf<FxProbe> sh_h_part;
+    std::vector<ShardStaged> sh_staged;
+    std::vector<uint64_t> sh_base;
+    uint64_t sh_n_reads = 0; bool sh_scanned = false, sh_loaded = false;
+    StageTimer<2> tm_probe;
+    float last_probe_ms = 0;
 };
 
 } // namespace crass

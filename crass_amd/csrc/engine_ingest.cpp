@@ -1,13 +1,15 @@
 // engine_ingest.cpp — the device ingest behind include/crass_hip.h: packed reads and sequence text in (pack.hip), the raw
 // bytes of FASTA / FASTQ files parsed on the device (fastx_scan.hip), BGZF and plain gzip inflated there (inflate.hip,
 // gunzip.hip), several files as one set, header ids, the name table, header lines and quality strings (fastx_names.hip), and
-// the text of resident reads back out (k_fetch_text).  The context and its Ingest member are engine_ctx.h; what a load ends
+// the text of resident reads back out (k_fetch_text), and one rank's steps of a group's files load (fastx_shards.h: stage and
+// probe, complete and scan, pack).  The context and its Ingest member are engine_ctx.h; what a load ends
 // with (finish_load: scratch, position hints, first-call bounds) is engine.cpp's.
 #include "engine_ctx.h"
 #include "pack_launch.h"
 #include "fastx_names_launch.h"
 #include "inflate_launch.h"
 #include "gunzip_launch.h"
+#include "fastx_shards.h"
 
 #include <new>
 
@@ -25,7 +27,7 @@ static void drop_arena(crass_hip_ctx *c)
 {
     if (c->in.have_names && c->in.nt_on_arena) names_drop(c);      // (a name table built on the arena refers to its bytes)
     if (c->in.fa_arena.p) { (void)hipStreamSynchronize(c->stream); c->in.fa_arena.release(); }
-    c->in.have_arena = false; c->in.fa_bytes = 0;
+    c->in.have_arena = false; c->in.fa_bytes = 0; c->in.sh_loaded = false;
 }
 
 // ---- the scratch goes back: one function per stage, which first waits for the streams that may still use the stage's buffers ----
@@ -80,11 +82,21 @@ static void release_names_find(crass_hip_ctx *c)
 
 static void release_lines(crass_hip_ctx *c, LineFetch &B) { wait_main(c); B.release_device(); }
 
+// a shard's staged text, its BGZF tail and the probe's parts (fastx_shards.h)
+static void release_shard(crass_hip_ctx *c)
+{
+    Ingest &I = c->in;
+    wait_both(c);
+    I.sh_stage.release(); I.sh_tail.release(); I.sh_part.release();
+    I.sh_staged.clear(); I.sh_scanned = false;
+}
+
 void ingest_free_all(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
     release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c);
     names_drop(c); drop_arena(c);
+    release_shard(c); I.sh_h_part.release(); I.tm_probe.destroy();
     I.hl.free_all(); I.ql.free_all();
     // what is kept from call to call, and the pinned sides of the results
     I.f_idx.release(); I.f_off.release(); I.f_rc.release(); I.f_chars.release();
@@ -552,9 +564,11 @@ static int bz_decline(crass_bgzf_verdict *v, int32_t reason, uint64_t member, ui
 }
 
 // the index is checked, d_in / d_out are device pointers: upload the offsets, launch, read the verdict
-static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_bgzf_index *ix, uint8_t *d_out, crass_bgzf_verdict *v)
+// (the members [m0, m0 + n) of the index alone: d_in and d_out stay the places of the FILE's byte 0 and the TEXT's byte 0, which
+// may lie outside what the caller holds — a member's bytes are read and written inside its own ranges only, inflate.hip)
+static int inflate_bgzf_members(crass_hip_ctx *c, const uint8_t *d_in, const crass_bgzf_index *ix, uint64_t m0, uint64_t n, uint8_t *d_out,
+                                crass_bgzf_verdict *v)
 {
-    const uint64_t n = ix->n_members;
     c->in.last_inflate_ms = 0;
     if (n == 0) return CRASS_OK;
     HIPCHK(c, c->in.z_idx.ensure(3 * n + 2)); HIPCHK(c, c->in.z_reason.ensure(n)); HIPCHK(c, c->in.z_verdict.ensure(1)); HIPCHK(c, c->in.z_h_verdict.ensure(1));
@@ -562,9 +576,9 @@ static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_
     J.in = d_in; J.out = d_out; J.n_members = n;
     J.in_off = c->in.z_idx.p; J.out_off = c->in.z_idx.p + (n + 1); J.data_off = c->in.z_idx.p + 2 * (n + 1);
     J.reason = c->in.z_reason.p; J.verdict = c->in.z_verdict.p; J.hbm_window = c->env.inflate_hbm_window ? 1 : 0;
-    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p, ix->in_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p + (n + 1), ix->out_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p + 2 * (n + 1), ix->data_off, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p, ix->in_off + m0, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p + (n + 1), ix->out_off + m0, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->in.z_idx.p + 2 * (n + 1), ix->data_off + m0, n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
     HIPCHK(c, c->in.tm_inflate.begin(c->timing_level >= 1, c->stream));
     HIPCHK(c, launch_bgzf_inflate(J, c->stream));
@@ -574,7 +588,12 @@ static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_
     HIPCHK(c, c->in.tm_inflate.elapsed(0, 1, &c->in.last_inflate_ms));
     const uint64_t w = c->in.z_h_verdict.p[0];
     if (w == kBzNoOffence) return CRASS_OK;
-    return bz_decline(v, (int32_t)(w & 0xFF), w >> 8, ix->in_off[w >> 8]);
+    return bz_decline(v, (int32_t)(w & 0xFF), m0 + (w >> 8), ix->in_off[m0 + (w >> 8)]);
+}
+
+static int inflate_bgzf_impl(crass_hip_ctx *c, const uint8_t *d_in, const crass_bgzf_index *ix, uint8_t *d_out, crass_bgzf_verdict *v)
+{
+    return inflate_bgzf_members(c, d_in, ix, 0, ix->n_members, d_out, v);
 }
 
 int crass_hip_inflate_bgzf_device(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, const crass_bgzf_index *ix, uint8_t *d_out, uint64_t out_cap,
@@ -1497,3 +1516,263 @@ int crass_hip_fetch_record_text(crass_hip_ctx *c, int pass, crass_text *out)
 float crass_hip_last_fetch_ms(const crass_hip_ctx *c) { return c ? c->in.last_fetch_ms : 0.0f; }
 
 } // extern "C"
+
+// ---- one rank's shard of a group's files load (fastx_shards.h; the group's threads and barriers are group.cpp's) ----
+// the probe of a range that lies on the device: launch, the blocks' parts back, folded in block order
+static int probe_impl(crass_hip_ctx *c, const uint8_t *d, uint64_t n, bool left_is_ls, FxProbe *out)
+{
+    Ingest &I = c->in;
+    FxProbe none{};
+    none.gt = kFxNone;
+    for (auto &x : none.ls) x = kFxNone;
+    *out = none;
+    I.last_probe_ms = 0;
+    if (!n) return CRASS_OK;
+    FxProbeJob P;
+    fx_probe_plan(d, n, left_is_ls ? 1u : 0u, &P);
+    HIPCHK(c, I.sh_part.ensure(P.n_blocks)); HIPCHK(c, I.sh_h_part.ensure(P.n_blocks));
+    P.part = I.sh_part.p;
+    HIPCHK(c, I.tm_probe.begin(c->timing_level >= 1, c->stream));
+    HIPCHK(c, launch_fx_cut_probe(P, c->stream));
+    HIPCHK(c, I.tm_probe.mark(c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.sh_h_part.p, I.sh_part.p, P.n_blocks * sizeof(FxProbe), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, I.tm_probe.elapsed(0, 1, &I.last_probe_ms));
+    fx_probe_fold(I.sh_h_part.p, P.n_blocks, out);
+    return CRASS_OK;
+}
+
+extern "C" int crass_hip_fastx_cut_probe_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, int left_is_ls, uint64_t out[7])
+{
+    if (!c || !out || (n_bytes && !d_bytes)) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    FxProbe P;
+    const int s = probe_impl(c, d_bytes, n_bytes, left_is_ls != 0, &P);
+    wait_main(c); c->in.sh_part.release();
+    if (s) return s;
+    out[0] = P.n_nl; out[1] = P.n_ls; for (int k = 0; k < 4; k++) out[2 + k] = P.ls[k]; out[6] = P.gt;
+    return CRASS_OK;
+}
+
+extern "C" float crass_hip_last_cut_probe_ms(const crass_hip_ctx *c) { return c ? c->in.last_probe_ms : 0.0f; }
+
+// The members of a BGZF index that hold the text range [a, b): [*m0, *m1).  Members without text are taken where they lie at
+// b, and from member 0 when a is 0 (in front of a > 0 they are the range before's), so that a file cut into ranges that tile
+// its text has every member inflated by somebody, the 28-byte end-of-file member included.
+static void bgzf_members_for(const crass_bgzf_index *ix, uint64_t a, uint64_t b, uint64_t *m0, uint64_t *m1)
+{
+    const uint64_t n = ix->n_members, *oo = ix->out_off;
+    *m0 = a == 0 ? 0 : (uint64_t)(std::upper_bound(oo + 1, oo + n + 1, a) - (oo + 1));      // the first member that ends behind a
+    uint64_t e = (uint64_t)(std::upper_bound(oo + 1, oo + n + 1, b) - (oo + 1));            // ... behind b
+    if (e < n && oo[e] < b) e++;
+    *m1 = e;
+}
+
+// the members [m0, m1) of a host file inflated so that text position t lies at text0 + t: the compressed bytes up into z_raw
+static int shard_inflate(crass_hip_ctx *c, const ShardFile &F, uint64_t m0, uint64_t m1, uint8_t *text0, crass_bgzf_verdict *bv)
+{
+    const uint64_t z0 = F.ix->in_off[m0], z1 = F.ix->in_off[m1];
+    HIPCHK(c, c->in.z_raw.ensure(z1 - z0 + 16));
+    const int up = upload_staged(c, F.bytes + z0, z1 - z0, c->in.z_raw.p);
+    if (up) return up;
+    // (waits for the stream before it returns: z_raw may be used again)
+    return inflate_bgzf_members(c, reinterpret_cast<const uint8_t *>((uintptr_t)c->in.z_raw.p - z0), F.ix, m0, m1 - m0, text0, bv);
+}
+
+int shard_stage_probe(crass_hip_ctx *c, const ShardFile *files, uint32_t n_files, ShardPos lo, ShardPos hi, std::vector<ShardPiece> *pieces,
+                      ShardVerdict *v)
+{
+    if (!c || !files || !pieces || !v) return CRASS_ERR_INVALID_ARG;
+    pieces->clear();
+    *v = ShardVerdict();
+    begin_fastx_load(c);
+    c->in.last_inflate_ms = 0;
+    release_shard(c);
+    Ingest &I = c->in;
+    try {
+        // the pieces and their places in the staging buffer: every piece at its text position modulo 16
+        struct Plan { uint32_t f; uint64_t a, b, sa, sb, off, m0, m1; };
+        std::vector<Plan> plan;
+        uint64_t cursor = 0;
+        for (uint32_t f = lo.file; f <= hi.file && f < n_files; f++) {
+            const uint64_t a = f == lo.file ? lo.pos : 0, b = f == hi.file ? hi.pos : files[f].n_text;
+            if (a >= b) continue;
+            Plan p{f, a, b, a, b, 0, 0, 0};
+            if (files[f].ix) {                          // (with the byte in front of a: it says whether a is a line start)
+                bgzf_members_for(files[f].ix, a ? a - 1 : 0, b, &p.m0, &p.m1);
+                p.sa = files[f].ix->out_off[p.m0]; p.sb = files[f].ix->out_off[p.m1];
+            }
+            p.off = ((cursor + 15) & ~15ull) + (p.sa & 15u);
+            cursor = p.off + (p.sb - p.sa);
+            plan.push_back(p);
+        }
+        HIPCHK(c, I.sh_stage.ensure(cursor + 32));
+        bool first = true;
+        for (const Plan &p : plan) {
+            const ShardFile &F = files[p.f];
+            uint8_t *dst = I.sh_stage.p + p.off;        // text position p.sa
+            if (!first) HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // (the staged buffers are the piece before's until its last copy is done)
+            first = false;
+            ShardPiece pc{};
+            pc.file = p.f; pc.a = p.a; pc.b = p.b;
+            if (F.ix) {
+                crass_bgzf_verdict bv{};
+                const int s = shard_inflate(c, F, p.m0, p.m1, reinterpret_cast<uint8_t *>((uintptr_t)dst - p.sa), &bv);
+                if (s == CRASS_ERR_UNSUPPORTED) { v->file = (int32_t)p.f; v->bgzf = bv; break; }
+                if (s) return s;
+                uint8_t one = 0;
+                HIPCHK(c, hipMemcpy(&one, dst + ((p.a ? p.a - 1 : 0) - p.sa), 1, hipMemcpyDeviceToHost));
+                if (p.a == 0) {
+                    pc.first_byte = one;
+                    if (!fx_is_hdr_char(one)) { v->file = (int32_t)p.f; v->reason = FX_FIRST_BYTE; break; }
+                }
+                pc.left_is_ls = p.a == 0 || fx_is_nl(one);
+            } else {
+                const int up = upload_staged(c, F.bytes + p.a, p.b - p.a, dst);
+                if (up) return up;
+                pc.left_is_ls = p.a == 0 || fx_is_nl(F.bytes[p.a - 1]);
+                if (p.a == 0) pc.first_byte = F.bytes[0];
+            }
+            const int ps = probe_impl(c, dst + (p.a - p.sa), p.b - p.a, pc.left_is_ls, &pc.probe);
+            if (ps) return ps;
+            I.sh_staged.push_back(Ingest::ShardStaged{p.f, p.sa, p.sb, p.off});
+            pieces->push_back(pc);
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+int shard_scan(crass_hip_ctx *c, const ShardFile *files, uint32_t n_files, ShardPos lo, ShardPos hi,
+               std::vector<std::pair<uint32_t, uint64_t>> *file_reads, uint64_t *n_reads, uint32_t *max_len, ShardVerdict *v)
+{
+    if (!c || !files || !file_reads || !n_reads || !max_len || !v) return CRASS_ERR_INVALID_ARG;
+    *n_reads = 0; *max_len = 0; *v = ShardVerdict();
+    file_reads->clear();
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    try {
+        struct Slice { uint32_t f; uint64_t a, b; };
+        std::vector<Slice> sl;
+        for (uint32_t f = lo.file; f <= hi.file && f < n_files; f++) {
+            const uint64_t a = f == lo.file ? lo.pos : 0, b = f == hi.file ? hi.pos : files[f].n_text;
+            if (a < b) sl.push_back(Slice{f, a, b});
+        }
+        // the arena: the slices in order, a byte of room behind each
+        std::vector<uint64_t> &base = I.sh_base;
+        base.assign(1, 0);
+        for (const Slice &S : sl) base.push_back(base.back() + (S.b - S.a) + 1);
+        HIPCHK(c, I.fa_arena.ensure(base.back() + 16));
+        uint8_t *arena = I.fa_arena.p;
+        uint32_t ns = (uint32_t)sl.size();
+        for (uint32_t i = 0; i < ns; i++) {
+            const Slice &S = sl[i];
+            const ShardFile &F = files[S.f];
+            uint8_t *dst = arena + base[i];
+            // what was staged of it comes device to device ...
+            uint64_t have = S.a;                        // [S.a, have) is in place
+            for (const Ingest::ShardStaged &st : I.sh_staged) {
+                if (st.file != S.f || S.a < st.a || S.a >= st.b) continue;
+                have = std::min(S.b, st.b);
+                HIPCHK(c, hipMemcpyAsync(dst, I.sh_stage.p + st.off + (S.a - st.a), have - S.a, hipMemcpyDeviceToDevice, c->stream));
+            }
+            if (have == S.b) continue;
+            // ... and the tail behind it from the host: plain bytes, or the further members
+            HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+            if (F.ix) {
+                uint64_t m0, m1;
+                bgzf_members_for(F.ix, have, S.b, &m0, &m1);
+                const uint64_t t0 = F.ix->out_off[m0], t1 = F.ix->out_off[m1];
+                HIPCHK(c, I.sh_tail.ensure(t1 - t0 + 16));
+                crass_bgzf_verdict bv{};
+                const int s = shard_inflate(c, F, m0, m1, reinterpret_cast<uint8_t *>((uintptr_t)I.sh_tail.p - t0), &bv);
+                if (s == CRASS_ERR_UNSUPPORTED) { v->file = (int32_t)S.f; v->bgzf = bv; ns = i; break; }      // (the slices in front of it are still scanned)
+                if (s) return s;
+                HIPCHK(c, hipMemcpyAsync(dst + (have - S.a), I.sh_tail.p + (have - t0), S.b - have, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));      // (sh_tail may be used again)
+            } else {
+                const int up = upload_staged(c, F.bytes + have, S.b - have, dst + (have - S.a));
+                if (up) return up;
+            }
+        }
+        base.resize((size_t)ns + 1);
+        I.sh_n_reads = 0;
+        if (ns == 0) { I.sh_scanned = v->file < 0; return CRASS_OK; }
+        std::vector<uint64_t> tile0(ns + 1, 0);
+        for (uint32_t i = 0; i < ns; i++) tile0[i + 1] = tile0[i] + fastx_n_tiles(arena + base[i], sl[i].b - sl[i].a);
+        if (tile0[ns] > 0x7FFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+        HIPCHK(c, I.x_tiles.ensure(tile0[ns])); HIPCHK(c, I.x_base.ensure(tile0[ns]));
+        HIPCHK(c, I.x_tot.ensure(5 * (uint64_t)ns)); HIPCHK(c, I.x_h_tot.ensure(5 * (uint64_t)ns));
+        std::vector<FxJob> jobs(ns);
+        HIPCHK(c, I.tm_scan.begin(c->timing_level >= 1, c->stream));
+        for (uint32_t i = 0; i < ns; i++) {
+            // a slice is scanned as a file of its file's format: it begins at a record start, so its lines count from 0
+            const int qs = scan_queue(c, jobs[i], i, arena + base[i], sl[i].b - sl[i].a, files[sl[i].f].format, tile0[i], tile0[i + 1] - tile0[i]);
+            if (qs) return qs;
+            HIPCHK(c, hipMemsetAsync(arena + base[i + 1] - 1, 0x0A, 1, c->stream));
+        }
+        ScanResult R;
+        const int es = scan_emit(c, jobs.data(), ns, ns, base.data(), 0xFFFFFFFFull, R);
+        if (es == CRASS_ERR_UNSUPPORTED && R.decline_file >= 0) {      // (in the FILE's positions)
+            ShardVerdict sv;
+            sv.file = (int32_t)sl[R.decline_file].f; sv.reason = R.decline_reason; sv.pos = R.decline_pos + sl[R.decline_file].a;
+            if (shard_verdict_before(sv, *v)) *v = sv;
+            return CRASS_OK;
+        }
+        if (es) return es;
+        if (v->file >= 0) return CRASS_OK;
+        for (uint32_t i = 0; i < ns; i++) file_reads->push_back(std::make_pair(sl[i].f, R.rbase[i + 1] - R.rbase[i]));
+        *n_reads = R.n_reads; *max_len = (uint32_t)R.max_len;
+        I.sh_n_reads = R.n_reads; I.sh_scanned = true;
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+static void shard_release_all(crass_hip_ctx *c)
+{
+    release_gzip(c); release_bgzf(c); release_scan(c); release_text(c); release_header_ids(c); release_shard(c);
+}
+
+int shard_pack(crass_hip_ctx *c, int pad_uniform, uint64_t read_index_base)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    if (!I.sh_scanned) return CRASS_ERR_STATE;
+    (void)hipSetDevice(c->device);
+    auto run = [&]() -> int {
+        const uint64_t nr = I.sh_n_reads, n_arena = I.sh_base.empty() ? 0 : I.sh_base.back();
+        HIPCHK(c, I.x_h_seq_off.ensure(1)); HIPCHK(c, I.x_h_rec_pos.ensure(1)); HIPCHK(c, I.fa_arena.ensure(16));
+        if (!nr) { I.x_h_seq_off.p[0] = 0; I.x_h_rec_pos.p[0] = 0; }      // (an empty shard: no slice was scanned)
+        const int s = load_text_impl(c, nullptr, I.x_text.p, I.x_h_seq_off.p, nr, pad_uniform, nullptr, read_index_base);
+        if (s) return s;
+        if (nr) {
+            uint64_t n_rep = 0;
+            const int hs = header_ids_device_impl(c, I.fa_arena.p, n_arena, I.x_h_rec_pos.p, nr, nullptr, 1, &n_rep);
+            if (hs) return hs;
+            if (n_rep == 0) c->R.header_id = nullptr;   // (all names of the shard unique: as a load without header ids)
+        }
+        I.fa_bytes = n_arena; I.have_arena = true;
+        return crass_hip_fastx_names_build_device(c, nullptr, 0, nullptr, 0);
+    };
+    const int s = run();
+    shard_release_all(c);
+    if (s) { c->have_reads = false; drop_arena(c); }
+    else I.sh_loaded = true;
+    return s;
+}
+
+void shard_abort(crass_hip_ctx *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    shard_release_all(c);
+    c->have_reads = false;
+    drop_arena(c);
+}
+
+int shard_records(const crass_hip_ctx *c, const uint8_t **arena, uint64_t *n_bytes, const uint64_t **rec_pos, uint64_t *n_reads)
+{
+    if (!c || !arena || !n_bytes || !rec_pos || !n_reads) return CRASS_ERR_INVALID_ARG;
+    if (!c->in.sh_loaded || !c->in.have_arena || !c->have_reads) return CRASS_ERR_STATE;
+    *arena = c->in.fa_arena.p; *n_bytes = c->in.fa_bytes; *rec_pos = c->in.x_h_rec_pos.p; *n_reads = c->R.n_reads;
+    return CRASS_OK;
+}

@@ -46,6 +46,19 @@ struct FxJob {
     // arena_base + the file position.  Offences stay in file positions.
     uint64_t text_base, read_base, arena_base;
 };
+// k_fx_cut_probe: the probe of fastx_scan.h over bytes[0, n) (device pointer, any alignment).  fx_probe_plan fills everything
+// but part, which the caller points at n_blocks FxProbe of device memory; fx_probe_fold folds their host copy.
+static constexpr uint32_t kFxProbeMaxBlocks = 1024;
+struct FxProbeJob {
+    const uint8_t *bytes; uint64_t n;
+    uint32_t lead, left_is_ls;      // address of bytes modulo 16; whether position 0 is a line start
+    uint64_t n_tiles, tiles_per_block;
+    uint32_t n_blocks;
+    FxProbe *part;
+};
+void fx_probe_plan(const uint8_t *bytes, uint64_t n, uint32_t left_is_ls, FxProbeJob *P);
+void fx_probe_fold(const FxProbe *part, uint32_t n_blocks, FxProbe *out);
+hipError_t launch_fx_cut_probe(const FxProbeJob &P, hipStream_t st);
 uint32_t fastx_tile_bytes();
 uint64_t fastx_n_tiles(const uint8_t *bytes, uint64_t n);
 hipError_t launch_fx_summary(const FxJob &J, hipStream_t st);

@@ -73,9 +73,88 @@ int fastx_scan_serial(const uint8_t *bytes, uint64_t n, FxHostScan *out)
     return CRASS_OK;
 }
 
+// the probe of fastx_scan.h, one byte after the other
+int fx_probe_serial(const uint8_t *bytes, uint64_t n, bool left_is_ls, FxProbe *out)
+{
+    FxProbe P{};
+    P.gt = kFxNone;
+    for (int k = 0; k < 4; k++) P.ls[k] = kFxNone;
+    bool ls = left_is_ls;
+    for (uint64_t i = 0; i < n; i++) {
+        if (ls) {
+            if (P.n_ls < 4) P.ls[P.n_ls++] = i;
+            if (bytes[i] == 0x3E && P.gt == kFxNone) P.gt = i;
+        }
+        ls = fx_is_nl(bytes[i]);
+        P.n_nl += ls ? 1 : 0;
+    }
+    *out = P;
+    return CRASS_OK;
+}
+
 } // namespace crass
 
 extern "C" {
+
+int crass_fastx_cut_probe_host(const uint8_t *bytes, uint64_t n_bytes, int left_is_ls, uint64_t out[7])
+{
+    if (!out || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
+    crass::FxProbe P;
+    crass::fx_probe_serial(bytes, n_bytes, left_is_ls != 0, &P);
+    out[0] = P.n_nl; out[1] = P.n_ls; for (int k = 0; k < 4; k++) out[2 + k] = P.ls[k]; out[6] = P.gt;
+    return CRASS_OK;
+}
+
+void crass_fastx_shards_free(crass_fastx_shards *s)
+{
+    if (!s) return;
+    free((void *)s->rank_read_base); free((void *)s->cut_file); free((void *)s->cut_pos); free((void *)s->file_read_base); free((void *)s->format);
+    s->rank_read_base = s->cut_pos = s->file_read_base = nullptr; s->cut_file = nullptr; s->format = nullptr;
+}
+
+// The cut rule of fastx_scan.h on the host.  The verdict is crass_fastx_files_scan_host's; an ACCEPTED file's record starts are
+// that scan's rec_pos (regular FASTA: the line starts whose byte is '>'; regular FASTQ: the lines of index 0 modulo 4), so the
+// actual cut is the first record position at or after the nominal one.
+int crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks, const uint64_t *nominal,
+                                  crass_fastx_shards *out)
+{
+    if (!out) return CRASS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->decline_file = -1; out->n_ranks = n_ranks; out->n_files = n_files;
+    if (!n_ranks || n_ranks > 64) return CRASS_ERR_INVALID_ARG;
+    crass_fastx_files_layout L;
+    const int s = crass_fastx_files_scan_host(bytes, n_bytes, n_files, &L);
+    out->decline_file = L.decline_file; out->decline_reason = L.decline_reason; out->decline_pos = L.decline_pos; out->bgzf = L.bgzf;
+    if (s) return s;
+    // text space: file f is [tb[f], tb[f + 1]); arena positions count one byte more per file in front
+    std::vector<uint64_t> tb(n_files + 1);
+    for (uint32_t f = 0; f <= n_files; f++) tb[f] = L.file_byte_base[f] - f;
+    const uint64_t T = tb[n_files], nr = L.n_reads;
+    for (uint32_t g = 1; nominal && g < n_ranks; g++)
+        if (nominal[g - 1] > T || (g > 1 && nominal[g - 1] < nominal[g - 2])) { crass_fastx_files_layout_free(&L); return CRASS_ERR_INVALID_ARG; }
+    uint64_t *rb = (uint64_t *)malloc((n_ranks + 1) * 8), *cp = (uint64_t *)malloc((n_ranks + 1) * 8), *fb = (uint64_t *)malloc((n_files + 1) * 8);
+    uint32_t *cf = (uint32_t *)malloc((n_ranks + 1) * 4);
+    int32_t *fm = (int32_t *)malloc(n_files * 4);
+    if (!rb || !cp || !fb || !cf || !fm) { free(rb); free(cp); free(fb); free(cf); free(fm); crass_fastx_files_layout_free(&L); return CRASS_ERR_OOM; }
+    for (uint32_t g = 0; g <= n_ranks; g++) {
+        const uint64_t x = g == 0 ? 0 : g == n_ranks ? T : nominal ? nominal[g - 1] : (uint64_t)((unsigned __int128)T * g / n_ranks);
+        // the file that holds text position x, and the first record of the set at or behind it
+        const uint32_t f = (uint32_t)(std::upper_bound(tb.begin(), tb.end(), x) - tb.begin()) - 1;
+        uint64_t r = nr;
+        if (f < n_files) r = (uint64_t)(std::lower_bound(L.rec_pos, L.rec_pos + nr, x + f) - L.rec_pos);
+        rb[g] = r;
+        if (r == nr) { cf[g] = n_files; cp[g] = 0; }
+        else {
+            const uint32_t rf = (uint32_t)(std::upper_bound(L.file_read_base, L.file_read_base + n_files + 1, r) - L.file_read_base) - 1;
+            cf[g] = rf; cp[g] = L.rec_pos[r] - L.file_byte_base[rf];
+        }
+    }
+    memcpy(fb, L.file_read_base, (n_files + 1) * 8); memcpy(fm, L.format, n_files * 4);
+    out->n_reads = nr; out->max_len = L.max_len;
+    out->rank_read_base = rb; out->cut_file = cf; out->cut_pos = cp; out->file_read_base = fb; out->format = fm;
+    crass_fastx_files_layout_free(&L);
+    return CRASS_OK;
+}
 
 int crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_layout *out)
 {

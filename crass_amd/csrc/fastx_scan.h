@@ -73,6 +73,38 @@ CRASS_HD inline FxClass4 fx_class4(uint32_t v)
 CRASS_HD inline uint64_t fx_offence(uint64_t line_pos, uint32_t reason) { return (line_pos << 8) | reason; }
 static const uint64_t kFxNoOffence = ~0ull;
 
+// ---- cutting a job's files into record-aligned shards (crass_fastx_files_shards_host, crass_hip_group_load_fastx_files) ----
+// TEXT SPACE: the files' texts back to back in file order, no byte between them (a BGZF file's text is its inflated text); T is
+// its size.  NOMINAL cuts: n_ranks - 1 non-decreasing positions in [0, T] (by default T g / n_ranks); cut 0 is 0, cut n_ranks is T.
+// A RECORD START is defined by lines alone, whether or not the file will be accepted: every file's position 0; in a file whose
+// byte 0 is '>' every line start whose byte is '>'; in a file whose byte 0 is '@' every line start whose line index (the '\n' bytes
+// in front of it in that file) is 0 modulo 4 — a quality line may start with '@', so nothing near the cut can tell.  A line start
+// is position 0 or a position behind a '\n', and it is smaller than the file's text length.  A file of another first byte has no
+// record start but 0 (the scan declines it with FX_FIRST_BYTE anyway).
+// The ACTUAL cut c_g is the smallest record start at or after nominal cut g, or T: c_g <= c_{g+1}, a rank may be empty, rank g
+// owns [c_g, c_{g+1}) — a tail of one file, whole files, a head of one file, each slice beginning at a record start.
+//
+// What a probe of a byte range [a, b) of ONE file's text reports (k_fx_cut_probe, and fx_probe_serial on the host), positions
+// counted from a; kFxNone: there is none.  left_is_ls says whether position a is itself a line start (a == 0, or byte a - 1 is '\n').
+static const uint64_t kFxNone = ~0ull;
+struct FxProbe {
+    uint64_t n_nl;           // '\n' bytes in the range
+    uint64_t n_ls;           // how many of ls[] are there: min(4, line starts in the range)
+    uint64_t ls[4];          // the range's first four line starts, ascending
+    uint64_t gt;             // its first line start whose byte is '>'
+};
+// the first record start in the range from its probe: format is the file's byte 0, nl_before the '\n' bytes of the file in
+// front of a (FASTQ: the k-th line start of the range is line nl_before + k, one more when a is no line start itself)
+CRASS_HD inline uint64_t fx_probe_pick(const FxProbe &P, int32_t format, uint64_t nl_before, bool left_is_ls)
+{
+    if (format == 0x3E) return P.gt;
+    if (format != 0x40) return kFxNone;
+    const uint64_t first_idx = nl_before + (left_is_ls ? 0u : 1u);
+    const uint64_t k = (0u - first_idx) & 3u;
+    return k < P.n_ls ? P.ls[k] : kFxNone;
+}
+int fx_probe_serial(const uint8_t *bytes, uint64_t n, bool left_is_ls, FxProbe *out);      // the host restatement (fastx_scan.cpp)
+
 // ---- the serial host restatement of the whole scan (fastx_scan.cpp) ----
 // rec_pos / seq_off: malloc'd arrays of n_reads + 1 entries (free()), nullptr when the input is declined
 struct FxHostScan {

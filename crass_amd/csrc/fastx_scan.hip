@@ -15,6 +15,8 @@
 //                   every header line start writes rec_pos / seq_off, every offence of fastx_scan.h is min-ed into the verdict.
 //                   Several files as one set (crass_hip_load_fastx_files): a launch per file with the file's text base, read
 //                   base and arena base, so that all files fill one text, one seq_off and one rec_pos (arena positions).
+//   k_fx_cut_probe  (beside the scan, for a group's files load) what a rank knows about a byte range before the cuts are known:
+//                   its '\n' bytes, first four line starts and first '>' line start — one pass, one part per block, no atomics.
 // Temporary HBM per input byte: 72 / 4096 for the tile arrays, at most 1 for the text, 16 per record for the two arrays.
 // No byte beyond the input is read: the first and the last vector are loaded byte by byte where they are not whole.
 #include "fastx_launch.h"
@@ -308,6 +310,89 @@ __global__ __launch_bounds__(kFxThreads) void k_fx_emit(const FxJob J)
             for (uint32_t i = a > shift ? a : shift; i < b && i < n_out; i++) if (g0 + i < J.text_cap) J.text[g0 + i] = s_out[i];
         }
     }
+}
+
+// The probe of fastx_scan.h over a byte range: a stream, one aligned 16-byte load per 16 bytes (fx_load: the range's first and
+// last vector byte by byte where they are not whole, so no byte outside the range is even loaded).  Block b walks the tiles
+// [b tiles_per_block, (b + 1) tiles_per_block) in order and writes ONE FxProbe of its own: the '\n' bytes of its tiles, their
+// first four line starts and their first '>' line start, positions from the range's first byte.  The blocks' parts are folded
+// in block order (fx_probe_fold), so every minimum is one by position: nothing depends on which block ran first, and there is
+// no atomic.
+__global__ __launch_bounds__(kFxThreads) void k_fx_cut_probe(const FxProbeJob P)
+{
+    __shared__ uint32_t s_w[kFxThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    FxJob J{};
+    J.bytes = P.bytes; J.n = P.n; J.lead = P.lead;      // (what fx_load reads of a job)
+    const uint64_t t_begin = (uint64_t)blockIdx.x * P.tiles_per_block;
+    const uint64_t t_end = t_begin + P.tiles_per_block < P.n_tiles ? t_begin + P.tiles_per_block : P.n_tiles;
+    FxProbe *out = P.part + blockIdx.x;
+    if (tid == 0) { out->ls[0] = out->ls[1] = out->ls[2] = out->ls[3] = kFxNone; }
+    __syncthreads();
+    uint32_t nl_cnt = 0, found = 0;                     // found: the block's line starts so far (the same in every thread)
+    uint64_t gt = kFxNone;                              // (the same in every thread)
+    for (uint64_t t = t_begin; t < t_end; t++) {
+        const uint64_t q0 = t * kFxTileBytes + 16u * tid;
+        FxVec V;
+        fx_load(J, q0, V);
+        // fx_load takes the input's position 0 for a line start; here the caller says whether it is one
+        if (!P.left_is_ls && P.lead >= q0 && P.lead < q0 + 16) V.ls &= ~(1u << (uint32_t)(P.lead - q0));
+        nl_cnt += (uint32_t)__builtin_popcount(V.nl);
+        if (found < 4u) {
+            uint32_t tot;
+            uint32_t k = found + fx_scan_add<kFxThreads / 64>((uint32_t)__builtin_popcount(V.ls), s_w, &tot);
+            for (uint32_t rem = V.ls; rem && k < 4u; rem &= rem - 1u) out->ls[k++] = q0 - P.lead + (uint32_t)__builtin_ctz(rem);
+            found += tot;
+        }
+        if (gt == kFxNone) {
+            const uint32_t m = V.ls & V.gt;
+            uint32_t code = m ? 16u * tid + (uint32_t)__builtin_ctz(m) : 0xFFFFFFFFu;      // offset in the tile
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) { const uint32_t y = (uint32_t)__shfl_xor((int)code, s); code = y < code ? y : code; }
+            if (lane == 0) s_w[wv] = code;
+            __syncthreads();
+            uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+            for (int k = 0; k < kFxThreads / 64; k++) mn = s_w[k] < mn ? s_w[k] : mn;
+            __syncthreads();
+            if (mn != 0xFFFFFFFFu) gt = t * kFxTileBytes - P.lead + mn;
+        }
+    }
+    uint32_t tot_nl;
+    (void)fx_scan_add<kFxThreads / 64>(nl_cnt, s_w, &tot_nl);      // (the launch keeps a block's tiles below 4 GB)
+    if (tid == 0) { out->n_nl = tot_nl; out->n_ls = found < 4u ? found : 4u; out->gt = gt; }
+}
+
+// the blocks' parts in block order -> the range's probe
+void fx_probe_fold(const FxProbe *part, uint32_t n_blocks, FxProbe *out)
+{
+    FxProbe R{};
+    R.gt = kFxNone;
+    for (int k = 0; k < 4; k++) R.ls[k] = kFxNone;
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        R.n_nl += part[b].n_nl;
+        for (uint64_t k = 0; k < part[b].n_ls && R.n_ls < 4; k++) R.ls[R.n_ls++] = part[b].ls[k];
+        if (R.gt == kFxNone) R.gt = part[b].gt;
+    }
+    *out = R;
+}
+
+// the grid of a probe over n bytes at this address: at most kFxProbeMaxBlocks blocks of as many tiles each
+void fx_probe_plan(const uint8_t *bytes, uint64_t n, uint32_t left_is_ls, FxProbeJob *P)
+{
+    *P = FxProbeJob{};
+    P->bytes = bytes; P->n = n; P->lead = (uint32_t)((uintptr_t)bytes & 15u); P->left_is_ls = left_is_ls ? 1u : 0u;
+    P->n_tiles = fastx_n_tiles(bytes, n);
+    P->tiles_per_block = (P->n_tiles + kFxProbeMaxBlocks - 1) / kFxProbeMaxBlocks;
+    if (!P->tiles_per_block) P->tiles_per_block = 1;
+    P->n_blocks = (uint32_t)((P->n_tiles + P->tiles_per_block - 1) / P->tiles_per_block);
+}
+
+hipError_t launch_fx_cut_probe(const FxProbeJob &P, hipStream_t st)
+{
+    if (!P.n || !P.n_blocks || !P.part || P.tiles_per_block > (0xFFFFFFFFull / kFxTileBytes)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_fx_cut_probe, dim3(P.n_blocks), dim3(kFxThreads), 0, st, P);
+    return hipGetLastError();
 }
 
 uint32_t fastx_tile_bytes() { return kFxTileBytes; }

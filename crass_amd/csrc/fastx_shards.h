@@ -1,0 +1,61 @@
+// fastx_shards.h — what the group (group.cpp) and the device ingest (engine_ingest.cpp) share about loading record-aligned
+// shards of a job's files (crass_hip_group_load_fastx_files): one rank's three steps, between which the group's threads meet
+// at barriers and rank 0 combines.  The cut rule is fastx_scan.h's.  Not part of the public ABI.
+#pragma once
+#include "../../include/crass_hip.h"
+#include "fastx_scan.h"
+
+#include <utility>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace crass {
+
+// what the host knows of a file before a byte goes up
+struct ShardFile {
+    const uint8_t *bytes; uint64_t n_bytes;
+    uint64_t n_text;                       // the text's size (BGZF: the members' ISIZE summed)
+    const crass_bgzf_index *ix;            // nullptr: plain text
+    int32_t format;                        // the text's byte 0; a BGZF file's is known once a rank has inflated its first member
+};
+struct ShardPos { uint32_t file; uint64_t pos; };      // a position of the text space: (n_files, 0) is its end
+// a rank's part of one file before the cuts are known, and its probe
+struct ShardPiece {
+    uint32_t file; uint64_t a, b;          // the text range [a, b) of that file
+    bool left_is_ls;                       // a is a line start
+    int32_t first_byte;                    // a == 0: the text's byte 0
+    FxProbe probe;
+};
+// a decline: file -1 is none.  Order: the first file wins; in a file a compression decline comes before a FASTA / FASTQ one
+// (the host inflates a file before it scans it), then the smallest (member | line position, reason)
+struct ShardVerdict { int32_t file = -1, reason = 0; uint64_t pos = 0; crass_bgzf_verdict bgzf{}; };
+inline bool shard_verdict_before(const ShardVerdict &x, const ShardVerdict &y)
+{
+    if (x.file < 0 || y.file < 0) return y.file < 0 && x.file >= 0;
+    if (x.file != y.file) return x.file < y.file;
+    const bool xz = x.bgzf.reason != 0, yz = y.bgzf.reason != 0;
+    if (xz != yz) return xz;
+    if (xz) return x.bgzf.member != y.bgzf.member ? x.bgzf.member < y.bgzf.member : x.bgzf.reason < y.bgzf.reason;
+    return x.pos != y.pos ? x.pos < y.pos : x.reason < y.reason;
+}
+
+} // namespace crass
+
+// 1. Opens a load (no reads resident from here on), stages the text of [lo, hi) into scratch — plain bytes from the host, of a
+//    BGZF file the members that overlap the range, inflated — and probes every piece.  A decline met here (a member that does
+//    not inflate, a BGZF text whose byte 0 is neither '>' nor '@') goes into *v with CRASS_OK: the pieces in front of that
+//    file are staged and probed all the same, the ones behind it are not.
+int shard_stage_probe(crass_hip_ctx *c, const crass::ShardFile *files, uint32_t n_files, crass::ShardPos lo, crass::ShardPos hi,
+                      std::vector<crass::ShardPiece> *pieces, crass::ShardVerdict *v);
+// 2. The actual range [lo, hi) as slices on the rank's arena (the staged bytes device to device, the tail behind them from the
+//    host or from further BGZF members), each followed by a '\n', scanned by the three scan kernels.  file_reads: (file, records)
+//    per slice.  Declines go into *v with CRASS_OK; n_reads is then not to be used.
+int shard_scan(crass_hip_ctx *c, const crass::ShardFile *files, uint32_t n_files, crass::ShardPos lo, crass::ShardPos hi,
+               std::vector<std::pair<uint32_t, uint64_t>> *file_reads, uint64_t *n_reads, uint32_t *max_len, crass::ShardVerdict *v);
+// 3. One pack launch over the scanned text, the header ids and the name table on the arena; every scratch goes back.
+int shard_pack(crass_hip_ctx *c, int pad_uniform, uint64_t read_index_base);
+// ... or nothing: the scratch goes back, no reads, no arena
+void shard_abort(crass_hip_ctx *c);
+// the arena and the records of the last shard_pack (CRASS_ERR_STATE: there is none)
+int shard_records(const crass_hip_ctx *c, const uint8_t **arena, uint64_t *n_bytes, const uint64_t **rec_pos, uint64_t *n_reads);
+#pragma GCC visibility pop

@@ -7,11 +7,13 @@
 // (communicators from ncclCommInitAll).  RCCL is bound at run time (dlopen of librccl.so.1: the library stays loadable
 // where RCCL is absent, and a process that already holds an RCCL — torch's — shares it); a failed RCCL call is
 // reported as CRASS_ERR_RCCL with its error string, never retried by other means.
-// Everything here goes through the public C ABI of the contexts; nothing computes a search result.
+// Everything here goes through the public C ABI of the contexts — but for a files load (crass_hip_group_load_fastx_files), whose
+// three steps per rank are fastx_shards.h's —; nothing computes a search result.
 #include "../../include/crass_hip.h"
 
 #include <hip/hip_runtime.h>
 #include "devmem.h"
+#include "fastx_shards.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 
@@ -130,7 +132,7 @@ private:
     std::condition_variable cv_;
 };
 
-enum Phase : unsigned { PH_SEED = 1, PH_MERGE = 2, PH_RECRUIT = 4, PH_LOAD = 8 };
+enum Phase : unsigned { PH_SEED = 1, PH_MERGE = 2, PH_RECRUIT = 4, PH_LOAD = 8, PH_LOAD_FILES = 16 };
 
 const bool g_debug = getenv("CRASS_GROUP_DEBUG") != nullptr;           // stage trace on stderr
 #define GDBG(...) do { if (g_debug) { fprintf(stderr, "[crass_group] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
@@ -180,7 +182,30 @@ struct crass_hip_group {
         std::vector<char> dr; uint32_t stride = 0, max_len = 0; bool ready = false;
     } C;
     struct { std::vector<uint32_t> cand_token; bool ready = false; } M;
-    struct { std::vector<uint8_t> chars; std::vector<uint64_t> off; } T;      // crass_hip_group_fetch_text's result
+    struct Text { std::vector<uint8_t> chars; std::vector<uint64_t> off; };
+    Text T;                                     // crass_hip_group_fetch_text's result
+    Text TH, TQ;                                // crass_hip_group_fetch_header_lines' and crass_hip_group_fetch_quality's
+    // a files load (crass_hip_group_load_fastx_files, fastx_shards.h): what the ranks share between its barriers.  Rank r writes
+    // entry r of the per-rank vectors, rank 0 combines between two barriers, everybody reads behind the second
+    bool files_load = false;                    // the last load was one, and was accepted
+    struct FilesJob {
+        std::vector<crass::ShardFile> files;
+        uint32_t nf = 0, nf_eff = 0;            // the files in front of the first one the host declined; ... or a rank's staging did
+        int pad_uniform = 0;
+        std::vector<uint64_t> tb;               // [nf+1] text-space position of every file's byte 0
+        std::vector<uint64_t> nom_x;            // [n+1] the nominal cuts in the text space
+        std::vector<crass::ShardPos> nom, cut;  // [n+1] nominal and actual cuts
+        std::vector<std::vector<crass::ShardPiece>> pieces;
+        std::vector<crass::ShardVerdict> v_stage, v_scan;
+        std::vector<std::vector<std::pair<uint32_t, uint64_t>>> file_reads;
+        std::vector<uint64_t> n_reads, rank_base;
+        std::vector<uint32_t> max_len;
+        crass::ShardVerdict pend, verdict;      // the decline that waits for the files in front of it; the job's
+        bool declined = false;
+    } F;
+    struct { std::vector<uint64_t> cut_pos, file_read_base; std::vector<uint32_t> cut_file; std::vector<int32_t> format; } S;      // crass_fastx_shards' arrays
+    // the names of every rank's pass-1 records, for the other ranks to look up (found headers across ranks)
+    std::vector<Text> names;
     struct {
         std::vector<uint64_t> read; std::vector<uint8_t> low; std::vector<uint32_t> start, end, token; std::vector<uint16_t> dr_len;
         std::vector<char> dr; uint32_t stride = 0; bool ready = false;
@@ -266,11 +291,128 @@ void collect_extra(crass_hip_group *g)
     }
 }
 
+// ---- a files load: record-aligned shards (fastx_shards.h) ----
+// the file and the position inside it of text-space position x, over the first nf files
+crass::ShardPos locate(const std::vector<uint64_t> &tb, uint32_t nf, uint64_t x)
+{
+    if (x >= tb[nf]) return crass::ShardPos{nf, 0};
+    const uint32_t f = (uint32_t)(std::upper_bound(tb.begin(), tb.begin() + nf + 1, x) - tb.begin()) - 1;
+    return crass::ShardPos{f, x - tb[f]};
+}
+
+// rank 0, between two barriers: every rank's pieces are probed.  The actual cuts by the rule of fastx_scan.h: a nominal cut at a
+// file's position 0 is a record start; else the cut's rank has probed the range that begins there — the '\n' bytes of that
+// file in front of it are the sum over the ranks before —, and "none in my range" is the next file's position 0 where the
+// range reaches its file's end, else the next rank's cut: resolved from the last rank down.
+int combine_cuts(crass_hip_group *g)
+{
+    auto &J = g->F;
+    const int N = g->n;
+    // a decline that a rank met while staging: the files in front of it go on, it waits for their verdict
+    for (int r = 0; r < N; r++) if (crass::shard_verdict_before(J.v_stage[r], J.pend)) J.pend = J.v_stage[r];
+    J.nf_eff = J.pend.file >= 0 ? (uint32_t)J.pend.file : J.nf;
+    for (int r = 0; r < N; r++) for (const crass::ShardPiece &pc : J.pieces[r]) if (pc.a == 0 && J.files[pc.file].ix) J.files[pc.file].format = pc.first_byte;
+    const uint32_t nf = J.nf_eff;
+    J.cut.assign(N + 1, crass::ShardPos{nf, 0});
+    J.cut[0] = crass::ShardPos{0, 0};
+    for (int k = N - 1; k >= 1; k--) {
+        const crass::ShardPos x = locate(J.tb, nf, J.nom_x[k]);
+        if (x.file >= nf || x.pos == 0) { J.cut[k] = x; continue; }
+        J.cut[k] = J.cut[k + 1];
+        if (J.pieces[k].empty()) continue;              // (an empty nominal range: the next rank's cut)
+        const crass::ShardPiece &pc = J.pieces[k][0];
+        if (pc.file != x.file || pc.a != x.pos) return CRASS_ERR_STATE;
+        uint64_t nl_before = 0;
+        for (int q = 0; q < k; q++) for (const crass::ShardPiece &o : J.pieces[q]) if (o.file == x.file) nl_before += o.probe.n_nl;
+        const uint64_t pick = crass::fx_probe_pick(pc.probe, J.files[x.file].format, nl_before, pc.left_is_ls);
+        if (pick != crass::kFxNone) J.cut[k] = crass::ShardPos{x.file, x.pos + pick};
+        else if (pc.b == J.files[x.file].n_text) J.cut[k] = crass::ShardPos{x.file + 1, 0};
+    }
+    return CRASS_OK;
+}
+
+// rank 0, between two barriers: every rank's slices are scanned.  The job's verdict, or every rank's first read and the
+// exchange's row capacity from the largest shard (every rank must use the same one)
+void finish_scan(crass_hip_group *g)
+{
+    auto &J = g->F;
+    J.verdict = J.pend;
+    for (int r = 0; r < g->n; r++) if (crass::shard_verdict_before(J.v_scan[r], J.verdict)) J.verdict = J.v_scan[r];
+    J.declined = J.verdict.file >= 0;
+    if (J.declined) return;
+    J.rank_base.assign(g->n + 1, 0);
+    uint64_t largest = 0;
+    for (int r = 0; r < g->n; r++) { J.rank_base[r + 1] = J.rank_base[r] + J.n_reads[r]; largest = std::max(largest, J.n_reads[r]); }
+    if (!g->cap_rows_forced) g->cap_rows = crass_hip_exchange_rows_for(largest);
+}
+
+void load_files_rank(crass_hip_group *g, int r)
+{
+    auto &J = g->F;
+    crass_hip_ctx *c = g->ctx[r];
+    auto ok = [&] { return g->failed.load(std::memory_order_acquire) == 0; };
+    note(g, r, shard_stage_probe(c, J.files.data(), J.nf, J.nom[r], J.nom[r + 1], &J.pieces[r], &J.v_stage[r]));
+    g->bar->wait();                                     // every rank's probes are there
+    if (r == 0 && ok()) { try { note(g, 0, combine_cuts(g)); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+    g->bar->wait();                                     // the actual cuts are known
+    if (ok()) note(g, r, shard_scan(c, J.files.data(), J.nf_eff, J.cut[r], J.cut[r + 1], &J.file_reads[r], &J.n_reads[r], &J.max_len[r], &J.v_scan[r]));
+    g->bar->wait();                                     // every rank's records are counted
+    if (r == 0 && ok()) { try { finish_scan(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+    g->bar->wait();                                     // the verdict, or every rank's first read
+    if (ok() && !J.declined) {
+        int s = shard_pack(c, J.pad_uniform, J.rank_base[r]);
+        if (!s) s = setup_exchange(g, r);
+        note(g, r, s);
+    } else shard_abort(c);
+}
+
+// found headers across the ranks of a files load (readsFound is keyed by header, libcrispr.cpp:138,411): installed header ids
+// are per rank, so every rank publishes the names of its pass-1 records (its header lines, cut at the name) ...
+int names_publish(crass_hip_group *g, int r)
+{
+    crass_hip_group::Text &NM = g->names[r];
+    NM.chars.clear(); NM.off.assign(1, 0);
+    crass_candidates cd;
+    int s = crass_hip_get_candidates(g->ctx[r], &cd);
+    if (s || !cd.n) return s;
+    const uint8_t *arena = nullptr; const uint64_t *rec_pos = nullptr; uint64_t nb = 0, nr = 0;
+    if ((s = shard_records(g->ctx[r], &arena, &nb, &rec_pos, &nr))) return s;
+    std::vector<uint64_t> idx(cd.n);
+    std::vector<uint32_t> name_len(cd.n);
+    for (uint64_t k = 0; k < cd.n; k++) idx[k] = cd.read_idx[k] - g->first[r];
+    crass_text t;
+    if ((s = crass_hip_fetch_header_lines_device(g->ctx[r], arena, nb, rec_pos, nr, idx.data(), cd.n, &t, name_len.data()))) return s;
+    for (uint64_t k = 0; k < cd.n; k++) {
+        NM.chars.insert(NM.chars.end(), t.chars + t.off[k], t.chars + t.off[k] + name_len[k]);
+        NM.off.push_back(NM.chars.size());
+    }
+    return CRASS_OK;
+}
+
+// ... and looks the other ranks' names up in its own table: its namesakes are marked found before pass 2
+int names_lookup(crass_hip_group *g, int r)
+{
+    std::vector<uint64_t> &e = g->extra[r];
+    e.clear();
+    std::vector<uint64_t> first;
+    for (int q = 0; q < g->n; q++) {
+        const crass_hip_group::Text &NM = g->names[q];
+        const uint64_t nq = NM.off.size() - 1;
+        if (q == r || !nq) continue;
+        first.resize(nq);
+        const int s = crass_hip_fastx_names_find(g->ctx[r], NM.chars.data(), NM.off.data(), nq, first.data());
+        if (s) return s;
+        for (uint64_t k = 0; k < nq; k++) if (first[k] != CRASS_NAME_NOT_FOUND) e.push_back(first[k]);
+    }
+    return CRASS_OK;
+}
+
 // one rank's part of a job; every rank passes the same barriers whatever happens
 void run_rank(crass_hip_group *g, int r, unsigned phases)
 {
     crass_hip_ctx *c = g->ctx[r];
     auto ok = [&] { return g->failed.load(std::memory_order_acquire) == 0; };
+    if (phases & PH_LOAD_FILES) { load_files_rank(g, r); return; }
     if (phases & PH_LOAD) {
         int s = crass_hip_load_reads(c, &g->shard[r]);
         if (!s) s = setup_exchange(g, r);
@@ -311,6 +453,11 @@ void run_rank(crass_hip_group *g, int r, unsigned phases)
             g->bar->wait();
             if (r == 0 && ok()) { try { collect_extra(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
             g->bar->wait();
+        }
+        if (g->files_load && g->n > 1) {                            // (with one rank nothing is exchanged)
+            try { if (ok()) note(g, r, names_publish(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
+            g->bar->wait();                                         // every rank's names are there
+            try { if (ok()) note(g, r, names_lookup(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
         }
     }
     if ((phases & PH_RECRUIT) && ok()) {
@@ -452,6 +599,7 @@ int crass_hip_group_load_reads(crass_hip_group *g, const crass_reads *h)
     const int N = g->n;
     const uint64_t n = h->n_reads;
     g->loaded = g->have_p1 = g->have_merge = g->have_p2 = false;
+    g->files_load = false;
     g->C.ready = g->M.ready = g->Q.ready = false;
     g->n_reads = n; g->base = h->read_index_base;
     g->first.assign(N + 1, 0);
@@ -663,6 +811,147 @@ int crass_hip_group_fetch_text(crass_hip_group *g, const uint64_t *read_idx, con
     } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
     o->n = n; o->chars = g->T.chars.data(); o->off = g->T.off.data();
     return CRASS_OK;
+}
+
+// the files of a job as record-aligned shards, one per rank (include/crass_hip.h; the ranks' steps are load_files_rank's)
+int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int pad_uniform,
+                                     const uint64_t *nominal, crass_fastx_shards *out)
+{
+    if (out) { memset(out, 0, sizeof(*out)); out->decline_file = -1; out->n_files = n_files; out->n_ranks = g ? (uint32_t)g->n : 0; }
+    if (!g || !n_files || !bytes || !n_bytes || pad_uniform < 0 || pad_uniform > 2) return CRASS_ERR_INVALID_ARG;
+    for (uint32_t f = 0; f < n_files; f++) if (n_bytes[f] && !bytes[f]) return CRASS_ERR_INVALID_ARG;
+    const int N = g->n;
+    for (int k = 1; nominal && k + 1 < N; k++) if (nominal[k] < nominal[k - 1]) return CRASS_ERR_INVALID_ARG;
+    g->loaded = g->have_p1 = g->have_merge = g->have_p2 = false;
+    g->files_load = false;
+    g->C.ready = g->M.ready = g->Q.ready = false;
+    g->n_reads = 0; g->base = 0;
+    g->first.assign(N + 1, 0);
+    for (auto &m : g->dup_local) m.clear();
+    for (auto &e : g->extra) e.clear();
+    g->have_dups = false; g->hid_global.clear();
+    std::vector<crass_bgzf_index> ixs;
+    struct FreeIx { std::vector<crass_bgzf_index> &v; ~FreeIx() { for (auto &x : v) crass_bgzf_index_free(&x); } } free_ix{ixs};
+    int st = CRASS_OK;
+    try {
+        g->F = crass_hip_group::FilesJob();
+        auto &J = g->F;
+        g->names.assign(N, crass_hip_group::Text());
+        ixs.assign(n_files, crass_bgzf_index{});
+        // what every file is and how much text it holds (host: first bytes, BGZF index); the first file that cannot be taken
+        // waits with its decline: a file in front of it may still offend in the scan
+        J.files.assign(n_files, crass::ShardFile{});
+        J.nf = n_files;
+        for (uint32_t f = 0; f < n_files; f++) {
+            crass::ShardFile &F = J.files[f];
+            F.bytes = bytes[f]; F.n_bytes = n_bytes[f];
+            auto pend = [&](int32_t reason) { J.pend.file = (int32_t)f; J.pend.reason = reason; J.nf = f; };
+            if (F.n_bytes >= 2 && F.bytes[0] == 0x1F && F.bytes[1] == 0x8B) {
+                const int s = crass_bgzf_index_host(F.bytes, F.n_bytes, &ixs[f]);
+                if (s == CRASS_ERR_UNSUPPORTED) { pend(0); J.pend.bgzf = ixs[f].decline; break; }      // (plain gzip too: one deflate stream cannot be cut)
+                if (s) return s;
+                F.ix = &ixs[f]; F.n_text = ixs[f].out_off[ixs[f].n_members];
+                if (F.n_text == 0) { pend(crass::FX_EMPTY); break; }
+            } else {
+                if (F.n_bytes == 0) { pend(crass::FX_EMPTY); break; }
+                if (!crass::fx_is_hdr_char(F.bytes[0])) { pend(crass::FX_FIRST_BYTE); break; }
+                F.n_text = F.n_bytes; F.format = F.bytes[0];
+            }
+        }
+        const uint32_t nf = J.nf;
+        J.tb.assign(nf + 1, 0);
+        for (uint32_t f = 0; f < nf; f++) J.tb[f + 1] = J.tb[f] + J.files[f].n_text;
+        const uint64_t T = J.tb[nf];
+        if (nominal && nf == n_files) for (int k = 0; k + 1 < N; k++) if (nominal[k] > T) return CRASS_ERR_INVALID_ARG;
+        J.nom_x.assign(N + 1, T);
+        J.nom_x[0] = 0;
+        for (int k = 1; k < N; k++) J.nom_x[k] = nominal ? std::min(nominal[k - 1], T) : (uint64_t)((unsigned __int128)T * (unsigned)k / (unsigned)N);
+        J.nom.resize(N + 1);
+        for (int k = 0; k <= N; k++) J.nom[k] = locate(J.tb, nf, J.nom_x[k]);
+        J.pad_uniform = pad_uniform;
+        J.pieces.assign(N, {}); J.v_stage.assign(N, crass::ShardVerdict()); J.v_scan.assign(N, crass::ShardVerdict());
+        J.file_reads.assign(N, {}); J.n_reads.assign(N, 0); J.max_len.assign(N, 0);
+        J.cut.assign(N + 1, crass::ShardPos{nf, 0});
+        st = dispatch(g, PH_LOAD_FILES);
+        for (auto &F : J.files) { F.ix = nullptr; F.bytes = nullptr; }      // (the caller's bytes and this call's indexes: used inside this call only)
+        if (st) return st;
+        if (J.declined) {
+            if (out) { out->decline_file = J.verdict.file; out->decline_reason = J.verdict.reason; out->decline_pos = J.verdict.pos; out->bgzf = J.verdict.bgzf; }
+            return CRASS_ERR_UNSUPPORTED;
+        }
+        g->first = J.rank_base; g->n_reads = J.rank_base[N];
+        auto &S = g->S;
+        S.cut_file.assign(N + 1, 0); S.cut_pos.assign(N + 1, 0); S.file_read_base.assign(n_files + 1, 0); S.format.assign(n_files, 0);
+        for (int k = 0; k <= N; k++) { S.cut_file[k] = J.cut[k].file; S.cut_pos[k] = J.cut[k].pos; }
+        for (int r = 0; r < N; r++) for (const auto &fr : J.file_reads[r]) S.file_read_base[fr.first + 1] += fr.second;
+        for (uint32_t f = 0; f < n_files; f++) { S.file_read_base[f + 1] += S.file_read_base[f]; S.format[f] = J.files[f].format; }
+        uint32_t max_len = 0;
+        for (int r = 0; r < N; r++) max_len = std::max(max_len, J.max_len[r]);
+        if (out) {
+            out->n_reads = g->n_reads; out->max_len = max_len;
+            out->rank_read_base = g->first.data(); out->cut_file = S.cut_file.data(); out->cut_pos = S.cut_pos.data();
+            out->file_read_base = S.file_read_base.data(); out->format = S.format.data();
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    g->loaded = true; g->files_load = true;
+    return CRASS_OK;
+}
+
+// header lines (quality == false) or quality strings of reads of the whole job: routed like crass_hip_group_fetch_text, each
+// rank fetches from its own arena, the records are put back in the caller's order
+static int group_fetch_lines(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, bool quality, crass_text *o, uint32_t *name_len_out,
+                             uint8_t *has_qual_out)
+{
+    if (!g || !o || (n && !read_idx)) return CRASS_ERR_INVALID_ARG;
+    if (!g->loaded || !g->files_load) return CRASS_ERR_STATE;
+    for (uint64_t k = 0; k < n; k++) if (read_idx[k] >= g->n_reads) return CRASS_ERR_INVALID_ARG;
+    crass_hip_group::Text &T = quality ? g->TQ : g->TH;
+    try {
+        std::vector<std::vector<uint64_t>> idx(g->n), at(g->n);
+        for (uint64_t k = 0; k < n; k++) {
+            const int r = (int)(std::upper_bound(g->first.begin(), g->first.end(), read_idx[k]) - g->first.begin()) - 1;
+            idx[r].push_back(read_idx[k] - g->first[r]); at[r].push_back(k);
+        }
+        // (a rank's result lives in its own context until that context's next fetch of the kind: all of them are there at once)
+        std::vector<crass_text> part(g->n, crass_text{0, nullptr, nullptr});
+        std::vector<uint32_t> nl;
+        std::vector<uint8_t> hq;
+        for (int r = 0; r < g->n; r++) {
+            const uint64_t m = idx[r].size();
+            if (!m) continue;
+            const uint8_t *arena = nullptr; const uint64_t *rec_pos = nullptr; uint64_t nb = 0, nr = 0;
+            int s = shard_records(g->ctx[r], &arena, &nb, &rec_pos, &nr);
+            if (s) return s;
+            nl.resize(m); hq.resize(m);
+            s = quality ? crass_hip_fetch_quality_device(g->ctx[r], arena, nb, rec_pos, nr, idx[r].data(), m, &part[r], hq.data())
+                        : crass_hip_fetch_header_lines_device(g->ctx[r], arena, nb, rec_pos, nr, idx[r].data(), m, &part[r], nl.data());
+            if (s) return s;
+            for (uint64_t q = 0; q < m; q++) {
+                if (quality && has_qual_out) has_qual_out[at[r][q]] = hq[q];
+                if (!quality && name_len_out) name_len_out[at[r][q]] = nl[q];
+            }
+        }
+        T.off.assign(n + 1, 0);
+        for (int r = 0; r < g->n; r++) for (uint64_t q = 0; q < part[r].n; q++) T.off[at[r][q] + 1] = part[r].off[q + 1] - part[r].off[q];
+        for (uint64_t k = 0; k < n; k++) T.off[k + 1] += T.off[k];
+        T.chars.resize(T.off[n] + 1);
+        for (int r = 0; r < g->n; r++) for (uint64_t q = 0; q < part[r].n; q++) {
+            const uint64_t len = part[r].off[q + 1] - part[r].off[q];
+            if (len) memcpy(T.chars.data() + T.off[at[r][q]], part[r].chars + part[r].off[q], len);
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    o->n = n; o->chars = T.chars.data(); o->off = T.off.data();
+    return CRASS_OK;
+}
+
+int crass_hip_group_fetch_header_lines(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint32_t *name_len_out)
+{
+    return group_fetch_lines(g, read_idx, n, false, out, name_len_out, nullptr);
+}
+
+int crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_qual_out)
+{
+    return group_fetch_lines(g, read_idx, n, true, out, nullptr, has_qual_out);
 }
 
 int crass_hip_group_get_merge(crass_hip_group *g, crass_merge_view *o)

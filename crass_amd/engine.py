@@ -459,6 +459,73 @@ def fastx_files_scan_host(bufs):
         lib.crass_fastx_files_layout_free(C.byref(v))
 
 
+class FastxShards:
+    """The files of a job cut into record-aligned shards (crass_fastx_shards), as numpy copies: n_ranks, n_files, n_reads,
+    max_len, rank_read_base (uint64, n_ranks + 1), cut_file / cut_pos (n_ranks + 1: the file and the text position inside it
+    of every actual cut), file_read_base (uint64, n_files + 1), formats.  A declined set has accepted False and the decline
+    fields of a FastxFilesLayout, and empty arrays."""
+
+    def __init__(self, v):
+        self.n_ranks, self.n_files, self.n_reads, self.max_len = int(v.n_ranks), int(v.n_files), int(v.n_reads), int(v.max_len)
+        self.decline_file, self.decline_reason, self.decline_pos = int(v.decline_file), int(v.decline_reason), int(v.decline_pos)
+        self.bgzf = (int(v.bgzf.reason), int(v.bgzf.member), int(v.bgzf.in_pos))
+        self.accepted = self.decline_file < 0
+        have = bool(v.rank_read_base) and bool(v.cut_file) and bool(v.cut_pos) and bool(v.file_read_base) and bool(v.format)
+        z = np.zeros(0, np.uint64)
+        self.rank_read_base = _np(v.rank_read_base, self.n_ranks + 1, np.uint64).copy() if have else z
+        self.cut_file = _np(v.cut_file, self.n_ranks + 1, np.uint32).copy() if have else np.zeros(0, np.uint32)
+        self.cut_pos = _np(v.cut_pos, self.n_ranks + 1, np.uint64).copy() if have else z
+        self.file_read_base = _np(v.file_read_base, self.n_files + 1, np.uint64).copy() if have else z
+        self.formats = [bytes([int(v.format[f]) & 0xFF]) for f in range(self.n_files)] if have else []
+
+    @property
+    def verdict(self):
+        """what a declined set is compared by: (file, FASTA / FASTQ reason, position, BGZF verdict)"""
+        return (self.decline_file, self.decline_reason, self.decline_pos, self.bgzf)
+
+    @property
+    def cuts(self):
+        """the actual cuts as a list of (file, position)"""
+        return [(int(f), int(p)) for f, p in zip(self.cut_file, self.cut_pos)]
+
+
+def _nominal_arg(nominal, n_ranks):
+    if nominal is None:
+        return None
+    a = np.ascontiguousarray(nominal, dtype=np.uint64).reshape(-1)
+    if len(a) != n_ranks - 1:
+        raise ValueError("nominal needs n_ranks - 1 cuts")
+    return a
+
+
+def fastx_files_shards_host(files, n_ranks, nominal=None):
+    """Several files' bytes cut into n_ranks record-aligned shards on the host (crass_fastx_files_shards_host; no GPU needed):
+    a FastxShards, accepted or declined — what SearchGroup.load_fastx_files is tested against.  nominal: n_ranks - 1
+    non-decreasing positions in the job's text space (None: even cuts)."""
+    lib = _abi.load()
+    arrs, ptrs, lens = _files_args(files)
+    nom = _nominal_arg(nominal, int(n_ranks))
+    v = _abi.FastxShardsC()
+    st = lib.crass_fastx_files_shards_host(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(n_ranks),
+                                           nom.ctypes.data if nom is not None and len(nom) else None, C.byref(v))
+    try:
+        if st not in (0, 2):
+            raise CrassError(st, "crass_fastx_files_shards_host")
+        return FastxShards(v)
+    finally:
+        lib.crass_fastx_shards_free(C.byref(v))
+
+
+def fastx_cut_probe_host(buf, left_is_ls):
+    """The probe of a byte range on the host (crass_fastx_cut_probe_host): uint64 [7] — '\\n' bytes, line starts listed (at most 4),
+    the first four line starts, the first line start whose byte is '>'; ~0 where there is none."""
+    a = _bytes_arg(buf)
+    out = np.zeros(7, np.uint64)
+    _chk(_abi.load().crass_fastx_cut_probe_host(a.ctypes.data if len(a) else None, len(a), 1 if left_is_ls else 0, out.ctypes.data),
+         "crass_fastx_cut_probe_host")
+    return out
+
+
 def fastx_header_ids(buf, rec_pos):
     """header_id[r] = index of the first read with the same name, from the file's bytes and the records' positions
     (crass_fastx_header_ids; host, names compared exactly).  rec_pos: n_reads + 1 entries as in a FastxLayout."""
@@ -1064,6 +1131,18 @@ class SearchEngine:
         self._keep = None
         return lay
 
+    def cut_probe_device(self, src, n_bytes, left_is_ls):
+        """fastx_cut_probe_host's answer for n_bytes bytes on the DEVICE (src: an address or a torch uint8 device tensor, any
+        alignment), by k_fx_cut_probe (crass_hip_fastx_cut_probe_device).  last_cut_probe_ms(): the kernel's HIP-event time."""
+        ptr = src if isinstance(src, int) else (int(src.data_ptr()) if src.numel() else 0)
+        out = np.zeros(7, np.uint64)
+        _chk(self.lib.crass_hip_fastx_cut_probe_device(self.h, ptr or None, int(n_bytes), 1 if left_is_ls else 0, out.ctypes.data),
+             "crass_hip_fastx_cut_probe_device")
+        return out
+
+    def last_cut_probe_ms(self):
+        return float(self.lib.crass_hip_last_cut_probe_ms(self.h))
+
     def resident_fastx(self):
         """(device address, n_bytes) of the arena of the last load_fastx_files (crass_hip_resident_fastx); CrassError with
         status CRASS_ERR_STATE when the last load was not one.  The address goes where fetch_quality takes `src`; for
@@ -1519,6 +1598,45 @@ class SearchGroup:
         self._chk(self.lib.crass_hip_group_fetch_text(self.h, a.ctypes.data if len(a) else None, None if rc is None else rc.ctypes.data,
                                                       len(a), C.byref(v)), "crass_hip_group_fetch_text")
         return Text(v)
+
+    def load_fastx_files(self, files, pad_uniform=2, nominal=None):
+        """Several input files' bytes (plain FASTA / FASTQ or BGZF) cut into record-aligned shards, one per rank, each parsed on
+        its rank's device beside the others (crass_hip_group_load_fastx_files).  nominal: n - 1 non-decreasing positions in the
+        job's text space (None: even cuts).  Returns a FastxShards; raises FastxFilesDeclined (status 2, no rank holds reads)
+        when a file is declined, with the shards' decline fields in its `layout`."""
+        arrs, ptrs, lens = _files_args(files)
+        nom = _nominal_arg(nominal, self.n)
+        v = _abi.FastxShardsC()
+        st = self.lib.crass_hip_group_load_fastx_files(self.h, ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(pad_uniform),
+                                                       nom.ctypes.data if nom is not None and len(nom) else None, C.byref(v))
+        sh = FastxShards(v)
+        if st == 2 and not sh.accepted:
+            raise FastxFilesDeclined(st, "crass_hip_group_load_fastx_files", sh)
+        self._chk(st, "crass_hip_group_load_fastx_files")
+        return sh
+
+    def fetch_header_lines(self, idx):
+        """The header lines of the reads idx (GLOBAL read indices, any order) of the last load_fastx_files, from the ranks' arenas
+        (crass_hip_group_fetch_header_lines).  Returns (chars, off, name_len): numpy copies of the lines back to back, their
+        offsets (n + 1) and the length of the NAME at each line's start."""
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        nl = np.zeros(len(a), np.uint32)
+        v = _abi.Text()
+        self._chk(self.lib.crass_hip_group_fetch_header_lines(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(v),
+                                                              nl.ctypes.data if len(a) else None), "crass_hip_group_fetch_header_lines")
+        t = Text(v)
+        return t.chars.copy(), t.off.copy(), nl
+
+    def fetch_quality(self, idx):
+        """The quality strings of the reads idx (GLOBAL read indices) of the last load_fastx_files
+        (crass_hip_group_fetch_quality).  Returns (chars, off, has_qual) as SearchEngine.fetch_quality."""
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        has = np.zeros(len(a), np.uint8)
+        v = _abi.Text()
+        self._chk(self.lib.crass_hip_group_fetch_quality(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(v),
+                                                         has.ctypes.data if len(a) else None), "crass_hip_group_fetch_quality")
+        t = Text(v)
+        return t.chars.copy(), t.off.copy(), has
 
     def rank_counters(self, rank):
         c = _abi.Counters()

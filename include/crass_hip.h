@@ -907,6 +907,79 @@ int  crass_hip_fetch_quality_device_to(crass_hip_ctx *ctx, const uint8_t *d_byte
  * over the whole job.  Every global index is routed to the rank whose shard holds it; the records come back in the caller's
  * order in one crass_text owned by the group, valid until the next group fetch, load or destroy. */
 int crass_hip_group_fetch_text(crass_hip_group *g, const uint64_t *read_idx, const uint8_t *revcomp, uint64_t n, crass_text *out);
+/* ---- the files of a job cut into record-aligned shards, one per rank of a group ----
+ * replaces: nothing in crass, which reads its files in one thread; in this library it replaces the host's indexed reader
+ * + crass_hip_group_load_reads in front of a group, the way crass_hip_load_fastx_files replaces it in front of one context.
+ * The CUT RULE (csrc/fastx_scan.h states it once for host and device): the job's TEXT SPACE is the files' texts back to back in
+ * file order (a BGZF file's text is its inflated text), T bytes in all.  nominal (may be NULL: T g / n_ranks) holds n_ranks - 1
+ * non-decreasing positions in [0, T].  A record start is every file's position 0, every line start whose byte is '>' in a file
+ * whose byte 0 is '>', and every line start of line index 0 modulo 4 in a file whose byte 0 is '@'.  The actual cut c_g is the
+ * smallest record start at or after nominal cut g, or T; rank g owns [c_g, c_{g+1}) and may be empty.
+ * cut_file / cut_pos [n_ranks+1]: the file and the text position inside it of every actual cut ([n_ranks] = (n_files, 0));
+ * rank_read_base [n_ranks+1]: the records in front of every cut, rank g holds reads [rank_read_base[g], rank_read_base[g+1]);
+ * file_read_base [n_files+1] and format [n_files] as in crass_fastx_files_layout.  The decline fields are that layout's. */
+typedef struct {
+    uint32_t n_ranks, n_files;
+    int32_t  decline_file;                 /* -1 when accepted */
+    int32_t  decline_reason;
+    uint64_t decline_pos;
+    crass_bgzf_verdict bgzf;
+    uint64_t n_reads;
+    uint32_t max_len;
+    const uint64_t *rank_read_base;
+    const uint32_t *cut_file;
+    const uint64_t *cut_pos;
+    const uint64_t *file_read_base;
+    const int32_t  *format;
+} crass_fastx_shards;
+/* the shards on the host, no GPU needed: what the group's load is tested against.  Exact: the verdict is
+ * crass_fastx_files_scan_host's, field for field, whatever the cuts (the first offending file wins, inside it the smallest
+ * (line position, reason)); the cuts are the rule's.  The arrays are malloc'd (crass_fastx_shards_free), NULL when the input is
+ * declined (n_ranks, n_files and the decline fields are always filled).  Errors: CRASS_ERR_INVALID_ARG — as
+ * crass_fastx_files_scan_host, n_ranks outside 1..64, nominal cuts that decrease or lie beyond T; CRASS_ERR_UNSUPPORTED —
+ * declined; CRASS_ERR_OOM. */
+int  crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
+                                   const uint64_t *nominal, crass_fastx_shards *out);
+void crass_fastx_shards_free(crass_fastx_shards *s);
+/* what a rank knows about a byte range of one file's text before the cuts are known (the probe of csrc/fastx_scan.h), serially
+ * on the host and by k_fx_cut_probe on bytes in HBM (d_bytes: a DEVICE pointer of any alignment; one aligned 16-byte load per 16
+ * bytes, nothing outside the vectors that cover the range is read).  left_is_ls: position 0 of the range is a line start.
+ * out: [0] the '\n' bytes, [1] how many line starts follow (at most 4), [2..6) the first four line starts, [6] the first line
+ * start whose byte is '>'; positions count from the range's first byte, ~0 where there is none.  The two agree word for word.
+ * Errors: CRASS_ERR_INVALID_ARG — NULL pointers with n_bytes > 0, a NULL out or context; CRASS_ERR_HIP. */
+int  crass_fastx_cut_probe_host(const uint8_t *bytes, uint64_t n_bytes, int left_is_ls, uint64_t out[7]);
+int  crass_hip_fastx_cut_probe_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, int left_is_ls, uint64_t out[7]);
+/* HIP-event time, in milliseconds on the context's stream, of the last k_fx_cut_probe launch of that call; measured when the
+ * stage timing level is >= 1, else 0. */
+float crass_hip_last_cut_probe_ms(const crass_hip_ctx *ctx);
+/* the device call: every rank of the group parses its own shard of the files beside the others (the rank threads of
+ * crass_hip_group_load_reads).  Each rank stages the bytes of its NOMINAL range (plain bytes from the caller's memory; of a BGZF
+ * file the members that overlap the range, inflated by k_bgzf_inflate), probes them with k_fx_cut_probe, the host combines the
+ * probes into the actual cuts, each rank drops the head in front of its cut and adds the tail behind its nominal end (the few
+ * bytes up to the next rank's cut, or the further BGZF members), and then does on its slices what crass_hip_load_fastx_files does
+ * on whole files: k_fx_summary / k_fx_tile_scan / k_fx_emit per slice, one k_pack_text, header ids by k_hid_insert /
+ * k_hid_lookup, and a name table on its arena (crass_hip_fastx_names_build_device).  A file's bytes cross the bus once, apart
+ * from those tails.  Rank r's read_index_base is rank_read_base[r]; the exchange's row capacity comes from the largest shard.
+ * exact: out (may be NULL) equals crass_fastx_files_shards_host's, its arrays group-owned and valid until the next group load
+ *   or destroy; the reads, their text, header lines and quality (crass_hip_group_fetch_*) are those of crass_hip_load_fastx_files
+ *   on the same files.  A rank's packed layout (uniform or ragged) is its own; no result depends on it.
+ *   Names that repeat across ranks: after the merge of a step every rank looks the names of the other ranks' pass-1 records up
+ *   in its own table, and its namesakes are marked found before pass 2 (readsFound, libcrispr.cpp:138,411).
+ * declined (CRASS_ERR_UNSUPPORTED): the verdict of crass_fastx_files_shards_host in out; no rank holds reads, and the group is as
+ *   after a failed load (step: CRASS_ERR_STATE).  Plain gzip is declined (one deflate stream cannot be cut).
+ * Other errors: CRASS_ERR_INVALID_ARG — a NULL group, n_files == 0, NULL arrays, a NULL bytes[f] with n_bytes[f] > 0, pad_uniform
+ * outside 0..2, nominal cuts that decrease or lie beyond T; CRASS_ERR_HIP / CRASS_ERR_OOM from a rank. */
+int  crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files,
+                                      int pad_uniform, const uint64_t *nominal, crass_fastx_shards *out);
+/* replaces: ReadHolder's RH_Header / RH_Comment and RH_Qual / RH_IsFasta for a group loaded by crass_hip_group_load_fastx_files:
+ * crass_hip_fetch_header_lines_device / crass_hip_fetch_quality_device on every rank's arena, over the whole job.  read_idx are
+ * GLOBAL read indices (0 .. n_reads), routed to the rank that holds them; the records come back in the caller's order in one
+ * crass_text owned by the group (each call its own), valid until the next call of the same function, group load or destroy.
+ * name_len_out / has_qual_out (host [n], may be NULL) as in the single-context calls.  Errors: CRASS_ERR_STATE — the last group
+ * load was not a files load (or was declined); CRASS_ERR_INVALID_ARG — NULL group or result, NULL read_idx with n > 0, an index
+ * >= n_reads. */
+int  crass_hip_group_fetch_header_lines(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint32_t *name_len_out);
+int  crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_qual_out);
 /* the two decisions of the packers on their own, for callers and tests without a GPU: the layout crass_pack_reads and
  * crass_hip_load_text give a set (stride_words / uniform_len as in crass_reads), and the byte -> code function both use —
  * four sequence bytes (byte 0 first) -> their 2-bit codes in bits [2i, 2i+2), *bad bit i set when byte i is not A C G T

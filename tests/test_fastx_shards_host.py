@@ -1,0 +1,141 @@
+"""crass_fastx_files_shards_host — the cut rule of csrc/fastx_scan.h on the host, no GPU — against the brute-force statement of
+tests/shard_sets.py: every byte position of each designed file as the nominal cut, 1 .. 7 ranks with even cuts, the records in
+front of every cut against crass_fastx_files_scan_host's rec_pos, and the verdict of every declined input unchanged by any cut.
+The serial probe (crass_fastx_cut_probe_host) and the pick of a record start from it, against the same brute force."""
+import numpy as np
+import pytest
+
+from tests import files_sets, shard_sets
+
+
+@pytest.fixture(scope="module")
+def ca():
+    import crass_amd
+    from crass_amd import build
+    build.build()
+    crass_amd.load()
+    return crass_amd
+
+
+DESIGNED = {"fastq": [shard_sets.small_fastq()], "fasta": [shard_sets.small_fasta()],
+            "fasta_fastq": [shard_sets.small_fasta(), shard_sets.small_fastq()]}
+DESIGNED.update({k: v[0] for k, v in shard_sets.cases().items() if not k.startswith("tile_edge") or k == "tile_edge_4096"})
+
+
+def assert_rule(ca, files, n_ranks, nominal, what):
+    sh = ca.fastx_files_shards_host(files, n_ranks, nominal)
+    cuts, base = shard_sets.brute_shards(files, n_ranks, nominal)
+    assert sh.accepted and sh.n_ranks == n_ranks and sh.n_files == len(files), what
+    assert sh.cuts == cuts, (what, sh.cuts, cuts)
+    assert sh.rank_read_base.tolist() == base, (what, sh.rank_read_base, base)
+    return sh
+
+
+@pytest.mark.parametrize("name", sorted(DESIGNED))
+def test_every_byte_as_the_nominal_cut_and_one_to_seven_ranks(ca, name):
+    files = DESIGNED[name]
+    T = shard_sets.text_bases(files)[-1]
+    step = 1 if T < 2000 else 37                          # (the larger sets: every 37th byte and the designed positions)
+    for x in sorted(set(range(0, T + 1, step)) | {T}):
+        assert_rule(ca, files, 2, [x], (name, x))
+    for n in range(1, 8):
+        assert_rule(ca, files, n, None, (name, n))
+
+
+@pytest.mark.parametrize("name", sorted(shard_sets.cases()))
+def test_the_designed_positions(ca, name):
+    files, positions = shard_sets.cases()[name]
+    for n in (2, 3, 4):
+        for nominal in shard_sets.nominal_lists(files, positions, n):
+            assert_rule(ca, files, n, nominal, (name, n, nominal))
+
+
+@pytest.mark.parametrize("name", sorted(DESIGNED))
+def test_rank_read_base_counts_the_records_in_front_of_each_cut(ca, name):
+    files = DESIGNED[name]
+    lay = ca.fastx_files_scan_host(files)
+    assert lay.accepted
+    tb = shard_sets.text_bases(files)
+    # rec_pos are arena positions: a byte more per file in front
+    rec_text = [int(p) - int(np.searchsorted(lay.file_byte_base, p, side="right") - 1) for p in lay.rec_pos[:-1]]
+    for n in (2, 3, 5):
+        sh = ca.fastx_files_shards_host(files, n)
+        assert sh.n_reads == lay.n_reads and sh.max_len == lay.max_len and sh.formats == lay.formats
+        assert np.array_equal(sh.file_read_base, lay.file_read_base)
+        for g, (f, p) in enumerate(sh.cuts):
+            x = tb[f] + p if f < len(files) else tb[-1]
+            assert int(sh.rank_read_base[g]) == sum(1 for r in rec_text if r < x), (name, n, g)
+
+
+def test_the_designed_sets_are_what_they_say():
+    fq, fa = shard_sets.small_fastq(), shard_sets.small_fasta()
+    assert 150 < len(fq) < 300 and 150 < len(fa) < 300
+    assert b"\n@IIIIII\n" in fq and b"\n+IIIIIII\n" in fq            # quality lines that start with '@' and '+'
+    assert any(len(rec.split(b"\n")) > 3 for rec in fa.split(b">")[1:])      # multi-line records
+    cuts, base = shard_sets.brute_shards([b">short\nACGT\n>long\n" + b"A" * 500 + b"\n"], 4)
+    assert len(set(cuts)) < len(cuts)                                  # an empty rank
+
+
+DECLINED = dict({k: v for k, v in shard_sets.declined().items()},
+                **{k: (v[0], [None]) for k, v in files_sets.declined().items()})
+
+
+@pytest.mark.parametrize("name", sorted(DECLINED))
+def test_a_declined_input_keeps_its_verdict_for_every_cut(ca, name):
+    files, positions = DECLINED[name]
+    want = ca.fastx_files_scan_host(files)
+    assert not want.accepted
+    small = sum(len(f) for f in files) < 2000
+    T = sum(len(f) for f in files)
+    sweeps = [[x] for x in range(T + 1)] if small else []
+    for n, nominal in [(2, s) for s in sweeps] + [(n, None) for n in range(1, 8)]:
+        try:
+            sh = ca.fastx_files_shards_host(files, n, nominal)
+        except ca.CrassError as e:                                    # (a cut beyond the text of the files in front of the decline)
+            assert e.status == 1 and nominal is not None
+            continue
+        assert not sh.accepted and sh.verdict == want.verdict, (name, n, nominal, sh.verdict, want.verdict)
+        assert len(sh.rank_read_base) == 0 and len(sh.cut_pos) == 0
+    if name == "fastq_header_lacks_at_on_the_cut":
+        assert want.decline_reason == 4
+    if name == "incomplete_last_record":
+        assert want.decline_reason == 3 and want.decline_pos == files[0].rindex(b"@q5")
+    if name == "lone_header_at_the_end":
+        assert want.decline_reason == 10
+
+
+def test_the_serial_probe_and_the_pick(ca):
+    none = (1 << 64) - 1
+    for text in (shard_sets.small_fastq(), shard_sets.small_fasta()):
+        starts = shard_sets.record_starts(text)
+        for a in range(len(text)):
+            for b in sorted({a, a + 1, a + 17, len(text)}):
+                if b > len(text):
+                    continue
+                left = a == 0 or text[a - 1:a] == b"\n"
+                out = ca.fastx_cut_probe_host(text[a:b], left)
+                ls = [p - a for p in range(a, b) if p == 0 or text[p - 1:p] == b"\n"]
+                assert int(out[0]) == text[a:b].count(b"\n") and int(out[1]) == min(4, len(ls))
+                assert [int(v) for v in out[2:6]] == (ls + [none] * 4)[:4]
+                gt = [p for p in ls if text[a + p] == 0x3E]
+                assert int(out[6]) == (gt[0] if gt else none)
+                # the pick (fx_probe_pick, restated): FASTA the first '>' line start; FASTQ the first of the four whose index is 0 mod 4
+                if text[:1] == b">":
+                    pick = int(out[6])
+                else:
+                    first_idx = text[:a].count(b"\n") + (0 if left else 1)
+                    k = (-first_idx) % 4
+                    pick = int(out[2 + k]) if k < int(out[1]) else none
+                want = [s for s in starts if a <= s < b]
+                if pick != none or not want:
+                    assert pick == (want[0] - a if want else none), (a, b)
+                else:                                                 # (more than four line starts in front of it: never in a range that holds one)
+                    raise AssertionError((a, b, want))
+
+
+def test_invalid_arguments(ca):
+    fq = shard_sets.small_fastq()
+    for n, nominal in ((0, None), (65, None), (3, [10, 5]), (2, [len(fq) + 1])):
+        with pytest.raises((ca.CrassError, ValueError)) as e:
+            ca.fastx_files_shards_host([fq], n, nominal)
+        assert not isinstance(e.value, ca.CrassError) or e.value.status == 1

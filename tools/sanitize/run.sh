@@ -57,3 +57,8 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinc
 python3 tools/sanitize/gzip_members_dump.py $out/members > /dev/null
 $out/gzip_members_asan $out/members/* > $out/report_members.txt 2> $out/sanitizer_members.txt || true
 echo "gzip members: $(tail -1 $out/report_members.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_members.txt || true) sanitizer reports"
+# the record-aligned shards on the host (crass_fastx_files_shards_host, the serial probe) over the sets of tests/fastx_sets.py, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/shards_main.cpp -o $out/shards_asan
+python3 tools/sanitize/fastx_scan_dump.py $out/fastx > /dev/null
+$out/shards_asan $out/fastx/* > $out/report_shards.txt 2> $out/sanitizer_shards.txt || true
+echo "shards: $(tail -1 $out/report_shards.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_shards.txt || true) sanitizer reports"
