@@ -530,5 +530,8 @@ hipError_t launch_dr_dedupe(const char *dr, const uint16_t *dr_len, uint32_t str
 // with err == 6 and are redone with the uncapped layout)
 SurvLds survivor_lds_layout(uint32_t max_len, const DevParams &P, uint32_t row_len_cap = 0xFFFFFFFFu,
                             uint32_t seq_window_bytes = 0, uint32_t ss_entries_cap = 0);   // the two caps of the long-read layout (0: none)
+// the full layout of the last-resort launch: survivor_lds_layout(max_len, P) where that fits a CU's 160 KB, else the same
+// with rows for strings of max(highDR, highSp) bases — all the kernel ever compares (the argument stands at its definition)
+SurvLds survivor_lds_last_resort(uint32_t max_len, const DevParams &P);
 
 } // namespace crass

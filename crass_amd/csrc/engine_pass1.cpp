@@ -79,10 +79,16 @@ static int run_survivors(crass_hip_ctx *c, bool exc, uint64_t n_total, crass_hip
     if (n_total == 0) return hint_wait_all(c);
     // Long reads: the Levenshtein fallback rows are sized for 256-base strings (spacers are a few dozen bases), which
     // is what lets several waves share a CU's LDS; a read that needs longer rows comes back with err == 6 and is
-    // redone by a second launch with the uncapped layout.
-    const SurvLds lds_full = survivor_lds_layout(c->max_len, c->dp);
+    // redone by a second launch with the full layout.  That layout's own rows are sized by the set's longest read as long as
+    // it then fits a CU's 160 KB (reads up to ~28 kbp under the defaults) and by the longest string the QC can compare,
+    // max(highDR, highSp) bases, beyond that (survivor_lds_last_resort: every read the library loads, up to 60 000 bases,
+    // is searched); only options under which even that layout passes 160 KB (an extreme -S) are refused.  A read the full
+    // layout answers err 6 for is an error status of the scan (the sink's worst-error word), never a dropped read.
+    const SurvLds lds_full = survivor_lds_last_resort(c->max_len, c->dp);
     if (lds_full.total_bytes > 160 * 1024) return CRASS_ERR_UNSUPPORTED;
-    const uint32_t row_cap = c->env.row_cap;            // (tests: CRASS_ROW_CAP forces the second launch)
+    const bool rows_bounded = lds_full.row_elems < survivor_lds_layout(c->max_len, c->dp).row_elems;
+    // (tests: CRASS_ROW_CAP forces the second launch; no launch of a set asks for longer rows than its last resort has)
+    const uint32_t row_cap = rows_bounded ? std::min(c->env.row_cap, std::max(c->dp.highDR, c->dp.highSp)) : c->env.row_cap;
     // Reads beyond 2 048 bases also get an ASCII WINDOW instead of room for the whole read (the byte-wise consumers only ever
     // read around the repeats of the candidate in hand: rh_ascii) and a start/stop list of 256 entries: 11.5 instead of 19.7 KB
     // of LDS per wave at 10 kbp — three waves per SIMD (with 168 registers) instead of two.  An array longer than the window
@@ -324,7 +330,7 @@ static int run_survivors(crass_hip_ctx *c, bool exc, uint64_t n_total, crass_hip
 void presize_hostloop(crass_hip_ctx *c)
 {
     if (!c->R.pos_hint || c->max_len <= c->env.long_min || c->env.no_presize || c->R.n_reads == 0) return;
-    const SurvLds lds_full = survivor_lds_layout(c->max_len, c->dp);
+    const SurvLds lds_full = survivor_lds_last_resort(c->max_len, c->dp);      // (run_survivors' test: what it refuses is not sized)
     if (lds_full.total_bytes > 160 * 1024) return;
     for (auto &d : c->dma_sink) if (!d) d = sdma_create();      // (an engine's queue is created by its first copy, ~6 ms: here)
     const uint64_t chunk_cap = std::min<uint64_t>(c->R.n_reads, 1u << 20);

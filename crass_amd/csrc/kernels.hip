@@ -3454,6 +3454,26 @@ SurvLds survivor_lds_layout(uint32_t max_len, const DevParams &P, uint32_t row_l
     return l;
 }
 
+// The layout of the last-resort launch: whole-read ASCII copy, full start/stop list, packed words, hint words, and rows.
+// Rows sized by the set's longest read (max_len + 8 entries) pass a CU's 160 KB from ~28 000 bases on under the
+// defaults (5.85 bytes per base) and on their own from 40 953.  They never need the read's length.  rowA / rowB are used by
+// wave_similarity / wave_lev alone (row index <= the longer string's length), and those are reached
+//   - in search_core only behind `actual_repeat_length <= highDR`; qc_found_repeats' rep_len is ss[1] - ss[0] + 1 of the
+//     extended, clamped list, i.e. <= that length;
+//   - with three repeats and more, only behind `max_spacer_length <= maxSpacerLength` (the length tests stand in front of every
+//     edit distance), and the strings of the fallback loop are rep_len and two of those spacers;
+//   - with two repeats, only behind `sp_len <= maxSpacerLength`.
+// So `max(al, bl, rep_len) + 8 > row_cap` can only ever be asked for strings of at most max(highDR, highSp) bases, and rows of
+// that + 8 entries hold every string the kernel compares: 1.85 bytes per base under the defaults (111 KB at 60 000 bases).
+// A set that fits with rows of its longest read keeps that layout, byte for byte; the bound applies only where it does not.
+// The caller refuses what still exceeds 160 KB (L + 32 + 8 ss_cap + 4 rows + L/4 + L/8 bytes, ss_cap = 2 (L / (w + lowSp) + 4)).
+SurvLds survivor_lds_last_resort(uint32_t max_len, const DevParams &P)
+{
+    const SurvLds l = survivor_lds_layout(max_len, P);
+    if (l.total_bytes <= 160 * 1024) return l;
+    return survivor_lds_layout(max_len, P, std::max(P.highDR, P.highSp));
+}
+
 hipError_t launch_survivor(const DevReads &R, const DevParams &P, bool exceptions, const uint64_t *surv_idx,
                            const uint32_t *d_n_surv, uint64_t n_surv_max, SurvOut *out, char *dr_chars,
                            uint32_t dr_stride, uint32_t *ss_pool, uint32_t ss_pool_cap, uint32_t *d_ss_used,

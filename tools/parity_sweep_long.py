@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity sweep for LONG reads on the GPU box (the walking kernel, position hints, the host-loop sink): read sets of
-2-14 kbp with repeat arrays of varied length, spacing and mutation rate through the HIP path and the oracle, field by field
+2-60 kbp (the library's ceiling, CRASS_HIP_MAX_READ_LEN) with repeat arrays of varied length, spacing and mutation rate through the HIP path and the oracle, field by field
 (tests/parity.py).  Each case also draws the long-read switches that are read per call (hint slices, ASCII window, full layout);
 CRASS_SINK_EAGER / CRASS_HL_HOST_DEDUPE are read once per process: set them outside for a whole sweep.  Not part of the test
 suite:  python tools/parity_sweep_long.py [n_cases] [seed]"""
@@ -21,9 +21,10 @@ t_start = time.time()
 for case in range(n_cases):
     n = rng.choice([200, 600, 1500, 4500])
     lo = rng.choice([2049, 2100, 3000, 6000])
-    hi = rng.choice([lo + 1, 5000, 9000, 14000])
+    hi = rng.choice([lo + 1, 5000, 9000, 14000, 27992, 27993, 40953, 60000])     # (27 992 / 27 993: the last-resort layout's rows change their rule)
     if hi <= lo:
         hi = lo + 1
+    n = max(20, min(n, 12_000_000 // hi))                    # (a case stays a few seconds on the oracle)
     uniform = rng.random() < 0.25
     n_dr = rng.choice([1, 4, 12, 40])
     every = rng.choice([3, 10, 40])
