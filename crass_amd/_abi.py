@@ -209,6 +209,15 @@ SYMBOLS = {
     "crass_hip_fastx_names_build_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "crass_hip_fastx_names_find": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fastx_names_drop": (C.c_int, [C.c_void_p]),
+    "crass_fastx_names_of": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_fastx_names_of_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "crass_hip_found_names_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "crass_hip_fastx_names_find_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_hip_names_scan_tile": (C.c_uint32, []),
+    "crass_hip_recruit_found": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "crass_hip_group_set_name_exchange": (C.c_int, [C.c_void_p, C.c_int]),
+    "crass_hip_group_name_exchange_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "crass_hip_group_name_exchange_ms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "crass_hip_last_names_ms": (C.c_float, [C.c_void_p, C.c_int]),
     "crass_hip_fetch_header_lines_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_hip_fetch_header_lines_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -243,6 +243,14 @@ struct Ingest {
     bool have_names = false, nt_on_arena = false;
     const uint8_t *nt_bytes = nullptr; uint64_t nt_n_bytes = 0, nt_n_reads = 0, nt_mask = 0;
     DevBuf<uint8_t> nq_names; DevBuf<uint64_t> nq_off, nq_out; DevBuf<uint32_t> nq_long;
+    // crass_hip_fastx_names_find_device: the queries, offsets and answers are the caller's; the list of long queries (nq_long) and
+    // the two control words (long queries, a bad offset pair) are ours.  crass_hip_fastx_names_of_device / crass_hip_found_names_device:
+    // the lengths, the tile sums, the flag word, the record numbers of a step without a dense blob and the offsets of a caller
+    // who gave too few words for them — all given back before the call returns; the pinned words the host reads (find: the two
+    // control words; names of: the total, then the flag)
+    DevBuf<uint32_t> nq_ctl, no_len, no_flag; DevBuf<uint64_t> no_tiles, no_idx, no_off;
+    PinBuf<uint64_t> nq_h_ctl, no_h;
+    uint64_t last_find_found = 0;            // answers of the last crass_hip_fastx_names_find_device that named a record
     StageTimer<2> tm_find;
     float last_names_ms[2] = {0, 0};         // the last build's insert launches, the last find's kernels
     LineFetch hl, ql;                        // header lines, quality strings
@@ -375,6 +383,7 @@ struct crass_hip_ctx {
     bool hints_valid = false;       // d_hit_info doubles as the pass-1 seed-hint array (pass 2 reuses it afterwards)
     DevBuf<SurvOut> d_surv; DevBuf<char> d_dr; DevBuf<uint32_t> d_ss_pool; DevBuf<uint32_t> d_ss_used;
     DevBuf<RecruitOut> d_rec; DevBuf<uint32_t> d_exc_hit; DevBuf<uint64_t> d_extra;
+    DevBuf<uint32_t> d_extra_bad; PinBuf<uint32_t> h_extra_bad;      // crass_hip_recruit_found: the word k_mark_found_skip sets for an entry out of range
     PinBuf<uint32_t> h_count; PinBuf<SurvOut> h_surv; PinBuf<char> h_dr; PinBuf<uint32_t> h_ss; PinBuf<uint64_t> h_idx;
     DevBuf<SurvOut> g_surv; DevBuf<char> g_dr; DevBuf<uint32_t> g_ss;       // host-loop sink: the found records, dense
     PinBuf<RecruitOut> h_rec;

@@ -77,7 +77,14 @@ static void release_names_find(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
     wait_main(c);
-    I.nq_names.release(); I.nq_off.release(); I.nq_out.release(); I.nq_long.release();
+    I.nq_names.release(); I.nq_off.release(); I.nq_out.release(); I.nq_long.release(); I.nq_ctl.release();
+}
+
+static void release_names_of(crass_hip_ctx *c)
+{
+    Ingest &I = c->in;
+    wait_main(c);
+    I.no_len.release(); I.no_flag.release(); I.no_tiles.release(); I.no_idx.release(); I.no_off.release();
 }
 
 static void release_lines(crass_hip_ctx *c, LineFetch &B) { wait_main(c); B.release_device(); }
@@ -94,14 +101,14 @@ static void release_shard(crass_hip_ctx *c)
 void ingest_free_all(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
-    release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c);
+    release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c); release_names_of(c);
     names_drop(c); drop_arena(c);
     release_shard(c); I.sh_h_part.release(); I.tm_probe.destroy();
     I.hl.free_all(); I.ql.free_all();
     // what is kept from call to call, and the pinned sides of the results
     I.f_idx.release(); I.f_off.release(); I.f_rc.release(); I.f_chars.release();
     I.f_h_idx.release(); I.f_h_off.release(); I.f_h_rc.release(); I.f_h_chars.release();
-    I.x_h_tot.release(); I.x_h_rec_pos.release(); I.x_h_seq_off.release(); I.z_h_verdict.release(); I.n_h_ctl.release();
+    I.x_h_tot.release(); I.x_h_rec_pos.release(); I.x_h_seq_off.release(); I.z_h_verdict.release(); I.n_h_ctl.release(); I.nq_h_ctl.release(); I.no_h.release();
     I.fa_h_base.release(); I.fa_h_format.release();
     for (hipEvent_t *e : {&I.ev_t_copy[0], &I.ev_t_copy[1], &I.ev_t_pack[0], &I.ev_t_pack[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     I.tm_pack.destroy(); I.tm_scan.destroy(); I.tm_inflate.destroy(); I.tm_gzip.destroy(); I.tm_fetch.destroy(); I.tm_names.destroy(); I.tm_find.destroy();
@@ -1100,6 +1107,138 @@ int crass_hip_fastx_names_find(crass_hip_ctx *c, const uint8_t *names, const uin
     return s;
 }
 
+// ---- the same exchange with everything in device memory: names out (k_nm_*), names looked up (k_hid_find_dev) ----
+// The host reads counts only: the total and the flag word of a names-of call, the two control words of a find.
+static int names_find_device_impl(crass_hip_ctx *c, const uint8_t *d_names, uint64_t n_name_bytes, const uint64_t *d_name_off, uint64_t n_names,
+                                  uint64_t *d_first_out)
+{
+    Ingest &I = c->in;
+    HIPCHK(c, I.nq_long.ensure(n_names)); HIPCHK(c, I.nq_ctl.ensure(4)); HIPCHK(c, I.nq_h_ctl.ensure(2));      // (words 2 and 3: the 64-bit count of answers that name a record)
+    HidFindJob J{};
+    J.bytes = I.nt_bytes; J.n_bytes = I.nt_n_bytes; J.rec_pos = I.nt_rec_pos.p;
+    J.table = I.nt_table.p; J.mask = I.nt_mask; J.hash_bits = c->env.hid_hash_bits;
+    J.names = d_names; J.name_off = d_name_off; J.n_names = n_names; J.long_list = I.nq_long.p; J.first_out = d_first_out;
+    HidFindDev D{};
+    D.n_name_bytes = n_name_bytes; D.long_app = I.nq_long.p; D.ctl = I.nq_ctl.p;
+    HIPCHK(c, hipMemsetAsync(I.nq_ctl.p, 0, 16, c->stream));
+    HIPCHK(c, I.tm_find.begin(c->timing_level >= 1, c->stream));
+    HIPCHK(c, launch_hid_find_dev(J, D, c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.nq_h_ctl.p, I.nq_ctl.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (how many long queries there are sizes the wave kernel's launch)
+    const uint32_t *h_ctl = reinterpret_cast<const uint32_t *>(I.nq_h_ctl.p);
+    const uint32_t n_long = h_ctl[0], bad = h_ctl[1];
+    if (n_long > n_names) return CRASS_ERR_STATE;       // (never expected: a lane appends at most once)
+    if (n_long) HIPCHK(c, launch_hid_find_long(J, n_long, c->stream));
+    HIPCHK(c, launch_hid_count_found(d_first_out, n_names, reinterpret_cast<unsigned long long *>(I.nq_ctl.p + 2), c->stream));
+    HIPCHK(c, I.tm_find.mark(c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.nq_h_ctl.p + 1, I.nq_ctl.p + 2, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, I.tm_find.elapsed(0, 1, &I.last_names_ms[1]));
+    I.last_find_found = I.nq_h_ctl.p[1];
+    return bad ? CRASS_ERR_INVALID_ARG : CRASS_OK;
+}
+
+int crass_hip_fastx_names_find_device(crass_hip_ctx *c, const uint8_t *d_names, uint64_t n_name_bytes, const uint64_t *d_name_off, uint64_t n_names,
+                                      uint64_t *d_first_out)
+{
+    if (!c || (n_names && (!d_name_off || !d_first_out)) || (n_name_bytes && !d_names)) return CRASS_ERR_INVALID_ARG;
+    if (n_names >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (the list of long queries holds 32-bit indices)
+    if (!c->in.have_names) return CRASS_ERR_STATE;
+    c->in.last_names_ms[1] = 0; c->in.last_find_found = 0;
+    if (n_names == 0) return CRASS_OK;
+    (void)hipSetDevice(c->device);
+    if (c->in.nt_n_reads == 0) {                        // a table of no records: every query is CRASS_NAME_NOT_FOUND (all bits set)
+        HIPCHK(c, hipMemsetAsync(d_first_out, 0xFF, n_names * 8, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return CRASS_OK;
+    }
+    const int s = names_find_device_impl(c, d_names, n_name_bytes, d_name_off, n_names, d_first_out);
+    release_names_find(c);                              // the scratch goes back on every way out; the table stays
+    return s;
+}
+
+static int names_of_device_impl(crass_hip_ctx *c, const uint64_t *d_idx, uint64_t n, uint64_t idx_base, uint8_t *d_chars, uint64_t cap_bytes,
+                                uint64_t *d_off, uint64_t *total_out)
+{
+    Ingest &I = c->in;
+    const uint64_t tiles = (n + nm_scan_tile() - 1) / nm_scan_tile();
+    HIPCHK(c, I.no_len.ensure(n)); HIPCHK(c, I.no_flag.ensure(1)); HIPCHK(c, I.no_tiles.ensure(tiles + 1)); HIPCHK(c, I.no_h.ensure(2));
+    NmOfJob J{};
+    J.bytes = I.nt_bytes; J.n_bytes = I.nt_n_bytes; J.rec_pos = I.nt_rec_pos.p; J.n_reads = I.nt_n_reads;
+    J.idx = d_idx; J.n = n; J.idx_base = idx_base;
+    J.len = I.no_len.p; J.flag = I.no_flag.p; J.tile_sum = I.no_tiles.p; J.off = d_off; J.out = d_chars;
+    HIPCHK(c, hipMemsetAsync(I.no_flag.p, 0, 4, c->stream));
+    I.no_h.p[1] = 0;
+    HIPCHK(c, launch_nm_measure_idx(J, c->stream));
+    HIPCHK(c, launch_nm_scan(J, c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.no_h.p, d_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.no_h.p + 1, I.no_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (the total sizes the copy launch and is the caller's one host read)
+    const uint64_t total = I.no_h.p[0];
+    if (total_out) *total_out = total;
+    if (I.no_h.p[1]) return CRASS_ERR_INVALID_ARG;      // an entry outside [0, n_reads): no byte is written
+    J.limit = std::min(total, cap_bytes);
+    if (J.limit) {
+        HIPCHK(c, launch_nm_copy(J, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return total > cap_bytes ? CRASS_ERR_OVERFLOW : CRASS_OK;
+}
+
+int crass_hip_fastx_names_of_device(crass_hip_ctx *c, const uint64_t *d_idx, uint64_t n, uint64_t idx_base, uint8_t *d_chars, uint64_t cap_bytes,
+                                    uint64_t *d_off, uint64_t *total_out)
+{
+    if (!c || !d_off || (n && !d_idx) || (cap_bytes && !d_chars)) return CRASS_ERR_INVALID_ARG;
+    if (n >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    if (!c->in.have_names) return CRASS_ERR_STATE;
+    if (total_out) *total_out = 0;
+    (void)hipSetDevice(c->device);
+    if (n == 0) {
+        HIPCHK(c, hipMemsetAsync(d_off, 0, 8, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return CRASS_OK;
+    }
+    const int s = names_of_device_impl(c, d_idx, n, idx_base, d_chars, cap_bytes, d_off, total_out);
+    release_names_of(c);                                // the scratch goes back on every way out
+    return s;
+}
+
+int crass_hip_found_names_device(crass_hip_ctx *c, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *d_off, uint64_t cap_names, uint64_t *n_out,
+                                 uint64_t *total_out)
+{
+    if (!c || !n_out || (cap_bytes && !d_chars) || (cap_names && !d_off)) return CRASS_ERR_INVALID_ARG;
+    *n_out = 0;
+    if (total_out) *total_out = 0;
+    if (!c->in.have_names) return CRASS_ERR_STATE;
+    if (c->p1d.active) { const int ds = settle_p1(c); if (ds) return ds; }
+    if (!c->have_pass1) return CRASS_ERR_STATE;
+    (void)hipSetDevice(c->device);
+    const uint64_t n = c->n_cand();
+    *n_out = n;
+    if (n >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    if (n == 0) {
+        if (d_off) { HIPCHK(c, hipMemsetAsync(d_off, 0, 8, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+        return CRASS_OK;
+    }
+    // too few offset words: the names are measured into scratch of ours, so that the caller learns n and the total at once
+    const bool short_off = cap_names < n;
+    if (short_off) { HIPCHK(c, c->in.no_off.ensure(n + 1)); d_off = c->in.no_off.p; cap_bytes = 0; }
+    const uint64_t *d_idx;
+    if (c->dense.active) d_idx = reinterpret_cast<const uint64_t *>(c->dense.d_blob.p + c->dense.lay.read);      // pass 1's records, where the gather kernel left them
+    else {                                              // the host-loop sink (long reads): its list is the one host array this route sends
+        crass_candidates cd;
+        if (const int gs = crass_hip_get_candidates(c, &cd)) return gs;
+        HIPCHK(c, c->in.no_idx.ensure(n));
+        HIPCHK(c, hipMemcpyAsync(c->in.no_idx.p, cd.read_idx, n * 8, hipMemcpyHostToDevice, c->stream));
+        d_idx = c->in.no_idx.p;
+    }
+    const int s = names_of_device_impl(c, d_idx, n, c->read_base, d_chars, cap_bytes, d_off, total_out);
+    release_names_of(c);
+    return (short_off && s == CRASS_OK) ? CRASS_ERR_OVERFLOW : s;
+}
+
+uint32_t crass_hip_names_scan_tile(void) { return nm_scan_tile(); }
+
 int crass_hip_fastx_names_drop(crass_hip_ctx *c)
 {
     if (!c) return CRASS_ERR_INVALID_ARG;
@@ -1776,3 +1915,4 @@ int shard_records(const crass_hip_ctx *c, const uint8_t **arena, uint64_t *n_byt
     *arena = c->in.fa_arena.p; *n_bytes = c->in.fa_bytes; *rec_pos = c->in.x_h_rec_pos.p; *n_reads = c->R.n_reads;
     return CRASS_OK;
 }
+uint64_t names_find_device_found(const crass_hip_ctx *c) { return c ? c->in.last_find_found : 0; }

@@ -440,6 +440,10 @@ hipError_t launch_levenshtein_batch(const uint8_t *chars, const uint64_t *a_off,
                                     int32_t *dist, float *sim, uint32_t max_len, hipStream_t st);
 // found_flag[header_id(idx[i])] = 1 for every listed read (readsFound entries of other input files, libcrispr.cpp:411)
 hipError_t launch_mark_found(const uint64_t *idx, uint64_t n, const uint64_t *header_id, uint8_t *found_flag, hipStream_t st);
+// the same over a device list that may hold CRASS_NAME_NOT_FOUND (skipped); another entry >= n_reads marks nothing and sets *bad;
+// found_flag == nullptr only checks
+hipError_t launch_mark_found_skip(const uint64_t *idx, uint64_t n, uint64_t n_reads, const uint64_t *header_id, uint8_t *found_flag, uint32_t *bad,
+                                  hipStream_t st);
 hipError_t launch_copy_to_host(const void *d_src, void *h_dst, uint64_t bytes, hipStream_t st);   // pinned destination, few workgroups
 // device -> pinned host on the DMA engines (sdma.cpp); nullptr / false: not available, use the copy kernel
 struct SdmaCopy;

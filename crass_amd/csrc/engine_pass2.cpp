@@ -20,10 +20,14 @@ int crass_hip_set_patterns(crass_hip_ctx *c, const char *const *patterns, const 
 // pass 2
 // ------------------------------------------------------------------------------------------
 // the device merge gave up (or its results do not add up): host merge, then pass 2 again
-static int recruit_after_host_merge(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_extra)
+// (the two lists of found reads a recruit call was given, the host's and the device's: every repeat carries both along)
+struct ExtraFound { const uint64_t *host; uint64_t n_host; const uint64_t *dev; uint64_t n_dev; };
+static int recruit_impl(crass_hip_ctx *c, const ExtraFound &x);
+
+static int recruit_after_host_merge(crass_hip_ctx *c, const ExtraFound &x)
 {
     if (const int fs = host_merge_fallback(c)) return fs;
-    return crass_hip_recruit(c, extra_found, n_extra);
+    return recruit_impl(c, x);
 }
 
 // additional found headers (local read indices, e.g. every header another input file found): one upload, one kernel
@@ -34,6 +38,21 @@ static int mark_extra_found(crass_hip_ctx *c, const uint64_t *extra_found, uint6
     HIPCHK(c, hipMemcpyAsync(c->d_extra.p, extra_found, n_extra * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_mark_found(c->d_extra.p, n_extra, c->R.header_id, c->d_found.p, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));        // (the caller's array may go away)
+    return CRASS_OK;
+}
+
+// the same for a list that lies in device memory and may hold CRASS_NAME_NOT_FOUND (the answers of
+// crass_hip_fastx_names_find_device as they are): nothing is uploaded.  Two launches of k_mark_found_skip: the first only
+// checks, so that a list with an entry out of range marks nothing; the host reads the one word between them
+static int mark_extra_found_device(crass_hip_ctx *c, const uint64_t *d_extra_found, uint64_t n_d_extra)
+{
+    HIPCHK(c, c->d_extra_bad.ensure(1)); HIPCHK(c, c->h_extra_bad.ensure(1));
+    HIPCHK(c, hipMemsetAsync(c->d_extra_bad.p, 0, 4, c->stream));
+    HIPCHK(c, launch_mark_found_skip(d_extra_found, n_d_extra, c->R.n_reads, c->R.header_id, nullptr, c->d_extra_bad.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_extra_bad.p, c->d_extra_bad.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (*c->h_extra_bad.p) return CRASS_ERR_INVALID_ARG;
+    HIPCHK(c, launch_mark_found_skip(d_extra_found, n_d_extra, c->R.n_reads, c->R.header_id, c->d_found.p, c->d_extra_bad.p, c->stream));
     return CRASS_OK;
 }
 
@@ -67,7 +86,7 @@ static int launch_probe(crass_hip_ctx *c, bool dmp, uint64_t n_exc, bool &anchor
 
 // device merge path: the sink runs on the device too (drop the slots without a match, pack the records in
 // read order) and ONE copy brings the hand-off arrays to pinned host memory
-static int recruit_device_sink(crass_hip_ctx *c, bool spec, uint64_t n_hits, const uint64_t *extra_found, uint64_t n_extra)
+static int recruit_device_sink(crass_hip_ctx *c, bool spec, uint64_t n_hits, const ExtraFound &x)
 {
     static const bool blob12 = getenv("CRASS_P2_BLOB12") != nullptr;      // A/B switch: the 12-byte form of round 3
     // (the 9-byte form needs the token strings when the records are widened: a context whose host view is the light one —
@@ -89,19 +108,19 @@ static int recruit_device_sink(crass_hip_ctx *c, bool spec, uint64_t n_hits, con
                 1e3 * (th0 - c->t_p1_sync), 1e3 * (now_ms() - th0));
     if (hs == CRASS_ERR_STATE) {                    // inconsistent device results: never expected
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        return recruit_after_host_merge(c, extra_found, n_extra);
+        return recruit_after_host_merge(c, x);
     }
     if (hs) return hs;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->env.merge_profile)
         fprintf(stderr, "[crass_dm] recruit: final synchronisation returned %.1f us after the pass-1 sync\n", 1e3 * (now_ms() - c->t_p1_sync));
     if (spec) {
-        if (c->dm.h_st.p->fail) return recruit_after_host_merge(c, extra_found, n_extra);
+        if (c->dm.h_st.p->fail) return recruit_after_host_merge(c, x);
         if (c->h_count.p[0] > n_hits) {             // bound too small: repeat with the exact count
             c->n_bound_overflows[2]++;
             c->hit_cap_hint = 0;
             c->recruit_exact = true;
-            return crass_hip_recruit(c, extra_found, n_extra);
+            return recruit_impl(c, x);
         }
     }
     c->hit_cap_hint = hit_bound(c->h_count.p[0]);
@@ -173,9 +192,8 @@ static int recruit_host_sink(crass_hip_ctx *c, uint64_t n_hits, uint64_t n_exc, 
     return c->lookback_ok();
 }
 
-int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_extra)
+static int recruit_impl(crass_hip_ctx *c, const ExtraFound &x)
 {
-    if (!c) return CRASS_ERR_INVALID_ARG;
     if (!c->have_reads) return CRASS_ERR_STATE;
     (void)hipSetDevice(c->device);
     if (c->p1d.active) { const int ds = settle_p1(c); if (ds) return ds; }
@@ -191,7 +209,8 @@ int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_
     if (!c->have_patterns) return CRASS_ERR_STATE;
     const uint64_t n = c->R.n_reads;
     const uint64_t n_words = (n + 63) / 64;
-    if (n_extra) { const int ms = mark_extra_found(c, extra_found, n_extra); if (ms) return ms; }
+    if (x.n_host) { const int ms = mark_extra_found(c, x.host, x.n_host); if (ms) return ms; }
+    if (x.n_dev) { const int ms = mark_extra_found_device(c, x.dev, x.n_dev); if (ms) return ms; }
     HIPCHK(c, c->stamp(5, 1));
     const bool dmp = c->dm.active;                  // pattern set built on the device (dmerge.hip)
     // exception reads: with a device-built (pure ACGT) pattern set they go through the anchor filter and the exact
@@ -211,7 +230,7 @@ int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_
     c->recruit_exact = false;
     // (speculative: the count reaches the host with the last kernel of the tail, k_pack_p2_blob)
     if (!spec) { const int rs = read_count(c); if (rs) return rs; }
-    if (!spec && dmp && c->dm.h_st.p->fail) return recruit_after_host_merge(c, extra_found, n_extra);
+    if (!spec && dmp && c->dm.h_st.p->fail) return recruit_after_host_merge(c, x);
     const uint64_t n_hits = spec ? c->hit_cap_hint : c->h_count.p[0];
     // (sized for the bound the next call will speculate with, so that it does not re-allocate)
     const uint64_t h_alloc = spec ? n_hits : std::max<uint64_t>(n_hits, hit_bound(n_hits));
@@ -228,8 +247,20 @@ int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_
         HIPCHK(c, launch_recruit_finish(c->R, nullptr, nullptr, n_exc, c->d_exc_hit.p, true, true, nullptr, nullptr, c->d_rec.p + n_hits,
                                         c->d_dr.p + n_hits * c->dr_stride, c->dr_stride, c->stream));
     HIPCHK(c, c->stamp(7, 2));
-    if (dmp) return recruit_device_sink(c, spec, n_hits, extra_found, n_extra);
+    if (dmp) return recruit_device_sink(c, spec, n_hits, x);
     return recruit_host_sink(c, n_hits, n_exc, anchors, lds);
+}
+
+int crass_hip_recruit(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_extra)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    return recruit_impl(c, ExtraFound{extra_found, n_extra, nullptr, 0});
+}
+
+int crass_hip_recruit_found(crass_hip_ctx *c, const uint64_t *extra_found, uint64_t n_extra, const uint64_t *d_extra_found, uint64_t n_d_extra)
+{
+    if (!c || (n_d_extra && !d_extra_found)) return CRASS_ERR_INVALID_ARG;
+    return recruit_impl(c, ExtraFound{extra_found, n_extra, d_extra_found, n_d_extra});
 }
 
 int crass_hip_get_recruits(const crass_hip_ctx *c, crass_recruits *o)

@@ -25,6 +25,10 @@
 //                      same tag: the query against the slot owner's name, lengths included; equal: the slot's index.  The table is
 //                      final and only read: no atomics, no waiting, and a probe that has seen every slot ends with not found.
 //   k_hid_find_long    a wave per query of kHidLaneEnd bytes or more, hashed as k_hid_insert_long hashes (hid_hash_wave).
+//   k_hid_find_dev     k_hid_find for queries made on the device (another rank's names): it checks the offsets nobody on the host
+//                      has seen and lists the long queries itself, one add per wave; k_hid_find_long then runs over that list.
+//   k_nm_measure_idx / k_nm_scan_tiles, _top, _apply / k_nm_copy   the names of listed records of the kept table, back to back in
+//                      device memory with their offsets: lengths, a three-launch prefix sum, a lane per output byte.
 // No answer rests on a hash: hash_bits (CRASS_HID_TEST_HASH_BITS) cuts the hash to its low bits, down to none, for the tests.
 // Slot accesses are agent-scope atomics; the name bytes and rec_pos are read-only input.
 //
@@ -359,6 +363,168 @@ __global__ __launch_bounds__(kNmThreads) void k_hid_find_long(const HidFindJob J
     if (lane == 0) J.first_out[k] = found;
 }
 
+// k_hid_find for queries that were made on the device (crass_hip_fastx_names_find_device): nobody has seen their offsets, so the
+// lane checks its pair — a decreasing pair or an end beyond n_name_bytes sets ctl[1], and that query reads nothing — and the
+// queries of kHidLaneEnd bytes or more are listed here for k_hid_find_long: one add per wave (the ballot's first lane), every
+// long lane stores behind the wave's base by its rank in the ballot.  The list's order depends on scheduling, no answer does.
+__global__ __launch_bounds__(kNmThreads) void k_hid_find_dev(const HidFindJob J, const HidFindDev D)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool in = k < J.n_names;
+    uint64_t qa = 0, qlen = 0;
+    bool bad = false;
+    if (in) {
+        const uint64_t qb = J.name_off[k + 1];
+        qa = J.name_off[k];
+        bad = qb < qa || qb > D.n_name_bytes;
+        qlen = bad ? 0 : qb - qa;
+    }
+    const bool is_long = in && qlen >= kHidLaneEnd;
+    const unsigned long long m = __ballot(is_long);     // (no lane has left: the wave's 64 queries)
+    if (m) {
+        const int first = __builtin_ctzll(m);
+        uint32_t base = 0;
+        if (lane == (uint32_t)first) base = atomicAdd(&D.ctl[0], (uint32_t)__builtin_popcountll(m));
+        base = (uint32_t)__shfl((int)base, first);
+        if (is_long) D.long_app[base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (uint32_t)k;
+    }
+    if (!in || is_long) return;
+    uint64_t h, found = kHidNotFound;
+    uint32_t len;
+    if (bad) D.ctl[1] = 1u;
+    else {
+        const uintptr_t qlo = (uintptr_t)J.names + qa, qhi = qlo + qlen;
+        if (hid_hash_lane(qlo, qhi, 0, &h, &len) && len == qlen) found = hid_probe_lane(J, qlo, qhi, nm_cut(h, J.hash_bits));
+    }
+    J.first_out[k] = found;
+}
+
+// how many answers name a record: the one figure of them the host learns (one add per wave)
+__global__ __launch_bounds__(kNmThreads) void k_hid_count_found(const uint64_t *first, const uint64_t n, unsigned long long *count)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    const unsigned long long m = __ballot(k < n && first[k] != kHidNotFound);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(count, (unsigned long long)__builtin_popcountll(m));
+}
+
+// ---- the names of listed records of a built table, back to back in device memory (crass_hip_fastx_names_of_device) ----
+// k_nm_measure_idx: a lane per entry walks its record's name (nm_name_bytes, the rule of k_hl_measure).  The prefix sum of the
+// lengths stays on the device, in three launches and without any block waiting for another: k_nm_scan_tiles sums kNmTile
+// lengths per block, k_nm_scan_top turns the tile sums into the bytes in front of every tile (one block, 256 tiles a step, the
+// total behind the last), k_nm_scan_apply writes every entry's offset and off[n].  k_nm_copy is k_hl_copy with the offsets and
+// the records' numbers read from the device.
+static constexpr uint32_t kNmTileItems = 4;                             // lengths per lane
+static constexpr uint32_t kNmTile = kNmThreads * kNmTileItems;          // ... per block
+
+__global__ __launch_bounds__(kNmThreads) void k_nm_measure_idx(const NmOfJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uint64_t g = J.idx[k];
+    if (g < J.idx_base || g - J.idx_base >= J.n_reads) { *J.flag = 1u; J.len[k] = 0u; return; }
+    const uintptr_t lo = (uintptr_t)J.bytes;
+    NmCur c;
+    c.init(lo, lo + J.n_bytes, J.rec_pos[g - J.idx_base] + 1);      // (rec_pos < n_bytes: the insert saw every one)
+    uint64_t name = 0;
+    for (;;) {
+        uint32_t avail;
+        const uint32_t w = c.next(&avail);
+        const uint32_t nb = nm_name_bytes(w, avail);
+        name += nb;
+        if (nb < 4) break;
+    }
+    J.len[k] = name > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)name;
+}
+
+// the block's sum of v, in every lane (sh: one word per wave)
+static __device__ __forceinline__ uint64_t nm_block_sum64(uint64_t v, uint64_t *sh)
+{
+    v = nm_wave_sum64(v);
+    __syncthreads();                                    // (sh may still be read from the step before)
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t s = 0;
+#pragma unroll
+    for (int w = 0; w < kNmThreads / 64; w++) s += sh[w];
+    return s;
+}
+// what the lanes in front of this one hold in v, summed (the exclusive prefix over the block); *total: the block's sum
+static __device__ __forceinline__ uint64_t nm_block_prefix64(uint64_t v, uint64_t *sh, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t a = (uint32_t)__shfl_up((int)(uint32_t)inc, s), b = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), s);
+        if (lane >= (uint32_t)s) inc += ((uint64_t)b << 32) | a;
+    }
+    __syncthreads();
+    if (lane == 63u) sh[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kNmThreads / 64; w++) { const uint64_t s = sh[w]; if (w < wave) before += s; all += s; }
+    *total = all;
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_nm_scan_tiles(const NmOfJob J)
+{
+    __shared__ uint64_t sh[kNmThreads / 64];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kNmTile + (uint64_t)threadIdx.x * kNmTileItems;
+    uint64_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kNmTileItems; j++) if (k0 + j < J.n) v += J.len[k0 + j];
+    const uint64_t s = nm_block_sum64(v, sh);
+    if (threadIdx.x == 0) J.tile_sum[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_nm_scan_top(const NmOfJob J, const uint64_t n_tiles)
+{
+    __shared__ uint64_t sh[kNmThreads / 64];
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < n_tiles; t0 += kNmThreads) {      // (the same trip count in every lane)
+        const uint64_t t = t0 + threadIdx.x;
+        const uint64_t v = t < n_tiles ? J.tile_sum[t] : 0;
+        uint64_t total;
+        const uint64_t before = nm_block_prefix64(v, sh, &total);
+        if (t < n_tiles) J.tile_sum[t] = carry + before;
+        carry += total;
+    }
+    if (threadIdx.x == 0) J.tile_sum[n_tiles] = carry;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_nm_scan_apply(const NmOfJob J, const uint64_t n_tiles)
+{
+    __shared__ uint64_t sh[kNmThreads / 64];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kNmTile + (uint64_t)threadIdx.x * kNmTileItems;
+    uint32_t l[kNmTileItems];
+    uint64_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kNmTileItems; j++) { l[j] = k0 + j < J.n ? J.len[k0 + j] : 0u; v += l[j]; }
+    uint64_t total;
+    uint64_t at = J.tile_sum[blockIdx.x] + nm_block_prefix64(v, sh, &total);
+#pragma unroll
+    for (uint32_t j = 0; j < kNmTileItems; j++) { if (k0 + j < J.n) J.off[k0 + j] = at; at += l[j]; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) J.off[J.n] = J.tile_sum[n_tiles];
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_nm_copy(const NmOfJob J)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (i >= J.limit) return;
+    uint64_t a = 0, b = J.n - 1;                        // the last entry whose offset is <= i, as in k_hl_copy
+    while (a < b) {
+        const uint64_t mid = (a + b + 1) >> 1;
+        if (J.off[mid] <= i) a = mid; else b = mid - 1;
+    }
+    const uint64_t r = J.idx[a] - J.idx_base;           // (an entry out of range has no byte: the bisection never ends on one ...)
+    if (r >= J.n_reads) return;                         // (... and this keeps a wrong offset array from reading rec_pos out of bounds)
+    const uint64_t p = J.rec_pos[r] + 1 + (i - J.off[a]);
+    if (p < J.n_bytes) J.out[i] = J.bytes[p];
+}
+
 __global__ __launch_bounds__(kNmThreads) void k_hl_measure(const HlJob J)
 {
     const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
@@ -488,6 +654,50 @@ hipError_t launch_hid_find_long(const HidFindJob &J, uint32_t n_long, hipStream_
     unsigned g;
     if (!nm_grid(n_long, kNmThreads / 64, &g) || n_long > J.n_names || (J.mask & (J.mask + 1))) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_hid_find_long, dim3(g), dim3(kNmThreads), 0, st, J, n_long);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_find_dev(const HidFindJob &J, const HidFindDev &D, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n_names, kNmThreads, &g) || J.n_names >= 0xFFFFFFFFull || (J.mask & (J.mask + 1)) || !D.long_app || !D.ctl) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_find_dev, dim3(g), dim3(kNmThreads), 0, st, J, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_hid_count_found(const uint64_t *first, uint64_t n, unsigned long long *count, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(n, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_hid_count_found, dim3(g), dim3(kNmThreads), 0, st, first, n, count);
+    return hipGetLastError();
+}
+
+uint32_t nm_scan_tile() { return kNmTile; }
+
+hipError_t launch_nm_measure_idx(const NmOfJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_nm_measure_idx, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_nm_scan(const NmOfJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmTile, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_nm_scan_tiles, dim3(g), dim3(kNmThreads), 0, st, J);
+    CRASS_LAUNCH(k_nm_scan_top, dim3(1), dim3(kNmThreads), 0, st, J, (uint64_t)g);
+    CRASS_LAUNCH(k_nm_scan_apply, dim3(g), dim3(kNmThreads), 0, st, J, (uint64_t)g);
+    return hipGetLastError();
+}
+
+hipError_t launch_nm_copy(const NmOfJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!J.n || !nm_grid(J.limit, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_nm_copy, dim3(g), dim3(kNmThreads), 0, st, J);
     return hipGetLastError();
 }
 

@@ -42,6 +42,34 @@ struct HidFindJob {
 uint32_t hid_lane_end();                         // names of this many bytes or more are hashed and compared by the wave kernels
 hipError_t launch_hid_find(const HidFindJob &J, hipStream_t st);
 hipError_t launch_hid_find_long(const HidFindJob &J, uint32_t n_long, hipStream_t st);
+// k_hid_find_dev: k_hid_find for queries whose offsets nobody on the host has seen.  J.names, J.name_off and J.first_out are the
+// caller's device memory; the kernel checks every offset pair against n_name_bytes, answers the short queries and lists the
+// long ones itself (long_app, the J.long_list of the launch_hid_find_long that follows once the host has read ctl[0])
+struct HidFindDev {
+    uint64_t n_name_bytes;                       // name_off[k] <= name_off[k + 1] <= this, else the query is bad
+    uint32_t *long_app;                          // [n_names] the queries of hid_lane_end() bytes or more, in any order
+    uint32_t *ctl;                               // [2] 0: entries of long_app, 1: a bad offset pair was seen; both 0 before the launch
+};
+hipError_t launch_hid_find_dev(const HidFindJob &J, const HidFindDev &D, hipStream_t st);
+// *count += the answers of first[0, n) that are not kHidNotFound
+hipError_t launch_hid_count_found(const uint64_t *first, uint64_t n, unsigned long long *count, hipStream_t st);
+
+// k_nm_measure_idx / k_nm_scan_* / k_nm_copy: the names of listed records of a built table, back to back, all in device memory
+struct NmOfJob {
+    const uint8_t *bytes; uint64_t n_bytes;      // the file the table was built on
+    const uint64_t *rec_pos; uint64_t n_reads;   // [n_reads] as at the insert: every entry < n_bytes
+    const uint64_t *idx; uint64_t n;             // [n] entry k is record idx[k] - idx_base, any order, repeats allowed
+    uint64_t idx_base;
+    uint32_t *len;                               // [n] k_nm_measure_idx: the name's bytes; 0 for an entry outside [0, n_reads)
+    uint32_t *flag;                              // set to 1 by such an entry; 0 before the launch
+    uint64_t *tile_sum;                          // [tiles + 1] k_nm_scan_tiles: a tile's bytes; k_nm_scan_top: the bytes in front of it
+    uint64_t *off;                               // [n + 1] k_nm_scan_apply: where the names lie in out; off[n] the total
+    uint8_t *out; uint64_t limit;                // k_nm_copy: min(off[n], the capacity of out) — nothing at or beyond out + limit is written
+};
+uint32_t nm_scan_tile();                         // entries per tile of the prefix sum
+hipError_t launch_nm_measure_idx(const NmOfJob &J, hipStream_t st);
+hipError_t launch_nm_scan(const NmOfJob &J, hipStream_t st);        // the three launches: tile sums, one block over them, apply
+hipError_t launch_nm_copy(const NmOfJob &J, hipStream_t st);
 
 // k_hl_measure / k_hl_copy
 struct HlJob {

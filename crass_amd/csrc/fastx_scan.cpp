@@ -285,4 +285,25 @@ int crass_fastx_find_names(const uint8_t *bytes, uint64_t n_bytes, const uint64_
     return CRASS_OK;
 }
 
+int crass_fastx_names_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint64_t *idx, uint64_t n,
+                         uint64_t idx_base, uint8_t *out, uint64_t cap_bytes, uint64_t *off_out)
+{
+    if (!off_out || (n && !idx) || (n_reads && (!bytes || !rec_pos)) || (cap_bytes && !out)) return CRASS_ERR_INVALID_ARG;
+    auto is_space = [](uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+    off_out[0] = 0;
+    // every index first: nothing is written to out by a call that fails with CRASS_ERR_INVALID_ARG
+    for (uint64_t k = 0; k < n; k++) {
+        if (idx[k] < idx_base || idx[k] - idx_base >= n_reads || rec_pos[idx[k] - idx_base] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+    }
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t a = rec_pos[idx[k] - idx_base] + 1;
+        uint64_t b = a;
+        while (b < n_bytes && !is_space(bytes[b])) b++;          // the name, as crass_fastx_header_ids cuts it
+        const uint64_t at = off_out[k];
+        if (at < cap_bytes) memcpy(out + at, bytes + a, (size_t)std::min(b - a, cap_bytes - at));      // (nothing at or beyond out + cap_bytes)
+        off_out[k + 1] = at + (b - a);
+    }
+    return off_out[n] > cap_bytes ? CRASS_ERR_OVERFLOW : CRASS_OK;
+}
+
 } // extern "C"

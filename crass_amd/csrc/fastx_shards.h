@@ -58,4 +58,6 @@ int shard_pack(crass_hip_ctx *c, int pad_uniform, uint64_t read_index_base);
 void shard_abort(crass_hip_ctx *c);
 // the arena and the records of the last shard_pack (CRASS_ERR_STATE: there is none)
 int shard_records(const crass_hip_ctx *c, const uint8_t **arena, uint64_t *n_bytes, const uint64_t **rec_pos, uint64_t *n_reads);
+// how many answers of the last crass_hip_fastx_names_find_device named a record (counted on the device: the answers stay there)
+uint64_t names_find_device_found(const crass_hip_ctx *c);
 #pragma GCC visibility pop

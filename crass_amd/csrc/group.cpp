@@ -206,6 +206,24 @@ struct crass_hip_group {
     struct { std::vector<uint64_t> cut_pos, file_read_base; std::vector<uint32_t> cut_file; std::vector<int32_t> format; } S;      // crass_fastx_shards' arrays
     // the names of every rank's pass-1 records, for the other ranks to look up (found headers across ranks)
     std::vector<Text> names;
+    // ... or, on the device route (crass_hip_group_set_name_exchange), per rank in its device's memory: its own names and their
+    // offsets (what the other ranks copy from, behind the barrier), the copy of ONE other rank's names at a time (the lookup of a
+    // source has finished before the next one is copied over it), and the answers to all of them back to back — what pass 2
+    // takes as its device list.  n / total: the last publish; cnt: crass_hip_group_name_exchange_counters
+    struct NameX {
+        uint8_t *chars = nullptr, *q_chars = nullptr; uint64_t *off = nullptr, *q_off = nullptr, *first = nullptr;
+        uint64_t cap_chars = 0, cap_names = 0, cap_q_chars = 0, cap_q_names = 0, cap_first = 0;
+        uint64_t n = 0, total = 0, n_first = 0;
+        bool first_valid = false;               // the last merge's exchange took the device route: first[0, n_first) is pass 2's list
+        uint64_t cnt[4] = {0, 0, 0, 0};
+        // the last exchange on this rank, publish to lookup with the barrier between them: wall milliseconds, and (timed groups
+        // only) HIP-event milliseconds on the rank's stream between the same two points
+        float wall_ms = 0, event_ms = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+    };
+    std::vector<NameX> nx;
+    bool names_on_device = false;
+    bool names_timed = false;                   // CRASS_GROUP_NAMES_TIMING at creation: the two events are recorded (tools/group_names_time.py)
     struct {
         std::vector<uint64_t> read; std::vector<uint8_t> low; std::vector<uint32_t> start, end, token; std::vector<uint16_t> dr_len;
         std::vector<char> dr; uint32_t stride = 0; bool ready = false;
@@ -395,6 +413,7 @@ int names_lookup(crass_hip_group *g, int r)
     std::vector<uint64_t> &e = g->extra[r];
     e.clear();
     std::vector<uint64_t> first;
+    uint64_t looked = 0;
     for (int q = 0; q < g->n; q++) {
         const crass_hip_group::Text &NM = g->names[q];
         const uint64_t nq = NM.off.size() - 1;
@@ -403,7 +422,98 @@ int names_lookup(crass_hip_group *g, int r)
         const int s = crass_hip_fastx_names_find(g->ctx[r], NM.chars.data(), NM.off.data(), nq, first.data());
         if (s) return s;
         for (uint64_t k = 0; k < nq; k++) if (first[k] != CRASS_NAME_NOT_FOUND) e.push_back(first[k]);
+        looked += nq;
     }
+    crass_hip_group::NameX &X = g->nx[r];
+    X.n_first = 0; X.first_valid = false;
+    X.cnt[0] = 0; X.cnt[1] = g->names[r].off.size() - 1; X.cnt[2] = looked; X.cnt[3] = e.size();
+    return CRASS_OK;
+}
+
+// ---- the same exchange on the device route: no name, answer or index crosses to the host, only counts and totals ----
+// a buffer of at least `want` elements (+ extra) on the rank's device (the current device); what it held is dropped
+template <typename T> int nx_grow(T *&p, uint64_t &cap, uint64_t want, uint64_t extra)
+{
+    if (p && cap >= want) return CRASS_OK;
+    if (p) { crass::dev_free(p); p = nullptr; cap = 0; }
+    void *q = nullptr;
+    if (crass::dev_alloc(&q, (size_t)((want + extra) * sizeof(T))) != hipSuccess) return CRASS_ERR_OOM;
+    p = (T *)q; cap = want;
+    return CRASS_OK;
+}
+
+void nx_free(crass_hip_group *g, int r)
+{
+    crass_hip_group::NameX &X = g->nx[r];
+    (void)hipSetDevice(g->devices[r]);
+    for (void *p : {(void *)X.chars, (void *)X.q_chars, (void *)X.off, (void *)X.q_off, (void *)X.first}) if (p) crass::dev_free(p);
+    for (hipEvent_t e : X.ev) if (e) (void)hipEventDestroy(e);
+    X = crass_hip_group::NameX{};
+}
+
+// no list of namesakes is left for pass 2, on either route (a load, an explicit pattern set)
+void clear_extra(crass_hip_group *g)
+{
+    for (auto &e : g->extra) e.clear();
+    for (auto &X : g->nx) { X.n_first = 0; X.first_valid = false; }
+}
+
+// rank r's names into its own buffer, sized from the step before (the first step: from the candidate count); too small: regrown
+// to the totals the call reported and the call repeated, once
+int names_publish_device(crass_hip_group *g, int r)
+{
+    crass_hip_group::NameX &X = g->nx[r];
+    X.n = X.total = 0;
+    if (hipSetDevice(g->devices[r]) != hipSuccess) return CRASS_ERR_HIP;
+    crass_counters k{};
+    (void)crass_hip_get_counters(g->ctx[r], &k);
+    const uint64_t want_n = std::max<uint64_t>(X.cap_names, k.n_pass1_found), want_b = std::max<uint64_t>(X.cap_chars, 32 * want_n);
+    int s;
+    if ((s = nx_grow(X.off, X.cap_names, want_n, 1)) || (s = nx_grow(X.chars, X.cap_chars, want_b, 0))) return s;
+    uint64_t n = 0, total = 0;
+    s = crass_hip_found_names_device(g->ctx[r], X.chars, X.cap_chars, X.off, X.cap_names, &n, &total);
+    if (s == CRASS_ERR_OVERFLOW) {
+        if ((s = nx_grow(X.off, X.cap_names, n + n / 4, 1)) || (s = nx_grow(X.chars, X.cap_chars, total + total / 4, 0))) return s;
+        s = crass_hip_found_names_device(g->ctx[r], X.chars, X.cap_chars, X.off, X.cap_names, &n, &total);
+    }
+    if (s) return s;
+    X.n = n; X.total = total;
+    return CRASS_OK;
+}
+
+// behind the barrier: every other rank's names and offsets to this rank's device on its stream, looked up there; the answers of
+// all sources back to back in X.first.  (A source's buffers are not written again before the next step's publish, which lies
+// behind that step's barriers.)
+int names_lookup_device(crass_hip_group *g, int r)
+{
+    crass_hip_group::NameX &X = g->nx[r];
+    g->extra[r].clear();
+    X.n_first = 0; X.first_valid = false;
+    if (hipSetDevice(g->devices[r]) != hipSuccess) return CRASS_ERR_HIP;
+    hipStream_t st = (hipStream_t)crass_hip_stream(g->ctx[r]);
+    uint64_t n_all = 0, found = 0, at = 0;
+    for (int q = 0; q < g->n; q++) if (q != r) n_all += g->nx[q].n;
+    int s;
+    if ((s = nx_grow(X.first, X.cap_first, n_all, 0))) return s;
+    for (int q = 0; q < g->n; q++) {
+        const crass_hip_group::NameX &Q = g->nx[q];
+        if (q == r || !Q.n) continue;
+        if ((s = nx_grow(X.q_off, X.cap_q_names, Q.n, 1)) || (s = nx_grow(X.q_chars, X.cap_q_chars, Q.total, 0))) return s;
+        hipError_t e = hipSuccess;
+        if (g->local_copies || g->devices[q] == g->devices[r]) {
+            e = hipMemcpyAsync(X.q_off, Q.off, (Q.n + 1) * 8, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess && Q.total) e = hipMemcpyAsync(X.q_chars, Q.chars, Q.total, hipMemcpyDeviceToDevice, st);
+        } else {
+            e = hipMemcpyPeerAsync(X.q_off, g->devices[r], Q.off, g->devices[q], (Q.n + 1) * 8, st);
+            if (e == hipSuccess && Q.total) e = hipMemcpyPeerAsync(X.q_chars, g->devices[r], Q.chars, g->devices[q], Q.total, st);
+        }
+        if (e != hipSuccess) { set_error(std::string("found-name exchange, copy of rank ") + std::to_string(q) + "'s names: " + hipGetErrorString(e)); return CRASS_ERR_HIP; }
+        if ((s = crass_hip_fastx_names_find_device(g->ctx[r], X.q_chars, Q.total, X.q_off, Q.n, X.first + at))) return s;
+        found += names_find_device_found(g->ctx[r]);
+        at += Q.n;
+    }
+    X.n_first = at; X.first_valid = true;
+    X.cnt[0] = 1; X.cnt[1] = X.n; X.cnt[2] = at; X.cnt[3] = found;
     return CRASS_OK;
 }
 
@@ -455,21 +565,35 @@ void run_rank(crass_hip_group *g, int r, unsigned phases)
             g->bar->wait();
         }
         if (g->files_load && g->n > 1) {                            // (with one rank nothing is exchanged)
-            try { if (ok()) note(g, r, names_publish(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
+            const bool dev = g->names_on_device;                    // (set between jobs: the same on every rank of a job)
+            crass_hip_group::NameX &X = g->nx[r];
+            const auto t0 = std::chrono::steady_clock::now();
+            bool timed = g->names_timed && ok() && hipSetDevice(g->devices[r]) == hipSuccess;
+            for (hipEvent_t &e : X.ev) if (timed && !e) timed = hipEventCreate(&e) == hipSuccess;
+            if (timed) timed = hipEventRecord(X.ev[0], (hipStream_t)crass_hip_stream(c)) == hipSuccess;
+            try { if (ok()) note(g, r, dev ? names_publish_device(g, r) : names_publish(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
             g->bar->wait();                                         // every rank's names are there
-            try { if (ok()) note(g, r, names_lookup(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
+            try { if (ok()) note(g, r, dev ? names_lookup_device(g, r) : names_lookup(g, r)); } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
+            X.event_ms = 0;
+            if (timed && hipSetDevice(g->devices[r]) == hipSuccess && hipEventRecord(X.ev[1], (hipStream_t)crass_hip_stream(c)) == hipSuccess &&
+                hipEventSynchronize(X.ev[1]) == hipSuccess) (void)hipEventElapsedTime(&X.event_ms, X.ev[0], X.ev[1]);
+            X.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     }
     if ((phases & PH_RECRUIT) && ok()) {
         std::vector<uint64_t> &e = g->extra[r];
         const std::vector<uint64_t> &u = g->extra_user[r];
+        // the device route's namesakes: the answers as the lookup left them on this rank's device, beside the host lists
+        const crass_hip_group::NameX &X = g->nx[r];
+        const uint64_t *d_first = X.first_valid && X.n_first ? X.first : nullptr;
+        const uint64_t n_d = d_first ? X.n_first : 0;
         // (no barrier behind this point: an allocation failure here only ends this rank's part)
         try {
             if (!u.empty()) {                                       // (this call's; extra[r] is rebuilt by the next merge)
                 std::vector<uint64_t> both(e);
                 both.insert(both.end(), u.begin(), u.end());
-                note(g, r, crass_hip_recruit(c, both.data(), both.size()));
-            } else note(g, r, crass_hip_recruit(c, e.empty() ? nullptr : e.data(), e.size()));
+                note(g, r, crass_hip_recruit_found(c, both.data(), both.size(), d_first, n_d));
+            } else note(g, r, crass_hip_recruit_found(c, e.empty() ? nullptr : e.data(), e.size(), d_first, n_d));
         } catch (const std::bad_alloc &) { note(g, r, CRASS_ERR_OOM); }
     }
 }
@@ -543,7 +667,9 @@ int crass_hip_group_create(const crass_params *p, const int *devices, int n, uns
     if (!g) return CRASS_ERR_OOM;
     g->n = n; g->devices.assign(devices, devices + n); g->local_copies = local;
     g->ctx.assign(n, nullptr); g->xc.assign(n, crass_exchange{}); g->recv.assign(n, nullptr); g->status.assign(n, 0); g->ev_send.assign(n, nullptr);
-    g->extra.resize(n); g->extra_user.resize(n); g->dup_local.resize(n);
+    g->extra.resize(n); g->extra_user.resize(n); g->dup_local.resize(n); g->nx.resize(n);
+    if (const char *e = getenv("CRASS_GROUP_NAMES")) g->names_on_device = strcmp(e, "device") == 0;      // (crass_hip_group_set_name_exchange)
+    g->names_timed = getenv("CRASS_GROUP_NAMES_TIMING") != nullptr;
     if (const char *e = getenv("CRASS_GROUP_CAP_ROWS")) { g->cap_rows = (uint64_t)std::max(1, atoi(e)); g->cap_rows_forced = true; }      // (tests: force the overflow path)
     for (int r = 0; r < n; r++) {
         const int s = crass_hip_create(p, devices[r], &g->ctx[r]);
@@ -578,6 +704,7 @@ void crass_hip_group_destroy(crass_hip_group *g)
             (void)hipStreamSynchronize((hipStream_t)crass_hip_stream(g->ctx[r]));
         }
     }
+    for (int r = 0; r < (int)g->nx.size(); r++) nx_free(g, r);      // (behind every stream's wait: a lookup may have read another rank's names)
     for (int r = 0; r < g->n; r++) if (g->ev_send[r]) { (void)hipSetDevice(g->devices[r]); (void)hipEventDestroy(g->ev_send[r]); }
     for (auto cm : g->comms) if (cm) (void)g_rccl.CommDestroy(cm);
     for (auto c : g->ctx) if (c) crass_hip_destroy(c);
@@ -586,6 +713,27 @@ void crass_hip_group_destroy(crass_hip_group *g)
 }
 
 int crass_hip_group_size(const crass_hip_group *g) { return g ? g->n : 0; }
+
+int crass_hip_group_set_name_exchange(crass_hip_group *g, int on_device)
+{
+    if (!g) return CRASS_ERR_INVALID_ARG;
+    g->names_on_device = on_device != 0;
+    return CRASS_OK;
+}
+
+int crass_hip_group_name_exchange_ms(const crass_hip_group *g, int rank, float out[2])
+{
+    if (!g || !out || rank < 0 || rank >= g->n) return CRASS_ERR_INVALID_ARG;
+    out[0] = g->nx[rank].wall_ms; out[1] = g->nx[rank].event_ms;
+    return CRASS_OK;
+}
+
+int crass_hip_group_name_exchange_counters(const crass_hip_group *g, int rank, uint64_t out[4])
+{
+    if (!g || !out || rank < 0 || rank >= g->n) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 4; k++) out[k] = g->nx[rank].cnt[k];
+    return CRASS_OK;
+}
 int crass_hip_group_rccl_ranks(const crass_hip_group *g) { return g ? g->rccl_ranks : 0; }
 crass_hip_ctx *crass_hip_group_ctx(crass_hip_group *g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->ctx[rank] : nullptr; }
 
@@ -607,7 +755,7 @@ int crass_hip_group_load_reads(crass_hip_group *g, const crass_reads *h)
     g->shard.assign(N, crass_reads{});
     g->sh_word_off.assign(N, {}); g->sh_exc_read.assign(N, {}); g->sh_exc_off.assign(N, {}); g->sh_header_id.assign(N, {});
     for (auto &m : g->dup_local) m.clear();
-    for (auto &e : g->extra) e.clear();
+    clear_extra(g);
     g->have_dups = false; g->hid_global.clear();
     // header ids that occur on more than one read (header_id[i] != i marks a repeat of read header_id[i]'s header)
     std::unordered_map<uint64_t, uint8_t> is_dup;
@@ -739,7 +887,7 @@ int crass_hip_group_set_patterns(crass_hip_group *g, const char *const *patterns
         const int s = crass_hip_set_patterns(g->ctx[r], patterns, lengths, n);
         if (s) return s;
     }
-    for (auto &e : g->extra) e.clear();                 // (no device merge ran: cross-shard found headers come from the caller)
+    clear_extra(g);                                     // (no device merge ran: cross-shard found headers come from the caller)
     g->have_merge = true; g->explicit_patterns = true;
     return CRASS_OK;
 }
@@ -828,7 +976,7 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
     g->n_reads = 0; g->base = 0;
     g->first.assign(N + 1, 0);
     for (auto &m : g->dup_local) m.clear();
-    for (auto &e : g->extra) e.clear();
+    clear_extra(g);
     g->have_dups = false; g->hid_global.clear();
     std::vector<crass_bgzf_index> ixs;
     struct FreeIx { std::vector<crass_bgzf_index> &v; ~FreeIx() { for (auto &x : v) crass_bgzf_index_free(&x); } } free_ix{ixs};

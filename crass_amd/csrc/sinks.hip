@@ -31,6 +31,28 @@ hipError_t launch_mark_found(const uint64_t *idx, uint64_t n, const uint64_t *he
     return hipGetLastError();
 }
 
+// k_mark_found over a list made on the device (the answers of crass_hip_fastx_names_find_device): entries equal to kSkip, names
+// nobody here carries, are passed over; any other entry >= n_reads marks nothing and sets *bad.  found_flag == nullptr: the
+// check alone (crass_hip_recruit_found marks only a list without a bad entry).
+__global__ void k_mark_found_skip(const uint64_t *idx, uint64_t n, uint64_t n_reads, const uint64_t *header_id, uint8_t *found_flag, uint32_t *bad)
+{
+    constexpr uint64_t kSkip = ~0ull;                   // CRASS_NAME_NOT_FOUND
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t r = idx[i];
+    if (r == kSkip) return;
+    if (r >= n_reads) { *bad = 1u; return; }
+    if (found_flag) found_flag[header_id ? header_id[r] : r] = 1;
+}
+hipError_t launch_mark_found_skip(const uint64_t *idx, uint64_t n, uint64_t n_reads, const uint64_t *header_id, uint8_t *found_flag, uint32_t *bad,
+                                  hipStream_t st)
+{
+    if (!n) return hipSuccess;
+    if ((n + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_mark_found_skip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, idx, n, n_reads, header_id, found_flag, bad);
+    return hipGetLastError();
+}
+
 // Device -> pinned host copy by a handful of workgroups (the link is the bound: ~55 GB/s needs a few hundred stores in
 // flight, not a chip): the fall-back of the DMA-engine copy (sdma.cpp).  Like the runtime's blit kernel it costs the kernels
 // of the other stream its own duration — PCIe stores from shader waves do, however few waves issue them and on however

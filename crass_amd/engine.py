@@ -562,6 +562,44 @@ def find_names(buf, rec_pos, names):
     return out
 
 
+def names_of(buf, rec_pos, idx, idx_base=0, cap_bytes=None, out=None):
+    """The NAMES of the records idx[k] - idx_base (any order, repeats allowed) back to back, from the file's bytes and the records'
+    positions (crass_fastx_names_of; host): the statement of the rule SearchEngine.names_of_device is tested against.  rec_pos:
+    n_reads + 1 entries as in a FastxLayout.  Returns (chars uint8, off uint64 [n + 1]).  cap_bytes / out: the capacity and the
+    buffer to write into (tests: an overflow raises CrassError with status 8, its `offsets` complete and out filled up to the cap)."""
+    a = _bytes_arg(buf)
+    rp = np.ascontiguousarray(rec_pos, dtype=np.uint64)
+    n = max(len(rp) - 1, 0)
+    ix = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+    off = np.zeros(len(ix) + 1, np.uint64)
+    lib = _abi.load()
+    args = (a.ctypes.data if len(a) else None, len(a), rp.ctypes.data if len(rp) else None, n, ix.ctypes.data if len(ix) else None, len(ix), int(idx_base))
+    if out is None and cap_bytes is None:          # measure, then fill
+        st = lib.crass_fastx_names_of(*args, None, 0, off.ctypes.data)
+        if st not in (0, _abi.ERR_OVERFLOW):
+            _chk(st, "crass_fastx_names_of")
+        cap_bytes = int(off[len(ix)])
+    if out is None:
+        out = np.zeros(int(cap_bytes), np.uint8)
+    cap = len(out) if cap_bytes is None else int(cap_bytes)
+    st = lib.crass_fastx_names_of(*args, out.ctypes.data if cap else None, cap, off.ctypes.data)
+    if st != 0:
+        e = CrassError(st, "crass_fastx_names_of")
+        e.offsets = off
+        raise e
+    return out[:int(off[len(ix)])], off
+
+
+def _device_array(x, dtype, what):
+    """(address, elements) of device memory: a raw address with its element count as a tuple (addr, n), or a contiguous torch
+    device tensor of that dtype"""
+    if isinstance(x, tuple):
+        return (int(x[0]) or None), int(x[1])
+    if str(x.dtype) != "torch." + dtype or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("%s: a contiguous %s device tensor or (address, elements)" % (what, dtype))
+    return (int(x.data_ptr()) if x.numel() else None), int(x.numel())
+
+
 class FastxFile:
     """FASTA/FASTQ(.gz) records with kseq_read semantics (C++ reader, crass_read_fastx)."""
 
@@ -1244,6 +1282,53 @@ class SearchEngine:
                                                  out.ctypes.data if m else None), "crass_hip_fastx_names_find")
         return out
 
+    def _names_out(self, st, where, n, d_off, total):
+        if st != 0:
+            e = CrassError(st, where)
+            e.n, e.total = int(n), int(total)
+            raise e
+        return int(n), int(total)
+
+    def names_of_device(self, idx, out_chars, out_off, idx_base=0):
+        """The NAMES of the records idx[k] - idx_base of the table names_build keeps, back to back in out_chars with their offsets
+        (n + 1) in out_off, everything in DEVICE memory (crass_hip_fastx_names_of_device): idx and out_off are contiguous torch
+        int64 device tensors or (address, elements), out_chars a torch uint8 device tensor or (address, bytes).  Returns the
+        total bytes, the call's one host read.  An out_chars too small raises CrassError with status 8, `total` set, the offsets
+        complete and nothing written at or beyond its end."""
+        pi, n = _device_array(idx, "int64", "names_of_device(idx)")
+        pc, cap = _device_array(out_chars, "uint8", "names_of_device(out_chars)")
+        po, no = _device_array(out_off, "int64", "names_of_device(out_off)")
+        if no < n + 1:
+            raise ValueError("names_of_device(out_off) needs n + 1 elements")
+        total = C.c_uint64()
+        st = self.lib.crass_hip_fastx_names_of_device(self.h, pi, n, int(idx_base), pc, cap, po, C.byref(total))
+        return self._names_out(st, "crass_hip_fastx_names_of_device", n, po, total.value)[1]
+
+    def found_names_device(self, out_chars, out_off):
+        """The NAMES of this context's pass-1 records, in record order, into DEVICE memory (crass_hip_found_names_device): what a
+        rank publishes for the found headers of other ranks, without the caller holding the records' indices.  out_chars /
+        out_off as names_of_device takes them (out_off: room for cap_names + 1 offsets).  Returns (n, total); too small a
+        buffer raises CrassError with status 8 and `n` / `total` set."""
+        pc, cap = _device_array(out_chars, "uint8", "found_names_device(out_chars)")
+        po, no = _device_array(out_off, "int64", "found_names_device(out_off)")
+        n, total = C.c_uint64(), C.c_uint64()
+        st = self.lib.crass_hip_found_names_device(self.h, pc, cap, po, max(no - 1, 0), C.byref(n), C.byref(total))
+        return self._names_out(st, "crass_hip_found_names_device", n.value, po, total.value)
+
+    def names_find_device(self, names, name_off, out_first, n_name_bytes=None):
+        """names_find with the queries (names: uint8, name_off: int64 [n + 1]) and the answers (out_first: int64 [n]; an answer's
+        bits are the uint64 of names_find, -1 where no record has the name) in DEVICE memory: torch device tensors or (address,
+        elements) (crass_hip_fastx_names_find_device).  n_name_bytes: the bytes of names the offsets may refer to (default: all
+        of the tensor)."""
+        pn, nb = _device_array(names, "uint8", "names_find_device(names)")
+        po, no = _device_array(name_off, "int64", "names_find_device(name_off)")
+        pf, nf = _device_array(out_first, "int64", "names_find_device(out_first)")
+        m = max(no - 1, 0)
+        if nf < m:
+            raise ValueError("names_find_device(out_first) needs one element per query")
+        _chk(self.lib.crass_hip_fastx_names_find_device(self.h, pn, nb if n_name_bytes is None else int(n_name_bytes), po, m, pf),
+             "crass_hip_fastx_names_find_device")
+
     def names_drop(self):
         """Gives the table of names_build back (crass_hip_fastx_names_drop); fine without one."""
         _chk(self.lib.crass_hip_fastx_names_drop(self.h), "crass_hip_fastx_names_drop")
@@ -1418,9 +1503,17 @@ class SearchEngine:
         lens = (C.c_uint32 * len(patterns))(*[len(p) for p in patterns])
         _chk(self.lib.crass_hip_set_patterns(self.h, arr, lens, len(patterns)), "crass_hip_set_patterns")
 
-    def recruit(self, extra_found=None, fetch=True):
+    def recruit(self, extra_found=None, fetch=True, extra_found_device=None):
+        """extra_found_device: a second list of found reads in DEVICE memory (a contiguous torch int64 device tensor or (address,
+        elements)) that may hold -1, names_find_device's "no record" (crass_hip_recruit_found)."""
+        ef = None
         if extra_found is not None and len(extra_found):
             ef = np.ascontiguousarray(extra_found, dtype=np.uint64)
+        if extra_found_device is not None:
+            pd, nd = _device_array(extra_found_device, "int64", "recruit(extra_found_device)")
+            _chk(self.lib.crass_hip_recruit_found(self.h, None if ef is None else ef.ctypes.data, 0 if ef is None else len(ef), pd, nd),
+                 "crass_hip_recruit_found")
+        elif ef is not None:
             _chk(self.lib.crass_hip_recruit(self.h, ef.ctypes.data, len(ef)), "crass_hip_recruit")
         else:
             _chk(self.lib.crass_hip_recruit(self.h, None, 0), "crass_hip_recruit")
@@ -1637,6 +1730,25 @@ class SearchGroup:
                                                          has.ctypes.data if len(a) else None), "crass_hip_group_fetch_quality")
         t = Text(v)
         return t.chars.copy(), t.off.copy(), has
+
+    def set_name_exchange(self, on_device):
+        """The route of the found-name exchange of a files load: False the host's (the default), True everything in device memory
+        (crass_hip_group_set_name_exchange; CRASS_GROUP_NAMES=device at creation does the same)."""
+        self._chk(self.lib.crass_hip_group_set_name_exchange(self.h, 1 if on_device else 0), "crass_hip_group_set_name_exchange")
+
+    def name_exchange_counters(self, rank):
+        """(route of the last step's exchange: 0 host / 1 device, names published, queries looked up, namesakes found) of a rank
+        (crass_hip_group_name_exchange_counters)."""
+        out = np.zeros(4, np.uint64)
+        self._chk(self.lib.crass_hip_group_name_exchange_counters(self.h, int(rank), out.ctypes.data), "crass_hip_group_name_exchange_counters")
+        return tuple(int(x) for x in out)
+
+    def name_exchange_ms(self, rank):
+        """(wall ms, HIP-event ms) of the last step's exchange on a rank, publish to lookup (crass_hip_group_name_exchange_ms); the
+        event time only in a group created with CRASS_GROUP_NAMES_TIMING set, else 0."""
+        out = np.zeros(2, np.float32)
+        self._chk(self.lib.crass_hip_group_name_exchange_ms(self.h, int(rank), out.ctypes.data), "crass_hip_group_name_exchange_ms")
+        return float(out[0]), float(out[1])
 
     def rank_counters(self, rank):
         c = _abi.Counters()

@@ -283,6 +283,13 @@ int crass_hip_set_patterns(crass_hip_ctx *ctx, const char *const *patterns,
  * libcrispr.cpp:411) are skipped; `extra_found` (may be NULL) lists further header ids,
  * as global read indices, found by OTHER ranks' pass 1 (duplicate headers across shards).  */
 int crass_hip_recruit(crass_hip_ctx *ctx, const uint64_t *extra_found, uint64_t n_extra);
+/* replaces: the same, with a second list of found reads that lies in DEVICE memory and may hold CRASS_NAME_NOT_FOUND — the
+ * answers of crass_hip_fastx_names_find_device as they are, no copy to the host and back (k_mark_found_skip passes those
+ * entries over).  n_d_extra == 0: crass_hip_recruit, call for call.  CRASS_ERR_INVALID_ARG: a NULL d_extra_found with
+ * n_d_extra > 0, or any other device entry >= the resident set's reads (seen on the device before anything of that list is
+ * marked): no pass-2 result is left, crass_hip_get_recruits returns CRASS_ERR_STATE.  The repeats inside the call (host merge
+ * fall-back, a bound that was too small) carry both lists along. */
+int crass_hip_recruit_found(crass_hip_ctx *ctx, const uint64_t *extra_found, uint64_t n_extra, const uint64_t *d_extra_found, uint64_t n_d_extra);
 
 typedef struct {
     uint64_t        n;
@@ -623,10 +630,52 @@ float crass_hip_last_header_ids_ms(const crass_hip_ctx *ctx, int part);
  * it; the build then keeps no table of its own); CRASS_ERR_STATE — find without a table; CRASS_ERR_UNSUPPORTED — n_reads or
  * n_names >= 2^32 - 1.  n_names == 0 (with a table): CRASS_OK.  n_reads == 0 (with a non-NULL pointer): build is CRASS_OK and every query is
  * CRASS_NAME_NOT_FOUND.  drop without a table: CRASS_OK.
- * Not here: queries that are already in device memory — a _device twin of find can follow. */
+ * Queries that are already in device memory: crass_hip_fastx_names_find_device, below. */
 int  crass_hip_fastx_names_build_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads);
 int  crass_hip_fastx_names_find(crass_hip_ctx *ctx, const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out);
 int  crass_hip_fastx_names_drop(crass_hip_ctx *ctx);
+/* ---- the found-name exchange with everything in device memory: names out, looked up, marked ----
+ * replaces: the name cut of kseq for listed records, on the host (no GPU): the statement of the rule the device call below is
+ * tested against.  Entry k is record idx[k] - idx_base (any order, repeats allowed); its NAME, as crass_fastx_header_ids cuts it,
+ * goes to out at off_out[k]; off_out ([n + 1], never NULL) holds the offsets and the total.  CRASS_ERR_OVERFLOW: cap_bytes <
+ * off_out[n] — the offsets are complete, the first cap_bytes bytes are written and nothing at or beyond out + cap_bytes is.
+ * CRASS_ERR_INVALID_ARG: a NULL off_out, NULL arrays with counts > 0, an index outside [idx_base, idx_base + n_reads), a
+ * rec_pos >= n_bytes — nothing is written to out.  n == 0: CRASS_OK, off_out[0] = 0. */
+int  crass_fastx_names_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint64_t *idx, uint64_t n,
+                          uint64_t idx_base, uint8_t *out, uint64_t cap_bytes, uint64_t *off_out);
+/* replaces: crass_hip_fetch_header_lines_device plus the host's cut at the name, for a caller who hands the names to another
+ * stream or device: the same names of records of the table crass_hip_fastx_names_build_device keeps (k_nm_measure_idx, a
+ * three-launch prefix sum, k_nm_copy).  d_idx ([n]), d_chars ([cap_bytes], any alignment) and d_off ([n + 1], never NULL) are
+ * DEVICE memory of the context's device; *total_out (host, may be NULL) is the call's one host read.  The call returns after its
+ * kernels have finished.  CRASS_ERR_STATE: no table.  CRASS_ERR_OVERFLOW: cap_bytes < total — *total_out and d_off are complete,
+ * the first cap_bytes bytes are written and nothing at or beyond d_chars + cap_bytes is (the rule of crass_hip_fetch_text_device).
+ * CRASS_ERR_INVALID_ARG: a NULL context or d_off, NULL arrays with counts > 0 (nothing launched), an entry outside [idx_base,
+ * idx_base + n_reads) (seen on the device: d_off holds length 0 for it, no byte is written).  CRASS_ERR_UNSUPPORTED: n >= 2^32 - 1.
+ * n == 0: CRASS_OK, d_off[0] = 0. */
+int  crass_hip_fastx_names_of_device(crass_hip_ctx *ctx, const uint64_t *d_idx, uint64_t n, uint64_t idx_base, uint8_t *d_chars, uint64_t cap_bytes,
+                                     uint64_t *d_off, uint64_t *total_out);
+/* replaces: crass_hip_get_candidates + crass_hip_fetch_header_lines_device + the cut at the name (what a rank publishes for the
+ * found headers of other ranks): the names of this context's pass-1 records, in record order, without the caller holding their
+ * indices — they are read where pass 1 left them on the device, with idx_base = the set's read_index_base.  A step without a
+ * device copy of them (the long reads' host-loop sink) uploads the host list: the only host array this call may send.
+ * d_off: DEVICE [cap_names + 1] (may be NULL with cap_names == 0); *n_out (never NULL) the records, *total_out the bytes.
+ * CRASS_ERR_STATE: no table, or no pass 1.  CRASS_ERR_OVERFLOW: cap_names < *n_out (nothing of the caller's is written; both
+ * counts are filled) or cap_bytes < *total_out (as above).  Other errors as crass_hip_fastx_names_of_device. */
+int  crass_hip_found_names_device(crass_hip_ctx *ctx, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *d_off, uint64_t cap_names, uint64_t *n_out,
+                                  uint64_t *total_out);
+/* replaces: crass_hip_fastx_names_find for queries that are in DEVICE memory (another rank's crass_hip_found_names_device, copied
+ * device to device): d_names ([n_name_bytes], any alignment), d_name_off ([n_names + 1]) and d_first_out ([n_names]) are device
+ * memory of the context's device; the answers are crass_fastx_find_names' (the hash, probe and comparison of k_hid_find).  Nobody
+ * on the host has seen the offsets: k_hid_find_dev checks them, and lists the queries of 260 bytes or more for k_hid_find_long
+ * itself — the host reads that count and one flag.  The call returns after its kernels have finished.  CRASS_ERR_STATE: no table.
+ * CRASS_ERR_INVALID_ARG: a NULL context, NULL arrays with counts > 0 (nothing launched), a decreasing offset pair or an offset
+ * beyond n_name_bytes (seen on the device: such a query reads nothing and answers CRASS_NAME_NOT_FOUND, the others are answered).
+ * CRASS_ERR_UNSUPPORTED: n_names >= 2^32 - 1.  n_names == 0: CRASS_OK.  A table of no records: every answer is
+ * CRASS_NAME_NOT_FOUND. */
+int  crass_hip_fastx_names_find_device(crass_hip_ctx *ctx, const uint8_t *d_names, uint64_t n_name_bytes, const uint64_t *d_name_off,
+                                       uint64_t n_names, uint64_t *d_first_out);
+/* entries per tile of the prefix sum of crass_hip_fastx_names_of_device (tests place n on its edges) */
+uint32_t crass_hip_names_scan_tile(void);
 /* HIP-event time, in milliseconds on the context's stream: part 0 the insert launches of the last crass_hip_fastx_names_build_device
  * (the host's look at the count of long names included), 1 the kernels of the last crass_hip_fastx_names_find; measured when the
  * stage timing level is >= 1, else 0.  (No reference counterpart: crass has no timers.) */
@@ -980,6 +1029,25 @@ int  crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *
  * >= n_reads. */
 int  crass_hip_group_fetch_header_lines(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint32_t *name_len_out);
 int  crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_qual_out);
+/* the route of the found-name exchange of a files load (names that repeat across ranks, above).  0, the default: through the host —
+ * header lines back, cut at the name, every other rank's names up (crass_hip_fastx_names_find), the namesakes up again.
+ * on_device != 0 (or CRASS_GROUP_NAMES=device in the environment when the group is created): rank r writes its names with
+ * crass_hip_found_names_device into a device buffer of its own (sized from the step before; regrown once to the reported totals
+ * on CRASS_ERR_OVERFLOW), copies every other rank's names and offsets to its device on its stream (hipMemcpyPeerAsync; with
+ * CRASS_GROUP_LOCAL_COPIES a device-to-device copy), looks them up with crass_hip_fastx_names_find_device into one answer array
+ * and hands that to crass_hip_recruit_found.  No name, answer or index crosses to the host, only counts and totals; a failed
+ * copy is CRASS_ERR_HIP of the step, never a change of route.  Both routes give the same results.  CRASS_ERR_INVALID_ARG: a NULL
+ * group. */
+int  crass_hip_group_set_name_exchange(crass_hip_group *g, int on_device);
+/* out: [0] the route of the last step's exchange on that rank (0 host, 1 device), [1] the names it published, [2] the queries
+ * it looked up (the other ranks' names), [3] the namesakes it found; zeros before the first exchange.  CRASS_ERR_INVALID_ARG: a
+ * NULL group or out, a rank outside the group. */
+int  crass_hip_group_name_exchange_counters(const crass_hip_group *g, int rank, uint64_t out[4]);
+/* what the last step's exchange took on that rank, from the publish to the end of the lookup, the barrier between them
+ * included: out[0] wall milliseconds; out[1] HIP-event milliseconds on the rank's stream between the same two points, measured
+ * only in a group created with CRASS_GROUP_NAMES_TIMING in the environment, else 0.  (No reference counterpart: crass has no
+ * timers.)  CRASS_ERR_INVALID_ARG as above. */
+int  crass_hip_group_name_exchange_ms(const crass_hip_group *g, int rank, float out[2]);
 /* the two decisions of the packers on their own, for callers and tests without a GPU: the layout crass_pack_reads and
  * crass_hip_load_text give a set (stride_words / uniform_len as in crass_reads), and the byte -> code function both use —
  * four sequence bytes (byte 0 first) -> their 2-bit codes in bits [2i, 2i+2), *bad bit i set when byte i is not A C G T

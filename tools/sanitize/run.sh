@@ -62,3 +62,7 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinc
 python3 tools/sanitize/fastx_scan_dump.py $out/fastx > /dev/null
 $out/shards_asan $out/fastx/* > $out/report_shards.txt 2> $out/sanitizer_shards.txt || true
 echo "shards: $(tail -1 $out/report_shards.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_shards.txt || true) sanitizer reports"
+# the names of listed records on the host (crass_fastx_names_of) over the same sets and designed inputs of its own, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/names_of_main.cpp -o $out/names_of_asan -lz
+$out/names_of_asan $out/fastx/* > $out/report_names_of.txt 2> $out/sanitizer_names_of.txt || true
+echo "names of: $(grep -c '^ok  ' $out/report_names_of.txt) ok, $(grep -c '^DIFF' $out/report_names_of.txt || true) differ; $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_names_of.txt || true) sanitizer reports"
