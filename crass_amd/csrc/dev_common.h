@@ -1,5 +1,6 @@
-// dev_common.h — device functions shared by the kernel files (kernels.hip, sinks.hip, pass2.hip): the wave helpers and the
-// accessors of a resident read set.  Everything here is static and force-inlined; a function used by one file only lives there.
+// dev_common.h — device functions shared by the kernel files (pass 1's, sinks.hip, pass2.hip): the wave helpers and the
+// accessors of a resident read set.  Everything here is static and force-inlined; a function used by one file only lives there,
+// and what only pass 1's files share is in search_bits.h.
 #pragma once
 #include "engine_internal.h"
 

@@ -1,4 +1,4 @@
-// engine_internal.h — types shared by the HIP kernels (kernels.hip, pass2.hip, sinks.hip) and the host engine
+// engine_internal.h — types shared by the HIP kernels (kernels.hip, survivors.hip and the three files it compiles, pass2.hip, sinks.hip) and the host engine
 // (engine.cpp, engine_pass1.cpp, engine_merge.cpp, engine_pass2.cpp, engine_ingest.cpp).  Not part of the public ABI (include/crass_hip.h is).
 #pragma once
 #include <stdint.h>
@@ -328,7 +328,7 @@ struct SurvLds {
     uint32_t ss_slot;             // entries per survivor slot of the start/stop pool in slot mode: the FULL layout's ss_cap in every launch of a set
 };
 
-// ---- launch wrappers implemented in kernels.hip, pass2.hip and sinks.hip (all asynchronous on `st`) ----
+// ---- launch wrappers implemented in kernels.hip (filters, hints), survivor_wave.hip, long_light.hip, survivor_lanes.hip, pass2.hip and sinks.hip (all asynchronous on `st`) ----
 hipError_t launch_filter_general(const DevReads &R, const DevParams &P, uint64_t *hitmask,
                                  uint32_t max_len, hipStream_t st);
 // per-position seed hints for long / ragged packed reads (default window and DR/spacer bounds only):

@@ -1,4 +1,4 @@
-// lane_find.h — the lane kernel's seed find (k_survivor_lanes, kernels.hip: ln_find) as a pure function on registers, one
+// lane_find.h — the lane kernel's seed find (k_survivor_lanes, survivor_lanes.hip: ln_find) as a pure function on registers, one
 // source for the device and for the host program that checks it against the serial rule (tools/lane_find_main.cpp,
 // tests/test_lane_find_host.py).  Plain C++ on the host; under hipcc a __host__ __device__ function whose three primitive
 // steps are single gfx950 instructions on the device.  Not part of the public ABI.

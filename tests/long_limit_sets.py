@@ -18,7 +18,7 @@ def revcomp(s):
 
 
 def full_layout_bytes(L, window=8, low_sp=26, row_len=None):
-    """survivor_lds_layout's total for a set whose longest read has L bases (kernels.hip): ASCII copy, start/stop list and sims,
+    """survivor_lds_layout's total for a set whose longest read has L bases (survivor_wave.hip): ASCII copy, start/stop list and sims,
     two rows of 16-bit cells, packed words, hint words.  row_len: the longest string the rows hold (None: the read itself)."""
     seq = (L + 32 + 15) & ~15
     ss_cap = (2 * (L // (window + low_sp) + 4) + 3) & ~3

@@ -1,4 +1,4 @@
-"""The lane kernel's packed seed find (crass_amd/csrc/lane_find.h, ln_find of kernels.hip) on designed reads: sets of 256 .. 512
+"""The lane kernel's packed seed find (crass_amd/csrc/lane_find.h, ln_find of survivor_lanes.hip) on designed reads: sets of 256 .. 512
 reads — one block to two blocks of k_survivor_lanes — through the whole pipeline against the oracle, field by field, and a
 second time in a fresh child process with CRASS_LANE_FIND_SERIAL=1 (the one-candidate-per-step loop), which must give the
 same.  The find's own rule, candidate by candidate, is tests/test_lane_find_host.py's business; here its windows sit where
@@ -15,7 +15,7 @@ the kernel puts them:
 
 The reads above are chance 8-mers or arrays found through a candidate in the middle of a window: their records do not change
 when a window's first or last candidate is lost.  What pins the window's edges — ln_find's candidate count, its clamps and
-its chunk loop exist in kernels.hip only — are the EDGE ARRAYS (edge_arrays): real arrays in which EVERY seed of
+its chunk loop exist in survivor_lanes.hip only — are the EDGE ARRAYS (edge_arrays): real arrays in which EVERY seed of
 the repeat has its only copy at one edge of its window, so the read is found iff that candidate is:
 
   first           THREE repeats, DR = lowDR, spacers = lowSp: the copy exactly at beginSearch and the third copy past the

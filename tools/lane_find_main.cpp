@@ -1,5 +1,5 @@
 // lane_find_main.cpp — the packed seed find of the lane kernel (crass_amd/csrc/lane_find.h: find_packed) against the serial
-// rule it replaces (bmpSearch's, one candidate at a time: a copy of ln_find_serial of kernels.hip on host words), on designed
+// rule it replaces (bmpSearch's, one candidate at a time: a copy of ln_find_serial of survivor_lanes.hip on host words), on designed
 // cases and on random draws.  Host only:  c++ -O2 -std=c++17 -I crass_amd/csrc tools/lane_find_main.cpp -o lane_find_main
 // (tests/test_lane_find_host.py does that; with -fsanitize=address,undefined it is the sanitizer run of the header).
 // Exit status 0: no difference; 1: the first difference is printed.     usage: lane_find_main [random draws, default 1000000]
