@@ -1,7 +1,8 @@
 // engine.cpp — the context behind include/crass_hip.h: its creation and destruction, what every call that makes a read set
 // resident ends with (scratch, position hints, first-call bounds), the install of a pattern set, Levenshtein, counters.
 // The stages are files of their own: engine_pass1.cpp (seed scan), engine_merge.cpp (merge, exchange), engine_pass2.cpp (recruit),
-// engine_ingest.cpp (device ingest).  The context itself is engine_ctx.h, which also declares what crosses these files.
+// engine_ingest.cpp, engine_fastx.cpp, engine_inflate.cpp, engine_names.cpp, engine_shards.cpp (device ingest).  The context itself
+// is engine_ctx.h, which also declares what crosses these files.
 //
 // There is no CPU fallback anywhere in these files: every search decision is made by the HIP kernels in kernels.hip, survivors.hip (survivor_wave.hip,
 // long_light.hip, survivor_lanes.hip), pass2.hip and sinks.hip; the host only orders, tokenises and clusters their output ("stays on host").

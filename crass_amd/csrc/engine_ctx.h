@@ -1,8 +1,10 @@
 // engine_ctx.h — the context behind include/crass_hip.h and what its members are made of, shared by the host files that
 // implement the ABI: engine.cpp (create / destroy, what every load ends with, pattern install, Levenshtein, counters),
 // engine_pass1.cpp (the seed scan and its sinks), engine_merge.cpp (the merge on the device and on the host, the exchange),
-// engine_pass2.cpp (set_patterns, recruit) and engine_ingest.cpp (the device ingest: load / attach, FASTA / FASTQ scan, BGZF
-// and gzip inflate, header ids, names, header lines, quality, fetch text).  What crosses these files is declared at the end.
+// engine_pass2.cpp (set_patterns, recruit) and the device ingest: engine_ingest.cpp (load / attach, fetch text, the scratch
+// given back), engine_fastx.cpp (FASTA / FASTQ scan), engine_inflate.cpp (BGZF and gzip inflate), engine_names.cpp (header ids,
+// names, header lines, quality), engine_shards.cpp (a group's file shards).  What crosses these files is declared at the end;
+// what crosses the ingest's five among themselves, in ingest_internal.h.
 // Host only: no .hip file includes this.
 #pragma once
 #include "../../include/crass_hip.h"
@@ -189,8 +191,9 @@ struct LineFetch {
     void free_all() { release_device(); h_src.release(); h_off.release(); h_len.release(); h_chars.release(); }
 };
 
-// ---- device ingest: everything the load / inflate / names / fetch calls keep in the context.  Each stage's device scratch goes
-// back through ONE function of engine_ingest.cpp (release_*); ingest_free_all is made of those plus what is kept.
+// ---- device ingest: everything the load / inflate / names / fetch calls keep in the context (engine_ingest.cpp, engine_fastx.cpp,
+// engine_inflate.cpp, engine_names.cpp, engine_shards.cpp).  Each stage's device scratch goes back through ONE function of
+// engine_ingest.cpp (release_*, declared in ingest_internal.h); ingest_free_all is made of those plus what is kept.
 struct Ingest {
     // crass_hip_load_text / crass_hip_attach_device_text: the text's offsets on the device (lengths that differ), the two
     // staged chunks of a host text (pinned source of the copy, device destination) and the events that order their reuse
@@ -375,7 +378,7 @@ struct crass_hip_ctx {
     DevBuf<uint32_t> r_exc_mask; DevBuf<uint64_t> r_exc_read; DevBuf<uint64_t> r_exc_off; DevBuf<uint8_t> r_exc_bytes;
     std::vector<uint64_t> h_exc_read;        // host copy of the exception read indices (local)
     std::vector<uint32_t> h_lengths;         // the lengths of a set whose reads differ in length, kept on the host (crass_hip_fetch_text sums a fetch's offsets from them)
-    Ingest in;                               // device ingest: loaders, inflate, header ids, names, header lines, quality, fetch text (engine_ingest.cpp)
+    Ingest in;                               // device ingest: loaders, inflate, header ids, names, header lines, quality, fetch text (engine_ingest.cpp and the four files beside it)
 
     // scratch
     DevBuf<uint64_t> d_mask; DevBuf<uint32_t> d_word_prefix; DevBuf<uint32_t> d_block_sums;

@@ -1,8 +1,10 @@
 // fastx_scan.cpp — the record scan of fastx_scan.h on the host, one byte after the other: the restatement the device scan
-// (fastx_scan.hip) is tested against, and the header ids of a scanned file.  Host-only C++17 that any compiler builds
+// (fastx_scan.hip) is tested against, the header ids of a scanned file, and the host arithmetic of a rank's shard
+// (fastx_shards.h: the BGZF members of a text range, the staging placement).  Host-only C++17 that any compiler builds
 // (tools/sanitize).
 #include "../../include/crass_hip.h"
 #include "fastx_scan.h"
+#include "fastx_shards.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -90,6 +92,25 @@ int fx_probe_serial(const uint8_t *bytes, uint64_t n, bool left_is_ls, FxProbe *
     }
     *out = P;
     return CRASS_OK;
+}
+
+// ---- the host arithmetic of a rank's shard (fastx_shards.h) ----
+void bgzf_members_for(const uint64_t *oo, uint64_t n, uint64_t a, uint64_t b, uint64_t *m0, uint64_t *m1)
+{
+    *m0 = a == 0 ? 0 : (uint64_t)(std::upper_bound(oo + 1, oo + n + 1, a) - (oo + 1));      // the first member that ends behind a
+    uint64_t e = (uint64_t)(std::upper_bound(oo + 1, oo + n + 1, b) - (oo + 1));            // ... behind b
+    if (e < n && oo[e] < b) e++;
+    *m1 = e;
+}
+
+uint64_t shard_stage_place(const uint64_t *sa, const uint64_t *sb, uint64_t n, uint64_t *off)
+{
+    uint64_t cursor = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        off[k] = ((cursor + 15) & ~15ull) + (sa[k] & 15u);
+        cursor = off[k] + (sb[k] - sa[k]);
+    }
+    return cursor + 32;
 }
 
 } // namespace crass

@@ -1,4 +1,4 @@
-// fastx_scan.h — what the host restatement (fastx_scan.cpp), the device scan (fastx_scan.hip) and the engine (engine_ingest.cpp)
+// fastx_scan.h — what the host restatement (fastx_scan.cpp), the device scan (fastx_scan.hip) and the engine (engine_fastx.cpp)
 // share about finding the records of a FASTA / FASTQ file by LINES: the byte classes, the line kinds, the decline reasons and
 // the order in which offences are reported.  Plain C++ with CRASS_HD (pack_text.h), so the rule exists once for host and
 // device.  Not part of the public ABI (the reasons' VALUES are: include/crass_hip.h names them).

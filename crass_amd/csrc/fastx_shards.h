@@ -1,6 +1,7 @@
-// fastx_shards.h — what the group (group.cpp) and the device ingest (engine_ingest.cpp) share about loading record-aligned
+// fastx_shards.h — what the group (group.cpp) and the device ingest (engine_shards.cpp) share about loading record-aligned
 // shards of a job's files (crass_hip_group_load_fastx_files): one rank's three steps, between which the group's threads meet
-// at barriers and rank 0 combines.  The cut rule is fastx_scan.h's.  Not part of the public ABI.
+// at barriers and rank 0 combines, and the host arithmetic of a shard (fastx_scan.cpp).  The cut rule is fastx_scan.h's.  Not
+// part of the public ABI.
 #pragma once
 #include "../../include/crass_hip.h"
 #include "fastx_scan.h"
@@ -38,6 +39,17 @@ inline bool shard_verdict_before(const ShardVerdict &x, const ShardVerdict &y)
     if (xz) return x.bgzf.member != y.bgzf.member ? x.bgzf.member < y.bgzf.member : x.bgzf.reason < y.bgzf.reason;
     return x.pos != y.pos ? x.pos < y.pos : x.reason < y.reason;
 }
+
+// ---- host arithmetic of a shard, no device byte read (fastx_scan.cpp; tools/sanitize/shards_main.cpp checks both) ----
+// The members of a BGZF index (out_off[n_members + 1], non-decreasing from 0) that hold the text range [a, b): [*m0, *m1).
+// Members without text are taken where they lie at b, and from member 0 when a is 0 (in front of a > 0 they are the range
+// before's), so that a file cut into ranges that tile its text has every member inflated by somebody, the 28-byte end-of-file
+// member included.
+void bgzf_members_for(const uint64_t *out_off, uint64_t n_members, uint64_t a, uint64_t b, uint64_t *m0, uint64_t *m1);
+// Where n pieces of text, piece k the range [sa[k], sb[k]) of its file, lie in one staging buffer: each at the next multiple of
+// 16 plus its text position modulo 16, off[k] = ((cursor + 15) & ~15) + (sa[k] & 15), so that a piece is aligned as its text is.
+// Returns the buffer's size: the last piece's end and 32 bytes of room behind it.
+uint64_t shard_stage_place(const uint64_t *sa, const uint64_t *sb, uint64_t n, uint64_t *off);
 
 } // namespace crass
 

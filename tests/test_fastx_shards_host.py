@@ -2,10 +2,16 @@
 tests/shard_sets.py: every byte position of each designed file as the nominal cut, 1 .. 7 ranks with even cuts, the records in
 front of every cut against crass_fastx_files_scan_host's rec_pos, and the verdict of every declined input unchanged by any cut.
 The serial probe (crass_fastx_cut_probe_host) and the pick of a record start from it, against the same brute force."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
 from tests import files_sets, shard_sets
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -139,3 +145,26 @@ def test_invalid_arguments(ca):
         with pytest.raises((ca.CrassError, ValueError)) as e:
             ca.fastx_files_shards_host([fq], n, nominal)
         assert not isinstance(e.value, ca.CrassError) or e.value.status == 1
+
+
+def test_member_rule_program(tmp_path):
+    """tools/sanitize/shards_main.cpp without a file: the self-check of the host arithmetic of a rank's shard (csrc/fastx_shards.h,
+    csrc/fastx_scan.cpp) under AddressSanitizer + UBSan, as a stand-alone program with the sanitizer runtimes linked statically and
+    nothing preloaded.  bgzf_members_for over every tiling it enumerates or draws (fixed seed; indices of 1 .. 8 members of 0, 1,
+    2, 5 or 16 bytes, up to three inner cuts): every range enclosed by its members and every member taken by some range, no case
+    failing; shard_stage_place over designed pieces: phase, no overlap, the buffer's size."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "shards_asan")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer",
+                           "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "crass_amd", "csrc", "fastx_scan.cpp"), os.path.join(ROOT, "crass_amd", "csrc", "bgzf.cpp"),
+                           os.path.join(ROOT, "tools", "sanitize", "shards_main.cpp"), "-o", exe])
+    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = r.stdout.splitlines()
+    assert lines[0].startswith("ok   member rule:") and lines[0].endswith(" 0 fail"), lines
+    assert int(lines[0].split()[3]) >= 100000, lines[0]      # tilings checked
+    assert lines[1].startswith("ok   placement:") and lines[-1] == "ok  : 0 failures", lines
+    assert not any(w in r.stderr for w in ("runtime error", "AddressSanitizer", "LeakSanitizer")), r.stderr[-3000:]
