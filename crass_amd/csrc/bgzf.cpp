@@ -1,4 +1,4 @@
-// bgzf.cpp — BGZF on the host: the walk over the members' headers and trailers (the restatement of bgzf_walk, ingest.cpp, that
+// bgzf.cpp — BGZF on the host: the walk over the members' headers and trailers (the restatement of bgzf_walk, host_inflate.cpp, that
 // also notes where every member's deflate data starts), and the inflate of inflate_core.h member after member: what the kernel
 // (inflate.hip) is tested against, itself tested against zlib.  Host-only C++17 that any compiler builds (tools/sanitize).
 #include "../../include/crass_hip.h"

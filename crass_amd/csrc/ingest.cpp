@@ -1,204 +1,10 @@
-// ingest.cpp — the ingest side of the boundary: 2-bit packer with an exception list,
-// FASTA/FASTQ(.gz) reader with kseq_read record semantics, and the deterministic synthetic
-// metagenome generator used by bench.py and the parity tests.  Host-only C++17 (+ zlib).
-#include "../../include/crass_hip.h"
-#include "pack_text.h"
+// ingest.cpp — the ingest side of the boundary, its first file: the 2-bit packer with an exception list.  The FASTA/FASTQ(.gz)
+// reader with kseq_read record semantics is fastx_parse.cpp (the parser), host_inflate.cpp and the three readers built on them
+// (fastx_read.cpp, fastx_index.cpp, fastx_stream.cpp); the synthetic metagenome of bench.py and the parity tests is synth.cpp.
+// Host-only C++17 (+ zlib); what crosses these files: host_ingest_internal.h.
+#include "host_ingest_internal.h"
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <memory>
-#include <new>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-#include <zlib.h>
-#include <immintrin.h>
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <sys/resource.h>
-#include <unistd.h>
-
-namespace {
-
-inline int base_code(uint8_t c)
-{
-    switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
-}
-
-struct PackedOwner {
-    std::vector<uint32_t> packed;
-    std::vector<uint64_t> word_off;
-    std::vector<uint32_t> lengths;
-    std::vector<uint64_t> exc_read, exc_off;
-    std::vector<uint8_t> exc_bytes;
-    std::vector<uint64_t> header_id;                   // (crass_hip_get_packed only)
-};
-
-}
-namespace crass { bool parallel_gunzip(const uint8_t *in, size_t n, uint8_t **out_p, size_t *out_n, unsigned threads); }      // pgzip.cpp
-namespace {
-unsigned hw_threads()
-{
-    unsigned n = std::thread::hardware_concurrency();
-    // (not limited to a cgroup CPU quota: the ingest is one short burst, and 64 threads for 70 ms beat 16 for 160 ms on
-    // the GPU box even though the quota there is 16 CPUs — the host pool, which polls for as long as a search runs, does
-    // follow the quota: merge.cpp)
-    return n ? n : 1;
-}
-
-template <typename F> void parallel_ranges(uint64_t n, unsigned nt, F f)
-{
-    if (nt <= 1 || n < 4096) { f(0, n, 0u); return; }
-    std::vector<std::thread> th;
-    uint64_t per = (n + nt - 1) / nt;
-    for (unsigned t = 0; t < nt; t++) {
-        uint64_t a = std::min<uint64_t>(n, t * per), b = std::min<uint64_t>(n, a + per);
-        if (a >= b) break;
-        th.emplace_back([=]() { f(a, b, t); });
-    }
-    for (auto &x : th) x.join();
-}
-
-// CPU seconds of the process so far (user + system): under a cgroup CPU quota a stage's wall time is its CPU seconds over the quota
-inline double cpu_seconds()
-{
-    struct rusage ru;
-    getrusage(RUSAGE_SELF, &ru);
-    return ru.ru_utime.tv_sec + 1e-6 * ru.ru_utime.tv_usec + ru.ru_stime.tv_sec + 1e-6 * ru.ru_stime.tv_usec;
-}
-
-// A large array that is written in full by many threads right after it is allocated: no value-initialisation (a std::vector's
-// resize() zero-fills — 2 GB of packed reads on ONE thread before the 64 that fill them start), 2 MB alignment and
-// MADV_HUGEPAGE where the kernel takes the hint (a first touch per 2 MB instead of per 4 KB: the page faults of the 3.4 GB of
-// arrays an index of 50 M reads allocates were most of its "words into place" second).
-// Giving gigabytes back: one munmap of 8 GB holds the address space's lock for a quarter of a second, and every other thread of
-// the process that touches a fresh page (the next stage's buffers) waits for it.  MADV_DONTNEED drops the pages under the SHARED
-// lock, slice by slice; the unmapping that follows finds nothing left to do.
-// Gigabytes at once go side by side: the kernel hands pages back (and clears them) at ~13 GB/s per thread in 4 KB pages, 27 GB/s in
-// 2 MB pages — 6 GB were 0.46 s on one thread, 0.11 s on sixteen (profiles/r06_exit_cost.txt); more threads than that meet on the
-// zone locks and are slower again.
-inline void drop_pages(void *p, size_t bytes)
-{
-    const size_t page = 4096, slice = 64u << 20;
-    const uintptr_t a0 = ((uintptr_t)p + page - 1) & ~(uintptr_t)(page - 1), e = ((uintptr_t)p + bytes) & ~(uintptr_t)(page - 1);
-    if (e <= a0) return;
-    const size_t ns = (e - a0 + slice - 1) / slice;
-    auto drop = [&](size_t q) { const uintptr_t a = a0 + q * slice; (void)madvise((void *)a, std::min<size_t>(slice, e - a), MADV_DONTNEED); };
-    const unsigned nt = (unsigned)std::min<size_t>(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u), ns / 2);
-    if (nt <= 1) { for (size_t q = 0; q < ns; q++) drop(q); return; }
-    std::atomic<size_t> next{0};
-    auto work = [&]() { for (;;) { const size_t q = next.fetch_add(1, std::memory_order_relaxed); if (q >= ns) break; drop(q); } };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
-
-// an array that is asked for again and again with about the same size: grown, never shrunk, not initialised
-template <typename T> struct KeepBuf {
-    T *p = nullptr; size_t cap = 0;
-    KeepBuf() = default;
-    KeepBuf(const KeepBuf &) = delete;
-    KeepBuf &operator=(const KeepBuf &) = delete;
-    ~KeepBuf() { free(p); }
-    T *ensure(size_t n) { if (n > cap) { free(p); cap = n + n / 8 + 64; p = (T *)malloc(cap * sizeof(T)); if (!p) cap = 0; } return p; }
-};
-
-template <typename T> struct RawBuf {
-    T *p = nullptr; size_t n = 0;
-    RawBuf() = default;
-    RawBuf(const RawBuf &) = delete;
-    RawBuf &operator=(const RawBuf &) = delete;
-    void release() { if (p && n * sizeof(T) >= (8u << 20)) drop_pages(p, n * sizeof(T)); free(p); p = nullptr; n = 0; }
-    ~RawBuf() { release(); }
-    bool alloc(size_t count)
-    {
-        release();
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        if (bytes >= (8u << 20)) {
-            const size_t al = 2u << 20, rounded = (bytes + al - 1) / al * al;
-            void *q = aligned_alloc(al, rounded);
-            if (!q) return false;
-            (void)madvise(q, rounded, MADV_HUGEPAGE);
-            p = (T *)q;
-        } else {
-            p = (T *)malloc(bytes);
-            if (!p) return false;
-        }
-        n = count;
-        return true;
-    }
-    T *data() { return p; }
-    const T *data() const { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-};
-
-// A per-record array a parser appends to without knowing its final size (a piece of an input: ~10^6 records).  A std::vector doubles
-// by allocate + copy + free: every doubling touches fresh pages, and what it frees stays in its thread's malloc arena (glibc's
-// mmap threshold moves up to 32 MB with the first large free) — 64 parsers left 1.8 GB of such arenas behind, resident until the
-// process's end.  This one is a mapping of its own from 1 MB on: grown by mremap (page tables move, no byte is copied or touched
-// again), MADV_HUGEPAGE, handed back to the kernel the moment it is released; no value-initialisation.
-template <typename T> struct GrowBuf {
-    T *p = nullptr; size_t n = 0, cap = 0;
-    bool mapped = false;
-    GrowBuf() = default;
-    GrowBuf(const GrowBuf &o) { assign(o); }
-    GrowBuf &operator=(const GrowBuf &o) { if (this != &o) { n = 0; assign(o); } return *this; }
-    GrowBuf(GrowBuf &&o) noexcept : p(o.p), n(o.n), cap(o.cap), mapped(o.mapped) { o.p = nullptr; o.n = o.cap = 0; o.mapped = false; }
-    GrowBuf &operator=(GrowBuf &&o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; cap = o.cap; mapped = o.mapped; o.p = nullptr; o.n = o.cap = 0; o.mapped = false; } return *this; }
-    ~GrowBuf() { release(); }
-    void release()
-    {
-        if (p) { if (mapped) munmap(p, cap * sizeof(T)); else free(p); }
-        p = nullptr; n = cap = 0; mapped = false;
-    }
-    // the pages go back under the address space's SHARED lock (several threads side by side); release() then unmaps nothing but
-    // page tables
-    void drop() { if (p && mapped) (void)madvise(p, cap * sizeof(T), MADV_DONTNEED); release(); }
-    void assign(const GrowBuf &o) { resize(o.n); if (o.n) memcpy(p, o.p, o.n * sizeof(T)); }
-    void grow(size_t want)
-    {
-        static const size_t kMap = 1u << 20, kHuge = 2u << 20;
-        size_t bytes = std::max<size_t>(std::max(want, cap * 2) * sizeof(T), 4096);
-        if (bytes < kMap) {
-            T *q = (T *)realloc(p, bytes);
-            if (!q) throw std::bad_alloc();
-            p = q; cap = bytes / sizeof(T);
-            return;
-        }
-        bytes = (bytes + kHuge - 1) / kHuge * kHuge;
-        void *q;
-        if (mapped) q = mremap(p, cap * sizeof(T), bytes, MREMAP_MAYMOVE);
-        else q = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (q == MAP_FAILED) throw std::bad_alloc();
-        (void)madvise(q, bytes, MADV_HUGEPAGE);
-        if (!mapped) { if (n) memcpy(q, p, n * sizeof(T)); free(p); mapped = true; }
-        p = (T *)q; cap = bytes / sizeof(T);
-    }
-    void push_back(const T &v) { if (n == cap) grow(n + 1); p[n++] = v; }
-    void resize(size_t m) { if (m > cap) grow(m); n = m; }           // (new elements are NOT initialised)
-    void clear() { n = 0; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    T *data() { return p; }
-    const T *data() const { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-};
-
-} // namespace
+using namespace crass;
 
 // the layout of a packed set: crass_pack_reads and the device packer (crass_hip_load_text, crass_hip_attach_device_text) decide here
 int crass::pack_layout(const uint64_t *off, uint64_t n, int pad_uniform, crass::PackLayout *out)
@@ -213,10 +19,17 @@ int crass::pack_layout(const uint64_t *off, uint64_t n, int pad_uniform, crass::
         min_len = std::min<uint32_t>(min_len, (uint32_t)l);
     }
     if (n == 0) min_len = 0;
-    const bool uniform_len = (n > 0 && max_len == min_len && max_len > 0);       // (uniform_len == 0 says "lengths differ": a set of empty reads keeps its lengths array)
-    uint32_t stride = 0;
     uint64_t tight = 0;
     for (uint64_t i = 0; i < n; i++) tight += (off[i + 1] - off[i] + 15) / 16;
+    crass::pack_layout_core(n, max_len, min_len, tight, pad_uniform, out);
+    return CRASS_OK;
+}
+
+// ... from what the offsets say: n reads of min_len .. max_len bases (min_len 0 where n is 0) in `tight` words when none is padded
+void crass::pack_layout_core(uint64_t n, uint32_t max_len, uint32_t min_len, uint64_t tight, int pad_uniform, crass::PackLayout *out)
+{
+    const bool uniform_len = (n > 0 && max_len == min_len && max_len > 0);       // (uniform_len == 0 says "lengths differ": a set of empty reads keeps its lengths array)
+    uint32_t stride = 0;
     if (pad_uniform == 2) {
         // auto: short reads of differing lengths (trimmed Illumina data) are padded to one stride when that costs at
         // most twice the words — the bit-parallel filter and the lane-per-read kernels need a uniform stride
@@ -226,7 +39,17 @@ int crass::pack_layout(const uint64_t *off, uint64_t n, int pad_uniform, crass::
     if (pad_uniform || uniform_len) stride = std::max<uint32_t>(1, (max_len + 15) / 16);
     out->max_len = max_len; out->stride_words = stride; out->uniform_len = uniform_len ? max_len : 0;
     out->total_words = stride ? n * (uint64_t)stride : tight;
-    return CRASS_OK;
+}
+
+void crass::fill_reads(crass_reads &r, uint64_t n, const crass::PackLayout &lay, const uint32_t *packed, const uint64_t *word_off, const uint32_t *lengths, const PackedOwner &exc)
+{
+    r.n_reads = n; r.packed = packed; r.stride_words = lay.stride_words;
+    r.word_off = lay.stride_words ? nullptr : word_off;
+    r.uniform_len = lay.uniform_len;
+    r.lengths = lay.uniform_len ? nullptr : lengths;
+    r.n_exceptions = exc.exc_read.size();
+    r.exc_read = exc.exc_read.data(); r.exc_off = exc.exc_off.data(); r.exc_bytes = exc.exc_bytes.data();
+    r.header_id = nullptr; r.read_index_base = 0;
 }
 
 int crass::packed_alloc(uint64_t n_words, uint64_t n_word_off, uint64_t n_lengths, uint64_t n_exc_read, uint64_t n_exc_off, uint64_t n_exc_bytes,
@@ -275,7 +98,7 @@ int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int p
     // (offsets that decrease have always been reported here as a read beyond the length limit)
     if (const int ls = crass::pack_layout(off, n, pad_uniform, &lay)) return ls == CRASS_ERR_INVALID_ARG ? CRASS_ERR_UNSUPPORTED : ls;
     PackedOwner *o = new PackedOwner();
-    const uint32_t max_len = lay.max_len, stride = lay.stride_words;
+    const uint32_t stride = lay.stride_words;
     const bool uniform_len = lay.uniform_len != 0;
     if (!stride) {
         o->word_off.resize(n + 1);
@@ -291,7 +114,7 @@ int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int p
     std::vector<std::vector<uint64_t>> exc_parts(nt);
     uint32_t *packed = o->packed.data();
     // byte -> 2-bit code, 0x80 for anything outside ACGT; one output word is built in a register per 16 bases
-    static const struct Lut { uint8_t t[256]; Lut() { memset(t, 0x80, sizeof(t)); t['A'] = 0; t['C'] = 1; t['G'] = 2; t['T'] = 3; } } lut;
+    const uint8_t *const lut = base_lut();
     parallel_ranges(n, nt, [&](uint64_t a, uint64_t b, unsigned t) {
         for (uint64_t i = a; i < b; i++) {
             const uint8_t *s = seqs + off[i];
@@ -301,12 +124,12 @@ int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int p
             uint32_t k = 0;
             for (; k + 16 <= L; k += 16) {
                 uint32_t acc = 0;
-                for (int q = 0; q < 16; q++) { const uint32_t c = lut.t[s[k + q]]; bad |= c; acc |= (c & 3u) << (2 * q); }
+                for (int q = 0; q < 16; q++) { const uint32_t c = lut[s[k + q]]; bad |= c; acc |= (c & 3u) << (2 * q); }
                 w[k >> 4] = acc;
             }
             if (k < L) {
                 uint32_t acc = 0;
-                for (uint32_t q = 0; k + q < L; q++) { const uint32_t c = lut.t[s[k + q]]; bad |= c; acc |= (c & 3u) << (2 * q); }
+                for (uint32_t q = 0; k + q < L; q++) { const uint32_t c = lut[s[k + q]]; bad |= c; acc |= (c & 3u) << (2 * q); }
                 w[k >> 4] = acc;
             }
             if (bad & 0x80u) exc_parts[t].push_back(i);
@@ -319,14 +142,7 @@ int crass_pack_reads(const uint8_t *seqs, const uint64_t *off, uint64_t n, int p
         o->exc_bytes.insert(o->exc_bytes.end(), seqs + off[r], seqs + off[r + 1]);
         o->exc_off.push_back(o->exc_bytes.size());
     }
-    crass_reads &r = out->reads;
-    r.n_reads = n; r.packed = o->packed.data(); r.stride_words = stride;
-    r.word_off = stride ? nullptr : o->word_off.data();
-    r.uniform_len = uniform_len ? max_len : 0;
-    r.lengths = uniform_len ? nullptr : o->lengths.data();
-    r.n_exceptions = o->exc_read.size();
-    r.exc_read = o->exc_read.data(); r.exc_off = o->exc_off.data(); r.exc_bytes = o->exc_bytes.data();
-    r.header_id = nullptr; r.read_index_base = 0;
+    fill_reads(out->reads, n, lay, o->packed.data(), o->word_off.data(), o->lengths.data(), *o);
     out->owner = o;
     return CRASS_OK;
 }
@@ -336,1822 +152,6 @@ void crass_free_packed(crass_packed *p)
     if (!p) return;
     delete static_cast<PackedOwner *>(p->owner);
     memset(p, 0, sizeof(*p));
-}
-
-// ---- FASTA/FASTQ reader: kseq_read record semantics (kseq.cpp:171-226) as driven by
-// searchFile (libcrispr.cpp:96-131).  The whole (decompressed) file is parsed from memory, in parallel:
-// the buffer is cut at guessed record starts, every piece is parsed by the same byte-exact state machine, and
-// the pieces are accepted only if each one ends exactly where the next one began (otherwise — odd layouts,
-// truncated files — the file is parsed again in one piece).  The reference's reader is single-threaded and
-// byte-at-a-time; on the 800 MB / 5 M-read FASTA of tools/e2e_cli.sh it was 99 % of the wall time.
-static bool is_space(int c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
-
-namespace {
-
-struct FxChunk {
-    std::vector<uint8_t> seq, name, comment, qual;                      // concatenated fields of the records parsed here
-    std::vector<uint64_t> seq_end, name_end, comment_end, qual_end;     // local end offsets per record
-    std::vector<uint8_t> own_c, own_q;                                  // the record carried its own comment / quality
-    uint32_t max_len = 0;
-    size_t next_start = 0;     // index of the header char of the first record NOT parsed here
-    size_t last_hdr = 0;       // index of the header char of the LAST record parsed here (streaming: a chunk's last record is re-read)
-    GrowBuf<uint64_t> hdr_pos;                                          // index of every record's header char (crass_index_fastx)
-    // pack mode (crass_index_fastx): a record's sequence is 2-bit packed the moment it is complete — while its bytes are still in
-    // the cache — and its text dropped; seq / name / comment / qual stay empty, seq_end / name_end count virtual bytes (the
-    // lengths), the name is kept as a hash
-    bool pack = false;
-    GrowBuf<uint32_t> words;                                            // the records' words, tightly packed (ceil(L/16) each)
-    GrowBuf<uint64_t> name_h;                                           // name_hash() of every record's name
-    // (pack mode keeps 24 bytes per record beside its words — header position, name hash, the two lengths — and the comment /
-    // quality flags per piece: the eight per-record vectors of the other mode were 50 bytes, 2.5 GB for 50 M reads, written by the
-    // parsers and freed again — 0.4 s on one thread — before the reads had even been looked at)
-    GrowBuf<uint32_t> len32, nlen32;                                    // sequence / name length of every record
-    uint8_t pk_flags = 12;                                              // bit 0 any comment, 1 any quality, 2 all comment, 3 all quality
-    uint32_t pk_min_len = 0xFFFFFFFFu;
-    std::vector<uint64_t> exc_rec, exc_off;                             // local indices of reads with a byte outside ACGT, ends in exc_bytes
-    std::vector<uint8_t> exc_bytes;
-    uint64_t v_seq = 0, v_name = 0;
-    bool ended = false;        // kseq_read returned < 0 inside this range
-    int last_ret = -1;         // ... with this value
-    size_t n_rec() const { return pack ? len32.size() : seq_end.size(); }
-    // as new, with the vectors' memory kept (a stream parses chunk after chunk into the same pieces: 64 MB of vectors allocated and
-    // given back per chunk were most of a chunk's time outside its parse)
-    void reset(bool pk)
-    {
-        seq.clear(); name.clear(); comment.clear(); qual.clear(); seq_end.clear(); name_end.clear(); comment_end.clear(); qual_end.clear();
-        own_c.clear(); own_q.clear(); hdr_pos.clear(); words.clear(); name_h.clear(); len32.clear(); nlen32.clear();
-        exc_rec.clear(); exc_off.clear(); exc_bytes.clear();
-        max_len = 0; next_start = 0; last_hdr = 0; pack = pk; pk_flags = 12; pk_min_len = 0xFFFFFFFFu; v_seq = 0; v_name = 0; ended = false; last_ret = -1;
-    }
-};
-
-uint64_t name_hash(const uint8_t *p, size_t n);
-// L bases -> ceil(L/16) words (A0 C1 G2 T3, base i in bits 2(i%16) of word i/16); true when a byte outside ACGT was met (it
-// packs as A: the read is an exception read and its slot's content is ignored).  Eight bases per step: the code of a letter is
-// ((c >> 1) & 3) with the two upper values exchanged, the letter a code stands for is rebuilt (0x41 + 2 b0 + 6 b1 + 11 b0 b1)
-// and compared with what was read
-// 32 bases per step (AVX2, where the CPU has it): the code as above, checked by looking the letter up again (pshufb) and comparing;
-// four codes become a byte through two multiply-adds (t0 + 4 t1, then + 16 (t2 + 4 t3)), the bytes of a 128-bit half are its word.
-// The parsers of an index are bound by CPU seconds, not threads (a 16-CPU quota on a 256-thread host): packing was a quarter of
-// the 130 ns they spent per 150-base record.
-__attribute__((target("avx2"))) inline uint32_t pack_bases_avx2(const uint8_t *s, uint32_t L, uint32_t *w, uint64_t &bad)
-{
-    const __m256i three = _mm256_set1_epi8(3), one = _mm256_set1_epi8(1);
-    const __m256i letters = _mm256_setr_epi8('A', 'C', 'G', 'T', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 'A', 'C', 'G', 'T', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
-    const __m256i pick = _mm256_setr_epi8(0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
-    __m256i ok = _mm256_set1_epi8(-1);
-    uint32_t k = 0;
-    for (; k + 32 <= L; k += 32) {
-        const __m256i x = _mm256_loadu_si256((const __m256i *)(s + k));
-        __m256i t = _mm256_and_si256(_mm256_srli_epi16(x, 1), three);
-        t = _mm256_xor_si256(t, _mm256_and_si256(_mm256_srli_epi16(t, 1), one));
-        ok = _mm256_and_si256(ok, _mm256_cmpeq_epi8(_mm256_shuffle_epi8(letters, t), x));
-        const __m256i p2 = _mm256_maddubs_epi16(t, _mm256_set1_epi16(0x0401));            // t0 + 4 t1 per 16-bit lane
-        const __m256i p4 = _mm256_madd_epi16(p2, _mm256_set1_epi32(0x00100001));           // + 16 (t2 + 4 t3) per 32-bit lane
-        const __m256i by = _mm256_shuffle_epi8(p4, pick);
-        w[k >> 4] = (uint32_t)_mm256_cvtsi256_si32(by);
-        w[(k >> 4) + 1] = (uint32_t)_mm256_extract_epi32(by, 4);
-    }
-    if (_mm256_movemask_epi8(ok) != -1) bad |= 1;
-    return k;
-}
-
-// The common record's sequence line in ONE pass: 32 bytes are loaded, looked at for the line's end and packed (the line's length
-// comes out of the same loads memchr would have made).  true: the line was pure ACGT up to a '\n' at p[*len] and its words have
-// been appended to `words` (the tail past the last base is zero); false: anything else — a byte outside ACGT, no line end within
-// `avail - 32` bytes — with `words` as it was: the caller's general path takes the record.
-__attribute__((target("avx2"))) inline bool pack_line_avx2(const uint8_t *p, size_t avail, GrowBuf<uint32_t> &words, size_t *len)
-{
-    alignas(32) static const uint8_t lane_mask[64] = {255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255,
-                                                      255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const __m256i three = _mm256_set1_epi8(3), one = _mm256_set1_epi8(1), nl = _mm256_set1_epi8('\n');
-    const __m256i letters = _mm256_setr_epi8('A', 'C', 'G', 'T', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 'A', 'C', 'G', 'T', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
-    const __m256i pick = _mm256_setr_epi8(0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
-    const size_t w0 = words.size();
-    size_t k = 0;
-    for (;; k += 32) {
-        if (k + 32 > avail || k >= (1u << 30)) { words.resize(w0); return false; }
-        const size_t wi = w0 + (k >> 4);
-        if (wi + 2 > words.cap) { words.n = wi; words.grow(wi + 2); }
-        const __m256i x = _mm256_loadu_si256((const __m256i *)(p + k));
-        const uint32_t nlm = (uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(x, nl));
-        __m256i t = _mm256_and_si256(_mm256_srli_epi16(x, 1), three);
-        t = _mm256_xor_si256(t, _mm256_and_si256(_mm256_srli_epi16(t, 1), one));
-        const uint32_t okm = (uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(_mm256_shuffle_epi8(letters, t), x));
-        uint32_t rem = 32;
-        if (nlm) {
-            rem = (uint32_t)__builtin_ctz(nlm);
-            const uint32_t lm = (1u << rem) - 1u;
-            if ((okm & lm) != lm) { words.resize(w0); return false; }
-            t = _mm256_and_si256(t, _mm256_loadu_si256((const __m256i *)(lane_mask + 32 - rem)));
-        } else if (okm != 0xFFFFFFFFu) { words.resize(w0); return false; }
-        const __m256i p2 = _mm256_maddubs_epi16(t, _mm256_set1_epi16(0x0401));
-        const __m256i p4 = _mm256_madd_epi16(p2, _mm256_set1_epi32(0x00100001));
-        const __m256i by = _mm256_shuffle_epi8(p4, pick);
-        words.p[wi] = (uint32_t)_mm256_cvtsi256_si32(by);
-        words.p[wi + 1] = (uint32_t)_mm256_extract_epi32(by, 4);
-        if (nlm) { *len = k + rem; words.n = w0 + (k + rem + 15) / 16; return true; }
-    }
-}
-
-inline bool pack_bases(const uint8_t *s, uint32_t L, uint32_t *w)
-{
-    uint64_t bad = 0;
-    uint32_t k = 0;
-    static const bool have_avx2 = __builtin_cpu_supports("avx2") && !getenv("CRASS_NO_AVX2");
-    if (have_avx2 && L >= 32) k = pack_bases_avx2(s, L, w, bad);
-    for (; k + 16 <= L; k += 16) {
-        uint32_t word = 0;
-        for (int half = 0; half < 2; half++) {
-            uint64_t x;
-            memcpy(&x, s + k + 8 * half, 8);
-            uint64_t t = (x >> 1) & 0x0303030303030303ull;
-            t ^= (t >> 1) & 0x0101010101010101ull;
-            const uint64_t b0 = t & 0x0101010101010101ull, b1 = (t >> 1) & 0x0101010101010101ull, b01 = b0 & b1;
-            const uint64_t recon = 0x4141414141414141ull + 2 * b0 + 6 * b1 + 11 * b01;
-            bad |= recon ^ x;
-            t = (t | (t >> 6)) & 0x000F000F000F000Full;
-            t = (t | (t >> 12)) & 0x000000FF000000FFull;
-            t = (t | (t >> 24)) & 0xFFFFull;
-            word |= (uint32_t)t << (16 * half);
-        }
-        w[k >> 4] = word;
-    }
-    if (k < L) {
-        static const struct Lut { uint8_t t[256]; Lut() { memset(t, 0x80, sizeof(t)); t['A'] = 0; t['C'] = 1; t['G'] = 2; t['T'] = 3; } } lut;
-        uint32_t acc = 0, b = 0;
-        for (uint32_t q = 0; k + q < L; q++) { const uint32_t cc = lut.t[s[k + q]]; b |= cc; acc |= (cc & 3u) << (2 * q); }
-        w[k >> 4] = acc;
-        if (b & 0x80u) bad |= 1;
-    }
-    return bad != 0;
-}
-
-// Parses the records whose header character ('>' / '@') lies in [start, limit).  `start` indexes a header
-// character unless scan_first (then the parser looks for the first one, as kseq_read does at the beginning).
-void parse_range(const uint8_t *data, size_t n, size_t start, size_t limit, bool scan_first, FxChunk &o)
-{
-    size_t pos = start;
-    int last_char = 0;
-    if (!scan_first) { last_char = data[start]; pos = start + 1; }
-    for (;;) {
-        size_t hdr;
-        if (last_char == 0) {
-            while (pos < n && data[pos] != '>' && data[pos] != '@') pos++;
-            if (pos >= n) { o.ended = true; o.last_ret = -1; o.next_start = n; return; }
-            hdr = pos;
-            if (hdr >= limit) { o.next_start = hdr; return; }
-            last_char = data[pos++];
-        } else {
-            hdr = pos - 1;
-            if (hdr >= limit) { o.next_start = hdr; return; }
-        }
-        if (pos >= n) { o.ended = true; o.last_ret = -1; o.next_start = n; return; }      // ks_getuntil < 0 at EOF
-        size_t st = pos;
-        if (pos + 16 <= n) {                              // (the name's end — the first isspace() byte — sixteen bytes at a look)
-            const __m128i x = _mm_loadu_si128((const __m128i *)(data + pos));
-            const __m128i sp = _mm_or_si128(_mm_cmpeq_epi8(x, _mm_set1_epi8(' ')),
-                                            _mm_cmpeq_epi8(_mm_min_epu8(_mm_sub_epi8(x, _mm_set1_epi8('\t')), _mm_set1_epi8(4)), _mm_sub_epi8(x, _mm_set1_epi8('\t'))));
-            const unsigned m = (unsigned)_mm_movemask_epi8(sp);
-            pos += m ? (size_t)__builtin_ctz(m) : 16;
-        }
-        while (pos < n && !is_space(data[pos])) pos++;
-        const size_t name_st = st, name_len = pos - st;
-        int c = pos < n ? data[pos] : -1;
-        pos++;
-        bool own_c = false;
-        size_t com_st = 0, com_len = 0;
-        if (c != -1 && c != '\n') {
-            st = pos;
-            const void *nl = pos < n ? memchr(data + pos, '\n', n - pos) : nullptr;
-            pos = nl ? (size_t)((const uint8_t *)nl - data) : n;
-            com_st = st; com_len = std::min(pos, n) - st;
-            own_c = true;
-            pos++;
-        }
-        const size_t seq_base = o.seq.size();
-        c = -1;
-        // pack mode, the common record: the sequence on ONE line of pure ACGT with the next header (or the '+' line) right behind
-        // it — packed straight from the mapping (pack_bases also tells whether a byte was anything else: then the general
-        // path below takes the record from the same position, as it does for wrapped lines, the last record and odd spacing)
-        bool packed_in_place = false;
-        size_t fast_len = 0;
-        const size_t words_base = o.words.size();       // (a record that turns out truncated takes its words back)
-        static const bool line_avx2 = __builtin_cpu_supports("avx2") && !getenv("CRASS_NO_AVX2");
-        if (o.pack && pos < n && line_avx2) {
-            size_t len = 0;
-            if (pack_line_avx2(data + pos, n - pos, o.words, &len)) {
-                const size_t nx = pos + len + 1;
-                if (len && nx < n && (data[nx] == '>' || data[nx] == '@' || data[nx] == '+')) { packed_in_place = true; fast_len = len; c = data[nx]; pos = nx + 1; }
-                else o.words.resize(words_base);
-            }
-        } else if (o.pack && pos < n) {
-            const uint8_t *p = data + pos;
-            const void *nlp = memchr(p, '\n', n - pos);
-            if (nlp) {
-                const size_t len = (size_t)((const uint8_t *)nlp - p), nx = pos + len + 1;
-                if (len && len < (1u << 30) && nx < n && (data[nx] == '>' || data[nx] == '@' || data[nx] == '+')) {
-                    const size_t w0 = o.words.size(), nw = (len + 15) / 16;
-                    o.words.resize(w0 + nw);
-                    if (!pack_bases(p, (uint32_t)len, o.words.data() + w0)) { packed_in_place = true; fast_len = len; c = data[nx]; pos = nx + 1; }
-                    else o.words.resize(w0);
-                }
-            }
-        }
-        while (!packed_in_place && pos < n) {
-            // fast path: a run of sequence bytes up to the end of the line.  The line's end comes from memchr; the bytes before
-            // it are then checked eight at a time against a table of the bytes that END such a run ('>', '+', '@', anything
-            // outside 33..126) — a sequence line has none, and one that does is walked byte by byte as before
-            const uint8_t *p = data + pos, *e = data + n;
-            const uint8_t *q = p;
-            {
-                static const struct Stop { uint8_t t[256]; Stop() { for (int i = 0; i < 256; i++) t[i] = (i < 33 || i > 126 || i == '>' || i == '+' || i == '@') ? 1 : 0; } } stop;
-                const void *nlp = memchr(p, '\n', (size_t)(e - p));
-                const uint8_t *le = nlp ? (const uint8_t *)nlp : e;
-                const uint8_t *x = p;
-                uint32_t bad = 0;
-                for (; x + 8 <= le; x += 8)
-                    bad |= stop.t[x[0]] | stop.t[x[1]] | stop.t[x[2]] | stop.t[x[3]] | stop.t[x[4]] | stop.t[x[5]] | stop.t[x[6]] | stop.t[x[7]];
-                for (; x < le; x++) bad |= stop.t[*x];
-                if (!bad) q = le;
-            }
-            while (q < e && *q != '\n' && *q != '>' && *q != '+' && *q != '@' && *q >= 33 && *q <= 126) q++;
-            if (q > p) { o.seq.insert(o.seq.end(), p, q); pos += (size_t)(q - p); if (pos >= n) break; }
-            c = data[pos++];
-            if (c == '>' || c == '+' || c == '@') break;
-            if (c >= 33 && c <= 126) o.seq.push_back((uint8_t)c);       // isgraph
-            c = -1;
-        }
-        const size_t sq_len = packed_in_place ? fast_len : o.seq.size() - seq_base;
-        if (c == '>' || c == '@') last_char = c;
-        bool own_q = false;
-        const size_t qual_base = o.qual.size();
-        if (c == '+') {
-            const void *nl = pos < n ? memchr(data + pos, '\n', n - pos) : nullptr;
-            if (!nl) { o.seq.resize(seq_base); o.words.resize(words_base); o.ended = true; o.last_ret = -2; o.next_start = n; return; }
-            pos = (size_t)((const uint8_t *)nl - data) + 1;
-            // `while ((c = ks_getc(ks)) != -1 && seq->qual.l < seq->seq.l)`: consumes one byte past the quality
-            size_t ql = 0;
-            // the common record: the quality string on ONE line, as long as the sequence, every byte in 33 .. 127 — checked eight
-            // bytes at a time and taken as a block (pack mode: not taken at all); the byte behind it is the one kseq's loop consumes
-            if (sq_len && pos + sq_len < n && data[pos + sq_len] == '\n') {
-                const uint8_t *q = data + pos;
-                const uint64_t H = 0x8080808080808080ull, L21 = 0x2121212121212121ull;
-                uint64_t bad = 0;
-                size_t i = 0;
-                for (; i + 8 <= sq_len; i += 8) { uint64_t x; memcpy(&x, q + i, 8); bad |= (~((x | H) - L21) | x) & H; }
-                for (; i < sq_len; i++) bad |= (uint64_t)(q[i] < 33 || q[i] > 127);
-                if (!bad) {
-                    if (!o.pack) o.qual.insert(o.qual.end(), q, q + sq_len);
-                    ql = sq_len;
-                    pos += sq_len + 1;
-                }
-            }
-            if (sq_len == 0 && pos < n) pos++;                           // (an empty sequence: the loop's one look still consumes a byte)
-            while (ql < sq_len && pos < n) {
-                const int ch = data[pos++];
-                if (ch >= 33 && ch <= 127) { o.qual.push_back((uint8_t)ch); ql++; }
-                if (!(ql < sq_len)) { if (pos < n) pos++; break; }       // (... and one byte past the quality)
-            }
-            last_char = 0;
-            if (ql != sq_len) { o.seq.resize(seq_base); o.qual.resize(qual_base); o.words.resize(words_base); o.ended = true; o.last_ret = -2; o.next_start = n; return; }
-            own_q = true;
-        }
-        o.last_hdr = hdr;
-        if (o.pack) {
-            o.hdr_pos.push_back(hdr);                     // (the index's: the whole-file and streamed readers never read it — 8 bytes per record)
-            if (!packed_in_place) {
-                const size_t w0 = o.words.size(), nw = (sq_len + 15) / 16;
-                o.words.resize(w0 + nw);
-                if (pack_bases(o.seq.data() + seq_base, (uint32_t)sq_len, o.words.data() + w0)) {
-                    o.exc_rec.push_back(o.len32.size());
-                    o.exc_bytes.insert(o.exc_bytes.end(), o.seq.begin() + seq_base, o.seq.end());
-                    o.exc_off.push_back(o.exc_bytes.size());
-                }
-                o.seq.resize(seq_base);
-            }
-            o.qual.resize(qual_base);
-            o.v_seq += sq_len; o.v_name += name_len;
-            o.name_h.push_back(name_hash(data + name_st, name_len));
-            o.len32.push_back((uint32_t)sq_len); o.nlen32.push_back((uint32_t)name_len);
-            if (own_c) o.pk_flags |= 1; else o.pk_flags &= (uint8_t)~4;
-            if (own_q) o.pk_flags |= 2; else o.pk_flags &= (uint8_t)~8;
-            o.pk_min_len = std::min<uint32_t>(o.pk_min_len, (uint32_t)sq_len);
-        } else {
-            o.name.insert(o.name.end(), data + name_st, data + name_st + name_len); o.name_end.push_back(o.name.size());
-            o.seq_end.push_back(o.seq.size());
-            if (own_c) o.comment.insert(o.comment.end(), data + com_st, data + com_st + com_len);
-            o.comment_end.push_back(o.comment.size());
-            o.qual_end.push_back(o.qual.size());
-        }
-        if (!o.pack) { o.own_c.push_back(own_c ? 1 : 0); o.own_q.push_back(own_q ? 1 : 0); }
-        o.max_len = std::max<uint32_t>(o.max_len, (uint32_t)sq_len);
-        if (c == -1 && pos >= n) { o.ended = true; o.last_ret = -1; o.next_start = n; return; }
-    }
-}
-
-// first plausible record start at or after `from`: a line that starts with the file's header character
-// (FASTQ: and whose line after next starts with '+', which tells a header from a quality line)
-size_t guess_start(const uint8_t *data, size_t n, size_t from, bool fastq)
-{
-    size_t p = from;
-    while (p < n) {
-        const void *nl = memchr(data + p, '\n', n - p);
-        if (!nl) return n;
-        const size_t cand = (size_t)((const uint8_t *)nl - data) + 1;
-        if (cand >= n) return n;
-        if (!fastq) { if (data[cand] == '>') return cand; }
-        else if (data[cand] == '@') {
-            const void *l1 = memchr(data + cand, '\n', n - cand);
-            if (l1) {
-                const size_t s2 = (size_t)((const uint8_t *)l1 - data) + 1;
-                const void *l2 = s2 < n ? memchr(data + s2, '\n', n - s2) : nullptr;
-                if (l2) { const size_t s3 = (size_t)((const uint8_t *)l2 - data) + 1; if (s3 < n && data[s3] == '+') return cand; }
-            }
-        }
-        p = cand;
-    }
-    return n;
-}
-
-uint64_t name_hash(const uint8_t *p, size_t n)
-{
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ (n * 0xD6E8FEB86659FD93ull);
-    while (n >= 8) { uint64_t v; memcpy(&v, p, 8); h = (h ^ v) * 0xFF51AFD7ED558CCDull; h ^= h >> 32; p += 8; n -= 8; }
-    if (n) { uint64_t v = 0; memcpy(&v, p, n); h = (h ^ v) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 29; }
-    return h ^ (h >> 31);
-}
-
-} // namespace
-
-namespace {
-// Whole-buffer gzip inflate through libdeflate when the runtime library is present (no header in the image: the four
-// entry points are bound by hand): about 3x zlib's streaming inflate, which is what bounds a .gz input end to end.
-// Members are decompressed one after the other like gzread does (SeqUtils.cpp:100-126 opens every input through
-// gzopen).  Any surprise — no library, damaged data, trailing garbage — returns false and the zlib path below decides.
-struct InflatedBuf {
-    uint8_t *p = nullptr; size_t n = 0;
-    ~InflatedBuf() { free(p); }
-};
-// BGZF (bgzip; Illumina's bcl2fastq / BCL Convert write their .fastq.gz this way): a series of gzip members of at most 64 KB, each
-// announcing its own compressed size in an extra field ('B' 'C', RFC 1952 2.3.1.1) and its text size in its last four bytes — the
-// members' places in the input AND in the output are known without inflating anything, so they can be inflated side by side (a
-// plain gzip stream is one member: 0.7 GB/s of text on one thread, which is what bounds a .gz input end to end).
-// ioff / ooff: member b is in[ioff[b], ioff[b+1]) and inflates to out[ooff[b], ooff[b+1]).  false: not (entirely) BGZF.
-bool bgzf_walk(const uint8_t *in, size_t csz, std::vector<uint64_t> &ioff, std::vector<uint64_t> &ooff)
-{
-    size_t p = 0;
-    uint64_t o = 0;
-    while (p < csz) {
-        if (csz - p < 28) return false;                   // 12 + 6 header bytes, at least 2 of deflate data, 8 of trailer
-        if (in[p] != 0x1f || in[p + 1] != 0x8b || in[p + 2] != 8 || !(in[p + 3] & 4)) return false;
-        const size_t xlen = (size_t)in[p + 10] | ((size_t)in[p + 11] << 8);
-        if (p + 12 + xlen > csz) return false;
-        size_t total = 0;
-        for (size_t q = p + 12; q + 4 <= p + 12 + xlen;) {
-            const size_t slen = (size_t)in[q + 2] | ((size_t)in[q + 3] << 8);
-            if (in[q] == 'B' && in[q + 1] == 'C' && slen == 2 && q + 6 <= p + 12 + xlen) total = ((size_t)in[q + 4] | ((size_t)in[q + 5] << 8)) + 1;
-            q += 4 + slen;
-        }
-        if (total < 12 + xlen + 10 || p + total > csz) return false;
-        uint32_t isz;
-        memcpy(&isz, in + p + total - 4, 4);
-        if (isz > 65536u) return false;
-        ioff.push_back(p); ooff.push_back(o);
-        p += total; o += isz;
-    }
-    ioff.push_back(p); ooff.push_back(o);
-    return ioff.size() > 1;
-}
-
-bool inflate_with_libdeflate(const char *path, InflatedBuf &out)
-{
-    typedef void *(*alloc_fn)(void);
-    typedef int (*gz_fn)(void *, const void *, size_t, void *, size_t, size_t *, size_t *);
-    typedef void (*free_fn)(void *);
-    static void *lib = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-    if (!lib || getenv("CRASS_NO_LIBDEFLATE")) return false;
-    static const alloc_fn d_alloc = (alloc_fn)dlsym(lib, "libdeflate_alloc_decompressor");
-    static const gz_fn d_gzip = (gz_fn)dlsym(lib, "libdeflate_gzip_decompress_ex");
-    static const free_fn d_free = (free_fn)dlsym(lib, "libdeflate_free_decompressor");
-    if (!d_alloc || !d_gzip || !d_free) return false;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return false;
-    struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 18) { close(fd); return false; }
-    const size_t csz = (size_t)st.st_size;
-    void *m = mmap(nullptr, csz, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-    close(fd);
-    if (m == MAP_FAILED) return false;
-    const uint8_t *in = (const uint8_t *)m;
-    {
-        std::vector<uint64_t> ioff, ooff;
-        if (!getenv("CRASS_NO_BGZF") && bgzf_walk(in, csz, ioff, ooff) && ioff.size() > 64) {
-            const size_t nb = ioff.size() - 1;
-            // (2 MB-aligned, MADV_HUGEPAGE: a gigabyte of first touches in 4 KB pages is a good part of what is left)
-            const size_t al = 2u << 20, bytes = ((size_t)ooff[nb] + 1 + al - 1) / al * al;
-            uint8_t *buf = (uint8_t *)aligned_alloc(al, bytes);
-            if (buf) (void)madvise(buf, bytes, MADV_HUGEPAGE);
-            std::atomic<int> bad{buf ? 0 : 1};
-            if (buf) {
-                const unsigned nt = (unsigned)std::min<size_t>(std::min<unsigned>(hw_threads(), 32u), nb / 32);
-                auto run = [&](unsigned t) {
-                    void *dec = d_alloc();
-                    if (!dec) { bad.store(1); return; }
-                    for (size_t b = nb * t / nt; b < nb * (t + 1) / nt && !bad.load(std::memory_order_relaxed); b++) {
-                        size_t ain = 0, aout = 0;
-                        const size_t want = (size_t)(ooff[b + 1] - ooff[b]);
-                        const int res = d_gzip(dec, in + ioff[b], (size_t)(ioff[b + 1] - ioff[b]), buf + ooff[b], want, &ain, &aout);
-                        if (res != 0 || aout != want) bad.store(1);
-                    }
-                    d_free(dec);
-                };
-                std::vector<std::thread> th;
-                for (unsigned t = 1; t < nt; t++) th.emplace_back(run, t);
-                run(0);
-                for (auto &x : th) x.join();
-            }
-            if (!bad.load()) {
-                if (getenv("CRASS_TIMING")) fprintf(stderr, "[crass_timing] inflate: BGZF, %zu members (%zu -> %llu bytes) side by side\n", nb, csz, (unsigned long long)ooff[nb]);
-                munmap(m, csz); out.p = buf; out.n = (size_t)ooff[nb]; return true;
-            }
-            free(buf);                                    // (a member that is not what its header says: the serial path decides)
-        }
-    }
-    bool pg_fits = true;
-    {
-        // (its symbols are two bytes per byte of text, held beside the text: only where three times the text — about four times the
-        // file each — fits half of the available memory)
-        uint64_t avail = 0;
-        if (FILE *fp = fopen("/proc/meminfo", "r")) {
-            char line[256];
-            while (fgets(line, sizeof(line), fp)) if (!strncmp(line, "MemAvailable:", 13)) { avail = (uint64_t)atoll(line + 13) << 10; break; }
-            fclose(fp);
-        }
-        // (the text: the trailer's ISIZE where it can be believed — a single member below 4 GB of text —, else eight times the file:
-        // FASTA and quality-binned FASTQ compress 6-8 x, and a guess of four let the several-thread inflate start on hosts where
-        // three times the real text did not fit)
-        uint32_t isz = 0;
-        memcpy(&isz, in + csz - 4, 4);
-        const uint64_t text = (csz < (1ull << 29) && (uint64_t)isz >= csz) ? (uint64_t)isz : (uint64_t)csz * 8;
-        if (avail && text * 3 > avail / 2) pg_fits = false;
-    }
-    if (pg_fits && !getenv("CRASS_NO_PGZIP")) {
-        // one member, large: inflated by several threads from block starts found in the middle of the stream (pgzip.cpp); its own
-        // checks (length, CRC-32) decide, and anything it does not take comes back here
-        uint8_t *pb = nullptr; size_t pn = 0;
-        const double tp0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        if (crass::parallel_gunzip(in, csz, &pb, &pn, std::min<unsigned>(hw_threads(), 16u))) {
-            if (getenv("CRASS_TIMING")) fprintf(stderr, "[crass_timing] inflate: one member, %zu -> %zu bytes on several threads, %.3f s\n", csz, pn,
-                                                std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tp0);
-            munmap(m, csz);
-            out.p = pb; out.n = pn;
-            return true;
-        }
-    }
-    uint32_t isize;                                       // size of the last member modulo 2^32: a first guess only
-    memcpy(&isize, in + csz - 4, 4);
-    size_t cap = std::max<size_t>((size_t)isize, csz * 3) + (1u << 20);
-    uint8_t *buf = (uint8_t *)malloc(cap);
-    // the output's pages are touched by other threads AHEAD of the one thread that inflates: first touches of a gigabyte (the kernel
-    // clears every page) were a good part of the inflate's time on that thread
-    std::atomic<bool> stop_touch{false};
-    std::vector<std::thread> touchers;
-    if (buf && cap >= (64u << 20) && !getenv("CRASS_NO_PREFAULT")) {
-        const unsigned nt = std::min<unsigned>(std::max(1u, hw_threads() / 2), 8u);
-        const size_t page = 4096;
-        uint8_t *const base = (uint8_t *)(((uintptr_t)buf + page - 1) / page * page);
-        const size_t span = (size_t)((buf + cap) - base) / page * page;
-        for (unsigned t = 0; t < nt; t++)
-            touchers.emplace_back([&, t, nt, base, span] {
-                // (interleaved 64 MB stripes, in output order: whoever is ahead of the inflater is useful)
-                // MADV_POPULATE_WRITE (Linux 5.14): the pages are made present and writable, their content is not touched — a page the
-                // inflater got to first keeps what it wrote
-                const size_t stripe = 16u << 20;
-                for (size_t s0 = (size_t)t * stripe; s0 < span && !stop_touch.load(std::memory_order_relaxed); s0 += (size_t)nt * stripe)
-                    if (madvise(base + s0, std::min(stripe, span - s0), 23 /* MADV_POPULATE_WRITE */) != 0) break;
-            });
-    }
-    struct JoinTouch { std::atomic<bool> &stop; std::vector<std::thread> &th; ~JoinTouch() { stop.store(true); for (auto &x : th) x.join(); } } join_touch{stop_touch, touchers};
-    void *dec = d_alloc();
-    bool ok = buf && dec;
-    size_t ipos = 0, opos = 0;
-    while (ok && ipos < csz) {
-        size_t ain = 0, aout = 0;
-        const int res = d_gzip(dec, in + ipos, csz - ipos, buf + opos, cap - opos, &ain, &aout);
-        if (res == 3) {                                   // LIBDEFLATE_INSUFFICIENT_SPACE: grow and repeat this member
-            const size_t ncap = cap * 2;
-            stop_touch.store(true);
-            for (auto &x : touchers) x.join();
-            touchers.clear();
-            uint8_t *nb = (uint8_t *)realloc(buf, ncap);
-            if (!nb) { ok = false; break; }
-            buf = nb; cap = ncap;
-            continue;
-        }
-        if (res != 0 || ain == 0) { ok = false; break; }
-        ipos += ain; opos += aout;
-    }
-    if (dec) d_free(dec);
-    munmap(m, csz);
-    if (!ok) { free(buf); return false; }
-    out.p = buf; out.n = opos;
-    return true;
-}
-} // namespace
-
-namespace {
-// the (decompressed) text d[0, n) cut into pieces at guessed record starts, every piece parsed by parse_range on its own thread;
-// accepted only if each piece ends exactly where the next one began, else parsed again in one piece (exact by construction)
-void parse_pieces(const uint8_t *d, size_t n, std::vector<FxChunk> &ch, size_t piece_bytes = 8u << 20, bool pack = false)
-{
-    size_t chunk_bytes = piece_bytes;
-    if (const char *e = getenv("CRASS_FASTX_CHUNK")) chunk_bytes = (size_t)std::max(64ll, atoll(e));     // tests: force small pieces
-    unsigned nt = (unsigned)std::min<size_t>(std::min<unsigned>(hw_threads(), 64u), n / chunk_bytes);
-    if (getenv("CRASS_FASTX_SERIAL")) nt = 1;
-    std::vector<size_t> starts{0};
-    if (nt > 1) {
-        size_t first = 0;
-        while (first < n && d[first] != '>' && d[first] != '@') first++;
-        const bool fastq = first < n && d[first] == '@';
-        for (unsigned k = 1; k < nt; k++) {
-            const size_t g = guess_start(d, n, std::max(starts.back(), (size_t)((unsigned __int128)n * k / nt)), fastq);
-            if (g >= n) break;
-            if (g > starts.back()) starts.push_back(g);
-        }
-    }
-    ch.resize(starts.size());
-    for (auto &c : ch) c.reset(pack);
-    auto run = [&](size_t k) { parse_range(d, n, starts[k], k + 1 < starts.size() ? starts[k + 1] : n, k == 0, ch[k]); };
-    if (starts.size() == 1) run(0);
-    else {
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < starts.size(); k++) th.emplace_back(run, k);
-        run(0);
-        for (auto &t : th) t.join();
-        bool ok = true;
-        for (size_t k = 0; k + 1 < starts.size() && ok; k++) ok = !ch[k].ended && ch[k].next_start == starts[k + 1];
-        if (!ok) {                                       // a guess was wrong or the stream ended early: one piece, exact
-            ch.assign(1, FxChunk());
-            ch[0].pack = pack;
-            parse_range(d, n, 0, n, true, ch[0]);
-        }
-    }
-}
-} // namespace
-
-int crass_read_fastx(const char *path, crass_fastx *out)
-{
-    if (!path || !out) return CRASS_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    const double tr0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    std::vector<uint8_t> data;
-    InflatedBuf inflated;
-    struct Mapping {                                     // plain text is parsed straight from the page cache
-        void *p = nullptr; size_t n = 0;
-        ~Mapping() { if (p && n) munmap(p, n); }
-    } map;
-    {
-        FILE *f = fopen(path, "rb");
-        if (!f) return CRASS_ERR_IO;
-        unsigned char magic[2] = {0, 0};
-        const size_t got2 = fread(magic, 1, 2, f);
-        const bool gz = got2 == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        if (!gz) {
-            fseek(f, 0, SEEK_END);
-            const long sz = ftell(f);
-            fseek(f, 0, SEEK_SET);
-            if (sz < 0) { fclose(f); return CRASS_ERR_IO; }
-            void *m = sz ? mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fileno(f), 0) : nullptr;
-            if (sz && m != MAP_FAILED) { map.p = m; map.n = (size_t)sz; }
-            else {                                       // (pipes, odd file systems): one read of the whole file
-                data.resize((size_t)sz);
-                if (sz && fread(data.data(), 1, (size_t)sz, f) != (size_t)sz) { fclose(f); return CRASS_ERR_IO; }
-            }
-            fclose(f);
-        } else if (inflate_with_libdeflate(path, inflated)) {
-            fclose(f);
-        } else {
-            fclose(f);
-            gzFile fp = gzopen(path, "r");
-            if (!fp) return CRASS_ERR_IO;
-            gzbuffer(fp, 1 << 20);
-            std::vector<uint8_t> buf(4 << 20);
-            int got;
-            while ((got = gzread(fp, buf.data(), (unsigned)buf.size())) > 0) data.insert(data.end(), buf.begin(), buf.begin() + got);
-            gzclose(fp);
-            if (got < 0) return CRASS_ERR_IO;
-        }
-    }
-    const bool timing = getenv("CRASS_TIMING") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tr1 = now_s();
-    const size_t n = map.p ? map.n : inflated.p ? inflated.n : data.size();
-    const uint8_t *d = map.p ? (const uint8_t *)map.p : inflated.p ? inflated.p : data.data();
-    std::vector<FxChunk> ch;
-    parse_pieces(d, n, ch);
-    const double tr2 = now_s();
-    // the pieces hold their own copies of everything: the file image goes before the record arrays are allocated
-    // (peak host memory = pieces + record arrays, not file + pieces + record arrays)
-    if (map.p && map.n) { munmap(map.p, map.n); map.p = nullptr; map.n = 0; }
-    free(inflated.p); inflated.p = nullptr; inflated.n = 0;
-    std::vector<uint8_t>().swap(data);
-    // ---- assemble ----
-    const size_t nc = ch.size();
-    std::vector<uint64_t> rec0(nc + 1, 0), seq0(nc + 1, 0), name0(nc + 1, 0), com0(nc + 1, 0), qual0(nc + 1, 0);
-    bool any_c = false, all_c = true, any_q = false, all_q = true;
-    uint32_t max_len = 0;
-    for (size_t k = 0; k < nc; k++) {
-        rec0[k + 1] = rec0[k] + ch[k].n_rec(); seq0[k + 1] = seq0[k] + ch[k].seq.size(); name0[k + 1] = name0[k] + ch[k].name.size();
-        com0[k + 1] = com0[k] + ch[k].comment.size(); qual0[k + 1] = qual0[k] + ch[k].qual.size();
-        for (uint8_t v : ch[k].own_c) { any_c |= v != 0; all_c &= v != 0; }
-        for (uint8_t v : ch[k].own_q) { any_q |= v != 0; all_q &= v != 0; }
-        max_len = std::max(max_len, ch[k].max_len);
-    }
-    const uint64_t nrec = rec0[nc];
-    auto alloc8 = [](uint64_t nb) { return (uint8_t *)malloc(nb + 1); };
-    auto alloc64 = [](uint64_t ne) { return (uint64_t *)malloc((ne + 1) * 8); };
-    out->n_reads = nrec;
-    out->seq = alloc8(seq0[nc]); out->seq_off = alloc64(nrec + 1);
-    out->name = alloc8(name0[nc]); out->name_off = alloc64(nrec + 1);
-    out->has_comment = alloc8(nrec); out->has_qual = alloc8(nrec);
-    out->comment_off = alloc64(nrec + 1); out->qual_off = alloc64(nrec + 1);
-    out->header_id = alloc64(nrec);
-    out->seq_off[0] = out->name_off[0] = out->comment_off[0] = out->qual_off[0] = 0;
-    // comments / qualities: every record its own, or none at all, is a plain concatenation; a mix follows the
-    // reference's stale-buffer semantics (once allocated, comment.s / qual.s keep their old bytes and searchFile
-    // passes them on, libcrispr.cpp:124-131) in one ordered pass
-    const bool simple_c = !any_c || all_c, simple_q = !any_q || all_q;
-    out->comment = simple_c ? alloc8(com0[nc]) : nullptr;
-    out->qual = simple_q ? alloc8(qual0[nc]) : nullptr;
-    auto copy_chunk = [&](size_t k) {
-        const FxChunk &c = ch[k];
-        if (!c.seq.empty()) memcpy(out->seq + seq0[k], c.seq.data(), c.seq.size());
-        if (!c.name.empty()) memcpy(out->name + name0[k], c.name.data(), c.name.size());
-        if (simple_c && !c.comment.empty()) memcpy(out->comment + com0[k], c.comment.data(), c.comment.size());
-        if (simple_q && !c.qual.empty()) memcpy(out->qual + qual0[k], c.qual.data(), c.qual.size());
-        for (size_t i = 0; i < c.n_rec(); i++) {
-            const uint64_t r = rec0[k] + i;
-            out->seq_off[r + 1] = seq0[k] + c.seq_end[i];
-            out->name_off[r + 1] = name0[k] + c.name_end[i];
-            if (simple_c) { out->comment_off[r + 1] = com0[k] + c.comment_end[i]; out->has_comment[r] = any_c ? 1 : 0; }
-            if (simple_q) { out->qual_off[r + 1] = qual0[k] + c.qual_end[i]; out->has_qual[r] = any_q ? 1 : 0; }
-        }
-    };
-    if (nc == 1) copy_chunk(0);
-    else {
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < nc; k++) th.emplace_back(copy_chunk, k);
-        copy_chunk(0);
-        for (auto &t : th) t.join();
-    }
-    auto ordered_stale = [&](bool comment) {
-        std::vector<uint8_t> bytes;
-        std::string stale;
-        bool any = false;
-        uint8_t *has = comment ? out->has_comment : out->has_qual;
-        uint64_t *off = comment ? out->comment_off : out->qual_off;
-        for (size_t k = 0; k < nc; k++) {
-            const FxChunk &c = ch[k];
-            const std::vector<uint8_t> &src = comment ? c.comment : c.qual;
-            const std::vector<uint64_t> &end = comment ? c.comment_end : c.qual_end;
-            const std::vector<uint8_t> &own = comment ? c.own_c : c.own_q;
-            for (size_t i = 0; i < c.n_rec(); i++) {
-                const uint64_t r = rec0[k] + i;
-                if (own[i]) { const uint64_t b0 = i ? end[i - 1] : 0; stale.assign((const char *)src.data() + b0, end[i] - b0); any = true; }
-                has[r] = any ? 1 : 0;
-                if (any) bytes.insert(bytes.end(), stale.begin(), stale.end());
-                off[r + 1] = bytes.size();
-            }
-        }
-        uint8_t *p = (uint8_t *)malloc(bytes.size() + 1);
-        if (!bytes.empty()) memcpy(p, bytes.data(), bytes.size());
-        if (comment) out->comment = p; else out->qual = p;
-    };
-    if (!simple_c) ordered_stale(true);
-    if (!simple_q) ordered_stale(false);
-    const int last_ret_of_stream = ch.back().last_ret;
-    std::vector<FxChunk>().swap(ch);                    // (and the pieces before the header table is built)
-    const double tr3 = now_s();
-    // ---- header_id: first read with the same name (readsFound is keyed by the header string) ----
-    {
-        // one 64-bit word per slot: (32-bit hash tag | 1) << 32 | index of the first read with that name; a tag match
-        // is confirmed by comparing the names, so two names never share a slot
-        size_t cap = 1024;
-        while (cap * 10 < nrec * 14) cap <<= 1;                  // load <= ~0.7
-        std::unique_ptr<std::atomic<uint64_t>[]> tab(new std::atomic<uint64_t>[cap]);
-        std::vector<uint64_t> slot_of(nrec);
-        const unsigned ht = (unsigned)std::min<uint64_t>(hw_threads(), std::max<uint64_t>(1, nrec / 65536));
-        parallel_ranges(cap, ht, [&](uint64_t a, uint64_t b2, unsigned) { for (uint64_t i = a; i < b2; i++) tab[i].store(0, std::memory_order_relaxed); });
-        auto same_name = [&](uint64_t x, uint64_t y) {
-            const uint64_t lx = out->name_off[x + 1] - out->name_off[x], ly = out->name_off[y + 1] - out->name_off[y];
-            return lx == ly && memcmp(out->name + out->name_off[x], out->name + out->name_off[y], lx) == 0;
-        };
-        parallel_ranges(nrec, ht, [&](uint64_t a, uint64_t b2, unsigned) {
-            for (uint64_t r = a; r < b2; r++) {
-                const uint64_t h = name_hash(out->name + out->name_off[r], out->name_off[r + 1] - out->name_off[r]);
-                const uint64_t tag = ((h >> 32) | 1ull) << 32;
-                size_t i = (size_t)h & (cap - 1);
-                for (;;) {
-                    uint64_t cur = tab[i].load(std::memory_order_acquire);
-                    if (cur == 0) {
-                        if (tab[i].compare_exchange_strong(cur, tag | r, std::memory_order_acq_rel)) break;      // claimed
-                    }
-                    if ((cur & 0xFFFFFFFF00000000ull) == tag && same_name((uint64_t)(uint32_t)cur, r)) {
-                        while ((uint32_t)cur > r && !tab[i].compare_exchange_weak(cur, tag | r, std::memory_order_acq_rel)) {}
-                        break;
-                    }
-                    i = (i + 1) & (cap - 1);
-                }
-                slot_of[r] = i;
-            }
-        });
-        parallel_ranges(nrec, ht, [&](uint64_t a, uint64_t b2, unsigned) {
-            for (uint64_t r = a; r < b2; r++) out->header_id[r] = (uint32_t)tab[slot_of[r]].load(std::memory_order_relaxed);
-        });
-        // the table stays with the records: crass_fastx_find() resolves a header name without a second index
-        out->name_index = (uint64_t *)malloc(cap * sizeof(uint64_t));
-        out->name_index_cap = out->name_index ? cap : 0;
-        if (out->name_index)
-            parallel_ranges(cap, ht, [&](uint64_t a, uint64_t b2, unsigned) { for (uint64_t i = a; i < b2; i++) out->name_index[i] = tab[i].load(std::memory_order_relaxed); });
-    }
-    out->max_len = max_len;
-    out->last_ret = last_ret_of_stream;
-    if (timing)
-        fprintf(stderr, "[crass_timing] fastx: %zu bytes, %zu pieces: read %.3f s, parse %.3f s, assemble %.3f s, header ids %.3f s\n", n, nc,
-                tr1 - tr0, tr2 - tr1, tr3 - tr2, now_s() - tr3);
-    return CRASS_OK;
-}
-
-void crass_free_fastx(crass_fastx *f)
-{
-    if (!f) return;
-    free(f->seq); free(f->seq_off); free(f->name); free(f->name_off); free(f->comment); free(f->comment_off);
-    free(f->has_comment); free(f->qual); free(f->qual_off); free(f->has_qual); free(f->header_id); free(f->name_index);
-    memset(f, 0, sizeof(*f));
-}
-
-uint64_t crass_fastx_find(const crass_fastx *f, const char *name, uint64_t len)
-{
-    if (!f || !f->name_index || !f->name_index_cap) return UINT64_MAX;
-    const uint64_t h = name_hash((const uint8_t *)name, (size_t)len);
-    const uint64_t tag = ((h >> 32) | 1ull) << 32, cap = f->name_index_cap;
-    for (uint64_t i = h & (cap - 1);; i = (i + 1) & (cap - 1)) {
-        const uint64_t cur = f->name_index[i];
-        if (cur == 0) return UINT64_MAX;
-        if ((cur & 0xFFFFFFFF00000000ull) == tag) {
-            const uint64_t r = (uint32_t)cur;
-            if (f->name_off[r + 1] - f->name_off[r] == len && memcmp(f->name + f->name_off[r], name, (size_t)len) == 0) return r;
-        }
-    }
-}
-
-// ---- the same reader as an INDEX over the file image (plain-text inputs) ----
-// What the device wants from an input is its reads as 2-bit words; what the hand-off wants is the TEXT of the ~1 % of reads that
-// are handed on.  crass_read_fastx builds every record's text as arrays (3.6 bytes of host memory per byte of input while it
-// assembles them, and a serial share — page faults of 1.6 GB of fresh arrays, the ordered header table — that is larger than the
-// parallel parse).  The index keeps the file mapped and, per record, the position of its header character: the pieces are parsed
-// by the same state machine, each piece packs its own records into the job's word array at once and drops its text, the header
-// table compares names in the mapping itself, and crass_fastx_index_fetch parses the few records that are handed on, again with
-// the same state machine, when they are asked for.  gzip'd inputs and files that mix records with and without a comment /
-// quality line (kseq's stale-buffer semantics need the records in order) are left to the two readers above: CRASS_ERR_UNSUPPORTED.
-struct crass_fastx_index {
-    // the text: per input a mapped file or, for a gzip'd input, its inflated image.  A record's header position is kept as a position
-    // in the inputs' concatenation (base = the bytes of the inputs before it)
-    struct File {
-        void *map = nullptr; size_t n = 0; uint8_t *own = nullptr;     // own: the inflated image (then map points at it)
-        int fd = -1;                                                   // a plain file stays open: its mapping goes when the index is built, the
-                                                                       // handed-on records are read from the file (crass_fastx_index_fetch)
-        uint64_t base = 0;
-        bool any_c = false, any_q = false;
-        int last_ret = -1;
-    };
-    std::vector<File> files;
-    const File &file_of(uint64_t pos) const
-    {
-        size_t f = files.size() - 1;
-        while (f > 0 && files[f].base > pos) f--;
-        return files[f];
-    }
-    const uint8_t *text(uint64_t pos) const { const File &f = file_of(pos); return (const uint8_t *)f.map + (pos - f.base); }
-    RawBuf<uint64_t> hdr_pos;                          // [n]
-    RawBuf<uint32_t> packed; RawBuf<uint64_t> word_off; RawBuf<uint32_t> lengths;
-    PackedOwner pk;                                    // (the exception lists)
-    RawBuf<uint64_t> header_id;                        // [n] or empty (all names unique)
-    crass_reads reads{};
-    uint32_t max_len = 0;
-    int last_ret = -1;
-    ~crass_fastx_index()
-    {
-        for (File &f : files) {
-            if (f.own) { drop_pages(f.own, f.n); free(f.own); }
-            else if (f.map && f.n) { drop_pages(f.map, f.n); munmap(f.map, f.n); }
-            if (f.fd >= 0) close(f.fd);
-        }
-    }
-};
-
-extern "C" {
-
-int crass_index_fastx(const char *path, crass_fastx_index **out) { return crass_index_fastx_files(&path, 1, out); }
-
-int crass_index_fastx_files(const char *const *paths, uint32_t n_paths, crass_fastx_index **out)
-{
-    if (!paths || !n_paths || !out) return CRASS_ERR_INVALID_ARG;
-    for (uint32_t f = 0; f < n_paths; f++) if (!paths[f]) return CRASS_ERR_INVALID_ARG;
-    *out = nullptr;
-    const bool timing = getenv("CRASS_TIMING") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now_s();
-    std::unique_ptr<crass_fastx_index> ix(new (std::nothrow) crass_fastx_index());
-    if (!ix) return CRASS_ERR_OOM;
-    ix->files.resize(n_paths);
-    // every input opened on its own thread: a gzip'd one is a single-threaded inflate (0.7 GB/s of text), and paired-end files are two
-    std::vector<int> frc(n_paths, CRASS_OK);
-    auto open_one = [&](uint32_t f) {
-        crass_fastx_index::File &F = ix->files[f];
-        const int fd = open(paths[f], O_RDONLY);
-        if (fd < 0) { frc[f] = CRASS_ERR_IO; return; }
-        struct stat st;
-        if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); frc[f] = CRASS_ERR_UNSUPPORTED; return; }
-        const size_t fn = (size_t)st.st_size;
-        unsigned char magic[2] = {0, 0};
-        const bool gz = fn >= 2 && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        if (gz) {
-            // a gzip'd input: its inflated image takes the mapping's place (libdeflate, whole buffer; without the library the
-            // whole-file reader's zlib path takes the input).  1 x the text + the packed reads instead of the whole-file reader's
-            // ~3.6 x, and none of its assemble / pack passes
-            // (only if the text — about four times the file — fits half of what this host has available: the bounded readers otherwise)
-            uint64_t avail = 0;
-            if (FILE *fp = fopen("/proc/meminfo", "r")) {
-                char line[256];
-                while (fgets(line, sizeof(line), fp)) if (!strncmp(line, "MemAvailable:", 13)) { avail = (uint64_t)atoll(line + 13) << 10; break; }
-                fclose(fp);
-            }
-            close(fd);
-            if (avail && (uint64_t)fn * 4 * n_paths > avail / 2) { frc[f] = CRASS_ERR_UNSUPPORTED; return; }
-            InflatedBuf inflated;
-            if (!inflate_with_libdeflate(paths[f], inflated)) { frc[f] = CRASS_ERR_UNSUPPORTED; return; }
-            F.own = inflated.p; F.map = inflated.p; F.n = inflated.n;
-            inflated.p = nullptr;
-        } else {
-            if (fn) {
-                // (no MAP_POPULATE: one thread filling 2 M page-table entries was 0.25 s for 8 GB; the 64 piece parsers take the
-                // faults of their own pieces)
-                void *m = mmap(nullptr, fn, PROT_READ, MAP_PRIVATE, fd, 0);
-                if (m == MAP_FAILED) { close(fd); frc[f] = CRASS_ERR_UNSUPPORTED; return; }
-                (void)madvise(m, fn, MADV_WILLNEED);
-                F.map = m; F.n = fn;
-            }
-            F.fd = fd;
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (uint32_t f = 1; f < n_paths; f++) th.emplace_back(open_one, f);
-        open_one(0);
-        for (auto &t : th) t.join();
-    }
-    for (uint32_t f = 0; f < n_paths; f++) if (frc[f] == CRASS_ERR_IO) return CRASS_ERR_IO;
-    for (uint32_t f = 0; f < n_paths; f++) if (frc[f] != CRASS_OK) return frc[f];
-    size_t n = 0;                                        // bytes of text, all inputs
-    for (uint32_t f = 0; f < n_paths; f++) { ix->files[f].base = n; n += ix->files[f].n; }
-    const double t1 = now_s(), c1 = cpu_seconds();
-    // every input parsed in pieces (pack mode: every record is packed as it is parsed, its text dropped); the pieces of all inputs in
-    // (input, position) order are the job's reads in (file, read) order
-    std::vector<FxChunk> ch;
-    std::vector<uint32_t> piece_file;
-    for (uint32_t f = 0; f < n_paths; f++) {
-        crass_fastx_index::File &F = ix->files[f];
-        std::vector<FxChunk> cf;
-        parse_pieces((const uint8_t *)F.map, F.n, cf, 8u << 20, true);
-        bool any_c = false, all_c = true, any_q = false, all_q = true;
-        for (FxChunk &c : cf) {                         // (the pieces kept their own comment / quality flags)
-            const uint8_t fl = c.pk_flags;
-            if (c.n_rec()) { any_c |= (fl & 1) != 0; any_q |= (fl & 2) != 0; all_c &= (fl & 4) != 0; all_q &= (fl & 8) != 0; }
-        }
-        if ((any_c && !all_c) || (any_q && !all_q)) return CRASS_ERR_UNSUPPORTED;      // stale comment / quality buffers: ordered readers
-        F.any_c = any_c; F.any_q = any_q; F.last_ret = cf.empty() ? -1 : cf.back().last_ret;
-        for (FxChunk &c : cf) { ch.emplace_back(std::move(c)); piece_file.push_back(f); }
-    }
-    const double t2 = now_s(), c2 = cpu_seconds();
-    const size_t nc = ch.size();
-    std::vector<uint64_t> rec0(nc + 1, 0), tight0(nc + 1, 0);
-    uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
-    for (size_t k = 0; k < nc; k++) {                    // (the pieces kept their own minimum length)
-        rec0[k + 1] = rec0[k] + ch[k].n_rec(); tight0[k + 1] = tight0[k] + ch[k].words.size();
-        max_len = std::max(max_len, ch[k].max_len); min_len = std::min(min_len, ch[k].pk_min_len);
-    }
-    if (max_len > CRASS_HIP_MAX_READ_LEN) return CRASS_ERR_UNSUPPORTED;
-    const uint64_t nrec = rec0[nc];
-    if (nrec == 0) min_len = 0;
-    ix->max_len = max_len; ix->last_ret = ix->files.back().last_ret;
-    // ---- layout: crass_pack_reads' rules (mode 2); the pieces' words are then copied into place ----
-    const bool uniform_len = nrec > 0 && max_len == min_len && max_len > 0;       // (uniform_len == 0 says "lengths differ": a set of empty reads keeps its lengths array)
-    const uint64_t padded = nrec * (uint64_t)((max_len + 15) / 16);
-    const bool pad = max_len <= 256 && max_len >= 64 && padded <= 2 * tight0[nc];
-    const uint32_t stride = (uniform_len || pad) ? std::max<uint32_t>(1, (max_len + 15) / 16) : 0;
-    PackedOwner &o = ix->pk;
-    RawBuf<uint32_t> name_len;
-    // shards of the header table (below): by the hash's top 12 bits — ~12 k names per shard for 50 M reads, a 256 KB table that
-    // stays in the filling core's L2 (256 shards of 4 MB tables spent 0.12 s on L3 / memory latency; CRASS_HDR_SHARD_BITS: the A/B)
-    unsigned shard_bits = nrec >= (1u << 22) ? 12 : 8;
-    if (const char *e = getenv("CRASS_HDR_SHARD_BITS")) shard_bits = (unsigned)std::min(14, std::max(1, atoi(e)));
-    const unsigned SH = 1u << shard_bits, shard_shift = 64 - shard_bits, low_shift = shard_shift - 32;
-    std::vector<uint64_t> cnt(nc * (size_t)SH, 0);     // [piece][shard]: records of the piece whose name hash starts with the shard's byte
-    const size_t n_words = (size_t)(stride ? nrec * (uint64_t)stride + 4 : tight0[nc] + 4);
-    // (no zero fill: the pieces write every word they own, pad words included)
-    if (!ix->packed.alloc(n_words) || (!stride && !ix->word_off.alloc(nrec + 1)) || (!uniform_len && !ix->lengths.alloc(nrec)) ||
-        !ix->hdr_pos.alloc(nrec) || !name_len.alloc(nrec)) return CRASS_ERR_OOM;
-    // the per-record arrays first (the header table below needs them), then the words — 2 GB for 50 M reads, most of this
-    // stage's time — on their own threads BESIDE the header table: both are bound by memory, neither by the other's data
-    uint32_t *packed = ix->packed.data();
-    {
-        auto place_small = [&](size_t k) {
-            FxChunk &c = ch[k];
-            const size_t m = c.n_rec();
-            if (m) {
-                const uint64_t fb = ix->files[piece_file[k]].base;
-                uint64_t *hp = ix->hdr_pos.data() + rec0[k];
-                for (size_t i = 0; i < m; i++) hp[i] = fb + c.hdr_pos[i];
-                uint64_t *cs = cnt.data() + k * SH;         // (the header table's counting pass: the hashes are read here anyway)
-                const uint64_t *nhk = c.name_h.data();
-                for (size_t i = 0; i < m; i++) cs[nhk[i] >> shard_shift]++;
-            }
-            uint64_t wat = 0;
-            for (size_t i = 0; i < m; i++) {
-                const uint64_t r = rec0[k] + i;
-                const uint32_t L = c.len32[i];
-                name_len[r] = c.nlen32[i];
-                if (!uniform_len) ix->lengths[r] = L;
-                if (!stride) ix->word_off[r] = tight0[k] + wat;
-                wat += (L + 15) / 16;
-            }
-            // (the pieces' arrays go with the pieces, at the end: sixty-four threads unmapping at once, here, meet on the address
-            // space's lock — 0.08 s; the name hashes are read once more, by the header table's scatter)
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < nc; k++) th.emplace_back(place_small, k);
-        if (nc) place_small(0);
-        for (auto &t : th) t.join();
-        if (!stride) ix->word_off[nrec] = tight0[nc];
-    }
-    auto place_words = [&](size_t k) {
-        FxChunk &c = ch[k];
-        if (uniform_len) { if (!c.words.empty()) memcpy(packed + rec0[k] * (uint64_t)stride, c.words.data(), c.words.size() * 4); }
-        else if (!stride) { if (!c.words.empty()) memcpy(packed + tight0[k], c.words.data(), c.words.size() * 4); }
-        else {                                           // padded to one stride
-            uint64_t wat = 0;
-            for (size_t i = 0; i < c.n_rec(); i++) {
-                const uint32_t L = c.len32[i];
-                const uint32_t nw = (L + 15) / 16;
-                uint32_t *w = packed + (rec0[k] + i) * (uint64_t)stride;
-                memcpy(w, c.words.data() + wat, (size_t)nw * 4);
-                for (uint32_t x = nw; x < stride; x++) w[x] = 0;
-                wat += nw;
-            }
-        }
-    };
-    double t_words = 0;
-    std::thread words_thread([&]() {
-        const double tw0 = now_s();
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < nc; k++) th.emplace_back(place_words, k);
-        if (nc) place_words(0);
-        for (auto &t : th) t.join();
-        for (size_t x = 0; x < 4; x++) ix->packed[n_words - 4 + x] = 0;
-        t_words = now_s() - tw0;
-    });
-    struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_words{words_thread};
-    o.exc_off.push_back(0);
-    for (size_t k = 0; k < nc; k++) {
-        const uint64_t base = o.exc_bytes.size();
-        for (uint64_t e : ch[k].exc_rec) o.exc_read.push_back(rec0[k] + e);
-        o.exc_bytes.insert(o.exc_bytes.end(), ch[k].exc_bytes.begin(), ch[k].exc_bytes.end());
-        for (uint64_t e : ch[k].exc_off) o.exc_off.push_back(base + e);
-    }
-    const double t3 = now_s();
-    // ---- header_id: first read with the same name, names compared in the mapping (exact) ----
-    // SHARDED by the hash's top byte: one table for 50 M names is 1 GB of random compare-and-swaps (0.7 s on the box's 16 CPUs);
-    // 256 shards of ~200 k names each fit a cache-resident table, are filled by ONE thread each — in read order, so the first
-    // occurrence is simply the first insert, no atomics — and are independent.  Records reach their shard by a stable counting
-    // sort of the record indices (two streaming passes over the hashes).
-    bool any_dup = false;
-    double th_ph[4] = {t3, t3, t3, t3};
-    RawBuf<uint32_t> order, order_h;                     // (released behind the words' placement, below: not beside it)
-    if (nrec) {
-        if (nrec >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
-        const unsigned ht = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<unsigned>(hw_threads(), 64u), nrec / 65536));
-        // order_h: the hashes in shard order too — the 32 bits below the shard's — so that the shard's thread reads them in a stream
-        // (looked up per record they were 50 M cache misses, most of this stage)
-        if (!order.alloc(nrec) || !order_h.alloc(nrec)) return CRASS_ERR_OOM;
-        th_ph[0] = now_s();
-        // (counted per piece while the record arrays were placed, above: no pass of its own, and no job-wide copy of the hashes)
-        th_ph[1] = now_s();
-        std::vector<uint64_t> sh_begin(SH + 1, 0);
-        {   // shard-major, piece-minor: a shard's records stay in read order
-            uint64_t at = 0;
-            for (unsigned sh = 0; sh < SH; sh++) {
-                sh_begin[sh] = at;
-                for (size_t k = 0; k < nc; k++) { const uint64_t c = cnt[k * SH + sh]; cnt[k * SH + sh] = at; at += c; }
-            }
-            sh_begin[SH] = at;
-        }
-        {
-            std::atomic<size_t> next_piece{0};
-            auto scatter = [&]() {
-                for (;;) {
-                    const size_t k = next_piece.fetch_add(1, std::memory_order_relaxed);
-                    if (k >= nc) break;
-                    uint64_t *c = cnt.data() + k * SH;
-                    const uint64_t *nhk = ch[k].name_h.data();
-                    const size_t m = ch[k].n_rec();
-                    for (size_t i = 0; i < m; i++) { const uint64_t h = nhk[i], at = c[h >> shard_shift]++; order[at] = (uint32_t)(rec0[k] + i); order_h[at] = (uint32_t)(h >> low_shift); }
-                }
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < std::min<size_t>(ht, nc); t++) th.emplace_back(scatter);
-            scatter();
-            for (auto &x : th) x.join();
-        }
-        th_ph[2] = now_s();
-        auto same_name = [&](uint64_t x, uint64_t y) {
-            return name_len[x] == name_len[y] && memcmp(ix->text(ix->hdr_pos[x]) + 1, ix->text(ix->hdr_pos[y]) + 1, name_len[x]) == 0;
-        };
-        std::atomic<unsigned> next_shard{0};
-        std::mutex dup_mu;
-        std::vector<std::pair<uint32_t, uint32_t>> dups;
-        {
-            std::vector<std::thread> th;
-            auto work = [&]() {
-                std::vector<uint64_t> tab;                // (tag | record index + 1), 0 = empty
-                std::vector<std::pair<uint32_t, uint32_t>> mine;      // (record, the first record of its name): the repeats only — a
-                                                          // first[] entry written per record was 50 M scattered cache lines
-                for (;;) {
-                    const unsigned sh = next_shard.fetch_add(1, std::memory_order_relaxed);
-                    if (sh >= SH) break;
-                    const uint64_t m = sh_begin[sh + 1] - sh_begin[sh];
-                    if (!m) continue;
-                    size_t cap = 1024;
-                    while (cap * 10 < m * 16) cap <<= 1;
-                    tab.assign(cap, 0);
-                    for (uint64_t q = sh_begin[sh]; q < sh_begin[sh + 1]; q++) {
-                        const uint64_t r = order[q];
-                        const uint64_t tag = (uint64_t)order_h[q] << 32;          // the 32 hash bits below the shard's
-                        size_t i = (size_t)order_h[q] & (cap - 1);
-                        for (;;) {
-                            const uint64_t cur = tab[i];
-                            if (cur == 0) { tab[i] = tag | (r + 1); break; }
-                            if ((cur & 0xFFFFFFFF00000000ull) == tag && same_name((uint32_t)cur - 1u, r)) { mine.emplace_back((uint32_t)r, (uint32_t)cur - 1u); break; }
-                            i = (i + 1) & (cap - 1);
-                        }
-                    }
-                }
-                if (!mine.empty()) { std::lock_guard<std::mutex> lk(dup_mu); dups.insert(dups.end(), mine.begin(), mine.end()); }
-            };
-            for (unsigned t = 1; t < ht; t++) th.emplace_back(work);
-            work();
-            for (auto &x : th) x.join();
-        }
-        th_ph[3] = now_s();
-        any_dup = !dups.empty();
-        if (any_dup) {
-            if (!ix->header_id.alloc(nrec)) return CRASS_ERR_OOM;
-            parallel_ranges(nrec, ht, [&](uint64_t a2, uint64_t b2, unsigned) { for (uint64_t r = a2; r < b2; r++) ix->header_id[r] = r; });
-            for (const auto &d : dups) ix->header_id[d.first] = d.second;
-        }
-    }
-    const double t_hdr = now_s() - t3;
-    words_thread.join();
-    const double t4 = now_s();
-    order.release(); order_h.release();
-    // (the pieces — 3.4 GB of per-record arrays and words for 50 M reads — are handed back here, over sixteen threads: their pages
-    // dropped under the shared lock side by side, ~25 ms.  One thread doing it beside whatever the caller does next took 0.15 s and
-    // the caller's host-to-device copy, which pins its source through the same address-space lock, waited for it)
-    {
-        std::atomic<size_t> next_piece{0};
-        auto drop = [&]() {
-            for (;;) {
-                const size_t k = next_piece.fetch_add(1, std::memory_order_relaxed);
-                if (k >= nc) break;
-                FxChunk &c = ch[k];
-                c.words.drop(); c.hdr_pos.drop(); c.name_h.drop(); c.len32.drop(); c.nlen32.drop();
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < std::min<size_t>(std::min<unsigned>(hw_threads(), 16u), nc); t++) th.emplace_back(drop);
-        drop();
-        for (auto &x : th) x.join();
-        std::vector<FxChunk>().swap(ch);
-    }
-    crass_reads &r = ix->reads;
-    r.n_reads = nrec; r.packed = ix->packed.data(); r.stride_words = stride;
-    r.word_off = stride ? nullptr : ix->word_off.data();
-    r.uniform_len = uniform_len ? max_len : 0;
-    r.lengths = uniform_len ? nullptr : ix->lengths.data();
-    r.n_exceptions = o.exc_read.size();
-    r.exc_read = o.exc_read.data(); r.exc_off = o.exc_off.data(); r.exc_bytes = o.exc_bytes.data();
-    r.header_id = any_dup ? ix->header_id.data() : nullptr; r.read_index_base = 0;
-    if (timing)
-        fprintf(stderr, "[crass_timing] fastx index: %zu bytes, %zu pieces, %llu records: map %.3f s, parse + pack %.3f s (%.2f CPU s), record arrays %.3f s, header ids %.3f s (arrays %.3f, count %.3f, scatter %.3f, shards %.3f) beside the words' placement %.3f s: %.3f s, pieces freed %.3f s; %.2f CPU s behind the parse\n",
-                n, nc, (unsigned long long)nrec, t1 - t0, t2 - t1, c2 - c1, t3 - t2, t_hdr, th_ph[0] - t3, th_ph[1] - th_ph[0], th_ph[2] - th_ph[1], th_ph[3] - th_ph[2], t_words, t4 - t3, now_s() - t4, cpu_seconds() - c2);
-    *out = ix.release();
-    return CRASS_OK;
-}
-
-int crass_fastx_index_reads(const crass_fastx_index *ix, crass_reads *reads, uint32_t *max_len, int *last_ret)
-{
-    if (!ix || !reads) return CRASS_ERR_INVALID_ARG;
-    *reads = ix->reads;
-    if (max_len) *max_len = ix->max_len;
-    if (last_ret) *last_ret = ix->last_ret;
-    return CRASS_OK;
-}
-
-// the records idx[0 .. n) (any order, repeats allowed) as a crass_fastx of n records in that order: parsed from the mapping by
-// the reader's own state machine; header_id[k] = idx[k] (the caller knows the job-level ids)
-int crass_fastx_index_fetch(const crass_fastx_index *ix, const uint64_t *idx, uint64_t n, crass_fastx *out)
-{
-    if (!ix || !out || (n && !idx)) return CRASS_ERR_INVALID_ARG;
-    memset(out, 0, sizeof(*out));
-    const uint64_t nrec = ix->reads.n_reads;
-    for (uint64_t k = 0; k < n; k++) if (idx[k] >= nrec) return CRASS_ERR_INVALID_ARG;
-    const unsigned nt = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw_threads(), 32u), std::max<uint64_t>(1, n / 2048));
-    std::vector<FxChunk> parts(nt ? nt : 1);
-    const uint64_t per = (n + parts.size() - 1) / parts.size();
-    std::atomic<bool> io_fail{false};
-    auto run = [&](size_t t) {
-        const uint64_t a = std::min<uint64_t>(n, t * per), b = std::min<uint64_t>(n, a + per);
-        std::vector<uint8_t> rb;
-        for (uint64_t k = a; k < b; k++) {
-            const uint64_t h = ix->hdr_pos[idx[k]];
-            const crass_fastx_index::File &F = ix->file_of(h);
-            const size_t lh = (size_t)(h - F.base);
-            if (F.map) { parse_range((const uint8_t *)F.map, F.n, lh, lh + 1, false, parts[t]); continue; }      // exactly the record whose header character is at h
-            // (the mapping is gone: the record's bytes — from its header character to the next record's, or to the file's end — from the file)
-            uint64_t e = F.base + F.n;
-            if (idx[k] + 1 < nrec && ix->hdr_pos[idx[k] + 1] < e) e = ix->hdr_pos[idx[k] + 1];
-            const size_t len = (size_t)(e - h);
-            rb.resize(len);
-            size_t got = 0;
-            while (got < len) { const ssize_t g = pread(F.fd, rb.data() + got, len - got, (off_t)(lh + got)); if (g <= 0) break; got += (size_t)g; }
-            if (got != len) { io_fail.store(true); return; }
-            parse_range(rb.data(), len, 0, 1, false, parts[t]);
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < parts.size(); t++) th.emplace_back(run, t);
-        run(0);
-        for (auto &t : th) t.join();
-    }
-    if (io_fail.load()) return CRASS_ERR_IO;
-    uint64_t got = 0, seq_b = 0, name_b = 0, com_b = 0, qual_b = 0;
-    for (auto &c : parts) { got += c.n_rec(); seq_b += c.seq.size(); name_b += c.name.size(); com_b += c.comment.size(); qual_b += c.qual.size(); }
-    if (got != n) return CRASS_ERR_STATE;
-    auto alloc8 = [](uint64_t nb) { return (uint8_t *)malloc(nb + 1); };
-    auto alloc64 = [](uint64_t ne) { return (uint64_t *)malloc((ne + 1) * 8); };
-    out->n_reads = n;
-    out->seq = alloc8(seq_b); out->seq_off = alloc64(n + 1); out->name = alloc8(name_b); out->name_off = alloc64(n + 1);
-    out->comment = alloc8(com_b); out->comment_off = alloc64(n + 1); out->has_comment = alloc8(n);
-    out->qual = alloc8(qual_b); out->qual_off = alloc64(n + 1); out->has_qual = alloc8(n);
-    out->header_id = alloc64(n);
-    if (!out->seq || !out->seq_off || !out->name || !out->name_off || !out->comment || !out->comment_off || !out->has_comment ||
-        !out->qual || !out->qual_off || !out->has_qual || !out->header_id) { crass_free_fastx(out); return CRASS_ERR_OOM; }
-    out->seq_off[0] = out->name_off[0] = out->comment_off[0] = out->qual_off[0] = 0;
-    uint64_t r = 0, sq = 0, nm = 0, cm = 0, ql = 0;
-    uint32_t max_len = 0;
-    for (auto &c : parts) {
-        if (!c.seq.empty()) memcpy(out->seq + sq, c.seq.data(), c.seq.size());
-        if (!c.name.empty()) memcpy(out->name + nm, c.name.data(), c.name.size());
-        if (!c.comment.empty()) memcpy(out->comment + cm, c.comment.data(), c.comment.size());
-        if (!c.qual.empty()) memcpy(out->qual + ql, c.qual.data(), c.qual.size());
-        for (size_t i = 0; i < c.n_rec(); i++, r++) {
-            out->seq_off[r + 1] = sq + c.seq_end[i]; out->name_off[r + 1] = nm + c.name_end[i];
-            out->comment_off[r + 1] = cm + c.comment_end[i]; out->qual_off[r + 1] = ql + c.qual_end[i];
-            { const crass_fastx_index::File &F = ix->file_of(ix->hdr_pos[idx[r]]); out->has_comment[r] = F.any_c ? 1 : 0; out->has_qual[r] = F.any_q ? 1 : 0; }
-            out->header_id[r] = idx[r];
-        }
-        sq += c.seq.size(); nm += c.name.size(); cm += c.comment.size(); ql += c.qual.size();
-        max_len = std::max(max_len, c.max_len);
-    }
-    out->max_len = max_len;
-    out->last_ret = ix->last_ret;
-    return CRASS_OK;
-}
-
-void crass_fastx_index_free(crass_fastx_index *ix) { delete ix; }
-
-// A plain file's mapping has done most of its work once the hand-off has fetched its records: 2 M page-table entries for 8 GB, taken
-// down side by side (the pages dropped under the shared lock by sixteen threads, then an unmapping that finds nothing) instead of by
-// one thread beside a later stage, whose allocations waited for it a quarter of a second.  Records fetched after this are read from
-// the file (pread: four times slower per record, which is why the hand-off fetches first).
-void crass_fastx_index_drop_text(crass_fastx_index *ix)
-{
-    if (!ix) return;
-    for (crass_fastx_index::File &F : ix->files) {
-        if (F.own || !F.map || !F.n || F.fd < 0) continue;
-        const size_t slice = 64u << 20, ns = (F.n + slice - 1) / slice;
-        uint8_t *mp = (uint8_t *)F.map;
-        const size_t fn = F.n;
-        {
-            const unsigned nt = (unsigned)std::min<size_t>(std::min<unsigned>(hw_threads(), 16u), ns);
-            std::atomic<size_t> next{0};
-            auto drop = [&]() { for (;;) { const size_t q = next.fetch_add(1); if (q >= ns) break; (void)madvise(mp + q * slice, std::min<size_t>(slice, fn - q * slice), MADV_DONTNEED); } };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < nt; t++) th.emplace_back(drop);
-            drop();
-            for (auto &x : th) x.join();
-        }
-        munmap(F.map, F.n);
-        F.map = nullptr;
-    }
-}
-
-
-} // extern "C"
-
-// ---- the same reader as a STREAM of chunks (bounded host memory; VERDICT r03 "the reference's streaming memory model") ----
-// kseq_read hands out one record at a time from a 4 KB buffer (kseq.cpp:171-226, libcrispr.cpp:96), so crass's memory does not
-// grow with the file.  crass_read_fastx holds the whole file's records; the stream holds one chunk of them: raw bytes are
-// read through zlib (gzread: plain and gzip'd input alike, SeqUtils.cpp:100-126) a chunk at a time, a chunk is parsed by the same
-// piece-parallel state machine, its LAST record — possibly cut by the chunk's end — is left for the next chunk (the carry
-// starts at its header character), and kseq's cross-record state travels with the stream: the stale comment / quality buffers
-// (libcrispr.cpp:124-131) and, through a job-level name table, the first read with the same header (readsFound's key).
-namespace {
-struct Hash128 { uint64_t a, b; };
-inline Hash128 name_hash128(const uint8_t *p, size_t n)
-{
-    Hash128 h;
-    h.a = name_hash(p, n);
-    uint64_t x = 0xC2B2AE3D27D4EB4Full ^ (n * 0x9E3779B97F4A7C15ull);
-    size_t m = n; const uint8_t *q = p;
-    while (m >= 8) { uint64_t v; memcpy(&v, q, 8); x = (x ^ (v * 0x87C37B91114253D5ull)) * 0x4CF5AD432745937Full; x ^= x >> 33; q += 8; m -= 8; }
-    if (m) { uint64_t v = 0; memcpy(&v, q, m); x = (x ^ (v * 0x87C37B91114253D5ull)) * 0x4CF5AD432745937Full; x ^= x >> 29; }
-    h.b = x ^ (x >> 32);
-    return h;
-}
-} // namespace
-
-// name -> index of the first read of the JOB with that name.  The names themselves are not kept: a name is its 128-bit hash —
-// two independent 64-bit mixes, BOTH stored and compared in full (round 4 kept 64 + 32 bits while saying 128: VERDICT r04 weak 1c).
-// Two different names of a job of n reads meet in both with probability ~ n^2 / 2^129 (1.5e-23 at n = 1e8); the whole-file reader
-// (crass_read_fastx) compares the names themselves.  29 bytes per distinct name at load <= 0.7.
-// One sub-table: 20 bytes per slot, 128 hash bits and a 32-bit index (jobs of up to 2^32 - 2 reads; beyond that a 64-bit side table)
-struct NameSubTable {
-    std::vector<uint64_t> ha, hb; std::vector<uint32_t> idx;     // idx == 0xFFFFFFFF: empty
-    std::vector<uint64_t> idx_wide;                              // (only once an index does not fit 32 bits)
-    size_t used = 0;
-    bool wide = false;
-    uint64_t get_idx(size_t j) const { return wide ? idx_wide[j] : idx[j]; }
-    void grow(size_t min_cap = 0)
-    {
-        size_t cap = ha.empty() ? (1u << 12) : ha.size() * 2;
-        while (cap < min_cap) cap *= 2;
-        std::vector<uint64_t> a(cap), b(cap), xw(wide ? cap : 0);
-        std::vector<uint32_t> x(cap, 0xFFFFFFFFu);
-        for (size_t i = 0; i < ha.size(); i++) {
-            if (idx[i] == 0xFFFFFFFFu) continue;
-            size_t j = (size_t)ha[i] & (cap - 1);
-            while (x[j] != 0xFFFFFFFFu) j = (j + 1) & (cap - 1);
-            a[j] = ha[i]; b[j] = hb[i]; x[j] = idx[i];
-            if (wide) xw[j] = idx_wide[i];
-        }
-        ha.swap(a); hb.swap(b); idx.swap(x); idx_wide.swap(xw);
-    }
-    uint64_t first_hashed(Hash128 h, uint64_t index)
-    {
-        if ((used + 1) * 10 > ha.size() * 7) grow();
-        if (!wide && index >= 0xFFFFFFFEull) { wide = true; idx_wide.resize(ha.size()); for (size_t i = 0; i < ha.size(); i++) idx_wide[i] = idx[i]; }
-        const size_t cap = ha.size();
-        const uint64_t b32 = h.b;
-        for (size_t j = (size_t)h.a & (cap - 1);; j = (j + 1) & (cap - 1)) {
-            if (idx[j] == 0xFFFFFFFFu) {
-                ha[j] = h.a; hb[j] = b32; idx[j] = wide ? 0u : (uint32_t)index; if (wide) idx_wide[j] = index;
-                used++;
-                return index;
-            }
-            if (ha[j] == h.a && hb[j] == b32) return get_idx(j);
-        }
-    }
-};
-
-// The job's names -> the first read that carried each.  64 sub-tables by the hash's top bits: a chunk's names are dealt to their
-// sub-tables in read order (a counting sort of the chunk's record numbers) and every sub-table is filled by ONE thread — the first
-// occurrence is simply the first insert, and the 50 M serial inserts of a streamed job (3 s of its 8.5 s ingest) spread over the
-// cores.
-struct crass_name_table {
-    static constexpr unsigned SH = 64;
-    NameSubTable sub[SH];
-    static unsigned shard(const Hash128 &h) { return (unsigned)(h.a >> 58); }
-    uint64_t first_hashed(Hash128 h, uint64_t index) { return sub[shard(h)].first_hashed(h, index); }
-    uint64_t first(const uint8_t *name, size_t len, uint64_t index) { return first_hashed(name_hash128(name, len), index); }
-    void reserve(uint64_t n_names)
-    {
-        const uint64_t per = n_names / SH + n_names / SH / 8 + 64;
-        size_t want = 1u << 12;
-        while ((per + 1) * 10 > want * 7) want *= 2;
-        parallel_ranges(SH, std::min<unsigned>(hw_threads(), 16u), [&](uint64_t a, uint64_t b, unsigned) { for (uint64_t k = a; k < b; k++) if (want > sub[k].ha.size()) sub[k].grow(want); });
-        for (auto &t : sub) if (want > t.ha.size()) t.grow(want);      // (parallel_ranges runs small counts on one thread)
-    }
-    // out[q] = first read of the job named like read base + q, for q in [0, n): the table as if the names had been inserted in order
-    void first_batch(const Hash128 *hs, uint64_t n, uint64_t base, uint64_t *out)
-    {
-        const unsigned nt = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw_threads(), 16u), n / 8192);
-        if (nt <= 1) { for (uint64_t q = 0; q < n; q++) out[q] = first_hashed(hs[q], base + q); return; }
-        std::vector<uint32_t> order(n);
-        std::vector<uint64_t> cnt((size_t)nt * SH, 0), sh_begin(SH + 1, 0);
-        const uint64_t per = (n + nt - 1) / nt;
-        auto range = [&](unsigned t, uint64_t &a, uint64_t &b) { a = std::min<uint64_t>(n, t * per); b = std::min<uint64_t>(n, a + per); };
-        auto run = [&](const std::function<void(unsigned)> &fn) { std::vector<std::thread> th; for (unsigned t = 1; t < nt; t++) th.emplace_back(fn, t); fn(0); for (auto &x : th) x.join(); };
-        run([&](unsigned t) { uint64_t a, b; range(t, a, b); uint64_t *c = cnt.data() + (size_t)t * SH; for (uint64_t q = a; q < b; q++) c[shard(hs[q])]++; });
-        { uint64_t at = 0; for (unsigned sh = 0; sh < SH; sh++) { sh_begin[sh] = at; for (unsigned t = 0; t < nt; t++) { const uint64_t c = cnt[(size_t)t * SH + sh]; cnt[(size_t)t * SH + sh] = at; at += c; } } sh_begin[SH] = at; }
-        run([&](unsigned t) { uint64_t a, b; range(t, a, b); uint64_t *c = cnt.data() + (size_t)t * SH; for (uint64_t q = a; q < b; q++) order[c[shard(hs[q])]++] = (uint32_t)q; });
-        std::atomic<unsigned> next{0};
-        run([&](unsigned) {
-            for (;;) {
-                const unsigned sh = next.fetch_add(1, std::memory_order_relaxed);
-                if (sh >= SH) break;
-                NameSubTable &T = sub[sh];
-                for (uint64_t p = sh_begin[sh]; p < sh_begin[sh + 1]; p++) { const uint64_t q = order[p]; out[q] = T.first_hashed(hs[q], base + q); }
-            }
-        });
-    }
-};
-
-static double stream_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct crass_fastx_stream {
-    gzFile fp = nullptr;
-    std::vector<uint8_t> buf;                       // the carried tail (the record a chunk's end cut: parsed again with the next chunk)
-    size_t carry = 0, chunk_bytes = 64u << 20;
-    // The file is read (and inflated) one block AHEAD on a thread of its own: reading 64 MB was 13 ms of a chunk's 23 in the
-    // second pass of a streamed job, and most of a gzip input's time.  A block has room in front of its bytes for the carried tail,
-    // so a chunk is parsed where it was read.
-    struct Block { std::unique_ptr<uint8_t[]> p; size_t gap = 0, len = 0; bool last = false; };
-    std::thread rd;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Block> ready;
-    bool rd_stop = false, rd_err = false, rd_done = false;
-    // what a chunk needs is kept from chunk to chunk: the pieces, the arrays handed out (crass_fastx's pointers: valid until the
-    // next call), the blocks of the reader thread
-    std::vector<FxChunk> ch;
-    KeepBuf<uint8_t> k_seq, k_name, k_hasc, k_hasq, k_com, k_qual;
-    KeepBuf<uint64_t> k_seq_off, k_name_off, k_com_off, k_qual_off, k_hid;
-    std::vector<std::unique_ptr<uint8_t[]>> pool;    // (under mu)
-    double t_wait = 0, t_parse = 0, t_asm = 0, t_names = 0, t_read = 0;      // CRASS_TIMING: where the chunks' time went
-    uint64_t n_chunks = 0;
-    void reader()
-    {
-        const size_t gap = std::min<size_t>(1u << 20, chunk_bytes);
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return ready.size() < 2 || rd_stop; });
-                if (rd_stop) break;
-            }
-            Block b;
-            b.gap = gap;
-            const double tr0 = stream_now();
-            { std::lock_guard<std::mutex> lk(mu); if (!pool.empty()) { b.p = std::move(pool.back()); pool.pop_back(); } }
-            if (!b.p) b.p.reset(new (std::nothrow) uint8_t[gap + chunk_bytes]);
-            bool err = !b.p;
-            size_t at = 0;
-            while (!err && at < chunk_bytes) {
-                const int got = gzread(fp, b.p.get() + gap + at, (unsigned)std::min<size_t>(chunk_bytes - at, 1u << 30));
-                if (got < 0) { err = true; break; }
-                if (got == 0) { b.last = true; break; }
-                at += (size_t)got;
-            }
-            b.len = at;
-            t_read += stream_now() - tr0;
-            const bool last = b.last;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (err) rd_err = true; else ready.push_back(std::move(b));
-                if (err || last) rd_done = true;
-            }
-            cv.notify_all();
-            if (err || last) break;
-        }
-        { std::lock_guard<std::mutex> lk(mu); rd_done = true; }
-        cv.notify_all();
-    }
-    bool take(Block &b)                             // false: read error
-    {
-        if (!rd.joinable()) rd = std::thread([this] { reader(); });
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return !ready.empty() || rd_done; });
-        if (ready.empty()) { if (rd_err) return false; b = Block(); b.last = true; return true; }
-        b = std::move(ready.front());
-        ready.pop_front();
-        lk.unlock();
-        cv.notify_all();
-        return true;
-    }
-    void stop_reader()
-    {
-        { std::lock_guard<std::mutex> lk(mu); rd_stop = true; }
-        cv.notify_all();
-        if (rd.joinable()) rd.join();
-    }
-    bool eof = false, finished = false;
-    bool any_c = false, any_q = false;              // some earlier record had its own comment / quality: later ones inherit
-    std::string stale_c, stale_q;
-    uint64_t n_done = 0, index_base = 0;
-    crass_name_table *names = nullptr;
-    uint32_t max_len = 0;
-    int final_ret = -1;                             // kseq_read's last return value, once the end of the file has been parsed
-    crass_fastx cur{};
-};
-
-extern "C" {
-
-crass_name_table *crass_name_table_create(void) { return new (std::nothrow) crass_name_table(); }
-void crass_name_table_reserve(crass_name_table *t, uint64_t n_names)
-{
-    if (!t) return;
-    t->reserve(n_names);
-}
-void crass_name_table_destroy(crass_name_table *t) { delete t; }
-uint64_t crass_name_table_first(crass_name_table *t, const char *name, uint64_t len, uint64_t index)
-{
-    return t ? t->first((const uint8_t *)name, (size_t)len, index) : index;
-}
-
-int crass_fastx_stream_open(const char *path, uint64_t chunk_bytes, crass_name_table *names, uint64_t index_base, crass_fastx_stream **out)
-{
-    if (!path || !out) return CRASS_ERR_INVALID_ARG;
-    *out = nullptr;
-    gzFile fp = gzopen(path, "r");
-    if (!fp) return CRASS_ERR_IO;
-    gzbuffer(fp, 1 << 20);
-    crass_fastx_stream *s = new (std::nothrow) crass_fastx_stream();
-    if (!s) { gzclose(fp); return CRASS_ERR_OOM; }
-    s->fp = fp;
-    if (chunk_bytes) s->chunk_bytes = (size_t)std::max<uint64_t>(chunk_bytes, 256);
-    if (const char *e = getenv("CRASS_INGEST_CHUNK_BYTES")) s->chunk_bytes = (size_t)std::max(256ll, atoll(e));      // tests: tiny chunks
-    s->names = names; s->index_base = index_base;
-    *out = s;
-    return CRASS_OK;
-}
-
-void crass_fastx_stream_close(crass_fastx_stream *s)
-{
-    if (!s) return;
-    s->stop_reader();
-    if (getenv("CRASS_TIMING"))
-        fprintf(stderr, "[crass_timing] fastx stream: %llu chunks, %llu records: waiting for a block %.3f s (reading them, beside: %.3f s), parse %.3f s, assemble %.3f s, names %.3f s\n",
-                (unsigned long long)s->n_chunks, (unsigned long long)s->n_done, s->t_wait, s->t_read, s->t_parse, s->t_asm, s->t_names);
-    if (s->fp) gzclose(s->fp);
-    delete s;
-}
-
-uint64_t crass_fastx_stream_reads_done(const crass_fastx_stream *s) { return s ? s->n_done : 0; }
-uint32_t crass_fastx_stream_max_len(const crass_fastx_stream *s) { return s ? s->max_len : 0; }
-
-// The next chunk's records: the fields of crass_fastx, valid until the next call on this stream; n_reads == 0 at the end of the
-// file (last_ret then holds kseq_read's final return value).  header_id[i] is a JOB-level read index (index_base + the
-// stream's running count) when the stream has a name table, else the chunk-local index i itself.
-int crass_fastx_stream_next(crass_fastx_stream *s, crass_fastx *out)
-{
-    if (!s || !out) return CRASS_ERR_INVALID_ARG;
-    memset(&s->cur, 0, sizeof(s->cur));                  // (its arrays belong to the stream)
-    memset(out, 0, sizeof(*out));
-    out->last_ret = s->final_ret;
-    if (s->finished) return CRASS_OK;
-    std::vector<FxChunk> &ch = s->ch;
-    size_t n_keep_pieces = 0, consumed = 0;
-    bool drop_last = false;
-    // the chunk's bytes: the carried tail (s->buf) followed by the next block, in the block's own memory when the tail fits the
-    // room in front of it
-    const uint8_t *data = s->buf.data();
-    size_t n = s->buf.size();
-    std::unique_ptr<uint8_t[]> hold;
-    bool hold_is_block = false;
-    size_t big_cap = 0, want = 0;
-    struct GiveBack {                                    // a block goes back to the reader's pool when the chunk is done with it
-        crass_fastx_stream *s; std::unique_ptr<uint8_t[]> &h; bool &is_block;
-        ~GiveBack() { if (h && is_block) { std::lock_guard<std::mutex> lk(s->mu); if (s->pool.size() < 3) s->pool.push_back(std::move(h)); } }
-    } give_back{s, hold, hold_is_block};
-    for (;;) {
-        if (!s->eof) {
-            crass_fastx_stream::Block b;
-            const double tw0 = stream_now();
-            if (!s->take(b)) return CRASS_ERR_IO;
-            s->t_wait += stream_now() - tw0;
-            if (b.last) s->eof = true;
-            if (b.p && n <= b.gap) {
-                if (n) memcpy(b.p.get() + b.gap - n, data, n);
-                data = b.p.get() + b.gap - n;
-                n += b.len;
-                if (hold && hold_is_block) { std::lock_guard<std::mutex> lk(s->mu); if (s->pool.size() < 3) s->pool.push_back(std::move(hold)); }
-                hold = std::move(b.p);                  // (what data pointed into until now — the tail, or an earlier block — is done with)
-                hold_is_block = true;
-            } else if (b.len) {
-                // the tail does not fit in front of the block: an owned buffer, grown geometrically and appended to in place (a
-                // record k blocks long is then copied O(k) bytes over, not O(k^2))
-                if (!hold_is_block && hold && n + b.len <= big_cap) {
-                    memcpy(hold.get() + n, b.p.get() + b.gap, b.len);
-                    n += b.len;
-                } else {
-                    const size_t cap = std::max<size_t>(2 * (n + b.len), (size_t)1 << 20);
-                    std::unique_ptr<uint8_t[]> big(new (std::nothrow) uint8_t[cap]);
-                    if (!big) return CRASS_ERR_OOM;
-                    if (n) memcpy(big.get(), data, n);
-                    memcpy(big.get() + n, b.p.get() + b.gap, b.len);
-                    data = big.get();
-                    n += b.len;
-                    if (hold && hold_is_block) { std::lock_guard<std::mutex> lk(s->mu); if (s->pool.size() < 3) s->pool.push_back(std::move(hold)); }
-                    hold = std::move(big);
-                    hold_is_block = false;
-                    big_cap = cap;
-                }
-                { std::lock_guard<std::mutex> lk(s->mu); if (s->pool.size() < 3) s->pool.push_back(std::move(b.p)); }
-            }
-            if (n < want && !s->eof) continue;           // (a chunk that parsed short is parsed again only once it has doubled)
-        }
-        const double tp0 = stream_now();
-        parse_pieces(data, n, ch, 2u << 20);                   // (2 MB pieces: a 64 MB chunk still keeps 32 threads busy)
-        s->t_parse += stream_now() - tp0;
-        size_t total = 0;
-        for (auto &c : ch) total += c.n_rec();
-        if (s->eof) { n_keep_pieces = ch.size(); consumed = n; drop_last = false; break; }
-        // not the end of the file: the last record may have been cut by the end of the buffer — it is parsed again with the
-        // next chunk.  A chunk that holds fewer than two records (a read longer than the chunk) is read again, larger.
-        if (total >= 2) {
-            n_keep_pieces = ch.size();
-            while (n_keep_pieces && ch[n_keep_pieces - 1].n_rec() == 0) n_keep_pieces--;
-            consumed = ch[n_keep_pieces - 1].last_hdr;
-            drop_last = true;
-            break;
-        }
-        // (keep everything, read more behind it — twice the bytes before the next parse, so that a read k blocks long is parsed
-        // O(log k) times)
-        want = 2 * n;
-    }
-    // ---- assemble the chunk's records in order (kseq's stale comment / quality buffers travel with the stream) ----
-    const double ta0 = stream_now();
-    s->n_chunks++;
-    uint64_t nrec = 0, seq_b = 0, name_b = 0;
-    for (size_t k = 0; k < n_keep_pieces; k++) { nrec += ch[k].n_rec(); seq_b += ch[k].seq.size(); name_b += ch[k].name.size(); }
-    if (drop_last) nrec--;
-    crass_fastx &o = s->cur;
-    o.n_reads = nrec;
-    o.seq = s->k_seq.ensure(seq_b + 1); o.seq_off = s->k_seq_off.ensure(nrec + 1); o.name = s->k_name.ensure(name_b + 1); o.name_off = s->k_name_off.ensure(nrec + 1);
-    o.has_comment = s->k_hasc.ensure(nrec + 1); o.has_qual = s->k_hasq.ensure(nrec + 1); o.comment_off = s->k_com_off.ensure(nrec + 1); o.qual_off = s->k_qual_off.ensure(nrec + 1);
-    o.header_id = s->k_hid.ensure(nrec + 1);
-    if (!o.seq || !o.seq_off || !o.name || !o.name_off || !o.has_comment || !o.has_qual || !o.comment_off || !o.qual_off || !o.header_id) return CRASS_ERR_OOM;
-    o.seq_off[0] = o.name_off[0] = o.comment_off[0] = o.qual_off[0] = 0;
-    std::vector<uint8_t> com_bytes, qual_bytes;
-    uint64_t r = 0, sq = 0, nm = 0;
-    uint32_t max_len = 0;
-    // The common layouts — no record of the chunk (and none before it) has a comment / a quality string, or every one has its own —
-    // need no record-by-record walk: every piece's fields are already concatenated in record order, so a piece is four block copies
-    // and its offsets, and the pieces go side by side.  (kseq's stale buffers — a record WITHOUT a comment inherits the last one
-    // seen — make the general case sequential: the loop below.  It was 4 s of a streamed 50 M-read job on one thread.)
-    bool assembled = false;
-    {
-        bool all_c = true, none_c = true, all_q = true, none_q = true;
-        for (size_t k = 0; k < n_keep_pieces; k++) {
-            for (uint8_t v : ch[k].own_c) { all_c &= v != 0; none_c &= v == 0; }
-            for (uint8_t v : ch[k].own_q) { all_q &= v != 0; none_q &= v == 0; }
-        }
-        const bool c_ok = (none_c && !s->any_c) || all_c, q_ok = (none_q && !s->any_q) || all_q;
-        if (c_ok && q_ok && nrec && !getenv("CRASS_STREAM_SERIAL_ASSEMBLE")) {
-            const bool with_c = all_c && !none_c, with_q = all_q && !none_q;
-            const size_t np = n_keep_pieces;
-            std::vector<uint64_t> cnt(np, 0), r0(np + 1, 0), sq0(np + 1, 0), nm0(np + 1, 0), cm0(np + 1, 0), ql0(np + 1, 0);
-            uint64_t left = nrec;
-            for (size_t k = 0; k < np; k++) {
-                const FxChunk &c = ch[k];
-                const uint64_t m = std::min<uint64_t>(c.n_rec(), left);
-                left -= m; cnt[k] = m;
-                r0[k + 1] = r0[k] + m;
-                sq0[k + 1] = sq0[k] + (m ? c.seq_end[m - 1] : 0); nm0[k + 1] = nm0[k] + (m ? c.name_end[m - 1] : 0);
-                cm0[k + 1] = cm0[k] + ((with_c && m) ? c.comment_end[m - 1] : 0); ql0[k + 1] = ql0[k] + ((with_q && m) ? c.qual_end[m - 1] : 0);
-            }
-            o.comment = s->k_com.ensure(cm0[np] + 1); o.qual = s->k_qual.ensure(ql0[np] + 1);
-            if (!o.comment || !o.qual) return CRASS_ERR_OOM;
-            std::vector<uint32_t> pmax(np, 0);
-            auto piece = [&](size_t k) {
-                const FxChunk &c = ch[k];
-                const uint64_t m = cnt[k];
-                if (!m) return;
-                if (c.seq_end[m - 1]) memcpy(o.seq + sq0[k], c.seq.data(), c.seq_end[m - 1]);
-                if (c.name_end[m - 1]) memcpy(o.name + nm0[k], c.name.data(), c.name_end[m - 1]);
-                if (with_c && c.comment_end[m - 1]) memcpy(o.comment + cm0[k], c.comment.data(), c.comment_end[m - 1]);
-                if (with_q && c.qual_end[m - 1]) memcpy(o.qual + ql0[k], c.qual.data(), c.qual_end[m - 1]);
-                uint32_t mx = 0;
-                for (uint64_t i = 0; i < m; i++) {
-                    const uint64_t rr = r0[k] + i;
-                    o.seq_off[rr + 1] = sq0[k] + c.seq_end[i]; o.name_off[rr + 1] = nm0[k] + c.name_end[i];
-                    o.comment_off[rr + 1] = with_c ? cm0[k] + c.comment_end[i] : 0; o.qual_off[rr + 1] = with_q ? ql0[k] + c.qual_end[i] : 0;
-                    o.has_comment[rr] = with_c ? 1 : 0; o.has_qual[rr] = with_q ? 1 : 0;
-                    o.header_id[rr] = rr;
-                    mx = std::max<uint32_t>(mx, (uint32_t)(c.seq_end[i] - (i ? c.seq_end[i - 1] : 0)));
-                }
-                pmax[k] = mx;
-            };
-            {
-                std::vector<std::thread> th;
-                const unsigned nt = (unsigned)std::min<size_t>(np, std::min<unsigned>(hw_threads(), 32u));
-                std::atomic<size_t> next{0};
-                auto work = [&]() { for (;;) { const size_t k = next.fetch_add(1, std::memory_order_relaxed); if (k >= np) break; piece(k); } };
-                for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-                work();
-                for (auto &x : th) x.join();
-            }
-            for (size_t k = 0; k < np; k++) max_len = std::max(max_len, pmax[k]);
-            // the stream's stale buffers as the record-by-record walk would leave them: the last kept record's own strings
-            for (size_t k = np; k-- > 0;) {
-                if (!cnt[k]) continue;
-                const FxChunk &c = ch[k];
-                const uint64_t i = cnt[k] - 1;
-                if (with_c) { const uint64_t b0 = i ? c.comment_end[i - 1] : 0; s->stale_c.assign((const char *)c.comment.data() + b0, c.comment_end[i] - b0); s->any_c = true; }
-                if (with_q) { const uint64_t b0 = i ? c.qual_end[i - 1] : 0; s->stale_q.assign((const char *)c.qual.data() + b0, c.qual_end[i] - b0); s->any_q = true; }
-                break;
-            }
-            r = nrec;
-            assembled = true;
-        }
-    }
-    for (size_t k = 0; !assembled && k < n_keep_pieces && r < nrec; k++) {
-        const FxChunk &c = ch[k];
-        for (size_t i = 0; i < c.n_rec() && r < nrec; i++, r++) {
-            const uint64_t s0 = i ? c.seq_end[i - 1] : 0, n0 = i ? c.name_end[i - 1] : 0;
-            const uint64_t sl = c.seq_end[i] - s0, nl = c.name_end[i] - n0;
-            if (sl) memcpy(o.seq + sq, c.seq.data() + s0, sl);
-            if (nl) memcpy(o.name + nm, c.name.data() + n0, nl);
-            sq += sl; nm += nl;
-            o.seq_off[r + 1] = sq; o.name_off[r + 1] = nm;
-            max_len = std::max<uint32_t>(max_len, (uint32_t)sl);
-            if (c.own_c[i]) { const uint64_t b0 = i ? c.comment_end[i - 1] : 0; s->stale_c.assign((const char *)c.comment.data() + b0, c.comment_end[i] - b0); s->any_c = true; }
-            o.has_comment[r] = s->any_c ? 1 : 0;
-            if (s->any_c) com_bytes.insert(com_bytes.end(), s->stale_c.begin(), s->stale_c.end());
-            o.comment_off[r + 1] = com_bytes.size();
-            if (c.own_q[i]) { const uint64_t b0 = i ? c.qual_end[i - 1] : 0; s->stale_q.assign((const char *)c.qual.data() + b0, c.qual_end[i] - b0); s->any_q = true; }
-            o.has_qual[r] = s->any_q ? 1 : 0;
-            if (s->any_q) qual_bytes.insert(qual_bytes.end(), s->stale_q.begin(), s->stale_q.end());
-            o.qual_off[r + 1] = qual_bytes.size();
-            o.header_id[r] = r;
-        }
-    }
-    const double tn0 = stream_now();
-    s->t_asm += tn0 - ta0;
-    if (s->names && nrec) {
-        // the names' hashes on every core, the table itself in read order (first occurrence wins)
-        std::vector<Hash128> hs(nrec);
-        parallel_ranges(nrec, std::min<unsigned>(hw_threads(), 32u), [&](uint64_t a, uint64_t b2, unsigned) {
-            for (uint64_t q = a; q < b2; q++) hs[q] = name_hash128(o.name + o.name_off[q], (size_t)(o.name_off[q + 1] - o.name_off[q]));
-        });
-        s->names->first_batch(hs.data(), nrec, s->index_base + s->n_done, o.header_id);
-    }
-    s->t_names += stream_now() - tn0;
-    if (!assembled) {
-        o.comment = s->k_com.ensure(com_bytes.size() + 1); o.qual = s->k_qual.ensure(qual_bytes.size() + 1);
-        if (!o.comment || !o.qual) return CRASS_ERR_OOM;
-        if (!com_bytes.empty()) memcpy(o.comment, com_bytes.data(), com_bytes.size());
-        if (!qual_bytes.empty()) memcpy(o.qual, qual_bytes.data(), qual_bytes.size());
-    }
-    o.max_len = max_len;
-    s->max_len = std::max(s->max_len, max_len);
-    o.last_ret = s->eof ? ch.back().last_ret : 0;
-    if (s->eof) s->final_ret = ch.back().last_ret;
-    s->n_done += nrec;
-    // the carry: from the header of the record that was left for the next chunk
-    if (drop_last) {
-        std::vector<uint8_t> tail(data + consumed, data + n);      // (data may point into s->buf itself)
-        s->buf.swap(tail);
-        s->carry = s->buf.size();
-    } else { s->buf.clear(); s->carry = 0; s->finished = true; }
-    *out = o;
-    return CRASS_OK;
-}
-
-} // extern "C"
-
-// ---- synthetic metagenome, counter-based ----
-static inline uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-static inline uint64_t key3(uint64_t seed, uint64_t a, uint64_t b) { return mix64(seed ^ mix64(a * 0xD1342543DE82EF95ull + mix64(b))); }
-
-void crass_synth_default(crass_synth_spec *s)
-{
-    s->seed = 42; s->read_len = 150; s->n_dr = 50; s->dr_len_min = 28; s->dr_len_max = 37;
-    s->spacer_len_min = 30; s->spacer_len_max = 38; s->crispr_per_million = 10000; s->gc_classes = 0;
-    s->array_min_repeats = 0; s->array_max_repeats = 0;
-}
-
-static inline uint32_t gc_word(uint64_t seed, uint64_t i, uint32_t w, uint32_t cls)
-{
-    // GC-content classes 30/45/55/70 %: 8-bit threshold draw + 1 bit to pick inside the pair
-    static const uint32_t thr[4] = {77, 115, 141, 179};
-    uint32_t out = 0;
-    for (int q = 0; q < 2; q++) {
-        uint64_t r0 = key3(seed ^ 0x6C62272E07BB0142ull, i, (uint64_t)w * 4 + q * 2);
-        uint64_t r1 = key3(seed ^ 0x6C62272E07BB0142ull, i, (uint64_t)w * 4 + q * 2 + 1);
-        for (int k = 0; k < 8; k++) {
-            uint32_t u = (uint32_t)(r0 >> (8 * k)) & 0xFF;
-            uint32_t pick = (uint32_t)(r1 >> k) & 1;
-            uint32_t code = (u < thr[cls & 3]) ? (pick ? 1u : 2u) : (pick ? 0u : 3u);   // C/G vs A/T
-            out |= code << (2 * (q * 8 + k));
-        }
-    }
-    return out;
-}
-
-int crass_synth_packed(const crass_synth_spec *s, uint64_t first, uint64_t n, uint32_t *packed, int n_threads)
-{
-    if (!s || (n && !packed)) return CRASS_ERR_INVALID_ARG;
-    if (s->read_len == 0 || s->read_len > CRASS_HIP_MAX_READ_LEN || s->n_dr == 0 || s->dr_len_max < s->dr_len_min ||
-        s->spacer_len_max < s->spacer_len_min || s->dr_len_max > 200) return CRASS_ERR_INVALID_ARG;
-    const bool arrays = s->array_max_repeats != 0;           // long-read mode: an array placed inside a random read
-    if (arrays && (s->array_max_repeats < s->array_min_repeats || s->array_max_repeats > 1000 || s->spacer_len_max > 64)) return CRASS_ERR_INVALID_ARG;
-    if (!arrays && s->read_len > 4096) return CRASS_ERR_INVALID_ARG;
-    const uint32_t L = s->read_len, W = (L + 15) / 16;
-    const uint64_t seed = s->seed;
-    // DR table
-    std::vector<std::vector<uint8_t>> drs(s->n_dr);
-    for (uint32_t d = 0; d < s->n_dr; d++) {
-        uint32_t len = s->dr_len_min + (uint32_t)(key3(seed, 1000, d) % (s->dr_len_max - s->dr_len_min + 1));
-        drs[d].resize(len);
-        for (uint32_t k = 0; k < len; k++) drs[d][k] = (uint8_t)((key3(seed, 2000 + d, k >> 5) >> (2 * (k & 31))) & 3);
-    }
-    unsigned nt = n_threads > 0 ? (unsigned)n_threads : hw_threads();
-    nt = std::min<unsigned>(nt, 64);
-    parallel_ranges(n, nt, [&](uint64_t a, uint64_t b, unsigned) {
-        std::vector<uint8_t> sbuf;
-        for (uint64_t k = a; k < b; k++) {
-            const uint64_t i = first + k;
-            uint32_t *w = packed + k * (uint64_t)W;
-            const uint64_t h = key3(seed, 1, i);
-            if (arrays) {
-                // BASELINE configs[3] shape: random background, and in a CRISPR read an array of U[min,max] repeats
-                // (DR + spacer units) written over it from a random offset (cut at the read end)
-                const uint32_t cls = s->gc_classes > 1 ? (uint32_t)((h >> 40) % s->gc_classes) : 0;
-                for (uint32_t q = 0; q < W; q++)
-                    w[q] = s->gc_classes > 1 ? gc_word(seed, i, q, cls) : (uint32_t)key3(seed ^ 0xA24BAED4963EE407ull, i, q);
-                if (L & 15) w[W - 1] &= (1u << ((L & 15) * 2)) - 1u;
-                if ((h % 1000000ull) < s->crispr_per_million) {
-                    const uint32_t d = (uint32_t)((h >> 24) % s->n_dr);
-                    const uint32_t reps = s->array_min_repeats + (uint32_t)(key3(seed, 8, i) % (s->array_max_repeats - s->array_min_repeats + 1));
-                    uint32_t pos = (uint32_t)(key3(seed, 3, i) % (L > 64 ? L * 2 / 5 : 1));
-                    auto put = [&](uint32_t at, uint32_t code) { w[at >> 4] = (w[at >> 4] & ~(3u << ((at & 15) * 2))) | (code << ((at & 15) * 2)); };
-                    for (uint32_t u = 0; u < reps; u++) {
-                        const uint32_t sl = s->spacer_len_min + (uint32_t)(key3(seed, 6, i * 1024 + u) % (s->spacer_len_max - s->spacer_len_min + 1));
-                        if (pos + drs[d].size() + sl > L) break;
-                        for (size_t p = 0; p < drs[d].size(); p++) put(pos + (uint32_t)p, drs[d][p]);
-                        pos += (uint32_t)drs[d].size();
-                        for (uint32_t p = 0; p < sl; p++) put(pos + p, (uint32_t)((key3(seed, 7, i * 65536 + (uint64_t)u * 64 + p) >> 11) & 3));
-                        pos += sl;
-                    }
-                }
-            } else if ((h % 1000000ull) < s->crispr_per_million) {
-                const uint32_t d = (uint32_t)((h >> 24) % s->n_dr);
-                const uint32_t prefix = (uint32_t)(key3(seed, 3, i) % 41);
-                const uint32_t cut = (uint32_t)(key3(seed, 4, i) % 41);
-                sbuf.clear();
-                for (uint32_t p = 0; p < prefix; p++) sbuf.push_back((uint8_t)((key3(seed, 5, i * 8192 + p) >> 7) & 3));
-                uint32_t u = 0;
-                while (sbuf.size() < (size_t)cut + L) {
-                    sbuf.insert(sbuf.end(), drs[d].begin(), drs[d].end());
-                    uint32_t sl = s->spacer_len_min + (uint32_t)(key3(seed, 6, i * 64 + u) % (s->spacer_len_max - s->spacer_len_min + 1));
-                    for (uint32_t p = 0; p < sl; p++) sbuf.push_back((uint8_t)((key3(seed, 7, i * 8192 + (uint64_t)(u + 1) * 64 + p) >> 11) & 3));
-                    u++;
-                }
-                for (uint32_t q = 0; q < W; q++) w[q] = 0;
-                for (uint32_t q = 0; q < L; q++) w[q >> 4] |= (uint32_t)sbuf[cut + q] << ((q & 15) * 2);
-            } else {
-                const uint32_t cls = s->gc_classes > 1 ? (uint32_t)((h >> 40) % s->gc_classes) : 0;
-                for (uint32_t q = 0; q < W; q++) {
-                    uint32_t v = s->gc_classes > 1 ? gc_word(seed, i, q, cls) : (uint32_t)key3(seed ^ 0xA24BAED4963EE407ull, i, q);
-                    w[q] = v;
-                }
-                if (L & 15) w[W - 1] &= (1u << ((L & 15) * 2)) - 1u;       // padding bases are zero
-            }
-        }
-    });
-    return CRASS_OK;
-}
-
-int crass_unpack_ascii(const uint32_t *packed, uint32_t stride_words, uint32_t read_len, uint64_t n, uint8_t *out)
-{
-    if (n && (!packed || !out || !stride_words)) return CRASS_ERR_INVALID_ARG;
-    static const char acgt[4] = {'A', 'C', 'G', 'T'};
-    parallel_ranges(n, std::min<unsigned>(hw_threads(), 32), [&](uint64_t a, uint64_t b, unsigned) {
-        for (uint64_t i = a; i < b; i++) {
-            const uint32_t *w = packed + i * (uint64_t)stride_words;
-            uint8_t *o = out + i * (uint64_t)read_len;
-            for (uint32_t q = 0; q < read_len; q++) o[q] = (uint8_t)acgt[(w[q >> 4] >> ((q & 15) * 2)) & 3];
-        }
-    });
-    return CRASS_OK;
 }
 
 } // extern "C"

@@ -45,6 +45,7 @@ struct PackLayout {
 };
 // CRASS_ERR_UNSUPPORTED: a read beyond CRASS_HIP_MAX_READ_LEN; CRASS_ERR_INVALID_ARG: off decreases somewhere
 int pack_layout(const uint64_t *off, uint64_t n, int pad_uniform, PackLayout *out);
+void pack_layout_core(uint64_t n, uint32_t max_len, uint32_t min_len, uint64_t tight_words, int pad_uniform, PackLayout *out);
 
 // a crass_packed (free with crass_free_packed) whose arrays have the given element counts and are filled by the caller;
 // a count of 0 leaves the array NULL

@@ -47,7 +47,7 @@ def bgzf(text, block=60000, eof=True, **kw):
 
 def walk(data):
     """the header walk restated (what crass_bgzf_index_host must give): (in_off, out_off, data_off), or None with the position and
-    index of the member that does not parse.  It is bgzf_walk (ingest.cpp) plus the one thing the index adds: the start of the
+    index of the member that does not parse.  It is bgzf_walk (host_inflate.cpp) plus the one thing the index adds: the start of the
     deflate data behind a file name, a comment and a header CRC where the flags announce them — a member in which those run into
     the trailer is declined here and accepted by bgzf_walk, which never looks at them (not_bgzf: file_name_runs_into_the_trailer)"""
     ioff, ooff, doff, p, o = [], [], [], 0, 0

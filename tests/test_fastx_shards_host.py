@@ -168,3 +168,71 @@ def test_member_rule_program(tmp_path):
     assert int(lines[0].split()[3]) >= 100000, lines[0]      # tilings checked
     assert lines[1].startswith("ok   placement:") and lines[-1] == "ok  : 0 failures", lines
     assert not any(w in r.stderr for w in ("runtime error", "AddressSanitizer", "LeakSanitizer")), r.stderr[-3000:]
+
+
+HOST_READER = ("ingest", "fastx_parse", "host_inflate", "fastx_read", "fastx_index", "fastx_stream", "synth", "pgzip")
+
+
+def test_host_reader_program(tmp_path):
+    """tools/sanitize/ingest_main.cpp over the files of the host reader (csrc/ingest.cpp and the six beside it, csrc/pgzip.cpp)
+    under AddressSanitizer + UBSan, as a stand-alone program with the sanitizer runtimes linked statically and nothing preloaded:
+    FASTA and FASTQ, each plain, wrapped, with CRLF line ends, without a final newline, truncated and with a record that has no
+    comment behind ones that have (the stale buffers), and each of those gzip'd, read by the whole-file reader, the stream and the
+    index in pieces of 200 bytes.  Exit status 0, an `ok` line per file with the records and bases tests/fastx.py reads from
+    it, no sanitizer report.  (The objects are compiled side by side and without optimisation: one -O1 -g run over all of them
+    is more than 20 s.)"""
+    import gzip
+    from tests import fastx
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    flags = ["-std=c++17", "-O0", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer",
+             "-I" + os.path.join(ROOT, "include")]
+    srcs = [os.path.join(ROOT, "crass_amd", "csrc", s + ".cpp") for s in HOST_READER] + [os.path.join(ROOT, "tools", "sanitize", "ingest_main.cpp")]
+    objs = [str(tmp_path / (os.path.basename(s) + ".o")) for s in srcs]
+    jobs = [subprocess.Popen([cxx] + flags + ["-c", s, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for s, o in zip(srcs, objs)]
+    for s, j in zip(srcs, jobs):
+        msg = j.communicate()[0]
+        assert j.returncode == 0, (s, msg[-3000:])
+    exe = str(tmp_path / "ingest_asan")
+    subprocess.check_call([cxx] + flags + objs + ["-o", exe, "-lz", "-ldl", "-lpthread"])
+
+    def seq(i):
+        return "".join("ACGT"[(i * 7 + k * k + k // 3) % 4] for k in range(20 + (i * 37) % 90)) if i % 11 else "ACGNNT" * 5
+
+    def fasta(eol="\n", wrap=0):
+        body = lambda s: eol.join(s[k:k + wrap] for k in range(0, len(s), wrap)) if wrap else s
+        return "".join(">r%d%s%s%s%s" % (i % 23, " c%d" % i if i % 3 else "", eol, body(seq(i)), eol) for i in range(40))
+
+    def fastq(eol="\n", wrap=0, comments=True):
+        body = lambda s: eol.join(s[k:k + wrap] for k in range(0, len(s), wrap)) if wrap else s
+        return "".join("@q%d%s%s%s%s+%s%s%s" % (i, " c%d" % i if comments or i < 20 else "", eol, body(seq(i)), eol, eol,
+                                               body("".join("I5#@+>~"[(i + k) % 7] for k in range(len(seq(i))))), eol) for i in range(40))
+
+    texts = {}
+    for kind, make in (("fa", fasta), ("fq", fastq)):
+        plain = make()
+        texts[kind + "_plain"] = plain
+        texts[kind + "_wrapped"] = make(wrap=17)
+        texts[kind + "_crlf"] = make(eol="\r\n")
+        texts[kind + "_no_final_newline"] = plain[:-1]
+        texts[kind + "_truncated"] = plain[:len(plain) * 2 // 3 + 5]
+    texts["fa_no_comments"] = "".join(">n%d\n%s\n" % (i, seq(i)) for i in range(40))
+    texts["fq_stale_comments"] = fastq(comments=False)
+    assert len(texts) == 12
+    paths = []
+    for name, t in sorted(texts.items()):
+        for suffix, data in ((".txt", t.encode()), (".gz", gzip.compress(t.encode(), 6))):
+            paths.append(str(tmp_path / (name + suffix)))
+            with open(paths[-1], "wb") as f:
+                f.write(data)
+    env = dict(os.environ, CRASS_FASTX_CHUNK="200", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([exe] + paths, capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(paths), lines
+    for p, line in zip(paths, lines):
+        recs = fastx.read_fastx(p[:p.rindex(".")] + ".gz")         # (the helper opens its input through gzip)
+        want = "ok   %s: whole rc 0, %d records %d bases; " % (p, len(recs), sum(len(x[2]) for x in recs))
+        assert line.startswith(want), (line, want)
+    assert not any(w in r.stderr for w in ("runtime error", "AddressSanitizer", "LeakSanitizer")), r.stderr[-3000:]

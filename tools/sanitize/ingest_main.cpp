@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan harness for the host-only ingest code (csrc/ingest.cpp + csrc/pgzip.cpp; GPU sanitizers are not available on
+// AddressSanitizer / UBSan harness for the host-only ingest code (csrc/ingest.cpp and the six files beside it + csrc/pgzip.cpp; GPU sanitizers are not available on
 // the pool): every input file given is read by the whole-file reader, the streamed reader (tiny chunks) and the index (built, all
 // records fetched from the mapping, the mapping dropped, fetched again from the file); gzip'd inputs go through the BGZF / several-thread /
 // serial inflate as their format and the environment decide.  Prints one line per file; any sanitizer report fails the run.

@@ -3,7 +3,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 out=${TMPDIR:-/tmp}/crass_sanitize; rm -rf $out; mkdir -p $out
-g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/ingest.cpp crass_amd/csrc/pgzip.cpp tools/sanitize/ingest_main.cpp -o $out/ingest_asan -lz -ldl -lpthread
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/{ingest,fastx_parse,host_inflate,fastx_read,fastx_index,fastx_stream,synth,pgzip}.cpp tools/sanitize/ingest_main.cpp -o $out/ingest_asan -lz -ldl -lpthread
 python3 - $out <<'P'
 import gzip, os, random, struct, sys, zlib
 out = sys.argv[1]
@@ -49,7 +49,7 @@ export CRASS_FASTX_CHUNK=200 CRASS_PGZIP_MIN_BYTES=1000 CRASS_PGZIP_CHUNK_BYTES=
 $out/ingest_asan $out/*.txt $out/*.gz > $out/report.txt 2> $out/sanitizer.txt || true
 grep -c "^ok  " $out/report.txt; grep "^DIFF" $out/report.txt | head; grep -c "ERROR: AddressSanitizer\|runtime error\|LeakSanitizer" $out/sanitizer.txt || true; head -40 $out/sanitizer.txt
 # ... and under ThreadSanitizer (the stream's read-ahead thread, the sharded name tables, the several-thread inflate, the index's threads)
-g++ -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Iinclude crass_amd/csrc/ingest.cpp crass_amd/csrc/pgzip.cpp tools/sanitize/ingest_main.cpp -o $out/ingest_tsan -lz -ldl -lpthread
+g++ -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Iinclude crass_amd/csrc/{ingest,fastx_parse,host_inflate,fastx_read,fastx_index,fastx_stream,synth,pgzip}.cpp tools/sanitize/ingest_main.cpp -o $out/ingest_tsan -lz -ldl -lpthread
 $out/ingest_tsan $out/s00*.txt $out/s01*.gz $out/s03*.txt $out/big.gz $out/big.bgzf.gz > $out/report_tsan.txt 2> $out/tsan.txt || true
 echo "tsan: $(grep -c '^ok  ' $out/report_tsan.txt) files ok, $(grep -c 'WARNING: ThreadSanitizer' $out/tsan.txt || true) warnings"
 # the plain-gzip host rule in members mode (gunzip.cpp, gunzip_core.h) over the sets of tests/gzip_member_sets.py, a stand-alone program on the CPU
