@@ -210,6 +210,13 @@ SYMBOLS = {
     "crass_hip_fastx_names_find": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "crass_hip_fastx_names_drop": (C.c_int, [C.c_void_p]),
     "crass_fastx_names_of": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "crass_fastx_comments_of": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "crass_hip_fastx_comments_build_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "crass_hip_fastx_comments_drop": (C.c_int, [C.c_void_p]),
+    "crass_hip_fetch_comments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
+    "crass_hip_fetch_comments_device_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "crass_hip_fastx_comments_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 2)]),
+    "crass_hip_last_comments_ms": (C.c_float, [C.c_void_p, C.c_int]),
     "crass_hip_fastx_names_of_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "crass_hip_found_names_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "crass_hip_fastx_names_find_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
@@ -334,6 +341,7 @@ SYMBOLS = {
     "crass_hip_last_cut_probe_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_group_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.c_void_p,
                                                    C.POINTER(FastxShardsC)]),
+    "crass_hip_group_fetch_comments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_hip_group_fetch_header_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_hip_group_fetch_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),
     "crass_build_outputs": (C.c_int, [C.POINTER(GraphInput), C.POINTER(OutputOpts), C.POINTER(C.c_void_p)]),

@@ -1001,15 +1001,18 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         for (size_t k = 0; k < nf; k++) want[k] = fills[k].idx;
         std::vector<uint32_t> name_len(nf);
         std::vector<uint8_t> has_qual(nf);
-        crass_text hl, ql;
+        std::vector<uint8_t> has_comment(nf);
+        crass_text hl, ql, cm;
         chk(crass_hip_fetch_header_lines_device(made.c, arena, arena_bytes, lay.rec_pos, lay.n_reads, want.data(), nf, &hl, name_len.data()), "crass_hip_fetch_header_lines_device");
         chk(crass_hip_fetch_quality_device(made.c, arena, arena_bytes, lay.rec_pos, lay.n_reads, want.data(), nf, &ql, has_qual.data()), "crass_hip_fetch_quality_device");
+        chk(crass_hip_fetch_comments_device(made.c, want.data(), nf, &cm, has_comment.data()), "crass_hip_fetch_comments_device");
         for (size_t k = 0; k < nf; k++) {
             ReadHolder &h = *fills[k].h;
             const char *line = (const char *)hl.chars + hl.off[k];
             const size_t len = (size_t)(hl.off[k + 1] - hl.off[k]), nl = std::min<size_t>(name_len[k], len);
-            h.RH_Header.assign(line, nl);                // kseq: the name ends at the first isspace() byte, the comment is the rest of the line behind it
-            if (nl < len) h.RH_Comment.assign(line + nl + 1, len - nl - 1);
+            h.RH_Header.assign(line, nl);                // kseq: the name ends at the first isspace() byte
+            // ... and the comment is the one kseq HANDS the record: its own, or the last one seen earlier in the same file
+            if (has_comment[k]) h.RH_Comment.assign((const char *)cm.chars + cm.off[k], (size_t)(cm.off[k + 1] - cm.off[k]));
             if (has_qual[k]) { h.RH_Qual.assign((const char *)ql.chars + ql.off[k], (size_t)(ql.off[k + 1] - ql.off[k])); h.RH_IsFasta = false; }
         }
         t_fill = now() - tf0;
@@ -1023,7 +1026,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         std::vector<uint8_t> rc(nf), has_qual(nf);
         std::vector<uint32_t> name_len(nf);
         for (size_t k = 0; k < nf; k++) { want[k] = fills[k].idx; rc[k] = fills[k].low ? 0 : 1; }
-        crass_text t, hl, ql;
+        std::vector<uint8_t> has_comment(nf);
+        crass_text t, hl, ql, cm;
+        chk(crass_hip_group_fetch_comments(made.g, want.data(), nf, &cm, has_comment.data()), "crass_hip_group_fetch_comments");
         chk(crass_hip_group_fetch_text(made.g, want.data(), rc.data(), nf, &t), "crass_hip_group_fetch_text");
         chk(crass_hip_group_fetch_header_lines(made.g, want.data(), nf, &hl, name_len.data()), "crass_hip_group_fetch_header_lines");
         chk(crass_hip_group_fetch_quality(made.g, want.data(), nf, &ql, has_qual.data()), "crass_hip_group_fetch_quality");
@@ -1034,7 +1039,7 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             const char *line = (const char *)hl.chars + hl.off[k];
             const size_t len = (size_t)(hl.off[k + 1] - hl.off[k]), nl = std::min<size_t>(name_len[k], len);
             h.RH_Header.assign(line, nl);
-            if (nl < len) h.RH_Comment.assign(line + nl + 1, len - nl - 1);
+            if (has_comment[k]) h.RH_Comment.assign((const char *)cm.chars + cm.off[k], (size_t)(cm.off[k + 1] - cm.off[k]));
             if (has_qual[k]) { h.RH_Qual.assign((const char *)ql.chars + ql.off[k], (size_t)(ql.off[k + 1] - ql.off[k])); h.RH_IsFasta = false; }
         }
         t_fill = now() - tf0;

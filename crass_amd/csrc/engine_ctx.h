@@ -257,9 +257,25 @@ struct Ingest {
     StageTimer<2> tm_find;
     float last_names_ms[2] = {0, 0};         // the last build's insert launches, the last find's kernels
     LineFetch hl, ql;                        // header lines, quality strings
+    // crass_hip_fastx_comments_build_device (k_cm_bits / _tiles / _top): the own-comment bitmap, the tiles' carries and the files'
+    // read bases on the device, KEPT until crass_hip_fastx_comments_drop, the next build, any load or attach, or destroy; the bytes
+    // are the caller's or the arena's; the record positions stay on the HOST (the layout's pinned array on the arena, else a copy
+    // of the caller's) — the fetch turns the few sources into positions there.  The build's scratch (the uploaded positions, the
+    // tiles' counts, the flag word) and the fetch's (cm: the indices then the positions, the sources behind them, the starts,
+    // lengths, offsets and text) are given back before the call returns; cm's pinned sides stay, h_off and h_chars are what
+    // crass_text points at
+    DevBuf<uint64_t> ct_bits, ct_carry, ct_frb;
+    bool have_comments = false, ct_on_arena = false;
+    const uint8_t *ct_bytes = nullptr; uint64_t ct_n_bytes = 0, ct_n_reads = 0, ct_counts[2] = {0, 0}; uint32_t ct_n_files = 0;
+    std::vector<uint64_t> ct_h_rec_pos;
+    DevBuf<uint64_t> cb_rec_pos, cb_cnt; DevBuf<uint32_t> cb_flag; PinBuf<uint64_t> cb_h;
+    LineFetch cm;
+    StageTimer<2> tm_cm;
+    float last_cm_ms[2] = {0, 0};            // the last build's three launches, the last fetch's kernels
     // crass_hip_load_fastx_files: the arena (every file's text, a '\n' behind each) stays until the next load, attach or destroy
     // (drop_arena); the pinned per-file arrays crass_fastx_files_layout points at (read bases, byte bases, formats)
     DevBuf<uint8_t> fa_arena; uint64_t fa_bytes = 0; bool have_arena = false;
+    std::vector<uint64_t> fa_read_base;      // the records in front of every piece of the arena (files, or a shard's slices) and their total
     PinBuf<uint64_t> fa_h_base; PinBuf<int32_t> fa_h_format;
     // a shard of a group's files load (fastx_shards.h): the staged text of the nominal range and where each file's part lies in
     // it, a BGZF tail, the probe's per-block parts — all given back by shard_pack / shard_abort; what shard_scan found for

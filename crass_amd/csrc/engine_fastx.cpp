@@ -359,6 +359,7 @@ static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, 
     HIPCHK(c, c->in.fa_h_base.ensure(2 * ((uint64_t)nf + 1))); HIPCHK(c, c->in.fa_h_format.ensure(nf));
     for (uint32_t f = 0; f <= nf; f++) { c->in.fa_h_base.p[f] = rbase[f]; c->in.fa_h_base.p[nf + 1 + f] = base[f]; }
     for (uint32_t f = 0; f < nf; f++) c->in.fa_h_format.p[f] = P.f[f].format;
+    c->in.fa_read_base.assign(rbase.begin(), rbase.begin() + nf + 1);
     if (out) {
         out->n_reads = nr; out->max_len = (uint32_t)max_len; out->rec_pos = rec_pos; out->seq_off = seq_off;
         out->file_read_base = c->in.fa_h_base.p; out->file_byte_base = c->in.fa_h_base.p + nf + 1; out->format = c->in.fa_h_format.p;

@@ -16,8 +16,19 @@ void names_drop(crass_hip_ctx *c)
     c->in.have_names = false; c->in.nt_on_arena = false; c->in.nt_bytes = nullptr; c->in.nt_n_bytes = c->in.nt_n_reads = c->in.nt_mask = 0;
 }
 
+// the comment structure goes with every load and attach, whatever it was built on (crass_hip_fastx_comments_build_device)
+void comments_drop(crass_hip_ctx *c)
+{
+    Ingest &I = c->in;
+    if (I.ct_bits.p || I.ct_carry.p || I.ct_frb.p) { (void)hipStreamSynchronize(c->stream); I.ct_bits.release(); I.ct_carry.release(); I.ct_frb.release(); }
+    I.have_comments = false; I.ct_on_arena = false; I.ct_bytes = nullptr; I.ct_n_bytes = I.ct_n_reads = 0; I.ct_n_files = 0;
+    I.ct_counts[0] = I.ct_counts[1] = 0;
+    std::vector<uint64_t>().swap(I.ct_h_rec_pos);
+}
+
 void drop_arena(crass_hip_ctx *c)
 {
+    comments_drop(c);
     if (c->in.have_names && c->in.nt_on_arena) names_drop(c);      // (a name table built on the arena refers to its bytes)
     if (c->in.fa_arena.p) { (void)hipStreamSynchronize(c->stream); c->in.fa_arena.release(); }
     c->in.have_arena = false; c->in.fa_bytes = 0; c->in.sh_loaded = false;
@@ -82,6 +93,13 @@ void release_names_of(crass_hip_ctx *c)
 
 void release_lines(crass_hip_ctx *c, LineFetch &B) { wait_main(c); B.release_device(); }
 
+void release_comments_build(crass_hip_ctx *c)
+{
+    Ingest &I = c->in;
+    wait_main(c);
+    I.cb_rec_pos.release(); I.cb_cnt.release(); I.cb_flag.release();
+}
+
 // a shard's staged text, its BGZF tail and the probe's parts (fastx_shards.h)
 void release_shard(crass_hip_ctx *c)
 {
@@ -95,6 +113,7 @@ void ingest_free_all(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
     release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c); release_names_of(c);
+    release_comments_build(c); I.cb_h.release(); I.cm.free_all(); I.tm_cm.destroy();
     names_drop(c); drop_arena(c);
     release_shard(c); I.sh_h_part.release(); I.tm_probe.destroy();
     I.hl.free_all(); I.ql.free_all();

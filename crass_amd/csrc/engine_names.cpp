@@ -1,7 +1,9 @@
 // engine_names.cpp — the names of device-resident FASTA / FASTQ records (fastx_names.hip): header ids, given or computed from
 // a file's raw bytes; the name table kept on the device, names looked up in it and names read out of it, from the host or with
-// everything in device memory; header lines and quality strings of selected records.
+// everything in device memory; header lines and quality strings of selected records; the comment kseq hands on from record to
+// record (the own-comment bitmap and the tiles' carries kept on the device, the handed comments of listed records).
 #include "ingest_internal.h"
+#include "fastx_scan.h"
 
 extern "C" {
 
@@ -455,6 +457,183 @@ int crass_hip_fetch_quality_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, 
     if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
     static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
     return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, has_qual_out);
+}
+
+// ---- the comment kseq hands on from record to record (fastx_scan.h; k_cm_* of fastx_names.hip) ----
+// The structure is built aside and replaces the one before only when every record position was accepted: a build that fails
+// leaves the context as it was.  Queued and waited for here: the positions up, the three launches, the flag and the total back.
+static int comments_build_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
+                               const uint64_t *frb, uint32_t n_files, DevBuf<uint64_t> &bits, DevBuf<uint64_t> &carry, DevBuf<uint64_t> &d_frb,
+                               uint64_t *n_own)
+{
+    Ingest &I = c->in;
+    const uint64_t words = (n + 63) / 64, tiles = (n + kFxCmTile - 1) / kFxCmTile;
+    HIPCHK(c, bits.ensure(words)); HIPCHK(c, carry.ensure(tiles)); HIPCHK(c, d_frb.ensure((uint64_t)n_files + 1));
+    HIPCHK(c, I.cb_rec_pos.ensure(n)); HIPCHK(c, I.cb_cnt.ensure(tiles + 1)); HIPCHK(c, I.cb_flag.ensure(1)); HIPCHK(c, I.cb_h.ensure(2));
+    CmBuildJob J{};
+    J.bytes = d_bytes; J.n_bytes = n_bytes; J.rec_pos = I.cb_rec_pos.p; J.n_reads = n;
+    J.bits = bits.p; J.carry = carry.p; J.tile_cnt = I.cb_cnt.p; J.flag = I.cb_flag.p;
+    I.cb_h.p[1] = 0;
+    HIPCHK(c, hipMemcpyAsync(I.cb_rec_pos.p, rec_pos, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_frb.p, frb, ((uint64_t)n_files + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(I.cb_flag.p, 0, 4, c->stream));
+    HIPCHK(c, I.tm_cm.begin(c->timing_level >= 1, c->stream));
+    HIPCHK(c, launch_cm_build(J, c->stream));
+    HIPCHK(c, I.tm_cm.mark(c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.cb_h.p, I.cb_cnt.p + tiles, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(I.cb_h.p + 1, I.cb_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, I.tm_cm.elapsed(0, 1, &I.last_cm_ms[0]));
+    if (I.cb_h.p[1]) return CRASS_ERR_INVALID_ARG;      // a rec_pos[r] >= n_bytes
+    *n_own = I.cb_h.p[0];
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_comments_build_device(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                          const uint64_t *file_read_base, uint32_t n_files)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    const bool on_arena = !d_bytes && !rec_pos;
+    const uint64_t one_file[2] = {0, n_reads};
+    if (on_arena) {                                     // the arena and layout of the last crass_hip_load_fastx_files (or of a shard)
+        if (!I.have_arena || !c->have_reads || I.fa_read_base.empty() || I.fa_read_base.back() != c->R.n_reads) return CRASS_ERR_STATE;
+        d_bytes = I.fa_arena.p; n_bytes = I.fa_bytes; rec_pos = I.x_h_rec_pos.p; n_reads = c->R.n_reads;
+        file_read_base = I.fa_read_base.data(); n_files = (uint32_t)(I.fa_read_base.size() - 1);
+    } else if (!file_read_base) { file_read_base = one_file; n_files = 1; }
+    if (n_reads && (!d_bytes || !rec_pos)) return CRASS_ERR_INVALID_ARG;
+    if (n_reads >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;
+    if (n_files == 0 ? n_reads != 0 : (file_read_base[0] != 0 || file_read_base[n_files] != n_reads)) return CRASS_ERR_INVALID_ARG;
+    for (uint32_t f = 0; f < n_files; f++) if (file_read_base[f + 1] < file_read_base[f]) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    I.last_cm_ms[0] = 0;
+    DevBuf<uint64_t> bits, carry, d_frb;
+    std::vector<uint64_t> h_rec_pos;
+    uint64_t n_own = 0;
+    int s = CRASS_OK;
+    if (n_reads) {
+        if (!on_arena) { try { h_rec_pos.assign(rec_pos, rec_pos + n_reads); } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; } }
+        s = comments_build_impl(c, d_bytes, n_bytes, rec_pos, n_reads, file_read_base, n_files, bits, carry, d_frb, &n_own);
+    }
+    release_comments_build(c);                          // the scratch goes back on every way out (the structure built here is a local)
+    if (s) { bits.release(); carry.release(); d_frb.release(); return s; }
+    comments_drop(c);
+    I.ct_bits = bits; I.ct_carry = carry; I.ct_frb = d_frb;      // (DevBuf owns nothing by itself: comments_drop gives them back)
+    I.ct_h_rec_pos.swap(h_rec_pos);
+    I.have_comments = true; I.ct_on_arena = on_arena;
+    I.ct_bytes = d_bytes; I.ct_n_bytes = n_bytes; I.ct_n_reads = n_reads; I.ct_n_files = n_files;
+    I.ct_counts[0] = n_own; I.ct_counts[1] = n_reads;
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_comments_drop(crass_hip_ctx *c)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    comments_drop(c);
+    return CRASS_OK;
+}
+
+int crass_hip_fastx_comments_counters(const crass_hip_ctx *c, uint64_t out[2])
+{
+    if (!c || !out) return CRASS_ERR_INVALID_ARG;
+    if (!c->in.have_comments) return CRASS_ERR_STATE;
+    out[0] = c->in.ct_counts[0]; out[1] = c->in.ct_counts[1];
+    return CRASS_OK;
+}
+
+float crass_hip_last_comments_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 2 ? c->in.last_cm_ms[part] : 0.0f; }
+
+// the fetch: the indices up, the sources back, their positions up (the host keeps the record positions), the lengths back (they
+// size the result), their prefix sum on the host, the copy launch, the text back or into the caller's device buffer — the shape
+// of fetch_lines with one step in front.  Every check comes before the first launch.
+static int comments_fetch_impl(crass_hip_ctx *c, const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
+                               uint8_t *has_out)
+{
+    Ingest &I = c->in;
+    LineFetch &B = I.cm;
+    const uint64_t *rec_pos = I.ct_on_arena ? I.x_h_rec_pos.p : I.ct_h_rec_pos.data();
+    HIPCHK(c, B.h_off.ensure(n + 1));
+    uint64_t *off = B.h_off.p;
+    off[0] = 0;
+    if (n) {
+        HIPCHK(c, B.h_src.ensure(2 * n)); HIPCHK(c, B.h_len.ensure(n));
+        HIPCHK(c, B.src.ensure(2 * n)); HIPCHK(c, B.start.ensure(n)); HIPCHK(c, B.len.ensure(n));
+        CmFetchJob J{};
+        J.bytes = I.ct_bytes; J.n_bytes = I.ct_n_bytes; J.bits = I.ct_bits.p; J.carry = I.ct_carry.p; J.n_reads = I.ct_n_reads;
+        J.file_read_base = I.ct_frb.p; J.n_files = I.ct_n_files;
+        J.idx = B.src.p; J.n = n; J.src = B.src.p + n; J.pos = B.src.p; J.start = B.start.p; J.len = B.len.p;
+        memcpy(B.h_src.p, idx, n * 8);
+        HIPCHK(c, hipMemcpyAsync(B.src.p, B.h_src.p, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, I.tm_cm.begin(c->timing_level >= 1, c->stream));
+        HIPCHK(c, launch_cm_source(J, c->stream));
+        HIPCHK(c, hipMemcpyAsync(B.h_src.p + n, B.src.p + n, n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the sources become positions on the host)
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t src = B.h_src.p[n + k];
+            const bool has = src < I.ct_n_reads;
+            if (has_out) has_out[k] = has ? 1 : 0;
+            B.h_src.p[k] = has ? rec_pos[src] + 1 : kFxNone;
+        }
+        HIPCHK(c, hipMemcpyAsync(B.src.p, B.h_src.p, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_cm_measure(J, c->stream));
+        HIPCHK(c, hipMemcpyAsync(B.h_len.p, B.len.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (the lengths size the result)
+        for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + B.h_len.p[k];
+        const uint64_t total = off[n];
+        if (off_user) memcpy(off_user, off, (n + 1) * 8);
+        if (d_user && cap < total) return CRASS_ERR_OVERFLOW;
+        if (!d_user) HIPCHK(c, B.h_chars.ensure(total));
+        if (out) { out->n = n; out->chars = B.h_chars.p; out->off = off; }
+        if (total) {
+            HIPCHK(c, B.off.ensure(n + 1));
+            if (!d_user) HIPCHK(c, B.chars.ensure(total));
+            HIPCHK(c, hipMemcpyAsync(B.off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            J.off = B.off.p; J.total = total; J.out = d_user ? d_user : B.chars.p;
+            HIPCHK(c, launch_cm_copy(J, c->stream));
+            if (!d_user) HIPCHK(c, hipMemcpyAsync(B.h_chars.p, B.chars.p, total, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, I.tm_cm.mark(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, I.tm_cm.elapsed(0, 1, &I.last_cm_ms[1]));
+        return CRASS_OK;
+    }
+    if (off_user) off_user[0] = 0;
+    if (!d_user) HIPCHK(c, B.h_chars.ensure(0));
+    if (out) { out->n = 0; out->chars = B.h_chars.p; out->off = off; }
+    return CRASS_OK;
+}
+
+static int comments_fetch_common(crass_hip_ctx *c, const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out,
+                                 uint8_t *has_out)
+{
+    if (!c || (n && !idx)) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    if (!I.have_comments) {                             // the first fetch after a files load builds on the resident arena
+        if (!I.have_arena || !c->have_reads) return CRASS_ERR_STATE;
+        const int bs = crass_hip_fastx_comments_build_device(c, nullptr, 0, nullptr, 0, nullptr, 0);
+        if (bs) return bs;
+    }
+    for (uint64_t k = 0; k < n; k++) if (idx[k] >= I.ct_n_reads) return CRASS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    I.last_cm_ms[1] = 0;
+    const int s = comments_fetch_impl(c, idx, n, d_user, cap, off_user, out, has_out);
+    release_lines(c, I.cm);                             // the scratch goes back on every way out; the structure and the pinned sides stay
+    return s;
+}
+
+int crass_hip_fetch_comments_device(crass_hip_ctx *c, const uint64_t *idx, uint64_t n, crass_text *out, uint8_t *has_out)
+{
+    if (!out) return CRASS_ERR_INVALID_ARG;
+    return comments_fetch_common(c, idx, n, nullptr, 0, nullptr, out, has_out);
+}
+
+int crass_hip_fetch_comments_device_to(crass_hip_ctx *c, const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes, uint64_t *off_out,
+                                       uint8_t *has_out)
+{
+    if (!off_out || (!d_chars && cap_bytes)) return CRASS_ERR_INVALID_ARG;
+    static uint8_t nowhere;                             // (a NULL buffer of capacity 0 asks for the offsets alone, as in crass_hip_fetch_text_device)
+    return comments_fetch_common(c, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, has_out);
 }
 
 } // extern "C"

@@ -177,6 +177,7 @@ int shard_scan(crass_hip_ctx *c, const ShardFile *files, uint32_t n_files, Shard
         }
         base.resize((size_t)ns + 1);
         I.sh_n_reads = 0;
+        I.fa_read_base.assign(1, 0);
         if (ns == 0) { I.sh_scanned = v->file < 0; return CRASS_OK; }
         ArenaScan A;
         const int os = A.open(c, arena, base.data(), ns);
@@ -199,6 +200,7 @@ int shard_scan(crass_hip_ctx *c, const ShardFile *files, uint32_t n_files, Shard
         for (uint32_t i = 0; i < ns; i++) file_reads->push_back(std::make_pair(sl[i].f, R.rbase[i + 1] - R.rbase[i]));
         *n_reads = R.n_reads; *max_len = (uint32_t)R.max_len;
         I.sh_n_reads = R.n_reads; I.sh_scanned = true;
+        I.fa_read_base.assign(R.rbase.begin(), R.rbase.begin() + ns + 1);
     } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
     return CRASS_OK;
 }

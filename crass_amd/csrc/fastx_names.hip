@@ -36,6 +36,14 @@
 // name's length.  The host sums the lengths.  k_hl_copy: driven by the OUTPUT, a lane per byte finds its record in the offsets;
 // nothing outside [out, out + total) is stored.  Neither is hot: about one read in a hundred is handed on.
 //
+// handed comments (RH_Comment as kseq hands it on, fastx_scan.h) — build: k_cm_bits, a lane per record walks its name as
+// k_hl_measure does, fx_own_comment decides, the wave's ballot is one word of the own-comment bitmap; k_cm_tiles, a wave per tile
+// of kFxCmTile records: the tile's last own-comment record and their number; k_cm_top, one block: the running maximum over the
+// tiles (the carries) and the total.  Three launches, no block waits for another, no atomics.  fetch: k_cm_source, a lane per
+// listed record: fx_comment_handed_from, the statements the host runs; the host turns the sources into positions (it keeps the
+// record positions, the device does not); k_cm_measure walks the source's name and comment, k_cm_copy is k_hl_copy from the
+// comments' starts.  Names of any length take the lane walk.
+//
 // quality strings (RH_Qual) — the same shape.  k_ql_measure: a lane per selected record; a record whose header character is '@'
 // has its quality on its fourth line, found by three line ends from the header character and bounded by the next record's header
 // character: the string is the bytes 33..126 of that line, as kseq keeps them (a '\r' in front of the '\n' is none).  A '>'
@@ -44,6 +52,7 @@
 // [src, min(lim, n_bytes)) of a record is read.
 #include "fastx_names_launch.h"
 #include "devmem.h"
+#include "fastx_scan.h"
 
 namespace crass {
 
@@ -606,6 +615,142 @@ __global__ __launch_bounds__(kNmThreads) void k_ql_copy(const QlJob J)
     if (p < end) J.out[i] = J.bytes[p];
 }
 
+// ---- the comment kseq hands on (fastx_scan.h: fx_own_comment, fx_comment_handed_from) ----
+// where the name that starts at pos ends: the position of its first isspace() byte, or n_bytes (pos <= n_bytes)
+static __device__ __forceinline__ uint64_t cm_name_end(uintptr_t lo, uint64_t n_bytes, uint64_t pos)
+{
+    NmCur c;
+    c.init(lo, lo + n_bytes, pos);
+    uint64_t name = 0;
+    for (;;) {
+        uint32_t avail;
+        const uint32_t w = c.next(&avail);
+        const uint32_t nb = nm_name_bytes(w, avail);
+        name += nb;
+        if (nb < 4) break;
+    }
+    return pos + name;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_cm_bits(const CmBuildJob J)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;      // (no lane leaves: the wave's 64 records are one word)
+    bool own = false;
+    if (r < J.n_reads) {
+        const uint64_t pos = J.rec_pos[r];
+        if (pos >= J.n_bytes) *J.flag = 1u;
+        else {
+            const uint64_t e = cm_name_end((uintptr_t)J.bytes, J.n_bytes, pos + 1);
+            own = fx_own_comment(e, J.n_bytes, e < J.n_bytes ? J.bytes[e] : (uint8_t)0);
+        }
+    }
+    const unsigned long long m = __ballot(own);
+    if ((threadIdx.x & 63u) == 0 && r < J.n_reads) J.bits[r >> 6] = m;
+}
+
+static __device__ __forceinline__ uint64_t cm_wave_max64(uint64_t v)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t a = (uint32_t)__shfl_xor((int)(uint32_t)v, s), b = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), s);
+        const uint64_t o = ((uint64_t)b << 32) | a;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// a wave per tile, a bitmap word per lane: 1 + the tile's last own-comment record (0: none) and how many it has
+__global__ __launch_bounds__(kNmThreads) void k_cm_tiles(const CmBuildJob J, const uint64_t n_words, const uint64_t n_tiles)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t t = (uint64_t)blockIdx.x * (kNmThreads / 64) + (threadIdx.x >> 6);
+    if (t >= n_tiles) return;                           // (the whole wave)
+    const uint64_t wi = t * (kFxCmTile / 64) + lane;
+    const uint64_t v = wi < n_words ? J.bits[wi] : 0ull;
+    const uint64_t last = cm_wave_max64(v ? wi * 64 + (63u - (uint32_t)__builtin_clzll(v)) + 1 : 0ull);
+    const uint64_t cnt = nm_wave_sum64((uint64_t)__builtin_popcountll(v));
+    if (lane == 0) { J.carry[t] = last; J.tile_cnt[t] = cnt; }
+}
+
+// one block, 256 tiles a step: carry[t] becomes the maximum over the tiles up to and including t, tile_cnt[n_tiles] the total
+__global__ __launch_bounds__(kNmThreads) void k_cm_top(const CmBuildJob J, const uint64_t n_tiles)
+{
+    __shared__ uint64_t sh[kNmThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t run = 0, cnt = 0;
+    for (uint64_t t0 = 0; t0 < n_tiles; t0 += kNmThreads) {      // (the same trip count in every lane)
+        const uint64_t t = t0 + threadIdx.x;
+        uint64_t inc = t < n_tiles ? J.carry[t] : 0ull;
+        cnt += t < n_tiles ? J.tile_cnt[t] : 0ull;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t a = (uint32_t)__shfl_up((int)(uint32_t)inc, s), b = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), s);
+            const uint64_t o = ((uint64_t)b << 32) | a;
+            if (lane >= (uint32_t)s && o > inc) inc = o;
+        }
+        __syncthreads();                                // (sh may still be read from the step before)
+        if (lane == 63u) sh[wave] = inc;
+        __syncthreads();
+        uint64_t all = run;
+#pragma unroll
+        for (uint32_t w = 0; w < kNmThreads / 64; w++) { const uint64_t s = sh[w]; if (w < wave && s > inc) inc = s; if (s > all) all = s; }
+        if (run > inc) inc = run;
+        if (t < n_tiles) J.carry[t] = inc;
+        run = all;
+    }
+    const uint64_t total = nm_block_sum64(cnt, sh);
+    if (threadIdx.x == 0) J.tile_cnt[n_tiles] = total;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_cm_source(const CmFetchJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uint64_t r = J.idx[k];
+    J.src[k] = r < J.n_reads ? fx_comment_handed_from(J.bits, J.carry, J.file_read_base, J.n_files, r) : kFxNone;
+}
+
+// pos[k]: the first byte behind the header character of entry k's source, kFxNone where nothing is handed
+__global__ __launch_bounds__(kNmThreads) void k_cm_measure(const CmFetchJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uint64_t pos = J.pos[k];
+    uint64_t start = 0, line = 0;
+    if (pos <= J.n_bytes) {                             // (kFxNone is beyond every input)
+        const uintptr_t lo = (uintptr_t)J.bytes;
+        const uint64_t e = cm_name_end(lo, J.n_bytes, pos);
+        if (fx_own_comment(e, J.n_bytes, e < J.n_bytes ? J.bytes[e] : (uint8_t)0)) {      // (so for every source: its bit says so)
+            start = e + 1;
+            NmCur c;
+            c.init(lo, lo + J.n_bytes, start);
+            for (;;) {
+                uint32_t avail;
+                const uint32_t w = c.next(&avail);
+                const uint32_t lb = nm_line_bytes(w, avail);
+                line += lb;
+                if (lb < 4) break;
+            }
+        }
+    }
+    J.start[k] = start;
+    J.len[k] = line > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)line;
+}
+
+__global__ __launch_bounds__(kNmThreads) void k_cm_copy(const CmFetchJob J)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (i >= J.total) return;
+    uint64_t a = 0, b = J.n - 1;                        // the last entry whose offset is <= i, as in k_hl_copy
+    while (a < b) {
+        const uint64_t mid = (a + b + 1) >> 1;
+        if (J.off[mid] <= i) a = mid; else b = mid - 1;
+    }
+    const uint64_t p = J.start[a] + (i - J.off[a]);
+    if (p < J.n_bytes) J.out[i] = J.bytes[p];
+}
+
+
 uint32_t hid_lane_max() { return kHidLaneMax; }
 uint32_t hid_lane_end() { return kHidLaneEnd; }
 
@@ -730,6 +875,41 @@ hipError_t launch_ql_copy(const QlJob &J, hipStream_t st)
     unsigned g;
     if (!J.n || !nm_grid(J.total, kNmThreads, &g)) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_ql_copy, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_cm_build(const CmBuildJob &J, hipStream_t st)
+{
+    unsigned g, gt;
+    const uint64_t n_words = (J.n_reads + 63) / 64, n_tiles = (J.n_reads + kFxCmTile - 1) / kFxCmTile;
+    if (!nm_grid(J.n_reads, kNmThreads, &g) || !nm_grid(n_tiles, kNmThreads / 64, &gt) || !J.bits || !J.carry || !J.tile_cnt || !J.flag) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_cm_bits, dim3(g), dim3(kNmThreads), 0, st, J);
+    CRASS_LAUNCH(k_cm_tiles, dim3(gt), dim3(kNmThreads), 0, st, J, n_words, n_tiles);
+    CRASS_LAUNCH(k_cm_top, dim3(1), dim3(kNmThreads), 0, st, J, n_tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_cm_source(const CmFetchJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmThreads, &g) || !J.n_files || !J.n_reads) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_cm_source, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_cm_measure(const CmFetchJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!nm_grid(J.n, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_cm_measure, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_cm_copy(const CmFetchJob &J, hipStream_t st)
+{
+    unsigned g;
+    if (!J.n || !nm_grid(J.total, kNmThreads, &g)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_cm_copy, dim3(g), dim3(kNmThreads), 0, st, J);
     return hipGetLastError();
 }
 

@@ -99,4 +99,32 @@ struct QlJob {
 hipError_t launch_ql_measure(const QlJob &J, hipStream_t st);
 hipError_t launch_ql_copy(const QlJob &J, hipStream_t st);
 
+// k_cm_bits / k_cm_tiles / k_cm_top: the own-comment bitmap of a file's records and the carry of every tile of kFxCmTile
+// (fastx_scan.h) records
+struct CmBuildJob {
+    const uint8_t *bytes; uint64_t n_bytes;
+    const uint64_t *rec_pos; uint64_t n_reads;   // [n_reads] position of every record's header character (scratch of the build)
+    uint64_t *bits;                              // [(n_reads + 63) / 64] bit r & 63 of word r >> 6: record r has a comment of its own
+    uint64_t *carry;                             // [tiles] 1 + the last such record in the tiles up to and including this one, 0: none
+    uint64_t *tile_cnt;                          // [tiles + 1] scratch: such records per tile, [tiles] their total
+    uint32_t *flag;                              // set to 1 by a rec_pos at or beyond n_bytes; 0 before the launch
+};
+hipError_t launch_cm_build(const CmBuildJob &J, hipStream_t st);      // the three launches
+
+// k_cm_source / k_cm_measure / k_cm_copy: the comments handed to listed records
+struct CmFetchJob {
+    const uint8_t *bytes; uint64_t n_bytes;
+    const uint64_t *bits, *carry; uint64_t n_reads;      // as built
+    const uint64_t *file_read_base; uint32_t n_files;    // [n_files + 1] from 0 to n_reads, not decreasing
+    const uint64_t *idx; uint64_t n;             // [n] local record numbers, any order, repeats allowed
+    uint64_t *src;                               // [n] k_cm_source: the record whose own comment entry k is handed, ~0: none
+    const uint64_t *pos;                         // [n] k_cm_measure: the first byte behind that record's header character, ~0: none
+    uint64_t *start; uint32_t *len;              // [n] k_cm_measure: where the comment starts and its bytes
+    const uint64_t *off; uint64_t total;         // [n + 1] k_cm_copy: where the comments lie in out; off[n]
+    uint8_t *out;                                // [total], any alignment
+};
+hipError_t launch_cm_source(const CmFetchJob &J, hipStream_t st);
+hipError_t launch_cm_measure(const CmFetchJob &J, hipStream_t st);
+hipError_t launch_cm_copy(const CmFetchJob &J, hipStream_t st);
+
 } // namespace crass

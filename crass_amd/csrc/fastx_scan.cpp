@@ -327,4 +327,49 @@ int crass_fastx_names_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t 
     return off_out[n] > cap_bytes ? CRASS_ERR_OVERFLOW : CRASS_OK;
 }
 
+// the comment kseq hands on (fastx_scan.h states the rule): the bitmap and the carries of ALL records first, serially — the
+// structure the device builds with k_cm_bits / k_cm_tiles / k_cm_top —, then every listed record looks its source up in it
+int crass_fastx_comments_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint64_t *file_read_base,
+                            uint32_t n_files, const uint64_t *idx, uint64_t n, uint64_t idx_base, uint8_t *out, uint64_t cap_bytes,
+                            uint64_t *off_out, uint8_t *has_out)
+{
+    if (!off_out || (n && !idx) || (n_reads && (!bytes || !rec_pos)) || (cap_bytes && !out)) return CRASS_ERR_INVALID_ARG;
+    const uint64_t one_file[2] = {0, n_reads};
+    if (!file_read_base) { file_read_base = one_file; n_files = 1; }
+    if (!n_files || file_read_base[0] != 0 || file_read_base[n_files] != n_reads) return CRASS_ERR_INVALID_ARG;
+    for (uint32_t f = 0; f < n_files; f++) if (file_read_base[f + 1] < file_read_base[f]) return CRASS_ERR_INVALID_ARG;
+    // every index and position first: nothing is written by a call that fails with CRASS_ERR_INVALID_ARG
+    for (uint64_t r = 0; r < n_reads; r++) if (rec_pos[r] >= n_bytes) return CRASS_ERR_INVALID_ARG;
+    for (uint64_t k = 0; k < n; k++) if (idx[k] < idx_base || idx[k] - idx_base >= n_reads) return CRASS_ERR_INVALID_ARG;
+    off_out[0] = 0;
+    if (n == 0) return CRASS_OK;
+    // where record r's name ends: the position of the first isspace() byte behind the header character, or n_bytes
+    auto name_end = [&](uint64_t r) { uint64_t e = rec_pos[r] + 1; while (e < n_bytes && !crass::fx_is_space(bytes[e])) e++; return e; };
+    std::vector<uint64_t> bits, carry;
+    try {
+        bits.assign((n_reads + 63) / 64, 0); carry.assign((n_reads + crass::kFxCmTile - 1) / crass::kFxCmTile, 0);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    uint64_t last = 0;                                  // 1 + the last own-comment record so far
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t e = name_end(r);
+        if (crass::fx_own_comment(e, n_bytes, e < n_bytes ? bytes[e] : 0)) { bits[r >> 6] |= 1ull << (r & 63); last = r + 1; }
+        if ((r + 1) % crass::kFxCmTile == 0 || r + 1 == n_reads) carry[r / crass::kFxCmTile] = last;
+    }
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t src = crass::fx_comment_handed_from(bits.data(), carry.data(), file_read_base, n_files, idx[k] - idx_base);
+        const uint64_t at = off_out[k];
+        uint64_t len = 0;
+        if (src != crass::kFxNone) {
+            const uint64_t a = name_end(src) + 1;       // (an own-comment record: its name ends in front of n_bytes)
+            uint64_t b = a;
+            while (b < n_bytes && !crass::fx_is_nl(bytes[b])) b++;
+            len = b - a;
+            if (at < cap_bytes) memcpy(out + at, bytes + a, (size_t)std::min(len, cap_bytes - at));      // (nothing at or beyond out + cap_bytes)
+        }
+        if (has_out) has_out[k] = src != crass::kFxNone ? 1 : 0;
+        off_out[k + 1] = at + len;
+    }
+    return off_out[n] > cap_bytes ? CRASS_ERR_OVERFLOW : CRASS_OK;
+}
+
 } // extern "C"

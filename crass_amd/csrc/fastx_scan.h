@@ -113,4 +113,51 @@ struct FxHostScan {
 };
 int fastx_scan_serial(const uint8_t *bytes, uint64_t n_bytes, FxHostScan *out);      // CRASS_OK, CRASS_ERR_UNSUPPORTED (declined), CRASS_ERR_OOM
 
+CRASS_HD inline bool fx_is_space(uint8_t b) { return b == 0x20 || (b >= 0x09 && b <= 0x0D); }       // isspace(): ends kseq's name
+
+// ---- the comment kseq hands on (crass_fastx_comments_of, the k_cm_* kernels of fastx_names.hip) ----
+// A record's NAME is the bytes behind its header character up to the first fx_is_space() byte or the end of the file's text.
+// The record has an OWN comment iff its name ends at a byte that exists and is not '\n' (kseq.cpp:179-186: the delimiter that
+// ended the name decides whether the rest of the line is read).  The own comment is the bytes behind that delimiter up to, not
+// including, the line's '\n' or the end of the text; it may be empty, and a '\r' in front of the '\n' stays in it.
+// kseq never clears comment.s, so the comment HANDED to record r is the own comment of the last record r' <= r of the SAME
+// file that has one; a record in front of its file's first comment is handed none.
+// name_end: the position of the byte that ended the name, n_bytes: the end of the text, end_byte: that byte where it exists
+CRASS_HD inline bool fx_own_comment(uint64_t name_end, uint64_t n_bytes, uint8_t end_byte) { return name_end < n_bytes && !fx_is_nl(end_byte); }
+
+// the structure both sides look a record's source up in: one bit per record (bit r & 63 of word r >> 6: record r has an own
+// comment) and one CARRY word per tile of kFxCmTile records: 1 + the last own-comment record in all tiles up to and including
+// that one, 0 where there is none.  File boundaries are not in it: whoever looks up drops a source in front of the file's first
+// record.  The last own-comment record at or in front of r, or kFxNone: r's own word masked to the bits at or below its
+// position, then the earlier words of its tile (at most 63), then the carry of the tile in front.
+static const uint64_t kFxCmTile = 4096;
+CRASS_HD inline uint64_t fx_comment_source(const uint64_t *bits, const uint64_t *carry, uint64_t r)
+{
+    uint64_t w = r >> 6;
+    const uint64_t tile = r / kFxCmTile, w0 = tile * (kFxCmTile / 64);
+    uint64_t m = bits[w] & (~0ull >> (63u - (uint32_t)(r & 63u)));
+    while (!m && w > w0) m = bits[--w];
+    if (m) return w * 64 + (63u - (uint32_t)__builtin_clzll(m));
+    if (tile == 0) return kFxNone;
+    const uint64_t c = carry[tile - 1];
+    return c ? c - 1 : kFxNone;
+}
+// the first record of the file that holds record r: file_read_base[0] == 0 <= r < file_read_base[n_files], not decreasing
+// (files of no records share their base with the next)
+CRASS_HD inline uint64_t fx_file_first_read(const uint64_t *file_read_base, uint32_t n_files, uint64_t r)
+{
+    uint32_t a = 0, b = n_files;                        // the last f with file_read_base[f] <= r
+    while (a < b) {
+        const uint32_t mid = (a + b + 1) >> 1;
+        if (file_read_base[mid] <= r) a = mid; else b = mid - 1;
+    }
+    return file_read_base[a];
+}
+// what r is handed: its source unless that lies in front of its file's first record
+CRASS_HD inline uint64_t fx_comment_handed_from(const uint64_t *bits, const uint64_t *carry, const uint64_t *file_read_base, uint32_t n_files, uint64_t r)
+{
+    const uint64_t src = fx_comment_source(bits, carry, r);
+    return src != kFxNone && src >= fx_file_first_read(file_read_base, n_files, r) ? src : kFxNone;
+}
+
 } // namespace crass

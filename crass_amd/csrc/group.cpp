@@ -185,6 +185,11 @@ struct crass_hip_group {
     struct Text { std::vector<uint8_t> chars; std::vector<uint64_t> off; };
     Text T;                                     // crass_hip_group_fetch_text's result
     Text TH, TQ;                                // crass_hip_group_fetch_header_lines' and crass_hip_group_fetch_quality's
+    // crass_hip_group_fetch_comments: its result, and what a files load's cuts carry — in[r] / has[r]: the comment handed to the
+    // records of rank r's FIRST file part that have no source in that part (the own comment of the last own-comment record of
+    // the same file on an earlier rank), first_n[r]: the records of that part; resolved at the first fetch after the load
+    Text TC;
+    struct { std::vector<std::string> in; std::vector<uint8_t> has; std::vector<uint64_t> first_n; bool ready = false; } CM;
     // a files load (crass_hip_group_load_fastx_files, fastx_shards.h): what the ranks share between its barriers.  Rank r writes
     // entry r of the per-rank vectors, rank 0 combines between two barriers, everybody reads behind the second
     bool files_load = false;                    // the last load was one, and was accepted
@@ -1041,7 +1046,7 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
             out->file_read_base = S.file_read_base.data(); out->format = S.format.data();
         }
     } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
-    g->loaded = true; g->files_load = true;
+    g->loaded = true; g->files_load = true; g->CM.ready = false;
     return CRASS_OK;
 }
 
@@ -1100,6 +1105,75 @@ int crass_hip_group_fetch_header_lines(crass_hip_group *g, const uint64_t *read_
 int crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_qual_out)
 {
     return group_fetch_lines(g, read_idx, n, true, out, nullptr, has_qual_out);
+}
+
+// what the cuts of a files load carry (include/crass_hip.h): rank after rank in file order, each rank "publishes" the comment handed
+// to its LAST record — the own comment of the last own-comment record of the file part its shard ends in, a host string — and
+// is handed what the ranks in front of it left for the file its shard begins in.  Empty ranks, and ranks that are one part of
+// one file without a comment, pass it through; nothing crosses a file boundary.
+static int group_comments_resolve(crass_hip_group *g)
+{
+    auto &J = g->F;
+    auto &CM = g->CM;
+    const int N = g->n;
+    CM.in.assign(N, std::string()); CM.has.assign(N, 0); CM.first_n.assign(N, 0);
+    bool carried = false; std::string text; int64_t file = -1;      // what the ranks so far leave, and for which file
+    for (int r = 0; r < N; r++) {
+        const uint64_t nr = g->first[r + 1] - g->first[r];
+        if (!nr) continue;
+        int64_t f0 = -1, fl = -1; size_t parts = 0;
+        for (const auto &fr : J.file_reads[r]) if (fr.second) { if (f0 < 0) { f0 = fr.first; CM.first_n[r] = fr.second; } fl = fr.first; parts++; }
+        if (carried && file == f0) { CM.in[r] = text; CM.has[r] = 1; }
+        const uint64_t last = nr - 1;
+        crass_text t; uint8_t has = 0;
+        const int s = crass_hip_fetch_comments_device(g->ctx[r], &last, 1, &t, &has);
+        if (s) return s;
+        if (has) { carried = true; text.assign((const char *)t.chars + t.off[0], (size_t)(t.off[1] - t.off[0])); }
+        else if (!(parts == 1 && file == f0)) { carried = false; text.clear(); }      // (else: one part of the file the carry belongs to)
+        file = fl;
+    }
+    CM.ready = true;
+    return CRASS_OK;
+}
+
+int crass_hip_group_fetch_comments(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *o, uint8_t *has_out)
+{
+    if (!g || !o || (n && !read_idx)) return CRASS_ERR_INVALID_ARG;
+    if (!g->loaded || !g->files_load) return CRASS_ERR_STATE;
+    for (uint64_t k = 0; k < n; k++) if (read_idx[k] >= g->n_reads) return CRASS_ERR_INVALID_ARG;
+    crass_hip_group::Text &T = g->TC;
+    try {
+        if (!g->CM.ready) { const int rs = group_comments_resolve(g); if (rs) return rs; }
+        std::vector<std::vector<uint64_t>> idx(g->n), at(g->n);
+        for (uint64_t k = 0; k < n; k++) {
+            const int r = (int)(std::upper_bound(g->first.begin(), g->first.end(), read_idx[k]) - g->first.begin()) - 1;
+            idx[r].push_back(read_idx[k] - g->first[r]); at[r].push_back(k);
+        }
+        // (a rank's result lives in its own context until that context's next fetch of the kind: all of them are there at once)
+        std::vector<crass_text> part(g->n, crass_text{0, nullptr, nullptr});
+        std::vector<std::vector<uint8_t>> hc(g->n);     // 0: nothing handed, 1: the rank's own text, 2: the carried string
+        T.off.assign(n + 1, 0);
+        for (int r = 0; r < g->n; r++) {
+            const uint64_t m = idx[r].size();
+            if (!m) continue;
+            hc[r].assign(m, 0);
+            const int s = crass_hip_fetch_comments_device(g->ctx[r], idx[r].data(), m, &part[r], hc[r].data());
+            if (s) return s;
+            for (uint64_t q = 0; q < m; q++) {
+                if (!hc[r][q] && g->CM.has[r] && idx[r][q] < g->CM.first_n[r]) hc[r][q] = 2;
+                T.off[at[r][q] + 1] = hc[r][q] == 2 ? g->CM.in[r].size() : part[r].off[q + 1] - part[r].off[q];
+                if (has_out) has_out[at[r][q]] = hc[r][q] ? 1 : 0;
+            }
+        }
+        for (uint64_t k = 0; k < n; k++) T.off[k + 1] += T.off[k];
+        T.chars.resize(T.off[n] + 1);
+        for (int r = 0; r < g->n; r++) for (uint64_t q = 0; q < part[r].n; q++) {
+            const uint64_t len = T.off[at[r][q] + 1] - T.off[at[r][q]];
+            if (len) memcpy(T.chars.data() + T.off[at[r][q]], hc[r][q] == 2 ? (const uint8_t *)g->CM.in[r].data() : part[r].chars + part[r].off[q], len);
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    o->n = n; o->chars = T.chars.data(); o->off = T.off.data();
+    return CRASS_OK;
 }
 
 int crass_hip_group_get_merge(crass_hip_group *g, crass_merge_view *o)

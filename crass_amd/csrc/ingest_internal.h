@@ -1,6 +1,6 @@
 // ingest_internal.h — what crosses the files of the device ingest, each declared once: engine_ingest.cpp (the scratch given
 // back, packed reads and text in, text out), engine_fastx.cpp (the scan and the FASTA / FASTQ loaders), engine_inflate.cpp
-// (BGZF and gzip inflate), engine_names.cpp (header ids, the name table, header lines, quality) and engine_shards.cpp (one
+// (BGZF and gzip inflate), engine_names.cpp (header ids, the name table, header lines, quality, comments) and engine_shards.cpp (one
 // rank's steps of a group's files load, declared in fastx_shards.h).  The context and its Ingest member are engine_ctx.h.
 // Host only: no .hip file includes this.
 #pragma once
@@ -58,9 +58,10 @@ struct ArenaScan {
 
 // (C linkage and hidden, as the block at the end of engine_ctx.h)
 extern "C" {
-// engine_ingest.cpp: the name table and the arena go; each stage's scratch goes back, after a wait for the streams that may
+// engine_ingest.cpp: the name table, the comment structure and the arena go; each stage's scratch goes back, after a wait for the streams that may
 // still use it; what opens a load; packed text in
 void names_drop(crass_hip_ctx *c);
+void comments_drop(crass_hip_ctx *c);
 void drop_arena(crass_hip_ctx *c);
 void wait_main(crass_hip_ctx *c);
 void release_text(crass_hip_ctx *c);
@@ -71,6 +72,7 @@ void release_header_ids(crass_hip_ctx *c);
 void release_names_find(crass_hip_ctx *c);
 void release_names_of(crass_hip_ctx *c);
 void release_lines(crass_hip_ctx *c, LineFetch &B);
+void release_comments_build(crass_hip_ctx *c);
 void release_shard(crass_hip_ctx *c);
 void begin_fastx_load(crass_hip_ctx *c);
 void reset_results_keep_set(crass_hip_ctx *c);

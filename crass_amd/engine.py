@@ -590,6 +590,40 @@ def names_of(buf, rec_pos, idx, idx_base=0, cap_bytes=None, out=None):
     return out[:int(off[len(ix)])], off
 
 
+def comments_of(buf, rec_pos, idx, file_read_base=None, idx_base=0, cap_bytes=None, out=None):
+    """The comment kseq HANDS to the records idx[k] - idx_base (any order, repeats allowed): the own comment of the last record at
+    or in front of it in the same file that has one (crass_fastx_comments_of; host) — the statement of the rule
+    SearchEngine.fetch_comments is tested against.  rec_pos: n_reads + 1 entries as in a FastxLayout; file_read_base: n_files + 1
+    read bases (None: one file), the bytes of several files in the arena layout (a '\n' behind each).  Returns (chars uint8, off
+    uint64 [n + 1], has uint8 [n]).  cap_bytes / out: the capacity and the buffer to write into (tests: an overflow raises
+    CrassError with status 8, its `offsets` and `has` complete and out filled up to the cap)."""
+    a = _bytes_arg(buf)
+    rp = np.ascontiguousarray(rec_pos, dtype=np.uint64)
+    n = max(len(rp) - 1, 0)
+    fb = None if file_read_base is None else np.ascontiguousarray(file_read_base, dtype=np.uint64)
+    ix = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+    off = np.zeros(len(ix) + 1, np.uint64)
+    has = np.zeros(len(ix), np.uint8)
+    lib = _abi.load()
+    args = (a.ctypes.data if len(a) else None, len(a), rp.ctypes.data if len(rp) else None, n, None if fb is None else fb.ctypes.data,
+            0 if fb is None else len(fb) - 1, ix.ctypes.data if len(ix) else None, len(ix), int(idx_base))
+    tail = (off.ctypes.data, has.ctypes.data if len(ix) else None)
+    if out is None and cap_bytes is None:          # measure, then fill
+        st = lib.crass_fastx_comments_of(*args, None, 0, *tail)
+        if st not in (0, _abi.ERR_OVERFLOW):
+            _chk(st, "crass_fastx_comments_of")
+        cap_bytes = int(off[len(ix)])
+    if out is None:
+        out = np.zeros(int(cap_bytes), np.uint8)
+    cap = len(out) if cap_bytes is None else int(cap_bytes)
+    st = lib.crass_fastx_comments_of(*args, out.ctypes.data if cap else None, cap, *tail)
+    if st != 0:
+        e = CrassError(st, "crass_fastx_comments_of")
+        e.offsets, e.has = off, has
+        raise e
+    return out[:int(off[len(ix)])], off, has
+
+
 def _device_array(x, dtype, what):
     """(address, elements) of device memory: a raw address with its element count as a tuple (addr, n), or a contiguous torch
     device tensor of that dtype"""
@@ -1367,6 +1401,64 @@ class SearchEngine:
             raise e
         return None, off, name_len
 
+    def comments_build(self, src=None, layout=None, file_read_base=None):
+        """Builds and KEEPS the own-comment bitmap and tile carries of file bytes on the DEVICE (src, layout: as
+        fetch_header_lines takes them; file_read_base: n_files + 1 read bases, None: one file) for fetch_comments
+        (crass_hip_fastx_comments_build_device).  The structure refers to the bytes: keep the tensor alive and unchanged until
+        comments_drop, the next comments_build, any load, or close.  comments_build(): the arena and layout of the last
+        load_fastx_files (fetch_comments does this by itself)."""
+        if src is None and layout is None:
+            _chk(self.lib.crass_hip_fastx_comments_build_device(self.h, None, 0, None, 0, None, 0), "crass_hip_fastx_comments_build_device")
+            self._comments_keep = None
+            return
+        ptr, nb, rp, n = self._device_bytes(src, layout)
+        fb = None if file_read_base is None else np.ascontiguousarray(file_read_base, dtype=np.uint64)
+        _chk(self.lib.crass_hip_fastx_comments_build_device(self.h, ptr, nb, rp.ctypes.data, n, None if fb is None else fb.ctypes.data,
+                                                            0 if fb is None else len(fb) - 1), "crass_hip_fastx_comments_build_device")
+        self._comments_keep = src
+
+    def comments_drop(self):
+        """Gives the structure of comments_build back (crass_hip_fastx_comments_drop); fine without one."""
+        _chk(self.lib.crass_hip_fastx_comments_drop(self.h), "crass_hip_fastx_comments_drop")
+        self._comments_keep = None
+
+    def comments_counters(self):
+        """(records with a comment of their own, records) of the built structure (crass_hip_fastx_comments_counters)."""
+        out = (C.c_uint64 * 2)()
+        _chk(self.lib.crass_hip_fastx_comments_counters(self.h, C.byref(out)), "crass_hip_fastx_comments_counters")
+        return int(out[0]), int(out[1])
+
+    def last_comments_ms(self):
+        """HIP-event milliseconds of (the last comments_build's launches, the last fetch_comments' kernels); stage timing >= 1,
+        else zeros."""
+        return tuple(float(self.lib.crass_hip_last_comments_ms(self.h, k)) for k in range(2))
+
+    def fetch_comments(self, idx, out=None):
+        """The comment kseq HANDS to the records idx (LOCAL record numbers, any order, repeats allowed), from the structure
+        comments_build keeps — after load_fastx_files the first call builds it on the arena (crass_hip_fetch_comments_device).
+        Returns (chars, off, has): numpy copies of the comments back to back (uint8), their offsets (uint64, n + 1) and whether
+        a comment is handed at all (uint8; it may be empty).  out: a contiguous torch uint8 DEVICE tensor — the comments are
+        written there instead (crass_hip_fetch_comments_device_to) and chars is None; a tensor too small raises CrassError with
+        status 8 and the offsets / has in its `offsets` / `has`."""
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        has = np.zeros(len(a), np.uint8)
+        args = (self.h, a.ctypes.data if len(a) else None, len(a))
+        if out is None:
+            v = _abi.Text()
+            _chk(self.lib.crass_hip_fetch_comments_device(*args, C.byref(v), has.ctypes.data if len(a) else None), "crass_hip_fetch_comments_device")
+            t = Text(v)
+            return t.chars.copy(), t.off.copy(), has
+        if str(out.dtype) != "torch.uint8" or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("fetch_comments(out=...) needs a contiguous uint8 device tensor")
+        off = np.zeros(len(a) + 1, np.uint64)
+        st = self.lib.crass_hip_fetch_comments_device_to(*args, int(out.data_ptr()) if out.numel() else None, int(out.numel()), off.ctypes.data,
+                                                         has.ctypes.data if len(a) else None)
+        if st != 0:
+            e = CrassError(st, "crass_hip_fetch_comments_device_to")
+            e.offsets, e.has = off, has
+            raise e
+        return None, off, has
+
     def last_scan_ms(self):
         """HIP-event milliseconds of the last load_fastx_bytes / attach_device_fastx call's scan kernels (stage timing >= 1, else 0)."""
         return float(self.lib.crass_hip_last_scan_ms(self.h))
@@ -1707,6 +1799,18 @@ class SearchGroup:
             raise FastxFilesDeclined(st, "crass_hip_group_load_fastx_files", sh)
         self._chk(st, "crass_hip_group_load_fastx_files")
         return sh
+
+    def fetch_comments(self, idx):
+        """The comment kseq HANDS to reads of the whole job (global indices) of a group loaded by load_fastx_files
+        (crass_hip_group_fetch_comments): carried across the ranks' cuts inside a file, never across a file boundary.  Returns
+        (chars, off, has) as SearchEngine.fetch_comments."""
+        a = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+        has = np.zeros(len(a), np.uint8)
+        v = _abi.Text()
+        self._chk(self.lib.crass_hip_group_fetch_comments(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(v),
+                                                          has.ctypes.data if len(a) else None), "crass_hip_group_fetch_comments")
+        t = Text(v)
+        return t.chars.copy(), t.off.copy(), has
 
     def fetch_header_lines(self, idx):
         """The header lines of the reads idx (GLOBAL read indices, any order) of the last load_fastx_files, from the ranks' arenas

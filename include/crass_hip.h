@@ -1029,6 +1029,63 @@ int  crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *
  * >= n_reads. */
 int  crass_hip_group_fetch_header_lines(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint32_t *name_len_out);
 int  crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_qual_out);
+/* ---- the comment kseq hands on from record to record ----
+ * replaces: ReadHolder's RH_Comment as searchFile / findSingletons fill it (libcrispr.cpp:124-127, :471-487).  kseq_read sets
+ * comment.l = 0 for every record but never clears comment.s (kseq.cpp:182-186), and the callers test only comment.s: a record
+ * whose header line has no comment of its own is handed the last comment seen earlier in the SAME file (the reference opens one
+ * kseq per file), a record in front of its file's first comment is handed none.  The rule (csrc/fastx_scan.h states it once for
+ * host and device): record r has an OWN comment iff its name — the bytes behind the header character up to the first isspace()
+ * byte or the end of the text — ends at a byte that exists and is not '\n'; the own comment is the bytes behind that byte up to,
+ * not including, the line's '\n' or the end of the text (it may be empty: ">a \n", ">a\r\n"; a '\r' in front of the '\n' stays).
+ * The comment HANDED to r is the own comment of the last record r' <= r of r's file that has one.
+ * the host rule, no GPU needed: the handed comments of the records idx[0..n) (idx[k] - idx_base in [0, n_reads), any order,
+ * repeats allowed) back to back in out, off_out[n+1], has_out[n] (may be NULL): 1 where a comment is handed (it may be empty),
+ * 0 where none is.  file_read_base[n_files+1] (file f holds records [file_read_base[f], file_read_base[f+1]); NULL: one file) as
+ * in crass_fastx_files_layout, whose arena layout the bytes of several files have: a '\n' behind every file's text, so that no
+ * name or comment runs into the next file (rec_pos has n_reads + 1 entries, the last is not read).
+ * By the conventions of crass_fastx_names_of: CRASS_ERR_OVERFLOW — off_out[n] > cap_bytes: off_out and has_out complete, nothing
+ * at or beyond out + cap_bytes written; CRASS_ERR_INVALID_ARG (nothing written) — NULL off_out, NULL idx with n > 0, NULL bytes or
+ * rec_pos with n_reads > 0, NULL out with cap_bytes > 0, an index outside the records, a rec_pos at or beyond n_bytes, a
+ * file_read_base that does not run from 0 to n_reads without decreasing.  n == 0: CRASS_OK. */
+int  crass_fastx_comments_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint64_t *file_read_base,
+                             uint32_t n_files, const uint64_t *idx, uint64_t n, uint64_t idx_base, uint8_t *out, uint64_t cap_bytes,
+                             uint64_t *off_out, uint8_t *has_out);
+/* the device side, for bytes that exist only in HBM (fastx_names.hip).  BUILD: k_cm_bits — a lane per record walks its name, a
+ * wave's ballot is one 64-bit word of the own-comment BITMAP; k_cm_tiles / k_cm_top — every tile of 4 096 records gets a carry
+ * word, the last own-comment record in all tiles up to and including it (a maximum scan in launches of their own: no block
+ * waits for another).  Kept in the context: one bit per record, 8 bytes per tile and file_read_base; the record positions are
+ * scratch of the build.  d_bytes == NULL and rec_pos == NULL: on the arena and the layout of the last
+ * crass_hip_load_fastx_files (the other arguments are ignored); else d_bytes is the caller's DEVICE memory, which must stay
+ * valid and unchanged until the drop, and rec_pos (HOST, n_reads + 1 entries) is copied into the context's host memory.
+ * Any load, attach or destroy drops a structure built on the arena.  Errors: CRASS_ERR_STATE — no arena; CRASS_ERR_INVALID_ARG —
+ * as the host rule; CRASS_ERR_UNSUPPORTED — n_reads >= 2^32 - 1; a failed build leaves the context as it was. */
+int  crass_hip_fastx_comments_build_device(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
+                                           const uint64_t *file_read_base, uint32_t n_files);
+int  crass_hip_fastx_comments_drop(crass_hip_ctx *ctx);
+/* FETCH: the handed comments of the records idx[0..n) (HOST array, LOCAL record numbers, any order, repeats allowed) — k_cm_source:
+ * a lane per listed record bisects file_read_base, finds its source in the bitmap (its own word, the earlier words of its tile,
+ * the carry of the tile in front) and drops a source in front of its file's first record; k_cm_measure walks the source's name
+ * and comment; k_cm_copy, a lane per OUTPUT byte, copies.  The result is a crass_text in the context's pinned memory (its own),
+ * valid until the next call of this function or destroy; has_out (host [n], may be NULL) as in the host rule.  Without a built
+ * structure the first fetch after crass_hip_load_fastx_files builds it on the arena; else CRASS_ERR_STATE.  Exact:
+ * crass_fastx_comments_of on the same bytes.  CRASS_ERR_INVALID_ARG — NULL context or result, NULL idx with n > 0, an idx[k] >= n_reads. */
+int  crass_hip_fetch_comments_device(crass_hip_ctx *ctx, const uint64_t *idx, uint64_t n, crass_text *out, uint8_t *has_out);
+/* the same into the caller's DEVICE buffer by the rules of crass_hip_fetch_header_lines_device_to: cap_bytes < off_out[n] is
+ * CRASS_ERR_OVERFLOW with off_out and has_out filled and nothing written; no byte outside [d_chars, d_chars + off_out[n]) is
+ * written; d_chars may be NULL with cap_bytes 0.  Without a built structure and without an arena: CRASS_ERR_STATE. */
+int  crass_hip_fetch_comments_device_to(crass_hip_ctx *ctx, const uint64_t *idx, uint64_t n, uint8_t *d_chars, uint64_t cap_bytes,
+                                        uint64_t *off_out, uint8_t *has_out);
+/* out[0]: the records of the built structure that have a comment of their own, out[1]: its records.  CRASS_ERR_STATE without one. */
+int  crass_hip_fastx_comments_counters(const crass_hip_ctx *ctx, uint64_t out[2]);
+/* HIP-event times, in milliseconds on the context's stream: part 0 the three launches of the last build, part 1 the kernels of
+ * the last fetch with the copies between them; measured when the stage timing level is >= 1, else 0. */
+float crass_hip_last_comments_ms(const crass_hip_ctx *ctx, int part);
+/* the same for a group loaded by crass_hip_group_load_fastx_files, routed and owned like crass_hip_group_fetch_header_lines.  A
+ * rank's shard may begin in the middle of a file: every rank publishes the own comment of the last own-comment record of the
+ * file part its shard ends in (a host string), the group resolves what is carried into every rank's first file part (empty
+ * ranks and ranks whose part holds no comment pass it through), and a listed record with no source in its rank's part of its
+ * file is handed that string.  Exact: crass_fastx_comments_of on the whole job. */
+int  crass_hip_group_fetch_comments(crass_hip_group *g, const uint64_t *read_idx, uint64_t n, crass_text *out, uint8_t *has_out);
 /* the route of the found-name exchange of a files load (names that repeat across ranks, above).  0, the default: through the host —
  * header lines back, cut at the name, every other rank's names up (crass_hip_fastx_names_find), the namesakes up again.
  * on_device != 0 (or CRASS_GROUP_NAMES=device in the environment when the group is created): rank r writes its names with

@@ -66,3 +66,7 @@ echo "shards: $(tail -1 $out/report_shards.txt); $(grep -c 'ERROR: AddressSaniti
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/names_of_main.cpp -o $out/names_of_asan -lz
 $out/names_of_asan $out/fastx/* > $out/report_names_of.txt 2> $out/sanitizer_names_of.txt || true
 echo "names of: $(grep -c '^ok  ' $out/report_names_of.txt) ok, $(grep -c '^DIFF' $out/report_names_of.txt || true) differ; $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_names_of.txt || true) sanitizer reports"
+# the comment kseq hands on, on the host (crass_fastx_comments_of) over designed jobs of its own, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/comments_of_main.cpp -o $out/comments_of_asan -lz
+$out/comments_of_asan > $out/report_comments_of.txt 2> $out/sanitizer_comments_of.txt || true
+echo "comments of: $(tail -1 $out/report_comments_of.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_comments_of.txt || true) sanitizer reports"
