@@ -459,8 +459,8 @@ static __device__ __forceinline__ void dm_table_params(uint32_t n, uint32_t tab_
 
 // ---- 6b. the keys' entry ranges of the verification index (count -> block allocation -> fill), and the keys
 // themselves into the cuckoo table.  Two-choice cuckoo insertion, all keys at once: a key is always either in the
-// table or in exactly one thread's hand (atomicExch).  0xFFFFFFFF marks a free slot; the all-T key itself is handled
-// by the last kernel.
+// table or in exactly one thread's hand (atomicExch).  0xFFFFFFFF marks a free slot; the all-T key itself is never
+// inserted: this kernel keeps its first slot free of other keys, and the last kernel leaves the free slots as they are.
 // (1 024 threads per block: the cursor atomic RETURNS a value, and returning atomics on one address retire every ~35 ns,
 // not every 3 — 2 600 blocks of 256 were 90 of this kernel's 102 us at 100 M reads)
 __global__ __launch_bounds__(1024) void k_dm_key_bases_insert(DevMerge M)
@@ -499,21 +499,26 @@ __global__ __launch_bounds__(1024) void k_dm_key_bases_insert(DevMerge M)
     }
     if (cur == 0xFFFFFFFFu) return;
     const uint32_t rsh = 32u - ls;
+    // The all-T key is never in the table: a window of T*16 is found through a FREE slot among its two.  Where that key is a member
+    // (all_t, from k_dm_keys, the launch before this one) its first slot is kept free — no other key settles there; without this,
+    // two keys whose first slots are the all-T key's two slots took both, and reads holding the pattern were not flagged.
+    const uint32_t keep = M.st->all_t ? ak_h(0xFFFFFFFFu, M.m1, rsh) : 0xFFFFFFFFu;      // (0xFFFFFFFF is no slot index: ls <= 24)
     uint32_t pos = ak_h(cur, M.m1, rsh);
+    const uint32_t alt = ak_h(cur, M.m2, rsh);
+    if (pos == keep) pos = alt;
+    if (pos == keep) { atomicOr(&M.st->fail, 4u); return; }         // (both of its slots are the kept one: the host merges)
     // a free slot of its own first: only a key whose two slots are both taken starts an eviction chain (every link of a
     // chain is a dependent atomic round trip; near load 1/2 — 30 k keys in 2^16 slots at 100 M reads — exchanging
     // unconditionally made 46 % of the keys start one and the longest took ~100 us)
     if (atomicCAS(&M.anchor_tab[pos], 0xFFFFFFFFu, cur) == 0xFFFFFFFFu) return;
-    {
-        const uint32_t p2 = ak_h(cur, M.m2, rsh);
-        if (p2 != pos && atomicCAS(&M.anchor_tab[p2], 0xFFFFFFFFu, cur) == 0xFFFFFFFFu) return;
-    }
+    if (alt != pos && alt != keep && atomicCAS(&M.anchor_tab[alt], 0xFFFFFFFFu, cur) == 0xFFFFFFFFu) return;
     for (int kicks = 0; kicks < 1000; kicks++) {
         const uint32_t old = atomicExch(&M.anchor_tab[pos], cur);
         if (old == 0xFFFFFFFFu) return;
         cur = old;
         const uint32_t p1 = ak_h(cur, M.m1, rsh), p2 = ak_h(cur, M.m2, rsh);
-        pos = (pos == p1) ? p2 : p1;
+        const uint32_t other = (pos == p1) ? p2 : p1;
+        if (other != keep) pos = other;                 // (a key whose other slot is the kept one stays: it evicts its successor)
     }
     atomicOr(&M.st->fail, 4u);
 }
