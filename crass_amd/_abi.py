@@ -198,6 +198,9 @@ SYMBOLS = {
     "crass_hip_last_pack_ms": (C.c_float, [C.c_void_p]),
     "crass_hip_get_packed": (C.c_int, [C.c_void_p, C.POINTER(Packed)]),
     "crass_fastx_scan_host": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(FastxLayoutC)]),
+    "crass_fastx_scan_host_class": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(FastxLayoutC)]),
+    "crass_hip_set_fastq_class": (C.c_int, [C.c_void_p, C.c_int]),
+    "crass_hip_last_scan_classes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "crass_fastx_layout_free": (None, [C.POINTER(FastxLayoutC)]),
     "crass_hip_load_fastx_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(FastxLayoutC)]),
     "crass_hip_attach_device_fastx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(FastxLayoutC)]),
@@ -254,6 +257,7 @@ SYMBOLS = {
     "crass_hip_set_gzip_on_device": (C.c_int, [C.c_void_p, C.c_int]),
     "crass_hip_last_gzip_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "crass_fastx_files_scan_host": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.POINTER(FastxFilesLayoutC)]),
+    "crass_fastx_files_scan_host_class": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.POINTER(FastxFilesLayoutC)]),
     "crass_fastx_files_layout_free": (None, [C.POINTER(FastxFilesLayoutC)]),
     "crass_hip_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.POINTER(FastxFilesLayoutC)]),
     "crass_hip_resident_fastx": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),

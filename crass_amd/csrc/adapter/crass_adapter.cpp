@@ -606,8 +606,12 @@ struct MappedFiles {
 };
 
 // the one line a declined input of the device reader gets: the file, the reason, the position
-std::string decline_message(const Vecstr &files, const crass_fastx_files_layout &lay, const char *mode = "device")
+// (wrapped: the load read FASTQ by class 1, whose reasons 3, 4, 8, 9 and 12 say something else)
+std::string decline_message(const Vecstr &files, const crass_fastx_files_layout &lay, const char *mode = "device", bool wrapped = false)
 {
+    static const char *const fw[] = {"", "", "", "a FASTQ record without a '+' line", "a line behind a FASTQ record that starts no record", "", "", "",
+                                     "the file ends inside a FASTQ record", "a quality that is longer than its sequence", "", "",
+                                     "an empty sequence whose '+' line is followed by '@'"};
     static const char *const fx[] = {"", "the file is empty", "byte 0 is neither '>' nor '@'", "the FASTQ lines are no multiple of 4", "a FASTQ record does not start with '@'",
                                      "'>', '@' or '+' in a sequence line", "the third line of a FASTQ record does not start with '+'", "byte 127 in a quality line",
                                      "a quality line is shorter than its sequence line", "a quality line is longer than its sequence line", "the file ends with a lone '>'",
@@ -625,7 +629,8 @@ std::string decline_message(const Vecstr &files, const crass_fastx_files_layout 
              ") at byte " + std::to_string(lay.bgzf.in_pos);
     } else {
         const int r = lay.decline_reason;
-        m += std::string(r >= 1 && r <= 11 ? fx[r] : "not a regular FASTA / FASTQ file") + " (reason " + std::to_string(r) + ") at byte " + std::to_string(lay.decline_pos);
+        const bool w = wrapped && lay.decline_file >= 0 && r >= 1 && r <= 12 && fw[r][0];
+        m += std::string(w ? fw[r] : r >= 1 && r <= 11 ? fx[r] : "not a regular FASTA / FASTQ file") + " (reason " + std::to_string(r) + ") at byte " + std::to_string(lay.decline_pos);
     }
     return m;
 }
@@ -831,8 +836,16 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         // CRASS_DEVICE_GZIP=1: a plain gzip input is inflated on the device too (gunzip.hip); without it such an input is declined.
         // The value goes through as it is: 2 takes plain gzip of any number of members (CRASS_GZIP_ON_DEVICE_MEMBERS)
         if (const char *e = getenv("CRASS_DEVICE_GZIP")) chk(crass_hip_set_gzip_on_device(made.c, atoi(e)), "crass_hip_set_gzip_on_device");
+        // CRASS_DEVICE_FASTQ=wrapped: FASTQ records over several lines and blank lines are read too (crass_hip_set_fastq_class);
+        // four-line, or the variable unset: the four-line form only, as before
+        bool wrapped = false;
+        if (const char *e = getenv("CRASS_DEVICE_FASTQ")) {
+            wrapped = !strcmp(e, "wrapped");
+            if (!wrapped && strcmp(e, "four-line")) throw input_error(std::string("crass [ERROR]: CRASS_DEVICE_FASTQ=") + e + " is neither wrapped nor four-line");
+            chk(crass_hip_set_fastq_class(made.c, wrapped ? 1 : 0), "crass_hip_set_fastq_class");
+        }
         const int s = crass_hip_load_fastx_files(made.c, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, &lay);
-        if (s == CRASS_ERR_UNSUPPORTED && lay.decline_file >= 0) throw input_error(decline_message(seqFiles, lay));
+        if (s == CRASS_ERR_UNSUPPORTED && lay.decline_file >= 0) throw input_error(decline_message(seqFiles, lay, "device", wrapped));
         chk(s, "crass_hip_load_fastx_files");
         n = lay.n_reads; max_len = (int)lay.max_len;
         if (timing) fprintf(stderr, "[crass_timing] %llu reads of %zu file(s) parsed and packed on the device (crass_hip_load_fastx_files)\n", (unsigned long long)n, seqFiles.size());

@@ -47,7 +47,9 @@ static void usage()
                  "                 several files as one read set; one device only; an input it declines (plain gzip, irregular\n"
                  "                 FASTA / FASTQ) is an error\n"
                  "  CRASS_DEVICE_GZIP=1   with CRASS_INGEST=device: a plain (single-member) gzip input is inflated on the GPU too\n"
-                 "  CRASS_DEVICE_GZIP=2   ... and plain gzip of any number of members (cat of .gz files, gzip's >>)\n";
+                 "  CRASS_DEVICE_GZIP=2   ... and plain gzip of any number of members (cat of .gz files, gzip's >>)\n"
+                 "  CRASS_DEVICE_FASTQ=wrapped   with CRASS_INGEST=device: FASTQ records whose sequence or quality runs over several\n"
+                 "                 lines, and blank lines between records and at the end, are read too (default: four-line)\n";
 }
 
 // CRASS_SMAPS_AT_EXIT=1: the mappings with the largest resident sets, at the end of every stage (what the kernel takes back at _exit)

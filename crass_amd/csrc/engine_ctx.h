@@ -208,6 +208,12 @@ struct Ingest {
     PinBuf<uint64_t> x_h_tot, x_h_rec_pos, x_h_seq_off;
     StageTimer<2> tm_scan;
     float last_scan_ms = 0;                  // HIP-event time of the last call's scan kernels (stage timing >= 1, else 0)
+    // crass_hip_set_fastq_class (fastx_wrapped.hip): the class, the pieces the last load's four-line / wrapped scan decided, one
+    // scratch buffer per wrapped piece (fw_scratch_words) — given back with the scan's — and the pinned copy of their totals
+    int fastq_class = 0;
+    uint64_t scan_classes[2] = {0, 0};
+    std::vector<DevBuf<uint64_t>> w_scratch;
+    PinBuf<uint64_t> x_h_wtot;
     // crass_hip_inflate_bgzf_device / crass_hip_load_fastx_bgzf (inflate.hip): the index's three arrays back to back, every
     // member's reason, the verdict word (the gzip decode step's too), the compressed bytes of a host file and the text that is
     // not the caller's — all given back before the call returns

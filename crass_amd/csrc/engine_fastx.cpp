@@ -32,6 +32,80 @@ int ArenaScan::queue(crass_hip_ctx *c, uint32_t i, int32_t format, bool newline)
     return CRASS_OK;
 }
 
+// FASTQ class 1 (fastx_wrapped.hip): the pieces f with w_of[f] >= 0 are read again under the wrapped rule of fastx_scan.h.  Each
+// gets scratch of its own (Ingest::w_scratch, given back by release_scan), its line table, successors, reachable records and
+// their ranks; the totals and verdicts come back in one wait.  The first piece in order that offends — under the wrapped rule,
+// or the piece the four-line scan declined for good — is the verdict.  Otherwise every piece emits again with the bases the new
+// totals give: the four-line pieces by k_fx_emit, the wrapped ones by k_fw_place / k_fw_emit.
+int ArenaScan::emit_wrapped(crass_hip_ctx *c, uint32_t nf, uint64_t max_reads, const std::vector<int32_t> &w_of, uint32_t n_w,
+                            std::vector<uint64_t> &tbase, ScanResult &R)
+{
+    Ingest &I = c->in;
+    std::vector<uint64_t> &rbase = R.rbase;
+    const uint64_t *h_verdict = I.x_h_tot.p + 4 * (uint64_t)jobs.size();
+    std::vector<FwJob> wj(n_w);
+    I.w_scratch.resize(n_w);
+    HIPCHK(c, I.x_h_wtot.ensure((uint64_t)kFwTot * n_w));
+    for (uint32_t f = 0; f < nf; f++) {
+        if (w_of[f] < 0) continue;
+        const FxJob &X = jobs[f];
+        FwJob &J = wj[w_of[f]];
+        J = FwJob{};
+        if (I.x_h_tot.p[4 * f] >= 0xFFFFFFFFull) return CRASS_ERR_UNSUPPORTED;      // (line indices are 32-bit, END is one of them)
+        J.bytes = X.bytes; J.n = X.n; J.lead = X.lead; J.n_tiles = X.n_tiles; J.n_lines = (uint32_t)I.x_h_tot.p[4 * f];
+        uint8_t last = 0;
+        HIPCHK(c, hipMemcpy(&last, X.bytes + X.n - 1, 1, hipMemcpyDeviceToHost));
+        J.ends_nl = fx_is_nl(last) ? 1u : 0u;
+        DevBuf<uint64_t> &S = I.w_scratch[w_of[f]];
+        HIPCHK(c, S.ensure(fw_scratch_words(J.n_tiles, J.n_lines)));
+        fw_lay_out(J, S.p);
+        HIPCHK(c, hipMemsetAsync(J.tot + 7, 0xFF, 8, c->stream));
+        HIPCHK(c, launch_fw_tiles(J, c->stream));
+        HIPCHK(c, launch_fw_analyse(J, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.x_h_wtot.p + (uint64_t)kFwTot * w_of[f], J.tot, 8 * kFwTot, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t f = 0; f < nf; f++) {
+        uint64_t verdict = h_verdict[f];
+        if (w_of[f] >= 0) {
+            const uint64_t *t = I.x_h_wtot.p + (uint64_t)kFwTot * w_of[f];
+            if (t[0] != wj[w_of[f]].n_lines) return CRASS_ERR_STATE;      // (never expected: both scans count the same line starts)
+            verdict = t[7];
+        }
+        if (verdict != kFxNoOffence) { R.decline_file = (int32_t)f; R.decline_reason = (int32_t)(verdict & 0xFF); R.decline_pos = verdict >> 8; return CRASS_ERR_UNSUPPORTED; }
+    }
+    for (uint32_t f = 0; f < nf; f++) {
+        const uint64_t *t = w_of[f] >= 0 ? I.x_h_wtot.p + (uint64_t)kFwTot * w_of[f] : nullptr;
+        rbase[f + 1] = rbase[f] + (t ? t[5] : I.x_h_tot.p[4 * f + 1]);
+        tbase[f + 1] = tbase[f] + (t ? t[6] : I.x_h_tot.p[4 * f + 2]);
+    }
+    const uint64_t nr = rbase[nf], total_seq = tbase[nf];
+    if (nr >= max_reads) return CRASS_ERR_UNSUPPORTED;
+    HIPCHK(c, I.x_text.ensure(total_seq + 32));
+    HIPCHK(c, I.x_rec_pos.ensure(nr + 1)); HIPCHK(c, I.x_seq_off.ensure(nr + 1));
+    HIPCHK(c, I.x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, I.x_h_seq_off.ensure(nr + 1));
+    for (uint32_t f = 0; f < nf; f++) {
+        if (w_of[f] >= 0) {
+            FwJob &J = wj[w_of[f]];
+            J.n_reads = rbase[f + 1] - rbase[f];
+            J.text = I.x_text.p; J.text_base = tbase[f]; J.text_cap = tbase[f + 1];
+            J.rec_pos = I.x_rec_pos.p; J.seq_off = I.x_seq_off.p; J.read_base = rbase[f]; J.arena_base = base[f];
+            HIPCHK(c, launch_fw_emit(J, c->stream));
+        } else {
+            FxJob &J = jobs[f];
+            J.text = I.x_text.p; J.text_base = tbase[f]; J.text_cap = tbase[f + 1];
+            J.rec_pos = I.x_rec_pos.p; J.seq_off = I.x_seq_off.p; J.read_base = rbase[f];
+            HIPCHK(c, launch_fx_emit(J, c->stream));
+        }
+    }
+    if (nr) {
+        HIPCHK(c, hipMemcpyAsync(I.x_h_rec_pos.p, I.x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.x_h_seq_off.p, I.x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CRASS_OK;
+}
+
 int ArenaScan::emit(crass_hip_ctx *c, uint32_t nf, uint64_t max_reads, ScanResult &R)
 {
     Ingest &I = c->in;
@@ -41,11 +115,11 @@ int ArenaScan::emit(crass_hip_ctx *c, uint32_t nf, uint64_t max_reads, ScanResul
     std::vector<uint64_t> &rbase = R.rbase, tbase(nf + 1, 0);
     rbase.assign(nf + 1, 0);
     for (uint32_t f = 0; f < nf; f++) { rbase[f + 1] = rbase[f] + I.x_h_tot.p[4 * f + 1]; tbase[f + 1] = tbase[f] + I.x_h_tot.p[4 * f + 2]; }
-    const uint64_t nr = rbase[nf], total_seq = tbase[nf];
-    if (nr >= max_reads) return CRASS_ERR_UNSUPPORTED;
-    HIPCHK(c, I.x_text.ensure(total_seq + 32));
-    HIPCHK(c, I.x_rec_pos.ensure(nr + 1)); HIPCHK(c, I.x_seq_off.ensure(nr + 1));
-    HIPCHK(c, I.x_h_rec_pos.ensure(nr + 1)); HIPCHK(c, I.x_h_seq_off.ensure(nr + 1));
+    const uint64_t nr4 = rbase[nf], total_seq4 = tbase[nf];      // (as the four-line scan counts them)
+    if (nr4 >= max_reads) return CRASS_ERR_UNSUPPORTED;
+    HIPCHK(c, I.x_text.ensure(total_seq4 + 32));
+    HIPCHK(c, I.x_rec_pos.ensure(nr4 + 1)); HIPCHK(c, I.x_seq_off.ensure(nr4 + 1));
+    HIPCHK(c, I.x_h_rec_pos.ensure(nr4 + 1)); HIPCHK(c, I.x_h_seq_off.ensure(nr4 + 1));
     unsigned long long *d_verdict = reinterpret_cast<unsigned long long *>(I.x_tot.p + 4 * n_planned);
     HIPCHK(c, hipMemsetAsync(d_verdict, 0xFF, 8 * (uint64_t)nf, c->stream));
     for (uint32_t f = 0; f < nf; f++) {
@@ -59,25 +133,40 @@ int ArenaScan::emit(crass_hip_ctx *c, uint32_t nf, uint64_t max_reads, ScanResul
     HIPCHK(c, I.tm_scan.mark(c->stream));
     uint64_t *h_verdict = I.x_h_tot.p + 4 * n_planned;
     HIPCHK(c, hipMemcpyAsync(h_verdict, d_verdict, 8 * (uint64_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (nr) {
-        HIPCHK(c, hipMemcpyAsync(I.x_h_rec_pos.p, I.x_rec_pos.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(I.x_h_seq_off.p, I.x_seq_off.p, nr * 8, hipMemcpyDeviceToHost, c->stream));
+    if (nr4) {
+        HIPCHK(c, hipMemcpyAsync(I.x_h_rec_pos.p, I.x_rec_pos.p, nr4 * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.x_h_seq_off.p, I.x_seq_off.p, nr4 * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, I.tm_scan.elapsed(0, 1, &I.last_scan_ms));
-    uint64_t *rec_pos = I.x_h_rec_pos.p, *seq_off = I.x_h_seq_off.p;
-    rec_pos[nr] = base[nf] - 1; seq_off[nr] = total_seq;
-    R.n_reads = nr; R.total_seq = total_seq; R.max_len = 0;
     auto decline = [&](uint32_t f, int32_t reason, uint64_t pos) {
         R.decline_file = (int32_t)f; R.decline_reason = reason; R.decline_pos = pos;
         return CRASS_ERR_UNSUPPORTED;
     };
+    // FASTQ class 1: the pieces the four-line scan declined for their shape, up to the first piece declined for good
+    std::vector<int32_t> w_of(nf, -1);
+    uint32_t n_w = 0;
+    for (uint32_t f = 0; wrapped && f < nf; f++) {
+        if (h_verdict[f] == kFxNoOffence) continue;
+        if (jobs[f].format != 0x40 || !fx_wrapped_takes((int32_t)(h_verdict[f] & 0xFF))) break;
+        w_of[f] = (int32_t)n_w++;
+    }
+    I.scan_classes[0] = nf - n_w; I.scan_classes[1] = n_w;
+    uint64_t nr = nr4, total_seq = total_seq4;
+    if (n_w) {
+        const int ws = emit_wrapped(c, nf, max_reads, w_of, n_w, tbase, R);
+        if (ws) return ws;
+        nr = rbase[nf]; total_seq = tbase[nf];
+    }
+    uint64_t *rec_pos = I.x_h_rec_pos.p, *seq_off = I.x_h_seq_off.p;
+    rec_pos[nr] = base[nf] - 1; seq_off[nr] = total_seq;
+    R.n_reads = nr; R.total_seq = total_seq; R.max_len = 0;
     for (uint32_t f = 0; f < nf; f++) {
         const uint64_t verdict = h_verdict[f];
-        if (verdict != kFxNoOffence) return decline(f, (int32_t)(verdict & 0xFF), verdict >> 8);
+        if (w_of[f] < 0 && verdict != kFxNoOffence) return decline(f, (int32_t)(verdict & 0xFF), verdict >> 8);
         const uint64_t seq_f = tbase[f + 1] - tbase[f];
         // (never expected: an accepted file has a record and as many quality as sequence bytes)
-        if (rbase[f + 1] == rbase[f] || I.x_h_tot.p[4 * f + 3] != (jobs[f].format == 0x40 ? seq_f : 0)) return CRASS_ERR_STATE;
+        if (rbase[f + 1] == rbase[f] || (w_of[f] < 0 && I.x_h_tot.p[4 * f + 3] != (jobs[f].format == 0x40 ? seq_f : 0))) return CRASS_ERR_STATE;
         for (uint64_t r = rbase[f]; r < rbase[f + 1]; r++) {
             const uint64_t l = (r + 1 < rbase[f + 1] ? seq_off[r + 1] : tbase[f + 1]) - seq_off[r];
             if (l > CRASS_HIP_MAX_READ_LEN) return decline(f, FX_READ_TOO_LONG, rec_pos[r] - base[f]);
@@ -114,6 +203,7 @@ static int load_fastx_impl(crass_hip_ctx *c, const uint8_t *h_bytes, const uint8
     ArenaScan A;
     int s = A.open(c, d_bytes, base, 1);
     if (s) return s;
+    A.wrapped = I.fastq_class == FX_CLASS_WRAPPED;
     s = A.queue(c, 0, b0, false);
     if (s) return s;
     ScanResult R;
@@ -151,6 +241,20 @@ int crass_hip_attach_device_fastx(crass_hip_ctx *c, const uint8_t *d_bytes, uint
 }
 
 uint32_t crass_hip_fastx_tile_bytes(void) { return fastx_tile_bytes(); }
+
+int crass_hip_set_fastq_class(crass_hip_ctx *c, int fastq_class)
+{
+    if (!c || (fastq_class != FX_CLASS_FOUR_LINE && fastq_class != FX_CLASS_WRAPPED)) return CRASS_ERR_INVALID_ARG;
+    c->in.fastq_class = fastq_class;
+    return CRASS_OK;
+}
+
+int crass_hip_last_scan_classes(const crass_hip_ctx *c, uint64_t out[2])
+{
+    if (!c || !out) return CRASS_ERR_INVALID_ARG;
+    out[0] = c->in.scan_classes[0]; out[1] = c->in.scan_classes[1];
+    return CRASS_OK;
+}
 float crass_hip_last_scan_ms(const crass_hip_ctx *c) { return c ? c->in.last_scan_ms : 0.0f; }
 
 static int load_fastx_bgzf_impl(crass_hip_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const crass_bgzf_index *ix, int pad_uniform,
@@ -321,6 +425,7 @@ static int load_fastx_files_impl(crass_hip_ctx *c, const uint8_t *const *bytes, 
     ArenaScan A;
     const int os = A.open(c, arena, base.data(), nf);
     if (os) return os;
+    A.wrapped = c->in.fastq_class == FX_CLASS_WRAPPED;
     for (uint32_t f = 0; f < nf; f++) {
         FilesPlan::File &F = P.f[f];
         if (f) HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // (the staged buffers are the file before's until its last copy is done)

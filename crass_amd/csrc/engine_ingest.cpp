@@ -52,6 +52,8 @@ void release_scan(crass_hip_ctx *c)
     Ingest &I = c->in;
     wait_both(c);
     I.x_raw.release(); I.x_text.release(); I.x_tiles.release(); I.x_base.release(); I.x_tot.release(); I.x_rec_pos.release(); I.x_seq_off.release();
+    for (auto &w : I.w_scratch) w.release();
+    I.w_scratch.clear();
 }
 
 // the BGZF inflate, and the verdict word the gzip decode step shares with it
@@ -141,6 +143,7 @@ void begin_fastx_load(crass_hip_ctx *c)
 {
     begin_load(c);
     c->in.last_scan_ms = 0; c->in.last_pack_ms = 0;
+    c->in.scan_classes[0] = c->in.scan_classes[1] = 0;
 }
 
 // new header ids: pass 1's found flags are keyed by them, so earlier results are void; the resident set's own counters stay

@@ -424,7 +424,8 @@ int crass_hip_fetch_header_lines_device_to(crass_hip_ctx *c, const uint8_t *d_by
 }
 
 // the quality string: two words per record, its position and its end; the starts of the quality lines stay on the device; the
-// second half is the flags, bit 0: the record has a quality line
+// second half is the flags, bit 0: the record has a quality line.  With FASTQ class 1 on the context the records are measured by
+// the wrapped rule (k_qw_measure)
 static int quality_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads,
                           const uint64_t *idx, uint64_t n, uint8_t *d_user, uint64_t cap, uint64_t *off_user, crass_text *out, uint8_t *has_qual_out)
 {
@@ -437,7 +438,7 @@ static int quality_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_b
         const hipError_t e = B.start.ensure(n);
         if (e != hipSuccess) return e;
         J.src = B.src.p; J.lim = B.src.p + n; J.start = B.start.p; J.len = B.len.p; J.flags = B.len.p + n;
-        return launch_ql_measure(J, c->stream);
+        return c->in.fastq_class == FX_CLASS_WRAPPED ? launch_qw_measure(J, c->stream) : launch_ql_measure(J, c->stream);
     };
     ops.copy = [&](LineFetch &B, uint64_t total, uint8_t *dst) { J.off = B.off.p; J.total = total; J.out = dst; return launch_ql_copy(J, c->stream); };
     ops.second = [&](const uint32_t *half) { if (has_qual_out) for (uint64_t k = 0; k < n; k++) has_qual_out[k] = (uint8_t)(half[k] & 1u); };

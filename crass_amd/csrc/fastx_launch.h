@@ -65,4 +65,43 @@ hipError_t launch_fx_summary(const FxJob &J, hipStream_t st);
 hipError_t launch_fx_tile_scan(const FxJob &J, hipStream_t st);
 hipError_t launch_fx_emit(const FxJob &J, hipStream_t st);
 
+// ---- the wrapped FASTQ scan (fastx_wrapped.hip; fastx_scan.h states the rule) ----
+// A table of the LINES (where each starts, its first byte, and how many bytes 33..126, bytes 127 and bytes '>' '@' '+' lie in
+// front of it), every '@' line's successor under the rule, the lines reachable from line 0 by pointer doubling, their ranks and
+// text offsets, then the sequence bytes out.  Line indices are 32-bit; END is n_lines.
+struct FwTile { uint32_t n_ls, n_pl, g, d, f; };        // a tile's line starts, those whose byte is '+', bytes 33..126, 127, forbidden
+struct FwBase { uint64_t ls, pl, g, d, f; };            // the same in front of the tile
+static constexpr uint32_t kFwRankTile = 1024;            // lines per block of the rank scan
+static constexpr uint32_t kFwTot = 8;                    // words of FwJob::tot
+struct FwJob {
+    const uint8_t *bytes; uint64_t n;                   // device pointer of any alignment, n > 0
+    uint32_t lead, ends_nl;                             // address modulo 16; the last byte is a '\n'
+    uint64_t n_tiles;
+    FwTile *tiles; FwBase *base;                        // [n_tiles]
+    uint64_t *tot;          // [kFwTot] lines, '+' lines, bytes 33..126, 127, forbidden (k_fw_tile_scan); records, sequence bytes
+                            // (k_fw_rank_top); the verdict (kFxNoOffence before k_fw_rank_apply)
+    uint32_t n_lines;       // tot[0], read back: the arrays below are sized by it
+    uint64_t *pos, *G, *D, *F;        // [n_lines + 1] the line's first byte; the three counts in front of it (entry n_lines: n, the totals)
+    uint8_t *first;         // [n_lines] the line's first byte
+    uint32_t *plus;         // [n_lines] the lines that start with '+', in order (tot[1] of them)
+    uint32_t *nxt[2];       // [n_lines + 1] the successor arrays of the doubling, in turns
+    uint32_t *mark;         // [n_lines + 1] the line is a header reachable from line 0
+    uint32_t *plus_of;      // [n_lines] a header candidate's '+' line
+    uint64_t *seqlen, *off; // [n_lines] a candidate's sequence bytes and its offence word (kFxNoOffence: none)
+    uint32_t *rank;         // [n_lines] marked lines in front
+    uint64_t *seqpre;       // [n_lines] their sequence bytes
+    uint64_t *tile_cnt, *tile_len;    // [n_rank_tiles + 1] the rank scan's tiles
+    uint32_t *hdr;          // [n_lines] record r's header line
+    uint64_t *delta;        // [n_lines] a sequence line of a marked record: where in the text its first byte 33..126 goes; else kFxNone
+    // k_fw_place / k_fw_emit: as FxJob's
+    uint64_t n_reads, text_cap, text_base, read_base, arena_base;
+    uint8_t *text; uint64_t *rec_pos, *seq_off;
+};
+// the scratch of one piece in 64-bit words (everything above but the bytes), and the job's pointers laid into it
+uint64_t fw_scratch_words(uint64_t n_tiles, uint64_t n_lines);
+void fw_lay_out(FwJob &J, uint64_t *scratch);
+hipError_t launch_fw_tiles(const FwJob &J, hipStream_t st);      // k_fw_summary, k_fw_tile_scan: tot[0 .. 5)
+hipError_t launch_fw_analyse(const FwJob &J, hipStream_t st);    // k_fw_lines, k_fw_next, k_fw_jump rounds, the rank scan: tot[5 .. 8)
+hipError_t launch_fw_emit(const FwJob &J, hipStream_t st);       // k_fw_place, k_fw_emit
+
 } // namespace crass

@@ -595,6 +595,41 @@ __global__ __launch_bounds__(kNmThreads) void k_ql_measure(const QlJob J)
     J.start[k] = start; J.len[k] = len; J.flags[k] = flags;
 }
 
+// the same for a record of the wrapped class (fastx_scan.h): behind the header line the sequence lines up to the first line that
+// starts with '+', L their bytes 33..126; the quality is the first L bytes 33..126 behind the '+' line, over however many lines.
+// On a four-line record the answer is k_ql_measure's.
+__global__ __launch_bounds__(kNmThreads) void k_qw_measure(const QlJob J)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
+    if (k >= J.n) return;
+    const uint64_t p0 = J.src[k];
+    const uint64_t end = J.lim[k] < J.n_bytes ? J.lim[k] : J.n_bytes;
+    uint64_t start = p0;
+    uint32_t len = 0, flags = 0;
+    if (p0 < end && J.bytes[p0] == 0x40) {
+        flags = 1u;
+        uint64_t p = p0, L = 0;
+        while (p < end && J.bytes[p] != 0x0A) p++;      // the header line
+        p++;
+        while (p < end && J.bytes[p] != 0x2B) {         // sequence lines
+            for (; p < end && J.bytes[p] != 0x0A; p++) L += ql_is_graph(J.bytes[p]) ? 1u : 0u;
+            p++;
+        }
+        while (p < end && J.bytes[p] != 0x0A) p++;      // the '+' line
+        p++;
+        start = p < end ? p : end;
+        bool gap = false, dense = true;
+        for (p = start; p < end && len < L && len != 0xFFFFFFFFu; p++) {
+            if (ql_is_graph(J.bytes[p])) { if (gap) dense = false; len++; }
+            else gap = true;
+        }
+        if (dense) flags |= 2u;
+    }
+    J.start[k] = start; J.len[k] = len; J.flags[k] = flags;
+}
+
+// a lane per output byte; nothing is stored outside [out, out + total).  Wrapped records too (k_qw_measure): the walk to the
+// k-th byte 33..126 goes over line ends up to the record's end
 __global__ __launch_bounds__(kNmThreads) void k_ql_copy(const QlJob J)
 {
     const uint64_t i = (uint64_t)blockIdx.x * kNmThreads + threadIdx.x;
@@ -867,6 +902,14 @@ hipError_t launch_ql_measure(const QlJob &J, hipStream_t st)
     unsigned g;
     if (!nm_grid(J.n, kNmThreads, &g)) return hipErrorInvalidValue;
     CRASS_LAUNCH(k_ql_measure, dim3(g), dim3(kNmThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_qw_measure(const QlJob &J, hipStream_t st)
+{
+    unsigned blocks;
+    if (!nm_grid(J.n, kNmThreads, &blocks)) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_qw_measure, dim3(blocks), dim3(kNmThreads), 0, st, J);
     return hipGetLastError();
 }
 

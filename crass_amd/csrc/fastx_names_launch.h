@@ -97,6 +97,7 @@ struct QlJob {
     uint8_t *out;                    // [total], any alignment
 };
 hipError_t launch_ql_measure(const QlJob &J, hipStream_t st);
+hipError_t launch_qw_measure(const QlJob &J, hipStream_t st);      // FASTQ class 1: start / len by the wrapped rule, the same copy
 hipError_t launch_ql_copy(const QlJob &J, hipStream_t st);
 
 // k_cm_bits / k_cm_tiles / k_cm_top: the own-comment bitmap of a file's records and the carry of every tile of kFxCmTile

@@ -75,6 +75,74 @@ int fastx_scan_serial(const uint8_t *bytes, uint64_t n, FxHostScan *out)
     return CRASS_OK;
 }
 
+// the wrapped FASTQ rule of fastx_scan.h, record by record from line 0: each record is judged from where the one before ended
+static int fastx_scan_wrapped_serial(const uint8_t *bytes, uint64_t n, FxHostScan *out)
+{
+    *out = FxHostScan();
+    out->format = 0x40;
+    auto decline = [&](uint64_t pos, int32_t reason) { out->reason = reason; out->decline_pos = pos; out->n_reads = 0; out->max_len = 0; return CRASS_ERR_UNSUPPORTED; };
+    struct Line { uint64_t e, graph; bool forbidden, del, is_void; };
+    auto line_at = [&](uint64_t p) {                     // the line that starts at p < n: [p, e), its '\n' (if any) at e
+        Line l{p, 0, false, false, true};
+        for (; l.e < n && !fx_is_nl(bytes[l.e]); l.e++) {
+            const uint8_t b = bytes[l.e];
+            l.graph += fx_is_seq_byte(b) ? 1 : 0; l.forbidden |= fx_is_forbidden(b); l.del |= fx_is_del(b); l.is_void &= fx_is_void_byte(b);
+        }
+        return l;
+    };
+    std::vector<uint64_t> rec_pos, seq_off;
+    try {
+        uint64_t seq = 0, max_len = 0;
+        for (uint64_t hdr = 0; hdr < n;) {               // (byte hdr is '@')
+            uint64_t p = line_at(hdr).e + 1, L = 0, first_forbidden = kFxNone;
+            bool plus = false, plus_ended = false;
+            while (p < n && !plus) {                     // the sequence lines, up to the first line that starts with '+'
+                const Line l = line_at(p);
+                if (bytes[p] == 0x2B) { plus = true; plus_ended = l.e < n; }
+                else { L += l.graph; if (l.forbidden && first_forbidden == kFxNone) first_forbidden = p; }
+                p = l.e + 1;
+            }
+            if (!plus) return decline(hdr, FX_LINE_COUNT);
+            if (first_forbidden != kFxNone) return decline(first_forbidden, FX_SEQ_CHAR);
+            if (L == 0 && p < n && bytes[p] == 0x40) return decline(p, FX_FQ_EMPTY_SEQ);
+            uint64_t count = 0, first_del = kFxNone, passed = kFxNone;
+            while (plus_ended && count < L && p < n) {   // the quality lines
+                const Line l = line_at(p);
+                if (l.del && first_del == kFxNone) first_del = p;
+                count += l.graph;
+                if (count > L) passed = p;
+                p = l.e + 1;
+            }
+            if (first_del != kFxNone) return decline(first_del, FX_QUAL_DEL);
+            if (passed != kFxNone) return decline(passed, FX_QUAL_LONG);
+            if (!plus_ended || count < L) return decline(hdr, FX_QUAL_SHORT);
+            while (p < n) {                              // void lines
+                const Line l = line_at(p);
+                if (!l.is_void) break;
+                p = l.e + 1;
+            }
+            if (p < n && bytes[p] != 0x40) return decline(p, FX_FQ_HEADER);
+            rec_pos.push_back(hdr); seq_off.push_back(seq);
+            seq += L; max_len = std::max(max_len, L);
+            hdr = p;
+        }
+        rec_pos.push_back(n); seq_off.push_back(seq);
+        out->n_reads = rec_pos.size() - 1;
+        out->max_len = (uint32_t)std::min<uint64_t>(max_len, 0xFFFFFFFFull);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    const size_t bytes_arr = rec_pos.size() * sizeof(uint64_t);
+    out->rec_pos = (uint64_t *)malloc(bytes_arr); out->seq_off = (uint64_t *)malloc(bytes_arr);
+    if (!out->rec_pos || !out->seq_off) { free(out->rec_pos); free(out->seq_off); *out = FxHostScan(); return CRASS_ERR_OOM; }
+    memcpy(out->rec_pos, rec_pos.data(), bytes_arr); memcpy(out->seq_off, seq_off.data(), bytes_arr);
+    return CRASS_OK;
+}
+
+int fastx_scan_class_serial(const uint8_t *bytes, uint64_t n, int32_t fastq_class, FxHostScan *out)
+{
+    if (fastq_class == FX_CLASS_WRAPPED && n && bytes[0] == 0x40) return fastx_scan_wrapped_serial(bytes, n, out);
+    return fastx_scan_serial(bytes, n, out);
+}
+
 // the probe of fastx_scan.h, one byte after the other
 int fx_probe_serial(const uint8_t *bytes, uint64_t n, bool left_is_ls, FxProbe *out)
 {
@@ -177,15 +245,20 @@ int crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n
     return CRASS_OK;
 }
 
-int crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_layout *out)
+int crass_fastx_scan_host_class(const uint8_t *bytes, uint64_t n_bytes, int fastq_class, crass_fastx_layout *out)
 {
-    if (!out || (n_bytes && !bytes)) return CRASS_ERR_INVALID_ARG;
+    if (!out || (n_bytes && !bytes) || fastq_class < 0 || fastq_class > 1) return CRASS_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     crass::FxHostScan h;
-    const int s = crass::fastx_scan_serial(bytes, n_bytes, &h);
+    const int s = crass::fastx_scan_class_serial(bytes, n_bytes, fastq_class, &h);
     out->n_reads = h.n_reads; out->format = h.format; out->decline_reason = h.reason; out->decline_pos = h.decline_pos; out->max_len = h.max_len;
     out->rec_pos = h.rec_pos; out->seq_off = h.seq_off;
     return s;
+}
+
+int crass_fastx_scan_host(const uint8_t *bytes, uint64_t n_bytes, crass_fastx_layout *out)
+{
+    return crass_fastx_scan_host_class(bytes, n_bytes, crass::FX_CLASS_FOUR_LINE, out);
 }
 
 void crass_fastx_layout_free(crass_fastx_layout *l)
@@ -196,9 +269,10 @@ void crass_fastx_layout_free(crass_fastx_layout *l)
 }
 
 // several files as one set (crass_hip_load_fastx_files' restatement): file after file, the first that is declined ends the walk
-int crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, crass_fastx_files_layout *out)
+int crass_fastx_files_scan_host_class(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int fastq_class,
+                                      crass_fastx_files_layout *out)
 {
-    if (!out) return CRASS_ERR_INVALID_ARG;
+    if (!out || fastq_class < 0 || fastq_class > 1) return CRASS_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     out->decline_file = -1;
     if (!n_files || !bytes || !n_bytes) return CRASS_ERR_INVALID_ARG;
@@ -229,7 +303,7 @@ int crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_b
                 if (status != CRASS_OK) break;
             }
             crass::FxHostScan h;
-            status = crass::fastx_scan_serial(b, n, &h);
+            status = crass::fastx_scan_class_serial(b, n, fastq_class, &h);
             if (status == CRASS_ERR_UNSUPPORTED) { out->decline_file = (int32_t)f; out->decline_reason = h.reason; out->decline_pos = h.decline_pos; }
             if (status == CRASS_OK) {
                 const uint64_t t0 = seq_off.empty() ? 0 : seq_off.back();
@@ -254,6 +328,11 @@ int crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_b
         out->n_reads = nr; out->max_len = max_len;
     } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
     return CRASS_OK;
+}
+
+int crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, crass_fastx_files_layout *out)
+{
+    return crass_fastx_files_scan_host_class(bytes, n_bytes, n_files, crass::FX_CLASS_FOUR_LINE, out);
 }
 
 void crass_fastx_files_layout_free(crass_fastx_files_layout *l)

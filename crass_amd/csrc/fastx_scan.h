@@ -33,8 +33,39 @@ enum FxReason : int32_t {
     FX_QUAL_SHORT = 8,       // FASTQ: the quality line holds fewer bytes in 33..126 than the sequence line
     FX_QUAL_LONG = 9,        // FASTQ: ... more
     FX_LONE_HEADER = 10,     // FASTA: the last byte is a '>' that starts its line (kseq finds no record there)
-    FX_READ_TOO_LONG = 11    // accepted by the scan, refused by the layout: a read beyond CRASS_HIP_MAX_READ_LEN (the load calls only)
+    FX_READ_TOO_LONG = 11,   // accepted by the scan, refused by the layout: a read beyond CRASS_HIP_MAX_READ_LEN (the load calls only)
+    FX_FQ_EMPTY_SEQ = 12     // wrapped FASTQ: an empty sequence whose '+' line is followed by a line that starts with '@' (kseq.cpp:217 consumes that byte)
 };
+
+// ---- wrapped FASTQ (class 1: crass_fastx_scan_host_class, crass_hip_set_fastq_class) ----
+// Byte 0 is '@'; lines as above.  A VOID line holds no byte in 33..127.  A record is
+//   a header line, whose first byte is '@';
+//   zero or more sequence lines, none holding '>' '@' or '+';
+//   the first following line whose first byte is '+' (the rest of it is ignored); it ends with a '\n';
+//   quality lines: with L the record's sequence bytes, the lines behind the '+' line up to the first line END at which their
+//   bytes 33..126 are L or more (L == 0: none) — and there they must be exactly L;
+//   any number of void lines;
+//   the next record's header line, or the end of the input.
+// This is what kseq_read (kseq.cpp:171-226) reads record by record without losing a byte: its quality loop counts the bytes
+// 33..127 and swallows ONE byte behind the last one — a '\n' here, or the end of the input.
+// Offences of ONE record in the order they are looked for; the first found is the record's, the position is the first byte of
+// the line named:
+//    3  no line behind the header starts with '+'                                   the header line
+//    5  '>' '@' or '+' in a sequence line                                           the first such line
+//   12  L == 0 and the line behind the '+' line starts with '@'                     that line
+//    7  byte 127 in a quality line (the one the count passes L in included)         the first such line
+//    9  the count passes L inside a line                                            that line
+//    8  the input ends before the count is L, or inside the '+' line                the header line
+//    4  the first line behind the quality that is not void does not start with '@'   that line
+// Only the records REACHABLE from line 0 are judged, each from where the one before ended: a quality line that starts with
+// '@' is no header, and what it would offend as one is nobody's business.  The verdict is the first reachable record's that
+// offends.  Every regular (four-line) FASTQ is in this class, with the same records.
+enum FxFastqClass : int32_t { FX_CLASS_FOUR_LINE = 0, FX_CLASS_WRAPPED = 1 };
+CRASS_HD inline bool fx_is_void_byte(uint8_t b) { return b < 33 || b > 127; }                       // a void line holds only these
+// the four-line scan's declines that the wrapped scan takes up: every one a FASTQ earns by its shape.  (Not only 3, 4, 6, 8
+// and 9: "@r\n+\n\n" puts a '+' line where line 4k+1 should be, reason 5, and a header line of a later record may lie where
+// a quality line should and hold a byte 127, reason 7 — both are wrapped FASTQ.)
+CRASS_HD inline bool fx_wrapped_takes(int32_t reason) { return reason >= FX_LINE_COUNT && reason <= FX_QUAL_LONG; }
 
 // the kind of a line.  FASTA: header or sequence; FASTQ: the line's index modulo 4 — so 0 is a header and 1 a sequence line in both
 enum FxKind : uint32_t { FX_HEADER = 0, FX_SEQ = 1, FX_PLUS = 2, FX_QUAL = 3 };
@@ -112,6 +143,9 @@ struct FxHostScan {
     uint64_t *rec_pos = nullptr, *seq_off = nullptr;
 };
 int fastx_scan_serial(const uint8_t *bytes, uint64_t n_bytes, FxHostScan *out);      // CRASS_OK, CRASS_ERR_UNSUPPORTED (declined), CRASS_ERR_OOM
+// the same for a FASTQ class: FX_CLASS_FOUR_LINE is fastx_scan_serial; FX_CLASS_WRAPPED walks a file whose byte 0 is '@' record
+// by record under the wrapped rule (anything else, FASTA included, is fastx_scan_serial's)
+int fastx_scan_class_serial(const uint8_t *bytes, uint64_t n_bytes, int32_t fastq_class, FxHostScan *out);
 
 CRASS_HD inline bool fx_is_space(uint8_t b) { return b == 0x20 || (b >= 0x09 && b <= 0x0D); }       // isspace(): ends kseq's name
 

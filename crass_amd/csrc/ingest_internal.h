@@ -46,8 +46,13 @@ struct ScanResult {
 //   emit   the totals of the n_kept first pieces back, every one of them emits into one text and one pair of per-record
 //          arrays, tm_scan's second mark, the verdict: the first piece in order that offends.  max_reads: a set of that many
 //          records or more is CRASS_ERR_UNSUPPORTED (the files' name table holds 32-bit indices)
+//   wrapped  set between open and emit by the callers that honour crass_hip_set_fastq_class (a shard's slices never do): emit
+//          hands the FASTQ pieces the four-line scan declined for their shape to emit_wrapped, whose verdict is theirs
 struct ArenaScan {
     const uint8_t *arena = nullptr; const uint64_t *base = nullptr;
+    bool wrapped = false;
+    int emit_wrapped(crass_hip_ctx *c, uint32_t n_kept, uint64_t max_reads, const std::vector<int32_t> &w_of, uint32_t n_w,
+                     std::vector<uint64_t> &tbase, ScanResult &R);
     std::vector<uint64_t> tile0; std::vector<FxJob> jobs;      // (jobs.size(): the pieces planned)
     int open(crass_hip_ctx *c, const uint8_t *arena_, const uint64_t *base_, uint32_t n_pieces);
     int queue(crass_hip_ctx *c, uint32_t i, int32_t format, bool newline);

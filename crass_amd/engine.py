@@ -222,16 +222,19 @@ def _bytes_arg(buf):
     return np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
 
 
-def fastx_scan_host(buf):
+def fastx_scan_host(buf, fastq_class=0):
     """The record scan of the raw bytes of a FASTA / FASTQ file on the host (crass_fastx_scan_host; no GPU needed): a
-    FastxLayout, accepted or declined."""
+    FastxLayout, accepted or declined.  fastq_class 1: FASTQ by the wrapped rule (crass_fastx_scan_host_class)."""
     lib = _abi.load()
     a = _bytes_arg(buf)
     v = _abi.FastxLayoutC()
-    st = lib.crass_fastx_scan_host(a.ctypes.data if len(a) else None, len(a), C.byref(v))
+    if fastq_class:
+        fn, st = "crass_fastx_scan_host_class", lib.crass_fastx_scan_host_class(a.ctypes.data if len(a) else None, len(a), int(fastq_class), C.byref(v))
+    else:
+        fn, st = "crass_fastx_scan_host", lib.crass_fastx_scan_host(a.ctypes.data if len(a) else None, len(a), C.byref(v))
     try:
         if st not in (0, 2):
-            raise CrassError(st, "crass_fastx_scan_host")
+            raise CrassError(st, fn)
         return FastxLayout(v)
     finally:
         lib.crass_fastx_layout_free(C.byref(v))
@@ -444,13 +447,17 @@ def _files_args(bufs):
     return arrs, ptrs, lens
 
 
-def fastx_files_scan_host(bufs):
+def fastx_files_scan_host(bufs, fastq_class=0):
     """Several files' bytes as one read set on the host (crass_fastx_files_scan_host; no GPU needed): a FastxFilesLayout,
-    accepted or declined — what SearchEngine.load_fastx_files is tested against."""
+    accepted or declined — what SearchEngine.load_fastx_files is tested against.  fastq_class 1: every FASTQ file by the
+    wrapped rule (crass_fastx_files_scan_host_class)."""
     lib = _abi.load()
     arrs, ptrs, lens = _files_args(bufs)
     v = _abi.FastxFilesLayoutC()
-    st = lib.crass_fastx_files_scan_host(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), C.byref(v))
+    if fastq_class:
+        st = lib.crass_fastx_files_scan_host_class(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(fastq_class), C.byref(v))
+    else:
+        st = lib.crass_fastx_files_scan_host(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), C.byref(v))
     try:
         if st not in (0, 2):
             raise CrassError(st, "crass_fastx_files_scan_host")
@@ -1181,6 +1188,18 @@ class SearchEngine:
         """load_fastx_files takes a plain gzip file on a BGZF file's terms (crass_hip_set_gzip_on_device); default off.  members:
         plain gzip of any number of members (CRASS_GZIP_ON_DEVICE_MEMBERS), else single-member files only."""
         _chk(self.lib.crass_hip_set_gzip_on_device(self.h, (2 if members else 1) if on else 0), "crass_hip_set_gzip_on_device")
+
+    def set_fastq_class(self, fastq_class):
+        """The class the device ingest reads FASTQ by (crass_hip_set_fastq_class): 0, the default, the four-line form only; 1 also
+        wrapped FASTQ — records over several lines, blank lines between records and at the end."""
+        _chk(self.lib.crass_hip_set_fastq_class(self.h, int(fastq_class)), "crass_hip_set_fastq_class")
+
+    def last_scan_classes(self):
+        """(pieces decided by the four-line scan, pieces decided by the wrapped scan) of the last device load
+        (crass_hip_last_scan_classes)."""
+        out = (C.c_uint64 * 2)()
+        _chk(self.lib.crass_hip_last_scan_classes(self.h, out), "crass_hip_last_scan_classes")
+        return int(out[0]), int(out[1])
 
     def last_gzip_ms(self):
         """HIP-event milliseconds of the last gzip inflate's steps: dict find, count, decode, windows, narrow (stage timing >= 1, else 0)."""

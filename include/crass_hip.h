@@ -577,6 +577,39 @@ int  crass_hip_load_fastx_bytes(crass_hip_ctx *ctx, const uint8_t *bytes, uint64
  * only during the call: the caller may free them on return. */
 int  crass_hip_attach_device_fastx(crass_hip_ctx *ctx, const uint8_t *d_bytes, uint64_t n_bytes, int pad_uniform, uint64_t read_index_base,
                                    crass_fastx_layout *out);
+/* ---- wrapped FASTQ: records whose sequence or quality runs over several lines, blank lines between records and at the end ----
+ * FASTQ class 1 (class 0, the default, is the four-line form above).  What kseq_read (kseq.cpp:171-226) reads record by record
+ * without losing a byte: byte 0 is '@'; a VOID line holds no byte in 33..127; a record is a header line whose first byte is '@',
+ * zero or more sequence lines holding none of '>' '@' '+', the first following line whose first byte is '+' (the rest of it is
+ * ignored, it ends with a '\n'), quality lines — with L the record's bytes 33..126 of its sequence lines, the lines behind the '+'
+ * line up to the first line END at which their bytes 33..126 are L or more (none when L is 0), and there they are exactly L —,
+ * any number of void lines, then the next header line or the end of the input.  Every regular four-line FASTQ is in the class
+ * with the same layout; FASTA is untouched by the class.
+ * Declines, per record in this order, the position the first byte of the line named: 3 no line behind the header starts with '+'
+ * (the header line), 5 '>' '@' '+' in a sequence line (the first such line), 12 CRASS_FX_FQ_EMPTY_SEQ: the sequence is empty and
+ * the line behind the '+' line starts with '@' — kseq_read swallows that byte (kseq.cpp:217) — (that line), 7 byte 127 in a
+ * quality line (the first such line), 9 the count passes L inside a line (that line), 8 the input ends before the count is L or
+ * inside the '+' line (the header line), 4 the first line behind the quality that is not void does not start with '@' (that
+ * line); 1, 2 and 11 as above.  Only the records reachable from line 0 are judged: a quality line that starts with '@' is no
+ * header.  An '@' record without a '+' line (kseq reads it like FASTA) is declined with 3 or 5. */
+#define CRASS_FX_FQ_EMPTY_SEQ 12
+/* the host rule for a class (kseq.cpp:171-226): fastq_class 0 is crass_fastx_scan_host, byte for byte; 1 walks a file whose byte 0
+ * is '@' record by record under the wrapped rule.  CRASS_ERR_INVALID_ARG: a class outside 0..1. */
+int  crass_fastx_scan_host_class(const uint8_t *bytes, uint64_t n_bytes, int fastq_class, crass_fastx_layout *out);
+/* the class the context's device ingest reads FASTQ by (kseq.cpp:171-226): crass_hip_load_fastx_bytes, crass_hip_attach_device_fastx,
+ * crass_hip_load_fastx_bgzf / _gzip / _gzip_members and crass_hip_load_fastx_files.  0 (the default): every call as before.  1: a
+ * FASTQ piece is scanned by four lines first; where that scan declines it for its shape (reasons 3 .. 9), the wrapped scan
+ * (fastx_wrapped.hip) reads the piece again and its verdict is the call's: exactly crass_fastx_scan_host_class(.., 1, ..).  The
+ * group load (crass_hip_group_load_fastx_files) ignores the switch and declines as before: a wrapped file has no cut rule by
+ * lines modulo 4.  With class 1 set, crass_hip_fetch_quality_device(_to) reads a record's quality by the wrapped rule (k_qw_measure):
+ * behind the '+' line as many bytes 33..126 as the record has sequence bytes, over however many lines — on a four-line record
+ * the same answer as with class 0.  Header lines, names, header ids and comments need the record positions alone.
+ * crass_hip_last_scan_ms stays the four-line scan's kernels; the wrapped scan's are not in it.
+ * CRASS_ERR_INVALID_ARG: a class outside 0..1. */
+int  crass_hip_set_fastq_class(crass_hip_ctx *ctx, int fastq_class);
+/* the pieces (files) of the context's last device load whose layout the four-line scan decided (FASTA counts here), out[0], and
+ * the wrapped scan, out[1] (kseq.cpp:171-226 is what both agree with) */
+int  crass_hip_last_scan_classes(const crass_hip_ctx *ctx, uint64_t out[2]);
 /* replaces: the header_id argument of the load calls, for ANY resident set: header_id[n_reads] (host; NULL: all headers unique)
  * is copied to the device and the results of earlier passes are dropped, as by a load.  CRASS_ERR_STATE: no reads resident. */
 int  crass_hip_set_header_ids(crass_hip_ctx *ctx, const uint64_t *header_id);
@@ -922,6 +955,9 @@ typedef struct {
  * BGZF file — what the device call is tested against.  The arrays are malloc'd (crass_fastx_files_layout_free), NULL when declined
  * (n_files and the decline fields are always filled).  With one plain file: crass_fastx_scan_host's answer with bases 0. */
 int  crass_fastx_files_scan_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, crass_fastx_files_layout *out);
+/* the same with every FASTQ file read by a class (crass_fastx_scan_host_class; kseq.cpp:171-226): 0 is the call above */
+int  crass_fastx_files_scan_host_class(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, int fastq_class,
+                                       crass_fastx_files_layout *out);
 void crass_fastx_files_layout_free(crass_fastx_files_layout *l);
 /* the device call.  Uploads go through the two staged buffers of crass_hip_load_text, file after file (a BGZF file's compressed bytes
  * into scratch, inflated from there into the arena); file f's two scan kernels are queued before file f+1 is staged, so they run

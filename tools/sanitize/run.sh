@@ -70,3 +70,7 @@ echo "names of: $(grep -c '^ok  ' $out/report_names_of.txt) ok, $(grep -c '^DIFF
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/comments_of_main.cpp -o $out/comments_of_asan -lz
 $out/comments_of_asan > $out/report_comments_of.txt 2> $out/sanitizer_comments_of.txt || true
 echo "comments of: $(tail -1 $out/report_comments_of.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_comments_of.txt || true) sanitizer reports"
+# the wrapped FASTQ rule on the host (crass_fastx_scan_host_class) over built-in inputs and all their prefixes, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/wrapped_scan_main.cpp -o $out/wrapped_scan_asan -lz
+$out/wrapped_scan_asan > $out/report_wrapped.txt 2> $out/sanitizer_wrapped.txt || true
+echo "wrapped scan: $(tail -1 $out/report_wrapped.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_wrapped.txt || true) sanitizer reports"
