@@ -124,8 +124,10 @@ inline void dev_free(void *p)
 } // namespace crass
 
 // kernel launches of the library's .hip files go through this (same arguments as hipLaunchKernelGGL)
-#define CRASS_LAUNCH(kernel, ...)                                                            \
+#define CRASS_LAUNCH(kernel, ...) CRASS_LAUNCH_AS(#kernel, kernel, __VA_ARGS__)
+// ... under a given name: for a launch from a template, where the kernel is a parameter
+#define CRASS_LAUNCH_AS(name, kernel, ...)                                                   \
     do {                                                                                     \
-        if (crass::trace_launches()) fprintf(stderr, "[crass launch] %s\n", #kernel);        \
+        if (crass::trace_launches()) fprintf(stderr, "[crass launch] %s\n", name);           \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);                                             \
     } while (0)

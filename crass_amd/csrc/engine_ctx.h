@@ -237,7 +237,7 @@ struct Ingest {
     StageTimer<2> tm_fetch;
     float last_fetch_ms = 0;
     std::vector<uint8_t> f_flags;
-    // crass_hip_fastx_header_ids_device (fastx_names.hip): the name table, the uploaded record positions, the ids, the list of
+    // crass_hip_fastx_header_ids_device (fastx_hid.hip): the name table, the uploaded record positions, the ids, the list of
     // long names and the control words ([0..4) 32-bit: long names, bad position; then the 64-bit count of repeats) — all given
     // back before the call returns; the marks around the insert launches and behind the lookup launch
     DevBuf<unsigned long long> n_table; DevBuf<uint64_t> n_rec_pos, n_ids, n_ctl; DevBuf<uint32_t> n_long;
@@ -323,7 +323,7 @@ struct EnvSwitches {
     uint32_t long_min = 2048;                        // read sets whose longest read is beyond this take the long-read path (CRASS_LONG_MIN: the A/B switch)
     uint64_t text_chunk_bytes = 64ull << 20;         // crass_hip_load_text: text bytes per staged chunk (CRASS_TEXT_CHUNK_BYTES: tests force many chunks)
     bool inflate_hbm_window = true;                  // CRASS_INFLATE_WINDOW=lds: k_bgzf_inflate decodes in the wave's LDS window, not in the output's own range (A/B switch, inflate.hip)
-    uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_names.hip)
+    uint32_t hid_hash_bits = 64;                     // tests: CRASS_HID_TEST_HASH_BITS keeps only that many low bits of a name's hash (fastx_hid.hip)
     bool lane_find_serial = false;                   // CRASS_LANE_FIND_SERIAL=1: the A/B switch of the lane kernel's packed seed find (lane_find.h)
     uint32_t probe_blocks = 0;                       // tests: CRASS_PROBE_BLOCKS caps the grid of pass 2's anchor probe, so that a few thousand reads are several tiles per wave (0: off)
     void read()

@@ -360,7 +360,7 @@ int arena_finish(crass_hip_ctx *c, const uint8_t *arena, uint64_t n_arena_bytes,
     return CRASS_OK;
 }
 
-// ---- several files into one resident set (fastx_scan.hip, inflate.hip, fastx_names.hip) ----
+// ---- several files into one resident set (fastx_scan.hip, inflate.hip, fastx_hid.hip) ----
 namespace {
 struct FilesPlan {
     struct File { bool bgzf = false, gz = false; crass_bgzf_index ix{}; GzState gzs; uint64_t n_text = 0; int32_t format = 0; };

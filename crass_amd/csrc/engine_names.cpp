@@ -1,4 +1,4 @@
-// engine_names.cpp — the names of device-resident FASTA / FASTQ records (fastx_names.hip): header ids, given or computed from
+// engine_names.cpp — the names of device-resident FASTA / FASTQ records (fastx_hid.hip, fastx_lines.hip): header ids, given or computed from
 // a file's raw bytes; the name table kept on the device, names looked up in it and names read out of it, from the host or with
 // everything in device memory; header lines and quality strings of selected records; the comment kseq hands on from record to
 // record (the own-comment bitmap and the tiles' carries kept on the device, the handed comments of listed records).
@@ -23,7 +23,7 @@ int crass_hip_set_header_ids(crass_hip_ctx *c, const uint64_t *header_id)
     return CRASS_OK;
 }
 
-// ---- header ids from a file's raw bytes on the device (fastx_names.hip) ----
+// ---- header ids from a file's raw bytes on the device (fastx_hid.hip) ----
 // Every check that needs no byte of the file comes first; a record position outside the input is seen by the insert launch and
 // reported before the lookup launch and before anything is installed.
 // the insert step, shared by the header ids (the table is scratch) and crass_hip_fastx_names_build_device (the table is kept):
@@ -103,7 +103,7 @@ int crass_hip_fastx_header_ids_device(crass_hip_ctx *c, const uint8_t *d_bytes, 
 
 float crass_hip_last_header_ids_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 3 ? c->in.last_hid_ms[part] : 0.0f; }
 
-// ---- the name table kept on the device: names in, first read index out (fastx_names.hip) ----
+// ---- the name table kept on the device: names in, first read index out (fastx_hid.hip) ----
 // The table is built aside and replaces the one before only when the insert step accepted every record position: a build that
 // fails leaves the context as it was.
 static int names_build_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
@@ -333,7 +333,7 @@ int crass_hip_fastx_names_drop(crass_hip_ctx *c)
 
 float crass_hip_last_names_ms(const crass_hip_ctx *c, int part) { return c && part >= 0 && part < 2 ? c->in.last_names_ms[part] : 0.0f; }
 
-// ---- header lines and quality strings of selected records from a file's raw bytes on the device (fastx_names.hip) ----
+// ---- header lines and quality strings of selected records from a file's raw bytes on the device (fastx_lines.hip) ----
 // One routine for both: the records' source words up, the measure launch, the lengths back (they size the result), their prefix
 // sum on the host, the copy launch, the text back.  d_user == nullptr: the host route (the text comes back into B's pinned
 // memory, *out points at it); else the caller's device buffer of cap bytes, the offsets into off_user.  Every check comes
@@ -402,7 +402,7 @@ static int header_lines_common(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_
     ops.words = 1;
     ops.fill = [&](uint64_t k, uint64_t r, uint64_t *src) { src[k] = rec_pos[r] + 1; };
     ops.measure = [&](LineFetch &B) { J.src = B.src.p; J.line_len = B.len.p; J.name_len = B.len.p + n; return launch_hl_measure(J, c->stream); };
-    ops.copy = [&](LineFetch &B, uint64_t total, uint8_t *dst) { J.off = B.off.p; J.total = total; J.out = dst; return launch_hl_copy(J, c->stream); };
+    ops.copy = [&](LineFetch &B, uint64_t total, uint8_t *dst) { return launch_span_copy(SpanCopyJob{d_bytes, n_bytes, B.src.p, B.off.p, n, total, dst}, c->stream); };
     ops.second = [&](const uint32_t *half) { if (name_len_out) memcpy(name_len_out, half, n * 4); };
     return fetch_lines(c, &Ingest::hl, ops, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_user, cap, off_user, out);
 }
@@ -460,7 +460,7 @@ int crass_hip_fetch_quality_device_to(crass_hip_ctx *c, const uint8_t *d_bytes, 
     return quality_common(c, d_bytes, n_bytes, rec_pos, n_reads, idx, n, d_chars ? d_chars : &nowhere, cap_bytes, off_out, nullptr, has_qual_out);
 }
 
-// ---- the comment kseq hands on from record to record (fastx_scan.h; k_cm_* of fastx_names.hip) ----
+// ---- the comment kseq hands on from record to record (fastx_scan.h; k_cm_* of fastx_lines.hip) ----
 // The structure is built aside and replaces the one before only when every record position was accepted: a build that fails
 // leaves the context as it was.  Queued and waited for here: the positions up, the three launches, the flag and the total back.
 static int comments_build_impl(crass_hip_ctx *c, const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n,
@@ -590,8 +590,7 @@ static int comments_fetch_impl(crass_hip_ctx *c, const uint64_t *idx, uint64_t n
             HIPCHK(c, B.off.ensure(n + 1));
             if (!d_user) HIPCHK(c, B.chars.ensure(total));
             HIPCHK(c, hipMemcpyAsync(B.off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            J.off = B.off.p; J.total = total; J.out = d_user ? d_user : B.chars.p;
-            HIPCHK(c, launch_cm_copy(J, c->stream));
+            HIPCHK(c, launch_span_copy(SpanCopyJob{J.bytes, J.n_bytes, J.start, B.off.p, n, total, d_user ? d_user : B.chars.p}, c->stream));
             if (!d_user) HIPCHK(c, hipMemcpyAsync(B.h_chars.p, B.chars.p, total, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, I.tm_cm.mark(c->stream));

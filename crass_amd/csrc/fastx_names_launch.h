@@ -1,5 +1,6 @@
-// fastx_names_launch.h — the job descriptions and launch wrappers of fastx_names.hip (header ids, name lookups and header lines from the raw
-// bytes of a FASTA / FASTQ file on the device), for the engine.  Not part of the public ABI.
+// fastx_names_launch.h — the job descriptions and launch wrappers of fastx_hid.hip (the name table: header ids, name lookups) and
+// fastx_lines.hip (names, header lines, quality strings and handed comments of listed records) over the raw bytes of a FASTA /
+// FASTQ file on the device, for the engine.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -71,18 +72,26 @@ hipError_t launch_nm_measure_idx(const NmOfJob &J, hipStream_t st);
 hipError_t launch_nm_scan(const NmOfJob &J, hipStream_t st);        // the three launches: tile sums, one block over them, apply
 hipError_t launch_nm_copy(const NmOfJob &J, hipStream_t st);
 
-// k_hl_measure / k_hl_copy
+// k_span_copy: entry a's bytes are bytes[start[a] ...), as many as off[a + 1] - off[a], and go to out + off[a] (header lines,
+// handed comments)
+struct SpanCopyJob {
+    const uint8_t *bytes; uint64_t n_bytes;      // no byte at or beyond n_bytes is read
+    const uint64_t *start;           // [n]
+    const uint64_t *off;             // [n + 1] not decreasing from 0
+    uint64_t n;                      // >= 1
+    uint64_t total;                  // off[n]
+    uint8_t *out;                    // [total], any alignment
+};
+hipError_t launch_span_copy(const SpanCopyJob &J, hipStream_t st);
+
+// k_hl_measure; the copy is k_span_copy from src
 struct HlJob {
     const uint8_t *bytes; uint64_t n_bytes;
     const uint64_t *src;             // [n] position of the first byte behind the record's header character (<= n_bytes)
     uint64_t n;
     uint32_t *line_len, *name_len;   // [n] k_hl_measure
-    const uint64_t *off;             // [n + 1] k_hl_copy: where the records lie in out
-    uint64_t total;                  // off[n]
-    uint8_t *out;                    // [total], any alignment
 };
 hipError_t launch_hl_measure(const HlJob &J, hipStream_t st);
-hipError_t launch_hl_copy(const HlJob &J, hipStream_t st);
 
 // k_ql_measure / k_ql_copy: the quality strings of selected records
 struct QlJob {
@@ -112,7 +121,7 @@ struct CmBuildJob {
 };
 hipError_t launch_cm_build(const CmBuildJob &J, hipStream_t st);      // the three launches
 
-// k_cm_source / k_cm_measure / k_cm_copy: the comments handed to listed records
+// k_cm_source / k_cm_measure: the comments handed to listed records; the copy is k_span_copy from start
 struct CmFetchJob {
     const uint8_t *bytes; uint64_t n_bytes;
     const uint64_t *bits, *carry; uint64_t n_reads;      // as built
@@ -121,11 +130,8 @@ struct CmFetchJob {
     uint64_t *src;                               // [n] k_cm_source: the record whose own comment entry k is handed, ~0: none
     const uint64_t *pos;                         // [n] k_cm_measure: the first byte behind that record's header character, ~0: none
     uint64_t *start; uint32_t *len;              // [n] k_cm_measure: where the comment starts and its bytes
-    const uint64_t *off; uint64_t total;         // [n + 1] k_cm_copy: where the comments lie in out; off[n]
-    uint8_t *out;                                // [total], any alignment
 };
 hipError_t launch_cm_source(const CmFetchJob &J, hipStream_t st);
 hipError_t launch_cm_measure(const CmFetchJob &J, hipStream_t st);
-hipError_t launch_cm_copy(const CmFetchJob &J, hipStream_t st);
 
 } // namespace crass

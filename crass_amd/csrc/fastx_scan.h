@@ -149,7 +149,7 @@ int fastx_scan_class_serial(const uint8_t *bytes, uint64_t n_bytes, int32_t fast
 
 CRASS_HD inline bool fx_is_space(uint8_t b) { return b == 0x20 || (b >= 0x09 && b <= 0x0D); }       // isspace(): ends kseq's name
 
-// ---- the comment kseq hands on (crass_fastx_comments_of, the k_cm_* kernels of fastx_names.hip) ----
+// ---- the comment kseq hands on (crass_fastx_comments_of, the k_cm_* kernels of fastx_lines.hip) ----
 // A record's NAME is the bytes behind its header character up to the first fx_is_space() byte or the end of the file's text.
 // The record has an OWN comment iff its name ends at a byte that exists and is not '\n' (kseq.cpp:179-186: the delimiter that
 // ended the name decides whether the rest of the line is read).  The own comment is the bytes behind that delimiter up to, not

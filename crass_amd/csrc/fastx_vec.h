@@ -1,6 +1,6 @@
-// fastx_vec.h — what the device kernels that walk raw FASTA / FASTQ bytes tile by tile share (fastx_scan.hip, fastx_wrapped.hip):
-// the tile's size, a lane's aligned 16-byte vector with its byte classes and line starts, and the block scans.  Device code:
-// only .hip files include this.
+// fastx_vec.h — what the device kernels over raw FASTA / FASTQ bytes share: the tile's size, a lane's aligned 16-byte vector with
+// its byte classes and line starts (fastx_scan.hip, fastx_wrapped.hip), and the block scans: 32-bit (those two) and 64-bit
+// (fastx_wrapped.hip, fastx_lines.hip, fastx_hid.hip).  Device code: only .hip files include this.
 #pragma once
 #include "fastx_launch.h"
 #include "devmem.h"
@@ -87,6 +87,78 @@ static __device__ __forceinline__ uint32_t fx_wave_sum(uint32_t v)
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
     return v;
+}
+
+// ---- the 64-bit scans (a shuffle moves 32 bits: a value travels as its two halves).  Of unsigned values, so 0 is "nothing yet"
+// for the sum and for the maximum alike ----
+struct FxAdd64 { static __device__ __forceinline__ uint64_t of(uint64_t a, uint64_t b) { return a + b; } };
+struct FxMax64 { static __device__ __forceinline__ uint64_t of(uint64_t a, uint64_t b) { return b > a ? b : a; } };
+
+static __device__ __forceinline__ uint64_t fx_shfl_up64(uint64_t v, int s)
+{
+    const uint32_t a = (uint32_t)__shfl_up((int)(uint32_t)v, s), b = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), s);
+    return ((uint64_t)b << 32) | a;
+}
+static __device__ __forceinline__ uint64_t fx_shfl_xor64(uint64_t v, int s)
+{
+    const uint32_t a = (uint32_t)__shfl_xor((int)(uint32_t)v, s), b = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), s);
+    return ((uint64_t)b << 32) | a;
+}
+// the wave's v under Op, in every lane
+template <class Op> static __device__ __forceinline__ uint64_t fx_wave_all64(uint64_t v)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v = Op::of(v, fx_shfl_xor64(v, s));
+    return v;
+}
+static __device__ __forceinline__ uint64_t fx_wave_sum64(uint64_t v) { return fx_wave_all64<FxAdd64>(v); }
+// the block's sum of v over its NW waves, in every lane.  sh: NW words of LDS; safe to call again and again on the same sh
+template <int NW> static __device__ __forceinline__ uint64_t fx_block_sum64(uint64_t v, uint64_t *sh)
+{
+    v = fx_wave_sum64(v);
+    __syncthreads();                                    // (sh may still be read from the call before)
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t s = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) s += sh[w];
+    return s;
+}
+// what the lanes in front of this one hold in v, under Op (the exclusive prefix over the block; 0: none); *total: the whole
+// block's.  sh as above, with the same barriers
+template <int NW, class Op> static __device__ __forceinline__ uint64_t fx_block_prefix64(uint64_t v, uint64_t *sh, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const uint64_t o = fx_shfl_up64(inc, s); if (lane >= (uint32_t)s) inc = Op::of(inc, o); }
+    uint64_t before = fx_shfl_up64(inc, 1);
+    if (lane == 0) before = 0;
+    __syncthreads();                                    // (sh may still be read from the call before)
+    if (lane == 63u) sh[wave] = inc;
+    __syncthreads();
+    uint64_t all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)NW; w++) { const uint64_t s = sh[w]; if (w < wave) before = Op::of(s, before); all = Op::of(all, s); }
+    *total = all;
+    return before;
+}
+// the one-block top step of a three-launch scan, by the block's NW waves: a[0, n) in place, 64 NW values a step with what the
+// steps before came to in front.  a[t] becomes Op over a[0, t) — with INCL over a[0, t] —; returned: Op over all of them, in every
+// lane.  Every lane of the block calls it (the same trip count in each)
+template <int NW, class Op, bool INCL> static __device__ __forceinline__ uint64_t fx_top_scan64(uint64_t *a, uint64_t n, uint64_t *sh)
+{
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < n; t0 += 64 * NW) {
+        const uint64_t t = t0 + threadIdx.x;
+        const uint64_t v = t < n ? a[t] : 0;
+        uint64_t total;
+        uint64_t r = Op::of(carry, fx_block_prefix64<NW, Op>(v, sh, &total));
+        if (INCL) r = Op::of(r, v);
+        if (t < n) a[t] = r;
+        carry = Op::of(carry, total);
+    }
+    return carry;
 }
 
 } // namespace crass

@@ -15,7 +15,7 @@
 //                   records are marked; the launcher runs ceil(log2(lines)) + 1 rounds whatever the data.  Marks are set in
 //                   place: a lane may see a mark of its own round, which only marks a reachable line earlier — after the last
 //                   round the marked lines are exactly the reachable ones under every schedule.
-//   k_fw_rank_*     three launches (tiles, top, apply, as k_nm_scan_* of fastx_names.hip): a marked line's record index and the
+//   k_fw_rank_*     three launches (tiles, top, apply, as k_nm_scan_* of fastx_lines.hip): a marked line's record index and the
 //                   sequence bytes in front of it, 64-bit sums; the records' header lines in order; the verdict, the smallest
 //                   offence word of a marked line (only the last reachable record can have one)
 //   k_fw_place      a lane per line: a marked line writes rec_pos / seq_off; every line looks up the last header at or in front
@@ -183,59 +183,31 @@ __global__ __launch_bounds__(kFxThreads) void k_fw_jump(const FwJob J, const uin
     out[i] = in[a];
 }
 
-// what the lanes in front of this one hold in v, summed; *total: the block's sum (sh: one word per wave)
-static __device__ __forceinline__ uint64_t fw_block_prefix64(uint64_t v, uint64_t *sh, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t a = (uint32_t)__shfl_up((int)(uint32_t)inc, s), b = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), s);
-        if (lane >= (uint32_t)s) inc += ((uint64_t)b << 32) | a;
-    }
-    __syncthreads();                                    // (sh may still be read from the call before)
-    if (lane == 63u) sh[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kFxThreads / 64; w++) { const uint64_t s = sh[w]; if (w < wave) before += s; all += s; }
-    *total = all;
-    return before + inc - v;
-}
-
+static constexpr int kFwWaves = kFxThreads / 64;
 static constexpr uint32_t kFwRankItems = kFwRankTile / kFxThreads;
 
 __global__ __launch_bounds__(kFxThreads) void k_fw_rank_tiles(const FwJob J)
 {
-    __shared__ uint64_t sh[kFxThreads / 64];
+    __shared__ uint64_t sh[kFwWaves];
     const uint64_t k0 = (uint64_t)blockIdx.x * kFwRankTile + (uint64_t)threadIdx.x * kFwRankItems;
     uint64_t cnt = 0, len = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kFwRankItems; j++) if (k0 + j < J.n_lines && J.mark[k0 + j]) { cnt++; len += J.seqlen[k0 + j]; }
-    uint64_t t_cnt, t_len;
-    (void)fw_block_prefix64(cnt, sh, &t_cnt);
-    (void)fw_block_prefix64(len, sh, &t_len);
+    const uint64_t t_cnt = fx_block_sum64<kFwWaves>(cnt, sh), t_len = fx_block_sum64<kFwWaves>(len, sh);
     if (threadIdx.x == 0) { J.tile_cnt[blockIdx.x] = t_cnt; J.tile_len[blockIdx.x] = t_len; }
 }
 
 __global__ __launch_bounds__(kFxThreads) void k_fw_rank_top(const FwJob J, const uint64_t n_tiles)
 {
-    __shared__ uint64_t sh[kFxThreads / 64];
-    uint64_t c_cnt = 0, c_len = 0;
-    for (uint64_t t0 = 0; t0 < n_tiles; t0 += kFxThreads) {      // (the same trip count in every lane)
-        const uint64_t t = t0 + threadIdx.x;
-        uint64_t t_cnt, t_len;
-        const uint64_t b_cnt = fw_block_prefix64(t < n_tiles ? J.tile_cnt[t] : 0, sh, &t_cnt);
-        const uint64_t b_len = fw_block_prefix64(t < n_tiles ? J.tile_len[t] : 0, sh, &t_len);
-        if (t < n_tiles) { J.tile_cnt[t] = c_cnt + b_cnt; J.tile_len[t] = c_len + b_len; }
-        c_cnt += t_cnt; c_len += t_len;
-    }
+    __shared__ uint64_t sh[kFwWaves];
+    const uint64_t c_cnt = fx_top_scan64<kFwWaves, FxAdd64, false>(J.tile_cnt, n_tiles, sh);
+    const uint64_t c_len = fx_top_scan64<kFwWaves, FxAdd64, false>(J.tile_len, n_tiles, sh);
     if (threadIdx.x == 0) { J.tile_cnt[n_tiles] = c_cnt; J.tile_len[n_tiles] = c_len; J.tot[5] = c_cnt; J.tot[6] = c_len; }
 }
 
 __global__ __launch_bounds__(kFxThreads) void k_fw_rank_apply(const FwJob J)
 {
-    __shared__ uint64_t sh[kFxThreads / 64];
+    __shared__ uint64_t sh[kFwWaves];
     const uint64_t k0 = (uint64_t)blockIdx.x * kFwRankTile + (uint64_t)threadIdx.x * kFwRankItems;
     uint32_t m[kFwRankItems];
     uint64_t l[kFwRankItems], cnt = 0, len = 0, off = kFxNoOffence;
@@ -247,8 +219,8 @@ __global__ __launch_bounds__(kFxThreads) void k_fw_rank_apply(const FwJob J)
         if (m[j] && J.off[k0 + j] < off) off = J.off[k0 + j];
     }
     uint64_t total;
-    uint64_t at = J.tile_cnt[blockIdx.x] + fw_block_prefix64(cnt, sh, &total);
-    uint64_t pre = J.tile_len[blockIdx.x] + fw_block_prefix64(len, sh, &total);
+    uint64_t at = J.tile_cnt[blockIdx.x] + fx_block_prefix64<kFwWaves, FxAdd64>(cnt, sh, &total);
+    uint64_t pre = J.tile_len[blockIdx.x] + fx_block_prefix64<kFwWaves, FxAdd64>(len, sh, &total);
 #pragma unroll
     for (uint32_t j = 0; j < kFwRankItems; j++) {
         if (k0 + j >= J.n_lines) break;

@@ -629,7 +629,7 @@ int  crass_fastx_find_names(const uint8_t *bytes, uint64_t n_bytes, const uint64
                             const uint8_t *names, const uint64_t *name_off, uint64_t n_names, uint64_t *first_out);
 /* replaces: the same (crass_fastx.header_id, readsFound's key) for a caller whose file bytes exist only on the DEVICE, which would
  * otherwise copy the file back to feed crass_fastx_header_ids: header_id_out[r] (host, [n_reads], may be NULL) is exactly that
- * function's result on the same bytes.  Names are hashed into a device table and compared byte for byte (fastx_names.hip): no
+ * function's result on the same bytes.  Names are hashed into a device table and compared byte for byte (fastx_hid.hip): no
  * answer rests on a hash.  d_bytes: a device pointer of any alignment, read only during the call; rec_pos: the HOST array of a
  * layout (the context's own pinned one is fine), uploaded into scratch that is given back with the table (8 bytes per slot,
  * the smallest power of two >= 2 n_reads slots) before the call returns.  install != 0: as crass_hip_set_header_ids(ctx, those
@@ -1086,7 +1086,7 @@ int  crass_hip_group_fetch_quality(crass_hip_group *g, const uint64_t *read_idx,
 int  crass_fastx_comments_of(const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_pos, uint64_t n_reads, const uint64_t *file_read_base,
                              uint32_t n_files, const uint64_t *idx, uint64_t n, uint64_t idx_base, uint8_t *out, uint64_t cap_bytes,
                              uint64_t *off_out, uint8_t *has_out);
-/* the device side, for bytes that exist only in HBM (fastx_names.hip).  BUILD: k_cm_bits — a lane per record walks its name, a
+/* the device side, for bytes that exist only in HBM (fastx_lines.hip).  BUILD: k_cm_bits — a lane per record walks its name, a
  * wave's ballot is one 64-bit word of the own-comment BITMAP; k_cm_tiles / k_cm_top — every tile of 4 096 records gets a carry
  * word, the last own-comment record in all tiles up to and including it (a maximum scan in launches of their own: no block
  * waits for another).  Kept in the context: one bit per record, 8 bytes per tile and file_read_base; the record positions are
@@ -1101,7 +1101,7 @@ int  crass_hip_fastx_comments_drop(crass_hip_ctx *ctx);
 /* FETCH: the handed comments of the records idx[0..n) (HOST array, LOCAL record numbers, any order, repeats allowed) — k_cm_source:
  * a lane per listed record bisects file_read_base, finds its source in the bitmap (its own word, the earlier words of its tile,
  * the carry of the tile in front) and drops a source in front of its file's first record; k_cm_measure walks the source's name
- * and comment; k_cm_copy, a lane per OUTPUT byte, copies.  The result is a crass_text in the context's pinned memory (its own),
+ * and comment; k_span_copy, a lane per OUTPUT byte, copies.  The result is a crass_text in the context's pinned memory (its own),
  * valid until the next call of this function or destroy; has_out (host [n], may be NULL) as in the host rule.  Without a built
  * structure the first fetch after crass_hip_load_fastx_files builds it on the arena; else CRASS_ERR_STATE.  Exact:
  * crass_fastx_comments_of on the same bytes.  CRASS_ERR_INVALID_ARG — NULL context or result, NULL idx with n > 0, an idx[k] >= n_reads. */

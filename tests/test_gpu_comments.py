@@ -1,5 +1,5 @@
 """The comment kseq hands on from record to record, on the device (k_cm_bits / k_cm_tiles / k_cm_top, k_cm_source / k_cm_measure
-/ k_cm_copy) against the host function crass_fastx_comments_of on every designed job of tests/comment_sets.py, exact: the bytes,
+/ k_span_copy) against the host function crass_fastx_comments_of on every designed job of tests/comment_sets.py, exact: the bytes,
 the offsets and `has`.  Through crass_hip_load_fastx_files (plain files, and the same files as BGZF) — the first fetch builds the
 structure on the arena — and through comments_build on caller-owned device bytes at every byte offset 0 .. 3; the _to form's
 overflow rule with guard bytes around the buffer; CRASS_ERR_STATE after a drop and after a new load; the counters."""
@@ -113,6 +113,40 @@ def test_caller_owned_bytes_equal_the_host_function(ca, eng, host, name):
     if lay.n_files == 1:                                 # file_read_base None: one file
         eng.comments_build(t, lay.rec_pos)
         check_fetch(eng, all_records, lists(name, lay.n_reads)[0], (name, "one file"))
+    eng.comments_drop()
+
+
+def test_more_tiles_than_one_step_of_the_carry_scan(ca, eng):
+    """256 * 4096 + 4097 minimal records: 258 tiles, so the one block over the tiles' carries takes a second step, with the running
+    maximum of the first in front.  Own comments only at record 0, at the last record of tile 255, at the first of tile 256 and
+    at one record of the last tile; about 40 records on both sides of each are fetched (both sides of the boundary between the
+    steps among them) and compared with crass_fastx_comments_of; the counters are the host's counts."""
+    tile = 4096
+    B = 256 * tile
+    n = B + tile + 1
+    own = {0: b"first", B - 1: b"end of tile 255", B: b"tile 256", n - 1: b"in the last tile"}
+    assert (n - 1) // tile == 257 and len({len(c) for c in own.values()}) == len(own)
+    recs = [b">x\n"] * n
+    for r, c in own.items():
+        recs[r] = b">x " + c + b"\n"
+    data = b"".join(recs)
+    rec_pos = np.zeros(n + 1, np.uint64)
+    rec_pos[1:] = np.cumsum(np.fromiter(map(len, recs), np.uint64, n))
+    assert int(rec_pos[-1]) == len(data)
+    idx = sorted({r for p in own for r in range(max(p - 40, 0), min(p + 41, n))})
+    idx = idx[::-1] + idx[::7]                           # out of order, with repeats
+    want_c, want_o, want_h = ca.comments_of(data, rec_pos, idx)
+    assert want_h.all() and bytes(want_c[:int(want_o[1])]) == own[n - 1]
+    # the host's counts: every record is handed one of four comments of four lengths, each from where it starts
+    all_o = ca.comments_of(data, rec_pos, np.arange(n, dtype=np.uint64))[1]
+    handed = np.diff(all_o.astype(np.int64))
+    starts = np.flatnonzero(np.diff(handed)) + 1
+    assert starts.tolist() == sorted(own)[1:]
+    big, t = dev_bytes(data, 3)
+    eng.comments_build(t, rec_pos)
+    assert eng.comments_counters() == (1 + len(starts), n)
+    c, o, h = eng.fetch_comments(idx)
+    assert np.array_equal(o, want_o) and np.array_equal(h, want_h) and np.array_equal(c[:int(want_o[-1])], want_c)
     eng.comments_drop()
 
 

@@ -1,5 +1,5 @@
 """Names in, first record index out, from a name table kept on the device (crass_hip_fastx_names_build_device / _find / _drop,
-k_hid_find and k_hid_find_long of fastx_names.hip) against the host's crass_fastx_find_names on the same bytes, element for
+k_hid_find and k_hid_find_long of fastx_hid.hip) against the host's crass_fastx_find_names on the same bytes, element for
 element: designed names, probe chains under a cut hash (CRASS_HID_TEST_HASH_BITS), every alignment of the bytes and of the
 queries, lane and wave kernel on both sides, the files route, errors, and the header ids of the same context left as they were."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """Header ids and header lines from FASTA / FASTQ bytes that live on the device (crass_hip_fastx_header_ids_device,
-crass_hip_fetch_header_lines_device, fastx_names.hip) against the host: crass_fastx_header_ids on the same bytes, the lines
+crass_hip_fetch_header_lines_device, fastx_hid.hip, fastx_lines.hip) against the host: crass_fastx_header_ids on the same bytes, the lines
 sliced from the bytes in Python, the names crass_read_fastx (kseq) cuts, and the same answers through seed scan, merge and
 recruit.  Every comparison is exact equality."""
 import os

@@ -139,6 +139,33 @@ def test_names_of_device_counts_around_the_scan_tile(ca, eng, T):
     eng.names_drop()
 
 
+def test_names_of_device_counts_beyond_one_step_of_the_top_scan(ca, eng, T):
+    """256 T, 256 T + 1 and 2 * 256 T + 1 entries: the one block over the tile sums takes 256 tiles a step, so these lists take
+    its second and third step, with the carry of the steps before in front.  Records of empty names at the entries 256 T - 1,
+    256 T and the last; then the other way round, only those three carry bytes.  (Nearly all entries are records of names up to 8
+    bytes, one in a thousand is any record: the output stays a few MB.)"""
+    data, rp = TEXTS["lengths_fa"]
+    n_reads = len(rp) - 1
+    lens = np.asarray([len(name_sets.name_at(data, int(rp[r]))) for r in range(n_reads)])
+    empty, short, named = np.flatnonzero(lens == 0), np.flatnonzero((lens > 0) & (lens <= 8)), np.flatnonzero(lens > 0)
+    assert len(empty) and len(short) > 8 and lens.max() >= 1000
+    S = 256 * T
+    big, t = dev_bytes(data, 2)
+    eng.names_build(t, rp)
+    rng = np.random.default_rng(12)
+    for n in (S, S + 1, 2 * S + 1):
+        edges = [e for e in (S - 1, S, n - 1) if e < n]
+        idx = short[rng.integers(0, len(short), n)]
+        any_at = rng.integers(0, n, n // 1000)
+        idx[any_at] = named[rng.integers(0, len(named), len(any_at))]
+        idx[edges] = empty[:1]
+        names_of_check(ca, eng, data, rp, idx, 7, n % 4, what=("n", n))
+        idx2 = np.full(n, empty[0])
+        idx2[edges] = named[rng.integers(0, len(named), len(edges))]
+        names_of_check(ca, eng, data, rp, idx2, 0, 2, what=("n edges", n))
+    eng.names_drop()
+
+
 def test_names_of_device_errors(ca, T):
     lib = ca.load()
     data, rp = TEXTS["prefixes"]

@@ -113,6 +113,30 @@ def test_designed_inputs_give_the_unwrapped_set(ca, eng, eng4, name):
         check_resident(eng, lay, ref, name, "%s attach_device_fastx lead %d" % (name, lead))
 
 
+@pytest.mark.parametrize("last", ["one_line", "two_lines"])
+def test_more_lines_than_one_step_of_the_rank_scan(ca, eng, eng4, last):
+    """65 537 four-line records of one base and a blank line behind them: more than 256 * 1024 lines, so the one block over the
+    rank scan's tiles takes a second step for both of its sums, with the carries of the first in front.  The layout is the host
+    rule's, the packed set that of the same reads as four-line FASTQ; then with the last record's sequence over two lines"""
+    n = 65537
+    tail = b"@r\nG\n+\nI\n" if last == "one_line" else b"@r\nG\nT\n+\nIJ\n"
+    data = b"@r\nA\n+\nI\n" * (n - 1) + tail + b"\n"
+    assert data.count(b"\n") > 256 * 1024
+    host = ca.fastx_scan_host(data, fastq_class=1)
+    assert host.accepted and host.n_reads == n and host.max_len == (1 if last == "one_line" else 2)
+    assert not ca.fastx_scan_host(data).accepted         # (the blank line: the four-line scan leaves it to the wrapped one)
+    eng4.load_fastx_bytes(b"@r\nA\n+\nI\n" * (n - 1) + (tail if last == "one_line" else b"@r\nGT\n+\nIJ\n"), pad_uniform=PAD)
+    want = eng4.packed()
+    lay = eng.load_fastx_bytes(data, pad_uniform=PAD)
+    assert eng.last_scan_classes() == (0, 1)
+    assert lay.accepted and (lay.n_reads, lay.format, lay.max_len, lay.decline_pos) == (n, b"@", host.max_len, 0)
+    assert np.array_equal(lay.rec_pos, host.rec_pos) and np.array_equal(lay.seq_off, host.seq_off)
+    got = eng.packed()
+    assert_same_set(got.arrays(), want.arrays(), last)
+    got.close()
+    want.close()
+
+
 # ---- 2. class 0 declines as before; class 1 declines with the host rule's verdict ----
 @pytest.mark.parametrize("name", sorted(n for n in DESIGNED if n not in wrapped_sets.FOUR_LINE and not n.startswith("records_")) + ["records_65"])
 def test_class_zero_declines_as_before(ca, eng4, name):

@@ -1,4 +1,4 @@
-"""The entry points of fastx_names.hip without a GPU: they resolve, and the checks that come before any device call answer
+"""The entry points of fastx_hid.hip and fastx_lines.hip without a GPU: they resolve, and the checks that come before any device call answer
 with the documented status (tests/test_gpu_header_ids.py does the rest on the device)."""
 import numpy as np
 

@@ -5,7 +5,7 @@ Two files of synthetic 150 bp reads as four-line FASTQ (--reads N in all, defaul
 tools/load_files_time.py with a comment on every third header line), loaded once with crass_hip_load_fastx_files.  Then, medians
 of --reps (5), wall milliseconds and the HIP-event milliseconds of crass_hip_last_comments_ms (timing level 1):
   (a) crass_hip_fastx_comments_build_device on the arena      k_cm_bits / k_cm_tiles / k_cm_top, the record positions up
-  (b) crass_hip_fetch_comments_device of 1 % of the records   k_cm_source / k_cm_measure / k_cm_copy, drawn without order
+  (b) crass_hip_fetch_comments_device of 1 % of the records   k_cm_source / k_cm_measure / k_span_copy, drawn without order
   (c) the arena copied back to the host + crass_fastx_comments_of for the same records       what (a) + (b) replace
 and whether (b) and (c) agree byte for byte.  Output: stdout and profiles/comments_time_mi355x.txt (--out)."""
 import argparse

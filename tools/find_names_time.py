@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What it costs to turn names that come from elsewhere into record indices of a FASTQ whose bytes live on the device: the name
-table kept on the device (crass_hip_fastx_names_build_device, crass_hip_fastx_names_find; fastx_names.hip) against the host
+table kept on the device (crass_hip_fastx_names_build_device, crass_hip_fastx_names_find; fastx_hid.hip) against the host
 function on host bytes, and the copy back a caller pays without it.
 
 Synthetic FASTQ built with numpy, fixed-width records ('@' + 'r' + nine digits + ' ' + mate + '\\n' + 50 bases + '\\n+\\n' + 50

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What header ids cost a caller whose FASTA bytes live on the device: the host function on host bytes against the device call
-(fastx_names.hip), and the copy back such a caller pays today to feed the host function.
+(fastx_hid.hip), and the copy back such a caller pays today to feed the host function.
 
 Synthetic FASTA built with numpy, fixed-width records ('>' + 'r' + nine digits + ' ' + mate + '\\n' + 50 bases + '\\n'), so the
 record positions are known without a scan; --reads in millions (default 1,10,50; sizes that do not fit half of the available
