@@ -44,7 +44,9 @@ an oracle whose searchCore window was moved by one base (not part of the suite: 
 
 QC ARRAYS (qc_arrays) pin ln_qc, the in-lane qcFoundRepeats that the pooled tests do not take: arrays of four to seven repeats
 (251 and 400 bases) and, under -S 90, spacers beyond 64 bases with two, three and four repeats — the similarity tests' one
-site in its three modes, the per-base distance loops, the float averages in the reference's order.
+site in its three modes, the per-base distance loops, the float averages in the reference's order.  The POOLED QC of two and
+three repeats (qc_pool_begin_queued .. qc_pool_end), the extension and the orientation are tests/test_gpu_lane_sets.py's, on
+the twin pairs of tests/lane_sets.py.
 """
 import hashlib
 import json
