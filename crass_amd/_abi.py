@@ -343,6 +343,10 @@ SYMBOLS = {
     "crass_fastx_cut_probe_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
     "crass_hip_fastx_cut_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
     "crass_hip_last_cut_probe_ms": (C.c_float, [C.c_void_p]),
+    "crass_hip_last_cut_chain_ms": (C.c_float, [C.c_void_p]),
+    "crass_fastx_files_shards_host_class": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(FastxShardsC)]),
+    "crass_hip_group_set_fastq_class": (C.c_int, [C.c_void_p, C.c_int]),
+    "crass_hip_group_load_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "crass_hip_group_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.c_void_p,
                                                    C.POINTER(FastxShardsC)]),
     "crass_hip_group_fetch_comments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Text), C.c_void_p]),

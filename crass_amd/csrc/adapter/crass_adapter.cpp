@@ -851,11 +851,19 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
         if (timing) fprintf(stderr, "[crass_timing] %llu reads of %zu file(s) parsed and packed on the device (crass_hip_load_fastx_files)\n", (unsigned long long)n, seqFiles.size());
     }
     if (devices_ingest) {
+        // CRASS_DEVICE_FASTQ, as the device route reads it: wrapped FASTQ is cut at the records reachable from a file's line 0
+        // (crass_hip_group_set_fastq_class)
+        bool wrapped = false;
+        if (const char *e = getenv("CRASS_DEVICE_FASTQ")) {
+            wrapped = !strcmp(e, "wrapped");
+            if (!wrapped && strcmp(e, "four-line")) throw input_error(std::string("crass [ERROR]: CRASS_DEVICE_FASTQ=") + e + " is neither wrapped nor four-line");
+            chk(crass_hip_group_set_fastq_class(made.g, wrapped ? 1 : 0), "crass_hip_group_set_fastq_class");
+        }
         crass_fastx_shards sh;
         const int s = crass_hip_group_load_fastx_files(made.g, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, nullptr, &sh);
         if (s == CRASS_ERR_UNSUPPORTED && sh.decline_file >= 0) {
             lay.decline_file = sh.decline_file; lay.decline_reason = sh.decline_reason; lay.decline_pos = sh.decline_pos; lay.bgzf = sh.bgzf;
-            throw input_error(decline_message(seqFiles, lay, "devices"));
+            throw input_error(decline_message(seqFiles, lay, "devices", wrapped));
         }
         if (s == CRASS_ERR_RCCL) CRASS_THROW(std::string("crass_hip_group_load_fastx_files: ") + crass_hip_group_last_error());
         chk(s, "crass_hip_group_load_fastx_files");

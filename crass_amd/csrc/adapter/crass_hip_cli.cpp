@@ -48,8 +48,9 @@ static void usage()
                  "                 FASTA / FASTQ) is an error\n"
                  "  CRASS_DEVICE_GZIP=1   with CRASS_INGEST=device: a plain (single-member) gzip input is inflated on the GPU too\n"
                  "  CRASS_DEVICE_GZIP=2   ... and plain gzip of any number of members (cat of .gz files, gzip's >>)\n"
-                 "  CRASS_DEVICE_FASTQ=wrapped   with CRASS_INGEST=device: FASTQ records whose sequence or quality runs over several\n"
-                 "                 lines, and blank lines between records and at the end, are read too (default: four-line)\n";
+                 "  CRASS_DEVICE_FASTQ=wrapped   with CRASS_INGEST=device or devices: FASTQ records whose sequence or quality runs over\n"
+                 "                 several lines, and blank lines between records and at the end, are read too (default: four-line);\n"
+                 "                 devices: the shards are cut at the records reachable from a file's first line\n";
 }
 
 // CRASS_SMAPS_AT_EXIT=1: the mappings with the largest resident sets, at the end of every stage (what the kernel takes back at _exit)

@@ -293,6 +293,20 @@ struct Ingest {
     uint64_t sh_n_reads = 0; bool sh_scanned = false, sh_loaded = false;
     StageTimer<2> tm_probe;
     float last_probe_ms = 0;
+    // ... and of a wrapped-mode piece (fastx_shards.h): its line table and chain (k_fw_cut_*, scratch as fw_scratch_words), kept
+    // from shard_stage_probe to the end of the chain over the ranks; text: the piece staged again with a larger margin, where the
+    // chain asked for it.  Given back with the shard's.  The answer of a look-up, and the cut kernels' event times of the load
+    struct ShardCut {
+        uint32_t file; uint64_t a, b, se, margin;      // the piece [a, b) of the file, staged up to se
+        bool left_is_ls; const uint8_t *bytes;          // a is a line start; the device bytes of position a
+        FwJob J; uint32_t which;
+        DevBuf<uint64_t> scratch; DevBuf<uint8_t> text;
+    };
+    std::vector<ShardCut> sh_cut;
+    DevBuf<uint64_t> sh_cut_out; PinBuf<uint64_t> sh_h_cut_out;
+    hipEvent_t ev_cut[2] = {nullptr, nullptr};
+    float cut_ms = 0;
+    uint64_t cut_lookups = 0, cut_doublings = 0;
 };
 
 } // namespace crass

@@ -102,13 +102,15 @@ void release_comments_build(crass_hip_ctx *c)
     I.cb_rec_pos.release(); I.cb_cnt.release(); I.cb_flag.release();
 }
 
-// a shard's staged text, its BGZF tail and the probe's parts (fastx_shards.h)
+// a shard's staged text, its BGZF tail, the probe's parts and the wrapped-mode pieces' chains (fastx_shards.h)
 void release_shard(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
     wait_both(c);
     I.sh_stage.release(); I.sh_tail.release(); I.sh_part.release();
     I.sh_staged.clear(); I.sh_scanned = false;
+    for (auto &k : I.sh_cut) { k.scratch.release(); k.text.release(); }
+    I.sh_cut.clear(); I.sh_cut_out.release();
 }
 
 void ingest_free_all(crass_hip_ctx *c)
@@ -117,7 +119,8 @@ void ingest_free_all(crass_hip_ctx *c)
     release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c); release_names_of(c);
     release_comments_build(c); I.cb_h.release(); I.cm.free_all(); I.tm_cm.destroy();
     names_drop(c); drop_arena(c);
-    release_shard(c); I.sh_h_part.release(); I.tm_probe.destroy();
+    release_shard(c); I.sh_h_part.release(); I.tm_probe.destroy(); I.sh_h_cut_out.release();
+    for (hipEvent_t &e : I.ev_cut) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     I.hl.free_all(); I.ql.free_all();
     // what is kept from call to call, and the pinned sides of the results
     I.f_idx.release(); I.f_off.release(); I.f_rc.release(); I.f_chars.release();

@@ -103,5 +103,13 @@ void fw_lay_out(FwJob &J, uint64_t *scratch);
 hipError_t launch_fw_tiles(const FwJob &J, hipStream_t st);      // k_fw_summary, k_fw_tile_scan: tot[0 .. 5)
 hipError_t launch_fw_analyse(const FwJob &J, hipStream_t st);    // k_fw_lines, k_fw_next, k_fw_jump rounds, the rank scan: tot[5 .. 8)
 hipError_t launch_fw_emit(const FwJob &J, hipStream_t st);       // k_fw_place, k_fw_emit
+// the cut of a group's files load: the job is a piece [a, b) of a wrapped file with a margin staged behind it, positions counted
+// from a.  What a look-up says of the chain that starts at a record start of the piece:
+// (FwCutKind, fastx_scan.h)
+struct FwCut { uint64_t b; uint32_t at_eof, first_cand; };      // the piece's end; the staged bytes end the file; 1: position 0 is no line start
+// k_fw_lines, k_fw_cut_next, the k_fw_cut_jump rounds (after launch_fw_tiles and with n_lines read back); *which: the nxt array that holds the terminals
+hipError_t launch_fw_cut(const FwJob &J, const FwCut &K, hipStream_t st, uint32_t *which);
+// k_fw_cut_lookup: d_out[3] = kind, the terminal's position, its offence word
+hipError_t launch_fw_cut_lookup(const FwJob &J, uint32_t which, uint64_t p, uint64_t *d_out, hipStream_t st);
 
 } // namespace crass

@@ -204,15 +204,17 @@ void crass_fastx_shards_free(crass_fastx_shards *s)
 // The cut rule of fastx_scan.h on the host.  The verdict is crass_fastx_files_scan_host's; an ACCEPTED file's record starts are
 // that scan's rec_pos (regular FASTA: the line starts whose byte is '>'; regular FASTQ: the lines of index 0 modulo 4), so the
 // actual cut is the first record position at or after the nominal one.
-int crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks, const uint64_t *nominal,
-                                  crass_fastx_shards *out)
+// Class 1: the same with crass_fastx_files_scan_host_class(.., 1, ..) — a wrapped file's rec_pos are the header lines of the
+// records the wrapped rule walks from line 0, which is that class's definition of a record start.
+int crass_fastx_files_shards_host_class(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks, const uint64_t *nominal,
+                                        int fastq_class, crass_fastx_shards *out)
 {
     if (!out) return CRASS_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     out->decline_file = -1; out->n_ranks = n_ranks; out->n_files = n_files;
-    if (!n_ranks || n_ranks > 64) return CRASS_ERR_INVALID_ARG;
+    if (!n_ranks || n_ranks > 64 || fastq_class < 0 || fastq_class > 1) return CRASS_ERR_INVALID_ARG;
     crass_fastx_files_layout L;
-    const int s = crass_fastx_files_scan_host(bytes, n_bytes, n_files, &L);
+    const int s = crass_fastx_files_scan_host_class(bytes, n_bytes, n_files, fastq_class, &L);
     out->decline_file = L.decline_file; out->decline_reason = L.decline_reason; out->decline_pos = L.decline_pos; out->bgzf = L.bgzf;
     if (s) return s;
     // text space: file f is [tb[f], tb[f + 1]); arena positions count one byte more per file in front
@@ -243,6 +245,12 @@ int crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n
     out->rank_read_base = rb; out->cut_file = cf; out->cut_pos = cp; out->file_read_base = fb; out->format = fm;
     crass_fastx_files_layout_free(&L);
     return CRASS_OK;
+}
+
+int crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks, const uint64_t *nominal,
+                                  crass_fastx_shards *out)
+{
+    return crass_fastx_files_shards_host_class(bytes, n_bytes, n_files, n_ranks, nominal, crass::FX_CLASS_FOUR_LINE, out);
 }
 
 int crass_fastx_scan_host_class(const uint8_t *bytes, uint64_t n_bytes, int fastq_class, crass_fastx_layout *out)

@@ -115,6 +115,24 @@ static const uint64_t kFxNoOffence = ~0ull;
 // The ACTUAL cut c_g is the smallest record start at or after nominal cut g, or T: c_g <= c_{g+1}, a rank may be empty, rank g
 // owns [c_g, c_{g+1}) — a tail of one file, whole files, a head of one file, each slice beginning at a record start.
 //
+// CLASS 1 (crass_fastx_files_shards_host_class, crass_hip_group_set_fastq_class): the record starts of a file whose byte 0 is '@'
+// are the header-line positions of the records the wrapped rule above walks from line 0 (fastx_scan_class_serial's walk), and
+// nothing else: a quality line may start with '@' and the lines behind it may parse as a complete record, which is not one of the
+// file's.  FASTA files and files of another first byte keep the definition above, the actual cut stays "the smallest record
+// start at or after the nominal cut, or T", and the verdict is crass_fastx_files_scan_host_class(.., 1, ..)'s whatever the cuts.
+// So the cut cannot be made by looking near it.  Each rank builds, for its piece [a, b) of the file and a margin staged behind
+// it, every '@' line's successor under the rule and doubles the pointers to where the chain leaves the piece (k_fw_cut_*,
+// fastx_wrapped.hip); the host then walks the ranks in piece order: the entry e of the file's first piece is 0, a piece with
+// e >= b is passed through (a record longer than the range), else the terminal of e's chain is looked up:
+enum FwCutKind : uint32_t {
+    FW_CUT_PASS = 0,        // (a line on the way: never a look-up's answer)
+    FW_CUT_LANDED = 1,      // the chain's first record start at or beyond b, or the file's end: the piece's exit, the next one's entry
+    FW_CUT_OFFENCE = 2,     // a record of the chain offends: the file's verdict, nothing behind it in the file is cut
+    FW_CUT_UNRESOLVED = 3,  // a record's outcome depends on bytes beyond the staged end: the rank doubles its margin and builds again
+    FW_CUT_NONE = 4         // the position starts no header line of the piece (never expected)
+};
+// c_g is the first exit at or after nominal cut g; an exit at the file's end is the next file's 0, or T.
+//
 // What a probe of a byte range [a, b) of ONE file's text reports (k_fx_cut_probe, and fx_probe_serial on the host), positions
 // counted from a; kFxNone: there is none.  left_is_ls says whether position a is itself a line start (a == 0, or byte a - 1 is '\n').
 static const uint64_t kFxNone = ~0ull;

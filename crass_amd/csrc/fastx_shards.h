@@ -57,13 +57,24 @@ uint64_t shard_stage_place(const uint64_t *sa, const uint64_t *sb, uint64_t n, u
 //    BGZF file the members that overlap the range, inflated — and probes every piece.  A decline met here (a member that does
 //    not inflate, a BGZF text whose byte 0 is neither '>' nor '@') goes into *v with CRASS_OK: the pieces in front of that
 //    file are staged and probed all the same, the ones behind it are not.
+//    wrapped (the second attempt of a class-1 group, fastx_scan.h): a piece [a, b) of a file whose format is '@' is staged up to
+//    min(n_text, b + margin) and is not probed: its line table and its chain are built (k_fw_cut_*) and stay for shard_cut_exit.
 int shard_stage_probe(crass_hip_ctx *c, const crass::ShardFile *files, uint32_t n_files, crass::ShardPos lo, crass::ShardPos hi,
-                      std::vector<crass::ShardPiece> *pieces, crass::ShardVerdict *v);
+                      std::vector<crass::ShardPiece> *pieces, crass::ShardVerdict *v, bool wrapped = false, uint64_t margin = 0);
+// 1b. Between the barriers, on rank 0's thread while the rank's own waits: where the chain that enters the rank's wrapped-mode
+//    piece of the file at record start e (a <= e < b) leaves it.  *kind FW_CUT_LANDED: *pos is the first record start at or behind
+//    b, or n_text; FW_CUT_OFFENCE: *off is the offending record's word, in the file's positions.  A chain that is unresolved at
+//    the staged end has the piece staged again with twice the margin, as often as it takes (bounded by the file's size).
+int shard_cut_exit(crass_hip_ctx *c, const crass::ShardFile *files, uint32_t file, uint64_t e, uint32_t *kind, uint64_t *pos, uint64_t *off);
+// the look-ups and margin doublings of the rank since its last shard_stage_probe, and (timed contexts) its cut kernels' event time
+void shard_cut_counters(const crass_hip_ctx *c, uint64_t *lookups, uint64_t *doublings, float *ms);
 // 2. The actual range [lo, hi) as slices on the rank's arena (the staged bytes device to device, the tail behind them from the
-//    host or from further BGZF members), each followed by a '\n', scanned by the three scan kernels.  file_reads: (file, records)
+//    host or from further BGZF members), each followed by a '\n', scanned by the three scan kernels — with wrapped, a FASTQ
+//    slice that the four-line scan declines for its shape by the wrapped scan (launch_fw_*), as a single context's class 1.  file_reads: (file, records)
 //    per slice.  Declines go into *v with CRASS_OK; n_reads is then not to be used.
 int shard_scan(crass_hip_ctx *c, const crass::ShardFile *files, uint32_t n_files, crass::ShardPos lo, crass::ShardPos hi,
-               std::vector<std::pair<uint32_t, uint64_t>> *file_reads, uint64_t *n_reads, uint32_t *max_len, crass::ShardVerdict *v);
+               std::vector<std::pair<uint32_t, uint64_t>> *file_reads, uint64_t *n_reads, uint32_t *max_len, crass::ShardVerdict *v,
+               bool wrapped = false);
 // 3. One pack launch over the scanned text, the header ids and the name table on the arena; every scratch goes back.
 int shard_pack(crass_hip_ctx *c, int pad_uniform, uint64_t read_index_base);
 // ... or nothing: the scratch goes back, no reads, no arena

@@ -23,6 +23,7 @@
 //                   its bytes go
 //   k_fw_emit       the tile once more: a byte 33..126 of such a line is stored at text_base + seq_off + (the bytes 33..126 in
 //                   front of it - those in front of its record's first sequence line), a lane its own 16 bytes
+//   k_fw_cut_*      the cut of a group's files load: the same rule as a chain to where it leaves a piece (below)
 // No block waits for another; every array index is checked against n_lines, every store into the text against its range.
 // Scratch: 72 bytes per tile and about 90 per line (fw_scratch_words), the caller's.
 #include "fastx_vec.h"
@@ -114,7 +115,59 @@ static __device__ __forceinline__ uint32_t fw_first_rise(const uint64_t *X, uint
     return lo;
 }
 
-// one header candidate under the rule of fastx_scan.h, offences in the rule's order
+// one header candidate (line i, whose first byte is '@') under the rule of fastx_scan.h, offences in the rule's order.  open:
+// what came out depended on where the bytes END — no '+' line, a '+' line that is the last and may be cut, a quality count not
+// reached or reached in the last line, no line behind the quality that is not void.  At a file's end that is the rule's "end of
+// the input"; at the end of a staged piece it is not known yet (k_fw_cut_next)
+struct FwCand { uint32_t nxt, plus_of; uint64_t L, off; bool open; };
+static __device__ __forceinline__ FwCand fw_candidate(const FwJob &J, const uint32_t i)
+{
+    const uint32_t END = J.n_lines;
+    FwCand C{END, END, 0, kFxNoOffence, false};
+    const uint32_t n_plus = (uint32_t)(J.tot[1] < END ? J.tot[1] : END);
+    uint32_t lo = 0, hi = n_plus;                       // the first '+' line behind line i
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (J.plus[mid] > i) hi = mid; else lo = mid + 1u;
+    }
+    if (lo == n_plus) { C.off = fx_offence(J.pos[i], FX_LINE_COUNT); C.open = true; return C; }
+    const uint32_t j = C.plus_of = J.plus[lo];
+    const uint64_t L = C.L = J.G[j] - J.G[i + 1u];
+    const bool plus_ended = j + 1u < END || J.ends_nl;
+    bool short_q = !plus_ended;
+    uint32_t q = END;                                   // the first line behind the quality
+    if (plus_ended) {
+        if (J.G[END] - J.G[j + 1u] < L) short_q = true;
+        else {
+            uint32_t a = j + 1u, b = END;
+            while (a < b) {
+                const uint32_t mid = a + ((b - a) >> 1);
+                if (J.G[mid] - J.G[j + 1u] >= L) b = mid; else a = mid + 1u;
+            }
+            q = a;
+        }
+    }
+    C.open = short_q || q == END;
+    if (J.F[j] > J.F[i + 1u]) { C.off = fx_offence(J.pos[fw_first_rise(J.F, i + 1u, j)], FX_SEQ_CHAR); C.open = false; }
+    else if (L == 0 && j + 1u < END && J.first[j + 1u] == 0x40) { C.off = fx_offence(J.pos[j + 1u], FX_FQ_EMPTY_SEQ); C.open = false; }
+    else if (J.D[q] > J.D[j + 1u]) C.off = fx_offence(J.pos[fw_first_rise(J.D, j + 1u, q)], FX_QUAL_DEL);
+    else if (!short_q && J.G[q] - J.G[j + 1u] > L) C.off = fx_offence(J.pos[q - 1u], FX_QUAL_LONG);
+    else if (short_q) C.off = fx_offence(J.pos[i], FX_QUAL_SHORT);
+    else {
+        const uint64_t gd = J.G[q] + J.D[q];
+        if (J.G[END] + J.D[END] > gd) {                 // the first line at or behind q that is not void
+            uint32_t a = q, b = END - 1u;
+            while (a < b) {
+                const uint32_t mid = a + ((b - a) >> 1);
+                if (J.G[mid + 1u] + J.D[mid + 1u] > gd) b = mid; else a = mid + 1u;
+            }
+            if (J.first[a] == 0x40) C.nxt = a; else C.off = fx_offence(J.pos[a], FX_FQ_HEADER);
+        } else C.open = true;
+    }
+    return C;
+}
+
+// A candidate that offends points at END, as every other line does.
 __global__ __launch_bounds__(kFxThreads) void k_fw_next(const FwJob J)
 {
     const uint64_t i64 = (uint64_t)blockIdx.x * kFxThreads + threadIdx.x;
@@ -122,52 +175,9 @@ __global__ __launch_bounds__(kFxThreads) void k_fw_next(const FwJob J)
     if (i64 > END) return;
     const uint32_t i = (uint32_t)i64;
     if (i == END) { J.nxt[0][END] = END; J.mark[END] = 0u; return; }
-    uint32_t nxt = END, plus_of = END;
-    uint64_t L = 0, off = kFxNoOffence;
-    if (J.first[i] == 0x40) {
-        const uint32_t n_plus = (uint32_t)(J.tot[1] < END ? J.tot[1] : END);
-        uint32_t lo = 0, hi = n_plus;                   // the first '+' line behind line i
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (J.plus[mid] > i) hi = mid; else lo = mid + 1u;
-        }
-        if (lo == n_plus) off = fx_offence(J.pos[i], FX_LINE_COUNT);
-        else {
-            const uint32_t j = plus_of = J.plus[lo];
-            L = J.G[j] - J.G[i + 1u];
-            const bool plus_ended = j + 1u < END || J.ends_nl;
-            bool short_q = !plus_ended;
-            uint32_t q = END;                           // the first line behind the quality
-            if (plus_ended) {
-                if (J.G[END] - J.G[j + 1u] < L) short_q = true;
-                else {
-                    uint32_t a = j + 1u, b = END;
-                    while (a < b) {
-                        const uint32_t mid = a + ((b - a) >> 1);
-                        if (J.G[mid] - J.G[j + 1u] >= L) b = mid; else a = mid + 1u;
-                    }
-                    q = a;
-                }
-            }
-            if (J.F[j] > J.F[i + 1u]) off = fx_offence(J.pos[fw_first_rise(J.F, i + 1u, j)], FX_SEQ_CHAR);
-            else if (L == 0 && j + 1u < END && J.first[j + 1u] == 0x40) off = fx_offence(J.pos[j + 1u], FX_FQ_EMPTY_SEQ);
-            else if (J.D[q] > J.D[j + 1u]) off = fx_offence(J.pos[fw_first_rise(J.D, j + 1u, q)], FX_QUAL_DEL);
-            else if (!short_q && J.G[q] - J.G[j + 1u] > L) off = fx_offence(J.pos[q - 1u], FX_QUAL_LONG);
-            else if (short_q) off = fx_offence(J.pos[i], FX_QUAL_SHORT);
-            else {
-                const uint64_t gd = J.G[q] + J.D[q];
-                if (J.G[END] + J.D[END] > gd) {         // the first line at or behind q that is not void
-                    uint32_t a = q, b = END - 1u;
-                    while (a < b) {
-                        const uint32_t mid = a + ((b - a) >> 1);
-                        if (J.G[mid + 1u] + J.D[mid + 1u] > gd) b = mid; else a = mid + 1u;
-                    }
-                    if (J.first[a] == 0x40) nxt = a; else off = fx_offence(J.pos[a], FX_FQ_HEADER);
-                }
-            }
-        }
-    }
-    J.nxt[0][i] = nxt; J.plus_of[i] = plus_of; J.seqlen[i] = off == kFxNoOffence ? L : 0; J.off[i] = off;
+    FwCand C{END, END, 0, kFxNoOffence, false};
+    if (J.first[i] == 0x40) C = fw_candidate(J, i);
+    J.nxt[0][i] = C.nxt; J.plus_of[i] = C.plus_of; J.seqlen[i] = C.off == kFxNoOffence ? C.L : 0; J.off[i] = C.off;
     J.mark[i] = i == 0 ? 1u : 0u;
 }
 
@@ -181,6 +191,63 @@ __global__ __launch_bounds__(kFxThreads) void k_fw_jump(const FwJob J, const uin
     if (a > J.n_lines) a = J.n_lines;
     if (i < J.n_lines && J.mark[i]) J.mark[a] = 1u;     // (END's mark is nobody's)
     out[i] = in[a];
+}
+
+// ---- the cut of a group's files load (fastx_scan.h: the record starts of a wrapped file are the ones reachable from line 0) ----
+// The job is a PIECE [a, b) of a file and a margin behind it, positions counted from a; K.b: where the piece ends.
+//   k_fw_cut_next    k_fw_next's rule per candidate, as a chain to where it leaves the piece.  TERMINALS point at themselves: a
+//                    line at or beyond K.b (LANDED; so is END, reached only at the file's end: "no further record" lands on n),
+//                    a candidate whose outcome is open while the staged bytes are not the file's last (UNRESOLVED), a candidate
+//                    that offends (OFFENCE, with its word), and what is no candidate — the fragment in front of the piece's
+//                    first line start, a line of another first byte (NONE: nobody arrives there)
+//   k_fw_cut_jump    k_fw_jump without marks: out[i] = in[in[i]], terminals are fixed points; after ceil(log2(lines)) + 1
+//                    rounds every line holds its terminal
+//   k_fw_cut_lookup  one text position: its line by bisection in pos[], that line's terminal: kind, position, offence word
+__global__ __launch_bounds__(kFxThreads) void k_fw_cut_next(const FwJob J, const FwCut K)
+{
+    const uint64_t i64 = (uint64_t)blockIdx.x * kFxThreads + threadIdx.x;
+    const uint32_t END = J.n_lines;
+    if (i64 > END) return;
+    const uint32_t i = (uint32_t)i64;
+    uint32_t nxt = i, kind = FW_CUT_NONE;
+    uint64_t off = kFxNoOffence;
+    if (i == END || J.pos[i] >= K.b) kind = FW_CUT_LANDED;
+    else if (i >= K.first_cand && J.first[i] == 0x40) {
+        const FwCand C = fw_candidate(J, i);
+        if (C.open && !K.at_eof) kind = FW_CUT_UNRESOLVED;
+        else if (C.off != kFxNoOffence) { kind = FW_CUT_OFFENCE; off = C.off; }
+        else { kind = FW_CUT_PASS; nxt = C.nxt; }
+    }
+    J.nxt[0][i] = nxt; J.mark[i] = kind; J.off[i] = off;
+}
+
+__global__ __launch_bounds__(kFxThreads) void k_fw_cut_jump(const FwJob J, const uint32_t round)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kFxThreads + threadIdx.x;
+    if (i > J.n_lines) return;
+    const uint32_t *in = J.nxt[round & 1u];
+    uint32_t a = in[i];
+    if (a > J.n_lines) a = J.n_lines;
+    uint32_t t = in[a];
+    if (t > J.n_lines) t = J.n_lines;
+    J.nxt[(round & 1u) ^ 1u][i] = t;
+}
+
+__global__ __launch_bounds__(64) void k_fw_cut_lookup(const FwJob J, const uint32_t which, const uint64_t p, uint64_t *out)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    uint32_t lo = 0, hi = J.n_lines;                    // the first line at or behind p
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (J.pos[mid] >= p) hi = mid; else lo = mid + 1u;
+    }
+    uint64_t kind = FW_CUT_NONE, at = kFxNone, off = kFxNoOffence;
+    if (lo < J.n_lines && J.pos[lo] == p) {
+        uint32_t t = J.nxt[which & 1u][lo];
+        if (t > J.n_lines) t = J.n_lines;
+        kind = J.mark[t]; at = J.pos[t]; off = J.off[t];
+    }
+    out[0] = kind; out[1] = at; out[2] = off;
 }
 
 static constexpr int kFwWaves = kFxThreads / 64;
@@ -327,6 +394,26 @@ hipError_t launch_fw_analyse(const FwJob &J, hipStream_t st)
     CRASS_LAUNCH(k_fw_rank_tiles, dim3((unsigned)rank_tiles), dim3(kFxThreads), 0, st, J);
     CRASS_LAUNCH(k_fw_rank_top, dim3(1), dim3(kFxThreads), 0, st, J, rank_tiles);
     CRASS_LAUNCH(k_fw_rank_apply, dim3((unsigned)rank_tiles), dim3(kFxThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_fw_cut(const FwJob &J, const FwCut &K, hipStream_t st, uint32_t *which)
+{
+    if (!J.n_lines || J.n_lines == 0xFFFFFFFFu || !J.n_tiles || J.n_tiles > 0x7FFFFFFFull || !which) return hipErrorInvalidValue;
+    const unsigned line_blocks = (unsigned)(((uint64_t)J.n_lines + 1 + kFxThreads - 1) / kFxThreads);
+    CRASS_LAUNCH(k_fw_lines, dim3((unsigned)J.n_tiles), dim3(kFxThreads), 0, st, J);
+    CRASS_LAUNCH(k_fw_cut_next, dim3(line_blocks), dim3(kFxThreads), 0, st, J, K);
+    uint32_t rounds = 1;                                // ceil(log2(lines)) + 1, as launch_fw_analyse's
+    while (rounds <= 32 && (1ull << (rounds - 1)) < J.n_lines) rounds++;
+    for (uint32_t k = 0; k < rounds; k++) CRASS_LAUNCH(k_fw_cut_jump, dim3(line_blocks), dim3(kFxThreads), 0, st, J, k);
+    *which = rounds & 1u;                               // (round k writes nxt[(k & 1) ^ 1])
+    return hipGetLastError();
+}
+
+hipError_t launch_fw_cut_lookup(const FwJob &J, uint32_t which, uint64_t p, uint64_t *d_out, hipStream_t st)
+{
+    if (!J.n_lines || !d_out) return hipErrorInvalidValue;
+    CRASS_LAUNCH(k_fw_cut_lookup, dim3(1), dim3(64), 0, st, J, which, p, d_out);
     return hipGetLastError();
 }
 

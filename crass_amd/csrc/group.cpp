@@ -207,7 +207,17 @@ struct crass_hip_group {
         std::vector<uint32_t> max_len;
         crass::ShardVerdict pend, verdict;      // the decline that waits for the files in front of it; the job's
         bool declined = false;
+        // class 1 (crass_hip_group_set_fastq_class): the attempts the load takes — rank 0 decides on the second between two
+        // barriers —, the pend the host left before the first, whether this attempt cuts and scans every '@' file by the wrapped
+        // rule, and how many files the chain cut
+        int attempts = 1;
+        crass::ShardVerdict pend0;
+        bool wrapped_pass = false;
+        uint64_t n_chained = 0;
     } F;
+    int fastq_class = 0;                        // crass_hip_group_set_fastq_class, CRASS_DEVICE_FASTQ at creation
+    uint64_t shard_margin = 256u << 10;         // what a wrapped-mode piece stages behind its end at first (CRASS_SHARD_MARGIN at creation)
+    uint64_t load_cnt[4] = {0, 0, 0, 0};        // crass_hip_group_load_counters
     struct { std::vector<uint64_t> cut_pos, file_read_base; std::vector<uint32_t> cut_file; std::vector<int32_t> format; } S;      // crass_fastx_shards' arrays
     // the names of every rank's pass-1 records, for the other ranks to look up (found headers across ranks)
     std::vector<Text> names;
@@ -335,12 +345,48 @@ int combine_cuts(crass_hip_group *g)
     for (int r = 0; r < N; r++) if (crass::shard_verdict_before(J.v_stage[r], J.pend)) J.pend = J.v_stage[r];
     J.nf_eff = J.pend.file >= 0 ? (uint32_t)J.pend.file : J.nf;
     for (int r = 0; r < N; r++) for (const crass::ShardPiece &pc : J.pieces[r]) if (pc.a == 0 && J.files[pc.file].ix) J.files[pc.file].format = pc.first_byte;
+    // the wrapped pass: every '@' file's chain over the ranks, in piece order.  A piece is entered at e, the exit of the one before
+    // (0 for the file's first); a record longer than the piece passes through it.  exits[f]: the pieces' exits, not decreasing
+    std::vector<std::vector<uint64_t>> exits(J.nf_eff);
+    J.n_chained = 0;
+    for (uint32_t f = 0; J.wrapped_pass && f < J.nf_eff; f++) {
+        if (J.files[f].format != 0x40) continue;
+        J.n_chained++;
+        uint64_t e = 0;
+        bool offended = false;
+        for (int r = 0; r < N && !offended; r++) for (const crass::ShardPiece &pc : J.pieces[r]) {
+            if (pc.file != f) continue;
+            if (e < pc.b) {
+                uint32_t kind = 0; uint64_t pos = 0, off = 0;
+                const int s = shard_cut_exit(g->ctx[r], J.files.data(), f, e, &kind, &pos, &off);
+                if (s) return s;
+                if (kind == crass::FW_CUT_OFFENCE) {    // the file's verdict: nothing behind it in this file is cut
+                    crass::ShardVerdict sv;
+                    sv.file = (int32_t)f; sv.reason = (int32_t)(off & 0xFF); sv.pos = off >> 8;
+                    if (crass::shard_verdict_before(sv, J.pend)) J.pend = sv;
+                    offended = true;
+                    break;
+                }
+                e = pos;
+            }
+            exits[f].push_back(e);
+        }
+        if (offended) break;                            // (the files behind it are out of the set)
+    }
+    J.nf_eff = J.pend.file >= 0 ? (uint32_t)J.pend.file : J.nf;
     const uint32_t nf = J.nf_eff;
     J.cut.assign(N + 1, crass::ShardPos{nf, 0});
     J.cut[0] = crass::ShardPos{0, 0};
     for (int k = N - 1; k >= 1; k--) {
         const crass::ShardPos x = locate(J.tb, nf, J.nom_x[k]);
         if (x.file >= nf || x.pos == 0) { J.cut[k] = x; continue; }
+        if (J.wrapped_pass && J.files[x.file].format == 0x40) {      // the first exit at or after the nominal cut; the file's end: the next file's 0
+            const std::vector<uint64_t> &ex = exits[x.file];
+            const auto it = std::lower_bound(ex.begin(), ex.end(), x.pos);
+            if (it == ex.end()) return CRASS_ERR_STATE;
+            J.cut[k] = *it < J.files[x.file].n_text ? crass::ShardPos{x.file, *it} : crass::ShardPos{x.file + 1, 0};
+            continue;
+        }
         J.cut[k] = J.cut[k + 1];
         if (J.pieces[k].empty()) continue;              // (an empty nominal range: the next rank's cut)
         const crass::ShardPiece &pc = J.pieces[k][0];
@@ -369,19 +415,37 @@ void finish_scan(crass_hip_group *g)
     if (!g->cap_rows_forced) g->cap_rows = crass_hip_exchange_rows_for(largest);
 }
 
+// rank 0, behind finish_scan of a class-1 group's first attempt: a file whose format is '@', declined for its shape, is what
+// the wrapped rule takes up — the load runs once more with every '@' file cut and scanned by that rule.  Any other decline is final
+void decide_second_attempt(crass_hip_group *g)
+{
+    auto &J = g->F;
+    if (g->fastq_class != crass::FX_CLASS_WRAPPED || !J.declined || J.verdict.bgzf.reason != 0) return;
+    if (J.files[J.verdict.file].format != 0x40 || !crass::fx_wrapped_takes(J.verdict.reason)) return;
+    J.attempts = 2; J.wrapped_pass = true;
+    J.pend = J.pend0; J.verdict = crass::ShardVerdict(); J.declined = false;
+}
+
 void load_files_rank(crass_hip_group *g, int r)
 {
     auto &J = g->F;
     crass_hip_ctx *c = g->ctx[r];
     auto ok = [&] { return g->failed.load(std::memory_order_acquire) == 0; };
-    note(g, r, shard_stage_probe(c, J.files.data(), J.nf, J.nom[r], J.nom[r + 1], &J.pieces[r], &J.v_stage[r]));
-    g->bar->wait();                                     // every rank's probes are there
-    if (r == 0 && ok()) { try { note(g, 0, combine_cuts(g)); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
-    g->bar->wait();                                     // the actual cuts are known
-    if (ok()) note(g, r, shard_scan(c, J.files.data(), J.nf_eff, J.cut[r], J.cut[r + 1], &J.file_reads[r], &J.n_reads[r], &J.max_len[r], &J.v_scan[r]));
-    g->bar->wait();                                     // every rank's records are counted
-    if (r == 0 && ok()) { try { finish_scan(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
-    g->bar->wait();                                     // the verdict, or every rank's first read
+    for (int attempt = 1;; attempt++) {                 // (at most two: the second is decided once, behind the first)
+        const bool w = attempt == 2;                    // (J.wrapped_pass, as every rank knows it)
+        if (ok()) note(g, r, shard_stage_probe(c, J.files.data(), J.nf, J.nom[r], J.nom[r + 1], &J.pieces[r], &J.v_stage[r], w, g->shard_margin));
+        g->bar->wait();                                 // every rank's probes (chains) are there
+        if (r == 0 && ok()) { try { note(g, 0, combine_cuts(g)); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+        g->bar->wait();                                 // the actual cuts are known
+        if (ok()) note(g, r, shard_scan(c, J.files.data(), J.nf_eff, J.cut[r], J.cut[r + 1], &J.file_reads[r], &J.n_reads[r], &J.max_len[r], &J.v_scan[r], w));
+        g->bar->wait();                                 // every rank's records are counted
+        if (r == 0 && ok()) {
+            try { finish_scan(g); if (attempt == 1) decide_second_attempt(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); }
+        }
+        g->bar->wait();                                 // the verdict, or every rank's first read — or one more attempt
+        if (J.attempts <= attempt) break;
+        shard_abort(c);
+    }
     if (ok() && !J.declined) {
         int s = shard_pack(c, J.pad_uniform, J.rank_base[r]);
         if (!s) s = setup_exchange(g, r);
@@ -675,11 +739,14 @@ int crass_hip_group_create(const crass_params *p, const int *devices, int n, uns
     g->extra.resize(n); g->extra_user.resize(n); g->dup_local.resize(n); g->nx.resize(n);
     if (const char *e = getenv("CRASS_GROUP_NAMES")) g->names_on_device = strcmp(e, "device") == 0;      // (crass_hip_group_set_name_exchange)
     g->names_timed = getenv("CRASS_GROUP_NAMES_TIMING") != nullptr;
+    if (const char *e = getenv("CRASS_DEVICE_FASTQ")) g->fastq_class = strcmp(e, "wrapped") == 0 ? 1 : 0;      // (crass_hip_group_set_fastq_class)
+    if (const char *e = getenv("CRASS_SHARD_MARGIN")) g->shard_margin = std::max<uint64_t>(1, strtoull(e, nullptr, 10));      // (tests: a tiny margin forces the doublings)
     if (const char *e = getenv("CRASS_GROUP_CAP_ROWS")) { g->cap_rows = (uint64_t)std::max(1, atoi(e)); g->cap_rows_forced = true; }      // (tests: force the overflow path)
     for (int r = 0; r < n; r++) {
         const int s = crass_hip_create(p, devices[r], &g->ctx[r]);
         if (s) { crass_hip_group_destroy(g); return s; }
         if (r > 0) (void)crass_hip_set_host_view(g->ctx[r], 1);       // ONE host view for the group: rank 0's
+        (void)crass_hip_set_fastq_class(g->ctx[r], g->fastq_class);
     }
     if (!local) {
         g->comms.assign(n, nullptr);
@@ -723,6 +790,21 @@ int crass_hip_group_set_name_exchange(crass_hip_group *g, int on_device)
 {
     if (!g) return CRASS_ERR_INVALID_ARG;
     g->names_on_device = on_device != 0;
+    return CRASS_OK;
+}
+
+int crass_hip_group_set_fastq_class(crass_hip_group *g, int fastq_class)
+{
+    if (!g || fastq_class < 0 || fastq_class > 1) return CRASS_ERR_INVALID_ARG;
+    for (crass_hip_ctx *c : g->ctx) { const int s = crass_hip_set_fastq_class(c, fastq_class); if (s) return s; }      // (fetch_quality reads by the context's class)
+    g->fastq_class = fastq_class;
+    return CRASS_OK;
+}
+
+int crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4])
+{
+    if (!g || !out) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 4; k++) out[k] = g->load_cnt[k];
     return CRASS_OK;
 }
 
@@ -1025,7 +1107,15 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
         J.pieces.assign(N, {}); J.v_stage.assign(N, crass::ShardVerdict()); J.v_scan.assign(N, crass::ShardVerdict());
         J.file_reads.assign(N, {}); J.n_reads.assign(N, 0); J.max_len.assign(N, 0);
         J.cut.assign(N + 1, crass::ShardPos{nf, 0});
+        J.pend0 = J.pend;
+        for (uint64_t &x : g->load_cnt) x = 0;
         st = dispatch(g, PH_LOAD_FILES);
+        g->load_cnt[0] = (uint64_t)J.attempts; g->load_cnt[1] = J.wrapped_pass ? J.n_chained : 0;
+        for (int r = 0; J.wrapped_pass && r < N; r++) {
+            uint64_t lk = 0, db = 0;
+            shard_cut_counters(g->ctx[r], &lk, &db, nullptr);
+            g->load_cnt[2] += db; g->load_cnt[3] += lk;
+        }
         for (auto &F : J.files) { F.ix = nullptr; F.bytes = nullptr; }      // (the caller's bytes and this call's indexes: used inside this call only)
         if (st) return st;
         if (J.declined) {

@@ -46,7 +46,8 @@ struct ScanResult {
 //   emit   the totals of the n_kept first pieces back, every one of them emits into one text and one pair of per-record
 //          arrays, tm_scan's second mark, the verdict: the first piece in order that offends.  max_reads: a set of that many
 //          records or more is CRASS_ERR_UNSUPPORTED (the files' name table holds 32-bit indices)
-//   wrapped  set between open and emit by the callers that honour crass_hip_set_fastq_class (a shard's slices never do): emit
+//   wrapped  set between open and emit by the callers that honour crass_hip_set_fastq_class (a shard's slices: in the wrapped
+//          pass of a class-1 group only): emit
 //          hands the FASTQ pieces the four-line scan declined for their shape to emit_wrapped, whose verdict is theirs
 struct ArenaScan {
     const uint8_t *arena = nullptr; const uint64_t *base = nullptr;

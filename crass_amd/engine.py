@@ -505,19 +505,20 @@ def _nominal_arg(nominal, n_ranks):
     return a
 
 
-def fastx_files_shards_host(files, n_ranks, nominal=None):
-    """Several files' bytes cut into n_ranks record-aligned shards on the host (crass_fastx_files_shards_host; no GPU needed):
-    a FastxShards, accepted or declined — what SearchGroup.load_fastx_files is tested against.  nominal: n_ranks - 1
-    non-decreasing positions in the job's text space (None: even cuts)."""
+def fastx_files_shards_host(files, n_ranks, nominal=None, fastq_class=0):
+    """Several files' bytes cut into n_ranks record-aligned shards on the host (crass_fastx_files_shards_host_class; no GPU
+    needed): a FastxShards, accepted or declined — what SearchGroup.load_fastx_files is tested against.  nominal: n_ranks - 1
+    non-decreasing positions in the job's text space (None: even cuts).  fastq_class 1: a FASTQ file's record starts are those
+    of the records the wrapped rule walks from line 0 (SearchGroup.set_fastq_class)."""
     lib = _abi.load()
     arrs, ptrs, lens = _files_args(files)
     nom = _nominal_arg(nominal, int(n_ranks))
     v = _abi.FastxShardsC()
-    st = lib.crass_fastx_files_shards_host(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(n_ranks),
-                                           nom.ctypes.data if nom is not None and len(nom) else None, C.byref(v))
+    st = lib.crass_fastx_files_shards_host_class(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(n_ranks),
+                                                 nom.ctypes.data if nom is not None and len(nom) else None, int(fastq_class), C.byref(v))
     try:
         if st not in (0, 2):
-            raise CrassError(st, "crass_fastx_files_shards_host")
+            raise CrassError(st, "crass_fastx_files_shards_host_class")
         return FastxShards(v)
     finally:
         lib.crass_fastx_shards_free(C.byref(v))
@@ -1234,6 +1235,11 @@ class SearchEngine:
     def last_cut_probe_ms(self):
         return float(self.lib.crass_hip_last_cut_probe_ms(self.h))
 
+    def last_cut_chain_ms(self):
+        """HIP-event ms of the cut kernels (k_fw_summary .. k_fw_cut_jump) of this context's part of a group's last wrapped-mode
+        files load (crass_hip_last_cut_chain_ms); measured at stage timing level >= 1, else 0."""
+        return float(self.lib.crass_hip_last_cut_chain_ms(self.h))
+
     def resident_fastx(self):
         """(device address, n_bytes) of the arena of the last load_fastx_files (crass_hip_resident_fastx); CrassError with
         status CRASS_ERR_STATE when the last load was not one.  The address goes where fetch_quality takes `src`; for
@@ -1854,6 +1860,20 @@ class SearchGroup:
         t = Text(v)
         return t.chars.copy(), t.off.copy(), has
 
+    def set_fastq_class(self, fastq_class):
+        """The class load_fastx_files reads FASTQ by (crass_hip_group_set_fastq_class; CRASS_DEVICE_FASTQ=wrapped at creation does
+        the same): 0, the default, the four-line form only; 1 also records over several lines and blank lines — a load that the
+        four-line cut declines for a FASTQ's shape runs once more with every FASTQ file cut at the records reachable from its
+        line 0.  Also set on every rank's context, so fetch_quality reads by the wrapped rule."""
+        self._chk(self.lib.crass_hip_group_set_fastq_class(self.h, int(fastq_class)), "crass_hip_group_set_fastq_class")
+
+    def load_counters(self):
+        """(attempts, files cut by the wrapped rule, margin doublings, chain look-ups) of the last load_fastx_files
+        (crass_hip_group_load_counters)."""
+        out = np.zeros(4, np.uint64)
+        self._chk(self.lib.crass_hip_group_load_counters(self.h, out.ctypes.data), "crass_hip_group_load_counters")
+        return tuple(int(x) for x in out)
+
     def set_name_exchange(self, on_device):
         """The route of the found-name exchange of a files load: False the host's (the default), True everything in device memory
         (crass_hip_group_set_name_exchange; CRASS_GROUP_NAMES=device at creation does the same)."""
@@ -1877,6 +1897,16 @@ class SearchGroup:
         c = _abi.Counters()
         _chk(self.lib.crass_hip_get_counters(C.c_void_p(self.lib.crass_hip_group_ctx(self.h, int(rank))), C.byref(c)), "crass_hip_get_counters")
         return c.asdict()
+
+    def rank_last_scan_classes(self, rank):
+        """(pieces the four-line scan decided, pieces the wrapped scan decided) of a rank's last load (crass_hip_last_scan_classes)"""
+        out = (C.c_uint64 * 2)()
+        _chk(self.lib.crass_hip_last_scan_classes(C.c_void_p(self.lib.crass_hip_group_ctx(self.h, int(rank))), out), "crass_hip_last_scan_classes")
+        return int(out[0]), int(out[1])
+
+    def rank_last_cut_chain_ms(self, rank):
+        """HIP-event ms of a rank's cut kernels in the last wrapped-mode load_fastx_files (crass_hip_last_cut_chain_ms; stage timing >= 1)"""
+        return float(self.lib.crass_hip_last_cut_chain_ms(C.c_void_p(self.lib.crass_hip_group_ctx(self.h, int(rank)))))
 
     def rank_set_stage_timing(self, rank, level):
         _chk(self.lib.crass_hip_set_stage_timing(C.c_void_p(self.lib.crass_hip_group_ctx(self.h, int(rank))), int(level)), "crass_hip_set_stage_timing")

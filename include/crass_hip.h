@@ -600,8 +600,8 @@ int  crass_fastx_scan_host_class(const uint8_t *bytes, uint64_t n_bytes, int fas
  * crass_hip_load_fastx_bgzf / _gzip / _gzip_members and crass_hip_load_fastx_files.  0 (the default): every call as before.  1: a
  * FASTQ piece is scanned by four lines first; where that scan declines it for its shape (reasons 3 .. 9), the wrapped scan
  * (fastx_wrapped.hip) reads the piece again and its verdict is the call's: exactly crass_fastx_scan_host_class(.., 1, ..).  The
- * group load (crass_hip_group_load_fastx_files) ignores the switch and declines as before: a wrapped file has no cut rule by
- * lines modulo 4.  With class 1 set, crass_hip_fetch_quality_device(_to) reads a record's quality by the wrapped rule (k_qw_measure):
+ * group load (crass_hip_group_load_fastx_files) has a switch of its own, crass_hip_group_set_fastq_class, which sets this one on
+ * every rank's context.  With class 1 set, crass_hip_fetch_quality_device(_to) reads a record's quality by the wrapped rule (k_qw_measure):
  * behind the '+' line as many bytes 33..126 as the record has sequence bytes, over however many lines — on a four-line record
  * the same answer as with class 0.  Header lines, names, header ids and comments need the record positions alone.
  * crass_hip_last_scan_ms stays the four-line scan's kernels; the wrapped scan's are not in it.
@@ -1026,6 +1026,13 @@ typedef struct {
 int  crass_fastx_files_shards_host(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
                                    const uint64_t *nominal, crass_fastx_shards *out);
 void crass_fastx_shards_free(crass_fastx_shards *s);
+/* the same for a FASTQ class (crass_hip_group_set_fastq_class).  0 is crass_fastx_files_shards_host, byte for byte.  1: the record
+ * starts of a file whose byte 0 is '@' are the header-line positions of the records the wrapped rule walks from line 0
+ * (crass_fastx_scan_host_class(.., 1, ..)) — a quality line that starts with '@' is none, whatever follows it; FASTA files keep
+ * their definition; the verdict is crass_fastx_files_scan_host_class(.., 1, ..)'s, field for field, whatever the cuts.
+ * CRASS_ERR_INVALID_ARG also for a class outside 0..1. */
+int  crass_fastx_files_shards_host_class(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
+                                         const uint64_t *nominal, int fastq_class, crass_fastx_shards *out);
 /* what a rank knows about a byte range of one file's text before the cuts are known (the probe of csrc/fastx_scan.h), serially
  * on the host and by k_fx_cut_probe on bytes in HBM (d_bytes: a DEVICE pointer of any alignment; one aligned 16-byte load per 16
  * bytes, nothing outside the vectors that cover the range is read).  left_is_ls: position 0 of the range is a line start.
@@ -1037,6 +1044,9 @@ int  crass_hip_fastx_cut_probe_device(crass_hip_ctx *ctx, const uint8_t *d_bytes
 /* HIP-event time, in milliseconds on the context's stream, of the last k_fx_cut_probe launch of that call; measured when the
  * stage timing level is >= 1, else 0. */
 float crass_hip_last_cut_probe_ms(const crass_hip_ctx *ctx);
+/* the same for the cut kernels of a wrapped-mode load of a group (k_fw_summary .. k_fw_cut_jump over the rank's pieces, every
+ * rebuild after a margin doubling included), summed over the context's part of the last crass_hip_group_load_fastx_files */
+float crass_hip_last_cut_chain_ms(const crass_hip_ctx *ctx);
 /* the device call: every rank of the group parses its own shard of the files beside the others (the rank threads of
  * crass_hip_group_load_reads).  Each rank stages the bytes of its NOMINAL range (plain bytes from the caller's memory; of a BGZF
  * file the members that overlap the range, inflated by k_bgzf_inflate), probes them with k_fx_cut_probe, the host combines the
@@ -1052,10 +1062,30 @@ float crass_hip_last_cut_probe_ms(const crass_hip_ctx *ctx);
  *   in its own table, and its namesakes are marked found before pass 2 (readsFound, libcrispr.cpp:138,411).
  * declined (CRASS_ERR_UNSUPPORTED): the verdict of crass_fastx_files_shards_host in out; no rank holds reads, and the group is as
  *   after a failed load (step: CRASS_ERR_STATE).  Plain gzip is declined (one deflate stream cannot be cut).
+ * FASTQ class 1 (crass_hip_group_set_fastq_class; default 0: everything above, unchanged): the load takes at most two attempts.
+ *   Attempt 1 is the load above; accepted, it is the load (a four-line job takes the same kernels as with class 0).  Attempt 2
+ *   runs only when attempt 1 declines a file whose format is '@' with one of the reasons 3 .. 9: every '@' file is then cut and
+ *   scanned by the wrapped rule.  A rank stages its piece [a, b) of such a file with a margin behind it (256 KiB;
+ *   CRASS_SHARD_MARGIN=<bytes> at group creation), builds the piece's line table (k_fw_summary / k_fw_tile_scan / k_fw_lines),
+ *   every '@' line's successor up to where the chain leaves the piece (k_fw_cut_next) and doubles the pointers (k_fw_cut_jump);
+ *   the host walks the ranks in piece order with one k_fw_cut_lookup per piece, a rank whose chain is unresolved at its staged
+ *   end doubles its margin and builds again; the slices go through the wrapped scan as a single context's class 1 does.
+ *   exact: out equals crass_fastx_files_shards_host_class(.., 1, ..)'s, accepted or declined, and the reads, header lines,
+ *   quality and comments are those of crass_hip_load_fastx_files with class 1 on the same files.
+ *   Line indices of a piece are 32-bit: a piece of more lines is CRASS_ERR_UNSUPPORTED.  Plain gzip stays declined, and
+ *   crass_hip_set_gzip_on_device has no counterpart in a group.
  * Other errors: CRASS_ERR_INVALID_ARG — a NULL group, n_files == 0, NULL arrays, a NULL bytes[f] with n_bytes[f] > 0, pad_uniform
  * outside 0..2, nominal cuts that decrease or lie beyond T; CRASS_ERR_HIP / CRASS_ERR_OOM from a rank. */
 int  crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files,
                                       int pad_uniform, const uint64_t *nominal, crass_fastx_shards *out);
+/* the class the group's files load reads FASTQ by; also set on every rank's context (crass_hip_set_fastq_class), so
+ * crass_hip_group_fetch_quality reads quality by the wrapped rule.  CRASS_DEVICE_FASTQ=wrapped|four-line at group creation does
+ * the same.  CRASS_ERR_INVALID_ARG: a NULL group, a class outside 0..1. */
+int  crass_hip_group_set_fastq_class(crass_hip_group *g, int fastq_class);
+/* the last crass_hip_group_load_fastx_files: out[0] its attempts (1 or 2; 0: the call failed before the ranks ran), out[1] the
+ * files cut by the wrapped rule (the '@' files in front of the first declined file, in attempt 2), out[2] margin doublings and
+ * out[3] chain look-ups, both summed over the ranks. */
+int  crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4]);
 /* replaces: ReadHolder's RH_Header / RH_Comment and RH_Qual / RH_IsFasta for a group loaded by crass_hip_group_load_fastx_files:
  * crass_hip_fetch_header_lines_device / crass_hip_fetch_quality_device on every rank's arena, over the whole job.  read_idx are
  * GLOBAL read indices (0 .. n_reads), routed to the rank that holds them; the records come back in the caller's order in one

@@ -74,3 +74,8 @@ echo "comments of: $(tail -1 $out/report_comments_of.txt); $(grep -c 'ERROR: Add
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/wrapped_scan_main.cpp -o $out/wrapped_scan_asan -lz
 $out/wrapped_scan_asan > $out/report_wrapped.txt 2> $out/sanitizer_wrapped.txt || true
 echo "wrapped scan: $(tail -1 $out/report_wrapped.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_wrapped.txt || true) sanitizer reports"
+# the cut rule of a FASTQ class on the host (crass_fastx_files_shards_host_class) over the designed jobs of tests/shard_wrapped_sets.py, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/fastx_scan.cpp crass_amd/csrc/bgzf.cpp tools/sanitize/shards_class_main.cpp -o $out/shards_class_asan
+python3 tools/sanitize/shards_class_dump.py $out/shards_class > /dev/null
+$out/shards_class_asan $out/shards_class/* > $out/report_shards_class.txt 2> $out/sanitizer_shards_class.txt || true
+echo "shards by class: $(tail -1 $out/report_shards_class.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_shards_class.txt || true) sanitizer reports"
