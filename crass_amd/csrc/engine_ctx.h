@@ -228,6 +228,21 @@ struct Ingest {
     DevBuf<uint64_t> gz_ends;                // members mode: the GzEnd records (3 words each)
     StageTimer<6> tm_gzip;                   // marks around find, count (count step: 0 1 2), decode, windows, narrow (decode step: 2 .. 5)
     float last_gzip_ms[5] = {0, 0, 0, 0, 0};  // find, count, decode, windows, narrow of the last gzip inflate (stage timing >= 1, else 0)
+    // a rank's part of crass_hip_group_inflate_gzip (gzip_rank_*, engine_inflate.cpp): the symbolic windows, the deflate bytes
+    // [gzr_lo, gzr_hi) that z_raw holds, a pair of marks per step and their times (find, count, decode, symbolic windows,
+    // resolve, narrow), the byte ranges this rank uploaded — all scratch given back by gzip_rank_release
+    DevBuf<uint16_t> gz_wsym;
+    const uint8_t *gzr_file = nullptr; uint64_t gzr_lo = 0, gzr_hi = 0;
+    // ... and of a group's files load: per gzip file the text of the elements [e0, e1) this rank inflated (text byte p of the file at
+    // text.p + 16 + p - off[e0]) and the resolved window in front of element e1, kept until the load ends (gzip_kept_release);
+    // the seeded window walks that added elements later: their marks, milliseconds and elements
+    struct GzKept { const uint8_t *file = nullptr; uint64_t e0 = 0, e1 = 0; DevBuf<uint8_t> text, seed; };
+    std::vector<GzKept> gz_kept;
+    StageTimer<2> tm_gzt;
+    float gzr_tail_ms = 0; uint64_t gzr_tail_elements = 0;
+    StageTimer<12> tm_gzr;
+    float gzr_ms[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<std::pair<uint64_t, uint64_t>> gzr_uploads;
     int gzip_on_device = 0;                  // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip (CRASS_GZIP_ON_DEVICE_*)
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the records' indices / flags / offsets and the text on the device, kept from
     // call to call, their pinned host sides (f_h_off and f_h_chars are what crass_text points at), the flags of

@@ -2,6 +2,7 @@
 // plain gzip of one member or several, chunk by chunk (gunzip.hip, gunzip_core.h).  The loaders that scan what is inflated
 // here are engine_fastx.cpp and engine_shards.cpp; what they call is declared in ingest_internal.h.
 #include "ingest_internal.h"
+#include "gunzip_ranges.h"
 
 extern "C" {
 
@@ -82,7 +83,7 @@ int gzip_count_impl(crass_hip_ctx *c, const uint8_t *d_in, uint64_t n_in, uint64
         const uint64_t nc = G.nc;
         HIPCHK(c, c->in.gz_a64.ensure((members ? 4 : 3) * nc)); HIPCHK(c, c->in.gz_a32.ensure((members ? 3 : 2) * nc));
         GzJob J{};
-        J.d = d_in + G.d_off; J.G = G;
+        J.d = d_in + G.d_off; J.G = G; gz_job_whole(J);
         J.start = c->in.gz_a64.p; J.text_len = c->in.gz_a64.p + nc; J.end_bit = c->in.gz_a64.p + 2 * nc;
         J.link = c->in.gz_a32.p; J.reason = reinterpret_cast<int32_t *>(c->in.gz_a32.p + nc);
         if (members) { J.last_end = c->in.gz_a64.p + 3 * nc; J.n_ends = c->in.gz_a32.p + 2 * nc; }
@@ -140,7 +141,7 @@ int gzip_decode_impl(crass_hip_ctx *c, const uint8_t *d_in, GzState &S, uint8_t 
         HIPCHK(c, c->in.gz_sym.ensure(S.n_text)); HIPCHK(c, c->in.gz_win.ensure(n * (uint64_t)kGzWindow));
         HIPCHK(c, c->in.z_verdict.ensure(1)); HIPCHK(c, c->in.z_h_verdict.ensure(1));
         GzJob J{};
-        J.d = d_in + G.d_off; J.G = G;
+        J.d = d_in + G.d_off; J.G = G; gz_job_whole(J);
         J.start = c->in.gz_b64.p; J.end_bit = c->in.gz_b64.p + nc;
         J.n_chain = n; J.off = c->in.gz_b64.p + 2 * nc; J.chain = c->in.gz_b32.p; J.crc_part = c->in.gz_b32.p + n;
         J.sym = c->in.gz_sym.p; J.win = c->in.gz_win.p; J.out = d_out; J.verdict = c->in.z_verdict.p;
@@ -259,3 +260,316 @@ int crass_hip_last_gzip_ms(const crass_hip_ctx *c, float *ms)
 float crass_hip_last_inflate_ms(const crass_hip_ctx *c) { return c ? c->in.last_inflate_ms : 0.0f; }
 
 } // extern "C"
+
+// ---- one plain gzip file inflated across the ranks of a group (gunzip_ranges.h): one rank's steps ----
+namespace {
+
+// the deflate bytes [lo, hi) of the file in z_raw.  What z_raw holds of this file stays: the new range is taken as the hull of
+// both, what is kept moves device to device, only the missing ends come up.  z_raw may have gone back in between (release_bgzf)
+int gzr_stage(crass_hip_ctx *c, const GzRangesFile &F, uint64_t lo, uint64_t hi)
+{
+    Ingest &I = c->in;
+    const bool kept = I.z_raw.p && I.gzr_file == F.bytes && I.gzr_hi > I.gzr_lo && I.z_raw.n >= I.gzr_hi - I.gzr_lo;
+    const uint64_t klo = kept ? I.gzr_lo : 0, khi = kept ? I.gzr_hi : 0;
+    if (kept && lo >= klo && hi <= khi) return CRASS_OK;
+    if (kept && lo <= khi && hi >= klo) { lo = std::min(lo, klo); hi = std::max(hi, khi); }      // (the hull, where they touch)
+    const uint8_t *src = F.bytes + F.M.G.d_off;
+    I.gzr_uploads.reserve(I.gzr_uploads.size() + 2);    // (nothing below throws)
+    DevBuf<uint8_t> fresh;
+    auto run = [&]() -> int {
+        HIPCHK(c, fresh.ensure(hi - lo + 16));
+        const uint64_t a = std::max(lo, klo), b = std::min(hi, khi);      // what is kept of [lo, hi): [a, b)
+        const bool some = kept && a < b;
+        if (some) HIPCHK(c, hipMemcpyAsync(fresh.p + (a - lo), I.z_raw.p + (a - klo), b - a, hipMemcpyDeviceToDevice, c->stream));
+        const uint64_t parts[2][2] = {{lo, some ? a : hi}, {some ? b : hi, hi}};
+        for (const auto &q : parts) {
+            if (q[0] >= q[1]) continue;
+            const int s = upload_staged(c, src + q[0], q[1] - q[0], fresh.p + (q[0] - lo));
+            if (s) return s;
+            I.gzr_uploads.push_back(std::make_pair((uint64_t)(uintptr_t)(src + q[0]), (uint64_t)(uintptr_t)(src + q[1])));      // (host addresses: files apart)
+            // (upload_staged begins with its first pinned buffer whatever the upload before left in flight: at most two uploads here)
+            HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return CRASS_OK;
+    };
+    const int s = run();
+    if (s) { fresh.release(); return s; }
+    I.z_raw.release();
+    I.z_raw = fresh;
+    I.gzr_file = F.bytes; I.gzr_lo = lo; I.gzr_hi = hi;
+    return CRASS_OK;
+}
+
+// a job over the staged bytes and the per-chunk arrays of gz_a64 / gz_a32
+GzJob gzr_job(crass_hip_ctx *c, const GzRangesFile &F)
+{
+    Ingest &I = c->in;
+    const uint64_t nc = F.M.G.nc;
+    GzJob J{};
+    J.d = reinterpret_cast<const uint8_t *>((uintptr_t)I.z_raw.p - I.gzr_lo); J.G = F.M.G;
+    J.in_lo = I.gzr_lo; J.in_hi = I.gzr_hi;
+    J.start = I.gz_a64.p; J.text_len = I.gz_a64.p + nc; J.end_bit = I.gz_a64.p + 2 * nc;
+    J.link = I.gz_a32.p; J.reason = reinterpret_cast<int32_t *>(I.gz_a32.p + nc);
+    return J;
+}
+
+} // namespace
+
+int gzip_rank_find(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    I.gzr_lo = I.gzr_hi = 0; I.gzr_file = nullptr;
+    for (float &m : I.gzr_ms) m = 0;
+    const GzGeom &G = F.M.G;
+    const uint64_t nc = G.nc, k0 = F.k_lo(r), k1 = F.k_lo(r + 1);
+    try {
+        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_a32.ensure(2 * nc));
+        if (k0 >= k1) return CRASS_OK;
+        const int ss = gzr_stage(c, F, gz_nominal(G, k0) >> 3, gz_input_end(G, k1 - 1));
+        if (ss) return ss;
+        GzJob J = gzr_job(c, F);
+        J.k0 = k0; J.k1 = k1;
+        HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 0));
+        HIPCHK(c, launch_gz_find(J, c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.start.data() + k0, J.start + k0, (k1 - k0) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, I.tm_gzr.elapsed(0, 1, &I.gzr_ms[0]));
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+int gzip_rank_count(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    const uint64_t nc = F.M.G.nc, k0 = F.k_lo(r), k1 = F.k_lo(r + 1);
+    if (k0 >= k1) return CRASS_OK;
+    GzJob J = gzr_job(c, F);
+    J.k0 = k0; J.k1 = k1;
+    HIPCHK(c, hipMemcpyAsync(J.start, F.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));      // (every rank's starts: a run links to any later chunk)
+    HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 2));
+    HIPCHK(c, launch_gz_count(J, c->stream));
+    HIPCHK(c, I.tm_gzr.mark(c->stream));
+    const uint64_t n = k1 - k0;
+    HIPCHK(c, hipMemcpyAsync(F.text_len.data() + k0, J.text_len + k0, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(F.end_bit.data() + k0, J.end_bit + k0, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(F.link.data() + k0, J.link + k0, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(F.reason.data() + k0, J.reason + k0, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, I.tm_gzr.elapsed(2, 3, &I.gzr_ms[1]));
+    return CRASS_OK;
+}
+
+// the job of the rank's elements [a, b): the chain arrays of gz_b64 / gz_b32, sym and out as the places of text byte 0
+static GzJob gzr_element_job(crass_hip_ctx *c, const GzRangesFile &F, uint64_t a, uint64_t b)
+{
+    Ingest &I = c->in;
+    GzJob J = gzr_job(c, F);
+    const uint64_t ne = b - a, last = std::min(b, F.n_chain - 1);
+    J.e0 = a; J.n_chain = ne; J.n_win = last - a;
+    J.off = I.gz_b64.p; J.chain = I.gz_b32.p; J.crc_part = I.gz_b32.p + ne;
+    J.sym = reinterpret_cast<uint16_t *>((uintptr_t)I.gz_sym.p - 2 * F.off[a]);
+    J.win = I.gz_win.p; J.wsym = I.gz_wsym.p;
+    return J;
+}
+
+int gzip_rank_decode(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    const GzGeom &G = F.M.G;
+    const uint64_t nc = G.nc, a = F.e0[r], b = F.e1[r], ne = b - a;
+    F.exported[r].clear();
+    if (ne == 0) return CRASS_OK;
+    try {
+        const int ss = gzr_stage(c, F, F.start[F.chain[a]] >> 3, gz_input_end(G, F.chain[b - 1]));
+        if (ss) return ss;
+        const uint64_t n_win = std::min(b, F.n_chain - 1) - a;
+        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1)); HIPCHK(c, I.gz_b32.ensure(2 * ne));
+        HIPCHK(c, I.gz_sym.ensure(F.off[b] - F.off[a] + 1)); HIPCHK(c, I.gz_win.ensure(std::max(ne, n_win + 1) * (uint64_t)kGzWindow));
+        HIPCHK(c, I.gz_wsym.ensure((n_win + 1) * (uint64_t)kGzWindow));
+        GzJob J = gzr_element_job(c, F, a, b);
+        HIPCHK(c, hipMemcpyAsync(J.start, F.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(J.end_bit, F.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.gz_b64.p, F.off.data() + a, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.gz_b32.p, F.chain.data() + a, ne * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 4));
+        HIPCHK(c, launch_gz_decode(J, c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        HIPCHK(c, launch_gz_windows_sym(J, c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        // the window in front of the next rank's first element: this range's where that element lies behind its first one
+        const uint64_t next = F.e0[r + 1];
+        if (next > a && next < F.n_chain) {
+            if (next - a > n_win) return CRASS_ERR_STATE;      // (never expected: e0 <= e0' <= e1)
+            F.exported[r].resize(kGzWindow);
+            HIPCHK(c, hipMemcpyAsync(F.exported[r].data(), J.wsym + (next - a) * (uint64_t)kGzWindow, kGzWindow * 2, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, I.tm_gzr.elapsed(4, 5, &I.gzr_ms[2])); HIPCHK(c, I.tm_gzr.elapsed(6, 7, &I.gzr_ms[3]));
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+int gzip_rank_finish(crass_hip_ctx *c, GzRangesFile &F, uint32_t r, uint8_t *out, bool keep)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    const uint64_t a = F.e0[r], b = F.e1[r], ne = b - a;
+    F.bad[r] = ~0ull;
+    if (ne == 0) return CRASS_OK;
+    try {
+        if (a && F.entry[r].size() != kGzWindow) return CRASS_ERR_STATE;
+        HIPCHK(c, I.z_text.ensure(F.off[b] - F.off[a] + 32)); HIPCHK(c, I.z_verdict.ensure(1)); HIPCHK(c, I.z_h_verdict.ensure(1));
+        GzJob J = gzr_element_job(c, F, a, b);
+        J.out = reinterpret_cast<uint8_t *>((uintptr_t)I.z_text.p + 16 - F.off[a]);
+        J.verdict = I.z_verdict.p;
+        if (a) HIPCHK(c, hipMemcpyAsync(J.win, F.entry[r].data(), kGzWindow, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
+        HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 8));
+        HIPCHK(c, launch_gz_window_resolve(J, c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        HIPCHK(c, I.tm_gzr.mark(c->stream));
+        // what no rank in front holds: its text to the caller, its CRC parts to the host
+        const uint64_t f = std::max(a, F.first[r]);
+        if (f < b) {
+            if (out && F.off[b] > F.off[f]) HIPCHK(c, hipMemcpyAsync(out + F.off[f], J.out + F.off[f], F.off[b] - F.off[f], hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(F.crc_part.data() + f, J.crc_part + (f - a), (b - f) * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(I.z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, I.tm_gzr.elapsed(8, 9, &I.gzr_ms[4])); HIPCHK(c, I.tm_gzr.elapsed(10, 11, &I.gzr_ms[5]));
+        const uint64_t w = I.z_h_verdict.p[0];
+        if (w != kBzNoOffence) F.bad[r] = a + w;
+        if (keep) {
+            // a files load: the text stays on this rank's device until the load ends, with the resolved window behind its last
+            // element, from which further elements are walked (gzip_kept_inflate)
+            I.gz_kept.emplace_back();
+            Ingest::GzKept &K = I.gz_kept.back();
+            K.file = F.bytes; K.e0 = a; K.e1 = b;
+            K.text = I.z_text; I.z_text = DevBuf<uint8_t>();
+            HIPCHK(c, K.seed.ensure(kGzWindow));
+            if (b < F.n_chain) HIPCHK(c, hipMemcpyAsync(K.seed.p, J.win + ne * (uint64_t)kGzWindow, kGzWindow, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+// further elements [K.e1, m1) of a kept range: decoded, their windows walked by k_gz_windows from the kept seed, narrowed behind the
+// text that is there; the seed moves on.  An unresolved marker: CRASS_ERR_UNSUPPORTED with *bv
+static int gzip_kept_grow(crass_hip_ctx *c, const GzRangesFile &F, Ingest::GzKept &K, uint64_t m1, crass_bgzf_verdict *bv)
+{
+    Ingest &I = c->in;
+    const GzGeom &G = F.M.G;
+    const uint64_t nc = G.nc, a = K.e1, b = m1, ne = b - a, n_win = std::min(b, F.n_chain - 1) - a;
+    const int ss = gzr_stage(c, F, F.start[F.chain[a]] >> 3, gz_input_end(G, F.chain[b - 1]));
+    if (ss) return ss;
+    DevBuf<uint8_t> grown;
+    auto run = [&]() -> int {
+        HIPCHK(c, grown.ensure(F.off[b] - F.off[K.e0] + 32));
+        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1)); HIPCHK(c, I.gz_b32.ensure(2 * ne));
+        HIPCHK(c, I.gz_sym.ensure(F.off[b] - F.off[a] + 1)); HIPCHK(c, I.gz_win.ensure(std::max(ne, n_win + 1) * (uint64_t)kGzWindow));
+        HIPCHK(c, I.z_verdict.ensure(1)); HIPCHK(c, I.z_h_verdict.ensure(1));
+        GzJob J = gzr_element_job(c, F, a, b);
+        J.out = reinterpret_cast<uint8_t *>((uintptr_t)grown.p + 16 - F.off[K.e0]);
+        J.verdict = I.z_verdict.p;
+        if (F.off[a] > F.off[K.e0]) HIPCHK(c, hipMemcpyAsync(grown.p + 16, K.text.p + 16, F.off[a] - F.off[K.e0], hipMemcpyDeviceToDevice, c->stream));
+        if (a) HIPCHK(c, hipMemcpyAsync(J.win, K.seed.p, kGzWindow, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(J.start, F.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(J.end_bit, F.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.gz_b64.p, F.off.data() + a, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.gz_b32.p, F.chain.data() + a, ne * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
+        HIPCHK(c, launch_gz_decode(J, c->stream));
+        HIPCHK(c, I.tm_gzt.begin(c->timing_level >= 1, c->stream));
+        HIPCHK(c, launch_gz_windows(J, c->stream));
+        HIPCHK(c, I.tm_gzt.mark(c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        if (b < F.n_chain) HIPCHK(c, hipMemcpyAsync(K.seed.p, J.win + ne * (uint64_t)kGzWindow, kGzWindow, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(I.z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIPCHK(c, I.tm_gzt.elapsed(0, 1, &ms));
+        I.gzr_tail_ms += ms; I.gzr_tail_elements += ne;
+        const uint64_t w = I.z_h_verdict.p[0];
+        if (w != kBzNoOffence) {
+            const uint64_t k = F.chain[a + w];
+            if (bv) { bv->reason = BZ_MARKER; bv->member = k; bv->in_pos = G.d_off + (F.start[k] >> 3); }
+            return CRASS_ERR_UNSUPPORTED;
+        }
+        return CRASS_OK;
+    };
+    const int s = run();
+    if (s) { grown.release(); return s; }
+    K.text.release();
+    K.text = grown; K.e1 = b;
+    return CRASS_OK;
+}
+
+int gzip_kept_inflate(crass_hip_ctx *c, const GzRangesFile &F, uint64_t m0, uint64_t m1, uint8_t *text0, crass_bgzf_verdict *bv)
+{
+    if (!c) return CRASS_ERR_INVALID_ARG;
+    if (m0 >= m1) return CRASS_OK;
+    Ingest &I = c->in;
+    (void)hipSetDevice(c->device);
+    try {
+        Ingest::GzKept *K = nullptr;
+        for (auto &k : I.gz_kept) if (k.file == F.bytes) K = &k;
+        // a rank whose nominal range held nothing of the file (a cut that moved into a file the range did not touch: the file's
+        // position 0, when no record starts between the nominal cut and the end of the file before): from element 0, which has no
+        // window — correct, and serial over everything in front of m1, which there is what the rank needs anyway (its range
+        // begins at the file's first byte)
+        if (!K) {
+            I.gz_kept.emplace_back();
+            K = &I.gz_kept.back();
+            K->file = F.bytes;
+            HIPCHK(c, K->seed.ensure(kGzWindow)); HIPCHK(c, K->text.ensure(32));
+        }
+        if (m0 < K->e0) return CRASS_ERR_STATE;         // (never expected: a rank's later needs lie behind its nominal range's first element)
+        if (m1 > K->e1) { const int s = gzip_kept_grow(c, F, *K, m1, bv); if (s) return s; }
+        HIPCHK(c, hipMemcpyAsync(text0 + F.off[m0], K->text.p + 16 + (F.off[m0] - F.off[K->e0]), F.off[m1] - F.off[m0], hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+void gzip_kept_release(crass_hip_ctx *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    wait_main(c);
+    for (auto &k : c->in.gz_kept) { k.text.release(); k.seed.release(); }
+    c->in.gz_kept.clear();
+}
+
+void gzip_kept_report(crass_hip_ctx *c, float *tail_ms, uint64_t *tail_elements, bool reset)
+{
+    if (tail_ms) *tail_ms = c ? c->in.gzr_tail_ms : 0.0f;
+    if (tail_elements) *tail_elements = c ? c->in.gzr_tail_elements : 0;
+    if (c && reset) { c->in.gzr_tail_ms = 0; c->in.gzr_tail_elements = 0; c->in.gzr_uploads.clear(); }
+}
+
+void gzip_rank_release(crass_hip_ctx *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    release_gzip(c); release_bgzf(c);                   // (the staged bytes, the text and the verdict word are the BGZF inflate's)
+    c->in.gzr_lo = c->in.gzr_hi = 0; c->in.gzr_file = nullptr;
+}
+
+void gzip_rank_report(const crass_hip_ctx *c, float ms[6], std::vector<std::pair<uint64_t, uint64_t>> *uploads)
+{
+    for (int k = 0; k < 6; k++) ms[k] = c ? c->in.gzr_ms[k] : 0.0f;
+    if (uploads) { uploads->clear(); if (c) *uploads = c->in.gzr_uploads; }
+}

@@ -68,7 +68,7 @@ void release_gzip(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
     wait_main(c);
-    I.gz_a64.release(); I.gz_b64.release(); I.gz_a32.release(); I.gz_b32.release(); I.gz_sym.release(); I.gz_win.release(); I.gz_ends.release();
+    I.gz_a64.release(); I.gz_b64.release(); I.gz_a32.release(); I.gz_b32.release(); I.gz_sym.release(); I.gz_win.release(); I.gz_ends.release(); I.gz_wsym.release();
 }
 
 // the header ids, and what a names build needs beside the table it keeps
@@ -116,6 +116,8 @@ void release_shard(crass_hip_ctx *c)
 void ingest_free_all(crass_hip_ctx *c)
 {
     Ingest &I = c->in;
+    for (auto &k : I.gz_kept) { k.text.release(); k.seed.release(); }
+    I.gz_kept.clear();
     release_text(c); release_scan(c); release_bgzf(c); release_gzip(c); release_header_ids(c); release_names_find(c); release_names_of(c);
     release_comments_build(c); I.cb_h.release(); I.cm.free_all(); I.tm_cm.destroy();
     names_drop(c); drop_arena(c);
@@ -128,7 +130,7 @@ void ingest_free_all(crass_hip_ctx *c)
     I.x_h_tot.release(); I.x_h_rec_pos.release(); I.x_h_seq_off.release(); I.z_h_verdict.release(); I.n_h_ctl.release(); I.nq_h_ctl.release(); I.no_h.release();
     I.fa_h_base.release(); I.fa_h_format.release();
     for (hipEvent_t *e : {&I.ev_t_copy[0], &I.ev_t_copy[1], &I.ev_t_pack[0], &I.ev_t_pack[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    I.tm_pack.destroy(); I.tm_scan.destroy(); I.tm_inflate.destroy(); I.tm_gzip.destroy(); I.tm_fetch.destroy(); I.tm_names.destroy(); I.tm_find.destroy();
+    I.tm_pack.destroy(); I.tm_scan.destroy(); I.tm_inflate.destroy(); I.tm_gzip.destroy(); I.tm_gzr.destroy(); I.tm_gzt.destroy(); I.tm_fetch.destroy(); I.tm_names.destroy(); I.tm_find.destroy();
 }
 
 // what opens every call that replaces the resident set: earlier results and the arena go, and a failure or a decline further

@@ -4,6 +4,7 @@
 // arena the resident set are engine_fastx.cpp's (ArenaScan, arena_finish), the members of a text range and the staging
 // placement fastx_scan.cpp's.
 #include "ingest_internal.h"
+#include "gunzip_ranges.h"
 
 // the probe of a range that lies on the device: launch, the blocks' parts back, folded in block order
 static int probe_impl(crass_hip_ctx *c, const uint8_t *d, uint64_t n, bool left_is_ls, FxProbe *out)
@@ -59,8 +60,11 @@ static std::vector<Slice> shard_slices(const ShardFile *files, uint32_t n_files,
 }
 
 // the members [m0, m1) of a host file inflated so that text position t lies at text0 + t: the compressed bytes up into z_raw
+// (a plain gzip file: its elements, from what the rank keeps of the file and a seeded window walk behind it, gzip_kept_inflate)
 static int shard_inflate(crass_hip_ctx *c, const ShardFile &F, uint64_t m0, uint64_t m1, uint8_t *text0, crass_bgzf_verdict *bv)
 {
+    if (F.gz) return gzip_kept_inflate(c, *F.gz, m0, m1, text0, bv);
+    c->in.gzr_file = nullptr;                           // (z_raw is this inflate's now)
     const uint64_t z0 = F.ix->in_off[m0], z1 = F.ix->in_off[m1];
     HIPCHK(c, c->in.z_raw.ensure(z1 - z0 + 16));
     const int up = upload_staged(c, F.bytes + z0, z1 - z0, c->in.z_raw.p);
@@ -138,7 +142,10 @@ static int shard_cut_grow(crass_hip_ctx *c, const ShardFile &F, Ingest::ShardCut
             HIPCHK(c, I.sh_tail.ensure(t1 - t0 + 16));
             crass_bgzf_verdict bv{};
             const int s = shard_inflate(c, F, m0, m1, reinterpret_cast<uint8_t *>((uintptr_t)I.sh_tail.p - t0), &bv);
-            if (s) return s == CRASS_ERR_UNSUPPORTED ? CRASS_ERR_STATE : s;      // (never expected: every member of the file inflated in step 1)
+            // (never expected: every member of the file inflated in step 1.  A gzip file's grown elements were narrowed before the
+            // load's steps by the rank whose piece holds them; a marker there is the file's pending decline, and a declined file
+            // is not chained)
+            if (s) return s == CRASS_ERR_UNSUPPORTED ? CRASS_ERR_STATE : s;
             HIPCHK(c, hipMemcpyAsync(dst + (K.se - K.a), I.sh_tail.p + (K.se - t0), t1 - K.se, hipMemcpyDeviceToDevice, c->stream));
         } else {
             const int up = upload_staged(c, F.bytes + K.se, t1 - K.se, dst + (K.se - K.a));

@@ -17,6 +17,9 @@ struct ShardFile {
     const uint8_t *bytes; uint64_t n_bytes;
     uint64_t n_text;                       // the text's size (BGZF: the members' ISIZE summed)
     const crass_bgzf_index *ix;            // nullptr: plain text
+    // a plain gzip file a group takes (crass_hip_group_set_gzip_on_device): its chain's ELEMENTS in place of BGZF members — ix
+    // then holds their text offsets (out_off; in_off / data_off unused) and gz what inflates them (gunzip_ranges.h); else nullptr
+    const struct GzRangesFile *gz;
     int32_t format;                        // the text's byte 0; a BGZF file's is known once a rank has inflated its first member
 };
 struct ShardPos { uint32_t file; uint64_t pos; };      // a position of the text space: (n_files, 0) is its end

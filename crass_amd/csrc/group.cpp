@@ -14,10 +14,13 @@
 #include <hip/hip_runtime.h>
 #include "devmem.h"
 #include "fastx_shards.h"
+#include "gunzip_launch.h"
+#include "gunzip_ranges.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -25,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -132,7 +136,7 @@ private:
     std::condition_variable cv_;
 };
 
-enum Phase : unsigned { PH_SEED = 1, PH_MERGE = 2, PH_RECRUIT = 4, PH_LOAD = 8, PH_LOAD_FILES = 16 };
+enum Phase : unsigned { PH_SEED = 1, PH_MERGE = 2, PH_RECRUIT = 4, PH_LOAD = 8, PH_LOAD_FILES = 16, PH_INFLATE_GZIP = 32 };
 
 const bool g_debug = getenv("CRASS_GROUP_DEBUG") != nullptr;           // stage trace on stderr
 #define GDBG(...) do { if (g_debug) { fprintf(stderr, "[crass_group] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
@@ -215,6 +219,32 @@ struct crass_hip_group {
         bool wrapped_pass = false;
         uint64_t n_chained = 0;
     } F;
+    // crass_hip_group_inflate_gzip (gunzip_ranges.h): the file's state, which the ranks fill between barriers; where the text
+    // goes; what rank 0 decided behind the count step (go on, or the call's status); the last call's counters and times
+    struct GzipJob {
+        crass::GzRangesFile Z;                  // crass_hip_group_inflate_gzip's file
+        crass::GzRangesFile *zp = nullptr;      // the file of the running job: &Z, or one of a files load's
+        // the steps of the running job: a files load indexes every gzip file first (find, count, chain: the text's size and the
+        // element index, before any cut) and inflates it once the nominal cuts are known, each rank the elements of its pieces,
+        // their text kept on its device (out NULL)
+        bool do_index = true, do_inflate = true;
+        std::vector<std::unique_ptr<crass::GzRangesFile>> files;      // a files load's, until it returns
+        std::vector<crass_bgzf_index> ix;       // ... and their element indexes in a BGZF index's form (out_off: the text offsets)
+        std::vector<std::vector<uint64_t>> ix_zero;
+        crass::ShardVerdict v_gz;               // the first gzip file of the load that did not inflate (CRC-32, marker)
+        std::vector<float> tail_ms;             // per rank: the seeded window walks of the last load, and the elements they added
+        std::vector<uint64_t> tail_el;
+        uint8_t *out = nullptr; uint64_t out_cap = 0;
+        const uint64_t *nominal = nullptr;
+        std::vector<std::vector<std::pair<uint64_t, uint64_t>>> up;      // per rank: the byte ranges of the deflate data it uploaded
+        bool go = false;
+        int status = 0;
+        crass::GzVerdict v{};
+        uint64_t cnt[6] = {0, 0, 0, 0, 0, 0};
+        std::vector<std::array<float, 6>> ms;
+    } GZ;
+    int gzip_mode = 0;                          // crass_hip_group_set_gzip_on_device
+    uint64_t gzip_chunk = 0;
     int fastq_class = 0;                        // crass_hip_group_set_fastq_class, CRASS_DEVICE_FASTQ at creation
     uint64_t shard_margin = 256u << 10;         // what a wrapped-mode piece stages behind its end at first (CRASS_SHARD_MARGIN at creation)
     uint64_t load_cnt[4] = {0, 0, 0, 0};        // crass_hip_group_load_counters
@@ -343,6 +373,7 @@ int combine_cuts(crass_hip_group *g)
     const int N = g->n;
     // a decline that a rank met while staging: the files in front of it go on, it waits for their verdict
     for (int r = 0; r < N; r++) if (crass::shard_verdict_before(J.v_stage[r], J.pend)) J.pend = J.v_stage[r];
+    if (crass::shard_verdict_before(g->GZ.v_gz, J.pend)) J.pend = g->GZ.v_gz;      // (a gzip file whose CRC-32 or markers failed before the load's steps)
     J.nf_eff = J.pend.file >= 0 ? (uint32_t)J.pend.file : J.nf;
     for (int r = 0; r < N; r++) for (const crass::ShardPiece &pc : J.pieces[r]) if (pc.a == 0 && J.files[pc.file].ix) J.files[pc.file].format = pc.first_byte;
     // the wrapped pass: every '@' file's chain over the ranks, in piece order.  A piece is entered at e, the exit of the one before
@@ -451,6 +482,11 @@ void load_files_rank(crass_hip_group *g, int r)
         if (!s) s = setup_exchange(g, r);
         note(g, r, s);
     } else shard_abort(c);
+    if (!g->GZ.files.empty()) {                          // what the rank kept of the gzip files, and what its seeded walks took
+        gzip_kept_report(c, &g->GZ.tail_ms[r], &g->GZ.tail_el[r], false);
+        gzip_rank_report(c, g->GZ.ms[r].data(), &g->GZ.up[r]);
+        gzip_kept_release(c);
+    }
 }
 
 // found headers across the ranks of a files load (readsFound is keyed by header, libcrispr.cpp:138,411): installed header ids
@@ -586,12 +622,90 @@ int names_lookup_device(crass_hip_group *g, int r)
     return CRASS_OK;
 }
 
+// crass_hip_group_inflate_gzip, rank 0 behind the count step: the chain, the text's size, every rank's elements.  A decline or a
+// text that does not fit ends the job there (J.go stays false, J.status says why)
+int gzip_chain_host(crass_hip_group *g)
+{
+    auto &J = g->GZ;
+    crass::GzRangesFile &Z = *J.zp;
+    const uint64_t nc = Z.M.G.nc;
+    Z.chain.assign(nc, 0);
+    const int32_t bad = crass::gz_chain(Z.M, Z.start.data(), Z.link.data(), Z.text_len.data(), Z.end_bit.data(), Z.reason.data(), Z.chain.data(),
+                                        &Z.n_chain, &Z.n_text, &J.v);
+    if (bad != crass::BZ_OK) { J.status = CRASS_ERR_UNSUPPORTED; return CRASS_OK; }
+    if (J.do_inflate && J.out_cap < Z.n_text) { J.status = CRASS_ERR_OVERFLOW; return CRASS_OK; }
+    const uint64_t n = Z.n_chain;
+    Z.off.assign(n + 1, 0);
+    for (uint64_t i = 0; i < n; i++) Z.off[i + 1] = Z.off[i] + Z.text_len[Z.chain[i]];
+    Z.crc_part.assign(n, 0);
+    if (!J.do_inflate) return CRASS_OK;                 // (a files load: the ranges follow once the cuts are known)
+    const uint32_t N = (uint32_t)g->n;
+    Z.e0.assign(N + 1, n); Z.e1.assign(N + 1, n); Z.first.assign(N + 1, 0);
+    if (!crass::gz_ranges(Z.off.data(), n, N, J.nominal, Z.e0.data(), Z.e1.data())) { J.status = CRASS_ERR_INVALID_ARG; return CRASS_OK; }
+    for (uint32_t r = 0; r < N; r++) Z.first[r + 1] = std::max(Z.first[r], Z.e1[r]);
+    J.go = true;
+    return CRASS_OK;
+}
+
+// ... behind the decode step: every rank's entry window, composed in rank order from what the rank in front exported (a rank
+// without elements of its own, or one that starts in the same element, passes its entry window on)
+void gzip_compose_host(crass_hip_group *g)
+{
+    crass::GzRangesFile &Z = *g->GZ.zp;
+    Z.entry[0].clear();
+    for (int r = 0; r + 1 < g->n; r++) {
+        if (Z.e0[r + 1] >= Z.n_chain) { Z.entry[r + 1].clear(); continue; }      // (no elements: nothing to enter)
+        if (Z.exported[r].empty()) { Z.entry[r + 1] = Z.entry[r]; continue; }
+        const uint8_t *in = Z.entry[r].empty() ? nullptr : Z.entry[r].data();
+        Z.entry[r + 1].resize(crass::kGzWindow);
+        for (uint32_t w = 0; w < crass::kGzWindow; w++) Z.entry[r + 1][w] = crass::gz_window_resolve(Z.exported[r][w], in);
+    }
+}
+
+// a file's state before the index step: the header and the trailer parsed (false: not a gzip member), the per-chunk arrays empty
+bool gzip_file_init(crass::GzRangesFile &Z, const uint8_t *bytes, uint64_t n_bytes, uint32_t n_ranks, uint64_t chunk_bytes)
+{
+    Z = crass::GzRangesFile();
+    Z.bytes = bytes; Z.n_bytes = n_bytes; Z.n_ranks = n_ranks;
+    if (crass::gz_parse_member(bytes, n_bytes, n_bytes >= 8 ? bytes + n_bytes - 8 : nullptr, n_bytes, chunk_bytes, &Z.M) != crass::BZ_OK) return false;
+    const uint64_t nc = Z.M.G.nc;
+    Z.start.assign(nc, crass::kGzNoStart); Z.text_len.assign(nc, 0); Z.end_bit.assign(nc, 0);
+    Z.link.assign(nc, crass::GZ_LINK_NONE); Z.reason.assign(nc, 0);
+    return true;
+}
+
+void gzip_inflate_rank(crass_hip_group *g, int r)
+{
+    auto &J = g->GZ;
+    crass_hip_ctx *c = g->ctx[r];
+    auto ok = [&] { return g->failed.load(std::memory_order_acquire) == 0; };
+    crass::GzRangesFile &Z = *J.zp;
+    if (J.do_index) {
+        if (ok()) note(g, r, gzip_rank_find(c, Z, (uint32_t)r));
+        g->bar->wait();                                 // every chunk's start is there
+        if (ok()) note(g, r, gzip_rank_count(c, Z, (uint32_t)r));
+        g->bar->wait();                                 // ... and what its run counted
+        if (r == 0 && ok()) { try { note(g, 0, gzip_chain_host(g)); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+        g->bar->wait();                                 // the chain and the ranges, or the end of the job
+    }
+    if (J.do_inflate) {
+        if (ok() && J.go) note(g, r, gzip_rank_decode(c, Z, (uint32_t)r));
+        g->bar->wait();                                 // every rank's exported window
+        if (r == 0 && ok() && J.go) { try { gzip_compose_host(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+        g->bar->wait();                                 // every rank's entry window
+        if (ok() && J.go) note(g, r, gzip_rank_finish(c, Z, (uint32_t)r, J.out, !J.do_index));
+    }
+    gzip_rank_report(c, J.ms[r].data(), &J.up[r]);
+    if (J.do_index && J.do_inflate) gzip_rank_release(c);      // (a files load keeps the staged bytes and gives all scratch back at its end)
+}
+
 // one rank's part of a job; every rank passes the same barriers whatever happens
 void run_rank(crass_hip_group *g, int r, unsigned phases)
 {
     crass_hip_ctx *c = g->ctx[r];
     auto ok = [&] { return g->failed.load(std::memory_order_acquire) == 0; };
     if (phases & PH_LOAD_FILES) { load_files_rank(g, r); return; }
+    if (phases & PH_INFLATE_GZIP) { gzip_inflate_rank(g, r); return; }
     if (phases & PH_LOAD) {
         int s = crass_hip_load_reads(c, &g->shard[r]);
         if (!s) s = setup_exchange(g, r);
@@ -706,6 +820,18 @@ int dispatch(crass_hip_group *g, unsigned phases)
     return CRASS_OK;
 }
 
+// a step of a files load on one of its gzip files: the index step, or — its ranges set — the inflate step whose text the ranks keep
+int gzip_job_run(crass_hip_group *g, crass::GzRangesFile &Z, bool index, bool inflate)
+{
+    auto &J = g->GZ;
+    const size_t N = (size_t)g->n;
+    J.zp = &Z; J.do_index = index; J.do_inflate = inflate;
+    J.out = nullptr; J.out_cap = 0; J.nominal = nullptr; J.status = CRASS_OK;
+    if (index) { J.v = crass::GzVerdict{}; J.go = false; }
+    else { Z.exported.assign(N, {}); Z.entry.assign(N, {}); Z.bad.assign(N, ~0ull); J.go = true; }
+    return dispatch(g, PH_INFLATE_GZIP);
+}
+
 } // namespace
 
 extern "C" {
@@ -805,6 +931,83 @@ int crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4])
 {
     if (!g || !out) return CRASS_ERR_INVALID_ARG;
     for (int k = 0; k < 4; k++) out[k] = g->load_cnt[k];
+    return CRASS_OK;
+}
+
+int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
+                                 uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    if (v) memset(v, 0, sizeof(*v));
+    if (plan) memset(plan, 0, sizeof(*plan));
+    if (n_text) *n_text = 0;
+    if (!g || !n_text || (n_bytes && !bytes) || (out_cap && !out_host)) return CRASS_ERR_INVALID_ARG;
+    auto &J = g->GZ;
+    for (auto &x : J.cnt) x = 0;
+    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
+        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
+        return CRASS_ERR_UNSUPPORTED;
+    };
+    try {
+        const uint32_t N = (uint32_t)g->n;
+        crass::GzRangesFile &Z = J.Z;
+        J.zp = &Z; J.do_index = J.do_inflate = true;
+        for (int r = 0; r < g->n; r++) gzip_kept_report(g->ctx[r], nullptr, nullptr, true);
+        J.ms.assign(N, std::array<float, 6>{}); J.up.assign(N, {}); J.tail_ms.assign(N, 0.0f); J.tail_el.assign(N, 0);
+        if (!gzip_file_init(Z, bytes, n_bytes, N, chunk_bytes)) return decline(crass::BZ_NOT_GZIP, 0, 0);
+        const uint64_t nc = Z.M.G.nc;
+        Z.exported.assign(N, {}); Z.entry.assign(N, {}); Z.bad.assign(N, ~0ull);
+        J.out = out_host; J.out_cap = out_cap; J.nominal = nominal; J.go = false; J.status = CRASS_OK; J.v = crass::GzVerdict{};
+        const int st = dispatch(g, PH_INFLATE_GZIP);
+        if (st) return st;
+        const int ps = crass::gz_plan_fill(plan, nc, Z.start.data(), Z.link.data(), Z.text_len.data(), Z.n_chain);
+        if (ps) return ps;
+        if (J.status == CRASS_ERR_UNSUPPORTED) return decline(J.v.reason, J.v.member, J.v.in_pos);
+        if (J.status == CRASS_ERR_INVALID_ARG) return J.status;
+        *n_text = Z.n_text;
+        if (J.status) return J.status;                  // (the text does not fit: known before anything is stored)
+        // the counters: elements held by a further rank, bytes uploaded and those of them that some upload had brought already
+        const uint64_t n = Z.n_chain;
+        uint64_t held = 0, sent = 0, distinct = 0;
+        std::vector<std::pair<uint64_t, uint64_t>> all;
+        for (uint32_t r = 0; r < N; r++) {
+            held += Z.e1[r] - Z.e0[r];
+            for (const auto &u : J.up[r]) { sent += u.second - u.first; all.push_back(u); }
+        }
+        std::sort(all.begin(), all.end());
+        uint64_t reach = 0;
+        for (const auto &u : all) { if (u.second > reach) { distinct += u.second - std::max(u.first, reach); reach = u.second; } }
+        J.cnt[0] = 1; J.cnt[1] = nc; J.cnt[2] = n; J.cnt[3] = held - n; J.cnt[4] = sent; J.cnt[5] = sent - distinct;
+        // an unresolved marker: the smallest element over the ranks; then the CRC-32, every part from the first rank that holds it
+        uint64_t bad = ~0ull;
+        for (uint32_t r = 0; r < N; r++) bad = std::min(bad, Z.bad[r]);
+        if (bad != ~0ull) { const uint64_t k = Z.chain[bad]; return decline(crass::BZ_MARKER, k, Z.M.G.d_off + (Z.start[k] >> 3)); }
+        uint32_t crc = 0;
+        for (uint64_t i = 0; i < n; i++) crc = crass::gz_crc_join(crc, Z.crc_part[i], Z.off[i + 1] - Z.off[i]);
+        if (crc != Z.M.crc) return decline(crass::BZ_CRC, 0, 0);
+    } catch (const std::bad_alloc &) { return CRASS_ERR_OOM; }
+    return CRASS_OK;
+}
+
+int crass_hip_group_set_gzip_on_device(crass_hip_group *g, int mode, uint64_t chunk_bytes)
+{
+    if (!g || mode < 0) return CRASS_ERR_INVALID_ARG;
+    g->gzip_mode = mode ? CRASS_GZIP_ON_DEVICE_ONE_MEMBER : CRASS_GZIP_ON_DEVICE_OFF;
+    g->gzip_chunk = chunk_bytes ? crass::gz_chunk_bytes(chunk_bytes) : 0;
+    return CRASS_OK;
+}
+
+int crass_hip_group_gzip_counters(const crass_hip_group *g, uint64_t out[6])
+{
+    if (!g || !out) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 6; k++) out[k] = g->GZ.cnt[k];
+    return CRASS_OK;
+}
+
+int crass_hip_group_gzip_ms(const crass_hip_group *g, int rank, float out[7])
+{
+    if (!g || !out || rank < 0 || rank >= g->n) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 6; k++) out[k] = (size_t)rank < g->GZ.ms.size() ? g->GZ.ms[rank][k] : 0.0f;
+    out[6] = (size_t)rank < g->GZ.tail_ms.size() ? g->GZ.tail_ms[rank] : 0.0f;
     return CRASS_OK;
 }
 
@@ -1077,13 +1280,37 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
         // waits with its decline: a file in front of it may still offend in the scan
         J.files.assign(n_files, crass::ShardFile{});
         J.nf = n_files;
+        for (uint64_t &x : g->GZ.cnt) x = 0;
+        g->GZ.files.clear(); g->GZ.ix.clear(); g->GZ.ix_zero.clear(); g->GZ.ix.reserve(n_files);
+        g->GZ.v_gz = crass::ShardVerdict();
+        g->GZ.ms.assign(N, std::array<float, 6>{}); g->GZ.up.assign(N, {}); g->GZ.tail_ms.assign(N, 0.0f); g->GZ.tail_el.assign(N, 0);
+        for (int r = 0; r < N; r++) { gzip_kept_release(g->ctx[r]); gzip_kept_report(g->ctx[r], nullptr, nullptr, true); }      // (what a failed load left)
         for (uint32_t f = 0; f < n_files; f++) {
             crass::ShardFile &F = J.files[f];
             F.bytes = bytes[f]; F.n_bytes = n_bytes[f];
             auto pend = [&](int32_t reason) { J.pend.file = (int32_t)f; J.pend.reason = reason; J.nf = f; };
             if (F.n_bytes >= 2 && F.bytes[0] == 0x1F && F.bytes[1] == 0x8B) {
                 const int s = crass_bgzf_index_host(F.bytes, F.n_bytes, &ixs[f]);
-                if (s == CRASS_ERR_UNSUPPORTED) { pend(0); J.pend.bgzf = ixs[f].decline; break; }      // (plain gzip too: one deflate stream cannot be cut)
+                if (s == CRASS_ERR_UNSUPPORTED && g->gzip_mode && ixs[f].decline.reason == crass::BZ_NOT_BGZF) {
+                    // plain gzip with the switch on, the index step: every rank finds and counts its share of the chunks, rank 0 walks
+                    // the chain.  The text's size and the element index (start bit, end bit, text offset of every chain element) are
+                    // known before any cut; the index takes a BGZF index's place, elements for members
+                    auto &GJ = g->GZ;
+                    GJ.files.emplace_back(new crass::GzRangesFile());
+                    crass::GzRangesFile &Z = *GJ.files.back();
+                    if (!gzip_file_init(Z, F.bytes, F.n_bytes, (uint32_t)N, g->gzip_chunk)) { pend(0); J.pend.bgzf.reason = crass::BZ_NOT_GZIP; break; }
+                    const int zs = gzip_job_run(g, Z, true, false);
+                    if (zs) return zs;
+                    if (GJ.status == CRASS_ERR_UNSUPPORTED) { pend(0); J.pend.bgzf.reason = GJ.v.reason; J.pend.bgzf.member = GJ.v.member; J.pend.bgzf.in_pos = GJ.v.in_pos; break; }
+                    GJ.ix_zero.emplace_back(Z.n_chain + 1, 0);
+                    crass_bgzf_index X{};
+                    X.n_members = Z.n_chain; X.out_off = Z.off.data(); X.in_off = X.data_off = GJ.ix_zero.back().data();
+                    GJ.ix.push_back(X);                     // (reserved for n_files: the pointers below stay)
+                    F.ix = &GJ.ix.back(); F.gz = &Z; F.n_text = Z.n_text;
+                    if (F.n_text == 0) { pend(crass::FX_EMPTY); break; }
+                    continue;
+                }
+                if (s == CRASS_ERR_UNSUPPORTED) { pend(0); J.pend.bgzf = ixs[f].decline; break; }      // (plain gzip with the switch off: declined)
                 if (s) return s;
                 F.ix = &ixs[f]; F.n_text = ixs[f].out_off[ixs[f].n_members];
                 if (F.n_text == 0) { pend(crass::FX_EMPTY); break; }
@@ -1107,16 +1334,62 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
         J.pieces.assign(N, {}); J.v_stage.assign(N, crass::ShardVerdict()); J.v_scan.assign(N, crass::ShardVerdict());
         J.file_reads.assign(N, {}); J.n_reads.assign(N, 0); J.max_len.assign(N, 0);
         J.cut.assign(N + 1, crass::ShardPos{nf, 0});
+        // the gzip files, now that the nominal cuts are known: every rank inflates the elements that hold its pieces (with the
+        // byte in front of a piece, as a BGZF file's members are taken) in two halves with the composition of the entry windows
+        // between them, and keeps their text on its device; rank 0 joins the CRC-32 parts.  The first file that does not inflate
+        // waits with its decline as a rank's staging decline does; the files behind it are inflated all the same
+        for (uint32_t f = 0; f < nf; f++) {
+            if (!J.files[f].gz) continue;
+            crass::GzRangesFile &Z = *const_cast<crass::GzRangesFile *>(J.files[f].gz);
+            const uint64_t n = Z.n_chain;
+            Z.e0.assign(N + 1, n); Z.e1.assign(N + 1, n); Z.first.assign(N + 1, 0);
+            std::vector<uint8_t> holds(N + 1, 0);
+            for (int r = 0; r < N; r++) {
+                const crass::ShardPos lo = J.nom[r], hi = J.nom[r + 1];
+                if (f < lo.file || f > hi.file) continue;
+                const uint64_t a = f == lo.file ? lo.pos : 0, b = f == hi.file ? hi.pos : Z.n_text;
+                if (a >= b) continue;
+                crass::bgzf_members_for(Z.off.data(), n, a ? a - 1 : 0, b, &Z.e0[r], &Z.e1[r]);
+                holds[r] = 1;
+            }
+            for (int r = N - 1; r >= 0; r--) if (!holds[r]) Z.e0[r] = Z.e1[r] = Z.e0[r + 1];      // (passes the window on to the next rank that holds some)
+            for (int r = 0; r < N; r++) Z.first[r + 1] = std::max(Z.first[r], Z.e1[r]);
+            const int zs = gzip_job_run(g, Z, false, true);
+            if (zs) return zs;
+            uint64_t bad = ~0ull;
+            for (int r = 0; r < N; r++) { bad = std::min(bad, Z.bad[r]); g->GZ.cnt[3] += Z.e1[r] - Z.e0[r]; }
+            g->GZ.cnt[0] += 1; g->GZ.cnt[1] += Z.M.G.nc; g->GZ.cnt[2] += n; g->GZ.cnt[3] -= n;
+            uint32_t crc = 0;
+            for (uint64_t i = 0; i < n; i++) crc = crass::gz_crc_join(crc, Z.crc_part[i], Z.off[i + 1] - Z.off[i]);
+            crass::ShardVerdict sv;
+            sv.file = (int32_t)f;
+            if (bad != ~0ull) { const uint64_t k = Z.chain[bad]; sv.bgzf.reason = crass::BZ_MARKER; sv.bgzf.member = k; sv.bgzf.in_pos = Z.M.G.d_off + (Z.start[k] >> 3); }
+            else if (crc != Z.M.crc) sv.bgzf.reason = crass::BZ_CRC;
+            if (sv.bgzf.reason && crass::shard_verdict_before(sv, g->GZ.v_gz)) g->GZ.v_gz = sv;
+        }
         J.pend0 = J.pend;
         for (uint64_t &x : g->load_cnt) x = 0;
         st = dispatch(g, PH_LOAD_FILES);
+        // the gzip counters of the load: the elements the seeded walks added count as inflated by a further rank; the uploads
+        // are ranges of host addresses, so bytes of different files never count as the same
+        if (!g->GZ.files.empty()) {
+            std::vector<std::pair<uint64_t, uint64_t>> all;
+            uint64_t sent = 0, distinct = 0, reach = 0;
+            for (int r = 0; r < N; r++) {
+                g->GZ.cnt[3] += g->GZ.tail_el[r];
+                for (const auto &u : g->GZ.up[r]) { sent += u.second - u.first; all.push_back(u); }
+            }
+            std::sort(all.begin(), all.end());
+            for (const auto &u : all) { if (u.second > reach) { distinct += u.second - std::max(u.first, reach); reach = u.second; } }
+            g->GZ.cnt[4] = sent; g->GZ.cnt[5] = sent - distinct;
+        }
         g->load_cnt[0] = (uint64_t)J.attempts; g->load_cnt[1] = J.wrapped_pass ? J.n_chained : 0;
         for (int r = 0; J.wrapped_pass && r < N; r++) {
             uint64_t lk = 0, db = 0;
             shard_cut_counters(g->ctx[r], &lk, &db, nullptr);
             g->load_cnt[2] += db; g->load_cnt[3] += lk;
         }
-        for (auto &F : J.files) { F.ix = nullptr; F.bytes = nullptr; }      // (the caller's bytes and this call's indexes: used inside this call only)
+        for (auto &F : J.files) { F.ix = nullptr; F.gz = nullptr; F.bytes = nullptr; }      // (the caller's bytes and this call's indexes: used inside this call only)
         if (st) return st;
         if (J.declined) {
             if (out) { out->decline_file = J.verdict.file; out->decline_reason = J.verdict.reason; out->decline_pos = J.verdict.pos; out->bgzf = J.verdict.bgzf; }

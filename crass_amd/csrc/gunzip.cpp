@@ -66,53 +66,81 @@ int gz_members_fill(crass_gzip_members *m, uint64_t nm, const uint64_t *in_off, 
 
 using namespace crass;
 
-// the serial run; MEM: members mode (gunzip_core.h), `members` (may be NULL) gets the member table
+// what find, count and the chain leave on the host
+struct GzHostCount {
+    GzMember M{};
+    std::vector<uint64_t> start, text_len, end_bit, last_end;
+    std::vector<uint32_t> link, chain, n_ends;
+    std::vector<int32_t> reason;
+    uint64_t n_chain = 0, total = 0;
+};
+
+static int gz_decline(crass_bgzf_verdict *v, int32_t reason, uint64_t member, uint64_t in_pos)
+{
+    if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
+    return CRASS_ERR_UNSUPPORTED;
+}
+
+// the arguments, the header, find, count, the chain and the plan: -1 when the text is to be made (P filled, *n_text set, out_cap
+// large enough), else what the caller returns
 template <bool MEM>
-static int gz_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
-                           crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
+static int gz_front_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                         crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v, GzHostIO &io, BzTables &T, GzHostCount &P)
 {
     if (v) memset(v, 0, sizeof(*v));
     if (plan) memset(plan, 0, sizeof(*plan));
     if (members) memset(members, 0, sizeof(*members));
     if (n_text) *n_text = 0;
     if (!n_text || (n_bytes && !bytes) || (out_cap && !out)) return CRASS_ERR_INVALID_ARG;
-    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
-        if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
-        return CRASS_ERR_UNSUPPORTED;
-    };
-    GzMember M{};
-    if (gz_parse_member(bytes, n_bytes, n_bytes >= 8 ? bytes + n_bytes - 8 : nullptr, n_bytes, chunk_bytes, &M) != BZ_OK) return decline(BZ_NOT_GZIP, 0, 0);
-    const GzGeom &G = M.G;
+    if (gz_parse_member(bytes, n_bytes, n_bytes >= 8 ? bytes + n_bytes - 8 : nullptr, n_bytes, chunk_bytes, &P.M) != BZ_OK) return gz_decline(v, BZ_NOT_GZIP, 0, 0);
+    const GzGeom &G = P.M.G;
     const uint64_t nc = G.nc;
+    P.start.assign(nc, kGzNoStart); P.text_len.assign(nc, 0); P.end_bit.assign(nc, 0); P.last_end.assign(nc, 0);
+    P.link.assign(nc, GZ_LINK_NONE); P.chain.assign(nc, 0); P.n_ends.assign(nc, 0); P.reason.assign(nc, 0);
+    io = GzHostIO{bytes + G.d_off, G.dn, nullptr, 0, nullptr, 0};
+    bz_prepare(io, T);
+    // find
+    P.start[0] = 0;
+    for (uint64_t k = 1; k < nc; k++) P.start[k] = gz_find<MEM>(io, T, G, k);
+    // count
+    for (uint64_t k = 0; k < nc; k++) {
+        if (P.start[k] == kGzNoStart) continue;
+        const GzRun R = gz_run<GZ_COUNT, MEM>(io, T, G, k, P.start[k], P.start.data(), 0);
+        P.link[k] = R.link; P.text_len[k] = R.text; P.end_bit[k] = R.end_bit; P.reason[k] = R.reason; P.n_ends[k] = R.n_ends; P.last_end[k] = R.last_end;
+    }
+    // chain
+    GzVerdict gv{};
+    const int32_t why = gz_chain(P.M, P.start.data(), P.link.data(), P.text_len.data(), P.end_bit.data(), P.reason.data(), P.chain.data(), &P.n_chain,
+                                 &P.total, &gv, MEM);
+    const int status = gz_plan_fill(plan, nc, P.start.data(), P.link.data(), P.text_len.data(), P.n_chain);
+    if (status) return status;
+    if (why != BZ_OK) return gz_decline(v, gv.reason, gv.member, gv.in_pos);
+    *n_text = P.total;
+    if (out_cap < P.total) return CRASS_ERR_OVERFLOW;
+    return -1;
+}
+
+// the serial run; MEM: members mode (gunzip_core.h), `members` (may be NULL) gets the member table
+template <bool MEM>
+static int gz_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
+                           crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
+{
+    auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) { return gz_decline(v, reason, member, in_pos); };
     BzTables *T = new (std::nothrow) BzTables;
     if (!T) return CRASS_ERR_OOM;
     int status = CRASS_OK;
     try {
-        std::vector<uint64_t> start(nc, kGzNoStart), text_len(nc, 0), end_bit(nc, 0), off(nc, 0);
-        std::vector<uint32_t> link(nc, GZ_LINK_NONE), chain(nc, 0);
-        std::vector<int32_t> reason(nc, 0);
-        std::vector<uint32_t> n_ends(nc, 0);
-        std::vector<uint64_t> last_end(nc, 0);
-        GzHostIO io{bytes + G.d_off, G.dn, nullptr, 0, nullptr, 0};
-        bz_prepare(io, *T);
-        // find
-        start[0] = 0;
-        for (uint64_t k = 1; k < nc; k++) start[k] = gz_find<MEM>(io, *T, G, k);
-        // count
-        for (uint64_t k = 0; k < nc; k++) {
-            if (start[k] == kGzNoStart) continue;
-            const GzRun R = gz_run<GZ_COUNT, MEM>(io, *T, G, k, start[k], start.data(), 0);
-            link[k] = R.link; text_len[k] = R.text; end_bit[k] = R.end_bit; reason[k] = R.reason; n_ends[k] = R.n_ends; last_end[k] = R.last_end;
-        }
-        // chain
-        uint64_t n_chain = 0, total = 0;
-        GzVerdict gv{};
-        const int32_t why = gz_chain(M, start.data(), link.data(), text_len.data(), end_bit.data(), reason.data(), chain.data(), &n_chain, &total, &gv, MEM);
-        status = gz_plan_fill(plan, nc, start.data(), link.data(), text_len.data(), n_chain);
-        if (status) { delete T; return status; }
-        if (why != BZ_OK) { delete T; return decline(gv.reason, gv.member, gv.in_pos); }
-        *n_text = total;
-        if (out_cap < total) { delete T; return CRASS_ERR_OVERFLOW; }
+        GzHostIO io{};
+        GzHostCount P;
+        status = gz_front_host<MEM>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, members, v, io, *T, P);
+        if (status >= 0) { delete T; return status; }
+        status = CRASS_OK;
+        const GzMember &M = P.M;
+        const GzGeom &G = M.G;
+        const uint64_t nc = G.nc, n_chain = P.n_chain, total = P.total;
+        const std::vector<uint64_t> &start = P.start, &text_len = P.text_len, &end_bit = P.end_bit, &last_end = P.last_end;
+        const std::vector<uint32_t> &chain = P.chain, &n_ends = P.n_ends;
+        std::vector<uint64_t> off(nc, 0);
         // decode
         std::vector<uint16_t> sym(total ? total : 1);
         std::vector<uint8_t> win(n_chain * (uint64_t)kGzWindow);
@@ -171,7 +199,86 @@ static int gz_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chun
     return status;
 }
 
+// the distributed rule (a group's ranks) as a serial run: range after range, each one its own symbols and symbolic windows from
+// an identity entry; the entry window of a range is composed from the range before it, which on the host has just finished
+static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal, uint8_t *out,
+                                  uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    BzTables *T = new (std::nothrow) BzTables;
+    if (!T) return CRASS_ERR_OOM;
+    int status = CRASS_OK;
+    try {
+        GzHostIO io{};
+        GzHostCount P;
+        status = gz_front_host<false>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, nullptr, v, io, *T, P);
+        if (status >= 0) { delete T; return status; }
+        status = CRASS_OK;
+        const GzGeom &G = P.M.G;
+        const uint64_t n = P.n_chain;
+        std::vector<uint64_t> off(n + 1, 0), e0(n_ranges + 1, n), e1(n_ranges + 1, n);      // (a range behind the last: no elements)
+        for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + P.text_len[P.chain[i]];
+        if (!gz_ranges(off.data(), n, n_ranges, nominal, e0.data(), e1.data())) { delete T; *n_text = 0; return CRASS_ERR_INVALID_ARG; }
+        std::vector<uint32_t> crc_part(n, 0);
+        std::vector<uint8_t> entry(kGzWindow, 0), next_entry(kGzWindow, 0), win(kGzWindow, 0);
+        std::vector<uint16_t> sym, wsym(kGzWindow), wsym_before(kGzWindow);
+        uint64_t done = 0;                              // elements [0, done) have their text: every part from the first range that holds it
+        for (uint32_t r = 0; r < n_ranges && status == CRASS_OK; r++) {
+            const uint64_t a = e0[r], b = e1[r];
+            // decode: the range's elements as symbols, element i at sym[off[i] - off[a]]
+            sym.assign(off[b] - off[a] + 1, 0);
+            for (uint64_t i = a; i < b; i++) {
+                const uint64_t k = P.chain[i];
+                io.sym = sym.data() + (off[i] - off[a]); io.cap = P.text_len[k];
+                (void)gz_run<GZ_DECODE, false>(io, *T, G, k, P.start[k], nullptr, P.end_bit[k]);
+            }
+            // element after element: the symbolic window in front of it (of a, the identity), resolved through the entry window; its
+            // text.  The window in front of b is made too where the next range starts there
+            const uint64_t last = std::min(b, n - 1);
+            for (uint64_t i = a; i <= last && status == CRASS_OK; i++) {
+                if (i > a) {
+                    wsym.swap(wsym_before);
+                    const uint16_t *sp = sym.data() + (off[i - 1] - off[a]);
+                    for (uint32_t e = 0; e < kGzWindow; e++) wsym[e] = gz_window_entry_sym(sp, off[i] - off[i - 1], i > a + 1 ? wsym_before.data() : nullptr, e);
+                    for (uint32_t e = 0; e < kGzWindow; e++) win[e] = gz_window_resolve(wsym[e], a ? entry.data() : nullptr);
+                }
+                const std::vector<uint8_t> &w = i > a ? win : entry;
+                if (i == e0[r + 1]) next_entry = w;
+                if (i >= b || i < done) continue;
+                const uint64_t k = P.chain[i];
+                uint32_t c = 0xFFFFFFFFu;
+                for (uint64_t p = off[i]; p < off[i + 1]; p++) {
+                    const uint32_t x = gz_narrow(sym[p - off[a]], i ? w.data() : nullptr, off[i]);
+                    if (x > 0xFFu) { status = gz_decline(v, BZ_MARKER, k, G.d_off + (P.start[k] >> 3)); break; }
+                    out[p] = (uint8_t)x;
+                    c = T->crc_tab[(c ^ x) & 0xFFu] ^ (c >> 8);
+                }
+                crc_part[i] = off[i + 1] > off[i] ? ~c : 0u;
+            }
+            done = std::max(done, b);
+            entry.swap(next_entry);
+        }
+        if (status == CRASS_OK && done != n) status = CRASS_ERR_STATE;      // (never expected: tiling ranges leave no element out)
+        uint32_t crc = 0;
+        for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
+        if (status == CRASS_OK && crc != P.M.crc) status = gz_decline(v, BZ_CRC, 0, 0);
+    } catch (const std::bad_alloc &) { status = CRASS_ERR_OOM; }
+    delete T;
+    return status;
+}
+
 extern "C" {
+
+int crass_gzip_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal, uint8_t *out,
+                                   uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    if (n_ranges < 1 || n_ranges > 64) {
+        if (v) memset(v, 0, sizeof(*v));
+        if (plan) memset(plan, 0, sizeof(*plan));
+        if (n_text) *n_text = 0;
+        return CRASS_ERR_INVALID_ARG;
+    }
+    return gz_inflate_ranges_host(bytes, n_bytes, chunk_bytes, n_ranges, nominal, out, out_cap, n_text, plan, v);
+}
 
 void crass_gzip_plan_free(crass_gzip_plan *p)
 {

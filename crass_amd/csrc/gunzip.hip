@@ -12,12 +12,21 @@
 // k_gz_decode_members and k_gz_narrow_members (the same bodies with the rule's MEM parameter on; narrow then leaves the CRC to)
 //   k_gz_member_crc  a wave per piece of text (cut at member boundaries and every 64 KB inside a member): 64 lane slices, as
 //                    k_gz_narrow's 256
+// A range of the file (a rank of a group, crass_hip_group_inflate_gzip): the same kernels over the chunks [k0, k1) and the chain
+// elements [e0, e0 + n_chain) of a job that holds only the bytes d[in_lo, in_hi) its runs may read (GzJob; a whole file is the
+// full range), and in place of k_gz_windows, which needs the window in front of the range's first element,
+//   k_gz_windows_sym     ONE workgroup walks the RANGE's elements from the identity: windows of bytes and references into the
+//                        unknown entry window (gz_window_entry_sym)
+//   k_gz_window_resolve  a workgroup per element, once the host has composed the ranges' entry windows: symbolic to bytes
 // As in inflate.hip: symbol decoding is serial, all 64 lanes run it with the same values; tables (BzTables, 7 KB per wave) are in
 // LDS, the text in HBM; what a lane wrote is read by lanes of the SAME wave only, so io.sync() is a wavefront-scope fence plus a
 // wave barrier (see inflate.hip for the memory model's wording); no workgroup barrier inside the serial decode.
 // Scratch is the engine's: 2 bytes per text byte (sym) plus 32 KB per chain element (win), taken from dev_alloc and given back
 // before the call returns.
-// Bounds: input is read inside d[0, dn) only (in() and gz_survives check the index); a decode wave writes sym[off[i], off[i+1])
+// Bounds: input is read inside d[in_lo, in_hi) only, a whole file's d[0, dn) (at() cuts a run's input to it, in() and gz_survives
+// check the index); find writes start[k0, k1), count link / text_len / end_bit / reason [k0, k1); k_gz_windows_sym writes
+// wsym[32768 i, 32768 (i + 1)) for i in [1, n_win]; k_gz_window_resolve writes win[32768 i, 32768 (i + 1)) for i in
+// [1, n_win]; a decode wave writes sym[off[i], off[i+1])
 // only (put() checks) and in members mode ends[slot[i], slot[i+1]) (end() checks); k_gz_member_crc reads out[piece[q], piece[q+1])
 // and writes crc_piece[q]; k_gz_windows writes win[32768 i, 32768 (i + 1)); k_gz_narrow writes out[off[i], off[i+1]).
 #include "gunzip_launch.h"
@@ -32,7 +41,13 @@ static constexpr int kGzNarrowThreads = 256, kGzWindowThreads = 1024;
 struct GzWaveIO {
     const uint8_t *d; uint64_t dn; const uint8_t *src; uint32_t n_in; uint16_t *sym; uint64_t cap; uint32_t lane;
     GzEnd *ends = nullptr; uint32_t ends_cap = 0;         // (members mode)
-    __device__ __forceinline__ void at(uint64_t b0, uint32_t n) { src = d + b0; n_in = n; }
+    uint64_t lo = 0, hi = 0;                              // the staged bytes d[lo, hi), hi <= dn (a whole file: [0, dn))
+    // (a run's input is cut to what is staged: a job stages what its runs may read, so nothing is cut that a whole-file run reads)
+    __device__ __forceinline__ void at(uint64_t b0, uint32_t n)
+    {
+        src = d + b0;
+        n_in = b0 < lo || b0 >= hi ? 0u : (uint32_t)(hi - b0 < n ? hi - b0 : n);
+    }
     __device__ __forceinline__ uint32_t in(uint32_t i) const { return i < n_in ? (uint32_t)src[i] : 0u; }
     __device__ __forceinline__ void put(uint64_t p, uint32_t s) { if (p < cap) sym[p] = (uint16_t)s; }
     __device__ __forceinline__ uint32_t get(uint64_t p) const { return p < cap ? (uint32_t)sym[p] : 0u; }
@@ -44,10 +59,11 @@ struct GzWaveIO {
         __builtin_amdgcn_wave_barrier();
     }
     // lane l answers for position base + l
-    __device__ __forceinline__ uint64_t survivors(uint64_t base, uint64_t hi, uint64_t limit) const
+    __device__ __forceinline__ uint64_t survivors(uint64_t base, uint64_t top, uint64_t limit) const
     {
-        return (uint64_t)__ballot(gz_survives(d, dn, base + lane, hi, limit) ? 1 : 0);
+        return (uint64_t)__ballot(gz_survives(d, hi, base + lane, top, limit, lo) ? 1 : 0);
     }
+    // (members mode only, whole files only: reads d / dn unclipped — never used on a job that holds a part of the file)
     __device__ __forceinline__ uint64_t header_survivors(uint64_t base, uint64_t hi, uint64_t limit) const
     {
         return (uint64_t)__ballot(gz_survives_header(d, dn, base + lane, hi, limit) ? 1 : 0);
@@ -61,9 +77,10 @@ template <bool MEM> __device__ __forceinline__ void gz_find_waves(const GzJob &J
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    io.lo = J.in_lo; io.hi = J.in_hi;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
-    for (uint64_t k = (uint64_t)blockIdx.x * kGzWaves + wv; k < J.G.nc; k += n_waves) {
+    for (uint64_t k = J.k0 + (uint64_t)blockIdx.x * kGzWaves + wv; k < J.k1; k += n_waves) {
         const uint64_t s = k ? gz_find<MEM>(io, T, J.G, k) : 0;
         if (lane == 0) J.start[k] = s;
         io.sync();
@@ -85,9 +102,10 @@ template <bool MEM> __device__ __forceinline__ void gz_count_waves(const GzJob &
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    io.lo = J.in_lo; io.hi = J.in_hi;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
-    for (uint64_t k = (uint64_t)blockIdx.x * kGzWaves + wv; k < J.G.nc; k += n_waves) {
+    for (uint64_t k = J.k0 + (uint64_t)blockIdx.x * kGzWaves + wv; k < J.k1; k += n_waves) {
         const uint64_t s = J.start[k];
         GzRun R{BZ_OK, GZ_LINK_NONE, 0, 0, 0, 0};
         if (s != kGzNoStart) R = gz_run<GZ_COUNT, MEM>(io, T, J.G, k, s, J.start, 0);
@@ -112,6 +130,7 @@ template <bool MEM> __device__ __forceinline__ void gz_decode_waves(const GzJob 
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
+    io.lo = J.in_lo; io.hi = J.in_hi;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
     for (uint64_t i = (uint64_t)blockIdx.x * kGzWaves + wv; i < J.n_chain; i += n_waves) {
@@ -134,15 +153,50 @@ __global__ __launch_bounds__(64 * kGzWaves) void k_gz_decode_members(GzJob J)
 }
 
 // element i's window needs element i - 1's: one workgroup, a barrier between elements
+// A job that starts behind the file's element 0 (e0 > 0: the elements a rank of a group adds later, gzip_kept_grow) is SEEDED: win[0,
+// 32768) holds the resolved window in front of its first element, and with n_win = n_chain the walk also leaves the window
+// behind its last element in slot n_chain, the seed of the next walk.  Writes win[32768 i, 32768 (i + 1)) for i in [1, n_chain),
+// or [1, n_win] where n_win is set
 __global__ __launch_bounds__(kGzWindowThreads) void k_gz_windows(GzJob J)
 {
-    for (uint64_t i = 1; i < J.n_chain; i++) {
+    const uint64_t n = J.n_win ? J.n_win + 1 : J.n_chain;
+    for (uint64_t i = 1; i < n; i++) {
         const uint16_t *sp = J.sym + J.off[i - 1];
         const uint64_t L = J.off[i] - J.off[i - 1];
-        const uint8_t *wp = i > 1 ? J.win + (i - 1) * (uint64_t)kGzWindow : nullptr;
+        const uint8_t *wp = J.e0 + i > 1 ? J.win + (i - 1) * (uint64_t)kGzWindow : nullptr;
         uint8_t *w = J.win + i * (uint64_t)kGzWindow;
         for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_entry(sp, L, wp, e);
         __syncthreads();                                  // (workgroup scope: the next element reads what all threads wrote)
+    }
+}
+
+// the same walk over a range of the chain whose entry window is unknown: symbolic windows (gz_window_entry_sym) from the
+// identity in front of the range's first element; ONE workgroup, a barrier between elements.  Writes wsym[32768 i, 32768 (i + 1))
+// for i in [1, n_win] only
+__global__ __launch_bounds__(kGzWindowThreads) void k_gz_windows_sym(GzJob J)
+{
+    for (uint64_t i = 1; i <= J.n_win; i++) {
+        const uint16_t *sp = J.sym + J.off[i - 1];
+        const uint64_t L = J.off[i] - J.off[i - 1];
+        const uint16_t *wp = i > 1 ? J.wsym + (i - 1) * (uint64_t)kGzWindow : nullptr;
+        uint16_t *w = J.wsym + i * (uint64_t)kGzWindow;
+        for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_entry_sym(sp, L, wp, e);
+        __syncthreads();                                  // (workgroup scope: the next element reads what all threads wrote)
+    }
+}
+
+// once the entry window has arrived in win[0, 32768): a workgroup per element, grid-stride, no order among them.  Writes
+// win[32768 i, 32768 (i + 1)) for i in [1, n_win] only: win has n_win + 1 slots, the last one the window behind the range's last
+// element where n_win = n_chain (a range that starts at the file's element 0 has no
+// entry window: its markers point in front of the text and read 0, as in gz_window_entry)
+__global__ __launch_bounds__(kGzWindowThreads) void k_gz_window_resolve(GzJob J)
+{
+    const uint8_t *entry = J.e0 ? J.win : nullptr;
+    const uint64_t n = J.n_win + 1;
+    for (uint64_t i = 1 + blockIdx.x; i < n; i += gridDim.x) {
+        const uint16_t *ws = J.wsym + i * (uint64_t)kGzWindow;
+        uint8_t *w = J.win + i * (uint64_t)kGzWindow;
+        for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_resolve(ws[e], entry);
     }
 }
 
@@ -155,7 +209,7 @@ template <bool MEM> __device__ __forceinline__ void gz_narrow_groups(const GzJob
         __syncthreads();
         const uint64_t o0 = J.off[i], L = J.off[i + 1] - o0;
         const uint16_t *sp = J.sym + o0;
-        const uint8_t *win = i ? J.win + i * (uint64_t)kGzWindow : nullptr;
+        const uint8_t *win = J.e0 + i ? J.win + i * (uint64_t)kGzWindow : nullptr;
         const uint64_t m0 = MEM ? J.m0[i] : 0;
         // vector by vector of the OUTPUT's aligned space: [lead, lead + L) of it is the element's
         const uint32_t lead = (uint32_t)(((uintptr_t)J.out + o0) & 15u);
@@ -257,7 +311,7 @@ static hipError_t gz_grid(uint64_t n_items, int per_group, int groups_per_cu, un
 hipError_t launch_gz_find(const GzJob &J, hipStream_t st, bool members)
 {
     unsigned grid = 1;
-    hipError_t e = gz_grid(J.G.nc, kGzWaves, 4, &grid);
+    hipError_t e = gz_grid(J.k1 - J.k0, kGzWaves, 4, &grid);
     if (e != hipSuccess) return e;
     if (members) CRASS_LAUNCH(k_gz_find_members, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
     else CRASS_LAUNCH(k_gz_find, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
@@ -267,7 +321,7 @@ hipError_t launch_gz_find(const GzJob &J, hipStream_t st, bool members)
 hipError_t launch_gz_count(const GzJob &J, hipStream_t st, bool members)
 {
     unsigned grid = 1;
-    hipError_t e = gz_grid(J.G.nc, kGzWaves, 4, &grid);
+    hipError_t e = gz_grid(J.k1 - J.k0, kGzWaves, 4, &grid);
     if (e != hipSuccess) return e;
     if (members) CRASS_LAUNCH(k_gz_count_members, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
     else CRASS_LAUNCH(k_gz_count, dim3(grid), dim3(64 * kGzWaves), 0, st, J);
@@ -287,8 +341,26 @@ hipError_t launch_gz_decode(const GzJob &J, hipStream_t st, bool members)
 
 hipError_t launch_gz_windows(const GzJob &J, hipStream_t st)
 {
-    if (J.n_chain < 2) return hipSuccess;
+    if ((J.n_win ? J.n_win + 1 : J.n_chain) < 2) return hipSuccess;
     CRASS_LAUNCH(k_gz_windows, dim3(1), dim3(kGzWindowThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_windows_sym(const GzJob &J, hipStream_t st)
+{
+    if (J.n_win == 0) return hipSuccess;
+    CRASS_LAUNCH(k_gz_windows_sym, dim3(1), dim3(kGzWindowThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+hipError_t launch_gz_window_resolve(const GzJob &J, hipStream_t st)
+{
+    const uint64_t n = J.n_win + 1;
+    if (n < 2) return hipSuccess;
+    unsigned grid = 1;
+    hipError_t e = gz_grid(n - 1, 1, 2, &grid);
+    if (e != hipSuccess) return e;
+    CRASS_LAUNCH(k_gz_window_resolve, dim3(grid), dim3(kGzWindowThreads), 0, st, J);
     return hipGetLastError();
 }
 

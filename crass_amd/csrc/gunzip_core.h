@@ -19,6 +19,16 @@
 //   windows  the 32 KB in front of chain element i from element i - 1's last symbols and its window, in chain order
 //   narrow   symbols to bytes through each element's window; per-element CRC-32 parts, combined with bz_crc_shift
 //
+// Ranges (a group's ranks, crass_hip_group_inflate_gzip; serially crass_gzip_inflate_ranges_host): chunk k is rank k N / nc's for
+// find and count, a rank holds only d[nominal[k0] / 8, gz_input_end(k1 - 1)) for them; the chain's text offsets are then what a
+// BGZF index is to the shard code: rank r takes the elements that hold its range of the text (gz_elements_for, gz_ranges), and
+//   windows  a rank cannot know the 32 KB in front of its first element before the rank in front has finished, so it walks its
+//            elements from an IDENTITY entry window: gz_window_entry_sym, entries are bytes or 0x8000 | index into that window
+//   compose  (host) entry(r + 1) = gz_window_resolve(the symbolic window rank r holds in front of rank r + 1's first element,
+//            entry(r)), in rank order; a rank that starts in the same element, or holds none, passes its entry on
+//   resolve  every symbolic window through the rank's entry window: the bytes `windows` would have made; narrow as above.  An
+//            element's text and CRC-32 part are taken from the first rank that holds it
+//
 // kGzMaxSpan = 32: a chunk gives up when it has gone through 32 chunks' worth of input without meeting a later chunk's start.
 // zlib ends a block after at most 32 767 symbols (memLevel 9; 16 383 at the default 8), which for FASTA / FASTQ text is 30 to
 // 50 KB of input and at most ~120 KB for text of any kind: 32 chunks of the smallest size (4096 bytes: 128 KB) get through such a
@@ -162,10 +172,11 @@ CRASS_HD inline bool gz_prefilter(uint64_t lo, uint64_t hi)
     }
     return kraft == 128u;
 }
-// position p of chunk range [.., hi) may be a start
-CRASS_HD inline bool gz_survives(const uint8_t *d, uint64_t dn, uint64_t p, uint64_t hi, uint64_t limit)
+// position p of chunk range [.., hi) may be a start.  d[d_lo, dn) is read, bytes beyond read 0 (a job that holds a part of the
+// file passes the end of what it holds as dn: 11 bytes from p on, all inside what a chunk's runs may read)
+CRASS_HD inline bool gz_survives(const uint8_t *d, uint64_t dn, uint64_t p, uint64_t hi, uint64_t limit, uint64_t d_lo = 0)
 {
-    if (p >= hi || p + 64 >= limit) return false;
+    if (p >= hi || p + 64 >= limit || (p >> 3) < d_lo) return false;
     const uint64_t b = p >> 3;
     const uint32_t sh = (uint32_t)(p & 7u);
     uint64_t a = 0, c = 0;
@@ -420,6 +431,15 @@ CRASS_HD inline GzRun gz_run(IO &io, BzTables &T, const GzGeom &G, uint64_t k, u
     return R;
 }
 
+// the end of the input a run of chunk k may read (gz_run's b0 + n_in): d[.., gz_input_end) is what a job stages for its last chunk
+CRASS_HD inline uint64_t gz_input_end(const GzGeom &G, uint64_t k)
+{
+    const uint64_t stop_bit = gz_nominal(G, k + kGzMaxSpan);
+    if (stop_bit >= G.dn * 8) return G.dn;
+    const uint64_t e = (stop_bit >> 3) + kGzSlack;
+    return e < G.dn ? e : G.dn;
+}
+
 // start[k] for k >= 1: positions in ascending order, 64 at a time through gz_survives, the survivors through the trial
 // (members mode: block starts and member starts alike, whichever comes first)
 template <bool MEM = false, class IO> CRASS_HD inline uint64_t gz_find(IO &io, BzTables &T, const GzGeom &G, uint64_t k)
@@ -451,6 +471,61 @@ CRASS_HD inline uint8_t gz_window_entry(const uint16_t *sp, uint64_t L, const ui
     }
     return wp ? wp[w + L] : (uint8_t)0;
 }
+// ---- a RANGE of the chain (a rank of a group): symbolic windows, composed afterwards ----
+// A range walks its elements [e0, e1) without knowing the 32 KB in front of element e0 (its ENTRY window: the range before has
+// not finished).  Its windows are symbolic: an entry is a byte (< 0x100) or 0x8000 | index into the entry window.
+// gz_window_entry_sym is gz_window_entry in that form: entry w of the window in front of an element, from the element before it
+// (its L symbols sp, its own symbolic window wp_sym; NULL: that element is the range's first, its window is the identity, so a
+// marker of its symbols and an entry that lies in front of it, w + L, stay markers)
+CRASS_HD inline uint16_t gz_window_entry_sym(const uint16_t *sp, uint64_t L, const uint16_t *wp_sym, uint32_t w)
+{
+    const uint64_t back = kGzWindow - w;
+    uint32_t idx = (uint32_t)(w + L);                     // (< kGzWindow where it is used: back > L)
+    if (back <= L) {
+        const uint32_t s = sp[L - back];
+        if (s < 0x8000u) return (uint16_t)(s & 0xFFu);
+        idx = s & 0x7FFFu;
+    }
+    return wp_sym ? wp_sym[idx] : (uint16_t)(0x8000u | idx);
+}
+// a symbolic entry through the range's entry window (NULL: the range starts at the file's element 0, entries in front of the
+// text read 0 as in gz_window_entry).  Also the composition step: the entry window of the next range is the resolve of the
+// symbolic window this range holds in front of that range's first element
+CRASS_HD inline uint8_t gz_window_resolve(uint16_t sym_entry, const uint8_t *entry_bytes)
+{
+    return sym_entry < 0x8000u ? (uint8_t)sym_entry : entry_bytes ? entry_bytes[sym_entry & 0x7FFFu] : (uint8_t)0;
+}
+// the elements that hold the text range [a, b), off[n + 1] the chain's text offsets: [*e0, *e1).  bgzf_members_for's rule
+// (fastx_shards.h) with elements in place of members: an element cut by a position is both neighbours', elements without text
+// are taken where they lie at b and from element 0 when a is 0, so ranges that tile the text leave no element out, and for
+// consecutive ranges e0 <= e0' <= e1
+inline void gz_elements_for(const uint64_t *off, uint64_t n, uint64_t a, uint64_t b, uint64_t *e0, uint64_t *e1)
+{
+    auto ends_behind = [&](uint64_t x) {                  // the first element that ends behind x, or n
+        uint64_t lo = 0, hi = n;
+        while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (off[mid + 1] > x) hi = mid; else lo = mid + 1; }
+        return lo;
+    };
+    *e0 = a == 0 ? 0 : ends_behind(a);
+    uint64_t e = ends_behind(b);
+    if (e < n && off[e] < b) e++;
+    *e1 = e;
+}
+// the element ranges of n_ranges >= 1 text ranges that tile [0, T = off[n]), cut at nominal[n_ranges - 1] (NULL: T k / n_ranges):
+// e0 / e1 [n_ranges].  false: cuts that decrease or lie beyond T
+inline bool gz_ranges(const uint64_t *off, uint64_t n, uint32_t n_ranges, const uint64_t *nominal, uint64_t *e0, uint64_t *e1)
+{
+    const uint64_t T = off[n];
+    uint64_t a = 0;
+    for (uint32_t r = 0; r < n_ranges; r++) {
+        const uint64_t b = r + 1 == n_ranges ? T : nominal ? nominal[r] : T / n_ranges * (r + 1) + T % n_ranges * (r + 1) / n_ranges;
+        if (b < a || b > T) return false;
+        gz_elements_for(off, n, a, b, &e0[r], &e1[r]);
+        a = b;
+    }
+    return true;
+}
+
 // a symbol of the element whose text starts at byte t0, through its window: the byte, or 0x100 for a marker that points in front
 // of the text — in members mode in front of the member that holds the element's first byte, whose text starts at m0 <= t0
 CRASS_HD inline uint32_t gz_narrow(uint32_t s, const uint8_t *win, uint64_t t0, uint64_t m0 = 0)

@@ -354,6 +354,53 @@ def gzip_inflate_host(buf, chunk_bytes=0, out_cap=None, with_plan=False):
     return (out, plan) if with_plan else out
 
 
+def _gzip_guess_cap(a):
+    """room for the text a gzip trailer promises (ISIZE, the file's last 4 bytes)"""
+    return int.from_bytes(a[-4:].tobytes(), "little") if len(a) >= 18 else 0
+
+
+def _gzip_ranges_call(fn, call, a, out_cap, with_plan):
+    """One call of a ranges inflate (call(out_ptr, cap, n_text, plan, verdict) -> status) with room for the text the trailer
+    promises, a second one where the text is larger; results and errors as gzip_inflate_host."""
+    lib = _abi.load()
+    cap = _gzip_guess_cap(a) if out_cap is None else int(out_cap)
+    while True:
+        out = np.zeros(cap, np.uint8)
+        n_text, ver, pc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC()
+        try:
+            st = call(out.ctypes.data if cap else None, cap, C.byref(n_text), C.byref(pc), C.byref(ver))
+            plan = GzipPlan(pc)
+        finally:
+            lib.crass_gzip_plan_free(C.byref(pc))
+        if st == 8 and out_cap is None:
+            cap = int(n_text.value)
+            continue
+        break
+    if st == 2:
+        e = BgzfDeclined(st, fn, ver)
+        e.plan = plan
+        raise e
+    if st == 8:
+        e = CrassError(st, fn)
+        e.n_text, e.out, e.plan = int(n_text.value), out, plan
+        raise e
+    _chk(st, fn)
+    out = out[:int(n_text.value)]
+    return (out, plan) if with_plan else out
+
+
+def gzip_inflate_ranges_host(buf, n_ranges, chunk_bytes=0, nominal=None, out_cap=None, with_plan=False):
+    """gzip_inflate_host by the rule a group's ranks run (crass_gzip_inflate_ranges_host; no GPU needed): the text cut into
+    n_ranges ranges at nominal (n_ranges - 1 text positions; None: even), every range's elements decoded and their windows walked
+    symbolically, the entry windows composed in order.  Results and errors as gzip_inflate_host, for every n_ranges."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    nom = _nominal_arg(nominal, int(n_ranges))
+    ptr = a.ctypes.data if len(a) else None
+    return _gzip_ranges_call("crass_gzip_inflate_ranges_host", lambda o, cap, n, p, v: lib.crass_gzip_inflate_ranges_host(
+        ptr, len(a), int(chunk_bytes), int(n_ranges), nom.ctypes.data if nom is not None and len(nom) else None, o, cap, n, p, v), a, out_cap, with_plan)
+
+
 class GzipMembers:
     """The members of a plain gzip file (crass_gzip_members), as numpy copies: n_members, in_off (uint64 [n + 1]: the file byte of
     each member's header, in_off[n] the file's size) and text_off (uint64 [n + 1]: member m is text[text_off[m] : text_off[m + 1]])."""
@@ -503,6 +550,25 @@ def _nominal_arg(nominal, n_ranks):
     if len(a) != n_ranks - 1:
         raise ValueError("nominal needs n_ranks - 1 cuts")
     return a
+
+
+def fastx_files_shards_host_gzip(files, n_ranks, nominal=None, fastq_class=0, gzip_mode=1, chunk_bytes=0):
+    """fastx_files_shards_host for a job whose plain gzip files are taken as their text (crass_fastx_files_shards_host_gzip; no
+    GPU needed): gzip_mode 0 is fastx_files_shards_host, the decline of plain gzip included; else such a file is
+    gzip_inflate_host's text (chunk_bytes: 0 the default chunk), and one that does not inflate is the job's decline."""
+    lib = _abi.load()
+    arrs, ptrs, lens = _files_args(files)
+    nom = _nominal_arg(nominal, int(n_ranks))
+    v = _abi.FastxShardsC()
+    st = lib.crass_fastx_files_shards_host_gzip(ptrs, lens.ctypes.data_as(_abi.u64p), len(arrs), int(n_ranks),
+                                                nom.ctypes.data if nom is not None and len(nom) else None, int(fastq_class), int(gzip_mode),
+                                                int(chunk_bytes), C.byref(v))
+    try:
+        if st not in (0, 2):
+            raise CrassError(st, "crass_fastx_files_shards_host_gzip")
+        return FastxShards(v)
+    finally:
+        lib.crass_fastx_shards_free(C.byref(v))
 
 
 def fastx_files_shards_host(files, n_ranks, nominal=None, fastq_class=0):
@@ -1866,6 +1932,41 @@ class SearchGroup:
         four-line cut declines for a FASTQ's shape runs once more with every FASTQ file cut at the records reachable from its
         line 0.  Also set on every rank's context, so fetch_quality reads by the wrapped rule."""
         self._chk(self.lib.crass_hip_group_set_fastq_class(self.h, int(fastq_class)), "crass_hip_group_set_fastq_class")
+
+    def inflate_gzip(self, buf, chunk_bytes=0, nominal=None, out_cap=None, with_plan=False):
+        """The text of a plain (single-member) gzip file's bytes, inflated across the ranks (crass_hip_group_inflate_gzip): chunks
+        dealt over the ranks for find and count, every rank the elements of its range of the text (nominal: size - 1 text
+        positions; None: even) with symbolic windows, the entry windows composed on the host.  Host memory in, host memory out;
+        results and errors as gzip_inflate_ranges_host with n_ranges = the group's size."""
+        a = _bytes_arg(buf)
+        nom = _nominal_arg(nominal, self.n)
+        ptr = a.ctypes.data if len(a) else None
+        return _gzip_ranges_call("crass_hip_group_inflate_gzip", lambda o, cap, n, p, v: self.lib.crass_hip_group_inflate_gzip(
+            self.h, ptr, len(a), int(chunk_bytes), nom.ctypes.data if nom is not None and len(nom) else None, o, cap, n, p, v), a, out_cap, with_plan)
+
+    def set_gzip_on_device(self, mode, chunk_bytes=0):
+        """load_fastx_files takes plain single-member gzip files (crass_hip_group_set_gzip_on_device): 0 / False, the default,
+        declines them as before; anything else takes such a file as a BGZF file is taken, chain elements for members: an index step
+        (find, count, the chain) before the shards are cut, then every rank inflates the elements of its pieces and keeps their text
+        on its device; tails and wrapped-mode margins pull further elements through a seeded window walk.  chunk_bytes: 0 the
+        default chunk."""
+        self._chk(self.lib.crass_hip_group_set_gzip_on_device(self.h, int(mode), int(chunk_bytes)), "crass_hip_group_set_gzip_on_device")
+
+    def gzip_counters(self):
+        """(gzip files taken, chunks, chain elements, elements inflated by a further rank, compressed bytes uploaded, of them
+        uploaded before) of the last inflate_gzip, or summed over the gzip files the last load_fastx_files took — the elements its
+        seeded walks added count as inflated by a further rank (crass_hip_group_gzip_counters)."""
+        out = np.zeros(6, np.uint64)
+        self._chk(self.lib.crass_hip_group_gzip_counters(self.h, out.ctypes.data), "crass_hip_group_gzip_counters")
+        return tuple(int(x) for x in out)
+
+    def gzip_ms(self, rank):
+        """HIP-event milliseconds of a rank's kernels in the last inflate_gzip, or for the last gzip file of the last
+        load_fastx_files (crass_hip_group_gzip_ms): a dict of find, count, decode, windows_sym, resolve, narrow, and tail_windows:
+        the seeded window walks of the last load_fastx_files, summed (0 after inflate_gzip); measured at stage timing level >= 1."""
+        out = np.zeros(7, np.float32)
+        self._chk(self.lib.crass_hip_group_gzip_ms(self.h, int(rank), out.ctypes.data), "crass_hip_group_gzip_ms")
+        return dict(zip(("find", "count", "decode", "windows_sym", "resolve", "narrow", "tail_windows"), (float(x) for x in out)))
 
     def load_counters(self):
         """(attempts, files cut by the wrapped rule, margin doublings, chain look-ups) of the last load_fastx_files

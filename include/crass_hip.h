@@ -805,6 +805,17 @@ void crass_gzip_plan_free(crass_gzip_plan *plan);
  * crass_gzip_plan_free.  CRASS_ERR_INVALID_ARG: NULL n_text, NULL bytes / out with a size. */
 int  crass_gzip_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_text,
                              crass_gzip_plan *plan, crass_bgzf_verdict *v);
+/* replaces: gzread (SeqUtils.cpp:100-126) — the rule as the ranks of a group run it (crass_hip_group_inflate_gzip), serially on the
+ * host, no GPU needed: what that call is tested against.  The text [0, T) is cut into n_ranges (1 .. 64) ranges at nominal
+ * (n_ranges - 1 non-decreasing text positions <= T; NULL: T k / n_ranges); a range takes the chain elements that hold its text (an
+ * element cut by a position is both neighbours'), decodes them to symbols and walks their windows SYMBOLICALLY from an identity
+ * entry window (an entry is a byte or a reference into the unknown 32 KB in front of the range's first element); the ranges'
+ * entry windows are composed in order, each range resolves and narrows, and every element's text and CRC-32 part are taken from
+ * the first range that holds it.  Text, plan, verdict and the overflow / argument protocol are crass_gzip_inflate_host's, field
+ * for field, for every n_ranges and every cut.  Also CRASS_ERR_INVALID_ARG: n_ranges outside 1 .. 64, cuts that decrease or lie
+ * beyond T (found once T is known: the plan is filled then). */
+int  crass_gzip_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal,
+                                    uint8_t *out, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v);
 /* replaces: gzread (SeqUtils.cpp:100-126) for compressed bytes that are in HBM: d_in and d_out are caller-owned DEVICE pointers of any
  * alignment.  k_gz_find (a lane per bit position), k_gz_count and k_gz_decode (a wave per chunk), k_gz_windows, k_gz_narrow.
  * Scratch: 2 bytes per text byte plus 32 KB per chain element, given back before the call returns.  Results as
@@ -1033,6 +1044,14 @@ void crass_fastx_shards_free(crass_fastx_shards *s);
  * CRASS_ERR_INVALID_ARG also for a class outside 0..1. */
 int  crass_fastx_files_shards_host_class(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
                                          const uint64_t *nominal, int fastq_class, crass_fastx_shards *out);
+/* replaces: the same, for a job whose plain gzip files are taken as their text.  gzip_mode 0 is
+ * crass_fastx_files_shards_host_class, the decline of a plain gzip file (reason 10) included.  gzip_mode != 0: a file that starts
+ * with the gzip magic and that crass_bgzf_index_host declines as not BGZF is replaced by crass_gzip_inflate_host's text
+ * (chunk_bytes: 0 is the default chunk) and the job is then cut and judged like any other; a file that does not inflate is the
+ * job's decline (decline_file, bgzf = that call's verdict; several members: 13) unless a file in front of it is declined. */
+int  crass_fastx_files_shards_host_gzip(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
+                                        const uint64_t *nominal, int fastq_class, int gzip_mode, uint64_t chunk_bytes,
+                                        crass_fastx_shards *out);
 /* what a rank knows about a byte range of one file's text before the cuts are known (the probe of csrc/fastx_scan.h), serially
  * on the host and by k_fx_cut_probe on bytes in HBM (d_bytes: a DEVICE pointer of any alignment; one aligned 16-byte load per 16
  * bytes, nothing outside the vectors that cover the range is read).  left_is_ls: position 0 of the range is a line start.
@@ -1061,7 +1080,8 @@ float crass_hip_last_cut_chain_ms(const crass_hip_ctx *ctx);
  *   Names that repeat across ranks: after the merge of a step every rank looks the names of the other ranks' pass-1 records up
  *   in its own table, and its namesakes are marked found before pass 2 (readsFound, libcrispr.cpp:138,411).
  * declined (CRASS_ERR_UNSUPPORTED): the verdict of crass_fastx_files_shards_host in out; no rank holds reads, and the group is as
- *   after a failed load (step: CRASS_ERR_STATE).  Plain gzip is declined (one deflate stream cannot be cut).
+ *   after a failed load (step: CRASS_ERR_STATE).  Plain gzip is declined unless crass_hip_group_set_gzip_on_device is on: then
+ *   the ranks inflate such a file together first (one deflate stream IS cut: crass_hip_group_inflate_gzip).
  * FASTQ class 1 (crass_hip_group_set_fastq_class; default 0: everything above, unchanged): the load takes at most two attempts.
  *   Attempt 1 is the load above; accepted, it is the load (a four-line job takes the same kernels as with class 0).  Attempt 2
  *   runs only when attempt 1 declines a file whose format is '@' with one of the reasons 3 .. 9: every '@' file is then cut and
@@ -1072,8 +1092,8 @@ float crass_hip_last_cut_chain_ms(const crass_hip_ctx *ctx);
  *   end doubles its margin and builds again; the slices go through the wrapped scan as a single context's class 1 does.
  *   exact: out equals crass_fastx_files_shards_host_class(.., 1, ..)'s, accepted or declined, and the reads, header lines,
  *   quality and comments are those of crass_hip_load_fastx_files with class 1 on the same files.
- *   Line indices of a piece are 32-bit: a piece of more lines is CRASS_ERR_UNSUPPORTED.  Plain gzip stays declined, and
- *   crass_hip_set_gzip_on_device has no counterpart in a group.
+ *   Line indices of a piece are 32-bit: a piece of more lines is CRASS_ERR_UNSUPPORTED.  A plain gzip file taken
+ *   by crass_hip_group_set_gzip_on_device (the group's counterpart of crass_hip_set_gzip_on_device) is cut by its text like any other.
  * Other errors: CRASS_ERR_INVALID_ARG — a NULL group, n_files == 0, NULL arrays, a NULL bytes[f] with n_bytes[f] > 0, pad_uniform
  * outside 0..2, nominal cuts that decrease or lie beyond T; CRASS_ERR_HIP / CRASS_ERR_OOM from a rank. */
 int  crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files,
@@ -1086,6 +1106,52 @@ int  crass_hip_group_set_fastq_class(crass_hip_group *g, int fastq_class);
  * files cut by the wrapped rule (the '@' files in front of the first declined file, in attempt 2), out[2] margin doublings and
  * out[3] chain look-ups, both summed over the ranks. */
 int  crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4]);
+/* ---- one plain gzip file inflated across the ranks of a group ----
+ * replaces: gzread (SeqUtils.cpp:100-126) for a .gz input of ONE member whose bytes are in HOST memory; the text comes back to host
+ * memory (out_host, out_cap bytes).  One deflate stream is cut without any rank waiting for the rank in front of it
+ * (gunzip_core.h, crass_gzip_inflate_ranges_host): chunk k of the nc chunks is rank k N / nc's for k_gz_find and k_gz_count (a
+ * rank stages only the compressed bytes its chunks' runs may read), the host gathers the starts between the two and walks the chain;
+ * rank r then takes the chain elements that hold its range of the text (nominal: N - 1 text positions, NULL: T k / N), fetches
+ * what their runs still need, decodes them (k_gz_decode) and walks their windows symbolically (k_gz_windows_sym); the host composes
+ * the ranks' entry windows, 32 768 look-ups per rank; every rank resolves (k_gz_window_resolve) and narrows (k_gz_narrow).  An
+ * element's text and CRC-32 part come from the first rank that holds it; the host joins the parts over the chain.
+ * exact: text, plan and verdict are crass_gzip_inflate_ranges_host's with n_ranges = the group's size and the same cuts, which are
+ * crass_gzip_inflate_host's; the overflow protocol is crass_hip_inflate_gzip_device's (CRASS_ERR_OVERFLOW with *n_text, known
+ * before anything is stored).  A file of several members is declined (13).  Scratch goes back before the call returns; the
+ * ranks' resident sets and the group's state are untouched.  Errors: CRASS_ERR_INVALID_ARG — a NULL group or n_text, NULL bytes /
+ * out_host with a size, cuts that decrease or lie beyond the text; CRASS_ERR_HIP / CRASS_ERR_OOM from a rank. */
+int  crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
+                                  uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v);
+/* crass_hip_group_load_fastx_files takes a plain gzip file of ONE member: mode 0 (the default) such a file is declined as before
+ * (reason 10); CRASS_GZIP_ON_DEVICE_ONE_MEMBER, or any other non-zero value: a file that starts with the gzip magic and that
+ * crass_bgzf_index_host declines as not BGZF goes through an index step before the shards are cut (chunk_bytes: 0 the default
+ * chunk, else clamped to 4096 .. 4 MB): every rank runs k_gz_find and k_gz_count on its share of the chunks, rank 0 walks the
+ * chain.  The text's size and the element index (start bit, end bit and text offset of every chain element) are then known and
+ * take a BGZF index's place, elements for members.  With the nominal cuts known every rank inflates the elements that hold its
+ * pieces, in two halves: k_gz_decode and k_gz_windows_sym, then — the entry windows composed on the host in rank order —
+ * k_gz_window_resolve and k_gz_narrow; the text stays on the rank's device, only compressed bytes cross the bus.  Elements a rank
+ * needs later (the tail up to the next rank's cut, a wrapped-mode margin that doubles) are decoded and their windows walked by
+ * k_gz_windows from the resolved window the rank keeps behind its last element (a seeded walk), through the one seam that inflates
+ * BGZF members for the shard code.  Every element's CRC-32 part comes from the first rank that narrowed it, rank 0 joins them over
+ * the chain.  A file that does not inflate — a chain decline (several members: 13), a wrong CRC-32 (9), an unresolved marker (14,
+ * the smallest element over the ranks) — is the job's decline (bgzf: crass_gzip_inflate_host's verdict) unless a file in front
+ * of it offends.  A rank keeps the compressed bytes it staged and fetches only what its elements still need, while the file is
+ * the one it staged last: every file's index step runs before any file is inflated, so only the LAST gzip file of a job gains
+ * from it (of a paired R1 / R2 job, R1's bytes go up twice).  Memory: a rank holds its text three times at the peak — what it
+ * keeps of every gzip file until the load ends, the stage buffer, the arena — beside 2 bytes per text byte of symbols and 96 KB
+ * per chain element of windows while a file is inflated.  exact: out equals crass_fastx_files_shards_host_gzip's with the same class,
+ * mode and chunk.  (No reference counterpart.)  CRASS_ERR_INVALID_ARG: a NULL group, a negative mode. */
+int  crass_hip_group_set_gzip_on_device(crass_hip_group *g, int mode, uint64_t chunk_bytes);
+/* the last crass_hip_group_inflate_gzip that got as far as the decode step (else zeros), or summed over the gzip files the last
+ * crass_hip_group_load_fastx_files took (a load that took none: zeros): out[0] gzip files taken, out[1] chunks,
+ * out[2] chain elements, out[3] how many times an element was inflated by a further rank (the elements the ranks hold, summed,
+ * minus out[2], plus in a load the elements its seeded walks added), out[4] compressed bytes uploaded, summed over the ranks, out[5] those of them that an upload had brought
+ * already (to any rank).  (No reference counterpart.) */
+int  crass_hip_group_gzip_counters(const crass_hip_group *g, uint64_t out[6]);
+/* HIP-event milliseconds on rank `rank`'s stream of its kernels in the last crass_hip_group_inflate_gzip: out[0 .. 6) find, count,
+ * decode, symbolic windows, resolve, narrow (of a load: its last gzip file's); out[6] the seeded window walks (k_gz_windows) of the
+ * last files load, summed; measured when that rank's stage timing level is >= 1, else 0.  (No reference counterpart.) */
+int  crass_hip_group_gzip_ms(const crass_hip_group *g, int rank, float out[7]);
 /* replaces: ReadHolder's RH_Header / RH_Comment and RH_Qual / RH_IsFasta for a group loaded by crass_hip_group_load_fastx_files:
  * crass_hip_fetch_header_lines_device / crass_hip_fetch_quality_device on every rank's arena, over the whole job.  read_idx are
  * GLOBAL read indices (0 .. n_reads), routed to the rank that holds them; the records come back in the caller's order in one

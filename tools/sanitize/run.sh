@@ -79,3 +79,7 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinc
 python3 tools/sanitize/shards_class_dump.py $out/shards_class > /dev/null
 $out/shards_class_asan $out/shards_class/* > $out/report_shards_class.txt 2> $out/sanitizer_shards_class.txt || true
 echo "shards by class: $(tail -1 $out/report_shards_class.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_shards_class.txt || true) sanitizer reports"
+# the plain-gzip host rule by ranges (crass_gzip_inflate_ranges_host: a group's distributed inflate as a serial run) over built-in streams, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/gunzip.cpp tools/sanitize/gzip_ranges_main.cpp -o $out/gzip_ranges_asan -lz
+$out/gzip_ranges_asan > $out/report_gzip_ranges.txt 2> $out/sanitizer_gzip_ranges.txt || true
+echo "gzip by ranges: $(tail -1 $out/report_gzip_ranges.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_gzip_ranges.txt || true) sanitizer reports"
