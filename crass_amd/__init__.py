@@ -11,7 +11,7 @@ from .engine import (ConsensusResult, CrassError, FastxFile, FastxIndex, PackedR
                      ResidentReads, Text, pack_code4, pack_layout, packed_arrays,
                      FastxDeclined, FastxLayout, fastx_header_ids, find_names, names_of, comments_of, fastx_scan_host,
                      FastxFilesDeclined, FastxFilesLayout, fastx_files_scan_host, FastxShards, fastx_files_shards_host, fastx_cut_probe_host,
-                     BgzfDeclined, BgzfIndex, bgzf_index, bgzf_inflate_host, GzipPlan, gzip_inflate_host, GzipMembers, gzip_inflate_members_host, gzip_inflate_ranges_host, fastx_files_shards_host_gzip)
+                     BgzfDeclined, BgzfIndex, bgzf_index, bgzf_inflate_host, GzipPlan, gzip_inflate_host, GzipMembers, gzip_inflate_members_host, gzip_inflate_ranges_host, gzip_inflate_members_ranges_host, fastx_files_shards_host_gzip)
 
 __all__ = ["ConsensusResult", "consensus", "ksw_batch", "smith_waterman_batch", "CrassError", "FastxFile", "FastxIndex", "PackedReads", "SearchEngine", "SearchGroup", "default_params", "search_pipeline", "search_pipeline_group", "merge_host", "merge_rebuild", "build_outputs", "dr_slots",
-           "ResidentReads", "Text", "pack_code4", "pack_layout", "packed_arrays", "FastxDeclined", "FastxLayout", "fastx_header_ids", "find_names", "names_of", "comments_of", "fastx_scan_host", "FastxFilesDeclined", "FastxFilesLayout", "fastx_files_scan_host", "FastxShards", "fastx_files_shards_host", "fastx_cut_probe_host", "BgzfDeclined", "BgzfIndex", "bgzf_index", "bgzf_inflate_host", "GzipPlan", "gzip_inflate_host", "GzipMembers", "gzip_inflate_members_host", "gzip_inflate_ranges_host", "fastx_files_shards_host_gzip", "stream_fastx", "synth_packed", "synth_spec", "unpack_ascii", "load", "LIB_PATH", "SYMBOLS"]
+           "ResidentReads", "Text", "pack_code4", "pack_layout", "packed_arrays", "FastxDeclined", "FastxLayout", "fastx_header_ids", "find_names", "names_of", "comments_of", "fastx_scan_host", "FastxFilesDeclined", "FastxFilesLayout", "fastx_files_scan_host", "FastxShards", "fastx_files_shards_host", "fastx_cut_probe_host", "BgzfDeclined", "BgzfIndex", "bgzf_index", "bgzf_inflate_host", "GzipPlan", "gzip_inflate_host", "GzipMembers", "gzip_inflate_members_host", "gzip_inflate_ranges_host", "gzip_inflate_members_ranges_host", "fastx_files_shards_host_gzip", "stream_fastx", "synth_packed", "synth_spec", "unpack_ascii", "load", "LIB_PATH", "SYMBOLS"]

@@ -349,11 +349,17 @@ SYMBOLS = {
     "crass_hip_group_load_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "crass_gzip_inflate_ranges_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64), C.POINTER(GzipPlanC), C.POINTER(BgzfVerdict)]),
+    "crass_gzip_inflate_members_ranges_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                         C.POINTER(C.c_uint64), C.POINTER(GzipPlanC), C.POINTER(GzipMembersC), C.POINTER(BgzfVerdict)]),
     "crass_fastx_files_shards_host_gzip": (C.c_int, [C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_uint64,
                                                      C.POINTER(FastxShardsC)]),
     "crass_hip_group_inflate_gzip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.POINTER(C.c_uint64), C.POINTER(GzipPlanC), C.POINTER(BgzfVerdict)]),
     "crass_hip_group_set_gzip_on_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    "crass_hip_group_inflate_gzip_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                       C.POINTER(C.c_uint64), C.POINTER(GzipPlanC), C.POINTER(GzipMembersC), C.POINTER(BgzfVerdict)]),
+    "crass_hip_group_gzip_members_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "crass_hip_group_gzip_members_ms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "crass_hip_group_gzip_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "crass_hip_group_gzip_ms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "crass_hip_group_load_fastx_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p, C.c_uint32, C.c_int, C.c_void_p,

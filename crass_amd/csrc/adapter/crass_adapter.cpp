@@ -859,8 +859,9 @@ int searchAndRecruit(const Vecstr &seqFiles, const options &opts, ReadMap *mRead
             if (!wrapped && strcmp(e, "four-line")) throw input_error(std::string("crass [ERROR]: CRASS_DEVICE_FASTQ=") + e + " is neither wrapped nor four-line");
             chk(crass_hip_group_set_fastq_class(made.g, wrapped ? 1 : 0), "crass_hip_group_set_fastq_class");
         }
-        // CRASS_DEVICE_GZIP=1 (or 2, taken as 1): a plain single-member gzip input is inflated by the group's devices together
-        // (crass_hip_group_set_gzip_on_device); without it such an input is declined
+        // CRASS_DEVICE_GZIP=1: a plain single-member gzip input is inflated by the group's devices together
+        // (crass_hip_group_set_gzip_on_device); without it such an input is declined.  The value goes through as it is: 2 takes
+        // plain gzip of any number of members (CRASS_GZIP_ON_DEVICE_MEMBERS), 1 declines further members
         if (const char *e = getenv("CRASS_DEVICE_GZIP")) chk(crass_hip_group_set_gzip_on_device(made.g, atoi(e), 0), "crass_hip_group_set_gzip_on_device");
         crass_fastx_shards sh;
         const int s = crass_hip_group_load_fastx_files(made.g, M.ptr.data(), M.len.data(), (uint32_t)M.ptr.size(), 2, nullptr, &sh);

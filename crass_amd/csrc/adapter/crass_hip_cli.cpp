@@ -48,8 +48,9 @@ static void usage()
                  "                 FASTA / FASTQ) is an error\n"
                  "  CRASS_DEVICE_GZIP=1   with CRASS_INGEST=device: a plain (single-member) gzip input is inflated on the GPU too\n"
                  "  CRASS_DEVICE_GZIP=2   ... and plain gzip of any number of members (cat of .gz files, gzip's >>)\n"
-                 "                 with CRASS_INGEST=devices: 1 (or 2, taken as 1) has the GPUs of the group inflate a plain\n"
-                 "                 single-member gzip input together before it is cut into shards (default: such an input is an error)\n"
+                 "                 with CRASS_INGEST=devices: 1 has the GPUs of the group inflate a plain single-member gzip input\n"
+                 "                 together before it is cut into shards, 2 plain gzip of any number of members too (1 declines\n"
+                 "                 further members; default: such an input is an error)\n"
                  "  CRASS_DEVICE_FASTQ=wrapped   with CRASS_INGEST=device or devices: FASTQ records whose sequence or quality runs over\n"
                  "                 several lines, and blank lines between records and at the end, are read too (default: four-line);\n"
                  "                 devices: the shards are cut at the records reachable from a file's first line\n";

@@ -240,8 +240,9 @@ struct Ingest {
     std::vector<GzKept> gz_kept;
     StageTimer<2> tm_gzt;
     float gzr_tail_ms = 0; uint64_t gzr_tail_elements = 0;
-    StageTimer<12> tm_gzr;
+    StageTimer<14> tm_gzr;
     float gzr_ms[6] = {0, 0, 0, 0, 0, 0};
+    float gzr_crc_ms = 0;                    // members mode: k_gz_member_crc over the rank's pieces, marks 12 and 13
     std::vector<std::pair<uint64_t, uint64_t>> gzr_uploads;
     int gzip_on_device = 0;                  // crass_hip_set_gzip_on_device: crass_hip_load_fastx_files takes plain gzip (CRASS_GZIP_ON_DEVICE_*)
     // crass_hip_fetch_text (k_fetch_text, pack.hip): the records' indices / flags / offsets and the text on the device, kept from

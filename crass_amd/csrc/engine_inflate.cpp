@@ -308,9 +308,11 @@ GzJob gzr_job(crass_hip_ctx *c, const GzRangesFile &F)
     const uint64_t nc = F.M.G.nc;
     GzJob J{};
     J.d = reinterpret_cast<const uint8_t *>((uintptr_t)I.z_raw.p - I.gzr_lo); J.G = F.M.G;
-    J.in_lo = I.gzr_lo; J.in_hi = I.gzr_hi;
+    // (members mode: a rank whose find runs see the region's end stages the 8 bytes behind it too; they are no part of the region)
+    J.in_lo = I.gzr_lo; J.in_hi = std::min(I.gzr_hi, F.M.G.dn); J.in_tail = I.gzr_hi >= F.M.G.dn + 8 ? 1u : 0u;
     J.start = I.gz_a64.p; J.text_len = I.gz_a64.p + nc; J.end_bit = I.gz_a64.p + 2 * nc;
     J.link = I.gz_a32.p; J.reason = reinterpret_cast<int32_t *>(I.gz_a32.p + nc);
+    if (F.members) { J.last_end = I.gz_a64.p + 3 * nc; J.n_ends = I.gz_a32.p + 2 * nc; }
     return J;
 }
 
@@ -323,17 +325,20 @@ int gzip_rank_find(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
     (void)hipSetDevice(c->device);
     I.gzr_lo = I.gzr_hi = 0; I.gzr_file = nullptr;
     for (float &m : I.gzr_ms) m = 0;
+    I.gzr_crc_ms = 0;
     const GzGeom &G = F.M.G;
     const uint64_t nc = G.nc, k0 = F.k_lo(r), k1 = F.k_lo(r + 1);
     try {
-        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_a32.ensure(2 * nc));
+        HIPCHK(c, I.gz_a64.ensure(4 * nc)); HIPCHK(c, I.gz_a32.ensure(3 * nc));
         if (k0 >= k1) return CRASS_OK;
-        const int ss = gzr_stage(c, F, gz_nominal(G, k0) >> 3, gz_input_end(G, k1 - 1));
+        uint64_t in_end = gz_input_end(G, k1 - 1);
+        if (F.members && in_end == G.dn) in_end += 8;       // (io.tail(): a member's start whose first block is final and ends the region)
+        const int ss = gzr_stage(c, F, gz_nominal(G, k0) >> 3, in_end);
         if (ss) return ss;
         GzJob J = gzr_job(c, F);
         J.k0 = k0; J.k1 = k1;
         HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 0));
-        HIPCHK(c, launch_gz_find(J, c->stream));
+        HIPCHK(c, launch_gz_find(J, c->stream, F.members));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
         HIPCHK(c, hipMemcpyAsync(F.start.data() + k0, J.start + k0, (k1 - k0) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -353,9 +358,13 @@ int gzip_rank_count(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
     J.k0 = k0; J.k1 = k1;
     HIPCHK(c, hipMemcpyAsync(J.start, F.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));      // (every rank's starts: a run links to any later chunk)
     HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 2));
-    HIPCHK(c, launch_gz_count(J, c->stream));
+    HIPCHK(c, launch_gz_count(J, c->stream, F.members));
     HIPCHK(c, I.tm_gzr.mark(c->stream));
     const uint64_t n = k1 - k0;
+    if (F.members) {
+        HIPCHK(c, hipMemcpyAsync(F.n_ends.data() + k0, J.n_ends + k0, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.last_end.data() + k0, J.last_end + k0, n * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(c, hipMemcpyAsync(F.text_len.data() + k0, J.text_len + k0, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(F.end_bit.data() + k0, J.end_bit + k0, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(F.link.data() + k0, J.link + k0, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -364,6 +373,8 @@ int gzip_rank_count(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
     HIPCHK(c, I.tm_gzr.elapsed(2, 3, &I.gzr_ms[1]));
     return CRASS_OK;
 }
+
+static uint64_t gzr_max_pieces(const GzRangesFile &F, uint64_t a, uint64_t b) { return (F.off[b] - F.off[a]) / kGzCrcPiece + (F.slot[b] - F.slot[a]) + 3; }
 
 // the job of the rank's elements [a, b): the chain arrays of gz_b64 / gz_b32, sym and out as the places of text byte 0
 static GzJob gzr_element_job(crass_hip_ctx *c, const GzRangesFile &F, uint64_t a, uint64_t b)
@@ -375,6 +386,10 @@ static GzJob gzr_element_job(crass_hip_ctx *c, const GzRangesFile &F, uint64_t a
     J.off = I.gz_b64.p; J.chain = I.gz_b32.p; J.crc_part = I.gz_b32.p + ne;
     J.sym = reinterpret_cast<uint16_t *>((uintptr_t)I.gz_sym.p - 2 * F.off[a]);
     J.win = I.gz_win.p; J.wsym = I.gz_wsym.p;
+    if (F.members) {                                    // [off (ne + 1) | slot (ne + 1) | m0 (ne + 1) | the rank's pieces]
+        J.slot = I.gz_b64.p + (ne + 1); J.m0 = I.gz_b64.p + 2 * (ne + 1);
+        J.ends = reinterpret_cast<GzEnd *>(I.gz_ends.p);
+    }
     return J;
 }
 
@@ -391,20 +406,37 @@ int gzip_rank_decode(crass_hip_ctx *c, GzRangesFile &F, uint32_t r)
         const int ss = gzr_stage(c, F, F.start[F.chain[a]] >> 3, gz_input_end(G, F.chain[b - 1]));
         if (ss) return ss;
         const uint64_t n_win = std::min(b, F.n_chain - 1) - a;
-        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1)); HIPCHK(c, I.gz_b32.ensure(2 * ne));
+        // (members mode: room for the rank's pieces too, which the finish step uploads behind what this step leaves here: at most
+        // one per 64 KB of its text, one per member it touches and one where its own text begins)
+        const uint64_t n_rec = F.members ? F.slot[b] - F.slot[a] : 0, max_p = F.members ? gzr_max_pieces(F, a, b) : 0;
+        HIPCHK(c, I.gz_a64.ensure(4 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1 + (F.members ? 2 * (ne + 1) + max_p + 1 : 0))); HIPCHK(c, I.gz_b32.ensure(2 * ne + max_p));
         HIPCHK(c, I.gz_sym.ensure(F.off[b] - F.off[a] + 1)); HIPCHK(c, I.gz_win.ensure(std::max(ne, n_win + 1) * (uint64_t)kGzWindow));
         HIPCHK(c, I.gz_wsym.ensure((n_win + 1) * (uint64_t)kGzWindow));
+        if (F.members) HIPCHK(c, I.gz_ends.ensure(3 * (n_rec ? n_rec : 1)));
         GzJob J = gzr_element_job(c, F, a, b);
+        if (F.members) {
+            // (m0 also of the element behind the last one where the walk makes its window: a + n_win <= n_chain - 1)
+            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(J.slot), F.slot.data() + a, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(J.m0), F.m0.data() + a, (n_win + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        }
         HIPCHK(c, hipMemcpyAsync(J.start, F.start.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(J.end_bit, F.end_bit.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(I.gz_b64.p, F.off.data() + a, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(I.gz_b32.p, F.chain.data() + a, ne * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, I.tm_gzr.begin(c->timing_level >= 1, c->stream, 4));
-        HIPCHK(c, launch_gz_decode(J, c->stream));
+        HIPCHK(c, launch_gz_decode(J, c->stream, F.members));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
-        HIPCHK(c, launch_gz_windows_sym(J, c->stream));
+        HIPCHK(c, launch_gz_windows_sym(J, c->stream, F.members));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
+        // members mode: the records of the elements no rank in front holds, into the file's table (ranges of F.ends apart)
+        const uint64_t f = std::max(a, F.first[r]);
+        if (F.members && f < b && F.slot[b] > F.slot[f]) {
+            static_assert(sizeof(GzEnd) == 24 && alignof(GzEnd) == 8, "GzEnd is three words");
+            if (F.ends.size() < F.slot[b]) return CRASS_ERR_STATE;
+            HIPCHK(c, hipMemcpyAsync(F.ends.data() + F.slot[f], J.ends + (F.slot[f] - F.slot[a]), (F.slot[b] - F.slot[f]) * sizeof(GzEnd), hipMemcpyDeviceToHost,
+                                     c->stream));
+        }
         // the window in front of the next rank's first element: this range's where that element lies behind its first one
         const uint64_t next = F.e0[r + 1];
         if (next > a && next < F.n_chain) {
@@ -438,17 +470,41 @@ int gzip_rank_finish(crass_hip_ctx *c, GzRangesFile &F, uint32_t r, uint8_t *out
         HIPCHK(c, launch_gz_window_resolve(J, c->stream));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
-        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream, F.members));
         HIPCHK(c, I.tm_gzr.mark(c->stream));
-        // what no rank in front holds: its text to the caller, its CRC parts to the host
         const uint64_t f = std::max(a, F.first[r]);
+        // members mode: the CRC-32 of the pieces of the text this rank holds first, [q0, q1) of the file's pieces, their cuts
+        // relative to the rank's text base (a rank that holds nothing first, or a table that is no table: none)
+        uint64_t q0 = 0, q1 = 0;
+        if (F.members && F.table_ok && f < b) {
+            q0 = std::lower_bound(F.piece.begin(), F.piece.begin() + F.n_pieces, F.off[f]) - F.piece.begin();
+            q1 = std::lower_bound(F.piece.begin(), F.piece.begin() + F.n_pieces, F.off[b]) - F.piece.begin();
+        }
+        std::vector<uint64_t> rel;                      // (read by an upload: lives until the stream is waited for below)
+        I.gzr_crc_ms = 0;
+        if (q1 > q0) {
+            // (never expected: a piece is one rank's, and the decode step left room for them)
+            if (F.piece[q1] > F.off[b] || F.crc_piece.size() < q1 || q1 - q0 > gzr_max_pieces(F, a, b)) return CRASS_ERR_STATE;
+            rel.resize(q1 - q0 + 1);
+            for (uint64_t q = q0; q <= q1; q++) rel[q - q0] = F.piece[q] - F.off[a];
+            GzJob P = J;
+            P.out = I.z_text.p + 16; P.n_pieces = q1 - q0;
+            P.piece = I.gz_b64.p + 3 * (ne + 1); P.crc_piece = I.gz_b32.p + 2 * ne;
+            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(P.piece), rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, I.tm_gzr.mark(c->stream));
+            HIPCHK(c, launch_gz_member_crc(P, c->stream));
+            HIPCHK(c, I.tm_gzr.mark(c->stream));
+            HIPCHK(c, hipMemcpyAsync(F.crc_piece.data() + q0, P.crc_piece, (q1 - q0) * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        // what no rank in front holds: its text to the caller, its CRC parts to the host
         if (f < b) {
             if (out && F.off[b] > F.off[f]) HIPCHK(c, hipMemcpyAsync(out + F.off[f], J.out + F.off[f], F.off[b] - F.off[f], hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(F.crc_part.data() + f, J.crc_part + (f - a), (b - f) * 4, hipMemcpyDeviceToHost, c->stream));
+            if (!F.members) HIPCHK(c, hipMemcpyAsync(F.crc_part.data() + f, J.crc_part + (f - a), (b - f) * 4, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipMemcpyAsync(I.z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, I.tm_gzr.elapsed(8, 9, &I.gzr_ms[4])); HIPCHK(c, I.tm_gzr.elapsed(10, 11, &I.gzr_ms[5]));
+        if (q1 > q0) HIPCHK(c, I.tm_gzr.elapsed(12, 13, &I.gzr_crc_ms));
         const uint64_t w = I.z_h_verdict.p[0];
         if (w != kBzNoOffence) F.bad[r] = a + w;
         if (keep) {
@@ -478,10 +534,15 @@ static int gzip_kept_grow(crass_hip_ctx *c, const GzRangesFile &F, Ingest::GzKep
     DevBuf<uint8_t> grown;
     auto run = [&]() -> int {
         HIPCHK(c, grown.ensure(F.off[b] - F.off[K.e0] + 32));
-        HIPCHK(c, I.gz_a64.ensure(3 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1)); HIPCHK(c, I.gz_b32.ensure(2 * ne));
+        HIPCHK(c, I.gz_a64.ensure(4 * nc)); HIPCHK(c, I.gz_b64.ensure(ne + 1 + (F.members ? 2 * (ne + 1) : 0))); HIPCHK(c, I.gz_b32.ensure(2 * ne));
         HIPCHK(c, I.gz_sym.ensure(F.off[b] - F.off[a] + 1)); HIPCHK(c, I.gz_win.ensure(std::max(ne, n_win + 1) * (uint64_t)kGzWindow));
         HIPCHK(c, I.z_verdict.ensure(1)); HIPCHK(c, I.z_h_verdict.ensure(1));
         GzJob J = gzr_element_job(c, F, a, b);
+        if (F.members) {
+            // the members rule with the elements' m0; the GzEnd records these runs meet again are in the table already: no slots
+            J.slot = nullptr; J.ends = nullptr;
+            HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t *>(J.m0), F.m0.data() + a, ne * 8, hipMemcpyHostToDevice, c->stream));
+        }
         J.out = reinterpret_cast<uint8_t *>((uintptr_t)grown.p + 16 - F.off[K.e0]);
         J.verdict = I.z_verdict.p;
         if (F.off[a] > F.off[K.e0]) HIPCHK(c, hipMemcpyAsync(grown.p + 16, K.text.p + 16, F.off[a] - F.off[K.e0], hipMemcpyDeviceToDevice, c->stream));
@@ -491,11 +552,11 @@ static int gzip_kept_grow(crass_hip_ctx *c, const GzRangesFile &F, Ingest::GzKep
         HIPCHK(c, hipMemcpyAsync(I.gz_b64.p, F.off.data() + a, (ne + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(I.gz_b32.p, F.chain.data() + a, ne * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(J.verdict, 0xFF, 8, c->stream));
-        HIPCHK(c, launch_gz_decode(J, c->stream));
+        HIPCHK(c, launch_gz_decode(J, c->stream, F.members));
         HIPCHK(c, I.tm_gzt.begin(c->timing_level >= 1, c->stream));
         HIPCHK(c, launch_gz_windows(J, c->stream));
         HIPCHK(c, I.tm_gzt.mark(c->stream));
-        HIPCHK(c, launch_gz_narrow(J, c->stream));
+        HIPCHK(c, launch_gz_narrow(J, c->stream, F.members));
         if (b < F.n_chain) HIPCHK(c, hipMemcpyAsync(K.seed.p, J.win + ne * (uint64_t)kGzWindow, kGzWindow, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(I.z_h_verdict.p, J.verdict, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -567,6 +628,8 @@ void gzip_rank_release(crass_hip_ctx *c)
     release_gzip(c); release_bgzf(c);                   // (the staged bytes, the text and the verdict word are the BGZF inflate's)
     c->in.gzr_lo = c->in.gzr_hi = 0; c->in.gzr_file = nullptr;
 }
+
+float gzip_rank_member_crc_ms(const crass_hip_ctx *c) { return c ? c->in.gzr_crc_ms : 0.0f; }
 
 void gzip_rank_report(const crass_hip_ctx *c, float ms[6], std::vector<std::pair<uint64_t, uint64_t>> *uploads)
 {

@@ -1,6 +1,7 @@
 // fastx_shards_gzip.cpp — the record-aligned shards of a job on the host (fastx_scan.cpp) when plain gzip files are taken
-// (crass_hip_group_set_gzip_on_device): such a file's text is crass_gzip_inflate_host's (gunzip.cpp), then the job is cut and
-// judged as crass_fastx_files_shards_host_class does.  Host-only C++17, no GPU needed.
+// (crass_hip_group_set_gzip_on_device): such a file's text is crass_gzip_inflate_host's (gunzip.cpp; with
+// CRASS_GZIP_ON_DEVICE_MEMBERS crass_gzip_inflate_members_host's, a file of any number of members), then the job is cut and judged
+// as crass_fastx_files_shards_host_class does.  Host-only C++17, no GPU needed.
 #include "../../include/crass_hip.h"
 #include "gunzip_core.h"
 
@@ -23,6 +24,7 @@ extern "C" int crass_fastx_files_shards_host_gzip(const uint8_t *const *bytes, c
         std::vector<const uint8_t *> b(bytes, bytes + n_files);
         std::vector<uint64_t> n(n_bytes, n_bytes + n_files);
         uint32_t nf = n_files;
+        const bool members = gzip_mode == CRASS_GZIP_ON_DEVICE_MEMBERS;
         crass_bgzf_verdict bad;
         memset(&bad, 0, sizeof(bad));
         for (uint32_t f = 0; f < nf; f++) {
@@ -33,10 +35,15 @@ extern "C" int crass_fastx_files_shards_host_gzip(const uint8_t *const *bytes, c
             crass_bgzf_index_free(&ix);
             if (!plain) continue;                         // (BGZF, or a decline that is the BGZF index's own)
             uint64_t nt = 0;
-            int s = crass_gzip_inflate_host(b[f], n[f], chunk_bytes, nullptr, 0, &nt, nullptr, &bad);
+            // (CRASS_GZIP_ON_DEVICE_MEMBERS: a file of any number of members, crass_gzip_inflate_members_host's text and verdict)
+            auto inflate = [&](uint8_t *o, uint64_t cap) {
+                return members ? crass_gzip_inflate_members_host(b[f], n[f], chunk_bytes, o, cap, &nt, nullptr, nullptr, &bad)
+                               : crass_gzip_inflate_host(b[f], n[f], chunk_bytes, o, cap, &nt, nullptr, &bad);
+            };
+            int s = inflate(nullptr, 0);
             if (s == CRASS_ERR_OVERFLOW || s == CRASS_OK) {
                 text[f].resize(nt + 1);
-                s = crass_gzip_inflate_host(b[f], n[f], chunk_bytes, text[f].data(), nt, &nt, nullptr, &bad);
+                s = inflate(text[f].data(), nt);
             }
             if (s == CRASS_ERR_UNSUPPORTED) { nf = f; break; }
             if (s) return s;

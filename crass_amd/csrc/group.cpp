@@ -241,7 +241,9 @@ struct crass_hip_group {
         int status = 0;
         crass::GzVerdict v{};
         uint64_t cnt[6] = {0, 0, 0, 0, 0, 0};
+        uint64_t cnt_members[4] = {0, 0, 0, 0};   // crass_hip_group_gzip_members_counters
         std::vector<std::array<float, 6>> ms;
+        std::vector<float> crc_ms;              // per rank, members mode: k_gz_member_crc of the last finish step
     } GZ;
     int gzip_mode = 0;                          // crass_hip_group_set_gzip_on_device
     uint64_t gzip_chunk = 0;
@@ -631,13 +633,19 @@ int gzip_chain_host(crass_hip_group *g)
     const uint64_t nc = Z.M.G.nc;
     Z.chain.assign(nc, 0);
     const int32_t bad = crass::gz_chain(Z.M, Z.start.data(), Z.link.data(), Z.text_len.data(), Z.end_bit.data(), Z.reason.data(), Z.chain.data(),
-                                        &Z.n_chain, &Z.n_text, &J.v);
+                                        &Z.n_chain, &Z.n_text, &J.v, Z.members);
     if (bad != crass::BZ_OK) { J.status = CRASS_ERR_UNSUPPORTED; return CRASS_OK; }
     if (J.do_inflate && J.out_cap < Z.n_text) { J.status = CRASS_ERR_OVERFLOW; return CRASS_OK; }
     const uint64_t n = Z.n_chain;
     Z.off.assign(n + 1, 0);
     for (uint64_t i = 0; i < n; i++) Z.off[i + 1] = Z.off[i] + Z.text_len[Z.chain[i]];
     Z.crc_part.assign(n, 0);
+    if (Z.members) {                                    // the places of the GzEnd records and every element's member start
+        Z.slot.assign(n + 1, 0); Z.m0.assign(n, 0);
+        crass::gz_places(Z.chain.data(), n, Z.text_len.data(), Z.n_ends.data(), Z.last_end.data(), Z.off.data(), Z.slot.data(), Z.m0.data());
+        Z.ends.assign(Z.slot[n], crass::GzEnd{0, 0, 0, 0});
+        Z.table_ok = false; Z.n_pieces = 0;
+    }
     if (!J.do_inflate) return CRASS_OK;                 // (a files load: the ranges follow once the cuts are known)
     const uint32_t N = (uint32_t)g->n;
     Z.e0.assign(N + 1, n); Z.e1.assign(N + 1, n); Z.first.assign(N + 1, 0);
@@ -662,15 +670,58 @@ void gzip_compose_host(crass_hip_group *g)
     }
 }
 
+// ... in members mode, behind the composition: the member table from the gathered GzEnd records (every element's from its first
+// holder) and the text cuts of the CRC pieces, cut also where a rank's own text begins; the exported windows that held no
+// reference are counted (a range that holds a member boundary exports such a window: its dead entries read 0)
+void gzip_members_host(crass_hip_group *g)
+{
+    crass::GzRangesFile &Z = *g->GZ.zp;
+    const uint64_t n = Z.n_chain, nm = Z.slot[n];
+    Z.exported_plain = 0;
+    for (int r = 0; r + 1 < g->n; r++) {
+        if (Z.exported[r].empty()) continue;
+        bool plain = true;
+        for (uint16_t w : Z.exported[r]) if (w >= 0x8000u) { plain = false; break; }
+        Z.exported_plain += plain;
+    }
+    Z.table_ok = false; Z.n_pieces = 0;
+    if (nm == 0) return;                                // (never expected: the chain ends behind a final block)
+    Z.in_off.assign(nm + 1, 0); Z.text_off.assign(nm + 1, 0); Z.mcrc.assign(nm, 0); Z.misz.assign(nm, 0);
+    crass::gz_member_table(Z.M, Z.n_bytes, Z.off.data(), Z.slot.data(), n, Z.ends.data(), Z.in_off.data(), Z.text_off.data(), Z.mcrc.data(), Z.misz.data());
+    for (uint64_t m = 0; m < nm; m++) if (Z.text_off[m + 1] < Z.text_off[m] || Z.text_off[m + 1] > Z.n_text) return;      // (a record nobody wrote)
+    if (Z.text_off[nm] != Z.n_text) return;
+    std::vector<uint64_t> base;
+    for (int r = 0; r < g->n; r++) {
+        const uint64_t f = std::max(Z.e0[r], Z.first[r]);
+        if (f < Z.e1[r]) base.push_back(Z.off[f]);
+    }
+    Z.piece.assign(nm + Z.n_text / crass::kGzCrcPiece + base.size() + 2, 0);
+    Z.n_pieces = crass::gz_crc_pieces(Z.text_off.data(), nm, base.data(), base.size(), Z.piece.data());
+    Z.crc_piece.assign(Z.n_pieces ? Z.n_pieces : 1, 0);
+    Z.table_ok = true;
+}
+
+// ... at the end: every member's CRC-32 joined from its pieces, the first offending member (7 / 8 before 9)
+int32_t gzip_members_verdict(const crass::GzRangesFile &Z, crass::GzVerdict *v)
+{
+    const uint64_t nm = Z.in_off.size() - 1;
+    std::vector<uint32_t> got(nm, 0);
+    uint64_t q = 0;
+    for (uint64_t m = 0; m < nm; m++)
+        for (; q < Z.n_pieces && Z.piece[q] < Z.text_off[m + 1]; q++) got[m] = crass::gz_crc_join(got[m], Z.crc_piece[q], Z.piece[q + 1] - Z.piece[q]);
+    return crass::gz_member_verdict(nm, Z.in_off.data(), Z.text_off.data(), Z.mcrc.data(), Z.misz.data(), got.data(), v);
+}
+
 // a file's state before the index step: the header and the trailer parsed (false: not a gzip member), the per-chunk arrays empty
-bool gzip_file_init(crass::GzRangesFile &Z, const uint8_t *bytes, uint64_t n_bytes, uint32_t n_ranks, uint64_t chunk_bytes)
+bool gzip_file_init(crass::GzRangesFile &Z, const uint8_t *bytes, uint64_t n_bytes, uint32_t n_ranks, uint64_t chunk_bytes, bool members = false)
 {
     Z = crass::GzRangesFile();
-    Z.bytes = bytes; Z.n_bytes = n_bytes; Z.n_ranks = n_ranks;
+    Z.bytes = bytes; Z.n_bytes = n_bytes; Z.n_ranks = n_ranks; Z.members = members;
     if (crass::gz_parse_member(bytes, n_bytes, n_bytes >= 8 ? bytes + n_bytes - 8 : nullptr, n_bytes, chunk_bytes, &Z.M) != crass::BZ_OK) return false;
     const uint64_t nc = Z.M.G.nc;
     Z.start.assign(nc, crass::kGzNoStart); Z.text_len.assign(nc, 0); Z.end_bit.assign(nc, 0);
     Z.link.assign(nc, crass::GZ_LINK_NONE); Z.reason.assign(nc, 0);
+    if (members) { Z.n_ends.assign(nc, 0); Z.last_end.assign(nc, 0); }
     return true;
 }
 
@@ -691,11 +742,12 @@ void gzip_inflate_rank(crass_hip_group *g, int r)
     if (J.do_inflate) {
         if (ok() && J.go) note(g, r, gzip_rank_decode(c, Z, (uint32_t)r));
         g->bar->wait();                                 // every rank's exported window
-        if (r == 0 && ok() && J.go) { try { gzip_compose_host(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
+        if (r == 0 && ok() && J.go) { try { gzip_compose_host(g); if (Z.members) gzip_members_host(g); } catch (const std::bad_alloc &) { note(g, 0, CRASS_ERR_OOM); } }
         g->bar->wait();                                 // every rank's entry window
         if (ok() && J.go) note(g, r, gzip_rank_finish(c, Z, (uint32_t)r, J.out, !J.do_index));
     }
     gzip_rank_report(c, J.ms[r].data(), &J.up[r]);
+    if (J.do_inflate && (size_t)r < J.crc_ms.size()) J.crc_ms[r] = gzip_rank_member_crc_ms(c);
     if (J.do_index && J.do_inflate) gzip_rank_release(c);      // (a files load keeps the staged bytes and gives all scratch back at its end)
 }
 
@@ -934,15 +986,17 @@ int crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4])
     return CRASS_OK;
 }
 
-int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
-                                 uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+static int group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal, uint8_t *out_host,
+                              uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, bool mem, crass_bgzf_verdict *v)
 {
     if (v) memset(v, 0, sizeof(*v));
     if (plan) memset(plan, 0, sizeof(*plan));
+    if (members) memset(members, 0, sizeof(*members));
     if (n_text) *n_text = 0;
     if (!g || !n_text || (n_bytes && !bytes) || (out_cap && !out_host)) return CRASS_ERR_INVALID_ARG;
     auto &J = g->GZ;
     for (auto &x : J.cnt) x = 0;
+    for (auto &x : J.cnt_members) x = 0;
     auto decline = [&](int32_t reason, uint64_t member, uint64_t in_pos) {
         if (v) { v->reason = reason; v->member = member; v->in_pos = in_pos; }
         return CRASS_ERR_UNSUPPORTED;
@@ -952,8 +1006,8 @@ int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint6
         crass::GzRangesFile &Z = J.Z;
         J.zp = &Z; J.do_index = J.do_inflate = true;
         for (int r = 0; r < g->n; r++) gzip_kept_report(g->ctx[r], nullptr, nullptr, true);
-        J.ms.assign(N, std::array<float, 6>{}); J.up.assign(N, {}); J.tail_ms.assign(N, 0.0f); J.tail_el.assign(N, 0);
-        if (!gzip_file_init(Z, bytes, n_bytes, N, chunk_bytes)) return decline(crass::BZ_NOT_GZIP, 0, 0);
+        J.ms.assign(N, std::array<float, 6>{}); J.up.assign(N, {}); J.tail_ms.assign(N, 0.0f); J.tail_el.assign(N, 0); J.crc_ms.assign(N, 0.0f);
+        if (!gzip_file_init(Z, bytes, n_bytes, N, chunk_bytes, mem)) return decline(crass::BZ_NOT_GZIP, 0, 0);
         const uint64_t nc = Z.M.G.nc;
         Z.exported.assign(N, {}); Z.entry.assign(N, {}); Z.bad.assign(N, ~0ull);
         J.out = out_host; J.out_cap = out_cap; J.nominal = nominal; J.go = false; J.status = CRASS_OK; J.v = crass::GzVerdict{};
@@ -981,6 +1035,14 @@ int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint6
         uint64_t bad = ~0ull;
         for (uint32_t r = 0; r < N; r++) bad = std::min(bad, Z.bad[r]);
         if (bad != ~0ull) { const uint64_t k = Z.chain[bad]; return decline(crass::BZ_MARKER, k, Z.M.G.d_off + (Z.start[k] >> 3)); }
+        if (mem) {
+            // the verdict in the host rule's order: 14 above, then the first offending member
+            if (!Z.table_ok) return CRASS_ERR_STATE;
+            J.cnt_members[0] = 1; J.cnt_members[1] = Z.in_off.size() - 1; J.cnt_members[2] = Z.n_pieces; J.cnt_members[3] = Z.exported_plain;
+            crass::GzVerdict mv{};
+            if (gzip_members_verdict(Z, &mv) != crass::BZ_OK) return decline(mv.reason, mv.member, mv.in_pos);
+            return crass::gz_members_fill(members, Z.in_off.size() - 1, Z.in_off.data(), Z.text_off.data());
+        }
         uint32_t crc = 0;
         for (uint64_t i = 0; i < n; i++) crc = crass::gz_crc_join(crc, Z.crc_part[i], Z.off[i + 1] - Z.off[i]);
         if (crc != Z.M.crc) return decline(crass::BZ_CRC, 0, 0);
@@ -988,10 +1050,37 @@ int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint6
     return CRASS_OK;
 }
 
+int crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
+                                 uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+{
+    return group_inflate_gzip(g, bytes, n_bytes, chunk_bytes, nominal, out_host, out_cap, n_text, plan, nullptr, false, v);
+}
+
+int crass_hip_group_inflate_gzip_members(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
+                                         uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members,
+                                         crass_bgzf_verdict *v)
+{
+    return group_inflate_gzip(g, bytes, n_bytes, chunk_bytes, nominal, out_host, out_cap, n_text, plan, members, true, v);
+}
+
+int crass_hip_group_gzip_members_counters(const crass_hip_group *g, uint64_t out[4])
+{
+    if (!g || !out) return CRASS_ERR_INVALID_ARG;
+    for (int k = 0; k < 4; k++) out[k] = g->GZ.cnt_members[k];
+    return CRASS_OK;
+}
+
+int crass_hip_group_gzip_members_ms(const crass_hip_group *g, int rank, float out[1])
+{
+    if (!g || !out || rank < 0 || rank >= g->n) return CRASS_ERR_INVALID_ARG;
+    out[0] = (size_t)rank < g->GZ.crc_ms.size() ? g->GZ.crc_ms[rank] : 0.0f;
+    return CRASS_OK;
+}
+
 int crass_hip_group_set_gzip_on_device(crass_hip_group *g, int mode, uint64_t chunk_bytes)
 {
     if (!g || mode < 0) return CRASS_ERR_INVALID_ARG;
-    g->gzip_mode = mode ? CRASS_GZIP_ON_DEVICE_ONE_MEMBER : CRASS_GZIP_ON_DEVICE_OFF;
+    g->gzip_mode = mode == CRASS_GZIP_ON_DEVICE_MEMBERS ? CRASS_GZIP_ON_DEVICE_MEMBERS : mode ? CRASS_GZIP_ON_DEVICE_ONE_MEMBER : CRASS_GZIP_ON_DEVICE_OFF;
     g->gzip_chunk = chunk_bytes ? crass::gz_chunk_bytes(chunk_bytes) : 0;
     return CRASS_OK;
 }
@@ -1281,9 +1370,10 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
         J.files.assign(n_files, crass::ShardFile{});
         J.nf = n_files;
         for (uint64_t &x : g->GZ.cnt) x = 0;
+        for (uint64_t &x : g->GZ.cnt_members) x = 0;
         g->GZ.files.clear(); g->GZ.ix.clear(); g->GZ.ix_zero.clear(); g->GZ.ix.reserve(n_files);
         g->GZ.v_gz = crass::ShardVerdict();
-        g->GZ.ms.assign(N, std::array<float, 6>{}); g->GZ.up.assign(N, {}); g->GZ.tail_ms.assign(N, 0.0f); g->GZ.tail_el.assign(N, 0);
+        g->GZ.ms.assign(N, std::array<float, 6>{}); g->GZ.up.assign(N, {}); g->GZ.tail_ms.assign(N, 0.0f); g->GZ.tail_el.assign(N, 0); g->GZ.crc_ms.assign(N, 0.0f);
         for (int r = 0; r < N; r++) { gzip_kept_release(g->ctx[r]); gzip_kept_report(g->ctx[r], nullptr, nullptr, true); }      // (what a failed load left)
         for (uint32_t f = 0; f < n_files; f++) {
             crass::ShardFile &F = J.files[f];
@@ -1298,7 +1388,7 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
                     auto &GJ = g->GZ;
                     GJ.files.emplace_back(new crass::GzRangesFile());
                     crass::GzRangesFile &Z = *GJ.files.back();
-                    if (!gzip_file_init(Z, F.bytes, F.n_bytes, (uint32_t)N, g->gzip_chunk)) { pend(0); J.pend.bgzf.reason = crass::BZ_NOT_GZIP; break; }
+                    if (!gzip_file_init(Z, F.bytes, F.n_bytes, (uint32_t)N, g->gzip_chunk, g->gzip_mode == CRASS_GZIP_ON_DEVICE_MEMBERS)) { pend(0); J.pend.bgzf.reason = crass::BZ_NOT_GZIP; break; }
                     const int zs = gzip_job_run(g, Z, true, false);
                     if (zs) return zs;
                     if (GJ.status == CRASS_ERR_UNSUPPORTED) { pend(0); J.pend.bgzf.reason = GJ.v.reason; J.pend.bgzf.member = GJ.v.member; J.pend.bgzf.in_pos = GJ.v.in_pos; break; }
@@ -1364,6 +1454,13 @@ int crass_hip_group_load_fastx_files(crass_hip_group *g, const uint8_t *const *b
             crass::ShardVerdict sv;
             sv.file = (int32_t)f;
             if (bad != ~0ull) { const uint64_t k = Z.chain[bad]; sv.bgzf.reason = crass::BZ_MARKER; sv.bgzf.member = k; sv.bgzf.in_pos = Z.M.G.d_off + (Z.start[k] >> 3); }
+            else if (Z.members) {
+                // members mode: the member verdict (7 / 8 / 9 with the member and the file byte of its header) is the file's
+                if (!Z.table_ok) return CRASS_ERR_STATE;
+                g->GZ.cnt_members[0] += 1; g->GZ.cnt_members[1] += Z.in_off.size() - 1; g->GZ.cnt_members[2] += Z.n_pieces; g->GZ.cnt_members[3] += Z.exported_plain;
+                crass::GzVerdict mv{};
+                if (gzip_members_verdict(Z, &mv) != crass::BZ_OK) { sv.bgzf.reason = mv.reason; sv.bgzf.member = mv.member; sv.bgzf.in_pos = mv.in_pos; }
+            }
             else if (crc != Z.M.crc) sv.bgzf.reason = crass::BZ_CRC;
             if (sv.bgzf.reason && crass::shard_verdict_before(sv, g->GZ.v_gz)) g->GZ.v_gz = sv;
         }

@@ -1,6 +1,7 @@
 // gunzip.cpp — plain gzip on the host: a serial run of gunzip_core.h's rule (find, count, chain, decode, windows, narrow), one
 // chunk after the other.  It needs no GPU; it is what the kernels (gunzip.hip) are tested against, itself tested against zlib.
-// crass_gzip_inflate_members_host is the same run in members mode (a file of several members).
+// crass_gzip_inflate_members_host is the same run in members mode (a file of several members); crass_gzip_inflate_ranges_host and
+// crass_gzip_inflate_members_ranges_host are both rules as the ranks of a group run them, range after range.
 // Host-only C++17 that any compiler builds (tools/sanitize).  Scratch: 2 bytes per text byte and 32 KB per chain element.
 #include "../../include/crass_hip.h"
 #include "gunzip_core.h"
@@ -200,9 +201,12 @@ static int gz_inflate_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chun
 }
 
 // the distributed rule (a group's ranks) as a serial run: range after range, each one its own symbols and symbolic windows from
-// an identity entry; the entry window of a range is composed from the range before it, which on the host has just finished
+// an identity entry; the entry window of a range is composed from the range before it, which on the host has just finished.
+// MEM: the members rule by ranges (gunzip_core.h): every range's GzEnd records in slots of its own, the table from each element's
+// first holder; dead window entries read 0; the members' CRC-32 from pieces, the verdict behind all narrowing
+template <bool MEM>
 static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal, uint8_t *out,
-                                  uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v)
+                                  uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v)
 {
     BzTables *T = new (std::nothrow) BzTables;
     if (!T) return CRASS_ERR_OOM;
@@ -210,26 +214,37 @@ static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64
     try {
         GzHostIO io{};
         GzHostCount P;
-        status = gz_front_host<false>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, nullptr, v, io, *T, P);
+        status = gz_front_host<MEM>(bytes, n_bytes, chunk_bytes, out, out_cap, n_text, plan, members, v, io, *T, P);
         if (status >= 0) { delete T; return status; }
         status = CRASS_OK;
         const GzGeom &G = P.M.G;
         const uint64_t n = P.n_chain;
         std::vector<uint64_t> off(n + 1, 0), e0(n_ranges + 1, n), e1(n_ranges + 1, n);      // (a range behind the last: no elements)
-        for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + P.text_len[P.chain[i]];
+        std::vector<uint64_t> slot(n + 1, 0), m0(n, 0);
+        if (MEM) gz_places(P.chain.data(), n, P.text_len.data(), P.n_ends.data(), P.last_end.data(), off.data(), slot.data(), m0.data());
+        else for (uint64_t i = 0; i < n; i++) off[i + 1] = off[i] + P.text_len[P.chain[i]];
         if (!gz_ranges(off.data(), n, n_ranges, nominal, e0.data(), e1.data())) { delete T; *n_text = 0; return CRASS_ERR_INVALID_ARG; }
         std::vector<uint32_t> crc_part(n, 0);
         std::vector<uint8_t> entry(kGzWindow, 0), next_entry(kGzWindow, 0), win(kGzWindow, 0);
         std::vector<uint16_t> sym, wsym(kGzWindow), wsym_before(kGzWindow);
+        std::vector<GzEnd> ends(slot[n] ? slot[n] : 1), own;      // (members mode: the table's records, a range's own)
+        std::vector<uint64_t> base;                     // (members mode: where the text a range holds first begins)
         uint64_t done = 0;                              // elements [0, done) have their text: every part from the first range that holds it
         for (uint32_t r = 0; r < n_ranges && status == CRASS_OK; r++) {
             const uint64_t a = e0[r], b = e1[r];
             // decode: the range's elements as symbols, element i at sym[off[i] - off[a]]
             sym.assign(off[b] - off[a] + 1, 0);
+            if (MEM) own.assign(slot[b] - slot[a] + 1, GzEnd{0, 0, 0, 0});
             for (uint64_t i = a; i < b; i++) {
                 const uint64_t k = P.chain[i];
                 io.sym = sym.data() + (off[i] - off[a]); io.cap = P.text_len[k];
-                (void)gz_run<GZ_DECODE, false>(io, *T, G, k, P.start[k], nullptr, P.end_bit[k]);
+                if (MEM) { io.ends = own.data() + (slot[i] - slot[a]); io.ends_cap = (uint32_t)(slot[i + 1] - slot[i]); }
+                (void)gz_run<GZ_DECODE, MEM>(io, *T, G, k, P.start[k], nullptr, P.end_bit[k]);
+            }
+            if (MEM && b > std::max(a, done)) {
+                const uint64_t f = std::max(a, done);
+                for (uint64_t e = slot[f]; e < slot[b]; e++) ends[e] = own[e - slot[a]];
+                base.push_back(off[f]);
             }
             // element after element: the symbolic window in front of it (of a, the identity), resolved through the entry window; its
             // text.  The window in front of b is made too where the next range starts there
@@ -238,7 +253,9 @@ static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64
                 if (i > a) {
                     wsym.swap(wsym_before);
                     const uint16_t *sp = sym.data() + (off[i - 1] - off[a]);
-                    for (uint32_t e = 0; e < kGzWindow; e++) wsym[e] = gz_window_entry_sym(sp, off[i] - off[i - 1], i > a + 1 ? wsym_before.data() : nullptr, e);
+                    const uint16_t *wp = i > a + 1 ? wsym_before.data() : nullptr;
+                    for (uint32_t e = 0; e < kGzWindow; e++)
+                        wsym[e] = MEM ? gz_window_entry_sym_members(sp, off[i] - off[i - 1], wp, e, off[i], m0[i]) : gz_window_entry_sym(sp, off[i] - off[i - 1], wp, e);
                     for (uint32_t e = 0; e < kGzWindow; e++) win[e] = gz_window_resolve(wsym[e], a ? entry.data() : nullptr);
                 }
                 const std::vector<uint8_t> &w = i > a ? win : entry;
@@ -247,7 +264,7 @@ static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64
                 const uint64_t k = P.chain[i];
                 uint32_t c = 0xFFFFFFFFu;
                 for (uint64_t p = off[i]; p < off[i + 1]; p++) {
-                    const uint32_t x = gz_narrow(sym[p - off[a]], i ? w.data() : nullptr, off[i]);
+                    const uint32_t x = gz_narrow(sym[p - off[a]], i ? w.data() : nullptr, off[i], MEM ? m0[i] : 0);
                     if (x > 0xFFu) { status = gz_decline(v, BZ_MARKER, k, G.d_off + (P.start[k] >> 3)); break; }
                     out[p] = (uint8_t)x;
                     c = T->crc_tab[(c ^ x) & 0xFFu] ^ (c >> 8);
@@ -258,9 +275,33 @@ static int gz_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64
             entry.swap(next_entry);
         }
         if (status == CRASS_OK && done != n) status = CRASS_ERR_STATE;      // (never expected: tiling ranges leave no element out)
-        uint32_t crc = 0;
-        for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
-        if (status == CRASS_OK && crc != P.M.crc) status = gz_decline(v, BZ_CRC, 0, 0);
+        if (!MEM) {
+            uint32_t crc = 0;
+            for (uint64_t i = 0; i < n; i++) crc = gz_crc_join(crc, crc_part[i], off[i + 1] - off[i]);
+            if (status == CRASS_OK && crc != P.M.crc) status = gz_decline(v, BZ_CRC, 0, 0);
+        } else if (status == CRASS_OK) {
+            // the member table, the pieces (cut also where a range's own text begins), every member's CRC-32 joined from them
+            const uint64_t nm = slot[n], total = off[n];
+            std::vector<uint64_t> in_off(nm + 1, 0), text_off(nm + 1, 0), piece(nm + total / kGzCrcPiece + base.size() + 2, 0);
+            std::vector<uint32_t> mcrc(nm, 0), misz(nm, 0), got(nm, 0);
+            gz_member_table(P.M, n_bytes, off.data(), slot.data(), n, ends.data(), in_off.data(), text_off.data(), mcrc.data(), misz.data());
+            for (uint64_t m = 0; m < nm && status == CRASS_OK; m++)
+                if (text_off[m + 1] < text_off[m] || text_off[m + 1] > total) status = CRASS_ERR_STATE;      // (a record nobody wrote)
+            if (status == CRASS_OK) {
+                const uint64_t np = gz_crc_pieces(text_off.data(), nm, base.data(), base.size(), piece.data());
+                uint64_t q = 0;
+                for (uint64_t m = 0; m < nm; m++)
+                    for (; q < np && piece[q] < text_off[m + 1]; q++) {
+                        uint32_t c = 0xFFFFFFFFu;
+                        for (uint64_t p = piece[q]; p < piece[q + 1]; p++) c = T->crc_tab[(c ^ out[p]) & 0xFFu] ^ (c >> 8);
+                        got[m] = gz_crc_join(got[m], ~c, piece[q + 1] - piece[q]);
+                    }
+                GzVerdict mv{};
+                if (gz_member_verdict(nm, in_off.data(), text_off.data(), mcrc.data(), misz.data(), got.data(), &mv) != BZ_OK)
+                    status = gz_decline(v, mv.reason, mv.member, mv.in_pos);
+                else status = gz_members_fill(members, nm, in_off.data(), text_off.data());
+            }
+        }
     } catch (const std::bad_alloc &) { status = CRASS_ERR_OOM; }
     delete T;
     return status;
@@ -277,7 +318,21 @@ int crass_gzip_inflate_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint6
         if (n_text) *n_text = 0;
         return CRASS_ERR_INVALID_ARG;
     }
-    return gz_inflate_ranges_host(bytes, n_bytes, chunk_bytes, n_ranges, nominal, out, out_cap, n_text, plan, v);
+    return gz_inflate_ranges_host<false>(bytes, n_bytes, chunk_bytes, n_ranges, nominal, out, out_cap, n_text, plan, nullptr, v);
+}
+
+int crass_gzip_inflate_members_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal,
+                                           uint8_t *out, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members,
+                                           crass_bgzf_verdict *v)
+{
+    if (n_ranges < 1 || n_ranges > 64) {
+        if (v) memset(v, 0, sizeof(*v));
+        if (plan) memset(plan, 0, sizeof(*plan));
+        if (members) memset(members, 0, sizeof(*members));
+        if (n_text) *n_text = 0;
+        return CRASS_ERR_INVALID_ARG;
+    }
+    return gz_inflate_ranges_host<true>(bytes, n_bytes, chunk_bytes, n_ranges, nominal, out, out_cap, n_text, plan, members, v);
 }
 
 void crass_gzip_plan_free(crass_gzip_plan *p)

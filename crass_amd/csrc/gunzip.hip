@@ -17,6 +17,7 @@
 // full range), and in place of k_gz_windows, which needs the window in front of the range's first element,
 //   k_gz_windows_sym     ONE workgroup walks the RANGE's elements from the identity: windows of bytes and references into the
 //                        unknown entry window (gz_window_entry_sym)
+//                        (k_gz_windows_sym_members: dead entries read 0, gunzip_core.h)
 //   k_gz_window_resolve  a workgroup per element, once the host has composed the ranges' entry windows: symbolic to bytes
 // As in inflate.hip: symbol decoding is serial, all 64 lanes run it with the same values; tables (BzTables, 7 KB per wave) are in
 // LDS, the text in HBM; what a lane wrote is read by lanes of the SAME wave only, so io.sync() is a wavefront-scope fence plus a
@@ -27,7 +28,7 @@
 // check the index); find writes start[k0, k1), count link / text_len / end_bit / reason [k0, k1); k_gz_windows_sym writes
 // wsym[32768 i, 32768 (i + 1)) for i in [1, n_win]; k_gz_window_resolve writes win[32768 i, 32768 (i + 1)) for i in
 // [1, n_win]; a decode wave writes sym[off[i], off[i+1])
-// only (put() checks) and in members mode ends[slot[i], slot[i+1]) (end() checks); k_gz_member_crc reads out[piece[q], piece[q+1])
+// only (put() checks) and in members mode ends[slot[i] - slot[0], slot[i+1] - slot[0]) (end() checks); k_gz_member_crc reads out[piece[q], piece[q+1])
 // and writes crc_piece[q]; k_gz_windows writes win[32768 i, 32768 (i + 1)); k_gz_narrow writes out[off[i], off[i+1]).
 #include "gunzip_launch.h"
 #include "engine_internal.h"
@@ -63,12 +64,14 @@ struct GzWaveIO {
     {
         return (uint64_t)__ballot(gz_survives(d, hi, base + lane, top, limit, lo) ? 1 : 0);
     }
-    // (members mode only, whole files only: reads d / dn unclipped — never used on a job that holds a part of the file)
-    __device__ __forceinline__ uint64_t header_survivors(uint64_t base, uint64_t hi, uint64_t limit) const
+    // (members mode only; clipped to what is staged as survivors is)
+    __device__ __forceinline__ uint64_t header_survivors(uint64_t base, uint64_t top, uint64_t limit) const
     {
-        return (uint64_t)__ballot(gz_survives_header(d, dn, base + lane, hi, limit) ? 1 : 0);
+        return (uint64_t)__ballot(gz_survives_header(d, hi, base + lane, top, limit, lo) ? 1 : 0);
     }
-    __device__ __forceinline__ uint32_t tail(uint32_t i) const { return i < 8u ? (uint32_t)d[dn + i] : 0u; }      // (the file's last 8 bytes)
+    // the file's last 8 bytes, where the job staged them (a whole file; of a group the ranks whose find runs see the region's end)
+    bool has_tail = false;
+    __device__ __forceinline__ uint32_t tail(uint32_t i) const { return has_tail && i < 8u ? (uint32_t)d[dn + i] : 0u; }
     __device__ __forceinline__ void end(uint32_t e, const GzEnd &r) { if (e < ends_cap) ends[e] = r; }
 };
 
@@ -77,7 +80,7 @@ template <bool MEM> __device__ __forceinline__ void gz_find_waves(const GzJob &J
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
-    io.lo = J.in_lo; io.hi = J.in_hi;
+    io.lo = J.in_lo; io.hi = J.in_hi; io.has_tail = J.in_tail != 0;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
     for (uint64_t k = J.k0 + (uint64_t)blockIdx.x * kGzWaves + wv; k < J.k1; k += n_waves) {
@@ -102,7 +105,7 @@ template <bool MEM> __device__ __forceinline__ void gz_count_waves(const GzJob &
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
-    io.lo = J.in_lo; io.hi = J.in_hi;
+    io.lo = J.in_lo; io.hi = J.in_hi; io.has_tail = J.in_tail != 0;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
     for (uint64_t k = J.k0 + (uint64_t)blockIdx.x * kGzWaves + wv; k < J.k1; k += n_waves) {
@@ -130,13 +133,14 @@ template <bool MEM> __device__ __forceinline__ void gz_decode_waves(const GzJob 
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     BzTables &T = tabs[wv];
     GzWaveIO io{J.d, J.G.dn, J.d, 0, nullptr, 0, lane};
-    io.lo = J.in_lo; io.hi = J.in_hi;
+    io.lo = J.in_lo; io.hi = J.in_hi; io.has_tail = J.in_tail != 0;
     bz_prepare(io, T);
     const uint64_t n_waves = (uint64_t)gridDim.x * kGzWaves;
     for (uint64_t i = (uint64_t)blockIdx.x * kGzWaves + wv; i < J.n_chain; i += n_waves) {
         const uint64_t k = J.chain[i];
         io.sym = J.sym + J.off[i]; io.cap = J.off[i + 1] - J.off[i];
-        if (MEM) { io.ends = J.ends + J.slot[i]; io.ends_cap = (uint32_t)(J.slot[i + 1] - J.slot[i]); }
+        // (a job's records lie at slots relative to its first element's; without slots — a seeded walk that meets records again — none is kept)
+        if (MEM && J.slot) { io.ends = J.ends + (J.slot[i] - J.slot[0]); io.ends_cap = (uint32_t)(J.slot[i + 1] - J.slot[i]); }
         (void)gz_run<GZ_DECODE, MEM>(io, T, J.G, k, J.start[k], nullptr, J.end_bit[k]);
         io.sync();
     }
@@ -181,6 +185,20 @@ __global__ __launch_bounds__(kGzWindowThreads) void k_gz_windows_sym(GzJob J)
         const uint16_t *wp = i > 1 ? J.wsym + (i - 1) * (uint64_t)kGzWindow : nullptr;
         uint16_t *w = J.wsym + i * (uint64_t)kGzWindow;
         for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_entry_sym(sp, L, wp, e);
+        __syncthreads();                                  // (workgroup scope: the next element reads what all threads wrote)
+    }
+}
+
+// ... in members mode: entries that lie in front of the member that holds the element's first byte are dead and read 0
+// (gunzip_core.h); m0[i] for i in [1, n_win] is read
+__global__ __launch_bounds__(kGzWindowThreads) void k_gz_windows_sym_members(GzJob J)
+{
+    for (uint64_t i = 1; i <= J.n_win; i++) {
+        const uint16_t *sp = J.sym + J.off[i - 1];
+        const uint64_t L = J.off[i] - J.off[i - 1], t0 = J.off[i], m0 = J.m0[i];
+        const uint16_t *wp = i > 1 ? J.wsym + (i - 1) * (uint64_t)kGzWindow : nullptr;
+        uint16_t *w = J.wsym + i * (uint64_t)kGzWindow;
+        for (uint32_t e = threadIdx.x; e < kGzWindow; e += kGzWindowThreads) w[e] = gz_window_entry_sym_members(sp, L, wp, e, t0, m0);
         __syncthreads();                                  // (workgroup scope: the next element reads what all threads wrote)
     }
 }
@@ -346,10 +364,11 @@ hipError_t launch_gz_windows(const GzJob &J, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_gz_windows_sym(const GzJob &J, hipStream_t st)
+hipError_t launch_gz_windows_sym(const GzJob &J, hipStream_t st, bool members)
 {
     if (J.n_win == 0) return hipSuccess;
-    CRASS_LAUNCH(k_gz_windows_sym, dim3(1), dim3(kGzWindowThreads), 0, st, J);
+    if (members) CRASS_LAUNCH(k_gz_windows_sym_members, dim3(1), dim3(kGzWindowThreads), 0, st, J);
+    else CRASS_LAUNCH(k_gz_windows_sym, dim3(1), dim3(kGzWindowThreads), 0, st, J);
     return hipGetLastError();
 }
 

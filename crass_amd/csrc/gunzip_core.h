@@ -29,6 +29,13 @@
 //   resolve  every symbolic window through the rank's entry window: the bytes `windows` would have made; narrow as above.  An
 //            element's text and CRC-32 part are taken from the first rank that holds it
 //
+// Members mode by ranges (crass_hip_group_inflate_gzip_members; serially crass_gzip_inflate_members_ranges_host): the two together.
+// The rank whose find runs see the region's end also stages the 8 bytes behind it (io.tail()); a decode over the elements
+// [e0, e1) writes its GzEnd records at slots relative to slot[e0], the member table is made from the records of each element's
+// FIRST holder; the symbolic walk writes dead entries as 0 (gz_entry_dead, below); the CRC pieces are cut also where a range's own
+// text begins (gz_crc_pieces), every range runs its own; the verdict comes behind all narrowing: 14 in chain order, then the
+// first offending member (gz_member_verdict)
+//
 // kGzMaxSpan = 32: a chunk gives up when it has gone through 32 chunks' worth of input without meeting a later chunk's start.
 // zlib ends a block after at most 32 767 symbols (memLevel 9; 16 383 at the default 8), which for FASTA / FASTQ text is 30 to
 // 50 KB of input and at most ~120 KB for text of any kind: 32 chunks of the smallest size (4096 bytes: 128 KB) get through such a
@@ -187,9 +194,10 @@ CRASS_HD inline bool gz_survives(const uint8_t *d, uint64_t dn, uint64_t p, uint
 }
 
 // members mode: position p may be a member's start: byte-aligned, the magic, method 8, no reserved flag
-CRASS_HD inline bool gz_survives_header(const uint8_t *d, uint64_t dn, uint64_t p, uint64_t hi, uint64_t limit)
+// (d[d_lo, dn) is read, as in gz_survives)
+CRASS_HD inline bool gz_survives_header(const uint8_t *d, uint64_t dn, uint64_t p, uint64_t hi, uint64_t limit, uint64_t d_lo = 0)
 {
-    if (p >= hi || p + 64 >= limit || (p & 7u)) return false;
+    if (p >= hi || p + 64 >= limit || (p & 7u) || (p >> 3) < d_lo) return false;
     const uint64_t b = p >> 3;                            // (b + 8 < dn)
     return b + 3 < dn && d[b] == 0x1Fu && d[b + 1] == 0x8Bu && d[b + 2] == 8u && !(d[b + 3] & 0xE0u);
 }
@@ -488,6 +496,17 @@ CRASS_HD inline uint16_t gz_window_entry_sym(const uint16_t *sp, uint64_t L, con
     }
     return wp_sym ? wp_sym[idx] : (uint16_t)(0x8000u | idx);
 }
+// Members mode by ranges, DEAD entries: entry w of the window in front of an element whose text starts at t0 lies at text
+// position t0 - (kGzWindow - w).  Where that lies in front of m0, the start of the member that holds the element's first byte,
+// no symbol may ever read it into the output: gz_narrow refuses such a marker by its position (14) before it looks at the window,
+// and a window further on holds the entry only at a position in front of its own m0 >= m0, dead again.  The symbolic walk writes
+// such an entry as the byte 0, not as a reference.  So the window behind a member boundary refers to nothing in front of that
+// boundary: a range that holds a boundary exports a window without references, and the range behind it needs nothing from it
+CRASS_HD inline bool gz_entry_dead(uint64_t t0, uint64_t m0, uint32_t w) { return t0 - m0 + w < kGzWindow; }
+CRASS_HD inline uint16_t gz_window_entry_sym_members(const uint16_t *sp, uint64_t L, const uint16_t *wp_sym, uint32_t w, uint64_t t0, uint64_t m0)
+{
+    return gz_entry_dead(t0, m0, w) ? (uint16_t)0 : gz_window_entry_sym(sp, L, wp_sym, w);
+}
 // a symbolic entry through the range's entry window (NULL: the range starts at the file's element 0, entries in front of the
 // text read 0 as in gz_window_entry).  Also the composition step: the entry window of the next range is the resolve of the
 // symbolic window this range holds in front of that range's first element
@@ -593,6 +612,23 @@ inline void gz_member_table(const GzMember &M, uint64_t n_file, const uint64_t *
         }
     const uint64_t nm = slot[n];
     in_off[nm] = n_file; crc[nm - 1] = M.crc; isize[nm - 1] = M.isize;
+}
+// the text cuts of the CRC pieces: every member's text from its start in steps of at most kGzCrcPiece, cut again at base[0, nb)
+// (ascending text positions: where the text a range holds FIRST begins, so that every piece is one range's).  piece[] has room for
+// nm + T / kGzCrcPiece + nb + 2 entries; piece[0, np] are set, piece[np] = T = text_off[nm]; returns np.  An empty member has no piece
+inline uint64_t gz_crc_pieces(const uint64_t *text_off, uint64_t nm, const uint64_t *base, uint64_t nb, uint64_t *piece)
+{
+    uint64_t np = 0, q = 0;
+    for (uint64_t m = 0; m < nm; m++)
+        for (uint64_t p = text_off[m]; p < text_off[m + 1];) {
+            while (q < nb && base[q] <= p) q++;
+            piece[np++] = p;
+            uint64_t nx = text_off[m + 1] - p > kGzCrcPiece ? p + kGzCrcPiece : text_off[m + 1];
+            if (q < nb && base[q] < nx) nx = base[q];
+            p = nx;
+        }
+    piece[np] = text_off[nm];
+    return np;
 }
 // the first offending member, ISIZE (7 / 8) before CRC-32 (9) within a member; crc_got[m]: the CRC-32 of member m's text
 inline int32_t gz_member_verdict(uint64_t nm, const uint64_t *in_off, const uint64_t *text_off, const uint32_t *crc, const uint32_t *isize,

@@ -16,6 +16,7 @@ struct GzJob {
     // d, sym and out of such a job are BIASED pointers that may lie in front of their allocations: nothing is wrong as long as every
     // access stays inside [in_lo, in_hi) and [off[0], off[n_chain]) — at(), gz_survives, put() / get() and narrow's bounds see to that
     uint64_t in_lo, in_hi, k0, k1, e0;
+    uint32_t in_tail;       // members mode: the 8 bytes behind the region, d[G.dn, G.dn + 8), are staged too (io.tail())
     // per chunk [G.nc]: find writes start (start[0] = 0 too), count the rest
     uint64_t *start; uint32_t *link; uint64_t *text_len, *end_bit; int32_t *reason;
     // per chain element, after the host's chain walk
@@ -34,20 +35,21 @@ struct GzJob {
     unsigned long long *verdict;      // the first chain element that holds an unresolved marker, kBzNoOffence before the launch
     // members mode (NULL / 0 otherwise)
     uint32_t *n_ends; uint64_t *last_end;      // per chunk [G.nc], from count
-    const uint64_t *slot;   // [n_chain + 1] where an element's GzEnd records start
-    const uint64_t *m0;     // [n_chain] the text offset of the start of the member that holds the element's first byte
-    GzEnd *ends;            // [slot[n_chain]]
+    const uint64_t *slot;   // [n_chain + 1] where an element's GzEnd records start (NULL: the decode keeps no records)
+    const uint64_t *m0;     // [n_chain] the text offset of the start of the member that holds the element's first byte ([n_win + 1] where
+                            // k_gz_windows_sym_members makes the window behind the last element)
+    GzEnd *ends;            // [slot[n_chain] - slot[0]] the job's records, relative to its first element's slot
     uint64_t n_pieces;
     const uint64_t *piece;  // [n_pieces + 1] the text cut at member boundaries and every kGzCrcPiece bytes inside a member
     uint32_t *crc_piece;    // [n_pieces]
 };
-inline void gz_job_whole(GzJob &J) { J.in_lo = 0; J.in_hi = J.G.dn; J.k0 = 0; J.k1 = J.G.nc; J.e0 = 0; }      // (behind J.G)
+inline void gz_job_whole(GzJob &J) { J.in_lo = 0; J.in_hi = J.G.dn; J.k0 = 0; J.k1 = J.G.nc; J.e0 = 0; J.in_tail = 1; }      // (behind J.G)
 // members: the kernels of members mode (k_gz_*_members)
 hipError_t launch_gz_find(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_count(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_decode(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_windows(const GzJob &J, hipStream_t st);
-hipError_t launch_gz_windows_sym(const GzJob &J, hipStream_t st);
+hipError_t launch_gz_windows_sym(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_window_resolve(const GzJob &J, hipStream_t st);
 hipError_t launch_gz_narrow(const GzJob &J, hipStream_t st, bool members = false);
 hipError_t launch_gz_member_crc(const GzJob &J, hipStream_t st);

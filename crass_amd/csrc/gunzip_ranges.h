@@ -32,6 +32,18 @@ struct GzRangesFile {
     // per element, from the first rank that holds it; per rank the smallest element with an unresolved marker (~0: none)
     std::vector<uint32_t> crc_part;
     std::vector<uint64_t> bad;
+    // members mode (gunzip_core.h; off, nothing below is touched): per chunk n_ends / last_end from count; rank 0 behind the count
+    // step: gz_places' slot [n_chain + 1] and m0 [n_chain]; the GzEnd records [slot[n_chain]], every element's from its FIRST
+    // holder (a rank writes the records of the elements no rank in front of it holds: ranges apart); rank 0 behind the decode
+    // step: the member table (gz_member_table; table_ok false: a record nobody wrote) and the text cuts of the CRC pieces
+    // (gz_crc_pieces, cut also where a rank's own text begins: a piece is one rank's); every rank the CRC-32 of its pieces
+    bool members = false, table_ok = false;
+    std::vector<uint32_t> n_ends;
+    std::vector<uint64_t> last_end, slot, m0;
+    std::vector<GzEnd> ends;
+    std::vector<uint64_t> in_off, text_off, piece;
+    std::vector<uint32_t> mcrc, misz, crc_piece;
+    uint64_t n_pieces = 0, exported_plain = 0;      // exported_plain: exported windows without a reference
     // the chunks of rank r: [k_lo(r), k_lo(r + 1))
     uint64_t k_lo(uint32_t r) const { return (M.G.nc * r + n_ranks - 1) / n_ranks; }
 };
@@ -40,6 +52,9 @@ struct GzRangesFile {
 
 // One rank's steps; the group's threads meet at a barrier behind each.  CRASS_OK or a HIP / memory error; declines are the
 // host's to find (gz_chain behind step 2, crc_part / bad behind step 4).
+// Members mode (F.members): the members kernels; find also stages the file's last 8 bytes on a rank whose runs see the region's
+// end, count brings n_ends / last_end, decode the rank's GzEnd records (slots relative to its first element's) and the symbolic
+// walk writes dead entries as 0, finish narrows with m0 and runs k_gz_member_crc over the rank's own pieces into F.crc_piece.
 // 1. stages the compressed bytes its chunks' runs may read and finds its chunks' starts (k_gz_find) into F.start
 int gzip_rank_find(crass_hip_ctx *c, crass::GzRangesFile &F, uint32_t r);
 // 2. with every rank's starts: counts its chunks (k_gz_count) into F.link / text_len / end_bit / reason
@@ -64,4 +79,6 @@ void gzip_kept_report(crass_hip_ctx *c, float *tail_ms, uint64_t *tail_elements,
 // >= 1, else 0); uploads: the host address ranges of deflate bytes this rank sent to its device since the last reset
 void gzip_rank_release(crass_hip_ctx *c);
 void gzip_rank_report(const crass_hip_ctx *c, float ms[6], std::vector<std::pair<uint64_t, uint64_t>> *uploads);
+// members mode: HIP-event milliseconds of k_gz_member_crc in the rank's last finish step (stage timing >= 1, else 0)
+float gzip_rank_member_crc_ms(const crass_hip_ctx *c);
 #pragma GCC visibility pop

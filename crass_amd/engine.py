@@ -453,6 +453,51 @@ def gzip_inflate_members_host(buf, chunk_bytes=0, out_cap=None, with_plan=False)
     return (out, plan, members) if with_plan else out
 
 
+def _gzip_members_ranges_call(fn, call, a, out_cap, with_plan):
+    """_gzip_ranges_call for a members inflate (call(out_ptr, cap, n_text, plan, members, verdict) -> status): with with_plan
+    (text, GzipPlan, GzipMembers)."""
+    lib = _abi.load()
+    cap = _gzip_guess_cap(a) if out_cap is None else int(out_cap)
+    while True:
+        out = np.zeros(cap, np.uint8)
+        n_text, ver, pc, mc = C.c_uint64(0), _abi.BgzfVerdict(), _abi.GzipPlanC(), _abi.GzipMembersC()
+        try:
+            st = call(out.ctypes.data if cap else None, cap, C.byref(n_text), C.byref(pc), C.byref(mc), C.byref(ver))
+            plan, members = GzipPlan(pc), GzipMembers(mc)
+        finally:
+            lib.crass_gzip_plan_free(C.byref(pc))
+            lib.crass_gzip_members_free(C.byref(mc))
+        if st == 8 and out_cap is None:
+            cap = int(n_text.value)
+            continue
+        break
+    if st == 2:
+        e = BgzfDeclined(st, fn, ver)
+        e.plan = plan
+        raise e
+    if st == 8:
+        e = CrassError(st, fn)
+        e.n_text, e.out, e.plan = int(n_text.value), out, plan
+        raise e
+    _chk(st, fn)
+    out = out[:int(n_text.value)]
+    return (out, plan, members) if with_plan else out
+
+
+def gzip_inflate_members_ranges_host(buf, n_ranges, chunk_bytes=0, nominal=None, out_cap=None, with_plan=False):
+    """gzip_inflate_members_host by the rule a group's ranks run (crass_gzip_inflate_members_ranges_host; no GPU needed): the text
+    cut into n_ranges ranges at nominal (n_ranges - 1 text positions; None: even), every range's elements decoded with member-end
+    records of its own, windows walked symbolically with dead entries as 0, the members' CRC-32 joined from pieces.  Results and
+    errors as gzip_inflate_members_host, for every n_ranges; with with_plan (text, GzipPlan, GzipMembers)."""
+    lib = _abi.load()
+    a = _bytes_arg(buf)
+    nom = _nominal_arg(nominal, int(n_ranges))
+    ptr = a.ctypes.data if len(a) else None
+    return _gzip_members_ranges_call("crass_gzip_inflate_members_ranges_host", lambda o, cap, n, p, m, v: lib.crass_gzip_inflate_members_ranges_host(
+        ptr, len(a), int(chunk_bytes), int(n_ranges), nom.ctypes.data if nom is not None and len(nom) else None, o, cap, n, p, m, v), a, out_cap,
+        with_plan)
+
+
 class FastxFilesLayout:
     """Several files as one read set (crass_fastx_files_layout), as numpy copies: n_files, n_reads, max_len, file_read_base /
     file_byte_base (uint64, n_files + 1; byte bases and rec_pos are ARENA positions: every file's text with a "\\n" behind it),
@@ -555,7 +600,8 @@ def _nominal_arg(nominal, n_ranks):
 def fastx_files_shards_host_gzip(files, n_ranks, nominal=None, fastq_class=0, gzip_mode=1, chunk_bytes=0):
     """fastx_files_shards_host for a job whose plain gzip files are taken as their text (crass_fastx_files_shards_host_gzip; no
     GPU needed): gzip_mode 0 is fastx_files_shards_host, the decline of plain gzip included; else such a file is
-    gzip_inflate_host's text (chunk_bytes: 0 the default chunk), and one that does not inflate is the job's decline."""
+    gzip_inflate_host's text (chunk_bytes: 0 the default chunk), and one that does not inflate is the job's decline; gzip_mode 2:
+    gzip_inflate_members_host's text, a file of any number of members."""
     lib = _abi.load()
     arrs, ptrs, lens = _files_args(files)
     nom = _nominal_arg(nominal, int(n_ranks))
@@ -1944,9 +1990,37 @@ class SearchGroup:
         return _gzip_ranges_call("crass_hip_group_inflate_gzip", lambda o, cap, n, p, v: self.lib.crass_hip_group_inflate_gzip(
             self.h, ptr, len(a), int(chunk_bytes), nom.ctypes.data if nom is not None and len(nom) else None, o, cap, n, p, v), a, out_cap, with_plan)
 
+    def inflate_gzip_members(self, buf, chunk_bytes=0, nominal=None, out_cap=None, with_plan=False):
+        """inflate_gzip for a plain gzip file of any number of members (crass_hip_group_inflate_gzip_members): the members rule by
+        ranges.  Results and errors as gzip_inflate_members_ranges_host with n_ranges = the group's size; with with_plan
+        (text, GzipPlan, GzipMembers)."""
+        a = _bytes_arg(buf)
+        nom = _nominal_arg(nominal, self.n)
+        ptr = a.ctypes.data if len(a) else None
+        return _gzip_members_ranges_call("crass_hip_group_inflate_gzip_members", lambda o, cap, n, p, m, v: self.lib.crass_hip_group_inflate_gzip_members(
+            self.h, ptr, len(a), int(chunk_bytes), nom.ctypes.data if nom is not None and len(nom) else None, o, cap, n, p, m, v), a, out_cap,
+            with_plan)
+
+    def gzip_members_counters(self):
+        """(files taken in members mode, their members, CRC pieces summed over the ranks, exported windows that held no reference)
+        of the last inflate_gzip_members, or summed over the files the last load_fastx_files took in members mode
+        (crass_hip_group_gzip_members_counters)."""
+        out = np.zeros(4, np.uint64)
+        self._chk(self.lib.crass_hip_group_gzip_members_counters(self.h, out.ctypes.data), "crass_hip_group_gzip_members_counters")
+        return tuple(int(x) for x in out)
+
+    def gzip_members_ms(self, rank):
+        """HIP-event milliseconds of a rank's k_gz_member_crc in the last inflate_gzip_members, or for the last gzip file of the
+        last load_fastx_files in members mode (crass_hip_group_gzip_members_ms): a dict of member_crc; measured at stage timing
+        level >= 1.  gzip_ms's narrow does not hold it."""
+        out = np.zeros(1, np.float32)
+        self._chk(self.lib.crass_hip_group_gzip_members_ms(self.h, int(rank), out.ctypes.data), "crass_hip_group_gzip_members_ms")
+        return {"member_crc": float(out[0])}
+
     def set_gzip_on_device(self, mode, chunk_bytes=0):
-        """load_fastx_files takes plain single-member gzip files (crass_hip_group_set_gzip_on_device): 0 / False, the default,
-        declines them as before; anything else takes such a file as a BGZF file is taken, chain elements for members: an index step
+        """load_fastx_files takes plain gzip files (crass_hip_group_set_gzip_on_device): 0 / False, the default,
+        declines them as before; 2 takes plain gzip of any number of members; anything else single-member files only (further
+        members: 13).  Such a file is taken as a BGZF file is taken, chain elements for members: an index step
         (find, count, the chain) before the shards are cut, then every rank inflates the elements of its pieces and keeps their text
         on its device; tails and wrapped-mode margins pull further elements through a seeded window walk.  chunk_bytes: 0 the
         default chunk."""

@@ -853,6 +853,18 @@ void crass_gzip_members_free(crass_gzip_members *m);
  * accepted, its arrays are malloc'd: crass_gzip_members_free. */
 int  crass_gzip_inflate_members_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint8_t *out, uint64_t out_cap,
                                      uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members, crass_bgzf_verdict *v);
+/* crass_gzip_inflate_members_host by the rule the ranks of a group run (crass_hip_group_inflate_gzip_members), serially on the host,
+ * no GPU needed: crass_gzip_inflate_ranges_host in members mode.  Every range decodes its elements with GzEnd records of its own
+ * (the member table is made from each element's first holder) and walks symbolic windows from an identity entry; an entry of the
+ * window in front of an element that lies in front of the member that holds the element's first byte is DEAD — nothing may read it
+ * (14) — and is written as the byte 0, so a range that holds a member boundary exports a window without references; the members'
+ * CRC-32 are joined from pieces cut at member boundaries, every 64 KB and where a range's own text begins; the verdict is given
+ * behind all narrowing: 14 in chain order first, then the first offending member, 7 / 8 before 9.  Text, plan, member table,
+ * verdict and the overflow / argument protocol are crass_gzip_inflate_members_host's, field for field, for every n_ranges in
+ * 1 .. 64 and every cut.  Also CRASS_ERR_INVALID_ARG as crass_gzip_inflate_ranges_host. */
+int  crass_gzip_inflate_members_ranges_host(const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, uint32_t n_ranges, const uint64_t *nominal,
+                                            uint8_t *out, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members,
+                                            crass_bgzf_verdict *v);
 /* crass_hip_inflate_gzip_device in members mode: results as crass_gzip_inflate_members_host, text, plan, members and verdict field
  * for field.  Further scratch: 24 bytes per member and 4 per 64 KB piece of text. */
 int  crass_hip_inflate_gzip_members_device(crass_hip_ctx *ctx, const uint8_t *d_in, uint64_t n_in, uint64_t chunk_bytes, uint8_t *d_out,
@@ -1048,7 +1060,9 @@ int  crass_fastx_files_shards_host_class(const uint8_t *const *bytes, const uint
  * crass_fastx_files_shards_host_class, the decline of a plain gzip file (reason 10) included.  gzip_mode != 0: a file that starts
  * with the gzip magic and that crass_bgzf_index_host declines as not BGZF is replaced by crass_gzip_inflate_host's text
  * (chunk_bytes: 0 is the default chunk) and the job is then cut and judged like any other; a file that does not inflate is the
- * job's decline (decline_file, bgzf = that call's verdict; several members: 13) unless a file in front of it is declined. */
+ * job's decline (decline_file, bgzf = that call's verdict; several members: 13) unless a file in front of it is declined.
+ * gzip_mode == CRASS_GZIP_ON_DEVICE_MEMBERS: such a file is replaced by crass_gzip_inflate_members_host's text, a file of any
+ * number of members; one that does not inflate gives that call's verdict. */
 int  crass_fastx_files_shards_host_gzip(const uint8_t *const *bytes, const uint64_t *n_bytes, uint32_t n_files, uint32_t n_ranks,
                                         const uint64_t *nominal, int fastq_class, int gzip_mode, uint64_t chunk_bytes,
                                         crass_fastx_shards *out);
@@ -1122,8 +1136,27 @@ int  crass_hip_group_load_counters(const crass_hip_group *g, uint64_t out[4]);
  * out_host with a size, cuts that decrease or lie beyond the text; CRASS_ERR_HIP / CRASS_ERR_OOM from a rank. */
 int  crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
                                   uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_bgzf_verdict *v);
-/* crass_hip_group_load_fastx_files takes a plain gzip file of ONE member: mode 0 (the default) such a file is declined as before
- * (reason 10); CRASS_GZIP_ON_DEVICE_ONE_MEMBER, or any other non-zero value: a file that starts with the gzip magic and that
+/* crass_hip_group_inflate_gzip for a plain gzip file of ANY number of members (cat of .gz files, gzip's >>, a member every N
+ * records): the members rule (gunzip_core.h) by ranges.  k_gz_find_members / k_gz_count_members over a rank's chunks (the rank whose
+ * runs see the region's end also stages the file's last 8 bytes); rank 0 walks the chain and places the member-end records
+ * (gz_places); k_gz_decode_members writes a rank's records at slots relative to its first element's, the records of every element
+ * come from its first holder; k_gz_windows_sym_members writes DEAD window entries — those in front of the member that holds the
+ * element's first byte, which nothing may read (14) — as the byte 0, so a rank whose range holds a member boundary exports a
+ * window without references and the rank behind it needs nothing from the ranks in front; rank 0 builds the member table and
+ * the text cuts of the CRC pieces (member boundaries, every 64 KB, where a rank's own text begins); every rank resolves, narrows
+ * with its elements' member starts (k_gz_narrow_members) and runs k_gz_member_crc over its own pieces; rank 0 joins the pieces
+ * per member.  exact: text, plan, member table and verdict are crass_gzip_inflate_members_ranges_host's with n_ranges = the
+ * group's size and the same cuts, which are crass_gzip_inflate_members_host's: 14 in chain order first, then the first offending
+ * member, 7 / 8 before 9.  members (may be NULL) as in crass_gzip_inflate_members_host.  Errors as crass_hip_group_inflate_gzip. */
+int  crass_hip_group_inflate_gzip_members(crass_hip_group *g, const uint8_t *bytes, uint64_t n_bytes, uint64_t chunk_bytes, const uint64_t *nominal,
+                                          uint8_t *out_host, uint64_t out_cap, uint64_t *n_text, crass_gzip_plan *plan, crass_gzip_members *members,
+                                          crass_bgzf_verdict *v);
+/* crass_hip_group_load_fastx_files takes a plain gzip file: mode 0 (the default) such a file is declined as before
+ * (reason 10); CRASS_GZIP_ON_DEVICE_MEMBERS (2): plain gzip of any number of members — everything below in members mode
+ * (crass_hip_group_inflate_gzip_members); members may end anywhere in the text, also inside a record: the cuts are by text; a
+ * member's verdict (7 / 8 / 9 with the member and the file byte of its header) is the file's decline like 9 and 14 below; a
+ * single-member file gives what mode 1 gives.  CRASS_GZIP_ON_DEVICE_ONE_MEMBER, or any other non-zero value, files of ONE member
+ * (further members: 13): a file that starts with the gzip magic and that
  * crass_bgzf_index_host declines as not BGZF goes through an index step before the shards are cut (chunk_bytes: 0 the default
  * chunk, else clamped to 4096 .. 4 MB): every rank runs k_gz_find and k_gz_count on its share of the chunks, rank 0 walks the
  * chain.  The text's size and the element index (start bit, end bit and text offset of every chain element) are then known and
@@ -1142,6 +1175,15 @@ int  crass_hip_group_inflate_gzip(crass_hip_group *g, const uint8_t *bytes, uint
  * per chain element of windows while a file is inflated.  exact: out equals crass_fastx_files_shards_host_gzip's with the same class,
  * mode and chunk.  (No reference counterpart.)  CRASS_ERR_INVALID_ARG: a NULL group, a negative mode. */
 int  crass_hip_group_set_gzip_on_device(crass_hip_group *g, int mode, uint64_t chunk_bytes);
+/* members mode, the last crass_hip_group_inflate_gzip_members that got to its end, or summed over the files the last
+ * crass_hip_group_load_fastx_files took in members mode (else zeros): out[0] files taken in members mode, out[1] their members,
+ * out[2] CRC pieces, summed over the ranks, out[3] exported windows that held no reference (a rank whose range holds a member
+ * boundary exports such a window).  (No reference counterpart.) */
+int  crass_hip_group_gzip_members_counters(const crass_hip_group *g, uint64_t out[4]);
+/* members mode: HIP-event milliseconds on rank `rank`'s stream of k_gz_member_crc over its pieces, out[0], in the last
+ * crass_hip_group_inflate_gzip_members (of a load: its last gzip file's); crass_hip_group_gzip_ms's narrow does not hold it.
+ * Measured when that rank's stage timing level is >= 1, else 0.  (No reference counterpart.) */
+int  crass_hip_group_gzip_members_ms(const crass_hip_group *g, int rank, float out[1]);
 /* the last crass_hip_group_inflate_gzip that got as far as the decode step (else zeros), or summed over the gzip files the last
  * crass_hip_group_load_fastx_files took (a load that took none: zeros): out[0] gzip files taken, out[1] chunks,
  * out[2] chain elements, out[3] how many times an element was inflated by a further rank (the elements the ranks hold, summed,

@@ -8,7 +8,10 @@ of 100 .. 150 bases compressed by zlib at level 6 as gzip writes them (one membe
       (crass_hip_group_inflate_gzip, host memory to host memory) beside it, its counters and the HIP-event times of its kernels
       on the busiest rank.
 Contexts that share one device say nothing about real devices: their kernels, copies and the host are one.
-Output: stdout and --out (default profiles/NOTES_r30_group_gzip.txt)."""
+--members N (N >= 1) writes the same reads as N concatenated members cut at even text positions and takes them in MEMBERS mode:
+(a) is the single context's members load, (c) the group with mode 2 and crass_hip_group_inflate_gzip_members, with the members
+counters (files, members, CRC pieces, exported windows without a reference); with N = 1 the group's mode 1 is timed beside it.
+Output: stdout and --out (default profiles/NOTES_r30_group_gzip.txt; with --members profiles/NOTES_r31_group_gzip_members_N.txt)."""
 import argparse
 import os
 import sys
@@ -58,16 +61,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "NOTES_r30_group_gzip.txt"))
+    ap.add_argument("--members", type=int, default=0, help="N >= 1: the reads as N concatenated members, taken in members mode")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    mem = a.members >= 1
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "NOTES_r31_group_gzip_members_%d.txt" % a.members if mem else "NOTES_r30_group_gzip.txt")
     OUT = open(a.out, "w") if a.out else None
     text = make_fastq(a.reads)
-    co = zlib.compressobj(6, zlib.DEFLATED, 31)
-    zipped = co.compress(text) + co.flush()
-    say("device %s; %d reads: text %.3f GB, gzip (level 6, one member) %.3f GB; medians of %d with min .. max" % (
-        torch.cuda.get_device_name(0), a.reads, len(text) / 1e9, len(zipped) / 1e9, a.reps))
+    n_mem = max(a.members, 1)
+    zipped = b""
+    for k in range(n_mem):
+        co = zlib.compressobj(6, zlib.DEFLATED, 31)
+        zipped += co.compress(text[len(text) * k // n_mem:len(text) * (k + 1) // n_mem]) + co.flush()
+    say("device %s; %d reads: text %.3f GB, gzip (level 6, %d member%s%s) %.3f GB; medians of %d with min .. max" % (
+        torch.cuda.get_device_name(0), a.reads, len(text) / 1e9, n_mem, "" if n_mem == 1 else "s", ", members mode" if mem else "", len(zipped) / 1e9, a.reps))
     with ca.SearchEngine() as e:
-        e.set_gzip_on_device(True)
+        e.set_gzip_on_device(True, members=mem)
         assert e.load_fastx_files([zipped]).n_reads == a.reads
         say("- (a) one context, gzip on device (crass_hip_load_fastx_files): wall %s" % wall(lambda: e.load_fastx_files([zipped]), a.reps))
     with tempfile.TemporaryDirectory() as d:
@@ -79,19 +90,26 @@ def main():
     for n in (1, 2, 4):
         label = "a group of one rank" if n == 1 else "%d contexts sharing one GPU" % n
         with ca.SearchGroup([0] * n, local_copies=n > 1) as g:
-            g.set_gzip_on_device(1)
+            g.set_gzip_on_device(2 if mem else 1)
             for r in range(n):
                 g.rank_set_stage_timing(r, 1)
             assert g.load_fastx_files([zipped]).n_reads == a.reads
             say("- (c) %s, the load (crass_hip_group_load_fastx_files): wall %s" % (label, wall(lambda: g.load_fastx_files([zipped]), a.reps)))
-            assert len(g.inflate_gzip(zipped, out_cap=len(text))) == len(text)
-            w = wall(lambda: g.inflate_gzip(zipped, out_cap=len(text)), a.reps)
+            inflate = g.inflate_gzip_members if mem else g.inflate_gzip
+            assert len(inflate(zipped, out_cap=len(text))) == len(text)
+            w = wall(lambda: inflate(zipped, out_cap=len(text)), a.reps)
             c = g.gzip_counters()
             ms = [g.gzip_ms(r) for r in range(n)]
             busiest = max(ms, key=lambda m: sum(m.values()))
-            say("      the inflate alone (crass_hip_group_inflate_gzip): wall %s; %d chunks, %d chain elements, %d inflated by a further rank, "
+            say("      the inflate alone (crass_hip_group_inflate_gzip%s): wall %s; %d chunks, %d chain elements, %d inflated by a further rank, "
                 "%.1f MB uploaded of which %.1f MB more than once; kernels of the busiest rank: %s" % (
-                    w, c[1], c[2], c[3], c[4] / 1e6, c[5] / 1e6, ", ".join("%s %.2f ms" % (k, v) for k, v in busiest.items() if k != "tail_windows")))
+                    "_members" if mem else "", w, c[1], c[2], c[3], c[4] / 1e6, c[5] / 1e6, ", ".join("%s %.2f ms" % (k, v) for k, v in busiest.items() if k != "tail_windows")
+                    + (", member_crc %.2f ms" % max(g.gzip_members_ms(r)["member_crc"] for r in range(n)) if mem else "")))
+            if mem:
+                say("      members counters: %d file, %d members, %d CRC pieces, %d exported windows without a reference" % g.gzip_members_counters())
+            if mem and n_mem == 1:
+                g.set_gzip_on_device(1)
+                say("      the same group with mode 1, the load: wall %s" % wall(lambda: g.load_fastx_files([zipped]), a.reps))
     say("The contexts of a group here share one device, its copy engines and one host: the rows say what the route costs there, not how")
     say("it scales over real devices, which a one-GPU box cannot measure.")
     if OUT:

@@ -83,3 +83,8 @@ echo "shards by class: $(tail -1 $out/report_shards_class.txt); $(grep -c 'ERROR
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/gunzip.cpp tools/sanitize/gzip_ranges_main.cpp -o $out/gzip_ranges_asan -lz
 $out/gzip_ranges_asan > $out/report_gzip_ranges.txt 2> $out/sanitizer_gzip_ranges.txt || true
 echo "gzip by ranges: $(tail -1 $out/report_gzip_ranges.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_gzip_ranges.txt || true) sanitizer reports"
+# the members rule by ranges (crass_gzip_inflate_members_ranges_host) over the files of tools/sanitize/gzip_members_dump.py for 1, 2, 3 and 7 ranges, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude crass_amd/csrc/gunzip.cpp tools/sanitize/gzip_members_ranges_main.cpp -o $out/gzip_members_ranges_asan
+python3 tools/sanitize/gzip_members_dump.py $out/members > /dev/null
+$out/gzip_members_ranges_asan $out/members/* > $out/report_members_ranges.txt 2> $out/sanitizer_members_ranges.txt || true
+echo "gzip members by ranges: $(tail -1 $out/report_members_ranges.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_members_ranges.txt || true) sanitizer reports"
