@@ -10,9 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrass_hip.so")
-SOURCES = ["kernels.hip", "survivors.hip", "pass2.hip", "sinks.hip", "dmerge.hip", "consensus.hip", "pack.hip", "fastx_scan.hip", "fastx_wrapped.hip", "fastx_hid.hip", "fastx_lines.hip", "inflate.hip", "gunzip.hip", "engine.cpp", "engine_pass1.cpp", "engine_merge.cpp", "engine_pass2.cpp", "engine_ingest.cpp", "engine_fastx.cpp", "engine_inflate.cpp", "engine_names.cpp", "engine_shards.cpp", "merge.cpp", "ingest.cpp", "fastx_parse.cpp", "host_inflate.cpp", "fastx_read.cpp", "fastx_index.cpp", "fastx_stream.cpp", "synth.cpp", "fastx_scan.cpp", "bgzf.cpp", "gunzip.cpp", "fastx_shards_gzip.cpp", "consensus.cpp", "group.cpp", "graph.cpp", "sdma.cpp", "pgzip.cpp"]
+SOURCES = ["kernels.hip", "survivors.hip", "pass2.hip", "sinks.hip", "dmerge.hip", "consensus.hip", "pack.hip", "fastx_scan.hip", "fastx_wrapped.hip", "fastx_hid.hip", "fastx_lines.hip", "inflate.hip", "gunzip.hip", "engine.cpp", "engine_pass1.cpp", "engine_merge.cpp", "engine_pass2.cpp", "engine_ingest.cpp", "engine_fastx.cpp", "engine_inflate.cpp", "engine_names.cpp", "engine_shards.cpp", "merge.cpp", "ingest.cpp", "fastx_parse.cpp", "host_inflate.cpp", "fastx_read.cpp", "fastx_index.cpp", "fastx_stream.cpp", "synth.cpp", "fastx_scan.cpp", "bgzf.cpp", "gunzip.cpp", "fastx_shards_gzip.cpp", "consensus.cpp", "group.cpp", "group_files.cpp", "group_gzip.cpp", "group_names.cpp", "group_fetch.cpp", "graph.cpp", "sdma.cpp", "pgzip.cpp"]
 # a newer header rebuilds every source: no per-source include lists to keep true (survivors.hip includes the three survivor .hip files)
-HEADERS = ["engine_internal.h", "engine_ctx.h", "ingest_internal.h", "host_ingest_internal.h", "dev_common.h", "search_bits.h", "survivor_wave.hip", "long_light.hip", "survivor_lanes.hip", "comp_table.h", "devmem.h", "pack_text.h", "lane_find.h", "pack_launch.h", "fastx_scan.h", "fastx_launch.h", "fastx_vec.h", "fastx_walk.h", "fastx_shards.h", "fastx_names_launch.h", "inflate_core.h", "inflate_launch.h", "gunzip_core.h", "gunzip_launch.h", "gunzip_ranges.h", "consensus_internal.h", "merge.h", os.path.join("..", "..", "include", "crass_hip.h")]
+HEADERS = ["engine_internal.h", "engine_ctx.h", "ingest_internal.h", "host_ingest_internal.h", "dev_common.h", "search_bits.h", "survivor_wave.hip", "long_light.hip", "survivor_lanes.hip", "comp_table.h", "devmem.h", "pack_text.h", "lane_find.h", "pack_launch.h", "fastx_scan.h", "fastx_launch.h", "fastx_vec.h", "fastx_walk.h", "fastx_shards.h", "fastx_names_launch.h", "inflate_core.h", "inflate_launch.h", "gunzip_core.h", "gunzip_launch.h", "gunzip_ranges.h", "group_internal.h", "group_route.h", "consensus_internal.h", "merge.h", os.path.join("..", "..", "include", "crass_hip.h")]
 
 
 def _hipcc():

@@ -1,5 +1,5 @@
 // engine_shards.cpp — one rank's shard of a group's files load (fastx_shards.h; the group's threads and barriers are
-// group.cpp's): the cut probe, then the three steps stage and probe, complete and scan, pack; for a class-1 group's wrapped pass
+// group.cpp's, the load's steps group_files.cpp's): the cut probe, then the three steps stage and probe, complete and scan, pack; for a class-1 group's wrapped pass
 // the chain of a piece in place of its probe (k_fw_cut_*, fastx_wrapped.hip) and what the host's walk over the ranks asks of it.  The scan and what makes its
 // arena the resident set are engine_fastx.cpp's (ArenaScan, arena_finish), the members of a text range and the staging
 // placement fastx_scan.cpp's.

@@ -1,4 +1,4 @@
-// fastx_shards.h — what the group (group.cpp) and the device ingest (engine_shards.cpp) share about loading record-aligned
+// fastx_shards.h — what the group (group_files.cpp) and the device ingest (engine_shards.cpp) share about loading record-aligned
 // shards of a job's files (crass_hip_group_load_fastx_files): one rank's three steps, between which the group's threads meet
 // at barriers and rank 0 combines, and the host arithmetic of a shard (fastx_scan.cpp).  The cut rule is fastx_scan.h's.  Not
 // part of the public ABI.

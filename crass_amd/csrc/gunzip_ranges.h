@@ -1,4 +1,4 @@
-// gunzip_ranges.h — what the group (group.cpp) and the device gunzip (engine_inflate.cpp) share about inflating ONE plain gzip
+// gunzip_ranges.h — what the group (group_gzip.cpp) and the device gunzip (engine_inflate.cpp) share about inflating ONE plain gzip
 // file across the ranks of a group (crass_hip_group_inflate_gzip): the file's state, which the group owns and the ranks fill
 // between barriers, and one rank's four steps.  The rule is gunzip_core.h's (chunks dealt over the ranks, symbolic windows,
 // composition); its serial restatement is crass_gzip_inflate_ranges_host.  Not part of the public ABI.

@@ -66,10 +66,13 @@ def assert_same_records(g, want, what):
         assert np.array_equal(got[2], ref[2]), (what, k, "second")
     if n > 2:                                           # any order, repeats
         pick = np.array([n - 1, 0, n // 2, 0], dtype=np.uint64)
-        got = g.fetch_header_lines(pick)
-        for j, r in enumerate(pick):
-            r = int(r)
-            assert bytes(got[0][int(got[1][j]):int(got[1][j + 1])]) == bytes(want["lines"][0][int(want["lines"][1][r]):int(want["lines"][1][r + 1])]), (what, j)
+        # header lines with their name lengths, quality strings with has_qual: each against the single context's for that record
+        for got, ref, k in ((g.fetch_header_lines(pick), want["lines"], "lines"), (g.fetch_quality(pick), want["quality"], "quality")):
+            assert len(got[1]) == len(pick) + 1 and len(got[2]) == len(pick), (what, k)
+            for j, r in enumerate(pick):
+                r = int(r)
+                assert bytes(got[0][int(got[1][j]):int(got[1][j + 1])]) == bytes(ref[0][int(ref[1][r]):int(ref[1][r + 1])]), (what, k, j)
+                assert got[2][j] == ref[2][r], (what, k, j, "second")
 
 
 def assert_same_shards(ca, sh, files, n, nominal, what):

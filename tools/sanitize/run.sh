@@ -88,3 +88,7 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinc
 python3 tools/sanitize/gzip_members_dump.py $out/members > /dev/null
 $out/gzip_members_ranges_asan $out/members/* > $out/report_members_ranges.txt 2> $out/sanitizer_members_ranges.txt || true
 echo "gzip members by ranges: $(tail -1 $out/report_members_ranges.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_members_ranges.txt || true) sanitizer reports"
+# the router and the gatherer of a group's fetches (group_route.h) against the per-index loop over built-in jobs, a stand-alone program on the CPU
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Icrass_amd/csrc tools/sanitize/group_route_main.cpp -o $out/group_route_asan
+$out/group_route_asan > $out/report_group_route.txt 2> $out/sanitizer_group_route.txt || true
+echo "group route: $(tail -1 $out/report_group_route.txt); $(grep -c 'ERROR: AddressSanitizer\|runtime error\|LeakSanitizer' $out/sanitizer_group_route.txt || true) sanitizer reports"
